@@ -1,14 +1,23 @@
 #!/usr/bin/env python
 """Benchmark of the MI355X-native stereo -> 8-view hot path.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step = one synthetic 1080p side-by-side frame per rank through the device-resident frame pipeline
 (stm_d_adcensus_stm: cost init -> cross aggregation -> WTA -> DCC / IRV x5 / bilateral -> 6 DIBR views ->
 interlacing).  Inputs are resident in HBM before the timed region.  Frames are independent, so ranks share no
 data-path collective (scaling = weak); the only communication is the RCCL broadcast of the input batch from
-rank 0 before timing starts.  With N > 1 the pipelined scatter / gather loop of the C5 batch path
-(sharding.FrameBatchPipeline) is timed beside it and reported as `batch_movement` (never `value`).
+rank 0 before timing starts.
+
+A plain run sets up, warms up, times the K steps (no events inside the timed region) and prints the headline.
+--full adds everything else the benchmark measures and checks: HIP events around the aggregation kernels inside the
+timed region (`roofline`), the per-kernel breakdown (`kernels_ms`), `rate_over_100_frames`, the CPU oracle baseline and
+the parity check on the timed frame, the two-frames-in-flight / real-content / PCIe / configuration legs and, with
+N > 1, the pipelined scatter / gather loop of the C5 batch path (sharding.FrameBatchPipeline) as `batch_movement`
+(never `value`).
+
+--dump-outputs DIR writes what the last timed step computed on rank 0 (disp_l, disp_r, interlaced) as DIR/<name>.npy in
+float32; the inputs depend on the arguments only (seeded synthetic frames), so two builds can be compared output for output.
 
 N > 1: one process per GPU.  Under `python -m torch.distributed.run` (RANK / WORLD_SIZE in the environment) this
 process is one of the ranks; started plainly (`python bench.py --gpus 8`) it launches torch.distributed.run itself as a
@@ -48,13 +57,34 @@ def parse():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--disp", type=int, default=64)
     ap.add_argument("--stages", type=int, default=3, help="1 = cost+agg+WTA (config 2), 2 = +refinement (config 3), 3 = full frame; add 256 for HSLO before WTA")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline and the parity check")
     ap.add_argument("--agg-variant", type=int, default=0, help="0 = matrix-pipe aggregation (default), 10000 = vector-ALU kernels")
-    ap.add_argument("--batch", type=int, default=0, help="--gpus N > 1, the `batch_movement` leg: frames per step (default N, one per rank); rank 0 "
+    ap.add_argument("--batch", type=int, default=0, help="--full, --gpus N > 1, the `batch_movement` leg: frames per step (default N, one per rank); rank 0 "
                     "scatters every step's frames and gathers its outputs inside that leg's timed region, double-buffered (sharding.FrameBatchPipeline)")
-    ap.add_argument("--no-batch-movement", action="store_true", help="--gpus N > 1: skip the `batch_movement` leg (`value` is always the resident-input form)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the two-frames-in-flight and real-content legs and the window statistics behind roofline.issue (profiling passes)")
+    ap.add_argument("--no-batch-movement", action="store_true", help="--full, --gpus N > 1: skip the `batch_movement` leg (`value` is always the resident-input form)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the two-frames-in-flight and real-content legs and the window statistics behind roofline.issue (profiling passes)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, every other measurement and check (roofline, kernels_ms, "
+                    "rate_over_100_frames, cpu_baseline + parity, extra legs, batch_movement); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6  # all files of --dump-outputs together, .npy headers included
+
+
+def dump_outputs(outdir, arrays):
+    """Each array as <outdir>/<name>.npy in float32.  When they would exceed DUMP_LIMIT_BYTES together, each is replaced by a
+    fixed, seeded sample of its flattened elements (sorted indices, the same share of every array)."""
+    os.makedirs(outdir, exist_ok=True)
+    host = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(host)
+    for name, a in host.items():
+        if total > budget:
+            k = int(a.size * (budget / float(total)))
+            idx = np.sort(np.random.RandomState(1234).choice(a.size, k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def spawn_ranks(args):
@@ -223,39 +253,44 @@ def main():
         return float(t.item())
 
     steps(args.warmup)
-    # the timed region carries events around the aggregation kernels only (four event pairs per frame: the roofline figures
-    # come from them); a second, short run with events around every named kernel gives the per-kernel breakdown
-    dt = timed(args.steps, 2)
-    kern = {}
-    if rank == 0:
-        for name in AGG_KERNELS:
-            n, ms = dev.prof_read(name)
-            if n:
-                kern[name] = {"launches": n, "avg_ms": ms / n, "total_ms": ms}
-    nbreak = min(args.steps, 20)
-    timed(nbreak, 1)
-    ALL_NAMES = AGG_KERNELS + ("cross_arms", "hslo_classes", "hslo_lr", "hslo_rl", "hslo_tb", "hslo_bt", "hslo_to_pq", "wta", "irv", "bilateral",
-                               "gaussian_max", "view_synth", "mux", "synth_mux")
+    # plain run: nothing but the frames in the timed region.  --full: the timed region carries events around the aggregation
+    # kernels only (four event pairs per frame: the roofline figures come from them); a second, short run with events around
+    # every named kernel gives the per-kernel breakdown
+    dt = timed(args.steps, 2 if args.full else False)
+    if args.dump_outputs and rank == 0:  # before anything else reuses the buffers
+        dump_outputs(args.dump_outputs, {"disp_l": dl, "disp_r": dr, "interlaced": out})
+    frames_per_step = world  # whole job: one frame per rank and step
+    movement = None
+    if args.full:
+        kern = {}
+        if rank == 0:
+            for name in AGG_KERNELS:
+                n, ms = dev.prof_read(name)
+                if n:
+                    kern[name] = {"launches": n, "avg_ms": ms / n, "total_ms": ms}
+        nbreak = min(args.steps, 20)
+        timed(nbreak, 1)
+        ALL_NAMES = AGG_KERNELS + ("cross_arms", "hslo_classes", "hslo_lr", "hslo_rl", "hslo_tb", "hslo_bt", "hslo_to_pq", "wta", "irv", "bilateral",
+                                   "gaussian_max", "view_synth", "mux", "synth_mux")
 
-    def read_all():
-        res = {}
-        for name in ALL_NAMES:
-            n, ms = dev.prof_read(name)
-            if n:
-                res[name] = ms / n
-        return res
-    other = read_all() if rank == 0 else {}
-    # "wall-clock over >= 100 frames": when the driver asks for fewer steps, a second, un-profiled loop gives it
-    n100 = max(100, args.steps)
-    dt100 = timed(n100, False) if args.steps < 100 else dt
+        def read_all():
+            res = {}
+            for name in ALL_NAMES:
+                n, ms = dev.prof_read(name)
+                if n:
+                    res[name] = ms / n
+            return res
+        other = read_all() if rank == 0 else {}
+        # "wall-clock over >= 100 frames": when the driver asks for fewer steps, a second, un-profiled loop gives it
+        n100 = max(100, args.steps)
+        dt100 = timed(n100, False) if args.steps < 100 else dt
 
-    movement = batch_movement_leg(torch, dist, dev, sharding, synth, args, p, H, W, D, zd, B, rank, world, move_dev, rehearsal,
-                                  (dl, dr, out)) if movement_leg else None
+        movement = batch_movement_leg(torch, dist, dev, sharding, synth, args, p, H, W, D, zd, B, rank, world, move_dev, rehearsal,
+                                      (dl, dr, out)) if movement_leg else None
 
-    if rank == 0:
+    if rank == 0 and args.full:
         V = float(D) * H * W * 4
         HW = float(H) * W
-        frames_per_step = world  # whole job: one frame per rank and step
         my_frames = float(per_rank * args.steps)  # frames behind this rank's kernel records
         L_host, R_host = np.ascontiguousarray(sbs_host[:, :W]), np.ascontiguousarray(sbs_host[:, W:])
         if args.no_extras:  # profiling passes: no launches besides the timed pipeline (the per-kernel averages stay clean)
@@ -313,6 +348,7 @@ def main():
                     "agg_stage_ms_per_frame": stage_ms, "agg_stage_GBps": stage_bytes / (stage_ms * 1e-3) / 1e9,
                     "agg_stage_frac": stage_bytes / (stage_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                     "window_sums": {"horizontal": sum_h, "vertical": sum_v, "mean_window_h": sum_h / (2 * HW), "mean_window_v": sum_v / (2 * HW)}}
+    if rank == 0:
         fps = frames_per_step * args.steps / dt
         res = {
             "metric": "stereo->8-view frames/sec @1080p d=64; cost-agg HBM GB/s vs roofline",
@@ -329,14 +365,17 @@ def main():
                        "sharding": "frames, 1 per rank and step, inputs resident before timing (RCCL broadcast of the batch from rank 0)",
                        "aggregation": "matrix pipe (stm_kernels_aggm.hip)" if args.agg_variant == 0 else "agg_variant %d" % args.agg_variant},
             "rccl_world_size": rccl_world,
-            "rate_over_100_frames": {"frames": n100 * frames_per_step, "frames_per_s": frames_per_step * n100 / dt100, "ms_per_frame": dt100 / (n100 * frames_per_step) * 1e3},
-            "roofline": roofline,
-            "kernels_ms": {k: round(v, 4) for k, v in other.items()},
-            "kernels_ms_source": "a separate %d-step run with HIP events around every named kernel (the timed region keeps events around the aggregation kernels only)" % nbreak,
         }
+        if args.full:
+            res["rate_over_100_frames"] = {"frames": n100 * frames_per_step, "frames_per_s": frames_per_step * n100 / dt100,
+                                           "ms_per_frame": dt100 / (n100 * frames_per_step) * 1e3}
+            res["roofline"] = roofline
+            res["kernels_ms"] = {k: round(v, 4) for k, v in other.items()}
+            res["kernels_ms_source"] = ("a separate %d-step run with HIP events around every named kernel (the timed region keeps events "
+                                        "around the aggregation kernels only)" % nbreak)
         if movement is not None:
             res["batch_movement"] = movement
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             res["rate_two_in_flight"] = two_in_flight(torch, dev, sbs_host, p, H, W, args.stages, max(30, min(args.steps, 100)))
             rc = real_content(torch, dev, synth, p, H, W, D, zd, args.stages, read_all)
             if rc:
@@ -347,7 +386,7 @@ def main():
         if rehearsal:
             res["invalid"] = "STM_BENCH_REHEARSAL=gloo: %d ranks on one GPU over gloo and host tensors -- a dry run of the multi-rank flow, not a measurement" % world
         bad = 0
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             def run_gpu(part, rows):
                 d_part = torch.from_numpy(part).cuda()
                 a = torch.zeros(rows, W, dtype=torch.float32, device="cuda")

@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -8,7 +9,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REF_IMG = "/root/reference/img"  # only present in the build container, never on the GPU box
+
+
+def load_golden(stem):
+    """The arrays of every tests/golden/<stem>_*.npz in one dict: a large fixture is split into parts, each below the size
+    limit for a committed file (tests/golden/make_golden_c1.py writes them)."""
+    g = {}
+    for f in sorted(glob.glob(os.path.join(GOLDEN, stem + "_*.npz"))):
+        g.update(np.load(f))
+    assert g, "no tests/golden/%s_*.npz" % stem
+    return g
 
 
 def pytest_configure(config):

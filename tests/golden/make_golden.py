@@ -1,8 +1,8 @@
 """Generates tests/golden/bud_crop_golden.npz.
 
 Inputs : 64x48 crops of the reference's own test pair img/bud_2.bmp (left) + img/bud_3.bmp (right) and of the
-         degenerate identical pair img/fish_1.bmp / img/fish_2.bmp (read in place from /root/reference/img, which
-         only exists in the build container -- the crops are DATA, committed so the GPU box can use them).
+         degenerate identical pair img/fish_1.bmp / img/fish_2.bmp (the reference's image files, committed as data
+         fixtures in this directory).
 Outputs: what the CPU oracle (oracle/stm_oracle.c) produces for every stage on those crops.
 The reference cannot be built or run here (nvcc / OpenCV / a CUDA GPU are absent), so these vectors pin the
 oracle against regressions and the HIP path against the oracle; they are not outputs of the CUDA binary.
@@ -24,11 +24,12 @@ P = dict(D=8, zd=5, ad=10.0, ce=30.0, ucd=6.0, lcd=20.0, usd=9, lsd=4, ts=20, th
 
 def main():
     rd = stm_amd.bmp_io.read_bmp
-    Lf, Rf = rd("/root/reference/img/bud_2.bmp"), rd("/root/reference/img/bud_3.bmp")
+    gold = os.path.join(ROOT, "tests", "golden")
+    Lf, Rf = rd(os.path.join(gold, "bud_2.bmp")), rd(os.path.join(gold, "bud_3.bmp"))
     y0, x0, H, W = 170, 290, 48, 64
     L, R = np.ascontiguousarray(Lf[y0:y0 + H, x0:x0 + W]), np.ascontiguousarray(Rf[y0:y0 + H, x0:x0 + W])
-    F = np.ascontiguousarray(rd("/root/reference/img/fish_1.bmp")[100:100 + H, 200:200 + W])
-    F2 = np.ascontiguousarray(rd("/root/reference/img/fish_2.bmp")[100:100 + H, 200:200 + W])
+    F = np.ascontiguousarray(rd(os.path.join(gold, "fish_1.bmp"))[100:100 + H, 200:200 + W])
+    F2 = np.ascontiguousarray(rd(os.path.join(gold, "fish_2.bmp"))[100:100 + H, 200:200 + W])
     assert np.array_equal(F, F2)
     D, zd = P["D"], P["zd"]
     out = {"L": L, "R": R, "fish": F, "params": np.array([P[k] for k in ("D", "zd", "ad", "ce", "ucd", "lcd", "usd", "lsd", "ts", "th", "N", "angle")], np.float64)}

@@ -1,16 +1,16 @@
 """BASELINE config 1 at its real size: the reference's own pair img/bud_2.bmp (left) + img/bud_3.bmp (right), 640x384,
 32 disparities (zero_disp 16), 8 views.
 
-  * copies the two BMP files (DATA the reference holds, 0.74 MB each) to tests/golden/ so the GPU box has them;
-  * writes tests/golden/bud_c1_golden.npz: what the CPU oracle produces for (a) the device-resident frame pipeline
+  * reads the two BMP files (the reference's image files, committed as data fixtures in tests/golden/);
+  * writes tests/golden/bud_c1_golden_*.npz: what the CPU oracle produces for (a) the device-resident frame pipeline
     (adcensus_stm, d_io.cu:7-238) and (b) the still-image driver's stage chain (image_io.cpp:171-292: IRV x1 host flavour,
-    bilateral 7/7/7, host-flavour dibr_dbm with the 7/10 mask gaussian).
+    bilateral 7/7/7, host-flavour dibr_dbm with the 7/10 mask gaussian), split into the PARTS below so that every file
+    stays under 1 MiB (tests load them with conftest.load_golden("bud_c1_golden")).
 The reference cannot be built here (nvcc / OpenCV / a CUDA GPU are absent): these are oracle outputs, not CUDA outputs.
 
-Run from the repo root (build container only):  python tests/golden/make_golden_c1.py
+Run from the repo root:  python tests/golden/make_golden_c1.py
 """
 import os
-import shutil
 import sys
 
 import numpy as np
@@ -23,6 +23,10 @@ from oracle import pyoracle as orc  # noqa: E402
 # parameters of SURVEY 8c's understanding check on this pair
 P = dict(D=32, zd=16, ad=10.0, ce=30.0, ucd=6.0, lcd=20.0, usd=17, lsd=8, ts=20, th=0.4, N=8, angle=18.43)
 GOLD = os.path.join(ROOT, "tests", "golden")
+PARTS = {"frame_disp": ("params", "stats", "frame_wta_l", "frame_wta_r", "frame_disp_l", "frame_disp_r"),
+         "frame_mux": ("frame_mux", "chain_cross_l", "chain_wta_l", "chain_outl_l"),
+         "chain_disp": ("chain_disp_l", "chain_disp_r"),
+         "chain_views": ("chain_view_3", "chain_mux")}
 
 
 def image_io_chain(o, L, R, p=P):
@@ -37,9 +41,6 @@ def image_io_chain(o, L, R, p=P):
 
 
 def main():
-    for n in ("bud_2.bmp", "bud_3.bmp"):
-        shutil.copyfile(os.path.join("/root/reference/img", n), os.path.join(GOLD, n))
-        os.chmod(os.path.join(GOLD, n), 0o644)
     rd = stm_amd.bmp_io.read_bmp
     L, R = rd(os.path.join(GOLD, "bud_2.bmp")), rd(os.path.join(GOLD, "bud_3.bmp"))
     H, W, _ = L.shape
@@ -72,7 +73,9 @@ def main():
     # statistics SURVEY 8c's independent check reported for this pair (plateau at offset -6, ~14.5 % L/R outliers)
     vals, cnt = np.unique(fr["wta_l"], return_counts=True)
     out["stats"] = np.array([vals[cnt.argmax()], cnt.max() / float(H * W), (ol > 0).mean()], np.float64)
-    np.savez_compressed(os.path.join(GOLD, "bud_c1_golden.npz"), **out)
+    assert sorted(out) == sorted(k for ks in PARTS.values() for k in ks)
+    for part, keys in PARTS.items():
+        np.savez_compressed(os.path.join(GOLD, "bud_c1_golden_%s.npz" % part), **{k: out[k] for k in keys})
     print("wrote", {k: (v.shape, str(v.dtype)) for k, v in out.items()}, "stats", out["stats"])
 
 

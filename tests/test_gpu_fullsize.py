@@ -221,9 +221,9 @@ def test_two_host_threads_first_frames_together(gpu_ready, orc, stm):
 @pytest.fixture(scope="module")
 def c1():
     import os
-    from conftest import GOLDEN
+    from conftest import GOLDEN, load_golden
     from stm_amd import bmp_io
-    g = dict(np.load(os.path.join(GOLDEN, "bud_c1_golden.npz")))
+    g = load_golden("bud_c1_golden")
     L, R = bmp_io.read_bmp(os.path.join(GOLDEN, "bud_2.bmp")), bmp_io.read_bmp(os.path.join(GOLDEN, "bud_3.bmp"))
     D, zd, ad, ce, ucd, lcd, usd, lsd, ts, th, N, angle = [float(x) for x in g["params"]]
     return g, L, R, dict(D=int(D), zd=int(zd), ad=ad, ce=ce, ucd=ucd, lcd=lcd, usd=int(usd), lsd=int(lsd), ts=int(ts), th=th, N=int(N), angle=angle)

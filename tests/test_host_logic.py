@@ -8,7 +8,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from conftest import REF_IMG, ROOT
+from conftest import GOLDEN, ROOT
 
 
 def test_bmp_roundtrip(stm, tmp_path):
@@ -30,14 +30,13 @@ def test_bmp_c_twin_agrees(stm, tmp_path):
     assert np.array_equal(host_api.bmp_read(p1), img)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_IMG), reason="reference img/ only exists in the build container")
 def test_reference_images_load(stm):
     from stm_amd import host_api
-    a = stm.bmp_io.read_bmp(os.path.join(REF_IMG, "bud_1.bmp"))  # 640x360 with 2 trailing bytes
+    a = stm.bmp_io.read_bmp(os.path.join(GOLDEN, "bud_1.bmp"))  # 640x360 with 2 trailing bytes
     assert a.shape == (360, 640, 3)
-    assert np.array_equal(a, host_api.bmp_read(os.path.join(REF_IMG, "bud_1.bmp")))
-    f1 = stm.bmp_io.read_bmp(os.path.join(REF_IMG, "fish_1.bmp"))
-    f2 = stm.bmp_io.read_bmp(os.path.join(REF_IMG, "fish_2.bmp"))
+    assert np.array_equal(a, host_api.bmp_read(os.path.join(GOLDEN, "bud_1.bmp")))
+    f1 = stm.bmp_io.read_bmp(os.path.join(GOLDEN, "fish_1.bmp"))
+    f2 = stm.bmp_io.read_bmp(os.path.join(GOLDEN, "fish_2.bmp"))
     assert f1.shape == (384, 640, 3) and np.array_equal(f1, f2)
 
 
@@ -201,3 +200,26 @@ def test_bench_spawns_its_own_ranks_without_touching_the_gpu(monkeypatch):
     assert seen["env"].get("HSA_ENABLE_IPC_MODE_LEGACY") == "0"
     if "torch" in sys.modules:
         assert sys.modules["torch"].cuda.is_initialized() == cuda_before  # the parent did not initialise the GPU
+
+
+def test_bench_dump_outputs_float32_and_bounded(monkeypatch, tmp_path):
+    """bench.py --dump-outputs: every array as float32 <name>.npy; whole arrays while they fit, beyond the limit the same
+    seeded sample in every run and all files together within it."""
+    import importlib
+    bench = importlib.import_module("bench")
+    rng = np.random.RandomState(3)
+    arrays = {"disp_l": torch.from_numpy(rng.randn(30, 40).astype(np.float32)),
+              "interlaced": torch.from_numpy(rng.randint(0, 256, size=(30, 40, 3)).astype(np.uint8))}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, v in arrays.items():
+        a = np.load(str(tmp_path / "whole" / (k + ".npy")))
+        assert a.dtype == np.float32 and np.array_equal(a, v.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 * 2 + 8000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    files = [tmp_path / r / (k + ".npy") for r in ("a", "b") for k in arrays]
+    assert sum(os.path.getsize(str(f)) for f in files[:2]) <= bench.DUMP_LIMIT_BYTES
+    for k in arrays:
+        a, b = np.load(str(tmp_path / "a" / (k + ".npy"))), np.load(str(tmp_path / "b" / (k + ".npy")))
+        assert a.dtype == np.float32 and 0 < a.size < arrays[k].numel() and np.array_equal(a, b)
+        assert np.isin(a, arrays[k].numpy().astype(np.float32).ravel()).all()

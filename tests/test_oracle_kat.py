@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import REF_IMG, rand_pair
+from conftest import GOLDEN, load_golden, rand_pair
 
 
 def test_hamdist_kats(orc):
@@ -187,11 +187,10 @@ def test_cost_init_lut_equals_direct(orc):
         assert np.array_equal(cl[d], la[ad] + lc[ham])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_IMG), reason="reference img/ only exists in the build container")
 def test_bud_pair_matches_survey_understanding_check(orc, stm):
     """background plateau at offset -6 (~52 %), mean arm ~9 px, L/R outliers ~14.5 %."""
-    L = stm.bmp_io.read_bmp(os.path.join(REF_IMG, "bud_2.bmp"))
-    R = stm.bmp_io.read_bmp(os.path.join(REF_IMG, "bud_3.bmp"))
+    L = stm.bmp_io.read_bmp(os.path.join(GOLDEN, "bud_2.bmp"))
+    R = stm.bmp_io.read_bmp(os.path.join(GOLDEN, "bud_3.bmp"))
     assert L.shape == (384, 640, 3)
     cl, cr = orc.ci_adcensus(L, R, 10, 30, 32, 16)
     xl, al = orc.ca_cross(L, cl, 6, 20, 17, 8)
@@ -251,7 +250,7 @@ def test_c1_full_size_golden_regression(orc):
     import os
     from conftest import GOLDEN
     from stm_amd import bmp_io
-    g = dict(np.load(os.path.join(GOLDEN, "bud_c1_golden.npz")))
+    g = load_golden("bud_c1_golden")
     L, R = bmp_io.read_bmp(os.path.join(GOLDEN, "bud_2.bmp")), bmp_io.read_bmp(os.path.join(GOLDEN, "bud_3.bmp"))
     assert L.shape == (384, 640, 3) and R.shape == (384, 640, 3)
     D, zd, ad, ce, ucd, lcd, usd, lsd, ts, th, N, angle = [float(x) for x in g["params"]]

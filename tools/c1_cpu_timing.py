@@ -2,7 +2,7 @@
 """BASELINE config 1 (bud_2 + bud_3, 640x384, D=32, 8 views) on the CPU oracle: frames/s of the frame pipeline and per-stage
 milliseconds of the still-image driver's stage chain (image_io.cpp:171-292), with the thread count stated.
 usage: python tools/c1_cpu_timing.py [out.json]"""
-import json, os, sys, time
+import glob, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
@@ -10,7 +10,9 @@ import stm_amd
 from oracle import pyoracle as orc
 
 GOLD = os.path.join(ROOT, "tests", "golden")
-g = dict(np.load(os.path.join(GOLD, "bud_c1_golden.npz")))
+g = {}
+for part in sorted(glob.glob(os.path.join(GOLD, "bud_c1_golden_*.npz"))):  # the golden vectors, split into parts (make_golden_c1.py)
+    g.update(np.load(part))
 L, R = stm_amd.bmp_io.read_bmp(os.path.join(GOLD, "bud_2.bmp")), stm_amd.bmp_io.read_bmp(os.path.join(GOLD, "bud_3.bmp"))
 D, zd, ad, ce, ucd, lcd, usd, lsd, ts, th, N, angle = [float(x) for x in g["params"]]
 D, zd, usd, lsd, ts, N = int(D), int(zd), int(usd), int(lsd), int(ts), int(N)
