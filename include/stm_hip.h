@@ -126,6 +126,15 @@ void stm_d_ca_cross(unsigned char *d_img, float **d_cost,
 /* d_dc_wta.h:16-18 / :12-14  (d_dc_wta.cu:9-59) */
 void stm_dc_wta(float **cost, float *disp, int num_disp, int zero_disp, int num_rows, int num_cols);
 void stm_d_dc_wta(float **d_cost, float *d_disp, int num_disp, int zero_disp, int num_rows, int num_cols);
+/* Sub-pixel disparity enhancement (Mei et al. section 3.4, last step; an addition: the reference has none).  cost = the
+ * AGGREGATED volume (ca_cross's result, what dc_wta minimises), same pointer contract as dc_wta; disp is refined in place.
+ * A pixel is eligible when v = disp[p] is a whole number with 1 <= d = v + zero_disp <= num_disp - 2 and cm = cost[d-1][p],
+ * c0 = cost[d][p], cp = cost[d+1][p] are finite; then, each step one f32 operation in this order:
+ *   den = (cm + cp) - (c0 + c0);  if den > 0:  disp[p] = v + min(max((cm - cp) / (den + den), -0.5), 0.5)
+ * (correctly rounded division).  Every other pixel keeps its value.  Parity is against a numpy statement of these lines on the
+ * oracle's volumes (parity unpinned by nature, as for HSLO: the reference has no such step). */
+void stm_dc_subpixel(float **cost, float *disp, int num_disp, int zero_disp, int num_rows, int num_cols);
+void stm_d_dc_subpixel(float **d_cost, float *d_disp, int num_disp, int zero_disp, int num_rows, int num_cols);
 /* d_dc_hslo.h:18-22  dc_hslo (d_dc_hslo.cu:97-221, a stub in the reference; implemented here, parity unpinned) */
 void stm_dc_hslo(float **cost, float *disp, unsigned char *img_l, unsigned char *img_r,
                  float T, float H1, float H2, int num_disp, int zero_disp,
@@ -214,7 +223,11 @@ void stm_adcensus_stm(unsigned char *img_sbs, float *disp_l, float *disp_r, unsi
  *         2 = + DCC / IRV x5 / bilateral          (config 3);
  *         3 = + DIBR views + interlacing           (config 4, the full adcensus_stm).
  * OR-ing 0x100 inserts the scanline optimisation (HSLO, constants of image_io.cpp:311-313) between aggregation
- * and WTA for both views, as Mei et al. order it; the reference never wires it in (parity unpinned). */
+ * and WTA for both views, as Mei et al. order it; the reference never wires it in (parity unpinned).
+ * OR-ing 0x200 adds the sub-pixel enhancement of stm_dc_subpixel on the aggregated costs of each view: with stages 1 on the
+ * WTA maps; with stages 2 and 3 after region voting and before the bilateral filter (DCC and IRV still see whole numbers;
+ * stage 3 renders from the refined, filtered maps).  Parity: the oracle chain with a numpy statement of the step.  0x200
+ * together with 0x100 is an error (stm_last_error), reported before anything is launched. */
 void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
                         int num_rows, int num_cols_sbs, int num_cols,
                         int num_rows_out, int num_cols_out, int elem_sz,

@@ -39,6 +39,8 @@ PROTOS = {
     "stm_d_ca_cross": ([vp, vp, vp, f32pp, vp, vp, f, f, i, i, i, i, i, i], None),
     "stm_dc_wta": ([f32pp, f32p, i, i, i, i], None),
     "stm_d_dc_wta": ([vp, vp, i, i, i, i], None),
+    "stm_dc_subpixel": ([f32pp, f32p, i, i, i, i], None),
+    "stm_d_dc_subpixel": ([vp, vp, i, i, i, i], None),
     "stm_dc_hslo": ([f32pp, f32p, u8p, u8p, f, f, f, i, i, i, i, i], None),
     "stm_d_dc_hslo": ([vp, vp, vp, vp, f, f, f, i, i, i, i, i], None),
     "stm_dr_dcc": ([u8p, u8p, f32p, f32p, i, i], None),

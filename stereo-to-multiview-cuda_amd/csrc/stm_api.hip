@@ -321,6 +321,24 @@ void stm_dc_wta(float **cost, float *disp, int num_disp, int zero_disp, int num_
     sync();
 }
 
+// sub-pixel enhancement (Mei et al. 3.4; an addition, the reference has none): disp refined in place, cost as for dc_wta
+void stm_d_dc_subpixel(float **d_cost, float *d_disp, int num_disp, int zero_disp, int num_rows, int num_cols)
+{
+    if (!args_ok("d_dc_subpixel", {{"num_disp", num_disp, 1}, {"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}})) return;
+    launch_subpix(vol_table(d_cost), d_disp, num_disp, zero_disp, num_rows, num_cols);
+}
+void stm_dc_subpixel(float **cost, float *disp, int num_disp, int zero_disp, int num_rows, int num_cols)
+{
+    if (!args_ok("dc_subpixel", {{"num_disp", num_disp, 1}, {"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}})) return;
+    size_t HW = (size_t)num_rows * num_cols;
+    Workspace::begin((size_t)num_disp * HW * 4 + HW * 4 + 4096);
+    float *c = up_planes(cost, num_disp, HW);
+    float *d = up(disp, HW);
+    launch_subpix(vol_slab(c, HW), d, num_disp, zero_disp, num_rows, num_cols);
+    down(disp, d, HW);
+    sync();
+}
+
 void stm_d_dc_hslo(float **d_cost, float *d_disp, unsigned char *d_img_l, unsigned char *d_img_r, float T, float H1,
                    float H2, int num_disp, int zero_disp, int num_rows, int num_cols, int elem_sz)
 {
@@ -699,7 +717,8 @@ namespace {
 // pre: optional {BGRX left, BGRX right, wide left, wide right} planes produced together with the split (full-resolution path)
 void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arms &al, Arms &ar, int H, int W, int elem_sz,
                      int D, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
-                     int thresh_s, float thresh_h, bool refine, bool hslo = false, uint32_t *const *pre = nullptr)
+                     int thresh_s, float thresh_h, bool refine, bool hslo = false, uint32_t *const *pre = nullptr,
+                     bool subpix = false)
 {
     const size_t HW = (size_t)H * W;
     const int NQ = (D + 3) / 4;
@@ -736,6 +755,7 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
     // reference's (commented-out) test call uses, image_io.cpp:311-313.  Parity unpinned.
     const u8 *hs_a[2] = {img_l, img_r}, *hs_b[2] = {img_r, img_l}; // the right view's own image plays "left"
     const int hs_sign[2] = {1, -1};
+    float *v2_pq[2] = {nullptr, nullptr}, *v2_quads[2] = {nullptr, nullptr}; // the input of the last horizontal pass, per view
     if (matrix_pipe) {
         // the aggregation kernels on the matrix pipe: cost -> H -> V, V -> H (+ WTA, or + the HSLO passes on the volume), two
         // PQ-layout volumes per view
@@ -747,6 +767,8 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
         float *dv[2] = {wl, wr};
         launch_aggm_frame(pk, cn, rho_table(ad_coeff, census_coeff), va, vb, u, d, l, r, dv, D, zero_disp, H, W, usd, hslo, htab, vtab);
         if (hslo) launch_hslo_wta_pq(2, vb, va, hs_a, hs_b, hs_sign, dv, 15.0f, 1.0f, 3.0f, D, zero_disp, H, W, elem_sz);
+        v2_pq[0] = va[0]; // the last horizontal pass's input (written by the vertical passes, read by the pass + WTA, kept)
+        v2_pq[1] = va[1];
     } else if (hslo) {
         core_agg(cl, sc, al, D, H, W, usd);
         core_agg(cr, sc, ar, D, H, W, usd);
@@ -765,8 +787,18 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
         launch_agg_v(cl, sc, al.up, al.down, D, H, W, usd);
         launch_agg_v(cr, s2, ar.up, ar.down, D, H, W, usd);
         launch_agg_h_wta2(sc, al.left, al.right, wl, s2, ar.left, ar.right, wr, D, zero_disp, H, W);
+        v2_quads[0] = sc.base;
+        v2_quads[1] = s2.base;
     }
-    if (!refine) return;
+    // sub-pixel enhancement (0x200): the parabola through the costs at d - 1, d, d + 1, rebuilt from the last horizontal pass's
+    // input, which nothing below overwrites (DCC / IRV carve their own workspace).  Without refinement it runs on the WTA maps
+    // here; with it, after region voting (DCC and IRV keep working on whole numbers) and before the bilateral filter.
+    float *sp_dv[2] = {wl, wr};
+    const u8 *sp_l[2] = {al.left, ar.left}, *sp_r[2] = {al.right, ar.right};
+    if (!refine) {
+        if (subpix) launch_subpix_frame(v2_pq[0] ? v2_pq : nullptr, v2_quads, sp_dv, sp_l, sp_r, D, zero_disp, H, W);
+        return;
+    }
 
     u8 *outl_l = Workspace::get<u8>(HW), *outl_r = Workspace::get<u8>(HW);
     launch_dcc_rows(outl_l, outl_r, wl, wr, H, W); // d_io.cu:138-143 (outlier maps zeroed, dr_dcc)
@@ -776,8 +808,10 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
         const u8 *u[2] = {al.up, ar.up}, *d[2] = {al.down, ar.down}, *l[2] = {al.left, ar.left}, *r[2] = {al.right, ar.right};
         launch_irv(2, dv, ov, u, d, l, r, thresh_s, thresh_h, H, W, D, zero_disp, usd, 5, true);
     }
-    // the maps are this pipeline's own WTA / region-voting output: integer-valued, any two of them differ by at most D - 1
-    launch_bilateral2(wl, d_disp_l, wr, d_disp_r, gauss2d_table(7, 10.0f), gauss1d_table(D, 5.0f), 7, H, W, D, true, // :150-151  (7, 5, 10)
+    if (subpix) launch_subpix_frame(v2_pq[0] ? v2_pq : nullptr, v2_quads, sp_dv, sp_l, sp_r, D, zero_disp, H, W);
+    // the maps are this pipeline's own WTA / region-voting output: integer-valued, any two of them differ by at most D - 1 --
+    // unless the sub-pixel step has run: then almost no tile is integer-valued and the general form is taken directly
+    launch_bilateral2(wl, d_disp_l, wr, d_disp_r, gauss2d_table(7, 10.0f), gauss1d_table(D, 5.0f), 7, H, W, D, !subpix, // :150-151  (7, 5, 10)
                       bilateral_one_value_table(D, zero_disp, 10.0f, 5.0f), zero_disp);
 }
 
@@ -830,6 +864,10 @@ void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp
                                     {"num_cols_out", num_cols_out, 1}, {"elem_sz", elem_sz, 3},
                                     {"num_views", num_views, 2}, {"num_disp", num_disp, 1}}))
         return;
+    if ((stages & 0x300) == 0x300) { // sub-pixel enhancement reads the last horizontal pass's input, which HSLO does not keep
+        fail("d_adcensus_stm: stages 0x200 (sub-pixel) together with 0x100 (HSLO) is not supported", "stages", __FILE__, __LINE__);
+        return;
+    }
     const int H = num_rows, W = num_cols, N = num_views;
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
     const size_t V = pq_volume_floats(num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
@@ -845,9 +883,10 @@ void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp
     }
     Arms al, ar;
     const bool hslo = (stages & 0x100) != 0; // + scanline optimisation between aggregation and WTA (BASELINE config 3)
+    const bool subpix = (stages & 0x200) != 0; // + sub-pixel enhancement of the whole-pixel maps (Mei et al. 3.4)
     stages &= 0xff;
     frame_disparity(img_l, img_r, d_disp_l, d_disp_r, al, ar, H, W, elem_sz, num_disp, zero_disp, ad_coeff, census_coeff, ucd,
-                    lcd, usd, lsd, thresh_s, thresh_h, stages >= 2, hslo, fused_split ? pre : nullptr);
+                    lcd, usd, lsd, thresh_s, thresh_h, stages >= 2, hslo, fused_split ? pre : nullptr, subpix);
     if (stages < 3) return;
     frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle);
 }

@@ -171,6 +171,11 @@ void launch_bilateral2(const float *in_a, float *out_a, const float *in_b, float
                        int radius, int H, int W, int D, bool integer_maps = false, const float *one_value = nullptr, int zd = 0);
 void launch_gaussian_max(const float *in, float *out, const float *spatial, int radius, float sigma, int H, int W,
                          bool invert_input);
+// sub-pixel enhancement (stm_kernels_subpix.hip): disp refined in place from the materialised volume (per-stage call), or in
+// the frame pipeline from the last horizontal pass's input -- PQ volumes (pq) or quads (quads, when pq == nullptr) -- of both views
+void launch_subpix(Vol cost, float *disp, int D, int zd, int H, int W);
+void launch_subpix_frame(float *const *pq, float *const *quads, float *const *disp, const u8 *const *armL, const u8 *const *armR, int D,
+                         int zd, int H, int W);
 // DIBR + mux (stm_kernels_dibr.hip)
 void launch_demux_sbs(u8 *l, u8 *r, const u8 *sbs, int H, int Wsbs, int W, int elem_sz);
 // same, and the BGRX dwords (launch_pack_bgrx) + wide pixels (launch_cross_arms2) of both halves in the same pass

@@ -18,6 +18,10 @@ def _p(t):
     return C.c_void_p(t.data_ptr())
 
 
+# d_adcensus_stm `stages` bit: sub-pixel enhancement of the whole-pixel maps (not together with 0x100, HSLO)
+STAGE_SUBPIXEL = 0x200
+
+
 class FrameParams:
     """Parameters of one adcensus_stm call (d_io.h:32-40), defaults from SURVEY.md section 8d."""
 
@@ -32,7 +36,8 @@ class FrameParams:
 
 def d_adcensus_stm(sbs, disp_l, disp_r, interlaced, p, stages=3):
     """stm_d_adcensus_stm: sbs uint8 [H][2W][3] on the GPU; outputs are written in place.
-    stages: 1 = cost+aggregation+WTA, 2 = + refinement, 3 = full frame (views + interlacing)."""
+    stages: 1 = cost+aggregation+WTA, 2 = + refinement, 3 = full frame (views + interlacing); OR-ing 0x100 adds the
+    scanline optimisation, OR-ing STAGE_SUBPIXEL the sub-pixel enhancement."""
     assert sbs.is_cuda and sbs.dtype == torch.uint8 and sbs.is_contiguous()
     H, Wsbs, E = sbs.shape
     W = Wsbs // 2
@@ -83,6 +88,13 @@ def d_dc_wta(cost_tab, disp, num_disp, zero_disp):
     H, W = disp.shape
     _use_current_stream()
     lib().stm_d_dc_wta(_p(cost_tab), _p(disp), num_disp, zero_disp, H, W)
+
+
+def d_dc_subpixel(cost_tab, disp, num_disp, zero_disp):
+    """stm_d_dc_subpixel: disp float32 [H][W] on the GPU refined in place on the aggregated volume behind cost_tab."""
+    H, W = disp.shape
+    _use_current_stream()
+    lib().stm_d_dc_subpixel(_p(cost_tab), _p(disp), num_disp, zero_disp, H, W)
 
 
 def prof_enable(on=True):

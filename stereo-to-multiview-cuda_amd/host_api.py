@@ -70,6 +70,17 @@ def dc_wta(cost, zero_disp):
     return disp
 
 
+def dc_subpixel(cost, disp, zero_disp):
+    """Sub-pixel enhancement of `disp` on the aggregated volume `cost` (stm_dc_subpixel; an addition, the reference has no such
+    step).  Returns the refined map; `disp` is not modified."""
+    cost, _ = _f32(cost)
+    D, H, W = cost.shape
+    out = np.array(disp, dtype=np.float32, order="C", copy=True)
+    assert out.shape == (H, W)
+    lib().stm_dc_subpixel(C.cast(_plane_table_f32(cost), f32pp), out.ctypes.data_as(f32p), D, zero_disp, H, W)
+    return out
+
+
 def dc_hslo(cost, img_l, img_r, T, H1, H2, zero_disp):
     """d_dc_hslo.h:18-22 (parity unpinned: the reference is a stub)."""
     cost, _ = _f32(cost)

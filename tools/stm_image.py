@@ -5,7 +5,10 @@ IRV x1, bilateral 7/7/7, host-flavour dibr_dbm), BMP files instead of the OpenCV
 source, cost slice, aggregated slice, disparity, outliers, occlusion mask, every view, interlaced output).
 
 usage: stm_image.py <left.bmp> <right.bmp> <ad coeff> <census coeff> <ndisp> <zerodisp> <ucd> <lcd> <usd> <lsd>
-                    <num views> <angle> <out width> <out height> <thresh_s> <thresh_h> [out dir]"""
+                    <num views> <angle> <out width> <out height> <thresh_s> <thresh_h> [out dir] [--subpixel]
+
+--subpixel (an addition, off by default): the sub-pixel enhancement (host_api.dc_subpixel) of both maps on their aggregated
+volumes after region voting, before the bilateral filter."""
 import os
 import sys
 
@@ -16,6 +19,8 @@ sys.path.insert(0, ROOT)
 
 
 def main(argv):
+    subpixel = "--subpixel" in argv
+    argv = [x for x in argv if x != "--subpixel"]
     if len(argv) not in (17, 18):
         print(__doc__)
         return -1
@@ -43,6 +48,8 @@ def main(argv):
     ol, orr = api.dr_dcc(dl, dr)                                          # :235
     dl, ol = api.dr_irv(dl, ol, xl, ts, th, D, zd, usd, 1)                # :237
     dr, orr = api.dr_irv(dr, orr, xr, ts, th, D, zd, usd, 1)              # :238
+    if subpixel:
+        dl, dr = api.dc_subpixel(al, dl, zd), api.dc_subpixel(ar, dr, zd)
     dl = api.filter_bilateral_1(dl, 7, 7.0, 7.0, D)                       # :242
     dr = api.filter_bilateral_1(dr, 7, 7.0, 7.0, D)                       # :243
     wr("disp_l", video.normalize_minmax_u8(dl)); wr("disp_r", video.normalize_minmax_u8(dr))
