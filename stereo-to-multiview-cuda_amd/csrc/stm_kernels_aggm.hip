@@ -1292,7 +1292,8 @@ bool launch_aggm_stage(Vol in, Vol out, const u8 *armU, const u8 *armD, const u8
     }
     launch_to_pq(in, m, D, H, W, odd);
     // An element that is not an ordinary number cannot go through masked multiply-adds (0 * inf = NaN would reach every pixel
-    // of the tile whose sweep passes it, where the reference only touches the windows that contain it, d_ca_cross_sum.cu:284-289)
+    // of the tile whose sweep passes it, where the reference only touches the windows that contain it, d_ca_cross_sum.cu:284-289);
+    // nor can one so large (|v| >= 2^90) that the sums of the four passes could overflow on the way: stm_k_to_pq flags both
     uint32_t h_odd = 0;
     STM_CHECK(hipMemcpyAsync(&h_odd, odd, 4, hipMemcpyDeviceToHost, stream()));
     STM_CHECK(hipStreamSynchronize(stream()));

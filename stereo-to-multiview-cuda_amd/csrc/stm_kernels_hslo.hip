@@ -94,10 +94,13 @@ __global__ __launch_bounds__(256) void stm_k_hslo_classes(HsloArgs a, float T, i
 // matrix-pipe aggregation adds window elements as acc += mask * b: a masked element must be finite for 0 * b to be 0, and
 // denormal operands are not guaranteed to survive the matrix instruction; the per-stage ca_cross then runs the vector-ALU
 // kernels, which touch an element only inside the windows that contain it (d_ca_cross_sum.cu:284-289).
+// A finite element can still make an infinity INSIDE the chain: two FLT_MAX "invalid cost" markers in one window overflow in the
+// first pass, and the later masked passes would spread 0 * inf = NaN over whole tiles.  So every |v| >= 2^90 counts as odd too:
+// the four passes grow a value by at most (2 * 255)^4 < 2^36, and 2^90 * 2^36 = 2^126 is still finite.
 __device__ __forceinline__ bool pq_odd(float v)
 {
     const uint32_t e = __builtin_bit_cast(uint32_t, v) & 0x7f800000u, m = __builtin_bit_cast(uint32_t, v) & 0x007fffffu;
-    return e == 0x7f800000u || (e == 0u && m != 0u);
+    return e >= ((90u + 127u) << 23) || (e == 0u && m != 0u);
 }
 template <bool QUAD> __global__ __launch_bounds__(256) void stm_k_to_pq(Vol in, f4 *__restrict__ out, int D, int H, int W, int G, uint32_t *__restrict__ odd)
 {

@@ -4,8 +4,8 @@ Inputs : 64x48 crops of the reference's own test pair img/bud_2.bmp (left) + img
          degenerate identical pair img/fish_1.bmp / img/fish_2.bmp (the reference's image files, committed as data
          fixtures in this directory).
 Outputs: what the CPU oracle (oracle/stm_oracle.c) produces for every stage on those crops.
-The reference cannot be built or run here (nvcc / OpenCV / a CUDA GPU are absent), so these vectors pin the
-oracle against regressions and the HIP path against the oracle; they are not outputs of the CUDA binary.
+These vectors pin the oracle against regressions and the HIP path against the oracle; they are not outputs of the
+reference's programs (those are recorded by make_golden_ref.py into ref_gfx950_*.npz).
 
 Run from the repo root:  python tests/golden/make_golden.py
 """

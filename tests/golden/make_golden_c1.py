@@ -6,7 +6,8 @@
     (adcensus_stm, d_io.cu:7-238) and (b) the still-image driver's stage chain (image_io.cpp:171-292: IRV x1 host flavour,
     bilateral 7/7/7, host-flavour dibr_dbm with the 7/10 mask gaussian), split into the PARTS below so that every file
     stays under 1 MiB (tests load them with conftest.load_golden("bud_c1_golden")).
-The reference cannot be built here (nvcc / OpenCV / a CUDA GPU are absent): these are oracle outputs, not CUDA outputs.
+These are oracle outputs, not outputs of the reference's programs (make_golden_ref.py records those, at the sizes
+the reference's launch geometry allows).
 
 Run from the repo root:  python tests/golden/make_golden_c1.py
 """

@@ -91,6 +91,20 @@ def _odd_volume(D, H, W, seed):
     return cost, spots
 
 
+def _overflow_volume(D, H, W, seed):
+    """ordinary costs with FINITE markers that overflow inside the chain: a run of FLT_MAX inside one horizontal window (their sum
+    is +inf after the first pass), a vertical pair and a lone marker.  No element of the INPUT is infinite, NaN or denormal (those
+    are _odd_volume's part): the infinities are made inside the chain"""
+    rs = np.random.RandomState(seed)
+    cost = (rs.random_sample((D, H, W)) * 2).astype(np.float32)
+    big = np.finfo(np.float32).max
+    cost[1 % D, H // 2, W // 2:W // 2 + 3] = big
+    cost[0, H - 9:H - 7, W - 11] = big
+    cost[D - 1, 5, 7] = big
+    assert np.isfinite(cost).all()
+    return cost
+
+
 def _same_with_nans(a, b):
     """element equality where NaNs must sit at the same places (their payload bits are not compared)"""
     na, nb = np.isnan(a), np.isnan(b)
@@ -105,6 +119,13 @@ def test_ca_cross_nonfinite_and_denormal_planes(api, gpu_ready, orc, H, W, D, us
     import torch
     from stm_amd import device_api as dev
     L, _ = rand_pair(H, W, 11 + H)
+    # finite markers that overflow on the way (two FLT_MAX in one window): +inf appears after the first pass and may still only
+    # reach the windows that contain it -- positions of the non-finite values and every finite value as in the oracle
+    over = _overflow_volume(D, H, W, 5 + W)
+    _, oover = orc.ca_cross(L, over, 6.0, 20.0, usd, lsd)
+    assert np.isfinite(oover).mean() > 0.5 and not np.isfinite(oover).all()
+    _, aover = api.ca_cross(L, over, 6.0, 20.0, usd, lsd)
+    assert np.array_equal(np.isfinite(aover), np.isfinite(oover)) and _same_with_nans(aover, oover)
     cost, spots = _odd_volume(D, H, W, 3 + W)
     ocross, oacost = orc.ca_cross(L, cost, 6.0, 20.0, usd, lsd)
     # the oracle itself: a NaN / infinity stays inside the windows that contain it -- most of the volume is finite
@@ -122,6 +143,10 @@ def test_ca_cross_nonfinite_and_denormal_planes(api, gpu_ready, orc, H, W, D, us
     dev.d_ca_cross(dL, tab, scratch, dcross, 6.0, 20.0, usd, lsd, D)
     assert np.array_equal(dcross.cpu().numpy(), ocross)
     assert _same_with_nans(slab.cpu().numpy(), oacost)
+    slab2 = torch.from_numpy(over.copy()).cuda()
+    tab2 = torch.tensor([slab2.data_ptr() + d * H * W * 4 for d in range(D)], dtype=torch.int64).cuda()
+    dev.d_ca_cross(dL, tab2, scratch, dcross, 6.0, 20.0, usd, lsd, D)
+    assert _same_with_nans(slab2.cpu().numpy(), oover)
     # and an ordinary volume right after it is back on the matrix-pipe kernels with the same answer as ever
     plain = (np.random.RandomState(1).random_sample((D, H, W)) * 2).astype(np.float32)
     _, a2 = api.ca_cross(L, plain, 6.0, 20.0, usd, lsd)
