@@ -134,17 +134,18 @@ bool args_ok(const char *fn, std::initializer_list<Dim> dims)
 // cost init: pack -> census -> fused AD + census + robust combine
 // packed_ready: pk_l / pk_r already hold the BGRX dwords of the two images (launch_demux_sbs_packed)
 // census_out != nullptr: stop after the census planes (returned there) -- the caller computes the costs on the fly
+// census_ready: the two census planes, already filled together with the packed planes (launch_front)
 void core_ci(const u8 *d_img_l, const u8 *d_img_r, Vol cl, Vol cr, uint32_t *pk_l, uint32_t *pk_r, float ad_coeff,
              float census_coeff, int D, int zd, int H, int W, int elem_sz, bool packed_ready = false,
-             uint32_t **census_out = nullptr)
+             uint32_t **census_out = nullptr, uint32_t *const *census_ready = nullptr)
 {
     size_t HW = (size_t)H * W;
-    uint32_t *cen_l = Workspace::get<uint32_t>(HW), *cen_r = Workspace::get<uint32_t>(HW);
+    uint32_t *cen_l = census_ready ? census_ready[0] : Workspace::get<uint32_t>(HW), *cen_r = census_ready ? census_ready[1] : Workspace::get<uint32_t>(HW);
     if (!packed_ready) {
         launch_pack_bgrx(d_img_l, pk_l, H, W, elem_sz);
         launch_pack_bgrx(d_img_r, pk_r, H, W, elem_sz);
     }
-    launch_census32_pair(pk_l, cen_l, pk_r, cen_r, H, W);
+    if (!census_ready) launch_census32_pair(pk_l, cen_l, pk_r, cen_r, H, W);
     if (census_out) {
         census_out[0] = cen_l;
         census_out[1] = cen_r;
@@ -714,7 +715,8 @@ void release_host_frame_bufs()
 namespace {
 
 // cost init .. WTA (.. DCC/IRV/bilateral when `refine`) on one rectified pair already split into L / R
-// pre: optional {BGRX left, BGRX right, wide left, wide right} planes produced together with the split (full-resolution path)
+// pre: optional {BGRX left, BGRX right, wide left, wide right, census left, census right} planes produced together with the split
+// (full-resolution path); the census pair may be null (then it is computed here)
 void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arms &al, Arms &ar, int H, int W, int elem_sz,
                      int D, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
                      int thresh_s, float thresh_h, bool refine, bool hslo = false, uint32_t *const *pre = nullptr,
@@ -732,7 +734,7 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
     const bool cost_volume = hslo && !matrix_pipe;
     uint32_t *cen[2] = {nullptr, nullptr};
     core_ci(img_l, img_r, cl, cr, pk_l, pk_r, ad_coeff, census_coeff, D, zero_disp, H, W, elem_sz, pre != nullptr,
-            cost_volume ? nullptr : cen);
+            cost_volume ? nullptr : cen, pre && pre[4] ? pre + 4 : nullptr);
 
     al = carve_arms(HW);
     ar = carve_arms(HW);
@@ -801,12 +803,11 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
     }
 
     u8 *outl_l = Workspace::get<u8>(HW), *outl_r = Workspace::get<u8>(HW);
-    launch_dcc_rows(outl_l, outl_r, wl, wr, H, W); // d_io.cu:138-143 (outlier maps zeroed, dr_dcc)
-    {   // d_io.cu:147-148, both views per launch
+    {   // d_io.cu:138-143 (outlier maps zeroed, dr_dcc) and :147-148, both views per launch
         float *dv[2] = {wl, wr};
         u8 *ov[2] = {outl_l, outl_r};
         const u8 *u[2] = {al.up, ar.up}, *d[2] = {al.down, ar.down}, *l[2] = {al.left, ar.left}, *r[2] = {al.right, ar.right};
-        launch_irv(2, dv, ov, u, d, l, r, thresh_s, thresh_h, H, W, D, zero_disp, usd, 5, true);
+        launch_irv(2, dv, ov, u, d, l, r, thresh_s, thresh_h, H, W, D, zero_disp, usd, 5, true, true);
     }
     if (subpix) launch_subpix_frame(v2_pq[0] ? v2_pq : nullptr, v2_quads, sp_dv, sp_l, sp_r, D, zero_disp, H, W);
     // the maps are this pipeline's own WTA / region-voting output: integer-valued, any two of them differ by at most D - 1 --
@@ -873,9 +874,12 @@ void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp
     const size_t V = pq_volume_floats(num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
     Workspace::begin(((stages & 0x100) ? 13 : 4) * V * 4 + (size_t)(N + 2) * IMG + 168 * HW + (1u << 20));
     u8 *img_l = Workspace::get<u8>(IMG), *img_r = Workspace::get<u8>(IMG);
-    uint32_t *pre[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t *pre[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const bool fused_split = num_cols_sbs >= 2 * W; // both halves complete: emit the derived pixel formats in the same pass
-    if (fused_split) {
+    if (fused_split && (agg_variant() / 100) % 10 != 6) { // ... and the census words; 600: the split and the census as two kernels
+        for (int i = 0; i < 6; ++i) pre[i] = Workspace::get<uint32_t>(HW);
+        launch_front(img_l, img_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], d_img_sbs, H, num_cols_sbs, W, elem_sz);
+    } else if (fused_split) {
         for (int i = 0; i < 4; ++i) pre[i] = Workspace::get<uint32_t>(HW);
         launch_demux_sbs_packed(img_l, img_r, pre[0], pre[1], pre[2], pre[3], d_img_sbs, H, num_cols_sbs, W, elem_sz);
     } else {

@@ -133,6 +133,9 @@ template <bool QUAD, bool STREAM = true> __device__ __forceinline__ void store_q
 // cost init (stm_kernels_cost.hip)
 void launch_pack_bgrx(const u8 *bgr, uint32_t *packed, int H, int W, int elem_sz);
 void launch_census32_pair(const uint32_t *packed_l, uint32_t *census_l, const uint32_t *packed_r, uint32_t *census_r, int H, int W);
+// frame pipeline: launch_demux_sbs_packed + launch_census32_pair in one kernel (Wsbs >= 2 W)
+void launch_front(u8 *l, u8 *r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l, uint32_t *wide_r, uint32_t *cen_l, uint32_t *cen_r,
+                  const u8 *sbs, int H, int Wsbs, int W, int elem_sz);
 void launch_cost_init(const uint32_t *pk_l, const uint32_t *pk_r, const uint32_t *cen_l, const uint32_t *cen_r,
                       Vol cost_l, Vol cost_r, const float *lut_ad, const float *lut_census,
                       int D, int zd, int H, int W);
@@ -159,10 +162,11 @@ void launch_wta(Vol cost, float *disp, int D, int zd, int H, int W);
 // refinement (stm_kernels_refine.hip)
 void launch_dcc(u8 *out_l, u8 *out_r, const float *disp_l, const float *disp_r, u8 *hit_l, u8 *hit_r, int H, int W);
 // nviews = 1 or 2 (both views of a frame share every launch); scratch comes from the current Workspace scope
-// (16 bytes per pixel per view)
+// (16 bytes per pixel per view).  with_dcc (frame pipeline, nviews = 2): the L/R check of disp[0] / disp[1] runs first and fills
+// outl[0] / outl[1] -- fused with the first region-voting pass where that form applies, as launch_dcc_rows otherwise
 void launch_irv(int nviews, float *const *disp, u8 *const *outl, const u8 *const *up, const u8 *const *down,
                 const u8 *const *left, const u8 *const *right, int thresh_s, float thresh_h,
-                int H, int W, int D, int zd, int usd, int iterations, bool device_flavour);
+                int H, int W, int D, int zd, int usd, int iterations, bool device_flavour, bool with_dcc = false);
 void launch_bilateral(const float *in, float *out, const float *spatial, const float *color,
                       int radius, int H, int W, int D);
 // integer_maps: both maps hold integer-valued disparities any two of which differ by less than D (the frame pipeline's own

@@ -122,6 +122,9 @@ struct IrvArgs {
     // vp[v][y][x], y in [0, H]: reliable (non-outlier) pixels, on the state BEFORE the first iteration, in the row segments of the
     // pixels (0 .. y - 1, x) -- a vertical prefix sum, so that the reliable pixels of a whole cross region are one subtraction
     const uint32_t *vp[2];
+    // cnt[v][y][x]: reliable pixels of row y inside the row segment of pixel (y, x), same state (stm_k_dcc_irv_rows writes it,
+    // stm_k_irv_compact_cm<true> sums it over a region's rows inside its tile: no vp plane on that path)
+    const uint16_t *cnt[2];
     // device_diag(): bit 0 = an append past the list's capacity was dropped, bit 1 = the vote found a counter beyond the
     // capacity, bit 2 = a list entry that is neither retired nor a pixel of the frame.  None can happen while the counters are
     // cleared per call; the consumers clamp regardless (a replayed graph once ran with a stale counter, section 4 of DESIGN.md)
@@ -219,6 +222,95 @@ __global__ __launch_bounds__(64 * IRC_W) void stm_k_irv_rowcount(IrvArgs a, uint
             }
         }
     }
+}
+
+// Frame pipeline: stm_k_dcc_rows and stm_k_irv_rowcount of both views in one block per image row.  Both are row-local and the
+// second only re-read what the first had just written: here the two disparity rows are staged in LDS (the L/R check's gathers
+// stay there), the classes never leave the block before they are final, the row prefix of `class == 0` is formed from them, and
+// the outlier map, the 16-bit vote codes of both code planes (what stm_k_irv_compact_cm otherwise packs from the map and the
+// disparities) and cnt leave once.  Eight waves: four per view, each with a quarter of the row as in stm_k_irv_rowcount.
+// LDS: disparities float[2][W], rp u16[2][W + 1] (a row holds at most W < 65536 reliable pixels), hit bytes [2][W].
+constexpr int DIR_T = 2 * 64 * IRC_W, DIR_PRE = 8;
+static size_t dcc_irv_rows_lds(int W) { return 8 * (size_t)W + 4 * (size_t)(W + 1) + 2 * (size_t)W; }
+__global__ __launch_bounds__(DIR_T) void stm_k_dcc_irv_rows(IrvArgs a, uint16_t *__restrict__ cnt0, uint16_t *__restrict__ cnt1, int H, int W,
+                                                            int zd, int nb, int *__restrict__ words, int nwords)
+{
+    extern __shared__ float dir_lds[];
+    __shared__ int s_tot[2][IRC_W];
+    float *dsp_l = dir_lds, *dsp_r = dir_lds + W;
+    uint16_t *rp0 = (uint16_t *)(dir_lds + 2 * W);
+    u8 *hit_l = (u8 *)(rp0 + 2 * (W + 1)), *hit_r = hit_l + W;
+    const int y = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = blockIdx.x * DIR_T + threadIdx.x; i < nwords; i += gridDim.x * DIR_T) words[i] = 0;
+    const size_t row = (size_t)y * W;
+    const int v = wave / IRC_W, wv = wave % IRC_W; // this wave's view and quarter of the row
+    const int Wq = (((W + IRC_W - 1) / IRC_W) + 63) & ~63; // columns per wave, a multiple of 64
+    const int xb = wv * Wq, xe = min(W, xb + Wq);
+    // the horizontal arms of the wave's first DIR_PRE chunks (all of them up to W = 2048) are asked for now and used last
+    const u8 *__restrict__ aL = a.aL[v], *__restrict__ aR = a.aR[v];
+    int al[DIR_PRE], ar[DIR_PRE];
+#pragma unroll
+    for (int k = 0; k < DIR_PRE; ++k) {
+        const int x = min(xb + 64 * k + lane, W - 1);
+        al[k] = aL[row + x];
+        ar[k] = aR[row + x];
+    }
+    for (int x = threadIdx.x; x < W; x += DIR_T) {
+        dsp_l[x] = a.disp[0][row + x];
+        dsp_r[x] = a.disp[1][row + x];
+        hit_l[x] = hit_r[x] = 1; // 1 = never hit (d_dr_dcc.cu:107,111)
+    }
+    __syncthreads();
+    for (int x = threadIdx.x; x < W; x += DIR_T) { // both scatters stay inside the row; every writer stores 0
+        hit_r[min(max(x + (int)dsp_l[x], 0), W - 1)] = 0;
+        hit_l[min(max(x - (int)dsp_r[x], 0), W - 1)] = 0;
+    }
+    __syncthreads();
+    uint16_t *rp = rp0 + v * (W + 1);
+    {
+        const float *own = v ? dsp_r : dsp_l, *oth = v ? dsp_l : dsp_r;
+        const u8 *hit = v ? hit_r : hit_l;
+        u8 *__restrict__ outl = a.outl[v];
+        uint16_t *__restrict__ code_a = a.code[v][0], *__restrict__ code_b = a.code[v][1];
+        const float thresh = 1.0f; // d_dr_dcc.cu:117
+        int carry = 0;
+        if (lane == 0 && wv == 0) rp[0] = 0;
+        for (int x0 = xb; x0 < xe; x0 += 64) { // prefix inside a chunk = population count of the ballot below the lane (v_mbcnt)
+            const int x = x0 + lane, xc = min(x, W - 1);
+            const float d = own[xc];
+            const int c = min(max(v ? xc - (int)d : xc + (int)d, 0), W - 1);
+            const u8 cls = fabsf(d - oth[c]) > thresh ? (hit[xc] ? 2 : 1) : 0; // 1 mismatch, 2 occlusion: never hit (d_dr_dcc.cu:18-82)
+            const bool r = x < xe && cls == 0;
+            const unsigned long long m = __ballot(r);
+            const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            if (x < xe) {
+                outl[row + x] = cls;
+                code_a[row + x] = code_b[row + x] = irv_code(cls, d, zd, nb);
+                rp[x + 1] = (uint16_t)(carry + below + (r ? 1 : 0)); // relative to the wave's first column
+            }
+            carry += __popcll(m);
+        }
+        if (lane == 0) s_tot[v][wv] = carry;
+    }
+    __syncthreads();
+    int off = 0; // reliable pixels left of this wave's part
+    for (int q = 0; q < wv; ++q) off += s_tot[v][q];
+    if (off)
+        for (int x = xb + lane; x < xe; x += 64) rp[x + 1] += (uint16_t)off;
+    __syncthreads();
+    uint16_t *__restrict__ cnt = (v ? cnt1 : cnt0) + row;
+    // the row segment of the vote kernel: [x - armL, x + armR] clamped into the row
+    auto count = [&](int x, int l, int r) {
+        const int cl = min(l, x);
+        const int w = max(min(cl + r + 1, W - (x - cl)), 0);
+        cnt[x] = (uint16_t)(rp[x - cl + w] - rp[x - cl]);
+    };
+#pragma unroll
+    for (int k = 0; k < DIR_PRE; ++k) {
+        const int x = xb + 64 * k + lane;
+        if (x < xe) count(x, al[k], ar[k]);
+    }
+    for (int x = xb + 64 * DIR_PRE + lane; x < xe; x += 64) count(x, aL[row + x], aR[row + x]);
 }
 
 constexpr int ICP_SEG = 16; // row segments per column block
@@ -572,8 +664,17 @@ __global__ __launch_bounds__(64 * IV_WAVES) void stm_k_irv_vote(IrvArgs a, int i
 // Everything else -- flags in the list entries, the two code planes, dirty tiles, the accept rule -- is stm_k_irv_vote's.
 constexpr int IVC_CH = 16; // most list entries per wave and trip (fewer when the list is short: the chip wants many more waves than it holds)
 
+// TILE (frame pipeline, after stm_k_dcc_irv_rows): the vote codes are already written, and S0 comes from the tile's own column
+// sums instead of from the full-height prefix plane vp: the block reads cnt for its 64 columns and the rows
+// [64 ty - usd, 64 ty + 64 + usd) of the image, 16 row segments per column as stm_k_irv_colprefix does, and keeps the running
+// sums in LDS (pf[i][c] = cnt of the rows before tile row i; 32 bits: a count is at most 2 usd + 1 and a column holds 64 + 2 usd
+// of them).  S0 is the same subtraction.  launch_irv takes this form only while the (65 + 2 usd) x 64 dwords fit IC_PF_ROWS.
+constexpr int IC_PF_ROWS = 224; // rows of pf, the total included: usd <= 79
+template <bool TILE>
 __global__ __launch_bounds__(IC_T) void stm_k_irv_compact_cm(IrvArgs a, uint32_t HW, int zd, int nb, int H, int W, int usd, float thresh_h, int thresh_s, int tiles_x)
 {
+    extern __shared__ uint32_t ic_pf[];
+    __shared__ uint32_t s_part[TILE ? IC_T / 64 : 1][64];
     __shared__ int s_tot[IC_T / 64];
     __shared__ int s_base;
     __shared__ uint32_t s_flag[64][16]; // per pixel of the tile one byte: 0 = not listed, 1 = listed, 2 = listed, not in the first iteration
@@ -588,8 +689,36 @@ __global__ __launch_bounds__(IC_T) void stm_k_irv_compact_cm(IrvArgs a, uint32_t
     const uint32_t p = (uint32_t)gy * (uint32_t)W + (uint32_t)gx0;
     const int nvalid = gy < H ? min(max(W - gx0, 0), 4) : 0; // pixels of this thread inside the image
     uint32_t w = 0;
-    // the same pass packs (outlier flag, disparity) into the 16-bit vote code the vote kernel reads
-    if (nvalid == 4 && (W & 3) == 0 && ((((uintptr_t)outl) & 3) | (((uintptr_t)disp) & 15)) == 0) {
+    const int yb = max(ty * 64 - usd, 0), nr = min(ty * 64 + 64 + usd, H) - yb; // TILE: image rows [yb, yb + nr) feed pf
+    if (TILE) {
+        const uint16_t *__restrict__ cnt = a.cnt[v];
+        const int gxc = tx * 64 + lane, rs = (nr + IC_T / 64 - 1) / (IC_T / 64); // wave = row segment, lane = column
+        const int i0 = min(wave * rs, nr), i1 = min(i0 + rs, nr);
+        constexpr int RS = (IC_PF_ROWS - 1 + IC_T / 64 - 1) / (IC_T / 64); // rs <= RS: a segment's counts stay in registers, all loads in flight together
+        uint32_t t[RS];
+#pragma unroll
+        for (int k = 0; k < RS; ++k) t[k] = (gxc < W && i0 + k < i1) ? cnt[(size_t)(yb + i0 + k) * W + gxc] : 0u;
+        if (nvalid == 4 && (W & 3) == 0 && (((uintptr_t)outl) & 3) == 0) w = *(const uint32_t *)(outl + p);
+        else
+            for (int j = 0; j < nvalid; ++j) w |= (uint32_t)outl[p + j] << (8 * j);
+        uint32_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < RS; ++k) sum += t[k];
+        s_part[wave][lane] = sum;
+        if (__syncthreads_or(w != 0)) { // a tile without outliers lists nothing and needs no sums
+            uint32_t run = 0;
+            for (int s2 = 0; s2 < wave; ++s2) run += s_part[s2][lane];
+#pragma unroll
+            for (int k = 0; k < RS; ++k)
+                if (i0 + k < i1) {
+                    ic_pf[(i0 + k) * 64 + lane] = run;
+                    run += t[k];
+                }
+            if (i1 == nr) ic_pf[nr * 64 + lane] = run; // the total (every segment that ends the column holds the same value)
+            __syncthreads();
+        }
+    } else if (nvalid == 4 && (W & 3) == 0 && ((((uintptr_t)outl) & 3) | (((uintptr_t)disp) & 15)) == 0) {
+        // the same pass packs (outlier flag, disparity) into the 16-bit vote code the vote kernel reads
         w = *(const uint32_t *)(outl + p);
         const float4 d = *(const float4 *)(disp + p);
         const uint32_t c0 = irv_code((u8)(w & 0xff), d.x, zd, nb), c1 = irv_code((u8)((w >> 8) & 0xff), d.y, zd, nb);
@@ -606,7 +735,7 @@ __global__ __launch_bounds__(IC_T) void stm_k_irv_compact_cm(IrvArgs a, uint32_t
     }
     const uint32_t *__restrict__ vp = a.vp[v];
     uint32_t later = 0; // bit j: pixel p + j cannot be accepted in the first iteration (S0 <= thresh_s, d_dr_irv.cu:35)
-    if (vp != nullptr && w != 0) { // outliers that can never be accepted are not listed (see stm_k_irv_rowcount)
+    if ((TILE || vp != nullptr) && w != 0) { // outliers that can never be accepted are not listed (see stm_k_irv_rowcount)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (((w >> (8 * j)) & 0xff) && j < nvalid) {
@@ -615,7 +744,9 @@ __global__ __launch_bounds__(IC_T) void stm_k_irv_compact_cm(IrvArgs a, uint32_t
                 if (cu > usd) cu = usd;   // the clamps of the vote kernel (d_dr_irv.cu:179-180)
                 cu = min(cu, gy);
                 cd = min(cd, H - 1 - gy);
-                const int s0 = (int)(vp[(size_t)(gy + cd + 1) * W + gx] - vp[(size_t)(gy - cu) * W + gx]);
+                if (TILE) cd = min(cd, usd); // arms of the frame's own stm_k_cross_arms never exceed usd: this only keeps the read inside pf
+                const int s0 = TILE ? (int)(ic_pf[(gy + cd + 1 - yb) * 64 + c4 + j] - ic_pf[(gy - cu - yb) * 64 + c4 + j])
+                                    : (int)(vp[(size_t)(gy + cd + 1) * W + gx] - vp[(size_t)(gy - cu) * W + gx]);
                 const int nmax = max(nb - 1, (int)disp[q] + zd);
                 if (s0 > 0 && !((float)nmax / (float)s0 > thresh_h)) w &= ~(0xffu << (8 * j));
                 else if (s0 <= thresh_s) later |= 1u << j;
@@ -866,12 +997,12 @@ __global__ __launch_bounds__(64 * IV_WAVES) void stm_k_irv_vote_cm(IrvArgs a, in
 
 void launch_irv(int nviews, float *const *disp, u8 *const *outl, const u8 *const *up, const u8 *const *down,
                 const u8 *const *left, const u8 *const *right, int thresh_s, float thresh_h, int H, int W, int D, int zd,
-                int usd, int iterations, bool device_flavour)
+                int usd, int iterations, bool device_flavour, bool with_dcc)
 {
     const size_t HW = (size_t)H * W;
     const int nb = D > 65 ? D : 65;
-    if (nviews < 1 || nviews > 2) {
-        fail("launch_irv: 1 or 2 views", "nviews", __FILE__, __LINE__);
+    if (nviews < 1 || nviews > 2 || (with_dcc && nviews != 2)) {
+        fail("launch_irv: 1 or 2 views (2 with the L/R check)", "nviews", __FILE__, __LINE__);
         return; // only reached in error mode 1
     }
     // host flavour (d_dr_irv.cu:344-353): one vote, then `iterations` applies of which only the first can change anything
@@ -900,16 +1031,26 @@ void launch_irv(int nviews, float *const *disp, u8 *const *outl, const u8 *const
     if (nviews == 1) { a.list[1] = a.list[0]; a.code[1][0] = a.code[0][0]; a.code[1][1] = a.code[0][1]; }
     // pruning tables (stm_k_irv_rowcount): not with the paper's accept rule (its numerator is a count: no such bound)
     const bool prune = !irv_paper_ratio() && W <= 16000;
+    // round 4: the list column-major inside 64 x 64 tiles, a wave votes for runs of a column incrementally; 300: the raster list of round 3
+    // (also for frames too large for the (row, column) entries of the new list)
+    const bool runs = (agg_variant() / 100) % 10 != 3 && H < (1 << 14) && W < (1 << 16);
+    // the frame's short chain: L/R check + row counts + vote codes in one row kernel, column sums inside the compaction kernel
+    // (no stm_k_irv_colprefix, no vp plane); 600: the separate kernels
+    const bool chain = with_dcc && prune && runs && rounds > 0 && HW < IV_LATER && (agg_variant() / 100) % 10 != 6 &&
+                       65 + 2 * std::min(usd, 255) <= IC_PF_ROWS && dcc_irv_rows_lds(W) <= 64 * 1024;
     uint16_t *cnt[2] = {nullptr, nullptr};
     uint32_t *vp[2] = {nullptr, nullptr};
     if (prune)
         for (int v = 0; v < nviews; ++v) {
             cnt[v] = Workspace::get<uint16_t>(HW);
-            vp[v] = Workspace::get<uint32_t>(HW + W);
+            if (!chain) vp[v] = Workspace::get<uint32_t>(HW + W);
         }
     a.vp[0] = vp[0];
     a.vp[1] = nviews == 2 ? vp[1] : vp[0];
+    a.cnt[0] = cnt[0];
+    a.cnt[1] = nviews == 2 ? cnt[1] : cnt[0];
     a.diag = device_diag();
+    if (with_dcc && !chain) launch_dcc_rows(outl[0], outl[1], disp[0], disp[1], H, W);
     if (rounds == 0) return; // nothing observable happens (a host-flavour vote without an apply only fills scratch)
     if (HW >= IV_LATER) {
         fail("dr_irv: more than 2^30 - 1 pixels", "num_rows * num_cols", __FILE__, __LINE__);
@@ -920,7 +1061,10 @@ void launch_irv(int nviews, float *const *disp, u8 *const *outl, const u8 *const
         STM_LAUNCH(stm_k_irv_clear, dim3((unsigned)cdiv((int)nwords, 256)), dim3(256), 0, stream(), counts, (int)nwords);
         STM_CHECK_LAUNCH();
     }
-    if (prune) {
+    if (chain) {
+        STM_LAUNCH(stm_k_dcc_irv_rows, dim3(H), dim3(DIR_T), dcc_irv_rows_lds(W), stream(), a, cnt[0], cnt[1], H, W, zd, nb, counts, (int)nwords);
+        STM_CHECK_LAUNCH();
+    } else if (prune) {
         STM_LAUNCH(stm_k_irv_rowcount, dim3(H, nviews), dim3(64 * IRC_W), (size_t)(W + 1) * 4, stream(), a, cnt[0], nviews == 2 ? cnt[1] : cnt[0], H, W,
                    counts, (int)nwords);
         STM_CHECK_LAUNCH();
@@ -928,12 +1072,13 @@ void launch_irv(int nviews, float *const *disp, u8 *const *outl, const u8 *const
                    nviews == 2 ? vp[1] : vp[0], H, W);
         STM_CHECK_LAUNCH();
     }
-    // round 4: the list column-major inside 64 x 64 tiles, a wave votes for runs of a column incrementally; 300: the raster list of round 3
-    // (also for frames too large for the (row, column) entries of the new list)
-    const bool runs = (agg_variant() / 100) % 10 != 3 && H < (1 << 14) && W < (1 << 16);
-    if (runs) {
+    if (chain) {
+        const int t64x = cdiv(W, 64), t64y = cdiv(H, 64), us = std::min(usd, 255); // (arms are bytes)
+        STM_LAUNCH(stm_k_irv_compact_cm<true>, dim3((unsigned)(t64x * t64y), nviews), dim3(IC_T), (size_t)(65 + 2 * us) * 64 * 4, stream(), a, (uint32_t)HW,
+                   zd, nb, H, W, us, thresh_h, thresh_s, t64x);
+    } else if (runs) {
         const int t64x = cdiv(W, 64), t64y = cdiv(H, 64);
-        STM_LAUNCH(stm_k_irv_compact_cm, dim3((unsigned)(t64x * t64y), nviews), dim3(IC_T), 0, stream(), a, (uint32_t)HW, zd, nb, H, W, usd, thresh_h,
+        STM_LAUNCH(stm_k_irv_compact_cm<false>, dim3((unsigned)(t64x * t64y), nviews), dim3(IC_T), 0, stream(), a, (uint32_t)HW, zd, nb, H, W, usd, thresh_h,
                    thresh_s, t64x);
     } else {
         STM_LAUNCH(stm_k_irv_compact, dim3((unsigned)((HW + 4 * IC_T - 1) / (4 * IC_T)), nviews), dim3(IC_T), 0, stream(), a, (uint32_t)HW, zd,
