@@ -65,7 +65,7 @@ void        stm_release_workspace(void);
 void        stm_prof_enable(int on);
 void        stm_prof_reset(void);
 /* returns number of timed launches of `kernel` ("pq_h","pq_v12","pq_hw","cross_arms","irv","hslo_lr","hslo_rl","hslo_tb",
- * "hslo_bt", ...) and their
+ * "hslo_bt", "subpixel", "interp", ...) and their
  * summed duration in ms; synchronises the recorded events. */
 int         stm_prof_read(const char *kernel, float *total_ms);
 /* aggregation variant of the frame pipeline (0 = default: matrix-pipe kernels, stm_kernels_aggm.hip); decimal digits, used by
@@ -160,6 +160,20 @@ void stm_dr_irv(float *disp, unsigned char *outliers, unsigned char **cross, int
                 int num_rows, int num_cols, int num_disp, int zero_disp, int usd, int iterations);
 void stm_d_dr_irv(float *d_disp, unsigned char *d_outliers, unsigned char **d_cross, int thresh_s, float thresh_h,
                   int num_rows, int num_cols, int num_disp, int zero_disp, int usd, int iterations);
+/* Outlier interpolation (Mei et al. section 3.4, "proper interpolation", the step after region voting; an addition: the reference
+ * has none).  disp is refined in place, outliers (dr_dcc's classes, after dr_irv) and img (the same view's image) are read only.
+ * A pixel is reliable iff outliers[p] == 0.  For every other pixel p, 16 directions (dx, dy), y growing downwards, in this order:
+ *   (1,0) (2,1) (1,1) (1,2) (0,1) (-1,2) (-1,1) (-2,1) (-1,0) (-2,-1) (-1,-1) (-1,-2) (0,-1) (1,-2) (1,-1) (2,-1)
+ * Along a direction p + k (dx, dy), k = 1, 2, ... is visited until it leaves the image; the first reliable pixel met is the
+ * direction's candidate (the knight's-move directions skip pixels).  outliers[p] == 2 (occlusion): the candidate with the largest
+ * stored value (the farthest surface), folded in the order above -- a candidate v replaces the best so far when there is none yet
+ * or v > best, so with NaN in the map the result is NaN iff the first direction that has a candidate carries NaN.  Any other
+ * non-zero class (mismatch): the candidate whose pixel is closest in colour to p, |dB| + |dG| + |dR| over the first three channels;
+ * a candidate replaces the best so far when there is none yet or its distance is strictly smaller (ties: the earlier direction).
+ * No candidate in any direction: p keeps its value.  Reliable pixels are never written and the outlier map is not modified; the
+ * values written are copies of values in the map.  Parity is against a numpy statement of these lines (parity unpinned). */
+void stm_dr_interp(float *disp, unsigned char *outliers, unsigned char *img, int num_rows, int num_cols, int elem_sz);
+void stm_d_dr_interp(float *d_disp, unsigned char *d_outliers, unsigned char *d_img, int num_rows, int num_cols, int elem_sz);
 /* d_filter_bilateral.h:17-20 / :13-15  (d_filter_bilateral.cu:517-630) */
 void stm_filter_bilateral_1(float *img, int radius, float sigma_color, float sigma_spatial,
                             int num_rows, int num_cols, int num_disp);
@@ -230,7 +244,11 @@ void stm_adcensus_stm(unsigned char *img_sbs, float *disp_l, float *disp_r, unsi
  * OR-ing 0x200 adds the sub-pixel enhancement of stm_dc_subpixel on the aggregated costs of each view: with stages 1 on the
  * WTA maps; with stages 2 and 3 after region voting and before the bilateral filter (DCC and IRV still see whole numbers;
  * stage 3 renders from the refined, filtered maps).  Parity: the oracle chain with a numpy statement of the step.  0x200
- * together with 0x100 is an error (stm_last_error), reported before anything is launched. */
+ * together with 0x100 is an error (stm_last_error), reported before anything is launched.
+ * OR-ing 0x400 adds the outlier interpolation of stm_dr_interp to stages 2 and 3: after region voting, before the sub-pixel step
+ * and the bilateral filter, each view on its own image and its own post-voting outlier map.  It combines with 0x100 and with
+ * 0x200 (order: voting, interpolation, sub-pixel, bilateral).  With stages 1 there are no outlier maps: 1 | 0x400 is an error
+ * (stm_last_error), reported before anything is launched. */
 void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
                         int num_rows, int num_cols_sbs, int num_cols,
                         int num_rows_out, int num_cols_out, int elem_sz,
@@ -274,6 +292,9 @@ void *stm_stream_create(int num_rows, int num_cols_sbs, int num_cols, int num_ro
 /* stages the next frame (the caller's buffer is reusable on return); at most two frames in flight.
  * Returns the frame index, or -1 if both slots are uncollected. */
 long  stm_stream_submit(void *stream, const unsigned char *img_sbs);
+/* the `stages` word of stm_d_adcensus_stm the stream's frames are computed with: 3 (the default), optionally OR-ed with 0x200 and /
+ * or 0x400 (not 0x100).  Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
+int   stm_stream_set_stages(void *stream, int stages);
 /* waits for the oldest uncollected frame and copies its results out (NULL = skip).  Returns its index or -1. */
 long  stm_stream_collect(void *stream, float *disp_l, float *disp_r, unsigned char *interlaced);
 /* zero-copy variants (at 1080p the two host copies of submit / collect take longer than the frame does on the GPU):

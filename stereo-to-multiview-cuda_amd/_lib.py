@@ -47,6 +47,8 @@ PROTOS = {
     "stm_d_dr_dcc": ([vp, vp, vp, vp, i, i], None),
     "stm_dr_irv": ([f32p, u8p, u8pp, i, f, i, i, i, i, i, i], None),
     "stm_d_dr_irv": ([vp, vp, vp, i, f, i, i, i, i, i, i], None),
+    "stm_dr_interp": ([f32p, u8p, u8p, i, i, i], None),
+    "stm_d_dr_interp": ([vp, vp, vp, i, i, i], None),
     "stm_filter_bilateral_1": ([f32p, i, f, f, i, i, i], None),
     "stm_d_filter_bilateral_1": ([vp, i, f, f, i, i, i], None),
     "stm_filter_gaussian_1": ([f32p, i, f, i, i], None),
@@ -74,6 +76,7 @@ PROTOS = {
     "stm_d_tx_scale": ([u8p, u8p, i, i, i, i, i], None),
     "stm_stream_create": ([i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f], C.c_void_p),
     "stm_stream_submit": ([C.c_void_p, u8p], C.c_long),
+    "stm_stream_set_stages": ([C.c_void_p, i], i),
     "stm_stream_collect": ([C.c_void_p, f32p, f32p, u8p], C.c_long),
     "stm_stream_input_buffer": ([C.c_void_p], C.c_void_p),
     "stm_stream_collect_view": ([C.c_void_p, C.POINTER(f32p), C.POINTER(f32p), C.POINTER(u8p)], C.c_long),

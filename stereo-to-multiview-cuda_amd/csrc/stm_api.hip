@@ -428,6 +428,28 @@ void stm_dr_irv(float *disp, unsigned char *outliers, unsigned char **cross, int
     sync();
 }
 
+// outlier interpolation (Mei et al. 3.4; an addition, the reference has none): disp refined in place where outliers != 0
+void stm_d_dr_interp(float *d_disp, unsigned char *d_outliers, unsigned char *d_img, int num_rows, int num_cols, int elem_sz)
+{
+    if (!args_ok("d_dr_interp", {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return;
+    float *dv[1] = {d_disp};
+    const u8 *ov[1] = {d_outliers}, *iv[1] = {d_img};
+    launch_interp(1, dv, ov, iv, num_rows, num_cols, elem_sz);
+}
+void stm_dr_interp(float *disp, unsigned char *outliers, unsigned char *img, int num_rows, int num_cols, int elem_sz)
+{
+    if (!args_ok("dr_interp", {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return;
+    size_t HW = (size_t)num_rows * num_cols;
+    Workspace::begin((5 + (size_t)elem_sz) * HW + 4096);
+    float *d = up(disp, HW);
+    u8 *o = up(outliers, HW), *im = up(img, HW * elem_sz);
+    float *dv[1] = {d};
+    const u8 *ov[1] = {o}, *iv[1] = {im};
+    launch_interp(1, dv, ov, iv, num_rows, num_cols, elem_sz);
+    down(disp, d, HW);
+    sync();
+}
+
 void stm_d_filter_bilateral_1(float *d_img, int radius, float sigma_color, float sigma_spatial, int num_rows, int num_cols,
                               int num_disp)
 {
@@ -720,7 +742,7 @@ namespace {
 void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arms &al, Arms &ar, int H, int W, int elem_sz,
                      int D, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
                      int thresh_s, float thresh_h, bool refine, bool hslo = false, uint32_t *const *pre = nullptr,
-                     bool subpix = false)
+                     bool subpix = false, bool interp = false)
 {
     const size_t HW = (size_t)H * W;
     const int NQ = (D + 3) / 4;
@@ -809,6 +831,13 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
         const u8 *u[2] = {al.up, ar.up}, *d[2] = {al.down, ar.down}, *l[2] = {al.left, ar.left}, *r[2] = {al.right, ar.right};
         launch_irv(2, dv, ov, u, d, l, r, thresh_s, thresh_h, H, W, D, zero_disp, usd, 5, true, true);
     }
+    // outlier interpolation (0x400): what region voting left marked takes a reliable neighbour's value, each view on its own image
+    // and its own post-voting outlier map (the vote kernels clear a pixel's mark when they accept it).  The values written are
+    // copies of values in the map, so the maps stay whole-number and in range for the sub-pixel step and the bilateral filter.
+    if (interp) {
+        const u8 *ov[2] = {outl_l, outl_r}, *iv[2] = {img_l, img_r};
+        launch_interp(2, sp_dv, ov, iv, H, W, elem_sz);
+    }
     if (subpix) launch_subpix_frame(v2_pq[0] ? v2_pq : nullptr, v2_quads, sp_dv, sp_l, sp_r, D, zero_disp, H, W);
     // the maps are this pipeline's own WTA / region-voting output: integer-valued, any two of them differ by at most D - 1 --
     // unless the sub-pixel step has run: then almost no tile is integer-valued and the general form is taken directly
@@ -869,6 +898,10 @@ void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp
         fail("d_adcensus_stm: stages 0x200 (sub-pixel) together with 0x100 (HSLO) is not supported", "stages", __FILE__, __LINE__);
         return;
     }
+    if ((stages & 0x400) && (stages & 0xff) < 2) { // interpolation fills what the L/R check marked: stage 1 has no outlier maps
+        fail("d_adcensus_stm: stages 0x400 (outlier interpolation) needs the refinement stages (2 or 3)", "stages", __FILE__, __LINE__);
+        return;
+    }
     const int H = num_rows, W = num_cols, N = num_views;
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
     const size_t V = pq_volume_floats(num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
@@ -888,9 +921,10 @@ void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp
     Arms al, ar;
     const bool hslo = (stages & 0x100) != 0; // + scanline optimisation between aggregation and WTA (BASELINE config 3)
     const bool subpix = (stages & 0x200) != 0; // + sub-pixel enhancement of the whole-pixel maps (Mei et al. 3.4)
+    const bool interp = (stages & 0x400) != 0; // + interpolation of the outliers region voting leaves (Mei et al. 3.4)
     stages &= 0xff;
     frame_disparity(img_l, img_r, d_disp_l, d_disp_r, al, ar, H, W, elem_sz, num_disp, zero_disp, ad_coeff, census_coeff, ucd,
-                    lcd, usd, lsd, thresh_s, thresh_h, stages >= 2, hslo, fused_split ? pre : nullptr, subpix);
+                    lcd, usd, lsd, thresh_s, thresh_h, stages >= 2, hslo, fused_split ? pre : nullptr, subpix, interp);
     if (stages < 3) return;
     frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle);
 }

@@ -180,6 +180,9 @@ void launch_gaussian_max(const float *in, float *out, const float *spatial, int 
 void launch_subpix(Vol cost, float *disp, int D, int zd, int H, int W);
 void launch_subpix_frame(float *const *pq, float *const *quads, float *const *disp, const u8 *const *armL, const u8 *const *armR, int D,
                          int zd, int H, int W);
+// outlier interpolation (stm_kernels_interp.hip): disp[v] refined in place where outl[v] != 0, from the reliable pixels (outl[v] == 0)
+// along 16 directions and the view's own image; nviews = 1 or 2 in one launch
+void launch_interp(int nviews, float *const *disp, const u8 *const *outl, const u8 *const *img, int H, int W, int elem_sz);
 // DIBR + mux (stm_kernels_dibr.hip)
 void launch_demux_sbs(u8 *l, u8 *r, const u8 *sbs, int H, int Wsbs, int W, int elem_sz);
 // same, and the BGRX dwords (launch_pack_bgrx) + wide pixels (launch_cross_arms2) of both halves in the same pass

@@ -40,6 +40,7 @@ struct FrameStream {
     hipStream_t s_in, s_out;
     bool overlap = true; // two frames in flight on the GPU (a compute stream + workspace per slot)
     bool use_graph = true;
+    int stages = 3; // stm_stream_set_stages: 3, optionally with 0x200 / 0x400
     Slot slot[2];
     long submitted = 0, collected = 0;
 };
@@ -91,6 +92,25 @@ void *stm_stream_create(int num_rows, int num_cols_sbs, int num_cols, int num_ro
     return f;
 }
 
+// The `stages` word every frame of the stream is computed with: 3 (the default), optionally OR-ed with 0x200 (sub-pixel) and / or
+// 0x400 (outlier interpolation).  Not 0x100: the stream's workspace is sized for the frame without HSLO.  Only before the first
+// submit: afterwards the slots replay their launches from a captured graph.  Returns 0, or -1 with the error recorded.
+int stm_stream_set_stages(void *h, int stages)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if ((stages & ~0x600) != 3) {
+        stm::fail("stream_set_stages: stages must be 3, optionally OR-ed with 0x200 and 0x400", "stages", __FILE__, __LINE__);
+        return -1;
+    }
+    if (f->submitted > 0) {
+        stm::fail("stream_set_stages: only before the first submit", "stages", __FILE__, __LINE__);
+        return -1;
+    }
+    f->stages = stages;
+    return 0;
+}
+
 // Stage frame `submitted`; at most two frames may be in flight (collect the older one first).
 // Returns the frame's index, or -1 when both slots are still uncollected.
 long stm_stream_submit(void *h, const unsigned char *img_sbs)
@@ -114,7 +134,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     auto pipeline = [&]() {
         stm::ApiNest nest; // a failed upload above must survive the nested call's argument screen
         stm_d_adcensus_stm(s.d_in, s.d_dl, s.d_dr, s.d_out, f->H, f->Wsbs, f->W, f->Hout, f->Wout, f->E, f->N, f->angle, f->D,
-                           f->zd, f->ad, f->ce, f->ucd, f->lcd, f->usd, f->lsd, f->thresh_s, f->thresh_h, 3);
+                           f->zd, f->ad, f->ce, f->ucd, f->lcd, f->usd, f->lsd, f->thresh_s, f->thresh_h, f->stages);
     };
     void *wb = nullptr;
     size_t wc = 0;

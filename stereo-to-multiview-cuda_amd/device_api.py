@@ -20,6 +20,8 @@ def _p(t):
 
 # d_adcensus_stm `stages` bit: sub-pixel enhancement of the whole-pixel maps (not together with 0x100, HSLO)
 STAGE_SUBPIXEL = 0x200
+# ... outlier interpolation after region voting (stages 2 and 3 only; combines with 0x100 and with STAGE_SUBPIXEL)
+STAGE_INTERP = 0x400
 
 
 class FrameParams:
@@ -37,7 +39,7 @@ class FrameParams:
 def d_adcensus_stm(sbs, disp_l, disp_r, interlaced, p, stages=3):
     """stm_d_adcensus_stm: sbs uint8 [H][2W][3] on the GPU; outputs are written in place.
     stages: 1 = cost+aggregation+WTA, 2 = + refinement, 3 = full frame (views + interlacing); OR-ing 0x100 adds the
-    scanline optimisation, OR-ing STAGE_SUBPIXEL the sub-pixel enhancement."""
+    scanline optimisation, OR-ing STAGE_SUBPIXEL the sub-pixel enhancement, OR-ing STAGE_INTERP the outlier interpolation."""
     assert sbs.is_cuda and sbs.dtype == torch.uint8 and sbs.is_contiguous()
     H, Wsbs, E = sbs.shape
     W = Wsbs // 2
@@ -95,6 +97,17 @@ def d_dc_subpixel(cost_tab, disp, num_disp, zero_disp):
     H, W = disp.shape
     _use_current_stream()
     lib().stm_d_dc_subpixel(_p(cost_tab), _p(disp), num_disp, zero_disp, H, W)
+
+
+def d_dr_interp(disp, outliers, img):
+    """stm_d_dr_interp: disp float32 [H][W] on the GPU refined in place where outliers (uint8 [H][W]) != 0; img uint8 [H][W][E]
+    is the same view's image.  outliers and img are only read."""
+    H, W = disp.shape
+    assert disp.is_cuda and disp.dtype == torch.float32 and disp.is_contiguous()
+    assert outliers.shape == (H, W) and outliers.dtype == torch.uint8 and outliers.is_contiguous()
+    assert img.shape[:2] == (H, W) and img.dtype == torch.uint8 and img.is_contiguous()
+    _use_current_stream()
+    lib().stm_d_dr_interp(_p(disp), _p(outliers), _p(img), H, W, img.shape[2])
 
 
 def prof_enable(on=True):

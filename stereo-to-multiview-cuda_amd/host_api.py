@@ -115,6 +115,19 @@ def dr_irv(disp, outliers, cross, thresh_s, thresh_h, num_disp, zero_disp, usd, 
     return disp, outliers
 
 
+def dr_interp(disp, outliers, img):
+    """Outlier interpolation (stm_dr_interp; an addition, the reference has no such step): every pixel with outliers != 0 takes
+    the value of a reliable pixel found along 16 directions -- class 2 the largest, any other class the closest in colour in
+    `img`, the same view's image.  Returns the refined map; nothing passed in is modified."""
+    out = np.array(disp, dtype=np.float32, order="C", copy=True)
+    outliers, po = _u8(outliers)
+    img, pi = _u8(img)
+    H, W = out.shape
+    assert outliers.shape == (H, W) and img.shape[:2] == (H, W) and img.ndim == 3
+    lib().stm_dr_interp(out.ctypes.data_as(f32p), po, pi, H, W, img.shape[2])
+    return out
+
+
 def filter_bilateral_1(img, radius, sigma_color, sigma_spatial, num_disp):
     """d_filter_bilateral.h:17-20."""
     img = np.array(img, dtype=np.float32, order="C", copy=True)

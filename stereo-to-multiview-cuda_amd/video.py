@@ -15,13 +15,21 @@ from ._lib import f32p, lib, u8p
 class FrameStream:
     """Pipelined adcensus_stm over a sequence: submit() frames, collect() results in order (two in flight)."""
 
-    def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None):
+    def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3):
         self.H, self.W = num_rows, num_cols
         self.Ho, self.Wo = out_rows or num_rows, out_cols or num_cols
         p = params
         self._h = lib().stm_stream_create(num_rows, 2 * num_cols, num_cols, self.Ho, self.Wo, 3, p.num_views, p.angle,
                                           p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff, p.ucd, p.lcd, p.usd, p.lsd,
                                           p.thresh_s, p.thresh_h)
+        if stages != 3:
+            self.set_stages(stages)
+
+    def set_stages(self, stages):
+        """stm_stream_set_stages: 3, optionally OR-ed with 0x200 (sub-pixel) and 0x400 (outlier interpolation); only before the
+        first submit.  Raises ValueError where the library refuses (it returns -1; in error mode 0 it exits like any error)."""
+        if int(lib().stm_stream_set_stages(self._h, int(stages))) != 0:
+            raise ValueError("stm_stream_set_stages(%#x) refused: %s" % (stages, lib().stm_last_error().decode()))
 
     def submit(self, sbs):
         sbs = np.ascontiguousarray(sbs, dtype=np.uint8)
@@ -68,13 +76,14 @@ class FrameStream:
             pass
 
 
-def process_sequence(frames, params, out_rows=None, out_cols=None):
-    """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`."""
+def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3):
+    """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
+    stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation)."""
     fs = None
     pending = 0
     for sbs in frames:
         if fs is None:
-            fs = FrameStream(sbs.shape[0], sbs.shape[1] // 2, params, out_rows, out_cols)
+            fs = FrameStream(sbs.shape[0], sbs.shape[1] // 2, params, out_rows, out_cols, stages)
         if pending == 2:
             yield fs.collect()
             pending -= 1

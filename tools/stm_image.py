@@ -5,8 +5,10 @@ IRV x1, bilateral 7/7/7, host-flavour dibr_dbm), BMP files instead of the OpenCV
 source, cost slice, aggregated slice, disparity, outliers, occlusion mask, every view, interlaced output).
 
 usage: stm_image.py <left.bmp> <right.bmp> <ad coeff> <census coeff> <ndisp> <zerodisp> <ucd> <lcd> <usd> <lsd>
-                    <num views> <angle> <out width> <out height> <thresh_s> <thresh_h> [out dir] [--subpixel]
+                    <num views> <angle> <out width> <out height> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel]
 
+--interp (an addition, off by default): the outlier interpolation (host_api.dr_interp) of both maps after region voting, each on
+its own image and outlier map, before --subpixel.
 --subpixel (an addition, off by default): the sub-pixel enhancement (host_api.dc_subpixel) of both maps on their aggregated
 volumes after region voting, before the bilateral filter."""
 import os
@@ -19,8 +21,8 @@ sys.path.insert(0, ROOT)
 
 
 def main(argv):
-    subpixel = "--subpixel" in argv
-    argv = [x for x in argv if x != "--subpixel"]
+    subpixel, interp = "--subpixel" in argv, "--interp" in argv
+    argv = [x for x in argv if x not in ("--subpixel", "--interp")]
     if len(argv) not in (17, 18):
         print(__doc__)
         return -1
@@ -48,6 +50,8 @@ def main(argv):
     ol, orr = api.dr_dcc(dl, dr)                                          # :235
     dl, ol = api.dr_irv(dl, ol, xl, ts, th, D, zd, usd, 1)                # :237
     dr, orr = api.dr_irv(dr, orr, xr, ts, th, D, zd, usd, 1)              # :238
+    if interp:
+        dl, dr = api.dr_interp(dl, ol, L), api.dr_interp(dr, orr, R)
     if subpixel:
         dl, dr = api.dc_subpixel(al, dl, zd), api.dc_subpixel(ar, dr, zd)
     dl = api.filter_bilateral_1(dl, 7, 7.0, 7.0, D)                       # :242

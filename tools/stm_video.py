@@ -3,8 +3,10 @@
 side-by-side BMP frames instead of a video file, BMP outputs instead of a window.
 
 usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <num disp> <zero disp> <ad coeff>
-                    <census coeff> <ucd> <lcd> <usd> <lsd> <thresh_s> <thresh_h> [out dir]
+                    <census coeff> <ucd> <lcd> <usd> <lsd> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
+--interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
+(sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -16,6 +18,8 @@ sys.path.insert(0, ROOT)
 
 
 def main(argv):
+    stages = 3 | (0x400 if "--interp" in argv else 0) | (0x200 if "--subpixel" in argv else 0)
+    argv = [x for x in argv if x not in ("--interp", "--subpixel")]
     if len(argv) not in (16, 17):
         print(__doc__)
         return -1
@@ -30,7 +34,7 @@ def main(argv):
     out_dir = a[15] if len(a) > 15 else os.path.join(a[0], "out")
     t0 = time.perf_counter()
     n = 0
-    for (k, dl, dr, inter) in video.process_sequence(video.read_bmp_sequence(a[0]), p, out_h, out_w):
+    for (k, dl, dr, inter) in video.process_sequence(video.read_bmp_sequence(a[0]), p, out_h, out_w, stages):
         video.write_outputs(out_dir, k, dl, dr, inter)
         n += 1
     dt = time.perf_counter() - t0
