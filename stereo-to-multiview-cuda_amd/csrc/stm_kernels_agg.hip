@@ -64,22 +64,10 @@ struct ArmsArgs {
     int vrec, vtop;
 };
 
-// MODE 0: the arms.  MODE 1: + the horizontal window table (a wave = 64 pixels of a row = four of its tiles, arms in registers).
-// MODE 2 (round 4; the review's item 1c): + the VERTICAL window table as well.  A block is 16 rows x 64 columns, wave w = row w of
-// the tile row; the arms leave through LDS, and after one barrier wave w builds the record of the block's w-th group of four columns
-// (vwin_build: lane = (column of the group, row of the tile)) -- stm_k_vwin_table's launch and its read of the arm planes are gone.
-template <int MODE>
-__global__ __launch_bounds__(MODE == 2 ? 1024 : 256) void stm_k_cross_arms(ArmsArgs a, uint32_t tg_far, uint32_t tg_near, int usd, int lsd, int H, int W)
+// The walk with vector min / select bookkeeping (round 3, above): behind stm_set_agg_variant(700), for comparison with the one below.
+static __device__ __forceinline__ void cross_arms_walk_vmin(const uint32_t *__restrict__ img, int x, int y, int p, uint32_t tg_far, uint32_t tg_near, int usd,
+                                                            int lsd, int H, int W, int (&arm)[4])
 {
-    constexpr bool HTAB = MODE >= 1;
-    const int v = blockIdx.z;
-    const int wv_ = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int xr = MODE == 2 ? blockIdx.x * 64 + (threadIdx.x & 63) : blockIdx.x * 256 + threadIdx.x;
-    const int yr = MODE == 2 ? blockIdx.y * 16 + wv_ : blockIdx.y;
-    if (MODE == 1 ? (xr & ~63) >= W : MODE == 0 ? xr >= W : false) return; // MODE 1: whole waves only (no block-wide barrier below); MODE 2: everybody stays for the barrier
-    const int x = min(xr, W - 1), y = min(yr, H - 1); // a lane past the row / a wave past the image repeats the last pixel / row and stores nothing
-    const int p = y * W + x;
-    const uint32_t *__restrict__ img = a.img[v];
     const uint32_t anchor = img[p];
     // the four arms of a pixel walk together: four independent loads per step, one exit test for all of them.
     // Addresses: a block is one image row, so the row an up / down step reads is wave-uniform -- a scalar base + the lane's
@@ -99,7 +87,7 @@ __global__ __launch_bounds__(MODE == 2 ? 1024 : 256) void stm_k_cross_arms(ArmsA
         c[2] = *(const uint32_t *)(rowbase + (size_t)(uint32_t)max((int)x4 - 4 * (K), 0));                        \
         c[3] = *(const uint32_t *)(rowbase + (size_t)(uint32_t)min((int)x4 + 4 * (K), xmax4));                    \
     }
-    int arm[4] = {kmax[0], kmax[1], kmax[2], kmax[3]};
+    for (int d = 0; d < 4; ++d) arm[d] = kmax[d];
     const uint32_t anchor_n = anchor + tg_near;
     uint32_t prev[4] = {anchor, anchor, anchor, anchor}, prev_t[4] = {anchor_n, anchor_n, anchor_n, anchor_n};
     int k = 1;
@@ -142,6 +130,129 @@ __global__ __launch_bounds__(MODE == 2 ? 1024 : 256) void stm_k_cross_arms(ArmsA
         }
     }
 #undef STM_ARM_LOADS
+}
+
+// The walk with the bookkeeping in scalar registers (the default).  What a step holds besides its four loads and colour tests:
+//   addresses: two buffer descriptors, the plane and the anchor's row.  An up / down step reads (plane, lane's 4 x, scalar byte offset
+//     of the row): the offset runs, one add or sub of 4 W per step, held at the arm's last row by a scalar min / max -- no product.
+//     A left / right step reads (row, 4 x -+ 4 k): one vector instruction, no clamp; past either end of the row the offset is >= 4 W
+//     (it wraps below 0) and the descriptor's range check returns 0.  No access leaves the plane.
+//   verdicts: v_cmp leaves the lanes that passed as a 64-bit mask; `open` (one mask per direction) &= it, and the arm counts
+//     1 + the steps it stayed open (an add with `open` as the carry): the first failing k, or usd + 1.  min(kmax) once, at the end,
+//     makes that the arm; what a step past a border tested cannot matter.
+//   exit: the OR of the four masks is empty.  Every second step the lanes whose border lies behind k are closed (up / down: a scalar
+//     test, left / right: one compare, in the waves near an end of the row only), so that a wave leaves as early as with per-lane arms.
+//   previous pixel: steps come in pairs that swap two register sets; nothing is copied.
+static __device__ __forceinline__ void cross_arms_walk(const uint32_t *__restrict__ img, int x, int y, uint32_t tg_far, uint32_t tg_near, int usd, int lsd, int H,
+                                                       int W, int (&arm)[4])
+{
+    const int W4 = 4 * W, x4 = 4 * x;
+    const int row0 = y * W4; // (the launcher keeps 4 H W below 2^31)
+    const __amdgpu_buffer_rsrc_t plane = __builtin_amdgcn_make_buffer_rsrc((void *)img, 0, (uint32_t)H * (uint32_t)W4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t row = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)img + row0), 0, (uint32_t)W4, 0x00020000);
+    const uint32_t anchor = __builtin_amdgcn_raw_buffer_load_b32(row, x4, 0, 0);
+    const int kmaxU = min(usd, y), kmaxD = min(usd, H - 1 - y); // wave-uniform
+    const int kmaxL = min(usd, x), kmaxR = min(usd, W - 1 - x);
+    const int offUmin = row0 - kmaxU * W4, offDmax = row0 + kmaxD * W4;
+    int offU = row0, offD = row0;
+    const bool edge_wave = __builtin_amdgcn_ballot_w64(kmaxL < usd || kmaxR < usd) != 0ull; // a wave with all its lanes usd and more from both ends of the row has nothing to close there
+    unsigned long long open[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+    for (int d = 0; d < 4; ++d) arm[d] = 1;
+#define STM_ARM_LOADS(C, K)                                                   \
+    offU = max(offU - W4, offUmin);                                           \
+    offD = min(offD + W4, offDmax);                                           \
+    C[0] = __builtin_amdgcn_raw_buffer_load_b32(plane, x4, offU, 0);          \
+    C[1] = __builtin_amdgcn_raw_buffer_load_b32(plane, x4, offD, 0);          \
+    {                                                                         \
+        int k4 = 4 * (K);                                                     \
+        asm("" : "+s"(k4)); /* the offsets stay (register - scalar) and (register + scalar), one dword per load: no running copies, and no pairing of neighbouring steps into one load, whose range check at a row's end is not this one */ \
+        C[2] = __builtin_amdgcn_raw_buffer_load_b32(row, x4 - k4, 0, 0);      \
+        C[3] = __builtin_amdgcn_raw_buffer_load_b32(row, x4 + k4, 0, 0);      \
+    }
+    // arm += lane's bit of open: one add with the mask as its carry-in (the compiler's own choice is a select and an add)
+#define STM_ARM_VERDICT(D, PASS)                                              \
+    open[D] &= __builtin_amdgcn_ballot_w64(PASS);                             \
+    {                                                                         \
+        unsigned long long co_;                                               \
+        asm("v_addc_co_u32_e64 %0, %1, 0, %0, %2" : "+v"(arm[D]), "=&s"(co_) : "s"(open[D])); \
+    }
+#define STM_ARM_CLOSE(K)                                                      \
+    open[0] = (K) <= kmaxU ? open[0] : 0ull;                                  \
+    open[1] = (K) <= kmaxD ? open[1] : 0ull;                                  \
+    if (edge_wave) {                                                          \
+        open[2] &= __builtin_amdgcn_ballot_w64((K) <= kmaxL);                 \
+        open[3] &= __builtin_amdgcn_ballot_w64((K) <= kmaxR);                 \
+    }                                                                         \
+    if (((open[0] | open[1]) | (open[2] | open[3])) == 0ull) break;
+    // near tier: C / CT = this step's pixels and pixels + tg_near, P / PT = the previous step's
+#define STM_ARM_NEAR(K, C, CT, P, PT)                                                                                   \
+    {                                                                                                                   \
+        STM_ARM_LOADS(C, K)                                                                                             \
+        _Pragma("unroll") for (int d = 0; d < 4; ++d)                                                                   \
+        {                                                                                                               \
+            CT[d] = C[d] + tg_near;                                                                                     \
+            const uint32_t ok = (CT[d] - anchor) & (anchor_n - C[d]) & (CT[d] - P[d]) & (PT[d] - C[d]) & W10_GUARD;     \
+            STM_ARM_VERDICT(d, ok == W10_GUARD)                                                                         \
+        }                                                                                                               \
+    }
+#define STM_ARM_FAR(K)                                                                     \
+    {                                                                                      \
+        uint32_t c[4];                                                                     \
+        STM_ARM_LOADS(c, K)                                                                \
+        _Pragma("unroll") for (int d = 0; d < 4; ++d)                                      \
+        {                                                                                  \
+            const uint32_t ok = (c[d] + far_lo) & (far_hi - c[d]) & W10_GUARD;             \
+            STM_ARM_VERDICT(d, ok == W10_GUARD)                                            \
+        }                                                                                  \
+    }
+    const uint32_t anchor_n = anchor + tg_near;
+    uint32_t ca[4], ta[4], cb[4] = {anchor, anchor, anchor, anchor}, tb[4] = {anchor_n, anchor_n, anchor_n, anchor_n};
+    const int knear = max(0, min(usd, lsd)); // lsd < 0: no near tier, as with lsd = 0; usd <= 0: no step at all (every kmax is <= 0)
+#define STM_ARM_ANY_OPEN (((open[0] | open[1]) | (open[2] | open[3])) != 0ull)
+    for (int k = 1; k < knear; k += 2) {
+        STM_ARM_CLOSE(k)
+        STM_ARM_NEAR(k, ca, ta, cb, tb)
+        STM_ARM_NEAR(k + 1, cb, tb, ca, ta)
+    }
+    // the odd last step of a tier: not after an early exit, when every arm is final (the far loop then leaves at its first test)
+    if ((knear & 1) && STM_ARM_ANY_OPEN) STM_ARM_NEAR(knear, ca, ta, cb, tb)
+    const uint32_t far_lo = tg_far - anchor, far_hi = anchor + tg_far;
+    for (int k = knear + 1; k < usd; k += 2) {
+        STM_ARM_CLOSE(k)
+        STM_ARM_FAR(k)
+        STM_ARM_FAR(k + 1)
+    }
+    if (usd > knear && ((usd - knear) & 1) && STM_ARM_ANY_OPEN) STM_ARM_FAR(usd)
+#undef STM_ARM_ANY_OPEN
+#undef STM_ARM_FAR
+#undef STM_ARM_NEAR
+#undef STM_ARM_CLOSE
+#undef STM_ARM_VERDICT
+#undef STM_ARM_LOADS
+    arm[0] = min(arm[0], kmaxU);
+    arm[1] = min(arm[1], kmaxD);
+    arm[2] = min(arm[2], kmaxL);
+    arm[3] = min(arm[3], kmaxR);
+}
+// MODE 0: the arms.  MODE 1: + the horizontal window table (a wave = 64 pixels of a row = four of its tiles, arms in registers).
+// MODE 2 (round 4; the review's item 1c): + the VERTICAL window table as well.  A block is 16 rows x 64 columns, wave w = row w of
+// the tile row; the arms leave through LDS, and after one barrier wave w builds the record of the block's w-th group of four columns
+// (vwin_build: lane = (column of the group, row of the tile)) -- stm_k_vwin_table's launch and its read of the arm planes are gone.
+// VMIN: the round-3 walk instead of the default one.
+template <int MODE, bool VMIN>
+static __device__ __forceinline__ void cross_arms_body(const ArmsArgs &a, uint32_t tg_far, uint32_t tg_near, int usd, int lsd, int H, int W)
+{
+    constexpr bool HTAB = MODE >= 1;
+    const int v = blockIdx.z;
+    const int wv_ = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int xr = MODE == 2 ? blockIdx.x * 64 + (threadIdx.x & 63) : blockIdx.x * 256 + threadIdx.x;
+    const int yr = MODE == 2 ? blockIdx.y * 16 + wv_ : blockIdx.y;
+    if (MODE == 1 ? (xr & ~63) >= W : MODE == 0 ? xr >= W : false) return; // MODE 1: whole waves only (no block-wide barrier below); MODE 2: everybody stays for the barrier
+    const int x = min(xr, W - 1), y = min(yr, H - 1); // a lane past the row / a wave past the image repeats the last pixel / row and stores nothing
+    const int p = y * W + x;
+    int arm[4];
+    if (VMIN) cross_arms_walk_vmin(a.img[v], x, y, p, tg_far, tg_near, usd, lsd, H, W, arm);
+    else cross_arms_walk(a.img[v], x, y, tg_far, tg_near, usd, lsd, H, W, arm);
     const bool inside = xr < W && yr < H;
     if (inside) {
         a.up[v][p] = (u8)arm[0];
@@ -169,6 +280,18 @@ __global__ __launch_bounds__(MODE == 2 ? 1024 : 256) void stm_k_cross_arms(ArmsA
             vwin_build(a.vtab + ((size_t)(v * nT + u) * G + gg) * a.vrec, ev_v[wv_], u, a.vtop, blockIdx.y * 16 + i - aU, aU + aD);
         }
     }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(MODE == 2 ? 1024 : 256) void stm_k_cross_arms(ArmsArgs a, uint32_t tg_far, uint32_t tg_near, int usd, int lsd, int H, int W)
+{
+    cross_arms_body<MODE, false>(a, tg_far, tg_near, usd, lsd, H, W);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(MODE == 2 ? 1024 : 256) void stm_k_cross_arms_vmin(ArmsArgs a, uint32_t tg_far, uint32_t tg_near, int usd, int lsd, int H, int W)
+{
+    cross_arms_body<MODE, true>(a, tg_far, tg_near, usd, lsd, H, W);
 }
 
 // threshold as the integer t with (int diff > threshold) <=> (diff > t), clamped to [-1, 255], times the field pattern
@@ -210,15 +333,21 @@ void launch_cross_arms2(int nviews, const uint32_t *const *packed, u8 *const *up
     a.vtab = vtab;
     a.vrec = vrec;
     a.vtop = vtop;
+    // 700 (and planes of 2 GiB and more, whose row offsets do not fit the scalar walk's 32 bits): the walk with vector min / select bookkeeping
+    const bool vmin = (agg_variant() / 100) % 10 == 7 || (size_t)H * W * 4 >= ((size_t)1 << 31);
+    const uint32_t tg_far = wide_threshold(ucd), tg_near = wide_threshold(lcd);
+#define STM_CROSS_LAUNCH(MODE, GRID, BLOCK)                                                                                      \
+    {                                                                                                                            \
+        if (vmin) STM_LAUNCH(stm_k_cross_arms_vmin<MODE>, GRID, BLOCK, 0, stream(), a, tg_far, tg_near, usd, lsd, H, W);         \
+        else STM_LAUNCH(stm_k_cross_arms<MODE>, GRID, BLOCK, 0, stream(), a, tg_far, tg_near, usd, lsd, H, W);                   \
+    }
     if (htab && vtab && vtop >= 0 && usd <= HR_TOP && usd <= vtop) // both window tables (the caller asks for them when the register-ring kernels will run)
-        STM_LAUNCH(stm_k_cross_arms<2>, dim3(cdiv(W, 64), cdiv(H, 16), nviews), dim3(1024), 0, stream(), a, wide_threshold(ucd),
-                           wide_threshold(lcd), usd, lsd, H, W);
+        STM_CROSS_LAUNCH(2, dim3(cdiv(W, 64), cdiv(H, 16), nviews), dim3(1024))
     else if (htab && usd <= HR_TOP) // (longer arms than the table's range: the caller does not ask for it, aggh_supports)
-        STM_LAUNCH(stm_k_cross_arms<1>, dim3(cdiv(W, 256), H, nviews), dim3(256), 0, stream(), a, wide_threshold(ucd),
-                           wide_threshold(lcd), usd, lsd, H, W);
+        STM_CROSS_LAUNCH(1, dim3(cdiv(W, 256), H, nviews), dim3(256))
     else
-        STM_LAUNCH(stm_k_cross_arms<0>, dim3(cdiv(W, 256), H, nviews), dim3(256), 0, stream(), a, wide_threshold(ucd),
-                           wide_threshold(lcd), usd, lsd, H, W);
+        STM_CROSS_LAUNCH(0, dim3(cdiv(W, 256), H, nviews), dim3(256))
+#undef STM_CROSS_LAUNCH
     STM_CHECK_LAUNCH();
 }
 
