@@ -16,7 +16,10 @@
  * d_io.cu style call sites -- include stm_dropin.hpp instead.
  *
  * Layouts (reference: image_io.cpp:155-189, d_io.cu:71-101):
- *   images      interleaved BGR u8, row-major, no row padding, elem_sz == 3
+ *   images      interleaved BGR u8, row-major, no row padding, elem_sz == 3 in the reference's drivers; any elem_sz >= 3 is
+ *               accepted: bytes 0..2 of a pixel are read and written, and the padding bytes (3 .. elem_sz-1) of an output
+ *               image are 0 after a host-flavour call, untouched by a device-flavour call -- except stm_d_dibr_dbm and
+ *               stm_d_dibr_dfm, which clear their whole output image like the reference (d_dibr_bwarp.cu:53, d_dibr_fwarp.cu:51,84)
  *   cost volume table of num_disp pointers, each a dense num_rows*num_cols float plane
  *   cross arms  table of 4 pointers to u8 planes, order UP, DOWN, LEFT, RIGHT
  *   disparity   float [H][W], signed offset (d - zero_disp)

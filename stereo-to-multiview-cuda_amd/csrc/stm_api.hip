@@ -579,6 +579,8 @@ void stm_d_dibr_dbm(unsigned char *d_img_out, unsigned char *d_img_in_l, unsigne
     if (!args_ok("d_dibr_dbm", {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return;
     (void)d_occl_l; (void)d_occl_r; // unused by the reference too (d_dibr_bwarp.cu:24-70)
     Workspace::begin((size_t)num_rows * num_cols * 4 + 1024);
+    if (elem_sz > 3) // d_dibr_bwarp.cu:53: the bytes of a pixel past the third come out 0 (the kernel writes the first three of every pixel)
+        STM_CHECK(hipMemsetAsync(d_img_out, 0, (size_t)num_rows * num_cols * elem_sz, stream()));
     core_dbm(d_img_out, d_img_in_l, d_img_in_r, d_disp_l, d_disp_r, d_mask_l, d_mask_r, shift, num_rows, num_cols, elem_sz,
              10, 15.0f); // d_dibr_bwarp.cu:63
 }
@@ -592,6 +594,7 @@ void stm_dibr_dbm(unsigned char *img_out, unsigned char *img_in_l, unsigned char
     Workspace::begin(3 * HW * elem_sz + 20 * HW + 8192);
     u8 *l = up(img_in_l, HW * elem_sz), *r = up(img_in_r, HW * elem_sz), *o = Workspace::get<u8>(HW * elem_sz);
     float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *ml = up(mask_l, HW), *mr = up(mask_r, HW);
+    STM_CHECK(hipMemsetAsync(o, 0, HW * elem_sz, stream())); // d_dibr_bwarp.cu:136: bytes past a pixel's third come back 0, not as the workspace held them
     core_dbm(o, l, r, dl, dr, ml, mr, shift, num_rows, num_cols, elem_sz, 7, 10.0f); // d_dibr_bwarp.cu:151
     down(img_out, o, HW * elem_sz);
     sync();
@@ -605,6 +608,8 @@ void stm_d_dibr_dfm(unsigned char *d_img_out, unsigned char *d_img_in_l, unsigne
     size_t HW = (size_t)num_rows * num_cols;
     Workspace::begin(HW * 8 + 1024);
     unsigned long long *keys = Workspace::get<unsigned long long>(HW);
+    if (elem_sz > 3) // d_dibr_fwarp.cu:51,84: the whole cleared staging image is copied over d_img_out
+        STM_CHECK(hipMemsetAsync(d_img_out, 0, HW * elem_sz, stream()));
     launch_fwarp(d_img_out, d_img_in_l, d_disp_l, shift, keys, num_rows, num_cols, elem_sz);
 }
 void stm_dibr_dfm(unsigned char *img_out, unsigned char *img_in_l, unsigned char *img_in_r, float *disp_l, float *disp_r,
@@ -617,6 +622,7 @@ void stm_dibr_dfm(unsigned char *img_out, unsigned char *img_in_l, unsigned char
     u8 *l = up(img_in_l, HW * elem_sz), *o = Workspace::get<u8>(HW * elem_sz);
     float *dl = up(disp_l, HW);
     unsigned long long *keys = Workspace::get<unsigned long long>(HW);
+    STM_CHECK(hipMemsetAsync(o, 0, HW * elem_sz, stream())); // d_dibr_fwarp.cu:139
     launch_fwarp(o, l, dl, shift, keys, num_rows, num_cols, elem_sz);
     down(img_out, o, HW * elem_sz);
     sync();
@@ -1002,6 +1008,8 @@ void stm_d_tx_scale(unsigned char *img_in, unsigned char *img_out, int in_rows, 
     size_t in_sz = (size_t)in_rows * in_cols * elem_sz, out_sz = (size_t)out_rows * out_cols * elem_sz;
     Workspace::begin(in_sz + out_sz + 4096);
     u8 *di = up(img_in, in_sz), *dout = Workspace::get<u8>(out_sz);
+    // the reference copies back an uncleared allocation (d_tx_scale.cu:95,115); here bytes past a pixel's third come back 0
+    STM_CHECK(hipMemsetAsync(dout, 0, out_sz, stream()));
     launch_scale_bilinear(di, dout, in_rows, in_cols, out_rows, out_cols, elem_sz);
     down(img_out, dout, out_sz);
     sync();
