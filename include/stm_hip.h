@@ -214,6 +214,31 @@ void stm_dibr_dbm(unsigned char *img_out, unsigned char *img_in_l, unsigned char
 void stm_d_dibr_dbm(unsigned char *d_img_out, unsigned char *d_img_in_l, unsigned char *d_img_in_r,
                     float *d_disp_l, float *d_disp_r, unsigned char *d_occl_l, unsigned char *d_occl_r,
                     float *d_mask_l, float *d_mask_r, float shift, int num_rows, int num_cols, int elem_sz);
+/* Linear sampling (an addition: the reference has none).  dibr_dbm with both backward warps fetched at the fractional warp
+ * coordinate instead of the truncated one: the reference's own alu_bilinear_interp (d_alu.cu:45-71) given the untruncated
+ * clamped position (d_dibr_bwarp.cu:17 assigns it to an int first, which makes the fetch a nearest one and shifts every view
+ * by up to a pixel, SURVEY A-Q20).  One warp of image `in` through map `disp`, mask `mask` and factor s, at pixel (x, y),
+ * channel c; f32 throughout, one operation per line, C fmaxf / fminf (a NaN position becomes 0):
+ *   sd  = disp[p] * s
+ *   fx  = (float)x + sd
+ *   fx  = fminf(fmaxf(fx, 0), (float)(W - 1))
+ *   x0  = (int)floorf(fx);  x1 = min(x0 + 1, W - 1)
+ *   wx  = fx - (float)x0
+ *   a   = (float)in[y][x0][c] * (1 - wx)
+ *   b   = (float)in[y][x1][c] * wx
+ *   top = a + b
+ *   smp = (u8)top                       (the vertical weight is 0: the row below is not read)
+ *   out = (u8)((float)smp * mask[p])
+ * Everything else is dibr_dbm's: s = -shift for the left image through disp_r / mask_r, s = (float)(1.0 - (double)shift) for the
+ * right image through disp_l / mask_l, the blend G(1 - mask_r) (host flavour gaussian(7,10), device flavour gaussian(10,15)),
+ * the merge with its u8 wrap, the bytes past a pixel's third.  Where disp * s is a whole number the result is dibr_dbm's.
+ * Parity is against a numpy statement of these lines (parity unpinned). */
+void stm_dibr_dbm_lin(unsigned char *img_out, unsigned char *img_in_l, unsigned char *img_in_r,
+                      float *disp_l, float *disp_r, unsigned char *occl_l, unsigned char *occl_r,
+                      float *mask_l, float *mask_r, float shift, int num_rows, int num_cols, int elem_sz);
+void stm_d_dibr_dbm_lin(unsigned char *d_img_out, unsigned char *d_img_in_l, unsigned char *d_img_in_r,
+                        float *d_disp_l, float *d_disp_r, unsigned char *d_occl_l, unsigned char *d_occl_r,
+                        float *d_mask_l, float *d_mask_r, float shift, int num_rows, int num_cols, int elem_sz);
 /* d_dibr_fwarp.h:12-20  (d_dibr_fwarp.cu:27-193): racy in the reference; deterministic here
  * (largest source x wins), parity unpinned */
 void stm_dibr_dfm(unsigned char *img_out, unsigned char *img_in_l, unsigned char *img_in_r,
@@ -253,7 +278,11 @@ void stm_adcensus_stm(unsigned char *img_sbs, float *disp_l, float *disp_r, unsi
  * OR-ing 0x400 adds the outlier interpolation of stm_dr_interp to stages 2 and 3: after region voting, before the sub-pixel step
  * and the bilateral filter, each view on its own image and its own post-voting outlier map.  It combines with 0x100 and with
  * 0x200 (order: voting, interpolation, sub-pixel, bilateral).  With stages 1 there are no outlier maps: 1 | 0x400 is an error
- * (stm_last_error), reported before anything is launched. */
+ * (stm_last_error), reported before anything is launched.
+ * OR-ing 0x800 renders the views of stage 3 with the linear sampling of stm_dibr_dbm_lin instead of the truncating fetch; the
+ * disparity maps are the same with and without it.  It combines with 0x100, 0x200 and 0x400.  Stages 1 and 2 render nothing:
+ * 1 | 0x800 and 2 | 0x800 are errors (stm_last_error), reported before anything is launched.  stm_adcensus_stm and the two
+ * adcensus_stm_2 calls keep the truncating fetch. */
 void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
                         int num_rows, int num_cols_sbs, int num_cols,
                         int num_rows_out, int num_cols_out, int elem_sz,
@@ -297,8 +326,8 @@ void *stm_stream_create(int num_rows, int num_cols_sbs, int num_cols, int num_ro
 /* stages the next frame (the caller's buffer is reusable on return); at most two frames in flight.
  * Returns the frame index, or -1 if both slots are uncollected. */
 long  stm_stream_submit(void *stream, const unsigned char *img_sbs);
-/* the `stages` word of stm_d_adcensus_stm the stream's frames are computed with: 3 (the default), optionally OR-ed with 0x200 and /
- * or 0x400 (not 0x100).  Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
+/* the `stages` word of stm_d_adcensus_stm the stream's frames are computed with: 3 (the default), optionally OR-ed with 0x200,
+ * 0x400 and / or 0x800 (not 0x100).  Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
 int   stm_stream_set_stages(void *stream, int stages);
 /* waits for the oldest uncollected frame and copies its results out (NULL = skip).  Returns its index or -1. */
 long  stm_stream_collect(void *stream, float *disp_l, float *disp_r, unsigned char *interlaced);

@@ -64,6 +64,8 @@ PROTOS = {
     "stm_d_dibr_occl_to_mask": ([vp, vp, vp, vp, i, i], None),
     "stm_dibr_dbm": ([u8p, u8p, u8p, f32p, f32p, u8p, u8p, f32p, f32p, f, i, i, i], None),
     "stm_d_dibr_dbm": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, f, i, i, i], None),
+    "stm_dibr_dbm_lin": ([u8p, u8p, u8p, f32p, f32p, u8p, u8p, f32p, f32p, f, i, i, i], None),
+    "stm_d_dibr_dbm_lin": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, f, i, i, i], None),
     "stm_dibr_dfm": ([u8p, u8p, u8p, f32p, f32p, f, i, i, i], None),
     "stm_d_dibr_dfm": ([vp, vp, vp, vp, vp, f, i, i, i], None),
     "stm_mux_multiview": ([u8pp, u8p, i, f, i, i, i, i, i], None),

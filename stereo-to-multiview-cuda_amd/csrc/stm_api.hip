@@ -192,12 +192,37 @@ void core_bilateral(float *d_img, int radius, float sigma_color, float sigma_spa
 }
 
 void core_dbm(u8 *d_out, const u8 *d_l, const u8 *d_r, const float *disp_l, const float *disp_r, const float *mask_l,
-              const float *mask_r, float shift, int H, int W, int elem_sz, int g_radius, float g_sigma)
+              const float *mask_r, float shift, int H, int W, int elem_sz, int g_radius, float g_sigma, bool linear = false)
 {
     size_t HW = (size_t)H * W;
     float *blend = Workspace::get<float>(HW);
     launch_gaussian_max(mask_r, blend, gauss2d_table(g_radius, g_sigma), g_radius, g_sigma, H, W, true); // G(1 - maskR)
-    launch_view_synth(d_out, d_l, d_r, disp_l, disp_r, mask_l, mask_r, blend, shift, H, W, elem_sz);
+    launch_view_synth(d_out, d_l, d_r, disp_l, disp_r, mask_l, mask_r, blend, shift, H, W, elem_sz, linear);
+}
+
+// dibr_dbm / dibr_dbm_lin: one body per flavour, `linear` selects the fetch of the two backward warps (stm_hip.h)
+void dbm_device(const char *fn, unsigned char *d_img_out, unsigned char *d_img_in_l, unsigned char *d_img_in_r, float *d_disp_l,
+                float *d_disp_r, float *d_mask_l, float *d_mask_r, float shift, int num_rows, int num_cols, int elem_sz, bool linear)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return;
+    Workspace::begin((size_t)num_rows * num_cols * 4 + 1024);
+    if (elem_sz > 3) // d_dibr_bwarp.cu:53: the bytes of a pixel past the third come out 0 (the kernel writes the first three of every pixel)
+        STM_CHECK(hipMemsetAsync(d_img_out, 0, (size_t)num_rows * num_cols * elem_sz, stream()));
+    core_dbm(d_img_out, d_img_in_l, d_img_in_r, d_disp_l, d_disp_r, d_mask_l, d_mask_r, shift, num_rows, num_cols, elem_sz,
+             10, 15.0f, linear); // d_dibr_bwarp.cu:63
+}
+void dbm_host(const char *fn, unsigned char *img_out, unsigned char *img_in_l, unsigned char *img_in_r, float *disp_l, float *disp_r,
+              float *mask_l, float *mask_r, float shift, int num_rows, int num_cols, int elem_sz, bool linear)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return;
+    size_t HW = (size_t)num_rows * num_cols;
+    Workspace::begin(3 * HW * elem_sz + 20 * HW + 8192);
+    u8 *l = up(img_in_l, HW * elem_sz), *r = up(img_in_r, HW * elem_sz), *o = Workspace::get<u8>(HW * elem_sz);
+    float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *ml = up(mask_l, HW), *mr = up(mask_r, HW);
+    STM_CHECK(hipMemsetAsync(o, 0, HW * elem_sz, stream())); // d_dibr_bwarp.cu:136: bytes past a pixel's third come back 0, not as the workspace held them
+    core_dbm(o, l, r, dl, dr, ml, mr, shift, num_rows, num_cols, elem_sz, 7, 10.0f, linear); // d_dibr_bwarp.cu:151
+    down(img_out, o, HW * elem_sz);
+    sync();
 }
 
 void core_mux(const u8 *const *d_views, u8 *d_out, int N, float angle, int Hin, int Win, int Hout, int Wout, int elem_sz,
@@ -576,28 +601,32 @@ void stm_d_dibr_dbm(unsigned char *d_img_out, unsigned char *d_img_in_l, unsigne
                     float *d_disp_r, unsigned char *d_occl_l, unsigned char *d_occl_r, float *d_mask_l, float *d_mask_r,
                     float shift, int num_rows, int num_cols, int elem_sz)
 {
-    if (!args_ok("d_dibr_dbm", {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return;
     (void)d_occl_l; (void)d_occl_r; // unused by the reference too (d_dibr_bwarp.cu:24-70)
-    Workspace::begin((size_t)num_rows * num_cols * 4 + 1024);
-    if (elem_sz > 3) // d_dibr_bwarp.cu:53: the bytes of a pixel past the third come out 0 (the kernel writes the first three of every pixel)
-        STM_CHECK(hipMemsetAsync(d_img_out, 0, (size_t)num_rows * num_cols * elem_sz, stream()));
-    core_dbm(d_img_out, d_img_in_l, d_img_in_r, d_disp_l, d_disp_r, d_mask_l, d_mask_r, shift, num_rows, num_cols, elem_sz,
-             10, 15.0f); // d_dibr_bwarp.cu:63
+    dbm_device("d_dibr_dbm", d_img_out, d_img_in_l, d_img_in_r, d_disp_l, d_disp_r, d_mask_l, d_mask_r, shift, num_rows, num_cols,
+               elem_sz, false);
 }
 void stm_dibr_dbm(unsigned char *img_out, unsigned char *img_in_l, unsigned char *img_in_r, float *disp_l, float *disp_r,
                   unsigned char *occl_l, unsigned char *occl_r, float *mask_l, float *mask_r, float shift, int num_rows,
                   int num_cols, int elem_sz)
 {
-    if (!args_ok("dibr_dbm", {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return;
     (void)occl_l; (void)occl_r;
-    size_t HW = (size_t)num_rows * num_cols;
-    Workspace::begin(3 * HW * elem_sz + 20 * HW + 8192);
-    u8 *l = up(img_in_l, HW * elem_sz), *r = up(img_in_r, HW * elem_sz), *o = Workspace::get<u8>(HW * elem_sz);
-    float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *ml = up(mask_l, HW), *mr = up(mask_r, HW);
-    STM_CHECK(hipMemsetAsync(o, 0, HW * elem_sz, stream())); // d_dibr_bwarp.cu:136: bytes past a pixel's third come back 0, not as the workspace held them
-    core_dbm(o, l, r, dl, dr, ml, mr, shift, num_rows, num_cols, elem_sz, 7, 10.0f); // d_dibr_bwarp.cu:151
-    down(img_out, o, HW * elem_sz);
-    sync();
+    dbm_host("dibr_dbm", img_out, img_in_l, img_in_r, disp_l, disp_r, mask_l, mask_r, shift, num_rows, num_cols, elem_sz, false);
+}
+// linear sampling (an addition, the reference has none): dibr_dbm with both backward warps fetched at the fractional coordinate
+void stm_d_dibr_dbm_lin(unsigned char *d_img_out, unsigned char *d_img_in_l, unsigned char *d_img_in_r, float *d_disp_l,
+                        float *d_disp_r, unsigned char *d_occl_l, unsigned char *d_occl_r, float *d_mask_l, float *d_mask_r,
+                        float shift, int num_rows, int num_cols, int elem_sz)
+{
+    (void)d_occl_l; (void)d_occl_r;
+    dbm_device("d_dibr_dbm_lin", d_img_out, d_img_in_l, d_img_in_r, d_disp_l, d_disp_r, d_mask_l, d_mask_r, shift, num_rows,
+               num_cols, elem_sz, true);
+}
+void stm_dibr_dbm_lin(unsigned char *img_out, unsigned char *img_in_l, unsigned char *img_in_r, float *disp_l, float *disp_r,
+                      unsigned char *occl_l, unsigned char *occl_r, float *mask_l, float *mask_r, float shift, int num_rows,
+                      int num_cols, int elem_sz)
+{
+    (void)occl_l; (void)occl_r;
+    dbm_host("dibr_dbm_lin", img_out, img_in_l, img_in_r, disp_l, disp_r, mask_l, mask_r, shift, num_rows, num_cols, elem_sz, true);
 }
 
 void stm_d_dibr_dfm(unsigned char *d_img_out, unsigned char *d_img_in_l, unsigned char *d_img_in_r, float *d_disp_l,
@@ -853,7 +882,7 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
 
 // hit maps -> bleed -> masks -> N-2 views -> interlace (d_io.cu:160-205)
 void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_interlaced, int H, int W, int Hout, int Wout,
-                  int elem_sz, int N, float angle)
+                  int elem_sz, int N, float angle, bool linear = false)
 {
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
     float *mask_l = Workspace::get<float>(HW), *mask_r = Workspace::get<float>(HW), *blend = Workspace::get<float>(HW);
@@ -873,13 +902,13 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
             return;
         }
         launch_synth_mux(img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, d_interlaced, N, yi, 1.0f / yi, ymod, H, W, Hout, Wout,
-                         elem_sz, 2);
+                         elem_sz, 2, linear);
         return;
     }
     // 200: the un-fused form (every view written, then interlaced), as the reference structures it (d_io.cu:182-203)
     u8 *views_mem = Workspace::get<u8>((size_t)N * IMG);
     // views[0] = right image, views[N-1] = left image (d_io.cu:182-183)
-    launch_view_synth_all(views_mem, IMG, N, img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, H, W, elem_sz); // :186-201
+    launch_view_synth_all(views_mem, IMG, N, img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, H, W, elem_sz, linear); // :186-201
     // view table built on the device (no host memory involved, so nothing to keep alive or synchronise)
     u8 **dv = Workspace::get<u8 *>(N);
     launch_view_table(dv, img_r, img_l, views_mem, IMG, N);
@@ -908,6 +937,10 @@ void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp
         fail("d_adcensus_stm: stages 0x400 (outlier interpolation) needs the refinement stages (2 or 3)", "stages", __FILE__, __LINE__);
         return;
     }
+    if ((stages & 0x800) && (stages & 0xff) < 3) { // linear sampling changes the renderer only: stages 1 and 2 render nothing
+        fail("d_adcensus_stm: stages 0x800 (linear sampling of the warps) needs the rendering stage (3)", "stages", __FILE__, __LINE__);
+        return;
+    }
     const int H = num_rows, W = num_cols, N = num_views;
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
     const size_t V = pq_volume_floats(num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
@@ -928,11 +961,12 @@ void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp
     const bool hslo = (stages & 0x100) != 0; // + scanline optimisation between aggregation and WTA (BASELINE config 3)
     const bool subpix = (stages & 0x200) != 0; // + sub-pixel enhancement of the whole-pixel maps (Mei et al. 3.4)
     const bool interp = (stages & 0x400) != 0; // + interpolation of the outliers region voting leaves (Mei et al. 3.4)
+    const bool linwarp = (stages & 0x800) != 0; // + the views' warps fetched at the fractional coordinate (stm_dibr_dbm_lin)
     stages &= 0xff;
     frame_disparity(img_l, img_r, d_disp_l, d_disp_r, al, ar, H, W, elem_sz, num_disp, zero_disp, ad_coeff, census_coeff, ucd,
                     lcd, usd, lsd, thresh_s, thresh_h, stages >= 2, hslo, fused_split ? pre : nullptr, subpix, interp);
     if (stages < 3) return;
-    frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle);
+    frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle, linwarp);
 }
 
 // adcensus_stm_2, d_io.cu:240-508: the disparity is computed on a bilinearly reduced pair

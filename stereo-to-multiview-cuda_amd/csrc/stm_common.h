@@ -195,10 +195,11 @@ void launch_dcc_rows(u8 *out_l, u8 *out_r, const float *disp_l, const float *dis
 void launch_hitmask_rows(float *mask_l, float *mask_r, const float *disp_l, const float *disp_r, int H, int W);
 void launch_occl_to_mask(float *mask_l, float *mask_r, const u8 *occl_l, const u8 *occl_r, int H, int W);
 void launch_view_synth(u8 *out, const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r,
-                       const float *mask_l, const float *mask_r, const float *blend, float shift, int H, int W, int elem_sz);
+                       const float *mask_l, const float *mask_r, const float *blend, float shift, int H, int W, int elem_sz,
+                       bool linear = false); // linear: warp_tap<true>, the fractional fetch of stm_dibr_dbm_lin / frame bit 0x800
 void launch_view_synth_all(u8 *views, size_t view_stride, int N, const u8 *img_l, const u8 *img_r, const float *disp_l,
                            const float *disp_r, const float *mask_l, const float *mask_r, const float *blend, int H, int W,
-                           int elem_sz);
+                           int elem_sz, bool linear = false);
 void launch_fwarp(u8 *out, const u8 *img, const float *disp, float shift, unsigned long long *keys, int H, int W, int elem_sz);
 void launch_scale_bilinear(const u8 *in, u8 *out, int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz);
 void launch_disp_scale(float *out, const float *in, int out_rows, int out_cols, int in_rows, int in_cols, float disp_scale);
@@ -206,7 +207,7 @@ void launch_view_table(u8 **tab, u8 *first, u8 *last, u8 *mem, size_t stride, in
 // frame pipeline: the N - 2 views are synthesised inside the interlacer, sample by sample (no view buffers)
 void launch_synth_mux(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l, const float *mask_r,
                       const float *blend, u8 *out, int N, float y_interval, float inv_y_interval, int ymod, int Hin, int Win, int Hout,
-                      int Wout, int elem_sz, int variant);
+                      int Wout, int elem_sz, int variant, bool linear = false);
 void launch_mux(const u8 *const *d_views, u8 *out, int N, float y_interval, float inv_y_interval, int ymod,
                 int Hin, int Win, int Hout, int Wout, int elem_sz, int variant);
 // aggregation on the matrix pipe (stm_kernels_aggm.hip): the frame pipeline's cost -> H -> V, V -> H + WTA

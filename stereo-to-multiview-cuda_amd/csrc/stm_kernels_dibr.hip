@@ -227,6 +227,29 @@ void launch_hitmask_rows(float *mask_l, float *mask_r, const float *disp_l, cons
 // outL = (u8)(L[sxL] * maskR), sxL = (int)clamp(x + dR * (-shift));  outR = (u8)(R[sxR] * maskL),
 // sxR = (int)clamp(x + dL * (1 - shift))   -- the truncation makes alu_bilinear_interp a nearest fetch
 // (d_dibr_bwarp.cu:16-21, SURVEY A-Q20);  out = (u8)((1-m) * outL) + (u8)(m * outR), u8 wrap (A-Q22).
+//
+// One sample of a backward warp: channel c of image row `row` at the clamped position fx in [0, W - 1].
+// LINEAR = false: the reference's fetch, img[(int)fx] (the default, bit for bit).
+// LINEAR = true (linear sampling, stm_dibr_dbm_lin / frame bit 0x800): alu_bilinear_interp (d_alu.cu:45-71) given the
+// untruncated position and cy = (float)y -- the bottom row has weight 0 and is not loaded; x1 = min(x0 + 1, W - 1) keeps the
+// second tap inside the row; one f32 operation per line (the file is compiled -ffp-contract=off), (u8) truncates.
+template <bool LINEAR>
+__device__ __forceinline__ u8 warp_tap(const u8 *__restrict__ img, size_t row, float fx, int c, int W, int elem_sz)
+{
+    if constexpr (!LINEAR) {
+        const int sx = (int)fx;
+        return img[(row + sx) * elem_sz + c];
+    } else {
+        const int x0 = (int)floorf(fx);
+        const int x1 = min(x0 + 1, W - 1);
+        const float wx = fx - (float)x0;
+        const float a = (float)img[(row + x0) * elem_sz + c] * (1.0f - wx);
+        const float b = (float)img[(row + x1) * elem_sz + c] * wx;
+        const float top = a + b;
+        return (u8)top;
+    }
+}
+template <bool LINEAR>
 __global__ __launch_bounds__(256) void stm_k_view_synth(u8 *__restrict__ out, const u8 *__restrict__ img_l,
                                                         const u8 *__restrict__ img_r, const float *__restrict__ disp_l,
                                                         const float *__restrict__ disp_r, const float *__restrict__ mask_l,
@@ -239,37 +262,42 @@ __global__ __launch_bounds__(256) void stm_k_view_synth(u8 *__restrict__ out, co
     float wmax = (float)(W - 1);
     float sd = disp_r[p] * shift_l;
     float fx = (float)x + sd;
-    int sxl = (int)fminf(fmaxf(fx, 0.0f), wmax);
+    const float fxl = fminf(fmaxf(fx, 0.0f), wmax);
     sd = disp_l[p] * shift_r;
     fx = (float)x + sd;
-    int sxr = (int)fminf(fmaxf(fx, 0.0f), wmax);
+    const float fxr = fminf(fmaxf(fx, 0.0f), wmax);
     float vmr = mask_r[p], vml = mask_l[p], m = blend[p];
     float one_m = 1.0f - m;
-    const u8 *sl = img_l + (row + sxl) * elem_sz, *sr = img_r + (row + sxr) * elem_sz;
     u8 *o = out + p * elem_sz;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        u8 a = (u8)((float)sl[c] * vmr); // left-sourced pixel
-        u8 b = (u8)((float)sr[c] * vml); // right-sourced pixel
+        u8 a = (u8)((float)warp_tap<LINEAR>(img_l, row, fxl, c, W, elem_sz) * vmr); // left-sourced pixel
+        u8 b = (u8)((float)warp_tap<LINEAR>(img_r, row, fxr, c, W, elem_sz) * vml); // right-sourced pixel
         float cb = one_m * (float)a;
         float ca = m * (float)b;
         o[c] = (u8)((u8)cb + (u8)ca);
     }
 }
 void launch_view_synth(u8 *out, const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r,
-                       const float *mask_l, const float *mask_r, const float *blend, float shift, int H, int W, int elem_sz)
+                       const float *mask_l, const float *mask_r, const float *blend, float shift, int H, int W, int elem_sz,
+                       bool linear)
 {
     float shift_l = -shift;                               // d_dibr_bwarp.cu:56
     float shift_r = (float)(1.0 - (double)shift);         // :57
     ProfScope p("view_synth");
-    STM_LAUNCH(stm_k_view_synth, dim3(cdiv(W, 256), H), dim3(256), 0, stream(), out, img_l, img_r, disp_l, disp_r,
-                       mask_l, mask_r, blend, shift_l, shift_r, H, W, elem_sz);
+    if (linear)
+        STM_LAUNCH(stm_k_view_synth<true>, dim3(cdiv(W, 256), H), dim3(256), 0, stream(), out, img_l, img_r, disp_l, disp_r,
+                   mask_l, mask_r, blend, shift_l, shift_r, H, W, elem_sz);
+    else
+        STM_LAUNCH(stm_k_view_synth<false>, dim3(cdiv(W, 256), H), dim3(256), 0, stream(), out, img_l, img_r, disp_l, disp_r,
+                   mask_l, mask_r, blend, shift_l, shift_r, H, W, elem_sz);
     STM_CHECK_LAUNCH();
 }
 
 // All N-2 synthesised views of a frame in one launch (d_io.cu:186-201 loops over d_dibr_dbm): a thread owns one
 // pixel, reads its two disparities, two masks and blend weight once and produces that pixel of every view v = 1..N-2
 // with shift = 1 - v / (N - 1) evaluated as the reference does (:189, in double, narrowed).
+template <bool LINEAR>
 __global__ __launch_bounds__(256) void stm_k_view_synth_all(u8 *__restrict__ views, size_t view_stride, int N,
                                                             const u8 *__restrict__ img_l, const u8 *__restrict__ img_r,
                                                             const float *__restrict__ disp_l, const float *__restrict__ disp_r,
@@ -289,16 +317,15 @@ __global__ __launch_bounds__(256) void stm_k_view_synth_all(u8 *__restrict__ vie
         const float shift_r = (float)(1.0 - (double)shift); // :57
         float sd = dr * shift_l;
         float fx = (float)x + sd;
-        const int sxl = (int)fminf(fmaxf(fx, 0.0f), wmax);
+        const float fxl = fminf(fmaxf(fx, 0.0f), wmax);
         sd = dl * shift_r;
         fx = (float)x + sd;
-        const int sxr = (int)fminf(fmaxf(fx, 0.0f), wmax);
-        const u8 *sl = img_l + (row + sxl) * elem_sz, *sr = img_r + (row + sxr) * elem_sz;
+        const float fxr = fminf(fmaxf(fx, 0.0f), wmax);
         u8 *o = views + (size_t)v * view_stride + p * elem_sz;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const u8 a = (u8)((float)sl[c] * vmr);
-            const u8 b = (u8)((float)sr[c] * vml);
+            const u8 a = (u8)((float)warp_tap<LINEAR>(img_l, row, fxl, c, W, elem_sz) * vmr);
+            const u8 b = (u8)((float)warp_tap<LINEAR>(img_r, row, fxr, c, W, elem_sz) * vml);
             const float cb = one_m * (float)a;
             const float ca = m * (float)b;
             o[c] = (u8)((u8)cb + (u8)ca);
@@ -308,12 +335,16 @@ __global__ __launch_bounds__(256) void stm_k_view_synth_all(u8 *__restrict__ vie
 // views = base of N view slots of view_stride bytes; slots 1..N-2 are written
 void launch_view_synth_all(u8 *views, size_t view_stride, int N, const u8 *img_l, const u8 *img_r, const float *disp_l,
                            const float *disp_r, const float *mask_l, const float *mask_r, const float *blend, int H, int W,
-                           int elem_sz)
+                           int elem_sz, bool linear)
 {
     if (N < 3) return;
     ProfScope p("view_synth");
-    STM_LAUNCH(stm_k_view_synth_all, dim3(cdiv(W, 256), H), dim3(256), 0, stream(), views, view_stride, N, img_l, img_r,
-                       disp_l, disp_r, mask_l, mask_r, blend, H, W, elem_sz);
+    if (linear)
+        STM_LAUNCH(stm_k_view_synth_all<true>, dim3(cdiv(W, 256), H), dim3(256), 0, stream(), views, view_stride, N, img_l, img_r,
+                   disp_l, disp_r, mask_l, mask_r, blend, H, W, elem_sz);
+    else
+        STM_LAUNCH(stm_k_view_synth_all<false>, dim3(cdiv(W, 256), H), dim3(256), 0, stream(), views, view_stride, N, img_l, img_r,
+                   disp_l, disp_r, mask_l, mask_r, blend, H, W, elem_sz);
     STM_CHECK_LAUNCH();
 }
 
@@ -482,6 +513,7 @@ struct SynthArgs {
     const u8 *img_l, *img_r;
     const float *disp_l, *disp_r, *mask_l, *mask_r, *blend;
 };
+template <bool LINEAR>
 __device__ __forceinline__ u8 synth_sample(const SynthArgs &a, int N, int v, int c, int x, int y, int W, int elem_sz)
 {
     const size_t row = (size_t)y * W, p = row + x;
@@ -493,31 +525,32 @@ __device__ __forceinline__ u8 synth_sample(const SynthArgs &a, int N, int v, int
     const float shift_r = (float)(1.0 - (double)shift); // :57
     float sd = a.disp_r[p] * shift_l;
     float fx = (float)x + sd;
-    const int sxl = (int)fminf(fmaxf(fx, 0.0f), wmax);
+    const float fxl = fminf(fmaxf(fx, 0.0f), wmax);
     sd = a.disp_l[p] * shift_r;
     fx = (float)x + sd;
-    const int sxr = (int)fminf(fmaxf(fx, 0.0f), wmax);
+    const float fxr = fminf(fmaxf(fx, 0.0f), wmax);
     const float m = a.blend[p], one_m = 1.0f - m;
-    const u8 pa = (u8)((float)a.img_l[(row + sxl) * elem_sz + c] * a.mask_r[p]); // left-sourced pixel
-    const u8 pb = (u8)((float)a.img_r[(row + sxr) * elem_sz + c] * a.mask_l[p]); // right-sourced pixel
+    const u8 pa = (u8)((float)warp_tap<LINEAR>(a.img_l, row, fxl, c, W, elem_sz) * a.mask_r[p]); // left-sourced pixel
+    const u8 pb = (u8)((float)warp_tap<LINEAR>(a.img_r, row, fxr, c, W, elem_sz) * a.mask_l[p]); // right-sourced pixel
     const float cb = one_m * (float)pa;
     const float ca = m * (float)pb;
     return (u8)((u8)cb + (u8)ca);
 }
+template <bool LINEAR>
 __device__ __forceinline__ u8 synth_bilinear(const SynthArgs &a, int N, int v, int c, float cx, float cy, int W, int H, int elem_sz)
 {
     const int x0 = (int)floorf(cx), y0 = (int)floorf(cy);
     const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
     const float wx = cx - (float)x0, wy = cy - (float)y0;
-    const float v00 = (float)synth_sample(a, N, v, c, x0, y0, W, elem_sz);
-    const float v01 = wx != 0.0f ? (float)synth_sample(a, N, v, c, x1, y0, W, elem_sz) : 0.0f;
+    const float v00 = (float)synth_sample<LINEAR>(a, N, v, c, x0, y0, W, elem_sz);
+    const float v01 = wx != 0.0f ? (float)synth_sample<LINEAR>(a, N, v, c, x1, y0, W, elem_sz) : 0.0f;
     float ta = v00 * (1.0f - wx);
     float tb = v01 * wx;
     const float top = ta + tb;
     float bot = 0.0f;
     if (wy != 0.0f) {
-        const float v10 = (float)synth_sample(a, N, v, c, x0, y1, W, elem_sz);
-        const float v11 = wx != 0.0f ? (float)synth_sample(a, N, v, c, x1, y1, W, elem_sz) : 0.0f;
+        const float v10 = (float)synth_sample<LINEAR>(a, N, v, c, x0, y1, W, elem_sz);
+        const float v11 = wx != 0.0f ? (float)synth_sample<LINEAR>(a, N, v, c, x1, y1, W, elem_sz) : 0.0f;
         ta = v10 * (1.0f - wx);
         tb = v11 * wx;
         bot = ta + tb;
@@ -526,6 +559,7 @@ __device__ __forceinline__ u8 synth_bilinear(const SynthArgs &a, int N, int v, i
     tb = bot * wy;
     return (u8)(ta + tb);
 }
+template <bool LINEAR>
 __global__ __launch_bounds__(256) void stm_k_synth_mux(SynthArgs a, u8 *__restrict__ out, int N, float y_interval, float inv_y, int ymod,
                                                        int Hin, int Win, int Hout, int Wout, int elem_sz, int variant)
 {
@@ -546,18 +580,22 @@ __global__ __launch_bounds__(256) void stm_k_synth_mux(SynthArgs a, u8 *__restri
     if (g_view >= N) g_view -= N;
     if (b_view >= N) b_view -= N;
     const size_t o = ((size_t)tx + (size_t)ty * Wout) * elem_sz;
-    out[o + 0] = synth_bilinear(a, N, b_view, 0, xs, ys, Win, Hin, elem_sz);
-    out[o + 1] = synth_bilinear(a, N, g_view, 1, xs, ys, Win, Hin, elem_sz);
-    out[o + 2] = synth_bilinear(a, N, r_view, 2, xs, ys, Win, Hin, elem_sz);
+    out[o + 0] = synth_bilinear<LINEAR>(a, N, b_view, 0, xs, ys, Win, Hin, elem_sz);
+    out[o + 1] = synth_bilinear<LINEAR>(a, N, g_view, 1, xs, ys, Win, Hin, elem_sz);
+    out[o + 2] = synth_bilinear<LINEAR>(a, N, r_view, 2, xs, ys, Win, Hin, elem_sz);
 }
 void launch_synth_mux(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l, const float *mask_r,
                       const float *blend, u8 *out, int N, float y_interval, float inv_y_interval, int ymod, int Hin, int Win, int Hout,
-                      int Wout, int elem_sz, int variant)
+                      int Wout, int elem_sz, int variant, bool linear)
 {
     SynthArgs a{img_l, img_r, disp_l, disp_r, mask_l, mask_r, blend};
     ProfScope p("synth_mux");
-    STM_LAUNCH(stm_k_synth_mux, dim3(cdiv(Wout, 256), Hout), dim3(256), 0, stream(), a, out, N, y_interval, inv_y_interval, ymod, Hin,
-               Win, Hout, Wout, elem_sz, variant);
+    if (linear)
+        STM_LAUNCH(stm_k_synth_mux<true>, dim3(cdiv(Wout, 256), Hout), dim3(256), 0, stream(), a, out, N, y_interval, inv_y_interval,
+                   ymod, Hin, Win, Hout, Wout, elem_sz, variant);
+    else
+        STM_LAUNCH(stm_k_synth_mux<false>, dim3(cdiv(Wout, 256), Hout), dim3(256), 0, stream(), a, out, N, y_interval, inv_y_interval,
+                   ymod, Hin, Win, Hout, Wout, elem_sz, variant);
     STM_CHECK_LAUNCH();
 }
 

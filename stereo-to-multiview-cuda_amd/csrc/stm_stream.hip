@@ -40,7 +40,7 @@ struct FrameStream {
     hipStream_t s_in, s_out;
     bool overlap = true; // two frames in flight on the GPU (a compute stream + workspace per slot)
     bool use_graph = true;
-    int stages = 3; // stm_stream_set_stages: 3, optionally with 0x200 / 0x400
+    int stages = 3; // stm_stream_set_stages: 3, optionally with 0x200 / 0x400 / 0x800
     Slot slot[2];
     long submitted = 0, collected = 0;
 };
@@ -92,15 +92,15 @@ void *stm_stream_create(int num_rows, int num_cols_sbs, int num_cols, int num_ro
     return f;
 }
 
-// The `stages` word every frame of the stream is computed with: 3 (the default), optionally OR-ed with 0x200 (sub-pixel) and / or
-// 0x400 (outlier interpolation).  Not 0x100: the stream's workspace is sized for the frame without HSLO.  Only before the first
+// The `stages` word every frame of the stream is computed with: 3 (the default), optionally OR-ed with 0x200 (sub-pixel), 0x400
+// (outlier interpolation) and / or 0x800 (linear sampling of the warps).  Not 0x100: the stream's workspace is sized for the frame without HSLO.  Only before the first
 // submit: afterwards the slots replay their launches from a captured graph.  Returns 0, or -1 with the error recorded.
 int stm_stream_set_stages(void *h, int stages)
 {
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
-    if ((stages & ~0x600) != 3) {
-        stm::fail("stream_set_stages: stages must be 3, optionally OR-ed with 0x200 and 0x400", "stages", __FILE__, __LINE__);
+    if ((stages & ~0xe00) != 3) {
+        stm::fail("stream_set_stages: stages must be 3, optionally OR-ed with 0x200, 0x400 and 0x800", "stages", __FILE__, __LINE__);
         return -1;
     }
     if (f->submitted > 0) {

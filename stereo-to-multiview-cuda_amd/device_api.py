@@ -22,6 +22,8 @@ def _p(t):
 STAGE_SUBPIXEL = 0x200
 # ... outlier interpolation after region voting (stages 2 and 3 only; combines with 0x100 and with STAGE_SUBPIXEL)
 STAGE_INTERP = 0x400
+# ... the views of stage 3 rendered at the fractional warp coordinate (stm_dibr_dbm_lin; stage 3 only, combines with every other bit)
+STAGE_LINEAR_WARP = 0x800
 
 
 class FrameParams:
@@ -39,7 +41,8 @@ class FrameParams:
 def d_adcensus_stm(sbs, disp_l, disp_r, interlaced, p, stages=3):
     """stm_d_adcensus_stm: sbs uint8 [H][2W][3] on the GPU; outputs are written in place.
     stages: 1 = cost+aggregation+WTA, 2 = + refinement, 3 = full frame (views + interlacing); OR-ing 0x100 adds the
-    scanline optimisation, OR-ing STAGE_SUBPIXEL the sub-pixel enhancement, OR-ing STAGE_INTERP the outlier interpolation."""
+    scanline optimisation, OR-ing STAGE_SUBPIXEL the sub-pixel enhancement, OR-ing STAGE_INTERP the outlier interpolation,
+    OR-ing STAGE_LINEAR_WARP (stage 3) the linear sampling of the views' warps."""
     assert sbs.is_cuda and sbs.dtype == torch.uint8 and sbs.is_contiguous()
     H, Wsbs, E = sbs.shape
     W = Wsbs // 2
@@ -108,6 +111,19 @@ def d_dr_interp(disp, outliers, img):
     assert img.shape[:2] == (H, W) and img.dtype == torch.uint8 and img.is_contiguous()
     _use_current_stream()
     lib().stm_d_dr_interp(_p(disp), _p(outliers), _p(img), H, W, img.shape[2])
+
+
+def d_dibr_dbm_lin(out, img_l, img_r, disp_l, disp_r, mask_l, mask_r, shift):
+    """stm_d_dibr_dbm_lin: one synthesised view written to out (uint8 [H][W][E], cleared first when E > 3) from the two images,
+    the two disparity maps and the two masks, both warps fetched at the fractional coordinate; mask blur gaussian(10, 15)."""
+    H, W, E = img_l.shape
+    for t in (out, img_l, img_r):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    for t in (disp_l, disp_r, mask_l, mask_r):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
+    _use_current_stream()
+    lib().stm_d_dibr_dbm_lin(_p(out), _p(img_l), _p(img_r), _p(disp_l), _p(disp_r), None, None, _p(mask_l), _p(mask_r),
+                             float(shift), H, W, E)
 
 
 def prof_enable(on=True):

@@ -198,6 +198,23 @@ def dibr_dbm(img_l, img_r, disp_l, disp_r, occl_l, occl_r, mask_l, mask_r, shift
     return out
 
 
+def dibr_dbm_lin(img_l, img_r, disp_l, disp_r, occl_l, occl_r, mask_l, mask_r, shift):
+    """dibr_dbm with both backward warps fetched at the fractional warp coordinate (stm_dibr_dbm_lin; an addition, the reference
+    truncates the coordinate).  Host flavour: mask blur gaussian(7,10)."""
+    H, W, E = img_l.shape
+    img_l, pil = _u8(img_l)
+    img_r, pir = _u8(img_r)
+    disp_l, pdl = _f32(disp_l)
+    disp_r, pdr = _f32(disp_r)
+    occl_l, pol = _u8(occl_l)
+    occl_r, por = _u8(occl_r)
+    mask_l, pml = _f32(mask_l)
+    mask_r, pmr = _f32(mask_r)
+    out = np.zeros((H, W, E), np.uint8)
+    lib().stm_dibr_dbm_lin(out.ctypes.data_as(u8p), pil, pir, pdl, pdr, pol, por, pml, pmr, shift, H, W, E)
+    return out
+
+
 def dibr_dfm(img_l, img_r, disp_l, disp_r, shift):
     """d_dibr_fwarp.h:17-20 (deterministic; parity unpinned)."""
     H, W, E = img_l.shape

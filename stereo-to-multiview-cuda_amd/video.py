@@ -26,8 +26,8 @@ class FrameStream:
             self.set_stages(stages)
 
     def set_stages(self, stages):
-        """stm_stream_set_stages: 3, optionally OR-ed with 0x200 (sub-pixel) and 0x400 (outlier interpolation); only before the
-        first submit.  Raises ValueError where the library refuses (it returns -1; in error mode 0 it exits like any error)."""
+        """stm_stream_set_stages: 3, optionally OR-ed with 0x200 (sub-pixel), 0x400 (outlier interpolation) and 0x800 (linear
+        sampling of the views' warps); only before the first submit.  Raises ValueError where the library refuses (it returns -1; in error mode 0 it exits like any error)."""
         if int(lib().stm_stream_set_stages(self._h, int(stages))) != 0:
             raise ValueError("stm_stream_set_stages(%#x) refused: %s" % (stages, lib().stm_last_error().decode()))
 
@@ -78,7 +78,7 @@ class FrameStream:
 
 def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
-    stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation)."""
+    stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling)."""
     fs = None
     pending = 0
     for sbs in frames:

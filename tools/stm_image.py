@@ -6,11 +6,14 @@ source, cost slice, aggregated slice, disparity, outliers, occlusion mask, every
 
 usage: stm_image.py <left.bmp> <right.bmp> <ad coeff> <census coeff> <ndisp> <zerodisp> <ucd> <lcd> <usd> <lsd>
                     <num views> <angle> <out width> <out height> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel]
+                    [--linear-warp]
 
 --interp (an addition, off by default): the outlier interpolation (host_api.dr_interp) of both maps after region voting, each on
 its own image and outlier map, before --subpixel.
 --subpixel (an addition, off by default): the sub-pixel enhancement (host_api.dc_subpixel) of both maps on their aggregated
-volumes after region voting, before the bilateral filter."""
+volumes after region voting, before the bilateral filter.
+--linear-warp (an addition, off by default): every view through host_api.dibr_dbm_lin (both warps fetched at the fractional
+coordinate) instead of dibr_dbm."""
 import os
 import sys
 
@@ -21,8 +24,8 @@ sys.path.insert(0, ROOT)
 
 
 def main(argv):
-    subpixel, interp = "--subpixel" in argv, "--interp" in argv
-    argv = [x for x in argv if x not in ("--subpixel", "--interp")]
+    subpixel, interp, linear_warp = "--subpixel" in argv, "--interp" in argv, "--linear-warp" in argv
+    argv = [x for x in argv if x not in ("--subpixel", "--interp", "--linear-warp")]
     if len(argv) not in (17, 18):
         print(__doc__)
         return -1
@@ -62,10 +65,11 @@ def main(argv):
     occl_l, occl_r = api.filter_bleed_1(occl_l, 1), api.filter_bleed_1(occl_r, 1)   # :257-258
     ml, mr = api.dibr_occl_to_mask(occl_l, occl_r)                        # :266
     wr("mask_l", (ml * 255).astype(np.uint8)); wr("mask_r", (mr * 255).astype(np.uint8))
+    dbm = api.dibr_dbm_lin if linear_warp else api.dibr_dbm
     views = [R]                                                           # :268-272: views[0] = right, views[N-1] = left
     for v in range(1, N - 1):
         shift = float(np.float32(1.0 - (1.0 * np.float32(v)) / (np.float32(N) - 1.0)))   # :281
-        views.append(api.dibr_dbm(L, R, dl, dr, occl_l, occl_r, ml, mr, shift))           # :282
+        views.append(dbm(L, R, dl, dr, occl_l, occl_r, ml, mr, shift))                    # :282
     views.append(L)
     for v, img in enumerate(views):
         wr("view_%d" % v, img)

@@ -3,10 +3,11 @@
 side-by-side BMP frames instead of a video file, BMP outputs instead of a window.
 
 usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <num disp> <zero disp> <ad coeff>
-                    <census coeff> <ucd> <lcd> <usd> <lsd> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel]
+                    <census coeff> <ucd> <lcd> <usd> <lsd> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel] [--linear-warp]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
+--linear-warp (an addition, off by default): frame bit 0x800, the views' warps fetched at the fractional coordinate.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -19,7 +20,8 @@ sys.path.insert(0, ROOT)
 
 def main(argv):
     stages = 3 | (0x400 if "--interp" in argv else 0) | (0x200 if "--subpixel" in argv else 0)
-    argv = [x for x in argv if x not in ("--interp", "--subpixel")]
+    stages |= 0x800 if "--linear-warp" in argv else 0
+    argv = [x for x in argv if x not in ("--interp", "--subpixel", "--linear-warp")]
     if len(argv) not in (16, 17):
         print(__doc__)
         return -1
