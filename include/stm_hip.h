@@ -68,7 +68,7 @@ void        stm_release_workspace(void);
 void        stm_prof_enable(int on);
 void        stm_prof_reset(void);
 /* returns number of timed launches of `kernel` ("pq_h","pq_v12","pq_hw","cross_arms","irv","hslo_lr","hslo_rl","hslo_tb",
- * "hslo_bt", "subpixel", "interp", ...) and their
+ * "hslo_bt", "subpixel", "interp", "upsample", ...) and their
  * summed duration in ms; synchronises the recorded events. */
 int         stm_prof_read(const char *kernel, float *total_ms);
 /* aggregation variant of the frame pipeline (0 = default: matrix-pipe kernels, stm_kernels_aggm.hip); decimal digits, used by
@@ -282,7 +282,8 @@ void stm_adcensus_stm(unsigned char *img_sbs, float *disp_l, float *disp_r, unsi
  * OR-ing 0x800 renders the views of stage 3 with the linear sampling of stm_dibr_dbm_lin instead of the truncating fetch; the
  * disparity maps are the same with and without it.  It combines with 0x100, 0x200 and 0x400.  Stages 1 and 2 render nothing:
  * 1 | 0x800 and 2 | 0x800 are errors (stm_last_error), reported before anything is launched.  stm_adcensus_stm and the two
- * adcensus_stm_2 calls keep the truncating fetch. */
+ * adcensus_stm_2 calls keep the truncating fetch.
+ * 0x1000 (guided up-sampling) belongs to the reduced-resolution frame, stm_d_adcensus_stm_2s: here it is an error. */
 void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
                         int num_rows, int num_cols_sbs, int num_cols,
                         int num_rows_out, int num_cols_out, int elem_sz,
@@ -305,6 +306,57 @@ void stm_d_adcensus_stm_2(unsigned char *d_img_sbs, float *d_disp_l, float *d_di
                           int num_views, float angle, int num_disp, int zero_disp,
                           float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
                           int thresh_s, float thresh_h);
+/* The reduced-resolution frame with a `stages` word (an addition: the reference's call has none).  Arguments as the two calls
+ * above plus `stages`, whose low byte must be 3 (this path always renders) and which may carry, with stm_d_adcensus_stm's rules
+ * (0x200 | 0x100 is an error):
+ *   0x100, 0x200, 0x400  HSLO, sub-pixel enhancement, outlier interpolation of the match on the reduced pair;
+ *   0x800                linear sampling of the warps in the full-resolution render;
+ *   0x1000               the guided up-sampling of stm_disp_upsample (sigma_color = 15) in place of the bilinear up-scale: the left
+ *                        map guided by the full-resolution left image against the reduced left image, the right map alike.
+ * Any other value is an error (stm_last_error), reported before anything is launched; the caller's buffers are not touched.
+ * stages == 3 is stm_adcensus_stm_2 / stm_d_adcensus_stm_2 bit for bit.  stm_d_adcensus_stm and stm_stream_set_stages reject
+ * 0x1000: at full resolution nothing is up-scaled. */
+void stm_adcensus_stm_2s(unsigned char *img_sbs, float *disp_l, float *disp_r, unsigned char *interlaced,
+                         int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
+                         int num_rows_disp, int num_cols_disp, int elem_sz, float disp_scale,
+                         int num_views, float angle, int num_disp, int zero_disp,
+                         float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
+                         int thresh_s, float thresh_h, int stages);
+void stm_d_adcensus_stm_2s(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                           int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
+                           int num_rows_disp, int num_cols_disp, int elem_sz, float disp_scale,
+                           int num_views, float angle, int num_disp, int zero_disp,
+                           float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
+                           int thresh_s, float thresh_h, int stages);
+/* Guided disparity up-sampling (joint bilateral upsampling, Kopf et al. 2007; an addition: the reference's tx_disp_scale_kernel
+ * blends four low-resolution values whatever the image shows, which smears every depth edge).  disp_low (f32, in_rows x in_cols)
+ * is the map to scale up, img_low (u8, in_rows x in_cols x elem_sz) the image it was computed on, img (u8, out_rows x out_cols x
+ * elem_sz) the guide; only the first three bytes of a pixel are read; all three are read only.  sigma_color must be > 0.
+ *   tab[s] = (float)exp(-(double)(s * s) / (2.0 * (double)sigma_color * (double)sigma_color)),  s = 0 .. 765  (host, double, rounded once)
+ * Per output pixel (x, y), f32 throughout, one operation per line, no contraction, C fmaxf / fminf / fabsf, correctly rounded
+ * division; W, H = out_cols, out_rows and w, h = in_cols, in_rows:
+ *   xs = ((float)x / (float)W) * (float)w;  xs = fminf(fmaxf(xs, 0), (float)(w - 1))          (tx_disp_scale's own mapping)
+ *   ys = ((float)y / (float)H) * (float)h;  ys = fminf(fmaxf(ys, 0), (float)(h - 1))
+ *   x0 = (int)floorf(xs);  y0 = (int)floorf(ys);  sw = 0;  swd = 0
+ *   for j = -1, 0, 1, 2:  yi = y0 + j;  the row is skipped if yi < 0 or yi >= h
+ *     wy = fmaxf(0, 1 - fabsf(ys - (float)yi) * 0.5f)
+ *     for i = -1, 0, 1, 2:  xi = x0 + i;  the tap is skipped if xi < 0 or xi >= w
+ *       wx  = fmaxf(0, 1 - fabsf(xs - (float)xi) * 0.5f)
+ *       sad = |img[y][x][0] - img_low[yi][xi][0]| + |..[1] - ..[1]| + |..[2] - ..[2]|          (integer, 0 .. 765)
+ *       wgt = (wy * wx) * tab[sad]
+ *       sw  = sw + wgt
+ *       t   = wgt * disp_low[yi][xi]
+ *       swd = swd + t
+ *   bil = what tx_disp_scale computes at (x, y) before its final multiplication (d_tx_scale.cu:8-28, d_alu.cu:17-43)
+ *   out = (sw > 0 ? swd / sw : bil) * up
+ * Taps outside the low-resolution image are skipped, not clamped.  In-image taps always take part, those of weight 0 included:
+ * their 0 * inf is NaN, so non-finite values in disp_low spread as these lines say; sw itself is always finite.  Where no tap
+ * resembles the guide pixel (sw == 0) the pixel is the plain bilinear value.  The 4 x 4 footprint is the same whatever the size
+ * ratio; in_rows >= out_rows is legal.  Parity is against a numpy statement of these lines (parity unpinned). */
+void stm_disp_upsample(float *disp_out, float *disp_low, unsigned char *img_low, unsigned char *img,
+                       int out_rows, int out_cols, int in_rows, int in_cols, int elem_sz, float up, float sigma_color);
+void stm_d_disp_upsample(float *d_disp_out, float *d_disp_low, unsigned char *d_img_low, unsigned char *d_img,
+                         int out_rows, int out_cols, int in_rows, int in_cols, int elem_sz, float up, float sigma_color);
 /* d_tx_scale.h:17-18  d_tx_scale (d_tx_scale.cu:83-121): bilinear image resize; HOST pointers despite the name */
 void stm_d_tx_scale(unsigned char *img_in, unsigned char *img_out, int in_rows, int in_cols, int out_rows, int out_cols,
                     int elem_sz);
@@ -327,7 +379,7 @@ void *stm_stream_create(int num_rows, int num_cols_sbs, int num_cols, int num_ro
  * Returns the frame index, or -1 if both slots are uncollected. */
 long  stm_stream_submit(void *stream, const unsigned char *img_sbs);
 /* the `stages` word of stm_d_adcensus_stm the stream's frames are computed with: 3 (the default), optionally OR-ed with 0x200,
- * 0x400 and / or 0x800 (not 0x100).  Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
+ * 0x400 and / or 0x800 (not 0x100, not 0x1000).  Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
 int   stm_stream_set_stages(void *stream, int stages);
 /* waits for the oldest uncollected frame and copies its results out (NULL = skip).  Returns its index or -1. */
 long  stm_stream_collect(void *stream, float *disp_l, float *disp_r, unsigned char *interlaced);

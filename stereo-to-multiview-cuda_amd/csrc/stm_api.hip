@@ -54,6 +54,12 @@ void fill_g1(float *h, int n, float s, float) { gaussian_kernel_1d(h, n, s); }
 const float *rho_table(float ad, float ce) { return dev_table(0, 0, ad, ce, 768 + 72, fill_rho); } // [0..765] ad, [768..832] census
 const float *gauss2d_table(int r, float s) { return dev_table(1, r, s, 0.f, (size_t)(2 * r + 1) * (2 * r + 1), fill_g2); }
 const float *gauss1d_table(int n, float s) { return dev_table(2, n, s, 0.f, (size_t)(n > 0 ? n : 1), fill_g1); }
+// the colour weights of the guided up-sampler (stm_hip.h): entry s = exp(-s^2 / (2 sigma^2)) in double, rounded once, s = 0 .. 765
+void fill_up(float *h, int, float sigma, float)
+{
+    for (int s = 0; s < 766; ++s) h[s] = (float)exp(-(double)(s * s) / (2.0 * (double)sigma * (double)sigma));
+}
+const float *upsample_table(float sigma_color) { return dev_table(4, 0, sigma_color, 0.f, 768, fill_up); }
 // The radius-7 bilateral filter of a map that holds ONE whole number c in a pixel's whole 15 x 15 neighbourhood: every tap has the
 // weight spatial x colour[0], and the pixel's result is the same sequence of float operations whatever the pixel
 // (d_filter_bilateral.cu:284-300: weight = spatial * colour, norm += weight, res += value * weight, res / norm) -- a function of c
@@ -243,6 +249,20 @@ void core_mux(const u8 *const *d_views, u8 *d_out, int N, float angle, int Hin, 
     launch_mux(d_views, d_out, N, yi, 1.0f / yi, ymod, Hin, Win, Hout, Wout, elem_sz, variant);
 }
 
+// guided up-sampling: the dimension screen, then sigma_color (stm_hip.h)
+bool upsample_args_ok(const char *fn, int out_rows, int out_cols, int in_rows, int in_cols, int elem_sz, float sigma_color)
+{
+    if (!args_ok(fn, {{"out_rows", out_rows, 1}, {"out_cols", out_cols, 1}, {"in_rows", in_rows, 1}, {"in_cols", in_cols, 1},
+                      {"elem_sz", elem_sz, 3}}))
+        return false;
+    if (!(sigma_color > 0.0f)) { // 0, negative, NaN: the table would hold 0 / 0
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: sigma_color = %g, must be > 0", fn, (double)sigma_color);
+        fail(msg, "sigma_color", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
 } // namespace
 
 extern "C" {
@@ -657,6 +677,33 @@ void stm_dibr_dfm(unsigned char *img_out, unsigned char *img_in_l, unsigned char
     sync();
 }
 
+// =============================================================== guided disparity up-sampling
+// (an addition, the reference has none: its tx_disp_scale_kernel blends four low-resolution values whatever the image shows)
+void stm_d_disp_upsample(float *d_disp_out, float *d_disp_low, unsigned char *d_img_low, unsigned char *d_img, int out_rows,
+                         int out_cols, int in_rows, int in_cols, int elem_sz, float up, float sigma_color)
+{
+    if (!upsample_args_ok("d_disp_upsample", out_rows, out_cols, in_rows, in_cols, elem_sz, sigma_color)) return;
+    float *o[1] = {d_disp_out};
+    const float *dl[1] = {d_disp_low};
+    const u8 *il[1] = {d_img_low}, *im[1] = {d_img};
+    launch_disp_upsample(1, o, dl, il, im, upsample_table(sigma_color), out_rows, out_cols, in_rows, in_cols, elem_sz, up);
+}
+void stm_disp_upsample(float *disp_out, float *disp_low, unsigned char *img_low, unsigned char *img, int out_rows, int out_cols,
+                       int in_rows, int in_cols, int elem_sz, float up_factor, float sigma_color)
+{
+    if (!upsample_args_ok("disp_upsample", out_rows, out_cols, in_rows, in_cols, elem_sz, sigma_color)) return;
+    const size_t HW = (size_t)out_rows * out_cols, hw = (size_t)in_rows * in_cols;
+    Workspace::begin((4 + (size_t)elem_sz) * (HW + hw) + 8192);
+    float *dl = up(disp_low, hw), *o = Workspace::get<float>(HW);
+    u8 *il = up(img_low, hw * elem_sz), *im = up(img, HW * elem_sz);
+    float *ov[1] = {o};
+    const float *dv[1] = {dl};
+    const u8 *ilv[1] = {il}, *imv[1] = {im};
+    launch_disp_upsample(1, ov, dv, ilv, imv, upsample_table(sigma_color), out_rows, out_cols, in_rows, in_cols, elem_sz, up_factor);
+    down(disp_out, o, HW);
+    sync();
+}
+
 // =============================================================== mux
 void stm_d_mux_multiview(unsigned char **d_views, unsigned char *d_out_data, int num_views, float angle, int in_rows,
                          int in_cols, int out_rows, int out_cols, int elem_sz)
@@ -941,6 +988,11 @@ void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp
         fail("d_adcensus_stm: stages 0x800 (linear sampling of the warps) needs the rendering stage (3)", "stages", __FILE__, __LINE__);
         return;
     }
+    if (stages & 0x1000) { // guided up-sampling belongs to the reduced-resolution frame: here nothing is up-scaled
+        fail("d_adcensus_stm: stages 0x1000 (guided disparity up-sampling) needs the reduced-resolution frame (d_adcensus_stm_2s)", "stages",
+             __FILE__, __LINE__);
+        return;
+    }
     const int H = num_rows, W = num_cols, N = num_views;
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
     const size_t V = pq_volume_floats(num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
@@ -972,22 +1024,48 @@ void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp
 // adcensus_stm_2, d_io.cu:240-508: the disparity is computed on a bilinearly reduced pair
 // (num_rows_disp x num_cols_disp, tx_scale_bilinear_kernel :302-304), scaled back up with
 // tx_disp_scale_kernel(1/disp_scale) (:415-417), then the views are rendered at full resolution.
-void stm_d_adcensus_stm_2(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
-                          int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
-                          int num_rows_disp, int num_cols_disp, int elem_sz, float disp_scale, int num_views, float angle,
-                          int num_disp, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd,
-                          int lsd, int thresh_s, float thresh_h)
+// The two _2s calls add the `stages` word (stm_hip.h); the two reference calls are the same bodies with stages = 3.
+} // extern "C"
+namespace {
+
+bool reduced_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int num_rows_disp,
+                     int num_cols_disp, int elem_sz, int num_views, int num_disp, int stages)
 {
-    if (!args_ok("d_adcensus_stm_2", {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1},
-                                      {"num_cols", num_cols, 1}, {"num_rows_out", num_rows_out, 1},
-                                      {"num_cols_out", num_cols_out, 1}, {"num_rows_disp", num_rows_disp, 1},
-                                      {"num_cols_disp", num_cols_disp, 1}, {"elem_sz", elem_sz, 3},
-                                      {"num_views", num_views, 2}, {"num_disp", num_disp, 1}}))
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols", num_cols, 1},
+                      {"num_rows_out", num_rows_out, 1}, {"num_cols_out", num_cols_out, 1}, {"num_rows_disp", num_rows_disp, 1},
+                      {"num_cols_disp", num_cols_disp, 1}, {"elem_sz", elem_sz, 3}, {"num_views", num_views, 2},
+                      {"num_disp", num_disp, 1}}))
+        return false;
+    char msg[200];
+    if ((stages & 0xff) != 3 || (stages & ~0x1fff)) { // this path always renders
+        snprintf(msg, sizeof msg, "%s: stages = 0x%x, must be 3, optionally OR-ed with 0x100, 0x200, 0x400, 0x800 and 0x1000", fn, stages);
+        fail(msg, "stages", __FILE__, __LINE__);
+        return false;
+    }
+    if ((stages & 0x300) == 0x300) { // as d_adcensus_stm
+        snprintf(msg, sizeof msg, "%s: stages 0x200 (sub-pixel) together with 0x100 (HSLO) is not supported", fn);
+        fail(msg, "stages", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
+
+void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                          int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int num_rows_disp,
+                          int num_cols_disp, int elem_sz, float disp_scale, int num_views, float angle, int num_disp, int zero_disp,
+                          float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h,
+                          int stages)
+{
+    if (!reduced_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp, num_cols_disp, elem_sz,
+                         num_views, num_disp, stages))
         return;
     const int H = num_rows, W = num_cols, h = num_rows_disp, w = num_cols_disp, N = num_views;
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz, hw = (size_t)h * w;
     const size_t V = pq_volume_floats(num_disp, h, w);
-    Workspace::begin(4 * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 8 * hw + (1u << 20));
+    const bool hslo = (stages & 0x100) != 0, subpix = (stages & 0x200) != 0, interp = (stages & 0x400) != 0; // on the reduced pair
+    const bool linwarp = (stages & 0x800) != 0;                                                             // in the full-size render
+    const bool guided = (stages & 0x1000) != 0; // the up-scale between the two: stm_disp_upsample instead of tx_disp_scale
+    Workspace::begin((hslo ? 13 : 4) * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 8 * hw + (1u << 20)); // HSLO: as d_adcensus_stm
     u8 *img_l = Workspace::get<u8>(IMG), *img_r = Workspace::get<u8>(IMG);
     launch_demux_sbs(img_l, img_r, d_img_sbs, H, num_cols_sbs, W, elem_sz);
     u8 *low_l = Workspace::get<u8>(hw * elem_sz), *low_r = Workspace::get<u8>(hw * elem_sz);
@@ -996,24 +1074,27 @@ void stm_d_adcensus_stm_2(unsigned char *d_img_sbs, float *d_disp_l, float *d_di
     float *low_dl = Workspace::get<float>(hw), *low_dr = Workspace::get<float>(hw);
     Arms al, ar;
     frame_disparity(low_l, low_r, low_dl, low_dr, al, ar, h, w, elem_sz, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd,
-                    usd, lsd, thresh_s, thresh_h, true);
+                    usd, lsd, thresh_s, thresh_h, true, hslo, nullptr, subpix, interp);
     const float up = 1.0f / disp_scale; // :415
-    launch_disp_scale(d_disp_l, low_dl, H, W, h, w, up);
-    launch_disp_scale(d_disp_r, low_dr, H, W, h, w, up);
-    frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle);
+    if (guided) { // each map guided by its own view: the full-size image the views are rendered from against the image the match ran on
+        float *o[2] = {d_disp_l, d_disp_r};
+        const float *dl[2] = {low_dl, low_dr};
+        const u8 *il[2] = {low_l, low_r}, *im[2] = {img_l, img_r};
+        launch_disp_upsample(2, o, dl, il, im, upsample_table(15.0f), H, W, h, w, elem_sz, up);
+    } else {
+        launch_disp_scale(d_disp_l, low_dl, H, W, h, w, up);
+        launch_disp_scale(d_disp_r, low_dr, H, W, h, w, up);
+    }
+    frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle, linwarp);
 }
 
-void stm_adcensus_stm_2(unsigned char *img_sbs, float *disp_l, float *disp_r, unsigned char *interlaced, int num_rows,
-                        int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int num_rows_disp,
-                        int num_cols_disp, int elem_sz, float disp_scale, int num_views, float angle, int num_disp,
-                        int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
-                        int thresh_s, float thresh_h)
+void reduced_frame_host(const char *fn, unsigned char *img_sbs, float *disp_l, float *disp_r, unsigned char *interlaced, int num_rows,
+                        int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int num_rows_disp, int num_cols_disp,
+                        int elem_sz, float disp_scale, int num_views, float angle, int num_disp, int zero_disp, float ad_coeff,
+                        float census_coeff, float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages)
 {
-    if (!args_ok("adcensus_stm_2", {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1},
-                                    {"num_cols", num_cols, 1}, {"num_rows_out", num_rows_out, 1},
-                                    {"num_cols_out", num_cols_out, 1}, {"num_rows_disp", num_rows_disp, 1},
-                                    {"num_cols_disp", num_cols_disp, 1}, {"elem_sz", elem_sz, 3},
-                                    {"num_views", num_views, 2}, {"num_disp", num_disp, 1}}))
+    if (!reduced_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp, num_cols_disp, elem_sz,
+                         num_views, num_disp, stages))
         return;
     size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
     size_t out_sz = (size_t)num_rows_out * num_cols_out * elem_sz;
@@ -1025,11 +1106,56 @@ void stm_adcensus_stm_2(unsigned char *img_sbs, float *disp_l, float *disp_r, un
     STM_CHECK(hipMemcpyAsync(d_sbs, img_sbs, sbs_sz, hipMemcpyHostToDevice, stream()));
     STM_CHECK(hipMemsetAsync(d_out, 0, out_sz, stream()));
     ApiNest nest; // the device flavour must not forget a failed upload
-    stm_d_adcensus_stm_2(d_sbs, d_dl, d_dr, d_out, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp,
-                         num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff, ucd,
-                         lcd, usd, lsd, thresh_s, thresh_h);
+    reduced_frame_device(fn, d_sbs, d_dl, d_dr, d_out, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp,
+                         num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd,
+                         usd, lsd, thresh_s, thresh_h, stages);
     down(disp_l, d_dl, HW); down(disp_r, d_dr, HW); down(interlaced, d_out, out_sz);
     sync();
+}
+
+} // namespace
+extern "C" {
+
+void stm_d_adcensus_stm_2(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                          int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
+                          int num_rows_disp, int num_cols_disp, int elem_sz, float disp_scale, int num_views, float angle,
+                          int num_disp, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd,
+                          int lsd, int thresh_s, float thresh_h)
+{
+    reduced_frame_device("d_adcensus_stm_2", d_img_sbs, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out,
+                         num_cols_out, num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp,
+                         ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, 3);
+}
+void stm_d_adcensus_stm_2s(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                           int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
+                           int num_rows_disp, int num_cols_disp, int elem_sz, float disp_scale, int num_views, float angle,
+                           int num_disp, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd,
+                           int lsd, int thresh_s, float thresh_h, int stages)
+{
+    reduced_frame_device("d_adcensus_stm_2s", d_img_sbs, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out,
+                         num_cols_out, num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp,
+                         ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages);
+}
+
+void stm_adcensus_stm_2(unsigned char *img_sbs, float *disp_l, float *disp_r, unsigned char *interlaced, int num_rows,
+                        int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int num_rows_disp,
+                        int num_cols_disp, int elem_sz, float disp_scale, int num_views, float angle, int num_disp,
+                        int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
+                        int thresh_s, float thresh_h)
+{
+    reduced_frame_host("adcensus_stm_2", img_sbs, disp_l, disp_r, interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out,
+                       num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp, ad_coeff,
+                       census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, 3);
+}
+void stm_adcensus_stm_2s(unsigned char *img_sbs, float *disp_l, float *disp_r, unsigned char *interlaced, int num_rows,
+                         int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int num_rows_disp,
+                         int num_cols_disp, int elem_sz, float disp_scale, int num_views, float angle, int num_disp,
+                         int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
+                         int thresh_s, float thresh_h, int stages)
+{
+    reduced_frame_host("adcensus_stm_2s", img_sbs, disp_l, disp_r, interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out,
+                       num_cols_out, num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp, ad_coeff,
+                       census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages);
 }
 
 // d_tx_scale.h:17-18  d_tx_scale (d_tx_scale.cu:83-121): despite the d_ prefix it takes HOST pointers

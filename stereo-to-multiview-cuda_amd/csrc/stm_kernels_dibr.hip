@@ -449,6 +449,7 @@ __global__ __launch_bounds__(256) void stm_k_disp_scale(float *__restrict__ out,
 }
 void launch_disp_scale(float *out, const float *in, int out_rows, int out_cols, int in_rows, int in_cols, float disp_scale)
 {
+    ProfScope p("disp_scale");
     STM_LAUNCH(stm_k_disp_scale, dim3(cdiv(out_cols, 256), out_rows), dim3(256), 0, stream(), out, in, out_rows, out_cols,
                        in_rows, in_cols, disp_scale);
     STM_CHECK_LAUNCH();

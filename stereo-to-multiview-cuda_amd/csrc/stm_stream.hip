@@ -99,6 +99,10 @@ int stm_stream_set_stages(void *h, int stages)
 {
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
+    if (stages & 0x1000) { // the stream runs the full-resolution frame: nothing is up-scaled
+        stm::fail("stream_set_stages: stages 0x1000 (guided disparity up-sampling) needs the reduced-resolution frame", "stages", __FILE__, __LINE__);
+        return -1;
+    }
     if ((stages & ~0xe00) != 3) {
         stm::fail("stream_set_stages: stages must be 3, optionally OR-ed with 0x200, 0x400 and 0x800", "stages", __FILE__, __LINE__);
         return -1;

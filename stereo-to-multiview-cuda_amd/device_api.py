@@ -24,6 +24,8 @@ STAGE_SUBPIXEL = 0x200
 STAGE_INTERP = 0x400
 # ... the views of stage 3 rendered at the fractional warp coordinate (stm_dibr_dbm_lin; stage 3 only, combines with every other bit)
 STAGE_LINEAR_WARP = 0x800
+# d_adcensus_stm_2s only: the disparity maps scaled up by the guided up-sampler (stm_disp_upsample) instead of the bilinear blend
+STAGE_GUIDED_UP = 0x1000
 
 
 class FrameParams:
@@ -52,6 +54,21 @@ def d_adcensus_stm(sbs, disp_l, disp_r, interlaced, p, stages=3):
     lib().stm_d_adcensus_stm(_p(sbs), _p(disp_l), _p(disp_r), _p(interlaced), H, Wsbs, W, Ho, Wo, E,
                              p.num_views, p.angle, p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff,
                              p.ucd, p.lcd, p.usd, p.lsd, p.thresh_s, p.thresh_h, stages)
+
+
+def d_adcensus_stm_2s(sbs, disp_l, disp_r, interlaced, p, disp_rows, disp_cols, disp_scale, stages=3):
+    """stm_d_adcensus_stm_2s: the reduced-resolution frame (match at disp_rows x disp_cols, maps scaled up by 1 / disp_scale,
+    views rendered at full size) with a `stages` word: 3, optionally OR-ed with 0x100, STAGE_SUBPIXEL, STAGE_INTERP (on the
+    reduced pair), STAGE_LINEAR_WARP (the render) and STAGE_GUIDED_UP (the up-scale).  stages = 3 is stm_d_adcensus_stm_2."""
+    assert sbs.is_cuda and sbs.dtype == torch.uint8 and sbs.is_contiguous()
+    H, Wsbs, E = sbs.shape
+    W = Wsbs // 2
+    assert disp_l.shape == (H, W) and disp_r.shape == (H, W) and disp_l.dtype == torch.float32
+    Ho, Wo = interlaced.shape[0], interlaced.shape[1]
+    _use_current_stream()
+    lib().stm_d_adcensus_stm_2s(_p(sbs), _p(disp_l), _p(disp_r), _p(interlaced), H, Wsbs, W, Ho, Wo, disp_rows, disp_cols, E,
+                                disp_scale, p.num_views, p.angle, p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff,
+                                p.ucd, p.lcd, p.usd, p.lsd, p.thresh_s, p.thresh_h, stages)
 
 
 def plane_table(slab):
@@ -124,6 +141,22 @@ def d_dibr_dbm_lin(out, img_l, img_r, disp_l, disp_r, mask_l, mask_r, shift):
     _use_current_stream()
     lib().stm_d_dibr_dbm_lin(_p(out), _p(img_l), _p(img_r), _p(disp_l), _p(disp_r), None, None, _p(mask_l), _p(mask_r),
                              float(shift), H, W, E)
+
+
+def d_disp_upsample(out, disp_low, img_low, img, up, sigma_color=15.0):
+    """stm_d_disp_upsample: out float32 [H][W] on the GPU from the low-resolution map disp_low float32 [h][w], the image it was
+    computed on (img_low uint8 [h][w][E]) and the guide image img uint8 [H][W][E]; the values are multiplied by `up`.  Only out
+    is written."""
+    H, W = out.shape
+    h, w = disp_low.shape
+    for t in (out, disp_low):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    E = img.shape[2]
+    assert img.shape == (H, W, E) and img_low.shape == (h, w, E)
+    for t in (img, img_low):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    _use_current_stream()
+    lib().stm_d_disp_upsample(_p(out), _p(disp_low), _p(img_low), _p(img), H, W, h, w, E, float(up), float(sigma_color))
 
 
 def prof_enable(on=True):

@@ -266,6 +266,36 @@ def adcensus_stm_2(img_sbs, num_cols, out_rows, out_cols, disp_rows, disp_cols, 
     return dl, dr, out
 
 
+def adcensus_stm_2s(img_sbs, num_cols, out_rows, out_cols, disp_rows, disp_cols, disp_scale, num_views, angle, num_disp,
+                    zero_disp, ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages=3):
+    """adcensus_stm_2 with a `stages` word (stm_adcensus_stm_2s): 3, optionally OR-ed with 0x100, 0x200, 0x400 (the match on the
+    reduced pair), 0x800 (linear sampling in the render) and 0x1000 (guided up-sampling of the maps).  stages = 3 is adcensus_stm_2."""
+    img_sbs, ps = _u8(img_sbs)
+    H, Wsbs, E = img_sbs.shape
+    dl = np.zeros((H, num_cols), np.float32)
+    dr = np.zeros((H, num_cols), np.float32)
+    out = np.zeros((out_rows, out_cols, E), np.uint8)
+    lib().stm_adcensus_stm_2s(ps, dl.ctypes.data_as(f32p), dr.ctypes.data_as(f32p), out.ctypes.data_as(u8p),
+                              H, Wsbs, num_cols, out_rows, out_cols, disp_rows, disp_cols, E, disp_scale, num_views, angle,
+                              num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages)
+    return dl, dr, out
+
+
+def disp_upsample(disp_low, img_low, img, up, sigma_color=15.0):
+    """Guided disparity up-sampling (stm_disp_upsample; an addition, the reference scales its maps up bilinearly): the map
+    disp_low [h][w], computed on img_low [h][w][E], brought to the size of the guide image img [H][W][E], every tap weighted by
+    its colour similarity to the guide pixel; values multiplied by `up`.  Returns the [H][W] map; nothing passed in is modified."""
+    disp_low, pd = _f32(disp_low)
+    img_low, pl = _u8(img_low)
+    img, pi = _u8(img)
+    h, w = disp_low.shape
+    H, W, E = img.shape
+    assert img_low.shape == (h, w, E)
+    out = np.zeros((H, W), np.float32)
+    lib().stm_disp_upsample(out.ctypes.data_as(f32p), pd, pl, pi, H, W, h, w, E, float(up), float(sigma_color))
+    return out
+
+
 def tx_scale(img, out_rows, out_cols):
     """d_tx_scale.h:17-18 (bilinear resize)."""
     img, pi = _u8(img)
