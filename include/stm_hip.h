@@ -68,7 +68,7 @@ void        stm_release_workspace(void);
 void        stm_prof_enable(int on);
 void        stm_prof_reset(void);
 /* returns number of timed launches of `kernel` ("pq_h","pq_v12","pq_hw","cross_arms","irv","hslo_lr","hslo_rl","hslo_tb",
- * "hslo_bt", "subpixel", "interp", "upsample", ...) and their
+ * "hslo_bt", "subpixel", "interp", "upsample", "temporal", ...) and their
  * summed duration in ms; synchronises the recorded events. */
 int         stm_prof_read(const char *kernel, float *total_ms);
 /* aggregation variant of the frame pipeline (0 = default: matrix-pipe kernels, stm_kernels_aggm.hip); decimal digits, used by
@@ -283,13 +283,37 @@ void stm_adcensus_stm(unsigned char *img_sbs, float *disp_l, float *disp_r, unsi
  * disparity maps are the same with and without it.  It combines with 0x100, 0x200 and 0x400.  Stages 1 and 2 render nothing:
  * 1 | 0x800 and 2 | 0x800 are errors (stm_last_error), reported before anything is launched.  stm_adcensus_stm and the two
  * adcensus_stm_2 calls keep the truncating fetch.
- * 0x1000 (guided up-sampling) belongs to the reduced-resolution frame, stm_d_adcensus_stm_2s: here it is an error. */
+ * 0x1000 (guided up-sampling) belongs to the reduced-resolution frame, stm_d_adcensus_stm_2s: here it is an error.
+ * 0x2000 (temporal stabilisation) needs the previous frame, which this call has no arguments for: here, and in the two _2s
+ * calls, it is an error; stm_d_adcensus_stm_t takes it. */
 void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
                         int num_rows, int num_cols_sbs, int num_cols,
                         int num_rows_out, int num_cols_out, int elem_sz,
                         int num_views, float angle, int num_disp, int zero_disp,
                         float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
                         int thresh_s, float thresh_h, int stages);
+/* The device-resident frame of a frame sequence (an addition): stm_d_adcensus_stm's arguments and rules plus the history of the
+ * temporal stabilisation, stage bit 0x2000: d_prev_img_sbs, the previous frame's side-by-side input (same geometry as
+ * d_img_sbs), d_prev_disp_l / d_prev_disp_r, the two maps the previous frame put out (its stabilised result), and
+ * stm_disp_temporal's three parameters.  With the bit set and all three history pointers non-null, stm_disp_temporal runs on
+ * d_disp_l and d_disp_r in place after the bilateral filter and before the renderer, each view on its own half of the two
+ * side-by-side buffers (a view's 3 x 3 neighbourhood is clipped to its own half): stages 2 | 0x2000 returns the stabilised maps,
+ * 3 | 0x2000 renders from them.  The bit combines with 0x100, 0x200, 0x400 and 0x800.  With the bit set and all three pointers
+ * null (the first frame of a sequence) nothing extra is launched: the call is stm_d_adcensus_stm without the bit, bit for bit.
+ * Without the bit the history arguments are ignored.  Errors (stm_last_error), all reported before anything is launched: some
+ * history pointers null and some not; a low byte of `stages` below 2; num_cols_sbs < 2 * num_cols; a history map that overlaps
+ * d_disp_l or d_disp_r; alpha, thresh_color or thresh_disp outside stm_disp_temporal's rules (checked whenever the bit is set).
+ * The defaults a frame sequence uses (stm_stream_set_temporal): alpha = 0.5, thresh_color = 24, thresh_disp = 1.5.  Why 24:
+ * sensor noise of +-2 per channel and frame gives |delta| <= 4 per channel, so sad <= 12: a static noisy pixel stays inside
+ * the gate with a factor of two to spare. */
+void stm_d_adcensus_stm_t(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                          int num_rows, int num_cols_sbs, int num_cols,
+                          int num_rows_out, int num_cols_out, int elem_sz,
+                          int num_views, float angle, int num_disp, int zero_disp,
+                          float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
+                          int thresh_s, float thresh_h, int stages,
+                          unsigned char *d_prev_img_sbs, float *d_prev_disp_l, float *d_prev_disp_r,
+                          float alpha, int thresh_color, float thresh_disp);
 
 /* Reduced-resolution disparity: d_io.h:42-52 adcensus_stm_2 (d_io.cu:240-508).  The pair is
  * bilinearly reduced to num_rows_disp x num_cols_disp, matched there, and the disparity maps are scaled back up
@@ -357,6 +381,31 @@ void stm_disp_upsample(float *disp_out, float *disp_low, unsigned char *img_low,
                        int out_rows, int out_cols, int in_rows, int in_cols, int elem_sz, float up, float sigma_color);
 void stm_d_disp_upsample(float *d_disp_out, float *d_disp_low, unsigned char *d_img_low, unsigned char *d_img,
                          int out_rows, int out_cols, int in_rows, int in_cols, int elem_sz, float up, float sigma_color);
+/* Temporal disparity stabilisation (an addition: the reference matches every frame of its video loop on its own, so on noisy
+ * footage the maps, and with 0x200 / 0x800 the views, shimmer where nothing moves).  A motion-adaptive recursive filter on the
+ * final maps, gated by how much the colour changed between two consecutive frames.  Inputs for one view:
+ *   disp (cur)      f32 H x W: this frame's filtered map.  It is rewritten in place.
+ *   disp_prev (prev) f32 H x W: the map that the previous frame output, which is that frame's filtered result.
+ *   img, img_prev   u8 H x W x E, dense: the view's image in this frame and the previous one.  Only the first three bytes of a
+ *                   pixel are read.  E = elem_sz >= 3.
+ *   alpha           f32, the weight given to the history;  thresh_color  int;  thresh_disp  f32.
+ *
+ *   sad(q) = |img[q][0]-img_prev[q][0]| + |..[1]-..[1]| + |..[2]-..[2]|        (integer, 0..765)
+ *   m(p)   = max of sad(q) over q = (x+i, y+j), i, j in {-1,0,1}, q inside the H x W image (clipped, not clamped)
+ *   c = cur[p];  q = prev[p]
+ *   t  = q - c
+ *   df = fabsf(t)
+ *   if (m(p) <= thresh_color && df <= thresh_disp) { u = alpha * t;  out = c + u; }   else out = c
+ *
+ * All arithmetic is f32, one operation per line, with no contraction.  A NaN in c or q makes the comparison false, so out = c.
+ * An infinity behaves exactly as the lines say; with thresh_disp = +inf an infinite t passes the gate.
+ * Argument rules: 0 <= alpha <= 1, 0 <= thresh_color <= 765, and thresh_disp >= 0 with +inf allowed.  Anything else, NaN
+ * included, fails through stm_last_error before anything is launched or written.  prev must not alias cur (an error as well).
+ * Parity is against a numpy statement of these lines (parity unpinned). */
+void stm_disp_temporal(float *disp, float *disp_prev, unsigned char *img, unsigned char *img_prev, int num_rows, int num_cols,
+                       int elem_sz, float alpha, int thresh_color, float thresh_disp);
+void stm_d_disp_temporal(float *d_disp, float *d_disp_prev, unsigned char *d_img, unsigned char *d_img_prev, int num_rows, int num_cols,
+                         int elem_sz, float alpha, int thresh_color, float thresh_disp);
 /* d_tx_scale.h:17-18  d_tx_scale (d_tx_scale.cu:83-121): bilinear image resize; HOST pointers despite the name */
 void stm_d_tx_scale(unsigned char *img_in, unsigned char *img_out, int in_rows, int in_cols, int out_rows, int out_cols,
                     int elem_sz);
@@ -378,9 +427,15 @@ void *stm_stream_create(int num_rows, int num_cols_sbs, int num_cols, int num_ro
 /* stages the next frame (the caller's buffer is reusable on return); at most two frames in flight.
  * Returns the frame index, or -1 if both slots are uncollected. */
 long  stm_stream_submit(void *stream, const unsigned char *img_sbs);
-/* the `stages` word of stm_d_adcensus_stm the stream's frames are computed with: 3 (the default), optionally OR-ed with 0x200,
- * 0x400 and / or 0x800 (not 0x100, not 0x1000).  Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
+/* the `stages` word the stream's frames are computed with: 3 (the default), optionally OR-ed with 0x200, 0x400, 0x800 and / or
+ * 0x2000 (not 0x100, not 0x1000).  With 0x2000 every frame but the first is an stm_d_adcensus_stm_t call whose history is the
+ * frame before it (its input and its stabilised maps, which stay in the stream's other buffer slot); the two frames in flight
+ * then run one after the other on the GPU, while upload and download still overlap.  A history reset at a scene cut is not
+ * offered: the colour gate refuses to blend across one.  Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
 int   stm_stream_set_stages(void *stream, int stages);
+/* the parameters of the temporal step of a stream whose stages carry 0x2000 (stm_disp_temporal's rules; defaults 0.5, 24, 1.5).
+ * Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
+int   stm_stream_set_temporal(void *stream, float alpha, int thresh_color, float thresh_disp);
 /* waits for the oldest uncollected frame and copies its results out (NULL = skip).  Returns its index or -1. */
 long  stm_stream_collect(void *stream, float *disp_l, float *disp_r, unsigned char *interlaced);
 /* zero-copy variants (at 1080p the two host copies of submit / collect take longer than the frame does on the GPU):

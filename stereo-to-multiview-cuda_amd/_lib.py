@@ -73,16 +73,20 @@ PROTOS = {
     "stm_d_demux_sbs": ([vp, vp, vp, i, i, i, i], None),
     "stm_adcensus_stm": ([u8p, f32p, f32p, u8p, i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f], None),
     "stm_d_adcensus_stm": ([vp, vp, vp, vp, i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f, i], None),
+    "stm_d_adcensus_stm_t": ([vp, vp, vp, vp, i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f, i, vp, vp, vp, f, i, f], None),
     "stm_adcensus_stm_2": ([u8p, f32p, f32p, u8p, i, i, i, i, i, i, i, i, f, i, f, i, i, f, f, f, f, i, i, i, f], None),
     "stm_d_adcensus_stm_2": ([vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, f, i, i, f, f, f, f, i, i, i, f], None),
     "stm_adcensus_stm_2s": ([u8p, f32p, f32p, u8p, i, i, i, i, i, i, i, i, f, i, f, i, i, f, f, f, f, i, i, i, f, i], None),
     "stm_d_adcensus_stm_2s": ([vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, f, i, i, f, f, f, f, i, i, i, f, i], None),
     "stm_disp_upsample": ([f32p, f32p, u8p, u8p, i, i, i, i, i, f, f], None),
     "stm_d_disp_upsample": ([vp, vp, vp, vp, i, i, i, i, i, f, f], None),
+    "stm_disp_temporal": ([f32p, f32p, u8p, u8p, i, i, i, f, i, f], None),
+    "stm_d_disp_temporal": ([vp, vp, vp, vp, i, i, i, f, i, f], None),
     "stm_d_tx_scale": ([u8p, u8p, i, i, i, i, i], None),
     "stm_stream_create": ([i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f], C.c_void_p),
     "stm_stream_submit": ([C.c_void_p, u8p], C.c_long),
     "stm_stream_set_stages": ([C.c_void_p, i], i),
+    "stm_stream_set_temporal": ([C.c_void_p, f, i, f], i),
     "stm_stream_collect": ([C.c_void_p, f32p, f32p, u8p], C.c_long),
     "stm_stream_input_buffer": ([C.c_void_p], C.c_void_p),
     "stm_stream_collect_view": ([C.c_void_p, C.POINTER(f32p), C.POINTER(f32p), C.POINTER(u8p)], C.c_long),

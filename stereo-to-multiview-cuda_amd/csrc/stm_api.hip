@@ -263,6 +263,47 @@ bool upsample_args_ok(const char *fn, int out_rows, int out_cols, int in_rows, i
     }
     return true;
 }
+// the three parameters of the temporal stabilisation (stm_hip.h): 0 <= alpha <= 1, 0 <= thresh_color <= 765, thresh_disp >= 0
+// (+inf allowed); a NaN fails every one of these comparisons
+bool temporal_params_ok(const char *fn, float alpha, int thresh_color, float thresh_disp)
+{
+    char msg[160];
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) {
+        snprintf(msg, sizeof msg, "%s: alpha = %g, must be in [0, 1]", fn, (double)alpha);
+        fail(msg, "alpha", __FILE__, __LINE__);
+        return false;
+    }
+    if (thresh_color < 0 || thresh_color > 765) {
+        snprintf(msg, sizeof msg, "%s: thresh_color = %d, must be in [0, 765]", fn, thresh_color);
+        fail(msg, "thresh_color", __FILE__, __LINE__);
+        return false;
+    }
+    if (!(thresh_disp >= 0.0f)) {
+        snprintf(msg, sizeof msg, "%s: thresh_disp = %g, must be >= 0", fn, (double)thresh_disp);
+        fail(msg, "thresh_disp", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
+// two maps of n floats each share at least one element
+bool maps_overlap(const float *a, const float *b, size_t n)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b, bytes = n * sizeof(float);
+    return pa < pb + bytes && pb < pa + bytes;
+}
+bool temporal_args_ok(const char *fn, const float *disp, const float *disp_prev, int num_rows, int num_cols, int elem_sz, float alpha,
+                      int thresh_color, float thresh_disp)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
+    if (!temporal_params_ok(fn, alpha, thresh_color, thresh_disp)) return false;
+    if (disp && disp_prev && maps_overlap(disp, disp_prev, (size_t)num_rows * num_cols)) { // the map is rewritten in place
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: disp_prev must not alias disp", fn);
+        fail(msg, "disp_prev", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
 } // namespace
 
 extern "C" {
@@ -704,6 +745,35 @@ void stm_disp_upsample(float *disp_out, float *disp_low, unsigned char *img_low,
     sync();
 }
 
+// =============================================================== temporal disparity stabilisation
+// (an addition, the reference has none: its video loop matches every frame on its own)
+void stm_d_disp_temporal(float *d_disp, float *d_disp_prev, unsigned char *d_img, unsigned char *d_img_prev, int num_rows, int num_cols,
+                         int elem_sz, float alpha, int thresh_color, float thresh_disp)
+{
+    if (!temporal_args_ok("d_disp_temporal", d_disp, d_disp_prev, num_rows, num_cols, elem_sz, alpha, thresh_color, thresh_disp)) return;
+    float *c[1] = {d_disp};
+    const float *q[1] = {d_disp_prev};
+    const u8 *im[1] = {d_img}, *ip[1] = {d_img_prev};
+    const size_t off[1] = {0};
+    launch_disp_temporal(1, c, q, im, ip, off, num_rows, num_cols, num_cols, elem_sz, alpha, thresh_color, thresh_disp);
+}
+void stm_disp_temporal(float *disp, float *disp_prev, unsigned char *img, unsigned char *img_prev, int num_rows, int num_cols,
+                       int elem_sz, float alpha, int thresh_color, float thresh_disp)
+{
+    if (!temporal_args_ok("disp_temporal", disp, disp_prev, num_rows, num_cols, elem_sz, alpha, thresh_color, thresh_disp)) return;
+    const size_t HW = (size_t)num_rows * num_cols;
+    Workspace::begin(2 * (4 + (size_t)elem_sz) * HW + 8192);
+    float *c = up(disp, HW), *q = up(disp_prev, HW);
+    u8 *im = up(img, HW * elem_sz), *ip = up(img_prev, HW * elem_sz);
+    float *cv[1] = {c};
+    const float *qv[1] = {q};
+    const u8 *imv[1] = {im}, *ipv[1] = {ip};
+    const size_t off[1] = {0};
+    launch_disp_temporal(1, cv, qv, imv, ipv, off, num_rows, num_cols, num_cols, elem_sz, alpha, thresh_color, thresh_disp);
+    down(disp, c, HW);
+    sync();
+}
+
 // =============================================================== mux
 void stm_d_mux_multiview(unsigned char **d_views, unsigned char *d_out_data, int num_views, float angle, int in_rows,
                          int in_cols, int out_rows, int out_cols, int elem_sz)
@@ -962,35 +1032,42 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
     core_mux((const u8 *const *)dv, d_interlaced, N, angle, H, W, Hout, Wout, elem_sz, 2); // :203
 }
 
-} // namespace
+// the history of the temporal stabilisation (stages bit 0x2000, stm_d_adcensus_stm_t): the previous frame's side-by-side input and
+// the two maps it put out
+struct TemporalHist {
+    const u8 *sbs;
+    const float *disp_l, *disp_r;
+    float alpha;
+    int thresh_color;
+    float thresh_disp;
+};
 
-extern "C" {
-
-void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
-                        int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz,
-                        int num_views, float angle, int num_disp, int zero_disp, float ad_coeff, float census_coeff,
-                        float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages)
+// the body of stm_d_adcensus_stm and stm_d_adcensus_stm_t; hist != nullptr: the temporal step between the bilateral filter and
+// the renderer.  Every argument has been screened by the caller except the `stages` rules the two calls share.
+void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced, int num_rows,
+                  int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz, int num_views, float angle,
+                  int num_disp, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd, int thresh_s,
+                  float thresh_h, int stages, const TemporalHist *hist)
 {
-    if (!args_ok("d_adcensus_stm", {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1},
-                                    {"num_cols", num_cols, 1}, {"num_rows_out", num_rows_out, 1},
-                                    {"num_cols_out", num_cols_out, 1}, {"elem_sz", elem_sz, 3},
-                                    {"num_views", num_views, 2}, {"num_disp", num_disp, 1}}))
-        return;
+    char msg[200];
     if ((stages & 0x300) == 0x300) { // sub-pixel enhancement reads the last horizontal pass's input, which HSLO does not keep
-        fail("d_adcensus_stm: stages 0x200 (sub-pixel) together with 0x100 (HSLO) is not supported", "stages", __FILE__, __LINE__);
+        snprintf(msg, sizeof msg, "%s: stages 0x200 (sub-pixel) together with 0x100 (HSLO) is not supported", fn);
+        fail(msg, "stages", __FILE__, __LINE__);
         return;
     }
     if ((stages & 0x400) && (stages & 0xff) < 2) { // interpolation fills what the L/R check marked: stage 1 has no outlier maps
-        fail("d_adcensus_stm: stages 0x400 (outlier interpolation) needs the refinement stages (2 or 3)", "stages", __FILE__, __LINE__);
+        snprintf(msg, sizeof msg, "%s: stages 0x400 (outlier interpolation) needs the refinement stages (2 or 3)", fn);
+        fail(msg, "stages", __FILE__, __LINE__);
         return;
     }
     if ((stages & 0x800) && (stages & 0xff) < 3) { // linear sampling changes the renderer only: stages 1 and 2 render nothing
-        fail("d_adcensus_stm: stages 0x800 (linear sampling of the warps) needs the rendering stage (3)", "stages", __FILE__, __LINE__);
+        snprintf(msg, sizeof msg, "%s: stages 0x800 (linear sampling of the warps) needs the rendering stage (3)", fn);
+        fail(msg, "stages", __FILE__, __LINE__);
         return;
     }
     if (stages & 0x1000) { // guided up-sampling belongs to the reduced-resolution frame: here nothing is up-scaled
-        fail("d_adcensus_stm: stages 0x1000 (guided disparity up-sampling) needs the reduced-resolution frame (d_adcensus_stm_2s)", "stages",
-             __FILE__, __LINE__);
+        snprintf(msg, sizeof msg, "%s: stages 0x1000 (guided disparity up-sampling) needs the reduced-resolution frame (d_adcensus_stm_2s)", fn);
+        fail(msg, "stages", __FILE__, __LINE__);
         return;
     }
     const int H = num_rows, W = num_cols, N = num_views;
@@ -1017,8 +1094,85 @@ void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp
     stages &= 0xff;
     frame_disparity(img_l, img_r, d_disp_l, d_disp_r, al, ar, H, W, elem_sz, num_disp, zero_disp, ad_coeff, census_coeff, ucd,
                     lcd, usd, lsd, thresh_s, thresh_h, stages >= 2, hslo, fused_split ? pre : nullptr, subpix, interp);
+    // temporal stabilisation (0x2000): the filtered maps pulled towards the previous frame's where neither colour nor disparity
+    // moved, each view on its own half of the two side-by-side buffers (read in place: the history was never split)
+    if (hist) {
+        float *c[2] = {d_disp_l, d_disp_r};
+        const float *q[2] = {hist->disp_l, hist->disp_r};
+        const u8 *im[2] = {d_img_sbs, d_img_sbs}, *ip[2] = {hist->sbs, hist->sbs};
+        const size_t off[2] = {0, (size_t)W * elem_sz};
+        launch_disp_temporal(2, c, q, im, ip, off, H, W, num_cols_sbs, elem_sz, hist->alpha, hist->thresh_color, hist->thresh_disp);
+    }
     if (stages < 3) return;
     frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle, linwarp);
+}
+
+bool frame_dims_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz,
+                   int num_views, int num_disp)
+{
+    return args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols", num_cols, 1},
+                        {"num_rows_out", num_rows_out, 1}, {"num_cols_out", num_cols_out, 1}, {"elem_sz", elem_sz, 3},
+                        {"num_views", num_views, 2}, {"num_disp", num_disp, 1}});
+}
+
+} // namespace
+
+extern "C" {
+
+void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                        int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz,
+                        int num_views, float angle, int num_disp, int zero_disp, float ad_coeff, float census_coeff,
+                        float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages)
+{
+    if (!frame_dims_ok("d_adcensus_stm", num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views, num_disp)) return;
+    if (stages & 0x2000) { // temporal stabilisation needs the previous frame: this call has no arguments for it
+        fail("d_adcensus_stm: stages 0x2000 (temporal stabilisation) needs the history arguments of d_adcensus_stm_t", "stages", __FILE__,
+             __LINE__);
+        return;
+    }
+    frame_device("d_adcensus_stm", d_img_sbs, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out,
+                 elem_sz, num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages, nullptr);
+}
+
+// stm_d_adcensus_stm with the history of the temporal stabilisation (stm_hip.h)
+void stm_d_adcensus_stm_t(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                          int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz,
+                          int num_views, float angle, int num_disp, int zero_disp, float ad_coeff, float census_coeff,
+                          float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages,
+                          unsigned char *d_prev_img_sbs, float *d_prev_disp_l, float *d_prev_disp_r, float alpha, int thresh_color,
+                          float thresh_disp)
+{
+    const char *fn = "d_adcensus_stm_t";
+    if (!frame_dims_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views, num_disp)) return;
+    TemporalHist hist = {d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp};
+    bool run = false;
+    if (stages & 0x2000) {
+        const int nset = (d_prev_img_sbs != nullptr) + (d_prev_disp_l != nullptr) + (d_prev_disp_r != nullptr);
+        const size_t HW = (size_t)num_rows * num_cols;
+        if (!temporal_params_ok(fn, alpha, thresh_color, thresh_disp)) return;
+        if ((stages & 0xff) < 2) { // the step filters the refined maps: stage 1 has none
+            fail("d_adcensus_stm_t: stages 0x2000 (temporal stabilisation) needs the refinement stages (2 or 3)", "stages", __FILE__, __LINE__);
+            return;
+        }
+        if (nset != 0 && nset != 3) {
+            fail("d_adcensus_stm_t: the three history pointers must be all null (first frame) or all set", "d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r",
+                 __FILE__, __LINE__);
+            return;
+        }
+        if (nset == 3 && num_cols_sbs < 2 * num_cols) { // the views are read from the two halves in place
+            fail("d_adcensus_stm_t: stages 0x2000 (temporal stabilisation) needs num_cols_sbs >= 2 * num_cols", "num_cols_sbs", __FILE__, __LINE__);
+            return;
+        }
+        if (nset == 3 && (maps_overlap(d_prev_disp_l, d_disp_l, HW) || maps_overlap(d_prev_disp_l, d_disp_r, HW) ||
+                          maps_overlap(d_prev_disp_r, d_disp_l, HW) || maps_overlap(d_prev_disp_r, d_disp_r, HW))) {
+            fail("d_adcensus_stm_t: a history map must not alias d_disp_l or d_disp_r", "d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
+            return;
+        }
+        run = nset == 3;
+    }
+    frame_device(fn, d_img_sbs, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz,
+                 num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages & ~0x2000,
+                 run ? &hist : nullptr);
 }
 
 // adcensus_stm_2, d_io.cu:240-508: the disparity is computed on a bilinearly reduced pair

@@ -208,6 +208,11 @@ void launch_view_table(u8 **tab, u8 *first, u8 *last, u8 *mem, size_t stride, in
 // (h x w) and the guide image img[v] (H x W), v < nviews (1 or 2) in one launch; tab = the 766 colour weights of sigma_color
 void launch_disp_upsample(int nviews, float *const *out, const float *const *dlow, const u8 *const *ilow, const u8 *const *img,
                           const float *tab, int H, int W, int h, int w, int elem_sz, float up);
+// temporal disparity stabilisation (stm_kernels_temporal.hip): cur[v] (H x W) blended in place towards prev[v] where the 3 x 3
+// maximum of the colour change between img[v] and img_prev[v] and the change of the disparity stay inside the gates; v < nviews
+// (1 or 2) in one launch.  Pixel (x, y) of view v's images lies at base + byte_off[v] + ((size_t)y * stride + x) * elem_sz
+void launch_disp_temporal(int nviews, float *const *cur, const float *const *prev, const u8 *const *img, const u8 *const *img_prev,
+                          const size_t *byte_off, int H, int W, int stride, int elem_sz, float alpha, int thresh_color, float thresh_disp);
 // frame pipeline: the N - 2 views are synthesised inside the interlacer, sample by sample (no view buffers)
 void launch_synth_mux(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l, const float *mask_r,
                       const float *blend, u8 *out, int N, float y_interval, float inv_y_interval, int ymod, int Hin, int Win, int Hout,

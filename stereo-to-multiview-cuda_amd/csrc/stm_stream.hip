@@ -40,7 +40,9 @@ struct FrameStream {
     hipStream_t s_in, s_out;
     bool overlap = true; // two frames in flight on the GPU (a compute stream + workspace per slot)
     bool use_graph = true;
-    int stages = 3; // stm_stream_set_stages: 3, optionally with 0x200 / 0x400 / 0x800
+    int stages = 3; // stm_stream_set_stages: 3, optionally with 0x200 / 0x400 / 0x800 / 0x2000
+    float t_alpha = 0.5f, t_disp = 1.5f; // stm_stream_set_temporal: the parameters of the temporal step (0x2000) and their defaults
+    int t_color = 24;
     Slot slot[2];
     long submitted = 0, collected = 0;
 };
@@ -93,8 +95,10 @@ void *stm_stream_create(int num_rows, int num_cols_sbs, int num_cols, int num_ro
 }
 
 // The `stages` word every frame of the stream is computed with: 3 (the default), optionally OR-ed with 0x200 (sub-pixel), 0x400
-// (outlier interpolation) and / or 0x800 (linear sampling of the warps).  Not 0x100: the stream's workspace is sized for the frame without HSLO.  Only before the first
-// submit: afterwards the slots replay their launches from a captured graph.  Returns 0, or -1 with the error recorded.
+// (outlier interpolation), 0x800 (linear sampling of the warps) and / or 0x2000 (temporal stabilisation: every frame but the first
+// is computed by stm_d_adcensus_stm_t with the frame before it as its history).  Not 0x100: the stream's workspace is sized for
+// the frame without HSLO.  Only before the first submit: afterwards the slots replay their launches from a captured graph.
+// Returns 0, or -1 with the error recorded.
 int stm_stream_set_stages(void *h, int stages)
 {
     FrameStream *f = (FrameStream *)h;
@@ -103,8 +107,8 @@ int stm_stream_set_stages(void *h, int stages)
         stm::fail("stream_set_stages: stages 0x1000 (guided disparity up-sampling) needs the reduced-resolution frame", "stages", __FILE__, __LINE__);
         return -1;
     }
-    if ((stages & ~0xe00) != 3) {
-        stm::fail("stream_set_stages: stages must be 3, optionally OR-ed with 0x200, 0x400 and 0x800", "stages", __FILE__, __LINE__);
+    if ((stages & ~0x2e00) != 3) {
+        stm::fail("stream_set_stages: stages must be 3, optionally OR-ed with 0x200, 0x400, 0x800 and 0x2000", "stages", __FILE__, __LINE__);
         return -1;
     }
     if (f->submitted > 0) {
@@ -112,6 +116,32 @@ int stm_stream_set_stages(void *h, int stages)
         return -1;
     }
     f->stages = stages;
+    return 0;
+}
+
+// The parameters of the temporal step (stages bit 0x2000; stm_disp_temporal's rules): defaults 0.5, 24, 1.5.  Only before the
+// first submit.  Returns 0, or -1 with the error recorded.
+int stm_stream_set_temporal(void *h, float alpha, int thresh_color, float thresh_disp)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) {
+        stm::fail("stream_set_temporal: alpha must be in [0, 1]", "alpha", __FILE__, __LINE__);
+        return -1;
+    }
+    if (thresh_color < 0 || thresh_color > 765) {
+        stm::fail("stream_set_temporal: thresh_color must be in [0, 765]", "thresh_color", __FILE__, __LINE__);
+        return -1;
+    }
+    if (!(thresh_disp >= 0.0f)) {
+        stm::fail("stream_set_temporal: thresh_disp must be >= 0", "thresh_disp", __FILE__, __LINE__);
+        return -1;
+    }
+    if (f->submitted > 0) {
+        stm::fail("stream_set_temporal: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    f->t_alpha = alpha; f->t_color = thresh_color; f->t_disp = thresh_disp;
     return 0;
 }
 
@@ -129,14 +159,29 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     // the caller's buffer is free again when this returns (as with adcensus_stm); a frame that was written straight into the
     // slot's pinned buffer (stm_stream_input_buffer) needs no copy
     if (img_sbs && img_sbs != s.h_in) memcpy(s.h_in, img_sbs, f->in_sz);
+    // temporal stabilisation: frame k reads the input and the maps of frame k - 1, which live in the other slot.  So the upload
+    // into this slot's d_in waits until the other slot's frame (which may still be reading this d_in as ITS history) is done,
+    // and this frame's compute waits for the other slot's outputs.  The two frames in flight then no longer overlap on the GPU;
+    // upload and download still do.  The other slot's ev_done was recorded by the previous submit.
+    Slot &other = f->slot[(f->submitted & 1) ^ 1];
+    const bool temporal = (f->stages & 0x2000) != 0, history = temporal && f->submitted > 0;
+    if (history) STM_CHECK(hipStreamWaitEvent(f->s_in, other.ev_done, 0));
     STM_CHECK(hipMemcpyAsync(s.d_in, s.h_in, f->in_sz, hipMemcpyHostToDevice, f->s_in));
     STM_CHECK(hipEventRecord(s.ev_in, f->s_in));
     STM_CHECK(hipStreamWaitEvent(s.s_compute, s.ev_in, 0));
+    if (history) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
     void *prev = stm_get_stream();
     stm_set_stream(s.s_compute);
     stm::ws_private_bind(s.ws);
     auto pipeline = [&]() {
         stm::ApiNest nest; // a failed upload above must survive the nested call's argument screen
+        if (temporal) { // the history pointers are fixed per slot: a captured frame (never the stream's first) replays them
+            stm_d_adcensus_stm_t(s.d_in, s.d_dl, s.d_dr, s.d_out, f->H, f->Wsbs, f->W, f->Hout, f->Wout, f->E, f->N, f->angle, f->D,
+                                 f->zd, f->ad, f->ce, f->ucd, f->lcd, f->usd, f->lsd, f->thresh_s, f->thresh_h, f->stages,
+                                 history ? other.d_in : nullptr, history ? other.d_dl : nullptr, history ? other.d_dr : nullptr,
+                                 f->t_alpha, f->t_color, f->t_disp);
+            return;
+        }
         stm_d_adcensus_stm(s.d_in, s.d_dl, s.d_dr, s.d_out, f->H, f->Wsbs, f->W, f->Hout, f->Wout, f->E, f->N, f->angle, f->D,
                            f->zd, f->ad, f->ce, f->ucd, f->lcd, f->usd, f->lsd, f->thresh_s, f->thresh_h, f->stages);
     };

@@ -26,6 +26,9 @@ STAGE_INTERP = 0x400
 STAGE_LINEAR_WARP = 0x800
 # d_adcensus_stm_2s only: the disparity maps scaled up by the guided up-sampler (stm_disp_upsample) instead of the bilinear blend
 STAGE_GUIDED_UP = 0x1000
+# d_adcensus_stm_t and the frame stream only: the filtered maps stabilised against the previous frame's (stm_disp_temporal)
+STAGE_TEMPORAL = 0x2000
+TEMPORAL_DEFAULTS = (0.5, 24, 1.5)  # alpha, thresh_color, thresh_disp of a frame sequence
 
 
 class FrameParams:
@@ -54,6 +57,29 @@ def d_adcensus_stm(sbs, disp_l, disp_r, interlaced, p, stages=3):
     lib().stm_d_adcensus_stm(_p(sbs), _p(disp_l), _p(disp_r), _p(interlaced), H, Wsbs, W, Ho, Wo, E,
                              p.num_views, p.angle, p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff,
                              p.ucd, p.lcd, p.usd, p.lsd, p.thresh_s, p.thresh_h, stages)
+
+
+def d_adcensus_stm_t(sbs, disp_l, disp_r, interlaced, p, stages=3, prev_sbs=None, prev_disp_l=None, prev_disp_r=None,
+                     alpha=TEMPORAL_DEFAULTS[0], thresh_color=TEMPORAL_DEFAULTS[1], thresh_disp=TEMPORAL_DEFAULTS[2]):
+    """stm_d_adcensus_stm_t: d_adcensus_stm with the history of the temporal stabilisation.  With STAGE_TEMPORAL in `stages` and
+    the previous frame's side-by-side input and output maps given, disp_l / disp_r are stabilised in place before the views are
+    rendered; with all three None (the first frame) the call is d_adcensus_stm without the bit."""
+    assert sbs.is_cuda and sbs.dtype == torch.uint8 and sbs.is_contiguous()
+    H, Wsbs, E = sbs.shape
+    W = Wsbs // 2
+    assert disp_l.shape == (H, W) and disp_r.shape == (H, W) and disp_l.dtype == torch.float32
+    if prev_sbs is not None:
+        assert prev_sbs.is_cuda and prev_sbs.dtype == torch.uint8 and prev_sbs.is_contiguous() and prev_sbs.shape == sbs.shape
+    for t in (prev_disp_l, prev_disp_r):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
+    Ho, Wo = interlaced.shape[0], interlaced.shape[1]
+    _use_current_stream()
+    lib().stm_d_adcensus_stm_t(_p(sbs), _p(disp_l), _p(disp_r), _p(interlaced), H, Wsbs, W, Ho, Wo, E,
+                               p.num_views, p.angle, p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff,
+                               p.ucd, p.lcd, p.usd, p.lsd, p.thresh_s, p.thresh_h, stages,
+                               None if prev_sbs is None else _p(prev_sbs), None if prev_disp_l is None else _p(prev_disp_l),
+                               None if prev_disp_r is None else _p(prev_disp_r), float(alpha), int(thresh_color), float(thresh_disp))
 
 
 def d_adcensus_stm_2s(sbs, disp_l, disp_r, interlaced, p, disp_rows, disp_cols, disp_scale, stages=3):
@@ -157,6 +183,21 @@ def d_disp_upsample(out, disp_low, img_low, img, up, sigma_color=15.0):
         assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
     _use_current_stream()
     lib().stm_d_disp_upsample(_p(out), _p(disp_low), _p(img_low), _p(img), H, W, h, w, E, float(up), float(sigma_color))
+
+
+def d_disp_temporal(disp, disp_prev, img, img_prev, alpha=TEMPORAL_DEFAULTS[0], thresh_color=TEMPORAL_DEFAULTS[1],
+                    thresh_disp=TEMPORAL_DEFAULTS[2]):
+    """stm_d_disp_temporal: disp float32 [H][W] on the GPU stabilised in place against disp_prev, the map the previous frame put
+    out, where the colour between img_prev and img (uint8 [H][W][E]) and the disparity stayed inside the gates.  Only disp is
+    written."""
+    H, W = disp.shape
+    for t in (disp, disp_prev):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
+    E = img.shape[2]
+    for t in (img, img_prev):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    _use_current_stream()
+    lib().stm_d_disp_temporal(_p(disp), _p(disp_prev), _p(img), _p(img_prev), H, W, E, float(alpha), int(thresh_color), float(thresh_disp))
 
 
 def prof_enable(on=True):

@@ -296,6 +296,21 @@ def disp_upsample(disp_low, img_low, img, up, sigma_color=15.0):
     return out
 
 
+def disp_temporal(disp, disp_prev, img, img_prev, alpha=0.5, thresh_color=24, thresh_disp=1.5):
+    """Temporal disparity stabilisation (stm_disp_temporal; an addition, the reference matches every frame on its own): this
+    frame's filtered map disp [H][W] pulled towards disp_prev, the map the previous frame put out, by the weight alpha wherever
+    the 3 x 3 maximum of the colour change between img_prev and img [H][W][E] is at most thresh_color and the maps differ by at
+    most thresh_disp.  Returns the [H][W] map; nothing passed in is modified."""
+    out = np.array(disp, dtype=np.float32, order="C")  # a copy: the library rewrites it in place
+    disp_prev, pq = _f32(disp_prev)
+    img, pi = _u8(img)
+    img_prev, pp = _u8(img_prev)
+    H, W, E = img.shape
+    assert out.shape == (H, W) and disp_prev.shape == (H, W) and img_prev.shape == img.shape
+    lib().stm_disp_temporal(out.ctypes.data_as(f32p), pq, pi, pp, H, W, E, float(alpha), int(thresh_color), float(thresh_disp))
+    return out
+
+
 def tx_scale(img, out_rows, out_cols):
     """d_tx_scale.h:17-18 (bilinear resize)."""
     img, pi = _u8(img)

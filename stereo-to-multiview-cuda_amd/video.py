@@ -26,10 +26,18 @@ class FrameStream:
             self.set_stages(stages)
 
     def set_stages(self, stages):
-        """stm_stream_set_stages: 3, optionally OR-ed with 0x200 (sub-pixel), 0x400 (outlier interpolation) and 0x800 (linear
-        sampling of the views' warps); only before the first submit.  Raises ValueError where the library refuses (it returns -1; in error mode 0 it exits like any error)."""
+        """stm_stream_set_stages: 3, optionally OR-ed with 0x200 (sub-pixel), 0x400 (outlier interpolation), 0x800 (linear
+        sampling of the views' warps) and 0x2000 (temporal stabilisation of the maps against the previous frame's); only before
+        the first submit.  Raises ValueError where the library refuses (it returns -1; in error mode 0 it exits like any error)."""
         if int(lib().stm_stream_set_stages(self._h, int(stages))) != 0:
             raise ValueError("stm_stream_set_stages(%#x) refused: %s" % (stages, lib().stm_last_error().decode()))
+
+    def set_temporal(self, alpha=0.5, thresh_color=24, thresh_disp=1.5):
+        """stm_stream_set_temporal: the parameters of the temporal step (stages bit 0x2000); only before the first submit.
+        Raises ValueError where the library refuses."""
+        if int(lib().stm_stream_set_temporal(self._h, float(alpha), int(thresh_color), float(thresh_disp))) != 0:
+            raise ValueError("stm_stream_set_temporal(%g, %d, %g) refused: %s"
+                             % (alpha, thresh_color, thresh_disp, lib().stm_last_error().decode()))
 
     def submit(self, sbs):
         sbs = np.ascontiguousarray(sbs, dtype=np.uint8)
@@ -76,14 +84,17 @@ class FrameStream:
             pass
 
 
-def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3):
+def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
-    stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling)."""
+    stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
+    stabilisation); temporal: (alpha, thresh_color, thresh_disp) for FrameStream.set_temporal, None = the defaults."""
     fs = None
     pending = 0
     for sbs in frames:
         if fs is None:
             fs = FrameStream(sbs.shape[0], sbs.shape[1] // 2, params, out_rows, out_cols, stages)
+            if temporal is not None:
+                fs.set_temporal(*temporal)
         if pending == 2:
             yield fs.collect()
             pending -= 1

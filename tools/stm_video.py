@@ -4,10 +4,13 @@ side-by-side BMP frames instead of a video file, BMP outputs instead of a window
 
 usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <num disp> <zero disp> <ad coeff>
                     <census coeff> <ucd> <lcd> <usd> <lsd> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel] [--linear-warp]
+                    [--temporal [--temporal-alpha A] [--temporal-color C] [--temporal-disp T]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
 --linear-warp (an addition, off by default): frame bit 0x800, the views' warps fetched at the fractional coordinate.
+--temporal (an addition, off by default): frame bit 0x2000, every frame's maps stabilised against the previous frame's where
+neither colour nor disparity moved; --temporal-alpha (0.5), --temporal-color (24) and --temporal-disp (1.5) set its parameters.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -21,7 +24,17 @@ sys.path.insert(0, ROOT)
 def main(argv):
     stages = 3 | (0x400 if "--interp" in argv else 0) | (0x200 if "--subpixel" in argv else 0)
     stages |= 0x800 if "--linear-warp" in argv else 0
-    argv = [x for x in argv if x not in ("--interp", "--subpixel", "--linear-warp")]
+    stages |= 0x2000 if "--temporal" in argv else 0
+    argv = [x for x in argv if x not in ("--interp", "--subpixel", "--linear-warp", "--temporal")]
+    temporal = [0.5, 24, 1.5]
+    for slot, (flag, conv) in enumerate((("--temporal-alpha", float), ("--temporal-color", int), ("--temporal-disp", float))):
+        if flag in argv:
+            at = argv.index(flag)
+            if at + 1 >= len(argv) or not (stages & 0x2000):
+                print(__doc__)
+                return -1
+            temporal[slot] = conv(argv[at + 1])
+            del argv[at:at + 2]
     if len(argv) not in (16, 17):
         print(__doc__)
         return -1
@@ -36,7 +49,8 @@ def main(argv):
     out_dir = a[15] if len(a) > 15 else os.path.join(a[0], "out")
     t0 = time.perf_counter()
     n = 0
-    for (k, dl, dr, inter) in video.process_sequence(video.read_bmp_sequence(a[0]), p, out_h, out_w, stages):
+    for (k, dl, dr, inter) in video.process_sequence(video.read_bmp_sequence(a[0]), p, out_h, out_w, stages,
+                                                       tuple(temporal) if stages & 0x2000 else None):
         video.write_outputs(out_dir, k, dl, dr, inter)
         n += 1
     dt = time.perf_counter() - t0
