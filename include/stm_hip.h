@@ -255,6 +255,38 @@ void stm_d_mux_multiview(unsigned char **d_views, unsigned char *d_out_data, int
 /* d_demux_common.h:10-13  demux_sbs kernel (d_demux_common.cu:8-33) as a host-callable stage */
 void stm_d_demux_sbs(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_img_sbs,
                      int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz);
+/* NV12 input (an addition: the reference takes one side-by-side BGR frame per call, which no video decoder delivers).  Colour
+ * conversion + split as a stage: the counterpart of stm_d_demux_sbs for a side-by-side NV12 frame of num_rows rows and
+ * num_cols_sbs columns, the left view in columns [0, W) and the right view in [W, 2 W), W = num_cols_out.
+ *   y    u8, num_rows rows of pitch_y bytes.
+ *   uv   u8, num_rows / 2 rows of pitch_uv bytes; bytes 2k and 2k + 1 of a row are U and V of the 2 x 2 luma block at columns 2k, 2k + 1.
+ * num_rows and W must be even (each half starts on a chroma sample), num_cols_sbs >= 2 W, pitch_y >= num_cols_sbs,
+ * pitch_uv >= 2 * ((num_cols_sbs + 1) / 2).  The base pointers may have any byte alignment.  Both planes are read only.
+ * Chroma is replicated: pixel (x, y) of the frame uses U = uv[y >> 1][2 (x >> 1)], V = uv[y >> 1][2 (x >> 1) + 1].
+ * `matrix` selects a row of coefficients: 0 = BT.601 limited range, 1 = BT.709 limited, 2 = BT.601 full, 3 = BT.709 full.
+ * All arithmetic is 32-bit signed integer, >> an arithmetic shift (floor):
+ *   C = Y - yo;  D = U - 128;  E = V - 128
+ *   B = clip255((ky*C + bu*D        + 32768) >> 16)
+ *   G = clip255((ky*C - gu*D - gv*E + 32768) >> 16)
+ *   R = clip255((ky*C + rv*E        + 32768) >> 16)
+ * With (Kr, Kb) = (0.299, 0.114) for 601 and (0.2126, 0.0722) for 709, Kg = 1 - Kr - Kb, and (ky, s, yo) = (255/219, 255/224, 16)
+ * for limited and (1, 1, 0) for full range: rv = 2(1-Kr)s, bu = 2(1-Kb)s, gu = 2Kb(1-Kb)s/Kg, gv = 2Kr(1-Kr)s/Kg, each times
+ * 65536 in double and rounded to nearest (none is a tie):
+ *   matrix   ky      rv      gu     gv      bu
+ *     0     76309  104597  25675  53279  132201
+ *     1     76309  117489  13975  34925  138438
+ *     2     65536   91881  22553  46802  116130
+ *     3     65536  103206  12276  30679  121609
+ * No intermediate exceeds 2^26.  E.g. matrix 0: (Y, U, V) = (16,128,128) -> (B, G, R) = (0,0,0); (235,128,128) -> (255,255,255);
+ * (81,90,240) -> (0,0,254); (0,0,0) -> (0,136,0); (255,0,255) -> (20,225,255).
+ * img_l / img_r are num_rows x W x elem_sz with B, G, R in a pixel's first three bytes; the bytes past the third come back 0
+ * from the host flavour and are left as they were by the device flavour.  Errors (stm_last_error), all reported before anything is
+ * launched or written: an odd num_rows or num_cols_out, num_cols_sbs < 2 W, a pitch below the rules, matrix outside 0 .. 3.
+ * Parity is against a numpy statement of these lines (parity unpinned). */
+void stm_demux_nv12(unsigned char *img_l, unsigned char *img_r, unsigned char *y, int pitch_y, unsigned char *uv, int pitch_uv,
+                    int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz, int matrix);
+void stm_d_demux_nv12(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv,
+                      int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz, int matrix);
 
 /* ------------------------------------------------------------ whole frame (a26) */
 /* d_io.h:32-40  adcensus_stm (d_io.cu:7-238).  `angle` is float here (the reference's int truncates
@@ -314,6 +346,29 @@ void stm_d_adcensus_stm_t(unsigned char *d_img_sbs, float *d_disp_l, float *d_di
                           int thresh_s, float thresh_h, int stages,
                           unsigned char *d_prev_img_sbs, float *d_prev_disp_l, float *d_prev_disp_r,
                           float alpha, int thresh_color, float thresh_disp);
+/* The device-resident frame on an NV12 frame (an addition): by definition stm_d_adcensus_stm_t applied to the side-by-side BGR frame
+ * that stm_demux_nv12's conversion gives, with every rule of `stages` unchanged; the conversion runs inside the frame's first
+ * kernel, no BGR frame is materialised.  Arguments as stm_d_adcensus_stm_t, except:
+ *   d_img_sbs      becomes d_y, pitch_y, d_uv, pitch_uv, matrix (stm_demux_nv12's layout and rules; num_cols_sbs >= 2 * num_cols
+ *                  is required whatever the stages);
+ *   d_prev_img_sbs becomes d_prev_img_l, d_prev_img_r: the previous frame's converted split images (num_rows x num_cols x elem_sz);
+ *   d_img_l, d_img_r (last) receive this frame's converted split images, in the device flavour's form (bytes past a pixel's third
+ *                  are left alone).  Both null: they stay in the workspace.  With 0x2000 both must be given: this frame's images
+ *                  are the next frame's history.
+ * With the bit set and all four history pointers null (the first frame) the call is the one without the bit.  Errors
+ * (stm_last_error), all reported before anything is launched or written: what stm_demux_nv12 and stm_d_adcensus_stm_t refuse;
+ * exactly one of d_img_l / d_img_r null; 0x2000 without them; some history pointers null and some not; a history buffer that
+ * overlaps d_img_l, d_img_r, d_disp_l or d_disp_r. */
+void stm_d_adcensus_stm_nv12(unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv, int matrix,
+                             float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                             int num_rows, int num_cols_sbs, int num_cols,
+                             int num_rows_out, int num_cols_out, int elem_sz,
+                             int num_views, float angle, int num_disp, int zero_disp,
+                             float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
+                             int thresh_s, float thresh_h, int stages,
+                             unsigned char *d_prev_img_l, unsigned char *d_prev_img_r, float *d_prev_disp_l, float *d_prev_disp_r,
+                             float alpha, int thresh_color, float thresh_disp,
+                             unsigned char *d_img_l, unsigned char *d_img_r);
 
 /* Reduced-resolution disparity: d_io.h:42-52 adcensus_stm_2 (d_io.cu:240-508).  The pair is
  * bilinearly reduced to num_rows_disp x num_cols_disp, matched there, and the disparity maps are scaled back up
@@ -436,6 +491,14 @@ int   stm_stream_set_stages(void *stream, int stages);
 /* the parameters of the temporal step of a stream whose stages carry 0x2000 (stm_disp_temporal's rules; defaults 0.5, 24, 1.5).
  * Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
 int   stm_stream_set_temporal(void *stream, float alpha, int thresh_color, float thresh_disp);
+/* the input format of the stream's frames: 0 = one side-by-side BGR frame (the default), 1 = NV12 with conversion `matrix`
+ * (stm_demux_nv12's rules: num_rows and num_cols even, num_cols_sbs even and >= 2 * num_cols; elem_sz as created).  In NV12 mode a
+ * frame is the Y plane (pitch num_cols_sbs) followed by the UV plane at byte num_rows * num_cols_sbs (pitch num_cols_sbs):
+ * stm_stream_submit reads, and stm_stream_input_buffer hands out, num_rows * num_cols_sbs * 3 / 2 bytes in that layout, and half
+ * the bytes of a BGR frame cross the link.  Every frame is an stm_d_adcensus_stm_nv12 call; each buffer slot owns its two split
+ * images, and with 0x2000 the other slot's images and maps are the history.  `matrix` is ignored for format 0.  Only before the
+ * first submit.  Returns 0, or -1 with stm_last_error set. */
+int   stm_stream_set_input(void *stream, int format, int matrix);
 /* waits for the oldest uncollected frame and copies its results out (NULL = skip).  Returns its index or -1. */
 long  stm_stream_collect(void *stream, float *disp_l, float *disp_r, unsigned char *interlaced);
 /* zero-copy variants (at 1080p the two host copies of submit / collect take longer than the frame does on the GPU):

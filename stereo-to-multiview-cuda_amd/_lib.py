@@ -71,9 +71,13 @@ PROTOS = {
     "stm_mux_multiview": ([u8pp, u8p, i, f, i, i, i, i, i], None),
     "stm_d_mux_multiview": ([vp, vp, i, f, i, i, i, i, i], None),
     "stm_d_demux_sbs": ([vp, vp, vp, i, i, i, i], None),
+    "stm_demux_nv12": ([u8p, u8p, u8p, i, u8p, i, i, i, i, i, i], None),
+    "stm_d_demux_nv12": ([vp, vp, vp, i, vp, i, i, i, i, i, i], None),
     "stm_adcensus_stm": ([u8p, f32p, f32p, u8p, i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f], None),
     "stm_d_adcensus_stm": ([vp, vp, vp, vp, i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f, i], None),
     "stm_d_adcensus_stm_t": ([vp, vp, vp, vp, i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f, i, vp, vp, vp, f, i, f], None),
+    "stm_d_adcensus_stm_nv12": ([vp, i, vp, i, i, vp, vp, vp, i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f, i, vp, vp, vp, vp, f, i, f,
+                                 vp, vp], None),
     "stm_adcensus_stm_2": ([u8p, f32p, f32p, u8p, i, i, i, i, i, i, i, i, f, i, f, i, i, f, f, f, f, i, i, i, f], None),
     "stm_d_adcensus_stm_2": ([vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, f, i, i, f, f, f, f, i, i, i, f], None),
     "stm_adcensus_stm_2s": ([u8p, f32p, f32p, u8p, i, i, i, i, i, i, i, i, f, i, f, i, i, f, f, f, f, i, i, i, f, i], None),
@@ -87,6 +91,7 @@ PROTOS = {
     "stm_stream_submit": ([C.c_void_p, u8p], C.c_long),
     "stm_stream_set_stages": ([C.c_void_p, i], i),
     "stm_stream_set_temporal": ([C.c_void_p, f, i, f], i),
+    "stm_stream_set_input": ([C.c_void_p, i, i], i),
     "stm_stream_collect": ([C.c_void_p, f32p, f32p, u8p], C.c_long),
     "stm_stream_input_buffer": ([C.c_void_p], C.c_void_p),
     "stm_stream_collect_view": ([C.c_void_p, C.POINTER(f32p), C.POINTER(f32p), C.POINTER(u8p)], C.c_long),

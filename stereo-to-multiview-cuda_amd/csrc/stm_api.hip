@@ -304,7 +304,43 @@ bool temporal_args_ok(const char *fn, const float *disp, const float *disp_prev,
     }
     return true;
 }
+// [a, a + n) and [b, b + m) share a byte
+bool bytes_overlap(const void *a, size_t n, const void *b, size_t m)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + m && pb < pa + n;
+}
 } // namespace
+
+// the rules of an NV12 frame (stm_hip.h, stm_demux_nv12), after the dimension screen; cols_name: what the call names the width of a view
+bool stm::nv12_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, const char *cols_name, int pitch_y, int pitch_uv,
+                       int matrix)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (num_rows & 1) {
+        snprintf(msg, sizeof msg, "%s: num_rows = %d, must be even (a chroma row serves two rows)", fn, num_rows);
+        arg = "num_rows";
+    } else if (num_cols & 1) {
+        snprintf(msg, sizeof msg, "%s: %s = %d, must be even (each half starts on a chroma sample)", fn, cols_name, num_cols);
+        arg = cols_name;
+    } else if (num_cols_sbs < 2 * num_cols) {
+        snprintf(msg, sizeof msg, "%s: num_cols_sbs = %d, must be >= 2 * %s = %d", fn, num_cols_sbs, cols_name, 2 * num_cols);
+        arg = "num_cols_sbs";
+    } else if (pitch_y < num_cols_sbs) {
+        snprintf(msg, sizeof msg, "%s: pitch_y = %d, must be >= num_cols_sbs = %d", fn, pitch_y, num_cols_sbs);
+        arg = "pitch_y";
+    } else if (pitch_uv < 2 * ((num_cols_sbs + 1) / 2)) {
+        snprintf(msg, sizeof msg, "%s: pitch_uv = %d, must be >= 2 * ((num_cols_sbs + 1) / 2) = %d", fn, pitch_uv, 2 * ((num_cols_sbs + 1) / 2));
+        arg = "pitch_uv";
+    } else if (matrix < 0 || matrix > 3) {
+        snprintf(msg, sizeof msg, "%s: matrix = %d, must be 0 (BT.601 limited), 1 (BT.709 limited), 2 (BT.601 full) or 3 (BT.709 full)", fn, matrix);
+        arg = "matrix";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
 
 extern "C" {
 
@@ -813,6 +849,37 @@ void stm_d_demux_sbs(unsigned char *d_img_l, unsigned char *d_img_r, unsigned ch
     launch_demux_sbs(d_img_l, d_img_r, d_img_sbs, num_rows, num_cols_sbs, num_cols_out, elem_sz);
 }
 
+// NV12 input (an addition, the reference takes BGR only): colour conversion + split as a stage (stm_hip.h)
+void stm_d_demux_nv12(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv,
+                      int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz, int matrix)
+{
+    const char *fn = "d_demux_nv12";
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols_out", num_cols_out, 1}, {"elem_sz", elem_sz, 3}}))
+        return;
+    if (!nv12_args_ok(fn, num_rows, num_cols_sbs, num_cols_out, "num_cols_out", pitch_y, pitch_uv, matrix)) return;
+    launch_demux_nv12(d_img_l, d_img_r, d_y, pitch_y, d_uv, pitch_uv, num_rows, num_cols_out, elem_sz, matrix);
+}
+void stm_demux_nv12(unsigned char *img_l, unsigned char *img_r, unsigned char *y, int pitch_y, unsigned char *uv, int pitch_uv,
+                    int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz, int matrix)
+{
+    const char *fn = "demux_nv12";
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols_out", num_cols_out, 1}, {"elem_sz", elem_sz, 3}}))
+        return;
+    if (!nv12_args_ok(fn, num_rows, num_cols_sbs, num_cols_out, "num_cols_out", pitch_y, pitch_uv, matrix)) return;
+    // a plane's last row need not be a whole pitch long
+    const size_t IMG = (size_t)num_rows * num_cols_out * elem_sz, uv_row = 2 * (size_t)((num_cols_sbs + 1) / 2);
+    const size_t y_sz = (size_t)(num_rows - 1) * pitch_y + num_cols_sbs, uv_sz = (size_t)(num_rows / 2 - 1) * pitch_uv + uv_row;
+    Workspace::begin(2 * IMG + y_sz + uv_sz + 4096);
+    u8 *dy = up(y, y_sz), *duv = up(uv, uv_sz), *l = Workspace::get<u8>(IMG), *r = Workspace::get<u8>(IMG);
+    if (elem_sz > 3) { // bytes past a pixel's third come back 0, not as the workspace held them
+        STM_CHECK(hipMemsetAsync(l, 0, IMG, stream()));
+        STM_CHECK(hipMemsetAsync(r, 0, IMG, stream()));
+    }
+    launch_demux_nv12(l, r, dy, pitch_y, duv, pitch_uv, num_rows, num_cols_out, elem_sz, matrix);
+    down(img_l, l, IMG); down(img_r, r, IMG);
+    sync();
+}
+
 } // extern "C"
 
 // device staging buffers of the blocking host-flavour frame calls: grow-only, one set per host thread and device (the
@@ -1035,19 +1102,28 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
 // the history of the temporal stabilisation (stages bit 0x2000, stm_d_adcensus_stm_t): the previous frame's side-by-side input and
 // the two maps it put out
 struct TemporalHist {
-    const u8 *sbs;
+    const u8 *sbs; // stm_d_adcensus_stm_t: read in place, each view in its own half
     const float *disp_l, *disp_r;
     float alpha;
     int thresh_color;
     float thresh_disp;
+    const u8 *img_l = nullptr, *img_r = nullptr; // stm_d_adcensus_stm_nv12: the previous frame's converted split images
+};
+// the input of stm_d_adcensus_stm_nv12 in place of d_img_sbs: the two planes, and where the converted split images go (both null:
+// the workspace)
+struct Nv12Input {
+    const u8 *y, *uv;
+    int pitch_y, pitch_uv, matrix;
+    u8 *img_l, *img_r;
 };
 
-// the body of stm_d_adcensus_stm and stm_d_adcensus_stm_t; hist != nullptr: the temporal step between the bilateral filter and
-// the renderer.  Every argument has been screened by the caller except the `stages` rules the two calls share.
+// the body of stm_d_adcensus_stm, stm_d_adcensus_stm_t and stm_d_adcensus_stm_nv12; hist != nullptr: the temporal step between
+// the bilateral filter and the renderer; nv != nullptr: the frame comes as NV12 planes (d_img_sbs is null, num_cols_sbs >= 2 W).
+// Every argument has been screened by the caller except the `stages` rules the calls share.
 void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced, int num_rows,
                   int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz, int num_views, float angle,
                   int num_disp, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd, int thresh_s,
-                  float thresh_h, int stages, const TemporalHist *hist)
+                  float thresh_h, int stages, const TemporalHist *hist, const Nv12Input *nv = nullptr)
 {
     char msg[200];
     if ((stages & 0x300) == 0x300) { // sub-pixel enhancement reads the last horizontal pass's input, which HSLO does not keep
@@ -1074,10 +1150,18 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
     const size_t V = pq_volume_floats(num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
     Workspace::begin(((stages & 0x100) ? 13 : 4) * V * 4 + (size_t)(N + 2) * IMG + 168 * HW + (1u << 20));
-    u8 *img_l = Workspace::get<u8>(IMG), *img_r = Workspace::get<u8>(IMG);
+    const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
+    u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     uint32_t *pre[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const bool fused_split = num_cols_sbs >= 2 * W; // both halves complete: emit the derived pixel formats in the same pass
-    if (fused_split && (agg_variant() / 100) % 10 != 6) { // ... and the census words; 600: the split and the census as two kernels
+    bool fused_split = num_cols_sbs >= 2 * W; // both halves complete: emit the derived pixel formats in the same pass
+    if (nv && (agg_variant() / 100) % 10 != 6) { // the conversion in stm_k_front's pass
+        for (int i = 0; i < 6; ++i) pre[i] = Workspace::get<uint32_t>(HW);
+        launch_front_nv12(img_l, img_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], nv->y, nv->pitch_y, nv->uv, nv->pitch_uv, H, W,
+                          elem_sz, nv->matrix);
+    } else if (nv) { // 600: the plain converter, then the pixel formats and the census as kernels of their own
+        launch_demux_nv12(img_l, img_r, nv->y, nv->pitch_y, nv->uv, nv->pitch_uv, H, W, elem_sz, nv->matrix);
+        fused_split = false;
+    } else if (fused_split && (agg_variant() / 100) % 10 != 6) { // ... and the census words; 600: the split and the census as two kernels
         for (int i = 0; i < 6; ++i) pre[i] = Workspace::get<uint32_t>(HW);
         launch_front(img_l, img_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], d_img_sbs, H, num_cols_sbs, W, elem_sz);
     } else if (fused_split) {
@@ -1095,13 +1179,14 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
     frame_disparity(img_l, img_r, d_disp_l, d_disp_r, al, ar, H, W, elem_sz, num_disp, zero_disp, ad_coeff, census_coeff, ucd,
                     lcd, usd, lsd, thresh_s, thresh_h, stages >= 2, hslo, fused_split ? pre : nullptr, subpix, interp);
     // temporal stabilisation (0x2000): the filtered maps pulled towards the previous frame's where neither colour nor disparity
-    // moved, each view on its own half of the two side-by-side buffers (read in place: the history was never split)
+    // moved, each view on its own half of the two side-by-side buffers (read in place: the history was never split) -- or, for an
+    // NV12 frame, on the two frames' converted split images
     if (hist) {
         float *c[2] = {d_disp_l, d_disp_r};
         const float *q[2] = {hist->disp_l, hist->disp_r};
-        const u8 *im[2] = {d_img_sbs, d_img_sbs}, *ip[2] = {hist->sbs, hist->sbs};
-        const size_t off[2] = {0, (size_t)W * elem_sz};
-        launch_disp_temporal(2, c, q, im, ip, off, H, W, num_cols_sbs, elem_sz, hist->alpha, hist->thresh_color, hist->thresh_disp);
+        const u8 *im[2] = {nv ? img_l : d_img_sbs, nv ? img_r : d_img_sbs}, *ip[2] = {nv ? hist->img_l : hist->sbs, nv ? hist->img_r : hist->sbs};
+        const size_t off[2] = {0, nv ? 0 : (size_t)W * elem_sz};
+        launch_disp_temporal(2, c, q, im, ip, off, H, W, nv ? W : num_cols_sbs, elem_sz, hist->alpha, hist->thresh_color, hist->thresh_disp);
     }
     if (stages < 3) return;
     frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle, linwarp);
@@ -1173,6 +1258,61 @@ void stm_d_adcensus_stm_t(unsigned char *d_img_sbs, float *d_disp_l, float *d_di
     frame_device(fn, d_img_sbs, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz,
                  num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages & ~0x2000,
                  run ? &hist : nullptr);
+}
+
+// stm_d_adcensus_stm_t on an NV12 frame (stm_hip.h): the same body, the conversion fused into its first kernel
+void stm_d_adcensus_stm_nv12(unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv, int matrix, float *d_disp_l, float *d_disp_r,
+                             unsigned char *d_interlaced, int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
+                             int elem_sz, int num_views, float angle, int num_disp, int zero_disp, float ad_coeff, float census_coeff,
+                             float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages,
+                             unsigned char *d_prev_img_l, unsigned char *d_prev_img_r, float *d_prev_disp_l, float *d_prev_disp_r, float alpha,
+                             int thresh_color, float thresh_disp, unsigned char *d_img_l, unsigned char *d_img_r)
+{
+    const char *fn = "d_adcensus_stm_nv12";
+    if (!frame_dims_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views, num_disp)) return;
+    if (!nv12_args_ok(fn, num_rows, num_cols_sbs, num_cols, "num_cols", pitch_y, pitch_uv, matrix)) return;
+    if ((d_img_l != nullptr) != (d_img_r != nullptr)) {
+        fail("d_adcensus_stm_nv12: d_img_l and d_img_r must be both null (the split images stay in the workspace) or both set", "d_img_l, d_img_r",
+             __FILE__, __LINE__);
+        return;
+    }
+    TemporalHist hist = {nullptr, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp, d_prev_img_l, d_prev_img_r};
+    Nv12Input nv = {d_y, d_uv, pitch_y, pitch_uv, matrix, d_img_l, d_img_r};
+    bool run = false;
+    if (stages & 0x2000) {
+        const int nset = (d_prev_img_l != nullptr) + (d_prev_img_r != nullptr) + (d_prev_disp_l != nullptr) + (d_prev_disp_r != nullptr);
+        const size_t HW = (size_t)num_rows * num_cols, IMG = HW * elem_sz;
+        if (!temporal_params_ok(fn, alpha, thresh_color, thresh_disp)) return;
+        if ((stages & 0xff) < 2) { // as d_adcensus_stm_t
+            fail("d_adcensus_stm_nv12: stages 0x2000 (temporal stabilisation) needs the refinement stages (2 or 3)", "stages", __FILE__, __LINE__);
+            return;
+        }
+        if (!d_img_l) { // this frame's converted images are the next frame's history: the caller must keep them
+            fail("d_adcensus_stm_nv12: stages 0x2000 (temporal stabilisation) needs the output images d_img_l and d_img_r", "d_img_l, d_img_r",
+                 __FILE__, __LINE__);
+            return;
+        }
+        if (nset != 0 && nset != 4) {
+            fail("d_adcensus_stm_nv12: the four history pointers must be all null (first frame) or all set",
+                 "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
+            return;
+        }
+        if (nset == 4) { // the history is read while the outputs are written
+            const void *h[4] = {d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r}, *o[4] = {d_img_l, d_img_r, d_disp_l, d_disp_r};
+            const size_t sz[4] = {IMG, IMG, HW * 4, HW * 4};
+            for (int i = 0; i < 4; ++i)
+                for (int j = 0; j < 4; ++j)
+                    if (bytes_overlap(h[i], sz[i], o[j], sz[j])) {
+                        fail("d_adcensus_stm_nv12: a history buffer must not alias an output (d_img_l, d_img_r, d_disp_l, d_disp_r)",
+                             "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
+                        return;
+                    }
+        }
+        run = nset == 4;
+    }
+    frame_device(fn, nullptr, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz,
+                 num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages & ~0x2000,
+                 run ? &hist : nullptr, &nv);
 }
 
 // adcensus_stm_2, d_io.cu:240-508: the disparity is computed on a bilinearly reduced pair

@@ -19,6 +19,9 @@ void clear_failed();
 struct ApiNest { ApiNest(); ~ApiNest(); }; // held by an entry point around the entry points it calls
 bool api_outermost();
 void release_host_frame_bufs(); // stm_api.hip: the calling thread's staging buffers of the host-flavour frame calls
+// stm_api.hip: the geometry rules of an NV12 frame (include/stm_hip.h); false with the error recorded.  cols_name: the caller's name
+// for the width of a view
+bool nv12_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, const char *cols_name, int pitch_y, int pitch_uv, int matrix);
 #define STM_CHECK(expr)                                                                  \
     do {                                                                                 \
         hipError_t _e = (expr);                                                          \
@@ -136,6 +139,11 @@ void launch_census32_pair(const uint32_t *packed_l, uint32_t *census_l, const ui
 // frame pipeline: launch_demux_sbs_packed + launch_census32_pair in one kernel (Wsbs >= 2 W)
 void launch_front(u8 *l, u8 *r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l, uint32_t *wide_r, uint32_t *cen_l, uint32_t *cen_r,
                   const u8 *sbs, int H, int Wsbs, int W, int elem_sz);
+// NV12 input (y: H rows of pitch_y bytes, uv: H / 2 rows of pitch_uv bytes; H, W even, pitches >= 2 W, matrix 0 .. 3, all
+// screened by the caller): launch_front on the converted frame, and the plain converter + split
+void launch_front_nv12(u8 *l, u8 *r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l, uint32_t *wide_r, uint32_t *cen_l, uint32_t *cen_r,
+                       const u8 *y, int pitch_y, const u8 *uv, int pitch_uv, int H, int W, int elem_sz, int matrix);
+void launch_demux_nv12(u8 *l, u8 *r, const u8 *y, int pitch_y, const u8 *uv, int pitch_uv, int H, int W, int elem_sz, int matrix);
 void launch_cost_init(const uint32_t *pk_l, const uint32_t *pk_r, const uint32_t *cen_l, const uint32_t *cen_r,
                       Vol cost_l, Vol cost_r, const float *lut_ad, const float *lut_census,
                       int D, int zd, int H, int W);

@@ -210,6 +210,161 @@ void launch_front(u8 *l, u8 *r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l
     STM_CHECK_LAUNCH();
 }
 
+// ---------------------------------------------------------------- NV12 input: colour conversion in the same pass
+// The integer conversion of stm_hip.h (stm_demux_nv12): 16.16 fixed point, 32-bit, arithmetic shift, no intermediate above 2^26.
+// Row `matrix` of the table: ky, rv, gu, gv, bu (each round(coefficient * 65536)) and the luma offset.
+struct Nv12Coef { int ky, rv, gu, gv, bu, yo; };
+static const Nv12Coef NV12_COEF[4] = {
+    {76309, 104597, 25675, 53279, 132201, 16}, // 0: BT.601 limited range
+    {76309, 117489, 13975, 34925, 138438, 16}, // 1: BT.709 limited range
+    {65536, 91881, 22553, 46802, 116130, 0},   // 2: BT.601 full range
+    {65536, 103206, 12276, 30679, 121609, 0},  // 3: BT.709 full range
+};
+__device__ __forceinline__ uint32_t nv12_bgrx(int Y, int U, int V, const Nv12Coef &c)
+{
+    const int C = Y - c.yo, D = U - 128, E = V - 128, k = c.ky * C + 32768;
+    const int b = min(max((k + c.bu * D) >> 16, 0), 255);
+    const int g = min(max((k - c.gu * D - c.gv * E) >> 16, 0), 255);
+    const int r = min(max((k + c.rv * E) >> 16, 0), 255);
+    return (uint32_t)b | ((uint32_t)g << 8) | ((uint32_t)r << 16);
+}
+// stm_k_front on an NV12 frame: stm_k_front's tile, phase by phase and line by line (see there), with each pixel converted as it is
+// fetched; from the converted BGRX dword on the two kernels are the same text.  (They do not share it through a device function:
+// moving stm_k_front's body, or only its census phase, into an inlined function changed the ISA hipcc emits for stm_k_front, and
+// the default path must not move -- DESIGN.md section 14.  Until the two are folded, DESIGN.md section 8 item 6, a change to
+// stm_k_front's store or census phase must be repeated here by hand.)  A fetch is one Y byte and the pixel's U, V pair; hipcc merges the
+// pair's two byte loads into one 16-bit load (gfx950 loads at any alignment), so a fetch issues two loads, as in stm_k_front.  The
+// two lanes of a column pair read the same pair in the same instruction (one request to the cache), and the second tile row of a
+// chroma row (another wave of the block: wave w keeps rows w, w + 4, .. so the store phase stays stm_k_front's) finds the line in
+// the CU's vector cache: a chroma row of a tile is 64 bytes.
+__global__ __launch_bounds__(256) void stm_k_front_nv12(u8 *__restrict__ l, u8 *__restrict__ r, uint32_t *__restrict__ pk_l,
+                                                        uint32_t *__restrict__ pk_r, uint32_t *__restrict__ wide_l,
+                                                        uint32_t *__restrict__ wide_r, uint32_t *__restrict__ cen_l,
+                                                        uint32_t *__restrict__ cen_r, const u8 *__restrict__ yp, int pitch_y,
+                                                        const u8 *__restrict__ uvp, int pitch_uv, int H, int W, int elem_sz, Nv12Coef c)
+{
+    constexpr int TW = FR_TX + 8, TH = FR_TY + 4;
+    __shared__ __attribute__((aligned(16))) u8 g[TH][TW + 4]; // (a row is 76 bytes: dword reads of a row stay aligned)
+    const int view = blockIdx.z, x0 = blockIdx.x * FR_TX, y0 = blockIdx.y * FR_TY, tid = threadIdx.x;
+    u8 *__restrict__ img = view ? r : l;
+    uint32_t *__restrict__ pk = view ? pk_r : pk_l, *__restrict__ wide = view ? wide_r : wide_l, *__restrict__ census = view ? cen_r : cen_l;
+    const u8 *__restrict__ y_half = yp + (size_t)view * W, *__restrict__ uv_half = uvp + (size_t)view * W; // (W is even: a half starts on a chroma sample)
+    // All loads of a thread are issued before the first is used.  Own pixels: lane = column, wave w takes tile rows w, w + 4, ..
+    // (a wave instruction = one 64-pixel row: aligned 256-byte stores of the dword formats); the 416 halo elements -- four full
+    // rows, then eight side columns of the sixteen own rows -- take two more trips.
+    const int lane = tid & 63, wave = tid >> 6;
+    auto fetch = [&](int ty, int tx) {
+        const int gx = min(max(x0 + tx - 4, 0), W - 1), gy = min(max(y0 + ty - 1, 0), H - 1); // clamp-to-edge inside this half
+        const int Y = y_half[(size_t)gy * pitch_y + gx];
+        const u8 *s = uv_half + (size_t)(gy >> 1) * pitch_uv + (gx & ~1);
+        return nv12_bgrx(Y, s[0], s[1], c);
+    };
+    constexpr int NH = TW * TH - FR_TX * FR_TY; // halo elements
+    uint32_t own[FR_TY / 4], halo[2];
+    int hty[2], htx[2];
+#pragma unroll
+    for (int k = 0; k < FR_TY / 4; ++k) own[k] = fetch(wave + 4 * k + 1, lane + 4);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const int h = min(tid + 256 * m, NH - 1);
+        if (h < 4 * TW) {
+            const int q = h / TW;
+            hty[m] = q == 0 ? 0 : FR_TY + q;
+            htx[m] = h - q * TW;
+        } else {
+            const int e = h - 4 * TW;
+            hty[m] = 1 + (e >> 3);
+            htx[m] = (e & 7) < 4 ? (e & 7) : FR_TX + (e & 7);
+        }
+        halo[m] = fetch(hty[m], htx[m]);
+    }
+    // the split image as dwords: 64 pixels of 3 bytes are 48 aligned dwords of the row, each built from two neighbouring pixels
+    const bool img_dwords = elem_sz == 3 && (W & 3) == 0 && x0 + FR_TX <= W && (((uintptr_t)img) & 3) == 0;
+    const int p0 = (4 * lane) / 3, o8 = 8 * (4 * lane - 3 * p0); // lane < 48: dword `lane` starts in byte o8 / 8 of pixel p0
+#pragma unroll
+    for (int k = 0; k < FR_TY / 4; ++k) {
+        const int r = wave + 4 * k, ux = x0 + lane, uy = y0 + r;
+        g[r + 1][lane + 4] = (u8)grey_of(own[k]);
+        if (uy >= H) continue; // (the whole wave)
+        const uint32_t b = own[k] & 0xff, gg = (own[k] >> 8) & 0xff, rr = own[k] >> 16;
+        const size_t p = (size_t)uy * W + ux;
+        if (img_dwords) {
+            const uint32_t lo = (uint32_t)__shfl((int)own[k], p0 & 63), hi = (uint32_t)__shfl((int)own[k], (p0 + 1) & 63);
+            if (lane < 48) ((uint32_t *)(img + ((size_t)uy * W + x0) * 3))[lane] = (uint32_t)((lo | ((unsigned long long)hi << 24)) >> o8);
+        } else if (ux < W) {
+            u8 *d = img + p * elem_sz;
+            d[0] = (u8)b; d[1] = (u8)gg; d[2] = (u8)rr;
+        }
+        if (ux < W) {
+            pk[p] = own[k];
+            wide[p] = b | (gg << 10) | (rr << 20);
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+        if (tid + 256 * m < NH) g[hty[m]][htx[m]] = (u8)grey_of(halo[m]);
+    __syncthreads();
+    const int col = tid & 63, band = tid >> 6, gx = x0 + col; // rows y0 + 4 band .. + 3 of column gx
+    if (gx >= W) return;
+    // tile rows 4 band .. 4 band + 7, columns col .. col + 8 (the pixel's own column is col + 4): lo = the four bytes left of the
+    // centre, ct = the centre, hi = the four bytes right of it
+    uint32_t lo[8], ct[8], hi[8];
+    const int a8 = (col & 3) * 8;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t *rw = (const uint32_t *)&g[band * 4 + k][col & ~3];
+        const uint32_t d0 = rw[0], d1 = rw[1], d2 = rw[2];
+        const unsigned long long q01 = d0 | ((unsigned long long)d1 << 32), q12 = d1 | ((unsigned long long)d2 << 32);
+        lo[k] = (uint32_t)(q01 >> a8);
+        ct[k] = (uint32_t)(q12 >> a8) & 0xffu;
+        hi[k] = (uint32_t)(q12 >> (a8 + 8));
+    }
+    // bit order of stm_k_census32: window rows -1, +1, +2, +3 (what survives the truncation to 32 bits), in a row x = -4 .. 4
+    // without 0, appended MSB first (d_ci_census.cu:35-47)
+    auto row_bits = [](uint32_t lo4, uint32_t hi4, uint32_t cmp) {
+        uint32_t b = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) b = (b << 1) | (((lo4 >> (8 * k)) & 0xffu) < cmp ? 1u : 0u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) b = (b << 1) | (((hi4 >> (8 * k)) & 0xffu) < cmp ? 1u : 0u);
+        return b;
+    };
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { // the pixel of tile row 4 band + j + 1
+        const int gy = y0 + band * 4 + j;
+        const uint32_t cmp = ct[j + 1];
+        const uint32_t w = (row_bits(lo[j], hi[j], cmp) << 24) | (row_bits(lo[j + 2], hi[j + 2], cmp) << 16) |
+                           (row_bits(lo[j + 3], hi[j + 3], cmp) << 8) | row_bits(lo[j + 4], hi[j + 4], cmp);
+        if (gy < H) census[(size_t)gy * W + gx] = w;
+    }
+}
+void launch_front_nv12(u8 *l, u8 *r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l, uint32_t *wide_r, uint32_t *cen_l, uint32_t *cen_r,
+                       const u8 *y, int pitch_y, const u8 *uv, int pitch_uv, int H, int W, int elem_sz, int matrix)
+{
+    STM_LAUNCH(stm_k_front_nv12, dim3(cdiv(W, FR_TX), cdiv(H, FR_TY), 2), dim3(256), 0, stream(), l, r, pk_l, pk_r, wide_l, wide_r, cen_l, cen_r,
+               y, pitch_y, uv, pitch_uv, H, W, elem_sz, NV12_COEF[matrix]);
+    STM_CHECK_LAUNCH();
+}
+// the plain converter + split (stm_demux_nv12, and the frame under stm_set_agg_variant(600)): one thread per pixel of the two halves,
+// no derived planes
+__global__ __launch_bounds__(256) void stm_k_demux_nv12(u8 *__restrict__ l, u8 *__restrict__ r, const u8 *__restrict__ yp, int pitch_y,
+                                                        const u8 *__restrict__ uvp, int pitch_uv, int W, int elem_sz, Nv12Coef c)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= 2 * W) return;
+    const u8 *s = uvp + (size_t)(y >> 1) * pitch_uv + (x & ~1);
+    const uint32_t px = nv12_bgrx(yp[(size_t)y * pitch_y + x], s[0], s[1], c);
+    const bool right = x >= W;
+    u8 *d = (right ? r : l) + ((size_t)y * W + (right ? x - W : x)) * elem_sz;
+    d[0] = (u8)px; d[1] = (u8)(px >> 8); d[2] = (u8)(px >> 16);
+}
+void launch_demux_nv12(u8 *l, u8 *r, const u8 *y, int pitch_y, const u8 *uv, int pitch_uv, int H, int W, int elem_sz, int matrix)
+{
+    STM_LAUNCH(stm_k_demux_nv12, dim3(cdiv(2 * W, 256), H), dim3(256), 0, stream(), l, r, y, pitch_y, uv, pitch_uv, W, elem_sz,
+               NV12_COEF[matrix]);
+    STM_CHECK_LAUNCH();
+}
+
 // ---------------------------------------------------------------- combined cost volume
 // popc(x & 0x7fffffff) + 33 * (x >> 31)  ==  the 64-iteration loop of d_alu.cu:7-15 (SURVEY A-Q1)
 __device__ __forceinline__ int hamdist_ref(uint32_t a, uint32_t b)

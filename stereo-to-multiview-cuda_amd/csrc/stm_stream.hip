@@ -20,6 +20,7 @@ namespace {
 struct Slot {
     u8 *h_in = nullptr, *d_in = nullptr, *d_out = nullptr, *h_out = nullptr;
     float *d_dl = nullptr, *d_dr = nullptr, *h_dl = nullptr, *h_dr = nullptr;
+    u8 *d_img_l = nullptr, *d_img_r = nullptr; // NV12 input: the slot's converted split images (the other slot's frame reads them as its history)
     hipEvent_t ev_in, ev_done, ev_out;
     bool busy = false;
     hipStream_t s_compute = nullptr; // this slot's compute stream and private workspace (shared by both slots when overlap is off)
@@ -43,6 +44,8 @@ struct FrameStream {
     int stages = 3; // stm_stream_set_stages: 3, optionally with 0x200 / 0x400 / 0x800 / 0x2000
     float t_alpha = 0.5f, t_disp = 1.5f; // stm_stream_set_temporal: the parameters of the temporal step (0x2000) and their defaults
     int t_color = 24;
+    int in_format = 0, in_matrix = 0; // stm_stream_set_input: 0 = side-by-side BGR, 1 = NV12 (Y plane, then the UV plane; pitch Wsbs)
+    size_t in_bytes = 0;              // what a submit copies and uploads: in_sz, or H * Wsbs * 3 / 2 for NV12
     Slot slot[2];
     long submitted = 0, collected = 0;
 };
@@ -60,6 +63,7 @@ void *stm_stream_create(int num_rows, int num_cols_sbs, int num_cols, int num_ro
     f->N = num_views; f->angle = angle; f->D = num_disp; f->zd = zero_disp; f->ad = ad_coeff; f->ce = census_coeff;
     f->ucd = ucd; f->lcd = lcd; f->usd = usd; f->lsd = lsd; f->thresh_s = thresh_s; f->thresh_h = thresh_h;
     f->in_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
+    f->in_bytes = f->in_sz;
     f->out_sz = (size_t)num_rows_out * num_cols_out * elem_sz;
     f->hw = (size_t)num_rows * num_cols;
     STM_CHECK(hipGetDevice(&f->dev));
@@ -145,6 +149,40 @@ int stm_stream_set_temporal(void *h, float alpha, int thresh_color, float thresh
     return 0;
 }
 
+// The input format of the stream's frames (stm_hip.h): 0 = BGR, 1 = NV12 with `matrix`.  The slots' input buffers, sized for a BGR
+// frame, hold the NV12 frame's two planes; the split images a slot's frames convert into are allocated here.  Only before the first
+// submit.  Returns 0, or -1 with the error recorded.
+int stm_stream_set_input(void *h, int format, int matrix)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (format != 0 && format != 1) {
+        stm::fail("stream_set_input: format must be 0 (side-by-side BGR) or 1 (NV12)", "format", __FILE__, __LINE__);
+        return -1;
+    }
+    if (f->submitted > 0) {
+        stm::fail("stream_set_input: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    if (format == 1) {
+        if (f->Wsbs & 1) { // the UV plane follows the Y plane with the same pitch
+            stm::fail("stream_set_input: NV12 needs an even num_cols_sbs", "num_cols_sbs", __FILE__, __LINE__);
+            return -1;
+        }
+        if (!stm::nv12_args_ok("stream_set_input", f->H, f->Wsbs, f->W, "num_cols", f->Wsbs, f->Wsbs, matrix)) return -1;
+        for (Slot &s : f->slot)
+            if (!s.d_img_l) {
+                STM_CHECK(hipMalloc((void **)&s.d_img_l, f->hw * f->E));
+                STM_CHECK(hipMalloc((void **)&s.d_img_r, f->hw * f->E));
+            }
+        if (stm::failed()) return -1;
+    }
+    f->in_format = format;
+    f->in_matrix = format == 1 ? matrix : 0;
+    f->in_bytes = format == 1 ? (size_t)f->H * f->Wsbs * 3 / 2 : f->in_sz;
+    return 0;
+}
+
 // Stage frame `submitted`; at most two frames may be in flight (collect the older one first).
 // Returns the frame's index, or -1 when both slots are still uncollected.
 long stm_stream_submit(void *h, const unsigned char *img_sbs)
@@ -158,15 +196,19 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     if (caller_dev != f->dev) STM_CHECK(hipSetDevice(f->dev));
     // the caller's buffer is free again when this returns (as with adcensus_stm); a frame that was written straight into the
     // slot's pinned buffer (stm_stream_input_buffer) needs no copy
-    if (img_sbs && img_sbs != s.h_in) memcpy(s.h_in, img_sbs, f->in_sz);
+    if (img_sbs && img_sbs != s.h_in) memcpy(s.h_in, img_sbs, f->in_bytes);
     // temporal stabilisation: frame k reads the input and the maps of frame k - 1, which live in the other slot.  So the upload
     // into this slot's d_in waits until the other slot's frame (which may still be reading this d_in as ITS history) is done,
     // and this frame's compute waits for the other slot's outputs.  The two frames in flight then no longer overlap on the GPU;
     // upload and download still do.  The other slot's ev_done was recorded by the previous submit.
     Slot &other = f->slot[(f->submitted & 1) ^ 1];
     const bool temporal = (f->stages & 0x2000) != 0, history = temporal && f->submitted > 0;
-    if (history) STM_CHECK(hipStreamWaitEvent(f->s_in, other.ev_done, 0));
-    STM_CHECK(hipMemcpyAsync(s.d_in, s.h_in, f->in_sz, hipMemcpyHostToDevice, f->s_in));
+    // In NV12 mode the history is the other slot's converted split images (d_img_l / d_img_r), which no upload touches, and this
+    // slot's d_in was last read by this slot's own previous frame, collected before the slot was handed out again: the upload
+    // waits for nothing.  This frame's compute still waits for the other slot's frame: it reads that frame's images and maps, and
+    // writes the images that frame reads as ITS history.
+    if (history && f->in_format == 0) STM_CHECK(hipStreamWaitEvent(f->s_in, other.ev_done, 0));
+    STM_CHECK(hipMemcpyAsync(s.d_in, s.h_in, f->in_bytes, hipMemcpyHostToDevice, f->s_in));
     STM_CHECK(hipEventRecord(s.ev_in, f->s_in));
     STM_CHECK(hipStreamWaitEvent(s.s_compute, s.ev_in, 0));
     if (history) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
@@ -175,6 +217,14 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     stm::ws_private_bind(s.ws);
     auto pipeline = [&]() {
         stm::ApiNest nest; // a failed upload above must survive the nested call's argument screen
+        if (f->in_format == 1) { // NV12: the slot's images receive the conversion; with 0x2000 the other slot's images and maps are the history
+            stm_d_adcensus_stm_nv12(s.d_in, f->Wsbs, s.d_in + (size_t)f->H * f->Wsbs, f->Wsbs, f->in_matrix, s.d_dl, s.d_dr, s.d_out, f->H,
+                                    f->Wsbs, f->W, f->Hout, f->Wout, f->E, f->N, f->angle, f->D, f->zd, f->ad, f->ce, f->ucd, f->lcd,
+                                    f->usd, f->lsd, f->thresh_s, f->thresh_h, f->stages, history ? other.d_img_l : nullptr,
+                                    history ? other.d_img_r : nullptr, history ? other.d_dl : nullptr, history ? other.d_dr : nullptr,
+                                    f->t_alpha, f->t_color, f->t_disp, s.d_img_l, s.d_img_r);
+            return;
+        }
         if (temporal) { // the history pointers are fixed per slot: a captured frame (never the stream's first) replays them
             stm_d_adcensus_stm_t(s.d_in, s.d_dl, s.d_dr, s.d_out, f->H, f->Wsbs, f->W, f->Hout, f->Wout, f->E, f->N, f->angle, f->D,
                                  f->zd, f->ad, f->ce, f->ucd, f->lcd, f->usd, f->lsd, f->thresh_s, f->thresh_h, f->stages,
@@ -284,6 +334,8 @@ void stm_stream_destroy(void *h)
         STM_CHECK(hipFree(s.d_in)); STM_CHECK(hipFree(s.d_out)); STM_CHECK(hipFree(s.d_dl)); STM_CHECK(hipFree(s.d_dr));
         STM_CHECK(hipEventDestroy(s.ev_in)); STM_CHECK(hipEventDestroy(s.ev_done)); STM_CHECK(hipEventDestroy(s.ev_out));
         if (s.gexec) STM_CHECK(hipGraphExecDestroy(s.gexec));
+        if (s.d_img_l) STM_CHECK(hipFree(s.d_img_l));
+        if (s.d_img_r) STM_CHECK(hipFree(s.d_img_r));
     }
     stm::ws_private_destroy(f->slot[0].ws);
     STM_CHECK(hipStreamDestroy(f->slot[0].s_compute));

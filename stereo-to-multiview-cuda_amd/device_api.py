@@ -82,6 +82,56 @@ def d_adcensus_stm_t(sbs, disp_l, disp_r, interlaced, p, stages=3, prev_sbs=None
                                None if prev_disp_r is None else _p(prev_disp_r), float(alpha), int(thresh_color), float(thresh_disp))
 
 
+def _nv12_planes(y, uv, num_cols_sbs):
+    """(H, Wsbs, pitch_y, pitch_uv) of a pair of 2-D uint8 plane tensors whose rows may be pitched (stride(0) >= the row, stride(1) == 1)"""
+    for t in (y, uv):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1)
+    H = y.shape[0]
+    Wsbs = y.shape[1] if num_cols_sbs is None else num_cols_sbs
+    assert uv.shape[0] * 2 == H and y.shape[1] >= Wsbs and uv.shape[1] >= 2 * ((Wsbs + 1) // 2)
+    return H, Wsbs, y.stride(0), uv.stride(0)
+
+
+def d_demux_nv12(img_l, img_r, y, uv, matrix=0, num_cols_sbs=None):
+    """stm_d_demux_nv12: the two views of a side-by-side NV12 frame converted to BGR into img_l / img_r (uint8 [H][W][E], only the
+    first three bytes of a pixel are written).  y uint8 [H][>= Wsbs] and uv uint8 [H / 2][>= Wsbs] are 2-D tensors whose row
+    stride is the plane's pitch (a view into a larger allocation is fine); matrix: 0 / 1 = BT.601 / BT.709 limited range, 2 / 3 =
+    BT.601 / BT.709 full range."""
+    H, Wsbs, pitch_y, pitch_uv = _nv12_planes(y, uv, num_cols_sbs)
+    W, E = img_l.shape[1], img_l.shape[2]
+    for t in (img_l, img_r):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    _use_current_stream()
+    lib().stm_d_demux_nv12(_p(img_l), _p(img_r), _p(y), pitch_y, _p(uv), pitch_uv, H, Wsbs, W, E, int(matrix))
+
+
+def d_adcensus_stm_nv12(y, uv, disp_l, disp_r, interlaced, p, stages=3, matrix=0, img_l=None, img_r=None, prev_img_l=None, prev_img_r=None,
+                        prev_disp_l=None, prev_disp_r=None, alpha=TEMPORAL_DEFAULTS[0], thresh_color=TEMPORAL_DEFAULTS[1],
+                        thresh_disp=TEMPORAL_DEFAULTS[2], num_cols_sbs=None, elem_sz=3):
+    """stm_d_adcensus_stm_nv12: d_adcensus_stm_t on a side-by-side NV12 frame (planes as for d_demux_nv12), the conversion fused
+    into the frame's first kernel.  img_l / img_r (uint8 [H][W][E], optional, required with STAGE_TEMPORAL) receive the converted
+    split images: they are the next frame's prev_img_l / prev_img_r.  elem_sz is taken from img_l where that is given."""
+    H, Wsbs, pitch_y, pitch_uv = _nv12_planes(y, uv, num_cols_sbs)
+    W = disp_l.shape[1]
+    assert disp_l.shape == (H, W) and disp_r.shape == (H, W) and disp_l.dtype == torch.float32
+    E = elem_sz if img_l is None else img_l.shape[2]
+    for t in (img_l, img_r, prev_img_l, prev_img_r):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    for t in (prev_disp_l, prev_disp_r):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
+    Ho, Wo = interlaced.shape[0], interlaced.shape[1]
+
+    def opt(t):
+        return None if t is None else _p(t)
+    _use_current_stream()
+    lib().stm_d_adcensus_stm_nv12(_p(y), pitch_y, _p(uv), pitch_uv, int(matrix), _p(disp_l), _p(disp_r), _p(interlaced), H, Wsbs, W, Ho, Wo, E,
+                                  p.num_views, p.angle, p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff, p.ucd, p.lcd, p.usd, p.lsd,
+                                  p.thresh_s, p.thresh_h, stages, opt(prev_img_l), opt(prev_img_r), opt(prev_disp_l), opt(prev_disp_r),
+                                  float(alpha), int(thresh_color), float(thresh_disp), opt(img_l), opt(img_r))
+
+
 def d_adcensus_stm_2s(sbs, disp_l, disp_r, interlaced, p, disp_rows, disp_cols, disp_scale, stages=3):
     """stm_d_adcensus_stm_2s: the reduced-resolution frame (match at disp_rows x disp_cols, maps scaled up by 1 / disp_scale,
     views rendered at full size) with a `stages` word: 3, optionally OR-ed with 0x100, STAGE_SUBPIXEL, STAGE_INTERP (on the

@@ -337,3 +337,19 @@ def bmp_write(path, img):
     img, pi = _u8(img)
     if lib().stm_bmp_write(path.encode(), pi, img.shape[0], img.shape[1]) != 0:
         raise IOError("stm_bmp_write failed for %s" % path)
+
+
+def demux_nv12(y, uv, num_cols, elem_sz=3, matrix=0, num_cols_sbs=None):
+    """stm_demux_nv12: the two views (each uint8 [H][num_cols][elem_sz], BGR in the first three bytes, 0 past them) of a
+    side-by-side NV12 frame.  y uint8 [H][>= Wsbs] and uv uint8 [H / 2][>= Wsbs] are 2-D arrays whose row stride is the plane's
+    pitch (a view into a larger buffer is fine); matrix: 0 / 1 = BT.601 / BT.709 limited range, 2 / 3 = BT.601 / BT.709 full."""
+    for a in (y, uv):
+        assert a.dtype == np.uint8 and a.ndim == 2 and (a.shape[1] == 1 or a.strides[1] == 1)
+    H = y.shape[0]
+    Wsbs = y.shape[1] if num_cols_sbs is None else num_cols_sbs
+    assert uv.shape[0] * 2 == H and y.shape[1] >= Wsbs and uv.shape[1] >= 2 * ((Wsbs + 1) // 2)
+    img_l = np.zeros((H, num_cols, elem_sz), np.uint8)
+    img_r = np.zeros_like(img_l)
+    lib().stm_demux_nv12(img_l.ctypes.data_as(u8p), img_r.ctypes.data_as(u8p), y.ctypes.data_as(u8p), y.strides[0],
+                         uv.ctypes.data_as(u8p), uv.strides[0], H, Wsbs, num_cols, elem_sz, int(matrix))
+    return img_l, img_r

@@ -106,3 +106,28 @@ def tiled_pair(left, right, H, W):
 def tiled_sbs_frame(left, right, H, W):
     L, R = tiled_pair(left, right, H, W)
     return np.ascontiguousarray(np.concatenate([L, R], axis=1))
+
+
+# (Kr, Kb), limited range?  -- the four conversion matrices of stm_demux_nv12, in its numbering
+NV12_MATRICES = ((0.299, 0.114, True), (0.2126, 0.0722, True), (0.299, 0.114, False), (0.2126, 0.0722, False))
+
+
+def bgr_to_nv12(frame, matrix=0):
+    """A BGR frame uint8 [H][W][3] (H, W even) as NV12: (y uint8 [H][W], uv uint8 [H / 2][W], U and V interleaved), chroma
+    the mean of each 2 x 2 block, in floating point and rounded.  It only manufactures inputs for the NV12 calls: the exact
+    integer conversion is the library's, in the other direction."""
+    kr, kb, limited = NV12_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    H, W, _ = frame.shape
+    assert H % 2 == 0 and W % 2 == 0
+    b, g, r = (frame[:, :, c].astype(np.float64) for c in range(3))
+    yf = kr * r + kg * g + kb * b
+    u = (b - yf) / (2.0 * (1.0 - kb))
+    v = (r - yf) / (2.0 * (1.0 - kr))
+    ys, cs, yo = (219.0 / 255.0, 224.0 / 255.0, 16.0) if limited else (1.0, 1.0, 0.0)
+    y = np.clip(np.rint(yf * ys + yo), 0, 255).astype(np.uint8)
+    uv = np.empty((H // 2, W), np.uint8)
+    for k, c in enumerate((u, v)):
+        m = c.reshape(H // 2, 2, W // 2, 2).mean(axis=(1, 3))
+        uv[:, k::2] = np.clip(np.rint(m * cs + 128.0), 0, 255).astype(np.uint8)
+    return y, uv

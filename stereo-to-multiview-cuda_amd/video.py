@@ -13,10 +13,14 @@ from ._lib import f32p, lib, u8p
 
 
 class FrameStream:
-    """Pipelined adcensus_stm over a sequence: submit() frames, collect() results in order (two in flight)."""
+    """Pipelined adcensus_stm over a sequence: submit() frames, collect() results in order (two in flight).
+    input_format "bgr" (the default): a frame is a side-by-side BGR array uint8 [H][2W][3].  "nv12": a frame is uint8 [H * 3 / 2][2W],
+    the Y plane followed by the interleaved UV plane, as a decoder or read_nv12_sequence delivers it; `matrix` selects the colour
+    conversion (stm_demux_nv12: 0 / 1 = BT.601 / BT.709 limited range, 2 / 3 = full range)."""
 
-    def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3):
+    def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0):
         self.H, self.W = num_rows, num_cols
+        self.in_shape = (num_rows, 2 * num_cols, 3)
         self.Ho, self.Wo = out_rows or num_rows, out_cols or num_cols
         p = params
         self._h = lib().stm_stream_create(num_rows, 2 * num_cols, num_cols, self.Ho, self.Wo, 3, p.num_views, p.angle,
@@ -24,6 +28,16 @@ class FrameStream:
                                           p.thresh_s, p.thresh_h)
         if stages != 3:
             self.set_stages(stages)
+        if input_format != "bgr":
+            self.set_input(input_format, matrix)
+
+    def set_input(self, input_format, matrix=0):
+        """stm_stream_set_input: "bgr" or "nv12" with its conversion matrix; only before the first submit.  Raises ValueError where
+        the library refuses."""
+        fmt = {"bgr": 0, "nv12": 1}.get(input_format, -1)
+        if int(lib().stm_stream_set_input(self._h, fmt, int(matrix))) != 0:
+            raise ValueError("stm_stream_set_input(%r, %d) refused: %s" % (input_format, matrix, lib().stm_last_error().decode()))
+        self.in_shape = (self.H * 3 // 2, 2 * self.W) if fmt == 1 else (self.H, 2 * self.W, 3)
 
     def set_stages(self, stages):
         """stm_stream_set_stages: 3, optionally OR-ed with 0x200 (sub-pixel), 0x400 (outlier interpolation), 0x800 (linear
@@ -41,16 +55,16 @@ class FrameStream:
 
     def submit(self, sbs):
         sbs = np.ascontiguousarray(sbs, dtype=np.uint8)
-        assert sbs.shape == (self.H, 2 * self.W, 3)
+        assert sbs.shape == self.in_shape
         return int(lib().stm_stream_submit(self._h, sbs.ctypes.data_as(u8p)))
 
     def input_buffer(self):
-        """The pinned buffer the next submit() will use, as an (H, 2W, 3) uint8 view (None while that slot is uncollected):
-        write the frame into it and call submit_inplace() -- no host copy."""
+        """The pinned buffer the next submit() will use, as an (H, 2W, 3) uint8 view -- (H * 3 / 2, 2W) in NV12 mode -- or None
+        while that slot is uncollected: write the frame into it and call submit_inplace() -- no host copy."""
         p = lib().stm_stream_input_buffer(self._h)
         if not p:
             return None
-        return np.ctypeslib.as_array(C.cast(p, u8p), shape=(self.H, 2 * self.W, 3))
+        return np.ctypeslib.as_array(C.cast(p, u8p), shape=self.in_shape)
 
     def submit_inplace(self):
         return int(lib().stm_stream_submit(self._h, None))
@@ -84,15 +98,17 @@ class FrameStream:
             pass
 
 
-def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None):
+def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
+    input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
     stabilisation); temporal: (alpha, thresh_color, thresh_disp) for FrameStream.set_temporal, None = the defaults."""
     fs = None
     pending = 0
     for sbs in frames:
         if fs is None:
-            fs = FrameStream(sbs.shape[0], sbs.shape[1] // 2, params, out_rows, out_cols, stages)
+            rows = sbs.shape[0] * 2 // 3 if input_format == "nv12" else sbs.shape[0]
+            fs = FrameStream(rows, sbs.shape[1] // 2, params, out_rows, out_cols, stages, input_format, matrix)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:
@@ -110,6 +126,21 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
 def read_bmp_sequence(directory, pattern="*.bmp"):
     for path in sorted(glob.glob(os.path.join(directory, pattern))):
         yield bmp_io.read_bmp(path)
+
+
+def read_nv12_sequence(path, num_rows, num_cols_sbs):
+    """The frames of a raw .yuv file of concatenated NV12 frames (num_rows x num_cols_sbs luma, no padding), each as a uint8
+    [num_rows * 3 / 2][num_cols_sbs] array: the Y plane, then the interleaved UV plane.  A trailing partial frame is an error."""
+    assert num_rows % 2 == 0 and num_cols_sbs % 2 == 0
+    n = num_rows * num_cols_sbs * 3 // 2
+    with open(path, "rb") as f:
+        while True:
+            buf = f.read(n)
+            if not buf:
+                return
+            if len(buf) != n:
+                raise ValueError("%s: %d trailing bytes are no whole %d x %d NV12 frame" % (path, len(buf), num_cols_sbs, num_rows))
+            yield np.frombuffer(buf, np.uint8).reshape(num_rows * 3 // 2, num_cols_sbs)
 
 
 def normalize_minmax_u8(a):

@@ -5,12 +5,16 @@ side-by-side BMP frames instead of a video file, BMP outputs instead of a window
 usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <num disp> <zero disp> <ad coeff>
                     <census coeff> <ucd> <lcd> <usd> <lsd> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel] [--linear-warp]
                     [--temporal [--temporal-alpha A] [--temporal-color C] [--temporal-disp T]]
+                    [--nv12 ROWS COLS_SBS [--matrix M]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
 --linear-warp (an addition, off by default): frame bit 0x800, the views' warps fetched at the fractional coordinate.
 --temporal (an addition, off by default): frame bit 0x2000, every frame's maps stabilised against the previous frame's where
 neither colour nor disparity moved; --temporal-alpha (0.5), --temporal-color (24) and --temporal-disp (1.5) set its parameters.
+--nv12 ROWS COLS_SBS (an addition): <frames dir> is instead one raw .yuv file of concatenated side-by-side NV12 frames of ROWS rows
+and COLS_SBS columns, converted on the GPU inside the frame's first kernel; --matrix M (0) picks the conversion: 0 / 1 = BT.601 /
+BT.709 limited range, 2 / 3 = BT.601 / BT.709 full range.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -35,6 +39,21 @@ def main(argv):
                 return -1
             temporal[slot] = conv(argv[at + 1])
             del argv[at:at + 2]
+    nv12, matrix = None, 0
+    if "--nv12" in argv:
+        at = argv.index("--nv12")
+        if at + 2 >= len(argv):
+            print(__doc__)
+            return -1
+        nv12 = (int(argv[at + 1]), int(argv[at + 2]))
+        del argv[at:at + 3]
+    if "--matrix" in argv:
+        at = argv.index("--matrix")
+        if at + 1 >= len(argv) or nv12 is None:
+            print(__doc__)
+            return -1
+        matrix = int(argv[at + 1])
+        del argv[at:at + 2]
     if len(argv) not in (16, 17):
         print(__doc__)
         return -1
@@ -46,11 +65,12 @@ def main(argv):
                         census_coeff=float(a[8]), ucd=float(a[9]), lcd=float(a[10]), usd=int(a[11]), lsd=int(a[12]),
                         thresh_s=int(a[13]), thresh_h=float(a[14]))
     out_w, out_h = int(a[3]), int(a[4])
-    out_dir = a[15] if len(a) > 15 else os.path.join(a[0], "out")
+    out_dir = a[15] if len(a) > 15 else os.path.join(a[0] if nv12 is None else os.path.dirname(os.path.abspath(a[0])), "out")
+    frames = video.read_bmp_sequence(a[0]) if nv12 is None else video.read_nv12_sequence(a[0], *nv12)
     t0 = time.perf_counter()
     n = 0
-    for (k, dl, dr, inter) in video.process_sequence(video.read_bmp_sequence(a[0]), p, out_h, out_w, stages,
-                                                       tuple(temporal) if stages & 0x2000 else None):
+    for (k, dl, dr, inter) in video.process_sequence(frames, p, out_h, out_w, stages, tuple(temporal) if stages & 0x2000 else None,
+                                                       "bgr" if nv12 is None else "nv12", matrix):
         video.write_outputs(out_dir, k, dl, dr, inter)
         n += 1
     dt = time.perf_counter() - t0
