@@ -96,6 +96,13 @@ void        stm_set_agg_variant(int v);
  * (d_dr_irv.cu:36 -- the bin INDEX, SURVEY A-Q17 iv); 1 = the paper's rule, (winning bin's COUNT) / S > thresh_h (Mei et al.,
  * region voting).  An addition: the reference has no such switch. */
 void        stm_set_irv_paper_ratio(int on);
+/* The calling thread's display geometry (see stm_mux_multiview_lens for the definition and the argument rules); the default is
+ * mode 0.  With mode != 0 every frame call that renders -- stm_adcensus_stm, stm_d_adcensus_stm, _t, _nv12, and _2 / _2s in both
+ * flavours -- interlaces through that definition instead of the reference's formula; `angle` is then ignored and not screened.
+ * With mode 0 not one launch or argument changes.  Modes 1 and 2 follow stm_set_agg_variant(200) into the un-fused form (every
+ * view written, then interlaced); mode 3 has no views, so it always takes the fused kernel.  This is an output geometry, not a
+ * stage: no `stages` bit belongs to it.  Returns 0, or -1 with stm_last_error set and the thread's geometry unchanged. */
+int         stm_set_lens(int mode, double pitch, double slope, double centre);
 /* ci_adcensus / d_ci_adcensus (the per-stage calls; the frame calls always compute the clean costs): 0 (default) = clean
  * clamped indexing, the canonical form (SURVEY A-Q7); 1 = reproduce the reference's shared-tile strays at d = 0 in columns
  * 160 k (left cost) and 160 k + 159 (right cost): the census term always, the AD term when num_disp - zero_disp <= zero_disp
@@ -252,6 +259,58 @@ void stm_mux_multiview(unsigned char **views, unsigned char *out_data, int num_v
                        int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz);
 void stm_d_mux_multiview(unsigned char **d_views, unsigned char *d_out_data, int num_views, float angle,
                          int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz);
+/* Calibrated lenticular interlacing (an addition: the reference's interlacer, mux_multiview_kernel_2 d_mux_multiview.cu:60-73, fixes
+ * the lens pitch at exactly num_views sub-pixels, has no phase offset and rounds the slant's row period to an integer -- it fits
+ * one panel).  A lenticular panel is calibrated by three numbers:
+ *   pitch   (double) sub-pixels per lens
+ *   slope   (double) the lens shift in sub-pixels per output row
+ *   centre  (double) the phase offset in lenses
+ * and `mode` selects what a sub-pixel shows.  Take output pixel (tx, ty) and byte c of the pixel.  Its sub-pixel index is
+ * k = 2 - c: R is the first sub-pixel, as in the reference, where R takes r_view, G r_view + 1 and B r_view + 2.  Everything is
+ * double, one operation per line, with no contraction:
+ *   s  = 3*tx + k                      (int)
+ *   t1 = (double)ty * slope
+ *   t2 = (double)s + t1
+ *   t3 = t2 / pitch                    (correctly rounded)
+ *   t4 = t3 + centre
+ *   a  = t4 - floor(t4);  if (a >= 1.0) a = 0.0          a in [0,1): the sub-pixel's lens phase
+ * (a t4 that is not finite -- a slope or centre at the end of the double range -- gives a = 0 as well.)
+ * (xs, ys) and the 4-neighbour sampler are the reference's own (fast_bilinear_interp, d_mux_multiview.cu:10-36), as in
+ * stm_mux_multiview; below bilinear_u8(view, c, xs, ys) is that sampler on byte c.  N = num_views.
+ * mode 1, nearest view:
+ *   g = a * (double)N
+ *   v = min((int)g, N - 1)
+ *   out = bilinear_u8(views[v], c, xs, ys)
+ * mode 2, blended:
+ *   g  = a * (double)N
+ *   g  = g - 0.5
+ *   g  = min(max(g, 0.0), (double)(N - 1))
+ *   v0 = min((int)g, N - 2)
+ *   w  = (float)(g - (double)v0)
+ *   A  = bilinear_u8(views[v0], c, xs, ys);  B = bilinear_u8(views[v0 + 1], c, xs, ys)
+ *   p  = (float)A * (1.0f - w)
+ *   q  = (float)B * w
+ *   out = (u8)(p + q)
+ * The half-bin at either lens edge shows the end view unblended: the two end views are never mixed.
+ * mode 3, continuous (the frame calls only: it needs the renderer, there are no views):
+ *   g as in mode 2 after the clamp
+ *   u = g / (double)(N - 1)
+ *   shift = (float)(1.0 - u)
+ * and a sample at (x, y, c) is the renderer's general form at this shift: shift_l = -shift, shift_r = (float)(1.0 - (double)shift),
+ * both backward warps (truncating, or linear as frame bit 0x800 says), the masks, the blend, the u8 wrap (stm_dibr_dbm /
+ * stm_dibr_dbm_lin with the frame's gaussian(10, 15) blend), without the shortcut that makes views 0 and N - 1 the two images.
+ * The four neighbours are combined as fast_bilinear_interp does; a neighbour of weight exactly 0 need not be evaluated.  At a bin
+ * centre (g a whole number) the shift is the discrete view's own, so mode 3 is the limit of mode 2.
+ * Argument rules: mode in 0 .. 3 (0 = off: the other arguments are ignored), pitch finite and >= 1, slope and centre finite,
+ * num_views >= 2.  Anything else fails through stm_last_error before anything is launched or written.
+ *
+ * The per-stage calls accept modes 1 and 2 (0 and 3 are errors).  Pixel format as stm_mux_multiview: the first three bytes of a
+ * pixel; the host flavour zeroes the padding, the device flavour leaves it alone.  Parity is against a numpy statement of these
+ * lines (parity unpinned). */
+void stm_mux_multiview_lens(unsigned char **views, unsigned char *out_data, int num_views, int mode, double pitch, double slope,
+                            double centre, int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz);
+void stm_d_mux_multiview_lens(unsigned char **d_views, unsigned char *d_out_data, int num_views, int mode, double pitch, double slope,
+                              double centre, int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz);
 /* d_demux_common.h:10-13  demux_sbs kernel (d_demux_common.cu:8-33) as a host-callable stage */
 void stm_d_demux_sbs(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_img_sbs,
                      int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz);
@@ -499,6 +558,10 @@ int   stm_stream_set_temporal(void *stream, float alpha, int thresh_color, float
  * images, and with 0x2000 the other slot's images and maps are the history.  `matrix` is ignored for format 0.  Only before the
  * first submit.  Returns 0, or -1 with stm_last_error set. */
 int   stm_stream_set_input(void *stream, int format, int matrix);
+/* the display geometry of the stream's frames (stm_set_lens's rules; the default is mode 0).  The stream keeps its own copy and
+ * installs it only for the duration of its frame calls: the calling thread's stm_set_lens neither reaches the stream's frames
+ * (or its captured graph) nor is changed by them.  Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
+int   stm_stream_set_lens(void *stream, int mode, double pitch, double slope, double centre);
 /* waits for the oldest uncollected frame and copies its results out (NULL = skip).  Returns its index or -1. */
 long  stm_stream_collect(void *stream, float *disp_l, float *disp_r, unsigned char *interlaced);
 /* zero-copy variants (at 1080p the two host copies of submit / collect take longer than the frame does on the GPU):

@@ -17,7 +17,7 @@ f32p = C.POINTER(C.c_float)
 u8pp = C.POINTER(u8p)
 f32pp = C.POINTER(f32p)
 vp = C.c_void_p
-i, f = C.c_int, C.c_float
+i, f, d = C.c_int, C.c_float, C.c_double
 
 # name -> argtypes, in the order of include/stm_hip.h.  Device-flavour entries take raw addresses (c_void_p).
 PROTOS = {
@@ -33,6 +33,7 @@ PROTOS = {
     "stm_set_agg_variant": ([i], None),
     "stm_set_irv_paper_ratio": ([i], None),
     "stm_set_ref_quirks": ([i], None),
+    "stm_set_lens": ([i, d, d, d], i),
     "stm_ci_adcensus": ([u8p, u8p, f32pp, f32pp, f, f, i, i, i, i, i], None),
     "stm_d_ci_adcensus": ([vp, vp, vp, vp, f32pp, f32pp, vp, f, f, i, i, i, i, i], None),
     "stm_ca_cross": ([u8p, u8pp, f32pp, f32pp, f, f, i, i, i, i, i, i], None),
@@ -70,6 +71,8 @@ PROTOS = {
     "stm_d_dibr_dfm": ([vp, vp, vp, vp, vp, f, i, i, i], None),
     "stm_mux_multiview": ([u8pp, u8p, i, f, i, i, i, i, i], None),
     "stm_d_mux_multiview": ([vp, vp, i, f, i, i, i, i, i], None),
+    "stm_mux_multiview_lens": ([u8pp, u8p, i, i, d, d, d, i, i, i, i, i], None),
+    "stm_d_mux_multiview_lens": ([vp, vp, i, i, d, d, d, i, i, i, i, i], None),
     "stm_d_demux_sbs": ([vp, vp, vp, i, i, i, i], None),
     "stm_demux_nv12": ([u8p, u8p, u8p, i, u8p, i, i, i, i, i, i], None),
     "stm_d_demux_nv12": ([vp, vp, vp, i, vp, i, i, i, i, i, i], None),
@@ -92,6 +95,7 @@ PROTOS = {
     "stm_stream_set_stages": ([C.c_void_p, i], i),
     "stm_stream_set_temporal": ([C.c_void_p, f, i, f], i),
     "stm_stream_set_input": ([C.c_void_p, i, i], i),
+    "stm_stream_set_lens": ([C.c_void_p, i, d, d, d], i),
     "stm_stream_collect": ([C.c_void_p, f32p, f32p, u8p], C.c_long),
     "stm_stream_input_buffer": ([C.c_void_p], C.c_void_p),
     "stm_stream_collect_view": ([C.c_void_p, C.POINTER(f32p), C.POINTER(f32p), C.POINTER(u8p)], C.c_long),

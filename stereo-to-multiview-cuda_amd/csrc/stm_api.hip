@@ -840,6 +840,40 @@ void stm_mux_multiview(unsigned char **views, unsigned char *out_data, int num_v
     sync();
 }
 
+// the interlacer under a lens geometry (an addition: the reference's interlacer fits one panel); modes 1 and 2 (stm_hip.h)
+void stm_d_mux_multiview_lens(unsigned char **d_views, unsigned char *d_out_data, int num_views, int mode, double pitch, double slope,
+                              double centre, int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz)
+{
+    const char *fn = "d_mux_multiview_lens";
+    if (!args_ok(fn, {{"num_views", num_views, 2}, {"in_rows", in_rows, 1}, {"in_cols", in_cols, 1}, {"out_rows", out_rows, 1},
+                      {"out_cols", out_cols, 1}, {"elem_sz", elem_sz, 3}}))
+        return;
+    if (!lens_params_ok(fn, mode, 1, 2, pitch, slope, centre)) return;
+    launch_mux_lens((const u8 *const *)d_views, d_out_data, num_views, Lens{mode, pitch, slope, centre}, in_rows, in_cols, out_rows,
+                    out_cols, elem_sz);
+}
+void stm_mux_multiview_lens(unsigned char **views, unsigned char *out_data, int num_views, int mode, double pitch, double slope,
+                            double centre, int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz)
+{
+    const char *fn = "mux_multiview_lens";
+    if (!args_ok(fn, {{"num_views", num_views, 2}, {"in_rows", in_rows, 1}, {"in_cols", in_cols, 1}, {"out_rows", out_rows, 1},
+                      {"out_cols", out_cols, 1}, {"elem_sz", elem_sz, 3}}))
+        return;
+    if (!lens_params_ok(fn, mode, 1, 2, pitch, slope, centre)) return;
+    size_t in_sz = (size_t)in_rows * in_cols * elem_sz, out_sz = (size_t)out_rows * out_cols * elem_sz;
+    Workspace::begin(num_views * (in_sz + 256) + out_sz + 8192);
+    std::vector<u8 *> h(num_views);
+    for (int v = 0; v < num_views; ++v) h[v] = up(views[v], in_sz);
+    u8 **dv = Workspace::get<u8 *>(num_views);
+    STM_CHECK(hipMemcpyAsync(dv, h.data(), sizeof(u8 *) * num_views, hipMemcpyHostToDevice, stream()));
+    sync(); // h goes out of scope below
+    u8 *o = Workspace::get<u8>(out_sz);
+    STM_CHECK(hipMemsetAsync(o, 0, out_sz, stream())); // bytes past a pixel's third come back 0
+    launch_mux_lens((const u8 *const *)dv, o, num_views, Lens{mode, pitch, slope, centre}, in_rows, in_cols, out_rows, out_cols, elem_sz);
+    down(out_data, o, out_sz);
+    sync();
+}
+
 void stm_d_demux_sbs(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_img_sbs, int num_rows,
                      int num_cols_sbs, int num_cols_out, int elem_sz)
 {
@@ -1073,6 +1107,21 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
     launch_hitmask_rows(mask_l, mask_r, d_disp_l, d_disp_r, H, W); // :165-176: dibr_occl, bleed(1) x2, occl_to_mask
     launch_gaussian_max(mask_r, blend, gauss2d_table(10, 15.0f), 10, 15.0f, H, W, true); // d_dibr_bwarp.cu:60-63, once per frame
 
+    // a lens geometry (stm_set_lens) replaces the reference's view assignment; `angle` is then neither used nor screened.  Mode 3
+    // renders every sub-pixel at a position of its own -- there are no views to write -- so it takes the fused kernel always
+    const Lens ln = lens();
+    if (ln.mode != 0 && (ln.mode == 3 || (agg_variant() / 100) % 10 != 2)) {
+        launch_synth_mux_lens(img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, d_interlaced, N, ln, H, W, Hout, Wout, elem_sz, linear);
+        return;
+    }
+    if (ln.mode != 0) { // 200: every view written, then interlaced through the lens
+        u8 *views_mem = Workspace::get<u8>((size_t)N * IMG);
+        launch_view_synth_all(views_mem, IMG, N, img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, H, W, elem_sz, linear);
+        u8 **dv = Workspace::get<u8 *>(N);
+        launch_view_table(dv, img_r, img_l, views_mem, IMG, N);
+        launch_mux_lens((const u8 *const *)dv, d_interlaced, N, ln, H, W, Hout, Wout, elem_sz);
+        return;
+    }
     if ((agg_variant() / 100) % 10 != 2) {
         // views + interlacing in one pass: an output pixel synthesises exactly the samples it interlaces (stm_k_synth_mux)
         const float yi = mux_y_interval(N, angle, elem_sz);

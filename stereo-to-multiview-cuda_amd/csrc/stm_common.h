@@ -63,6 +63,17 @@ struct ProfScope {
 };
 
 int agg_variant();
+// The display geometry of the lenticular interlacer (stm_set_lens, include/stm_hip.h): mode 0 = off (the reference's interlacer),
+// 1 = nearest view, 2 = two views blended, 3 = every sub-pixel rendered at its own continuous position (frame calls only).
+// One per host thread; a frame stream installs its own copy around its frame calls (stm_stream_set_lens).
+struct Lens {
+    int mode;
+    double pitch, slope, centre;
+};
+Lens lens();
+void set_lens(const Lens &l);
+// the argument rules of a lens geometry with mode in [mode_lo, mode_hi]; false with the error recorded
+bool lens_params_ok(const char *fn, int mode, int mode_lo, int mode_hi, double pitch, double slope, double centre);
 int irv_paper_ratio(); // stm_set_irv_paper_ratio: accept on count / S instead of the reference's bin index / S (SURVEY A-Q17 iv)
 // Timing experiments (skip loads / sweeps / stores; results NOT valid) exist only in the separate libstm_hip_timing.so
 // (make timing, -DSTM_TIMING): in the product library every STM_DBG test is the constant false and stm_set_agg_variant
@@ -227,6 +238,12 @@ void launch_synth_mux(const u8 *img_l, const u8 *img_r, const float *disp_l, con
                       int Wout, int elem_sz, int variant, bool linear = false);
 void launch_mux(const u8 *const *d_views, u8 *out, int N, float y_interval, float inv_y_interval, int ymod,
                 int Hin, int Win, int Hout, int Wout, int elem_sz, int variant);
+// the lenticular interlacer (stm_set_lens): launch_mux on a table of views (ln.mode 1 or 2) and launch_synth_mux (ln.mode 1, 2 or 3)
+// with each sub-pixel's view taken from its lens phase
+void launch_mux_lens(const u8 *const *d_views, u8 *out, int N, const Lens &ln, int Hin, int Win, int Hout, int Wout, int elem_sz);
+void launch_synth_mux_lens(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l,
+                           const float *mask_r, const float *blend, u8 *out, int N, const Lens &ln, int Hin, int Win, int Hout, int Wout,
+                           int elem_sz, bool linear);
 // aggregation on the matrix pipe (stm_kernels_aggm.hip): the frame pipeline's cost -> H -> V, V -> H + WTA
 struct PQViews { // both views of a frame; a / b = the two PQ volumes of a view
     const uint32_t *pk[2], *cen[2];

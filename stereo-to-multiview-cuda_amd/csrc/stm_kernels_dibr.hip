@@ -609,4 +609,214 @@ void launch_mux(const u8 *const *d_views, u8 *out, int N, float y_interval, floa
     STM_CHECK_LAUNCH();
 }
 
+// ------------------------------------------------------------------ calibrated lenticular interlacing (stm_hip.h, stm_set_lens)
+// mux_multiview_kernel_2 takes a sub-pixel's view from (3 tx + int((ty % round(yi) + 1) N / yi)) % N: a lens pitch of exactly N
+// sub-pixels, no phase offset, a slant whose row period is rounded to an integer.  Here the view follows from the panel's
+// calibration: the lens phase of sub-pixel k = 2 - c of output pixel (tx, ty), in double, one operation per line (the file is
+// compiled -ffp-contract=off and the f64 division is the correctly rounded one).  The sampling position (xs, ys) and the
+// 4-neighbour sampler stay the reference's.
+__device__ __forceinline__ double lens_phase(int tx, int ty, int c, const Lens &g)
+{
+    const int s = 3 * tx + (2 - c);
+    const double t1 = (double)ty * g.slope;
+    const double t2 = (double)s + t1;
+    const double t3 = t2 / g.pitch;
+    const double t4 = t3 + g.centre;
+    const double a = t4 - floor(t4);
+    return a < 1.0 ? a : 0.0; // a >= 1: t4 was a tiny negative number and the subtraction rounded to 1 (a t4 that is not finite lands here too)
+}
+// what a phase selects -- MODE 1: the nearest view v; MODE 2: the views v, v + 1 and the weight w of the second; MODE 3: the shift
+// of the sub-pixel's own position between the cameras
+template <int MODE>
+__device__ __forceinline__ void lens_pick(double a, int N, int &v, float &w, float &shift)
+{
+    double g = a * (double)N;
+    v = 0; w = 0.0f; shift = 0.0f;
+    if constexpr (MODE == 1) {
+        v = min((int)g, N - 1);
+    } else {
+        g = g - 0.5;
+        g = fmin(fmax(g, 0.0), (double)(N - 1)); // the half-bin at either lens edge shows the end view
+        if constexpr (MODE == 2) {
+            v = min((int)g, N - 2);
+            w = (float)(g - (double)v);
+        } else {
+            const double u = g / (double)(N - 1);
+            shift = (float)(1.0 - u);
+        }
+    }
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void stm_k_mux_lens(const u8 *const *__restrict__ views, u8 *__restrict__ out, int N, Lens g, int Hin,
+                                                      int Win, int Hout, int Wout, int elem_sz)
+{
+    const int tx = blockIdx.x * 256 + threadIdx.x, ty = blockIdx.y;
+    if (tx >= Wout) return;
+    float xs = ((float)tx / (float)Wout) * (float)Win;
+    xs = fminf(fmaxf(xs, 0.0f), (float)(Win - 1));
+    float ys = ((float)ty / (float)Hout) * (float)Hin;
+    ys = fminf(fmaxf(ys, 0.0f), (float)(Hin - 1));
+    const size_t o = ((size_t)tx + (size_t)ty * Wout) * elem_sz;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int v;
+        float w, shift;
+        lens_pick<MODE>(lens_phase(tx, ty, c, g), N, v, w, shift);
+        const u8 A = bilinear_u8(views[v], elem_sz, c, xs, ys, Win, Hin);
+        if constexpr (MODE == 1) {
+            out[o + c] = A;
+        } else {
+            const u8 B = bilinear_u8(views[v + 1], elem_sz, c, xs, ys, Win, Hin);
+            const float p = (float)A * (1.0f - w);
+            const float q = (float)B * w;
+            out[o + c] = (u8)(p + q);
+        }
+    }
+}
+void launch_mux_lens(const u8 *const *d_views, u8 *out, int N, const Lens &ln, int Hin, int Win, int Hout, int Wout, int elem_sz)
+{
+    ProfScope p("mux");
+    if (ln.mode == 1)
+        STM_LAUNCH(stm_k_mux_lens<1>, dim3(cdiv(Wout, 256), Hout), dim3(256), 0, stream(), d_views, out, N, ln, Hin, Win, Hout, Wout, elem_sz);
+    else
+        STM_LAUNCH(stm_k_mux_lens<2>, dim3(cdiv(Wout, 256), Hout), dim3(256), 0, stream(), d_views, out, N, ln, Hin, Win, Hout, Wout, elem_sz);
+    STM_CHECK_LAUNCH();
+}
+
+// The fused renderer under a lens geometry: stm_k_synth_mux with each sub-pixel's view -- or, in mode 3, its own shift -- taken
+// from the lens phase.  One thread per output pixel; what a neighbour contributes besides the two warped colours (its two
+// disparities, two masks and blend weight) is loaded once and serves the three channels.
+struct LensNb {
+    size_t row;
+    int x;
+    float dl, dr, ml, mr, m;
+};
+__device__ __forceinline__ LensNb lens_nb(const SynthArgs &a, int x, int y, int W)
+{
+    LensNb n;
+    n.row = (size_t)y * W;
+    n.x = x;
+    const size_t p = n.row + x;
+    n.dl = a.disp_l[p]; n.dr = a.disp_r[p];
+    n.ml = a.mask_l[p]; n.mr = a.mask_r[p];
+    n.m = a.blend[p];
+    return n;
+}
+// synth_sample's general branch at an arbitrary shift (no end-view shortcut)
+template <bool LINEAR>
+__device__ __forceinline__ u8 lens_sample_shift(const SynthArgs &a, const LensNb &n, float shift, int c, int W, int elem_sz)
+{
+    const float wmax = (float)(W - 1);
+    const float shift_l = -shift;                       // d_dibr_bwarp.cu:56
+    const float shift_r = (float)(1.0 - (double)shift); // :57
+    float sd = n.dr * shift_l;
+    float fx = (float)n.x + sd;
+    const float fxl = fminf(fmaxf(fx, 0.0f), wmax);
+    sd = n.dl * shift_r;
+    fx = (float)n.x + sd;
+    const float fxr = fminf(fmaxf(fx, 0.0f), wmax);
+    const float one_m = 1.0f - n.m;
+    const u8 pa = (u8)((float)warp_tap<LINEAR>(a.img_l, n.row, fxl, c, W, elem_sz) * n.mr); // left-sourced pixel
+    const u8 pb = (u8)((float)warp_tap<LINEAR>(a.img_r, n.row, fxr, c, W, elem_sz) * n.ml); // right-sourced pixel
+    const float cb = one_m * (float)pa;
+    const float ca = n.m * (float)pb;
+    return (u8)((u8)cb + (u8)ca);
+}
+// CONTINUOUS = false: synth_sample of the discrete view v; true: the sample at `shift`
+template <bool LINEAR, bool CONTINUOUS>
+__device__ __forceinline__ u8 lens_sample(const SynthArgs &a, const LensNb &n, int N, int v, float shift, int c, int W, int elem_sz)
+{
+    if constexpr (!CONTINUOUS) {
+        if (v == 0) return a.img_r[(n.row + n.x) * elem_sz + c];
+        if (v == N - 1) return a.img_l[(n.row + n.x) * elem_sz + c];
+        shift = (float)(1.0 - ((1.0 * (double)(float)v) / ((double)(float)N - 1.0))); // d_io.cu:189
+    }
+    return lens_sample_shift<LINEAR>(a, n, shift, c, W, elem_sz);
+}
+// synth_bilinear on the loaded neighbours (a neighbour of weight exactly 0 is not evaluated)
+template <bool LINEAR, bool CONTINUOUS>
+__device__ __forceinline__ u8 lens_bilinear(const SynthArgs &a, const LensNb &n00, const LensNb &n01, const LensNb &n10, const LensNb &n11,
+                                            float wx, float wy, int N, int v, float shift, int c, int W, int elem_sz)
+{
+    const float v00 = (float)lens_sample<LINEAR, CONTINUOUS>(a, n00, N, v, shift, c, W, elem_sz);
+    const float v01 = wx != 0.0f ? (float)lens_sample<LINEAR, CONTINUOUS>(a, n01, N, v, shift, c, W, elem_sz) : 0.0f;
+    float ta = v00 * (1.0f - wx);
+    float tb = v01 * wx;
+    const float top = ta + tb;
+    float bot = 0.0f;
+    if (wy != 0.0f) {
+        const float v10 = (float)lens_sample<LINEAR, CONTINUOUS>(a, n10, N, v, shift, c, W, elem_sz);
+        const float v11 = wx != 0.0f ? (float)lens_sample<LINEAR, CONTINUOUS>(a, n11, N, v, shift, c, W, elem_sz) : 0.0f;
+        ta = v10 * (1.0f - wx);
+        tb = v11 * wx;
+        bot = ta + tb;
+    }
+    ta = top * (1.0f - wy);
+    tb = bot * wy;
+    return (u8)(ta + tb);
+}
+template <int MODE, bool LINEAR>
+__global__ __launch_bounds__(256) void stm_k_synth_mux_lens(SynthArgs a, u8 *__restrict__ out, int N, Lens g, int Hin, int Win, int Hout,
+                                                            int Wout, int elem_sz)
+{
+    const int tx = blockIdx.x * 256 + threadIdx.x, ty = blockIdx.y;
+    if (tx >= Wout) return;
+    float xs = ((float)tx / (float)Wout) * (float)Win;
+    xs = fminf(fmaxf(xs, 0.0f), (float)(Win - 1));
+    float ys = ((float)ty / (float)Hout) * (float)Hin;
+    ys = fminf(fmaxf(ys, 0.0f), (float)(Hin - 1));
+    const int x0 = (int)floorf(xs), y0 = (int)floorf(ys);
+    const int x1 = min(x0 + 1, Win - 1), y1 = min(y0 + 1, Hin - 1);
+    const float wx = xs - (float)x0, wy = ys - (float)y0;
+    const LensNb n00 = lens_nb(a, x0, y0, Win);
+    LensNb n01 = n00, n10 = n00, n11 = n00; // only read where the weight is not 0
+    if (wx != 0.0f) n01 = lens_nb(a, x1, y0, Win);
+    if (wy != 0.0f) {
+        n10 = lens_nb(a, x0, y1, Win);
+        if (wx != 0.0f) n11 = lens_nb(a, x1, y1, Win);
+    }
+    const size_t o = ((size_t)tx + (size_t)ty * Wout) * elem_sz;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int v;
+        float w, shift;
+        lens_pick<MODE>(lens_phase(tx, ty, c, g), N, v, w, shift);
+        if constexpr (MODE == 3) {
+            out[o + c] = lens_bilinear<LINEAR, true>(a, n00, n01, n10, n11, wx, wy, N, 0, shift, c, Win, elem_sz);
+        } else {
+            const u8 A = lens_bilinear<LINEAR, false>(a, n00, n01, n10, n11, wx, wy, N, v, 0.0f, c, Win, elem_sz);
+            if constexpr (MODE == 1) {
+                out[o + c] = A;
+            } else {
+                const u8 B = lens_bilinear<LINEAR, false>(a, n00, n01, n10, n11, wx, wy, N, v + 1, 0.0f, c, Win, elem_sz);
+                const float p = (float)A * (1.0f - w);
+                const float q = (float)B * w;
+                out[o + c] = (u8)(p + q);
+            }
+        }
+    }
+}
+template <int MODE>
+static void launch_synth_mux_lens_mode(const SynthArgs &a, u8 *out, int N, const Lens &ln, int Hin, int Win, int Hout, int Wout,
+                                       int elem_sz, bool linear)
+{
+    if (linear)
+        STM_LAUNCH((stm_k_synth_mux_lens<MODE, true>), dim3(cdiv(Wout, 256), Hout), dim3(256), 0, stream(), a, out, N, ln, Hin, Win, Hout,
+                   Wout, elem_sz);
+    else
+        STM_LAUNCH((stm_k_synth_mux_lens<MODE, false>), dim3(cdiv(Wout, 256), Hout), dim3(256), 0, stream(), a, out, N, ln, Hin, Win, Hout,
+                   Wout, elem_sz);
+}
+void launch_synth_mux_lens(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l,
+                           const float *mask_r, const float *blend, u8 *out, int N, const Lens &ln, int Hin, int Win, int Hout, int Wout,
+                           int elem_sz, bool linear)
+{
+    SynthArgs a{img_l, img_r, disp_l, disp_r, mask_l, mask_r, blend};
+    ProfScope p("synth_mux");
+    if (ln.mode == 1) launch_synth_mux_lens_mode<1>(a, out, N, ln, Hin, Win, Hout, Wout, elem_sz, linear);
+    else if (ln.mode == 2) launch_synth_mux_lens_mode<2>(a, out, N, ln, Hin, Win, Hout, Wout, elem_sz, linear);
+    else launch_synth_mux_lens_mode<3>(a, out, N, ln, Hin, Win, Hout, Wout, elem_sz, linear);
+    STM_CHECK_LAUNCH();
+}
+
 } // namespace stm

@@ -4,6 +4,7 @@
 #include "../../include/stm_hip.h"
 
 #include <math.h>
+#include <cmath>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -231,6 +232,33 @@ static int g_ref_quirks = 0;
 int ref_quirks() { return g_ref_quirks; }
 static int g_irv_paper_ratio = 0;
 int irv_paper_ratio() { return g_irv_paper_ratio; }
+// the calling thread's display geometry (stm_set_lens)
+static thread_local Lens g_lens = {0, 0.0, 0.0, 0.0};
+Lens lens() { return g_lens; }
+void set_lens(const Lens &l) { g_lens = l; }
+bool lens_params_ok(const char *fn, int mode, int mode_lo, int mode_hi, double pitch, double slope, double centre)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (mode < mode_lo || mode > mode_hi) {
+        snprintf(msg, sizeof msg, "%s: lens mode = %d, must be in %d .. %d", fn, mode, mode_lo, mode_hi);
+        arg = "mode";
+    } else if (mode == 0) {
+        return true; // off: the other arguments are ignored
+    } else if (!(pitch >= 1.0) || std::isinf(pitch)) { // NaN fails the comparison
+        snprintf(msg, sizeof msg, "%s: lens pitch = %g, must be finite and >= 1 (sub-pixels per lens)", fn, pitch);
+        arg = "pitch";
+    } else if (!std::isfinite(slope)) {
+        snprintf(msg, sizeof msg, "%s: lens slope = %g, must be finite", fn, slope);
+        arg = "slope";
+    } else if (!std::isfinite(centre)) {
+        snprintf(msg, sizeof msg, "%s: lens centre = %g, must be finite", fn, centre);
+        arg = "centre";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
 
 // ------------------------------------------------------------------ tables
 // rho(c) = 1 - exp(-c/lambda): d_ci_adcensus.cu:27-34 with inv = 1.0/coeff narrowed (:160).
@@ -334,6 +362,13 @@ int stm_prof_read(const char *kernel, float *total_ms)
 }
 void stm_set_ref_quirks(int on) { stm::g_ref_quirks = on ? 1 : 0; }
 void stm_set_irv_paper_ratio(int on) { stm::g_irv_paper_ratio = on ? 1 : 0; }
+int stm_set_lens(int mode, double pitch, double slope, double centre)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (!stm::lens_params_ok("set_lens", mode, 0, 3, pitch, slope, centre)) return -1; // the thread's geometry stays as it was
+    stm::set_lens(mode == 0 ? stm::Lens{0, 0.0, 0.0, 0.0} : stm::Lens{mode, pitch, slope, centre});
+    return 0;
+}
 void stm_set_agg_variant(int v)
 {
 #ifndef STM_TIMING

@@ -46,8 +46,16 @@ struct FrameStream {
     int t_color = 24;
     int in_format = 0, in_matrix = 0; // stm_stream_set_input: 0 = side-by-side BGR, 1 = NV12 (Y plane, then the UV plane; pitch Wsbs)
     size_t in_bytes = 0;              // what a submit copies and uploads: in_sz, or H * Wsbs * 3 / 2 for NV12
+    stm::Lens lens = {0, 0.0, 0.0, 0.0}; // stm_stream_set_lens: the stream's own display geometry, installed around its frame calls
     Slot slot[2];
     long submitted = 0, collected = 0;
+};
+
+// the stream's geometry in place of the calling thread's for the duration of a submit
+struct LensScope {
+    stm::Lens saved;
+    explicit LensScope(const stm::Lens &l) : saved(stm::lens()) { stm::set_lens(l); }
+    ~LensScope() { stm::set_lens(saved); }
 };
 
 } // namespace
@@ -183,6 +191,23 @@ int stm_stream_set_input(void *h, int format, int matrix)
     return 0;
 }
 
+// The display geometry every frame of the stream is interlaced through (stm_set_lens's rules; the default is mode 0, the reference's
+// interlacer).  The stream keeps its own copy: a submit installs it for its frame call and puts the calling thread's setting back,
+// so neither changes the other.  Only before the first submit: afterwards the slots replay their launches from a captured graph.
+// Returns 0, or -1 with the error recorded.
+int stm_stream_set_lens(void *h, int mode, double pitch, double slope, double centre)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (!stm::lens_params_ok("stream_set_lens", mode, 0, 3, pitch, slope, centre)) return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_lens: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    f->lens = mode == 0 ? stm::Lens{0, 0.0, 0.0, 0.0} : stm::Lens{mode, pitch, slope, centre};
+    return 0;
+}
+
 // Stage frame `submitted`; at most two frames may be in flight (collect the older one first).
 // Returns the frame's index, or -1 when both slots are still uncollected.
 long stm_stream_submit(void *h, const unsigned char *img_sbs)
@@ -213,6 +238,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     STM_CHECK(hipStreamWaitEvent(s.s_compute, s.ev_in, 0));
     if (history) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
     void *prev = stm_get_stream();
+    LensScope lens_scope(f->lens);
     stm_set_stream(s.s_compute);
     stm::ws_private_bind(s.ws);
     auto pipeline = [&]() {

@@ -43,6 +43,30 @@ class FrameParams:
         self.out_rows, self.out_cols = out_rows, out_cols
 
 
+def set_lens(mode, pitch=0.0, slope=0.0, centre=0.0):
+    """stm_set_lens: the calling thread's display geometry, which every rendering frame call interlaces through.  mode 0 = off (the
+    reference's interlacer, the default), 1 = nearest view, 2 = two views blended, 3 = every sub-pixel rendered at its own
+    continuous position; pitch in sub-pixels per lens (>= 1), slope in sub-pixels per output row, centre in lenses.  Raises
+    ValueError where the library refuses (it returns -1; in error mode 0 it exits like any error)."""
+    if int(lib().stm_set_lens(int(mode), float(pitch), float(slope), float(centre))) != 0:
+        raise ValueError("stm_set_lens(%d, %g, %g, %g) refused: %s" % (mode, pitch, slope, centre, lib().stm_last_error().decode()))
+
+
+def d_mux_multiview_lens(views, out, mode, pitch, slope, centre):
+    """stm_d_mux_multiview_lens: the views (a list of N uint8 [H][W][E] tensors on the GPU, views[0] = the right image ...
+    views[N - 1] = the left image) interlaced into out (uint8 [Ho][Wo][E], only the first three bytes of a pixel are written)
+    through the lens geometry; mode 1 or 2."""
+    H, W, E = views[0].shape
+    for t in views:
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.shape[2] == E
+    tab = torch.tensor([t.data_ptr() for t in views], dtype=torch.int64).to(out.device)
+    _use_current_stream()
+    lib().stm_d_mux_multiview_lens(_p(tab), _p(out), len(views), int(mode), float(pitch), float(slope), float(centre), H, W,
+                                   out.shape[0], out.shape[1], E)
+    torch.cuda.current_stream().synchronize()  # the kernel reads the pointer table: keep it alive until it has run
+
+
 def d_adcensus_stm(sbs, disp_l, disp_r, interlaced, p, stages=3):
     """stm_d_adcensus_stm: sbs uint8 [H][2W][3] on the GPU; outputs are written in place.
     stages: 1 = cost+aggregation+WTA, 2 = + refinement, 3 = full frame (views + interlacing); OR-ing 0x100 adds the

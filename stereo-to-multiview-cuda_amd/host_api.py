@@ -238,6 +238,20 @@ def mux_multiview(views, angle, out_rows, out_cols):
     return out
 
 
+def mux_multiview_lens(views, mode, pitch, slope, centre, out_rows, out_cols):
+    """stm_mux_multiview_lens (an addition, the reference's interlacer fits one panel): mux_multiview with each sub-pixel's view
+    taken from its phase under a lens sheet of `pitch` sub-pixels per lens, slanted by `slope` sub-pixels per row, offset by
+    `centre` lenses; mode 1 = the nearest view, 2 = the two nearest views blended."""
+    views = [np.ascontiguousarray(v, dtype=np.uint8) for v in views]
+    N = len(views)
+    H, W, E = views[0].shape
+    tab = (u8p * N)(*[v.ctypes.data_as(u8p) for v in views])
+    out = np.zeros((out_rows, out_cols, E), np.uint8)
+    lib().stm_mux_multiview_lens(C.cast(tab, u8pp), out.ctypes.data_as(u8p), N, int(mode), float(pitch), float(slope), float(centre),
+                                 H, W, out_rows, out_cols, E)
+    return out
+
+
 def adcensus_stm(img_sbs, num_cols, out_rows, out_cols, num_views, angle, num_disp, zero_disp,
                  ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h):
     """d_io.h:32-40: host SBS frame in, (disp_l, disp_r, interlaced) out."""

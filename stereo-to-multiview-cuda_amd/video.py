@@ -16,9 +16,10 @@ class FrameStream:
     """Pipelined adcensus_stm over a sequence: submit() frames, collect() results in order (two in flight).
     input_format "bgr" (the default): a frame is a side-by-side BGR array uint8 [H][2W][3].  "nv12": a frame is uint8 [H * 3 / 2][2W],
     the Y plane followed by the interleaved UV plane, as a decoder or read_nv12_sequence delivers it; `matrix` selects the colour
-    conversion (stm_demux_nv12: 0 / 1 = BT.601 / BT.709 limited range, 2 / 3 = full range)."""
+    conversion (stm_demux_nv12: 0 / 1 = BT.601 / BT.709 limited range, 2 / 3 = full range).  lens = (mode, pitch, slope, centre): the
+    panel's calibration (set_lens); None = the reference's interlacer."""
 
-    def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0):
+    def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None):
         self.H, self.W = num_rows, num_cols
         self.in_shape = (num_rows, 2 * num_cols, 3)
         self.Ho, self.Wo = out_rows or num_rows, out_cols or num_cols
@@ -30,6 +31,16 @@ class FrameStream:
             self.set_stages(stages)
         if input_format != "bgr":
             self.set_input(input_format, matrix)
+        if lens is not None:
+            self.set_lens(*lens)
+
+    def set_lens(self, mode, pitch=0.0, slope=0.0, centre=0.0):
+        """stm_stream_set_lens: the display geometry the stream's frames are interlaced through (device_api.set_lens's arguments);
+        the stream's own, independent of the calling thread's; only before the first submit.  Raises ValueError where the library
+        refuses."""
+        if int(lib().stm_stream_set_lens(self._h, int(mode), float(pitch), float(slope), float(centre))) != 0:
+            raise ValueError("stm_stream_set_lens(%d, %g, %g, %g) refused: %s"
+                             % (mode, pitch, slope, centre, lib().stm_last_error().decode()))
 
     def set_input(self, input_format, matrix=0):
         """stm_stream_set_input: "bgr" or "nv12" with its conversion matrix; only before the first submit.  Raises ValueError where
@@ -98,17 +109,18 @@ class FrameStream:
             pass
 
 
-def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0):
+def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
-    stabilisation); temporal: (alpha, thresh_color, thresh_disp) for FrameStream.set_temporal, None = the defaults."""
+    stabilisation); temporal: (alpha, thresh_color, thresh_disp) for FrameStream.set_temporal, None = the defaults; lens: (mode,
+    pitch, slope, centre) for FrameStream.set_lens, None = the reference's interlacer."""
     fs = None
     pending = 0
     for sbs in frames:
         if fs is None:
             rows = sbs.shape[0] * 2 // 3 if input_format == "nv12" else sbs.shape[0]
-            fs = FrameStream(rows, sbs.shape[1] // 2, params, out_rows, out_cols, stages, input_format, matrix)
+            fs = FrameStream(rows, sbs.shape[1] // 2, params, out_rows, out_cols, stages, input_format, matrix, lens)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:

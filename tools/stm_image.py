@@ -6,14 +6,18 @@ source, cost slice, aggregated slice, disparity, outliers, occlusion mask, every
 
 usage: stm_image.py <left.bmp> <right.bmp> <ad coeff> <census coeff> <ndisp> <zerodisp> <ucd> <lcd> <usd> <lsd>
                     <num views> <angle> <out width> <out height> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel]
-                    [--linear-warp]
+                    [--linear-warp] [--lens MODE PITCH SLOPE CENTRE]
 
 --interp (an addition, off by default): the outlier interpolation (host_api.dr_interp) of both maps after region voting, each on
 its own image and outlier map, before --subpixel.
 --subpixel (an addition, off by default): the sub-pixel enhancement (host_api.dc_subpixel) of both maps on their aggregated
 volumes after region voting, before the bilateral filter.
 --linear-warp (an addition, off by default): every view through host_api.dibr_dbm_lin (both warps fetched at the fractional
-coordinate) instead of dibr_dbm."""
+coordinate) instead of dibr_dbm.
+--lens MODE PITCH SLOPE CENTRE (an addition): the views interlaced through the panel's calibration (host_api.mux_multiview_lens:
+PITCH sub-pixels per lens, SLOPE sub-pixels of lens shift per output row, CENTRE lenses of phase offset; MODE 1 = nearest view,
+2 = two views blended) instead of the reference's interlacer; <angle> is then ignored.  Mode 3 renders without views: it exists
+in the frame calls only (stm_video.py)."""
 import os
 import sys
 
@@ -26,6 +30,14 @@ sys.path.insert(0, ROOT)
 def main(argv):
     subpixel, interp, linear_warp = "--subpixel" in argv, "--interp" in argv, "--linear-warp" in argv
     argv = [x for x in argv if x not in ("--subpixel", "--interp", "--linear-warp")]
+    lens = None
+    if "--lens" in argv:
+        at = argv.index("--lens")
+        if at + 4 >= len(argv) or argv[at + 1] not in ("1", "2"):
+            print(__doc__)
+            return -1
+        lens = (int(argv[at + 1]), float(argv[at + 2]), float(argv[at + 3]), float(argv[at + 4]))
+        del argv[at:at + 5]
     if len(argv) not in (17, 18):
         print(__doc__)
         return -1
@@ -73,7 +85,7 @@ def main(argv):
     views.append(L)
     for v, img in enumerate(views):
         wr("view_%d" % v, img)
-    wr("interlaced", api.mux_multiview(views, angle, Ho, Wo))             # :292
+    wr("interlaced", api.mux_multiview(views, angle, Ho, Wo) if lens is None else api.mux_multiview_lens(views, *lens, Ho, Wo))  # :292
     print("wrote %d files to %s (%dx%d, D=%d, %d views)" % (len(os.listdir(out)), out, W, H, D, N))
     return 0
 

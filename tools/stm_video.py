@@ -5,7 +5,7 @@ side-by-side BMP frames instead of a video file, BMP outputs instead of a window
 usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <num disp> <zero disp> <ad coeff>
                     <census coeff> <ucd> <lcd> <usd> <lsd> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel] [--linear-warp]
                     [--temporal [--temporal-alpha A] [--temporal-color C] [--temporal-disp T]]
-                    [--nv12 ROWS COLS_SBS [--matrix M]]
+                    [--nv12 ROWS COLS_SBS [--matrix M]] [--lens MODE PITCH SLOPE CENTRE]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -15,6 +15,9 @@ neither colour nor disparity moved; --temporal-alpha (0.5), --temporal-color (24
 --nv12 ROWS COLS_SBS (an addition): <frames dir> is instead one raw .yuv file of concatenated side-by-side NV12 frames of ROWS rows
 and COLS_SBS columns, converted on the GPU inside the frame's first kernel; --matrix M (0) picks the conversion: 0 / 1 = BT.601 /
 BT.709 limited range, 2 / 3 = BT.601 / BT.709 full range.
+--lens MODE PITCH SLOPE CENTRE (an addition): the panel's calibration (stm_set_lens) -- PITCH sub-pixels per lens, SLOPE sub-pixels
+of lens shift per output row, CENTRE lenses of phase offset; MODE 1 = nearest view, 2 = two views blended, 3 = every sub-pixel
+rendered at its own continuous position.  Replaces the reference's interlacer; <angle> is then ignored.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -54,6 +57,14 @@ def main(argv):
             return -1
         matrix = int(argv[at + 1])
         del argv[at:at + 2]
+    lens = None
+    if "--lens" in argv:
+        at = argv.index("--lens")
+        if at + 4 >= len(argv):
+            print(__doc__)
+            return -1
+        lens = (int(argv[at + 1]), float(argv[at + 2]), float(argv[at + 3]), float(argv[at + 4]))
+        del argv[at:at + 5]
     if len(argv) not in (16, 17):
         print(__doc__)
         return -1
@@ -70,7 +81,7 @@ def main(argv):
     t0 = time.perf_counter()
     n = 0
     for (k, dl, dr, inter) in video.process_sequence(frames, p, out_h, out_w, stages, tuple(temporal) if stages & 0x2000 else None,
-                                                       "bgr" if nv12 is None else "nv12", matrix):
+                                                       "bgr" if nv12 is None else "nv12", matrix, lens):
         video.write_outputs(out_dir, k, dl, dr, inter)
         n += 1
     dt = time.perf_counter() - t0
