@@ -103,6 +103,46 @@ void        stm_set_irv_paper_ratio(int on);
  * view written, then interlaced); mode 3 has no views, so it always takes the fused kernel.  This is an output geometry, not a
  * stage: no `stages` bit belongs to it.  Returns 0, or -1 with stm_last_error set and the thread's geometry unchanged. */
 int         stm_set_lens(int mode, double pitch, double slope, double centre);
+/* The calling thread's depth budget (an addition: the reference's N views always span exactly the camera baseline -- view v sits at
+ * shift = 1 - v/(N-1) -- and the zero-parallax plane is wherever zero_disp put it).  A lenticular panel has a limited usable
+ * parallax range; a scene that exceeds it ghosts.  mode 0 = off (the default: not one launch, argument or kernel of the path
+ * changes), 1 = manual (gain, conv), 2 = automatic (gain and conv fitted to each frame's disparity range on the device, see
+ * stm_set_depth_auto and stm_depth_fit).  With mode != 0 every frame call that renders -- stm_adcensus_stm, stm_d_adcensus_stm, _t,
+ * _nv12, and _2 / _2s in both flavours -- takes every sample by the rule below.  It combines with every lens mode and with 0x800.
+ * There are no views to write, so the fused renderer is taken always, also under stm_set_agg_variant(200).  Like the lens geometry
+ * this is an output geometry, not a stage: no `stages` bit belongs to it.
+ *
+ * Sign convention: the maps hold delta = x_right - x_left (disp = d - zero_disp).
+ * Sample rule.  A sample is taken for the view position s: for a discrete view v, s = (float)(1 - v/(N-1)) as the reference
+ * evaluates it (d_io.cu:189); in lens mode 3, the sub-pixel's own shift.  (xs, ys) is the interlacer's sampling position; gain and
+ * conv are floats, conv in input-view pixels.  f32 or f64 as written, one operation per line, no contraction, C fminf / fmaxf:
+ *   t   = (double)s - 0.5
+ *   u   = (double)gain * t
+ *   s2  = (float)(0.5 + u)
+ *   u   = (double)conv * t
+ *   off = (float)u
+ *   cx  = xs + off
+ *   cx  = fminf(fmaxf(cx, 0), (float)(Win - 1))
+ * The value is fast_bilinear_interp's combination (d_mux_multiview.cu:10-36) of the <= 4 neighbours of (cx, ys), each neighbour
+ * being the renderer's general form at shift s2: shift_l = -s2, shift_r = (float)(1.0 - (double)s2), both backward warps
+ * (truncating, or linear with 0x800), masks, blend, u8 wrap.  The end-view shortcut (view 0 = the right image, view N-1 = the left
+ * image) is not taken; a neighbour of weight exactly 0 is not evaluated.  Lens mode 2 blends two views, each with its own s2 and cx.
+ * A scene point of disparity delta is then shown with the end-to-end disparity gain * delta - conv.  gain > 1 makes s2 leave [0, 1]:
+ * the formulas are used unchanged, which is extrapolation beyond the two cameras, with the quality that implies (disocclusions the
+ * masks were not made for).  gain = 1, conv = 0 renders the interior views 1 .. N-2 as mode 0 does and the two end views as warps
+ * at s = 1 and s = 0 instead of the unwarped images.
+ * Argument rules: mode 0, 1 or 2; in mode 1 gain finite in [0, 8], conv finite with |conv| <= 4096 (both ignored otherwise); mode 2
+ * needs a budget from stm_set_depth_auto first.  Returns 0, or -1 with stm_last_error set and the thread's setting unchanged. */
+int         stm_set_depth(int mode, float gain, float conv);
+/* Mode 2's parameters (kept when the mode changes): the budget [disp_lo, disp_hi] of end-to-end disparity in input-view pixels
+ * (disp_lo < disp_hi, both finite and of magnitude <= 4096), max_gain in (0, 8] (1 = never amplify), clip_permille in 0 .. 499 (the
+ * share of pixels ignored at either end of the range; a sequence's default is 20), rate in (0, 1] (1 = every frame on its own),
+ * d_state = four floats in device memory, {valid, gain, conv, 0}, or null.  In mode 2 the frame call runs stm_d_depth_fit on the
+ * maps it renders from (the up-scaled maps of the reduced frame, the stabilised maps of 0x2000) with these parameters and d_state,
+ * and the renderer of the same frame reads gain and conv from that memory: nothing is synchronised or read back.  A null d_state
+ * means scratch memory, with every frame fitted on its own.  A caller resets the history, for a scene cut, by zeroing `valid`.
+ * Returns 0, or -1 with stm_last_error set and the old parameters in place. */
+int         stm_set_depth_auto(float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate, float *d_state);
 /* ci_adcensus / d_ci_adcensus (the per-stage calls; the frame calls always compute the clean costs): 0 (default) = clean
  * clamped indexing, the canonical form (SURVEY A-Q7); 1 = reproduce the reference's shared-tile strays at d = 0 in columns
  * 160 k (left cost) and 160 k + 159 (right cost): the census term always, the AD term when num_disp - zero_disp <= zero_disp
@@ -520,6 +560,35 @@ void stm_disp_temporal(float *disp, float *disp_prev, unsigned char *img, unsign
                        int elem_sz, float alpha, int thresh_color, float thresh_disp);
 void stm_d_disp_temporal(float *d_disp, float *d_disp_prev, unsigned char *d_img, unsigned char *d_img_prev, int num_rows, int num_cols,
                          int elem_sz, float alpha, int thresh_color, float thresh_disp);
+/* The measurement behind the automatic depth budget (an addition; see stm_set_depth for what gain and conv do).  Both maps (f32,
+ * num_rows x num_cols, read only) go into one histogram of 4096 quarter-pixel bins; per pixel, f32, one operation per line:
+ *   v = disp * 4.0f
+ *   v = fminf(fmaxf(v, -2048.0f), 2047.0f)          (C fmaxf: a NaN lands in bin 0; values beyond +-512 px land in the end bins)
+ *   b = (int)floorf(v + 0.5f) + 2048
+ * Every pixel of both maps counts once: n = 2 * num_rows * num_cols (u32; num_rows * num_cols must be below 2^31).
+ *   k    = (u64)n * clip_permille / 1000
+ *   lo   = the smallest b with cum(b) > k            (cum(b) = the count of bins 0 .. b)
+ *   hi   = the largest b whose suffix count (bins b .. 4095) is > k          (clip_permille <= 499: lo <= hi always)
+ *   d_lo = (float)(lo - 2048) * 0.25f;  d_hi = (float)(hi - 2048) * 0.25f
+ * Then, in double, one operation per line, no contraction, correctly rounded division:
+ *   span   = (double)d_hi - (double)d_lo
+ *   budget = (double)disp_hi - (double)disp_lo
+ *   g = span > 0 ? budget / span : max_gain
+ *   g = min(g, max_gain)
+ *   a = g * d_hi;  a = a - disp_hi                   (the least conv that brings the far end in)
+ *   b = g * d_lo;  b = b - disp_lo                   (the most conv that keeps the near end in)
+ *   c = min(max(0.0, a), b)
+ * The minimal intervention: a scene that already fits [disp_lo, disp_hi] gets g = min(budget / span, max_gain) and c = 0.
+ * state = four floats {valid, gain, conv, 0}.  valid == 0: the state becomes (1, (float)g, (float)c, 0).  Otherwise gain and conv
+ * each move by rate, the other two floats stay:
+ *   t = value - (double)old;  t = (double)rate * t;  new = (float)((double)old + t)
+ * The device flavour reads and writes d_state in device memory and synchronises nothing; the host flavour takes and returns the
+ * four floats in host memory.  Argument rules as stm_set_depth_auto; violations fail through stm_last_error before anything is
+ * launched or written.  Parity is against a numpy statement of these lines (parity unpinned). */
+void stm_depth_fit(float *disp_l, float *disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
+                   int clip_permille, float rate, float *state);
+void stm_d_depth_fit(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
+                     int clip_permille, float rate, float *d_state);
 /* d_tx_scale.h:17-18  d_tx_scale (d_tx_scale.cu:83-121): bilinear image resize; HOST pointers despite the name */
 void stm_d_tx_scale(unsigned char *img_in, unsigned char *img_out, int in_rows, int in_cols, int out_rows, int out_cols,
                     int elem_sz);
@@ -562,6 +631,18 @@ int   stm_stream_set_input(void *stream, int format, int matrix);
  * installs it only for the duration of its frame calls: the calling thread's stm_set_lens neither reaches the stream's frames
  * (or its captured graph) nor is changed by them.  Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
 int   stm_stream_set_lens(void *stream, int mode, double pitch, double slope, double centre);
+/* the depth budget of the stream's frames (stm_set_depth's rules; the default is mode 0).  As with the lens geometry the stream keeps
+ * its own copy and installs it only around its frame calls.  stm_stream_set_depth_auto sets mode 2's parameters (stm_set_depth_auto's
+ * rules; call it before stm_stream_set_depth(stream, 2, 0, 0)); the state is the stream's own: one buffer at a fixed address, zeroed
+ * at creation, so the slots' captured graphs stay valid.  Frame k reads what frame k - 1 wrote, so in mode 2 the two frames in
+ * flight run one after the other on the GPU, as with 0x2000; upload and download still overlap.  Only before the first submit.
+ * Return 0, or -1 with stm_last_error set. */
+int   stm_stream_set_depth(void *stream, int mode, float gain, float conv);
+int   stm_stream_set_depth_auto(void *stream, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate);
+/* out = {gain, conv} applied to the most recently collected frame: in mode 2 the state as that frame's fit left it (a 16-byte copy
+ * taken on the frame's compute stream and downloaded with its results, so the next frame's update cannot race it), in mode 1 the
+ * setting, in mode 0 {1, 0}.  Returns 0, or -1 if no frame has been collected yet. */
+int   stm_stream_depth(void *stream, float out[2]);
 /* waits for the oldest uncollected frame and copies its results out (NULL = skip).  Returns its index or -1. */
 long  stm_stream_collect(void *stream, float *disp_l, float *disp_r, unsigned char *interlaced);
 /* zero-copy variants (at 1080p the two host copies of submit / collect take longer than the frame does on the GPU):

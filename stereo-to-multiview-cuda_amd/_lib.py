@@ -34,6 +34,8 @@ PROTOS = {
     "stm_set_irv_paper_ratio": ([i], None),
     "stm_set_ref_quirks": ([i], None),
     "stm_set_lens": ([i, d, d, d], i),
+    "stm_set_depth": ([i, f, f], i),
+    "stm_set_depth_auto": ([f, f, f, i, f, vp], i),
     "stm_ci_adcensus": ([u8p, u8p, f32pp, f32pp, f, f, i, i, i, i, i], None),
     "stm_d_ci_adcensus": ([vp, vp, vp, vp, f32pp, f32pp, vp, f, f, i, i, i, i, i], None),
     "stm_ca_cross": ([u8p, u8pp, f32pp, f32pp, f, f, i, i, i, i, i, i], None),
@@ -89,6 +91,8 @@ PROTOS = {
     "stm_d_disp_upsample": ([vp, vp, vp, vp, i, i, i, i, i, f, f], None),
     "stm_disp_temporal": ([f32p, f32p, u8p, u8p, i, i, i, f, i, f], None),
     "stm_d_disp_temporal": ([vp, vp, vp, vp, i, i, i, f, i, f], None),
+    "stm_depth_fit": ([f32p, f32p, i, i, f, f, f, i, f, f32p], None),
+    "stm_d_depth_fit": ([vp, vp, i, i, f, f, f, i, f, vp], None),
     "stm_d_tx_scale": ([u8p, u8p, i, i, i, i, i], None),
     "stm_stream_create": ([i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f], C.c_void_p),
     "stm_stream_submit": ([C.c_void_p, u8p], C.c_long),
@@ -96,6 +100,9 @@ PROTOS = {
     "stm_stream_set_temporal": ([C.c_void_p, f, i, f], i),
     "stm_stream_set_input": ([C.c_void_p, i, i], i),
     "stm_stream_set_lens": ([C.c_void_p, i, d, d, d], i),
+    "stm_stream_set_depth": ([C.c_void_p, i, f, f], i),
+    "stm_stream_set_depth_auto": ([C.c_void_p, f, f, f, i, f], i),
+    "stm_stream_depth": ([C.c_void_p, f32p], i),
     "stm_stream_collect": ([C.c_void_p, f32p, f32p, u8p], C.c_long),
     "stm_stream_input_buffer": ([C.c_void_p], C.c_void_p),
     "stm_stream_collect_view": ([C.c_void_p, C.POINTER(f32p), C.POINTER(f32p), C.POINTER(u8p)], C.c_long),

@@ -810,6 +810,41 @@ void stm_disp_temporal(float *disp, float *disp_prev, unsigned char *img, unsign
     sync();
 }
 
+// =============================================================== depth budget: the measurement as a stage
+// (an addition, the reference has none: its views always span the camera baseline)
+static bool depth_fit_args_ok(const char *fn, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain, int clip_permille,
+                              float rate)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}})) return false;
+    if ((size_t)num_rows * num_cols > 0x7fffffffu) { // n = 2 H W is counted in 32 bits
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: num_rows * num_cols = %zu, must be below 2^31", fn, (size_t)num_rows * num_cols);
+        fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
+        return false;
+    }
+    return depth_auto_params_ok(fn, disp_lo, disp_hi, max_gain, clip_permille, rate);
+}
+void stm_d_depth_fit(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
+                     int clip_permille, float rate, float *d_state)
+{
+    if (!depth_fit_args_ok("d_depth_fit", num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate)) return;
+    Workspace::begin(4096 * 4 + 8192);
+    uint32_t *hist = Workspace::get<uint32_t>(4096);
+    launch_depth_fit(d_state, hist, d_disp_l, d_disp_r, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, false);
+}
+void stm_depth_fit(float *disp_l, float *disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
+                   int clip_permille, float rate, float *state)
+{
+    if (!depth_fit_args_ok("depth_fit", num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate)) return;
+    const size_t HW = (size_t)num_rows * num_cols;
+    Workspace::begin(8 * HW + 4096 * 4 + 8192);
+    float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *st = up(state, 4);
+    uint32_t *hist = Workspace::get<uint32_t>(4096);
+    launch_depth_fit(st, hist, dl, dr, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, false);
+    down(state, st, 4);
+    sync();
+}
+
 // =============================================================== mux
 void stm_d_mux_multiview(unsigned char **d_views, unsigned char *d_out_data, int num_views, float angle, int in_rows,
                          int in_cols, int out_rows, int out_cols, int elem_sz)
@@ -1110,6 +1145,38 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
     // a lens geometry (stm_set_lens) replaces the reference's view assignment; `angle` is then neither used nor screened.  Mode 3
     // renders every sub-pixel at a position of its own -- there are no views to write -- so it takes the fused kernel always
     const Lens ln = lens();
+    // a depth budget (stm_set_depth) maps every view's position to the shift it is rendered at and to an offset of its sampling
+    // position: as in lens mode 3 there are no views to write, so the fused kernel is taken always.  Mode 2 first measures the maps
+    // this render reads (the up-scaled ones of the reduced frame, the stabilised ones of 0x2000) and leaves gain and conv in the
+    // state, which the renderer reads on the device.
+    const Depth dp = depth();
+    if (dp.mode != 0) {
+        float inv_y = 0.0f;
+        int ymod = 1;
+        if (ln.mode == 0) {
+            const float yi = mux_y_interval(N, angle, elem_sz);
+            if (!(fabsf(yi) < 1.0e9f)) {
+                fail("mux_multiview: y_interval is not finite (tan(angle) == 0 or angle is not a number)", "angle", __FILE__, __LINE__);
+                return;
+            }
+            ymod = (int)roundf(yi);
+            if (ymod == 0) {
+                fail("mux_multiview: round(y_interval) == 0 (angle too steep)", "ymod", __FILE__, __LINE__);
+                return;
+            }
+            inv_y = 1.0f / yi;
+        }
+        float *state = nullptr;
+        if (dp.mode == 2) {
+            uint32_t *hist = Workspace::get<uint32_t>(4096);
+            state = dp.d_state ? dp.d_state : Workspace::get<float>(4);
+            launch_depth_fit(state, hist, d_disp_l, d_disp_r, H, W, dp.disp_lo, dp.disp_hi, dp.max_gain, dp.clip_permille, dp.rate,
+                             dp.d_state == nullptr);
+        }
+        launch_synth_mux_depth(img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, d_interlaced, N, ln, inv_y, ymod, dp.gain, dp.conv,
+                               state, H, W, Hout, Wout, elem_sz, linear);
+        return;
+    }
     if (ln.mode != 0 && (ln.mode == 3 || (agg_variant() / 100) % 10 != 2)) {
         launch_synth_mux_lens(img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, d_interlaced, N, ln, H, W, Hout, Wout, elem_sz, linear);
         return;

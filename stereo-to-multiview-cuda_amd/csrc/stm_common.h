@@ -74,6 +74,21 @@ Lens lens();
 void set_lens(const Lens &l);
 // the argument rules of a lens geometry with mode in [mode_lo, mode_hi]; false with the error recorded
 bool lens_params_ok(const char *fn, int mode, int mode_lo, int mode_hi, double pitch, double slope, double centre);
+// The depth budget of the renderer (stm_set_depth / stm_set_depth_auto, include/stm_hip.h): mode 0 = off (the views span the camera
+// baseline), 1 = manual (gain, conv), 2 = automatic (gain and conv fitted to the frame's disparity range on the device).  One per
+// host thread, next to the lens geometry; a frame stream installs its own copy around its frame calls.
+struct Depth {
+    int mode;
+    float gain, conv;                                // mode 1
+    float disp_lo, disp_hi, max_gain, rate;          // mode 2: the budget in view pixels, the gain's ceiling, the state's update rate
+    int clip_permille;
+    float *d_state;                                  // mode 2: {valid, gain, conv, 0} in device memory; null = scratch, every frame on its own
+};
+Depth depth();
+void set_depth(const Depth &d);
+// the argument rules of the two settings; false with the error recorded
+bool depth_params_ok(const char *fn, int mode, float gain, float conv);
+bool depth_auto_params_ok(const char *fn, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate);
 int irv_paper_ratio(); // stm_set_irv_paper_ratio: accept on count / S instead of the reference's bin index / S (SURVEY A-Q17 iv)
 // Timing experiments (skip loads / sweeps / stores; results NOT valid) exist only in the separate libstm_hip_timing.so
 // (make timing, -DSTM_TIMING): in the product library every STM_DBG test is the constant false and stm_set_agg_variant
@@ -244,6 +259,16 @@ void launch_mux_lens(const u8 *const *d_views, u8 *out, int N, const Lens &ln, i
 void launch_synth_mux_lens(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l,
                            const float *mask_r, const float *blend, u8 *out, int N, const Lens &ln, int Hin, int Win, int Hout, int Wout,
                            int elem_sz, bool linear);
+// the depth budget (stm_set_depth): launch_synth_mux / launch_synth_mux_lens with every view's shift and sampling position mapped
+// through gain and conv (ln.mode 0: the reference's view assignment from inv_y_interval and ymod); state != nullptr: gain and conv
+// are read from state[1] and state[2] on the device
+void launch_synth_mux_depth(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l,
+                            const float *mask_r, const float *blend, u8 *out, int N, const Lens &ln, float inv_y_interval, int ymod,
+                            float gain, float conv, const float *state, int Hin, int Win, int Hout, int Wout, int elem_sz, bool linear);
+// the measurement (stm_kernels_depth.hip): both maps into the 4096-bin histogram `hist` (scratch), the fit, the update of `state`
+// (four floats); fresh: the state's history is ignored
+void launch_depth_fit(float *state, uint32_t *hist, const float *disp_l, const float *disp_r, int H, int W, float disp_lo, float disp_hi,
+                      float max_gain, int clip_permille, float rate, bool fresh);
 // aggregation on the matrix pipe (stm_kernels_aggm.hip): the frame pipeline's cost -> H -> V, V -> H + WTA
 struct PQViews { // both views of a frame; a / b = the two PQ volumes of a view
     const uint32_t *pk[2], *cen[2];

@@ -819,4 +819,133 @@ void launch_synth_mux_lens(const u8 *img_l, const u8 *img_r, const float *disp_l
     STM_CHECK_LAUNCH();
 }
 
+// ------------------------------------------------------------------ depth budget (stm_hip.h, stm_set_depth)
+// The fused renderer with a view's position s mapped to the shift it is rendered at and to a horizontal offset of its sampling
+// position: s2 = 0.5 + gain (s - 0.5), cx = clamp(xs + conv (s - 0.5)).  Every sample takes the general form at s2 (no end-view
+// shortcut: at gain != 1 the end views are warps too).  LMODE 0 = the reference's view assignment, 1 .. 3 = the lens modes.
+__device__ __forceinline__ float view_shift(int v, int N)
+{
+    return (float)(1.0 - ((1.0 * (double)(float)v) / ((double)(float)N - 1.0))); // d_io.cu:189
+}
+// the four neighbours of the position a sample is taken at.  The three channels of a pixel belong to three views, so with
+// conv != 0 their positions differ; where two of them share x0 (always, with conv == 0) the neighbours' maps are loaded once.
+struct DepthNbs {
+    int x0;
+    bool has_x1;
+    LensNb n00, n01, n10, n11;
+};
+template <bool LINEAR>
+__device__ __forceinline__ u8 depth_sample(const SynthArgs &a, DepthNbs &nb, float s, float xs, int y0, int y1, float wy, float gain,
+                                           float conv, int c, int Win, int elem_sz)
+{
+    const double t = (double)s - 0.5;
+    double u = (double)gain * t;
+    const float s2 = (float)(0.5 + u);
+    u = (double)conv * t;
+    const float off = (float)u;
+    float cx = xs + off;
+    cx = fminf(fmaxf(cx, 0.0f), (float)(Win - 1)); // C fmaxf: a NaN becomes 0
+    const int x0 = (int)floorf(cx);
+    const int x1 = min(x0 + 1, Win - 1);
+    const float wx = cx - (float)x0;
+    if (x0 != nb.x0 || (wx != 0.0f && !nb.has_x1)) { // only read where the weight is not 0
+        nb.x0 = x0;
+        nb.has_x1 = wx != 0.0f;
+        nb.n00 = lens_nb(a, x0, y0, Win);
+        nb.n01 = nb.n10 = nb.n11 = nb.n00;
+        if (wx != 0.0f) nb.n01 = lens_nb(a, x1, y0, Win);
+        if (wy != 0.0f) {
+            nb.n10 = lens_nb(a, x0, y1, Win);
+            if (wx != 0.0f) nb.n11 = lens_nb(a, x1, y1, Win);
+        }
+    }
+    return lens_bilinear<LINEAR, true>(a, nb.n00, nb.n01, nb.n10, nb.n11, wx, wy, 0, 0, s2, c, Win, elem_sz);
+}
+struct MuxGeom { // the reference's view assignment (LMODE 0): mux_multiview_kernel_2's arguments
+    float inv_y;
+    int ymod;
+};
+template <int LMODE, bool LINEAR>
+__global__ __launch_bounds__(256) void stm_k_synth_mux_depth(SynthArgs a, u8 *__restrict__ out, int N, MuxGeom mg, Lens g, float gain,
+                                                             float conv, const float *__restrict__ state, int Hin, int Win, int Hout,
+                                                             int Wout, int elem_sz)
+{
+    const int tx = blockIdx.x * 256 + threadIdx.x, ty = blockIdx.y;
+    if (tx >= Wout) return;
+    if (state) { // automatic mode: what stm_k_depth_fit left for this frame
+        gain = state[1];
+        conv = state[2];
+    }
+    float xs = ((float)tx / (float)Wout) * (float)Win;
+    xs = fminf(fmaxf(xs, 0.0f), (float)(Win - 1));
+    float ys = ((float)ty / (float)Hout) * (float)Hin;
+    ys = fminf(fmaxf(ys, 0.0f), (float)(Hin - 1));
+    const int y0 = (int)floorf(ys);
+    const int y1 = min(y0 + 1, Hin - 1);
+    const float wy = ys - (float)y0;
+    int r_view = 0;
+    if constexpr (LMODE == 0) {
+        const float x_interval = (float)N;
+        float y_view = (float)(ty % mg.ymod) + 1.0f;
+        y_view = y_view * x_interval;
+        y_view = y_view * mg.inv_y; // d_mux_multiview.cu:62-63
+        r_view = (tx * 3 + (int)y_view) % N;
+        if (r_view < 0) r_view += N;
+    }
+    DepthNbs nb;
+    nb.x0 = -1;
+    nb.has_x1 = false;
+    const size_t o = ((size_t)tx + (size_t)ty * Wout) * elem_sz;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if constexpr (LMODE == 0) {
+            int v = r_view + (2 - c); // byte 0 = the b view (r + 2), byte 2 = the r view
+            if (v >= N) v -= N;
+            out[o + c] = depth_sample<LINEAR>(a, nb, view_shift(v, N), xs, y0, y1, wy, gain, conv, c, Win, elem_sz);
+        } else {
+            int v;
+            float w, shift;
+            lens_pick<LMODE>(lens_phase(tx, ty, c, g), N, v, w, shift);
+            if constexpr (LMODE == 3) {
+                out[o + c] = depth_sample<LINEAR>(a, nb, shift, xs, y0, y1, wy, gain, conv, c, Win, elem_sz);
+            } else {
+                const u8 A = depth_sample<LINEAR>(a, nb, view_shift(v, N), xs, y0, y1, wy, gain, conv, c, Win, elem_sz);
+                if constexpr (LMODE == 1) {
+                    out[o + c] = A;
+                } else {
+                    const u8 B = depth_sample<LINEAR>(a, nb, view_shift(v + 1, N), xs, y0, y1, wy, gain, conv, c, Win, elem_sz);
+                    const float p = (float)A * (1.0f - w);
+                    const float q = (float)B * w;
+                    out[o + c] = (u8)(p + q);
+                }
+            }
+        }
+    }
+}
+template <int LMODE>
+static void launch_synth_mux_depth_mode(const SynthArgs &a, u8 *out, int N, const MuxGeom &mg, const Lens &ln, float gain, float conv,
+                                        const float *state, int Hin, int Win, int Hout, int Wout, int elem_sz, bool linear)
+{
+    if (linear)
+        STM_LAUNCH((stm_k_synth_mux_depth<LMODE, true>), dim3(cdiv(Wout, 256), Hout), dim3(256), 0, stream(), a, out, N, mg, ln, gain, conv,
+                   state, Hin, Win, Hout, Wout, elem_sz);
+    else
+        STM_LAUNCH((stm_k_synth_mux_depth<LMODE, false>), dim3(cdiv(Wout, 256), Hout), dim3(256), 0, stream(), a, out, N, mg, ln, gain, conv,
+                   state, Hin, Win, Hout, Wout, elem_sz);
+}
+// ln.mode 0: the reference's assignment from inv_y_interval and ymod; state != nullptr: gain and conv are read from state[1], state[2]
+void launch_synth_mux_depth(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l,
+                            const float *mask_r, const float *blend, u8 *out, int N, const Lens &ln, float inv_y_interval, int ymod,
+                            float gain, float conv, const float *state, int Hin, int Win, int Hout, int Wout, int elem_sz, bool linear)
+{
+    SynthArgs a{img_l, img_r, disp_l, disp_r, mask_l, mask_r, blend};
+    const MuxGeom mg{inv_y_interval, ymod};
+    ProfScope p("synth_mux");
+    if (ln.mode == 0) launch_synth_mux_depth_mode<0>(a, out, N, mg, ln, gain, conv, state, Hin, Win, Hout, Wout, elem_sz, linear);
+    else if (ln.mode == 1) launch_synth_mux_depth_mode<1>(a, out, N, mg, ln, gain, conv, state, Hin, Win, Hout, Wout, elem_sz, linear);
+    else if (ln.mode == 2) launch_synth_mux_depth_mode<2>(a, out, N, mg, ln, gain, conv, state, Hin, Win, Hout, Wout, elem_sz, linear);
+    else launch_synth_mux_depth_mode<3>(a, out, N, mg, ln, gain, conv, state, Hin, Win, Hout, Wout, elem_sz, linear);
+    STM_CHECK_LAUNCH();
+}
+
 } // namespace stm

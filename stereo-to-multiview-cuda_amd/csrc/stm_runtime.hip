@@ -260,6 +260,53 @@ bool lens_params_ok(const char *fn, int mode, int mode_lo, int mode_hi, double p
     return false;
 }
 
+// the calling thread's depth budget (stm_set_depth, stm_set_depth_auto)
+static thread_local Depth g_depth = {0, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 20, nullptr}; // disp_lo == disp_hi: no budget set yet
+Depth depth() { return g_depth; }
+void set_depth(const Depth &d) { g_depth = d; }
+bool depth_params_ok(const char *fn, int mode, float gain, float conv)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (mode < 0 || mode > 2) {
+        snprintf(msg, sizeof msg, "%s: depth mode = %d, must be 0 (off), 1 (manual) or 2 (automatic)", fn, mode);
+        arg = "mode";
+    } else if (mode != 1) {
+        return true; // off / automatic: gain and conv are ignored
+    } else if (!(gain >= 0.0f && gain <= 8.0f)) { // NaN fails the comparison
+        snprintf(msg, sizeof msg, "%s: depth gain = %g, must be in [0, 8]", fn, (double)gain);
+        arg = "gain";
+    } else if (!(fabsf(conv) <= 4096.0f)) {
+        snprintf(msg, sizeof msg, "%s: depth conv = %g, must be finite with |conv| <= 4096", fn, (double)conv);
+        arg = "conv";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+bool depth_auto_params_ok(const char *fn, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (!(fabsf(disp_lo) <= 4096.0f) || !(fabsf(disp_hi) <= 4096.0f) || !(disp_lo < disp_hi)) {
+        snprintf(msg, sizeof msg, "%s: depth budget [%g, %g]: disp_lo < disp_hi, both finite and of magnitude <= 4096", fn, (double)disp_lo,
+                 (double)disp_hi);
+        arg = "disp_lo, disp_hi";
+    } else if (!(max_gain > 0.0f && max_gain <= 8.0f)) {
+        snprintf(msg, sizeof msg, "%s: max_gain = %g, must be in (0, 8]", fn, (double)max_gain);
+        arg = "max_gain";
+    } else if (clip_permille < 0 || clip_permille > 499) {
+        snprintf(msg, sizeof msg, "%s: clip_permille = %d, must be in 0 .. 499", fn, clip_permille);
+        arg = "clip_permille";
+    } else if (!(rate > 0.0f && rate <= 1.0f)) {
+        snprintf(msg, sizeof msg, "%s: rate = %g, must be in (0, 1]", fn, (double)rate);
+        arg = "rate";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+
 // ------------------------------------------------------------------ tables
 // rho(c) = 1 - exp(-c/lambda): d_ci_adcensus.cu:27-34 with inv = 1.0/coeff narrowed (:160).
 // The reference's __expf is replaced by a correctly rounded exp evaluated on the host once per
@@ -367,6 +414,30 @@ int stm_set_lens(int mode, double pitch, double slope, double centre)
     if (stm::api_outermost()) stm::clear_failed();
     if (!stm::lens_params_ok("set_lens", mode, 0, 3, pitch, slope, centre)) return -1; // the thread's geometry stays as it was
     stm::set_lens(mode == 0 ? stm::Lens{0, 0.0, 0.0, 0.0} : stm::Lens{mode, pitch, slope, centre});
+    return 0;
+}
+int stm_set_depth(int mode, float gain, float conv)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (!stm::depth_params_ok("set_depth", mode, gain, conv)) return -1; // the thread's setting stays as it was
+    stm::Depth d = stm::depth(); // mode 2's parameters (stm_set_depth_auto) are kept
+    if (mode == 2 && !(d.disp_lo < d.disp_hi)) {
+        stm::fail("set_depth: mode 2 (automatic) needs the budget of stm_set_depth_auto first", "mode", __FILE__, __LINE__);
+        return -1;
+    }
+    d.mode = mode;
+    d.gain = mode == 1 ? gain : 1.0f;
+    d.conv = mode == 1 ? conv : 0.0f;
+    stm::set_depth(d);
+    return 0;
+}
+int stm_set_depth_auto(float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate, float *d_state)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (!stm::depth_auto_params_ok("set_depth_auto", disp_lo, disp_hi, max_gain, clip_permille, rate)) return -1;
+    stm::Depth d = stm::depth();
+    d.disp_lo = disp_lo; d.disp_hi = disp_hi; d.max_gain = max_gain; d.clip_permille = clip_permille; d.rate = rate; d.d_state = d_state;
+    stm::set_depth(d);
     return 0;
 }
 void stm_set_agg_variant(int v)

@@ -21,6 +21,7 @@ struct Slot {
     u8 *h_in = nullptr, *d_in = nullptr, *d_out = nullptr, *h_out = nullptr;
     float *d_dl = nullptr, *d_dr = nullptr, *h_dl = nullptr, *h_dr = nullptr;
     u8 *d_img_l = nullptr, *d_img_r = nullptr; // NV12 input: the slot's converted split images (the other slot's frame reads them as its history)
+    float *d_rec = nullptr, *h_rec = nullptr; // depth mode 2: the state as this slot's frame left it (16 bytes), and its download
     hipEvent_t ev_in, ev_done, ev_out;
     bool busy = false;
     hipStream_t s_compute = nullptr; // this slot's compute stream and private workspace (shared by both slots when overlap is off)
@@ -47,6 +48,8 @@ struct FrameStream {
     int in_format = 0, in_matrix = 0; // stm_stream_set_input: 0 = side-by-side BGR, 1 = NV12 (Y plane, then the UV plane; pitch Wsbs)
     size_t in_bytes = 0;              // what a submit copies and uploads: in_sz, or H * Wsbs * 3 / 2 for NV12
     stm::Lens lens = {0, 0.0, 0.0, 0.0}; // stm_stream_set_lens: the stream's own display geometry, installed around its frame calls
+    stm::Depth depth = {0, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 20, nullptr}; // stm_stream_set_depth / _auto: the stream's own depth budget
+    float *d_depth_state = nullptr; // mode 2: the state every frame updates, at one address for both slots' graphs
     Slot slot[2];
     long submitted = 0, collected = 0;
 };
@@ -56,6 +59,12 @@ struct LensScope {
     stm::Lens saved;
     explicit LensScope(const stm::Lens &l) : saved(stm::lens()) { stm::set_lens(l); }
     ~LensScope() { stm::set_lens(saved); }
+};
+
+struct DepthScope {
+    stm::Depth saved;
+    explicit DepthScope(const stm::Depth &d) : saved(stm::depth()) { stm::set_depth(d); }
+    ~DepthScope() { stm::set_depth(saved); }
 };
 
 } // namespace
@@ -208,6 +217,60 @@ int stm_stream_set_lens(void *h, int mode, double pitch, double slope, double ce
     return 0;
 }
 
+// The depth budget every frame of the stream is rendered with (stm_set_depth's rules; the default is mode 0).  Kept and installed
+// like the lens geometry.  Mode 2 allocates the stream's state and the slots' records.  Only before the first submit.
+int stm_stream_set_depth(void *h, int mode, float gain, float conv)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (!stm::depth_params_ok("stream_set_depth", mode, gain, conv)) return -1;
+    if (mode == 2 && !(f->depth.disp_lo < f->depth.disp_hi)) {
+        stm::fail("stream_set_depth: mode 2 (automatic) needs the budget of stm_stream_set_depth_auto first", "mode", __FILE__, __LINE__);
+        return -1;
+    }
+    if (f->submitted > 0) {
+        stm::fail("stream_set_depth: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    if (mode == 2 && !f->d_depth_state) {
+        STM_CHECK(hipMalloc((void **)&f->d_depth_state, 16));
+        STM_CHECK(hipMemset(f->d_depth_state, 0, 16)); // valid = 0: the first frame starts the history
+        for (Slot &s : f->slot) {
+            STM_CHECK(hipMalloc((void **)&s.d_rec, 16));
+            STM_CHECK(hipHostMalloc((void **)&s.h_rec, 16, hipHostMallocDefault));
+        }
+        if (stm::failed()) return -1;
+    }
+    f->depth.mode = mode;
+    f->depth.gain = mode == 1 ? gain : 1.0f;
+    f->depth.conv = mode == 1 ? conv : 0.0f;
+    f->depth.d_state = f->d_depth_state;
+    return 0;
+}
+int stm_stream_set_depth_auto(void *h, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (!stm::depth_auto_params_ok("stream_set_depth_auto", disp_lo, disp_hi, max_gain, clip_permille, rate)) return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_depth_auto: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    f->depth.disp_lo = disp_lo; f->depth.disp_hi = disp_hi; f->depth.max_gain = max_gain; f->depth.clip_permille = clip_permille;
+    f->depth.rate = rate;
+    return 0;
+}
+// gain and conv applied to the most recently collected frame
+int stm_stream_depth(void *h, float out[2])
+{
+    FrameStream *f = (FrameStream *)h;
+    if (f->collected == 0) return -1;
+    const Slot &s = f->slot[(f->collected - 1) & 1];
+    if (f->depth.mode == 2) { out[0] = s.h_rec[1]; out[1] = s.h_rec[2]; }
+    else { out[0] = f->depth.gain; out[1] = f->depth.conv; }
+    return 0;
+}
+
 // Stage frame `submitted`; at most two frames may be in flight (collect the older one first).
 // Returns the frame's index, or -1 when both slots are still uncollected.
 long stm_stream_submit(void *h, const unsigned char *img_sbs)
@@ -228,6 +291,8 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     // upload and download still do.  The other slot's ev_done was recorded by the previous submit.
     Slot &other = f->slot[(f->submitted & 1) ^ 1];
     const bool temporal = (f->stages & 0x2000) != 0, history = temporal && f->submitted > 0;
+    // depth mode 2: frame k's fit reads the state frame k - 1 wrote, so its compute waits for the other slot's frame as well
+    const bool depth_auto = f->depth.mode == 2;
     // In NV12 mode the history is the other slot's converted split images (d_img_l / d_img_r), which no upload touches, and this
     // slot's d_in was last read by this slot's own previous frame, collected before the slot was handed out again: the upload
     // waits for nothing.  This frame's compute still waits for the other slot's frame: it reads that frame's images and maps, and
@@ -236,9 +301,10 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     STM_CHECK(hipMemcpyAsync(s.d_in, s.h_in, f->in_bytes, hipMemcpyHostToDevice, f->s_in));
     STM_CHECK(hipEventRecord(s.ev_in, f->s_in));
     STM_CHECK(hipStreamWaitEvent(s.s_compute, s.ev_in, 0));
-    if (history) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
+    if (history || (depth_auto && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
     void *prev = stm_get_stream();
     LensScope lens_scope(f->lens);
+    DepthScope depth_scope(f->depth);
     stm_set_stream(s.s_compute);
     stm::ws_private_bind(s.ws);
     auto pipeline = [&]() {
@@ -296,11 +362,14 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     }
     stm::ws_private_bind(nullptr);
     stm_set_stream(prev);
+    // the state as this frame left it, before ev_done lets the next frame's fit update it
+    if (depth_auto) STM_CHECK(hipMemcpyAsync(s.d_rec, f->d_depth_state, 16, hipMemcpyDeviceToDevice, s.s_compute));
     STM_CHECK(hipEventRecord(s.ev_done, s.s_compute));
     STM_CHECK(hipStreamWaitEvent(f->s_out, s.ev_done, 0));
     STM_CHECK(hipMemcpyAsync(s.h_dl, s.d_dl, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
     STM_CHECK(hipMemcpyAsync(s.h_dr, s.d_dr, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
     STM_CHECK(hipMemcpyAsync(s.h_out, s.d_out, f->out_sz, hipMemcpyDeviceToHost, f->s_out));
+    if (depth_auto) STM_CHECK(hipMemcpyAsync(s.h_rec, s.d_rec, 16, hipMemcpyDeviceToHost, f->s_out));
     STM_CHECK(hipEventRecord(s.ev_out, f->s_out));
     if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
     if (stm::failed()) return -1; // error mode 1: the frame was not (completely) enqueued
@@ -362,7 +431,10 @@ void stm_stream_destroy(void *h)
         if (s.gexec) STM_CHECK(hipGraphExecDestroy(s.gexec));
         if (s.d_img_l) STM_CHECK(hipFree(s.d_img_l));
         if (s.d_img_r) STM_CHECK(hipFree(s.d_img_r));
+        if (s.d_rec) STM_CHECK(hipFree(s.d_rec));
+        if (s.h_rec) STM_CHECK(hipHostFree(s.h_rec));
     }
+    if (f->d_depth_state) STM_CHECK(hipFree(f->d_depth_state));
     stm::ws_private_destroy(f->slot[0].ws);
     STM_CHECK(hipStreamDestroy(f->slot[0].s_compute));
     if (f->overlap) {

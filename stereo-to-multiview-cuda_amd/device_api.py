@@ -52,6 +52,44 @@ def set_lens(mode, pitch=0.0, slope=0.0, centre=0.0):
         raise ValueError("stm_set_lens(%d, %g, %g, %g) refused: %s" % (mode, pitch, slope, centre, lib().stm_last_error().decode()))
 
 
+DEPTH_AUTO_DEFAULTS = (1.0, 20, 1.0)  # max_gain, clip_permille, rate of stm_set_depth_auto
+
+
+def set_depth(mode, gain=1.0, conv=0.0):
+    """stm_set_depth: the calling thread's depth budget, which every rendering frame call samples through.  mode 0 = off (the views
+    span the camera baseline, the default), 1 = manual: a scene point of disparity delta is shown with gain * delta - conv (conv in
+    input-view pixels; gain > 1 extrapolates beyond the two cameras), 2 = automatic: gain and conv fitted to every frame's disparity
+    range on the GPU with set_depth_auto's parameters.  Raises ValueError where the library refuses."""
+    if int(lib().stm_set_depth(int(mode), float(gain), float(conv))) != 0:
+        raise ValueError("stm_set_depth(%d, %g, %g) refused: %s" % (mode, gain, conv, lib().stm_last_error().decode()))
+
+
+def set_depth_auto(disp_lo, disp_hi, max_gain=1.0, clip_permille=20, rate=1.0, state=None):
+    """stm_set_depth_auto: mode 2's parameters -- the budget [disp_lo, disp_hi] of displayed disparity in input-view pixels, the
+    gain's ceiling, the share (in 1/1000) of pixels ignored at either end of the frame's range, the rate at which gain and conv
+    follow a frame's fit, and `state`: a float32 tensor of four elements on the GPU, {valid, gain, conv, 0}, which carries the
+    history from frame to frame (zero `valid` to reset it) -- the caller keeps it alive while the setting is in use; None = every
+    frame on its own.  Raises ValueError where the library refuses."""
+    if state is not None:
+        assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous() and state.numel() == 4
+    if int(lib().stm_set_depth_auto(float(disp_lo), float(disp_hi), float(max_gain), int(clip_permille), float(rate),
+                                    _p(state) if state is not None else None)) != 0:
+        raise ValueError("stm_set_depth_auto(%g, %g, %g, %d, %g) refused: %s"
+                         % (disp_lo, disp_hi, max_gain, clip_permille, rate, lib().stm_last_error().decode()))
+
+
+def d_depth_fit(disp_l, disp_r, disp_lo, disp_hi, max_gain, clip_permille, rate, state):
+    """stm_d_depth_fit: the measurement of the automatic depth budget as a stage -- both maps (float32 [H][W] on the GPU) into the
+    quarter-pixel histogram, the fit, the update of `state` (float32, four elements on the GPU) in place; nothing synchronised."""
+    H, W = disp_l.shape
+    for t in (disp_l, disp_r):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
+    assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous() and state.numel() == 4
+    _use_current_stream()
+    lib().stm_d_depth_fit(_p(disp_l), _p(disp_r), H, W, float(disp_lo), float(disp_hi), float(max_gain), int(clip_permille), float(rate),
+                          _p(state))
+
+
 def d_mux_multiview_lens(views, out, mode, pitch, slope, centre):
     """stm_d_mux_multiview_lens: the views (a list of N uint8 [H][W][E] tensors on the GPU, views[0] = the right image ...
     views[N - 1] = the left image) interlaced into out (uint8 [Ho][Wo][E], only the first three bytes of a pixel are written)

@@ -325,6 +325,22 @@ def disp_temporal(disp, disp_prev, img, img_prev, alpha=0.5, thresh_color=24, th
     return out
 
 
+def depth_fit(disp_l, disp_r, disp_lo, disp_hi, max_gain=1.0, clip_permille=20, rate=1.0, state=None):
+    """The measurement of the automatic depth budget (stm_depth_fit; an addition, the reference's views always span the camera
+    baseline): the gain and convergence that bring the clipped disparity range of the two maps [H][W] into [disp_lo, disp_hi],
+    folded into `state` = (valid, gain, conv, 0) (None = no history).  Returns the new state as a float32 array of four; nothing
+    passed in is modified."""
+    disp_l, pl = _f32(disp_l)
+    disp_r, pr = _f32(disp_r)
+    H, W = disp_l.shape
+    assert disp_r.shape == (H, W)
+    st = np.zeros(4, np.float32) if state is None else np.array(state, dtype=np.float32, order="C")
+    assert st.shape == (4,)
+    lib().stm_depth_fit(pl, pr, H, W, float(disp_lo), float(disp_hi), float(max_gain), int(clip_permille), float(rate),
+                        st.ctypes.data_as(f32p))
+    return st
+
+
 def tx_scale(img, out_rows, out_cols):
     """d_tx_scale.h:17-18 (bilinear resize)."""
     img, pi = _u8(img)

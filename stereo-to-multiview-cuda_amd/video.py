@@ -17,9 +17,12 @@ class FrameStream:
     input_format "bgr" (the default): a frame is a side-by-side BGR array uint8 [H][2W][3].  "nv12": a frame is uint8 [H * 3 / 2][2W],
     the Y plane followed by the interleaved UV plane, as a decoder or read_nv12_sequence delivers it; `matrix` selects the colour
     conversion (stm_demux_nv12: 0 / 1 = BT.601 / BT.709 limited range, 2 / 3 = full range).  lens = (mode, pitch, slope, centre): the
-    panel's calibration (set_lens); None = the reference's interlacer."""
+    panel's calibration (set_lens); None = the reference's interlacer.  depth = (gain, conv): the manual depth budget (set_depth mode 1);
+    depth_auto = (disp_lo, disp_hi[, max_gain, clip_permille, rate]): the automatic one (mode 2), fitted to every frame on the GPU;
+    at most one of the two."""
 
-    def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None):
+    def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
+                 depth=None, depth_auto=None):
         self.H, self.W = num_rows, num_cols
         self.in_shape = (num_rows, 2 * num_cols, 3)
         self.Ho, self.Wo = out_rows or num_rows, out_cols or num_cols
@@ -33,6 +36,35 @@ class FrameStream:
             self.set_input(input_format, matrix)
         if lens is not None:
             self.set_lens(*lens)
+        if depth is not None and depth_auto is not None:
+            raise ValueError("FrameStream: depth and depth_auto are mutually exclusive")
+        if depth is not None:
+            self.set_depth(1, *depth)
+        if depth_auto is not None:
+            self.set_depth_auto(*depth_auto)
+            self.set_depth(2)
+
+    def set_depth(self, mode, gain=1.0, conv=0.0):
+        """stm_stream_set_depth: the depth budget of the stream's frames (device_api.set_depth's arguments); the stream's own,
+        independent of the calling thread's; only before the first submit.  Mode 2 needs set_depth_auto first.  Raises ValueError
+        where the library refuses."""
+        if int(lib().stm_stream_set_depth(self._h, int(mode), float(gain), float(conv))) != 0:
+            raise ValueError("stm_stream_set_depth(%d, %g, %g) refused: %s" % (mode, gain, conv, lib().stm_last_error().decode()))
+
+    def set_depth_auto(self, disp_lo, disp_hi, max_gain=1.0, clip_permille=20, rate=1.0):
+        """stm_stream_set_depth_auto: mode 2's parameters (device_api.set_depth_auto's; the state is the stream's own); only before
+        the first submit.  Raises ValueError where the library refuses."""
+        if int(lib().stm_stream_set_depth_auto(self._h, float(disp_lo), float(disp_hi), float(max_gain), int(clip_permille),
+                                               float(rate))) != 0:
+            raise ValueError("stm_stream_set_depth_auto(%g, %g, %g, %d, %g) refused: %s"
+                             % (disp_lo, disp_hi, max_gain, clip_permille, rate, lib().stm_last_error().decode()))
+
+    def depth(self):
+        """stm_stream_depth: (gain, conv) applied to the most recently collected frame, or None before the first collect."""
+        out = (C.c_float * 2)()
+        if int(lib().stm_stream_depth(self._h, C.cast(out, f32p))) != 0:
+            return None
+        return float(out[0]), float(out[1])
 
     def set_lens(self, mode, pitch=0.0, slope=0.0, centre=0.0):
         """stm_stream_set_lens: the display geometry the stream's frames are interlaced through (device_api.set_lens's arguments);
@@ -109,27 +141,36 @@ class FrameStream:
             pass
 
 
-def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None):
+def _collect(fs, on_depth):
+    r = fs.collect()
+    if on_depth is not None and r is not None:
+        on_depth(r[0], fs.depth())
+    return r
+
+
+def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None,
+                     depth=None, depth_auto=None, on_depth=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
     stabilisation); temporal: (alpha, thresh_color, thresh_disp) for FrameStream.set_temporal, None = the defaults; lens: (mode,
-    pitch, slope, centre) for FrameStream.set_lens, None = the reference's interlacer."""
+    pitch, slope, centre) for FrameStream.set_lens, None = the reference's interlacer; depth / depth_auto: FrameStream's depth
+    budget; on_depth: called with (index, (gain, conv)) after every collected frame."""
     fs = None
     pending = 0
     for sbs in frames:
         if fs is None:
             rows = sbs.shape[0] * 2 // 3 if input_format == "nv12" else sbs.shape[0]
-            fs = FrameStream(rows, sbs.shape[1] // 2, params, out_rows, out_cols, stages, input_format, matrix, lens)
+            fs = FrameStream(rows, sbs.shape[1] // 2, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:
-            yield fs.collect()
+            yield _collect(fs, on_depth)
             pending -= 1
         fs.submit(sbs)
         pending += 1
     while fs is not None and pending:
-        yield fs.collect()
+        yield _collect(fs, on_depth)
         pending -= 1
     if fs is not None:
         fs.close()

@@ -6,6 +6,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     <census coeff> <ucd> <lcd> <usd> <lsd> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel] [--linear-warp]
                     [--temporal [--temporal-alpha A] [--temporal-color C] [--temporal-disp T]]
                     [--nv12 ROWS COLS_SBS [--matrix M]] [--lens MODE PITCH SLOPE CENTRE]
+                    [--depth GAIN CONV | --depth-auto LO HI [MAX_GAIN CLIP RATE]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -18,6 +19,11 @@ BT.709 limited range, 2 / 3 = BT.601 / BT.709 full range.
 --lens MODE PITCH SLOPE CENTRE (an addition): the panel's calibration (stm_set_lens) -- PITCH sub-pixels per lens, SLOPE sub-pixels
 of lens shift per output row, CENTRE lenses of phase offset; MODE 1 = nearest view, 2 = two views blended, 3 = every sub-pixel
 rendered at its own continuous position.  Replaces the reference's interlacer; <angle> is then ignored.
+--depth GAIN CONV (an addition): the manual depth budget (stm_set_depth mode 1) -- a scene point of disparity d is shown with
+GAIN * d - CONV (GAIN in [0, 8]; CONV in input-view pixels, |CONV| <= 4096).  --depth-auto LO HI [MAX_GAIN CLIP RATE]: the automatic
+one (mode 2) -- every frame's disparity range, less CLIP/1000 of its pixels at either end (20), is brought into the panel's budget
+[LO, HI] with a gain of at most MAX_GAIN (1), following the fit at RATE (1); each frame's applied pair is printed.  The two
+options are mutually exclusive.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -65,6 +71,36 @@ def main(argv):
             return -1
         lens = (int(argv[at + 1]), float(argv[at + 2]), float(argv[at + 3]), float(argv[at + 4]))
         del argv[at:at + 5]
+    depth, depth_auto = None, None
+    try:
+        if "--depth" in argv:
+            at = argv.index("--depth")
+            depth = (float(argv[at + 1]), float(argv[at + 2]))
+            if not (0.0 <= depth[0] <= 8.0 and abs(depth[1]) <= 4096.0):
+                raise ValueError(depth)
+            del argv[at:at + 3]
+        if "--depth-auto" in argv:
+            at = argv.index("--depth-auto")
+            vals = []
+            for x in argv[at + 1:at + 6]:  # LO HI, then up to three optional numbers
+                try:
+                    vals.append(float(x))
+                except ValueError:
+                    break
+            if len(vals) not in (2, 5):
+                raise ValueError(vals)
+            lo, hi = vals[0], vals[1]
+            mg, clip, rate = vals[2:] if len(vals) == 5 else (1.0, 20.0, 1.0)
+            if not (lo < hi and abs(lo) <= 4096.0 and abs(hi) <= 4096.0 and 0.0 < mg <= 8.0 and clip == int(clip) and 0 <= clip <= 499
+                    and 0.0 < rate <= 1.0):
+                raise ValueError(vals)
+            depth_auto = (lo, hi, mg, int(clip), rate)
+            del argv[at:at + 1 + len(vals)]
+        if depth is not None and depth_auto is not None:
+            raise ValueError("--depth and --depth-auto")
+    except (ValueError, IndexError):
+        print(__doc__)
+        return -1
     if len(argv) not in (16, 17):
         print(__doc__)
         return -1
@@ -81,7 +117,9 @@ def main(argv):
     t0 = time.perf_counter()
     n = 0
     for (k, dl, dr, inter) in video.process_sequence(frames, p, out_h, out_w, stages, tuple(temporal) if stages & 0x2000 else None,
-                                                       "bgr" if nv12 is None else "nv12", matrix, lens):
+                                                       "bgr" if nv12 is None else "nv12", matrix, lens, depth, depth_auto,
+                                                       (lambda k, gc: print("frame %d: gain %.6g conv %.6g" % (k, gc[0], gc[1])))
+                                                       if depth_auto is not None else None):
         video.write_outputs(out_dir, k, dl, dr, inter)
         n += 1
     dt = time.perf_counter() - t0
