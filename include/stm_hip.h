@@ -143,6 +143,24 @@ int         stm_set_depth(int mode, float gain, float conv);
  * means scratch memory, with every frame fitted on its own.  A caller resets the history, for a scene cut, by zeroing `valid`.
  * Returns 0, or -1 with stm_last_error set and the old parameters in place. */
 int         stm_set_depth_auto(float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate, float *d_state);
+/* The calling thread's input packing (an addition; see stm_demux_packed for the definition and the rules): where the two eyes lie in
+ * the frame that stm_d_adcensus_stm, stm_d_adcensus_stm_t and stm_d_adcensus_stm_nv12 are given.  The default is (0, 0, 0, 0), the
+ * reference's layout, with which not one launch, argument or kernel changes.  Under any other setting num_rows and num_cols stay the
+ * size of an eye AFTER unpacking (what every later stage sees), num_cols_sbs stays the frame's row length in pixels, the frame has
+ * rows_f rows, and the geometry rules of stm_demux_packed (stm_demux_nv12_packed for the NV12 call) replace num_cols_sbs >= 2 *
+ * num_cols; a violation fails through stm_last_error before anything is launched.  The frame is by definition the same call, packing
+ * off, on the side-by-side frame whose halves are the two unpacked eyes; the frame's first kernel gathers, filters and (NV12)
+ * converts as it fetches, no unpacked frame is materialised, every `stages` bit keeps its meaning and every later kernel is unchanged.
+ * With 0x2000, stm_d_adcensus_stm_t's d_prev_img_sbs is the previous PACKED frame and its images are by definition its unpacking
+ * (one extra launch); stm_d_adcensus_stm_nv12 takes split history as always.  This is an input geometry, not a stage: no `stages`
+ * bit belongs to it.  The host-flavour stm_adcensus_stm and the four adcensus_stm_2 / _2s calls take the reference's layout only:
+ * with a packing set on the thread they fail through stm_last_error, they do not ignore it.
+ * Returns 0, or -1 with stm_last_error set and the thread's packing unchanged (a setting outside its range; filter != 0 with packing
+ * 0 or 2). */
+int         stm_set_packing(int packing, int swap, int filter, int gap);
+/* out[0 .. 3] = the calling thread's packing, swap, filter and gap as the last accepted stm_set_packing left them ((0, 0, 0, 0) if
+ * none was made).  A frame stream's own packing is not visible here except during its submit. */
+void        stm_get_packing(int *out);
 /* ci_adcensus / d_ci_adcensus (the per-stage calls; the frame calls always compute the clean costs): 0 (default) = clean
  * clamped indexing, the canonical form (SURVEY A-Q7); 1 = reproduce the reference's shared-tile strays at d = 0 in columns
  * 160 k (left cost) and 160 k + 159 (right cost): the census term always, the AD term when num_disp - zero_disp <= zero_disp
@@ -386,6 +404,54 @@ void stm_demux_nv12(unsigned char *img_l, unsigned char *img_r, unsigned char *y
                     int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz, int matrix);
 void stm_d_demux_nv12(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv,
                       int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz, int matrix);
+/* Packed stereo frames (an addition: the reference takes two full-resolution eyes side by side, left first, a layout almost no stereo
+ * video is stored in).  The unpacking as a stage: the counterpart of stm_d_demux_sbs for a frame in one of the common packings.
+ *   packing  0 = side by side, full;  1 = side by side, each eye squeezed to half the columns;
+ *            2 = top and bottom, full;  3 = top and bottom, each eye squeezed to half the rows.
+ *   swap     0 or 1: the right eye comes first.
+ *   filter   0 = linear, 1 = Catmull-Rom: how a squeezed eye is expanded (packings 1 and 3 only; with 0 and 2 it must be 0).
+ *   gap      >= 0 (at most 2^24): pixels between the two eyes along the packing axis -- columns for packings 0 and 1, rows for 2 and 3
+ *            (HDMI / Blu-ray frame packing is packing 2 with the blank band as the gap).
+ * H = num_rows and W = num_cols_out are the size of an eye AFTER unpacking.  The packed eye is Hp x Wp, the frame has rows_f rows of
+ * num_cols_sbs pixels:
+ *   packing   Hp x Wp      rows_f        required row length
+ *      0      H x W        H             num_cols_sbs >= 2 W + gap
+ *      1      H x W/2      H             num_cols_sbs >= 2 Wp + gap
+ *      2      H x W        2 H + gap     num_cols_sbs >= W
+ *      3      H/2 x W      2 Hp + gap    num_cols_sbs >= W
+ * Eye e (0 = left, 1 = right) is the q-th in the frame, q = e ^ swap; its origin (row, column) is
+ *   (0, q (Wp + gap))   for packings 0 and 1
+ *   (q (Hp + gap), 0)   for packings 2 and 3.
+ * Packings 0 and 2 copy.  Packings 1 and 3 expand by two along one axis (x for 1, y for 3).  P = the packed eye along that axis, n
+ * samples; every index is clamped to [0, n - 1] of the eye's own region, never into the gap or the other eye.  Per byte B, G, R, for
+ * output index x, in 32-bit signed integers, >> an arithmetic shift:
+ *   k = x >> 1;  s = +1 if x is odd, else -1
+ *   out = clip255((w0 P[k - s] + w1 P[k] + w2 P[k + s] + w3 P[k + 2 s] + 64) >> 7)
+ *   (w0, w1, w2, w3) = (0, 96, 32, 0)      filter 0: exactly (3 P[k] + P[k + s] + 2) >> 2
+ *                      (-9, 111, 29, -3)   filter 1
+ * These are the half-pixel-centred 2 x up-sampling positions k -+ 1/4 of the linear and the Catmull-Rom kernels (the latter's weights
+ * at 1/4 are whole multiples of 1/128); both sets sum to 128, so a constant eye is reproduced exactly; a tap of weight 0 need not be read.
+ * Pixel format as stm_demux_nv12: img_l / img_r are H x W x elem_sz with B, G, R in a pixel's first three bytes, of the frame only
+ * the first three bytes of a pixel are read; the bytes past the third come back 0 from the host flavour and are left as they were
+ * by the device flavour.  The frame is read only and may have any byte alignment.
+ * stm_demux_nv12_packed takes stm_demux_nv12's planes and matrix: the result is by definition the unpacking above applied to the BGR
+ * picture that stm_demux_nv12's conversion gives on the PACKED frame -- chroma replicated at packed resolution, in frame coordinates:
+ * frame pixel (row, col) uses uv[row >> 1][2 (col >> 1)], [.. + 1].  y has rows_f rows, uv rows_f / 2.  Every eye origin and Wp, Hp
+ * must be even: W and H even, W % 4 == 0 for packing 1, H % 4 == 0 for packing 3, gap even; pitch_y >= num_cols_sbs, pitch_uv >=
+ * 2 * ((num_cols_sbs + 1) / 2).
+ * Errors (stm_last_error), all reported before anything is launched or written: a setting outside its range; filter != 0 with
+ * packing 0 or 2 (an error, not ignored); an odd W with packing 1, an odd H with packing 3; a row length or a pitch below the rule;
+ * the NV12 evenness rules; matrix outside 0 .. 3.  Parity is against a numpy statement of these lines (parity unpinned). */
+void stm_demux_packed(unsigned char *img_l, unsigned char *img_r, unsigned char *img, int num_rows, int num_cols_sbs, int num_cols_out,
+                      int elem_sz, int packing, int swap, int filter, int gap);
+void stm_d_demux_packed(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_img, int num_rows, int num_cols_sbs,
+                        int num_cols_out, int elem_sz, int packing, int swap, int filter, int gap);
+void stm_demux_nv12_packed(unsigned char *img_l, unsigned char *img_r, unsigned char *y, int pitch_y, unsigned char *uv, int pitch_uv,
+                           int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz, int matrix, int packing, int swap, int filter,
+                           int gap);
+void stm_d_demux_nv12_packed(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_y, int pitch_y, unsigned char *d_uv,
+                             int pitch_uv, int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz, int matrix, int packing, int swap,
+                             int filter, int gap);
 
 /* ------------------------------------------------------------ whole frame (a26) */
 /* d_io.h:32-40  adcensus_stm (d_io.cu:7-238).  `angle` is float here (the reference's int truncates
@@ -627,6 +693,17 @@ int   stm_stream_set_temporal(void *stream, float alpha, int thresh_color, float
  * images, and with 0x2000 the other slot's images and maps are the history.  `matrix` is ignored for format 0.  Only before the
  * first submit.  Returns 0, or -1 with stm_last_error set. */
 int   stm_stream_set_input(void *stream, int format, int matrix);
+/* the packing of the stream's input frames (stm_set_packing's settings; the geometry rules of stm_demux_packed, in NV12 mode those of
+ * stm_demux_nv12_packed, on the stream's num_rows, num_cols_sbs and num_cols with both pitches num_cols_sbs; the default is
+ * (0, 0, 0, 0)).  num_rows and num_cols stay the unpacked eye's size; a frame then has rows_f rows of num_cols_sbs pixels:
+ * stm_stream_submit reads rows_f * num_cols_sbs * elem_sz bytes, in NV12 mode rows_f * num_cols_sbs * 3 / 2 (the UV plane at byte
+ * rows_f * num_cols_sbs), so a half packing uploads half the bytes again.  Each slot's pinned and device input buffers are allocated
+ * anew for rows_f * num_cols_sbs * elem_sz bytes: pointers obtained from stm_stream_input_buffer BEFORE this call are void afterwards.
+ * It combines with stm_stream_set_input in either order (whichever comes second checks the combination), with 0x2000 (in BGR mode the
+ * other slot's packed frame is the history, unpacked by one extra launch) and with the captured graphs: the gather reads nothing back.
+ * The stream keeps its own copy and installs it only around its frame calls, like the lens geometry.  Only before the first submit.
+ * Returns 0, or -1 with stm_last_error set and the stream unchanged. */
+int   stm_stream_set_packing(void *stream, int packing, int swap, int filter, int gap);
 /* the display geometry of the stream's frames (stm_set_lens's rules; the default is mode 0).  The stream keeps its own copy and
  * installs it only for the duration of its frame calls: the calling thread's stm_set_lens neither reaches the stream's frames
  * (or its captured graph) nor is changed by them.  Only before the first submit.  Returns 0, or -1 with stm_last_error set. */

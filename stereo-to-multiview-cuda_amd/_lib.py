@@ -34,6 +34,8 @@ PROTOS = {
     "stm_set_irv_paper_ratio": ([i], None),
     "stm_set_ref_quirks": ([i], None),
     "stm_set_lens": ([i, d, d, d], i),
+    "stm_set_packing": ([i, i, i, i], i),
+    "stm_get_packing": ([C.POINTER(C.c_int)], None),
     "stm_set_depth": ([i, f, f], i),
     "stm_set_depth_auto": ([f, f, f, i, f, vp], i),
     "stm_ci_adcensus": ([u8p, u8p, f32pp, f32pp, f, f, i, i, i, i, i], None),
@@ -78,6 +80,10 @@ PROTOS = {
     "stm_d_demux_sbs": ([vp, vp, vp, i, i, i, i], None),
     "stm_demux_nv12": ([u8p, u8p, u8p, i, u8p, i, i, i, i, i, i], None),
     "stm_d_demux_nv12": ([vp, vp, vp, i, vp, i, i, i, i, i, i], None),
+    "stm_demux_packed": ([u8p, u8p, u8p, i, i, i, i, i, i, i, i], None),
+    "stm_d_demux_packed": ([vp, vp, vp, i, i, i, i, i, i, i, i], None),
+    "stm_demux_nv12_packed": ([u8p, u8p, u8p, i, u8p, i, i, i, i, i, i, i, i, i, i], None),
+    "stm_d_demux_nv12_packed": ([vp, vp, vp, i, vp, i, i, i, i, i, i, i, i, i, i], None),
     "stm_adcensus_stm": ([u8p, f32p, f32p, u8p, i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f], None),
     "stm_d_adcensus_stm": ([vp, vp, vp, vp, i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f, i], None),
     "stm_d_adcensus_stm_t": ([vp, vp, vp, vp, i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f, i, vp, vp, vp, f, i, f], None),
@@ -99,6 +105,7 @@ PROTOS = {
     "stm_stream_set_stages": ([C.c_void_p, i], i),
     "stm_stream_set_temporal": ([C.c_void_p, f, i, f], i),
     "stm_stream_set_input": ([C.c_void_p, i, i], i),
+    "stm_stream_set_packing": ([C.c_void_p, i, i, i, i], i),
     "stm_stream_set_lens": ([C.c_void_p, i, d, d, d], i),
     "stm_stream_set_depth": ([C.c_void_p, i, f, f], i),
     "stm_stream_set_depth_auto": ([C.c_void_p, f, f, f, i, f], i),

@@ -342,6 +342,51 @@ bool stm::nv12_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_c
     return false;
 }
 
+// the rules of a packed frame (stm_hip.h, stm_demux_packed), after the dimension screen
+bool stm::packing_args_ok(const char *fn, const Packing &pk, int num_rows, int num_cols_sbs, int num_cols, const char *cols_name, bool nv12,
+                          int pitch_y, int pitch_uv, int matrix)
+{
+    if (!packing_params_ok(fn, pk)) return false;
+    char msg[240];
+    const char *arg = nullptr;
+    const int H = num_rows, W = num_cols, half = pk.packing & 1, axis = pk.packing >> 1;
+    const long long need = axis == 0 ? 2LL * (half ? W / 2 : W) + pk.gap : W; // the row the rule asks for
+    if (pk.packing == 1 && (W & 1)) {
+        snprintf(msg, sizeof msg, "%s: %s = %d, must be even with packing 1 (each eye is squeezed to half the columns)", fn, cols_name, W);
+        arg = cols_name;
+    } else if (pk.packing == 3 && (H & 1)) {
+        snprintf(msg, sizeof msg, "%s: num_rows = %d, must be even with packing 3 (each eye is squeezed to half the rows)", fn, H);
+        arg = "num_rows";
+    } else if (num_cols_sbs < need) {
+        snprintf(msg, sizeof msg, "%s: num_cols_sbs = %d, must be >= %lld with packing %d, gap %d and %s = %d", fn, num_cols_sbs, need, pk.packing,
+                 pk.gap, cols_name, W);
+        arg = "num_cols_sbs";
+    } else if (nv12 && ((H & 1) || (pk.packing == 3 && (H & 3)))) {
+        snprintf(msg, sizeof msg, "%s: num_rows = %d, must be a multiple of %d for NV12 with packing %d (each packed eye has an even number of rows)",
+                 fn, H, pk.packing == 3 ? 4 : 2, pk.packing);
+        arg = "num_rows";
+    } else if (nv12 && ((W & 1) || (pk.packing == 1 && (W & 3)))) {
+        snprintf(msg, sizeof msg, "%s: %s = %d, must be a multiple of %d for NV12 with packing %d (each packed eye starts on a chroma sample)",
+                 fn, cols_name, W, pk.packing == 1 ? 4 : 2, pk.packing);
+        arg = cols_name;
+    } else if (nv12 && (pk.gap & 1)) {
+        snprintf(msg, sizeof msg, "%s: gap = %d, must be even for NV12 (the second eye starts on a chroma sample)", fn, pk.gap);
+        arg = "gap";
+    } else if (nv12 && pitch_y < num_cols_sbs) {
+        snprintf(msg, sizeof msg, "%s: pitch_y = %d, must be >= num_cols_sbs = %d", fn, pitch_y, num_cols_sbs);
+        arg = "pitch_y";
+    } else if (nv12 && pitch_uv < 2 * ((num_cols_sbs + 1) / 2)) {
+        snprintf(msg, sizeof msg, "%s: pitch_uv = %d, must be >= 2 * ((num_cols_sbs + 1) / 2) = %d", fn, pitch_uv, 2 * ((num_cols_sbs + 1) / 2));
+        arg = "pitch_uv";
+    } else if (nv12 && (matrix < 0 || matrix > 3)) {
+        snprintf(msg, sizeof msg, "%s: matrix = %d, must be 0 (BT.601 limited), 1 (BT.709 limited), 2 (BT.601 full) or 3 (BT.709 full)", fn, matrix);
+        arg = "matrix";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+
 extern "C" {
 
 // =============================================================== cost init
@@ -949,6 +994,73 @@ void stm_demux_nv12(unsigned char *img_l, unsigned char *img_r, unsigned char *y
     sync();
 }
 
+
+// packed input (an addition): the unpacking as a stage, from a BGR frame and from NV12 planes (stm_hip.h)
+void stm_d_demux_packed(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_img, int num_rows, int num_cols_sbs,
+                        int num_cols_out, int elem_sz, int packing, int swap, int filter, int gap)
+{
+    const char *fn = "d_demux_packed";
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols_out", num_cols_out, 1}, {"elem_sz", elem_sz, 3}}))
+        return;
+    const Packing pk = {packing, swap, filter, gap};
+    if (!packing_args_ok(fn, pk, num_rows, num_cols_sbs, num_cols_out, "num_cols_out", false, 0, 0, 0)) return;
+    launch_demux_packed(d_img_l, d_img_r, PackInput{pk, false, d_img, num_cols_sbs, nullptr, nullptr, 0, 0, 0}, num_rows, num_cols_out, elem_sz);
+}
+void stm_demux_packed(unsigned char *img_l, unsigned char *img_r, unsigned char *img, int num_rows, int num_cols_sbs, int num_cols_out,
+                      int elem_sz, int packing, int swap, int filter, int gap)
+{
+    const char *fn = "demux_packed";
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols_out", num_cols_out, 1}, {"elem_sz", elem_sz, 3}}))
+        return;
+    const Packing pk = {packing, swap, filter, gap};
+    if (!packing_args_ok(fn, pk, num_rows, num_cols_sbs, num_cols_out, "num_cols_out", false, 0, 0, 0)) return;
+    const size_t IMG = (size_t)num_rows * num_cols_out * elem_sz, in_sz = (size_t)pk.rows_f(num_rows) * num_cols_sbs * elem_sz;
+    Workspace::begin(2 * IMG + in_sz + 4096);
+    u8 *d = up(img, in_sz), *l = Workspace::get<u8>(IMG), *r = Workspace::get<u8>(IMG);
+    if (elem_sz > 3) { // bytes past a pixel's third come back 0, not as the workspace held them
+        STM_CHECK(hipMemsetAsync(l, 0, IMG, stream()));
+        STM_CHECK(hipMemsetAsync(r, 0, IMG, stream()));
+    }
+    launch_demux_packed(l, r, PackInput{pk, false, d, num_cols_sbs, nullptr, nullptr, 0, 0, 0}, num_rows, num_cols_out, elem_sz);
+    down(img_l, l, IMG); down(img_r, r, IMG);
+    sync();
+}
+void stm_d_demux_nv12_packed(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_y, int pitch_y, unsigned char *d_uv,
+                             int pitch_uv, int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz, int matrix, int packing, int swap,
+                             int filter, int gap)
+{
+    const char *fn = "d_demux_nv12_packed";
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols_out", num_cols_out, 1}, {"elem_sz", elem_sz, 3}}))
+        return;
+    const Packing pk = {packing, swap, filter, gap};
+    if (!packing_args_ok(fn, pk, num_rows, num_cols_sbs, num_cols_out, "num_cols_out", true, pitch_y, pitch_uv, matrix)) return;
+    launch_demux_packed(d_img_l, d_img_r, PackInput{pk, true, nullptr, num_cols_sbs, d_y, d_uv, pitch_y, pitch_uv, matrix}, num_rows,
+                        num_cols_out, elem_sz);
+}
+void stm_demux_nv12_packed(unsigned char *img_l, unsigned char *img_r, unsigned char *y, int pitch_y, unsigned char *uv, int pitch_uv,
+                           int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz, int matrix, int packing, int swap, int filter,
+                           int gap)
+{
+    const char *fn = "demux_nv12_packed";
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols_out", num_cols_out, 1}, {"elem_sz", elem_sz, 3}}))
+        return;
+    const Packing pk = {packing, swap, filter, gap};
+    if (!packing_args_ok(fn, pk, num_rows, num_cols_sbs, num_cols_out, "num_cols_out", true, pitch_y, pitch_uv, matrix)) return;
+    // the planes follow the frame's rows; a plane's last row need not be a whole pitch long
+    const int rows_f = pk.rows_f(num_rows);
+    const size_t IMG = (size_t)num_rows * num_cols_out * elem_sz, uv_row = 2 * (size_t)((num_cols_sbs + 1) / 2);
+    const size_t y_sz = (size_t)(rows_f - 1) * pitch_y + num_cols_sbs, uv_sz = (size_t)(rows_f / 2 - 1) * pitch_uv + uv_row;
+    Workspace::begin(2 * IMG + y_sz + uv_sz + 4096);
+    u8 *dy = up(y, y_sz), *duv = up(uv, uv_sz), *l = Workspace::get<u8>(IMG), *r = Workspace::get<u8>(IMG);
+    if (elem_sz > 3) {
+        STM_CHECK(hipMemsetAsync(l, 0, IMG, stream()));
+        STM_CHECK(hipMemsetAsync(r, 0, IMG, stream()));
+    }
+    launch_demux_packed(l, r, PackInput{pk, true, nullptr, num_cols_sbs, dy, duv, pitch_y, pitch_uv, matrix}, num_rows, num_cols_out, elem_sz);
+    down(img_l, l, IMG); down(img_r, r, IMG);
+    sync();
+}
+
 } // extern "C"
 
 // device staging buffers of the blocking host-flavour frame calls: grow-only, one set per host thread and device (the
@@ -1265,12 +1377,22 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
     const int H = num_rows, W = num_cols, N = num_views;
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
     const size_t V = pq_volume_floats(num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
-    Workspace::begin(((stages & 0x100) ? 13 : 4) * V * 4 + (size_t)(N + 2) * IMG + 168 * HW + (1u << 20));
+    const Packing pack = packing(); // a packed frame (stm_set_packing): the caller has screened its geometry
+    Workspace::begin(((stages & 0x100) ? 13 : 4) * V * 4 + (size_t)(N + 2 + (pack.on() && hist && !nv ? 2 : 0)) * IMG + 168 * HW + (1u << 20));
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     uint32_t *pre[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool fused_split = num_cols_sbs >= 2 * W; // both halves complete: emit the derived pixel formats in the same pass
-    if (nv && (agg_variant() / 100) % 10 != 6) { // the conversion in stm_k_front's pass
+    const PackInput pin = {pack, nv != nullptr, d_img_sbs, num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr, nv ? nv->pitch_y : 0,
+                           nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0};
+    if (pack.on() && (agg_variant() / 100) % 10 != 6) { // the gather, the filter and the conversion in stm_k_front's pass
+        for (int i = 0; i < 6; ++i) pre[i] = Workspace::get<uint32_t>(HW);
+        launch_front_pack(img_l, img_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], pin, H, W, elem_sz);
+        fused_split = true;
+    } else if (pack.on()) { // 600: the plain unpacking, then the pixel formats and the census as kernels of their own
+        launch_demux_packed(img_l, img_r, pin, H, W, elem_sz);
+        fused_split = false;
+    } else if (nv && (agg_variant() / 100) % 10 != 6) { // the conversion in stm_k_front's pass
         for (int i = 0; i < 6; ++i) pre[i] = Workspace::get<uint32_t>(HW);
         launch_front_nv12(img_l, img_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], nv->y, nv->pitch_y, nv->uv, nv->pitch_uv, H, W,
                           elem_sz, nv->matrix);
@@ -1300,9 +1422,19 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
     if (hist) {
         float *c[2] = {d_disp_l, d_disp_r};
         const float *q[2] = {hist->disp_l, hist->disp_r};
-        const u8 *im[2] = {nv ? img_l : d_img_sbs, nv ? img_r : d_img_sbs}, *ip[2] = {nv ? hist->img_l : hist->sbs, nv ? hist->img_r : hist->sbs};
-        const size_t off[2] = {0, nv ? 0 : (size_t)W * elem_sz};
-        launch_disp_temporal(2, c, q, im, ip, off, H, W, nv ? W : num_cols_sbs, elem_sz, hist->alpha, hist->thresh_color, hist->thresh_disp);
+        const bool split = nv || pack.on(); // the views as split images; otherwise in place in the two side-by-side frames
+        const u8 *prev_l = hist->img_l, *prev_r = hist->img_r;
+        if (pack.on() && !nv) { // the previous PACKED frame: its images are its unpacking (one more launch in this combination only)
+            u8 *ul = Workspace::get<u8>(IMG), *ur = Workspace::get<u8>(IMG);
+            PackInput prev = pin;
+            prev.frame = hist->sbs;
+            launch_demux_packed(ul, ur, prev, H, W, elem_sz);
+            prev_l = ul;
+            prev_r = ur;
+        }
+        const u8 *im[2] = {split ? img_l : d_img_sbs, split ? img_r : d_img_sbs}, *ip[2] = {split ? prev_l : hist->sbs, split ? prev_r : hist->sbs};
+        const size_t off[2] = {0, split ? 0 : (size_t)W * elem_sz};
+        launch_disp_temporal(2, c, q, im, ip, off, H, W, split ? W : num_cols_sbs, elem_sz, hist->alpha, hist->thresh_color, hist->thresh_disp);
     }
     if (stages < 3) return;
     frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle, linwarp);
@@ -1316,6 +1448,23 @@ bool frame_dims_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols,
                         {"num_views", num_views, 2}, {"num_disp", num_disp, 1}});
 }
 
+// the thread's packing (stm_set_packing) against a BGR frame call's geometry; packing off: nothing to check, the call is as it was
+bool frame_packing_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols)
+{
+    const Packing pk = packing();
+    return !pk.on() || packing_args_ok(fn, pk, num_rows, num_cols_sbs, num_cols, "num_cols", false, 0, 0, 0);
+}
+// the calls that take the reference's layout only
+bool packing_unsupported(const char *fn)
+{
+    if (!packing().on()) return false;
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: a packing is set on this thread (stm_set_packing), which this call does not support: use d_adcensus_stm, "
+             "d_adcensus_stm_t or d_adcensus_stm_nv12", fn);
+    fail(msg, "packing", __FILE__, __LINE__);
+    return true;
+}
+
 } // namespace
 
 extern "C" {
@@ -1326,6 +1475,7 @@ void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp
                         float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages)
 {
     if (!frame_dims_ok("d_adcensus_stm", num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views, num_disp)) return;
+    if (!frame_packing_ok("d_adcensus_stm", num_rows, num_cols_sbs, num_cols)) return;
     if (stages & 0x2000) { // temporal stabilisation needs the previous frame: this call has no arguments for it
         fail("d_adcensus_stm: stages 0x2000 (temporal stabilisation) needs the history arguments of d_adcensus_stm_t", "stages", __FILE__,
              __LINE__);
@@ -1345,6 +1495,7 @@ void stm_d_adcensus_stm_t(unsigned char *d_img_sbs, float *d_disp_l, float *d_di
 {
     const char *fn = "d_adcensus_stm_t";
     if (!frame_dims_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views, num_disp)) return;
+    if (!frame_packing_ok(fn, num_rows, num_cols_sbs, num_cols)) return;
     TemporalHist hist = {d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp};
     bool run = false;
     if (stages & 0x2000) {
@@ -1360,7 +1511,7 @@ void stm_d_adcensus_stm_t(unsigned char *d_img_sbs, float *d_disp_l, float *d_di
                  __FILE__, __LINE__);
             return;
         }
-        if (nset == 3 && num_cols_sbs < 2 * num_cols) { // the views are read from the two halves in place
+        if (nset == 3 && !packing().on() && num_cols_sbs < 2 * num_cols) { // the views are read from the two halves in place
             fail("d_adcensus_stm_t: stages 0x2000 (temporal stabilisation) needs num_cols_sbs >= 2 * num_cols", "num_cols_sbs", __FILE__, __LINE__);
             return;
         }
@@ -1386,7 +1537,9 @@ void stm_d_adcensus_stm_nv12(unsigned char *d_y, int pitch_y, unsigned char *d_u
 {
     const char *fn = "d_adcensus_stm_nv12";
     if (!frame_dims_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views, num_disp)) return;
-    if (!nv12_args_ok(fn, num_rows, num_cols_sbs, num_cols, "num_cols", pitch_y, pitch_uv, matrix)) return;
+    if (packing().on()) { // a packed NV12 frame: the packing's own geometry rules in place of the side-by-side ones
+        if (!packing_args_ok(fn, packing(), num_rows, num_cols_sbs, num_cols, "num_cols", true, pitch_y, pitch_uv, matrix)) return;
+    } else if (!nv12_args_ok(fn, num_rows, num_cols_sbs, num_cols, "num_cols", pitch_y, pitch_uv, matrix)) return;
     if ((d_img_l != nullptr) != (d_img_r != nullptr)) {
         fail("d_adcensus_stm_nv12: d_img_l and d_img_r must be both null (the split images stay in the workspace) or both set", "d_img_l, d_img_r",
              __FILE__, __LINE__);
@@ -1446,6 +1599,7 @@ bool reduced_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_col
                       {"num_cols_disp", num_cols_disp, 1}, {"elem_sz", elem_sz, 3}, {"num_views", num_views, 2},
                       {"num_disp", num_disp, 1}}))
         return false;
+    if (packing_unsupported(fn)) return false;
     char msg[200];
     if ((stages & 0xff) != 3 || (stages & ~0x1fff)) { // this path always renders
         snprintf(msg, sizeof msg, "%s: stages = 0x%x, must be 3, optionally OR-ed with 0x100, 0x200, 0x400, 0x800 and 0x1000", fn, stages);
@@ -1600,6 +1754,7 @@ void stm_adcensus_stm(unsigned char *img_sbs, float *disp_l, float *disp_r, unsi
                                   {"num_rows_out", num_rows_out, 1}, {"num_cols_out", num_cols_out, 1},
                                   {"elem_sz", elem_sz, 3}, {"num_views", num_views, 2}, {"num_disp", num_disp, 1}}))
         return;
+    if (packing_unsupported("adcensus_stm")) return;
     size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
     size_t out_sz = (size_t)num_rows_out * num_cols_out * elem_sz;
     // own buffers are cached outside the workspace: the pipeline call below re-carves the workspace

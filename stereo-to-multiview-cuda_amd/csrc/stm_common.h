@@ -89,6 +89,32 @@ void set_depth(const Depth &d);
 // the argument rules of the two settings; false with the error recorded
 bool depth_params_ok(const char *fn, int mode, float gain, float conv);
 bool depth_auto_params_ok(const char *fn, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate);
+// The packing of the input frame (stm_set_packing, include/stm_hip.h): where the two eyes lie in the frame and how a squeezed eye is
+// expanded.  packing 0 / 1 = side by side full / half width, 2 / 3 = top and bottom full / half height; swap: the right eye comes
+// first; filter 0 = linear, 1 = Catmull-Rom (packings 1 and 3); gap: pixels between the eyes along the packing axis.  All 0 = off:
+// the reference's layout and the existing kernels.  One per host thread, next to the lens geometry; a frame stream installs its own.
+struct Packing {
+    int packing, swap, filter, gap;
+    bool on() const { return (packing | swap | filter | gap) != 0; }
+    int rows_f(int H) const { return packing == 2 ? 2 * H + gap : packing == 3 ? 2 * (H / 2) + gap : H; } // the frame's rows
+};
+Packing packing();
+void set_packing(const Packing &p);
+// the rules of the four settings alone (ranges; a filter with a full packing); false with the error recorded
+bool packing_params_ok(const char *fn, const Packing &pk);
+// stm_api.hip: the four settings and the geometry rules of a packed frame whose unpacked eyes are num_rows x num_cols (stm_hip.h);
+// nv12: the evenness rules, the two pitches and the matrix as well.  false with the error recorded.  cols_name: as nv12_args_ok
+bool packing_args_ok(const char *fn, const Packing &pk, int num_rows, int num_cols_sbs, int num_cols, const char *cols_name, bool nv12,
+                     int pitch_y, int pitch_uv, int matrix);
+// a screened packed frame as the kernels of stm_kernels_pack.hip take it: BGR (frame, num_cols_sbs pixels a row) or NV12 planes
+struct PackInput {
+    Packing pk;
+    bool nv12;
+    const u8 *frame;
+    int num_cols_sbs;
+    const u8 *y, *uv;
+    int pitch_y, pitch_uv, matrix;
+};
 int irv_paper_ratio(); // stm_set_irv_paper_ratio: accept on count / S instead of the reference's bin index / S (SURVEY A-Q17 iv)
 // Timing experiments (skip loads / sweeps / stores; results NOT valid) exist only in the separate libstm_hip_timing.so
 // (make timing, -DSTM_TIMING): in the product library every STM_DBG test is the constant false and stm_set_agg_variant
@@ -170,6 +196,11 @@ void launch_front(u8 *l, u8 *r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l
 void launch_front_nv12(u8 *l, u8 *r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l, uint32_t *wide_r, uint32_t *cen_l, uint32_t *cen_r,
                        const u8 *y, int pitch_y, const u8 *uv, int pitch_uv, int H, int W, int elem_sz, int matrix);
 void launch_demux_nv12(u8 *l, u8 *r, const u8 *y, int pitch_y, const u8 *uv, int pitch_uv, int H, int W, int elem_sz, int matrix);
+// packed input (stm_kernels_pack.hip; `in` screened by packing_args_ok): the two unpacked eyes H x W x elem_sz as a stage, and
+// launch_front on the unpacked frame without materialising it
+void launch_demux_packed(u8 *l, u8 *r, const PackInput &in, int H, int W, int elem_sz);
+void launch_front_pack(u8 *l, u8 *r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l, uint32_t *wide_r, uint32_t *cen_l, uint32_t *cen_r,
+                       const PackInput &in, int H, int W, int elem_sz);
 void launch_cost_init(const uint32_t *pk_l, const uint32_t *pk_r, const uint32_t *cen_l, const uint32_t *cen_r,
                       Vol cost_l, Vol cost_r, const float *lut_ad, const float *lut_census,
                       int D, int zd, int H, int W);

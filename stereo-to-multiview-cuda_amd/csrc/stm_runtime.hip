@@ -260,6 +260,35 @@ bool lens_params_ok(const char *fn, int mode, int mode_lo, int mode_hi, double p
     return false;
 }
 
+// the calling thread's input packing (stm_set_packing)
+static thread_local Packing g_packing = {0, 0, 0, 0};
+Packing packing() { return g_packing; }
+void set_packing(const Packing &p) { g_packing = p; }
+bool packing_params_ok(const char *fn, const Packing &pk)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (pk.packing < 0 || pk.packing > 3) {
+        snprintf(msg, sizeof msg, "%s: packing = %d, must be 0 (side by side), 1 (half-width side by side), 2 (top and bottom) or 3 (half-height top and bottom)", fn, pk.packing);
+        arg = "packing";
+    } else if (pk.swap != 0 && pk.swap != 1) {
+        snprintf(msg, sizeof msg, "%s: swap = %d, must be 0 (left eye first) or 1 (right eye first)", fn, pk.swap);
+        arg = "swap";
+    } else if (pk.filter != 0 && pk.filter != 1) {
+        snprintf(msg, sizeof msg, "%s: filter = %d, must be 0 (linear) or 1 (Catmull-Rom)", fn, pk.filter);
+        arg = "filter";
+    } else if (pk.gap < 0 || pk.gap > (1 << 24)) {
+        snprintf(msg, sizeof msg, "%s: gap = %d, must be >= 0 (and at most 2^24)", fn, pk.gap);
+        arg = "gap";
+    } else if (pk.filter != 0 && (pk.packing & 1) == 0) {
+        snprintf(msg, sizeof msg, "%s: filter = %d with packing = %d: a full packing copies, the filter must be 0", fn, pk.filter, pk.packing);
+        arg = "filter";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+
 // the calling thread's depth budget (stm_set_depth, stm_set_depth_auto)
 static thread_local Depth g_depth = {0, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 20, nullptr}; // disp_lo == disp_hi: no budget set yet
 Depth depth() { return g_depth; }
@@ -415,6 +444,19 @@ int stm_set_lens(int mode, double pitch, double slope, double centre)
     if (!stm::lens_params_ok("set_lens", mode, 0, 3, pitch, slope, centre)) return -1; // the thread's geometry stays as it was
     stm::set_lens(mode == 0 ? stm::Lens{0, 0.0, 0.0, 0.0} : stm::Lens{mode, pitch, slope, centre});
     return 0;
+}
+int stm_set_packing(int packing, int swap, int filter, int gap)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    const stm::Packing pk = {packing, swap, filter, gap};
+    if (!stm::packing_params_ok("set_packing", pk)) return -1; // the thread's packing stays as it was
+    stm::set_packing(pk);
+    return 0;
+}
+void stm_get_packing(int *out)
+{
+    const stm::Packing pk = stm::packing();
+    out[0] = pk.packing; out[1] = pk.swap; out[2] = pk.filter; out[3] = pk.gap;
 }
 int stm_set_depth(int mode, float gain, float conv)
 {

@@ -12,6 +12,7 @@
 #include "stm_common.h"
 #include "../../include/stm_hip.h"
 
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -49,6 +50,8 @@ struct FrameStream {
     size_t in_bytes = 0;              // what a submit copies and uploads: in_sz, or H * Wsbs * 3 / 2 for NV12
     stm::Lens lens = {0, 0.0, 0.0, 0.0}; // stm_stream_set_lens: the stream's own display geometry, installed around its frame calls
     stm::Depth depth = {0, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 20, nullptr}; // stm_stream_set_depth / _auto: the stream's own depth budget
+    stm::Packing packing = {0, 0, 0, 0}; // stm_stream_set_packing: the stream's own input packing, installed around its frame calls
+    int rows_f = 0;                      // the rows of an input frame: H, or what the packing makes of it
     float *d_depth_state = nullptr; // mode 2: the state every frame updates, at one address for both slots' graphs
     Slot slot[2];
     long submitted = 0, collected = 0;
@@ -67,6 +70,25 @@ struct DepthScope {
     ~DepthScope() { stm::set_depth(saved); }
 };
 
+struct PackingScope {
+    stm::Packing saved;
+    explicit PackingScope(const stm::Packing &p) : saved(stm::packing()) { stm::set_packing(p); }
+    ~PackingScope() { stm::set_packing(saved); }
+};
+
+// the rules an input format and a packing set together on the stream's geometry (either may come first); false with the error recorded
+bool stream_input_ok(const char *fn, const FrameStream *f, int format, int matrix, const stm::Packing &pk)
+{
+    if (format == 1 && (f->Wsbs & 1)) { // the UV plane follows the Y plane with the same pitch
+        char msg[120];
+        snprintf(msg, sizeof msg, "%s: NV12 needs an even num_cols_sbs", fn);
+        stm::fail(msg, "num_cols_sbs", __FILE__, __LINE__);
+        return false;
+    }
+    if (pk.on()) return stm::packing_args_ok(fn, pk, f->H, f->Wsbs, f->W, "num_cols", format == 1, f->Wsbs, f->Wsbs, matrix);
+    return format != 1 || stm::nv12_args_ok(fn, f->H, f->Wsbs, f->W, "num_cols", f->Wsbs, f->Wsbs, matrix);
+}
+
 } // namespace
 
 extern "C" {
@@ -81,6 +103,7 @@ void *stm_stream_create(int num_rows, int num_cols_sbs, int num_cols, int num_ro
     f->ucd = ucd; f->lcd = lcd; f->usd = usd; f->lsd = lsd; f->thresh_s = thresh_s; f->thresh_h = thresh_h;
     f->in_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
     f->in_bytes = f->in_sz;
+    f->rows_f = num_rows;
     f->out_sz = (size_t)num_rows_out * num_cols_out * elem_sz;
     f->hw = (size_t)num_rows * num_cols;
     STM_CHECK(hipGetDevice(&f->dev));
@@ -182,11 +205,7 @@ int stm_stream_set_input(void *h, int format, int matrix)
         return -1;
     }
     if (format == 1) {
-        if (f->Wsbs & 1) { // the UV plane follows the Y plane with the same pitch
-            stm::fail("stream_set_input: NV12 needs an even num_cols_sbs", "num_cols_sbs", __FILE__, __LINE__);
-            return -1;
-        }
-        if (!stm::nv12_args_ok("stream_set_input", f->H, f->Wsbs, f->W, "num_cols", f->Wsbs, f->Wsbs, matrix)) return -1;
+        if (!stream_input_ok("stream_set_input", f, format, matrix, f->packing)) return -1;
         for (Slot &s : f->slot)
             if (!s.d_img_l) {
                 STM_CHECK(hipMalloc((void **)&s.d_img_l, f->hw * f->E));
@@ -196,7 +215,59 @@ int stm_stream_set_input(void *h, int format, int matrix)
     }
     f->in_format = format;
     f->in_matrix = format == 1 ? matrix : 0;
-    f->in_bytes = format == 1 ? (size_t)f->H * f->Wsbs * 3 / 2 : f->in_sz;
+    f->in_bytes = format == 1 ? (size_t)f->rows_f * f->Wsbs * 3 / 2 : f->in_sz;
+    return 0;
+}
+
+// The packing of the stream's input frames (stm_hip.h; stm_set_packing's settings and the geometry rules of stm_demux_packed, or of
+// stm_demux_nv12_packed in NV12 mode, on the stream's num_rows, num_cols_sbs and num_cols).  A packed frame has rows_f rows, so each
+// slot's pinned and device input buffers are allocated anew for rows_f * num_cols_sbs * elem_sz bytes: pointers handed out by
+// stm_stream_input_buffer before this call are void.  Kept and installed like the lens geometry.  Only before the first submit.
+// Returns 0, or -1 with the error recorded.
+int stm_stream_set_packing(void *h, int packing, int swap, int filter, int gap)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    const stm::Packing pk = {packing, swap, filter, gap};
+    if (!stm::packing_params_ok("stream_set_packing", pk)) return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_packing: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    if (!stream_input_ok("stream_set_packing", f, f->in_format, f->in_matrix, pk)) return -1;
+    const int rows_f = pk.rows_f(f->H);
+    const size_t in_sz = (size_t)rows_f * f->Wsbs * f->E;
+    if (in_sz != f->in_sz) {
+        int caller_dev = f->dev;
+        STM_CHECK(hipGetDevice(&caller_dev));
+        if (caller_dev != f->dev) STM_CHECK(hipSetDevice(f->dev));
+        // the new buffers first, the old ones freed only once all four exist: a failed allocation leaves the stream as it was
+        u8 *h_new[2] = {nullptr, nullptr}, *d_new[2] = {nullptr, nullptr};
+        for (int i = 0; i < 2; ++i) {
+            STM_CHECK(hipHostMalloc((void **)&h_new[i], in_sz, hipHostMallocDefault));
+            STM_CHECK(hipMalloc((void **)&d_new[i], in_sz));
+        }
+        if (stm::failed()) { // (error mode 1; the hip calls take null pointers)
+            for (int i = 0; i < 2; ++i) {
+                if (h_new[i]) (void)hipHostFree(h_new[i]);
+                if (d_new[i]) (void)hipFree(d_new[i]);
+            }
+            if (caller_dev != f->dev) (void)hipSetDevice(caller_dev);
+            return -1;
+        }
+        for (int i = 0; i < 2; ++i) {
+            Slot &s = f->slot[i];
+            STM_CHECK(hipHostFree(s.h_in));
+            STM_CHECK(hipFree(s.d_in));
+            s.h_in = h_new[i];
+            s.d_in = d_new[i];
+        }
+        if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
+    }
+    f->packing = pk;
+    f->rows_f = rows_f;
+    f->in_sz = in_sz;
+    f->in_bytes = f->in_format == 1 ? (size_t)rows_f * f->Wsbs * 3 / 2 : in_sz;
     return 0;
 }
 
@@ -305,12 +376,13 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     void *prev = stm_get_stream();
     LensScope lens_scope(f->lens);
     DepthScope depth_scope(f->depth);
+    PackingScope packing_scope(f->packing);
     stm_set_stream(s.s_compute);
     stm::ws_private_bind(s.ws);
     auto pipeline = [&]() {
         stm::ApiNest nest; // a failed upload above must survive the nested call's argument screen
         if (f->in_format == 1) { // NV12: the slot's images receive the conversion; with 0x2000 the other slot's images and maps are the history
-            stm_d_adcensus_stm_nv12(s.d_in, f->Wsbs, s.d_in + (size_t)f->H * f->Wsbs, f->Wsbs, f->in_matrix, s.d_dl, s.d_dr, s.d_out, f->H,
+            stm_d_adcensus_stm_nv12(s.d_in, f->Wsbs, s.d_in + (size_t)f->rows_f * f->Wsbs, f->Wsbs, f->in_matrix, s.d_dl, s.d_dr, s.d_out, f->H,
                                     f->Wsbs, f->W, f->Hout, f->Wout, f->E, f->N, f->angle, f->D, f->zd, f->ad, f->ce, f->ucd, f->lcd,
                                     f->usd, f->lsd, f->thresh_s, f->thresh_h, f->stages, history ? other.d_img_l : nullptr,
                                     history ? other.d_img_r : nullptr, history ? other.d_dl : nullptr, history ? other.d_dr : nullptr,

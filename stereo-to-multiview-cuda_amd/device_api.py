@@ -52,6 +52,70 @@ def set_lens(mode, pitch=0.0, slope=0.0, centre=0.0):
         raise ValueError("stm_set_lens(%d, %g, %g, %g) refused: %s" % (mode, pitch, slope, centre, lib().stm_last_error().decode()))
 
 
+PACKING_OFF = (0, 0, 0, 0)
+
+def set_packing(packing=0, swap=0, filter=0, gap=0):
+    """stm_set_packing: where the two eyes lie in the frames this thread's d_adcensus_stm, d_adcensus_stm_t and d_adcensus_stm_nv12
+    are given.  packing 0 / 1 = side by side full / half width, 2 / 3 = top and bottom full / half height; swap 1 = the right eye
+    first; filter 0 = linear, 1 = Catmull-Rom (the expansion of packings 1 and 3); gap = pixels between the eyes along the packing
+    axis.  (0, 0, 0, 0) = off, the default.  Under a packing the unpacked eye's size is taken from disp_l.  Raises ValueError where
+    the library refuses."""
+    if int(lib().stm_set_packing(int(packing), int(swap), int(filter), int(gap))) != 0:
+        raise ValueError("stm_set_packing(%d, %d, %d, %d) refused: %s" % (packing, swap, filter, gap, lib().stm_last_error().decode()))
+
+
+def get_packing():
+    """stm_get_packing: the calling thread's (packing, swap, filter, gap) as the library holds it, whoever set it"""
+    out = (C.c_int * 4)()
+    lib().stm_get_packing(out)
+    return tuple(int(v) for v in out)
+
+
+def packed_frame_rows(num_rows, packing):
+    """rows_f of stm_hip.h: the rows of a packed frame whose unpacked eyes have num_rows rows; packing = (packing, swap, filter, gap)"""
+    pk, gap = int(packing[0]), int(packing[3])
+    return 2 * num_rows + gap if pk == 2 else 2 * (num_rows // 2) + gap if pk == 3 else num_rows
+
+
+def _eye_shape(frame_rows, Wsbs, disp_l):
+    """(H, W) of a frame call: half the frame's columns with packing off, disp_l's shape (the unpacked eye) under a packing"""
+    pk = get_packing()
+    if pk == PACKING_OFF:
+        return frame_rows, Wsbs // 2
+    H, W = disp_l.shape
+    if frame_rows < packed_frame_rows(H, pk):
+        raise ValueError("a frame of %d rows cannot hold two eyes of %d rows under packing %r" % (frame_rows, H, pk))
+    return H, W
+
+
+def d_demux_packed(img_l, img_r, img, packing):
+    """stm_d_demux_packed: the two unpacked eyes of the packed BGR frame img (uint8 [rows_f][Wsbs][E] on the GPU) into img_l / img_r
+    (uint8 [H][W][E], only the first three bytes of a pixel are written); packing = (packing, swap, filter, gap)."""
+    H, W, E = img_l.shape
+    assert img.is_cuda and img.dtype == torch.uint8 and img.is_contiguous() and img.dim() == 3 and img.shape[2] == E
+    for t in (img_l, img_r):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    pk, sw, fl, gap = (int(v) for v in packing)
+    assert img.shape[0] >= packed_frame_rows(H, packing)
+    _use_current_stream()
+    lib().stm_d_demux_packed(_p(img_l), _p(img_r), _p(img), H, img.shape[1], W, E, pk, sw, fl, gap)
+
+
+def d_demux_nv12_packed(img_l, img_r, y, uv, packing, matrix=0, num_cols_sbs=None):
+    """stm_d_demux_nv12_packed: d_demux_packed on a packed NV12 frame (planes as for d_demux_nv12, rows_f and rows_f / 2 rows)."""
+    for t in (y, uv):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1)
+    H, W, E = img_l.shape
+    for t in (img_l, img_r):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    Wsbs = y.shape[1] if num_cols_sbs is None else num_cols_sbs
+    assert y.shape[0] >= packed_frame_rows(H, packing) and uv.shape[0] * 2 == y.shape[0]
+    assert y.shape[1] >= Wsbs and uv.shape[1] >= 2 * ((Wsbs + 1) // 2)
+    pk, sw, fl, gap = (int(v) for v in packing)
+    _use_current_stream()
+    lib().stm_d_demux_nv12_packed(_p(img_l), _p(img_r), _p(y), y.stride(0), _p(uv), uv.stride(0), H, Wsbs, W, E, int(matrix), pk, sw, fl, gap)
+
+
 DEPTH_AUTO_DEFAULTS = (1.0, 20, 1.0)  # max_gain, clip_permille, rate of stm_set_depth_auto
 
 
@@ -112,7 +176,7 @@ def d_adcensus_stm(sbs, disp_l, disp_r, interlaced, p, stages=3):
     OR-ing STAGE_LINEAR_WARP (stage 3) the linear sampling of the views' warps."""
     assert sbs.is_cuda and sbs.dtype == torch.uint8 and sbs.is_contiguous()
     H, Wsbs, E = sbs.shape
-    W = Wsbs // 2
+    H, W = _eye_shape(H, Wsbs, disp_l)
     assert disp_l.shape == (H, W) and disp_r.shape == (H, W) and disp_l.dtype == torch.float32
     Ho, Wo = interlaced.shape[0], interlaced.shape[1]
     _use_current_stream()
@@ -128,7 +192,7 @@ def d_adcensus_stm_t(sbs, disp_l, disp_r, interlaced, p, stages=3, prev_sbs=None
     rendered; with all three None (the first frame) the call is d_adcensus_stm without the bit."""
     assert sbs.is_cuda and sbs.dtype == torch.uint8 and sbs.is_contiguous()
     H, Wsbs, E = sbs.shape
-    W = Wsbs // 2
+    H, W = _eye_shape(H, Wsbs, disp_l)
     assert disp_l.shape == (H, W) and disp_r.shape == (H, W) and disp_l.dtype == torch.float32
     if prev_sbs is not None:
         assert prev_sbs.is_cuda and prev_sbs.dtype == torch.uint8 and prev_sbs.is_contiguous() and prev_sbs.shape == sbs.shape
@@ -175,6 +239,8 @@ def d_adcensus_stm_nv12(y, uv, disp_l, disp_r, interlaced, p, stages=3, matrix=0
     split images: they are the next frame's prev_img_l / prev_img_r.  elem_sz is taken from img_l where that is given."""
     H, Wsbs, pitch_y, pitch_uv = _nv12_planes(y, uv, num_cols_sbs)
     W = disp_l.shape[1]
+    if get_packing() != PACKING_OFF:  # the planes hold the packed frame: the unpacked eye's size is disp_l's
+        H = _eye_shape(H, Wsbs, disp_l)[0]
     assert disp_l.shape == (H, W) and disp_r.shape == (H, W) and disp_l.dtype == torch.float32
     E = elem_sz if img_l is None else img_l.shape[2]
     for t in (img_l, img_r, prev_img_l, prev_img_r):

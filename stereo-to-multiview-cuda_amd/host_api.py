@@ -383,3 +383,32 @@ def demux_nv12(y, uv, num_cols, elem_sz=3, matrix=0, num_cols_sbs=None):
     lib().stm_demux_nv12(img_l.ctypes.data_as(u8p), img_r.ctypes.data_as(u8p), y.ctypes.data_as(u8p), y.strides[0],
                          uv.ctypes.data_as(u8p), uv.strides[0], H, Wsbs, num_cols, elem_sz, int(matrix))
     return img_l, img_r
+
+
+def demux_packed(img, num_rows, num_cols, packing, elem_sz=None):
+    """stm_demux_packed: the two unpacked eyes (each uint8 [num_rows][num_cols][E], BGR in the first three bytes, 0 past them) of a
+    packed BGR frame img uint8 [rows_f][Wsbs][E] (contiguous); packing = (packing, swap, filter, gap), stm_set_packing's settings."""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    assert img.ndim == 3
+    E = img.shape[2] if elem_sz is None else elem_sz
+    img_l = np.zeros((num_rows, num_cols, E), np.uint8)
+    img_r = np.zeros_like(img_l)
+    pk, sw, fl, gap = (int(v) for v in packing)
+    lib().stm_demux_packed(img_l.ctypes.data_as(u8p), img_r.ctypes.data_as(u8p), img.ctypes.data_as(u8p), num_rows, img.shape[1], num_cols,
+                           E, pk, sw, fl, gap)
+    return img_l, img_r
+
+
+def demux_nv12_packed(y, uv, num_rows, num_cols, packing, elem_sz=3, matrix=0, num_cols_sbs=None):
+    """stm_demux_nv12_packed: demux_packed on a packed NV12 frame: y uint8 [rows_f][>= Wsbs], uv uint8 [rows_f / 2][>= Wsbs], planes
+    as for demux_nv12 (the row stride is the pitch)."""
+    for a in (y, uv):
+        assert a.dtype == np.uint8 and a.ndim == 2 and (a.shape[1] == 1 or a.strides[1] == 1)
+    Wsbs = y.shape[1] if num_cols_sbs is None else num_cols_sbs
+    assert uv.shape[0] * 2 == y.shape[0] and y.shape[1] >= Wsbs and uv.shape[1] >= 2 * ((Wsbs + 1) // 2)
+    img_l = np.zeros((num_rows, num_cols, elem_sz), np.uint8)
+    img_r = np.zeros_like(img_l)
+    pk, sw, fl, gap = (int(v) for v in packing)
+    lib().stm_demux_nv12_packed(img_l.ctypes.data_as(u8p), img_r.ctypes.data_as(u8p), y.ctypes.data_as(u8p), y.strides[0],
+                                uv.ctypes.data_as(u8p), uv.strides[0], num_rows, Wsbs, num_cols, elem_sz, int(matrix), pk, sw, fl, gap)
+    return img_l, img_r

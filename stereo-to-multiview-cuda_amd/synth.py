@@ -108,6 +108,32 @@ def tiled_sbs_frame(left, right, H, W):
     return np.ascontiguousarray(np.concatenate([L, R], axis=1))
 
 
+def pack_frame(left, right, packing=0, swap=0, gap=0, extra_cols=0, fill=0):
+    """A packed BGR frame uint8 [rows_f][Wsbs][3] (include/stm_hip.h, stm_demux_packed) from a full-resolution pair uint8 [H][W][3]:
+    packing 0 / 2 = the eyes side by side / one above the other, 1 / 3 = each eye first squeezed to half the columns / rows by
+    averaging pairs ((a + b + 1) >> 1); swap: the right eye first; `gap` pixels of `fill` between the eyes along the packing axis and
+    extra_cols columns of it past the row the rule asks for.  It only manufactures inputs, as a 3D encoder would: the expansion is
+    the library's."""
+    def squeeze(img, axis):
+        a = np.moveaxis(img.astype(np.int32), axis, 0)
+        return np.moveaxis(((a[0::2] + a[1::2] + 1) >> 1).astype(np.uint8), 0, axis)
+    eyes = [left, right]
+    if packing & 1:
+        assert left.shape[1 if packing == 1 else 0] % 2 == 0
+        eyes = [squeeze(e, 1 if packing == 1 else 0) for e in eyes]
+    if swap:
+        eyes = eyes[::-1]
+    Hp, Wp, _ = eyes[0].shape
+    rows, cols = (Hp, 2 * Wp + gap) if packing < 2 else (2 * Hp + gap, Wp)
+    frame = np.full((rows, cols + extra_cols, 3), fill, np.uint8)
+    frame[:Hp, :Wp] = eyes[0]
+    if packing < 2:
+        frame[:, Wp + gap:2 * Wp + gap] = eyes[1]
+    else:
+        frame[Hp + gap:, :Wp] = eyes[1]
+    return frame
+
+
 # (Kr, Kb), limited range?  -- the four conversion matrices of stm_demux_nv12, in its numbering
 NV12_MATRICES = ((0.299, 0.114, True), (0.2126, 0.0722, True), (0.299, 0.114, False), (0.2126, 0.0722, False))
 

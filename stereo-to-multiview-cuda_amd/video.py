@@ -19,19 +19,27 @@ class FrameStream:
     conversion (stm_demux_nv12: 0 / 1 = BT.601 / BT.709 limited range, 2 / 3 = full range).  lens = (mode, pitch, slope, centre): the
     panel's calibration (set_lens); None = the reference's interlacer.  depth = (gain, conv): the manual depth budget (set_depth mode 1);
     depth_auto = (disp_lo, disp_hi[, max_gain, clip_permille, rate]): the automatic one (mode 2), fitted to every frame on the GPU;
-    at most one of the two."""
+    at most one of the two.  packing = (packing, swap, filter, gap): the frames come packed (stm_set_packing's settings: half-width
+    side by side, top and bottom, ...); num_rows x num_cols stay the size of an unpacked eye, and a frame is then [rows_f][Wsbs][3]
+    (NV12: [rows_f * 3 / 2][Wsbs]) with Wsbs = 2 * (packed eye's columns) + gap for the side-by-side packings and num_cols for the
+    top-and-bottom ones: the shape `in_shape` holds."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
-                 depth=None, depth_auto=None):
+                 depth=None, depth_auto=None, packing=None):
         self.H, self.W = num_rows, num_cols
-        self.in_shape = (num_rows, 2 * num_cols, 3)
+        self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
+        self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
+        self._nv12 = False
+        self.in_shape = (self.rows_f, self.Wsbs, 3)
         self.Ho, self.Wo = out_rows or num_rows, out_cols or num_cols
         p = params
-        self._h = lib().stm_stream_create(num_rows, 2 * num_cols, num_cols, self.Ho, self.Wo, 3, p.num_views, p.angle,
+        self._h = lib().stm_stream_create(num_rows, self.Wsbs, num_cols, self.Ho, self.Wo, 3, p.num_views, p.angle,
                                           p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff, p.ucd, p.lcd, p.usd, p.lsd,
                                           p.thresh_s, p.thresh_h)
         if stages != 3:
             self.set_stages(stages)
+        if packing is not None:
+            self.set_packing(*self.packing)
         if input_format != "bgr":
             self.set_input(input_format, matrix)
         if lens is not None:
@@ -80,7 +88,20 @@ class FrameStream:
         fmt = {"bgr": 0, "nv12": 1}.get(input_format, -1)
         if int(lib().stm_stream_set_input(self._h, fmt, int(matrix))) != 0:
             raise ValueError("stm_stream_set_input(%r, %d) refused: %s" % (input_format, matrix, lib().stm_last_error().decode()))
-        self.in_shape = (self.H * 3 // 2, 2 * self.W) if fmt == 1 else (self.H, 2 * self.W, 3)
+        self._nv12 = fmt == 1
+        self.in_shape = (self.rows_f * 3 // 2, self.Wsbs) if fmt == 1 else (self.rows_f, self.Wsbs, 3)
+
+    def set_packing(self, packing=0, swap=0, filter=0, gap=0):
+        """stm_stream_set_packing: the packing of the stream's input frames; the stream's own, independent of the calling thread's;
+        only before the first submit.  The frame's row length was fixed when the stream was created (the `packing` argument of the
+        constructor sizes it), so this is for changing swap or filter, or for a stream created with that row length.  Buffers handed
+        out by input_buffer() before this call are void.  Raises ValueError where the library refuses."""
+        if int(lib().stm_stream_set_packing(self._h, int(packing), int(swap), int(filter), int(gap))) != 0:
+            raise ValueError("stm_stream_set_packing(%d, %d, %d, %d) refused: %s"
+                             % (packing, swap, filter, gap, lib().stm_last_error().decode()))
+        self.packing = (int(packing), int(swap), int(filter), int(gap))
+        self.rows_f = packed_frame_geometry(self.H, self.W, self.packing)[1]
+        self.in_shape = (self.rows_f * 3 // 2, self.Wsbs) if self._nv12 else (self.rows_f, self.Wsbs, 3)
 
     def set_stages(self, stages):
         """stm_stream_set_stages: 3, optionally OR-ed with 0x200 (sub-pixel), 0x400 (outlier interpolation), 0x800 (linear
@@ -141,6 +162,27 @@ class FrameStream:
             pass
 
 
+def packed_frame_geometry(num_rows, num_cols, packing):
+    """(Wsbs, rows_f) of the smallest frame that holds two eyes of num_rows x num_cols after unpacking (include/stm_hip.h,
+    stm_demux_packed); packing = (packing, swap, filter, gap)"""
+    pk, gap = int(packing[0]), int(packing[3])
+    if pk == 0:
+        return 2 * num_cols + gap, num_rows
+    if pk == 1:
+        return 2 * (num_cols // 2) + gap, num_rows
+    if pk == 2:
+        return num_cols, 2 * num_rows + gap
+    return num_cols, 2 * (num_rows // 2) + gap
+
+
+def unpacked_eye_shape(frame_rows, frame_cols, packing):
+    """(num_rows, num_cols) of an unpacked eye of a packed frame that is exactly as large as packed_frame_geometry says"""
+    pk, gap = int(packing[0]), int(packing[3])
+    if pk < 2:
+        return frame_rows, ((frame_cols - gap) // 2) * (2 if pk == 1 else 1)
+    return ((frame_rows - gap) // 2) * (2 if pk == 3 else 1), frame_cols
+
+
 def _collect(fs, on_depth):
     r = fs.collect()
     if on_depth is not None and r is not None:
@@ -149,19 +191,23 @@ def _collect(fs, on_depth):
 
 
 def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None,
-                     depth=None, depth_auto=None, on_depth=None):
+                     depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
     stabilisation); temporal: (alpha, thresh_color, thresh_disp) for FrameStream.set_temporal, None = the defaults; lens: (mode,
     pitch, slope, centre) for FrameStream.set_lens, None = the reference's interlacer; depth / depth_auto: FrameStream's depth
-    budget; on_depth: called with (index, (gain, conv)) after every collected frame."""
+    budget; on_depth: called with (index, (gain, conv)) after every collected frame.  packing: FrameStream's; the frames are then packed
+    ones; eye_shape = (num_rows, num_cols), the size of an unpacked eye, defaults to what a frame without spare columns holds."""
     fs = None
     pending = 0
     for sbs in frames:
         if fs is None:
             rows = sbs.shape[0] * 2 // 3 if input_format == "nv12" else sbs.shape[0]
-            fs = FrameStream(rows, sbs.shape[1] // 2, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto)
+            cols = sbs.shape[1] // 2
+            if packing is not None:
+                rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
+            fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:

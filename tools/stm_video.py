@@ -7,6 +7,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--temporal [--temporal-alpha A] [--temporal-color C] [--temporal-disp T]]
                     [--nv12 ROWS COLS_SBS [--matrix M]] [--lens MODE PITCH SLOPE CENTRE]
                     [--depth GAIN CONV | --depth-auto LO HI [MAX_GAIN CLIP RATE]]
+                    [--packing P SWAP FILTER GAP]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -24,6 +25,10 @@ GAIN * d - CONV (GAIN in [0, 8]; CONV in input-view pixels, |CONV| <= 4096).  --
 one (mode 2) -- every frame's disparity range, less CLIP/1000 of its pixels at either end (20), is brought into the panel's budget
 [LO, HI] with a gain of at most MAX_GAIN (1), following the fit at RATE (1); each frame's applied pair is printed.  The two
 options are mutually exclusive.
+--packing P SWAP FILTER GAP (an addition): the frames are packed stereo frames (stm_set_packing) -- P 0 / 1 = side by side full /
+half width, 2 / 3 = top and bottom full / half height; SWAP 1 = the right eye first; FILTER 0 = linear, 1 = Catmull-Rom (how a
+squeezed eye is expanded); GAP pixels between the eyes (45 blank rows in 1080p HDMI frame packing).  Unpacked inside the frame's first
+kernel; combines with --nv12, whose ROWS and COLS_SBS are then the packed frame's.  The frames carry no spare columns.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -70,6 +75,17 @@ def main(argv):
             print(__doc__)
             return -1
         lens = (int(argv[at + 1]), float(argv[at + 2]), float(argv[at + 3]), float(argv[at + 4]))
+        del argv[at:at + 5]
+    packing = None
+    if "--packing" in argv:
+        at = argv.index("--packing")
+        try:
+            packing = tuple(int(x) for x in argv[at + 1:at + 5])
+        except ValueError:
+            packing = ()
+        if len(packing) != 4:
+            print(__doc__)
+            return -1
         del argv[at:at + 5]
     depth, depth_auto = None, None
     try:
@@ -119,7 +135,7 @@ def main(argv):
     for (k, dl, dr, inter) in video.process_sequence(frames, p, out_h, out_w, stages, tuple(temporal) if stages & 0x2000 else None,
                                                        "bgr" if nv12 is None else "nv12", matrix, lens, depth, depth_auto,
                                                        (lambda k, gc: print("frame %d: gain %.6g conv %.6g" % (k, gc[0], gc[1])))
-                                                       if depth_auto is not None else None):
+                                                       if depth_auto is not None else None, packing):
         video.write_outputs(out_dir, k, dl, dr, inter)
         n += 1
     dt = time.perf_counter() - t0
