@@ -143,6 +143,35 @@ int         stm_set_depth(int mode, float gain, float conv);
  * means scratch memory, with every frame fitted on its own.  A caller resets the history, for a scene cut, by zeroing `valid`.
  * Returns 0, or -1 with stm_last_error set and the old parameters in place. */
 int         stm_set_depth_auto(float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate, float *d_state);
+/* The calling thread's output geometry (an addition: the reference shows its views in one form only, sub-pixel interlaced).
+ * layout 0 = the interlaced frame (the default; tiles_x, tiles_y, order and filter are ignored, and not one launch, argument or
+ * kernel changes), 1 = a quilt: the views side by side as a grid of tiles, whole, for a display that interlaces with its own
+ * calibration, for an encoder of multiview video, or to get a depth-retargeted stereo pair back (num_views 2, tiles 2 x 1, order 2,
+ * stm_set_depth).  With layout 1 every frame call that renders -- stm_adcensus_stm, stm_d_adcensus_stm, _t, _nv12, and _2 / _2s in
+ * both flavours -- writes the quilt defined at stm_quilt_multiview into its output frame; `angle` is then ignored and not screened.
+ * The views V(v, x, y, c) are the renderer's, none is written to memory:
+ *   depth mode 0      view 0 = the right image, view N-1 = the left image, view v the reference's d_dibr_dbm at
+ *                     shift = (float)(1 - v/(N-1)) (d_io.cu:189)
+ *   depth mode 1, 2   stm_set_depth's sample rule at s = (float)(1 - v/(N-1)), xs = (float)x, ys = (float)y (so wy = 0 and only row
+ *                     y is read), the conv offset included; mode 2 reads gain and conv on the device as in the interlaced frame
+ * with the linear tap under 0x800 in both.  Under filter 0 the sample at a fractional (xs, ys) is the renderer's own: the
+ * four-neighbour combination of view v's samples in depth mode 0, stm_set_depth's sample rule at (xs, ys) in modes 1 and 2.
+ * Depth mode 0 follows stm_set_agg_variant(200) into the un-fused form (every view written, then stm_d_quilt_multiview); with a depth
+ * budget there are no views to write and the fused kernels are taken always.
+ * Errors of a frame call under layout 1, through stm_last_error before anything is launched or written: tiles_x * tiles_y !=
+ * num_views; a tile of width num_cols_out / tiles_x == 0 or height num_rows_out / tiles_y == 0; a lens mode != 0 on the thread (a quilt
+ * is not interlaced).  A frame call whose `stages` low byte is below 3 renders nothing and ignores the layout, as it ignores the lens.
+ * This is an output geometry, not a stage: no `stages` bit belongs to it.
+ * Argument rules: layout 0 or 1; with layout 1 tiles_x, tiles_y in 1 .. 65535, order in 0 .. 3, filter 0 or 1.  Returns 0, or -1 with
+ * stm_last_error set and the thread's layout unchanged. */
+int         stm_set_layout(int layout, int tiles_x, int tiles_y, int order, int filter);
+/* out[0 .. 4] = the calling thread's layout, tiles_x, tiles_y, order and filter as the last accepted stm_set_layout left them
+ * ((0, 1, 1, 0, 0) if none was made, and after layout 0).  A frame stream's own layout is not visible here except during its submit. */
+void        stm_get_layout(int *out);
+/* (tests, tools) the bytes of LDS a workgroup of the area filter's staged kernel may take: the block of output pixels it owns is sized
+ * so that its footprint's staging fits, and where not even one output pixel's does the per-pixel form runs -- same arithmetic, same
+ * bytes.  <= 0: the default, 32768 (five workgroups on a CU); at most 65536.  Process-wide, like stm_set_agg_variant. */
+void        stm_set_quilt_lds_limit(int bytes);
 /* The calling thread's input packing (an addition; see stm_demux_packed for the definition and the rules): where the two eyes lie in
  * the frame that stm_d_adcensus_stm, stm_d_adcensus_stm_t and stm_d_adcensus_stm_nv12 are given.  The default is (0, 0, 0, 0), the
  * reference's layout, with which not one launch, argument or kernel changes.  Under any other setting num_rows and num_cols stay the
@@ -369,6 +398,41 @@ void stm_mux_multiview_lens(unsigned char **views, unsigned char *out_data, int 
                             double centre, int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz);
 void stm_d_mux_multiview_lens(unsigned char **d_views, unsigned char *d_out_data, int num_views, int mode, double pitch, double slope,
                               double centre, int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz);
+
+/* The views tiled into one frame, a quilt (an addition; the counterpart of stm_mux_multiview_lens for a display that does its own
+ * interlacing).  views = table of num_views images in_rows x in_cols x elem_sz, views[0] = the right image ... views[num_views-1]
+ * = the left image, as the interlacer takes them; V(v, x, y, c) is byte c of pixel (x, y) of views[v].
+ *   tiles_x, tiles_y >= 1 with tiles_x * tiles_y == num_views
+ *   order    bit 0: tile rows run bottom-up (the Looking Glass convention); bit 1: the view order is reversed, so tile 0 holds the
+ *            leftmost camera (view num_views-1)
+ *   filter   0 = the reference's four-neighbour sampler (fast_bilinear_interp), 1 = the area average
+ * Geometry, with N = num_views, the output Hout x Wout and the views Hin x Win, integer division:
+ *   tw = Wout / tiles_x;  th = Hout / tiles_y                      the size of a tile (both must be >= 1)
+ *   k  = (order & 2) ? N - 1 - v : v                               the tile view v goes to
+ *   i  = k % tiles_x;  j = k / tiles_x
+ *   left = i * tw                                                  the tile's left column
+ *   top  = (order & 1) ? Hout - (j + 1) * th : j * th              the tile's top row
+ * The Wout - tiles_x * tw remainder columns at the right and the Hout - tiles_y * th remainder rows -- at the bottom when top-down, at
+ * the top when bottom-up -- belong to no tile: bytes 0 .. 2 of such a pixel are written 0.  All three bytes of a tile pixel come
+ * from the same view.  For tile pixel (u, w), 0 <= u < tw, 0 <= w < th, at output pixel (left + u, top + w):
+ * Filter 0 (f32, one operation per line, C fminf / fmaxf -- mux_multiview_kernel_2's lines with the tile's size for the frame's):
+ *   xs = ((float)u / (float)tw) * (float)Win;  xs = fminf(fmaxf(xs, 0), (float)(Win - 1))
+ *   ys = ((float)w / (float)th) * (float)Hin;  ys = fminf(fmaxf(ys, 0), (float)(Hin - 1))
+ *   out[c] = fast_bilinear_interp of V(v, ., ., c) at (xs, ys)     (d_mux_multiview.cu:10-36)
+ * Filter 1 (unsigned integers wide enough for 255 * Win * Hin, `/` the integer division; any summation order gives the same bits).
+ * In units of 1/tw of a view pixel tile column u covers [u Win, (u+1) Win) and view column x covers [x tw, (x+1) tw):
+ *   wx(x) = max(0, min((u+1) Win, (x+1) tw) - max(u Win, x tw))    non-zero for x = u Win / tw .. ((u+1) Win - 1) / tw; sum = Win
+ *   wy(y) = max(0, min((w+1) Hin, (y+1) th) - max(w Hin, y th))    non-zero for y = w Hin / th .. ((w+1) Hin - 1) / th; sum = Hin
+ *   out[c] = (sum_y sum_x wy(y) wx(x) V(v, x, y, c) + (Win Hin) / 2) / (Win Hin)
+ * the exact mean of the view over the tile pixel's footprint, rounded half up.  With tw >= Win the footprint is at most two view
+ * columns (a tile pixel inside one view pixel copies it); the same lines define that case.
+ * Pixel format: as stm_mux_multiview -- the host flavour returns bytes 3 .. elem_sz-1 as 0, the device flavour leaves them alone.
+ * Errors, through stm_last_error with nothing launched: a dimension < 1, elem_sz < 3, num_views < 2, order or filter out of range,
+ * tiles_x * tiles_y != num_views, a tile of width or height 0, tw * in_cols or th * in_rows >= 2^31. */
+void stm_quilt_multiview(unsigned char **views, unsigned char *out_data, int num_views, int tiles_x, int tiles_y, int order, int filter,
+                         int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz);
+void stm_d_quilt_multiview(unsigned char **d_views, unsigned char *d_out_data, int num_views, int tiles_x, int tiles_y, int order, int filter,
+                           int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz);
 /* d_demux_common.h:10-13  demux_sbs kernel (d_demux_common.cu:8-33) as a host-callable stage */
 void stm_d_demux_sbs(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_img_sbs,
                      int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz);
@@ -708,6 +772,10 @@ int   stm_stream_set_packing(void *stream, int packing, int swap, int filter, in
  * installs it only for the duration of its frame calls: the calling thread's stm_set_lens neither reaches the stream's frames
  * (or its captured graph) nor is changed by them.  Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
 int   stm_stream_set_lens(void *stream, int mode, double pitch, double slope, double centre);
+/* the output geometry of the stream's frames (stm_set_layout's rules; the default is layout 0).  The stream keeps its own copy and
+ * installs it only for the duration of its frame calls, like the lens geometry: the calling thread's stm_set_layout neither reaches
+ * the stream's frames nor is changed by them.  Only before the first submit.  Returns 0, or -1 with the error recorded. */
+int   stm_stream_set_layout(void *stream, int layout, int tiles_x, int tiles_y, int order, int filter);
 /* the depth budget of the stream's frames (stm_set_depth's rules; the default is mode 0).  As with the lens geometry the stream keeps
  * its own copy and installs it only around its frame calls.  stm_stream_set_depth_auto sets mode 2's parameters (stm_set_depth_auto's
  * rules; call it before stm_stream_set_depth(stream, 2, 0, 0)); the state is the stream's own: one buffer at a fixed address, zeroed

@@ -34,6 +34,9 @@ PROTOS = {
     "stm_set_irv_paper_ratio": ([i], None),
     "stm_set_ref_quirks": ([i], None),
     "stm_set_lens": ([i, d, d, d], i),
+    "stm_set_layout": ([i, i, i, i, i], i),
+    "stm_get_layout": ([C.POINTER(C.c_int)], None),
+    "stm_set_quilt_lds_limit": ([i], None),
     "stm_set_packing": ([i, i, i, i], i),
     "stm_get_packing": ([C.POINTER(C.c_int)], None),
     "stm_set_depth": ([i, f, f], i),
@@ -77,6 +80,8 @@ PROTOS = {
     "stm_d_mux_multiview": ([vp, vp, i, f, i, i, i, i, i], None),
     "stm_mux_multiview_lens": ([u8pp, u8p, i, i, d, d, d, i, i, i, i, i], None),
     "stm_d_mux_multiview_lens": ([vp, vp, i, i, d, d, d, i, i, i, i, i], None),
+    "stm_quilt_multiview": ([u8pp, u8p, i, i, i, i, i, i, i, i, i, i], None),
+    "stm_d_quilt_multiview": ([vp, vp, i, i, i, i, i, i, i, i, i, i], None),
     "stm_d_demux_sbs": ([vp, vp, vp, i, i, i, i], None),
     "stm_demux_nv12": ([u8p, u8p, u8p, i, u8p, i, i, i, i, i, i], None),
     "stm_d_demux_nv12": ([vp, vp, vp, i, vp, i, i, i, i, i, i], None),
@@ -107,6 +112,7 @@ PROTOS = {
     "stm_stream_set_input": ([C.c_void_p, i, i], i),
     "stm_stream_set_packing": ([C.c_void_p, i, i, i, i], i),
     "stm_stream_set_lens": ([C.c_void_p, i, d, d, d], i),
+    "stm_stream_set_layout": ([C.c_void_p, i, i, i, i, i], i),
     "stm_stream_set_depth": ([C.c_void_p, i, f, f], i),
     "stm_stream_set_depth_auto": ([C.c_void_p, f, f, f, i, f], i),
     "stm_stream_depth": ([C.c_void_p, f32p], i),

@@ -343,6 +343,33 @@ bool stm::nv12_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_c
 }
 
 // the rules of a packed frame (stm_hip.h, stm_demux_packed), after the dimension screen
+bool stm::quilt_args_ok(const char *fn, const Layout &lo, int num_views, int in_rows, int in_cols, int out_rows, int out_cols,
+                        const char *views_name, const char *rows_name, const char *cols_name)
+{
+    char msg[240];
+    const char *arg = nullptr;
+    const int tw = out_cols / lo.tiles_x, th = out_rows / lo.tiles_y;
+    if ((long long)lo.tiles_x * lo.tiles_y != num_views) {
+        snprintf(msg, sizeof msg, "%s: a quilt of tiles_x * tiles_y = %d * %d tiles needs as many views, %s = %d", fn, lo.tiles_x, lo.tiles_y,
+                 views_name, num_views);
+        arg = views_name;
+    } else if (tw == 0) {
+        snprintf(msg, sizeof msg, "%s: %s = %d leaves tiles_x = %d tiles no column", fn, cols_name, out_cols, lo.tiles_x);
+        arg = cols_name;
+    } else if (th == 0) {
+        snprintf(msg, sizeof msg, "%s: %s = %d leaves tiles_y = %d tiles no row", fn, rows_name, out_rows, lo.tiles_y);
+        arg = rows_name;
+    } else if ((long long)tw * in_cols > 0x7fffffffll) { // the area filter's weights are ints
+        snprintf(msg, sizeof msg, "%s: tile width * view width = %d * %d does not fit 31 bits (%s)", fn, tw, in_cols, cols_name);
+        arg = cols_name;
+    } else if ((long long)th * in_rows > 0x7fffffffll) {
+        snprintf(msg, sizeof msg, "%s: tile height * view height = %d * %d does not fit 31 bits (%s)", fn, th, in_rows, rows_name);
+        arg = rows_name;
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
 bool stm::packing_args_ok(const char *fn, const Packing &pk, int num_rows, int num_cols_sbs, int num_cols, const char *cols_name, bool nv12,
                           int pitch_y, int pitch_uv, int matrix)
 {
@@ -954,6 +981,43 @@ void stm_mux_multiview_lens(unsigned char **views, unsigned char *out_data, int 
     sync();
 }
 
+// the views tiled into one frame (an addition; stm_hip.h): the quilt as a stage, filter 0 or 1
+void stm_d_quilt_multiview(unsigned char **d_views, unsigned char *d_out_data, int num_views, int tiles_x, int tiles_y, int order, int filter,
+                           int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz)
+{
+    const char *fn = "d_quilt_multiview";
+    if (!args_ok(fn, {{"num_views", num_views, 2}, {"in_rows", in_rows, 1}, {"in_cols", in_cols, 1}, {"out_rows", out_rows, 1},
+                      {"out_cols", out_cols, 1}, {"elem_sz", elem_sz, 3}}))
+        return;
+    if (!layout_params_ok(fn, 1, tiles_x, tiles_y, order, filter)) return;
+    const Layout lo = {1, tiles_x, tiles_y, order, filter};
+    if (!quilt_args_ok(fn, lo, num_views, in_rows, in_cols, out_rows, out_cols, "num_views", "out_rows", "out_cols")) return;
+    launch_quilt((const u8 *const *)d_views, d_out_data, num_views, lo, in_rows, in_cols, out_rows, out_cols, elem_sz);
+}
+void stm_quilt_multiview(unsigned char **views, unsigned char *out_data, int num_views, int tiles_x, int tiles_y, int order, int filter,
+                         int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz)
+{
+    const char *fn = "quilt_multiview";
+    if (!args_ok(fn, {{"num_views", num_views, 2}, {"in_rows", in_rows, 1}, {"in_cols", in_cols, 1}, {"out_rows", out_rows, 1},
+                      {"out_cols", out_cols, 1}, {"elem_sz", elem_sz, 3}}))
+        return;
+    if (!layout_params_ok(fn, 1, tiles_x, tiles_y, order, filter)) return;
+    const Layout lo = {1, tiles_x, tiles_y, order, filter};
+    if (!quilt_args_ok(fn, lo, num_views, in_rows, in_cols, out_rows, out_cols, "num_views", "out_rows", "out_cols")) return;
+    size_t in_sz = (size_t)in_rows * in_cols * elem_sz, out_sz = (size_t)out_rows * out_cols * elem_sz;
+    Workspace::begin(num_views * (in_sz + 256) + out_sz + 8192);
+    std::vector<u8 *> h(num_views);
+    for (int v = 0; v < num_views; ++v) h[v] = up(views[v], in_sz);
+    u8 **dv = Workspace::get<u8 *>(num_views);
+    STM_CHECK(hipMemcpyAsync(dv, h.data(), sizeof(u8 *) * num_views, hipMemcpyHostToDevice, stream()));
+    sync(); // h goes out of scope below
+    u8 *o = Workspace::get<u8>(out_sz);
+    STM_CHECK(hipMemsetAsync(o, 0, out_sz, stream())); // bytes past a pixel's third come back 0
+    launch_quilt((const u8 *const *)dv, o, num_views, lo, in_rows, in_cols, out_rows, out_cols, elem_sz);
+    down(out_data, o, out_sz);
+    sync();
+}
+
 void stm_d_demux_sbs(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_img_sbs, int num_rows,
                      int num_cols_sbs, int num_cols_out, int elem_sz)
 {
@@ -1245,6 +1309,21 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
                       bilateral_one_value_table(D, zero_disp, 10.0f, 5.0f), zero_disp);
 }
 
+// the thread's layout (stm_set_layout) against a rendering frame call's geometry, before anything is launched; layout 0, or a call
+// that renders nothing: nothing to check, the call is as it was
+bool frame_layout_ok(const char *fn, int stages, int num_views, int H, int W, int Hout, int Wout)
+{
+    const Layout lo = layout();
+    if (lo.layout == 0 || (stages & 0xff) < 3) return true;
+    if (lens().mode != 0) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "%s: layout 1 (quilt) together with lens mode %d: a quilt is not interlaced, set one of them to 0", fn, lens().mode);
+        fail(msg, "layout, lens", __FILE__, __LINE__);
+        return false;
+    }
+    return quilt_args_ok(fn, lo, num_views, H, W, Hout, Wout, "num_views", "num_rows_out", "num_cols_out");
+}
+
 // hit maps -> bleed -> masks -> N-2 views -> interlace (d_io.cu:160-205)
 void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_interlaced, int H, int W, int Hout, int Wout,
                   int elem_sz, int N, float angle, bool linear = false)
@@ -1262,6 +1341,29 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
     // this render reads (the up-scaled ones of the reduced frame, the stabilised ones of 0x2000) and leaves gain and conv in the
     // state, which the renderer reads on the device.
     const Depth dp = depth();
+    // a quilt (stm_set_layout) replaces the interlacer altogether: the views are tiled, whole.  The caller has screened the tiling
+    // (frame_layout_ok).  With a depth budget there are no views to write; without one, 200 writes every view and tiles the table.
+    const Layout lo = layout();
+    if (lo.layout == 1) {
+        float *state = nullptr;
+        if (dp.mode == 2) {
+            uint32_t *hist = Workspace::get<uint32_t>(4096);
+            state = dp.d_state ? dp.d_state : Workspace::get<float>(4);
+            launch_depth_fit(state, hist, d_disp_l, d_disp_r, H, W, dp.disp_lo, dp.disp_hi, dp.max_gain, dp.clip_permille, dp.rate,
+                             dp.d_state == nullptr);
+        }
+        if (dp.mode == 0 && (agg_variant() / 100) % 10 == 2) {
+            u8 *views_mem = Workspace::get<u8>((size_t)N * IMG);
+            launch_view_synth_all(views_mem, IMG, N, img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, H, W, elem_sz, linear);
+            u8 **dv = Workspace::get<u8 *>(N);
+            launch_view_table(dv, img_r, img_l, views_mem, IMG, N);
+            launch_quilt((const u8 *const *)dv, d_interlaced, N, lo, H, W, Hout, Wout, elem_sz);
+            return;
+        }
+        launch_synth_quilt(img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, d_interlaced, N, lo, dp.mode, dp.gain, dp.conv, state, H, W,
+                           Hout, Wout, elem_sz, linear);
+        return;
+    }
     if (dp.mode != 0) {
         float inv_y = 0.0f;
         int ymod = 1;
@@ -1374,6 +1476,7 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
         fail(msg, "stages", __FILE__, __LINE__);
         return;
     }
+    if (!frame_layout_ok(fn, stages, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return;
     const int H = num_rows, W = num_cols, N = num_views;
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
     const size_t V = pq_volume_floats(num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
@@ -1623,6 +1726,7 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
     if (!reduced_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp, num_cols_disp, elem_sz,
                          num_views, num_disp, stages))
         return;
+    if (!frame_layout_ok(fn, stages, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return;
     const int H = num_rows, W = num_cols, h = num_rows_disp, w = num_cols_disp, N = num_views;
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz, hw = (size_t)h * w;
     const size_t V = pq_volume_floats(num_disp, h, w);
@@ -1660,6 +1764,7 @@ void reduced_frame_host(const char *fn, unsigned char *img_sbs, float *disp_l, f
     if (!reduced_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp, num_cols_disp, elem_sz,
                          num_views, num_disp, stages))
         return;
+    if (!frame_layout_ok(fn, stages, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return; // before the caller's arrays are written
     size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
     size_t out_sz = (size_t)num_rows_out * num_cols_out * elem_sz;
     const size_t need[4] = {sbs_sz, out_sz, HW * 4, HW * 4};
@@ -1755,6 +1860,7 @@ void stm_adcensus_stm(unsigned char *img_sbs, float *disp_l, float *disp_r, unsi
                                   {"elem_sz", elem_sz, 3}, {"num_views", num_views, 2}, {"num_disp", num_disp, 1}}))
         return;
     if (packing_unsupported("adcensus_stm")) return;
+    if (!frame_layout_ok("adcensus_stm", 3, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return; // before the caller's arrays are written
     size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
     size_t out_sz = (size_t)num_rows_out * num_cols_out * elem_sz;
     // own buffers are cached outside the workspace: the pipeline call below re-carves the workspace

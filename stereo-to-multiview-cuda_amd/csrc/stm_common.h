@@ -115,6 +115,22 @@ struct PackInput {
     const u8 *y, *uv;
     int pitch_y, pitch_uv, matrix;
 };
+// The geometry of the output frame (stm_set_layout, include/stm_hip.h): layout 0 = the interlaced frame (the lens geometry applies),
+// 1 = a quilt of tiles_x x tiles_y tiles, one view each; order bit 0: tile rows run bottom-up, bit 1: the view order is reversed;
+// filter 0 = the reference's four-neighbour sampler, 1 = the area average.  One per host thread, next to the lens geometry; a frame
+// stream installs its own copy around its frame calls (stm_stream_set_layout).
+struct Layout {
+    int layout, tiles_x, tiles_y, order, filter;
+};
+Layout layout();
+void set_layout(const Layout &l);
+// the rules of the five settings alone; false with the error recorded
+bool layout_params_ok(const char *fn, int layout, int tiles_x, int tiles_y, int order, int filter);
+// stm_api.hip: a quilt's tiling against the views and the output frame (stm_hip.h); false with the error recorded.  views_name,
+// rows_name, cols_name: the caller's names for the number of views and the output's size
+bool quilt_args_ok(const char *fn, const Layout &lo, int num_views, int in_rows, int in_cols, int out_rows, int out_cols, const char *views_name,
+                   const char *rows_name, const char *cols_name);
+int quilt_lds_limit(); // stm_set_quilt_lds_limit: the bytes of LDS the area filter's staged kernel may take per workgroup
 int irv_paper_ratio(); // stm_set_irv_paper_ratio: accept on count / S instead of the reference's bin index / S (SURVEY A-Q17 iv)
 // Timing experiments (skip loads / sweeps / stores; results NOT valid) exist only in the separate libstm_hip_timing.so
 // (make timing, -DSTM_TIMING): in the product library every STM_DBG test is the constant false and stm_set_agg_variant
@@ -296,6 +312,12 @@ void launch_synth_mux_lens(const u8 *img_l, const u8 *img_r, const float *disp_l
 void launch_synth_mux_depth(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l,
                             const float *mask_r, const float *blend, u8 *out, int N, const Lens &ln, float inv_y_interval, int ymod,
                             float gain, float conv, const float *state, int Hin, int Win, int Hout, int Wout, int elem_sz, bool linear);
+// the quilt (stm_set_layout, lo.layout == 1, screened by quilt_args_ok): a table of finished views tiled into `out`, and the frame's
+// renderer tiled directly with no view written (depth_mode 0: synth_sample's views; 1, 2: the depth budget's, state as above)
+void launch_quilt(const u8 *const *d_views, u8 *out, int N, const Layout &lo, int Hin, int Win, int Hout, int Wout, int elem_sz);
+void launch_synth_quilt(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l, const float *mask_r,
+                        const float *blend, u8 *out, int N, const Layout &lo, int depth_mode, float gain, float conv, const float *state,
+                        int Hin, int Win, int Hout, int Wout, int elem_sz, bool linear);
 // the measurement (stm_kernels_depth.hip): both maps into the 4096-bin histogram `hist` (scratch), the fit, the update of `state`
 // (four floats); fresh: the state's history is ignored
 void launch_depth_fit(float *state, uint32_t *hist, const float *disp_l, const float *disp_r, int H, int W, float disp_lo, float disp_hi,

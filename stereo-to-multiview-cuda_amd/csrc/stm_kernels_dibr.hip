@@ -948,4 +948,355 @@ void launch_synth_mux_depth(const u8 *img_l, const u8 *img_r, const float *disp_
     STM_CHECK_LAUNCH();
 }
 
+// ------------------------------------------------------------------ quilt output (stm_hip.h, stm_set_layout)
+// The views as a grid of tiles instead of interlaced sub-pixels: view v fills tile k = (order & 2) ? N - 1 - v : v of tiles_x x
+// tiles_y tiles of tw x th pixels, each tile the whole view resampled -- by the reference's four-neighbour sampler (filter 0) or by
+// the exact area average (filter 1).  A view's pixel V(v, x, y, c) comes from one of three sources:
+//   QSRC_VIEWS  a table of finished views (the stage stm_quilt_multiview, and the frame under stm_set_agg_variant(200))
+//   QSRC_SYNTH  the frame's renderer, synth_sample (the end views are the two images)
+//   QSRC_DEPTH  the renderer under a depth budget, depth_sample at s = view_shift(v, N), xs = (float)x, y0 = y1 = y, wy = 0
+// so the fused kernels write no view to memory.
+enum { QSRC_VIEWS = 0, QSRC_SYNTH = 1, QSRC_DEPTH = 2, QSRC_IMAGE = 3 }; // QSRC_IMAGE (inside the kernels): an end view of QSRC_SYNTH
+struct QuiltSrc {
+    const u8 *image;        // QSRC_IMAGE
+    const u8 *const *views; // QSRC_VIEWS
+    SynthArgs a;            // QSRC_SYNTH, QSRC_DEPTH
+    float gain, conv;       // QSRC_DEPTH
+    const float *state;     // QSRC_DEPTH, automatic mode: gain and conv are read from state[1], state[2]
+};
+struct QuiltGeom {
+    int N, tiles_x, tiles_y, order, tw, th, Hin, Win, Hout, Wout, elem_sz;
+    int narrow; // 255 Win Hin + Win Hin / 2 fits 32 bits
+};
+// where tile k lies: its left column and top row
+__device__ __forceinline__ void quilt_tile_origin(const QuiltGeom &g, int k, int &left, int &top)
+{
+    const int i = k % g.tiles_x, j = k / g.tiles_x;
+    left = i * g.tw;
+    top = (g.order & 1) ? g.Hout - (j + 1) * g.th : j * g.th;
+}
+// the three channels of V(v, x, y): the maps of the pixel are loaded once
+template <int SRC, bool LINEAR>
+__device__ __forceinline__ void quilt_render3(const QuiltSrc &s, const QuiltGeom &g, int v, int x, int y, uint32_t (&px)[3])
+{
+    if constexpr (SRC == QSRC_VIEWS || SRC == QSRC_IMAGE) {
+        const u8 *p = (SRC == QSRC_VIEWS ? s.views[v] : s.image) + ((size_t)y * g.Win + x) * g.elem_sz;
+        px[0] = p[0]; px[1] = p[1]; px[2] = p[2];
+    } else if constexpr (SRC == QSRC_SYNTH) { // an interior view (the callers take the end views as QSRC_IMAGE): synth_sample's general branch
+        const LensNb n = lens_nb(s.a, x, y, g.Win);
+        const float sh = view_shift(v, g.N);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[c] = lens_sample_shift<LINEAR>(s.a, n, sh, c, g.Win, g.elem_sz);
+    } else {
+        DepthNbs nb;
+        nb.x0 = -1;
+        nb.has_x1 = false;
+        const float sh = view_shift(v, g.N);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[c] = depth_sample<LINEAR>(s.a, nb, sh, (float)x, y, y, 0.0f, s.gain, s.conv, c, g.Win, g.elem_sz);
+    }
+}
+// the overlap of output interval u with source interval x in units of 1 / t of a source pixel (t = the tile's size, n = the view's)
+__device__ __forceinline__ uint32_t quilt_weight(int u, int x, int n, int t)
+{
+    const int lo = max(u * n, x * t), hi = min((u + 1) * n, (x + 1) * t);
+    return (uint32_t)max(hi - lo, 0);
+}
+__device__ __forceinline__ u8 quilt_round(unsigned long long acc, const QuiltGeom &g)
+{
+    const unsigned long long den = (unsigned long long)g.Win * (unsigned long long)g.Hin;
+    if (g.narrow) return (u8)(((uint32_t)acc + (uint32_t)den / 2u) / (uint32_t)den);
+    return (u8)((acc + den / 2) / den);
+}
+
+// The pixels that belong to no tile: the remainder columns at the right over every row, then the remainder rows over the tiles'
+// columns.  Their first three bytes are written 0.
+__global__ __launch_bounds__(256) void stm_k_quilt_pad(u8 *__restrict__ out, QuiltGeom g, int rem_w, int rem_h)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t n_right = (size_t)rem_w * g.Hout, used_w = (size_t)(g.Wout - rem_w);
+    int x, y;
+    if (t < n_right) {
+        y = (int)(t / rem_w);
+        x = (int)used_w + (int)(t - (size_t)y * rem_w);
+    } else {
+        const size_t q = t - n_right;
+        if (q >= used_w * rem_h) return;
+        const int r = (int)(q / used_w);
+        x = (int)(q - (size_t)r * used_w);
+        y = (g.order & 1) ? r : g.Hout - rem_h + r; // bottom-up tiles leave the top rows
+    }
+    u8 *o = out + ((size_t)y * g.Wout + x) * g.elem_sz;
+    o[0] = 0; o[1] = 0; o[2] = 0;
+}
+
+// Filter 0, one thread per output pixel: stm_k_mux's sampling position with the tile's size in place of the frame's, the
+// four-neighbour sampler on the renderer's samples.  The pixels outside every tile are written here.
+template <int SRC, bool LINEAR>
+__global__ __launch_bounds__(256) void stm_k_quilt_nb(QuiltSrc s, u8 *__restrict__ out, QuiltGeom g)
+{
+    const int tx = blockIdx.x * 256 + threadIdx.x, ty = blockIdx.y;
+    if (tx >= g.Wout) return;
+    if constexpr (SRC == QSRC_DEPTH)
+        if (s.state) { // automatic mode: what stm_k_depth_fit left for this frame
+            s.gain = s.state[1];
+            s.conv = s.state[2];
+        }
+    u8 *o = out + ((size_t)tx + (size_t)ty * g.Wout) * g.elem_sz;
+    const int i = tx / g.tw;
+    const int r = (g.order & 1) ? g.Hout - 1 - ty : ty; // rows counted from the edge the tile rows start at
+    const int j = r / g.th;
+    if (i >= g.tiles_x || j >= g.tiles_y) {
+        o[0] = 0; o[1] = 0; o[2] = 0;
+        return;
+    }
+    const int k = j * g.tiles_x + i;
+    const int v = (g.order & 2) ? g.N - 1 - k : k;
+    int left, top;
+    quilt_tile_origin(g, k, left, top);
+    const int u = tx - left, w = ty - top;
+    float xs = ((float)u / (float)g.tw) * (float)g.Win;
+    xs = fminf(fmaxf(xs, 0.0f), (float)(g.Win - 1));
+    float ys = ((float)w / (float)g.th) * (float)g.Hin;
+    ys = fminf(fmaxf(ys, 0.0f), (float)(g.Hin - 1));
+    if constexpr (SRC == QSRC_VIEWS) {
+        const u8 *vw = s.views[v];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = bilinear_u8(vw, g.elem_sz, c, xs, ys, g.Win, g.Hin);
+    } else {
+        const int y0 = (int)floorf(ys);
+        const int y1 = min(y0 + 1, g.Hin - 1);
+        const float wy = ys - (float)y0;
+        if constexpr (SRC == QSRC_SYNTH) {
+            const int x0 = (int)floorf(xs);
+            const int x1 = min(x0 + 1, g.Win - 1);
+            const float wx = xs - (float)x0;
+            const LensNb n00 = lens_nb(s.a, x0, y0, g.Win);
+            LensNb n01 = n00, n10 = n00, n11 = n00; // only read where the weight is not 0
+            if (wx != 0.0f) n01 = lens_nb(s.a, x1, y0, g.Win);
+            if (wy != 0.0f) {
+                n10 = lens_nb(s.a, x0, y1, g.Win);
+                if (wx != 0.0f) n11 = lens_nb(s.a, x1, y1, g.Win);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = lens_bilinear<LINEAR, false>(s.a, n00, n01, n10, n11, wx, wy, g.N, v, 0.0f, c, g.Win, g.elem_sz);
+        } else {
+            DepthNbs nb;
+            nb.x0 = -1;
+            nb.has_x1 = false;
+            const float sh = view_shift(v, g.N);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = depth_sample<LINEAR>(s.a, nb, sh, xs, y0, y1, wy, s.gain, s.conv, c, g.Win, g.elem_sz);
+        }
+    }
+}
+
+// The staging of stm_k_quilt_area: the fw x fh view pixels from (fx0, fy0) rendered into pix, QUILT_STAGE_UNROLL independent pixels
+// per thread and step so that their loads are in flight together (a step past the end renders the last pixel again and stores nothing)
+#define QUILT_STAGE_UNROLL 4
+template <int SRC, bool LINEAR>
+__device__ __forceinline__ void quilt_stage(const QuiltSrc &s, const QuiltGeom &g, int v, int fx0, int fy0, int fw, int fh, uint32_t *pix)
+{
+    const int n = fw * fh;
+    for (int t0 = threadIdx.x; t0 < n; t0 += 256 * QUILT_STAGE_UNROLL) {
+        uint32_t r[QUILT_STAGE_UNROLL];
+#pragma unroll
+        for (int i = 0; i < QUILT_STAGE_UNROLL; ++i) {
+            const int t = min(t0 + i * 256, n - 1);
+            const int fy = t / fw, fx = t - fy * fw;
+            uint32_t px[3];
+            quilt_render3<SRC, LINEAR>(s, g, v, fx0 + fx, fy0 + fy, px);
+            r[i] = px[0] | (px[1] << 8) | (px[2] << 16);
+        }
+#pragma unroll
+        for (int i = 0; i < QUILT_STAGE_UNROLL; ++i)
+            if (t0 + i * 256 < n) pix[t0 + i * 256] = r[i];
+    }
+}
+// the same choice of source for one pixel (stm_k_quilt_area_px)
+template <int SRC, bool LINEAR>
+__device__ __forceinline__ void quilt_render3_any(const QuiltSrc &s, const QuiltGeom &g, int v, int x, int y, uint32_t (&px)[3])
+{
+    if constexpr (SRC == QSRC_SYNTH) {
+        if (v == 0 || v == g.N - 1) { // view 0 = the right image, view N - 1 = the left image (d_io.cu:182-183)
+            QuiltSrc e = s;
+            e.image = v == 0 ? s.a.img_r : s.a.img_l;
+            quilt_render3<QSRC_IMAGE, LINEAR>(e, g, v, x, y, px);
+            return;
+        }
+    }
+    quilt_render3<SRC, LINEAR>(s, g, v, x, y, px);
+}
+
+// Filter 1, the area average.  A workgroup owns bw x bh output pixels of tile blockIdx.z.  It renders every view pixel of the block's
+// footprint once into LDS (three channels in one dword, from one load of the pixel's maps), reduces each footprint row with the
+// column weights into 32-bit partial sums (at most 255 Win), then the partial sums with the row weights, rounds and writes u8.
+// Integer arithmetic throughout, so the order of the sums does not matter.  LDS: [fh_max][fw_max] pixels, then [fh_max][BW][3] sums.
+template <int SRC, bool LINEAR>
+__global__ __launch_bounds__(256) void stm_k_quilt_area(QuiltSrc s, u8 *__restrict__ out, QuiltGeom g, int BW, int BH, int fw_max, int fh_max)
+{
+    extern __shared__ uint32_t quilt_lds[];
+    if constexpr (SRC == QSRC_DEPTH)
+        if (s.state) {
+            s.gain = s.state[1];
+            s.conv = s.state[2];
+        }
+    uint32_t *pix = quilt_lds, *hs = quilt_lds + (size_t)fw_max * fh_max;
+    const int k = blockIdx.z;
+    const int v = (g.order & 2) ? g.N - 1 - k : k;
+    int left, top;
+    quilt_tile_origin(g, k, left, top);
+    const int u0 = blockIdx.x * BW, w0 = blockIdx.y * BH;
+    const int bw = min(BW, g.tw - u0), bh = min(BH, g.th - w0);
+    const int fx0 = (u0 * g.Win) / g.tw, fy0 = (w0 * g.Hin) / g.th;
+    const int fw = ((u0 + bw) * g.Win - 1) / g.tw - fx0 + 1, fh = ((w0 + bh) * g.Hin - 1) / g.th - fy0 + 1; // <= fw_max, fh_max
+    bool staged = false;
+    if constexpr (SRC == QSRC_SYNTH)
+        if (v == 0 || v == g.N - 1) { // view 0 = the right image, view N - 1 = the left image (d_io.cu:182-183): block-uniform
+            s.image = v == 0 ? s.a.img_r : s.a.img_l;
+            quilt_stage<QSRC_IMAGE, LINEAR>(s, g, v, fx0, fy0, fw, fh, pix);
+            staged = true;
+        }
+    if (!staged) quilt_stage<SRC, LINEAR>(s, g, v, fx0, fy0, fw, fh, pix);
+    __syncthreads();
+    for (int t = threadIdx.x; t < fh * bw; t += 256) {
+        const int fy = t / bw, u = u0 + (t - fy * bw);
+        const int xa = (u * g.Win) / g.tw, xb = ((u + 1) * g.Win - 1) / g.tw;
+        uint32_t s0 = 0, s1 = 0, s2 = 0;
+        const uint32_t *row = pix + fy * fw;
+        for (int x = xa; x <= xb; ++x) {
+            const uint32_t wx = quilt_weight(u, x, g.Win, g.tw), p = row[x - fx0];
+            s0 += wx * (p & 255u);
+            s1 += wx * ((p >> 8) & 255u);
+            s2 += wx * (p >> 16);
+        }
+        hs[3 * t] = s0; hs[3 * t + 1] = s1; hs[3 * t + 2] = s2;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < bh * bw; t += 256) {
+        const int wl = t / bw, ul = t - wl * bw;
+        const int w = w0 + wl;
+        const int ya = (w * g.Hin) / g.th, yb = ((w + 1) * g.Hin - 1) / g.th;
+        unsigned long long a0 = 0, a1 = 0, a2 = 0;
+        for (int y = ya; y <= yb; ++y) {
+            const unsigned long long wy = quilt_weight(w, y, g.Hin, g.th);
+            const uint32_t *h = hs + 3 * ((y - fy0) * bw + ul);
+            a0 += wy * h[0];
+            a1 += wy * h[1];
+            a2 += wy * h[2];
+        }
+        u8 *o = out + ((size_t)(left + u0 + ul) + (size_t)(top + w) * g.Wout) * g.elem_sz;
+        o[0] = quilt_round(a0, g); o[1] = quilt_round(a1, g); o[2] = quilt_round(a2, g);
+    }
+}
+// The same average with one thread per output pixel looping over its own footprint: taken where even a 1 x 1 block's footprint
+// does not fit the staging (a tiny tile of a large view).  Every view pixel is rendered by each output pixel that overlaps it.
+template <int SRC, bool LINEAR>
+__global__ __launch_bounds__(256) void stm_k_quilt_area_px(QuiltSrc s, u8 *__restrict__ out, QuiltGeom g)
+{
+    const int u = blockIdx.x * 256 + threadIdx.x, w = blockIdx.y, k = blockIdx.z;
+    if (u >= g.tw) return;
+    if constexpr (SRC == QSRC_DEPTH)
+        if (s.state) {
+            s.gain = s.state[1];
+            s.conv = s.state[2];
+        }
+    const int v = (g.order & 2) ? g.N - 1 - k : k;
+    int left, top;
+    quilt_tile_origin(g, k, left, top);
+    const int xa = (u * g.Win) / g.tw, xb = ((u + 1) * g.Win - 1) / g.tw;
+    const int ya = (w * g.Hin) / g.th, yb = ((w + 1) * g.Hin - 1) / g.th;
+    unsigned long long a0 = 0, a1 = 0, a2 = 0;
+    for (int y = ya; y <= yb; ++y) {
+        uint32_t s0 = 0, s1 = 0, s2 = 0;
+        for (int x = xa; x <= xb; ++x) {
+            const uint32_t wx = quilt_weight(u, x, g.Win, g.tw);
+            uint32_t px[3];
+            quilt_render3_any<SRC, LINEAR>(s, g, v, x, y, px);
+            s0 += wx * px[0];
+            s1 += wx * px[1];
+            s2 += wx * px[2];
+        }
+        const unsigned long long wy = quilt_weight(w, y, g.Hin, g.th);
+        a0 += wy * s0;
+        a1 += wy * s1;
+        a2 += wy * s2;
+    }
+    u8 *o = out + ((size_t)(left + u) + (size_t)(top + w) * g.Wout) * g.elem_sz;
+    o[0] = quilt_round(a0, g); o[1] = quilt_round(a1, g); o[2] = quilt_round(a2, g);
+}
+
+// The block of the staged kernel: the largest of 32 x 16, halved along the axis with the longer footprint, whose staging fits
+// `limit` bytes of LDS; false where not even one output pixel's footprint does.
+static bool quilt_block(const QuiltGeom &g, size_t limit, int &BW, int &BH, int &fw_max, int &fh_max, size_t &bytes)
+{
+    BW = 32;
+    BH = 16;
+    for (;;) {
+        fw_max = min(g.Win, cdiv(BW * g.Win, g.tw) + 1); // tw Win and th Hin fit an int (quilt_args_ok)
+        fh_max = min(g.Hin, cdiv(BH * g.Hin, g.th) + 1);
+        bytes = 4 * ((size_t)fw_max * fh_max + (size_t)fh_max * BW * 3);
+        if (bytes <= limit) return true;
+        if (BH > 1 && (fh_max >= fw_max || BW == 1)) BH /= 2;
+        else if (BW > 1) BW /= 2;
+        else return false;
+    }
+}
+template <int SRC, bool LINEAR>
+static void launch_quilt_src(const QuiltSrc &s, u8 *out, const QuiltGeom &g, int filter)
+{
+    const dim3 full(cdiv(g.Wout, 256), g.Hout);
+    if (filter == 0) {
+        STM_LAUNCH((stm_k_quilt_nb<SRC, LINEAR>), full, dim3(256), 0, stream(), s, out, g);
+        return;
+    }
+    const int rem_w = g.Wout - g.tiles_x * g.tw, rem_h = g.Hout - g.tiles_y * g.th;
+    const size_t n_pad = (size_t)rem_w * g.Hout + (size_t)(g.Wout - rem_w) * rem_h;
+    if (n_pad) STM_LAUNCH(stm_k_quilt_pad, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, stream(), out, g, rem_w, rem_h);
+    int BW, BH, fw_max, fh_max;
+    size_t bytes;
+    if (quilt_block(g, (size_t)quilt_lds_limit(), BW, BH, fw_max, fh_max, bytes))
+        STM_LAUNCH((stm_k_quilt_area<SRC, LINEAR>), dim3(cdiv(g.tw, BW), cdiv(g.th, BH), g.N), dim3(256), bytes, stream(), s, out, g, BW, BH,
+                   fw_max, fh_max);
+    else
+        STM_LAUNCH((stm_k_quilt_area_px<SRC, LINEAR>), dim3(cdiv(g.tw, 256), g.th, g.N), dim3(256), 0, stream(), s, out, g);
+}
+static QuiltGeom quilt_geom(const Layout &lo, int N, int Hin, int Win, int Hout, int Wout, int elem_sz)
+{
+    QuiltGeom g{N, lo.tiles_x, lo.tiles_y, lo.order, Wout / lo.tiles_x, Hout / lo.tiles_y, Hin, Win, Hout, Wout, elem_sz, 0};
+    const unsigned long long den = (unsigned long long)Win * (unsigned long long)Hin;
+    g.narrow = 255ull * den + den / 2 <= 0xffffffffull;
+    return g;
+}
+// lo screened by the caller (quilt_args_ok)
+void launch_quilt(const u8 *const *d_views, u8 *out, int N, const Layout &lo, int Hin, int Win, int Hout, int Wout, int elem_sz)
+{
+    QuiltSrc s{};
+    s.views = d_views;
+    ProfScope p("quilt");
+    launch_quilt_src<QSRC_VIEWS, false>(s, out, quilt_geom(lo, N, Hin, Win, Hout, Wout, elem_sz), lo.filter);
+    STM_CHECK_LAUNCH();
+}
+// depth_mode 0: synth_sample's views; 1, 2: the depth budget's (state != nullptr: gain and conv are read on the device)
+void launch_synth_quilt(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l, const float *mask_r,
+                        const float *blend, u8 *out, int N, const Layout &lo, int depth_mode, float gain, float conv, const float *state,
+                        int Hin, int Win, int Hout, int Wout, int elem_sz, bool linear)
+{
+    QuiltSrc s{};
+    s.a = SynthArgs{img_l, img_r, disp_l, disp_r, mask_l, mask_r, blend};
+    s.gain = gain;
+    s.conv = conv;
+    s.state = state;
+    const QuiltGeom g = quilt_geom(lo, N, Hin, Win, Hout, Wout, elem_sz);
+    ProfScope p("synth_quilt");
+    if (depth_mode == 0) {
+        if (linear) launch_quilt_src<QSRC_SYNTH, true>(s, out, g, lo.filter);
+        else launch_quilt_src<QSRC_SYNTH, false>(s, out, g, lo.filter);
+    } else {
+        if (linear) launch_quilt_src<QSRC_DEPTH, true>(s, out, g, lo.filter);
+        else launch_quilt_src<QSRC_DEPTH, false>(s, out, g, lo.filter);
+    }
+    STM_CHECK_LAUNCH();
+}
+
 } // namespace stm

@@ -260,6 +260,39 @@ bool lens_params_ok(const char *fn, int mode, int mode_lo, int mode_hi, double p
     return false;
 }
 
+// the calling thread's output geometry (stm_set_layout)
+static thread_local Layout g_layout = {0, 1, 1, 0, 0};
+Layout layout() { return g_layout; }
+void set_layout(const Layout &l) { g_layout = l; }
+bool layout_params_ok(const char *fn, int layout, int tiles_x, int tiles_y, int order, int filter)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (layout != 0 && layout != 1) {
+        snprintf(msg, sizeof msg, "%s: layout = %d, must be 0 (interlaced) or 1 (quilt)", fn, layout);
+        arg = "layout";
+    } else if (layout == 0) {
+        return true; // interlaced: the other arguments are ignored
+    } else if (tiles_x < 1 || tiles_x > 65535) {
+        snprintf(msg, sizeof msg, "%s: tiles_x = %d, must be in 1 .. 65535", fn, tiles_x);
+        arg = "tiles_x";
+    } else if (tiles_y < 1 || tiles_y > 65535) {
+        snprintf(msg, sizeof msg, "%s: tiles_y = %d, must be in 1 .. 65535", fn, tiles_y);
+        arg = "tiles_y";
+    } else if (order < 0 || order > 3) {
+        snprintf(msg, sizeof msg, "%s: order = %d, must be 0 .. 3 (bit 0: tile rows bottom-up, bit 1: view order reversed)", fn, order);
+        arg = "order";
+    } else if (filter != 0 && filter != 1) {
+        snprintf(msg, sizeof msg, "%s: filter = %d, must be 0 (four-neighbour sampler) or 1 (area average)", fn, filter);
+        arg = "filter";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+static int g_quilt_lds_limit = 32 * 1024; // five workgroups of the staged kernel share a CU's 160 KiB
+int quilt_lds_limit() { return g_quilt_lds_limit; }
+
 // the calling thread's input packing (stm_set_packing)
 static thread_local Packing g_packing = {0, 0, 0, 0};
 Packing packing() { return g_packing; }
@@ -445,6 +478,19 @@ int stm_set_lens(int mode, double pitch, double slope, double centre)
     stm::set_lens(mode == 0 ? stm::Lens{0, 0.0, 0.0, 0.0} : stm::Lens{mode, pitch, slope, centre});
     return 0;
 }
+int stm_set_layout(int layout, int tiles_x, int tiles_y, int order, int filter)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (!stm::layout_params_ok("set_layout", layout, tiles_x, tiles_y, order, filter)) return -1; // the thread's layout stays as it was
+    stm::set_layout(layout == 0 ? stm::Layout{0, 1, 1, 0, 0} : stm::Layout{layout, tiles_x, tiles_y, order, filter});
+    return 0;
+}
+void stm_get_layout(int *out)
+{
+    const stm::Layout lo = stm::layout();
+    out[0] = lo.layout; out[1] = lo.tiles_x; out[2] = lo.tiles_y; out[3] = lo.order; out[4] = lo.filter;
+}
+void stm_set_quilt_lds_limit(int bytes) { stm::g_quilt_lds_limit = bytes <= 0 ? 32 * 1024 : (bytes > 64 * 1024 ? 64 * 1024 : bytes); }
 int stm_set_packing(int packing, int swap, int filter, int gap)
 {
     if (stm::api_outermost()) stm::clear_failed();

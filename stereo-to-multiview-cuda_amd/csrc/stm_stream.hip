@@ -49,6 +49,7 @@ struct FrameStream {
     int in_format = 0, in_matrix = 0; // stm_stream_set_input: 0 = side-by-side BGR, 1 = NV12 (Y plane, then the UV plane; pitch Wsbs)
     size_t in_bytes = 0;              // what a submit copies and uploads: in_sz, or H * Wsbs * 3 / 2 for NV12
     stm::Lens lens = {0, 0.0, 0.0, 0.0}; // stm_stream_set_lens: the stream's own display geometry, installed around its frame calls
+    stm::Layout layout = {0, 1, 1, 0, 0}; // stm_stream_set_layout: the stream's own output geometry, installed around its frame calls
     stm::Depth depth = {0, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 20, nullptr}; // stm_stream_set_depth / _auto: the stream's own depth budget
     stm::Packing packing = {0, 0, 0, 0}; // stm_stream_set_packing: the stream's own input packing, installed around its frame calls
     int rows_f = 0;                      // the rows of an input frame: H, or what the packing makes of it
@@ -62,6 +63,12 @@ struct LensScope {
     stm::Lens saved;
     explicit LensScope(const stm::Lens &l) : saved(stm::lens()) { stm::set_lens(l); }
     ~LensScope() { stm::set_lens(saved); }
+};
+
+struct LayoutScope {
+    stm::Layout saved;
+    explicit LayoutScope(const stm::Layout &l) : saved(stm::layout()) { stm::set_layout(l); }
+    ~LayoutScope() { stm::set_layout(saved); }
 };
 
 struct DepthScope {
@@ -288,6 +295,22 @@ int stm_stream_set_lens(void *h, int mode, double pitch, double slope, double ce
     return 0;
 }
 
+// The output geometry of every frame of the stream (stm_set_layout's rules; the default is layout 0, the interlaced frame).  Kept and
+// installed like the lens geometry; the tiling is screened against the stream's geometry by the first frame call.  Only before the
+// first submit.  Returns 0, or -1 with the error recorded.
+int stm_stream_set_layout(void *h, int layout, int tiles_x, int tiles_y, int order, int filter)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (!stm::layout_params_ok("stream_set_layout", layout, tiles_x, tiles_y, order, filter)) return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_layout: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    f->layout = layout == 0 ? stm::Layout{0, 1, 1, 0, 0} : stm::Layout{layout, tiles_x, tiles_y, order, filter};
+    return 0;
+}
+
 // The depth budget every frame of the stream is rendered with (stm_set_depth's rules; the default is mode 0).  Kept and installed
 // like the lens geometry.  Mode 2 allocates the stream's state and the slots' records.  Only before the first submit.
 int stm_stream_set_depth(void *h, int mode, float gain, float conv)
@@ -375,6 +398,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     if (history || (depth_auto && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
     void *prev = stm_get_stream();
     LensScope lens_scope(f->lens);
+    LayoutScope layout_scope(f->layout);
     DepthScope depth_scope(f->depth);
     PackingScope packing_scope(f->packing);
     stm_set_stream(s.s_compute);

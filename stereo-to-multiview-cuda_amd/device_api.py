@@ -52,6 +52,24 @@ def set_lens(mode, pitch=0.0, slope=0.0, centre=0.0):
         raise ValueError("stm_set_lens(%d, %g, %g, %g) refused: %s" % (mode, pitch, slope, centre, lib().stm_last_error().decode()))
 
 
+def set_layout(layout=0, tiles_x=1, tiles_y=1, order=0, filter=0):
+    """stm_set_layout: the calling thread's output geometry, which every rendering frame call writes.  layout 0 = the interlaced
+    frame (the default; the other arguments are ignored), 1 = a quilt of tiles_x x tiles_y tiles, one whole view each (tiles_x *
+    tiles_y must equal the frame's num_views); order bit 0 = tile rows bottom-up, bit 1 = view order reversed (tile 0 = the
+    leftmost camera); filter 0 = the reference's four-neighbour sampler, 1 = the area average.  Raises ValueError where the
+    library refuses."""
+    if int(lib().stm_set_layout(int(layout), int(tiles_x), int(tiles_y), int(order), int(filter))) != 0:
+        raise ValueError("stm_set_layout(%d, %d, %d, %d, %d) refused: %s"
+                         % (layout, tiles_x, tiles_y, order, filter, lib().stm_last_error().decode()))
+
+
+def get_layout():
+    """stm_get_layout: the calling thread's (layout, tiles_x, tiles_y, order, filter) as the library holds it"""
+    out = (C.c_int * 5)()
+    lib().stm_get_layout(out)
+    return tuple(int(v) for v in out)
+
+
 PACKING_OFF = (0, 0, 0, 0)
 
 def set_packing(packing=0, swap=0, filter=0, gap=0):
@@ -166,6 +184,21 @@ def d_mux_multiview_lens(views, out, mode, pitch, slope, centre):
     _use_current_stream()
     lib().stm_d_mux_multiview_lens(_p(tab), _p(out), len(views), int(mode), float(pitch), float(slope), float(centre), H, W,
                                    out.shape[0], out.shape[1], E)
+    torch.cuda.current_stream().synchronize()  # the kernel reads the pointer table: keep it alive until it has run
+
+
+def d_quilt_multiview(views, out, tiles_x, tiles_y, order=0, filter=0):
+    """stm_d_quilt_multiview: the views (a list of N = tiles_x * tiles_y uint8 [H][W][E] tensors on the GPU, views[0] = the right
+    image ... views[N - 1] = the left image) tiled into out (uint8 [Ho][Wo][E], only the first three bytes of a pixel are
+    written); set_layout's order and filter."""
+    H, W, E = views[0].shape
+    for t in views:
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.shape[2] == E
+    tab = torch.tensor([t.data_ptr() for t in views], dtype=torch.int64).to(out.device)
+    _use_current_stream()
+    lib().stm_d_quilt_multiview(_p(tab), _p(out), len(views), int(tiles_x), int(tiles_y), int(order), int(filter), H, W,
+                                out.shape[0], out.shape[1], E)
     torch.cuda.current_stream().synchronize()  # the kernel reads the pointer table: keep it alive until it has run
 
 

@@ -252,6 +252,20 @@ def mux_multiview_lens(views, mode, pitch, slope, centre, out_rows, out_cols):
     return out
 
 
+def quilt_multiview(views, tiles_x, tiles_y, order, filter, out_rows, out_cols):
+    """stm_quilt_multiview (an addition): the views tiled into one out_rows x out_cols frame, view v whole in tile k = v (order bit
+    1: N - 1 - v) of tiles_x x tiles_y tiles counted row by row from the top (order bit 0: from the bottom); filter 0 = the
+    reference's four-neighbour sampler, 1 = the area average.  Pixels outside every tile are 0."""
+    views = [np.ascontiguousarray(v, dtype=np.uint8) for v in views]
+    N = len(views)
+    H, W, E = views[0].shape
+    tab = (u8p * N)(*[v.ctypes.data_as(u8p) for v in views])
+    out = np.zeros((out_rows, out_cols, E), np.uint8)
+    lib().stm_quilt_multiview(C.cast(tab, u8pp), out.ctypes.data_as(u8p), N, int(tiles_x), int(tiles_y), int(order), int(filter),
+                              H, W, out_rows, out_cols, E)
+    return out
+
+
 def adcensus_stm(img_sbs, num_cols, out_rows, out_cols, num_views, angle, num_disp, zero_disp,
                  ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h):
     """d_io.h:32-40: host SBS frame in, (disp_l, disp_r, interlaced) out."""

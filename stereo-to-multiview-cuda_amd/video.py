@@ -22,10 +22,11 @@ class FrameStream:
     at most one of the two.  packing = (packing, swap, filter, gap): the frames come packed (stm_set_packing's settings: half-width
     side by side, top and bottom, ...); num_rows x num_cols stay the size of an unpacked eye, and a frame is then [rows_f][Wsbs][3]
     (NV12: [rows_f * 3 / 2][Wsbs]) with Wsbs = 2 * (packed eye's columns) + gap for the side-by-side packings and num_cols for the
-    top-and-bottom ones: the shape `in_shape` holds."""
+    top-and-bottom ones: the shape `in_shape` holds.  layout = (1, tiles_x, tiles_y, order, filter): the frames come out as a
+    quilt of tiles_x x tiles_y whole views (set_layout); None = the interlaced frame."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
-                 depth=None, depth_auto=None, packing=None):
+                 depth=None, depth_auto=None, packing=None, layout=None):
         self.H, self.W = num_rows, num_cols
         self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
@@ -44,6 +45,8 @@ class FrameStream:
             self.set_input(input_format, matrix)
         if lens is not None:
             self.set_lens(*lens)
+        if layout is not None:
+            self.set_layout(*layout)
         if depth is not None and depth_auto is not None:
             raise ValueError("FrameStream: depth and depth_auto are mutually exclusive")
         if depth is not None:
@@ -81,6 +84,13 @@ class FrameStream:
         if int(lib().stm_stream_set_lens(self._h, int(mode), float(pitch), float(slope), float(centre))) != 0:
             raise ValueError("stm_stream_set_lens(%d, %g, %g, %g) refused: %s"
                              % (mode, pitch, slope, centre, lib().stm_last_error().decode()))
+
+    def set_layout(self, layout=0, tiles_x=1, tiles_y=1, order=0, filter=0):
+        """stm_stream_set_layout: the output geometry of the stream's frames (device_api.set_layout's arguments); the stream's own,
+        independent of the calling thread's; only before the first submit.  Raises ValueError where the library refuses."""
+        if int(lib().stm_stream_set_layout(self._h, int(layout), int(tiles_x), int(tiles_y), int(order), int(filter))) != 0:
+            raise ValueError("stm_stream_set_layout(%d, %d, %d, %d, %d) refused: %s"
+                             % (layout, tiles_x, tiles_y, order, filter, lib().stm_last_error().decode()))
 
     def set_input(self, input_format, matrix=0):
         """stm_stream_set_input: "bgr" or "nv12" with its conversion matrix; only before the first submit.  Raises ValueError where
@@ -191,14 +201,15 @@ def _collect(fs, on_depth):
 
 
 def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None,
-                     depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None):
+                     depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
     stabilisation); temporal: (alpha, thresh_color, thresh_disp) for FrameStream.set_temporal, None = the defaults; lens: (mode,
     pitch, slope, centre) for FrameStream.set_lens, None = the reference's interlacer; depth / depth_auto: FrameStream's depth
     budget; on_depth: called with (index, (gain, conv)) after every collected frame.  packing: FrameStream's; the frames are then packed
-    ones; eye_shape = (num_rows, num_cols), the size of an unpacked eye, defaults to what a frame without spare columns holds."""
+    ones; eye_shape = (num_rows, num_cols), the size of an unpacked eye, defaults to what a frame without spare columns holds.
+    layout: FrameStream's (the interlaced output is then a quilt)."""
     fs = None
     pending = 0
     for sbs in frames:
@@ -207,7 +218,7 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
             cols = sbs.shape[1] // 2
             if packing is not None:
                 rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
-            fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing)
+            fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:

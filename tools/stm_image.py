@@ -6,7 +6,7 @@ source, cost slice, aggregated slice, disparity, outliers, occlusion mask, every
 
 usage: stm_image.py <left.bmp> <right.bmp> <ad coeff> <census coeff> <ndisp> <zerodisp> <ucd> <lcd> <usd> <lsd>
                     <num views> <angle> <out width> <out height> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel]
-                    [--linear-warp] [--lens MODE PITCH SLOPE CENTRE]
+                    [--linear-warp] [--lens MODE PITCH SLOPE CENTRE] [--quilt TX TY ORDER FILTER]
 
 --interp (an addition, off by default): the outlier interpolation (host_api.dr_interp) of both maps after region voting, each on
 its own image and outlier map, before --subpixel.
@@ -17,7 +17,10 @@ coordinate) instead of dibr_dbm.
 --lens MODE PITCH SLOPE CENTRE (an addition): the views interlaced through the panel's calibration (host_api.mux_multiview_lens:
 PITCH sub-pixels per lens, SLOPE sub-pixels of lens shift per output row, CENTRE lenses of phase offset; MODE 1 = nearest view,
 2 = two views blended) instead of the reference's interlacer; <angle> is then ignored.  Mode 3 renders without views: it exists
-in the frame calls only (stm_video.py)."""
+in the frame calls only (stm_video.py).
+--quilt TX TY ORDER FILTER (an addition): the views tiled whole into the output frame (host_api.quilt_multiview: <num views> = TX *
+TY tiles; ORDER bit 0 = tile rows bottom-up, bit 1 = tile 0 holds the leftmost camera; FILTER 0 = the reference's four-neighbour
+sampler, 1 = the area average) instead of interlaced; <angle> is then ignored.  Excludes --lens."""
 import os
 import sys
 
@@ -30,6 +33,17 @@ sys.path.insert(0, ROOT)
 def main(argv):
     subpixel, interp, linear_warp = "--subpixel" in argv, "--interp" in argv, "--linear-warp" in argv
     argv = [x for x in argv if x not in ("--subpixel", "--interp", "--linear-warp")]
+    quilt = None
+    if "--quilt" in argv:
+        at = argv.index("--quilt")
+        try:
+            quilt = tuple(int(x) for x in argv[at + 1:at + 5])
+        except ValueError:
+            quilt = ()
+        if len(quilt) != 4 or quilt[0] < 1 or quilt[1] < 1 or not 0 <= quilt[2] <= 3 or quilt[3] not in (0, 1) or "--lens" in argv:
+            print(__doc__)
+            return -1
+        del argv[at:at + 5]
     lens = None
     if "--lens" in argv:
         at = argv.index("--lens")
@@ -85,7 +99,10 @@ def main(argv):
     views.append(L)
     for v, img in enumerate(views):
         wr("view_%d" % v, img)
-    wr("interlaced", api.mux_multiview(views, angle, Ho, Wo) if lens is None else api.mux_multiview_lens(views, *lens, Ho, Wo))  # :292
+    if quilt is not None:
+        wr("interlaced", api.quilt_multiview(views, *quilt, Ho, Wo))
+    else:
+        wr("interlaced", api.mux_multiview(views, angle, Ho, Wo) if lens is None else api.mux_multiview_lens(views, *lens, Ho, Wo))  # :292
     print("wrote %d files to %s (%dx%d, D=%d, %d views)" % (len(os.listdir(out)), out, W, H, D, N))
     return 0
 

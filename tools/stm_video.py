@@ -7,7 +7,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--temporal [--temporal-alpha A] [--temporal-color C] [--temporal-disp T]]
                     [--nv12 ROWS COLS_SBS [--matrix M]] [--lens MODE PITCH SLOPE CENTRE]
                     [--depth GAIN CONV | --depth-auto LO HI [MAX_GAIN CLIP RATE]]
-                    [--packing P SWAP FILTER GAP]
+                    [--packing P SWAP FILTER GAP] [--quilt TX TY ORDER FILTER]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -29,6 +29,9 @@ options are mutually exclusive.
 half width, 2 / 3 = top and bottom full / half height; SWAP 1 = the right eye first; FILTER 0 = linear, 1 = Catmull-Rom (how a
 squeezed eye is expanded); GAP pixels between the eyes (45 blank rows in 1080p HDMI frame packing).  Unpacked inside the frame's first
 kernel; combines with --nv12, whose ROWS and COLS_SBS are then the packed frame's.  The frames carry no spare columns.
+--quilt TX TY ORDER FILTER (an addition): the output frame is a quilt (stm_set_layout) -- the <num views> = TX * TY views whole, as
+TX x TY tiles, instead of interlaced; ORDER bit 0 = tile rows bottom-up, bit 1 = tile 0 holds the leftmost camera (3 = the Looking
+Glass convention); FILTER 0 = the reference's four-neighbour sampler, 1 = the area average.  <angle> is then ignored; excludes --lens.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -75,6 +78,17 @@ def main(argv):
             print(__doc__)
             return -1
         lens = (int(argv[at + 1]), float(argv[at + 2]), float(argv[at + 3]), float(argv[at + 4]))
+        del argv[at:at + 5]
+    quilt = None
+    if "--quilt" in argv:
+        at = argv.index("--quilt")
+        try:
+            quilt = tuple(int(x) for x in argv[at + 1:at + 5])
+        except ValueError:
+            quilt = ()
+        if len(quilt) != 4 or quilt[0] < 1 or quilt[1] < 1 or not 0 <= quilt[2] <= 3 or quilt[3] not in (0, 1) or lens is not None:
+            print(__doc__)
+            return -1
         del argv[at:at + 5]
     packing = None
     if "--packing" in argv:
@@ -135,7 +149,8 @@ def main(argv):
     for (k, dl, dr, inter) in video.process_sequence(frames, p, out_h, out_w, stages, tuple(temporal) if stages & 0x2000 else None,
                                                        "bgr" if nv12 is None else "nv12", matrix, lens, depth, depth_auto,
                                                        (lambda k, gc: print("frame %d: gain %.6g conv %.6g" % (k, gc[0], gc[1])))
-                                                       if depth_auto is not None else None, packing):
+                                                       if depth_auto is not None else None, packing,
+                                                       layout=None if quilt is None else (1,) + quilt):
         video.write_outputs(out_dir, k, dl, dr, inter)
         n += 1
     dt = time.perf_counter() - t0
