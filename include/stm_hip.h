@@ -84,11 +84,13 @@ int         stm_prof_read(const char *kernel, float *total_ms);
  * column prefix, with the vote codes packed by the compaction kernel) instead of the fused front kernel, the fused row kernel and
  * the column sums inside the compaction kernel, 700 = the cross-arm walk with its bookkeeping in vector registers (round 3) instead
  * of in lane masks and scalar row offsets, 10000000 = the vertical passes on the LDS-ring
- * kernel of round 3 instead of the register-ring kernel (stm_kernels_aggv.hip), 100000000 = the last horizontal pass + WTA on the
+ * kernel of round 3 instead of the register-ring kernel (stm_kernels_aggv.hip), 20000000 = the register-ring kernel with a strip of
+ * four columns per wave and the PQ volume layout end to end instead of one column per wave on pixel-major volumes (48 < num_disp <= 64
+ * only; elsewhere the default already is the former), 100000000 = the last horizontal pass + WTA on the
  * LDS row walk instead of the register-ring kernel (stm_kernels_aggh.hip), 1000000000 = the window tables of the two register-ring
  * kernels from their own launches instead of from the cross-arm kernel.  Every accepted variant produces identical
  * results (tests/test_gpu_parity.py::test_device_frame_agg_variants, tests/test_gpu_image_chain.py,
- * tests/test_gpu_cross_arms.py).  The
+ * tests/test_gpu_cross_arms.py, tests/test_gpu_px_layout.py).  The
  * digit N00000 (timing experiments that skip parts of kernels) is ignored here: it exists only in libstm_hip_timing.so,
  * a separate build of the same sources with -DSTM_TIMING (csrc/Makefile, `make timing`). */
 void        stm_set_agg_variant(int v);

@@ -229,7 +229,8 @@ void launch_cross_arms(const uint32_t *packed, u8 *up, u8 *down, u8 *left, u8 *r
 void launch_cross_arms2(int nviews, const uint32_t *const *packed, u8 *const *up, u8 *const *down, u8 *const *left,
                         u8 *const *right, float ucd, float lcd, int usd, int lsd, int H, int W, const uint32_t *const *wide_ready = nullptr,
                         uint32_t *htab = nullptr, // htab: also build stm_k_pq_hsr's horizontal window table (aggh_table_dwords(nviews, H, W))
-                        uint32_t *vtab = nullptr, int vrec = 0, int vtop = -1); // + vtab: and stm_k_pq_v12r's vertical one (aggm_frame_vtab_dwords)
+                        uint32_t *vtab = nullptr, int vrec = 0, int vtop = -1, // + vtab: and the vertical one of the register-ring kernel (aggm_frame_vtab_dwords)
+                        bool vcol = false);                                    // vcol: in stm_k_pq_v12r's per-column layout (stm_hwin.h)
 void launch_agg_h(Vol in, Vol out, const u8 *armL, const u8 *armR, int D, int H, int W);
 void launch_agg_v(Vol in, Vol out, const u8 *armU, const u8 *armD, int D, int H, int W, int usd);
 void launch_agg_h2(Vol in_a, Vol out_a, const u8 *armL_a, const u8 *armR_a, Vol in_b, Vol out_b, const u8 *armL_b, const u8 *armR_b,
@@ -333,9 +334,14 @@ size_t pq_volume_floats(int D, int H, int W);
 bool aggm_supports(int usd, int H, int W);
 void launch_aggm_frame(const uint32_t *const *pk, const uint32_t *const *cen, const float *lut, float *const *vol_a, float *const *vol_b,
                        const u8 *const *armU, const u8 *const *armD, const u8 *const *armL, const u8 *const *armR, float *const *disp,
-                       int D, int zd, int H, int W, int usd, bool keep_volume = false, uint32_t *htab_ready = nullptr, uint32_t *vtab_ready = nullptr);
+                       int D, int zd, int H, int W, int usd, bool keep_volume = false, uint32_t *htab_ready = nullptr, uint32_t *vtab_ready = nullptr,
+                       bool v2_read_later = false); // v2_read_later: a later stage reads vol_a as a PQ volume (no PX layout)
 size_t aggm_frame_htab_dwords(int D, int H, int W, int usd, bool keep_volume);
-size_t aggm_frame_vtab_dwords(int H, int W, int usd, int *rec, int *top); // the vertical table in the register-ring kernel's static layout, or 0
+// the vertical table in a register-ring kernel's static layout, or 0; *col: the per-column layout of the PX fast path (aggm_frame_px)
+size_t aggm_frame_vtab_dwords(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later, int *rec, int *top, bool *col);
+// whether the frame's two intermediate volumes take the pixel-major layout PX (float index ((y 4G + x) 64 + d), DESIGN.md
+// section 4): all three register / streaming kernels run, 48 < D <= 64, WTA, and nobody reads a volume afterwards
+bool aggm_frame_px(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later);
 // ca_cross / d_ca_cross of one volume in the caller's layout on the matrix-pipe kernels; `out` may be `in`.  Returns false, with
 // `out` untouched, when the volume holds an infinite, NaN or denormal element (one host read-back of a flag): the caller runs
 // the vector-ALU kernels instead.  aggm_stage_bytes: what it carves from the current Workspace scope.
@@ -345,11 +351,14 @@ size_t aggm_stage_bytes(int D, int H, int W, int usd);
 bool aggh_supports(int usd, int D); // stm_kernels_aggh.hip: last horizontal pass + WTA with the row's window range in registers
 size_t aggh_table_dwords(int nviews, int H, int W);
 void launch_hwin_table(PQViews &v, int nviews, uint32_t *tab, int H, int W); // (the frame path builds the table inside stm_k_cross_arms: launch_cross_arms2's htab)
-void launch_pq_hsr(PQViews &v, int nviews, const uint32_t *tab, int D, int zd, int H, int W);
+void launch_pq_hsr(PQViews &v, int nviews, const uint32_t *tab, int D, int zd, int H, int W, bool px = false); // px: vol_a in the PX layout
 bool aggv_supports(int usd);
 int aggv_table_top();
 int aggv_table_rec();
-void launch_pq_v12r(PQViews &v, int nviews, const uint32_t *tab, int rec, int H, int W, int G, int NC);
+void launch_pq_v12q(PQViews &v, int nviews, const uint32_t *tab, int rec, int H, int W, int G, int NC); // PQ volumes, a strip of four columns per wave
+void launch_pq_v12r(PQViews &v, int nviews, const uint32_t *tab, int H, int W, int G);                  // PX volumes, one column per wave; tab: vcol_build's records
+void launch_vcol_table(PQViews &v, int nviews, uint32_t *tab, int H, int W);                            // that table from the arm planes (aggv_col_table_dwords)
+size_t aggv_col_table_dwords(int nviews, int H, int W);
 void launch_to_pq(Vol in, float *pq, int D, int H, int W, uint32_t *odd = nullptr); // stm_kernels_hslo.hip; odd: see stm_k_to_pq
 void launch_from_pq(const float *pq, Vol out, int D, int H, int W); // stm_kernels_aggm.hip
 // HSLO (stm_kernels_hslo.hip)

@@ -15,24 +15,17 @@ template <int N> __device__ __forceinline__ int hr_row_ror(int v) { return __bui
 
 template <int N> __device__ __forceinline__ uint32_t hr_row_shr(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x110 + N, 0xf, 0xf, false); }
 
-// lane l of the wave = pixel x0 + l of image row y (x0 a multiple of 64), aL / aR its horizontal arms (any value for x >= W).
-// A DPP row of 16 lanes per tile.  A window toggles its pixel's bit at its first step and at the step after its last; the
-// running XOR over the steps gives every step's set of pixels, and four consecutive steps are one group's 64-bit mask
-// (d_ca_cross_sum.cu:277-289).  ev: 4 x 96 dwords of LDS owned by this wave.  `tab`: records of this view.
-static __device__ __forceinline__ void hwin_build(uint32_t *__restrict__ tab, uint32_t *ev4, int y, int x0, int aL, int aR, int W, int nTx)
+// One record per DPP row of 16 lanes.  Lane m of the row owns the window [s0, s0 + nn) (nn = 0: none) along the walk's axis,
+// R0 (a multiple of 4) is the first step of the tile's range, every window lies inside [R0, R0 + 88).  A window toggles its
+// lane's bit at its first step and at the step after its last; the running XOR over the steps gives every step's set of
+// lanes, and four consecutive steps are one group's 64-bit mask.  ev: 96 dwords of LDS owned by this row of lanes.  dst: the
+// record, or nullptr (nothing is stored).
+static __device__ __forceinline__ void win16_build(uint32_t *__restrict__ dst, uint32_t *ev, int R0, int s0, int nn)
 {
-    const int l = threadIdx.x & 63, r = l >> 4, m = l & 15;
-    const int x = x0 + l, t = x >> 4;
-    uint32_t *ev = ev4 + r * 96;
-    int s0 = 0, nn = 0;
-    if (x < W) { // (a tile past the row: no windows, nothing is stored)
-        s0 = x - aL;
-        nn = aL + aR;
-    }
+    const int m = threadIdx.x & 15;
     int lo = nn ? s0 : 0x7fffffff, hi = nn ? s0 + nn : -0x7fffffff; // over the tile's 16 lanes; every lane gets the result
     lo = min(lo, hr_row_ror<8>(lo)); lo = min(lo, hr_row_ror<4>(lo)); lo = min(lo, hr_row_ror<2>(lo)); lo = min(lo, hr_row_ror<1>(lo));
     hi = max(hi, hr_row_ror<8>(hi)); hi = max(hi, hr_row_ror<4>(hi)); hi = max(hi, hr_row_ror<2>(hi)); hi = max(hi, hr_row_ror<1>(hi));
-    const int R0 = 16 * t - HR_TOP; // a multiple of 4
     const int K0 = hi > lo ? (lo & ~3) : 0, n = hi > lo ? (hi - K0 + 3) >> 2 : 0; // n <= 22
     const int q0 = n ? (K0 - R0) >> 2 : 0;
 #pragma unroll
@@ -54,10 +47,9 @@ static __device__ __forceinline__ void hwin_build(uint32_t *__restrict__ tab, ui
     const uint32_t before = hr_row_shr<1>(tot); // XOR of all steps in front of this lane's six
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int i = 0; i < 6; ++i) ev[6 * m + i] = e[i] ^ before; // the step's set of pixels
+    for (int i = 0; i < 6; ++i) ev[6 * m + i] = e[i] ^ before; // the step's set of lanes
     __builtin_amdgcn_wave_barrier();
-    if (t >= nTx) return;
-    uint32_t *dst = tab + ((size_t)y * nTx + t) * HR_REC;
+    if (!dst) return;
     if (m < 2) dst[m] = m == 0 ? (uint32_t)q0 : (uint32_t)n;
 #pragma unroll
     for (int j = m; j < HR_NG; j += 16)
@@ -66,6 +58,31 @@ static __device__ __forceinline__ void hwin_build(uint32_t *__restrict__ tab, ui
                                           ((unsigned long long)ev[4 * j + 2] << 32) | ((unsigned long long)ev[4 * j + 3] << 48);
             *(unsigned long long *)(dst + 8 + 2 * (HR_NG - n + j)) = mk; // the sweep's last group in slot 21
         }
+}
+
+// lane l of the wave = pixel x0 + l of image row y (x0 a multiple of 64), aL / aR its horizontal arms (any value for x >= W).
+// A DPP row of 16 lanes per tile: lane 16 r + m = pixel m of the wave's r-th tile, whose window is [x - armL, x + armR)
+// (d_ca_cross_sum.cu:277-289).  ev4: 4 x 96 dwords of LDS owned by this wave.  `tab`: records of this view.
+static __device__ __forceinline__ void hwin_build(uint32_t *__restrict__ tab, uint32_t *ev4, int y, int x0, int aL, int aR, int W, int nTx)
+{
+    const int l = threadIdx.x & 63, r = l >> 4;
+    const int x = x0 + l, t = x >> 4;
+    int s0 = 0, nn = 0;
+    if (x < W) { // (a tile past the row: no windows, nothing is stored)
+        s0 = x - aL;
+        nn = aL + aR;
+    }
+    win16_build(t < nTx ? tab + ((size_t)y * nTx + t) * HR_REC : nullptr, ev4 + r * 96, 16 * t - HR_TOP, s0, nn);
+}
+
+// The vertical twin (stm_k_pq_v12r, stm_kernels_aggv.hip: one column per wave): the same record per (tile of 16 rows, column),
+// the walk's axis being y.  Lane 16 c + m = row 16 u + m of column x0 + c, s0 / nn its window [y - armU, y + armD) (nn = 0: none;
+// d_ca_cross_sum.cu:172-173,189-194): mask bit 16 a + m of a group = row m has the group's row a in its window.
+// `tile`: the records of (view, tile u), column x at + x * HR_REC; every column in [x0, x0 + 4) must exist there.
+static __device__ __forceinline__ void vcol_build(uint32_t *__restrict__ tile, uint32_t *ev4, int u, int x0, int s0, int nn)
+{
+    const int r = (threadIdx.x & 63) >> 4;
+    win16_build(tile + (size_t)(x0 + r) * HR_REC, ev4 + r * 96, 16 * u - HR_TOP, s0, nn);
 }
 
 // ---- the vertical window table (stm_k_vwin_table, stm_kernels_aggm.hip; layout: DESIGN.md section 3) -- one record, one wave.

@@ -60,8 +60,9 @@ struct ArmsArgs {
     const uint32_t *img[2]; // wide pixels
     u8 *up[2], *down[2], *left[2], *right[2];
     uint32_t *htab; // MODE >= 1: the horizontal window table of stm_k_pq_hsr, records of view 0 then view 1 (stm_hwin.h)
-    uint32_t *vtab; // MODE 2: the vertical window table of stm_k_pq_v12r (static layout), `vrec` dwords per record, `vtop` = its range's reach
+    uint32_t *vtab; // MODE 2: the vertical window table of a register-ring kernel (static layout), `vrec` dwords per record, `vtop` = its range's reach
     int vrec, vtop;
+    int vcol;       // MODE 2: one record per column (stm_k_pq_v12r, vcol_build) instead of one per group of four (stm_k_pq_v12q, vwin_build)
 };
 
 // The walk with vector min / select bookkeeping (round 3, above): behind stm_set_agg_variant(700), for comparison with the one below.
@@ -260,8 +261,8 @@ static __device__ __forceinline__ void cross_arms_body(const ArmsArgs &a, uint32
         a.left[v][p] = (u8)arm[2];
         a.right[v][p] = (u8)arm[3];
     }
+    __shared__ uint32_t ev_all[MODE == 2 ? 16 : 4][4 * 96]; // (MODE 0: unused)
     if (HTAB) {
-        __shared__ uint32_t ev_all[MODE == 2 ? 16 : 4][4 * 96];
         const int nTx = (W + 15) >> 4;
         if (yr < H) // (wave-uniform)
             hwin_build(a.htab + (size_t)v * H * nTx * HR_REC, ev_all[wv_], yr, xr & ~63, arm[2], arm[3], W, nTx);
@@ -277,7 +278,10 @@ static __device__ __forceinline__ void cross_arms_body(const ArmsArgs &a, uint32
         if (gg < G) { // (wave-uniform)
             const int b = l >> 4, i = l & 15;
             const int aU = s_u[i][4 * wv_ + b], aD = s_d[i][4 * wv_ + b];
-            vwin_build(a.vtab + ((size_t)(v * nT + u) * G + gg) * a.vrec, ev_v[wv_], u, a.vtop, blockIdx.y * 16 + i - aU, aU + aD);
+            if (a.vcol) // (uniform) the wave's four columns, one record each; the wave's own event slots are free again
+                vcol_build(a.vtab + (size_t)(v * nT + u) * (4 * G) * HR_REC, ev_all[wv_], u, 4 * gg, blockIdx.y * 16 + i - aU, aU + aD);
+            else
+                vwin_build(a.vtab + ((size_t)(v * nT + u) * G + gg) * a.vrec, ev_v[wv_], u, a.vtop, blockIdx.y * 16 + i - aU, aU + aD);
         }
     }
 }
@@ -308,7 +312,7 @@ static uint32_t wide_threshold(float t)
 // nviews = 1 or 2: both views of a frame share the launch.  packed[] = BGRX planes (launch_pack_bgrx).
 void launch_cross_arms2(int nviews, const uint32_t *const *packed, u8 *const *up, u8 *const *down, u8 *const *left,
                         u8 *const *right, float ucd, float lcd, int usd, int lsd, int H, int W, const uint32_t *const *wide_ready,
-                        uint32_t *htab, uint32_t *vtab, int vrec, int vtop)
+                        uint32_t *htab, uint32_t *vtab, int vrec, int vtop, bool vcol)
 {
     ArmsArgs a;
     const int n = H * W;
@@ -333,6 +337,7 @@ void launch_cross_arms2(int nviews, const uint32_t *const *packed, u8 *const *up
     a.vtab = vtab;
     a.vrec = vrec;
     a.vtop = vtop;
+    a.vcol = vcol ? 1 : 0;
     // 700 (and planes of 2 GiB and more, whose row offsets do not fit the scalar walk's 32 bits): the walk with vector min / select bookkeeping
     const bool vmin = (agg_variant() / 100) % 10 == 7 || (size_t)H * W * 4 >= ((size_t)1 << 31);
     const uint32_t tg_far = wide_threshold(ucd), tg_near = wide_threshold(lcd);

@@ -49,7 +49,10 @@ __global__ __launch_bounds__(256) void stm_k_hwin_table(PQViews v, uint32_t *__r
 //   range start, s29 ring size, s30 ring index of the running block, s[36:83] the 24 mask pairs of the tile (pair p = block p),
 //   s84 / s85 first group and groups of the tile's sweep, s[86:87] the next tile's, s[88:89] mask address of block 0, s90 entry
 //   block, s[92:93] jump target, s[94:99] temporaries / compare masks.
-template <int EXP> // timing experiments (libstm_hip_timing.so only; results invalid): 1 no sweeps, 2 no volume loads, 4 no WTA, 8 no mask loads
+// PX: the volume in the pixel-major layout of the frame's fast path (float index ((y 4G + x) 64 + d), NC == 4): a pixel's 64
+// hypotheses are one register (lane = d), a group is four buffer_load_dword of 256 contiguous bytes each.  Four times the loads:
+// the waits below count 16 per step instead of 4.
+template <int EXP, bool PX> // timing experiments (libstm_hip_timing.so only; results invalid): 1 no sweeps, 2 no volume loads, 4 no WTA, 8 no mask loads
 __global__ __launch_bounds__(64, 3) void stm_k_pq_hsr(PQViews pv, const uint32_t *__restrict__ htab, int D, int zd, int H, int W, int G, int NC, int nTx,
                                                       int parts, int nviews)
 {
@@ -64,7 +67,7 @@ __global__ __launch_bounds__(64, 3) void stm_k_pq_hsr(PQViews pv, const uint32_t
     const uint32_t *hrec = htab + ((size_t)(view * H + y) * nTx + t0) * HR_REC; // record of tile t0; tile t at + (t - t0) * HR_REC
     const uint32_t cstride = (uint32_t)H * (uint32_t)G * 256u;                    // bytes between chunks
     const uint32_t nrec = (uint32_t)NC * cstride;                                // bytes of the volume (chunks past the last: out of range -> zeros)
-    const int vload = (l >> 4) * (int)cstride + (l & 15) * 16;                   // lane 16 b + n reads chunk b, hypothesis n of a group
+    const int vload = PX ? 4 * l : (l >> 4) * (int)cstride + (l & 15) * 16;      // lane 16 b + n reads chunk b, hypothesis n of a group (PX: of a pixel)
     const int vn = l & 15;
     const int vst = (l & 15) == 0 ? (l >> 4) * 16 : 0x7ffffff0;                   // lane n == 0 of a pixel quad stores its four pixels
     // hypotheses d >= D (padding of the last chunk, chunks past the last) must never win: their costs become FLT_MAX
@@ -75,6 +78,7 @@ __global__ __launch_bounds__(64, 3) void stm_k_pq_hsr(PQViews pv, const uint32_t
     const float zdf = (float)zd;
     asm volatile(R"ASM(
         .set HR_EXP, %[exp]
+        .set HR_PX, %[px]
         ; ---------------------------------------------------------------- macros
         ; one block of a sweep: four MFMAs on one pixel group (its four registers = four window steps), the A operand (lanes 16 a + m =
         ; step a, pixel m) shared through CBSZ / ABID.  p = block index, acur / anxt = the A registers of this / the next block
@@ -185,9 +189,19 @@ HR_end_%=_\@:
         s_max_i32 s98, s97, 0
         s_min_i32 s98, s98, %[Gm1]
         s_add_u32 s98, s98, %[yG]
+        .if HR_PX
+        s_lshl_b32 s98, s98, 10               ; pixel y 4G + 4 g, 256 bytes each
+        .if (HR_EXP & 2) == 0
+        buffer_load_dword v[\lb+4*\k], %[vload], s[16:19], s98 offen
+        buffer_load_dword v[\lb+4*\k+1], %[vload], s[16:19], s98 offen offset:256
+        buffer_load_dword v[\lb+4*\k+2], %[vload], s[16:19], s98 offen offset:512
+        buffer_load_dword v[\lb+4*\k+3], %[vload], s[16:19], s98 offen offset:768
+        .endif
+        .else
         s_lshl_b32 s98, s98, 8
         .if (HR_EXP & 2) == 0
         buffer_load_dwordx4 v[\lb+4*\k:\lb+4*\k+3], %[vload], s[16:19], s98 offen
+        .endif
         .endif
         s_add_i32 s97, s97, 1
         .endm
@@ -239,7 +253,11 @@ HR_end_%=_\@:
         s_cmp_eq_u32 s24, %[t0]
         s_cbranch_scc1 HR_nomove_%=_\@
         .if (HR_EXP & 2) == 0
+        .if HR_PX
+        s_waitcnt vmcnt(24)                   ; issued since: 4 stores, 16 loads, 4 stores
+        .else
         s_waitcnt vmcnt(12)                   ; issued since: 4 stores, 4 loads, 4 stores
+        .endif
         .endif
         s_add_u32 s96, s26, 72                ; group 4 t + 9 = range start + 18 groups
         s_sub_u32 s31, s96, s29
@@ -401,7 +419,11 @@ HR_nofix_%=_\@:
         buffer_store_dword v142, v146, s[20:23], 0 offen
         s_mov_b32 s22, %[W4]
         .if (HR_EXP & 2) == 0
+        .if HR_PX
+        s_waitcnt vmcnt(20)                   ; the ring is in (behind it: 16 loads, 4 stores)
+        .else
         s_waitcnt vmcnt(8)                    ; the ring is in
+        .endif
         .endif
 HR_loop_%=:
         HR_STEP 88
@@ -425,7 +447,7 @@ HR_done_%=:
         .purgem HR_STEP
         )ASM"
                  :
-                 : [exp] "n"(EXP), [in] "s"(in), [disp] "s"(disp_row), [hrec_lo] "s"((uint32_t)(uintptr_t)hrec), [hrec_hi] "s"((uint32_t)((uintptr_t)hrec >> 32)),
+                 : [exp] "n"(EXP), [px] "n"(PX ? 1 : 0), [in] "s"(in), [disp] "s"(disp_row), [hrec_lo] "s"((uint32_t)(uintptr_t)hrec), [hrec_hi] "s"((uint32_t)((uintptr_t)hrec >> 32)),
                    [yG] "s"(yG), [Gm1] "s"(Gm1), [nrec] "s"(nrec), [W4] "s"(W4), [t0] "s"(t0), [t1] "s"(t1), [zdf] "s"(zdf),
                    [vload] "v"(vload), [vn] "v"(vn), [vst] "v"(vst), [vb0] "v"(vbig[0]),
                    [vb1] "v"(vbig[1]), [vb2] "v"(vbig[2]), [vb3] "v"(vbig[3])
@@ -458,7 +480,7 @@ void launch_hwin_table(PQViews &v, int nviews, uint32_t *tab, int H, int W)
 }
 
 // last horizontal pass + WTA, vol_a -> disparities, for `nviews` views
-void launch_pq_hsr(PQViews &v, int nviews, const uint32_t *tab, int D, int zd, int H, int W)
+void launch_pq_hsr(PQViews &v, int nviews, const uint32_t *tab, int D, int zd, int H, int W, bool px)
 {
     const int G = (W + 3) / 4, NC = (D + 15) / 16, nTx = cdiv(W, 16);
     // parts per row: about ten tiles per wave measured best at 1080p (0.275 ms against 0.303 with 30 and 0.342 with 5: a wave's
@@ -466,23 +488,29 @@ void launch_pq_hsr(PQViews &v, int nviews, const uint32_t *tab, int D, int zd, i
     int parts = (nTx + 5) / 10;
     parts = parts < 1 ? 1 : parts;
     const dim3 grid(nviews * H * parts);
+#define STM_HSR_LAUNCH(E, GRID)                                                                                                       \
+    {                                                                                                                                 \
+        if (px) STM_LAUNCH((stm_k_pq_hsr<E, true>), GRID, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews);      \
+        else STM_LAUNCH((stm_k_pq_hsr<E, false>), GRID, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews);        \
+    }
 #ifdef STM_TIMING
     if (const char *e = getenv("STM_HSR_PARTS")) parts = atoi(e);
     const dim3 gridt(nviews * H * parts);
     switch (timing_knobs()) {
-    case 1: STM_LAUNCH(stm_k_pq_hsr<1>, gridt, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews); break;
-    case 2: STM_LAUNCH(stm_k_pq_hsr<2>, gridt, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews); break;
-    case 3: STM_LAUNCH(stm_k_pq_hsr<3>, gridt, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews); break;
-    case 4: STM_LAUNCH(stm_k_pq_hsr<4>, gridt, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews); break;
-    case 5: STM_LAUNCH(stm_k_pq_hsr<5>, gridt, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews); break;
-    case 6: STM_LAUNCH(stm_k_pq_hsr<6>, gridt, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews); break;
-    case 7: STM_LAUNCH(stm_k_pq_hsr<7>, gridt, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews); break;
-    case 8: STM_LAUNCH(stm_k_pq_hsr<8>, gridt, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews); break;
-    default: STM_LAUNCH(stm_k_pq_hsr<0>, gridt, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews); break;
+    case 1: STM_HSR_LAUNCH(1, gridt); break;
+    case 2: STM_HSR_LAUNCH(2, gridt); break;
+    case 3: STM_HSR_LAUNCH(3, gridt); break;
+    case 4: STM_HSR_LAUNCH(4, gridt); break;
+    case 5: STM_HSR_LAUNCH(5, gridt); break;
+    case 6: STM_HSR_LAUNCH(6, gridt); break;
+    case 7: STM_HSR_LAUNCH(7, gridt); break;
+    case 8: STM_HSR_LAUNCH(8, gridt); break;
+    default: STM_HSR_LAUNCH(0, gridt); break;
     }
 #else
-    STM_LAUNCH(stm_k_pq_hsr<0>, grid, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews);
+    STM_HSR_LAUNCH(0, grid);
 #endif
+#undef STM_HSR_LAUNCH
     STM_CHECK_LAUNCH();
 }
 

@@ -582,7 +582,11 @@ __global__ __launch_bounds__(64 * NW, (3 * NW) / 4) void stm_k_pq_hs(PQViews v, 
 // between the two barriers that end the segment.  D <= 64 (one chunk set).
 // C(d, x) = rho_ad(|own(x) - other(x')|_1) + rho_c(ham(cen_own(x), cen_other(x'))), x' = clamp(x + sgn (d - zd)) (SURVEY A-Q6);
 // hypotheses d >= D and pixels outside the row are 0.
-template <int NW>
+// PX: the output volume in the pixel-major layout PX of the frame's fast path (float index ((y 4G + x) 64 + d), 256 contiguous
+// bytes per pixel; NC == 4): sixteen dword stores straight from the accumulators, each four 64-byte pieces.  (Transposing the
+// accumulators first, as stm_k_pq_v12r does, so that every store writes one pixel's 256 bytes, measured 0.010 ms slower:
+// 0.377 against 0.367 ms, profiles/vcol_store_forms.json.)
+template <int NW, bool PX>
 __global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void stm_k_pq_hc(PQViews v, int D, int zd, int H, int W, int G, int NC, int HG, int nseg,
                                                                      int spl, const float *__restrict__ lut_g, int pad, int dbg)
 {
@@ -618,6 +622,8 @@ __global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void stm_k_pq_hc(PQViews v, 
 #pragma unroll
     for (int cl = 0; cl < 4; ++cl)
         rout[cl] = __builtin_amdgcn_make_buffer_rsrc((void *)(out + ((size_t)min(c0 + cl, NC - 1) * H + y) * G * 16), 0, c0 + cl < NC ? rowbytes : 0u, 0x00020000);
+    // PX: the row's 4 G pixels of 256 bytes (pixels past them are out of range, dropped)
+    const __amdgpu_buffer_rsrc_t rpx = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)y * G * 64), 0, PX ? 4u * rowbytes : 0u, 0x00020000);
     // pixels for the costs of the groups that start at shifted group A0 (group = A0 - HG): own image NEWPX pixels from
     // x0 = 4 (A0 - HG), other image the same +- pad, both clamped to the row (clamp-to-edge, d_ci_ad.cu:102)
 #define STM_HC_FETCH(A0)                                                                           \
@@ -771,10 +777,18 @@ __global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void stm_k_pq_hc(PQViews v, 
                 for (int i = 0; i < 16; ++i) acc[i] = 0.f;
             }
             // registers 4b..4b+3 of lane 16q + n = out[pixels X0 + 4q .. +3][hypothesis 16 b + n]
+            if (!PX) {
 #pragma unroll
-            for (int cl = 0; cl < 4; ++cl) { // groups past the row, chunks past the last: out of range, dropped
-                const f4 o = {acc[4 * cl], acc[4 * cl + 1], acc[4 * cl + 2], acc[4 * cl + 3]};
-                if (!STM_DBG(dbg, 4)) STM_BSTORE(rout[cl], (X0 >> 2) * 256 + l * 16, o);
+                for (int cl = 0; cl < 4; ++cl) { // groups past the row, chunks past the last: out of range, dropped
+                    const f4 o = {acc[4 * cl], acc[4 * cl + 1], acc[4 * cl + 2], acc[4 * cl + 3]};
+                    if (!STM_DBG(dbg, 4)) STM_BSTORE(rout[cl], (X0 >> 2) * 256 + l * 16, o);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) // register 4 b + i of lane 16 q + n = pixel X0 + 4 q + i, hypothesis 16 b + n
+                    if (!STM_DBG(dbg, 4))
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, (float)acc[k]), rpx,
+                                                              (X0 + 4 * lb + (k & 3)) * 256 + (16 * (k >> 2) + dd) * 4, 0, 2);
             }
         }
         if (more) STM_HC_COSTS((sq + 1) & 1, 4 * NW * (sq + 1) + NG - 4 * NW)
@@ -1112,11 +1126,47 @@ void launch_from_pq(const float *pq, Vol out, int D, int H, int W)
     STM_CHECK_LAUNCH();
 }
 
+// Which cost-fusing streaming kernel (stm_k_pq_hc) the first pass of a chain that starts from the images runs: its waves per
+// block (12: 192-pixel segments, 8: 128-pixel segments for large D), or 0 when another kernel runs.
+static int hc_waves(int D, int zd, int usd)
+{
+    constexpr int NW = 8, NWC = 12;
+    const int NC = (D + 15) / 16;
+    const int HG = ((usd + 3) / 4 + 2) & ~1, NG = 4 * NW + 2 * HG, NGc = 4 * NWC + 2 * HG;
+    int pad = zd > D - 1 - zd ? zd : D - 1 - zd;
+    pad = (pad < 0 ? 0 : pad) + 15;
+    const size_t smem_hc = (size_t)4 * NGc * 256 + 16 * NWC * 4 + 8 * NWC + (size_t)(2 * 16 * NWC + 2 * (16 * NWC + 2 * pad)) * 8 + (768 + 72) * 4;
+    const size_t smem_hc8 = (size_t)4 * NG * 256 + 16 * NW * 4 + 8 * NW + (size_t)(2 * 16 * NW + 2 * (16 * NW + 2 * pad)) * 8 + (768 + 72) * 4;
+    const bool hc_ok = (agg_variant() / 1000000) % 10 != 1 && (agg_variant() / 1000) % 10 == 0 && (NC <= 4 || (agg_variant() / 10) % 10 != 2);
+    if (hc_ok && smem_hc <= 80 * 1024 && 16 * NWC + 2 * pad <= 64 * NWC) return NWC;
+    if (hc_ok && smem_hc8 <= 80 * 1024 && 16 * NW + 2 * pad <= 64 * NW) return NW;
+    return 0;
+}
+
+// PX: the frame's two intermediate volumes pixel-major, float index ((y 4G + x) 64 + d) -- a column's 64 hypotheses are 256
+// contiguous bytes, so that stm_k_pq_v12r's waves can own ONE column each.  Only when all three
+// register / streaming kernels run (the cost-fusing stm_k_pq_hc, stm_k_pq_v12r, stm_k_pq_hsr), NC == 4, and the chain ends in
+// WTA with nobody reading a volume afterwards; 20000000: the PQ layout and the four-column kernel stm_k_pq_v12q end to end.
+static bool chain_px(bool from_costs, bool wta, int D, int zd, int usd)
+{
+    if (usd > 255) usd = 255;
+    const int NC = (D + 15) / 16;
+    return from_costs && wta && NC == 4 && aggv_supports(usd) && (agg_variant() / 10000000) % 10 == 0 && aggh_supports(usd, D) &&
+           (agg_variant() / 100000000) % 10 != 1 && hc_waves(D, zd, usd) != 0;
+}
+bool aggm_frame_px(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later)
+{
+    (void)H;
+    (void)W;
+    return !v2_read_later && chain_px(true, !keep_volume, D, zd, usd);
+}
+
 // The aggregation chain on PQ volumes for `nviews` views (1 or 2).
 //   from_costs: the first horizontal pass computes the initial costs itself (images -> vol_b), else it reads vol_a;
 //   then both vertical passes (vol_b -> vol_a); then the last horizontal pass, vol_a -> disparities (wta) or -> vol_b.
+//   px: the two intermediate volumes in the PX layout (chain_px holds; the caller's vtab_ready, if any, is in the per-column layout)
 static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const float *lut, int D, int zd, int H, int W, int usd,
-                       uint32_t *htab_ready = nullptr, uint32_t *vtab_ready = nullptr)
+                       uint32_t *htab_ready = nullptr, uint32_t *vtab_ready = nullptr, bool px = false)
 {
     const int G = (W + 3) / 4, NC = (D + 15) / 16;
     if (usd > 255) usd = 255;
@@ -1139,14 +1189,15 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
     const int rec = regs ? aggv_table_rec() : 8 + 8 * ((2 * usd + 21) / 4 + 2); // header + the longest sweep + one quad of read-ahead
     const int LAG = (UQ + TS - 1) / TS + 1;
     const int RQ1 = (TS + 2 * UQ) / 4, RQ2 = (TS * (LAG + 1) + UQ) / 4;
-    uint32_t *vtab = regs && vtab_ready ? vtab_ready : Workspace::get<uint32_t>((size_t)nviews * nT * G * rec);
+    uint32_t *vtab = regs && vtab_ready ? vtab_ready : Workspace::get<uint32_t>(px ? aggv_col_table_dwords(nviews, H, W) : (size_t)nviews * nT * G * rec);
     // round 4: the row's window range in registers (stm_kernels_aggh.hip); 100000000: the LDS row walk stm_k_pq_hs
     const bool hregs = wta && aggh_supports(usd, D) && (agg_variant() / 100000000) % 10 != 1;
     uint32_t *htab = !hregs ? nullptr : htab_ready ? htab_ready : Workspace::get<uint32_t>(aggh_table_dwords(nviews, H, W));
     {
         if (!(regs && vtab_ready)) {
             ProfScope p("pq_vtab");
-            STM_LAUNCH(stm_k_vwin_table, dim3(cdiv(G, 4), nT, nviews), dim3(256), 0, stream(), v, vtab, rec, H, W, G, nT, regs ? aggv_table_top() : -1);
+            if (px) launch_vcol_table(v, nviews, vtab, H, W);
+            else STM_LAUNCH(stm_k_vwin_table, dim3(cdiv(G, 4), nT, nviews), dim3(256), 0, stream(), v, vtab, rec, H, W, G, nT, regs ? aggv_table_top() : -1);
             STM_CHECK_LAUNCH();
         }
         if (hregs && !htab_ready) {
@@ -1170,16 +1221,23 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
         const size_t smem_hc = (size_t)4 * NGc * 256 + 16 * NWC * 4 + 8 * NWC + (size_t)(2 * 16 * NWC + 2 * (16 * NWC + 2 * pad)) * 8 + (768 + 72) * 4;
         const int nsegc = cdiv(W, 16 * NWC);
         const size_t smem_hc8 = (size_t)4 * NG * 256 + 16 * NW * 4 + 8 * NW + (size_t)(2 * 16 * NW + 2 * (16 * NW + 2 * pad)) * 8 + (768 + 72) * 4;
-        const bool hc_ok = fuse_cost && (agg_variant() / 1000) % 10 == 0 && (NC <= 4 || (agg_variant() / 10) % 10 != 2);
-        if (hc_ok && smem_hc <= 80 * 1024 && 16 * NWC + 2 * pad <= 64 * NWC) {
+        const int hcw = fuse_cost ? hc_waves(D, zd, usd) : 0;
+#define STM_HC_LAUNCH(NWX, PXS, GRID, SMEM, NSEG, SPL)                                                                                      \
+    {                                                                                                                                     \
+        allow_lds_m((const void *)stm_k_pq_hc<NWX, PXS>, SMEM);                                                                            \
+        STM_LAUNCH((stm_k_pq_hc<NWX, PXS>), GRID, dim3(64 * NWX), SMEM, stream(), v, D, zd, H, W, G, NC, HG, NSEG, SPL, lut, pad, dbgh);    \
+    }
+        if (hcw == NWC) {
             // streaming row walk (the staged pixels fit one per thread); 2000: one block per segment as in round 2
             const int splc = nsegc > 24 ? cdiv(nsegc, 16) : 1;
-            allow_lds_m((const void *)stm_k_pq_hc<NWC>, smem_hc);
-            STM_LAUNCH((stm_k_pq_hc<NWC>), dim3(nviews * H * splc), dim3(64 * NWC), smem_hc, stream(), v, D, zd, H, W, G, NC, HG, nsegc, splc, lut, pad, dbgh);
-        } else if (hc_ok && smem_hc8 <= 80 * 1024 && 16 * NW + 2 * pad <= 64 * NW) {
+            const dim3 grid(nviews * H * splc);
+            if (px) STM_HC_LAUNCH(NWC, true, grid, smem_hc, nsegc, splc)
+            else STM_HC_LAUNCH(NWC, false, grid, smem_hc, nsegc, splc)
+        } else if (hcw == NW) {
             // large D (more staged pixels): 128-pixel segments keep two blocks per CU
-            allow_lds_m((const void *)stm_k_pq_hc<NW>, smem_hc8);
-            STM_LAUNCH((stm_k_pq_hc<NW>), dim3(nviews * H * spl), dim3(64 * NW), smem_hc8, stream(), v, D, zd, H, W, G, NC, HG, nseg, spl, lut, pad, dbgh);
+            const dim3 grid(nviews * H * spl);
+            if (px) STM_HC_LAUNCH(NW, true, grid, smem_hc8, nseg, spl)
+            else STM_HC_LAUNCH(NW, false, grid, smem_hc8, nseg, spl)
         } else if (fuse_cost && smem_c12 <= 80 * 1024 && (agg_variant() / 1000) % 10 != 1) { // 1000: 128-pixel segments as in the other passes
             const int nblkc = ((nsegc * H * nviews + 7) / 8) * 8;
             allow_lds_m((const void *)stm_k_pq_h<NWC, false, true>, smem_c12);
@@ -1194,13 +1252,16 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
             allow_lds_m((const void *)stm_k_pq_h<NW, false, false>, smem_h);
             STM_LAUNCH((stm_k_pq_h<NW, false, false>), dim3(nblk), dim3(64 * NW), smem_h, stream(), v, D, zd, H, W, G, NC, HG, nseg, dbgh, lut, 0, nviews);
         }
+#undef STM_HC_LAUNCH
         STM_CHECK_LAUNCH();
     }
     {
         // fused vertical kernel
         ProfScope p("pq_v12");
-        if (regs) {
-            launch_pq_v12r(v, nviews, vtab, rec, H, W, G, NC);
+        if (px) {
+            launch_pq_v12r(v, nviews, vtab, H, W, G);
+        } else if (regs) {
+            launch_pq_v12q(v, nviews, vtab, rec, H, W, G, NC);
         } else {
             const size_t smem = (size_t)(RQ1 + RQ2) * 1024;
             allow_lds_m((const void *)stm_k_pq_v12t<NTP>, smem);
@@ -1211,7 +1272,7 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
     {
         ProfScope p("pq_hw");
         if (hregs) {
-            launch_pq_hsr(v, nviews, htab, D, zd, H, W);
+            launch_pq_hsr(v, nviews, htab, D, zd, H, W, px);
         } else if (streaming && !wta) {
             allow_lds_m((const void *)stm_k_pq_hs<NW, false>, smem_h);
             STM_LAUNCH((stm_k_pq_hs<NW, false>), dim3(nviews * H * spl), dim3(64 * NW), smem_h, stream(), v, D, zd, H, W, G, NC, HG, nseg, spl, dbgh);
@@ -1237,14 +1298,15 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
 // keep_volume: the last pass writes the aggregated costs to vol_b instead of doing WTA (the HSLO stage follows; disp unused).
 // htab_ready: the horizontal window table of both views (aggm_frame_htab_dwords) already built by launch_cross_arms2, or nullptr.
 // aggm_frame_htab_dwords: its size when this frame's last pass will use it, else 0.
-size_t aggm_frame_vtab_dwords(int H, int W, int usd, int *rec, int *top)
+size_t aggm_frame_vtab_dwords(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later, int *rec, int *top, bool *col)
 {
     if (usd > 255) usd = 255;
     const bool regs = aggv_supports(usd) && (agg_variant() / 10000000) % 10 != 1;
-    *rec = regs ? aggv_table_rec() : 0;
+    *col = aggm_frame_px(D, zd, H, W, usd, keep_volume, v2_read_later);
+    *rec = !regs ? 0 : *col ? HR_REC : aggv_table_rec();
     *top = regs ? aggv_table_top() : -1;
     if (!regs || (agg_variant() / 1000000000) % 10 == 1) return 0; // 1000000000: the stand-alone table kernels
-    return (size_t)2 * ((H + 15) / 16) * ((W + 3) / 4) * *rec;
+    return *col ? aggv_col_table_dwords(2, H, W) : (size_t)2 * ((H + 15) / 16) * ((W + 3) / 4) * *rec;
 }
 size_t aggm_frame_htab_dwords(int D, int H, int W, int usd, bool keep_volume)
 {
@@ -1254,14 +1316,14 @@ size_t aggm_frame_htab_dwords(int D, int H, int W, int usd, bool keep_volume)
 }
 void launch_aggm_frame(const uint32_t *const *pk, const uint32_t *const *cen, const float *lut, float *const *vol_a, float *const *vol_b,
                        const u8 *const *armU, const u8 *const *armD, const u8 *const *armL, const u8 *const *armR, float *const *disp,
-                       int D, int zd, int H, int W, int usd, bool keep_volume, uint32_t *htab_ready, uint32_t *vtab_ready)
+                       int D, int zd, int H, int W, int usd, bool keep_volume, uint32_t *htab_ready, uint32_t *vtab_ready, bool v2_read_later)
 {
     PQViews v;
     for (int i = 0; i < 2; ++i) {
         v.pk[i] = pk[i]; v.cen[i] = cen[i]; v.a[i] = vol_a[i]; v.b[i] = vol_b[i];
         v.armU[i] = armU[i]; v.armD[i] = armD[i]; v.armL[i] = armL[i]; v.armR[i] = armR[i]; v.disp[i] = disp[i];
     }
-    aggm_chain(v, 2, true, !keep_volume, lut, D, zd, H, W, usd, htab_ready, vtab_ready);
+    aggm_chain(v, 2, true, !keep_volume, lut, D, zd, H, W, usd, htab_ready, vtab_ready, aggm_frame_px(D, zd, H, W, usd, keep_volume, v2_read_later));
 }
 
 // The per-stage aggregation (ca_cross / d_ca_cross, d_ca_cross.cu:255-270) of ONE volume in the caller's layout on the

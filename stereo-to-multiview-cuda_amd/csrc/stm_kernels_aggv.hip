@@ -5,7 +5,9 @@
 //
 // Round 3's fused vertical kernel (stm_k_pq_v12t, stm_kernels_aggm.hip) streams a strip through two LDS rings shared by the
 // six waves of a block, two barriers per step; its matrix pipe was busy 48 % of the time (profiles/r03_pmc_sq_aggm.txt).
-// Here a strip of 4 columns x 16 hypotheses belongs to ONE wave and nothing is shared:
+// Two kernels.  stm_k_pq_v12q (first below, round 4; PQ volumes, every path but the frame's fast one): a strip of 4 columns x 16
+// hypotheses belongs to ONE wave.  stm_k_pq_v12r (second below; PX volumes, the frame's fast path): ONE column x 64 hypotheses per
+// wave, the same walk with the sweep block of stm_k_pq_hsr; its comment says what differs.  In stm_k_pq_v12q nothing is shared:
 //  * a row of the strip is 64 floats = ONE vector register, laid out exactly as the B operand of v_mfma_f32_16x16x1_4B_f32
 //    wants it (lane 16 b + n = column b, hypothesis n).  The CU's register file (512 KB) is three times its LDS: the 88 input
 //    rows a tile's sweep can touch and the 100 first-pass rows the second pass needs are two rings of registers per wave;
@@ -33,7 +35,7 @@
 // row's position inside the tile's range), read in batches of two quads (s_load_dwordx16) a batch ahead.
 // Results are bit-identical to stm_k_pq_v12t (same chains, same order).  Limits: usd <= 36 (sweep range of 88 rows); longer
 // arms run stm_k_pq_v12t.
-#include "stm_common.h"
+#include "stm_hwin.h"
 
 namespace stm {
 
@@ -56,7 +58,7 @@ constexpr int VR_NQ = 22;  // quads of rows in that range
 // EXP: timing experiments (libstm_hip_timing.so only; results NOT valid): 1 = no sweeps, 2 = no loads / stores, 4 = sweeps without
 // their mask waits and loads, 8 = no transposition / ring moves.  The product library instantiates EXP = 0 only.
 template <int EXP>
-__global__ __launch_bounds__(64, 2) void stm_k_pq_v12r(PQViews pv, const uint32_t *__restrict__ wtab, int rec, int H, int G, int NC, int nviews)
+__global__ __launch_bounds__(64, 2) void stm_k_pq_v12q(PQViews pv, const uint32_t *__restrict__ wtab, int rec, int H, int G, int NC, int nviews)
 {
     // block (one wave) -> (view, group, chunk); the NC chunk waves of a strip read the same window records: consecutive blocks
     // Consecutive blocks go to different XCDs (8, each with its own L2), but the NC chunk waves of a strip read the same window
@@ -523,29 +525,526 @@ VR_done_%=:
                    "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247");
 }
 
+// ------------------------------------------------------------------ one column per wave (the frame's fast path, PX volumes)
+// The kernel above spends one v_cndmask per MFMA: with a tile of 16 rows x 4 columns every MFMA carries 64 distinct mask bits.
+// Here a wave owns ONE column and all 64 hypotheses of it (the volumes are pixel-major, PX: float index ((y 4G + x) 64 + d), a
+// row of the column = 256 contiguous bytes = one register, lane 16 b + n = chunk b, hypothesis n).  The MFMA's four blocks are the
+// four chunks, which share their masks, so one A register (lanes 16 a + m = window row a of a quad, tile row m) serves the
+// quad's four MFMAs through CBSZ / ABID -- the sweep block of stm_k_pq_hsr (56 bytes, one select per four MFMAs), and the sweep of
+// a single column is shorter than that of four (its range is the union over 16 windows instead of 64).  Chains, their order
+// and every rounding are those of stm_k_pq_v12q: results are bit-identical.
+// Window table: vcol_build's records (stm_hwin.h; HR_REC dwords per tile of 16 rows and column: first quad of the sweep inside the
+// tile's range, quads n, the mask of the quad that sweep block p handles at 8 + 2 p, the sweep being blocks 22 - n .. 21); the 24
+// mask pairs of a sweep are three s_load_dwordx16, issued where the kernel above issued its first batches.
+// Rings, landing registers, the two-steps-ahead loads, the 16-row step and the three-tile lag are the kernel's above.  Register
+// map: v[0:87] ring 1, v[88:103] / v[228:243] landing registers, v[104:203] ring 2, v[204:219] accumulators, v220 / v221 the A
+// operand of the even / odd blocks.  s[16:19] / s[20:23] buffer descriptors (input column, output column), s24 u (step), s25 / s26
+// ring index of row 16 u + 36 in ring 1 / of row 16 u in ring 2, s27 last step + 1, s28 u - 3, s29 ring size of the running
+// sweep, s30 ring index of the running block, s31 temporary, s[36:83] the 24 mask pairs of the sweep, s[84:85] record address,
+// then jump target, s[86:87] temporaries, s88 .. s91 this step's headers (q0, n of either pass), s[92:95] the next step's (in
+// flight during a step), s96 / s97 temporaries, s98 store offset, s99 entry block (s32 .. s35 are left alone: the ABI's stack
+// registers).  v[224:227] the store addresses.
+// The first pass's accumulators are transposed into row registers for ring 2; the second pass's leave straight from the
+// accumulator registers (register 4 b + i of lane 16 q + n = row 4 q + i, hypothesis 16 b + n: sixteen dword stores of four 64-byte
+// pieces each, four v_add for their row offsets).  Transposing them too, for stores of 256 contiguous bytes with scalar row
+// offsets, measured 0.013 ms slower (0.525 against 0.512 ms, profiles/vcol_store_forms.json).
+// EXP: timing experiments (libstm_hip_timing.so only; results NOT valid): 1 = no sweeps, 2 = no loads / stores, 4 = no mask loads,
+// 8 = no transposition / ring moves.
+// Blocks are dealt to the XCDs as they come: neighbouring columns share no cache line of the volumes and no table record, so
+// the remap of the kernel above (a strip's chunk waves on one XCD) has nothing left to keep together.
+template <int EXP>
+__global__ __launch_bounds__(64, 2) void stm_k_pq_v12r(PQViews pv, const uint32_t *__restrict__ wtab, int H, int G4, int nviews)
+{
+    // block (one wave) -> (view, column); columns in [W, 4G) have empty windows and write zeros
+    const int x = blockIdx.x % G4, view = blockIdx.x / G4;
+    if (view >= nviews) return;
+    const int l = threadIdx.x;
+    const int nT = (H + 15) >> 4;
+    const int rsb = G4 * 256; // bytes between consecutive rows of the column
+    const float *in = (const float *)(view ? pv.b[1] : pv.b[0]) + (size_t)x * 64;
+    float *out = (float *)(view ? pv.a[1] : pv.a[0]) + (size_t)x * 64;
+    const uint32_t range = (uint32_t)(H - 1) * (uint32_t)rsb + 256u; // bytes of a column up to the end of its last row
+    const uint32_t *trow = wtab + ((size_t)view * nT * G4 + x) * HR_REC; // record of tile 0; tile u at + u * G4 * HR_REC dwords
+    const int tstep = G4 * HR_REC * 4;
+    const int voff = 4 * l; // lane 16 b + n = hypothesis 16 b + n
+    const int vst = 4 * (l >> 4) * rsb + (l & 15) * 4; // lane 16 q + n stores rows 4 q (+ i) of hypotheses (16 b +) n
+    asm volatile(R"ASM(
+        .set VC_EXP, %[exp]
+        ; ---------------------------------------------------------------- macros
+        ; one block of a sweep: four MFMAs on one quad of ring rows, the A operand (lanes 16 a + m = row a of the quad, tile row m)
+        ; shared through CBSZ / ABID.  p = block index, rb = first register of the ring, acur / anxt = the A registers of this / the
+        ; next block
+        .macro VC_BLOCK p, rb, acur, anxt
+        s_set_gpr_idx_idx s30
+        v_mfma_f32_16x16x1_4b_f32 v[204:219], v[\acur], v[\rb], v[204:219] cbsz:2 abid:0
+        v_cndmask_b32_e64 v[\anxt], 0, 1.0, s[36+2*((\p)+1):37+2*((\p)+1)]
+        v_mfma_f32_16x16x1_4b_f32 v[204:219], v[\acur], v[\rb+1], v[204:219] cbsz:2 abid:1
+        s_add_u32 s30, s30, 4
+        s_cmp_eq_u32 s30, s29
+        s_cselect_b32 s30, 0, s30
+        v_mfma_f32_16x16x1_4b_f32 v[204:219], v[\acur], v[\rb+2], v[204:219] cbsz:2 abid:2
+        v_mfma_f32_16x16x1_4b_f32 v[204:219], v[\acur], v[\rb+3], v[204:219] cbsz:2 abid:3
+        .endm
+        .macro VC_PAIR b, rb
+        VC_BLOCK 2*(\b), \rb, 220, 221
+        VC_BLOCK 2*(\b)+1, \rb, 221, 220
+        .endm
+        ; the loads a sweep starts from.  q0 / n = the tile's header (n in 1 .. 22), s96 = ring index of the range's first row,
+        ; s29 = ring size, s[84:85] = the tile's record.  out: s99 = entry block 22 - n, s30 = ring index of the sweep's first row;
+        ; in flight: the 24 mask pairs (block p reads pair p + 1 for its successor, the entry block's own comes through M0)
+        .macro VC_SWEEP_ISSUE q0, n
+        s_sub_u32 s99, 22, \n
+        s_lshl_b32 s31, \q0, 2
+        s_add_u32 s30, s96, s31
+        s_sub_u32 s31, s30, s29
+        s_cmp_ge_u32 s30, s29
+        s_cselect_b32 s30, s31, s30
+        .if (VC_EXP & 4) == 0
+        s_load_dwordx16 s[36:51], s[84:85], 0x20
+        s_load_dwordx16 s[52:67], s[84:85], 0x60
+        s_load_dwordx16 s[68:83], s[84:85], 0xa0
+        .endif
+        .endm
+        ; the sweep: prologue (the entry block's A operand, first MFMA with the constant 0 as accumulator input), computed jump into
+        ; the sequence of blocks, epilogue (the accumulators are read by vector instructions next: the last MFMA must have left
+        ; the pipe)
+        .macro VC_SWEEP_RUN rb
+        s_waitcnt lgkmcnt(0)
+        s_lshl_b32 m0, s99, 1
+        s_nop 0
+        s_movrels_b64 s[86:87], s[36:37]      ; the entry block's mask
+        v_cndmask_b32_e64 v220, 0, 1.0, s[86:87]
+        v_cndmask_b32_e64 v221, 0, 1.0, s[86:87]
+        s_set_gpr_idx_on s30, 0x2
+        s_mul_i32 s31, s99, 56
+        s_getpc_b64 s[84:85]
+VC_pc_%=_\@:
+        s_add_u32 s31, s31, VC_blk0_%=_\@-VC_pc_%=_\@+12
+        s_add_u32 s84, s84, s31
+        s_addc_u32 s85, s85, 0
+        v_mfma_f32_16x16x1_4b_f32 v[204:219], v220, v[\rb], 0 cbsz:2 abid:0
+        s_setpc_b64 s[84:85]
+VC_blk0_%=_\@:
+        VC_PAIR 0, \rb
+        VC_PAIR 1, \rb
+        VC_PAIR 2, \rb
+        VC_PAIR 3, \rb
+        VC_PAIR 4, \rb
+        VC_PAIR 5, \rb
+        VC_PAIR 6, \rb
+        VC_PAIR 7, \rb
+        VC_PAIR 8, \rb
+        VC_PAIR 9, \rb
+        VC_PAIR 10, \rb
+VC_end_%=_\@:
+        .if (VC_end_%=_\@-VC_blk0_%=_\@) != 22*56
+        .error "sweep blocks are not 56 bytes each"
+        .endif
+        s_set_gpr_idx_off
+        s_nop 15
+        s_nop 3
+        .endm
+        .macro VC_ZERO_ACC
+        v_mov_b32 v204, 0
+        v_mov_b32 v205, 0
+        v_mov_b32 v206, 0
+        v_mov_b32 v207, 0
+        v_mov_b32 v208, 0
+        v_mov_b32 v209, 0
+        v_mov_b32 v210, 0
+        v_mov_b32 v211, 0
+        v_mov_b32 v212, 0
+        v_mov_b32 v213, 0
+        v_mov_b32 v214, 0
+        v_mov_b32 v215, 0
+        v_mov_b32 v216, 0
+        v_mov_b32 v217, 0
+        v_mov_b32 v218, 0
+        v_mov_b32 v219, 0
+        .endm
+        ; accumulators (register 4 b + i of lane 16 q + n = [row 4 q + i][chunk b][hypothesis n]) -> row registers (register
+        ; 4 q + i of lane 16 b + n): for each i a 4 x 4 transposition of (register b, lane group q)
+        .macro VC_TRANSPOSE
+        v_permlane32_swap_b32 v204, v212
+        v_permlane32_swap_b32 v208, v216
+        v_permlane32_swap_b32 v205, v213
+        v_permlane32_swap_b32 v209, v217
+        v_permlane32_swap_b32 v206, v214
+        v_permlane32_swap_b32 v210, v218
+        v_permlane32_swap_b32 v207, v215
+        v_permlane32_swap_b32 v211, v219
+        s_nop 1
+        v_permlane16_swap_b32 v204, v208
+        v_permlane16_swap_b32 v212, v216
+        v_permlane16_swap_b32 v205, v209
+        v_permlane16_swap_b32 v213, v217
+        v_permlane16_swap_b32 v206, v210
+        v_permlane16_swap_b32 v214, v218
+        v_permlane16_swap_b32 v207, v211
+        v_permlane16_swap_b32 v215, v219
+        s_nop 1
+        .endm
+        ; four registers src.. -> ring registers rb + index.. (relative destination), then index += 4 with wrap at `size` (s31)
+        .macro VC_PUT4 rb, src
+        v_mov_b32 v[\rb], v[\src]
+        v_mov_b32 v[\rb+1], v[\src+1]
+        v_mov_b32 v[\rb+2], v[\src+2]
+        v_mov_b32 v[\rb+3], v[\src+3]
+        s_add_u32 s97, s97, 4
+        s_cmp_eq_u32 s97, s31
+        s_cselect_b32 s97, 0, s97
+        s_set_gpr_idx_idx s97
+        .endm
+        ; rows are addressed by a scalar offset, which the buffer's range check does not see: a row outside the image goes to an
+        ; empty buffer (loads return zeros, stores are dropped), a row of the image passes (its lane offset is below 256)
+        .macro VC_LOAD_ROW lb, k
+        s_cmp_lt_u32 s86, %[H]
+        s_cselect_b32 s18, %[range], 0
+        s_mul_i32 s87, s86, %[rsb]
+        .if (VC_EXP & 2) == 0
+        buffer_load_dword v[\lb+\k], %[voff], s[16:19], s87 offen nt
+        .endif
+        s_add_u32 s86, s86, 1
+        .endm
+        .macro VC_LOAD_FAST lb, k
+        .if (VC_EXP & 2) == 0
+        buffer_load_dword v[\lb+\k], %[voff], s[16:19], s87 offen nt
+        .endif
+        s_add_u32 s87, s87, %[rsb]
+        .endm
+
+        ; ---------------------------------------------------------------- setup
+        s_mov_b64 s[16:17], %[in]
+        s_and_b32 s17, s17, 0xffff
+        s_mov_b32 s18, 0
+        s_mov_b32 s19, 0x20000
+        s_mov_b64 s[20:21], %[out]
+        s_and_b32 s21, s21, 0xffff
+        s_mov_b32 s22, 0
+        s_mov_b32 s23, 0x20000
+        s_mov_b32 s24, -5                     ; u: five steps that only bring rows [0, 52) into ring 1
+        s_mov_b32 s25, 44                     ; ring-1 index of row 16 u + 36 = -44
+        s_mov_b32 s26, 20                     ; ring-2 index of row 16 u = -80
+        s_add_u32 s27, %[nT], 3               ; the second pass runs three tiles behind
+        s_mov_b64 s[92:93], 0
+        s_mov_b64 s[94:95], 0
+        s_mov_b32 s88, 0                      ; the first step has no tiles
+        s_mov_b32 s89, 0
+        s_mov_b32 s90, 0
+        s_mov_b32 s91, 0
+        s_sub_i32 s28, s24, 3
+        .macro VC_STEP lb
+        ; s88 .. s91 = (q0, n) of this step's first-pass tile u and second-pass tile u - 3, s28 = u - 3: set at the end of the step
+        ; before, where the masks of this step's first pass were requested too
+        ; ------------------------------------------------------------ the rows loaded during the last step -> ring 1
+        s_cmp_lt_i32 s24, -3
+        s_cbranch_scc1 VC_nocopy_%=_\@
+        .if (VC_EXP & 2) == 0
+        s_waitcnt vmcnt(48)                   ; the 16 loads of the step before the last (issued since: 16 stores, 16 loads, 16 stores)
+        .endif
+        .if (VC_EXP & 8) == 0
+        s_mov_b32 s97, s25
+        s_movk_i32 s31, 88
+        s_set_gpr_idx_on s97, 0x8
+        VC_PUT4 0, \lb
+        VC_PUT4 0, \lb+4
+        VC_PUT4 0, \lb+8
+        VC_PUT4 0, \lb+12
+        s_set_gpr_idx_off
+        .endif
+VC_nocopy_%=_\@:
+        s_cmp_lt_i32 s24, 0
+        s_cbranch_scc1 VC_loads_%=_\@
+        ; ------------------------------------------------------------ first pass of tile u
+        s_cmp_eq_u32 s89, 0
+        s_cbranch_scc1 VC_zero1_%=_\@
+        VC_SWEEP_RUN 0
+        s_branch VC_p1done_%=_\@
+VC_zero1_%=_\@:
+        VC_ZERO_ACC
+VC_p1done_%=_\@:
+        ; masks of the second pass (they travel during the transposition and the loads)
+        s_cmp_eq_u32 s91, 0
+        s_cbranch_scc1 VC_noissue2_%=_\@
+        s_add_u32 s96, s26, 16                ; row 16 u - 84, and -84 = 16 (mod 100)
+        s_sub_u32 s31, s96, 100
+        s_cmp_ge_u32 s96, 100
+        s_cselect_b32 s96, s31, s96
+        s_movk_i32 s29, 100
+        s_mul_i32 s97, s28, %[tstep]
+        s_add_u32 s84, %[trow_lo], s97
+        s_addc_u32 s85, %[trow_hi], 0
+        VC_SWEEP_ISSUE s90, s91
+VC_noissue2_%=_\@:
+        .if (VC_EXP & 8) == 0
+        VC_TRANSPOSE
+        ; rows [16 u, 16 u + 16) of the first pass -> ring 2
+        s_mov_b32 s97, s26
+        s_movk_i32 s31, 100
+        s_set_gpr_idx_on s97, 0x8
+        VC_PUT4 104, 204
+        VC_PUT4 104, 208
+        VC_PUT4 104, 212
+        VC_PUT4 104, 216
+        s_set_gpr_idx_off
+        .endif
+VC_loads_%=_\@:
+        ; ------------------------------------------------------------ rows [16 u + 68, 16 u + 84) -> the landing registers just emptied
+        s_lshl_b32 s86, s24, 4
+        s_add_i32 s86, s86, 68
+        s_add_i32 s87, s86, 15
+        s_cmp_lt_u32 s87, %[H]                ; (unsigned: also false for rows above the image)
+        s_cbranch_scc0 VC_slowloads_%=_\@
+        s_cmp_lt_u32 s86, %[H]
+        s_cbranch_scc0 VC_slowloads_%=_\@
+        ; all sixteen rows inside the image (every step but the first and the last few): one scalar add per row
+        s_mov_b32 s18, %[range]
+        s_mul_i32 s87, s86, %[rsb]
+        VC_LOAD_FAST \lb, 0
+        VC_LOAD_FAST \lb, 1
+        VC_LOAD_FAST \lb, 2
+        VC_LOAD_FAST \lb, 3
+        VC_LOAD_FAST \lb, 4
+        VC_LOAD_FAST \lb, 5
+        VC_LOAD_FAST \lb, 6
+        VC_LOAD_FAST \lb, 7
+        VC_LOAD_FAST \lb, 8
+        VC_LOAD_FAST \lb, 9
+        VC_LOAD_FAST \lb, 10
+        VC_LOAD_FAST \lb, 11
+        VC_LOAD_FAST \lb, 12
+        VC_LOAD_FAST \lb, 13
+        VC_LOAD_FAST \lb, 14
+        VC_LOAD_FAST \lb, 15
+        s_branch VC_loaded_%=_\@
+VC_slowloads_%=_\@:
+        VC_LOAD_ROW \lb, 0
+        VC_LOAD_ROW \lb, 1
+        VC_LOAD_ROW \lb, 2
+        VC_LOAD_ROW \lb, 3
+        VC_LOAD_ROW \lb, 4
+        VC_LOAD_ROW \lb, 5
+        VC_LOAD_ROW \lb, 6
+        VC_LOAD_ROW \lb, 7
+        VC_LOAD_ROW \lb, 8
+        VC_LOAD_ROW \lb, 9
+        VC_LOAD_ROW \lb, 10
+        VC_LOAD_ROW \lb, 11
+        VC_LOAD_ROW \lb, 12
+        VC_LOAD_ROW \lb, 13
+        VC_LOAD_ROW \lb, 14
+        VC_LOAD_ROW \lb, 15
+VC_loaded_%=_\@:
+        s_cmp_lt_i32 s24, 0
+        s_cbranch_scc1 VC_end_of_step_%=_\@
+        ; ------------------------------------------------------------ second pass of tile u - 3
+        s_cmp_eq_u32 s91, 0
+        s_cbranch_scc1 VC_zero2_%=_\@
+        VC_SWEEP_RUN 104
+        s_branch VC_end_of_step_%=_\@
+VC_zero2_%=_\@:
+        VC_ZERO_ACC
+VC_end_of_step_%=_\@:
+        ; the tile's accumulators leave below, behind the next step's bookkeeping.  Always sixteen stores (a step's loads are
+        ; counted against them); before tile 0 into an empty buffer
+        s_lshl_b32 s86, s28, 4                ; first row of the tile (s86 stays untouched until the stores)
+        s_mul_i32 s98, s86, %[rsb]
+        ; ------------------------------------------------------------ the next step: ring indices, tiles, masks -- in front of the
+        ; stores, so that the masks travel behind them and behind the next step's row moves
+        s_add_u32 s25, s25, 16
+        s_sub_u32 s31, s25, 88
+        s_cmp_ge_u32 s25, 88
+        s_cselect_b32 s25, s31, s25
+        s_add_u32 s26, s26, 16
+        s_sub_u32 s31, s26, 100
+        s_cmp_ge_u32 s26, 100
+        s_cselect_b32 s26, s31, s26
+        s_add_i32 s24, s24, 1
+        s_waitcnt lgkmcnt(0)                  ; the headers of its tiles, requested a step ago
+        s_mov_b32 s88, s92
+        s_cmp_ge_i32 s24, 0
+        s_cselect_b32 s89, s93, 0
+        s_cmp_lt_i32 s24, %[nT]
+        s_cselect_b32 s89, s89, 0             ; first-pass tiles past the image: no window rows (their rows are zeros)
+        s_min_u32 s89, s89, 22                ; (the table cannot hold more: the jump must stay inside the sequence)
+        s_sub_i32 s28, s24, 3
+        s_mov_b32 s90, s94
+        s_cmp_ge_i32 s28, 0
+        s_cselect_b32 s91, s95, 0
+        s_min_u32 s91, s91, 22
+        .if VC_EXP & 1
+        s_mov_b32 s89, 0
+        s_mov_b32 s91, 0
+        .endif
+        ; headers of the tiles of the step after it (tile indices clamped into the table; unused entries are masked above)
+        s_sub_u32 s96, %[nT], 1
+        s_add_i32 s97, s24, 1
+        s_max_i32 s97, s97, 0
+        s_min_i32 s97, s97, s96
+        s_mul_i32 s97, s97, %[tstep]
+        s_load_dwordx2 s[92:93], %[trow], s97
+        s_sub_i32 s97, s24, 2
+        s_max_i32 s97, s97, 0
+        s_min_i32 s97, s97, s96
+        s_mul_i32 s97, s97, %[tstep]
+        s_load_dwordx2 s[94:95], %[trow], s97
+        s_cmp_eq_u32 s89, 0
+        s_cbranch_scc1 VC_noissue1_%=_\@
+        s_add_u32 s96, s25, 16                ; row 16 u - 36 = row 16 u + 36 - 72, and -72 = 16 (mod 88)
+        s_sub_u32 s31, s96, 88
+        s_cmp_ge_u32 s96, 88
+        s_cselect_b32 s96, s31, s96
+        s_movk_i32 s29, 88
+        s_mul_i32 s97, s24, %[tstep]
+        s_add_u32 s84, %[trow_lo], s97
+        s_addc_u32 s85, %[trow_hi], 0
+        VC_SWEEP_ISSUE s88, s89
+VC_noissue1_%=_\@:
+        ; straight from the accumulators: register 4 b + i of lane 16 q + n = row 4 q + i, hypothesis 16 b + n.  The whole row
+        ; offset is in the vector register, so the range check sees it (rows past the image are dropped); before tile 0: empty buffer
+        s_cmp_ge_i32 s86, 0
+        s_cselect_b32 s22, %[range], 0
+        v_add_u32 v224, s98, %[vst]
+        s_add_u32 s98, s98, %[rsb]
+        v_add_u32 v225, s98, %[vst]
+        s_add_u32 s98, s98, %[rsb]
+        v_add_u32 v226, s98, %[vst]
+        s_add_u32 s98, s98, %[rsb]
+        v_add_u32 v227, s98, %[vst]
+        .if (VC_EXP & 2) == 0
+        buffer_store_dword v204, v224, s[20:23], 0 offen nt
+        buffer_store_dword v208, v224, s[20:23], 0 offen offset:64 nt
+        buffer_store_dword v212, v224, s[20:23], 0 offen offset:128 nt
+        buffer_store_dword v216, v224, s[20:23], 0 offen offset:192 nt
+        buffer_store_dword v205, v225, s[20:23], 0 offen nt
+        buffer_store_dword v209, v225, s[20:23], 0 offen offset:64 nt
+        buffer_store_dword v213, v225, s[20:23], 0 offen offset:128 nt
+        buffer_store_dword v217, v225, s[20:23], 0 offen offset:192 nt
+        buffer_store_dword v206, v226, s[20:23], 0 offen nt
+        buffer_store_dword v210, v226, s[20:23], 0 offen offset:64 nt
+        buffer_store_dword v214, v226, s[20:23], 0 offen offset:128 nt
+        buffer_store_dword v218, v226, s[20:23], 0 offen offset:192 nt
+        buffer_store_dword v207, v227, s[20:23], 0 offen nt
+        buffer_store_dword v211, v227, s[20:23], 0 offen offset:64 nt
+        buffer_store_dword v215, v227, s[20:23], 0 offen offset:128 nt
+        buffer_store_dword v219, v227, s[20:23], 0 offen offset:192 nt
+        .endif
+        .endm
+VC_loop_%=:
+        VC_STEP 88
+        s_cmp_ge_i32 s24, s27
+        s_cbranch_scc1 VC_done_%=
+        VC_STEP 228
+        s_cmp_lt_i32 s24, s27
+        s_cbranch_scc1 VC_loop_%=
+VC_done_%=:
+        s_waitcnt vmcnt(0) lgkmcnt(0)         ; the last rows, masks and headers: nothing may be in flight when the wave ends
+        .purgem VC_BLOCK
+        .purgem VC_PAIR
+        .purgem VC_SWEEP_ISSUE
+        .purgem VC_SWEEP_RUN
+        .purgem VC_ZERO_ACC
+        .purgem VC_TRANSPOSE
+        .purgem VC_PUT4
+        .purgem VC_LOAD_ROW
+        .purgem VC_LOAD_FAST
+        .purgem VC_STEP
+        )ASM"
+                 :
+                 : [in] "s"(in), [out] "s"(out), [trow] "s"(trow), [trow_lo] "s"((uint32_t)(uintptr_t)trow), [trow_hi] "s"((uint32_t)((uintptr_t)trow >> 32)),
+                   [tstep] "s"(tstep), [rsb] "s"(rsb), [H] "s"(H), [nT] "s"(nT), [range] "s"(range), [voff] "v"(voff), [vst] "v"(vst), [exp] "n"(EXP)
+                 : "memory", "scc", "vcc",
+                   "s16", "s17", "s18", "s19", "s20", "s21", "s22", "s23", "s24", "s25", "s26", "s27", "s28", "s29", "s30", "s31", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99",
+                   "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19",
+                   "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39",
+                   "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59",
+                   "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79",
+                   "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", "v96", "v97", "v98", "v99",
+                   "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116",
+                   "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", "v128", "v129", "v130", "v131", "v132", "v133",
+                   "v134", "v135", "v136", "v137", "v138", "v139", "v140", "v141", "v142", "v143", "v144", "v145", "v146", "v147", "v148", "v149", "v150",
+                   "v151", "v152", "v153", "v154", "v155", "v156", "v157", "v158", "v159", "v160", "v161", "v162", "v163", "v164", "v165", "v166", "v167",
+                   "v168", "v169", "v170", "v171", "v172", "v173", "v174", "v175", "v176", "v177", "v178", "v179", "v180", "v181", "v182", "v183", "v184",
+                   "v185", "v186", "v187", "v188", "v189", "v190", "v191", "v192", "v193", "v194", "v195", "v196", "v197", "v198", "v199", "v200", "v201",
+                   "v202", "v203", "v204", "v205", "v206", "v207", "v208", "v209", "v210", "v211", "v212", "v213", "v214", "v215", "v216", "v217", "v218",
+                   "v219", "v220", "v221", "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235",
+                   "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243");
+}
+
+// The per-column window table of `nviews` views from the arm planes (the frame path builds it inside stm_k_cross_arms instead).
+// A wave = the tile's 16 rows x four columns, lane 16 c + m.
+__global__ __launch_bounds__(256) void stm_k_vcol_table(PQViews v, uint32_t *__restrict__ tab, int H, int W, int G, int nT)
+{
+    __shared__ uint32_t ev_all[4][4 * 96];
+    const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, g = blockIdx.x * 4 + wv, u = blockIdx.y, view = blockIdx.z;
+    if (g >= G) return; // uniform per wave; no block-wide barrier below
+    const u8 *__restrict__ armU = view ? v.armU[1] : v.armU[0], *__restrict__ armD = view ? v.armD[1] : v.armD[0];
+    const int c = l >> 4, m = l & 15, y = u * 16 + m, x = 4 * g + c;
+    int s0 = 0, nn = 0;
+    if (y < H && x < W) {
+        const int aU = armU[(size_t)y * W + x], aD = armD[(size_t)y * W + x];
+        s0 = y - aU;
+        nn = aU + aD;
+    }
+    vcol_build(tab + (size_t)(view * nT + u) * (4 * G) * HR_REC, ev_all[wv], u, 4 * g, s0, nn);
+}
+
 bool aggv_supports(int usd) { return usd >= 1 && usd <= VR_TOP; }
 int aggv_table_top() { return VR_TOP; }
 int aggv_table_rec() { return 8 + 8 * (VR_NQ + 2); } // header + 22 quads + the batch read-ahead
 
 // both vertical passes, vol_b -> vol_a, for `nviews` views; `tab` / `rec`: the window table of stm_k_vwin_table (static layout)
-void launch_pq_v12r(PQViews &v, int nviews, const uint32_t *tab, int rec, int H, int W, int G, int NC)
+void launch_pq_v12q(PQViews &v, int nviews, const uint32_t *tab, int rec, int H, int W, int G, int NC)
 {
     (void)W;
     const dim3 grid(G * nviews * NC);
 #ifdef STM_TIMING
     switch (timing_knobs()) {
-    case 1: STM_LAUNCH(stm_k_pq_v12r<1>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
-    case 2: STM_LAUNCH(stm_k_pq_v12r<2>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
-    case 3: STM_LAUNCH(stm_k_pq_v12r<3>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
-    case 4: STM_LAUNCH(stm_k_pq_v12r<4>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
-    case 6: STM_LAUNCH(stm_k_pq_v12r<6>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
-    case 8: STM_LAUNCH(stm_k_pq_v12r<8>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
-    case 9: STM_LAUNCH(stm_k_pq_v12r<9>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
-    default: STM_LAUNCH(stm_k_pq_v12r<0>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
+    case 1: STM_LAUNCH(stm_k_pq_v12q<1>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
+    case 2: STM_LAUNCH(stm_k_pq_v12q<2>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
+    case 3: STM_LAUNCH(stm_k_pq_v12q<3>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
+    case 4: STM_LAUNCH(stm_k_pq_v12q<4>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
+    case 6: STM_LAUNCH(stm_k_pq_v12q<6>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
+    case 8: STM_LAUNCH(stm_k_pq_v12q<8>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
+    case 9: STM_LAUNCH(stm_k_pq_v12q<9>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
+    default: STM_LAUNCH(stm_k_pq_v12q<0>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews); break;
     }
 #else
-    STM_LAUNCH(stm_k_pq_v12r<0>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews);
+    STM_LAUNCH(stm_k_pq_v12q<0>, grid, dim3(64), 0, stream(), v, tab, rec, H, G, NC, nviews);
 #endif
+    STM_CHECK_LAUNCH();
+}
+
+
+size_t aggv_col_table_dwords(int nviews, int H, int W) { return (size_t)nviews * cdiv(H, 16) * (4 * cdiv(W, 4)) * HR_REC + 64; }
+
+void launch_vcol_table(PQViews &v, int nviews, uint32_t *tab, int H, int W)
+{
+    const int G = cdiv(W, 4), nT = cdiv(H, 16);
+    STM_LAUNCH(stm_k_vcol_table, dim3(cdiv(G, 4), nT, nviews), dim3(256), 0, stream(), v, tab, H, W, G, nT);
+    STM_CHECK_LAUNCH();
+}
+
+// both vertical passes on PX volumes, vol_b -> vol_a, for `nviews` views; `tab`: the per-column window table (vcol_build)
+void launch_pq_v12r(PQViews &v, int nviews, const uint32_t *tab, int H, int W, int G)
+{
+    (void)W;
+    const int G4 = 4 * G;
+    const dim3 grid(G4 * nviews);
+#define STM_V12R_LAUNCH(E) STM_LAUNCH(stm_k_pq_v12r<E>, grid, dim3(64), 0, stream(), v, tab, H, G4, nviews)
+#ifdef STM_TIMING
+    switch (timing_knobs()) {
+    case 1: STM_V12R_LAUNCH(1); break;
+    case 2: STM_V12R_LAUNCH(2); break;
+    case 3: STM_V12R_LAUNCH(3); break;
+    case 4: STM_V12R_LAUNCH(4); break;
+    case 8: STM_V12R_LAUNCH(8); break;
+    default: STM_V12R_LAUNCH(0); break;
+    }
+#else
+    STM_V12R_LAUNCH(0);
+#endif
+#undef STM_V12R_LAUNCH
     STM_CHECK_LAUNCH();
 }
 
