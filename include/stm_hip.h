@@ -94,6 +94,19 @@ int         stm_prof_read(const char *kernel, float *total_ms);
  * digit N00000 (timing experiments that skip parts of kernels) is ignored here: it exists only in libstm_hip_timing.so,
  * a separate build of the same sources with -DSTM_TIMING (csrc/Makefile, `make timing`). */
 void        stm_set_agg_variant(int v);
+/* Which aggregation kernels a frame call (stm_adcensus_stm, stm_d_adcensus_stm, _t, _nv12; _2 / _2s with the size the match runs
+ * at) takes for these arguments under the current stm_set_agg_variant.  Host arithmetic only: nothing is launched, no device is
+ * touched, no argument is screened, and the answer comes from the very functions the frame call dispatches through.  num_rows,
+ * num_cols: one eye's size; stages: as the frame call takes it.  A bit field:
+ *   bit 0        the chain on the matrix pipe (stm_kernels_aggm.hip); 0: the vector-ALU kernels, and every other bit is 0
+ *   bit 1        the two intermediate volumes pixel-major (PX): stm_k_pq_hc's PX stores, stm_k_pq_v12r, stm_k_pq_hsr's PX loads
+ *   bit 2        the vertical passes with a strip's rows in registers (stm_k_pq_v12r / stm_k_pq_v12q; 0: stm_k_pq_v12t)
+ *   bit 3        the last horizontal pass + WTA on the register ring (stm_k_pq_hsr; 0: an LDS walk, or a volume is kept)
+ *   bits 8..15   waves per block of the cost-fusing streaming first pass stm_k_pq_hc: 12 (192-pixel segments), 8 (128-pixel
+ *                segments), or 0 when another kernel runs the first pass
+ *   bit 16       that pass splits an image row over more than one block
+ * An addition: the reference has one aggregation path and no such query. */
+int         stm_agg_path(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages);
 /* dr_irv / d_dr_irv / the frame calls: 0 (default) = the reference's accept rule, (winning bin index + zero_disp) / S > thresh_h
  * (d_dr_irv.cu:36 -- the bin INDEX, SURVEY A-Q17 iv); 1 = the paper's rule, (winning bin's COUNT) / S > thresh_h (Mei et al.,
  * region voting).  An addition: the reference has no such switch. */

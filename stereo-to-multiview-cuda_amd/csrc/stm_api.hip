@@ -165,6 +165,15 @@ void core_ci(const u8 *d_img_l, const u8 *d_img_r, Vol cl, Vol cr, uint32_t *pk_
 // aggregation H, V, V, H (d_ca_cross.cu:255-270 minus the transposes); result ends in `cost`
 // scratch.base == nullptr: carved here when the vector-ALU kernels run (a plane slab of D * H * W floats)
 static bool agg_on_matrix_pipe(int usd, int H, int W) { return (agg_variant() / 10000) % 10 != 1 && aggm_supports(usd, H, W); }
+// the `stages` bits of a frame call that decide what its aggregation chain has to leave behind (frame_disparity's hslo and subpix)
+static bool stages_hslo(int stages) { return (stages & 0x100) != 0; }   // + scanline optimisation between aggregation and WTA (BASELINE config 3)
+static bool stages_subpix(int stages) { return (stages & 0x200) != 0; } // + sub-pixel enhancement of the whole-pixel maps (Mei et al. 3.4)
+// stm_agg_path (stm_hip.h): the same predicates, in the same order, as frame_disparity and launch_aggm_frame
+int frame_agg_path(int D, int zd, int H, int W, int usd, int stages)
+{
+    if (D < 1 || H < 1 || W < 1 || !agg_on_matrix_pipe(usd, H, W)) return 0;
+    return 1 | aggm_frame_path(D, zd, H, W, usd, stages_hslo(stages), stages_subpix(stages));
+}
 void core_agg(Vol cost, Vol scratch, const Arms &a, int D, int H, int W, int usd)
 {
     // the frame pipeline's matrix-pipe kernels (round 3) -- unless the caller's volume holds infinities, NaNs or denormals
@@ -1211,7 +1220,7 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
     const size_t HW = (size_t)H * W;
     const int NQ = (D + 3) / 4;
     const size_t V = HW * NQ * 4; // volumes are kept quad-interleaved (float4 [NQ][H][W]) inside the frame
-    const bool matrix_pipe = (agg_variant() / 10000) % 10 != 1 && aggm_supports(usd, H, W); // default aggregation path: stm_kernels_aggm.hip
+    const bool matrix_pipe = agg_on_matrix_pipe(usd, H, W); // default aggregation path: stm_kernels_aggm.hip
     float *cost = matrix_pipe ? nullptr : Workspace::get<float>(2 * V), *scratch = matrix_pipe ? nullptr : Workspace::get<float>(V);
     uint32_t *pk_l = pre ? pre[0] : Workspace::get<uint32_t>(HW), *pk_r = pre ? pre[1] : Workspace::get<uint32_t>(HW);
     Vol cl = vol_quads(cost, HW), cr = vol_quads(cost ? cost + V : nullptr, HW), sc = vol_quads(scratch, HW);
@@ -1514,8 +1523,7 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
         launch_demux_sbs(img_l, img_r, d_img_sbs, H, num_cols_sbs, W, elem_sz);
     }
     Arms al, ar;
-    const bool hslo = (stages & 0x100) != 0; // + scanline optimisation between aggregation and WTA (BASELINE config 3)
-    const bool subpix = (stages & 0x200) != 0; // + sub-pixel enhancement of the whole-pixel maps (Mei et al. 3.4)
+    const bool hslo = stages_hslo(stages), subpix = stages_subpix(stages);
     const bool interp = (stages & 0x400) != 0; // + interpolation of the outliers region voting leaves (Mei et al. 3.4)
     const bool linwarp = (stages & 0x800) != 0; // + the views' warps fetched at the fractional coordinate (stm_dibr_dbm_lin)
     stages &= 0xff;
@@ -1573,6 +1581,12 @@ bool packing_unsupported(const char *fn)
 } // namespace
 
 extern "C" {
+
+// which aggregation kernels a frame call with these arguments runs (stm_hip.h); no launch, no device
+int stm_agg_path(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages)
+{
+    return frame_agg_path(num_disp, zero_disp, num_rows, num_cols, usd, stages);
+}
 
 void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
                         int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz,
@@ -1732,7 +1746,7 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
     const int H = num_rows, W = num_cols, h = num_rows_disp, w = num_cols_disp, N = num_views;
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz, hw = (size_t)h * w;
     const size_t V = pq_volume_floats(num_disp, h, w);
-    const bool hslo = (stages & 0x100) != 0, subpix = (stages & 0x200) != 0, interp = (stages & 0x400) != 0; // on the reduced pair
+    const bool hslo = stages_hslo(stages), subpix = stages_subpix(stages), interp = (stages & 0x400) != 0; // on the reduced pair
     const bool linwarp = (stages & 0x800) != 0;                                                             // in the full-size render
     const bool guided = (stages & 0x1000) != 0; // the up-scale between the two: stm_disp_upsample instead of tx_disp_scale
     Workspace::begin((hslo ? 13 : 4) * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 8 * hw + (1u << 20)); // HSLO: as d_adcensus_stm

@@ -1143,6 +1143,13 @@ static int hc_waves(int D, int zd, int usd)
     return 0;
 }
 
+// blocks per image row of a streaming pass whose row has nseg segments
+static int row_split(int nseg) { return nseg > 24 ? cdiv(nseg, 16) : 1; }
+// round 4: a strip's rows in registers in the vertical passes (stm_kernels_aggv.hip); 10000000: the LDS-ring kernel
+static bool chain_vregs(int usd) { return aggv_supports(usd) && (agg_variant() / 10000000) % 10 != 1; }
+// round 4: the row's window range in registers in the last pass + WTA (stm_kernels_aggh.hip); 100000000: the LDS row walk stm_k_pq_hs
+static bool chain_hregs(bool wta, int usd, int D) { return wta && aggh_supports(usd, D) && (agg_variant() / 100000000) % 10 != 1; }
+
 // PX: the frame's two intermediate volumes pixel-major, float index ((y 4G + x) 64 + d) -- a column's 64 hypotheses are 256
 // contiguous bytes, so that stm_k_pq_v12r's waves can own ONE column each.  Only when all three
 // register / streaming kernels run (the cost-fusing stm_k_pq_hc, stm_k_pq_v12r, stm_k_pq_hsr), NC == 4, and the chain ends in
@@ -1151,14 +1158,40 @@ static bool chain_px(bool from_costs, bool wta, int D, int zd, int usd)
 {
     if (usd > 255) usd = 255;
     const int NC = (D + 15) / 16;
-    return from_costs && wta && NC == 4 && aggv_supports(usd) && (agg_variant() / 10000000) % 10 == 0 && aggh_supports(usd, D) &&
-           (agg_variant() / 100000000) % 10 != 1 && hc_waves(D, zd, usd) != 0;
+    return from_costs && NC == 4 && chain_vregs(usd) && (agg_variant() / 10000000) % 10 == 0 && chain_hregs(wta, usd, D) &&
+           hc_waves(D, zd, usd) != 0;
 }
 bool aggm_frame_px(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later)
 {
     (void)H;
     (void)W;
     return !v2_read_later && chain_px(true, !keep_volume, D, zd, usd);
+}
+
+// Which kernels a chain runs, decided in one place for aggm_chain and for the query aggm_frame_path (usd <= 255)
+struct ChainPlan {
+    bool regs, hregs;    // chain_vregs, chain_hregs
+    int hcw;             // hc_waves of a chain that computes its costs in the first pass, else 0
+    int hc_nseg, hc_spl; // stm_k_pq_hc's segments per image row, and its blocks per image row
+};
+static ChainPlan chain_plan(bool from_costs, bool wta, int D, int zd, int W, int usd)
+{
+    ChainPlan c;
+    c.regs = chain_vregs(usd);
+    c.hregs = chain_hregs(wta, usd, D);
+    const bool fuse_cost = from_costs && (agg_variant() / 1000000) % 10 != 1; // 1: separate stm_k_pq_cost + volume-reading first pass
+    c.hcw = fuse_cost ? hc_waves(D, zd, usd) : 0;
+    c.hc_nseg = c.hcw ? cdiv(W, 16 * c.hcw) : 0;
+    c.hc_spl = row_split(c.hc_nseg);
+    return c;
+}
+// the bits 1 .. 16 of stm_agg_path (include/stm_hip.h) for launch_aggm_frame with these arguments
+int aggm_frame_path(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later)
+{
+    if (usd > 255) usd = 255;
+    const ChainPlan c = chain_plan(true, !keep_volume, D, zd, W, usd);
+    return (aggm_frame_px(D, zd, H, W, usd, keep_volume, v2_read_later) ? 2 : 0) | (c.regs ? 4 : 0) | (c.hregs ? 8 : 0) | (c.hcw << 8) |
+           (c.hc_spl > 1 ? 1 << 16 : 0);
 }
 
 // The aggregation chain on PQ volumes for `nviews` views (1 or 2).
@@ -1179,19 +1212,19 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
     pad = (pad < 0 ? 0 : pad) + 15; // + the padded hypotheses of the last chunk
     const size_t smem_cost = smem_h + (size_t)(4 * NG * 4 + 4 * pad + 768 + 72) * 4;
     const bool fuse_cost = from_costs && (agg_variant() / 1000000) % 10 != 1; // 1: separate stm_k_pq_cost + volume-reading first pass
-    const int spl = nseg > 24 ? cdiv(nseg, 16) : 1; // blocks per image row of the streaming passes
+    const int spl = row_split(nseg); // blocks per image row of the streaming passes
+    const ChainPlan plan = chain_plan(from_costs, wta, D, zd, W, usd);
     const bool streaming = NG / 4 >= NW && (agg_variant() / 10) % 10 != 1 && (NC <= 4 || (agg_variant() / 10) % 10 != 2); // the ring is at least one segment long; 20: D > 64 on the block-per-segment kernels as before
     // The window tables of the vertical passes and of the last horizontal pass depend on the arms only; they are built once
     // per call for all views (the horizontal one already by stm_k_cross_arms when the caller passes htab_ready)
     constexpr int NTP = 3, TS = 16 * NTP; // stm_k_pq_v12t: 2 and 4 tiles per pass and step: 0.729 ms each against 0.679
     const int UQ = (usd + 3) & ~3, nT = (H + 15) / 16;
-    const bool regs = aggv_supports(usd) && (agg_variant() / 10000000) % 10 != 1; // round 4: a strip's rows in registers (stm_kernels_aggv.hip); 10000000: the LDS-ring kernel
+    const bool regs = plan.regs;
     const int rec = regs ? aggv_table_rec() : 8 + 8 * ((2 * usd + 21) / 4 + 2); // header + the longest sweep + one quad of read-ahead
     const int LAG = (UQ + TS - 1) / TS + 1;
     const int RQ1 = (TS + 2 * UQ) / 4, RQ2 = (TS * (LAG + 1) + UQ) / 4;
     uint32_t *vtab = regs && vtab_ready ? vtab_ready : Workspace::get<uint32_t>(px ? aggv_col_table_dwords(nviews, H, W) : (size_t)nviews * nT * G * rec);
-    // round 4: the row's window range in registers (stm_kernels_aggh.hip); 100000000: the LDS row walk stm_k_pq_hs
-    const bool hregs = wta && aggh_supports(usd, D) && (agg_variant() / 100000000) % 10 != 1;
+    const bool hregs = plan.hregs;
     uint32_t *htab = !hregs ? nullptr : htab_ready ? htab_ready : Workspace::get<uint32_t>(aggh_table_dwords(nviews, H, W));
     {
         if (!(regs && vtab_ready)) {
@@ -1221,7 +1254,7 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
         const size_t smem_hc = (size_t)4 * NGc * 256 + 16 * NWC * 4 + 8 * NWC + (size_t)(2 * 16 * NWC + 2 * (16 * NWC + 2 * pad)) * 8 + (768 + 72) * 4;
         const int nsegc = cdiv(W, 16 * NWC);
         const size_t smem_hc8 = (size_t)4 * NG * 256 + 16 * NW * 4 + 8 * NW + (size_t)(2 * 16 * NW + 2 * (16 * NW + 2 * pad)) * 8 + (768 + 72) * 4;
-        const int hcw = fuse_cost ? hc_waves(D, zd, usd) : 0;
+        const int hcw = plan.hcw;
 #define STM_HC_LAUNCH(NWX, PXS, GRID, SMEM, NSEG, SPL)                                                                                      \
     {                                                                                                                                     \
         allow_lds_m((const void *)stm_k_pq_hc<NWX, PXS>, SMEM);                                                                            \
@@ -1229,15 +1262,14 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
     }
         if (hcw == NWC) {
             // streaming row walk (the staged pixels fit one per thread); 2000: one block per segment as in round 2
-            const int splc = nsegc > 24 ? cdiv(nsegc, 16) : 1;
-            const dim3 grid(nviews * H * splc);
-            if (px) STM_HC_LAUNCH(NWC, true, grid, smem_hc, nsegc, splc)
-            else STM_HC_LAUNCH(NWC, false, grid, smem_hc, nsegc, splc)
+            const dim3 grid(nviews * H * plan.hc_spl);
+            if (px) STM_HC_LAUNCH(NWC, true, grid, smem_hc, plan.hc_nseg, plan.hc_spl)
+            else STM_HC_LAUNCH(NWC, false, grid, smem_hc, plan.hc_nseg, plan.hc_spl)
         } else if (hcw == NW) {
             // large D (more staged pixels): 128-pixel segments keep two blocks per CU
-            const dim3 grid(nviews * H * spl);
-            if (px) STM_HC_LAUNCH(NW, true, grid, smem_hc8, nseg, spl)
-            else STM_HC_LAUNCH(NW, false, grid, smem_hc8, nseg, spl)
+            const dim3 grid(nviews * H * plan.hc_spl);
+            if (px) STM_HC_LAUNCH(NW, true, grid, smem_hc8, plan.hc_nseg, plan.hc_spl)
+            else STM_HC_LAUNCH(NW, false, grid, smem_hc8, plan.hc_nseg, plan.hc_spl)
         } else if (fuse_cost && smem_c12 <= 80 * 1024 && (agg_variant() / 1000) % 10 != 1) { // 1000: 128-pixel segments as in the other passes
             const int nblkc = ((nsegc * H * nviews + 7) / 8) * 8;
             allow_lds_m((const void *)stm_k_pq_h<NWC, false, true>, smem_c12);
@@ -1301,7 +1333,7 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
 size_t aggm_frame_vtab_dwords(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later, int *rec, int *top, bool *col)
 {
     if (usd > 255) usd = 255;
-    const bool regs = aggv_supports(usd) && (agg_variant() / 10000000) % 10 != 1;
+    const bool regs = chain_vregs(usd);
     *col = aggm_frame_px(D, zd, H, W, usd, keep_volume, v2_read_later);
     *rec = !regs ? 0 : *col ? HR_REC : aggv_table_rec();
     *top = regs ? aggv_table_top() : -1;
@@ -1311,7 +1343,7 @@ size_t aggm_frame_vtab_dwords(int D, int zd, int H, int W, int usd, bool keep_vo
 size_t aggm_frame_htab_dwords(int D, int H, int W, int usd, bool keep_volume)
 {
     if (usd > 255) usd = 255;
-    const bool hregs = !keep_volume && aggh_supports(usd, D) && (agg_variant() / 100000000) % 10 != 1;
+    const bool hregs = chain_hregs(!keep_volume, usd, D);
     return hregs && (agg_variant() / 1000000000) % 10 != 1 ? aggh_table_dwords(2, H, W) : 0; // 1000000000: the stand-alone table kernel
 }
 void launch_aggm_frame(const uint32_t *const *pk, const uint32_t *const *cen, const float *lut, float *const *vol_a, float *const *vol_b,
@@ -1332,7 +1364,7 @@ void launch_aggm_frame(const uint32_t *const *pk, const uint32_t *const *cen, co
 static int vtab_rec(int usd)
 {
     if (usd > 255) usd = 255;
-    const bool regs = aggv_supports(usd) && (agg_variant() / 10000000) % 10 != 1;
+    const bool regs = chain_vregs(usd);
     return regs ? aggv_table_rec() : 8 + 8 * ((2 * usd + 21) / 4 + 2);
 }
 size_t aggm_stage_bytes(int D, int H, int W, int usd)

@@ -43,6 +43,21 @@ class FrameParams:
         self.out_rows, self.out_cols = out_rows, out_cols
 
 
+# stm_agg_path's bit field
+AGG_MATRIX_PIPE, AGG_PX, AGG_VREGS, AGG_HREGS, AGG_SPLIT = 1, 2, 4, 8, 1 << 16
+
+
+def agg_path(num_disp, zero_disp, num_rows, num_cols, usd, stages=3):
+    """stm_agg_path: which aggregation kernels a frame call with these arguments takes under the current stm_set_agg_variant, as a
+    bit field (AGG_*; bits 8..15 = agg_path_waves).  Host arithmetic only: it launches nothing and needs no GPU."""
+    return int(lib().stm_agg_path(int(num_disp), int(zero_disp), int(num_rows), int(num_cols), int(usd), int(stages)))
+
+
+def agg_path_waves(path):
+    """waves per block of the cost-fusing first pass in an agg_path value: 12, 8, or 0 when another kernel runs"""
+    return (int(path) >> 8) & 0xff
+
+
 def set_lens(mode, pitch=0.0, slope=0.0, centre=0.0):
     """stm_set_lens: the calling thread's display geometry, which every rendering frame call interlaces through.  mode 0 = off (the
     reference's interlacer, the default), 1 = nearest view, 2 = two views blended, 3 = every sub-pixel rendered at its own

@@ -1020,15 +1020,18 @@ def test_side_by_side_frame_with_an_odd_column(gpu_ready, orc):
     assert np.array_equal(out.cpu().numpy(), want["interlaced"])
 
 
-def _fuzz_cases(n, seed):
+def _fuzz_cases(n, seed, H=(1, 90), W=(2, 140), D=(1, 41), usd=(1, 41)):
+    """n seeded draws of a frame's shape and of every parameter of adcensus_stm; H, W, D, usd: the half-open ranges of those four
+    (tests/test_gpu_px_forms.py moves them onto the pixel-major chain), everything else from the lists below"""
     rng = np.random.RandomState(seed)
+    rows, cols, disps, arms = H, W, D, usd
     cases = []
     for i in range(n):
-        H = int(rng.randint(1, 90))
-        W = int(rng.randint(2, 140))
-        D = int(rng.randint(1, 41))
+        H = int(rng.randint(*rows))
+        W = int(rng.randint(*cols))
+        D = int(rng.randint(*disps))
         zd = int(rng.randint(0, D)) if rng.rand() < 0.85 else int(rng.randint(-3, D + 4))
-        usd = int(rng.randint(1, 41))
+        usd = int(rng.randint(*arms))
         lsd = int(rng.randint(1, usd + 1))
         views = int(rng.randint(2, 10))
         angle = float(rng.choice([18.43, -18.43, 45.0, 7.0, 60.0, 30.0]))

@@ -35,11 +35,25 @@ def _oracle(orc, sbs, p, H, W):
                             p.usd, p.lsd, p.thresh_s, p.thresh_h)
 
 
-def _check_frame(orc, sbs, p, H, W, variants=(0, PQ_END_TO_END)):
+def _on_px(p, H, W, stages, variant):
+    """stm_agg_path: whether the dispatcher puts this call on the PX layout under `variant`"""
+    import stm_amd
+    from stm_amd import device_api as dev
+    stm_amd.lib().stm_set_agg_variant(variant)
+    try:
+        return bool(dev.agg_path(p.num_disp, p.zero_disp, H, W, p.usd, stages) & dev.AGG_PX)
+    finally:
+        stm_amd.lib().stm_set_agg_variant(0)
+
+
+def _check_frame(orc, sbs, p, H, W, variants=(0, PQ_END_TO_END), px=True):
     """stages = 1 (raw WTA maps) and stages = 3 (the finished frame) of every variant against the oracle -- and so against
-    each other, bit for bit."""
+    each other, bit for bit.  px: whether the case is one for the PX layout; the dispatcher is asked (stm_agg_path), so that a
+    change of its conditions cannot move a case off the path it is here for without failing it."""
     want = _oracle(orc, sbs, p, H, W)
     for variant in variants:
+        for stages in (1, 3):
+            assert _on_px(p, H, W, stages, variant) == (px and variant != PQ_END_TO_END), "PX, variant %d" % variant
         w_l, w_r, _ = _run(sbs, p, 1, H, W, variant)
         assert np.array_equal(w_l, want["wta_l"].astype(np.float32)), "wta_l, variant %d" % variant
         assert np.array_equal(w_r, want["wta_r"].astype(np.float32)), "wta_r, variant %d" % variant
@@ -73,7 +87,7 @@ def test_hypothesis_counts(gpu_ready, orc, D):
     H, W = 37, 67
     p = _params(D)
     sbs, _ = synth.sbs_frame(H, W, p.num_disp, p.zero_disp)
-    _check_frame(orc, sbs, p, H, W)
+    _check_frame(orc, sbs, p, H, W, px=D in (50, 49))
 
 
 @pytest.mark.parametrize("arms", [(36, 18), (1, 1), (37, 18)])
@@ -84,7 +98,7 @@ def test_arm_limits(gpu_ready, orc, arms):
     H, W = 70, 40
     p = _params(64, usd=arms[0], lsd=arms[1])
     sbs, _ = synth.sbs_frame(H, W, p.num_disp, p.zero_disp)
-    _check_frame(orc, sbs, p, H, W)
+    _check_frame(orc, sbs, p, H, W, px=arms[0] <= 36)
 
 
 @pytest.mark.parametrize("seed", [11, 12, 13])
