@@ -111,6 +111,26 @@ int         stm_agg_path(int num_disp, int zero_disp, int num_rows, int num_cols
  * (d_dr_irv.cu:36 -- the bin INDEX, SURVEY A-Q17 iv); 1 = the paper's rule, (winning bin's COUNT) / S > thresh_h (Mei et al.,
  * region voting).  An addition: the reference has no such switch. */
 void        stm_set_irv_paper_ratio(int on);
+/* Region voting over column runs (stm_k_irv_vote_cm) gives a wave `entries` consecutive entries of the outlier list, and from the
+ * second one on it updates the histogram of the region before instead of counting the region anew.  0 (the default) = the
+ * kernel's own rule, max(1, min(16, listed outliers >> 14)), under which a view with fewer than 32768 listed outliers never takes
+ * the update; 1 .. 16 = that many, whatever the list's length (the tests' way to the update at small sizes; results do not
+ * depend on it).  Read when a call enqueues its kernels, like stm_set_irv_paper_ratio.  Returns 0; a refused value is an error like
+ * any other: under stm_set_error_mode(1) the call returns -1 with stm_last_error set and the setting unchanged, under the default
+ * mode 0 the process exits.  An addition: the reference has no such kernel. */
+int         stm_set_irv_chunk(int entries);
+/* Which region-voting kernels a call takes for these arguments under the current stm_set_agg_variant, stm_set_irv_paper_ratio and
+ * stm_set_irv_chunk.  Host arithmetic only: nothing is launched, no device is touched, no argument is screened, and the answer
+ * comes from the very function the calls dispatch through.  device_flavour: 1 = stm_d_dr_irv and the frame calls, 0 = stm_dr_irv
+ * (one vote); with_dcc: 1 = a frame call (both views, the L/R check in front, arms of its own making), 0 = the per-stage calls
+ * (the caller's arm table).  A bit field:
+ *   bit 0        pruning: outliers that can never be accepted are not listed (stm_k_irv_rowcount + stm_k_irv_colprefix, or the chain)
+ *   bit 1        column runs (stm_k_irv_compact_cm, stm_k_irv_vote_cm; 0: the raster list, stm_k_irv_compact, stm_k_irv_vote)
+ *   bit 2        the frame's short chain (stm_k_dcc_irv_rows + stm_k_irv_compact_cm<true>)
+ *   bits 8..11   log2 of the edge of the tiles in which accepted pixels are recorded between iterations
+ *   bits 16..20  the forced entries per trip where column runs vote, else 0
+ * An addition: the reference has one path and no such query. */
+int         stm_irv_path(int num_rows, int num_cols, int usd, int iterations, int device_flavour, int with_dcc);
 /* The calling thread's display geometry (see stm_mux_multiview_lens for the definition and the argument rules); the default is
  * mode 0.  With mode != 0 every frame call that renders -- stm_adcensus_stm, stm_d_adcensus_stm, _t, _nv12, and _2 / _2s in both
  * flavours -- interlaces through that definition instead of the reference's formula; `angle` is then ignored and not screened.

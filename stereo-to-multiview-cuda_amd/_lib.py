@@ -33,6 +33,8 @@ PROTOS = {
     "stm_set_agg_variant": ([i], None),
     "stm_agg_path": ([i, i, i, i, i, i], i),
     "stm_set_irv_paper_ratio": ([i], None),
+    "stm_set_irv_chunk": ([i], i),
+    "stm_irv_path": ([i, i, i, i, i, i], i),
     "stm_set_ref_quirks": ([i], None),
     "stm_set_lens": ([i, d, d, d], i),
     "stm_set_layout": ([i, i, i, i, i], i),

@@ -132,6 +132,7 @@ bool quilt_args_ok(const char *fn, const Layout &lo, int num_views, int in_rows,
                    const char *rows_name, const char *cols_name);
 int quilt_lds_limit(); // stm_set_quilt_lds_limit: the bytes of LDS the area filter's staged kernel may take per workgroup
 int irv_paper_ratio(); // stm_set_irv_paper_ratio: accept on count / S instead of the reference's bin index / S (SURVEY A-Q17 iv)
+int irv_chunk();       // stm_set_irv_chunk: list entries per wave and trip of stm_k_irv_vote_cm, 0 = the kernel's own rule
 // Timing experiments (skip loads / sweeps / stores; results NOT valid) exist only in the separate libstm_hip_timing.so
 // (make timing, -DSTM_TIMING): in the product library every STM_DBG test is the constant false and stm_set_agg_variant
 // accepts result-preserving variants only.
@@ -249,6 +250,8 @@ void launch_dcc(u8 *out_l, u8 *out_r, const float *disp_l, const float *disp_r, 
 void launch_irv(int nviews, float *const *disp, u8 *const *outl, const u8 *const *up, const u8 *const *down,
                 const u8 *const *left, const u8 *const *right, int thresh_s, float thresh_h,
                 int H, int W, int D, int zd, int usd, int iterations, bool device_flavour, bool with_dcc = false);
+// what launch_irv runs for these arguments, as stm_irv_path's bit field (include/stm_hip.h); launches nothing
+int irv_path(int H, int W, int usd, int iterations, bool device_flavour, bool with_dcc);
 void launch_bilateral(const float *in, float *out, const float *spatial, const float *color,
                       int radius, int H, int W, int D);
 // integer_maps: both maps hold integer-valued disparities any two of which differ by less than D (the frame pipeline's own

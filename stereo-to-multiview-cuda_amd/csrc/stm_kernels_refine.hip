@@ -484,11 +484,15 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 // outliers whose cross regions overlap in cache (re-listing through atomics scrambled that and cost 40 %).
 // Pruning: an outlier whose cross region saw no accepted pixel in the previous iteration would repeat its
 // previous vote exactly (the vote is a pure function of the region) and be rejected again, so it is skipped;
-// `dirty` holds one byte per tile (16x16 for usd <= 48) and iteration.
+// `dirty` holds one byte per tile (irv_plan: 16 x 16 up to usd 55 in a frame) and iteration.  The region's box is
+// [x - harm, x + harm] x [y - up, y + down]: only the up arm is clamped to usd, so the horizontal half-width is the longest arm the
+// arm planes can hold -- usd where the frame made them, a byte's 255 where a caller supplied the table (irv_plan picks the tile size
+// so that the box is at most 8 tiles wide).  The down arm is not clamped either: a box of more than 64 tiles (more than a lane
+// each) is not tested at all and the outlier votes.
 // paper_ratio: accept on (winning COUNT) / S > thresh_h (Mei et al.) instead of the reference's (winning BIN INDEX) / S
 // (d_dr_irv.cu:36, SURVEY A-Q17 iv); off by default.
 __global__ __launch_bounds__(64 * IV_WAVES) void stm_k_irv_vote(IrvArgs a, int it, int thresh_s, float thresh_h, int H, int W,
-                                                                int nb, int zd, int usd, int tiles_x, int tiles_y, int tile_sh, int paper_ratio)
+                                                                int nb, int zd, int usd, int harm, int tiles_x, int tiles_y, int tile_sh, int paper_ratio)
 {
     extern __shared__ uint32_t irv_lds[]; // per wave: uint4 slots[nb + 1 + 64]: slot 0 = "other", 1 + b = bin b, then one per lane
     const int v = blockIdx.y;
@@ -536,12 +540,12 @@ __global__ __launch_bounds__(64 * IV_WAVES) void stm_k_irv_vote(IrvArgs a, int i
         cd = min(cd, H - 1 - gy); // caller who passes inconsistent arms from reading outside the planes
         cu = __builtin_amdgcn_readfirstlane(cu);
         cd = __builtin_amdgcn_readfirstlane(cd);
-        if (dirty) { // bounding box of the region = [gx-usd, gx+usd] x [gy-cu, gy+cd]: at most 8x8 tiles (launch_irv picks the tile size)
-            const int tx0 = max(gx - usd, 0) >> tile_sh, tx1 = min(gx + usd, W - 1) >> tile_sh;
+        if (dirty) { // the region's box, [gx-harm, gx+harm] x [gy-cu, gy+cd] (see above the kernel): at most 8 tiles wide
+            const int tx0 = max(gx - harm, 0) >> tile_sh, tx1 = min(gx + harm, W - 1) >> tile_sh;
             const int ty0 = (gy - cu) >> tile_sh, ty1 = (gy + cd) >> tile_sh;
             const int nx = tx1 - tx0 + 1, nt = nx * (ty1 - ty0 + 1);
-            int d = nt > 64; // more tiles than lanes (cannot happen with launch_irv's tile size): do not prune
-            if (lane < nt) d = dirty[(ty0 + lane / nx) * tiles_x + tx0 + lane % nx];
+            int d = nt > 64; // more tiles than lanes (a down arm beyond usd): do not prune
+            if (nt <= 64 && lane < nt) d = dirty[(ty0 + lane / nx) * tiles_x + tx0 + lane % nx];
             if (__ballot(d != 0) == 0) continue; // same region contents as last time -> same vote -> rejected again
         }
         const int nrows = cu + cd + 1; // rows gy-cu .. gy+cd inclusive (SURVEY A-Q17 iii)
@@ -794,8 +798,11 @@ __global__ __launch_bounds__(IC_T) void stm_k_irv_compact_cm(IrvArgs a, uint32_t
         }
 }
 
-__global__ __launch_bounds__(64 * IV_WAVES) void stm_k_irv_vote_cm(IrvArgs a, int it, int thresh_s, float thresh_h, int H, int W,
-                                                                   int nb, int zd, int usd, int tiles_x, int tiles_y, int tile_sh, int paper_ratio)
+// amdgpu_waves_per_eu(7, 7): with the `harm` and `chunk` arguments the register allocation came out at 63 VGPRs instead of 65 and the
+// vote on real content at 52.6 instead of 49.4 us per launch (kernel trace, 1080p); scheduled for seven waves per SIMD -- what 65
+// VGPRs had meant -- region voting on that frame takes 0.299 ms against 0.292 before the arguments (0.315 without the attribute)
+__global__ __launch_bounds__(64 * IV_WAVES) __attribute__((amdgpu_waves_per_eu(7, 7))) void stm_k_irv_vote_cm(IrvArgs a, int it, int thresh_s, float thresh_h, int H, int W,
+                                                                   int nb, int zd, int usd, int harm, int tiles_x, int tiles_y, int tile_sh, int paper_ratio, int chunk)
 {
     extern __shared__ uint32_t irv_lds[]; // per wave: uint4 slots[nb + 1 + 64]: slot 0 = "other", 1 + b = bin b, then one per lane
     const int v = blockIdx.y;
@@ -814,7 +821,8 @@ __global__ __launch_bounds__(64 * IV_WAVES) void stm_k_irv_vote_cm(IrvArgs a, in
     const int n_raw = a.counts[v][0];
     const int n = min(n_raw, H * W); // never past the list (capacity H W), whatever the counter holds
     if (n_raw > H * W && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.diag, 2u);
-    const int chl = max(1, min(IVC_CH, n >> 14)); // entries per trip (1080p, real content: 5; 4 to 16 measured alike, 16 slower)
+    // entries per trip (1080p, real content: 5; 4 to 16 measured alike, 16 slower); chunk: stm_set_irv_chunk's 1 .. IVC_CH, 0 = this rule
+    const int chl = chunk > 0 ? min(chunk, IVC_CH) : max(1, min(IVC_CH, n >> 14));
     const int nchunks = (n + chl - 1) / chl, stride = gridDim.x * IV_WAVES;
     const int half4 = (lane >> 5) * 4, lw = lane & 31;
     const uint32_t l2h = 2u * (uint32_t)lw, lane2 = 2u * lane;
@@ -928,13 +936,13 @@ __global__ __launch_bounds__(64 * IV_WAVES) void stm_k_irv_vote_cm(IrvArgs a, in
             if (cu > usd) cu = usd;   // d_dr_irv.cu:179-180
             cu = min(cu, gy);         // arms built by ca_cross never leave the image; these two clamps only keep a
             cd = min(cd, H - 1 - gy); // caller who passes inconsistent arms from reading outside the planes
-            if (dirty) { // bounding box of the region = [gx-usd, gx+usd] x [gy-cu, gy+cd]: at most 8x8 tiles (launch_irv picks the tile size)
-                const int tx0 = max(gx - usd, 0) >> tile_sh, tx1 = min(gx + usd, W - 1) >> tile_sh;
+            if (dirty) { // the region's box, [gx-harm, gx+harm] x [gy-cu, gy+cd] (see stm_k_irv_vote): at most 8 tiles wide
+                const int tx0 = max(gx - harm, 0) >> tile_sh, tx1 = min(gx + harm, W - 1) >> tile_sh;
                 const int ty0 = (gy - cu) >> tile_sh, ty1 = (gy + cd) >> tile_sh;
                 const int nx = tx1 - tx0 + 1, nt = nx * (ty1 - ty0 + 1);
-                int d = nt > 64; // more tiles than lanes (cannot happen with launch_irv's tile size): do not prune
+                int d = nt > 64; // more tiles than lanes (a down arm beyond usd): do not prune
                 const int lq = (lane * ((0x10000 + nx - 1) / nx)) >> 16; // lane / nx for lane < 64, nx <= 8 (the scalar unit divides once)
-                if (lane < nt) d = dirty[(ty0 + lq) * tiles_x + tx0 + (lane - lq * nx)];
+                if (nt <= 64 && lane < nt) d = dirty[(ty0 + lq) * tiles_x + tx0 + (lane - lq * nx)];
                 if (__ballot(d != 0) == 0) continue; // same region contents as last time -> same vote -> rejected again
             }
             const int t0 = gy - cu, t1 = gy + cd; // rows t0 .. t1 inclusive (SURVEY A-Q17 iii)
@@ -995,6 +1003,47 @@ __global__ __launch_bounds__(64 * IV_WAVES) void stm_k_irv_vote_cm(IrvArgs a, in
     }
 }
 
+// The dispatch of launch_irv, as host arithmetic: stm_irv_path (stm_hip.h) reports it, launch_irv runs it.
+struct IrvPlan {
+    int rounds;  // vote launches
+    int harm;    // the longest horizontal arm the arm planes can hold: the half-width of the dirty box
+    int tile_sh; // log2 of the dirty tiles' edge
+    int chunk;   // stm_set_irv_chunk's value where the column-run kernel votes, else 0
+    bool prune, runs, chain;
+};
+static IrvPlan irv_plan(int H, int W, int usd, int iterations, bool device_flavour, bool with_dcc)
+{
+    IrvPlan pl;
+    const size_t HW = (size_t)H * W;
+    // host flavour (d_dr_irv.cu:344-353): one vote, then `iterations` applies of which only the first can change anything
+    pl.rounds = device_flavour ? std::max(iterations, 0) : (iterations > 0 ? 1 : 0);
+    // dirty tiles: the smallest power of two >= 16 for which a region's bounding box spans at most 8 x 8 tiles.  Vertically the box
+    // is the region's own rows (the up arm is clamped to usd, d_dr_irv.cu:179-180).  Horizontally nothing clamps the arms (neither
+    // here nor in the reference): the frame's own stm_k_cross_arms never makes one longer than usd, a caller's table (dr_irv,
+    // d_dr_irv) holds bytes, so the box is [x - harm, x + harm] cut to the image row
+    const int us = std::min(std::max(usd, 0), 255);
+    pl.harm = with_dcc ? us : 255;
+    pl.tile_sh = 4;
+    while ((2 * us) / (1 << pl.tile_sh) + 2 > 8) ++pl.tile_sh; // (the frame: this alone, as it always was)
+    while (std::min(2 * pl.harm, W - 1) / (1 << pl.tile_sh) + 2 > 8) ++pl.tile_sh;
+    // pruning tables (stm_k_irv_rowcount): not with the paper's accept rule (its numerator is a count: no such bound)
+    pl.prune = !irv_paper_ratio() && W <= 16000;
+    // round 4: the list column-major inside 64 x 64 tiles, a wave votes for runs of a column incrementally; 300: the raster list of round 3
+    // (also for frames too large for the (row, column) entries of the new list)
+    pl.runs = (agg_variant() / 100) % 10 != 3 && H < (1 << 14) && W < (1 << 16);
+    // the frame's short chain: L/R check + row counts + vote codes in one row kernel, column sums inside the compaction kernel
+    // (no stm_k_irv_colprefix, no vp plane); 600: the separate kernels
+    pl.chain = with_dcc && pl.prune && pl.runs && pl.rounds > 0 && HW < IV_LATER && (agg_variant() / 100) % 10 != 6 &&
+               65 + 2 * std::min(usd, 255) <= IC_PF_ROWS && dcc_irv_rows_lds(W) <= 64 * 1024;
+    pl.chunk = pl.runs ? irv_chunk() : 0;
+    return pl;
+}
+int irv_path(int H, int W, int usd, int iterations, bool device_flavour, bool with_dcc)
+{
+    const IrvPlan pl = irv_plan(H, W, usd, iterations, device_flavour, with_dcc);
+    return (pl.prune ? 1 : 0) | (pl.runs ? 2 : 0) | (pl.chain ? 4 : 0) | (pl.tile_sh << 8) | (pl.chunk << 16);
+}
+
 void launch_irv(int nviews, float *const *disp, u8 *const *outl, const u8 *const *up, const u8 *const *down,
                 const u8 *const *left, const u8 *const *right, int thresh_s, float thresh_h, int H, int W, int D, int zd,
                 int usd, int iterations, bool device_flavour, bool with_dcc)
@@ -1005,12 +1054,10 @@ void launch_irv(int nviews, float *const *disp, u8 *const *outl, const u8 *const
         fail("launch_irv: 1 or 2 views (2 with the L/R check)", "nviews", __FILE__, __LINE__);
         return; // only reached in error mode 1
     }
-    // host flavour (d_dr_irv.cu:344-353): one vote, then `iterations` applies of which only the first can change anything
-    const int rounds = device_flavour ? iterations : (iterations > 0 ? 1 : 0);
+    const IrvPlan pl = irv_plan(H, W, usd, iterations, device_flavour, with_dcc);
+    const int rounds = pl.rounds, tile_sh = pl.tile_sh;
+    const bool prune = pl.prune, runs = pl.runs, chain = pl.chain;
     IrvArgs a;
-    // dirty tiles: the smallest power of two >= 16 for which a region's bounding box (2 usd + 1 wide) spans at most 8 x 8 tiles
-    int tile_sh = 4;
-    while ((2 * std::min(usd, 255)) / (1 << tile_sh) + 2 > 8) ++tile_sh;
     const int tiles_x = cdiv(W, 1 << tile_sh), tiles_y = cdiv(H, 1 << tile_sh);
     const size_t dirty_sz = (size_t)(rounds + 1) * tiles_x * tiles_y;
     const size_t ncount = 4; // per view: list length
@@ -1029,15 +1076,6 @@ void launch_irv(int nviews, float *const *disp, u8 *const *outl, const u8 *const
         a.code[v][1] = Workspace::get<uint16_t>(HW + 64);
     }
     if (nviews == 1) { a.list[1] = a.list[0]; a.code[1][0] = a.code[0][0]; a.code[1][1] = a.code[0][1]; }
-    // pruning tables (stm_k_irv_rowcount): not with the paper's accept rule (its numerator is a count: no such bound)
-    const bool prune = !irv_paper_ratio() && W <= 16000;
-    // round 4: the list column-major inside 64 x 64 tiles, a wave votes for runs of a column incrementally; 300: the raster list of round 3
-    // (also for frames too large for the (row, column) entries of the new list)
-    const bool runs = (agg_variant() / 100) % 10 != 3 && H < (1 << 14) && W < (1 << 16);
-    // the frame's short chain: L/R check + row counts + vote codes in one row kernel, column sums inside the compaction kernel
-    // (no stm_k_irv_colprefix, no vp plane); 600: the separate kernels
-    const bool chain = with_dcc && prune && runs && rounds > 0 && HW < IV_LATER && (agg_variant() / 100) % 10 != 6 &&
-                       65 + 2 * std::min(usd, 255) <= IC_PF_ROWS && dcc_irv_rows_lds(W) <= 64 * 1024;
     uint16_t *cnt[2] = {nullptr, nullptr};
     uint32_t *vp[2] = {nullptr, nullptr};
     if (prune)
@@ -1094,10 +1132,10 @@ void launch_irv(int nviews, float *const *disp, u8 *const *outl, const u8 *const
     for (int it = 0; it < rounds; ++it) {
         if (runs)
             STM_LAUNCH(stm_k_irv_vote_cm, dim3(iv_blocks, nviews), dim3(64 * IV_WAVES), smem, stream(), a, it, thresh_s, thresh_h, H,
-                               W, nb, zd, usd, tiles_x, tiles_y, tile_sh, irv_paper_ratio());
+                               W, nb, zd, usd, pl.harm, tiles_x, tiles_y, tile_sh, irv_paper_ratio(), pl.chunk);
         else
             STM_LAUNCH(stm_k_irv_vote, dim3(iv_blocks, nviews), dim3(64 * IV_WAVES), smem, stream(), a, it, thresh_s, thresh_h, H,
-                               W, nb, zd, usd, tiles_x, tiles_y, tile_sh, irv_paper_ratio());
+                               W, nb, zd, usd, pl.harm, tiles_x, tiles_y, tile_sh, irv_paper_ratio());
         STM_CHECK_LAUNCH();
     }
 }

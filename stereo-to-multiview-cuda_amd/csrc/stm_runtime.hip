@@ -232,6 +232,8 @@ static int g_ref_quirks = 0;
 int ref_quirks() { return g_ref_quirks; }
 static int g_irv_paper_ratio = 0;
 int irv_paper_ratio() { return g_irv_paper_ratio; }
+static int g_irv_chunk = 0;
+int irv_chunk() { return g_irv_chunk; }
 // the calling thread's display geometry (stm_set_lens)
 static thread_local Lens g_lens = {0, 0.0, 0.0, 0.0};
 Lens lens() { return g_lens; }
@@ -471,6 +473,22 @@ int stm_prof_read(const char *kernel, float *total_ms)
 }
 void stm_set_ref_quirks(int on) { stm::g_ref_quirks = on ? 1 : 0; }
 void stm_set_irv_paper_ratio(int on) { stm::g_irv_paper_ratio = on ? 1 : 0; }
+int stm_set_irv_chunk(int entries)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (entries < 0 || entries > 16) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "set_irv_chunk: entries = %d, must be 0 (the library's own rule) or 1 .. 16", entries);
+        stm::fail(msg, "entries", __FILE__, __LINE__);
+        return -1; // the setting stays as it was
+    }
+    stm::g_irv_chunk = entries;
+    return 0;
+}
+int stm_irv_path(int num_rows, int num_cols, int usd, int iterations, int device_flavour, int with_dcc)
+{
+    return stm::irv_path(num_rows, num_cols, usd, iterations, device_flavour != 0, with_dcc != 0);
+}
 int stm_set_lens(int mode, double pitch, double slope, double centre)
 {
     if (stm::api_outermost()) stm::clear_failed();

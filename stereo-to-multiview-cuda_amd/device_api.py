@@ -58,6 +58,35 @@ def agg_path_waves(path):
     return (int(path) >> 8) & 0xff
 
 
+# stm_irv_path's bit field
+IRV_PRUNE, IRV_RUNS, IRV_CHAIN = 1, 2, 4
+
+
+def irv_path(num_rows, num_cols, usd, iterations=5, device_flavour=True, with_dcc=False):
+    """stm_irv_path: which region-voting kernels a call with these arguments takes under the current stm_set_agg_variant,
+    stm_set_irv_paper_ratio and stm_set_irv_chunk, as a bit field (IRV_*; irv_path_tile_sh, irv_path_chunk).  with_dcc: a frame
+    call; otherwise d_dr_irv (device_flavour) or dr_irv.  Host arithmetic only: it launches nothing and needs no GPU."""
+    return int(lib().stm_irv_path(int(num_rows), int(num_cols), int(usd), int(iterations), int(bool(device_flavour)), int(bool(with_dcc))))
+
+
+def irv_path_tile_sh(path):
+    """log2 of the dirty tiles' edge in an irv_path value"""
+    return (int(path) >> 8) & 0xf
+
+
+def irv_path_chunk(path):
+    """the forced entries per trip in an irv_path value, 0 = the kernel's own rule"""
+    return (int(path) >> 16) & 0x1f
+
+
+def set_irv_chunk(entries=0):
+    """stm_set_irv_chunk: list entries per wave and trip of the column-run vote kernel; 0 = the kernel's own rule (the default),
+    1 .. 16 = forced.  Raises ValueError where the library refuses (the setting then stays as it was) -- under stm_set_error_mode(1);
+    in the default error mode 0 the library exits, like on any error."""
+    if int(lib().stm_set_irv_chunk(int(entries))) != 0:
+        raise ValueError("stm_set_irv_chunk(%d) refused: %s" % (entries, lib().stm_last_error().decode()))
+
+
 def set_lens(mode, pitch=0.0, slope=0.0, centre=0.0):
     """stm_set_lens: the calling thread's display geometry, which every rendering frame call interlaces through.  mode 0 = off (the
     reference's interlacer, the default), 1 = nearest view, 2 = two views blended, 3 = every sub-pixel rendered at its own
