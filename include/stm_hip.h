@@ -671,6 +671,65 @@ void stm_d_adcensus_stm_2s(unsigned char *d_img_sbs, float *d_disp_l, float *d_d
                            int num_views, float angle, int num_disp, int zero_disp,
                            float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
                            int thresh_s, float thresh_h, int stages);
+/* The reduced-resolution frame for frame sequences (an addition).  stm_d_adcensus_stm_2t is stm_d_adcensus_stm_2s with the history
+ * of the temporal stabilisation: stm_d_adcensus_stm_2s's arguments, then stm_d_adcensus_stm_t's six history arguments.
+ *   stages   low byte 3; 0x100, 0x200, 0x400, 0x800, 0x1000 as stm_d_adcensus_stm_2s; 0x2000 = temporal stabilisation with
+ *            stm_d_adcensus_stm_t's rules: the three history pointers all null (the first frame: the bit does nothing) or all set, no
+ *            history map aliasing d_disp_l / d_disp_r, stm_disp_temporal's parameter rules, num_cols_sbs >= 2 * num_cols with a history.
+ * The temporal step runs on the UP-SCALED full-size maps (after tx_disp_scale, or after the guided up-sampler with 0x1000) with the
+ * two full-size side-by-side frames, and before the render: the same placement as in the full-resolution frame, on the final maps.
+ * So d_prev_disp_l / d_prev_disp_r are the previous call's d_disp_l / d_disp_r (num_rows x num_cols).
+ * stm_d_adcensus_stm_2nv12 is the same frame on NV12 planes: stm_d_adcensus_stm_nv12's arguments with num_rows_disp, num_cols_disp
+ * after num_cols_out and disp_scale after elem_sz (stm_d_adcensus_stm_2s's places), stm_demux_nv12's geometry rules, and
+ * stm_d_adcensus_stm_nv12's rules for the four history pointers and for d_img_l / d_img_r (both or neither; required with 0x2000).
+ * The reduced pair is tx_scale_bilinear of the CONVERTED split images.
+ * 0x300, any other low byte and any other bit are errors; a packing set on the thread (stm_set_packing) is refused.  Every error is
+ * reported (stm_last_error) before anything is launched; the caller's buffers are not touched.  stm_d_adcensus_stm_2s itself keeps
+ * rejecting 0x2000.  Without 0x2000 and history, stm_d_adcensus_stm_2t is stm_d_adcensus_stm_2s bit for bit. */
+void stm_d_adcensus_stm_2t(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                           int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
+                           int num_rows_disp, int num_cols_disp, int elem_sz, float disp_scale,
+                           int num_views, float angle, int num_disp, int zero_disp,
+                           float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
+                           int thresh_s, float thresh_h, int stages,
+                           unsigned char *d_prev_img_sbs, float *d_prev_disp_l, float *d_prev_disp_r,
+                           float alpha, int thresh_color, float thresh_disp);
+void stm_d_adcensus_stm_2nv12(unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv, int matrix,
+                              float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                              int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
+                              int num_rows_disp, int num_cols_disp, int elem_sz, float disp_scale,
+                              int num_views, float angle, int num_disp, int zero_disp,
+                              float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
+                              int thresh_s, float thresh_h, int stages,
+                              unsigned char *d_prev_img_l, unsigned char *d_prev_img_r, float *d_prev_disp_l, float *d_prev_disp_r,
+                              float alpha, int thresh_color, float thresh_disp,
+                              unsigned char *d_img_l, unsigned char *d_img_r);
+/* The front of the reduced-resolution frame as a stage (an addition): from one side-by-side frame
+ *   img_l, img_r      the two full-size split images, num_rows x num_cols x elem_sz (stm_d_demux_sbs's);
+ *   low_l, low_r      the two reduced images, num_rows_disp x num_cols_disp x elem_sz: tx_scale_bilinear of img_l / img_r bit for bit
+ *                     (the taps never cross from one eye into the other);
+ *   census_l, _r      u32 planes of num_rows_disp x num_cols_disp: the low 32 bits of the reduced images' census transform, the word
+ *                     the cost kernels read (window rows -1, +1, +2, +3; in a row x = -4 .. 4 without 0; MSB first).  Both null: not
+ *                     returned.
+ * Only the first three bytes of a pixel are written by the device flavour; the host flavour returns the bytes past the third as 0.
+ * With num_cols_sbs >= 2 * num_cols all of it is one kernel launch (the same launch the reduced-resolution frame calls start with);
+ * a narrower frame, and stm_set_agg_variant(600), run the chain of stages it replaces, with equal results.  Any sizes >= 1 are
+ * legal, num_rows_disp >= num_rows included.  The _nv12_ calls take the NV12 planes of stm_demux_nv12 (its geometry rules, W =
+ * num_cols) in place of the frame: the reduced images are tx_scale_bilinear of the converted split images.  Errors (stm_last_error),
+ * all reported before anything is launched or written: a size < 1, elem_sz < 3, exactly one census plane null, the NV12 rules. */
+void stm_demux_sbs_low(unsigned char *img_l, unsigned char *img_r, unsigned char *low_l, unsigned char *low_r,
+                       unsigned int *census_l, unsigned int *census_r, unsigned char *img_sbs,
+                       int num_rows, int num_cols_sbs, int num_cols, int num_rows_disp, int num_cols_disp, int elem_sz);
+void stm_d_demux_sbs_low(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_low_l, unsigned char *d_low_r,
+                         unsigned int *d_census_l, unsigned int *d_census_r, unsigned char *d_img_sbs,
+                         int num_rows, int num_cols_sbs, int num_cols, int num_rows_disp, int num_cols_disp, int elem_sz);
+void stm_demux_nv12_low(unsigned char *img_l, unsigned char *img_r, unsigned char *low_l, unsigned char *low_r,
+                        unsigned int *census_l, unsigned int *census_r, unsigned char *y, int pitch_y, unsigned char *uv, int pitch_uv,
+                        int num_rows, int num_cols_sbs, int num_cols, int num_rows_disp, int num_cols_disp, int elem_sz, int matrix);
+void stm_d_demux_nv12_low(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_low_l, unsigned char *d_low_r,
+                          unsigned int *d_census_l, unsigned int *d_census_r, unsigned char *d_y, int pitch_y, unsigned char *d_uv,
+                          int pitch_uv, int num_rows, int num_cols_sbs, int num_cols, int num_rows_disp, int num_cols_disp, int elem_sz,
+                          int matrix);
 /* Guided disparity up-sampling (joint bilateral upsampling, Kopf et al. 2007; an addition: the reference's tx_disp_scale_kernel
  * blends four low-resolution values whatever the image shows, which smears every depth edge).  disp_low (f32, in_rows x in_cols)
  * is the map to scale up, img_low (u8, in_rows x in_cols x elem_sz) the image it was computed on, img (u8, out_rows x out_cols x
@@ -776,11 +835,19 @@ void *stm_stream_create(int num_rows, int num_cols_sbs, int num_cols, int num_ro
  * Returns the frame index, or -1 if both slots are uncollected. */
 long  stm_stream_submit(void *stream, const unsigned char *img_sbs);
 /* the `stages` word the stream's frames are computed with: 3 (the default), optionally OR-ed with 0x200, 0x400, 0x800 and / or
- * 0x2000 (not 0x100, not 0x1000).  With 0x2000 every frame but the first is an stm_d_adcensus_stm_t call whose history is the
+ * 0x2000 (not 0x100; 0x1000 only after stm_stream_set_match_size).  With 0x2000 every frame but the first is an stm_d_adcensus_stm_t call whose history is the
  * frame before it (its input and its stabilised maps, which stay in the stream's other buffer slot); the two frames in flight
  * then run one after the other on the GPU, while upload and download still overlap.  A history reset at a scene cut is not
  * offered: the colour gate refuses to blend across one.  Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
 int   stm_stream_set_stages(void *stream, int stages);
+/* the size every frame of the stream is matched at: with num_rows_disp x num_cols_disp set, a frame is the reduced-resolution frame
+ * with this disp_scale -- an stm_d_adcensus_stm_2s call, stm_d_adcensus_stm_2t with 0x2000 in the stream's stages, or
+ * stm_d_adcensus_stm_2nv12 in NV12 mode, picked as the full-resolution calls are -- and stm_stream_set_stages also accepts 0x1000.
+ * (0, 0, any) = off, the default.  Otherwise both sizes must be >= 1 and disp_scale finite and > 0.  Lens, layout and depth reach the
+ * reduced frame's render as they reach the full-resolution one.  Errors: after the first submit; together with a packing of the
+ * stream, in whichever order the two setters are called; switching it off while the stream's stages hold 0x1000.  Returns 0, or -1
+ * with stm_last_error set and the stream unchanged. */
+int   stm_stream_set_match_size(void *stream, int num_rows_disp, int num_cols_disp, float disp_scale);
 /* the parameters of the temporal step of a stream whose stages carry 0x2000 (stm_disp_temporal's rules; defaults 0.5, 24, 1.5).
  * Only before the first submit.  Returns 0, or -1 with stm_last_error set. */
 int   stm_stream_set_temporal(void *stream, float alpha, int thresh_color, float thresh_disp);

@@ -14,6 +14,7 @@ if os.environ.get("STM_LIB") == "timing":
 
 u8p = C.POINTER(C.c_uint8)
 f32p = C.POINTER(C.c_float)
+u32p = C.POINTER(C.c_uint32)
 u8pp = C.POINTER(u8p)
 f32pp = C.POINTER(f32p)
 vp = C.c_void_p
@@ -101,6 +102,13 @@ PROTOS = {
     "stm_d_adcensus_stm_2": ([vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, f, i, i, f, f, f, f, i, i, i, f], None),
     "stm_adcensus_stm_2s": ([u8p, f32p, f32p, u8p, i, i, i, i, i, i, i, i, f, i, f, i, i, f, f, f, f, i, i, i, f, i], None),
     "stm_d_adcensus_stm_2s": ([vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, f, i, i, f, f, f, f, i, i, i, f, i], None),
+    "stm_d_adcensus_stm_2t": ([vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, f, i, i, f, f, f, f, i, i, i, f, i, vp, vp, vp, f, i, f], None),
+    "stm_d_adcensus_stm_2nv12": ([vp, i, vp, i, i, vp, vp, vp, i, i, i, i, i, i, i, i, f, i, f, i, i, f, f, f, f, i, i, i, f, i, vp, vp, vp, vp,
+                                  f, i, f, vp, vp], None),
+    "stm_demux_sbs_low": ([u8p, u8p, u8p, u8p, u32p, u32p, u8p, i, i, i, i, i, i], None),
+    "stm_d_demux_sbs_low": ([vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i], None),
+    "stm_demux_nv12_low": ([u8p, u8p, u8p, u8p, u32p, u32p, u8p, i, u8p, i, i, i, i, i, i, i, i], None),
+    "stm_d_demux_nv12_low": ([vp, vp, vp, vp, vp, vp, vp, i, vp, i, i, i, i, i, i, i, i], None),
     "stm_disp_upsample": ([f32p, f32p, u8p, u8p, i, i, i, i, i, f, f], None),
     "stm_d_disp_upsample": ([vp, vp, vp, vp, i, i, i, i, i, f, f], None),
     "stm_disp_temporal": ([f32p, f32p, u8p, u8p, i, i, i, f, i, f], None),
@@ -111,6 +119,7 @@ PROTOS = {
     "stm_stream_create": ([i, i, i, i, i, i, i, f, i, i, f, f, f, f, i, i, i, f], C.c_void_p),
     "stm_stream_submit": ([C.c_void_p, u8p], C.c_long),
     "stm_stream_set_stages": ([C.c_void_p, i], i),
+    "stm_stream_set_match_size": ([C.c_void_p, i, i, f], i),
     "stm_stream_set_temporal": ([C.c_void_p, f, i, f], i),
     "stm_stream_set_input": ([C.c_void_p, i, i], i),
     "stm_stream_set_packing": ([C.c_void_p, i, i, i, i], i),

@@ -1710,8 +1710,9 @@ void stm_d_adcensus_stm_nv12(unsigned char *d_y, int pitch_y, unsigned char *d_u
 } // extern "C"
 namespace {
 
+// temporal_ok: the call has the history arguments of stages bit 0x2000 (d_adcensus_stm_2t, d_adcensus_stm_2nv12)
 bool reduced_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int num_rows_disp,
-                     int num_cols_disp, int elem_sz, int num_views, int num_disp, int stages)
+                     int num_cols_disp, int elem_sz, int num_views, int num_disp, int stages, bool temporal_ok = false)
 {
     if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols", num_cols, 1},
                       {"num_rows_out", num_rows_out, 1}, {"num_cols_out", num_cols_out, 1}, {"num_rows_disp", num_rows_disp, 1},
@@ -1720,8 +1721,9 @@ bool reduced_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_col
         return false;
     if (packing_unsupported(fn)) return false;
     char msg[200];
-    if ((stages & 0xff) != 3 || (stages & ~0x1fff)) { // this path always renders
-        snprintf(msg, sizeof msg, "%s: stages = 0x%x, must be 3, optionally OR-ed with 0x100, 0x200, 0x400, 0x800 and 0x1000", fn, stages);
+    if ((stages & 0xff) != 3 || (stages & ~(temporal_ok ? 0x3fff : 0x1fff))) { // this path always renders
+        snprintf(msg, sizeof msg, "%s: stages = 0x%x, must be 3, optionally OR-ed with 0x100, 0x200, 0x400, 0x800%s 0x1000%s", fn, stages,
+                 temporal_ok ? "," : " and", temporal_ok ? " and 0x2000" : "");
         fail(msg, "stages", __FILE__, __LINE__);
         return false;
     }
@@ -1733,11 +1735,26 @@ bool reduced_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_col
     return true;
 }
 
+// the reduced pair's front as the parent of stm_k_front_low ran it and as narrow frames and stm_set_agg_variant(600) still do: the
+// split (NV12: the plain converter) and one reduction per view; the pixel formats and the census follow in frame_disparity
+void reduced_front_chain(u8 *img_l, u8 *img_r, u8 *low_l, u8 *low_r, const u8 *d_img_sbs, int num_cols_sbs, const Nv12Input *nv, int H, int W,
+                         int h, int w, int elem_sz)
+{
+    if (nv) launch_demux_nv12(img_l, img_r, nv->y, nv->pitch_y, nv->uv, nv->pitch_uv, H, W, elem_sz, nv->matrix);
+    else launch_demux_sbs(img_l, img_r, d_img_sbs, H, num_cols_sbs, W, elem_sz);
+    launch_scale_bilinear(img_l, low_l, H, W, h, w, elem_sz);
+    launch_scale_bilinear(img_r, low_r, H, W, h, w, elem_sz);
+}
+bool reduced_front_fused(int num_cols_sbs, int W) { return num_cols_sbs >= 2 * W && (agg_variant() / 100) % 10 != 6; }
+
+// the body of the reduced-resolution frame calls; hist != nullptr: the temporal step on the up-scaled full-size maps, between the
+// up-scale and the renderer (the placement rule of frame_device: on the final maps); nv != nullptr: the frame comes as NV12 planes
+// (d_img_sbs is null, num_cols_sbs >= 2 W).  temporal_ok: the caller has screened bit 0x2000 and taken it out of `stages`.
 void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
                           int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int num_rows_disp,
                           int num_cols_disp, int elem_sz, float disp_scale, int num_views, float angle, int num_disp, int zero_disp,
                           float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h,
-                          int stages)
+                          int stages, const TemporalHist *hist = nullptr, const Nv12Input *nv = nullptr)
 {
     if (!reduced_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp, num_cols_disp, elem_sz,
                          num_views, num_disp, stages))
@@ -1749,16 +1766,27 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
     const bool hslo = stages_hslo(stages), subpix = stages_subpix(stages), interp = (stages & 0x400) != 0; // on the reduced pair
     const bool linwarp = (stages & 0x800) != 0;                                                             // in the full-size render
     const bool guided = (stages & 0x1000) != 0; // the up-scale between the two: stm_disp_upsample instead of tx_disp_scale
-    Workspace::begin((hslo ? 13 : 4) * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 8 * hw + (1u << 20)); // HSLO: as d_adcensus_stm
-    u8 *img_l = Workspace::get<u8>(IMG), *img_r = Workspace::get<u8>(IMG);
-    launch_demux_sbs(img_l, img_r, d_img_sbs, H, num_cols_sbs, W, elem_sz);
+    Workspace::begin((hslo ? 13 : 4) * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 32 * hw + (1u << 20)); // HSLO: as d_adcensus_stm
+    const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
+    u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     u8 *low_l = Workspace::get<u8>(hw * elem_sz), *low_r = Workspace::get<u8>(hw * elem_sz);
-    launch_scale_bilinear(img_l, low_l, H, W, h, w, elem_sz);
-    launch_scale_bilinear(img_r, low_r, H, W, h, w, elem_sz);
+    uint32_t *pre[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const bool fused = reduced_front_fused(num_cols_sbs, W); // both halves complete; 600: the chain of kernels
+    {
+        ProfScope p("reduced_front");
+        if (fused) { // the split, both reductions, the reduced pair's pixel formats and census words in one launch
+            for (int i = 0; i < 6; ++i) pre[i] = Workspace::get<uint32_t>(hw);
+            launch_front_low(img_l, img_r, low_l, low_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], nv ? nullptr : d_img_sbs, num_cols_sbs,
+                             nv ? nv->y : nullptr, nv ? nv->pitch_y : 0, nv ? nv->uv : nullptr, nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0, H, W,
+                             h, w, elem_sz);
+        } else {
+            reduced_front_chain(img_l, img_r, low_l, low_r, d_img_sbs, num_cols_sbs, nv, H, W, h, w, elem_sz);
+        }
+    }
     float *low_dl = Workspace::get<float>(hw), *low_dr = Workspace::get<float>(hw);
     Arms al, ar;
     frame_disparity(low_l, low_r, low_dl, low_dr, al, ar, h, w, elem_sz, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd,
-                    usd, lsd, thresh_s, thresh_h, true, hslo, nullptr, subpix, interp);
+                    usd, lsd, thresh_s, thresh_h, true, hslo, fused ? pre : nullptr, subpix, interp);
     const float up = 1.0f / disp_scale; // :415
     if (guided) { // each map guided by its own view: the full-size image the views are rendered from against the image the match ran on
         float *o[2] = {d_disp_l, d_disp_r};
@@ -1768,6 +1796,16 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
     } else {
         launch_disp_scale(d_disp_l, low_dl, H, W, h, w, up);
         launch_disp_scale(d_disp_r, low_dr, H, W, h, w, up);
+    }
+    // temporal stabilisation (0x2000), as in frame_device: each view on its own half of the two side-by-side frames, read in place,
+    // or -- for an NV12 frame -- on the two frames' converted split images
+    if (hist) {
+        float *c[2] = {d_disp_l, d_disp_r};
+        const float *q[2] = {hist->disp_l, hist->disp_r};
+        const bool split = nv != nullptr;
+        const u8 *im[2] = {split ? img_l : d_img_sbs, split ? img_r : d_img_sbs}, *ip[2] = {split ? hist->img_l : hist->sbs, split ? hist->img_r : hist->sbs};
+        const size_t off[2] = {0, split ? 0 : (size_t)W * elem_sz};
+        launch_disp_temporal(2, c, q, im, ip, off, H, W, split ? W : num_cols_sbs, elem_sz, hist->alpha, hist->thresh_color, hist->thresh_disp);
     }
     frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle, linwarp);
 }
@@ -1820,6 +1858,218 @@ void stm_d_adcensus_stm_2s(unsigned char *d_img_sbs, float *d_disp_l, float *d_d
     reduced_frame_device("d_adcensus_stm_2s", d_img_sbs, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out,
                          num_cols_out, num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp,
                          ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages);
+}
+
+// stm_d_adcensus_stm_2s with the history of the temporal stabilisation (stm_hip.h): stm_d_adcensus_stm_t's rules for bit 0x2000
+void stm_d_adcensus_stm_2t(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                           int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
+                           int num_rows_disp, int num_cols_disp, int elem_sz, float disp_scale, int num_views, float angle,
+                           int num_disp, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd,
+                           int lsd, int thresh_s, float thresh_h, int stages, unsigned char *d_prev_img_sbs, float *d_prev_disp_l,
+                           float *d_prev_disp_r, float alpha, int thresh_color, float thresh_disp)
+{
+    const char *fn = "d_adcensus_stm_2t";
+    if (!reduced_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp, num_cols_disp, elem_sz, num_views,
+                         num_disp, stages, true))
+        return;
+    TemporalHist hist = {d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp};
+    bool run = false;
+    if (stages & 0x2000) {
+        const int nset = (d_prev_img_sbs != nullptr) + (d_prev_disp_l != nullptr) + (d_prev_disp_r != nullptr);
+        const size_t HW = (size_t)num_rows * num_cols;
+        if (!temporal_params_ok(fn, alpha, thresh_color, thresh_disp)) return;
+        if (nset != 0 && nset != 3) {
+            fail("d_adcensus_stm_2t: the three history pointers must be all null (first frame) or all set",
+                 "d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
+            return;
+        }
+        if (nset == 3 && num_cols_sbs < 2 * num_cols) { // the views are read from the two halves in place
+            fail("d_adcensus_stm_2t: stages 0x2000 (temporal stabilisation) needs num_cols_sbs >= 2 * num_cols", "num_cols_sbs", __FILE__, __LINE__);
+            return;
+        }
+        if (nset == 3 && (maps_overlap(d_prev_disp_l, d_disp_l, HW) || maps_overlap(d_prev_disp_l, d_disp_r, HW) ||
+                          maps_overlap(d_prev_disp_r, d_disp_l, HW) || maps_overlap(d_prev_disp_r, d_disp_r, HW))) {
+            fail("d_adcensus_stm_2t: a history map must not alias d_disp_l or d_disp_r", "d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
+            return;
+        }
+        run = nset == 3;
+    }
+    reduced_frame_device(fn, d_img_sbs, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out,
+                         num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff,
+                         ucd, lcd, usd, lsd, thresh_s, thresh_h, stages & ~0x2000, run ? &hist : nullptr);
+}
+
+// stm_d_adcensus_stm_2t on an NV12 frame (stm_hip.h): stm_d_adcensus_stm_nv12's rules, the conversion fused into the front kernel
+void stm_d_adcensus_stm_2nv12(unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv, int matrix, float *d_disp_l, float *d_disp_r,
+                              unsigned char *d_interlaced, int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
+                              int num_rows_disp, int num_cols_disp, int elem_sz, float disp_scale, int num_views, float angle, int num_disp,
+                              int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd, int thresh_s,
+                              float thresh_h, int stages, unsigned char *d_prev_img_l, unsigned char *d_prev_img_r, float *d_prev_disp_l,
+                              float *d_prev_disp_r, float alpha, int thresh_color, float thresh_disp, unsigned char *d_img_l,
+                              unsigned char *d_img_r)
+{
+    const char *fn = "d_adcensus_stm_2nv12";
+    if (!reduced_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp, num_cols_disp, elem_sz, num_views,
+                         num_disp, stages, true))
+        return;
+    if (!nv12_args_ok(fn, num_rows, num_cols_sbs, num_cols, "num_cols", pitch_y, pitch_uv, matrix)) return;
+    if ((d_img_l != nullptr) != (d_img_r != nullptr)) {
+        fail("d_adcensus_stm_2nv12: d_img_l and d_img_r must be both null (the split images stay in the workspace) or both set", "d_img_l, d_img_r",
+             __FILE__, __LINE__);
+        return;
+    }
+    TemporalHist hist = {nullptr, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp, d_prev_img_l, d_prev_img_r};
+    Nv12Input nv = {d_y, d_uv, pitch_y, pitch_uv, matrix, d_img_l, d_img_r};
+    bool run = false;
+    if (stages & 0x2000) {
+        const int nset = (d_prev_img_l != nullptr) + (d_prev_img_r != nullptr) + (d_prev_disp_l != nullptr) + (d_prev_disp_r != nullptr);
+        const size_t HW = (size_t)num_rows * num_cols, IMG = HW * elem_sz;
+        if (!temporal_params_ok(fn, alpha, thresh_color, thresh_disp)) return;
+        if (!d_img_l) { // this frame's converted images are the next frame's history: the caller must keep them
+            fail("d_adcensus_stm_2nv12: stages 0x2000 (temporal stabilisation) needs the output images d_img_l and d_img_r", "d_img_l, d_img_r",
+                 __FILE__, __LINE__);
+            return;
+        }
+        if (nset != 0 && nset != 4) {
+            fail("d_adcensus_stm_2nv12: the four history pointers must be all null (first frame) or all set",
+                 "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
+            return;
+        }
+        if (nset == 4) { // the history is read while the outputs are written
+            const void *hp[4] = {d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r}, *o[4] = {d_img_l, d_img_r, d_disp_l, d_disp_r};
+            const size_t sz[4] = {IMG, IMG, HW * 4, HW * 4};
+            for (int i = 0; i < 4; ++i)
+                for (int j = 0; j < 4; ++j)
+                    if (bytes_overlap(hp[i], sz[i], o[j], sz[j])) {
+                        fail("d_adcensus_stm_2nv12: a history buffer must not alias an output (d_img_l, d_img_r, d_disp_l, d_disp_r)",
+                             "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
+                        return;
+                    }
+        }
+        run = nset == 4;
+    }
+    reduced_frame_device(fn, nullptr, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out,
+                         num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff,
+                         ucd, lcd, usd, lsd, thresh_s, thresh_h, stages & ~0x2000, run ? &hist : nullptr, &nv);
+}
+
+// the reduced-resolution frame's front as a stage (stm_hip.h): stm_k_front_low itself, the BGRX and wide planes in the workspace;
+// num_cols_sbs < 2 * num_cols and stm_set_agg_variant(600): the chain of kernels it replaces
+} // extern "C"
+namespace {
+bool front_low_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, int num_rows_disp, int num_cols_disp, int elem_sz,
+                       const void *census_l, const void *census_r)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols", num_cols, 1},
+                      {"num_rows_disp", num_rows_disp, 1}, {"num_cols_disp", num_cols_disp, 1}, {"elem_sz", elem_sz, 3}}))
+        return false;
+    if ((census_l != nullptr) != (census_r != nullptr)) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: the two census planes must be both null or both set", fn);
+        fail(msg, "census_l, census_r", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
+// inside a Workspace scope; cen_l / cen_r both null: the census words stay in the workspace
+void front_low_device(u8 *img_l, u8 *img_r, u8 *low_l, u8 *low_r, uint32_t *cen_l, uint32_t *cen_r, const u8 *d_img_sbs, int num_cols_sbs,
+                      const Nv12Input *nv, int H, int W, int h, int w, int elem_sz)
+{
+    const size_t hw = (size_t)h * w;
+    uint32_t *pl[4];
+    for (int i = 0; i < 4; ++i) pl[i] = Workspace::get<uint32_t>(hw);
+    const bool want_census = cen_l != nullptr;
+    if (!want_census) {
+        cen_l = Workspace::get<uint32_t>(hw);
+        cen_r = Workspace::get<uint32_t>(hw);
+    }
+    if (reduced_front_fused(num_cols_sbs, W)) {
+        launch_front_low(img_l, img_r, low_l, low_r, pl[0], pl[1], pl[2], pl[3], cen_l, cen_r, nv ? nullptr : d_img_sbs, num_cols_sbs,
+                         nv ? nv->y : nullptr, nv ? nv->pitch_y : 0, nv ? nv->uv : nullptr, nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0, H, W, h, w,
+                         elem_sz);
+        return;
+    }
+    reduced_front_chain(img_l, img_r, low_l, low_r, d_img_sbs, num_cols_sbs, nv, H, W, h, w, elem_sz);
+    if (!want_census) return;
+    launch_pack_bgrx(low_l, pl[0], h, w, elem_sz);
+    launch_pack_bgrx(low_r, pl[1], h, w, elem_sz);
+    launch_census32_pair(pl[0], cen_l, pl[1], cen_r, h, w);
+}
+// the host flavour of both stage calls: the input already uploaded
+void front_low_host(unsigned char *img_l, unsigned char *img_r, unsigned char *low_l, unsigned char *low_r, unsigned int *census_l,
+                    unsigned int *census_r, const u8 *d_img_sbs, int num_cols_sbs, const Nv12Input *nv, int H, int W, int h, int w, int elem_sz)
+{
+    const size_t IMG = (size_t)H * W * elem_sz, hw = (size_t)h * w, LOW = hw * elem_sz;
+    u8 *l = Workspace::get<u8>(IMG), *r = Workspace::get<u8>(IMG), *ll = Workspace::get<u8>(LOW), *lr = Workspace::get<u8>(LOW);
+    uint32_t *cl = census_l ? Workspace::get<uint32_t>(hw) : nullptr, *cr = census_l ? Workspace::get<uint32_t>(hw) : nullptr;
+    if (elem_sz > 3) { // bytes past a pixel's third come back 0, not as the workspace held them
+        STM_CHECK(hipMemsetAsync(l, 0, IMG, stream()));
+        STM_CHECK(hipMemsetAsync(r, 0, IMG, stream()));
+        STM_CHECK(hipMemsetAsync(ll, 0, LOW, stream()));
+        STM_CHECK(hipMemsetAsync(lr, 0, LOW, stream()));
+    }
+    front_low_device(l, r, ll, lr, cl, cr, d_img_sbs, num_cols_sbs, nv, H, W, h, w, elem_sz);
+    down(img_l, l, IMG); down(img_r, r, IMG); down(low_l, ll, LOW); down(low_r, lr, LOW);
+    if (census_l) {
+        down(census_l, cl, hw);
+        down(census_r, cr, hw);
+    }
+    sync();
+}
+} // namespace
+extern "C" {
+
+void stm_d_demux_sbs_low(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_low_l, unsigned char *d_low_r,
+                         unsigned int *d_census_l, unsigned int *d_census_r, unsigned char *d_img_sbs, int num_rows, int num_cols_sbs,
+                         int num_cols, int num_rows_disp, int num_cols_disp, int elem_sz)
+{
+    const char *fn = "d_demux_sbs_low";
+    if (!front_low_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_disp, num_cols_disp, elem_sz, d_census_l, d_census_r)) return;
+    Workspace::begin((size_t)num_rows_disp * num_cols_disp * 24 + 8192);
+    front_low_device(d_img_l, d_img_r, d_low_l, d_low_r, d_census_l, d_census_r, d_img_sbs, num_cols_sbs, nullptr, num_rows, num_cols,
+                     num_rows_disp, num_cols_disp, elem_sz);
+}
+void stm_demux_sbs_low(unsigned char *img_l, unsigned char *img_r, unsigned char *low_l, unsigned char *low_r, unsigned int *census_l,
+                       unsigned int *census_r, unsigned char *img_sbs, int num_rows, int num_cols_sbs, int num_cols, int num_rows_disp,
+                       int num_cols_disp, int elem_sz)
+{
+    const char *fn = "demux_sbs_low";
+    if (!front_low_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_disp, num_cols_disp, elem_sz, census_l, census_r)) return;
+    const size_t IMG = (size_t)num_rows * num_cols * elem_sz, hw = (size_t)num_rows_disp * num_cols_disp;
+    const size_t in_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
+    Workspace::begin(2 * IMG + in_sz + hw * (2 * (size_t)elem_sz + 32) + 16384);
+    u8 *d = up(img_sbs, in_sz);
+    front_low_host(img_l, img_r, low_l, low_r, census_l, census_r, d, num_cols_sbs, nullptr, num_rows, num_cols, num_rows_disp, num_cols_disp,
+                   elem_sz);
+}
+void stm_d_demux_nv12_low(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_low_l, unsigned char *d_low_r,
+                          unsigned int *d_census_l, unsigned int *d_census_r, unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv,
+                          int num_rows, int num_cols_sbs, int num_cols, int num_rows_disp, int num_cols_disp, int elem_sz, int matrix)
+{
+    const char *fn = "d_demux_nv12_low";
+    if (!front_low_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_disp, num_cols_disp, elem_sz, d_census_l, d_census_r)) return;
+    if (!nv12_args_ok(fn, num_rows, num_cols_sbs, num_cols, "num_cols", pitch_y, pitch_uv, matrix)) return;
+    const Nv12Input nv = {d_y, d_uv, pitch_y, pitch_uv, matrix, nullptr, nullptr};
+    Workspace::begin((size_t)num_rows_disp * num_cols_disp * 24 + 8192);
+    front_low_device(d_img_l, d_img_r, d_low_l, d_low_r, d_census_l, d_census_r, nullptr, num_cols_sbs, &nv, num_rows, num_cols,
+                     num_rows_disp, num_cols_disp, elem_sz);
+}
+void stm_demux_nv12_low(unsigned char *img_l, unsigned char *img_r, unsigned char *low_l, unsigned char *low_r, unsigned int *census_l,
+                        unsigned int *census_r, unsigned char *y, int pitch_y, unsigned char *uv, int pitch_uv, int num_rows, int num_cols_sbs,
+                        int num_cols, int num_rows_disp, int num_cols_disp, int elem_sz, int matrix)
+{
+    const char *fn = "demux_nv12_low";
+    if (!front_low_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_disp, num_cols_disp, elem_sz, census_l, census_r)) return;
+    if (!nv12_args_ok(fn, num_rows, num_cols_sbs, num_cols, "num_cols", pitch_y, pitch_uv, matrix)) return;
+    // a plane's last row need not be a whole pitch long
+    const size_t IMG = (size_t)num_rows * num_cols * elem_sz, hw = (size_t)num_rows_disp * num_cols_disp;
+    const size_t uv_row = 2 * (size_t)((num_cols_sbs + 1) / 2);
+    const size_t y_sz = (size_t)(num_rows - 1) * pitch_y + num_cols_sbs, uv_sz = (size_t)(num_rows / 2 - 1) * pitch_uv + uv_row;
+    Workspace::begin(2 * IMG + y_sz + uv_sz + hw * (2 * (size_t)elem_sz + 32) + 16384);
+    u8 *dy = up(y, y_sz), *duv = up(uv, uv_sz);
+    const Nv12Input nv = {dy, duv, pitch_y, pitch_uv, matrix, nullptr, nullptr};
+    front_low_host(img_l, img_r, low_l, low_r, census_l, census_r, nullptr, num_cols_sbs, &nv, num_rows, num_cols, num_rows_disp, num_cols_disp,
+                   elem_sz);
 }
 
 void stm_adcensus_stm_2(unsigned char *img_sbs, float *disp_l, float *disp_r, unsigned char *interlaced, int num_rows,

@@ -213,6 +213,12 @@ void launch_front(u8 *l, u8 *r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l
 void launch_front_nv12(u8 *l, u8 *r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l, uint32_t *wide_r, uint32_t *cen_l, uint32_t *cen_r,
                        const u8 *y, int pitch_y, const u8 *uv, int pitch_uv, int H, int W, int elem_sz, int matrix);
 void launch_demux_nv12(u8 *l, u8 *r, const u8 *y, int pitch_y, const u8 *uv, int pitch_uv, int H, int W, int elem_sz, int matrix);
+// the reduced-resolution frame's front in one launch: the full-size split images l / r (H x W), the bilinearly reduced images
+// low_l / low_r (h x w, bit for bit launch_scale_bilinear of the split images) and the reduced pair's BGRX, wide and census planes
+// (launch_front's formats).  sbs != nullptr: a side-by-side BGR frame, Wsbs >= 2 W; otherwise the NV12 planes of launch_front_nv12
+void launch_front_low(u8 *l, u8 *r, u8 *low_l, u8 *low_r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l, uint32_t *wide_r, uint32_t *cen_l,
+                      uint32_t *cen_r, const u8 *sbs, int Wsbs, const u8 *y, int pitch_y, const u8 *uv, int pitch_uv, int matrix, int H, int W,
+                      int h, int w, int elem_sz);
 // packed input (stm_kernels_pack.hip; `in` screened by packing_args_ok): the two unpacked eyes H x W x elem_sz as a stage, and
 // launch_front on the unpacked frame without materialising it
 void launch_demux_packed(u8 *l, u8 *r, const PackInput &in, int H, int W, int elem_sz);

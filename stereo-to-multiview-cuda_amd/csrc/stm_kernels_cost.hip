@@ -365,6 +365,209 @@ void launch_demux_nv12(u8 *l, u8 *r, const u8 *y, int pitch_y, const u8 *uv, int
     STM_CHECK_LAUNCH();
 }
 
+// ---------------------------------------------------------------- reduced-resolution frame: split + reduction + pixel formats + census
+// Everything the reduced frame needs before frame_disparity, in one launch.  The grid is one list of 64 x 16 tiles: rows
+// blockIdx.y < nty are tiles of the REDUCED image (h x w), the rows after them tiles of the full-size split image (H x W);
+// blockIdx.z = view.  The branch between the two is uniform for the block.
+//   A reduced tile is stm_k_front's tile, phase by phase and line by line (see there), with one difference: a `fetch` does not read
+// a pixel of the frame but computes a pixel of the reduced image -- stm_k_scale_bilinear's arithmetic (tx_scale_bilinear_kernel,
+// d_tx_scale.cu:30-52, and bilinear_u8: the same f32 operations in the same order, its clamps) on four taps read straight from
+// the input frame.  The taps clamp to the last column and row of the block's OWN eye, as the scale kernel does on the split image;
+// the halo clamps to the reduced image's edge BEFORE the pixel is computed, as stm_k_census32 does on the reduced image.  So the
+// low image, the three derived planes and the census words are bit for bit those of the unfused chain (demux, scale, pack,
+// census32), and the reduced image is never read back.
+//   A split tile copies (NV12: converts) its 64 x 16 pixels of one eye into the full-size image the renderer, the guided
+// up-sampler and the temporal step read, with stm_k_front's dword stores.
+//   SRC: where a tap comes from.  BGR: p0 = the side-by-side frame, pitch0 = its pixels a row.  NV12: p0 / p1 = the Y / UV planes,
+// pitch0 / pitch1 their bytes a row, a tap is nv12_bgrx of its samples -- so the reduced image is the reduction of the CONVERTED
+// split image.  Any h, w >= 1: w < 9 (the halo is wider than the image), h >= H (ratio 1, up-scaling), elem_sz > 3.
+struct LowSrc {
+    const u8 *p0, *p1;
+    int pitch0, pitch1;
+    Nv12Coef c;
+};
+template <bool NV12>
+__device__ __forceinline__ uint32_t low_src_px(const LowSrc &s, int view, int W, int elem_sz, int x, int y) // 0 <= x < W, 0 <= y < H
+{
+    if (NV12) {
+        const int X = view * W + x; // (W is even: a half starts on a chroma sample)
+        const int Y = s.p0[(size_t)y * s.pitch0 + X];
+        const u8 *q = s.p1 + (size_t)(y >> 1) * s.pitch1 + (X & ~1);
+        return nv12_bgrx(Y, q[0], q[1], s.c);
+    }
+    const u8 *q = s.p0 + ((size_t)y * s.pitch0 + (size_t)view * W + x) * elem_sz;
+    return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+}
+// bilinear_u8 (stm_kernels_dibr.hip) on the three channels of four BGRX taps
+__device__ __forceinline__ uint32_t bilinear_bgrx(uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11, float wx, float wy)
+{
+    uint32_t o = 0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float v00 = (float)((p00 >> (8 * ch)) & 0xffu), v01 = (float)((p01 >> (8 * ch)) & 0xffu);
+        const float v10 = (float)((p10 >> (8 * ch)) & 0xffu), v11 = (float)((p11 >> (8 * ch)) & 0xffu);
+        float a = v00 * (1.0f - wx);
+        float b = v01 * wx;
+        const float top = a + b;
+        a = v10 * (1.0f - wx);
+        b = v11 * wx;
+        const float bot = a + b;
+        a = top * (1.0f - wy);
+        b = bot * wy;
+        o |= (uint32_t)(u8)(a + b) << (8 * ch);
+    }
+    return o;
+}
+template <bool NV12>
+__global__ __launch_bounds__(256) void stm_k_front_low(u8 *__restrict__ l, u8 *__restrict__ r, u8 *__restrict__ low_l, u8 *__restrict__ low_r,
+                                                       uint32_t *__restrict__ pk_l, uint32_t *__restrict__ pk_r, uint32_t *__restrict__ wide_l,
+                                                       uint32_t *__restrict__ wide_r, uint32_t *__restrict__ cen_l, uint32_t *__restrict__ cen_r,
+                                                       LowSrc src, int H, int W, int h, int w, int elem_sz, int ntx, int nty, int stx)
+{
+    constexpr int TW = FR_TX + 8, TH = FR_TY + 4;
+    __shared__ __attribute__((aligned(16))) u8 g[TH][TW + 4]; // (a row is 76 bytes: dword reads of a row stay aligned)
+    const int view = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p0 = (4 * lane) / 3, o8 = 8 * (4 * lane - 3 * p0); // lane < 48: dword `lane` starts in byte o8 / 8 of pixel p0
+    if ((int)blockIdx.y >= nty) { // ---- a tile of the full-size split image
+        if ((int)blockIdx.x >= stx) return;
+        const int x0 = blockIdx.x * FR_TX, y0 = ((int)blockIdx.y - nty) * FR_TY;
+        u8 *__restrict__ img = view ? r : l;
+        uint32_t own[FR_TY / 4];
+#pragma unroll
+        for (int k = 0; k < FR_TY / 4; ++k) own[k] = low_src_px<NV12>(src, view, W, elem_sz, min(x0 + lane, W - 1), min(y0 + wave + 4 * k, H - 1));
+        const bool img_dwords = elem_sz == 3 && (W & 3) == 0 && x0 + FR_TX <= W && (((uintptr_t)img) & 3) == 0;
+#pragma unroll
+        for (int k = 0; k < FR_TY / 4; ++k) {
+            const int ux = x0 + lane, uy = y0 + wave + 4 * k;
+            if (uy >= H) continue; // (the whole wave)
+            if (img_dwords) {
+                const uint32_t lo = (uint32_t)__shfl((int)own[k], p0 & 63), hi = (uint32_t)__shfl((int)own[k], (p0 + 1) & 63);
+                if (lane < 48) ((uint32_t *)(img + ((size_t)uy * W + x0) * 3))[lane] = (uint32_t)((lo | ((unsigned long long)hi << 24)) >> o8);
+            } else if (ux < W) {
+                u8 *d = img + ((size_t)uy * W + ux) * elem_sz;
+                d[0] = (u8)own[k]; d[1] = (u8)(own[k] >> 8); d[2] = (u8)(own[k] >> 16);
+            }
+        }
+        return;
+    }
+    // ---- a tile of the reduced image
+    if ((int)blockIdx.x >= ntx) return;
+    const int x0 = blockIdx.x * FR_TX, y0 = blockIdx.y * FR_TY;
+    u8 *__restrict__ img = view ? low_r : low_l;
+    uint32_t *__restrict__ pk = view ? pk_r : pk_l, *__restrict__ wide = view ? wide_r : wide_l, *__restrict__ census = view ? cen_r : cen_l;
+    const float fw = (float)w, fh = (float)h, fW = (float)W, fH = (float)H;
+    auto fetch = [&](int ty, int tx) {
+        const int gx = min(max(x0 + tx - 4, 0), w - 1), gy = min(max(y0 + ty - 1, 0), h - 1); // clamp-to-edge of the reduced image
+        float xs = ((float)gx / fw) * fW;
+        xs = fminf(fmaxf(xs, 0.0f), (float)(W - 1));
+        float ys = ((float)gy / fh) * fH;
+        ys = fminf(fmaxf(ys, 0.0f), (float)(H - 1));
+        const int sx0 = (int)floorf(xs), sy0 = (int)floorf(ys); // in 0 .. W - 1, 0 .. H - 1: xs, ys were clamped
+        const int sx1 = min(sx0 + 1, W - 1), sy1 = min(sy0 + 1, H - 1); // inside this eye, never the other half
+        const float wx = xs - (float)sx0, wy = ys - (float)sy0;
+        return bilinear_bgrx(low_src_px<NV12>(src, view, W, elem_sz, sx0, sy0), low_src_px<NV12>(src, view, W, elem_sz, sx1, sy0),
+                             low_src_px<NV12>(src, view, W, elem_sz, sx0, sy1), low_src_px<NV12>(src, view, W, elem_sz, sx1, sy1), wx, wy);
+    };
+    // own pixels: lane = column, wave w takes tile rows w, w + 4, ..; the 416 halo elements -- four full rows, then eight side
+    // columns of the sixteen own rows -- take two more trips (stm_k_front)
+    constexpr int NH = TW * TH - FR_TX * FR_TY; // halo elements
+    uint32_t own[FR_TY / 4], halo[2];
+    int hty[2], htx[2];
+#pragma unroll
+    for (int k = 0; k < FR_TY / 4; ++k) own[k] = fetch(wave + 4 * k + 1, lane + 4);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const int e0 = min(tid + 256 * m, NH - 1);
+        if (e0 < 4 * TW) {
+            const int q = e0 / TW;
+            hty[m] = q == 0 ? 0 : FR_TY + q;
+            htx[m] = e0 - q * TW;
+        } else {
+            const int e = e0 - 4 * TW;
+            hty[m] = 1 + (e >> 3);
+            htx[m] = (e & 7) < 4 ? (e & 7) : FR_TX + (e & 7);
+        }
+        halo[m] = fetch(hty[m], htx[m]);
+    }
+    // the reduced image as dwords: 64 pixels of 3 bytes are 48 aligned dwords of the row, each built from two neighbouring pixels
+    const bool img_dwords = elem_sz == 3 && (w & 3) == 0 && x0 + FR_TX <= w && (((uintptr_t)img) & 3) == 0;
+#pragma unroll
+    for (int k = 0; k < FR_TY / 4; ++k) {
+        const int rr0 = wave + 4 * k, ux = x0 + lane, uy = y0 + rr0;
+        g[rr0 + 1][lane + 4] = (u8)grey_of(own[k]);
+        if (uy >= h) continue; // (the whole wave)
+        const uint32_t b = own[k] & 0xff, gg = (own[k] >> 8) & 0xff, rr = own[k] >> 16;
+        const size_t p = (size_t)uy * w + ux;
+        if (img_dwords) {
+            const uint32_t lo = (uint32_t)__shfl((int)own[k], p0 & 63), hi = (uint32_t)__shfl((int)own[k], (p0 + 1) & 63);
+            if (lane < 48) ((uint32_t *)(img + ((size_t)uy * w + x0) * 3))[lane] = (uint32_t)((lo | ((unsigned long long)hi << 24)) >> o8);
+        } else if (ux < w) {
+            u8 *d = img + p * elem_sz;
+            d[0] = (u8)b; d[1] = (u8)gg; d[2] = (u8)rr;
+        }
+        if (ux < w) {
+            pk[p] = own[k];
+            wide[p] = b | (gg << 10) | (rr << 20);
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+        if (tid + 256 * m < NH) g[hty[m]][htx[m]] = (u8)grey_of(halo[m]);
+    __syncthreads();
+    const int col = tid & 63, band = tid >> 6, gx = x0 + col; // rows y0 + 4 band .. + 3 of column gx
+    if (gx >= w) return;
+    // tile rows 4 band .. 4 band + 7, columns col .. col + 8 (the pixel's own column is col + 4): lo = the four bytes left of the
+    // centre, ct = the centre, hi = the four bytes right of it
+    uint32_t lo[8], ct[8], hi[8];
+    const int a8 = (col & 3) * 8;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t *rw = (const uint32_t *)&g[band * 4 + k][col & ~3];
+        const uint32_t d0 = rw[0], d1 = rw[1], d2 = rw[2];
+        const unsigned long long q01 = d0 | ((unsigned long long)d1 << 32), q12 = d1 | ((unsigned long long)d2 << 32);
+        lo[k] = (uint32_t)(q01 >> a8);
+        ct[k] = (uint32_t)(q12 >> a8) & 0xffu;
+        hi[k] = (uint32_t)(q12 >> (a8 + 8));
+    }
+    // bit order of stm_k_census32: window rows -1, +1, +2, +3 (what survives the truncation to 32 bits), in a row x = -4 .. 4
+    // without 0, appended MSB first (d_ci_census.cu:35-47)
+    auto row_bits = [](uint32_t lo4, uint32_t hi4, uint32_t cmp) {
+        uint32_t b = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) b = (b << 1) | (((lo4 >> (8 * k)) & 0xffu) < cmp ? 1u : 0u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) b = (b << 1) | (((hi4 >> (8 * k)) & 0xffu) < cmp ? 1u : 0u);
+        return b;
+    };
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { // the pixel of tile row 4 band + j + 1
+        const int gy = y0 + band * 4 + j;
+        const uint32_t cmp = ct[j + 1];
+        const uint32_t wd = (row_bits(lo[j], hi[j], cmp) << 24) | (row_bits(lo[j + 2], hi[j + 2], cmp) << 16) |
+                            (row_bits(lo[j + 3], hi[j + 3], cmp) << 8) | row_bits(lo[j + 4], hi[j + 4], cmp);
+        if (gy < h) census[(size_t)gy * w + gx] = wd;
+    }
+}
+// sbs != nullptr: a side-by-side BGR frame of Wsbs >= 2 W pixels a row; otherwise NV12 planes (y, uv, their pitches, matrix), all
+// screened by the caller.  l / r: H x W x elem_sz, low_l / low_r: h x w x elem_sz, the six planes: h x w dwords
+void launch_front_low(u8 *l, u8 *r, u8 *low_l, u8 *low_r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l, uint32_t *wide_r, uint32_t *cen_l,
+                      uint32_t *cen_r, const u8 *sbs, int Wsbs, const u8 *y, int pitch_y, const u8 *uv, int pitch_uv, int matrix, int H, int W,
+                      int h, int w, int elem_sz)
+{
+    const int ntx = cdiv(w, FR_TX), nty = cdiv(h, FR_TY), stx = cdiv(W, FR_TX), sty = cdiv(H, FR_TY);
+    const dim3 grid(ntx > stx ? ntx : stx, nty + sty, 2);
+    if (sbs) {
+        const LowSrc src = {sbs, nullptr, Wsbs, 0, NV12_COEF[0]};
+        STM_LAUNCH(stm_k_front_low<false>, grid, dim3(256), 0, stream(), l, r, low_l, low_r, pk_l, pk_r, wide_l, wide_r, cen_l, cen_r, src, H, W,
+                   h, w, elem_sz, ntx, nty, stx);
+    } else {
+        const LowSrc src = {y, uv, pitch_y, pitch_uv, NV12_COEF[matrix]};
+        STM_LAUNCH(stm_k_front_low<true>, grid, dim3(256), 0, stream(), l, r, low_l, low_r, pk_l, pk_r, wide_l, wide_r, cen_l, cen_r, src, H, W,
+                   h, w, elem_sz, ntx, nty, stx);
+    }
+    STM_CHECK_LAUNCH();
+}
+
 // ---------------------------------------------------------------- combined cost volume
 // popc(x & 0x7fffffff) + 33 * (x >> 31)  ==  the 64-iteration loop of d_alu.cu:7-15 (SURVEY A-Q1)
 __device__ __forceinline__ int hamdist_ref(uint32_t a, uint32_t b)

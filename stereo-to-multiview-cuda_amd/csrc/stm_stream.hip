@@ -43,7 +43,7 @@ struct FrameStream {
     hipStream_t s_in, s_out;
     bool overlap = true; // two frames in flight on the GPU (a compute stream + workspace per slot)
     bool use_graph = true;
-    int stages = 3; // stm_stream_set_stages: 3, optionally with 0x200 / 0x400 / 0x800 / 0x2000
+    int stages = 3; // stm_stream_set_stages: 3, optionally with 0x200 / 0x400 / 0x800 / 0x2000 (and 0x1000 with a match size)
     float t_alpha = 0.5f, t_disp = 1.5f; // stm_stream_set_temporal: the parameters of the temporal step (0x2000) and their defaults
     int t_color = 24;
     int in_format = 0, in_matrix = 0; // stm_stream_set_input: 0 = side-by-side BGR, 1 = NV12 (Y plane, then the UV plane; pitch Wsbs)
@@ -53,6 +53,8 @@ struct FrameStream {
     stm::Depth depth = {0, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 20, nullptr}; // stm_stream_set_depth / _auto: the stream's own depth budget
     stm::Packing packing = {0, 0, 0, 0}; // stm_stream_set_packing: the stream's own input packing, installed around its frame calls
     int rows_f = 0;                      // the rows of an input frame: H, or what the packing makes of it
+    int match_h = 0, match_w = 0;        // stm_stream_set_match_size: the size the pair is matched at (0, 0 = off: the full-resolution frame)
+    float match_scale = 1.0f;            // ... and the reduced frame's disp_scale
     float *d_depth_state = nullptr; // mode 2: the state every frame updates, at one address for both slots' graphs
     Slot slot[2];
     long submitted = 0, collected = 0;
@@ -154,12 +156,14 @@ int stm_stream_set_stages(void *h, int stages)
 {
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
-    if (stages & 0x1000) { // the stream runs the full-resolution frame: nothing is up-scaled
+    const bool reduced = f->match_h > 0;
+    if ((stages & 0x1000) && !reduced) { // the stream runs the full-resolution frame: nothing is up-scaled
         stm::fail("stream_set_stages: stages 0x1000 (guided disparity up-sampling) needs the reduced-resolution frame", "stages", __FILE__, __LINE__);
         return -1;
     }
-    if ((stages & ~0x2e00) != 3) {
-        stm::fail("stream_set_stages: stages must be 3, optionally OR-ed with 0x200, 0x400, 0x800 and 0x2000", "stages", __FILE__, __LINE__);
+    if ((stages & ~(reduced ? 0x3e00 : 0x2e00)) != 3) {
+        stm::fail(reduced ? "stream_set_stages: stages must be 3, optionally OR-ed with 0x200, 0x400, 0x800, 0x1000 and 0x2000"
+                          : "stream_set_stages: stages must be 3, optionally OR-ed with 0x200, 0x400, 0x800 and 0x2000", "stages", __FILE__, __LINE__);
         return -1;
     }
     if (f->submitted > 0) {
@@ -167,6 +171,44 @@ int stm_stream_set_stages(void *h, int stages)
         return -1;
     }
     f->stages = stages;
+    return 0;
+}
+
+// The size every frame of the stream is matched at (stm_hip.h): with a size set, a frame is the reduced-resolution frame
+// (stm_d_adcensus_stm_2s, _2t with stages bit 0x2000, _2nv12 in NV12 mode) and stm_stream_set_stages also takes 0x1000.  (0, 0, any)
+// = off, the default.  Not together with a packing of the stream, and not switched off while the stream's stages hold 0x1000.  Only
+// before the first submit.  Returns 0, or -1 with the error recorded.
+int stm_stream_set_match_size(void *h, int num_rows_disp, int num_cols_disp, float disp_scale)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    const bool off = num_rows_disp == 0 && num_cols_disp == 0;
+    if (!off && (num_rows_disp < 1 || num_cols_disp < 1)) {
+        stm::fail("stream_set_match_size: num_rows_disp and num_cols_disp must be >= 1, or both 0 (off)", "num_rows_disp, num_cols_disp", __FILE__,
+                  __LINE__);
+        return -1;
+    }
+    if (!off && !(disp_scale > 0.0f && disp_scale <= 3.402823466e38f)) { // (NaN fails the first comparison)
+        stm::fail("stream_set_match_size: disp_scale must be finite and > 0", "disp_scale", __FILE__, __LINE__);
+        return -1;
+    }
+    if (f->submitted > 0) {
+        stm::fail("stream_set_match_size: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    if (!off && f->packing.on()) {
+        stm::fail("stream_set_match_size: the stream has a packing (stm_stream_set_packing), which the reduced-resolution frame does not support",
+                  "packing", __FILE__, __LINE__);
+        return -1;
+    }
+    if (off && (f->stages & 0x1000)) {
+        stm::fail("stream_set_match_size: the stream's stages hold 0x1000 (guided disparity up-sampling), which needs a match size", "stages",
+                  __FILE__, __LINE__);
+        return -1;
+    }
+    f->match_h = off ? 0 : num_rows_disp;
+    f->match_w = off ? 0 : num_cols_disp;
+    f->match_scale = off ? 1.0f : disp_scale;
     return 0;
 }
 
@@ -239,6 +281,11 @@ int stm_stream_set_packing(void *h, int packing, int swap, int filter, int gap)
     if (!stm::packing_params_ok("stream_set_packing", pk)) return -1;
     if (f->submitted > 0) {
         stm::fail("stream_set_packing: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    if (pk.on() && f->match_h > 0) {
+        stm::fail("stream_set_packing: the stream has a match size (stm_stream_set_match_size): the reduced-resolution frame takes no packing",
+                  "packing", __FILE__, __LINE__);
         return -1;
     }
     if (!stream_input_ok("stream_set_packing", f, f->in_format, f->in_matrix, pk)) return -1;
@@ -405,6 +452,25 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     stm::ws_private_bind(s.ws);
     auto pipeline = [&]() {
         stm::ApiNest nest; // a failed upload above must survive the nested call's argument screen
+        if (f->match_h > 0) { // the reduced-resolution frame, picked as below
+            if (f->in_format == 1) {
+                stm_d_adcensus_stm_2nv12(s.d_in, f->Wsbs, s.d_in + (size_t)f->rows_f * f->Wsbs, f->Wsbs, f->in_matrix, s.d_dl, s.d_dr, s.d_out,
+                                         f->H, f->Wsbs, f->W, f->Hout, f->Wout, f->match_h, f->match_w, f->E, f->match_scale, f->N, f->angle,
+                                         f->D, f->zd, f->ad, f->ce, f->ucd, f->lcd, f->usd, f->lsd, f->thresh_s, f->thresh_h, f->stages,
+                                         history ? other.d_img_l : nullptr, history ? other.d_img_r : nullptr, history ? other.d_dl : nullptr,
+                                         history ? other.d_dr : nullptr, f->t_alpha, f->t_color, f->t_disp, s.d_img_l, s.d_img_r);
+            } else if (temporal) {
+                stm_d_adcensus_stm_2t(s.d_in, s.d_dl, s.d_dr, s.d_out, f->H, f->Wsbs, f->W, f->Hout, f->Wout, f->match_h, f->match_w, f->E,
+                                      f->match_scale, f->N, f->angle, f->D, f->zd, f->ad, f->ce, f->ucd, f->lcd, f->usd, f->lsd, f->thresh_s,
+                                      f->thresh_h, f->stages, history ? other.d_in : nullptr, history ? other.d_dl : nullptr,
+                                      history ? other.d_dr : nullptr, f->t_alpha, f->t_color, f->t_disp);
+            } else {
+                stm_d_adcensus_stm_2s(s.d_in, s.d_dl, s.d_dr, s.d_out, f->H, f->Wsbs, f->W, f->Hout, f->Wout, f->match_h, f->match_w, f->E,
+                                      f->match_scale, f->N, f->angle, f->D, f->zd, f->ad, f->ce, f->ucd, f->lcd, f->usd, f->lsd, f->thresh_s,
+                                      f->thresh_h, f->stages);
+            }
+            return;
+        }
         if (f->in_format == 1) { // NV12: the slot's images receive the conversion; with 0x2000 the other slot's images and maps are the history
             stm_d_adcensus_stm_nv12(s.d_in, f->Wsbs, s.d_in + (size_t)f->rows_f * f->Wsbs, f->Wsbs, f->in_matrix, s.d_dl, s.d_dr, s.d_out, f->H,
                                     f->Wsbs, f->W, f->Hout, f->Wout, f->E, f->N, f->angle, f->D, f->zd, f->ad, f->ce, f->ucd, f->lcd,

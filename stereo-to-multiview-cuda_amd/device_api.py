@@ -352,6 +352,95 @@ def d_adcensus_stm_2s(sbs, disp_l, disp_r, interlaced, p, disp_rows, disp_cols, 
                                 p.ucd, p.lcd, p.usd, p.lsd, p.thresh_s, p.thresh_h, stages)
 
 
+def d_adcensus_stm_2t(sbs, disp_l, disp_r, interlaced, p, disp_rows, disp_cols, disp_scale, stages=3, prev_sbs=None, prev_disp_l=None,
+                      prev_disp_r=None, alpha=TEMPORAL_DEFAULTS[0], thresh_color=TEMPORAL_DEFAULTS[1], thresh_disp=TEMPORAL_DEFAULTS[2]):
+    """stm_d_adcensus_stm_2t: d_adcensus_stm_2s with the history of the temporal stabilisation.  With STAGE_TEMPORAL in `stages` and
+    the previous frame's side-by-side input and full-size output maps given, the up-scaled disp_l / disp_r are stabilised in place
+    before the views are rendered; with all three None (the first frame) the call is d_adcensus_stm_2s without the bit."""
+    assert sbs.is_cuda and sbs.dtype == torch.uint8 and sbs.is_contiguous()
+    H, Wsbs, E = sbs.shape
+    W = Wsbs // 2
+    assert disp_l.shape == (H, W) and disp_r.shape == (H, W) and disp_l.dtype == torch.float32
+    if prev_sbs is not None:
+        assert prev_sbs.is_cuda and prev_sbs.dtype == torch.uint8 and prev_sbs.is_contiguous() and prev_sbs.shape == sbs.shape
+    for t in (prev_disp_l, prev_disp_r):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
+    Ho, Wo = interlaced.shape[0], interlaced.shape[1]
+
+    def opt(t):
+        return None if t is None else _p(t)
+    _use_current_stream()
+    lib().stm_d_adcensus_stm_2t(_p(sbs), _p(disp_l), _p(disp_r), _p(interlaced), H, Wsbs, W, Ho, Wo, disp_rows, disp_cols, E,
+                                disp_scale, p.num_views, p.angle, p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff,
+                                p.ucd, p.lcd, p.usd, p.lsd, p.thresh_s, p.thresh_h, stages, opt(prev_sbs), opt(prev_disp_l), opt(prev_disp_r),
+                                float(alpha), int(thresh_color), float(thresh_disp))
+
+
+def d_adcensus_stm_2nv12(y, uv, disp_l, disp_r, interlaced, p, disp_rows, disp_cols, disp_scale, stages=3, matrix=0, img_l=None, img_r=None,
+                         prev_img_l=None, prev_img_r=None, prev_disp_l=None, prev_disp_r=None, alpha=TEMPORAL_DEFAULTS[0],
+                         thresh_color=TEMPORAL_DEFAULTS[1], thresh_disp=TEMPORAL_DEFAULTS[2], num_cols_sbs=None, elem_sz=3):
+    """stm_d_adcensus_stm_2nv12: d_adcensus_stm_2t on a side-by-side NV12 frame (planes as for d_demux_nv12), the conversion fused
+    into the frame's first kernel.  img_l / img_r (uint8 [H][W][E], optional, required with STAGE_TEMPORAL) receive the converted
+    split images: they are the next frame's prev_img_l / prev_img_r.  elem_sz is taken from img_l where that is given."""
+    H, Wsbs, pitch_y, pitch_uv = _nv12_planes(y, uv, num_cols_sbs)
+    W = disp_l.shape[1]
+    assert disp_l.shape == (H, W) and disp_r.shape == (H, W) and disp_l.dtype == torch.float32
+    E = elem_sz if img_l is None else img_l.shape[2]
+    for t in (img_l, img_r, prev_img_l, prev_img_r):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    for t in (prev_disp_l, prev_disp_r):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
+    Ho, Wo = interlaced.shape[0], interlaced.shape[1]
+
+    def opt(t):
+        return None if t is None else _p(t)
+    _use_current_stream()
+    lib().stm_d_adcensus_stm_2nv12(_p(y), pitch_y, _p(uv), pitch_uv, int(matrix), _p(disp_l), _p(disp_r), _p(interlaced), H, Wsbs, W, Ho, Wo,
+                                   disp_rows, disp_cols, E, disp_scale, p.num_views, p.angle, p.num_disp, p.zero_disp, p.ad_coeff,
+                                   p.census_coeff, p.ucd, p.lcd, p.usd, p.lsd, p.thresh_s, p.thresh_h, stages, opt(prev_img_l), opt(prev_img_r),
+                                   opt(prev_disp_l), opt(prev_disp_r), float(alpha), int(thresh_color), float(thresh_disp), opt(img_l),
+                                   opt(img_r))
+
+
+def _low_outputs(img_l, img_r, low_l, low_r, census_l, census_r):
+    H, W, E = img_l.shape
+    h, w = low_l.shape[:2]
+    for t, shape in ((img_l, (H, W, E)), (img_r, (H, W, E)), (low_l, (h, w, E)), (low_r, (h, w, E))):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == shape
+    for t in (census_l, census_r):
+        if t is not None:  # 32-bit words: int32 tensors (torch has no arithmetic on uint32), viewed as uint32 by the caller
+            assert t.is_cuda and t.element_size() == 4 and t.is_contiguous() and t.shape == (h, w)
+    return H, W, E, h, w
+
+
+def d_demux_sbs_low(img_l, img_r, low_l, low_r, sbs, census_l=None, census_r=None, num_cols_sbs=None):
+    """stm_d_demux_sbs_low: the reduced-resolution frame's front as a stage.  From sbs (uint8 [H][Wsbs][E] on the GPU): the split
+    images img_l / img_r (uint8 [H][W][E]), the bilinearly reduced images low_l / low_r (uint8 [h][w][E]) and, where given, the
+    reduced images' 32-bit census words census_l / census_r (4-byte integer tensors [h][w]).  Only the first three bytes of a pixel
+    are written."""
+    H, W, E, h, w = _low_outputs(img_l, img_r, low_l, low_r, census_l, census_r)
+    assert sbs.is_cuda and sbs.dtype == torch.uint8 and sbs.is_contiguous() and sbs.shape[0] == H and sbs.shape[2] == E
+    Wsbs = sbs.shape[1] if num_cols_sbs is None else num_cols_sbs
+    assert Wsbs == sbs.shape[1]
+    _use_current_stream()
+    lib().stm_d_demux_sbs_low(_p(img_l), _p(img_r), _p(low_l), _p(low_r), None if census_l is None else _p(census_l),
+                              None if census_r is None else _p(census_r), _p(sbs), H, Wsbs, W, h, w, E)
+
+
+def d_demux_nv12_low(img_l, img_r, low_l, low_r, y, uv, matrix=0, census_l=None, census_r=None, num_cols_sbs=None):
+    """stm_d_demux_nv12_low: d_demux_sbs_low on a side-by-side NV12 frame (planes as for d_demux_nv12): the reduced images are the
+    reduction of the converted split images."""
+    H, W, E, h, w = _low_outputs(img_l, img_r, low_l, low_r, census_l, census_r)
+    Hy, Wsbs, pitch_y, pitch_uv = _nv12_planes(y, uv, num_cols_sbs)
+    assert Hy == H
+    _use_current_stream()
+    lib().stm_d_demux_nv12_low(_p(img_l), _p(img_r), _p(low_l), _p(low_r), None if census_l is None else _p(census_l),
+                               None if census_r is None else _p(census_r), _p(y), pitch_y, _p(uv), pitch_uv, H, Wsbs, W, h, w, E, int(matrix))
+
+
 def plane_table(slab):
     """Device table of plane pointers for a contiguous [D][H][W] float tensor."""
     D = slab.shape[0]

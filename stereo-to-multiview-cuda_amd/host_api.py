@@ -12,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import f32p, f32pp, lib, u8p, u8pp
+from ._lib import f32p, f32pp, lib, u32p, u8p, u8pp
 
 
 def _u8(a):
@@ -426,3 +426,22 @@ def demux_nv12_packed(y, uv, num_rows, num_cols, packing, elem_sz=3, matrix=0, n
     lib().stm_demux_nv12_packed(img_l.ctypes.data_as(u8p), img_r.ctypes.data_as(u8p), y.ctypes.data_as(u8p), y.strides[0],
                                 uv.ctypes.data_as(u8p), uv.strides[0], num_rows, Wsbs, num_cols, elem_sz, int(matrix), pk, sw, fl, gap)
     return img_l, img_r
+
+
+def demux_sbs_low(img_sbs, num_cols, disp_rows, disp_cols, census=True):
+    """stm_demux_sbs_low: the reduced-resolution frame's front on host arrays.  img_sbs uint8 [H][Wsbs][E] (contiguous).  Returns
+    (img_l, img_r, low_l, low_r, census_l, census_r): the split images [H][num_cols][E], the bilinearly reduced images
+    [disp_rows][disp_cols][E] (BGR in the first three bytes, 0 past them) and the reduced images' 32-bit census words (uint32
+    [disp_rows][disp_cols]; None, None with census=False)."""
+    img_sbs = np.ascontiguousarray(img_sbs, dtype=np.uint8)
+    H, Wsbs, E = img_sbs.shape
+    img_l = np.zeros((H, num_cols, E), np.uint8)
+    img_r = np.zeros_like(img_l)
+    low_l = np.zeros((disp_rows, disp_cols, E), np.uint8)
+    low_r = np.zeros_like(low_l)
+    cen_l = np.zeros((disp_rows, disp_cols), np.uint32) if census else None
+    cen_r = np.zeros((disp_rows, disp_cols), np.uint32) if census else None
+    lib().stm_demux_sbs_low(img_l.ctypes.data_as(u8p), img_r.ctypes.data_as(u8p), low_l.ctypes.data_as(u8p), low_r.ctypes.data_as(u8p),
+                            cen_l.ctypes.data_as(u32p) if census else None, cen_r.ctypes.data_as(u32p) if census else None,
+                            img_sbs.ctypes.data_as(u8p), H, Wsbs, num_cols, disp_rows, disp_cols, E)
+    return img_l, img_r, low_l, low_r, cen_l, cen_r

@@ -23,10 +23,12 @@ class FrameStream:
     side by side, top and bottom, ...); num_rows x num_cols stay the size of an unpacked eye, and a frame is then [rows_f][Wsbs][3]
     (NV12: [rows_f * 3 / 2][Wsbs]) with Wsbs = 2 * (packed eye's columns) + gap for the side-by-side packings and num_cols for the
     top-and-bottom ones: the shape `in_shape` holds.  layout = (1, tiles_x, tiles_y, order, filter): the frames come out as a
-    quilt of tiles_x x tiles_y whole views (set_layout); None = the interlaced frame."""
+    quilt of tiles_x x tiles_y whole views (set_layout); None = the interlaced frame.  match = (h, w, disp_scale): every frame is the
+    reduced-resolution frame -- matched at h x w, the maps scaled up by 1 / disp_scale, the views rendered at full size -- and
+    `stages` may then carry 0x1000 (the guided up-sampler); None = the full-resolution frame.  Not together with a packing."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
-                 depth=None, depth_auto=None, packing=None, layout=None):
+                 depth=None, depth_auto=None, packing=None, layout=None, match=None):
         self.H, self.W = num_rows, num_cols
         self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
@@ -37,6 +39,8 @@ class FrameStream:
         self._h = lib().stm_stream_create(num_rows, self.Wsbs, num_cols, self.Ho, self.Wo, 3, p.num_views, p.angle,
                                           p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff, p.ucd, p.lcd, p.usd, p.lsd,
                                           p.thresh_s, p.thresh_h)
+        if match is not None:  # before the stages: 0x1000 needs it
+            self.set_match_size(*match)
         if stages != 3:
             self.set_stages(stages)
         if packing is not None:
@@ -113,9 +117,17 @@ class FrameStream:
         self.rows_f = packed_frame_geometry(self.H, self.W, self.packing)[1]
         self.in_shape = (self.rows_f * 3 // 2, self.Wsbs) if self._nv12 else (self.rows_f, self.Wsbs, 3)
 
+    def set_match_size(self, num_rows_disp=0, num_cols_disp=0, disp_scale=1.0):
+        """stm_stream_set_match_size: the size the stream's frames are matched at and the reduced frame's disp_scale; (0, 0) = off,
+        the full-resolution frame.  Only before the first submit.  Raises ValueError where the library refuses."""
+        if int(lib().stm_stream_set_match_size(self._h, int(num_rows_disp), int(num_cols_disp), float(disp_scale))) != 0:
+            raise ValueError("stm_stream_set_match_size(%d, %d, %g) refused: %s"
+                             % (num_rows_disp, num_cols_disp, disp_scale, lib().stm_last_error().decode()))
+
     def set_stages(self, stages):
         """stm_stream_set_stages: 3, optionally OR-ed with 0x200 (sub-pixel), 0x400 (outlier interpolation), 0x800 (linear
-        sampling of the views' warps) and 0x2000 (temporal stabilisation of the maps against the previous frame's); only before
+        sampling of the views' warps), 0x2000 (temporal stabilisation of the maps against the previous frame's) and -- with a match
+        size -- 0x1000 (guided up-sampling of the maps); only before
         the first submit.  Raises ValueError where the library refuses (it returns -1; in error mode 0 it exits like any error)."""
         if int(lib().stm_stream_set_stages(self._h, int(stages))) != 0:
             raise ValueError("stm_stream_set_stages(%#x) refused: %s" % (stages, lib().stm_last_error().decode()))
@@ -201,7 +213,7 @@ def _collect(fs, on_depth):
 
 
 def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None,
-                     depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None):
+                     depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
@@ -209,7 +221,7 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
     pitch, slope, centre) for FrameStream.set_lens, None = the reference's interlacer; depth / depth_auto: FrameStream's depth
     budget; on_depth: called with (index, (gain, conv)) after every collected frame.  packing: FrameStream's; the frames are then packed
     ones; eye_shape = (num_rows, num_cols), the size of an unpacked eye, defaults to what a frame without spare columns holds.
-    layout: FrameStream's (the interlaced output is then a quilt)."""
+    layout: FrameStream's (the interlaced output is then a quilt).  match: FrameStream's (h, w, disp_scale): the reduced-resolution frame."""
     fs = None
     pending = 0
     for sbs in frames:
@@ -218,7 +230,7 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
             cols = sbs.shape[1] // 2
             if packing is not None:
                 rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
-            fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout)
+            fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:

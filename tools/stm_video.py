@@ -7,7 +7,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--temporal [--temporal-alpha A] [--temporal-color C] [--temporal-disp T]]
                     [--nv12 ROWS COLS_SBS [--matrix M]] [--lens MODE PITCH SLOPE CENTRE]
                     [--depth GAIN CONV | --depth-auto LO HI [MAX_GAIN CLIP RATE]]
-                    [--packing P SWAP FILTER GAP] [--quilt TX TY ORDER FILTER]
+                    [--packing P SWAP FILTER GAP] [--quilt TX TY ORDER FILTER] [--match H W SCALE [--guided-up]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -32,6 +32,9 @@ kernel; combines with --nv12, whose ROWS and COLS_SBS are then the packed frame'
 --quilt TX TY ORDER FILTER (an addition): the output frame is a quilt (stm_set_layout) -- the <num views> = TX * TY views whole, as
 TX x TY tiles, instead of interlaced; ORDER bit 0 = tile rows bottom-up, bit 1 = tile 0 holds the leftmost camera (3 = the Looking
 Glass convention); FILTER 0 = the reference's four-neighbour sampler, 1 = the area average.  <angle> is then ignored; excludes --lens.
+--match H W SCALE (an addition): every frame is the reduced-resolution frame (stm_stream_set_match_size) -- the pair is matched at
+H x W, the maps are scaled up by 1 / SCALE and the views rendered at full size; <num disp> and <zero disp> then count pixels of the
+reduced pair.  --guided-up adds frame bit 0x1000, the guided up-sampler in place of the bilinear up-scale.  Excludes --packing.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -101,6 +104,23 @@ def main(argv):
             print(__doc__)
             return -1
         del argv[at:at + 5]
+    match = None
+    if "--match" in argv:
+        at = argv.index("--match")
+        try:
+            match = (int(argv[at + 1]), int(argv[at + 2]), float(argv[at + 3]))
+        except (ValueError, IndexError):
+            match = None
+        if match is None or match[0] < 1 or match[1] < 1 or not match[2] > 0.0 or packing is not None:
+            print(__doc__)
+            return -1
+        del argv[at:at + 4]
+    if "--guided-up" in argv:
+        if match is None:
+            print(__doc__)
+            return -1
+        stages |= 0x1000
+        argv.remove("--guided-up")
     depth, depth_auto = None, None
     try:
         if "--depth" in argv:
@@ -150,7 +170,7 @@ def main(argv):
                                                        "bgr" if nv12 is None else "nv12", matrix, lens, depth, depth_auto,
                                                        (lambda k, gc: print("frame %d: gain %.6g conv %.6g" % (k, gc[0], gc[1])))
                                                        if depth_auto is not None else None, packing,
-                                                       layout=None if quilt is None else (1,) + quilt):
+                                                       layout=None if quilt is None else (1,) + quilt, match=match):
         video.write_outputs(out_dir, k, dl, dr, inter)
         n += 1
     dt = time.perf_counter() - t0
