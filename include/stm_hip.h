@@ -203,6 +203,29 @@ int         stm_set_layout(int layout, int tiles_x, int tiles_y, int order, int 
 /* out[0 .. 4] = the calling thread's layout, tiles_x, tiles_y, order and filter as the last accepted stm_set_layout left them
  * ((0, 1, 1, 0, 0) if none was made, and after layout 0).  A frame stream's own layout is not visible here except during its submit. */
 void        stm_get_layout(int *out);
+/* The calling thread's output format (an addition: the reference writes BGR only, which no hardware video encoder takes).
+ * format 0 = BGR, elem_sz bytes a pixel (the default; matrix, pitch and uv_row are ignored, and not one launch, argument or kernel
+ * changes), 1 = NV12.  With format 1 the d_interlaced / interlaced argument of every frame call that renders -- stm_adcensus_stm,
+ * stm_d_adcensus_stm, _t, _nv12, and _2 / _2s / _2t / _2nv12 in both flavours where they exist -- is ONE NV12 surface holding the
+ * picture that stm_mux_nv12 (the definition and the matrices are there) gives on the BGR quilt the call would have written:
+ *   Y plane    num_rows_out rows of P bytes from byte 0;              P = pitch, or num_cols_out if pitch == 0
+ *   UV plane   num_rows_out / 2 rows of P bytes from byte P * R;      R = uv_row, or num_rows_out if uv_row == 0
+ * so an encoder's pitch and height alignment are met in place.  elem_sz keeps describing the input pixels only.  The conversion runs
+ * inside the kernel that renders the pixels: no BGR quilt is written (stm_set_agg_variant(200) with depth mode 0 is the un-fused
+ * form: the BGR quilt in the workspace, then stm_d_mux_nv12's kernel).  The device flavours leave every byte of the surface that is
+ * neither a Y nor a UV sample as it was; the host flavours return those bytes 0 and copy P * (R + num_rows_out / 2) bytes.
+ * Errors of a frame call under format 1, through stm_last_error before anything is launched or written: the thread's layout is 0
+ * (chroma subsampling destroys a sub-pixel interlaced frame: NV12 exists for quilts only); num_rows_out or num_cols_out odd; a tile
+ * width num_cols_out / tiles_x or height num_rows_out / tiles_y odd (every tile starts on a chroma sample, so no chroma sample mixes
+ * two views, and the remainders are then even too); P < num_cols_out; R < num_rows_out.  (P * (R + num_rows_out / 2) fits 63 bits for
+ * every int P, R and num_rows_out, so that rule needs no test.)  A frame call whose `stages` low byte is below 3 renders nothing and
+ * ignores the format, as it ignores the layout.
+ * Argument rules: format 0 or 1; with format 1 matrix in 0 .. 3, pitch >= 0, uv_row >= 0.  Returns 0, or -1 with stm_last_error set
+ * and the thread's format unchanged. */
+int         stm_set_output(int format, int matrix, int pitch, int uv_row);
+/* out[0 .. 3] = the calling thread's format, matrix, pitch and uv_row as the last accepted stm_set_output left them ((0, 0, 0, 0) if
+ * none was made, and after format 0).  A frame stream's own format is not visible here except during its submit. */
+void        stm_get_output(int out[4]);
 /* (tests, tools) the bytes of LDS a workgroup of the area filter's staged kernel may take: the block of output pixels it owns is sized
  * so that its footprint's staging fits, and where not even one output pixel's does the per-pixel form runs -- same arithmetic, same
  * bytes.  <= 0: the default, 32768 (five workgroups on a CU); at most 65536.  Process-wide, like stm_set_agg_variant. */
@@ -503,6 +526,44 @@ void stm_demux_nv12(unsigned char *img_l, unsigned char *img_r, unsigned char *y
                     int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz, int matrix);
 void stm_d_demux_nv12(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv,
                       int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz, int matrix);
+/* NV12 output (an addition; the counterpart of stm_demux_nv12 for what an encoder takes).  Colour conversion as a stage: the NV12
+ * picture of a BGR image img (num_rows x num_cols x elem_sz, B, G, R in a pixel's first three bytes; H = num_rows and W = num_cols
+ * even and >= 2).  The image is read through the bytes as stored: for a quilt, the rounded u8 output of stm_quilt_multiview's rules,
+ * pad pixels 0 included.  The conversion does not read the filter's unrounded accumulators.
+ *   y    u8, H rows of pitch_y bytes.
+ *   uv   u8, H / 2 rows of pitch_uv bytes; bytes 2k and 2k + 1 of row j are U and V of the 2 x 2 block at rows 2j, 2j + 1 and columns
+ *        2k, 2k + 1.
+ * All arithmetic is 32-bit signed integer.  >> is an arithmetic shift.
+ *   Y[y][x]       = clip255((yr*R + yg*G + yb*B + (yo << 16) + 32768) >> 16)
+ *   SB, SG, SR    = the sums of B, G, R over the block rows 2j, 2j+1 x columns 2k, 2k+1      (0 .. 1020)
+ *   UV[j][2k]     = clip255((h*SB - ug*SG - ur*SR + (128 << 18) + (1 << 17)) >> 18)         (U)
+ *   UV[j][2k + 1] = clip255((h*SR - vg*SG - vb*SB + (128 << 18) + (1 << 17)) >> 18)         (V)
+ * So chroma is the exact mean of the four pixels' chroma, rounded once (centre siting).  This is the counterpart of the input side's
+ * replicated chroma.
+ * Coefficients use stm_demux_nv12's (Kr, Kb) and range per `matrix` 0 .. 3.  (sy, sc, yo) is (219/255, 224/255, 16) for limited range
+ * and (1, 1, 0) for full range.  Each rounded coefficient is computed in double and rounded to nearest (none is a tie):
+ *   ys = round(65536 sy), yr = round(65536 Kr sy), yb = round(65536 Kb sy), yg = ys - yr - yb
+ *   h = round(32768 sc), ur = round(65536 Kr sc / (2 (1 - Kb))), ug = h - ur
+ *   vb = round(65536 Kb sc / (2 (1 - Kr))), vg = h - vb
+ * The three derived coefficients make white land exactly on 235 / 255.  They also make every grey give U = V = 128 exactly.
+ *   matrix  yo    yr     yg     yb     h      ur     ug     vg     vb
+ *     0     16  16829  33039   6416  28784   9714  19070  24103   4681
+ *     1     16  11966  40254   4064  28784   6596  22188  26145   2639
+ *     2      0  19595  38470   7471  32768  11058  21710  27439   5329
+ *     3      0  13933  46871   4732  32768   7509  25259  29763   3005
+ * Known answers for a uniform 2 x 2 block, (B, G, R) -> (Y, U, V).  Matrix 0: (0,0,0) -> (16,128,128); (255,255,255) -> (235,128,128);
+ * (0,0,255) -> (81,90,240); (255,0,0) -> (41,240,110); (0,255,0) -> (145,54,34).  Matrix 2: (255,0,0) -> (29,255,107), where U is
+ * clipped from 256.  Matrix 3: (0,255,0) -> (182,30,12).
+ * No intermediate exceeds 2^26.  Y never needs its clip.  Chroma needs only the clip at 256.
+ * Rules: num_rows and num_cols even and >= 2, pitch_y >= num_cols, pitch_uv >= num_cols, matrix in 0 .. 3, elem_sz >= 3.  The base
+ * pointers may have any byte alignment.  img is read only.  The device flavour leaves every byte of the two planes that is not a
+ * sample as it was; the host flavour returns the bytes between a row's samples and the next row as 0.  Errors (stm_last_error), all
+ * reported before anything is launched or written.  Parity is against a numpy statement of these lines (parity unpinned).
+ * Out of scope: left-co-sited chroma, P010 / 10-bit, planar I420. */
+void stm_mux_nv12(unsigned char *y, int pitch_y, unsigned char *uv, int pitch_uv, unsigned char *img, int num_rows, int num_cols,
+                  int elem_sz, int matrix);
+void stm_d_mux_nv12(unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv, unsigned char *d_img, int num_rows, int num_cols,
+                    int elem_sz, int matrix);
 /* Packed stereo frames (an addition: the reference takes two full-resolution eyes side by side, left first, a layout almost no stereo
  * video is stored in).  The unpacking as a stage: the counterpart of stm_d_demux_sbs for a frame in one of the common packings.
  *   packing  0 = side by side, full;  1 = side by side, each eye squeezed to half the columns;
@@ -878,6 +939,14 @@ int   stm_stream_set_lens(void *stream, int mode, double pitch, double slope, do
  * installs it only for the duration of its frame calls, like the lens geometry: the calling thread's stm_set_layout neither reaches
  * the stream's frames nor is changed by them.  Only before the first submit.  Returns 0, or -1 with the error recorded. */
 int   stm_stream_set_layout(void *stream, int layout, int tiles_x, int tiles_y, int order, int filter);
+/* the output format of the stream's frames (stm_set_output's formats and matrices; the default is format 0).  Format 1: every frame
+ * leaves as one contiguous NV12 surface, P = num_cols_out and R = num_rows_out, as the stream's NV12 input is contiguous; the output
+ * size becomes num_rows_out * num_cols_out * 3 / 2 bytes: what stm_stream_collect copies, what the download moves and what
+ * stm_stream_collect_view points at.  The stream keeps its own copy and installs it only around its frame calls, like the layout.
+ * Refused while the stream's layout is 0, and stm_stream_set_layout(stream, 0, ...) is refused while the format is 1.  It replays
+ * under the captured graphs (nothing is read back) and combines with every input format, packing, match size, 0x2000 and depth mode.
+ * Only before the first submit.  Returns 0, or -1 with stm_last_error set and the stream unchanged. */
+int   stm_stream_set_output(void *stream, int format, int matrix);
 /* the depth budget of the stream's frames (stm_set_depth's rules; the default is mode 0).  As with the lens geometry the stream keeps
  * its own copy and installs it only around its frame calls.  stm_stream_set_depth_auto sets mode 2's parameters (stm_set_depth_auto's
  * rules; call it before stm_stream_set_depth(stream, 2, 0, 0)); the state is the stream's own: one buffer at a fixed address, zeroed

@@ -1067,6 +1067,58 @@ void stm_demux_nv12(unsigned char *img_l, unsigned char *img_r, unsigned char *y
     sync();
 }
 
+// NV12 output (an addition): the conversion as a stage, the counterpart of stm_demux_nv12 (stm_hip.h)
+} // extern "C"
+namespace {
+bool mux_nv12_args_ok(const char *fn, int pitch_y, int pitch_uv, int num_rows, int num_cols, int elem_sz, int matrix)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 2}, {"num_cols", num_cols, 2}, {"elem_sz", elem_sz, 3}})) return false;
+    char msg[200];
+    const char *arg = nullptr;
+    if (num_rows & 1) {
+        snprintf(msg, sizeof msg, "%s: num_rows = %d, must be even (a chroma row serves two rows)", fn, num_rows);
+        arg = "num_rows";
+    } else if (num_cols & 1) {
+        snprintf(msg, sizeof msg, "%s: num_cols = %d, must be even (a chroma sample serves two columns)", fn, num_cols);
+        arg = "num_cols";
+    } else if (pitch_y < num_cols) {
+        snprintf(msg, sizeof msg, "%s: pitch_y = %d, must be >= num_cols = %d", fn, pitch_y, num_cols);
+        arg = "pitch_y";
+    } else if (pitch_uv < num_cols) {
+        snprintf(msg, sizeof msg, "%s: pitch_uv = %d, must be >= num_cols = %d", fn, pitch_uv, num_cols);
+        arg = "pitch_uv";
+    } else if (matrix < 0 || matrix > 3) {
+        snprintf(msg, sizeof msg, "%s: matrix = %d, must be 0 (BT.601 limited), 1 (BT.709 limited), 2 (BT.601 full) or 3 (BT.709 full)", fn, matrix);
+        arg = "matrix";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+} // namespace
+extern "C" {
+void stm_d_mux_nv12(unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv, unsigned char *d_img, int num_rows, int num_cols,
+                    int elem_sz, int matrix)
+{
+    if (!mux_nv12_args_ok("d_mux_nv12", pitch_y, pitch_uv, num_rows, num_cols, elem_sz, matrix)) return;
+    launch_mux_nv12(nv12_out(d_y, pitch_y, d_uv, pitch_uv, matrix), d_img, num_rows, num_cols, elem_sz);
+}
+void stm_mux_nv12(unsigned char *y, int pitch_y, unsigned char *uv, int pitch_uv, unsigned char *img, int num_rows, int num_cols, int elem_sz,
+                  int matrix)
+{
+    if (!mux_nv12_args_ok("mux_nv12", pitch_y, pitch_uv, num_rows, num_cols, elem_sz, matrix)) return;
+    // a plane's last row need not be a whole pitch long
+    const size_t IMG = (size_t)num_rows * num_cols * elem_sz;
+    const size_t y_sz = (size_t)(num_rows - 1) * pitch_y + num_cols, uv_sz = (size_t)(num_rows / 2 - 1) * pitch_uv + num_cols;
+    Workspace::begin(IMG + y_sz + uv_sz + 4096);
+    u8 *di = up(img, IMG), *dy = Workspace::get<u8>(y_sz), *duv = Workspace::get<u8>(uv_sz);
+    STM_CHECK(hipMemsetAsync(dy, 0, y_sz, stream())); // the bytes between a row's samples and the next row come back 0
+    STM_CHECK(hipMemsetAsync(duv, 0, uv_sz, stream()));
+    launch_mux_nv12(nv12_out(dy, pitch_y, duv, pitch_uv, matrix), di, num_rows, num_cols, elem_sz);
+    down(y, dy, y_sz); down(uv, duv, uv_sz);
+    sync();
+}
+
 
 // packed input (an addition): the unpacking as a stage, from a BGR frame and from NV12 planes (stm_hip.h)
 void stm_d_demux_packed(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_img, int num_rows, int num_cols_sbs,
@@ -1321,18 +1373,56 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
 }
 
 // the thread's layout (stm_set_layout) against a rendering frame call's geometry, before anything is launched; layout 0, or a call
-// that renders nothing: nothing to check, the call is as it was
+// that renders nothing: nothing to check, the call is as it was.  The thread's output format (stm_set_output) is screened here too.
+// the thread's output format (stm_set_output) against a rendering frame call's geometry under the already screened layout `lo`
+static bool frame_output_ok(const char *fn, const Layout &lo, int Hout, int Wout)
+{
+    const Output o = output();
+    if (o.format == 0) return true;
+    char msg[240];
+    const char *arg = nullptr;
+    const long long P = o.pitch ? o.pitch : Wout, R = o.uv_row ? o.uv_row : Hout;
+    if (lo.layout == 0) {
+        snprintf(msg, sizeof msg, "%s: output format 1 (NV12) exists for quilts only (chroma subsampling destroys a sub-pixel interlaced frame): "
+                 "set a layout (stm_set_layout) or format 0", fn);
+        arg = "format, layout";
+    } else if (Hout & 1) {
+        snprintf(msg, sizeof msg, "%s: num_rows_out = %d, must be even for NV12 output (a chroma row serves two rows)", fn, Hout);
+        arg = "num_rows_out";
+    } else if (Wout & 1) {
+        snprintf(msg, sizeof msg, "%s: num_cols_out = %d, must be even for NV12 output (a chroma sample serves two columns)", fn, Wout);
+        arg = "num_cols_out";
+    } else if ((Wout / lo.tiles_x) & 1) {
+        snprintf(msg, sizeof msg, "%s: tile width num_cols_out / tiles_x = %d, must be even for NV12 output (every tile starts on a chroma sample)",
+                 fn, Wout / lo.tiles_x);
+        arg = "num_cols_out";
+    } else if ((Hout / lo.tiles_y) & 1) {
+        snprintf(msg, sizeof msg, "%s: tile height num_rows_out / tiles_y = %d, must be even for NV12 output (every tile starts on a chroma sample)",
+                 fn, Hout / lo.tiles_y);
+        arg = "num_rows_out";
+    } else if (P < Wout) {
+        snprintf(msg, sizeof msg, "%s: the NV12 surface's pitch = %lld, must be >= num_cols_out = %d", fn, P, Wout);
+        arg = "pitch";
+    } else if (R < Hout) {
+        snprintf(msg, sizeof msg, "%s: the NV12 surface's uv_row = %lld, must be >= num_rows_out = %d", fn, R, Hout);
+        arg = "uv_row";
+    } // pitch * (uv_row + num_rows_out / 2) < 2^31 * 1.5 * 2^31 < 2^63 for every int
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
 bool frame_layout_ok(const char *fn, int stages, int num_views, int H, int W, int Hout, int Wout)
 {
     const Layout lo = layout();
-    if (lo.layout == 0 || (stages & 0xff) < 3) return true;
+    if ((stages & 0xff) < 3) return true;
+    if (lo.layout == 0) return frame_output_ok(fn, lo, Hout, Wout);
     if (lens().mode != 0) {
         char msg[200];
         snprintf(msg, sizeof msg, "%s: layout 1 (quilt) together with lens mode %d: a quilt is not interlaced, set one of them to 0", fn, lens().mode);
         fail(msg, "layout, lens", __FILE__, __LINE__);
         return false;
     }
-    return quilt_args_ok(fn, lo, num_views, H, W, Hout, Wout, "num_views", "num_rows_out", "num_cols_out");
+    return quilt_args_ok(fn, lo, num_views, H, W, Hout, Wout, "num_views", "num_rows_out", "num_cols_out") && frame_output_ok(fn, lo, Hout, Wout);
 }
 
 // hit maps -> bleed -> masks -> N-2 views -> interlace (d_io.cu:160-205)
@@ -1354,8 +1444,13 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
     const Depth dp = depth();
     // a quilt (stm_set_layout) replaces the interlacer altogether: the views are tiled, whole.  The caller has screened the tiling
     // (frame_layout_ok).  With a depth budget there are no views to write; without one, 200 writes every view and tiles the table.
+    // Under stm_set_output's format 1 d_interlaced is an NV12 surface (screened by frame_layout_ok) and the quilt's kernels convert the
+    // pixels they render; 200 with depth mode 0 writes the BGR quilt into the workspace and converts that (stm_k_mux_nv12).
     const Layout lo = layout();
     if (lo.layout == 1) {
+        const Output of = output();
+        const Nv12Out surf = of.format == 1 ? nv12_out_surface(d_interlaced, of, Hout, Wout) : Nv12Out{};
+        const Nv12Out *nv = of.format == 1 ? &surf : nullptr;
         float *state = nullptr;
         if (dp.mode == 2) {
             uint32_t *hist = Workspace::get<uint32_t>(4096);
@@ -1368,11 +1463,13 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
             launch_view_synth_all(views_mem, IMG, N, img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, H, W, elem_sz, linear);
             u8 **dv = Workspace::get<u8 *>(N);
             launch_view_table(dv, img_r, img_l, views_mem, IMG, N);
-            launch_quilt((const u8 *const *)dv, d_interlaced, N, lo, H, W, Hout, Wout, elem_sz);
+            u8 *quilt = nv ? Workspace::get<u8>((size_t)Hout * Wout * elem_sz) : d_interlaced;
+            launch_quilt((const u8 *const *)dv, quilt, N, lo, H, W, Hout, Wout, elem_sz);
+            if (nv) launch_mux_nv12(surf, quilt, Hout, Wout, elem_sz);
             return;
         }
         launch_synth_quilt(img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, d_interlaced, N, lo, dp.mode, dp.gain, dp.conv, state, H, W,
-                           Hout, Wout, elem_sz, linear);
+                           Hout, Wout, elem_sz, linear, nv);
         return;
     }
     if (dp.mode != 0) {
@@ -1492,7 +1589,8 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
     const size_t V = pq_volume_floats(num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
     const Packing pack = packing(); // a packed frame (stm_set_packing): the caller has screened its geometry
-    Workspace::begin(((stages & 0x100) ? 13 : 4) * V * 4 + (size_t)(N + 2 + (pack.on() && hist && !nv ? 2 : 0)) * IMG + 168 * HW + (1u << 20));
+    Workspace::begin(((stages & 0x100) ? 13 : 4) * V * 4 + (size_t)(N + 2 + (pack.on() && hist && !nv ? 2 : 0)) * IMG + 168 * HW + (1u << 20) +
+                     (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0)); // the un-fused NV12 frame's BGR quilt
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     uint32_t *pre[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1766,7 +1864,8 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
     const bool hslo = stages_hslo(stages), subpix = stages_subpix(stages), interp = (stages & 0x400) != 0; // on the reduced pair
     const bool linwarp = (stages & 0x800) != 0;                                                             // in the full-size render
     const bool guided = (stages & 0x1000) != 0; // the up-scale between the two: stm_disp_upsample instead of tx_disp_scale
-    Workspace::begin((hslo ? 13 : 4) * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 32 * hw + (1u << 20)); // HSLO: as d_adcensus_stm
+    Workspace::begin((hslo ? 13 : 4) * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 32 * hw + (1u << 20) + // HSLO: as d_adcensus_stm
+                     (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0));
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     u8 *low_l = Workspace::get<u8>(hw * elem_sz), *low_r = Workspace::get<u8>(hw * elem_sz);
@@ -1820,7 +1919,7 @@ void reduced_frame_host(const char *fn, unsigned char *img_sbs, float *disp_l, f
         return;
     if (!frame_layout_ok(fn, stages, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return; // before the caller's arrays are written
     size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
-    size_t out_sz = (size_t)num_rows_out * num_cols_out * elem_sz;
+    size_t out_sz = frame_out_bytes(num_rows_out, num_cols_out, elem_sz); // stm_set_output: the NV12 surface
     const size_t need[4] = {sbs_sz, out_sz, HW * 4, HW * 4};
     void *buf[4];
     if (!host_frame_bufs(need, buf)) return;
@@ -2128,7 +2227,7 @@ void stm_adcensus_stm(unsigned char *img_sbs, float *disp_l, float *disp_r, unsi
     if (packing_unsupported("adcensus_stm")) return;
     if (!frame_layout_ok("adcensus_stm", 3, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return; // before the caller's arrays are written
     size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
-    size_t out_sz = (size_t)num_rows_out * num_cols_out * elem_sz;
+    size_t out_sz = frame_out_bytes(num_rows_out, num_cols_out, elem_sz); // stm_set_output: the NV12 surface
     // own buffers are cached outside the workspace: the pipeline call below re-carves the workspace
     const size_t need[4] = {sbs_sz, out_sz, HW * 4, HW * 4};
     void *buf[4];

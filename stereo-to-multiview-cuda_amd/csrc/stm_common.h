@@ -130,6 +130,34 @@ bool layout_params_ok(const char *fn, int layout, int tiles_x, int tiles_y, int 
 // rows_name, cols_name: the caller's names for the number of views and the output's size
 bool quilt_args_ok(const char *fn, const Layout &lo, int num_views, int in_rows, int in_cols, int out_rows, int out_cols, const char *views_name,
                    const char *rows_name, const char *cols_name);
+// The format of the output frame (stm_set_output, include/stm_hip.h): format 0 = BGR (the default), 1 = one NV12 surface -- the Y plane
+// of `pitch` bytes a row (0: num_cols_out) from byte 0, the UV plane from row `uv_row` (0: num_rows_out) -- converted by `matrix`.
+// One per host thread, next to the layout; a frame stream installs its own copy around its frame calls (stm_stream_set_output).
+struct Output {
+    int format, matrix, pitch, uv_row;
+};
+Output output();
+void set_output(const Output &o);
+// the rules of the four settings alone; false with the error recorded
+bool output_params_ok(const char *fn, int format, int matrix, int pitch, int uv_row);
+// the integer coefficients of stm_mux_nv12 (stm_hip.h) for `matrix`, and a screened NV12 destination as the kernels take it
+struct Nv12OutCoef {
+    int yo, yr, yg, yb, h, ur, ug, vg, vb;
+};
+Nv12OutCoef nv12_out_coef(int matrix);
+struct Nv12Out {
+    u8 *y, *uv;
+    size_t pitch_y, pitch_uv;
+    Nv12OutCoef k;
+    int pairs; // both planes' bases and pitches are even: a block's two samples of a row leave as one 16-bit store
+};
+Nv12Out nv12_out(u8 *y, size_t pitch_y, u8 *uv, size_t pitch_uv, int matrix);
+// the thread's NV12 surface at `surface` for a frame of Hout x Wout (format 1, screened by the frame call)
+Nv12Out nv12_out_surface(u8 *surface, const Output &o, int Hout, int Wout);
+// bytes of the thread's output frame: Hout * Wout * elem_sz, or the NV12 surface's pitch * (uv_row + Hout / 2)
+size_t frame_out_bytes(int Hout, int Wout, int elem_sz);
+// stm_k_mux_nv12 (stm_kernels_dibr.hip): the BGR image img (H x W x elem_sz, H and W even) into o
+void launch_mux_nv12(const Nv12Out &o, const u8 *img, int H, int W, int elem_sz);
 int quilt_lds_limit(); // stm_set_quilt_lds_limit: the bytes of LDS the area filter's staged kernel may take per workgroup
 int irv_paper_ratio(); // stm_set_irv_paper_ratio: accept on count / S instead of the reference's bin index / S (SURVEY A-Q17 iv)
 int irv_chunk();       // stm_set_irv_chunk: list entries per wave and trip of stm_k_irv_vote_cm, 0 = the kernel's own rule
@@ -325,9 +353,10 @@ void launch_synth_mux_depth(const u8 *img_l, const u8 *img_r, const float *disp_
 // the quilt (stm_set_layout, lo.layout == 1, screened by quilt_args_ok): a table of finished views tiled into `out`, and the frame's
 // renderer tiled directly with no view written (depth_mode 0: synth_sample's views; 1, 2: the depth budget's, state as above)
 void launch_quilt(const u8 *const *d_views, u8 *out, int N, const Layout &lo, int Hin, int Win, int Hout, int Wout, int elem_sz);
+// nv != nullptr (stm_set_output, format 1; every tile and remainder even): the same pixels leave as NV12 into *nv and `out` is not used
 void launch_synth_quilt(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l, const float *mask_r,
                         const float *blend, u8 *out, int N, const Layout &lo, int depth_mode, float gain, float conv, const float *state,
-                        int Hin, int Win, int Hout, int Wout, int elem_sz, bool linear);
+                        int Hin, int Win, int Hout, int Wout, int elem_sz, bool linear, const Nv12Out *nv = nullptr);
 // the measurement (stm_kernels_depth.hip): both maps into the 4096-bin histogram `hist` (scratch), the fit, the update of `state`
 // (four floats); fresh: the state's history is ignored
 void launch_depth_fit(float *state, uint32_t *hist, const float *disp_l, const float *disp_r, int H, int W, float disp_lo, float disp_hi,

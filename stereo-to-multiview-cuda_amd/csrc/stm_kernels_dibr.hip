@@ -1226,9 +1226,303 @@ __global__ __launch_bounds__(256) void stm_k_quilt_area_px(QuiltSrc s, u8 *__res
     o[0] = quilt_round(a0, g); o[1] = quilt_round(a1, g); o[2] = quilt_round(a2, g);
 }
 
+// ------------------------------------------------------------------ NV12 output (stm_hip.h, stm_set_output / stm_mux_nv12)
+// The quilt's pixels converted where they are rendered: a thread (filter 0: four lanes) owns whole 2 x 2 blocks, renders their four
+// pixels by the rules above (the rounded u8 values, as a BGR quilt would store them), and writes four Y samples and the block's
+// U, V pair.  Every tile and both remainders are even (the frame call's screen), so a block lies in one tile or in none.
+// The three functions below are the bodies of stm_k_quilt_nb, stm_k_quilt_area and stm_k_quilt_area_px, line for line, with the
+// pixel handed back instead of stored: the BGR kernels above keep their own text, so their code is what it was.
+// Filter 0: the three channels of output pixel (tx, ty) of tile (i, j) -- stm_k_mux's sampling position with the tile's size in place
+// of the frame's, the four-neighbour sampler on the renderer's samples
+template <int SRC, bool LINEAR>
+__device__ __forceinline__ void quilt_nb_sample(const QuiltSrc &s, const QuiltGeom &g, int i, int j, int tx, int ty, u8 (&o)[3])
+{
+    const int k = j * g.tiles_x + i;
+    const int v = (g.order & 2) ? g.N - 1 - k : k;
+    int left, top;
+    quilt_tile_origin(g, k, left, top);
+    const int u = tx - left, w = ty - top;
+    float xs = ((float)u / (float)g.tw) * (float)g.Win;
+    xs = fminf(fmaxf(xs, 0.0f), (float)(g.Win - 1));
+    float ys = ((float)w / (float)g.th) * (float)g.Hin;
+    ys = fminf(fmaxf(ys, 0.0f), (float)(g.Hin - 1));
+    if constexpr (SRC == QSRC_VIEWS) {
+        const u8 *vw = s.views[v];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = bilinear_u8(vw, g.elem_sz, c, xs, ys, g.Win, g.Hin);
+    } else {
+        const int y0 = (int)floorf(ys);
+        const int y1 = min(y0 + 1, g.Hin - 1);
+        const float wy = ys - (float)y0;
+        if constexpr (SRC == QSRC_SYNTH) {
+            const int x0 = (int)floorf(xs);
+            const int x1 = min(x0 + 1, g.Win - 1);
+            const float wx = xs - (float)x0;
+            const LensNb n00 = lens_nb(s.a, x0, y0, g.Win);
+            LensNb n01 = n00, n10 = n00, n11 = n00; // only read where the weight is not 0
+            if (wx != 0.0f) n01 = lens_nb(s.a, x1, y0, g.Win);
+            if (wy != 0.0f) {
+                n10 = lens_nb(s.a, x0, y1, g.Win);
+                if (wx != 0.0f) n11 = lens_nb(s.a, x1, y1, g.Win);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = lens_bilinear<LINEAR, false>(s.a, n00, n01, n10, n11, wx, wy, g.N, v, 0.0f, c, g.Win, g.elem_sz);
+        } else {
+            DepthNbs nb;
+            nb.x0 = -1;
+            nb.has_x1 = false;
+            const float sh = view_shift(v, g.N);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = depth_sample<LINEAR>(s.a, nb, sh, xs, y0, y1, wy, s.gain, s.conv, c, g.Win, g.elem_sz);
+        }
+    }
+}
+// the tile of output pixel (tx, ty); false: the pixel belongs to no tile
+__device__ __forceinline__ bool quilt_nb_tile(const QuiltGeom &g, int tx, int ty, int &i, int &j)
+{
+    i = tx / g.tw;
+    const int r = (g.order & 1) ? g.Hout - 1 - ty : ty; // rows counted from the edge the tile rows start at
+    j = r / g.th;
+    return i < g.tiles_x && j < g.tiles_y;
+}
+// the workgroup's block after the staging and the first reduction: where it lies and its partial sums
+struct QuiltAreaBlock {
+    int left, top, u0, w0, bw, bh, fy0;
+    const uint32_t *hs;
+};
+template <int SRC, bool LINEAR>
+__device__ __forceinline__ QuiltAreaBlock quilt_area_rows(QuiltSrc &s, const QuiltGeom &g, int BW, int BH, int fw_max, int fh_max)
+{
+    extern __shared__ uint32_t quilt_lds[];
+    if constexpr (SRC == QSRC_DEPTH)
+        if (s.state) {
+            s.gain = s.state[1];
+            s.conv = s.state[2];
+        }
+    uint32_t *pix = quilt_lds, *hs = quilt_lds + (size_t)fw_max * fh_max;
+    const int k = blockIdx.z;
+    const int v = (g.order & 2) ? g.N - 1 - k : k;
+    int left, top;
+    quilt_tile_origin(g, k, left, top);
+    const int u0 = blockIdx.x * BW, w0 = blockIdx.y * BH;
+    const int bw = min(BW, g.tw - u0), bh = min(BH, g.th - w0);
+    const int fx0 = (u0 * g.Win) / g.tw, fy0 = (w0 * g.Hin) / g.th;
+    const int fw = ((u0 + bw) * g.Win - 1) / g.tw - fx0 + 1, fh = ((w0 + bh) * g.Hin - 1) / g.th - fy0 + 1; // <= fw_max, fh_max
+    bool staged = false;
+    if constexpr (SRC == QSRC_SYNTH)
+        if (v == 0 || v == g.N - 1) { // view 0 = the right image, view N - 1 = the left image (d_io.cu:182-183): block-uniform
+            s.image = v == 0 ? s.a.img_r : s.a.img_l;
+            quilt_stage<QSRC_IMAGE, LINEAR>(s, g, v, fx0, fy0, fw, fh, pix);
+            staged = true;
+        }
+    if (!staged) quilt_stage<SRC, LINEAR>(s, g, v, fx0, fy0, fw, fh, pix);
+    __syncthreads();
+    for (int t = threadIdx.x; t < fh * bw; t += 256) {
+        const int fy = t / bw, u = u0 + (t - fy * bw);
+        const int xa = (u * g.Win) / g.tw, xb = ((u + 1) * g.Win - 1) / g.tw;
+        uint32_t s0 = 0, s1 = 0, s2 = 0;
+        const uint32_t *row = pix + fy * fw;
+        for (int x = xa; x <= xb; ++x) {
+            const uint32_t wx = quilt_weight(u, x, g.Win, g.tw), p = row[x - fx0];
+            s0 += wx * (p & 255u);
+            s1 += wx * ((p >> 8) & 255u);
+            s2 += wx * (p >> 16);
+        }
+        hs[3 * t] = s0; hs[3 * t + 1] = s1; hs[3 * t + 2] = s2;
+    }
+    __syncthreads();
+    return QuiltAreaBlock{left, top, u0, w0, bw, bh, fy0, hs};
+}
+// the second reduction of the block's pixel (ul, wl), rounded
+__device__ __forceinline__ void quilt_area_pixel(const QuiltAreaBlock &b, const QuiltGeom &g, int ul, int wl, u8 (&o)[3])
+{
+    const int w = b.w0 + wl;
+    const int ya = (w * g.Hin) / g.th, yb = ((w + 1) * g.Hin - 1) / g.th;
+    unsigned long long a0 = 0, a1 = 0, a2 = 0;
+    for (int y = ya; y <= yb; ++y) {
+        const unsigned long long wy = quilt_weight(w, y, g.Hin, g.th);
+        const uint32_t *h = b.hs + 3 * ((y - b.fy0) * b.bw + ul);
+        a0 += wy * h[0];
+        a1 += wy * h[1];
+        a2 += wy * h[2];
+    }
+    o[0] = quilt_round(a0, g); o[1] = quilt_round(a1, g); o[2] = quilt_round(a2, g);
+}
+// The same average of tile pixel (u, w) of view v by one thread looping over the pixel's own footprint: every view pixel is rendered
+// by each output pixel that overlaps it
+template <int SRC, bool LINEAR>
+__device__ __forceinline__ void quilt_area_own(const QuiltSrc &s, const QuiltGeom &g, int v, int u, int w, u8 (&o)[3])
+{
+    const int xa = (u * g.Win) / g.tw, xb = ((u + 1) * g.Win - 1) / g.tw;
+    const int ya = (w * g.Hin) / g.th, yb = ((w + 1) * g.Hin - 1) / g.th;
+    unsigned long long a0 = 0, a1 = 0, a2 = 0;
+    for (int y = ya; y <= yb; ++y) {
+        uint32_t s0 = 0, s1 = 0, s2 = 0;
+        for (int x = xa; x <= xb; ++x) {
+            const uint32_t wx = quilt_weight(u, x, g.Win, g.tw);
+            uint32_t px[3];
+            quilt_render3_any<SRC, LINEAR>(s, g, v, x, y, px);
+            s0 += wx * px[0];
+            s1 += wx * px[1];
+            s2 += wx * px[2];
+        }
+        const unsigned long long wy = quilt_weight(w, y, g.Hin, g.th);
+        a0 += wy * s0;
+        a1 += wy * s1;
+        a2 += wy * s2;
+    }
+    o[0] = quilt_round(a0, g); o[1] = quilt_round(a1, g); o[2] = quilt_round(a2, g);
+}
+// A block's two samples of a plane row leave as one 16-bit store where both planes' bases and pitches are even, as bytes otherwise.
+__device__ __forceinline__ void nv12_store_pair(u8 *p, uint32_t a, uint32_t b, int pairs)
+{
+    if (pairs) {
+        *(unsigned short *)p = (unsigned short)(a | (b << 8));
+    } else {
+        p[0] = (u8)a;
+        p[1] = (u8)b;
+    }
+}
+__device__ __forceinline__ int nv12_luma(const Nv12OutCoef &k, int b, int g, int r)
+{
+    return (k.yr * r + k.yg * g + k.yb * b + (k.yo << 16) + 32768) >> 16; // in 0 .. 255 for every pixel: no clip
+}
+// U and V of a block from the sums of its four pixels' B, G and R
+__device__ __forceinline__ void nv12_chroma(const Nv12OutCoef &k, int sb, int sg, int sr, int &U, int &V)
+{
+    U = min(max((k.h * sb - k.ug * sg - k.ur * sr + (128 << 18) + (1 << 17)) >> 18, 0), 255);
+    V = min(max((k.h * sr - k.vg * sg - k.vb * sb + (128 << 18) + (1 << 17)) >> 18, 0), 255);
+}
+// stm_mux_nv12's arithmetic on the block at even (x, y): px = its pixels (x, y), (x + 1, y), (x, y + 1), (x + 1, y + 1) as B, G, R
+__device__ __forceinline__ void nv12_store_block(const Nv12Out &o, int x, int y, const u8 (&px)[4][3])
+{
+    const Nv12OutCoef &k = o.k;
+    int Y[4], sb = 0, sg = 0, sr = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int b = px[q][0], gr = px[q][1], r = px[q][2];
+        Y[q] = nv12_luma(k, b, gr, r);
+        sb += b;
+        sg += gr;
+        sr += r;
+    }
+    int U, V;
+    nv12_chroma(k, sb, sg, sr, U, V);
+    u8 *py = o.y + (size_t)y * o.pitch_y + x;
+    nv12_store_pair(py, Y[0], Y[1], o.pairs);
+    nv12_store_pair(py + o.pitch_y, Y[2], Y[3], o.pairs);
+    nv12_store_pair(o.uv + (size_t)(y >> 1) * o.pitch_uv + x, U, V, o.pairs);
+}
+
+// The conversion as a stage (stm_mux_nv12), and the un-fused frame's second kernel: one thread per 2 x 2 block of img
+__global__ __launch_bounds__(256) void stm_k_mux_nv12(Nv12Out o, const u8 *__restrict__ img, int W, int elem_sz)
+{
+    const int x = 2 * (blockIdx.x * 256 + threadIdx.x), y = 2 * blockIdx.y;
+    if (x >= W) return;
+    u8 px[4][3];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const u8 *p = img + ((size_t)(y + (q >> 1)) * W + x + (q & 1)) * elem_sz;
+        px[q][0] = p[0]; px[q][1] = p[1]; px[q][2] = p[2];
+    }
+    nv12_store_block(o, x, y, px);
+}
+void launch_mux_nv12(const Nv12Out &o, const u8 *img, int H, int W, int elem_sz)
+{
+    ProfScope p("mux_nv12");
+    STM_LAUNCH(stm_k_mux_nv12, dim3(cdiv(W / 2, 256), H / 2), dim3(256), 0, stream(), o, img, W, elem_sz);
+    STM_CHECK_LAUNCH();
+}
+
+// Filter 0 into NV12: four adjacent lanes own a 2 x 2 block, one pixel each, rendered as stm_k_quilt_nb renders it -- a wave has the
+// loads of 64 pixels in flight, as there; one thread rendering the block's four pixels in turn took 2.4 times as long (DESIGN.md
+// section 20).  A row's neighbour and the block's sums cross the lanes; a block of no tile is (0, 0, 0) four times.
+template <int SRC, bool LINEAR>
+__global__ __launch_bounds__(256) void stm_k_quilt_nb_nv12(QuiltSrc s, Nv12Out o, QuiltGeom g)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x, sub = t & 3;
+    const int bx = 2 * (t >> 2), by = 2 * blockIdx.y;
+    if (bx >= g.Wout) return; // the four lanes of a block leave together
+    if constexpr (SRC == QSRC_DEPTH)
+        if (s.state) {
+            s.gain = s.state[1];
+            s.conv = s.state[2];
+        }
+    const int tx = bx + (sub & 1), ty = by + (sub >> 1);
+    u8 px[3] = {0, 0, 0};
+    int i, j;
+    if (quilt_nb_tile(g, tx, ty, i, j)) quilt_nb_sample<SRC, LINEAR>(s, g, i, j, tx, ty, px); // the same for all four lanes
+    const uint32_t Y = (uint32_t)nv12_luma(o.k, px[0], px[1], px[2]);
+    const uint32_t Yn = (uint32_t)__shfl_xor((int)Y, 1);
+    uint32_t sum = px[0] | ((uint32_t)px[1] << 10) | ((uint32_t)px[2] << 20); // three sums of at most 1020, ten bits each
+    sum += (uint32_t)__shfl_xor((int)sum, 1);
+    sum += (uint32_t)__shfl_xor((int)sum, 2);
+    u8 *py = o.y + (size_t)ty * o.pitch_y + tx;
+    if (!o.pairs) *py = (u8)Y;
+    else if (!(sub & 1)) *(unsigned short *)py = (unsigned short)(Y | (Yn << 8));
+    if (sub == 0) {
+        int U, V;
+        nv12_chroma(o.k, sum & 1023u, (sum >> 10) & 1023u, sum >> 20, U, V);
+        nv12_store_pair(o.uv + (size_t)(by >> 1) * o.pitch_uv + bx, U, V, o.pairs);
+    }
+}
+// Filter 1 into NV12: stm_k_quilt_area with its last phase walking the 2 x 2 blocks of the workgroup's pixels (BW and BH even)
+template <int SRC, bool LINEAR>
+__global__ __launch_bounds__(256) void stm_k_quilt_area_nv12(QuiltSrc s, Nv12Out o, QuiltGeom g, int BW, int BH, int fw_max, int fh_max)
+{
+    const QuiltAreaBlock b = quilt_area_rows<SRC, LINEAR>(s, g, BW, BH, fw_max, fh_max);
+    const int cw = b.bw >> 1;
+    for (int t = threadIdx.x; t < (b.bh >> 1) * cw; t += 256) {
+        const int wl = 2 * (t / cw), ul = 2 * (t % cw);
+        u8 px[4][3];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) quilt_area_pixel(b, g, ul + (q & 1), wl + (q >> 1), px[q]);
+        nv12_store_block(o, b.left + b.u0 + ul, b.top + b.w0 + wl, px);
+    }
+}
+// ... and the per-pixel form with one thread per 2 x 2 block, where not even such a block's footprint fits the staging
+template <int SRC, bool LINEAR>
+__global__ __launch_bounds__(256) void stm_k_quilt_area_px_nv12(QuiltSrc s, Nv12Out o, QuiltGeom g)
+{
+    const int u = 2 * (blockIdx.x * 256 + threadIdx.x), w = 2 * blockIdx.y, k = blockIdx.z;
+    if (u >= g.tw) return;
+    if constexpr (SRC == QSRC_DEPTH)
+        if (s.state) {
+            s.gain = s.state[1];
+            s.conv = s.state[2];
+        }
+    const int v = (g.order & 2) ? g.N - 1 - k : k;
+    int left, top;
+    quilt_tile_origin(g, k, left, top);
+    u8 px[4][3];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) quilt_area_own<SRC, LINEAR>(s, g, v, u + (q & 1), w + (q >> 1), px[q]);
+    nv12_store_block(o, left + u, top + w, px);
+}
+// the blocks of no tile (stm_k_quilt_pad's pixels, both remainders even): Y of black and 128 / 128
+__global__ __launch_bounds__(256) void stm_k_quilt_pad_nv12(Nv12Out o, QuiltGeom g, int rem_w, int rem_h)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t bw = (size_t)(rem_w >> 1), n_right = bw * (g.Hout >> 1), used_w = (size_t)((g.Wout - rem_w) >> 1);
+    int x, y;
+    if (t < n_right) {
+        y = (int)(t / bw);
+        x = (int)used_w + (int)(t - (size_t)y * bw);
+    } else {
+        const size_t q = t - n_right;
+        if (q >= used_w * (rem_h >> 1)) return;
+        const int r = (int)(q / used_w);
+        x = (int)(q - (size_t)r * used_w);
+        y = (g.order & 1) ? r : ((g.Hout - rem_h) >> 1) + r; // bottom-up tiles leave the top rows
+    }
+    const u8 px[4][3] = {};
+    nv12_store_block(o, 2 * x, 2 * y, px);
+}
+
 // The block of the staged kernel: the largest of 32 x 16, halved along the axis with the longer footprint, whose staging fits
-// `limit` bytes of LDS; false where not even one output pixel's footprint does.
-static bool quilt_block(const QuiltGeom &g, size_t limit, int &BW, int &BH, int &fw_max, int &fh_max, size_t &bytes)
+// `limit` bytes of LDS; false where not even one output pixel's footprint does.  least = 2 (NV12): BW and BH stay even, and false where
+// not even a 2 x 2 block's footprint fits.
+static bool quilt_block(const QuiltGeom &g, size_t limit, int &BW, int &BH, int &fw_max, int &fh_max, size_t &bytes, int least = 1)
 {
     BW = 32;
     BH = 16;
@@ -1237,14 +1531,38 @@ static bool quilt_block(const QuiltGeom &g, size_t limit, int &BW, int &BH, int 
         fh_max = min(g.Hin, cdiv(BH * g.Hin, g.th) + 1);
         bytes = 4 * ((size_t)fw_max * fh_max + (size_t)fh_max * BW * 3);
         if (bytes <= limit) return true;
-        if (BH > 1 && (fh_max >= fw_max || BW == 1)) BH /= 2;
-        else if (BW > 1) BW /= 2;
+        if (BH > least && (fh_max >= fw_max || BW == least)) BH /= 2;
+        else if (BW > least) BW /= 2;
         else return false;
     }
 }
+// the same pixels into an NV12 surface: every kernel's NV12 form, a thread per 2 x 2 block
 template <int SRC, bool LINEAR>
-static void launch_quilt_src(const QuiltSrc &s, u8 *out, const QuiltGeom &g, int filter)
+static void launch_quilt_src_nv12(const QuiltSrc &s, const Nv12Out &o, const QuiltGeom &g, int filter)
 {
+    if (filter == 0) {
+        STM_LAUNCH((stm_k_quilt_nb_nv12<SRC, LINEAR>), dim3(cdiv(2 * g.Wout, 256), g.Hout / 2), dim3(256), 0, stream(), s, o, g);
+        return;
+    }
+    const int rem_w = g.Wout - g.tiles_x * g.tw, rem_h = g.Hout - g.tiles_y * g.th;
+    const size_t n_pad = ((size_t)rem_w * g.Hout + (size_t)(g.Wout - rem_w) * rem_h) / 4;
+    if (n_pad) STM_LAUNCH(stm_k_quilt_pad_nv12, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, stream(), o, g, rem_w, rem_h);
+    int BW, BH, fw_max, fh_max;
+    size_t bytes;
+    if (quilt_block(g, (size_t)quilt_lds_limit(), BW, BH, fw_max, fh_max, bytes, 2))
+        STM_LAUNCH((stm_k_quilt_area_nv12<SRC, LINEAR>), dim3(cdiv(g.tw, BW), cdiv(g.th, BH), g.N), dim3(256), bytes, stream(), s, o, g, BW, BH,
+                   fw_max, fh_max);
+    else
+        STM_LAUNCH((stm_k_quilt_area_px_nv12<SRC, LINEAR>), dim3(cdiv(g.tw / 2, 256), g.th / 2, g.N), dim3(256), 0, stream(), s, o, g);
+}
+template <int SRC, bool LINEAR>
+static void launch_quilt_src(const QuiltSrc &s, u8 *out, const QuiltGeom &g, int filter, const Nv12Out *nv = nullptr)
+{
+    if constexpr (SRC != QSRC_VIEWS) // a table of views is never tiled into NV12: the un-fused frame converts its BGR quilt
+        if (nv) {
+            launch_quilt_src_nv12<SRC, LINEAR>(s, *nv, g, filter);
+            return;
+        }
     const dim3 full(cdiv(g.Wout, 256), g.Hout);
     if (filter == 0) {
         STM_LAUNCH((stm_k_quilt_nb<SRC, LINEAR>), full, dim3(256), 0, stream(), s, out, g);
@@ -1280,7 +1598,7 @@ void launch_quilt(const u8 *const *d_views, u8 *out, int N, const Layout &lo, in
 // depth_mode 0: synth_sample's views; 1, 2: the depth budget's (state != nullptr: gain and conv are read on the device)
 void launch_synth_quilt(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l, const float *mask_r,
                         const float *blend, u8 *out, int N, const Layout &lo, int depth_mode, float gain, float conv, const float *state,
-                        int Hin, int Win, int Hout, int Wout, int elem_sz, bool linear)
+                        int Hin, int Win, int Hout, int Wout, int elem_sz, bool linear, const Nv12Out *nv)
 {
     QuiltSrc s{};
     s.a = SynthArgs{img_l, img_r, disp_l, disp_r, mask_l, mask_r, blend};
@@ -1290,11 +1608,11 @@ void launch_synth_quilt(const u8 *img_l, const u8 *img_r, const float *disp_l, c
     const QuiltGeom g = quilt_geom(lo, N, Hin, Win, Hout, Wout, elem_sz);
     ProfScope p("synth_quilt");
     if (depth_mode == 0) {
-        if (linear) launch_quilt_src<QSRC_SYNTH, true>(s, out, g, lo.filter);
-        else launch_quilt_src<QSRC_SYNTH, false>(s, out, g, lo.filter);
+        if (linear) launch_quilt_src<QSRC_SYNTH, true>(s, out, g, lo.filter, nv);
+        else launch_quilt_src<QSRC_SYNTH, false>(s, out, g, lo.filter, nv);
     } else {
-        if (linear) launch_quilt_src<QSRC_DEPTH, true>(s, out, g, lo.filter);
-        else launch_quilt_src<QSRC_DEPTH, false>(s, out, g, lo.filter);
+        if (linear) launch_quilt_src<QSRC_DEPTH, true>(s, out, g, lo.filter, nv);
+        else launch_quilt_src<QSRC_DEPTH, false>(s, out, g, lo.filter, nv);
     }
     STM_CHECK_LAUNCH();
 }

@@ -292,6 +292,70 @@ bool layout_params_ok(const char *fn, int layout, int tiles_x, int tiles_y, int 
     fail(msg, arg, __FILE__, __LINE__);
     return false;
 }
+// the calling thread's output format (stm_set_output)
+static thread_local Output g_output = {0, 0, 0, 0};
+Output output() { return g_output; }
+void set_output(const Output &o) { g_output = o; }
+bool output_params_ok(const char *fn, int format, int matrix, int pitch, int uv_row)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (format != 0 && format != 1) {
+        snprintf(msg, sizeof msg, "%s: format = %d, must be 0 (BGR) or 1 (NV12)", fn, format);
+        arg = "format";
+    } else if (format == 0) {
+        return true; // BGR: the other arguments are ignored
+    } else if (matrix < 0 || matrix > 3) {
+        snprintf(msg, sizeof msg, "%s: matrix = %d, must be 0 (BT.601 limited), 1 (BT.709 limited), 2 (BT.601 full) or 3 (BT.709 full)", fn, matrix);
+        arg = "matrix";
+    } else if (pitch < 0) {
+        snprintf(msg, sizeof msg, "%s: pitch = %d, must be >= 0 (0: num_cols_out)", fn, pitch);
+        arg = "pitch";
+    } else if (uv_row < 0) {
+        snprintf(msg, sizeof msg, "%s: uv_row = %d, must be >= 0 (0: num_rows_out)", fn, uv_row);
+        arg = "uv_row";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+// stm_mux_nv12's coefficients (stm_hip.h): each rounded one computed in double and rounded to nearest, the three derived ones by
+// subtraction, so that white lands on the range's end and every grey on 128 / 128
+Nv12OutCoef nv12_out_coef(int matrix)
+{
+    const double Kr = (matrix & 1) ? 0.2126 : 0.299, Kb = (matrix & 1) ? 0.0722 : 0.114;
+    const bool full = matrix >= 2;
+    const double sy = full ? 1.0 : 219.0 / 255.0, sc = full ? 1.0 : 224.0 / 255.0;
+    Nv12OutCoef k;
+    k.yo = full ? 0 : 16;
+    const int ys = (int)std::lround(65536.0 * sy);
+    k.yr = (int)std::lround(65536.0 * Kr * sy);
+    k.yb = (int)std::lround(65536.0 * Kb * sy);
+    k.yg = ys - k.yr - k.yb;
+    k.h = (int)std::lround(32768.0 * sc);
+    k.ur = (int)std::lround(65536.0 * Kr * sc / (2.0 * (1.0 - Kb)));
+    k.ug = k.h - k.ur;
+    k.vb = (int)std::lround(65536.0 * Kb * sc / (2.0 * (1.0 - Kr)));
+    k.vg = k.h - k.vb;
+    return k;
+}
+Nv12Out nv12_out(u8 *y, size_t pitch_y, u8 *uv, size_t pitch_uv, int matrix)
+{
+    const int pairs = (((uintptr_t)y | (uintptr_t)uv | pitch_y | pitch_uv) & 1) == 0;
+    return Nv12Out{y, uv, pitch_y, pitch_uv, nv12_out_coef(matrix), pairs};
+}
+Nv12Out nv12_out_surface(u8 *surface, const Output &o, int Hout, int Wout)
+{
+    const size_t P = o.pitch ? o.pitch : Wout, R = o.uv_row ? o.uv_row : Hout;
+    return nv12_out(surface, P, surface + P * R, P, o.matrix);
+}
+size_t frame_out_bytes(int Hout, int Wout, int elem_sz)
+{
+    const Output o = output();
+    if (o.format == 0) return (size_t)Hout * Wout * elem_sz;
+    const size_t P = o.pitch ? o.pitch : Wout, R = o.uv_row ? o.uv_row : Hout;
+    return P * (R + (size_t)Hout / 2);
+}
 static int g_quilt_lds_limit = 32 * 1024; // five workgroups of the staged kernel share a CU's 160 KiB
 int quilt_lds_limit() { return g_quilt_lds_limit; }
 
@@ -507,6 +571,18 @@ void stm_get_layout(int *out)
 {
     const stm::Layout lo = stm::layout();
     out[0] = lo.layout; out[1] = lo.tiles_x; out[2] = lo.tiles_y; out[3] = lo.order; out[4] = lo.filter;
+}
+int stm_set_output(int format, int matrix, int pitch, int uv_row)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (!stm::output_params_ok("set_output", format, matrix, pitch, uv_row)) return -1; // the thread's format stays as it was
+    stm::set_output(format == 0 ? stm::Output{0, 0, 0, 0} : stm::Output{format, matrix, pitch, uv_row});
+    return 0;
+}
+void stm_get_output(int out[4])
+{
+    const stm::Output o = stm::output();
+    out[0] = o.format; out[1] = o.matrix; out[2] = o.pitch; out[3] = o.uv_row;
 }
 void stm_set_quilt_lds_limit(int bytes) { stm::g_quilt_lds_limit = bytes <= 0 ? 32 * 1024 : (bytes > 64 * 1024 ? 64 * 1024 : bytes); }
 int stm_set_packing(int packing, int swap, int filter, int gap)

@@ -50,6 +50,8 @@ struct FrameStream {
     size_t in_bytes = 0;              // what a submit copies and uploads: in_sz, or H * Wsbs * 3 / 2 for NV12
     stm::Lens lens = {0, 0.0, 0.0, 0.0}; // stm_stream_set_lens: the stream's own display geometry, installed around its frame calls
     stm::Layout layout = {0, 1, 1, 0, 0}; // stm_stream_set_layout: the stream's own output geometry, installed around its frame calls
+    stm::Output output = {0, 0, 0, 0};    // stm_stream_set_output: the stream's own output format, installed around its frame calls
+    size_t out_bytes = 0;                 // what a collect copies and the download moves: out_sz, or Hout * Wout * 3 / 2 for NV12
     stm::Depth depth = {0, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 20, nullptr}; // stm_stream_set_depth / _auto: the stream's own depth budget
     stm::Packing packing = {0, 0, 0, 0}; // stm_stream_set_packing: the stream's own input packing, installed around its frame calls
     int rows_f = 0;                      // the rows of an input frame: H, or what the packing makes of it
@@ -71,6 +73,12 @@ struct LayoutScope {
     stm::Layout saved;
     explicit LayoutScope(const stm::Layout &l) : saved(stm::layout()) { stm::set_layout(l); }
     ~LayoutScope() { stm::set_layout(saved); }
+};
+
+struct OutputScope {
+    stm::Output saved;
+    explicit OutputScope(const stm::Output &o) : saved(stm::output()) { stm::set_output(o); }
+    ~OutputScope() { stm::set_output(saved); }
 };
 
 struct DepthScope {
@@ -114,6 +122,7 @@ void *stm_stream_create(int num_rows, int num_cols_sbs, int num_cols, int num_ro
     f->in_bytes = f->in_sz;
     f->rows_f = num_rows;
     f->out_sz = (size_t)num_rows_out * num_cols_out * elem_sz;
+    f->out_bytes = f->out_sz;
     f->hw = (size_t)num_rows * num_cols;
     STM_CHECK(hipGetDevice(&f->dev));
     STM_CHECK(hipStreamCreateWithFlags(&f->s_in, hipStreamNonBlocking));
@@ -354,7 +363,36 @@ int stm_stream_set_layout(void *h, int layout, int tiles_x, int tiles_y, int ord
         stm::fail("stream_set_layout: only before the first submit", "stream", __FILE__, __LINE__);
         return -1;
     }
+    if (layout == 0 && f->output.format == 1) {
+        stm::fail("stream_set_layout: the stream's output format is 1 (NV12), which exists for quilts only: set format 0 first "
+                  "(stm_stream_set_output)", "layout", __FILE__, __LINE__);
+        return -1;
+    }
     f->layout = layout == 0 ? stm::Layout{0, 1, 1, 0, 0} : stm::Layout{layout, tiles_x, tiles_y, order, filter};
+    return 0;
+}
+
+// The output format of every frame of the stream (stm_set_output's formats and matrices; the default is format 0, BGR).  Format 1:
+// each frame leaves as one contiguous NV12 surface, the Y plane of num_rows_out rows of num_cols_out bytes and the UV plane right
+// behind it, num_rows_out * num_cols_out * 3 / 2 bytes in all -- that is what the download moves and a collect copies.  Kept and
+// installed like the layout; the surface is screened against the stream's geometry by the first frame call.  Refused while the
+// stream's layout is 0, and only before the first submit.  Returns 0, or -1 with the error recorded.
+int stm_stream_set_output(void *h, int format, int matrix)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (!stm::output_params_ok("stream_set_output", format, matrix, 0, 0)) return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_output: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    if (format == 1 && f->layout.layout == 0) {
+        stm::fail("stream_set_output: format 1 (NV12) exists for quilts only: set the stream's layout first (stm_stream_set_layout)", "format",
+                  __FILE__, __LINE__);
+        return -1;
+    }
+    f->output = format == 0 ? stm::Output{0, 0, 0, 0} : stm::Output{1, matrix, 0, 0};
+    f->out_bytes = format == 1 ? (size_t)f->Hout * f->Wout * 3 / 2 : f->out_sz;
     return 0;
 }
 
@@ -446,6 +484,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     void *prev = stm_get_stream();
     LensScope lens_scope(f->lens);
     LayoutScope layout_scope(f->layout);
+    OutputScope output_scope(f->output);
     DepthScope depth_scope(f->depth);
     PackingScope packing_scope(f->packing);
     stm_set_stream(s.s_compute);
@@ -530,7 +569,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     STM_CHECK(hipStreamWaitEvent(f->s_out, s.ev_done, 0));
     STM_CHECK(hipMemcpyAsync(s.h_dl, s.d_dl, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
     STM_CHECK(hipMemcpyAsync(s.h_dr, s.d_dr, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
-    STM_CHECK(hipMemcpyAsync(s.h_out, s.d_out, f->out_sz, hipMemcpyDeviceToHost, f->s_out));
+    STM_CHECK(hipMemcpyAsync(s.h_out, s.d_out, f->out_bytes, hipMemcpyDeviceToHost, f->s_out));
     if (depth_auto) STM_CHECK(hipMemcpyAsync(s.h_rec, s.d_rec, 16, hipMemcpyDeviceToHost, f->s_out));
     STM_CHECK(hipEventRecord(s.ev_out, f->s_out));
     if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
@@ -549,7 +588,7 @@ long stm_stream_collect(void *h, float *disp_l, float *disp_r, unsigned char *in
     STM_CHECK(hipEventSynchronize(s.ev_out));
     if (disp_l) memcpy(disp_l, s.h_dl, f->hw * 4);
     if (disp_r) memcpy(disp_r, s.h_dr, f->hw * 4);
-    if (interlaced) memcpy(interlaced, s.h_out, f->out_sz);
+    if (interlaced) memcpy(interlaced, s.h_out, f->out_bytes);
     s.busy = false;
     return f->collected++;
 }

@@ -114,6 +114,51 @@ def get_layout():
     return tuple(int(v) for v in out)
 
 
+def set_output(format=0, matrix=0, pitch=0, uv_row=0):
+    """stm_set_output: the calling thread's output format, which every rendering frame call writes.  format 0 = BGR (the default; the
+    other arguments are ignored), 1 = NV12 (quilts only): the frame calls' `interlaced` is then ONE surface, a 2-D uint8 tensor of
+    (R + Hout / 2) x P -- the Y plane in rows 0 .. Hout - 1, the interleaved UV plane from row R; P = pitch or Wout, R = uv_row or
+    Hout -- converted by `matrix` (0 / 1 = BT.601 / BT.709 limited range, 2 / 3 = full range).  Raises ValueError where the library
+    refuses."""
+    if int(lib().stm_set_output(int(format), int(matrix), int(pitch), int(uv_row))) != 0:
+        raise ValueError("stm_set_output(%d, %d, %d, %d) refused: %s" % (format, matrix, pitch, uv_row, lib().stm_last_error().decode()))
+
+
+def get_output():
+    """stm_get_output: the calling thread's (format, matrix, pitch, uv_row) as the library holds it"""
+    out = (C.c_int * 4)()
+    lib().stm_get_output(out)
+    return tuple(int(v) for v in out)
+
+
+def _out_size(interlaced, p):
+    """(Hout, Wout) of a frame call's output: a BGR frame's first two dimensions, or -- under set_output's format 1 -- what the 2-D
+    surface of (R + Hout / 2) x P holds; p.out_rows / p.out_cols, where set, say it outright (needed with a pitch beyond Wout)"""
+    fmt, _, pitch, uv_row = get_output()
+    if fmt == 0:
+        return interlaced.shape[0], interlaced.shape[1]
+    assert interlaced.dim() == 2 and interlaced.dtype == torch.uint8 and interlaced.is_contiguous()
+    rows, P = interlaced.shape
+    assert pitch in (0, P), "the surface's row length must be the pitch of set_output"
+    Wo = p.out_cols or P
+    Ho = p.out_rows or ((rows - uv_row) * 2 if uv_row else rows * 2 // 3)
+    assert rows >= (uv_row or Ho) + Ho // 2
+    return Ho, Wo
+
+
+def d_mux_nv12(y, uv, img, matrix=0):
+    """stm_d_mux_nv12: the BGR image img (uint8 [H][W][E], H and W even) converted into the NV12 planes y (uint8 [H][>= W]) and uv
+    (uint8 [H / 2][>= W], U and V interleaved, each the mean of a 2 x 2 block), 2-D tensors whose row stride is the plane's pitch;
+    only the samples are written.  matrix: 0 / 1 = BT.601 / BT.709 limited range, 2 / 3 = BT.601 / BT.709 full range."""
+    assert img.is_cuda and img.dtype == torch.uint8 and img.is_contiguous() and img.dim() == 3
+    H, W, E = img.shape
+    for t in (y, uv):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1) and t.shape[1] >= W
+    assert y.shape[0] == H and uv.shape[0] * 2 == H
+    _use_current_stream()
+    lib().stm_d_mux_nv12(_p(y), y.stride(0), _p(uv), uv.stride(0), _p(img), H, W, E, int(matrix))
+
+
 PACKING_OFF = (0, 0, 0, 0)
 
 def set_packing(packing=0, swap=0, filter=0, gap=0):
@@ -255,7 +300,7 @@ def d_adcensus_stm(sbs, disp_l, disp_r, interlaced, p, stages=3):
     H, Wsbs, E = sbs.shape
     H, W = _eye_shape(H, Wsbs, disp_l)
     assert disp_l.shape == (H, W) and disp_r.shape == (H, W) and disp_l.dtype == torch.float32
-    Ho, Wo = interlaced.shape[0], interlaced.shape[1]
+    Ho, Wo = _out_size(interlaced, p)
     _use_current_stream()
     lib().stm_d_adcensus_stm(_p(sbs), _p(disp_l), _p(disp_r), _p(interlaced), H, Wsbs, W, Ho, Wo, E,
                              p.num_views, p.angle, p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff,
@@ -276,7 +321,7 @@ def d_adcensus_stm_t(sbs, disp_l, disp_r, interlaced, p, stages=3, prev_sbs=None
     for t in (prev_disp_l, prev_disp_r):
         if t is not None:
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
-    Ho, Wo = interlaced.shape[0], interlaced.shape[1]
+    Ho, Wo = _out_size(interlaced, p)
     _use_current_stream()
     lib().stm_d_adcensus_stm_t(_p(sbs), _p(disp_l), _p(disp_r), _p(interlaced), H, Wsbs, W, Ho, Wo, E,
                                p.num_views, p.angle, p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff,
@@ -326,7 +371,7 @@ def d_adcensus_stm_nv12(y, uv, disp_l, disp_r, interlaced, p, stages=3, matrix=0
     for t in (prev_disp_l, prev_disp_r):
         if t is not None:
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
-    Ho, Wo = interlaced.shape[0], interlaced.shape[1]
+    Ho, Wo = _out_size(interlaced, p)
 
     def opt(t):
         return None if t is None else _p(t)
@@ -345,7 +390,7 @@ def d_adcensus_stm_2s(sbs, disp_l, disp_r, interlaced, p, disp_rows, disp_cols, 
     H, Wsbs, E = sbs.shape
     W = Wsbs // 2
     assert disp_l.shape == (H, W) and disp_r.shape == (H, W) and disp_l.dtype == torch.float32
-    Ho, Wo = interlaced.shape[0], interlaced.shape[1]
+    Ho, Wo = _out_size(interlaced, p)
     _use_current_stream()
     lib().stm_d_adcensus_stm_2s(_p(sbs), _p(disp_l), _p(disp_r), _p(interlaced), H, Wsbs, W, Ho, Wo, disp_rows, disp_cols, E,
                                 disp_scale, p.num_views, p.angle, p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff,
@@ -366,7 +411,7 @@ def d_adcensus_stm_2t(sbs, disp_l, disp_r, interlaced, p, disp_rows, disp_cols, 
     for t in (prev_disp_l, prev_disp_r):
         if t is not None:
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
-    Ho, Wo = interlaced.shape[0], interlaced.shape[1]
+    Ho, Wo = _out_size(interlaced, p)
 
     def opt(t):
         return None if t is None else _p(t)
@@ -393,7 +438,7 @@ def d_adcensus_stm_2nv12(y, uv, disp_l, disp_r, interlaced, p, disp_rows, disp_c
     for t in (prev_disp_l, prev_disp_r):
         if t is not None:
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
-    Ho, Wo = interlaced.shape[0], interlaced.shape[1]
+    Ho, Wo = _out_size(interlaced, p)
 
     def opt(t):
         return None if t is None else _p(t)

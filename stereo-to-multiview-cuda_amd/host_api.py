@@ -266,14 +266,24 @@ def quilt_multiview(views, tiles_x, tiles_y, order, filter, out_rows, out_cols):
     return out
 
 
+def _frame_out(out_rows, out_cols, E):
+    """the array a rendering frame call fills: the BGR frame, or -- under stm_set_output's format 1 -- the NV12 surface of
+    (R + out_rows / 2) x P bytes (P = pitch or out_cols, R = uv_row or out_rows)"""
+    now = (C.c_int * 4)()
+    lib().stm_get_output(now)
+    if now[0] == 0:
+        return np.zeros((out_rows, out_cols, E), np.uint8)
+    return np.zeros(((now[3] or out_rows) + out_rows // 2, now[2] or out_cols), np.uint8)
+
+
 def adcensus_stm(img_sbs, num_cols, out_rows, out_cols, num_views, angle, num_disp, zero_disp,
                  ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h):
-    """d_io.h:32-40: host SBS frame in, (disp_l, disp_r, interlaced) out."""
+    """d_io.h:32-40: host SBS frame in, (disp_l, disp_r, interlaced) out (interlaced: the frame, or the NV12 surface of _frame_out)."""
     img_sbs, ps = _u8(img_sbs)
     H, Wsbs, E = img_sbs.shape
     dl = np.zeros((H, num_cols), np.float32)
     dr = np.zeros((H, num_cols), np.float32)
-    out = np.zeros((out_rows, out_cols, E), np.uint8)
+    out = _frame_out(out_rows, out_cols, E)
     lib().stm_adcensus_stm(ps, dl.ctypes.data_as(f32p), dr.ctypes.data_as(f32p), out.ctypes.data_as(u8p),
                            H, Wsbs, num_cols, out_rows, out_cols, E, num_views, angle, num_disp, zero_disp,
                            ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h)
@@ -287,7 +297,7 @@ def adcensus_stm_2(img_sbs, num_cols, out_rows, out_cols, disp_rows, disp_cols, 
     H, Wsbs, E = img_sbs.shape
     dl = np.zeros((H, num_cols), np.float32)
     dr = np.zeros((H, num_cols), np.float32)
-    out = np.zeros((out_rows, out_cols, E), np.uint8)
+    out = _frame_out(out_rows, out_cols, E)
     lib().stm_adcensus_stm_2(ps, dl.ctypes.data_as(f32p), dr.ctypes.data_as(f32p), out.ctypes.data_as(u8p),
                              H, Wsbs, num_cols, out_rows, out_cols, disp_rows, disp_cols, E, disp_scale, num_views, angle,
                              num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h)
@@ -302,7 +312,7 @@ def adcensus_stm_2s(img_sbs, num_cols, out_rows, out_cols, disp_rows, disp_cols,
     H, Wsbs, E = img_sbs.shape
     dl = np.zeros((H, num_cols), np.float32)
     dr = np.zeros((H, num_cols), np.float32)
-    out = np.zeros((out_rows, out_cols, E), np.uint8)
+    out = _frame_out(out_rows, out_cols, E)
     lib().stm_adcensus_stm_2s(ps, dl.ctypes.data_as(f32p), dr.ctypes.data_as(f32p), out.ctypes.data_as(u8p),
                               H, Wsbs, num_cols, out_rows, out_cols, disp_rows, disp_cols, E, disp_scale, num_views, angle,
                               num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages)
@@ -397,6 +407,19 @@ def demux_nv12(y, uv, num_cols, elem_sz=3, matrix=0, num_cols_sbs=None):
     lib().stm_demux_nv12(img_l.ctypes.data_as(u8p), img_r.ctypes.data_as(u8p), y.ctypes.data_as(u8p), y.strides[0],
                          uv.ctypes.data_as(u8p), uv.strides[0], H, Wsbs, num_cols, elem_sz, int(matrix))
     return img_l, img_r
+
+
+def mux_nv12(img, matrix=0, pitch_y=None, pitch_uv=None):
+    """stm_mux_nv12: the NV12 picture (y uint8 [H][pitch_y], uv uint8 [H / 2][pitch_uv]; the samples in the first W bytes of a row, 0
+    past them) of the BGR image img uint8 [H][W][E], H and W even: 16.16 integer luma, chroma the mean of each 2 x 2 block.  matrix:
+    0 / 1 = BT.601 / BT.709 limited range, 2 / 3 = BT.601 / BT.709 full range; the pitches default to W."""
+    img, pi = _u8(img)
+    H, W, E = img.shape
+    pitch_y, pitch_uv = pitch_y or W, pitch_uv or W
+    y = np.zeros((H, max(pitch_y, 1)), np.uint8)
+    uv = np.zeros((max(H // 2, 1), max(pitch_uv, 1)), np.uint8)
+    lib().stm_mux_nv12(y.ctypes.data_as(u8p), pitch_y, uv.ctypes.data_as(u8p), pitch_uv, pi, H, W, E, int(matrix))
+    return y, uv
 
 
 def demux_packed(img, num_rows, num_cols, packing, elem_sz=None):

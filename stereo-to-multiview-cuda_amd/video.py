@@ -25,16 +25,19 @@ class FrameStream:
     top-and-bottom ones: the shape `in_shape` holds.  layout = (1, tiles_x, tiles_y, order, filter): the frames come out as a
     quilt of tiles_x x tiles_y whole views (set_layout); None = the interlaced frame.  match = (h, w, disp_scale): every frame is the
     reduced-resolution frame -- matched at h x w, the maps scaled up by 1 / disp_scale, the views rendered at full size -- and
-    `stages` may then carry 0x1000 (the guided up-sampler); None = the full-resolution frame.  Not together with a packing."""
+    `stages` may then carry 0x1000 (the guided up-sampler); None = the full-resolution frame.  Not together with a packing.
+    output = (1, matrix): the quilt comes out as NV12 (set_output), each frame uint8 [out_rows * 3 / 2][out_cols], the Y plane followed
+    by the interleaved UV plane; None = BGR.  Needs a layout."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
-                 depth=None, depth_auto=None, packing=None, layout=None, match=None):
+                 depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None):
         self.H, self.W = num_rows, num_cols
         self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
         self._nv12 = False
         self.in_shape = (self.rows_f, self.Wsbs, 3)
         self.Ho, self.Wo = out_rows or num_rows, out_cols or num_cols
+        self.out_shape = (self.Ho, self.Wo, 3)
         p = params
         self._h = lib().stm_stream_create(num_rows, self.Wsbs, num_cols, self.Ho, self.Wo, 3, p.num_views, p.angle,
                                           p.num_disp, p.zero_disp, p.ad_coeff, p.census_coeff, p.ucd, p.lcd, p.usd, p.lsd,
@@ -51,6 +54,8 @@ class FrameStream:
             self.set_lens(*lens)
         if layout is not None:
             self.set_layout(*layout)
+        if output is not None:
+            self.set_output(*output)
         if depth is not None and depth_auto is not None:
             raise ValueError("FrameStream: depth and depth_auto are mutually exclusive")
         if depth is not None:
@@ -95,6 +100,14 @@ class FrameStream:
         if int(lib().stm_stream_set_layout(self._h, int(layout), int(tiles_x), int(tiles_y), int(order), int(filter))) != 0:
             raise ValueError("stm_stream_set_layout(%d, %d, %d, %d, %d) refused: %s"
                              % (layout, tiles_x, tiles_y, order, filter, lib().stm_last_error().decode()))
+
+    def set_output(self, format=0, matrix=0):
+        """stm_stream_set_output: the format of the stream's output frames, 0 = BGR [out_rows][out_cols][3], 1 = NV12
+        [out_rows * 3 / 2][out_cols] converted by `matrix` (quilts only: set the layout first); the stream's own, independent of the
+        calling thread's; only before the first submit.  Raises ValueError where the library refuses."""
+        if int(lib().stm_stream_set_output(self._h, int(format), int(matrix))) != 0:
+            raise ValueError("stm_stream_set_output(%d, %d) refused: %s" % (format, matrix, lib().stm_last_error().decode()))
+        self.out_shape = (self.Ho * 3 // 2, self.Wo) if int(format) == 1 else (self.Ho, self.Wo, 3)
 
     def set_input(self, input_format, matrix=0):
         """stm_stream_set_input: "bgr" or "nv12" with its conversion matrix; only before the first submit.  Raises ValueError where
@@ -163,12 +176,12 @@ class FrameStream:
         if k < 0:
             return None
         return (k, np.ctypeslib.as_array(pl, shape=(self.H, self.W)), np.ctypeslib.as_array(pr, shape=(self.H, self.W)),
-                np.ctypeslib.as_array(po, shape=(self.Ho, self.Wo, 3)))
+                np.ctypeslib.as_array(po, shape=self.out_shape))
 
     def collect(self):
         dl = np.empty((self.H, self.W), np.float32)
         dr = np.empty((self.H, self.W), np.float32)
-        out = np.empty((self.Ho, self.Wo, 3), np.uint8)
+        out = np.empty(self.out_shape, np.uint8)
         k = int(lib().stm_stream_collect(self._h, dl.ctypes.data_as(f32p), dr.ctypes.data_as(f32p), out.ctypes.data_as(u8p)))
         return (k, dl, dr, out) if k >= 0 else None
 
@@ -213,7 +226,7 @@ def _collect(fs, on_depth):
 
 
 def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None,
-                     depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None):
+                     depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
@@ -221,7 +234,8 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
     pitch, slope, centre) for FrameStream.set_lens, None = the reference's interlacer; depth / depth_auto: FrameStream's depth
     budget; on_depth: called with (index, (gain, conv)) after every collected frame.  packing: FrameStream's; the frames are then packed
     ones; eye_shape = (num_rows, num_cols), the size of an unpacked eye, defaults to what a frame without spare columns holds.
-    layout: FrameStream's (the interlaced output is then a quilt).  match: FrameStream's (h, w, disp_scale): the reduced-resolution frame."""
+    layout: FrameStream's (the interlaced output is then a quilt).  match: FrameStream's (h, w, disp_scale): the reduced-resolution frame.
+    output: FrameStream's (1, matrix): the quilt comes out as NV12, [out_rows * 3 / 2][out_cols]."""
     fs = None
     pending = 0
     for sbs in frames:
@@ -230,7 +244,7 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
             cols = sbs.shape[1] // 2
             if packing is not None:
                 rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
-            fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match)
+            fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:
@@ -276,5 +290,10 @@ def normalize_minmax_u8(a):
 def write_outputs(out_dir, index, disp_l, disp_r, interlaced):
     os.makedirs(out_dir, exist_ok=True)
     bmp_io.write_bmp(os.path.join(out_dir, "interlaced_%05d.bmp" % index), interlaced)
+    write_disparities(out_dir, index, disp_l, disp_r)
+
+
+def write_disparities(out_dir, index, disp_l, disp_r):
+    os.makedirs(out_dir, exist_ok=True)
     bmp_io.write_bmp(os.path.join(out_dir, "disp_l_%05d.bmp" % index), normalize_minmax_u8(disp_l))
     bmp_io.write_bmp(os.path.join(out_dir, "disp_r_%05d.bmp" % index), normalize_minmax_u8(disp_r))

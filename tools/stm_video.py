@@ -7,7 +7,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--temporal [--temporal-alpha A] [--temporal-color C] [--temporal-disp T]]
                     [--nv12 ROWS COLS_SBS [--matrix M]] [--lens MODE PITCH SLOPE CENTRE]
                     [--depth GAIN CONV | --depth-auto LO HI [MAX_GAIN CLIP RATE]]
-                    [--packing P SWAP FILTER GAP] [--quilt TX TY ORDER FILTER] [--match H W SCALE [--guided-up]]
+                    [--packing P SWAP FILTER GAP] [--quilt TX TY ORDER FILTER [--nv12-out MATRIX]] [--match H W SCALE [--guided-up]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -32,6 +32,9 @@ kernel; combines with --nv12, whose ROWS and COLS_SBS are then the packed frame'
 --quilt TX TY ORDER FILTER (an addition): the output frame is a quilt (stm_set_layout) -- the <num views> = TX * TY views whole, as
 TX x TY tiles, instead of interlaced; ORDER bit 0 = tile rows bottom-up, bit 1 = tile 0 holds the leftmost camera (3 = the Looking
 Glass convention); FILTER 0 = the reference's four-neighbour sampler, 1 = the area average.  <angle> is then ignored; excludes --lens.
+--nv12-out MATRIX (an addition; needs --quilt): the quilt leaves the GPU as NV12 (stm_set_output), what a video encoder takes --
+converted by MATRIX (as --matrix) inside the kernel that renders it -- and every frame is appended, raw, to <out dir>/quilt.yuv (a
+file from an earlier run is replaced) instead of being written as a BMP; <out width> and <out height> and the tiles must be even.
 --match H W SCALE (an addition): every frame is the reduced-resolution frame (stm_stream_set_match_size) -- the pair is matched at
 H x W, the maps are scaled up by 1 / SCALE and the views rendered at full size; <num disp> and <zero disp> then count pixels of the
 reduced pair.  --guided-up adds frame bit 0x1000, the guided up-sampler in place of the bilinear up-scale.  Excludes --packing.
@@ -93,6 +96,17 @@ def main(argv):
             print(__doc__)
             return -1
         del argv[at:at + 5]
+    nv12_out = None
+    if "--nv12-out" in argv:
+        at = argv.index("--nv12-out")
+        try:
+            nv12_out = int(argv[at + 1])
+        except (ValueError, IndexError):
+            nv12_out = -1
+        if quilt is None or not 0 <= nv12_out <= 3:
+            print(__doc__)
+            return -1
+        del argv[at:at + 2]
     packing = None
     if "--packing" in argv:
         at = argv.index("--packing")
@@ -164,15 +178,26 @@ def main(argv):
     out_w, out_h = int(a[3]), int(a[4])
     out_dir = a[15] if len(a) > 15 else os.path.join(a[0] if nv12 is None else os.path.dirname(os.path.abspath(a[0])), "out")
     frames = video.read_bmp_sequence(a[0]) if nv12 is None else video.read_nv12_sequence(a[0], *nv12)
+    yuv = None
+    if nv12_out is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        yuv = open(os.path.join(out_dir, "quilt.yuv"), "wb")
     t0 = time.perf_counter()
     n = 0
     for (k, dl, dr, inter) in video.process_sequence(frames, p, out_h, out_w, stages, tuple(temporal) if stages & 0x2000 else None,
                                                        "bgr" if nv12 is None else "nv12", matrix, lens, depth, depth_auto,
                                                        (lambda k, gc: print("frame %d: gain %.6g conv %.6g" % (k, gc[0], gc[1])))
                                                        if depth_auto is not None else None, packing,
-                                                       layout=None if quilt is None else (1,) + quilt, match=match):
-        video.write_outputs(out_dir, k, dl, dr, inter)
+                                                       layout=None if quilt is None else (1,) + quilt, match=match,
+                                                       output=None if nv12_out is None else (1, nv12_out)):
+        if yuv is not None:  # the frame is [out height * 3 / 2][out width]: the Y plane, then the interleaved UV plane
+            yuv.write(inter.tobytes())
+            video.write_disparities(out_dir, k, dl, dr)
+        else:
+            video.write_outputs(out_dir, k, dl, dr, inter)
         n += 1
+    if yuv is not None:
+        yuv.close()
     dt = time.perf_counter() - t0
     print("%d frames in %.3f s (%.1f frames/s including BMP I/O)" % (n, dt, n / dt if dt > 0 else 0.0))
     return 0
