@@ -74,7 +74,8 @@ int         stm_prof_read(const char *kernel, float *total_ms);
 /* aggregation variant of the frame pipeline (0 = default: matrix-pipe kernels, stm_kernels_aggm.hip); decimal digits, used by
  * the benchmark and the tools to A/B result-preserving variants in one process: 10000 = vector-ALU aggregation kernels
  * (stm_kernels_agg.hip; the low digits then select their tunables), 1000000 = separate initial-cost kernel instead of
- * computing the costs inside the first pass, 1000 / 2000 = the cost-computing pass as one block per segment (128- / 192-pixel
+ * computing the costs inside the first pass, 2000000 = the cost-computing first pass with one view per block (stm_k_pq_hc) where
+ * the default sweeps both views of a row part from one ring of costs (stm_k_pq_hc2; stm_first_pass_path), 1000 / 2000 = the cost-computing pass as one block per segment (128- / 192-pixel
  * segments) instead of the row walk, 10 = the volume-reading horizontal passes as one block per segment instead of the row walk
  * (20: only for num_disp > 64), 200 = view synthesis and interlacing as two kernels, 300 = region voting over the raster-ordered outlier list of round 3
  * instead of over column runs, 400 = the two horizontal scanline-optimisation passes as two launches instead of one walk from both
@@ -105,8 +106,16 @@ void        stm_set_agg_variant(int v);
  *   bits 8..15   waves per block of the cost-fusing streaming first pass stm_k_pq_hc: 12 (192-pixel segments), 8 (128-pixel
  *                segments), or 0 when another kernel runs the first pass
  *   bit 16       that pass splits an image row over more than one block
+ * Bits 8..16 describe the plan of stm_k_pq_hc: what runs under stm_set_agg_variant(2000000), and the plan that stm_k_pq_hc2
+ * replaces where stm_first_pass_path is not 0 (the other bits hold for both).
  * An addition: the reference has one aggregation path and no such query. */
 int         stm_agg_path(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages);
+/* Whether such a frame call runs its first horizontal pass on stm_k_pq_hc2 -- one block sweeps a part of an image row for BOTH views
+ * from one ring of initial costs, each cost evaluated once -- under the current stm_set_agg_variant: the blocks (parts) per image
+ * row of that kernel, or 0 when stm_k_pq_hc or another kernel runs the pass.  It runs where stm_agg_path reports bit 1 and 12 waves,
+ * 0 <= zero_disp < num_disp, and not under variant 2000000.  Host arithmetic only, from the dispatcher's own functions, like
+ * stm_agg_path.  An addition. */
+int         stm_first_pass_path(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages);
 /* dr_irv / d_dr_irv / the frame calls: 0 (default) = the reference's accept rule, (winning bin index + zero_disp) / S > thresh_h
  * (d_dr_irv.cu:36 -- the bin INDEX, SURVEY A-Q17 iv); 1 = the paper's rule, (winning bin's COUNT) / S > thresh_h (Mei et al.,
  * region voting).  An addition: the reference has no such switch. */

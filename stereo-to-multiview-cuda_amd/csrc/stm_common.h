@@ -382,6 +382,8 @@ size_t aggm_frame_vtab_dwords(int D, int zd, int H, int W, int usd, bool keep_vo
 bool aggm_frame_px(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later);
 // what launch_aggm_frame runs for these arguments, as the bits 1 .. 16 of stm_agg_path (include/stm_hip.h); launches nothing
 int aggm_frame_path(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later);
+// the blocks per image row of stm_k_pq_hc2 (first pass, both views from one ring of costs) where launch_aggm_frame runs it, else 0
+int aggm_frame_hc2_parts(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later);
 // ca_cross / d_ca_cross of one volume in the caller's layout on the matrix-pipe kernels; `out` may be `in`.  Returns false, with
 // `out` untouched, when the volume holds an infinite, NaN or denormal element (one host read-back of a flag): the caller runs
 // the vector-ALU kernels instead.  aggm_stage_bytes: what it carves from the current Workspace scope.

@@ -813,6 +813,217 @@ __global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void stm_k_pq_hc(PQViews v, 
 #undef STM_HC_SN
 }
 
+// ------------------------------------------------------------------ the same pass, both views swept from ONE ring of costs
+// The right view's initial cost is the left view's at a sheared position.  With s = d - zd and both clamps to [0, W - 1],
+//   T(xl, d) = rho_ad(|L(clamp(xl)) - R(clamp(xl + s))|_1) + rho_c(ham(cenL(clamp(xl)), cenR(clamp(xl + s))))
+// is C_L(d, x) at xl = x and C_R(d, x) at xl = x - s for EVERY x of the row: where x - s leaves the row the reference clamps the
+// left index, which is T's first clamp (the SAD, the Hamming distance and the add's operand order are the same in both views).
+// stm_k_pq_hc evaluates every (x, d) once per view, in two blocks; here one block of 12 waves serves 96-pixel segments of both
+// views -- waves 0..5 the left view's six tiles, waves 6..11 the right view's -- from one ring of T, so each cost is evaluated once.
+// Ring: pixel-major, float index (xl mod 256) 64 + d, 64 KB at the start of the LDS, its first 3 pixels repeated behind its end
+// so that a group of four pixels never straddles the wrap.  Lane d of a sweep reads the group at pixel position p from byte
+// ((p - shear) mod 256) 256 + 4 d, shear = 0 (left) or d - zd (right): the shear moves a lane by multiples of 256 bytes, so the
+// 64 lanes of a read stay on 64 different banks, and one 16-bit add per group steps and wraps the address.
+// A segment at X0 reads [X0 - 40 - (D - 1 - zd), X0 + 136 + zd): 175 + D <= 256 positions (usd <= 36: halo of 40 on the left, 36 + a
+// group of read-ahead on the right).  Per segment the 12 waves evaluate the 96 new positions [X0 + 136 + zd, + 96) of the next
+// segment, 8 per wave with lane = hypothesis (ring writes of 64 consecutive dwords); a block's first segment fills all 256.
+// No pixel is zeroed: positions outside a window carry A = 0 in the MFMA and every T is finite.  Hypotheses d >= D are 0, and the
+// right view's lanes d >= D read with the shear of D - 1, inside what the ring holds.  Everything else is stm_k_pq_hc<12, true>'s:
+// barriers, pixel staging two segments ahead, the sweep, the PX stores.  48 < D <= 64, 0 <= zd < D, usd <= 36 (hc2_parts).
+constexpr int HC2_TX = 96, HC2_SR = HC2_TX + 64, HC2_HALO = 40, HC2_RING = 256, HC2_FRONT = HC2_TX + HC2_HALO;
+typedef const float __attribute__((address_space(3))) *hc2_lds_cf;
+constexpr size_t HC2_SMEM =(size_t)(HC2_RING + 3) * 256 + 2 * HC2_TX * 4 + 12 * 8 + (size_t)(2 * HC2_TX + 2 * HC2_SR) * 8 + (768 + 72) * 4;
+__global__ __launch_bounds__(768, 6) void stm_k_pq_hc2(PQViews v, int D, int zd, int H, int W, int G, int nseg, int spl,
+                                                       const float *__restrict__ lut_g, int dbg)
+{
+    constexpr int NW = 12, NT = 64 * NW, TX = HC2_TX, SR = HC2_SR;
+    extern __shared__ f4 lds4[];
+    float *ring = (float *)lds4; // [256 + 3 positions][64 hypotheses]
+    uint32_t *sn = (uint32_t *)(ring + (HC2_RING + 3) * 64); // [2 views][TX]: window start relative to the segment's origin | length << 16
+    int2 *sg = (int2 *)(sn + 2 * TX); // per wave: first group and length of its sweep
+    uint2 *s_l = (uint2 *)(sg + NW), *s_r = s_l + 2 * TX; // two buffers each: [2][TX] left pixels, [2][SR] right pixels
+    float *s_lut_ad = (float *)(s_r + 2 * SR), *s_lut_c = s_lut_ad + 768;
+    const int tid = threadIdx.x, l = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lb = l >> 4, dd = l & 15;
+    const int part = blockIdx.x % spl, y = blockIdx.x / spl;
+    const int seg_per = (nseg + spl - 1) / spl, seg0 = part * seg_per, seg1 = min(nseg, seg0 + seg_per);
+    if (seg0 >= seg1) return;
+    const int view = w >= NW / 2, wt = view ? w - NW / 2 : w; // uniform per wave: the view it sweeps, its tile of the segment
+    f4 *__restrict__ out = (f4 *)(view ? v.b[1] : v.b[0]);
+    const uint32_t *__restrict__ pk_l = v.pk[0], *__restrict__ pk_r = v.pk[1], *__restrict__ cen_l = v.cen[0], *__restrict__ cen_r = v.cen[1];
+    // threads 0 .. 2 TX - 1 keep the windows: view tid / TX, pixel tid % TX of the segment
+    const int aview = tid >= TX, apx = aview ? tid - TX : tid;
+    const u8 *__restrict__ armL = aview ? v.armL[1] : v.armL[0], *__restrict__ armR = aview ? v.armR[1] : v.armR[0];
+    const size_t row = (size_t)y * W;
+    const uint32_t rowbytes = (uint32_t)G * 256u;
+    for (int i = tid; i < 768 + 65; i += NT) s_lut_ad[i] = lut_g[i];
+    uint2 sl = make_uint2(0, 0), sr = make_uint2(0, 0);
+    int aLn = 0, aRn = 0;
+    float cst[8];
+    // the row's 4 G pixels of 256 bytes (pixels past them are out of range, dropped)
+    const __amdgpu_buffer_rsrc_t rpx = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (size_t)y * G * 64), 0, 4u * rowbytes, 0x00020000);
+    // pixels for the TX ring positions from P0: left image P0 .., right image P0 - zd .. P0 + TX + 63 - zd, clamped to the row
+#define STM_HC2_FETCH(P0)                                                                          \
+    {                                                                                              \
+        if (tid < TX) {                                                                            \
+            const int gx = min(max((P0) + tid, 0), W - 1);                                         \
+            sl = make_uint2(pk_l[row + gx], cen_l[row + gx]);                                      \
+        }                                                                                          \
+        if (tid < SR) {                                                                            \
+            const int gx = min(max((P0) - zd + tid, 0), W - 1);                                    \
+            sr = make_uint2(pk_r[row + gx], cen_r[row + gx]);                                      \
+        }                                                                                          \
+    }
+#define STM_HC2_STAGE(B)                                           \
+    {                                                              \
+        if (tid < TX) s_l[(B) * TX + tid] = sl;                    \
+        if (tid < SR) s_r[(B) * SR + tid] = sr;                    \
+    }
+    // T of the staged positions 8 w .. 8 w + 7, lane = hypothesis: the left pixel is the wave's, the right pixels are 64 in a row
+#define STM_HC2_COSTS(B)                                                                                                  \
+    {                                                                                                                     \
+        const uint2 *lp = s_l + (B) * TX + 8 * w, *rp = s_r + (B) * SR + 8 * w + l;                                       \
+        _Pragma("unroll") for (int k = 0; k < 8; ++k) {                                                                   \
+            const uint2 o = lp[k], q = rp[k];                                                                             \
+            const float a = s_lut_ad[__builtin_amdgcn_sad_u8(o.x, q.x, 0u)], c = s_lut_c[hamdist_q1(o.y, q.y)];           \
+            cst[k] = l < D ? a + c : 0.f;                                                                                 \
+        }                                                                                                                 \
+    }
+    // ... into the ring at positions P0 + 8 w ..; positions 0 .. 2 (mod 256) also behind the ring's end
+#define STM_HC2_WRITE(P0)                                                              \
+    _Pragma("unroll") for (int k = 0; k < 8; ++k) {                                    \
+        const int rp_ = ((P0) + 8 * w + k) & (HC2_RING - 1); /* uniform */             \
+        ring[rp_ * 64 + l] = cst[k];                                                   \
+        if (rp_ < 3) ring[(HC2_RING + rp_) * 64 + l] = cst[k];                         \
+    }
+#define STM_HC2_ARMS(S)                                                         \
+    if (tid < 2 * TX) {                                                         \
+        const int x = min((S) * TX + apx, W - 1);                               \
+        aLn = armL[row + x];                                                    \
+        aRn = armR[row + x];                                                    \
+    }
+#define STM_HC2_SN(S)                                                                                                      \
+    if (tid < 2 * TX) {                                                                                                    \
+        const int x = (S) * TX + apx, org = (S) * TX - HC2_HALO;                                                           \
+        /* window [x - armL, x + armR) relative to the segment's origin (d_ca_cross_sum.cu:277-289); past the row: empty */ \
+        const int srel_ = x < W ? x - aLn - org : x - org, nn_ = x < W ? aLn + aRn : 0;                                    \
+        sn[tid] = (uint32_t)srel_ | ((uint32_t)nn_ << 16);                                                                 \
+        /* the sweep of the wave that owns these 16 pixels (a DPP row): first group, number of groups */                   \
+        int lo_ = nn_ ? (srel_ >> 2) : 0x7fffffff, hi_ = nn_ ? ((srel_ + nn_ + 3) >> 2) : -0x7fffffff;                     \
+        lo_ = min(lo_, row_ror_i<8>(lo_)); lo_ = min(lo_, row_ror_i<4>(lo_)); lo_ = min(lo_, row_ror_i<2>(lo_)); lo_ = min(lo_, row_ror_i<1>(lo_)); \
+        hi_ = max(hi_, row_ror_i<8>(hi_)); hi_ = max(hi_, row_ror_i<4>(hi_)); hi_ = max(hi_, row_ror_i<2>(hi_)); hi_ = max(hi_, row_ror_i<1>(hi_)); \
+        if ((tid & 15) == 0) sg[tid >> 4] = make_int2(lo_, hi_ - lo_);                                                     \
+    }
+    // first segment: the whole ring, the 256 positions that end at the segment's front, in rounds of TX
+    const int front0 = TX * seg0 + HC2_FRONT + zd;
+    for (int r0 = 0; r0 < HC2_RING; r0 += TX) {
+        const int p0 = front0 - HC2_RING + r0;
+        STM_HC2_FETCH(p0)
+        __syncthreads(); // the previous round's readers are done with buffer 0 (first round: the tables are being written)
+        STM_HC2_STAGE(0)
+        __syncthreads();
+        if (r0 + 8 * w < HC2_RING) { // uniform
+            STM_HC2_COSTS(0)
+            STM_HC2_WRITE(p0)
+        }
+    }
+    __syncthreads();
+    // staging of segment seg0 + 1's new positions into buffer (seg0 + 1) & 1, arms of seg0
+    {
+        STM_HC2_FETCH(front0)
+        STM_HC2_STAGE((seg0 + 1) & 1)
+        STM_HC2_ARMS(seg0)
+        STM_HC2_SN(seg0)
+    }
+    __syncthreads();
+    const int shear = view ? min(l, D - 1) - zd : 0;
+    for (int sq = seg0; sq < seg1; ++sq) {
+        const int X0 = sq * TX + 16 * wt;
+        const int front = TX * sq + HC2_FRONT + zd; // the ring holds the positions below it
+        const bool more = sq + 1 < seg1;
+        // pixels for the new positions of segment sq + 2 (consumed after the next segment's sweep), arms of segment sq + 1
+        if (more) {
+            STM_HC2_FETCH(front + TX)
+            STM_HC2_ARMS(sq + 1)
+        }
+        if (X0 < W) { // uniform per wave
+            const uint32_t e = sn[16 * w + dd]; // mask lanes: pixel dd of the wave's tile
+            const int srel = (int)(e & 0xffffu), nn = (int)(e >> 16);
+            const int2 sgw = sg[w]; // first group of the wave's sweep, its length in groups (STM_HC2_SN)
+            const int G0r = __builtin_amdgcn_readfirstlane(sgw.x);
+            const int n_it = STM_DBG(dbg, 1) ? 0 : __builtin_amdgcn_readfirstlane(sgw.y); // <= 0 when every window of the wave is empty
+            f16v acc;
+            if (n_it > 0) {
+                // the lane's byte address in the ring, which starts at LDS address 0 (the kernel has no static LDS, so its dynamic
+                // LDS starts there): the 16-bit add of a step wraps it at the ring's 64 KB
+                // (v_add_u16 clears the upper half of its result on gfx9; the compiler widens a 16-bit C++ add to an add and a mask)
+                uint32_t a = ((((unsigned)(sq * TX - HC2_HALO + 4 * G0r - shear) << 8) + 4u * l) & 0xffffu);
+                int t = 4 * G0r + lb - srel;
+                // two register sets: the LDS read of a group is issued before the MFMAs of the group in front of it
+#define STM_HS_NEXT(C)                                                        \
+    {                                                                         \
+        const hc2_lds_cf r_ = (hc2_lds_cf)(size_t)a;                          \
+        C.x = r_[0]; C.y = r_[64]; C.z = r_[128]; C.w = r_[192];              \
+        asm("v_add_u16_e32 %0, 0x400, %1" : "=v"(a) : "v"(a));                \
+    }
+#define STM_HS_MFMA(C)                                                          \
+    {                                                                           \
+        const float m = ((unsigned)t < (unsigned)nn) ? 1.0f : 0.0f;             \
+        t += 4;                                                                 \
+        acc = STM_MFMA16(m, C.x, acc, 0);                                       \
+        acc = STM_MFMA16(m, C.y, acc, 1);                                       \
+        acc = STM_MFMA16(m, C.z, acc, 2);                                       \
+        acc = STM_MFMA16(m, C.w, acc, 3);                                       \
+    }
+                f4 ca, cb;
+                STM_HS_NEXT(ca)
+                STM_HS_NEXT(cb) // a sweep of one group: one group past it (inside the ring, unused)
+                {   // the first MFMA takes the constant 0 as its accumulator input: no register is cleared
+                    const float m = ((unsigned)t < (unsigned)nn) ? 1.0f : 0.0f;
+                    t += 4;
+                    const f16v z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                    acc = STM_MFMA16(m, ca.x, z, 0);
+                    acc = STM_MFMA16(m, ca.y, acc, 1);
+                    acc = STM_MFMA16(m, ca.z, acc, 2);
+                    acc = STM_MFMA16(m, ca.w, acc, 3);
+                }
+                int it = 1;
+                for (; it + 2 <= n_it; it += 2) {
+                    STM_HS_NEXT(ca)
+                    STM_HS_MFMA(cb)
+                    STM_HS_NEXT(cb) // on the last trip one group past the sweep: inside the ring, unused
+                    STM_HS_MFMA(ca)
+                }
+                if (it < n_it) STM_HS_MFMA(cb)
+#undef STM_HS_NEXT
+#undef STM_HS_MFMA
+            } else {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+            }
+#pragma unroll
+            for (int k = 0; k < 16; ++k) // register 4 b + i of lane 16 q + n = pixel X0 + 4 q + i, hypothesis 16 b + n
+                if (!STM_DBG(dbg, 4))
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, (float)acc[k]), rpx,
+                                                          (X0 + 4 * lb + (k & 3)) * 256 + (16 * (k >> 2) + dd) * 4, 0, 2);
+        }
+        if (more) STM_HC2_COSTS((sq + 1) & 1)
+        __syncthreads(); // every wave is done reading the ring and the staging buffers
+        if (more) {
+            STM_HC2_WRITE(front) // the new positions replace the TX oldest
+            STM_HC2_STAGE(sq & 1) // = (sq + 2) & 1
+            STM_HC2_SN(sq + 1)
+        }
+        __syncthreads();
+    }
+#undef STM_HC2_FETCH
+#undef STM_HC2_STAGE
+#undef STM_HC2_COSTS
+#undef STM_HC2_WRITE
+#undef STM_HC2_ARMS
+#undef STM_HC2_SN
+}
+
 // ------------------------------------------------------------------ both vertical passes, fused, table-driven
 // One block = one strip of 4 columns (one group) x one chunk of 16 hypotheses, 2 NTP waves: waves 0..NTP-1 run the first
 // vertical pass, 16 output rows each per step, from LDS ring 1 (rows of the input volume) into LDS ring 2; waves NTP..2NTP-1
@@ -1168,13 +1379,31 @@ bool aggm_frame_px(int D, int zd, int H, int W, int usd, bool keep_volume, bool 
     return !v2_read_later && chain_px(true, !keep_volume, D, zd, usd);
 }
 
-// Which kernels a chain runs, decided in one place for aggm_chain and for the query aggm_frame_path (usd <= 255)
+// Blocks per image row of stm_k_pq_hc2 (one block = a part of a row, both views), or 0 where stm_k_pq_hc runs the first pass: the
+// new kernel takes exactly the frames stm_k_pq_hc<12, true> took (px: aggm_frame_px), whose geometry its ring of 256 positions
+// holds: a halo of at most 40 (usd <= 36), 0 <= zd < D <= 64.  2000000: stm_k_pq_hc, one view per block, as before.
+// Parts: a block of both views runs twice as long as one of stm_k_pq_hc, so one block per row would halve the block count and
+// leave the chip's last round of resident blocks (two per CU) emptier; a row is split so that the count stays what it was,
+// 2 row_split blocks per row.  A part pays a ring fill of 256 positions before its first sweep, so rows shorter than eight
+// segments stay whole, and so do frames of so many rows that the last round is an eighth of the work or less.
+constexpr int HC2_SLOTS = 2 * 256; // resident blocks of the chip: two on each of MI355X's 256 CUs
+static int hc2_parts(bool px, int D, int zd, int H, int W, int usd)
+{
+    const int HG = ((usd + 3) / 4 + 2) & ~1;
+    if (!px || (agg_variant() / 1000000) % 10 == 2 || hc_waves(D, zd, usd) != 12) return 0;
+    if (zd < 0 || zd >= D || D > 64 || 4 * HG > HC2_HALO) return 0;
+    if (cdiv(W, HC2_TX) < 8 || H >= 8 * HC2_SLOTS) return 1;
+    return 2 * row_split(cdiv(W, 2 * HC2_TX));
+}
+
+// Which kernels a chain runs, decided in one place for aggm_chain and for the queries aggm_frame_path and aggm_frame_hc2_parts (usd <= 255)
 struct ChainPlan {
     bool regs, hregs;    // chain_vregs, chain_hregs
     int hcw;             // hc_waves of a chain that computes its costs in the first pass, else 0
     int hc_nseg, hc_spl; // stm_k_pq_hc's segments per image row, and its blocks per image row
+    int hc2_spl;         // hc2_parts: > 0 when stm_k_pq_hc2 runs the first pass in place of stm_k_pq_hc
 };
-static ChainPlan chain_plan(bool from_costs, bool wta, int D, int zd, int W, int usd)
+static ChainPlan chain_plan(bool from_costs, bool wta, int D, int zd, int H, int W, int usd, bool px)
 {
     ChainPlan c;
     c.regs = chain_vregs(usd);
@@ -1183,15 +1412,23 @@ static ChainPlan chain_plan(bool from_costs, bool wta, int D, int zd, int W, int
     c.hcw = fuse_cost ? hc_waves(D, zd, usd) : 0;
     c.hc_nseg = c.hcw ? cdiv(W, 16 * c.hcw) : 0;
     c.hc_spl = row_split(c.hc_nseg);
+    c.hc2_spl = fuse_cost && c.hcw ? hc2_parts(px, D, zd, H, W, usd) : 0;
     return c;
 }
 // the bits 1 .. 16 of stm_agg_path (include/stm_hip.h) for launch_aggm_frame with these arguments
 int aggm_frame_path(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later)
 {
     if (usd > 255) usd = 255;
-    const ChainPlan c = chain_plan(true, !keep_volume, D, zd, W, usd);
+    const ChainPlan c = chain_plan(true, !keep_volume, D, zd, H, W, usd, false); // stm_k_pq_hc's plan, also where stm_k_pq_hc2 runs in its place
     return (aggm_frame_px(D, zd, H, W, usd, keep_volume, v2_read_later) ? 2 : 0) | (c.regs ? 4 : 0) | (c.hregs ? 8 : 0) | (c.hcw << 8) |
            (c.hc_spl > 1 ? 1 << 16 : 0);
+}
+
+// stm_first_pass_path (include/stm_hip.h): the parts per row of stm_k_pq_hc2 where launch_aggm_frame runs it, else 0
+int aggm_frame_hc2_parts(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later)
+{
+    if (usd > 255) usd = 255;
+    return chain_plan(true, !keep_volume, D, zd, H, W, usd, aggm_frame_px(D, zd, H, W, usd, keep_volume, v2_read_later)).hc2_spl;
 }
 
 // The aggregation chain on PQ volumes for `nviews` views (1 or 2).
@@ -1213,7 +1450,7 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
     const size_t smem_cost = smem_h + (size_t)(4 * NG * 4 + 4 * pad + 768 + 72) * 4;
     const bool fuse_cost = from_costs && (agg_variant() / 1000000) % 10 != 1; // 1: separate stm_k_pq_cost + volume-reading first pass
     const int spl = row_split(nseg); // blocks per image row of the streaming passes
-    const ChainPlan plan = chain_plan(from_costs, wta, D, zd, W, usd);
+    const ChainPlan plan = chain_plan(from_costs, wta, D, zd, H, W, usd, px && nviews == 2);
     const bool streaming = NG / 4 >= NW && (agg_variant() / 10) % 10 != 1 && (NC <= 4 || (agg_variant() / 10) % 10 != 2); // the ring is at least one segment long; 20: D > 64 on the block-per-segment kernels as before
     // The window tables of the vertical passes and of the last horizontal pass depend on the arms only; they are built once
     // per call for all views (the horizontal one already by stm_k_cross_arms when the caller passes htab_ready)
@@ -1260,7 +1497,11 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
         allow_lds_m((const void *)stm_k_pq_hc<NWX, PXS>, SMEM);                                                                            \
         STM_LAUNCH((stm_k_pq_hc<NWX, PXS>), GRID, dim3(64 * NWX), SMEM, stream(), v, D, zd, H, W, G, NC, HG, NSEG, SPL, lut, pad, dbgh);    \
     }
-        if (hcw == NWC) {
+        if (plan.hc2_spl) {
+            // both views of a row part per block, every cost evaluated once
+            allow_lds_m((const void *)stm_k_pq_hc2, HC2_SMEM);
+            STM_LAUNCH(stm_k_pq_hc2, dim3(H * plan.hc2_spl), dim3(768), HC2_SMEM, stream(), v, D, zd, H, W, G, cdiv(W, HC2_TX), plan.hc2_spl, lut, dbgh);
+        } else if (hcw == NWC) {
             // streaming row walk (the staged pixels fit one per thread); 2000: one block per segment as in round 2
             const dim3 grid(nviews * H * plan.hc_spl);
             if (px) STM_HC_LAUNCH(NWC, true, grid, smem_hc, plan.hc_nseg, plan.hc_spl)

@@ -58,6 +58,13 @@ def agg_path_waves(path):
     return (int(path) >> 8) & 0xff
 
 
+def first_pass_path(num_disp, zero_disp, num_rows, num_cols, usd, stages=3):
+    """stm_first_pass_path: 0 when stm_k_pq_hc (or another kernel) runs the first horizontal pass of such a frame call under the
+    current stm_set_agg_variant, else the blocks per image row of stm_k_pq_hc2, which sweeps both views from one ring of costs.
+    Host arithmetic only: it launches nothing and needs no GPU."""
+    return int(lib().stm_first_pass_path(int(num_disp), int(zero_disp), int(num_rows), int(num_cols), int(usd), int(stages)))
+
+
 # stm_irv_path's bit field
 IRV_PRUNE, IRV_RUNS, IRV_CHAIN = 1, 2, 4
 
