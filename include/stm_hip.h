@@ -235,6 +235,24 @@ int         stm_set_output(int format, int matrix, int pitch, int uv_row);
 /* out[0 .. 3] = the calling thread's format, matrix, pitch and uv_row as the last accepted stm_set_output left them ((0, 0, 0, 0) if
  * none was made, and after format 0).  A frame stream's own format is not visible here except during its submit. */
 void        stm_get_output(int out[4]);
+/* The calling thread's overlay (an addition; stm_mux_overlay has the definition): subtitles, a logo or a player's OSD composited
+ * into every finished frame at a chosen depth.  mode 0 = off (the default; the other arguments are ignored, and not one launch,
+ * argument or kernel of any frame call changes), 1 = on: every frame call that renders -- stm_adcensus_stm, stm_d_adcensus_stm, _t,
+ * _nv12, and _2 / _2s / _2t / _2nv12 in both flavours where they exist -- composites the overlay as its LAST launch, exactly as
+ * stm_d_mux_overlay would on the frame it wrote, under the thread's lens (stm_set_lens) and layout (stm_set_layout), with the call's
+ * num_views, angle, num_rows_out, num_cols_out and elem_sz.  d_overlay is DEVICE memory in both flavours, ov_rows x ov_cols x 4 bytes,
+ * which the caller owns and keeps alive and unchanged while the setting is on, as d_state of stm_set_depth_auto.
+ * It is an output addition, not a stage: no `stages` bit belongs to it, a frame call whose `stages` low byte is below 3 renders
+ * nothing and ignores it, and the disparity maps never change.
+ * Errors of a frame call under mode 1, through stm_last_error before anything is launched or written: the thread's output format is 1
+ * (NV12) -- compositing on a chroma-subsampled surface needs a definition of its own, which is out of scope; format 1 with an
+ * overlay is refused whichever of the two was set first.
+ * Argument rules: mode 0 or 1; with mode 1 stm_mux_overlay's rules for the overlay's own arguments (a non-null, 4-byte aligned
+ * pointer, the sizes, the position, the disparity).  Returns 0, or -1 with stm_last_error set and the thread's setting unchanged. */
+int         stm_set_overlay(int mode, const unsigned char *d_overlay, int ov_rows, int ov_cols, int x0, int y0, float disparity);
+/* out[0 .. 4] = the calling thread's mode, ov_rows, ov_cols, x0 and y0, *disparity its disparity, as the last accepted
+ * stm_set_overlay left them ((0, 0, 0, 0, 0) and 0 if none was made, and after mode 0).  A frame stream's overlay is never visible here. */
+void        stm_get_overlay(int out[5], float *disparity);
 /* (tests, tools) the bytes of LDS a workgroup of the area filter's staged kernel may take: the block of output pixels it owns is sized
  * so that its footprint's staging fits, and where not even one output pixel's does the per-pixel form runs -- same arithmetic, same
  * bytes.  <= 0: the default, 32768 (five workgroups on a CU); at most 65536.  Process-wide, like stm_set_agg_variant. */
@@ -500,6 +518,67 @@ void stm_quilt_multiview(unsigned char **views, unsigned char *out_data, int num
                          int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz);
 void stm_d_quilt_multiview(unsigned char **d_views, unsigned char *d_out_data, int num_views, int tiles_x, int tiles_y, int order, int filter,
                            int in_rows, int in_cols, int out_rows, int out_cols, int elem_sz);
+/* An overlay composited into a finished frame at a chosen depth (an addition: the reference has nowhere to put subtitles, a logo or
+ * a player's OSD; painted on the finished frame they are pinned to the screen plane, and on a quilt they would have to be drawn once
+ * per tile with offsets derived from this library's internals).  The overlay is a small image in VIEW PIXEL SPACE:
+ *   overlay    ov_rows x ov_cols pixels of 4 bytes B, G, R, A with PREMULTIPLIED alpha (colour <= alpha expected), dense, read only;
+ *              O[r][q] is its pixel at row r, column q
+ *   x0, y0     the view pixel its top-left corner sits at (either may be negative or beyond the view: the overlay is clipped)
+ *   disparity  one end-to-end disparity in the maps' sign convention (x_right - x_left): > 0 behind the screen, < 0 in front, 0 on it
+ * View pixel space, Hv x Wv:
+ *   layout 0          the output frame, out_rows x out_cols
+ *   layout 1 (quilt)  one tile, th x tw (stm_quilt_multiview's geometry); the overlay is composited into every tile, clipped to that
+ *                     tile; the remainder pixels that belong to no tile are never touched
+ * The overlay is drawn at the output's own resolution (text stays as sharp as the panel); it is not resampled vertically.
+ * Take view pixel (x, y) and byte c (0 .. 2) of that pixel; in a quilt (x, y) = (u, w) inside the tile of view v, at output pixel
+ * (left + u, top + w); in layout 0 the output pixel is (x, y) itself.  N = num_views.
+ * 1. The sub-pixel's shift s, the camera position it shows (1 = the right image, 0 = the left image):
+ *   layout 0, lens mode 0   v = the view the frame's interlacer shows there: mux_multiview_kernel_2's b_view, g_view, r_view for c = 0,
+ *                           1, 2 (d_mux_multiview.cu:60-73, the form that multiplies by 1 / y_interval, which the frame calls use), from
+ *                           `angle`;  s = (float)(1.0 - (double)(float)v / ((double)(float)N - 1.0))            (d_io.cu:189)
+ *   lens mode 1             v by stm_mux_multiview_lens's mode 1 lines at output pixel (x, y), byte c; then the same s
+ *   lens modes 2 and 3      mode 3's shift at output pixel (x, y), byte c: g after the clamp, u = g / (double)(N - 1), s = (float)(1.0 - u).
+ *                           The overlay is drawn at the sub-pixel's own continuous position, in mode 2 as well
+ *   layout 1                v = the tile's view; then the same s as for a discrete view
+ *   The depth budget (stm_set_depth) does not enter: `disparity` is end-to-end.  A caller who wants it relative to the scene reads
+ *   stm_stream_depth.
+ * 2. The position.  double, one operation per line, no contraction:
+ *   t  = (double)s - 0.5
+ *   o  = (double)disparity * t
+ *   p  = (double)(x - x0) - o                  (x - x0 in 64-bit integers)
+ *   p  = p * 256.0
+ *   F  = (long long)floor(p)
+ *   q  = F >> 8 (arithmetic);  fr = F & 255
+ *   r  = y - y0;  r outside [0, ov_rows): the sub-pixel is unchanged
+ *   So overlay pixel q' appears at x0 + q' + (s - 0.5) * disparity.
+ * 3. The sample.  P0 = O[r][q], P1 = O[r][q + 1]; a column outside [0, ov_cols) reads as (0, 0, 0, 0).  For byte j of the overlay pixel
+ *   I_j = (256 - fr) * P0_j + fr * P1_j                                                        (0 .. 65280)
+ * 4. The blend.  Unsigned 32-bit integers, `/` the integer division; the numerator stays below 2^26:
+ *   out = min(255, (255 * I_c + (65280 - I_3) * dst + 32640) / 65280)
+ *   I_c = I_3 = 0 leaves dst exactly; full alpha (I_3 = 65280) gives I_c / 256 exactly; the result stays in 0 .. 255 for every
+ *   premultiplied pixel, so the min only guards an overlay that is not (colour > alpha).
+ * Bytes 3 .. elem_sz - 1 of an output pixel are never written.  Only sub-pixels inside the bounding box can change, and only they are
+ * visited: view rows [max(0, y0), min(Hv, y0 + ov_rows)), view columns [x0 - m, x0 + ov_cols + m) within [0, Wv), m =
+ * ceil(|disparity| / 2) + 1; an empty box launches nothing.  The device flavour composites in place on a finished frame of the stated
+ * geometry and writes only bytes 0 .. 2 of the pixels inside the box; the frame and the overlay may not overlap; the frame may have
+ * any byte alignment.  The host flavour uploads the frame and the overlay, composites, and downloads the frame (every byte of it
+ * comes back as it went in, except what the compositor wrote).
+ * Geometry arguments: num_views, angle (lens mode 0 with layout 0 only), the lens (lens_mode 0 .. 3 with stm_set_lens's rules; mode 3
+ * is allowed here: it needs no views), the layout (0, or 1 with tiles_x, tiles_y, order and stm_quilt_multiview's rules; a lens mode
+ * != 0 with layout 1 is an error), out_rows, out_cols, elem_sz.
+ * Errors, through stm_last_error with nothing launched or written: a null or not 4-byte aligned overlay; ov_rows or ov_cols outside
+ * 1 .. 65535; |x0| or |y0| > 65536; a disparity that is not finite or of magnitude > 4096; out_rows or out_cols < 1, elem_sz < 3,
+ * num_views < 2; the lens rules; the layout rules (tiles_x * tiles_y != num_views, a tile of width or height 0, more than 65535 tiles);
+ * in lens mode 0 with layout 0 an angle whose tangent is 0 or too steep, as stm_mux_multiview.
+ * Out of scope: NV12 output (compositing on a chroma-subsampled surface needs a definition of its own: the frame calls and the frame
+ * stream refuse the combination), animated or several simultaneous overlays (a caller flattens them into one), vertical resampling,
+ * straight alpha (convert first).  Parity is against a numpy statement of these lines (parity unpinned). */
+void stm_mux_overlay(unsigned char *frame, const unsigned char *overlay, int ov_rows, int ov_cols, int x0, int y0, float disparity,
+                     int num_views, float angle, int lens_mode, double pitch, double slope, double centre, int layout, int tiles_x,
+                     int tiles_y, int order, int out_rows, int out_cols, int elem_sz);
+void stm_d_mux_overlay(unsigned char *d_frame, const unsigned char *d_overlay, int ov_rows, int ov_cols, int x0, int y0, float disparity,
+                       int num_views, float angle, int lens_mode, double pitch, double slope, double centre, int layout, int tiles_x,
+                       int tiles_y, int order, int out_rows, int out_cols, int elem_sz);
 /* d_demux_common.h:10-13  demux_sbs kernel (d_demux_common.cu:8-33) as a host-callable stage */
 void stm_d_demux_sbs(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_img_sbs,
                      int num_rows, int num_cols_sbs, int num_cols_out, int elem_sz);
@@ -952,10 +1031,26 @@ int   stm_stream_set_layout(void *stream, int layout, int tiles_x, int tiles_y, 
  * leaves as one contiguous NV12 surface, P = num_cols_out and R = num_rows_out, as the stream's NV12 input is contiguous; the output
  * size becomes num_rows_out * num_cols_out * 3 / 2 bytes: what stm_stream_collect copies, what the download moves and what
  * stm_stream_collect_view points at.  The stream keeps its own copy and installs it only around its frame calls, like the layout.
- * Refused while the stream's layout is 0, and stm_stream_set_layout(stream, 0, ...) is refused while the format is 1.  It replays
+ * Refused while the stream's layout is 0, and stm_stream_set_layout(stream, 0, ...) is refused while the format is 1; refused as well
+ * while the stream has an overlay (stm_stream_set_overlay), which in turn is refused while the format is 1.  It replays
  * under the captured graphs (nothing is read back) and combines with every input format, packing, match size, 0x2000 and depth mode.
  * Only before the first submit.  Returns 0, or -1 with stm_last_error set and the stream unchanged. */
 int   stm_stream_set_output(void *stream, int format, int matrix);
+/* the overlay of the stream's frames (stm_mux_overlay's definition, under the stream's own lens and layout).
+ * stm_stream_set_overlay(stream, max_rows, max_cols) switches it on for overlays of up to max_rows x max_cols pixels (both in
+ * 1 .. 65535; (0, 0) = off, the default) and allocates a pinned and a device copy per buffer slot.  Only before the first submit.
+ * Refused while the stream's output format is 1 (NV12), and stm_stream_set_output(stream, 1, ...) is refused while it is on.
+ * stm_stream_overlay sets the overlay every LATER submit composites, until the next call: host memory, ov_rows x ov_cols x 4 bytes,
+ * reusable on return; NULL or a zero size = no overlay (the other arguments are then ignored).  It may be called between any two
+ * submits (subtitles change): frame k shows exactly the overlay in force when it was submitted.  That holds with the captured graphs
+ * on: a slot whose device copy is stale uploads it on the upload stream ahead of the frame, and the composite is launched on the slot's
+ * compute stream after the frame's graph (or its eager pipeline) and before the frame counts as done, so its arguments are never baked
+ * into a graph.  The maps, and with 0x2000 the history, never see the overlay.  The calling thread's stm_set_overlay neither reaches
+ * a stream's frames nor is changed by them.  Errors (stm_last_error, the stream unchanged): stm_mux_overlay's rules for the overlay's
+ * own arguments (its pointer may have any alignment here); an overlay larger than max_rows x max_cols; stm_stream_overlay on a stream
+ * without stm_stream_set_overlay.  Return 0, or -1 with stm_last_error set. */
+int   stm_stream_set_overlay(void *stream, int max_rows, int max_cols);
+int   stm_stream_overlay(void *stream, const unsigned char *overlay, int ov_rows, int ov_cols, int x0, int y0, float disparity);
 /* the depth budget of the stream's frames (stm_set_depth's rules; the default is mode 0).  As with the lens geometry the stream keeps
  * its own copy and installs it only around its frame calls.  stm_stream_set_depth_auto sets mode 2's parameters (stm_set_depth_auto's
  * rules; call it before stm_stream_set_depth(stream, 2, 0, 0)); the state is the stream's own: one buffer at a fixed address, zeroed

@@ -43,6 +43,8 @@ PROTOS = {
     "stm_get_layout": ([C.POINTER(C.c_int)], None),
     "stm_set_output": ([i, i, i, i], i),
     "stm_get_output": ([C.POINTER(C.c_int)], None),
+    "stm_set_overlay": ([i, vp, i, i, i, i, f], i),
+    "stm_get_overlay": ([C.POINTER(C.c_int), f32p], None),
     "stm_set_quilt_lds_limit": ([i], None),
     "stm_set_packing": ([i, i, i, i], i),
     "stm_get_packing": ([C.POINTER(C.c_int)], None),
@@ -89,6 +91,8 @@ PROTOS = {
     "stm_d_mux_multiview_lens": ([vp, vp, i, i, d, d, d, i, i, i, i, i], None),
     "stm_quilt_multiview": ([u8pp, u8p, i, i, i, i, i, i, i, i, i, i], None),
     "stm_d_quilt_multiview": ([vp, vp, i, i, i, i, i, i, i, i, i, i], None),
+    "stm_mux_overlay": ([u8p, u8p, i, i, i, i, f, i, f, i, d, d, d, i, i, i, i, i, i, i], None),
+    "stm_d_mux_overlay": ([vp, vp, i, i, i, i, f, i, f, i, d, d, d, i, i, i, i, i, i, i], None),
     "stm_d_demux_sbs": ([vp, vp, vp, i, i, i, i], None),
     "stm_demux_nv12": ([u8p, u8p, u8p, i, u8p, i, i, i, i, i, i], None),
     "stm_d_demux_nv12": ([vp, vp, vp, i, vp, i, i, i, i, i, i], None),
@@ -131,6 +135,8 @@ PROTOS = {
     "stm_stream_set_lens": ([C.c_void_p, i, d, d, d], i),
     "stm_stream_set_layout": ([C.c_void_p, i, i, i, i, i], i),
     "stm_stream_set_output": ([C.c_void_p, i, i], i),
+    "stm_stream_set_overlay": ([C.c_void_p, i, i], i),
+    "stm_stream_overlay": ([C.c_void_p, u8p, i, i, i, i, f], i),
     "stm_stream_set_depth": ([C.c_void_p, i, f, f], i),
     "stm_stream_set_depth_auto": ([C.c_void_p, f, f, f, i, f], i),
     "stm_stream_depth": ([C.c_void_p, f32p], i),

@@ -246,22 +246,43 @@ void dbm_host(const char *fn, unsigned char *img_out, unsigned char *img_in_l, u
     sync();
 }
 
-void core_mux(const u8 *const *d_views, u8 *d_out, int N, float angle, int Hin, int Win, int Hout, int Wout, int elem_sz,
-              int variant)
+// the reference's view assignment from `angle`: y_interval, 1 / y_interval and round(y_interval) (any of the three may be null);
+// false with the error recorded
+bool mux_geom_ok(int N, float angle, int elem_sz, float *y_interval, float *inv_y_interval, int *ymod_out)
 {
     float yi = mux_y_interval(N, angle, elem_sz);
     // tan(angle) = 0 divides by zero in the reference (d_mux_multiview.cu:146, SURVEY A-Q24); a period beyond the int
     // range would make the (int) conversion undefined
     if (!(fabsf(yi) < 1.0e9f)) {
         fail("mux_multiview: y_interval is not finite (tan(angle) == 0 or angle is not a number)", "angle", __FILE__, __LINE__);
-        return;
+        return false;
     }
     int ymod = (int)roundf(yi);
     if (ymod == 0) {
         fail("mux_multiview: round(y_interval) == 0 (angle too steep)", "ymod", __FILE__, __LINE__);
-        return;
+        return false;
     }
-    launch_mux(d_views, d_out, N, yi, 1.0f / yi, ymod, Hin, Win, Hout, Wout, elem_sz, variant);
+    if (y_interval) *y_interval = yi;
+    if (inv_y_interval) *inv_y_interval = 1.0f / yi;
+    if (ymod_out) *ymod_out = ymod;
+    return true;
+}
+void core_mux(const u8 *const *d_views, u8 *d_out, int N, float angle, int Hin, int Win, int Hout, int Wout, int elem_sz,
+              int variant)
+{
+    float yi, inv_y;
+    int ymod;
+    if (!mux_geom_ok(N, angle, elem_sz, &yi, &inv_y, &ymod)) return;
+    launch_mux(d_views, d_out, N, yi, inv_y, ymod, Hin, Win, Hout, Wout, elem_sz, variant);
+}
+// a quilt's tiles go along the compositor's third grid dimension
+bool overlay_tiles_ok(const char *fn, const Layout &lo, int num_views)
+{
+    if (lo.layout == 0 || num_views <= 65535) return true;
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: an overlay on a quilt of %d tiles: at most 65535 tiles", fn, num_views);
+    fail(msg, "num_views", __FILE__, __LINE__);
+    return false;
 }
 
 // guided up-sampling: the dimension screen, then sigma_color (stm_hip.h)
@@ -326,6 +347,18 @@ bool bytes_overlap(const void *a, size_t n, const void *b, size_t m)
     return pa < pb + m && pb < pa + n;
 }
 } // namespace
+
+// the overlay composited on the finished frame d_frame, rendered under ln and lo (stm_common.h).  In lens mode 0 of layout 0 the
+// sub-pixels' views follow from `angle` as in the frame's interlacer, whose screen the frame call has already passed
+void stm::frame_overlay(u8 *d_frame, const Overlay &ov, const Lens &ln, const Layout &lo, int num_views, float angle, int Hout, int Wout,
+                        int elem_sz)
+{
+    float yi = 0.0f, inv_y = 0.0f;
+    int ymod = 1;
+    if (lo.layout == 0 && ln.mode == 0 && !mux_geom_ok(num_views, angle, elem_sz, &yi, &inv_y, &ymod)) return;
+    launch_overlay(d_frame, ov.d_overlay, ov.ov_rows, ov.ov_cols, ov.x0, ov.y0, ov.disparity, num_views, ln, yi, inv_y, ymod, lo, Hout, Wout,
+                   elem_sz);
+}
 
 // the rules of an NV12 frame (stm_hip.h, stm_demux_nv12), after the dimension screen; cols_name: what the call names the width of a view
 bool stm::nv12_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, const char *cols_name, int pitch_y, int pitch_uv,
@@ -1033,6 +1066,63 @@ void stm_quilt_multiview(unsigned char **views, unsigned char *out_data, int num
     sync();
 }
 
+// an overlay composited into a finished frame (an addition; stm_hip.h).  The screen of both flavours: the overlay's own arguments
+// (words: the device flavour reads a pixel as one aligned word; the host flavour copies into an aligned buffer), then the frame's
+// geometry under the stage's lens and layout rules; false with the error recorded
+static bool overlay_stage_ok(const char *fn, const unsigned char *overlay, bool words, int ov_rows, int ov_cols, int x0, int y0, float disparity,
+                             int num_views, int lens_mode, double pitch, double slope, double centre, int layout, int tiles_x, int tiles_y,
+                             int order, int out_rows, int out_cols, int elem_sz)
+{
+    if (!args_ok(fn, {{"num_views", num_views, 2}, {"out_rows", out_rows, 1}, {"out_cols", out_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
+    if (!overlay_params_ok(fn, overlay, words, ov_rows, ov_cols, x0, y0, disparity)) return false;
+    if (!overlay) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "%s: the overlay is null", fn);
+        fail(msg, "overlay", __FILE__, __LINE__);
+        return false;
+    }
+    if (!lens_params_ok(fn, lens_mode, 0, 3, pitch, slope, centre)) return false;
+    if (!layout_params_ok(fn, layout, tiles_x, tiles_y, order, 0)) return false;
+    if (layout == 0) return true;
+    if (!overlay_tiles_ok(fn, Layout{1, tiles_x, tiles_y, order, 0}, num_views)) return false;
+    if (lens_mode != 0) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "%s: layout 1 (quilt) together with lens mode %d: a quilt is not interlaced, set one of them to 0", fn, lens_mode);
+        fail(msg, "layout, lens_mode", __FILE__, __LINE__);
+        return false;
+    }
+    return quilt_args_ok(fn, Layout{1, tiles_x, tiles_y, order, 0}, num_views, 1, 1, out_rows, out_cols, "num_views", "out_rows", "out_cols");
+}
+void stm_d_mux_overlay(unsigned char *d_frame, const unsigned char *d_overlay, int ov_rows, int ov_cols, int x0, int y0, float disparity,
+                       int num_views, float angle, int lens_mode, double pitch, double slope, double centre, int layout, int tiles_x,
+                       int tiles_y, int order, int out_rows, int out_cols, int elem_sz)
+{
+    if (!overlay_stage_ok("d_mux_overlay", d_overlay, true, ov_rows, ov_cols, x0, y0, disparity, num_views, lens_mode, pitch, slope, centre, layout,
+                          tiles_x, tiles_y, order, out_rows, out_cols, elem_sz))
+        return;
+    frame_overlay(d_frame, Overlay{1, d_overlay, ov_rows, ov_cols, x0, y0, disparity},
+                  lens_mode == 0 ? Lens{0, 0.0, 0.0, 0.0} : Lens{lens_mode, pitch, slope, centre},
+                  layout == 0 ? Layout{0, 1, 1, 0, 0} : Layout{1, tiles_x, tiles_y, order, 0}, num_views, angle, out_rows, out_cols, elem_sz);
+}
+void stm_mux_overlay(unsigned char *frame, const unsigned char *overlay, int ov_rows, int ov_cols, int x0, int y0, float disparity,
+                     int num_views, float angle, int lens_mode, double pitch, double slope, double centre, int layout, int tiles_x,
+                     int tiles_y, int order, int out_rows, int out_cols, int elem_sz)
+{
+    if (!overlay_stage_ok("mux_overlay", overlay, false, ov_rows, ov_cols, x0, y0, disparity, num_views, lens_mode, pitch, slope, centre, layout,
+                          tiles_x, tiles_y, order, out_rows, out_cols, elem_sz))
+        return;
+    if (layout == 0 && lens_mode == 0 && !mux_geom_ok(num_views, angle, elem_sz, nullptr, nullptr, nullptr)) return; // before the upload
+    const size_t out_sz = (size_t)out_rows * out_cols * elem_sz, ov_sz = (size_t)ov_rows * ov_cols * 4;
+    Workspace::begin(out_sz + ov_sz + 8192);
+    u8 *f = up(frame, out_sz), *o = up(overlay, ov_sz);
+    frame_overlay(f, Overlay{1, o, ov_rows, ov_cols, x0, y0, disparity},
+                  lens_mode == 0 ? Lens{0, 0.0, 0.0, 0.0} : Lens{lens_mode, pitch, slope, centre},
+                  layout == 0 ? Layout{0, 1, 1, 0, 0} : Layout{1, tiles_x, tiles_y, order, 0}, num_views, angle, out_rows, out_cols, elem_sz);
+    if (failed()) return; // the caller's frame stays as it was
+    down(frame, f, out_sz);
+    sync();
+}
+
 void stm_d_demux_sbs(unsigned char *d_img_l, unsigned char *d_img_r, unsigned char *d_img_sbs, int num_rows,
                      int num_cols_sbs, int num_cols_out, int elem_sz)
 {
@@ -1421,6 +1511,16 @@ bool frame_layout_ok(const char *fn, int stages, int num_views, int H, int W, in
 {
     const Layout lo = layout();
     if ((stages & 0xff) < 3) return true;
+    if (overlay().mode == 1) { // an overlay (stm_set_overlay) is composited on BGR frames only
+        if (output().format == 1) {
+            char msg[240];
+            snprintf(msg, sizeof msg, "%s: an overlay (stm_set_overlay) together with output format 1 (NV12): compositing on a chroma-subsampled "
+                     "surface is not defined, set one of them to 0", fn);
+            fail(msg, "overlay, format", __FILE__, __LINE__);
+            return false;
+        }
+        if (!overlay_tiles_ok(fn, lo, num_views)) return false;
+    }
     if (lo.layout == 0) return frame_output_ok(fn, lo, Hout, Wout);
     if (lens().mode != 0) {
         char msg[200];
@@ -1655,6 +1755,8 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
     }
     if (stages < 3) return;
     frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle, linwarp);
+    // the thread's overlay (stm_set_overlay), composited on the finished frame: the call's last launch
+    if (overlay().mode == 1) frame_overlay(d_interlaced, overlay(), lens(), layout(), N, angle, num_rows_out, num_cols_out, elem_sz);
 }
 
 bool frame_dims_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz,
@@ -1918,6 +2020,8 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
         launch_disp_temporal(2, c, q, im, ip, off, H, W, split ? W : num_cols_sbs, elem_sz, hist->alpha, hist->thresh_color, hist->thresh_disp);
     }
     frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle, linwarp);
+    // the thread's overlay (stm_set_overlay), composited on the finished frame: the call's last launch
+    if (overlay().mode == 1) frame_overlay(d_interlaced, overlay(), lens(), layout(), N, angle, num_rows_out, num_cols_out, elem_sz);
 }
 
 void reduced_frame_host(const char *fn, unsigned char *img_sbs, float *disp_l, float *disp_r, unsigned char *interlaced, int num_rows,

@@ -357,6 +357,27 @@ void launch_quilt(const u8 *const *d_views, u8 *out, int N, const Layout &lo, in
 void launch_synth_quilt(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l, const float *mask_r,
                         const float *blend, u8 *out, int N, const Layout &lo, int depth_mode, float gain, float conv, const float *state,
                         int Hin, int Win, int Hout, int Wout, int elem_sz, bool linear, const Nv12Out *nv = nullptr);
+// The overlay composited into finished frames (stm_set_overlay, include/stm_hip.h): mode 0 = off, 1 = every rendering frame call
+// composites `d_overlay` (ov_rows x ov_cols x 4 bytes B, G, R, A premultiplied, device memory the caller keeps alive) as its last
+// launch.  One per host thread; a frame stream composites its own after its frame calls and never installs it here.
+struct Overlay {
+    int mode;
+    const u8 *d_overlay;
+    int ov_rows, ov_cols, x0, y0;
+    float disparity;
+};
+Overlay overlay();
+void set_overlay(const Overlay &o);
+// the rules of an overlay's own arguments (stm_hip.h, stm_mux_overlay); check_ptr: the pointer's too.  false with the error recorded
+bool overlay_params_ok(const char *fn, const void *ov, bool check_ptr, int ov_rows, int ov_cols, int x0, int y0, float disparity);
+// stm_api.hip: an overlay composited on a finished frame rendered under ln and lo, which the frame call has screened (the frame
+// calls' last launch with the thread's settings, and a frame stream's after its frame call with the stream's own)
+void frame_overlay(u8 *d_frame, const Overlay &ov, const Lens &ln, const Layout &lo, int num_views, float angle, int Hout, int Wout,
+                   int elem_sz);
+// the compositor (stm_kernels_overlay.hip): `ov` in place on the finished frame `out` (Hout x Wout x elem_sz); lo.layout 0: interlaced
+// under ln (ln.mode 0: the reference's view assignment from y_interval, inv_y_interval and ymod), 1: a quilt.  Screened by the caller
+void launch_overlay(u8 *out, const u8 *ov, int ov_rows, int ov_cols, int x0, int y0, float disparity, int N, const Lens &ln,
+                    float y_interval, float inv_y_interval, int ymod, const Layout &lo, int Hout, int Wout, int elem_sz);
 // the measurement (stm_kernels_depth.hip): both maps into the 4096-bin histogram `hist` (scratch), the fit, the update of `state`
 // (four floats); fresh: the state's history is ignored
 void launch_depth_fit(float *state, uint32_t *hist, const float *disp_l, const float *disp_r, int H, int W, float disp_lo, float disp_hi,

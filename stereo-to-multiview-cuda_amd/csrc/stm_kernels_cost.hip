@@ -205,6 +205,7 @@ __global__ __launch_bounds__(256) void stm_k_front(u8 *__restrict__ l, u8 *__res
 void launch_front(u8 *l, u8 *r, uint32_t *pk_l, uint32_t *pk_r, uint32_t *wide_l, uint32_t *wide_r, uint32_t *cen_l, uint32_t *cen_r,
                   const u8 *sbs, int H, int Wsbs, int W, int elem_sz)
 {
+    ProfScope p("front"); // (host side only, and nothing at all unless stm_prof_enable: the yardstick of tools/overlay_time.py)
     STM_LAUNCH(stm_k_front, dim3(cdiv(W, FR_TX), cdiv(H, FR_TY), 2), dim3(256), 0, stream(), l, r, pk_l, pk_r, wide_l, wide_r, cen_l, cen_r,
                sbs, H, Wsbs, W, elem_sz);
     STM_CHECK_LAUNCH();

@@ -11,6 +11,7 @@
 // The reference synthesises one view with two warp launches, two temporaries and a merge launch;
 // here one kernel gathers both sources and blends in registers (same arithmetic, same truncations).
 #include "stm_common.h"
+#include "stm_views.h"
 
 namespace stm {
 
@@ -487,13 +488,7 @@ __global__ __launch_bounds__(256) void stm_k_mux(const u8 *const *__restrict__ v
     xs = fminf(fmaxf(xs, 0.0f), (float)(Win - 1));
     float ys = ((float)ty / (float)Hout) * (float)Hin;
     ys = fminf(fmaxf(ys, 0.0f), (float)(Hin - 1));
-    float x_interval = (float)N;
-    float y_view = (float)(ty % ymod) + 1.0f;
-    y_view = y_view * x_interval;
-    y_view = (variant == 2) ? y_view * inv_y : y_view / y_interval; // :62-63 vs :105-106
-    int x_view = (tx * 3 + (int)y_view) % N;
-    int r_view = x_view;
-    if (r_view < 0) r_view += N;
+    int r_view = mux_r_view(tx, ty, N, y_interval, inv_y, ymod, variant); // :62-63 vs :105-106
     int g_view = r_view + 1, b_view = r_view + 2;
     if (g_view >= N) g_view -= N;
     if (b_view >= N) b_view -= N;
@@ -570,13 +565,7 @@ __global__ __launch_bounds__(256) void stm_k_synth_mux(SynthArgs a, u8 *__restri
     xs = fminf(fmaxf(xs, 0.0f), (float)(Win - 1));
     float ys = ((float)ty / (float)Hout) * (float)Hin;
     ys = fminf(fmaxf(ys, 0.0f), (float)(Hin - 1));
-    const float x_interval = (float)N;
-    float y_view = (float)(ty % ymod) + 1.0f;
-    y_view = y_view * x_interval;
-    y_view = (variant == 2) ? y_view * inv_y : y_view / y_interval; // d_mux_multiview.cu:62-63 vs :105-106
-    const int x_view = (tx * 3 + (int)y_view) % N;
-    int r_view = x_view;
-    if (r_view < 0) r_view += N;
+    const int r_view = mux_r_view(tx, ty, N, y_interval, inv_y, ymod, variant); // d_mux_multiview.cu:62-63 vs :105-106
     int g_view = r_view + 1, b_view = r_view + 2;
     if (g_view >= N) g_view -= N;
     if (b_view >= N) b_view -= N;
@@ -614,38 +603,7 @@ void launch_mux(const u8 *const *d_views, u8 *out, int N, float y_interval, floa
 // sub-pixels, no phase offset, a slant whose row period is rounded to an integer.  Here the view follows from the panel's
 // calibration: the lens phase of sub-pixel k = 2 - c of output pixel (tx, ty), in double, one operation per line (the file is
 // compiled -ffp-contract=off and the f64 division is the correctly rounded one).  The sampling position (xs, ys) and the
-// 4-neighbour sampler stay the reference's.
-__device__ __forceinline__ double lens_phase(int tx, int ty, int c, const Lens &g)
-{
-    const int s = 3 * tx + (2 - c);
-    const double t1 = (double)ty * g.slope;
-    const double t2 = (double)s + t1;
-    const double t3 = t2 / g.pitch;
-    const double t4 = t3 + g.centre;
-    const double a = t4 - floor(t4);
-    return a < 1.0 ? a : 0.0; // a >= 1: t4 was a tiny negative number and the subtraction rounded to 1 (a t4 that is not finite lands here too)
-}
-// what a phase selects -- MODE 1: the nearest view v; MODE 2: the views v, v + 1 and the weight w of the second; MODE 3: the shift
-// of the sub-pixel's own position between the cameras
-template <int MODE>
-__device__ __forceinline__ void lens_pick(double a, int N, int &v, float &w, float &shift)
-{
-    double g = a * (double)N;
-    v = 0; w = 0.0f; shift = 0.0f;
-    if constexpr (MODE == 1) {
-        v = min((int)g, N - 1);
-    } else {
-        g = g - 0.5;
-        g = fmin(fmax(g, 0.0), (double)(N - 1)); // the half-bin at either lens edge shows the end view
-        if constexpr (MODE == 2) {
-            v = min((int)g, N - 2);
-            w = (float)(g - (double)v);
-        } else {
-            const double u = g / (double)(N - 1);
-            shift = (float)(1.0 - u);
-        }
-    }
-}
+// 4-neighbour sampler stay the reference's.  lens_phase and lens_pick live in stm_views.h: the overlay compositor shares them.
 template <int MODE>
 __global__ __launch_bounds__(256) void stm_k_mux_lens(const u8 *const *__restrict__ views, u8 *__restrict__ out, int N, Lens g, int Hin,
                                                       int Win, int Hout, int Wout, int elem_sz)
@@ -823,10 +781,7 @@ void launch_synth_mux_lens(const u8 *img_l, const u8 *img_r, const float *disp_l
 // The fused renderer with a view's position s mapped to the shift it is rendered at and to a horizontal offset of its sampling
 // position: s2 = 0.5 + gain (s - 0.5), cx = clamp(xs + conv (s - 0.5)).  Every sample takes the general form at s2 (no end-view
 // shortcut: at gain != 1 the end views are warps too).  LMODE 0 = the reference's view assignment, 1 .. 3 = the lens modes.
-__device__ __forceinline__ float view_shift(int v, int N)
-{
-    return (float)(1.0 - ((1.0 * (double)(float)v) / ((double)(float)N - 1.0))); // d_io.cu:189
-}
+// (view_shift and MuxGeom: stm_views.h.)
 // the four neighbours of the position a sample is taken at.  The three channels of a pixel belong to three views, so with
 // conv != 0 their positions differ; where two of them share x0 (always, with conv == 0) the neighbours' maps are loaded once.
 struct DepthNbs {
@@ -861,10 +816,6 @@ __device__ __forceinline__ u8 depth_sample(const SynthArgs &a, DepthNbs &nb, flo
     }
     return lens_bilinear<LINEAR, true>(a, nb.n00, nb.n01, nb.n10, nb.n11, wx, wy, 0, 0, s2, c, Win, elem_sz);
 }
-struct MuxGeom { // the reference's view assignment (LMODE 0): mux_multiview_kernel_2's arguments
-    float inv_y;
-    int ymod;
-};
 template <int LMODE, bool LINEAR>
 __global__ __launch_bounds__(256) void stm_k_synth_mux_depth(SynthArgs a, u8 *__restrict__ out, int N, MuxGeom mg, Lens g, float gain,
                                                              float conv, const float *__restrict__ state, int Hin, int Win, int Hout,
@@ -884,14 +835,7 @@ __global__ __launch_bounds__(256) void stm_k_synth_mux_depth(SynthArgs a, u8 *__
     const int y1 = min(y0 + 1, Hin - 1);
     const float wy = ys - (float)y0;
     int r_view = 0;
-    if constexpr (LMODE == 0) {
-        const float x_interval = (float)N;
-        float y_view = (float)(ty % mg.ymod) + 1.0f;
-        y_view = y_view * x_interval;
-        y_view = y_view * mg.inv_y; // d_mux_multiview.cu:62-63
-        r_view = (tx * 3 + (int)y_view) % N;
-        if (r_view < 0) r_view += N;
-    }
+    if constexpr (LMODE == 0) r_view = mux_r_view(tx, ty, N, 0.0f, mg.inv_y, mg.ymod, 2); // d_mux_multiview.cu:62-63
     DepthNbs nb;
     nb.x0 = -1;
     nb.has_x1 = false;
@@ -964,17 +908,7 @@ struct QuiltSrc {
     float gain, conv;       // QSRC_DEPTH
     const float *state;     // QSRC_DEPTH, automatic mode: gain and conv are read from state[1], state[2]
 };
-struct QuiltGeom {
-    int N, tiles_x, tiles_y, order, tw, th, Hin, Win, Hout, Wout, elem_sz;
-    int narrow; // 255 Win Hin + Win Hin / 2 fits 32 bits
-};
-// where tile k lies: its left column and top row
-__device__ __forceinline__ void quilt_tile_origin(const QuiltGeom &g, int k, int &left, int &top)
-{
-    const int i = k % g.tiles_x, j = k / g.tiles_x;
-    left = i * g.tw;
-    top = (g.order & 1) ? g.Hout - (j + 1) * g.th : j * g.th;
-}
+// (QuiltGeom and quilt_tile_origin: stm_views.h)
 // the three channels of V(v, x, y): the maps of the pixel are loaded once
 template <int SRC, bool LINEAR>
 __device__ __forceinline__ void quilt_render3(const QuiltSrc &s, const QuiltGeom &g, int v, int x, int y, uint32_t (&px)[3])

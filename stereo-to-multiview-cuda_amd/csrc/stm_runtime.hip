@@ -319,6 +319,40 @@ bool output_params_ok(const char *fn, int format, int matrix, int pitch, int uv_
     fail(msg, arg, __FILE__, __LINE__);
     return false;
 }
+// the calling thread's overlay (stm_set_overlay)
+static thread_local Overlay g_overlay = {0, nullptr, 0, 0, 0, 0, 0.0f};
+Overlay overlay() { return g_overlay; }
+void set_overlay(const Overlay &o) { g_overlay = o; }
+bool overlay_params_ok(const char *fn, const void *ov, bool check_ptr, int ov_rows, int ov_cols, int x0, int y0, float disparity)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (check_ptr && !ov) {
+        snprintf(msg, sizeof msg, "%s: the overlay is null", fn);
+        arg = "overlay";
+    } else if (check_ptr && ((uintptr_t)ov & 3) != 0) {
+        snprintf(msg, sizeof msg, "%s: the overlay must be 4-byte aligned (a pixel is read as one word)", fn);
+        arg = "overlay";
+    } else if (ov_rows < 1 || ov_rows > 65535) {
+        snprintf(msg, sizeof msg, "%s: ov_rows = %d, must be in 1 .. 65535", fn, ov_rows);
+        arg = "ov_rows";
+    } else if (ov_cols < 1 || ov_cols > 65535) {
+        snprintf(msg, sizeof msg, "%s: ov_cols = %d, must be in 1 .. 65535", fn, ov_cols);
+        arg = "ov_cols";
+    } else if (x0 < -65536 || x0 > 65536) {
+        snprintf(msg, sizeof msg, "%s: x0 = %d, must be in -65536 .. 65536", fn, x0);
+        arg = "x0";
+    } else if (y0 < -65536 || y0 > 65536) {
+        snprintf(msg, sizeof msg, "%s: y0 = %d, must be in -65536 .. 65536", fn, y0);
+        arg = "y0";
+    } else if (!(fabsf(disparity) <= 4096.0f)) { // NaN fails the comparison
+        snprintf(msg, sizeof msg, "%s: disparity = %g, must be finite and of magnitude <= 4096", fn, (double)disparity);
+        arg = "disparity";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
 // stm_mux_nv12's coefficients (stm_hip.h): each rounded one computed in double and rounded to nearest, the three derived ones by
 // subtraction, so that white lands on the range's end and every grey on 128 / 128
 Nv12OutCoef nv12_out_coef(int matrix)
@@ -583,6 +617,25 @@ void stm_get_output(int out[4])
 {
     const stm::Output o = stm::output();
     out[0] = o.format; out[1] = o.matrix; out[2] = o.pitch; out[3] = o.uv_row;
+}
+int stm_set_overlay(int mode, const unsigned char *d_overlay, int ov_rows, int ov_cols, int x0, int y0, float disparity)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (mode != 0 && mode != 1) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "set_overlay: mode = %d, must be 0 (off) or 1 (on)", mode);
+        stm::fail(msg, "mode", __FILE__, __LINE__);
+        return -1; // the thread's setting stays as it was
+    }
+    if (mode == 1 && !stm::overlay_params_ok("set_overlay", d_overlay, true, ov_rows, ov_cols, x0, y0, disparity)) return -1;
+    stm::set_overlay(mode == 0 ? stm::Overlay{0, nullptr, 0, 0, 0, 0, 0.0f} : stm::Overlay{1, d_overlay, ov_rows, ov_cols, x0, y0, disparity});
+    return 0;
+}
+void stm_get_overlay(int out[5], float *disparity)
+{
+    const stm::Overlay o = stm::overlay();
+    out[0] = o.mode; out[1] = o.ov_rows; out[2] = o.ov_cols; out[3] = o.x0; out[4] = o.y0;
+    if (disparity) *disparity = o.disparity;
 }
 void stm_set_quilt_lds_limit(int bytes) { stm::g_quilt_lds_limit = bytes <= 0 ? 32 * 1024 : (bytes > 64 * 1024 ? 64 * 1024 : bytes); }
 int stm_set_packing(int packing, int swap, int filter, int gap)

@@ -23,6 +23,8 @@ struct Slot {
     float *d_dl = nullptr, *d_dr = nullptr, *h_dl = nullptr, *h_dr = nullptr;
     u8 *d_img_l = nullptr, *d_img_r = nullptr; // NV12 input: the slot's converted split images (the other slot's frame reads them as its history)
     float *d_rec = nullptr, *h_rec = nullptr; // depth mode 2: the state as this slot's frame left it (16 bytes), and its download
+    u8 *h_ov = nullptr, *d_ov = nullptr;      // stm_stream_set_overlay: the slot's pinned and device copy of the overlay's pixels
+    long ov_gen = 0;                          // ... and which stm_stream_overlay call they hold (0 = none yet)
     hipEvent_t ev_in, ev_done, ev_out;
     bool busy = false;
     hipStream_t s_compute = nullptr; // this slot's compute stream and private workspace (shared by both slots when overlap is off)
@@ -58,6 +60,10 @@ struct FrameStream {
     int match_h = 0, match_w = 0;        // stm_stream_set_match_size: the size the pair is matched at (0, 0 = off: the full-resolution frame)
     float match_scale = 1.0f;            // ... and the reduced frame's disp_scale
     float *d_depth_state = nullptr; // mode 2: the state every frame updates, at one address for both slots' graphs
+    int ov_max_rows = 0, ov_max_cols = 0; // stm_stream_set_overlay: the largest overlay the slots' copies hold ((0, 0) = off)
+    u8 *ov_pixels = nullptr;              // stm_stream_overlay: the pixels of the overlay in force (host memory of the stream's own)
+    stm::Overlay ov = {0, nullptr, 0, 0, 0, 0, 0.0f}; // ... and its arguments; mode 0 = none.  d_overlay is filled in per slot
+    long ov_gen = 0;                      // counts the stm_stream_overlay calls that brought pixels
     Slot slot[2];
     long submitted = 0, collected = 0;
 };
@@ -85,6 +91,13 @@ struct DepthScope {
     stm::Depth saved;
     explicit DepthScope(const stm::Depth &d) : saved(stm::depth()) { stm::set_depth(d); }
     ~DepthScope() { stm::set_depth(saved); }
+};
+
+// the calling thread's overlay (stm_set_overlay) never reaches a stream's frames: the stream composites its own after the frame call
+struct OverlayOffScope {
+    stm::Overlay saved;
+    OverlayOffScope() : saved(stm::overlay()) { stm::set_overlay(stm::Overlay{0, nullptr, 0, 0, 0, 0, 0.0f}); }
+    ~OverlayOffScope() { stm::set_overlay(saved); }
 };
 
 struct PackingScope {
@@ -391,8 +404,104 @@ int stm_stream_set_output(void *h, int format, int matrix)
                   __FILE__, __LINE__);
         return -1;
     }
+    if (format == 1 && f->ov_max_rows > 0) {
+        stm::fail("stream_set_output: format 1 (NV12) together with the stream's overlay (stm_stream_set_overlay): compositing on a "
+                  "chroma-subsampled surface is not defined, switch the overlay off first", "format", __FILE__, __LINE__);
+        return -1;
+    }
     f->output = format == 0 ? stm::Output{0, 0, 0, 0} : stm::Output{1, matrix, 0, 0};
     f->out_bytes = format == 1 ? (size_t)f->Hout * f->Wout * 3 / 2 : f->out_sz;
+    return 0;
+}
+
+// The overlay of the stream's frames (stm_hip.h): room for overlays of up to max_rows x max_cols pixels -- the stream's own host copy
+// of the pixels in force and, per slot, a pinned and a device copy; (0, 0) = off.  Only before the first submit, and not together with
+// output format 1.  Returns 0, or -1 with the error recorded and the stream unchanged.
+int stm_stream_set_overlay(void *h, int max_rows, int max_cols)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    const bool off = max_rows == 0 && max_cols == 0;
+    if (!off && (max_rows < 1 || max_rows > 65535 || max_cols < 1 || max_cols > 65535)) {
+        stm::fail("stream_set_overlay: max_rows and max_cols must be in 1 .. 65535, or both 0 (off)", "max_rows, max_cols", __FILE__, __LINE__);
+        return -1;
+    }
+    if (f->submitted > 0) {
+        stm::fail("stream_set_overlay: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    if (!off && f->output.format == 1) {
+        stm::fail("stream_set_overlay: the stream's output format is 1 (NV12): compositing on a chroma-subsampled surface is not defined, "
+                  "set format 0 first (stm_stream_set_output)", "format", __FILE__, __LINE__);
+        return -1;
+    }
+    int caller_dev = f->dev;
+    STM_CHECK(hipGetDevice(&caller_dev));
+    if (caller_dev != f->dev) STM_CHECK(hipSetDevice(f->dev));
+    // the new buffers first, the old ones freed only once all exist: a failed allocation leaves the stream as it was
+    const size_t bytes = (size_t)max_rows * max_cols * 4;
+    u8 *pix = nullptr, *h_new[2] = {nullptr, nullptr}, *d_new[2] = {nullptr, nullptr};
+    if (!off) {
+        pix = (u8 *)malloc(bytes);
+        if (!pix) stm::fail("stream_set_overlay: out of host memory", "malloc", __FILE__, __LINE__);
+        for (int i = 0; i < 2 && !stm::failed(); ++i) {
+            STM_CHECK(hipHostMalloc((void **)&h_new[i], bytes, hipHostMallocDefault));
+            STM_CHECK(hipMalloc((void **)&d_new[i], bytes));
+        }
+    }
+    if (stm::failed()) {
+        free(pix);
+        for (int i = 0; i < 2; ++i) {
+            if (h_new[i]) (void)hipHostFree(h_new[i]);
+            if (d_new[i]) (void)hipFree(d_new[i]);
+        }
+        if (caller_dev != f->dev) (void)hipSetDevice(caller_dev);
+        return -1;
+    }
+    free(f->ov_pixels);
+    f->ov_pixels = pix;
+    for (int i = 0; i < 2; ++i) {
+        Slot &s = f->slot[i];
+        if (s.h_ov) STM_CHECK(hipHostFree(s.h_ov));
+        if (s.d_ov) STM_CHECK(hipFree(s.d_ov));
+        s.h_ov = h_new[i];
+        s.d_ov = d_new[i];
+        s.ov_gen = 0;
+    }
+    if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
+    f->ov_max_rows = max_rows;
+    f->ov_max_cols = max_cols;
+    f->ov = stm::Overlay{0, nullptr, 0, 0, 0, 0, 0.0f};
+    f->ov_gen = 0;
+    return 0;
+}
+
+// The overlay every later submit composites, until the next call (stm_hip.h): the pixels are copied into the stream's own memory, so the
+// caller's are reusable on return; a slot uploads them when it next takes a frame.  NULL or a zero size = none.  Returns 0, or -1 with
+// the error recorded and the overlay in force unchanged.
+int stm_stream_overlay(void *h, const unsigned char *overlay, int ov_rows, int ov_cols, int x0, int y0, float disparity)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (f->ov_max_rows == 0) {
+        stm::fail("stream_overlay: the stream has no overlay (stm_stream_set_overlay, before the first submit)", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    if (!overlay || ov_rows == 0 || ov_cols == 0) {
+        f->ov.mode = 0;
+        return 0;
+    }
+    if (!stm::overlay_params_ok("stream_overlay", overlay, false, ov_rows, ov_cols, x0, y0, disparity)) return -1;
+    if (ov_rows > f->ov_max_rows || ov_cols > f->ov_max_cols) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "stream_overlay: an overlay of %d x %d pixels, the stream holds at most %d x %d (stm_stream_set_overlay)", ov_rows,
+                 ov_cols, f->ov_max_rows, f->ov_max_cols);
+        stm::fail(msg, "ov_rows, ov_cols", __FILE__, __LINE__);
+        return -1;
+    }
+    memcpy(f->ov_pixels, overlay, (size_t)ov_rows * ov_cols * 4);
+    f->ov = stm::Overlay{1, nullptr, ov_rows, ov_cols, x0, y0, disparity};
+    ++f->ov_gen;
     return 0;
 }
 
@@ -478,6 +587,15 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     // writes the images that frame reads as ITS history.
     if (history && f->in_format == 0) STM_CHECK(hipStreamWaitEvent(f->s_in, other.ev_done, 0));
     STM_CHECK(hipMemcpyAsync(s.d_in, s.h_in, f->in_bytes, hipMemcpyHostToDevice, f->s_in));
+    // the overlay in force (stm_stream_overlay): a slot whose device copy holds another call's pixels uploads them ahead of the
+    // frame.  The slot's previous frame, the last reader of both copies, was collected before the slot was handed out again.
+    const stm::Overlay ov = f->ov;
+    if (ov.mode == 1 && s.ov_gen != f->ov_gen) {
+        const size_t ov_bytes = (size_t)ov.ov_rows * ov.ov_cols * 4;
+        memcpy(s.h_ov, f->ov_pixels, ov_bytes);
+        STM_CHECK(hipMemcpyAsync(s.d_ov, s.h_ov, ov_bytes, hipMemcpyHostToDevice, f->s_in));
+        s.ov_gen = f->ov_gen;
+    }
     STM_CHECK(hipEventRecord(s.ev_in, f->s_in));
     STM_CHECK(hipStreamWaitEvent(s.s_compute, s.ev_in, 0));
     if (history || (depth_auto && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
@@ -487,6 +605,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     OutputScope output_scope(f->output);
     DepthScope depth_scope(f->depth);
     PackingScope packing_scope(f->packing);
+    OverlayOffScope overlay_scope;
     stm_set_stream(s.s_compute);
     stm::ws_private_bind(s.ws);
     auto pipeline = [&]() {
@@ -561,6 +680,11 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
         pipeline();
         ++s.eager_runs;
     }
+    // the overlay, composited on the slot's finished frame: a launch of its own behind the graph (or the eager pipeline) on the slot's
+    // compute stream, so its arguments change from frame to frame without touching the capture
+    if (ov.mode == 1)
+        stm::frame_overlay(s.d_out, stm::Overlay{1, s.d_ov, ov.ov_rows, ov.ov_cols, ov.x0, ov.y0, ov.disparity}, f->lens, f->layout, f->N,
+                           f->angle, f->Hout, f->Wout, f->E);
     stm::ws_private_bind(nullptr);
     stm_set_stream(prev);
     // the state as this frame left it, before ev_done lets the next frame's fit update it
@@ -634,7 +758,10 @@ void stm_stream_destroy(void *h)
         if (s.d_img_r) STM_CHECK(hipFree(s.d_img_r));
         if (s.d_rec) STM_CHECK(hipFree(s.d_rec));
         if (s.h_rec) STM_CHECK(hipHostFree(s.h_rec));
+        if (s.h_ov) STM_CHECK(hipHostFree(s.h_ov));
+        if (s.d_ov) STM_CHECK(hipFree(s.d_ov));
     }
+    free(f->ov_pixels);
     if (f->d_depth_state) STM_CHECK(hipFree(f->d_depth_state));
     stm::ws_private_destroy(f->slot[0].ws);
     STM_CHECK(hipStreamDestroy(f->slot[0].s_compute));

@@ -138,6 +138,56 @@ def get_output():
     return tuple(int(v) for v in out)
 
 
+_overlay_keepalive = {}  # thread id -> the tensor the library's setting of that thread points into
+
+
+def _check_overlay(overlay):
+    assert overlay.is_cuda and overlay.dtype == torch.uint8 and overlay.is_contiguous()
+    assert overlay.dim() == 3 and overlay.shape[2] == 4, "an overlay is uint8 [rows][cols][4]: B, G, R, A, premultiplied"
+
+
+def set_overlay(d_overlay, x0=0, y0=0, disparity=0.0):
+    """stm_set_overlay: the calling thread's overlay, which every rendering frame call composites into its finished frame as its
+    last launch (include/stm_hip.h, stm_mux_overlay).  d_overlay: a uint8 [rows][cols][4] tensor on the GPU -- B, G, R, A with
+    premultiplied alpha (video.premultiply converts straight alpha) -- or None = off, the default.  (x0, y0): the view pixel its
+    top-left corner sits at -- a pixel of the frame, or of one tile of a quilt; disparity: end to end in the maps' sign convention,
+    > 0 behind the screen, < 0 in front, 0 on it.  The tensor is kept alive here until the setting changes; its contents must not
+    change while a frame call may read it.  Raises ValueError where the library refuses."""
+    import threading
+    if d_overlay is None:
+        lib().stm_set_overlay(0, None, 0, 0, 0, 0, 0.0)
+        _overlay_keepalive.pop(threading.get_ident(), None)
+        return
+    _check_overlay(d_overlay)
+    if int(lib().stm_set_overlay(1, _p(d_overlay), d_overlay.shape[0], d_overlay.shape[1], int(x0), int(y0), float(disparity))) != 0:
+        raise ValueError("stm_set_overlay(%d x %d at (%d, %d), disparity %g) refused: %s"
+                         % (d_overlay.shape[0], d_overlay.shape[1], x0, y0, disparity, lib().stm_last_error().decode()))
+    _overlay_keepalive[threading.get_ident()] = d_overlay
+
+
+def get_overlay():
+    """stm_get_overlay: the calling thread's (mode, ov_rows, ov_cols, x0, y0, disparity) as the library holds it"""
+    out = (C.c_int * 5)()
+    disp = C.c_float(0.0)
+    lib().stm_get_overlay(out, C.cast(C.byref(disp), f32p))
+    return tuple(int(v) for v in out) + (float(disp.value),)
+
+
+def d_mux_overlay(frame, overlay, x0, y0, disparity, num_views, angle=18.43, lens=None, layout=None):
+    """stm_d_mux_overlay: the overlay (uint8 [rows][cols][4] on the GPU, premultiplied B, G, R, A) composited in place into the
+    finished frame (uint8 [Ho][Wo][E] on the GPU; only bytes 0 .. 2 of the pixels inside the overlay's bounding box are written).
+    lens = (mode, pitch, slope, centre) as set_lens, None = the reference's interlacer at `angle`; layout = (1, tiles_x, tiles_y,
+    order) for a quilt, None = the interlaced frame."""
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.dim() == 3 and frame.is_contiguous()
+    _check_overlay(overlay)
+    ln = tuple(lens) if lens is not None else (0, 0.0, 0.0, 0.0)
+    lo = tuple(layout)[:4] if layout is not None else (0, 1, 1, 0)
+    _use_current_stream()
+    lib().stm_d_mux_overlay(_p(frame), _p(overlay), overlay.shape[0], overlay.shape[1], int(x0), int(y0), float(disparity),
+                            int(num_views), float(angle), int(ln[0]), float(ln[1]), float(ln[2]), float(ln[3]), int(lo[0]), int(lo[1]),
+                            int(lo[2]), int(lo[3]), frame.shape[0], frame.shape[1], frame.shape[2])
+
+
 def _out_size(interlaced, p):
     """(Hout, Wout) of a frame call's output: a BGR frame's first two dimensions, or -- under set_output's format 1 -- what the 2-D
     surface of (R + Hout / 2) x P holds; p.out_rows / p.out_cols, where set, say it outright (needed with a pitch beyond Wout)"""

@@ -266,6 +266,22 @@ def quilt_multiview(views, tiles_x, tiles_y, order, filter, out_rows, out_cols):
     return out
 
 
+def mux_overlay(frame, overlay, x0, y0, disparity, num_views, angle=18.43, lens=None, layout=None):
+    """stm_mux_overlay (an addition): the overlay (uint8 [rows][cols][4], premultiplied B, G, R, A) composited into a copy of the
+    finished frame (uint8 [Ho][Wo][E]) at view pixel (x0, y0) -- a pixel of the frame, or of every tile of a quilt -- and at the
+    end-to-end `disparity` (> 0 behind the screen, < 0 in front).  lens = (mode, pitch, slope, centre), None = the reference's
+    interlacer at `angle`; layout = (1, tiles_x, tiles_y, order) for a quilt, None = the interlaced frame.  Returns the frame."""
+    out = np.array(frame, dtype=np.uint8, order="C")
+    overlay, po = _u8(overlay)
+    assert out.ndim == 3 and overlay.ndim == 3 and overlay.shape[2] == 4
+    ln = tuple(lens) if lens is not None else (0, 0.0, 0.0, 0.0)
+    lo = tuple(layout)[:4] if layout is not None else (0, 1, 1, 0)
+    lib().stm_mux_overlay(out.ctypes.data_as(u8p), po, overlay.shape[0], overlay.shape[1], int(x0), int(y0), float(disparity),
+                          int(num_views), float(angle), int(ln[0]), float(ln[1]), float(ln[2]), float(ln[3]), int(lo[0]), int(lo[1]),
+                          int(lo[2]), int(lo[3]), out.shape[0], out.shape[1], out.shape[2])
+    return out
+
+
 def _frame_out(out_rows, out_cols, E):
     """the array a rendering frame call fills: the BGR frame, or -- under stm_set_output's format 1 -- the NV12 surface of
     (R + out_rows / 2) x P bytes (P = pitch or out_cols, R = uv_row or out_rows)"""

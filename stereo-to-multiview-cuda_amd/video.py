@@ -27,10 +27,11 @@ class FrameStream:
     reduced-resolution frame -- matched at h x w, the maps scaled up by 1 / disp_scale, the views rendered at full size -- and
     `stages` may then carry 0x1000 (the guided up-sampler); None = the full-resolution frame.  Not together with a packing.
     output = (1, matrix): the quilt comes out as NV12 (set_output), each frame uint8 [out_rows * 3 / 2][out_cols], the Y plane followed
-    by the interleaved UV plane; None = BGR.  Needs a layout."""
+    by the interleaved UV plane; None = BGR.  Needs a layout.  overlay = (max_rows, max_cols): the stream composites an overlay of up
+    to that size into its frames (set_overlay; .overlay() sets the one in force); None = none.  Not together with an NV12 output."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
-                 depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None):
+                 depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None, overlay=None):
         self.H, self.W = num_rows, num_cols
         self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
@@ -63,6 +64,28 @@ class FrameStream:
         if depth_auto is not None:
             self.set_depth_auto(*depth_auto)
             self.set_depth(2)
+        if overlay is not None:
+            self.set_overlay(*overlay)
+
+    def set_overlay(self, max_rows=0, max_cols=0):
+        """stm_stream_set_overlay: room for overlays of up to max_rows x max_cols pixels; (0, 0) = off.  Only before the first
+        submit; refused together with an NV12 output.  Raises ValueError where the library refuses."""
+        if int(lib().stm_stream_set_overlay(self._h, int(max_rows), int(max_cols))) != 0:
+            raise ValueError("stm_stream_set_overlay(%d, %d) refused: %s" % (max_rows, max_cols, lib().stm_last_error().decode()))
+
+    def overlay(self, bgra, x0=0, y0=0, disparity=0.0):
+        """stm_stream_overlay: the overlay every later submit composites, until the next call -- uint8 [rows][cols][4], B, G, R, A
+        with premultiplied alpha (premultiply converts straight alpha), its top-left corner at view pixel (x0, y0), at the
+        end-to-end `disparity` (> 0 behind the screen, < 0 in front) -- or None = none.  Callable between any two submits; the
+        array is reusable on return.  Raises ValueError where the library refuses."""
+        if bgra is None:
+            r = lib().stm_stream_overlay(self._h, None, 0, 0, 0, 0, 0.0)
+        else:
+            bgra = np.ascontiguousarray(bgra, dtype=np.uint8)
+            assert bgra.ndim == 3 and bgra.shape[2] == 4
+            r = lib().stm_stream_overlay(self._h, bgra.ctypes.data_as(u8p), bgra.shape[0], bgra.shape[1], int(x0), int(y0), float(disparity))
+        if int(r) != 0:
+            raise ValueError("stm_stream_overlay refused: %s" % lib().stm_last_error().decode())
 
     def set_depth(self, mode, gain=1.0, conv=0.0):
         """stm_stream_set_depth: the depth budget of the stream's frames (device_api.set_depth's arguments); the stream's own,
@@ -197,6 +220,17 @@ class FrameStream:
             pass
 
 
+def premultiply(bgra_straight):
+    """A straight-alpha overlay (uint8 [rows][cols][4], B, G, R, A) as the premultiplied one the library composites: each colour
+    byte becomes (c * a + 127) // 255 -- never above its alpha, exact at a = 0 and a = 255."""
+    a = np.asarray(bgra_straight, dtype=np.uint8)
+    assert a.ndim == 3 and a.shape[2] == 4
+    out = a.copy()
+    alpha = a[..., 3:4].astype(np.uint32)
+    out[..., :3] = ((a[..., :3].astype(np.uint32) * alpha + 127) // 255).astype(np.uint8)
+    return out
+
+
 def packed_frame_geometry(num_rows, num_cols, packing):
     """(Wsbs, rows_f) of the smallest frame that holds two eyes of num_rows x num_cols after unpacking (include/stm_hip.h,
     stm_demux_packed); packing = (packing, swap, filter, gap)"""
@@ -226,7 +260,8 @@ def _collect(fs, on_depth):
 
 
 def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None,
-                     depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None):
+                     depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None,
+                     overlay=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
@@ -235,7 +270,8 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
     budget; on_depth: called with (index, (gain, conv)) after every collected frame.  packing: FrameStream's; the frames are then packed
     ones; eye_shape = (num_rows, num_cols), the size of an unpacked eye, defaults to what a frame without spare columns holds.
     layout: FrameStream's (the interlaced output is then a quilt).  match: FrameStream's (h, w, disp_scale): the reduced-resolution frame.
-    output: FrameStream's (1, matrix): the quilt comes out as NV12, [out_rows * 3 / 2][out_cols]."""
+    output: FrameStream's (1, matrix): the quilt comes out as NV12, [out_rows * 3 / 2][out_cols].
+    overlay: (bgra, x0, y0, disparity), one premultiplied overlay composited into every frame of the sequence (FrameStream.overlay)."""
     fs = None
     pending = 0
     for sbs in frames:
@@ -244,7 +280,10 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
             cols = sbs.shape[1] // 2
             if packing is not None:
                 rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
-            fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output)
+            fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output,
+                             overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]))
+            if overlay is not None:
+                fs.overlay(*overlay)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:

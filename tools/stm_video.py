@@ -8,6 +8,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--nv12 ROWS COLS_SBS [--matrix M]] [--lens MODE PITCH SLOPE CENTRE]
                     [--depth GAIN CONV | --depth-auto LO HI [MAX_GAIN CLIP RATE]]
                     [--packing P SWAP FILTER GAP] [--quilt TX TY ORDER FILTER [--nv12-out MATRIX]] [--match H W SCALE [--guided-up]]
+                    [--overlay FILE.npy X0 Y0 DISPARITY]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -38,6 +39,10 @@ file from an earlier run is replaced) instead of being written as a BMP; <out wi
 --match H W SCALE (an addition): every frame is the reduced-resolution frame (stm_stream_set_match_size) -- the pair is matched at
 H x W, the maps are scaled up by 1 / SCALE and the views rendered at full size; <num disp> and <zero disp> then count pixels of the
 reduced pair.  --guided-up adds frame bit 0x1000, the guided up-sampler in place of the bilinear up-scale.  Excludes --packing.
+--overlay FILE.npy X0 Y0 DISPARITY (an addition): FILE.npy holds one overlay, uint8 [rows][cols][4] -- B, G, R, A with premultiplied
+alpha (video.premultiply converts straight alpha) -- composited into every frame of the sequence with its top-left corner at view pixel
+(X0, Y0) -- a pixel of the frame, or of every tile under --quilt -- and at the end-to-end DISPARITY in pixels: > 0 behind the screen,
+< 0 in front, 0 on it (stm_stream_overlay).  Excludes --nv12-out.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -135,6 +140,21 @@ def main(argv):
             return -1
         stages |= 0x1000
         argv.remove("--guided-up")
+    overlay = None
+    if "--overlay" in argv:
+        at = argv.index("--overlay")
+        try:
+            import numpy as np
+            pix = np.load(argv[at + 1])
+            overlay = (pix, int(argv[at + 2]), int(argv[at + 3]), float(argv[at + 4]))
+            if pix.dtype != np.uint8 or pix.ndim != 3 or pix.shape[2] != 4 or 0 in pix.shape or max(pix.shape[:2]) > 65535:
+                raise ValueError(pix.shape)
+            if max(abs(overlay[1]), abs(overlay[2])) > 65536 or not abs(overlay[3]) <= 4096.0 or nv12_out is not None:
+                raise ValueError(overlay[1:])
+        except (ValueError, IndexError, OSError):
+            print(__doc__)
+            return -1
+        del argv[at:at + 5]
     depth, depth_auto = None, None
     try:
         if "--depth" in argv:
@@ -189,7 +209,7 @@ def main(argv):
                                                        (lambda k, gc: print("frame %d: gain %.6g conv %.6g" % (k, gc[0], gc[1])))
                                                        if depth_auto is not None else None, packing,
                                                        layout=None if quilt is None else (1,) + quilt, match=match,
-                                                       output=None if nv12_out is None else (1, nv12_out)):
+                                                       output=None if nv12_out is None else (1, nv12_out), overlay=overlay):
         if yuv is not None:  # the frame is [out height * 3 / 2][out width]: the Y plane, then the interleaved UV plane
             yuv.write(inter.tobytes())
             video.write_disparities(out_dir, k, dl, dr)
