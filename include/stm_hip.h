@@ -187,6 +187,24 @@ int         stm_set_depth(int mode, float gain, float conv);
  * means scratch memory, with every frame fitted on its own.  A caller resets the history, for a scene cut, by zeroing `valid`.
  * Returns 0, or -1 with stm_last_error set and the old parameters in place. */
 int         stm_set_depth_auto(float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate, float *d_state);
+/* The calling thread's view antialiasing (an addition; stm_view_prefilter has the definition and the reason).  The depth budget above
+ * flattens a scene that exceeds the panel's range; this is the second remedy, band-limiting what stays off the screen plane.
+ * mode 0 = off (the default; the other arguments are ignored, and not one launch, argument or kernel of any call changes), 1 = on:
+ * every frame call that renders -- stm_adcensus_stm, stm_d_adcensus_stm, _t, _nv12, and _2 / _2s / _2t / _2nv12 in both flavours where
+ * they exist -- filters the left image by disp_l and the right image by disp_r, exactly as stm_d_view_prefilter would with the call's
+ * num_views, into fresh workspace, before it renders; whichever renderer the frame takes (the fused interlacer, every lens mode, the
+ * depth renderers, both quilt kernels with BGR or NV12 output, the un-fused forms of stm_set_agg_variant(200), whose end views are then
+ * the filtered images) is handed the filtered pair.  gain and conv: depth mode 0 filters with gain 1, conv 0; mode 1 with the setting;
+ * mode 2 with the state -- the fit runs first and the prefilter reads gain and conv on the device where the renderers read them.
+ * The unfiltered images (0x2000's history, _nv12's d_img_l / d_img_r) and the maps never change; an overlay is composited afterwards
+ * and is not blurred.  It is an output quality setting, not a stage: no `stages` bit belongs to it, and a frame call whose `stages`
+ * low byte is below 3 renders nothing and ignores it.
+ * Argument rules: mode 0 or 1; with mode 1 stm_view_prefilter's rules for strength, max_radius and gate.  Returns 0, or -1 with
+ * stm_last_error set and the thread's setting unchanged. */
+int         stm_set_antialias(int mode, float strength, int max_radius, float gate);
+/* out_mode = {mode, max_radius}, out = {strength, gate} as the last accepted stm_set_antialias left them ((0, 0) and (0, 0) if none
+ * was made, and after mode 0).  A frame stream's own setting is not visible here except during its submit. */
+void        stm_get_antialias(int out_mode[2], float out[2]);
 /* The calling thread's output geometry (an addition: the reference shows its views in one form only, sub-pixel interlaced).
  * layout 0 = the interlaced frame (the default; tiles_x, tiles_y, order and filter are ignored, and not one launch, argument or
  * kernel changes), 1 = a quilt: the views side by side as a grid of tiles, whole, for a display that interlaces with its own
@@ -962,6 +980,33 @@ void stm_depth_fit(float *disp_l, float *disp_r, int num_rows, int num_cols, flo
                    int clip_permille, float rate, float *state);
 void stm_d_depth_fit(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
                      int clip_permille, float rate, float *d_state);
+/* View antialiasing: the depth-adaptive prefilter of one image by its own map (an addition, the reference has none: each of its views
+ * is a pinhole image at one camera position s, while a lenticular lens shows a band about one view spacing wide.  A scene point of
+ * displayed end-to-end disparity e moves e / (N - 1) pixels between adjacent views, so detail finer than that step aliases between
+ * views: doubled edges, crawling texture).  For locally constant depth the band limit along the view axis is a horizontal box blur
+ * whose width grows with the pixel's displayed disparity.  img (num_rows x num_cols x elem_sz, B G R first) is filtered by disp (f32,
+ * num_rows x num_cols, delta = d - zero_disp): the left image by disp_l, the right image by disp_r.  img_out must not overlap img.
+ * Per pixel x of a row -- f32, one operation per line, no contraction, C fabsf / fminf:
+ *   k16 = (float)((double)strength * 8.0 / (double)(num_views - 1))                                  (host, once)
+ *   p = gain * delta[x];  e = p - conv;  a = fabsf(e)           (e: the displayed disparity, stm_set_depth's gain * delta - conv)
+ *   H = 0 if a is not finite, else (int)(fminf(a * k16, (float)(16 * max_radius)) + 0.5f)            per-side extension in 1/16 px
+ *   K = (H + 15) >> 4
+ *   for k = 1 .. K:  w_k = min(16, H - 16 * (k - 1))
+ *       for j in (x - k, x + k):  jc = clamp(j, 0, num_cols - 1)
+ *           the tap jc is USED iff fabsf(delta[jc] - delta[x]) <= gate                               (false for NaN)
+ *   T      = 16 + the sum of the used taps' w_k
+ *   out[c] = (16 * img[x][c] + the sum of the used w_k * img[jc][c] + (T >> 1)) / T                  integer division, c = 0, 1, 2
+ * H = 0 copies the pixel: content on the displayed screen plane is byte-identical.  With every tap used the box is
+ * 1 + strength * |e| / (N - 1) pixels wide in all -- continuous at 0, and it never sharpens.  The gate keeps a blurred pixel from
+ * pulling in colours across a depth edge (the usual leak of a gather blur).  T <= 528 and every numerator <= 255 * 528 + 264.
+ * Bytes of a pixel past the third: the device flavour leaves them as they are in d_img_out, the host flavour returns them 0.
+ * Argument rules: num_rows, num_cols >= 1, elem_sz >= 3, num_views >= 2; strength finite in [0, 8]; max_radius in 1 .. 16; gate finite
+ * and >= 0; gain, conv by stm_set_depth's mode-1 rules; no null pointer; img_out and img share no byte.  Violations fail through
+ * stm_last_error before anything is launched or written.  Parity is against a numpy statement of these lines (parity unpinned). */
+void stm_view_prefilter(unsigned char *img_out, const unsigned char *img, const float *disp, int num_rows, int num_cols, int elem_sz,
+                        int num_views, float strength, int max_radius, float gate, float gain, float conv);
+void stm_d_view_prefilter(unsigned char *d_img_out, const unsigned char *d_img, const float *d_disp, int num_rows, int num_cols,
+                          int elem_sz, int num_views, float strength, int max_radius, float gate, float gain, float conv);
 /* d_tx_scale.h:17-18  d_tx_scale (d_tx_scale.cu:83-121): bilinear image resize; HOST pointers despite the name */
 void stm_d_tx_scale(unsigned char *img_in, unsigned char *img_out, int in_rows, int in_cols, int out_rows, int out_cols,
                     int elem_sz);
@@ -1059,6 +1104,10 @@ int   stm_stream_overlay(void *stream, const unsigned char *overlay, int ov_rows
  * Return 0, or -1 with stm_last_error set. */
 int   stm_stream_set_depth(void *stream, int mode, float gain, float conv);
 int   stm_stream_set_depth_auto(void *stream, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate);
+/* the view antialiasing of the stream's frames (stm_set_antialias's rules; the default is mode 0).  As with the depth budget the
+ * stream keeps its own copy and installs it only around its frame calls, so the prefilter is part of the slots' captured graphs and
+ * replays with them.  Only before the first submit.  Returns 0, or -1 with stm_last_error set and the stream unchanged. */
+int   stm_stream_set_antialias(void *stream, int mode, float strength, int max_radius, float gate);
 /* out = {gain, conv} applied to the most recently collected frame: in mode 2 the state as that frame's fit left it (a 16-byte copy
  * taken on the frame's compute stream and downloaded with its results, so the next frame's update cannot race it), in mode 1 the
  * setting, in mode 0 {1, 0}.  Returns 0, or -1 if no frame has been collected yet. */

@@ -965,6 +965,52 @@ void stm_depth_fit(float *disp_l, float *disp_r, int num_rows, int num_cols, flo
     sync();
 }
 
+// =============================================================== view antialiasing: the prefilter as a stage
+// (an addition, the reference has none: its views are pinhole images whatever the lens shows of them)
+static bool prefilter_args_ok(const char *fn, const unsigned char *img_out, const unsigned char *img, const float *disp, int num_rows,
+                              int num_cols, int elem_sz, int num_views, float strength, int max_radius, float gate, float gain, float conv)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}, {"num_views", num_views, 2}})) return false;
+    if (!antialias_params_ok(fn, strength, max_radius, gate)) return false;
+    if (!depth_params_ok(fn, 1, gain, conv)) return false;
+    char msg[160];
+    if (!img_out || !img || !disp) {
+        snprintf(msg, sizeof msg, "%s: img_out, img and disp must not be null", fn);
+        fail(msg, "img_out, img, disp", __FILE__, __LINE__);
+        return false;
+    }
+    const size_t bytes = (size_t)num_rows * num_cols * elem_sz;
+    if (bytes_overlap(img_out, bytes, img, bytes)) { // a pixel's taps are its neighbours' inputs
+        snprintf(msg, sizeof msg, "%s: img_out must not overlap img", fn);
+        fail(msg, "img_out", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
+void stm_d_view_prefilter(unsigned char *d_img_out, const unsigned char *d_img, const float *d_disp, int num_rows, int num_cols, int elem_sz,
+                          int num_views, float strength, int max_radius, float gate, float gain, float conv)
+{
+    if (!prefilter_args_ok("d_view_prefilter", d_img_out, d_img, d_disp, num_rows, num_cols, elem_sz, num_views, strength, max_radius, gate, gain,
+                           conv))
+        return;
+    launch_view_prefilter(1, &d_img_out, &d_img, &d_disp, num_rows, num_cols, elem_sz, num_views, strength, max_radius, gate, gain, conv, nullptr);
+}
+void stm_view_prefilter(unsigned char *img_out, const unsigned char *img, const float *disp, int num_rows, int num_cols, int elem_sz,
+                        int num_views, float strength, int max_radius, float gate, float gain, float conv)
+{
+    if (!prefilter_args_ok("view_prefilter", img_out, img, disp, num_rows, num_cols, elem_sz, num_views, strength, max_radius, gate, gain, conv))
+        return;
+    const size_t HW = (size_t)num_rows * num_cols;
+    Workspace::begin(2 * HW * elem_sz + 4 * HW + 8192);
+    const u8 *i = up(img, HW * elem_sz);
+    const float *d = up(disp, HW);
+    u8 *o = Workspace::get<u8>(HW * elem_sz);
+    if (elem_sz > 3) STM_CHECK(hipMemsetAsync(o, 0, HW * elem_sz, stream())); // bytes past the third come back 0
+    launch_view_prefilter(1, &o, &i, &d, num_rows, num_cols, elem_sz, num_views, strength, max_radius, gate, gain, conv, nullptr);
+    down(img_out, o, HW * elem_sz);
+    sync();
+}
+
 // =============================================================== mux
 void stm_d_mux_multiview(unsigned char **d_views, unsigned char *d_out_data, int num_views, float angle, int in_rows,
                          int in_cols, int out_rows, int out_cols, int elem_sz)
@@ -1553,17 +1599,35 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
     // Under stm_set_output's format 1 d_interlaced is an NV12 surface (screened by frame_layout_ok) and the quilt's kernels convert the
     // pixels they render; 200 with depth mode 0 writes the BGR quilt into the workspace and converts that (stm_k_mux_nv12).
     const Layout lo = layout();
+    // the reference's view assignment from `angle`, which the depth renderer of the interlaced frame takes: screened before the fit
+    float inv_y = 0.0f;
+    int ymod = 1;
+    if (lo.layout == 0 && dp.mode != 0 && ln.mode == 0 && !mux_geom_ok(N, angle, elem_sz, nullptr, &inv_y, &ymod)) return;
+    // mode 2's fit, ahead of everything that reads gain and conv from the state: the prefilter below and the renderer
+    float *state = nullptr;
+    if (dp.mode == 2) {
+        uint32_t *hist = Workspace::get<uint32_t>(4096);
+        state = dp.d_state ? dp.d_state : Workspace::get<float>(4);
+        launch_depth_fit(state, hist, d_disp_l, d_disp_r, H, W, dp.disp_lo, dp.disp_hi, dp.max_gain, dp.clip_permille, dp.rate,
+                         dp.d_state == nullptr);
+    }
+    // view antialiasing (stm_set_antialias): both images filtered by their own maps into fresh workspace, and every renderer below
+    // takes the filtered pair -- the caller's images (0x2000's history, _nv12's outputs) and the maps stay as they are.  The displayed
+    // disparity of a pixel is gain * delta - conv under a depth budget, delta itself without one
+    const Antialias aa = antialias();
+    if (aa.mode == 1) {
+        u8 *flt[2] = {Workspace::get<u8>(IMG), Workspace::get<u8>(IMG)};
+        const u8 *src[2] = {img_l, img_r};
+        const float *dsp[2] = {d_disp_l, d_disp_r};
+        launch_view_prefilter(2, flt, src, dsp, H, W, elem_sz, N, aa.strength, aa.max_radius, aa.gate, dp.mode == 1 ? dp.gain : 1.0f,
+                              dp.mode == 1 ? dp.conv : 0.0f, state);
+        img_l = flt[0];
+        img_r = flt[1];
+    }
     if (lo.layout == 1) {
         const Output of = output();
         const Nv12Out surf = of.format == 1 ? nv12_out_surface(d_interlaced, of, Hout, Wout) : Nv12Out{};
         const Nv12Out *nv = of.format == 1 ? &surf : nullptr;
-        float *state = nullptr;
-        if (dp.mode == 2) {
-            uint32_t *hist = Workspace::get<uint32_t>(4096);
-            state = dp.d_state ? dp.d_state : Workspace::get<float>(4);
-            launch_depth_fit(state, hist, d_disp_l, d_disp_r, H, W, dp.disp_lo, dp.disp_hi, dp.max_gain, dp.clip_permille, dp.rate,
-                             dp.d_state == nullptr);
-        }
         if (dp.mode == 0 && (agg_variant() / 100) % 10 == 2) {
             u8 *views_mem = Workspace::get<u8>((size_t)N * IMG);
             launch_view_synth_all(views_mem, IMG, N, img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, H, W, elem_sz, linear);
@@ -1579,28 +1643,6 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
         return;
     }
     if (dp.mode != 0) {
-        float inv_y = 0.0f;
-        int ymod = 1;
-        if (ln.mode == 0) {
-            const float yi = mux_y_interval(N, angle, elem_sz);
-            if (!(fabsf(yi) < 1.0e9f)) {
-                fail("mux_multiview: y_interval is not finite (tan(angle) == 0 or angle is not a number)", "angle", __FILE__, __LINE__);
-                return;
-            }
-            ymod = (int)roundf(yi);
-            if (ymod == 0) {
-                fail("mux_multiview: round(y_interval) == 0 (angle too steep)", "ymod", __FILE__, __LINE__);
-                return;
-            }
-            inv_y = 1.0f / yi;
-        }
-        float *state = nullptr;
-        if (dp.mode == 2) {
-            uint32_t *hist = Workspace::get<uint32_t>(4096);
-            state = dp.d_state ? dp.d_state : Workspace::get<float>(4);
-            launch_depth_fit(state, hist, d_disp_l, d_disp_r, H, W, dp.disp_lo, dp.disp_hi, dp.max_gain, dp.clip_permille, dp.rate,
-                             dp.d_state == nullptr);
-        }
         launch_synth_mux_depth(img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, d_interlaced, N, ln, inv_y, ymod, dp.gain, dp.conv,
                                state, H, W, Hout, Wout, elem_sz, linear);
         return;
@@ -1696,7 +1738,8 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
     const size_t V = pq_volume_floats(num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
     const Packing pack = packing(); // a packed frame (stm_set_packing): the caller has screened its geometry
     Workspace::begin(((stages & 0x100) ? 13 : 4) * V * 4 + (size_t)(N + 2 + (pack.on() && hist && !nv ? 2 : 0)) * IMG + 168 * HW + (1u << 20) +
-                     (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0)); // the un-fused NV12 frame's BGR quilt
+                     (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0) + // the un-fused NV12 frame's BGR quilt
+                     (antialias().mode == 1 ? 2 * IMG + 512 : 0));                                  // the prefiltered pair
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     uint32_t *pre[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1978,7 +2021,8 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
     const bool linwarp = (stages & 0x800) != 0;                                                             // in the full-size render
     const bool guided = (stages & 0x1000) != 0; // the up-scale between the two: stm_disp_upsample instead of tx_disp_scale
     Workspace::begin((hslo ? 13 : 4) * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 32 * hw + (1u << 20) + // HSLO: as d_adcensus_stm
-                     (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0));
+                     (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0) +
+                     (antialias().mode == 1 ? 2 * IMG + 512 : 0)); // the prefiltered pair
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     u8 *low_l = Workspace::get<u8>(hw * elem_sz), *low_r = Workspace::get<u8>(hw * elem_sz);

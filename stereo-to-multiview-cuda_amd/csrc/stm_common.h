@@ -378,6 +378,23 @@ void frame_overlay(u8 *d_frame, const Overlay &ov, const Lens &ln, const Layout 
 // under ln (ln.mode 0: the reference's view assignment from y_interval, inv_y_interval and ymod), 1: a quilt.  Screened by the caller
 void launch_overlay(u8 *out, const u8 *ov, int ov_rows, int ov_cols, int x0, int y0, float disparity, int N, const Lens &ln,
                     float y_interval, float inv_y_interval, int ymod, const Layout &lo, int Hout, int Wout, int elem_sz);
+// View antialiasing (stm_set_antialias, include/stm_hip.h): mode 0 = off, 1 = every rendering frame call filters both images by
+// their own maps (stm_view_prefilter's rule) before it renders from them.  One per host thread, next to the depth budget; a frame
+// stream installs its own copy around its frame calls (stm_stream_set_antialias).
+struct Antialias {
+    int mode;
+    float strength;
+    int max_radius;
+    float gate;
+};
+Antialias antialias();
+void set_antialias(const Antialias &a);
+// the rules of the three parameters (stm_hip.h, stm_view_prefilter); false with the error recorded
+bool antialias_params_ok(const char *fn, float strength, int max_radius, float gate);
+// the prefilter (stm_kernels_prefilter.hip): out[i] = in[i] (H x W x elem_sz) filtered by disp[i], i < nimg (1 or 2) in one launch;
+// state != nullptr: gain and conv are read from state[1] and state[2] on the device.  Screened by the caller
+void launch_view_prefilter(int nimg, u8 *const *out, const u8 *const *in, const float *const *disp, int H, int W, int elem_sz, int num_views,
+                           float strength, int max_radius, float gate, float gain, float conv, const float *state);
 // the measurement (stm_kernels_depth.hip): both maps into the 4096-bin histogram `hist` (scratch), the fit, the update of `state`
 // (four floats); fresh: the state's history is ignored
 void launch_depth_fit(float *state, uint32_t *hist, const float *disp_l, const float *disp_r, int H, int W, float disp_lo, float disp_hi,

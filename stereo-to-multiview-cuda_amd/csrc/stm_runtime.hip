@@ -3,6 +3,7 @@
 #include "stm_common.h"
 #include "../../include/stm_hip.h"
 
+#include <float.h>
 #include <math.h>
 #include <cmath>
 #include <stdio.h>
@@ -446,6 +447,28 @@ bool depth_params_ok(const char *fn, int mode, float gain, float conv)
     fail(msg, arg, __FILE__, __LINE__);
     return false;
 }
+// the calling thread's view antialiasing (stm_set_antialias)
+static thread_local Antialias g_antialias = {0, 0.0f, 0, 0.0f};
+Antialias antialias() { return g_antialias; }
+void set_antialias(const Antialias &a) { g_antialias = a; }
+bool antialias_params_ok(const char *fn, float strength, int max_radius, float gate)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (!(strength >= 0.0f && strength <= 8.0f)) { // NaN fails the comparison
+        snprintf(msg, sizeof msg, "%s: antialias strength = %g, must be in [0, 8]", fn, (double)strength);
+        arg = "strength";
+    } else if (max_radius < 1 || max_radius > 16) {
+        snprintf(msg, sizeof msg, "%s: antialias max_radius = %d, must be in 1 .. 16", fn, max_radius);
+        arg = "max_radius";
+    } else if (!(gate >= 0.0f && gate <= FLT_MAX)) {
+        snprintf(msg, sizeof msg, "%s: antialias gate = %g, must be finite and >= 0", fn, (double)gate);
+        arg = "gate";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
 bool depth_auto_params_ok(const char *fn, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate)
 {
     char msg[200];
@@ -674,6 +697,25 @@ int stm_set_depth_auto(float disp_lo, float disp_hi, float max_gain, int clip_pe
     d.disp_lo = disp_lo; d.disp_hi = disp_hi; d.max_gain = max_gain; d.clip_permille = clip_permille; d.rate = rate; d.d_state = d_state;
     stm::set_depth(d);
     return 0;
+}
+int stm_set_antialias(int mode, float strength, int max_radius, float gate)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (mode != 0 && mode != 1) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "set_antialias: mode = %d, must be 0 (off) or 1 (on)", mode);
+        stm::fail(msg, "mode", __FILE__, __LINE__);
+        return -1; // the thread's setting stays as it was
+    }
+    if (mode == 1 && !stm::antialias_params_ok("set_antialias", strength, max_radius, gate)) return -1;
+    stm::set_antialias(mode == 0 ? stm::Antialias{0, 0.0f, 0, 0.0f} : stm::Antialias{1, strength, max_radius, gate});
+    return 0;
+}
+void stm_get_antialias(int out_mode[2], float out[2])
+{
+    const stm::Antialias a = stm::antialias();
+    out_mode[0] = a.mode; out_mode[1] = a.max_radius;
+    out[0] = a.strength; out[1] = a.gate;
 }
 void stm_set_agg_variant(int v)
 {

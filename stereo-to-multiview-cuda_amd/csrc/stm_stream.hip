@@ -59,6 +59,7 @@ struct FrameStream {
     int rows_f = 0;                      // the rows of an input frame: H, or what the packing makes of it
     int match_h = 0, match_w = 0;        // stm_stream_set_match_size: the size the pair is matched at (0, 0 = off: the full-resolution frame)
     float match_scale = 1.0f;            // ... and the reduced frame's disp_scale
+    stm::Antialias antialias = {0, 0.0f, 0, 0.0f}; // stm_stream_set_antialias: the stream's own view antialiasing
     float *d_depth_state = nullptr; // mode 2: the state every frame updates, at one address for both slots' graphs
     int ov_max_rows = 0, ov_max_cols = 0; // stm_stream_set_overlay: the largest overlay the slots' copies hold ((0, 0) = off)
     u8 *ov_pixels = nullptr;              // stm_stream_overlay: the pixels of the overlay in force (host memory of the stream's own)
@@ -91,6 +92,12 @@ struct DepthScope {
     stm::Depth saved;
     explicit DepthScope(const stm::Depth &d) : saved(stm::depth()) { stm::set_depth(d); }
     ~DepthScope() { stm::set_depth(saved); }
+};
+
+struct AntialiasScope {
+    stm::Antialias saved;
+    explicit AntialiasScope(const stm::Antialias &a) : saved(stm::antialias()) { stm::set_antialias(a); }
+    ~AntialiasScope() { stm::set_antialias(saved); }
 };
 
 // the calling thread's overlay (stm_set_overlay) never reaches a stream's frames: the stream composites its own after the frame call
@@ -535,6 +542,26 @@ int stm_stream_set_depth(void *h, int mode, float gain, float conv)
     f->depth.d_state = f->d_depth_state;
     return 0;
 }
+// The view antialiasing of every frame of the stream (stm_set_antialias's rules; the default is mode 0).  Kept and installed like the
+// depth budget, so the prefilter is part of the slots' captured graphs.  Only before the first submit.
+int stm_stream_set_antialias(void *h, int mode, float strength, int max_radius, float gate)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (mode != 0 && mode != 1) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "stream_set_antialias: mode = %d, must be 0 (off) or 1 (on)", mode);
+        stm::fail(msg, "mode", __FILE__, __LINE__);
+        return -1;
+    }
+    if (mode == 1 && !stm::antialias_params_ok("stream_set_antialias", strength, max_radius, gate)) return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_antialias: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    f->antialias = mode == 0 ? stm::Antialias{0, 0.0f, 0, 0.0f} : stm::Antialias{1, strength, max_radius, gate};
+    return 0;
+}
 int stm_stream_set_depth_auto(void *h, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate)
 {
     FrameStream *f = (FrameStream *)h;
@@ -604,6 +631,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     LayoutScope layout_scope(f->layout);
     OutputScope output_scope(f->output);
     DepthScope depth_scope(f->depth);
+    AntialiasScope antialias_scope(f->antialias);
     PackingScope packing_scope(f->packing);
     OverlayOffScope overlay_scope;
     stm_set_stream(s.s_compute);

@@ -318,6 +318,35 @@ def d_depth_fit(disp_l, disp_r, disp_lo, disp_hi, max_gain, clip_permille, rate,
                           _p(state))
 
 
+def set_antialias(mode, strength=1.0, max_radius=8, gate=1.0):
+    """stm_set_antialias: the calling thread's view antialiasing.  mode 0 = off (the default), 1 = every rendering frame call
+    filters both images by their own maps before it renders from them (d_view_prefilter's rule): a horizontal box of
+    1 + strength * |displayed disparity| / (N - 1) pixels, at most max_radius (1 .. 16) pixels to a side, whose taps are used only
+    where the map stays within `gate` of the pixel's own value.  Raises ValueError where the library refuses."""
+    if int(lib().stm_set_antialias(int(mode), float(strength), int(max_radius), float(gate))) != 0:
+        raise ValueError("stm_set_antialias(%d, %g, %d, %g) refused: %s" % (mode, strength, max_radius, gate, lib().stm_last_error().decode()))
+
+
+def get_antialias():
+    """stm_get_antialias: the calling thread's (mode, strength, max_radius, gate) as the library holds it"""
+    m = (C.c_int * 2)()
+    v = (C.c_float * 2)()
+    lib().stm_get_antialias(m, C.cast(v, f32p))
+    return int(m[0]), float(v[0]), int(m[1]), float(v[1])
+
+
+def d_view_prefilter(out, img, disp, num_views, strength=1.0, max_radius=8, gate=1.0, gain=1.0, conv=0.0):
+    """stm_d_view_prefilter: img (uint8 [H][W][E] on the GPU) filtered by its own map disp (float32 [H][W]) into out, which must not
+    overlap img; only bytes 0 .. 2 of a pixel are written.  gain, conv: the depth budget the views are rendered with (set_depth)."""
+    H, W, E = img.shape
+    for t in (out, img):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    assert disp.is_cuda and disp.dtype == torch.float32 and disp.is_contiguous() and disp.shape == (H, W)
+    _use_current_stream()
+    lib().stm_d_view_prefilter(_p(out), _p(img), _p(disp), H, W, E, int(num_views), float(strength), int(max_radius), float(gate),
+                               float(gain), float(conv))
+
+
 def d_mux_multiview_lens(views, out, mode, pitch, slope, centre):
     """stm_d_mux_multiview_lens: the views (a list of N uint8 [H][W][E] tensors on the GPU, views[0] = the right image ...
     views[N - 1] = the left image) interlaced into out (uint8 [Ho][Wo][E], only the first three bytes of a pixel are written)

@@ -381,6 +381,21 @@ def depth_fit(disp_l, disp_r, disp_lo, disp_hi, max_gain=1.0, clip_permille=20, 
     return st
 
 
+def view_prefilter(img, disp, num_views, strength=1.0, max_radius=8, gate=1.0, gain=1.0, conv=0.0):
+    """View antialiasing (stm_view_prefilter; an addition, the reference's views are pinhole images): img [H][W][E] filtered along
+    its rows by its own map disp [H][W] -- a box of 1 + strength * |gain * disp - conv| / (num_views - 1) pixels, at most max_radius
+    to a side, whose taps are used only where the map stays within `gate` of the pixel's own value.  Returns the [H][W][E] image
+    (bytes of a pixel past the third are 0); nothing passed in is modified."""
+    img, pi = _u8(img)
+    disp, pd = _f32(disp)
+    H, W, E = img.shape
+    assert disp.shape == (H, W)
+    out = np.zeros((H, W, E), np.uint8)
+    lib().stm_view_prefilter(out.ctypes.data_as(u8p), pi, pd, H, W, E, int(num_views), float(strength), int(max_radius), float(gate),
+                             float(gain), float(conv))
+    return out
+
+
 def tx_scale(img, out_rows, out_cols):
     """d_tx_scale.h:17-18 (bilinear resize)."""
     img, pi = _u8(img)

@@ -28,10 +28,13 @@ class FrameStream:
     `stages` may then carry 0x1000 (the guided up-sampler); None = the full-resolution frame.  Not together with a packing.
     output = (1, matrix): the quilt comes out as NV12 (set_output), each frame uint8 [out_rows * 3 / 2][out_cols], the Y plane followed
     by the interleaved UV plane; None = BGR.  Needs a layout.  overlay = (max_rows, max_cols): the stream composites an overlay of up
-    to that size into its frames (set_overlay; .overlay() sets the one in force); None = none.  Not together with an NV12 output."""
+    to that size into its frames (set_overlay; .overlay() sets the one in force); None = none.  Not together with an NV12 output.
+    antialias = (strength, max_radius, gate): view antialiasing (set_antialias mode 1) -- both images filtered by their own maps
+    before the views are rendered from them; None = off."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
-                 depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None, overlay=None):
+                 depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None, overlay=None,
+                 antialias=None):
         self.H, self.W = num_rows, num_cols
         self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
@@ -66,6 +69,16 @@ class FrameStream:
             self.set_depth(2)
         if overlay is not None:
             self.set_overlay(*overlay)
+        if antialias is not None:
+            self.set_antialias(1, *antialias)
+
+    def set_antialias(self, mode, strength=1.0, max_radius=8, gate=1.0):
+        """stm_stream_set_antialias: the view antialiasing of the stream's frames (device_api.set_antialias's arguments); the
+        stream's own, independent of the calling thread's; only before the first submit.  Raises ValueError where the library
+        refuses."""
+        if int(lib().stm_stream_set_antialias(self._h, int(mode), float(strength), int(max_radius), float(gate))) != 0:
+            raise ValueError("stm_stream_set_antialias(%d, %g, %d, %g) refused: %s"
+                             % (mode, strength, max_radius, gate, lib().stm_last_error().decode()))
 
     def set_overlay(self, max_rows=0, max_cols=0):
         """stm_stream_set_overlay: room for overlays of up to max_rows x max_cols pixels; (0, 0) = off.  Only before the first
@@ -261,7 +274,7 @@ def _collect(fs, on_depth):
 
 def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None,
                      depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None,
-                     overlay=None):
+                     overlay=None, antialias=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
@@ -271,7 +284,8 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
     ones; eye_shape = (num_rows, num_cols), the size of an unpacked eye, defaults to what a frame without spare columns holds.
     layout: FrameStream's (the interlaced output is then a quilt).  match: FrameStream's (h, w, disp_scale): the reduced-resolution frame.
     output: FrameStream's (1, matrix): the quilt comes out as NV12, [out_rows * 3 / 2][out_cols].
-    overlay: (bgra, x0, y0, disparity), one premultiplied overlay composited into every frame of the sequence (FrameStream.overlay)."""
+    overlay: (bgra, x0, y0, disparity), one premultiplied overlay composited into every frame of the sequence (FrameStream.overlay).
+    antialias: FrameStream's (strength, max_radius, gate): view antialiasing of every frame."""
     fs = None
     pending = 0
     for sbs in frames:
@@ -281,7 +295,7 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
             if packing is not None:
                 rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
             fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output,
-                             overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]))
+                             overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]), antialias=antialias)
             if overlay is not None:
                 fs.overlay(*overlay)
             if temporal is not None:

@@ -7,6 +7,7 @@ source, cost slice, aggregated slice, disparity, outliers, occlusion mask, every
 usage: stm_image.py <left.bmp> <right.bmp> <ad coeff> <census coeff> <ndisp> <zerodisp> <ucd> <lcd> <usd> <lsd>
                     <num views> <angle> <out width> <out height> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel]
                     [--linear-warp] [--lens MODE PITCH SLOPE CENTRE] [--quilt TX TY ORDER FILTER]
+                    [--antialias STRENGTH MAX_RADIUS GATE]
 
 --interp (an addition, off by default): the outlier interpolation (host_api.dr_interp) of both maps after region voting, each on
 its own image and outlier map, before --subpixel.
@@ -20,7 +21,10 @@ PITCH sub-pixels per lens, SLOPE sub-pixels of lens shift per output row, CENTRE
 in the frame calls only (stm_video.py).
 --quilt TX TY ORDER FILTER (an addition): the views tiled whole into the output frame (host_api.quilt_multiview: <num views> = TX *
 TY tiles; ORDER bit 0 = tile rows bottom-up, bit 1 = tile 0 holds the leftmost camera; FILTER 0 = the reference's four-neighbour
-sampler, 1 = the area average) instead of interlaced; <angle> is then ignored.  Excludes --lens."""
+sampler, 1 = the area average) instead of interlaced; <angle> is then ignored.  Excludes --lens.
+--antialias STRENGTH MAX_RADIUS GATE (an addition): view antialiasing (host_api.view_prefilter) -- before the views are rendered each
+image is blurred along its rows by its own final map: a box of 1 + STRENGTH * |disparity| / (<num views> - 1) pixels (STRENGTH in
+[0, 8]), at most MAX_RADIUS (1 .. 16) pixels to a side, using only neighbours whose disparity lies within GATE (>= 0) of the pixel's."""
 import os
 import sys
 
@@ -52,6 +56,17 @@ def main(argv):
             return -1
         lens = (int(argv[at + 1]), float(argv[at + 2]), float(argv[at + 3]), float(argv[at + 4]))
         del argv[at:at + 5]
+    antialias = None
+    if "--antialias" in argv:
+        at = argv.index("--antialias")
+        try:
+            antialias = (float(argv[at + 1]), int(argv[at + 2]), float(argv[at + 3]))
+            if not (0.0 <= antialias[0] <= 8.0 and 1 <= antialias[1] <= 16 and 0.0 <= antialias[2] < float("inf")):
+                raise ValueError(antialias)
+        except (ValueError, IndexError):
+            print(__doc__)
+            return -1
+        del argv[at:at + 4]
     if len(argv) not in (17, 18):
         print(__doc__)
         return -1
@@ -92,7 +107,9 @@ def main(argv):
     ml, mr = api.dibr_occl_to_mask(occl_l, occl_r)                        # :266
     wr("mask_l", (ml * 255).astype(np.uint8)); wr("mask_r", (mr * 255).astype(np.uint8))
     dbm = api.dibr_dbm_lin if linear_warp else api.dibr_dbm
-    views = [R]                                                           # :268-272: views[0] = right, views[N-1] = left
+    if antialias is not None:  # every view, the two end views included, from the prefiltered pair
+        L, R = api.view_prefilter(L, dl, N, *antialias), api.view_prefilter(R, dr, N, *antialias)
+    views = [R]                                                          # :268-272: views[0] = right, views[N-1] = left
     for v in range(1, N - 1):
         shift = float(np.float32(1.0 - (1.0 * np.float32(v)) / (np.float32(N) - 1.0)))   # :281
         views.append(dbm(L, R, dl, dr, occl_l, occl_r, ml, mr, shift))                    # :282

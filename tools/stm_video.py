@@ -8,7 +8,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--nv12 ROWS COLS_SBS [--matrix M]] [--lens MODE PITCH SLOPE CENTRE]
                     [--depth GAIN CONV | --depth-auto LO HI [MAX_GAIN CLIP RATE]]
                     [--packing P SWAP FILTER GAP] [--quilt TX TY ORDER FILTER [--nv12-out MATRIX]] [--match H W SCALE [--guided-up]]
-                    [--overlay FILE.npy X0 Y0 DISPARITY]
+                    [--overlay FILE.npy X0 Y0 DISPARITY] [--antialias STRENGTH MAX_RADIUS GATE]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -43,6 +43,10 @@ reduced pair.  --guided-up adds frame bit 0x1000, the guided up-sampler in place
 alpha (video.premultiply converts straight alpha) -- composited into every frame of the sequence with its top-left corner at view pixel
 (X0, Y0) -- a pixel of the frame, or of every tile under --quilt -- and at the end-to-end DISPARITY in pixels: > 0 behind the screen,
 < 0 in front, 0 on it (stm_stream_overlay).  Excludes --nv12-out.
+--antialias STRENGTH MAX_RADIUS GATE (an addition): view antialiasing (stm_stream_set_antialias) -- before the views are rendered both
+images are blurred along their rows by a box of 1 + STRENGTH * |displayed disparity| / (<num views> - 1) pixels (STRENGTH in [0, 8],
+1 = one view spacing), at most MAX_RADIUS (1 .. 16) pixels to a side, using only neighbours whose disparity lies within GATE (>= 0) of
+the pixel's own.  Content on the screen plane stays byte-identical; combines with every other option.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -185,6 +189,17 @@ def main(argv):
     except (ValueError, IndexError):
         print(__doc__)
         return -1
+    antialias = None
+    if "--antialias" in argv:
+        at = argv.index("--antialias")
+        try:
+            antialias = (float(argv[at + 1]), int(argv[at + 2]), float(argv[at + 3]))
+            if not (0.0 <= antialias[0] <= 8.0 and 1 <= antialias[1] <= 16 and 0.0 <= antialias[2] < float("inf")):
+                raise ValueError(antialias)
+        except (ValueError, IndexError):
+            print(__doc__)
+            return -1
+        del argv[at:at + 4]
     if len(argv) not in (16, 17):
         print(__doc__)
         return -1
@@ -209,7 +224,8 @@ def main(argv):
                                                        (lambda k, gc: print("frame %d: gain %.6g conv %.6g" % (k, gc[0], gc[1])))
                                                        if depth_auto is not None else None, packing,
                                                        layout=None if quilt is None else (1,) + quilt, match=match,
-                                                       output=None if nv12_out is None else (1, nv12_out), overlay=overlay):
+                                                       output=None if nv12_out is None else (1, nv12_out), overlay=overlay,
+                                                       antialias=antialias):
         if yuv is not None:  # the frame is [out height * 3 / 2][out width]: the Y plane, then the interleaved UV plane
             yuv.write(inter.tobytes())
             video.write_disparities(out_dir, k, dl, dr)
