@@ -205,6 +205,35 @@ int         stm_set_antialias(int mode, float strength, int max_radius, float ga
 /* out_mode = {mode, max_radius}, out = {strength, gate} as the last accepted stm_set_antialias left them ((0, 0) and (0, 0) if none
  * was made, and after mode 0).  A frame stream's own setting is not visible here except during its submit. */
 void        stm_get_antialias(int out_mode[2], float out[2]);
+/* The calling thread's vertical alignment of the pair (an addition: the reference takes rectified studio masters, and every matcher
+ * here searches along image rows.  A pitch, roll or focal-length difference between two lenses leaves a vertical offset between the
+ * eyes that is constant, linear across the width, or linear down the height; a few pixels of it send AD-Census to the wrong
+ * disparity on every horizontal edge).  mode 0 = off (the default: not one launch, argument or kernel of any call changes),
+ * 1 = manual (the field a, b, c), 2 = automatic (the field measured on every frame on the device: stm_set_align_auto, stm_align_fit).
+ * The field is dy(x, y) = a + b u + c v with u = x - (W-1)/2, v = y - (H-1)/2 on one unpacked eye of H x W pixels; the left eye is the
+ * reference, and the aligned right eye at (y, x) is the right eye sampled at row y + dy(x, y) by stm_align_rows' rule.
+ * With mode != 0 the frame calls stm_d_adcensus_stm, _t, _nv12, _2s, _2t, _2nv12 (and the host flavours through them) first write the
+ * aligned, unpacked, converted pair as one side-by-side BGR frame into the workspace (one launch; mode 2: three small launches before
+ * it for the measurement, always on the full-resolution input) and then ARE the plain BGR frame call on that frame, packing off:
+ * every `stages` bit, the reduced-resolution frame, and the lens, depth, layout, output, overlay and antialias settings behave as they
+ * do on a side-by-side BGR frame; _nv12's d_img_l / d_img_r receive the aligned images.  With 0x2000 on a BGR frame (_t, _2t) the
+ * previous frame passes through the same kernel with the CURRENT frame's field (one more launch), so both frames are compared in
+ * one geometry.  With 0x2000 on an NV12 frame the history is the caller's d_prev_img_l / d_prev_img_r as the previous call wrote
+ * them: aligned by that frame's field.  Rules under mode != 0: an unpacked BGR frame needs num_cols_sbs >= 2 * num_cols; mode 2
+ * needs num_rows >= 4, num_cols >= 8 and (num_rows/4 + 1) * (num_cols/8 + 1) <= 8421504 (any frame up to 16384 x 16384).
+ * Argument rules: mode 0, 1 or 2; in mode 1 a, b, c finite (ignored otherwise; the offset itself is clamped to +-64 rows per pixel).
+ * Returns 0, or -1 with stm_last_error set and the thread's setting unchanged. */
+int         stm_set_align(int mode, float a, float b, float c);
+/* Mode 2's parameters (kept when the mode changes; the defaults are 16, 1, null): radius in 1 .. 32, the search range in rows; rate
+ * in (0, 1] (1 = every frame on its own); d_state = four floats in device memory, {valid, a, b, c}, or null.  In mode 2 the frame
+ * call runs stm_d_align_fit's measurement on its input with these parameters and d_state, and the kernel that applies the field
+ * reads a, b, c from that memory: nothing is synchronised or read back.  A null d_state means scratch memory, with every frame
+ * fitted on its own.  A caller resets the history, for a scene cut, by zeroing `valid`.  Returns 0, or -1 with stm_last_error set
+ * and the old parameters in place. */
+int         stm_set_align_auto(int radius, float rate, float *d_state);
+/* out_mode = {mode, radius}, out = {a, b, c, rate} as the last accepted calls left them.  A frame stream's own setting is not
+ * visible here except during its submit. */
+void        stm_get_align(int out_mode[2], float out[4]);
 /* The calling thread's output geometry (an addition: the reference shows its views in one form only, sub-pixel interlaced).
  * layout 0 = the interlaced frame (the default; tiles_x, tiles_y, order and filter are ignored, and not one launch, argument or
  * kernel changes), 1 = a quilt: the views side by side as a grid of tiles, whole, for a display that interlaces with its own
@@ -980,6 +1009,55 @@ void stm_depth_fit(float *disp_l, float *disp_r, int num_rows, int num_cols, flo
                    int clip_permille, float rate, float *state);
 void stm_d_depth_fit(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
                      int clip_permille, float rate, float *d_state);
+/* Vertical alignment as stages (an addition, see stm_set_align).  H = num_rows, W = num_cols of one unpacked eye.
+ * stm_align_rows applies a field to one image (H x W x elem_sz, B G R first): out(y, x) = img sampled at row y + dy(x, y).
+ * Per pixel -- f32, one operation per line, no contraction; then exact integers:
+ *   u = (float)x - 0.5f * (float)(W - 1);  v = (float)y - 0.5f * (float)(H - 1)
+ *   t = b * u;  s = a + t;  t = c * v;  s = s + t
+ *   m = s * 16.0f;  m = m + 0.5f;  m = floorf(m);  m = fminf(fmaxf(m, -1024.0f), 1024.0f);  q = (int)m       (+-64 rows)
+ *   y0 = y + (q >> 4);  f = q & 15                                                                 (arithmetic shift)
+ *   out[ch] = ((16 - f) * img[clamp(y0)][x][ch] + f * img[clamp(y0 + 1)][x][ch] + 8) >> 4          ch = 0, 1, 2; rows clamp to [0, H-1]
+ * f = 0 copies a row's pixel; a = b = c = 0 reproduces the image byte for byte.  Bytes of a pixel past the third: the device flavour
+ * leaves them as they are in d_img_out, the host flavour returns them 0.  Rules: num_rows, num_cols >= 1, elem_sz >= 3, a, b, c
+ * finite, no null pointer, img_out and img share no byte.
+ *
+ * stm_align_fit measures the field between two unpacked images.  KB = 8 column bands, band j = columns [j W / 8, (j+1) W / 8);
+ * KR = 4 row blocks, block k = rows [k H / 4, (k+1) H / 4); R = radius; grey = (u8)(b*c + g*c + r*c), c = 0.33333334f, f32 one
+ * operation per line (the grey of the census):
+ *   1. P_e[j][y] = the sum of grey_e(y, x) over band j                                              u32, e = left, right
+ *   2. G_e[j][y] = P_e[j][min(y+1, H-1)] - P_e[j][max(y-1, 0)]                                      i32 (a gradient: an exposure
+ *                                                                                                   difference between the eyes cancels)
+ *   3. S[j][k][d] = the sum over the rows y of block k of |G_L[j][y] - G_R[j][clamp(y + d, 0, H-1)]|, d = -R .. R      u32
+ *      (at most 510 (W/8 + 1) (H/4 + 1): it fits 32 bits while (H/4 + 1) (W/8 + 1) <= 8421504, which is a rule of the call)
+ *   4. per block i = j * 4 + k: the minimum of S over d, scanned d = 0, -1, +1, -2, +2, ... with strict less-than (ties go to the
+ *      smaller |d|, then to the negative one).  The block is VALID iff the minimum is not at d = +-R and
+ *      den = S[d-1] - 2 S[d] + S[d+1] > 0.  Then, in f64, one operation per line:
+ *        t = (double)(S[d-1] - S[d+1]) / (double)den;  t = 0.5 * t;  o = (double)d + t
+ *        t = (double)den * (double)(2R+1);  w = t / (double)max(1, the sum of S over d)
+ *      with centre u_c = (x0 + x1 - 1) * 0.5 - (W - 1) * 0.5 of its band [x0, x1) and v_c likewise of its rows.
+ *   5. the plane o ~ a + b u_c + c v_c by least squares over the blocks of weight > 0, a residual weighted by w (not w^2): the
+ *      normal equations  M = sum w [1 u v]^T [1 u v],  r = sum w o [1 u v]^T  summed in block order i = 0 .. 31 and solved by
+ *      Cramer's rule through the cofactors of M, f64, one operation per line, correctly rounded division (tests/test_align_ref.py's
+ *      solve_ref states every line).  Fewer than 3 such blocks, or det(M) <= 1e-6 * M00 * M11 * M22 (the product of the diagonal
+ *      bounds the determinant from above; a bare `det > 0` would let rounding decide for blocks of one band or one row block):
+ *      b = c = 0 and a = r0 / M00, the weighted mean.  Then every block whose residual |o - (a + b u_c + c v_c)| exceeds 1.0
+ *      loses its weight and the plane is solved once more over the rest (if nothing is left the first solution stands).
+ *   6. state = four floats {valid, a, b, c}.  No valid block: the state is kept (one with valid == 0 becomes four zeros).
+ *      Otherwise valid == 0: the state becomes (1, (float)a, (float)b, (float)c); else a, b, c each move by rate as stm_depth_fit's:
+ *        t = value - (double)old;  t = (double)rate * t;  new = (float)((double)old + t)
+ * The device flavour reads and writes d_state in device memory and synchronises nothing; d_valid_blocks (one int), d_profiles
+ * (2 * 8 * num_rows words: P_left then P_right, [j][y]) and d_sad (8 * 4 * (2 radius + 1) words: [j][k][d + R]) receive what their
+ * names say and may each be null.  The host flavour takes and returns the four floats in host memory and returns the number of
+ * valid blocks (-1 on an error).  Rules: num_rows >= 4, num_cols >= 8, the size rule of step 3, elem_sz >= 3, radius in 1 .. 32, rate
+ * in (0, 1], no null image or state.  Violations fail through stm_last_error before anything is launched or written.  Parity is
+ * against the numpy statement of these lines in tests/test_align_ref.py (parity unpinned). */
+void stm_align_rows(unsigned char *img_out, const unsigned char *img, int num_rows, int num_cols, int elem_sz, float a, float b, float c);
+void stm_d_align_rows(unsigned char *d_img_out, const unsigned char *d_img, int num_rows, int num_cols, int elem_sz, float a, float b,
+                      float c);
+int  stm_align_fit(const unsigned char *img_l, const unsigned char *img_r, int num_rows, int num_cols, int elem_sz, int radius, float rate,
+                   float *state);
+void stm_d_align_fit(const unsigned char *d_img_l, const unsigned char *d_img_r, int num_rows, int num_cols, int elem_sz, int radius,
+                     float rate, float *d_state, int *d_valid_blocks, unsigned int *d_profiles, unsigned int *d_sad);
 /* View antialiasing: the depth-adaptive prefilter of one image by its own map (an addition, the reference has none: each of its views
  * is a pinhole image at one camera position s, while a lenticular lens shows a band about one view spacing wide.  A scene point of
  * displayed end-to-end disparity e moves e / (N - 1) pixels between adjacent views, so detail finer than that step aliases between
@@ -1112,6 +1190,18 @@ int   stm_stream_set_antialias(void *stream, int mode, float strength, int max_r
  * taken on the frame's compute stream and downloaded with its results, so the next frame's update cannot race it), in mode 1 the
  * setting, in mode 0 {1, 0}.  Returns 0, or -1 if no frame has been collected yet. */
 int   stm_stream_depth(void *stream, float out[2]);
+/* the vertical alignment of the stream's frames (stm_set_align's rules; the default is mode 0, and the calling thread's own setting
+ * never reaches a stream's frames).  The stream keeps its own copy and installs it only around its frame calls, so the measurement
+ * and the kernel that applies the field are part of the slots' captured graphs.  stm_stream_set_align_auto sets mode 2's radius and
+ * rate (stm_set_align_auto's rules; the defaults are 16 and 1); the state is the stream's own: one buffer at a fixed address, zeroed
+ * when mode 2 is first set.  Frame k reads what frame k - 1 wrote, so in mode 2 the two frames in flight run one after the other
+ * on the GPU, as with depth mode 2.  Mode 2 needs stm_set_align's size rules on the stream's geometry.  Only before the first
+ * submit.  Return 0, or -1 with stm_last_error set and the stream unchanged. */
+int   stm_stream_set_align(void *stream, int mode, float a, float b, float c);
+int   stm_stream_set_align_auto(void *stream, int radius, float rate);
+/* out = {a, b, c} applied to the most recently collected frame: in mode 2 the state as that frame's fit left it (copied and
+ * downloaded as stm_stream_depth's), in mode 1 the setting, in mode 0 zeros.  Returns 0, or -1 if no frame has been collected yet. */
+int   stm_stream_align(void *stream, float out[3]);
 /* waits for the oldest uncollected frame and copies its results out (NULL = skip).  Returns its index or -1. */
 long  stm_stream_collect(void *stream, float *disp_l, float *disp_r, unsigned char *interlaced);
 /* zero-copy variants (at 1080p the two host copies of submit / collect take longer than the frame does on the GPU):

@@ -52,6 +52,9 @@ PROTOS = {
     "stm_set_depth_auto": ([f, f, f, i, f, vp], i),
     "stm_set_antialias": ([i, f, i, f], i),
     "stm_get_antialias": ([C.POINTER(C.c_int), f32p], None),
+    "stm_set_align": ([i, f, f, f], i),
+    "stm_set_align_auto": ([i, f, vp], i),
+    "stm_get_align": ([C.POINTER(C.c_int), f32p], None),
     "stm_ci_adcensus": ([u8p, u8p, f32pp, f32pp, f, f, i, i, i, i, i], None),
     "stm_d_ci_adcensus": ([vp, vp, vp, vp, f32pp, f32pp, vp, f, f, i, i, i, i, i], None),
     "stm_ca_cross": ([u8p, u8pp, f32pp, f32pp, f, f, i, i, i, i, i, i], None),
@@ -126,6 +129,10 @@ PROTOS = {
     "stm_d_disp_temporal": ([vp, vp, vp, vp, i, i, i, f, i, f], None),
     "stm_depth_fit": ([f32p, f32p, i, i, f, f, f, i, f, f32p], None),
     "stm_d_depth_fit": ([vp, vp, i, i, f, f, f, i, f, vp], None),
+    "stm_align_rows": ([u8p, u8p, i, i, i, f, f, f], None),
+    "stm_d_align_rows": ([vp, vp, i, i, i, f, f, f], None),
+    "stm_align_fit": ([u8p, u8p, i, i, i, i, f, f32p], i),
+    "stm_d_align_fit": ([vp, vp, i, i, i, i, f, vp, vp, vp, vp], None),
     "stm_view_prefilter": ([u8p, u8p, f32p, i, i, i, i, f, i, f, f, f], None),
     "stm_d_view_prefilter": ([vp, vp, vp, i, i, i, i, f, i, f, f, f], None),
     "stm_d_tx_scale": ([u8p, u8p, i, i, i, i, i], None),
@@ -145,6 +152,9 @@ PROTOS = {
     "stm_stream_set_depth_auto": ([C.c_void_p, f, f, f, i, f], i),
     "stm_stream_set_antialias": ([C.c_void_p, i, f, i, f], i),
     "stm_stream_depth": ([C.c_void_p, f32p], i),
+    "stm_stream_set_align": ([C.c_void_p, i, f, f, f], i),
+    "stm_stream_set_align_auto": ([C.c_void_p, i, f], i),
+    "stm_stream_align": ([C.c_void_p, f32p], i),
     "stm_stream_collect": ([C.c_void_p, f32p, f32p, u8p], C.c_long),
     "stm_stream_input_buffer": ([C.c_void_p], C.c_void_p),
     "stm_stream_collect_view": ([C.c_void_p, C.POINTER(f32p), C.POINTER(f32p), C.POINTER(u8p)], C.c_long),

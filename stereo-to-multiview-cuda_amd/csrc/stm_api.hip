@@ -965,6 +965,84 @@ void stm_depth_fit(float *disp_l, float *disp_r, int num_rows, int num_cols, flo
     sync();
 }
 
+// =============================================================== vertical alignment: the field applied and measured as stages
+// (an addition, the reference has none: it takes rectified pairs)
+static bool align_rows_args_ok(const char *fn, const unsigned char *img_out, const unsigned char *img, int num_rows, int num_cols, int elem_sz,
+                               float a, float b, float c)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
+    if (!align_params_ok(fn, 1, a, b, c)) return false;
+    char msg[160];
+    if (!img_out || !img) {
+        snprintf(msg, sizeof msg, "%s: img_out and img must not be null", fn);
+        fail(msg, "img_out, img", __FILE__, __LINE__);
+        return false;
+    }
+    const size_t bytes = (size_t)num_rows * num_cols * elem_sz;
+    if (bytes_overlap(img_out, bytes, img, bytes)) { // a pixel's taps are other rows' outputs
+        snprintf(msg, sizeof msg, "%s: img_out must not overlap img", fn);
+        fail(msg, "img_out", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
+void stm_d_align_rows(unsigned char *d_img_out, const unsigned char *d_img, int num_rows, int num_cols, int elem_sz, float a, float b, float c)
+{
+    if (!align_rows_args_ok("d_align_rows", d_img_out, d_img, num_rows, num_cols, elem_sz, a, b, c)) return;
+    launch_align_frame(d_img_out, nullptr, d_img, num_rows, num_cols, elem_sz, a, b, c, nullptr);
+}
+void stm_align_rows(unsigned char *img_out, const unsigned char *img, int num_rows, int num_cols, int elem_sz, float a, float b, float c)
+{
+    if (!align_rows_args_ok("align_rows", img_out, img, num_rows, num_cols, elem_sz, a, b, c)) return;
+    const size_t IMG = (size_t)num_rows * num_cols * elem_sz;
+    Workspace::begin(2 * IMG + 8192);
+    const u8 *i = up(img, IMG);
+    u8 *o = Workspace::get<u8>(IMG);
+    if (elem_sz > 3) STM_CHECK(hipMemsetAsync(o, 0, IMG, stream())); // bytes past the third come back 0
+    launch_align_frame(o, nullptr, i, num_rows, num_cols, elem_sz, a, b, c, nullptr);
+    down(img_out, o, IMG);
+    sync();
+}
+static bool align_fit_args_ok(const char *fn, const unsigned char *img_l, const unsigned char *img_r, int num_rows, int num_cols, int elem_sz,
+                              int radius, float rate, const float *state)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
+    if (!align_size_ok(fn, num_rows, num_cols) || !align_auto_params_ok(fn, radius, rate)) return false;
+    if (!img_l || !img_r || !state) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: img_l, img_r and state must not be null", fn);
+        fail(msg, "img_l, img_r, state", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
+void stm_d_align_fit(const unsigned char *d_img_l, const unsigned char *d_img_r, int num_rows, int num_cols, int elem_sz, int radius,
+                     float rate, float *d_state, int *d_valid_blocks, unsigned int *d_profiles, unsigned int *d_sad)
+{
+    if (!align_fit_args_ok("d_align_fit", d_img_l, d_img_r, num_rows, num_cols, elem_sz, radius, rate, d_state)) return;
+    Workspace::begin((align_profile_words(num_rows) + align_sad_words(radius)) * 4 + 8192);
+    uint32_t *prof = d_profiles ? d_profiles : Workspace::get<uint32_t>(align_profile_words(num_rows));
+    uint32_t *sad = d_sad ? d_sad : Workspace::get<uint32_t>(align_sad_words(radius));
+    launch_align_measure(d_state, d_valid_blocks, prof, sad, nullptr, d_img_l, d_img_r, num_rows, num_cols, elem_sz, radius, rate, false);
+}
+int stm_align_fit(const unsigned char *img_l, const unsigned char *img_r, int num_rows, int num_cols, int elem_sz, int radius, float rate,
+                  float *state)
+{
+    if (!align_fit_args_ok("align_fit", img_l, img_r, num_rows, num_cols, elem_sz, radius, rate, state)) return -1;
+    const size_t IMG = (size_t)num_rows * num_cols * elem_sz;
+    Workspace::begin(2 * IMG + (align_profile_words(num_rows) + align_sad_words(radius)) * 4 + 8192);
+    const u8 *l = up(img_l, IMG), *r = up(img_r, IMG);
+    float *st = up(state, 4);
+    int *nv = Workspace::get<int>(1);
+    uint32_t *prof = Workspace::get<uint32_t>(align_profile_words(num_rows)), *sad = Workspace::get<uint32_t>(align_sad_words(radius));
+    launch_align_measure(st, nv, prof, sad, nullptr, l, r, num_rows, num_cols, elem_sz, radius, rate, false);
+    int count = -1;
+    down(state, st, 4);
+    down(&count, nv, 1);
+    sync();
+    return failed() ? -1 : count;
+}
+
 // =============================================================== view antialiasing: the prefilter as a stage
 // (an addition, the reference has none: its views are pinhole images whatever the lens shows of them)
 static bool prefilter_args_ok(const char *fn, const unsigned char *img_out, const unsigned char *img, const float *disp, int num_rows,
@@ -1703,6 +1781,48 @@ struct Nv12Input {
     u8 *img_l, *img_r;
 };
 
+// ---- the vertical alignment of a frame call's input (stm_set_align)
+// the thread's setting against a frame call's geometry; off: nothing to check, the call is as it was
+bool frame_align_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, bool bgr_sbs)
+{
+    const Align al = align();
+    if (!al.mode) return true;
+    if (bgr_sbs && num_cols_sbs < 2 * num_cols) { // both eyes are gathered from the frame
+        char msg[200];
+        snprintf(msg, sizeof msg, "%s: an alignment is set on this thread (stm_set_align), which needs num_cols_sbs >= 2 * num_cols", fn);
+        fail(msg, "num_cols_sbs", __FILE__, __LINE__);
+        return false;
+    }
+    return al.mode != 2 || align_size_ok(fn, num_rows, num_cols);
+}
+// the workspace the prelude below takes: the aligned frame (and the previous frame's), the profiles, the SADs, a scratch state
+size_t align_ws_bytes(int H, size_t IMG, bool prev) { return (prev ? 4 : 2) * IMG + (align_profile_words(H) + align_sad_words(32)) * 4 + 4096; }
+// The prelude, inside the frame call's Workspace scope: mode 2 measures the screened frame `in` at full resolution and updates the
+// state; the aligned, unpacked, converted pair is returned as one side-by-side BGR frame (H x 2 W x elem_sz) in the workspace.
+// prev_frame != nullptr: the previous BGR frame, of the same geometry, through the same kernel with THIS frame's field into prev_out.
+u8 *align_frame_input(const Align &al, const PackInput &in, const u8 *prev_frame, int H, int W, int elem_sz, const u8 *&prev_out)
+{
+    const size_t IMG = (size_t)H * W * elem_sz;
+    const float *st = nullptr;
+    if (al.mode == 2) {
+        float *state = al.d_state ? al.d_state : Workspace::get<float>(4); // scratch: every frame on its own
+        uint32_t *prof = Workspace::get<uint32_t>(align_profile_words(H)), *sad = Workspace::get<uint32_t>(align_sad_words(al.radius));
+        launch_align_measure(state, nullptr, prof, sad, &in, nullptr, nullptr, H, W, elem_sz, al.radius, al.rate, al.d_state == nullptr);
+        st = state;
+    }
+    u8 *out = Workspace::get<u8>(2 * IMG);
+    launch_align_frame(out, &in, nullptr, H, W, elem_sz, al.a, al.b, al.c, st);
+    prev_out = nullptr;
+    if (prev_frame) {
+        PackInput prev = in;
+        prev.frame = prev_frame;
+        u8 *po = Workspace::get<u8>(2 * IMG);
+        launch_align_frame(po, &prev, nullptr, H, W, elem_sz, al.a, al.b, al.c, st);
+        prev_out = po;
+    }
+    return out;
+}
+
 // the body of stm_d_adcensus_stm, stm_d_adcensus_stm_t and stm_d_adcensus_stm_nv12; hist != nullptr: the temporal step between
 // the bilateral filter and the renderer; nv != nullptr: the frame comes as NV12 planes (d_img_sbs is null, num_cols_sbs >= 2 W).
 // Every argument has been screened by the caller except the `stages` rules the calls share.
@@ -1737,20 +1857,37 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
     const size_t V = pq_volume_floats(num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
     const Packing pack = packing(); // a packed frame (stm_set_packing): the caller has screened its geometry
+    if (!frame_align_ok(fn, H, num_cols_sbs, W, !nv && !pack.on())) return;
+    const Align aln = align();       // the vertical alignment (stm_set_align), screened above
     Workspace::begin(((stages & 0x100) ? 13 : 4) * V * 4 + (size_t)(N + 2 + (pack.on() && hist && !nv ? 2 : 0)) * IMG + 168 * HW + (1u << 20) +
                      (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0) + // the un-fused NV12 frame's BGR quilt
-                     (antialias().mode == 1 ? 2 * IMG + 512 : 0));                                  // the prefiltered pair
+                     (antialias().mode == 1 ? 2 * IMG + 512 : 0) +                                  // the prefiltered pair
+                     (aln.mode ? align_ws_bytes(H, IMG, hist && !nv) : 0));                          // the aligned frame(s)
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
+    const bool split_hist = nv != nullptr; // ... and an NV12 frame's history comes as split images
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     uint32_t *pre[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool fused_split = num_cols_sbs >= 2 * W; // both halves complete: emit the derived pixel formats in the same pass
     const PackInput pin = {pack, nv != nullptr, d_img_sbs, num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr, nv ? nv->pitch_y : 0,
                            nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0};
-    if (pack.on() && (agg_variant() / 100) % 10 != 6) { // the gather, the filter and the conversion in stm_k_front's pass
+    const bool pack_on = pack.on() && !aln.mode;
+    TemporalHist hist_aligned;
+    if (aln.mode) { // from here on the call is the plain BGR frame call on the aligned side-by-side frame
+        d_img_sbs = align_frame_input(aln, pin, hist && !nv ? hist->sbs : nullptr, H, W, elem_sz, hist_aligned.sbs);
+        if (hist && !nv) {
+            const u8 *prev = hist_aligned.sbs;
+            hist_aligned = *hist;
+            hist_aligned.sbs = prev;
+            hist = &hist_aligned;
+        }
+        num_cols_sbs = 2 * W;
+        nv = nullptr;
+    }
+    bool fused_split = num_cols_sbs >= 2 * W; // both halves complete: emit the derived pixel formats in the same pass
+    if (pack_on && (agg_variant() / 100) % 10 != 6) { // the gather, the filter and the conversion in stm_k_front's pass
         for (int i = 0; i < 6; ++i) pre[i] = Workspace::get<uint32_t>(HW);
         launch_front_pack(img_l, img_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], pin, H, W, elem_sz);
         fused_split = true;
-    } else if (pack.on()) { // 600: the plain unpacking, then the pixel formats and the census as kernels of their own
+    } else if (pack_on) { // 600: the plain unpacking, then the pixel formats and the census as kernels of their own
         launch_demux_packed(img_l, img_r, pin, H, W, elem_sz);
         fused_split = false;
     } else if (nv && (agg_variant() / 100) % 10 != 6) { // the conversion in stm_k_front's pass
@@ -1782,9 +1919,9 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
     if (hist) {
         float *c[2] = {d_disp_l, d_disp_r};
         const float *q[2] = {hist->disp_l, hist->disp_r};
-        const bool split = nv || pack.on(); // the views as split images; otherwise in place in the two side-by-side frames
+        const bool split = split_hist || pack_on; // the views as split images; otherwise in place in the two side-by-side frames
         const u8 *prev_l = hist->img_l, *prev_r = hist->img_r;
-        if (pack.on() && !nv) { // the previous PACKED frame: its images are its unpacking (one more launch in this combination only)
+        if (pack_on && !nv) { // the previous PACKED frame: its images are its unpacking (one more launch in this combination only)
             u8 *ul = Workspace::get<u8>(IMG), *ur = Workspace::get<u8>(IMG);
             PackInput prev = pin;
             prev.frame = hist->sbs;
@@ -2020,12 +2157,30 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
     const bool hslo = stages_hslo(stages), subpix = stages_subpix(stages), interp = (stages & 0x400) != 0; // on the reduced pair
     const bool linwarp = (stages & 0x800) != 0;                                                             // in the full-size render
     const bool guided = (stages & 0x1000) != 0; // the up-scale between the two: stm_disp_upsample instead of tx_disp_scale
+    if (!frame_align_ok(fn, H, num_cols_sbs, W, !nv)) return;
+    const Align aln = align(); // the vertical alignment (stm_set_align), screened above
     Workspace::begin((hslo ? 13 : 4) * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 32 * hw + (1u << 20) + // HSLO: as d_adcensus_stm
                      (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0) +
-                     (antialias().mode == 1 ? 2 * IMG + 512 : 0)); // the prefiltered pair
+                     (antialias().mode == 1 ? 2 * IMG + 512 : 0) +                // the prefiltered pair
+                     (aln.mode ? align_ws_bytes(H, IMG, hist && !nv) : 0));        // the aligned frame(s)
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
+    const bool split_hist = nv != nullptr; // ... and an NV12 frame's history comes as split images
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     u8 *low_l = Workspace::get<u8>(hw * elem_sz), *low_r = Workspace::get<u8>(hw * elem_sz);
+    TemporalHist hist_aligned;
+    if (aln.mode) { // from here on the call is the plain BGR reduced-resolution frame call on the aligned side-by-side frame
+        const PackInput pin = {Packing{0, 0, 0, 0}, nv != nullptr, d_img_sbs, num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr,
+                               nv ? nv->pitch_y : 0, nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0};
+        d_img_sbs = align_frame_input(aln, pin, hist && !nv ? hist->sbs : nullptr, H, W, elem_sz, hist_aligned.sbs);
+        if (hist && !nv) {
+            const u8 *prev = hist_aligned.sbs;
+            hist_aligned = *hist;
+            hist_aligned.sbs = prev;
+            hist = &hist_aligned;
+        }
+        num_cols_sbs = 2 * W;
+        nv = nullptr;
+    }
     uint32_t *pre[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const bool fused = reduced_front_fused(num_cols_sbs, W); // both halves complete; 600: the chain of kernels
     {
@@ -2058,7 +2213,7 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
     if (hist) {
         float *c[2] = {d_disp_l, d_disp_r};
         const float *q[2] = {hist->disp_l, hist->disp_r};
-        const bool split = nv != nullptr;
+        const bool split = split_hist;
         const u8 *im[2] = {split ? img_l : d_img_sbs, split ? img_r : d_img_sbs}, *ip[2] = {split ? hist->img_l : hist->sbs, split ? hist->img_r : hist->sbs};
         const size_t off[2] = {0, split ? 0 : (size_t)W * elem_sz};
         launch_disp_temporal(2, c, q, im, ip, off, H, W, split ? W : num_cols_sbs, elem_sz, hist->alpha, hist->thresh_color, hist->thresh_disp);
@@ -2077,6 +2232,7 @@ void reduced_frame_host(const char *fn, unsigned char *img_sbs, float *disp_l, f
                          num_views, num_disp, stages))
         return;
     if (!frame_layout_ok(fn, stages, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return; // before the caller's arrays are written
+    if (!frame_align_ok(fn, num_rows, num_cols_sbs, num_cols, true)) return;
     size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
     size_t out_sz = frame_out_bytes(num_rows_out, num_cols_out, elem_sz); // stm_set_output: the NV12 surface
     const size_t need[4] = {sbs_sz, out_sz, HW * 4, HW * 4};
@@ -2385,6 +2541,7 @@ void stm_adcensus_stm(unsigned char *img_sbs, float *disp_l, float *disp_r, unsi
         return;
     if (packing_unsupported("adcensus_stm")) return;
     if (!frame_layout_ok("adcensus_stm", 3, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return; // before the caller's arrays are written
+    if (!frame_align_ok("adcensus_stm", num_rows, num_cols_sbs, num_cols, true)) return;
     size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
     size_t out_sz = frame_out_bytes(num_rows_out, num_cols_out, elem_sz); // stm_set_output: the NV12 surface
     // own buffers are cached outside the workspace: the pipeline call below re-carves the workspace

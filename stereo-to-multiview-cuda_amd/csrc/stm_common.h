@@ -399,6 +399,33 @@ void launch_view_prefilter(int nimg, u8 *const *out, const u8 *const *in, const 
 // (four floats); fresh: the state's history is ignored
 void launch_depth_fit(float *state, uint32_t *hist, const float *disp_l, const float *disp_r, int H, int W, float disp_lo, float disp_hi,
                       float max_gain, int clip_permille, float rate, bool fresh);
+// The vertical alignment of the pair (stm_set_align / stm_set_align_auto, include/stm_hip.h): mode 0 = off (not one launch changes),
+// 1 = manual (the field a, b, c), 2 = automatic (the field measured on each frame on the device).  One per host thread, next to the
+// depth budget; a frame stream installs its own copy around its frame calls.
+struct Align {
+    int mode;
+    float a, b, c;      // mode 1
+    int radius;         // mode 2: the search radius in rows, the state's update rate
+    float rate;
+    float *d_state;     // mode 2: {valid, a, b, c} in device memory; null = scratch, every frame on its own
+};
+Align align();
+void set_align(const Align &a);
+// the argument rules of the two settings; false with the error recorded
+bool align_params_ok(const char *fn, int mode, float a, float b, float c);
+bool align_auto_params_ok(const char *fn, int radius, float rate);
+// the measurement's frame rules: num_rows >= 4, num_cols >= 8, and a size whose sums fit 32 bits; false with the error recorded
+bool align_size_ok(const char *fn, int num_rows, int num_cols);
+// the measurement (stm_kernels_align.hip) of a screened frame (in != nullptr) or of two unpacked images H x W x elem_sz: the profiles
+// into prof (align_profile_words(H) words), the SADs into sad (align_sad_words(radius) words), the fit, the update of `state` (four
+// floats) and the number of valid blocks into nvalid (may be null); fresh: the state's history is ignored
+size_t align_profile_words(int H);
+size_t align_sad_words(int radius);
+void launch_align_measure(float *state, int *nvalid, uint32_t *prof, uint32_t *sad, const PackInput *in, const u8 *img_l, const u8 *img_r,
+                          int H, int W, int elem_sz, int radius, float rate, bool fresh);
+// the field applied: a screened frame (in != nullptr) as the aligned side-by-side BGR frame `out` (H x 2 W x elem_sz, the left eye
+// copied), or the one image img (H x W x elem_sz) into out; state != nullptr: a, b, c are read from state[1 .. 3] on the device
+void launch_align_frame(u8 *out, const PackInput *in, const u8 *img, int H, int W, int elem_sz, float a, float b, float c, const float *state);
 // aggregation on the matrix pipe (stm_kernels_aggm.hip): the frame pipeline's cost -> H -> V, V -> H + WTA
 struct PQViews { // both views of a frame; a / b = the two PQ volumes of a view
     const uint32_t *pk[2], *cen[2];

@@ -469,6 +469,65 @@ bool antialias_params_ok(const char *fn, float strength, int max_radius, float g
     fail(msg, arg, __FILE__, __LINE__);
     return false;
 }
+// the calling thread's vertical alignment (stm_set_align, stm_set_align_auto)
+static thread_local Align g_align = {0, 0.0f, 0.0f, 0.0f, 16, 1.0f, nullptr};
+Align align() { return g_align; }
+void set_align(const Align &a) { g_align = a; }
+bool align_params_ok(const char *fn, int mode, float a, float b, float c)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (mode < 0 || mode > 2) {
+        snprintf(msg, sizeof msg, "%s: align mode = %d, must be 0 (off), 1 (manual) or 2 (automatic)", fn, mode);
+        arg = "mode";
+    } else if (mode != 1) {
+        return true; // off / automatic: a, b and c are ignored
+    } else if (!(fabsf(a) <= FLT_MAX)) { // NaN fails the comparison
+        snprintf(msg, sizeof msg, "%s: align a = %g, must be finite", fn, (double)a);
+        arg = "a";
+    } else if (!(fabsf(b) <= FLT_MAX)) {
+        snprintf(msg, sizeof msg, "%s: align b = %g, must be finite", fn, (double)b);
+        arg = "b";
+    } else if (!(fabsf(c) <= FLT_MAX)) {
+        snprintf(msg, sizeof msg, "%s: align c = %g, must be finite", fn, (double)c);
+        arg = "c";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+bool align_auto_params_ok(const char *fn, int radius, float rate)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (radius < 1 || radius > 32) {
+        snprintf(msg, sizeof msg, "%s: radius = %d, must be in 1 .. 32", fn, radius);
+        arg = "radius";
+    } else if (!(rate > 0.0f && rate <= 1.0f)) {
+        snprintf(msg, sizeof msg, "%s: rate = %g, must be in (0, 1]", fn, (double)rate);
+        arg = "rate";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+bool align_size_ok(const char *fn, int num_rows, int num_cols)
+{
+    char msg[200];
+    if (num_rows < 4 || num_cols < 8) {
+        snprintf(msg, sizeof msg, "%s: the alignment measurement needs num_rows >= 4 and num_cols >= 8 (got %d x %d)", fn, num_rows, num_cols);
+        fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
+        return false;
+    }
+    // a block's sum of |G_L - G_R| is at most 510 (W/8 + 1) (H/4 + 1), kept in 32 bits
+    if ((unsigned long long)(num_rows / 4 + 1) * (unsigned long long)(num_cols / 8 + 1) > 0xffffffffull / 510) {
+        snprintf(msg, sizeof msg, "%s: the alignment measurement needs (num_rows/4 + 1) * (num_cols/8 + 1) <= %llu (got %d x %d)", fn,
+                 0xffffffffull / 510, num_rows, num_cols);
+        fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
 bool depth_auto_params_ok(const char *fn, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate)
 {
     char msg[200];
@@ -716,6 +775,33 @@ void stm_get_antialias(int out_mode[2], float out[2])
     const stm::Antialias a = stm::antialias();
     out_mode[0] = a.mode; out_mode[1] = a.max_radius;
     out[0] = a.strength; out[1] = a.gate;
+}
+int stm_set_align(int mode, float a, float b, float c)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (!stm::align_params_ok("set_align", mode, a, b, c)) return -1; // the thread's setting stays as it was
+    stm::Align al = stm::align(); // mode 2's parameters (stm_set_align_auto) are kept
+    al.mode = mode;
+    al.a = mode == 1 ? a : 0.0f;
+    al.b = mode == 1 ? b : 0.0f;
+    al.c = mode == 1 ? c : 0.0f;
+    stm::set_align(al);
+    return 0;
+}
+int stm_set_align_auto(int radius, float rate, float *d_state)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (!stm::align_auto_params_ok("set_align_auto", radius, rate)) return -1;
+    stm::Align al = stm::align();
+    al.radius = radius; al.rate = rate; al.d_state = d_state;
+    stm::set_align(al);
+    return 0;
+}
+void stm_get_align(int out_mode[2], float out[4])
+{
+    const stm::Align al = stm::align();
+    out_mode[0] = al.mode; out_mode[1] = al.radius;
+    out[0] = al.a; out[1] = al.b; out[2] = al.c; out[3] = al.rate;
 }
 void stm_set_agg_variant(int v)
 {

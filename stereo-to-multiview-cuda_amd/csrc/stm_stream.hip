@@ -23,6 +23,7 @@ struct Slot {
     float *d_dl = nullptr, *d_dr = nullptr, *h_dl = nullptr, *h_dr = nullptr;
     u8 *d_img_l = nullptr, *d_img_r = nullptr; // NV12 input: the slot's converted split images (the other slot's frame reads them as its history)
     float *d_rec = nullptr, *h_rec = nullptr; // depth mode 2: the state as this slot's frame left it (16 bytes), and its download
+    float *d_arec = nullptr, *h_arec = nullptr; // align mode 2: likewise the alignment's state
     u8 *h_ov = nullptr, *d_ov = nullptr;      // stm_stream_set_overlay: the slot's pinned and device copy of the overlay's pixels
     long ov_gen = 0;                          // ... and which stm_stream_overlay call they hold (0 = none yet)
     hipEvent_t ev_in, ev_done, ev_out;
@@ -61,6 +62,8 @@ struct FrameStream {
     float match_scale = 1.0f;            // ... and the reduced frame's disp_scale
     stm::Antialias antialias = {0, 0.0f, 0, 0.0f}; // stm_stream_set_antialias: the stream's own view antialiasing
     float *d_depth_state = nullptr; // mode 2: the state every frame updates, at one address for both slots' graphs
+    stm::Align align = {0, 0.0f, 0.0f, 0.0f, 16, 1.0f, nullptr}; // stm_stream_set_align / _auto: the stream's own vertical alignment
+    float *d_align_state = nullptr; // align mode 2: the state every frame updates, at one address for both slots' graphs
     int ov_max_rows = 0, ov_max_cols = 0; // stm_stream_set_overlay: the largest overlay the slots' copies hold ((0, 0) = off)
     u8 *ov_pixels = nullptr;              // stm_stream_overlay: the pixels of the overlay in force (host memory of the stream's own)
     stm::Overlay ov = {0, nullptr, 0, 0, 0, 0, 0.0f}; // ... and its arguments; mode 0 = none.  d_overlay is filled in per slot
@@ -92,6 +95,12 @@ struct DepthScope {
     stm::Depth saved;
     explicit DepthScope(const stm::Depth &d) : saved(stm::depth()) { stm::set_depth(d); }
     ~DepthScope() { stm::set_depth(saved); }
+};
+
+struct AlignScope {
+    stm::Align saved;
+    explicit AlignScope(const stm::Align &a) : saved(stm::align()) { stm::set_align(a); }
+    ~AlignScope() { stm::set_align(saved); }
 };
 
 struct AntialiasScope {
@@ -575,6 +584,61 @@ int stm_stream_set_depth_auto(void *h, float disp_lo, float disp_hi, float max_g
     f->depth.rate = rate;
     return 0;
 }
+// The vertical alignment every frame of the stream is conditioned with (stm_set_align's rules; the default is mode 0).  Kept and
+// installed like the depth budget.  Mode 2 allocates the stream's state and the slots' records.  Only before the first submit.
+int stm_stream_set_align(void *h, int mode, float a, float b, float c)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (!stm::align_params_ok("stream_set_align", mode, a, b, c)) return -1;
+    if (mode != 0 && !f->packing.on() && f->in_format == 0 && f->Wsbs < 2 * f->W) {
+        stm::fail("stream_set_align: an alignment needs num_cols_sbs >= 2 * num_cols", "num_cols_sbs", __FILE__, __LINE__);
+        return -1;
+    }
+    if (mode == 2 && !stm::align_size_ok("stream_set_align", f->H, f->W)) return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_align: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    if (mode == 2 && !f->d_align_state) {
+        STM_CHECK(hipMalloc((void **)&f->d_align_state, 16));
+        STM_CHECK(hipMemset(f->d_align_state, 0, 16)); // valid = 0: the first frame starts the history
+        for (Slot &s : f->slot) {
+            STM_CHECK(hipMalloc((void **)&s.d_arec, 16));
+            STM_CHECK(hipHostMalloc((void **)&s.h_arec, 16, hipHostMallocDefault));
+        }
+        if (stm::failed()) return -1;
+    }
+    f->align.mode = mode;
+    f->align.a = mode == 1 ? a : 0.0f;
+    f->align.b = mode == 1 ? b : 0.0f;
+    f->align.c = mode == 1 ? c : 0.0f;
+    f->align.d_state = f->d_align_state;
+    return 0;
+}
+int stm_stream_set_align_auto(void *h, int radius, float rate)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (!stm::align_auto_params_ok("stream_set_align_auto", radius, rate)) return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_align_auto: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    f->align.radius = radius;
+    f->align.rate = rate;
+    return 0;
+}
+// a, b and c applied to the most recently collected frame
+int stm_stream_align(void *h, float out[3])
+{
+    FrameStream *f = (FrameStream *)h;
+    if (f->collected == 0) return -1;
+    const Slot &s = f->slot[(f->collected - 1) & 1];
+    if (f->align.mode == 2) { out[0] = s.h_arec[1]; out[1] = s.h_arec[2]; out[2] = s.h_arec[3]; }
+    else { out[0] = f->align.a; out[1] = f->align.b; out[2] = f->align.c; }
+    return 0;
+}
 // gain and conv applied to the most recently collected frame
 int stm_stream_depth(void *h, float out[2])
 {
@@ -608,6 +672,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     const bool temporal = (f->stages & 0x2000) != 0, history = temporal && f->submitted > 0;
     // depth mode 2: frame k's fit reads the state frame k - 1 wrote, so its compute waits for the other slot's frame as well
     const bool depth_auto = f->depth.mode == 2;
+    const bool align_auto = f->align.mode == 2; // likewise the alignment's state
     // In NV12 mode the history is the other slot's converted split images (d_img_l / d_img_r), which no upload touches, and this
     // slot's d_in was last read by this slot's own previous frame, collected before the slot was handed out again: the upload
     // waits for nothing.  This frame's compute still waits for the other slot's frame: it reads that frame's images and maps, and
@@ -625,13 +690,14 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     }
     STM_CHECK(hipEventRecord(s.ev_in, f->s_in));
     STM_CHECK(hipStreamWaitEvent(s.s_compute, s.ev_in, 0));
-    if (history || (depth_auto && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
+    if (history || ((depth_auto || align_auto) && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
     void *prev = stm_get_stream();
     LensScope lens_scope(f->lens);
     LayoutScope layout_scope(f->layout);
     OutputScope output_scope(f->output);
     DepthScope depth_scope(f->depth);
     AntialiasScope antialias_scope(f->antialias);
+    AlignScope align_scope(f->align);
     PackingScope packing_scope(f->packing);
     OverlayOffScope overlay_scope;
     stm_set_stream(s.s_compute);
@@ -717,12 +783,14 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     stm_set_stream(prev);
     // the state as this frame left it, before ev_done lets the next frame's fit update it
     if (depth_auto) STM_CHECK(hipMemcpyAsync(s.d_rec, f->d_depth_state, 16, hipMemcpyDeviceToDevice, s.s_compute));
+    if (align_auto) STM_CHECK(hipMemcpyAsync(s.d_arec, f->d_align_state, 16, hipMemcpyDeviceToDevice, s.s_compute));
     STM_CHECK(hipEventRecord(s.ev_done, s.s_compute));
     STM_CHECK(hipStreamWaitEvent(f->s_out, s.ev_done, 0));
     STM_CHECK(hipMemcpyAsync(s.h_dl, s.d_dl, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
     STM_CHECK(hipMemcpyAsync(s.h_dr, s.d_dr, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
     STM_CHECK(hipMemcpyAsync(s.h_out, s.d_out, f->out_bytes, hipMemcpyDeviceToHost, f->s_out));
     if (depth_auto) STM_CHECK(hipMemcpyAsync(s.h_rec, s.d_rec, 16, hipMemcpyDeviceToHost, f->s_out));
+    if (align_auto) STM_CHECK(hipMemcpyAsync(s.h_arec, s.d_arec, 16, hipMemcpyDeviceToHost, f->s_out));
     STM_CHECK(hipEventRecord(s.ev_out, f->s_out));
     if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
     if (stm::failed()) return -1; // error mode 1: the frame was not (completely) enqueued
@@ -786,11 +854,14 @@ void stm_stream_destroy(void *h)
         if (s.d_img_r) STM_CHECK(hipFree(s.d_img_r));
         if (s.d_rec) STM_CHECK(hipFree(s.d_rec));
         if (s.h_rec) STM_CHECK(hipHostFree(s.h_rec));
+        if (s.d_arec) STM_CHECK(hipFree(s.d_arec));
+        if (s.h_arec) STM_CHECK(hipHostFree(s.h_arec));
         if (s.h_ov) STM_CHECK(hipHostFree(s.h_ov));
         if (s.d_ov) STM_CHECK(hipFree(s.d_ov));
     }
     free(f->ov_pixels);
     if (f->d_depth_state) STM_CHECK(hipFree(f->d_depth_state));
+    if (f->d_align_state) STM_CHECK(hipFree(f->d_align_state));
     stm::ws_private_destroy(f->slot[0].ws);
     STM_CHECK(hipStreamDestroy(f->slot[0].s_compute));
     if (f->overlap) {

@@ -335,6 +335,61 @@ def get_antialias():
     return int(m[0]), float(v[0]), int(m[1]), float(v[1])
 
 
+def set_align(mode, a=0.0, b=0.0, c=0.0):
+    """stm_set_align: the calling thread's vertical alignment of the pair, applied to every frame call's input ahead of the matcher.
+    mode 0 = off (the default), 1 = manual: the right eye is sampled at row y + a + b u + c v (u, v from the frame's centre),
+    2 = automatic: the field measured on every frame on the GPU with set_align_auto's parameters.  Raises ValueError where the
+    library refuses."""
+    if int(lib().stm_set_align(int(mode), float(a), float(b), float(c))) != 0:
+        raise ValueError("stm_set_align(%d, %g, %g, %g) refused: %s" % (mode, a, b, c, lib().stm_last_error().decode()))
+
+
+def set_align_auto(radius=16, rate=1.0, state=None):
+    """stm_set_align_auto: mode 2's parameters -- the search radius in rows (1 .. 32), the rate at which the field follows a
+    frame's fit, and `state`: a float32 tensor of four elements on the GPU, {valid, a, b, c}, which carries the history from frame
+    to frame (zero `valid` to reset it) -- the caller keeps it alive while the setting is in use; None = every frame on its own.
+    Raises ValueError where the library refuses."""
+    if state is not None:
+        assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous() and state.numel() == 4
+    if int(lib().stm_set_align_auto(int(radius), float(rate), _p(state) if state is not None else None)) != 0:
+        raise ValueError("stm_set_align_auto(%d, %g) refused: %s" % (radius, rate, lib().stm_last_error().decode()))
+
+
+def get_align():
+    """stm_get_align: the calling thread's (mode, a, b, c, radius, rate) as the library holds it"""
+    m = (C.c_int * 2)()
+    v = (C.c_float * 4)()
+    lib().stm_get_align(m, C.cast(v, f32p))
+    return int(m[0]), float(v[0]), float(v[1]), float(v[2]), int(m[1]), float(v[3])
+
+
+def d_align_rows(out, img, a, b, c):
+    """stm_d_align_rows: img (uint8 [H][W][E] on the GPU) sampled at row y + a + b u + c v into out, which must not overlap img;
+    only bytes 0 .. 2 of a pixel are written."""
+    H, W, E = img.shape
+    for t in (out, img):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    _use_current_stream()
+    lib().stm_d_align_rows(_p(out), _p(img), H, W, E, float(a), float(b), float(c))
+
+
+def d_align_fit(img_l, img_r, radius, rate, state, valid_blocks=None, profiles=None, sad=None):
+    """stm_d_align_fit: the measurement of the automatic alignment as a stage -- the two unpacked images (uint8 [H][W][E] on the
+    GPU) into the band profiles, their gradients' SADs, the fit, the update of `state` (float32, four elements on the GPU) in
+    place; nothing synchronised.  valid_blocks (int32, 1), profiles (int32 [2][8][H]) and sad (int32 [8][4][2 radius + 1]) receive
+    the intermediate results where given."""
+    H, W, E = img_l.shape
+    for t in (img_l, img_r):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous() and state.numel() == 4
+    for t, n in ((valid_blocks, 1), (profiles, 2 * 8 * H), (sad, 8 * 4 * (2 * int(radius) + 1))):
+        assert t is None or (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n)
+    _use_current_stream()
+    lib().stm_d_align_fit(_p(img_l), _p(img_r), H, W, E, int(radius), float(rate), _p(state),
+                          _p(valid_blocks) if valid_blocks is not None else None, _p(profiles) if profiles is not None else None,
+                          _p(sad) if sad is not None else None)
+
+
 def d_view_prefilter(out, img, disp, num_views, strength=1.0, max_radius=8, gate=1.0, gain=1.0, conv=0.0):
     """stm_d_view_prefilter: img (uint8 [H][W][E] on the GPU) filtered by its own map disp (float32 [H][W]) into out, which must not
     overlap img; only bytes 0 .. 2 of a pixel are written.  gain, conv: the depth budget the views are rendered with (set_depth)."""

@@ -396,6 +396,32 @@ def view_prefilter(img, disp, num_views, strength=1.0, max_radius=8, gate=1.0, g
     return out
 
 
+def align_rows(img, a, b, c):
+    """The vertical alignment applied to one image (stm_align_rows; an addition, the reference takes rectified pairs): img
+    [H][W][E] sampled at row y + a + b u + c v (u, v from the image's centre), two rows blended in sixteenths, rows clamped to the
+    image.  Returns the [H][W][E] image (bytes of a pixel past the third are 0); nothing passed in is modified."""
+    img, pi = _u8(img)
+    H, W, E = img.shape
+    out = np.zeros((H, W, E), np.uint8)
+    lib().stm_align_rows(out.ctypes.data_as(u8p), pi, H, W, E, float(a), float(b), float(c))
+    return out
+
+
+def align_fit(img_l, img_r, radius=16, rate=1.0, state=None):
+    """The measurement of the automatic alignment (stm_align_fit): the vertical offset field a + b u + c v at which the right
+    image's content matches the left image's rows, from the SADs of band profiles over +-radius rows, folded into `state` =
+    (valid, a, b, c) (None = no history).  Returns (state, valid_blocks): the new state as a float32 array of four and the number
+    of the 32 blocks that took part; nothing passed in is modified."""
+    img_l, pl = _u8(img_l)
+    img_r, pr = _u8(img_r)
+    H, W, E = img_l.shape
+    assert img_r.shape == (H, W, E)
+    st = np.zeros(4, np.float32) if state is None else np.array(state, dtype=np.float32, order="C")
+    assert st.shape == (4,)
+    n = int(lib().stm_align_fit(pl, pr, H, W, E, int(radius), float(rate), st.ctypes.data_as(f32p)))
+    return st, n
+
+
 def tx_scale(img, out_rows, out_cols):
     """d_tx_scale.h:17-18 (bilinear resize)."""
     img, pi = _u8(img)

@@ -30,11 +30,13 @@ class FrameStream:
     by the interleaved UV plane; None = BGR.  Needs a layout.  overlay = (max_rows, max_cols): the stream composites an overlay of up
     to that size into its frames (set_overlay; .overlay() sets the one in force); None = none.  Not together with an NV12 output.
     antialias = (strength, max_radius, gate): view antialiasing (set_antialias mode 1) -- both images filtered by their own maps
-    before the views are rendered from them; None = off."""
+    before the views are rendered from them; None = off.  align = (a, b, c): the right eye of every frame sampled at row
+    y + a + b u + c v ahead of the matcher (set_align mode 1); align_auto = (radius[, rate]): the field measured on every frame on
+    the GPU (mode 2); at most one of the two; .align() reads the field of the last collected frame."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
                  depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None, overlay=None,
-                 antialias=None):
+                 antialias=None, align=None, align_auto=None):
         self.H, self.W = num_rows, num_cols
         self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
@@ -71,6 +73,32 @@ class FrameStream:
             self.set_overlay(*overlay)
         if antialias is not None:
             self.set_antialias(1, *antialias)
+        if align is not None and align_auto is not None:
+            raise ValueError("FrameStream: align and align_auto are mutually exclusive")
+        if align is not None:
+            self.set_align(1, *align)
+        if align_auto is not None:
+            self.set_align_auto(*align_auto)
+            self.set_align(2)
+
+    def set_align(self, mode, a=0.0, b=0.0, c=0.0):
+        """stm_stream_set_align: the vertical alignment of the stream's frames (device_api.set_align's arguments); the stream's
+        own, independent of the calling thread's; only before the first submit.  Raises ValueError where the library refuses."""
+        if int(lib().stm_stream_set_align(self._h, int(mode), float(a), float(b), float(c))) != 0:
+            raise ValueError("stm_stream_set_align(%d, %g, %g, %g) refused: %s" % (mode, a, b, c, lib().stm_last_error().decode()))
+
+    def set_align_auto(self, radius=16, rate=1.0):
+        """stm_stream_set_align_auto: mode 2's parameters (device_api.set_align_auto's; the state is the stream's own); only before
+        the first submit.  Raises ValueError where the library refuses."""
+        if int(lib().stm_stream_set_align_auto(self._h, int(radius), float(rate))) != 0:
+            raise ValueError("stm_stream_set_align_auto(%d, %g) refused: %s" % (radius, rate, lib().stm_last_error().decode()))
+
+    def align(self):
+        """stm_stream_align: (a, b, c) applied to the most recently collected frame, or None before the first collect."""
+        out = (C.c_float * 3)()
+        if int(lib().stm_stream_align(self._h, C.cast(out, f32p))) != 0:
+            return None
+        return float(out[0]), float(out[1]), float(out[2])
 
     def set_antialias(self, mode, strength=1.0, max_radius=8, gate=1.0):
         """stm_stream_set_antialias: the view antialiasing of the stream's frames (device_api.set_antialias's arguments); the
@@ -265,16 +293,18 @@ def unpacked_eye_shape(frame_rows, frame_cols, packing):
     return ((frame_rows - gap) // 2) * (2 if pk == 3 else 1), frame_cols
 
 
-def _collect(fs, on_depth):
+def _collect(fs, on_depth, on_align=None):
     r = fs.collect()
     if on_depth is not None and r is not None:
         on_depth(r[0], fs.depth())
+    if on_align is not None and r is not None:
+        on_align(r[0], fs.align())
     return r
 
 
 def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None,
                      depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None,
-                     overlay=None, antialias=None):
+                     overlay=None, antialias=None, align=None, align_auto=None, on_align=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
@@ -285,7 +315,8 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
     layout: FrameStream's (the interlaced output is then a quilt).  match: FrameStream's (h, w, disp_scale): the reduced-resolution frame.
     output: FrameStream's (1, matrix): the quilt comes out as NV12, [out_rows * 3 / 2][out_cols].
     overlay: (bgra, x0, y0, disparity), one premultiplied overlay composited into every frame of the sequence (FrameStream.overlay).
-    antialias: FrameStream's (strength, max_radius, gate): view antialiasing of every frame."""
+    antialias: FrameStream's (strength, max_radius, gate): view antialiasing of every frame.  align / align_auto: FrameStream's
+    vertical alignment of every frame's pair; on_align: called with (index, (a, b, c)) after every collected frame."""
     fs = None
     pending = 0
     for sbs in frames:
@@ -295,18 +326,19 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
             if packing is not None:
                 rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
             fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output,
-                             overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]), antialias=antialias)
+                             overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]), antialias=antialias,
+                             align=align, align_auto=align_auto)
             if overlay is not None:
                 fs.overlay(*overlay)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:
-            yield _collect(fs, on_depth)
+            yield _collect(fs, on_depth, on_align)
             pending -= 1
         fs.submit(sbs)
         pending += 1
     while fs is not None and pending:
-        yield _collect(fs, on_depth)
+        yield _collect(fs, on_depth, on_align)
         pending -= 1
     if fs is not None:
         fs.close()

@@ -7,7 +7,7 @@ source, cost slice, aggregated slice, disparity, outliers, occlusion mask, every
 usage: stm_image.py <left.bmp> <right.bmp> <ad coeff> <census coeff> <ndisp> <zerodisp> <ucd> <lcd> <usd> <lsd>
                     <num views> <angle> <out width> <out height> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel]
                     [--linear-warp] [--lens MODE PITCH SLOPE CENTRE] [--quilt TX TY ORDER FILTER]
-                    [--antialias STRENGTH MAX_RADIUS GATE]
+                    [--antialias STRENGTH MAX_RADIUS GATE] [--align A B C | --align-auto RADIUS [RATE]]
 
 --interp (an addition, off by default): the outlier interpolation (host_api.dr_interp) of both maps after region voting, each on
 its own image and outlier map, before --subpixel.
@@ -24,7 +24,10 @@ TY tiles; ORDER bit 0 = tile rows bottom-up, bit 1 = tile 0 holds the leftmost c
 sampler, 1 = the area average) instead of interlaced; <angle> is then ignored.  Excludes --lens.
 --antialias STRENGTH MAX_RADIUS GATE (an addition): view antialiasing (host_api.view_prefilter) -- before the views are rendered each
 image is blurred along its rows by its own final map: a box of 1 + STRENGTH * |disparity| / (<num views> - 1) pixels (STRENGTH in
-[0, 8]), at most MAX_RADIUS (1 .. 16) pixels to a side, using only neighbours whose disparity lies within GATE (>= 0) of the pixel's."""
+[0, 8]), at most MAX_RADIUS (1 .. 16) pixels to a side, using only neighbours whose disparity lies within GATE (>= 0) of the pixel's.
+--align A B C (an addition): the right image is first sampled at row y + A + B u + C v (host_api.align_rows; u, v from the image's
+centre), so that a vertical offset between the two cameras does not reach the row-wise matcher.  --align-auto RADIUS [RATE]: the
+field is measured within +-RADIUS rows (host_api.align_fit) and printed.  The aligned right image is what every later stage sees."""
 import os
 import sys
 
@@ -67,6 +70,32 @@ def main(argv):
             print(__doc__)
             return -1
         del argv[at:at + 4]
+    align, align_auto = None, None
+    try:
+        if "--align" in argv:
+            at = argv.index("--align")
+            align = (float(argv[at + 1]), float(argv[at + 2]), float(argv[at + 3]))
+            if not all(abs(v) < float("inf") for v in align):
+                raise ValueError(align)
+            del argv[at:at + 4]
+        if "--align-auto" in argv:  # one still pair: RATE has nothing to follow and is accepted for symmetry
+            at = argv.index("--align-auto")
+            vals = [argv[at + 1]]
+            if at + 2 < len(argv) and not argv[at + 2].startswith("--"):
+                try:
+                    float(argv[at + 2])
+                    vals.append(argv[at + 2])
+                except ValueError:
+                    pass
+            align_auto = (int(vals[0]),) + tuple(float(v) for v in vals[1:])
+            if not 1 <= align_auto[0] <= 32 or (len(align_auto) > 1 and not 0.0 < align_auto[1] <= 1.0):
+                raise ValueError(align_auto)
+            del argv[at:at + 1 + len(vals)]
+        if align is not None and align_auto is not None:
+            raise ValueError("--align and --align-auto")
+    except (ValueError, IndexError):
+        print(__doc__)
+        return -1
     if len(argv) not in (17, 18):
         print(__doc__)
         return -1
@@ -77,6 +106,12 @@ def main(argv):
     if L.shape != R.shape:
         print("Error! left and right image sizes differ: %s vs %s" % (L.shape, R.shape))
         return -1
+    if align_auto is not None:
+        st, nvalid = api.align_fit(L, R, align_auto[0])
+        align = tuple(float(v) for v in st[1:])
+        print("align: a %.6g b %.6g c %.6g (%d of 32 blocks)" % (align + (nvalid,)))
+    if align is not None:
+        R = api.align_rows(R, *align)
     ad, ce, D, zd = float(a[2]), float(a[3]), int(a[4]), int(a[5])
     ucd, lcd, usd, lsd = float(a[6]), float(a[7]), int(a[8]), int(a[9])
     N, angle, Wo, Ho, ts, th = int(a[10]), float(a[11]), int(a[12]), int(a[13]), int(a[14]), float(a[15])

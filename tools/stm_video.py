@@ -9,6 +9,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--depth GAIN CONV | --depth-auto LO HI [MAX_GAIN CLIP RATE]]
                     [--packing P SWAP FILTER GAP] [--quilt TX TY ORDER FILTER [--nv12-out MATRIX]] [--match H W SCALE [--guided-up]]
                     [--overlay FILE.npy X0 Y0 DISPARITY] [--antialias STRENGTH MAX_RADIUS GATE]
+                    [--align A B C | --align-auto RADIUS [RATE]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -47,6 +48,11 @@ alpha (video.premultiply converts straight alpha) -- composited into every frame
 images are blurred along their rows by a box of 1 + STRENGTH * |displayed disparity| / (<num views> - 1) pixels (STRENGTH in [0, 8],
 1 = one view spacing), at most MAX_RADIUS (1 .. 16) pixels to a side, using only neighbours whose disparity lies within GATE (>= 0) of
 the pixel's own.  Content on the screen plane stays byte-identical; combines with every other option.
+--align A B C (an addition): the vertical alignment of every frame's pair ahead of the matcher (stm_stream_set_align mode 1) -- the
+right eye is sampled at row y + A + B u + C v, u and v counted from the centre of an eye: A rows of constant offset (a pitch
+difference between the lenses), B rows per column (roll), C rows per row (focal length).  --align-auto RADIUS [RATE]: the field is
+measured on every frame on the GPU within +-RADIUS rows (1 .. 32) and followed at RATE (1); each frame's applied field is printed.
+The two options are mutually exclusive; both combine with every input format and every other option.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -200,6 +206,32 @@ def main(argv):
             print(__doc__)
             return -1
         del argv[at:at + 4]
+    align, align_auto = None, None
+    try:
+        if "--align" in argv:
+            at = argv.index("--align")
+            align = (float(argv[at + 1]), float(argv[at + 2]), float(argv[at + 3]))
+            if not all(abs(v) < float("inf") for v in align):
+                raise ValueError(align)
+            del argv[at:at + 4]
+        if "--align-auto" in argv:
+            at = argv.index("--align-auto")
+            vals = [argv[at + 1]]
+            if at + 2 < len(argv) and not argv[at + 2].startswith("--"):
+                try:
+                    float(argv[at + 2])
+                    vals.append(argv[at + 2])
+                except ValueError:
+                    pass
+            align_auto = (int(vals[0]),) + tuple(float(v) for v in vals[1:])
+            if not 1 <= align_auto[0] <= 32 or (len(align_auto) > 1 and not 0.0 < align_auto[1] <= 1.0):
+                raise ValueError(align_auto)
+            del argv[at:at + 1 + len(vals)]
+        if align is not None and align_auto is not None:
+            raise ValueError("--align and --align-auto")
+    except (ValueError, IndexError):
+        print(__doc__)
+        return -1
     if len(argv) not in (16, 17):
         print(__doc__)
         return -1
@@ -225,7 +257,9 @@ def main(argv):
                                                        if depth_auto is not None else None, packing,
                                                        layout=None if quilt is None else (1,) + quilt, match=match,
                                                        output=None if nv12_out is None else (1, nv12_out), overlay=overlay,
-                                                       antialias=antialias):
+                                                       antialias=antialias, align=align, align_auto=align_auto,
+                                                       on_align=(lambda k, f: print("frame %d: align a %.6g b %.6g c %.6g" % ((k,) + f)))
+                                                       if align_auto is not None else None):
         if yuv is not None:  # the frame is [out height * 3 / 2][out width]: the Y plane, then the interleaved UV plane
             yuv.write(inter.tobytes())
             video.write_disparities(out_dir, k, dl, dr)
