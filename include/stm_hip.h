@@ -234,6 +234,32 @@ int         stm_set_align_auto(int radius, float rate, float *d_state);
 /* out_mode = {mode, radius}, out = {a, b, c, rate} as the last accepted calls left them.  A frame stream's own setting is not
  * visible here except during its submit. */
 void        stm_get_align(int out_mode[2], float out[4]);
+/* The calling thread's colour balance between the eyes (an addition: the reference takes graded studio masters.  Two-lens phones and
+ * hand-built rigs have two sensors with different exposure, white balance and tone curves, while the AD half of AD-Census is an
+ * absolute colour difference, the cross arms are built from colour thresholds, and every rendered view blends the two images).
+ * Three per-channel 256-entry tables are applied to the RIGHT eye ahead of the matcher; the left eye is the reference, as with
+ * stm_set_align.  mode 0 = off (the default: not one launch, argument or kernel of any call changes), 1 = given (lut768: B, G, R,
+ * 256 bytes each, copied; no monotonicity demanded), 2 = measured (lut768 ignored; the tables fitted on every frame on the device
+ * from the two eyes' histograms: stm_set_balance_auto, stm_balance_fit).
+ * With mode != 0 the frame calls stm_d_adcensus_stm, _t, _nv12, _2s, _2t, _2nv12 (and the host flavours through them) first write
+ * the unpacked, converted pair, its right eye through the tables, as one side-by-side BGR frame into the workspace (one launch;
+ * mode 2: three small launches before it for the measurement) and then ARE the plain BGR frame call on that frame, packing off,
+ * exactly as under stm_set_align.  With an alignment set as well the balance comes second and measures the aligned pair: two passes
+ * over the pair.  With 0x2000 on a BGR frame the previous frame passes through the same kernel with the CURRENT frame's tables;
+ * on an NV12 frame the history is what the previous call handed out.  Rules under mode != 0: an unpacked BGR frame needs
+ * num_cols_sbs >= 2 * num_cols; mode 2 needs num_rows * num_cols < 2^31.
+ * Returns 0, or -1 with stm_last_error set and the thread's setting unchanged (mode not 0, 1, 2; mode 1 with a null lut768). */
+int         stm_set_balance(int mode, const unsigned char *lut768);
+/* Mode 2's parameters (kept when the mode changes; the defaults are 48, 1, null): max_shift in 0 .. 255, the most levels a table
+ * moves a level by; rate in (0, 1] (1 = every frame on its own; NaN is refused); d_state = 769 ints in device memory, {valid, 768
+ * levels in 1/256 units}, or null.  In mode 2 the frame call runs stm_d_balance_fit's measurement on its input with these
+ * parameters and d_state, and the kernel that applies the tables reads them from that memory: nothing is synchronised or read
+ * back.  A null d_state means scratch memory, with every frame fitted on its own.  A caller resets the history, for a scene cut,
+ * by zeroing `valid`.  Returns 0, or -1 with stm_last_error set and the old parameters in place. */
+int         stm_set_balance_auto(int max_shift, float rate, int *d_state);
+/* out_mode = {mode, max_shift}, *out_rate and out_lut (mode 1's tables; the identity otherwise) as the last accepted calls left
+ * them.  A frame stream's own setting is not visible here except during its submit. */
+void        stm_get_balance(int out_mode[2], float *out_rate, unsigned char out_lut[768]);
 /* The calling thread's output geometry (an addition: the reference shows its views in one form only, sub-pixel interlaced).
  * layout 0 = the interlaced frame (the default; tiles_x, tiles_y, order and filter are ignored, and not one launch, argument or
  * kernel changes), 1 = a quilt: the views side by side as a grid of tiles, whole, for a display that interlaces with its own
@@ -1058,6 +1084,43 @@ int  stm_align_fit(const unsigned char *img_l, const unsigned char *img_r, int n
                    float *state);
 void stm_d_align_fit(const unsigned char *d_img_l, const unsigned char *d_img_r, int num_rows, int num_cols, int elem_sz, int radius,
                      float rate, float *d_state, int *d_valid_blocks, unsigned int *d_profiles, unsigned int *d_sad);
+/* Colour balance as stages (an addition, see stm_set_balance).  Everything is integer arithmetic, so the result depends on no order
+ * of execution and no rounding mode.  N = H * W pixels of one unpacked eye; c is one of B, G, R; v, u, t are levels 0 .. 255.
+ * stm_balance_fit:
+ *   1. Histograms.  h[e][c][v], u32, over every pixel of eye e (0 = left, 1 = right); hist[(e * 3 + c) * 256 + v].  The calls
+ *      refuse H * W >= 2^31.  From here on i64.
+ *   2. Cumulative counts.  C[e][c][v] = sum of h[e][c][t] for t <= v.
+ *   3. Mid-rank match.  m[c][v] = min{u : 2 C[0][c][u] >= 2 C[1][c][v] - h[1][c][v]}; the minimum exists because 2 C[0][c][255] = 2N.
+ *      For two equal eyes m[v] = v at every occupied level.
+ *   4. Offsets, smoothed over +-8 levels and weighted by the right eye's counts.  off[v] = m[v] - v; den[v] = the sum of h[1][c][t]
+ *      over |t - v| <= 8, clipped to 0 .. 255; num[v] = the sum of h[1][c][t] * off[t] over the same range.  Where den[v] > 0:
+ *      s[v] = floor((2 num[v] + den[v]) / (2 den[v])) -- floor division, which rounds half up for negative numerators as well (C's /
+ *      truncates).  Where den[v] = 0: s[v] is the s of the nearest level BELOW v that has den > 0; if there is none, of the nearest
+ *      above (one exists because N >= 1).
+ *   5. Limit and order.  s[v] = clamp(s[v], -max_shift, max_shift); t[v] = clamp(v + s[v], 0, 255); then t[v] = max(t[v], t[v-1]) for
+ *      v = 1 .. 255, so the table never inverts tones.
+ *   6. State.  int32 state[769]: state[0] is the valid flag, state[1 + c * 256 + v] a level in 1/256 units.  With x = 256 t[v]: with no
+ *      history (state[0] == 0) state = x and state[0] = 1; otherwise state += (rate_q * (x - state) + 128) >> 8, an arithmetic
+ *      shift, with rate_q = clamp((int)floorf(rate * 256 + 0.5f), 1, 256) computed once on the host.  The update is
+ *      non-decreasing in both state and x, so it keeps a monotone table monotone.
+ * stm_balance_apply:
+ *   7. lut[c][v] = clamp((state[1 + c*256 + v] + 128) >> 8, 0, 255) where a state is given, else the caller's 768 bytes (B, G, R, 256
+ *      each, no monotonicity demanded).  out.c = lut[c][in.c] for the first three bytes of a pixel; the bytes past the third follow
+ *      stm_align_rows' rules: the device flavour leaves them alone, the host flavour returns them 0.  img_out must not overlap img.
+ * stm_d_balance_fit takes device pointers, synchronises nothing and writes the histograms into d_hist (1536 words) where it is not
+ * null.  The host flavour takes and returns the 769 ints in host memory and returns 0 (-1 on an error).  stm_d_balance_apply takes
+ * lut768 in HOST memory (it travels as a kernel argument) or d_state in device memory; the host flavour takes both in host memory.
+ * Rules: num_rows, num_cols >= 1, num_rows * num_cols < 2^31, elem_sz >= 3, max_shift in 0 .. 255, rate in (0, 1], no null image or
+ * state; for the apply calls exactly one of lut768 and state non-null.  Violations fail through stm_last_error before anything is
+ * launched or written.  Parity is against the numpy statement of these lines in tests/test_balance_ref.py (parity unpinned). */
+int  stm_balance_fit(const unsigned char *img_l, const unsigned char *img_r, int num_rows, int num_cols, int elem_sz, int max_shift,
+                     float rate, int *state);
+void stm_d_balance_fit(const unsigned char *d_img_l, const unsigned char *d_img_r, int num_rows, int num_cols, int elem_sz, int max_shift,
+                       float rate, int *d_state, unsigned int *d_hist);
+void stm_balance_apply(unsigned char *img_out, const unsigned char *img, int num_rows, int num_cols, int elem_sz,
+                       const unsigned char *lut768, const int *state);
+void stm_d_balance_apply(unsigned char *d_img_out, const unsigned char *d_img, int num_rows, int num_cols, int elem_sz,
+                         const unsigned char *lut768, const int *d_state);
 /* View antialiasing: the depth-adaptive prefilter of one image by its own map (an addition, the reference has none: each of its views
  * is a pinhole image at one camera position s, while a lenticular lens shows a band about one view spacing wide.  A scene point of
  * displayed end-to-end disparity e moves e / (N - 1) pixels between adjacent views, so detail finer than that step aliases between
@@ -1202,6 +1265,18 @@ int   stm_stream_set_align_auto(void *stream, int radius, float rate);
 /* out = {a, b, c} applied to the most recently collected frame: in mode 2 the state as that frame's fit left it (copied and
  * downloaded as stm_stream_depth's), in mode 1 the setting, in mode 0 zeros.  Returns 0, or -1 if no frame has been collected yet. */
 int   stm_stream_align(void *stream, float out[3]);
+/* the colour balance of the stream's frames (stm_set_balance's rules; the default is mode 0, and the calling thread's own setting
+ * never reaches a stream's frames).  Kept and installed like the alignment.  stm_stream_set_balance_auto sets mode 2's max_shift
+ * and rate (stm_set_balance_auto's rules; the defaults are 48 and 1); the state is the stream's own: one buffer at a fixed
+ * address, zeroed when mode 2 is first set.  Frame k reads what frame k - 1 wrote, so in mode 2 the two frames in flight run one
+ * after the other on the GPU, as with depth mode 2 and alignment mode 2.  Only before the first submit.  Return 0, or -1 with
+ * stm_last_error set and the stream unchanged. */
+int   stm_stream_set_balance(void *stream, int mode, const unsigned char *lut768);
+int   stm_stream_set_balance_auto(void *stream, int max_shift, float rate);
+/* out_lut = the 768 bytes applied to the most recently collected frame: in mode 2 step 7's tables of the state as that frame's fit
+ * left it (copied per slot and downloaded with the results), in mode 1 the setting, in mode 0 the identity.  Returns 0, or -1 if
+ * no frame has been collected yet. */
+int   stm_stream_balance(void *stream, unsigned char out_lut[768]);
 /* waits for the oldest uncollected frame and copies its results out (NULL = skip).  Returns its index or -1. */
 long  stm_stream_collect(void *stream, float *disp_l, float *disp_r, unsigned char *interlaced);
 /* zero-copy variants (at 1080p the two host copies of submit / collect take longer than the frame does on the GPU):

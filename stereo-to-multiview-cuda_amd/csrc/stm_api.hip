@@ -1043,6 +1043,87 @@ int stm_align_fit(const unsigned char *img_l, const unsigned char *img_r, int nu
     return failed() ? -1 : count;
 }
 
+// =============================================================== colour balance between the eyes: measured and applied as stages
+// (an addition, the reference has none: it takes graded pairs)
+static bool balance_fit_args_ok(const char *fn, const unsigned char *img_l, const unsigned char *img_r, int num_rows, int num_cols, int elem_sz,
+                                int max_shift, float rate, const int *state)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
+    if (!balance_size_ok(fn, num_rows, num_cols) || !balance_auto_params_ok(fn, max_shift, rate)) return false;
+    if (!img_l || !img_r || !state) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: img_l, img_r and state must not be null", fn);
+        fail(msg, "img_l, img_r, state", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
+void stm_d_balance_fit(const unsigned char *d_img_l, const unsigned char *d_img_r, int num_rows, int num_cols, int elem_sz, int max_shift,
+                       float rate, int *d_state, unsigned int *d_hist)
+{
+    if (!balance_fit_args_ok("d_balance_fit", d_img_l, d_img_r, num_rows, num_cols, elem_sz, max_shift, rate, d_state)) return;
+    Workspace::begin(BALANCE_HIST_WORDS * 4 + 8192);
+    uint32_t *hist = d_hist ? d_hist : Workspace::get<uint32_t>(BALANCE_HIST_WORDS);
+    launch_balance_measure(d_state, hist, nullptr, d_img_l, d_img_r, num_rows, num_cols, elem_sz, max_shift, balance_rate_q(rate), false);
+}
+int stm_balance_fit(const unsigned char *img_l, const unsigned char *img_r, int num_rows, int num_cols, int elem_sz, int max_shift, float rate,
+                    int *state)
+{
+    if (!balance_fit_args_ok("balance_fit", img_l, img_r, num_rows, num_cols, elem_sz, max_shift, rate, state)) return -1;
+    const size_t IMG = (size_t)num_rows * num_cols * elem_sz;
+    Workspace::begin(2 * IMG + (BALANCE_HIST_WORDS + BALANCE_STATE_WORDS) * 4 + 8192);
+    const u8 *l = up(img_l, IMG), *r = up(img_r, IMG);
+    int *st = up(state, BALANCE_STATE_WORDS);
+    uint32_t *hist = Workspace::get<uint32_t>(BALANCE_HIST_WORDS);
+    launch_balance_measure(st, hist, nullptr, l, r, num_rows, num_cols, elem_sz, max_shift, balance_rate_q(rate), false);
+    down(state, st, BALANCE_STATE_WORDS);
+    sync();
+    return failed() ? -1 : 0;
+}
+static bool balance_apply_args_ok(const char *fn, const unsigned char *img_out, const unsigned char *img, int num_rows, int num_cols, int elem_sz,
+                                  const unsigned char *lut768, const int *state)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
+    char msg[160];
+    if (!img_out || !img) {
+        snprintf(msg, sizeof msg, "%s: img_out and img must not be null", fn);
+        fail(msg, "img_out, img", __FILE__, __LINE__);
+        return false;
+    }
+    if ((lut768 != nullptr) == (state != nullptr)) {
+        snprintf(msg, sizeof msg, "%s: exactly one of lut768 and state must be given", fn);
+        fail(msg, "lut768, state", __FILE__, __LINE__);
+        return false;
+    }
+    const size_t bytes = (size_t)num_rows * num_cols * elem_sz;
+    if (bytes_overlap(img_out, bytes, img, bytes)) {
+        snprintf(msg, sizeof msg, "%s: img_out must not overlap img", fn);
+        fail(msg, "img_out", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
+void stm_d_balance_apply(unsigned char *d_img_out, const unsigned char *d_img, int num_rows, int num_cols, int elem_sz,
+                         const unsigned char *lut768, const int *d_state)
+{
+    if (!balance_apply_args_ok("d_balance_apply", d_img_out, d_img, num_rows, num_cols, elem_sz, lut768, d_state)) return;
+    launch_balance_frame(d_img_out, nullptr, d_img, num_rows, num_cols, elem_sz, lut768, d_state);
+}
+void stm_balance_apply(unsigned char *img_out, const unsigned char *img, int num_rows, int num_cols, int elem_sz, const unsigned char *lut768,
+                       const int *state)
+{
+    if (!balance_apply_args_ok("balance_apply", img_out, img, num_rows, num_cols, elem_sz, lut768, state)) return;
+    const size_t IMG = (size_t)num_rows * num_cols * elem_sz;
+    Workspace::begin(2 * IMG + BALANCE_STATE_WORDS * 4 + 8192);
+    const u8 *i = up(img, IMG);
+    const int *st = state ? up(state, BALANCE_STATE_WORDS) : nullptr;
+    u8 *o = Workspace::get<u8>(IMG);
+    if (elem_sz > 3) STM_CHECK(hipMemsetAsync(o, 0, IMG, stream())); // bytes past the third come back 0
+    launch_balance_frame(o, nullptr, i, num_rows, num_cols, elem_sz, lut768, st);
+    down(img_out, o, IMG);
+    sync();
+}
+
 // =============================================================== view antialiasing: the prefilter as a stage
 // (an addition, the reference has none: its views are pinhole images whatever the lens shows of them)
 static bool prefilter_args_ok(const char *fn, const unsigned char *img_out, const unsigned char *img, const float *disp, int num_rows,
@@ -1823,6 +1904,50 @@ u8 *align_frame_input(const Align &al, const PackInput &in, const u8 *prev_frame
     return out;
 }
 
+// ---- the colour balance of a frame call's input (stm_set_balance), after the alignment
+// the thread's setting against a frame call's geometry; off: nothing to check, the call is as it was
+bool frame_balance_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, bool bgr_sbs)
+{
+    const Balance bl = balance();
+    if (!bl.mode) return true;
+    if (bgr_sbs && num_cols_sbs < 2 * num_cols) { // both eyes are gathered from the frame
+        char msg[200];
+        snprintf(msg, sizeof msg, "%s: a colour balance is set on this thread (stm_set_balance), which needs num_cols_sbs >= 2 * num_cols", fn);
+        fail(msg, "num_cols_sbs", __FILE__, __LINE__);
+        return false;
+    }
+    return bl.mode != 2 || balance_size_ok(fn, num_rows, num_cols);
+}
+// the workspace the prelude below takes: the balanced frame (and the previous frame's), the histograms, a scratch state
+size_t balance_ws_bytes(size_t IMG, bool prev) { return (prev ? 4 : 2) * IMG + (BALANCE_HIST_WORDS + BALANCE_STATE_WORDS) * 4 + 4096; }
+// The prelude, inside the frame call's Workspace scope, after the alignment's: mode 2 measures the screened frame `in` (the aligned
+// frame where an alignment is on) and updates the state; the unpacked, converted pair, its right eye through the tables, is returned
+// as one side-by-side BGR frame (H x 2 W x elem_sz) in the workspace.  prev_frame != nullptr: the previous BGR frame, of the same
+// geometry, through the same kernel with THIS frame's tables into prev_out.
+u8 *balance_frame_input(const Balance &bl, const PackInput &in, const u8 *prev_frame, int H, int W, int elem_sz, const u8 *&prev_out)
+{
+    const size_t IMG = (size_t)H * W * elem_sz;
+    const int *st = nullptr;
+    if (bl.mode == 2) {
+        int *state = bl.d_state ? bl.d_state : Workspace::get<int>(BALANCE_STATE_WORDS); // scratch: every frame on its own
+        uint32_t *hist = Workspace::get<uint32_t>(BALANCE_HIST_WORDS);
+        launch_balance_measure(state, hist, &in, nullptr, nullptr, H, W, elem_sz, bl.max_shift, balance_rate_q(bl.rate), bl.d_state == nullptr);
+        st = state;
+    }
+    const u8 *lut = st ? nullptr : bl.lut;
+    u8 *out = Workspace::get<u8>(2 * IMG);
+    launch_balance_frame(out, &in, nullptr, H, W, elem_sz, lut, st);
+    prev_out = nullptr;
+    if (prev_frame) {
+        PackInput prev = in;
+        prev.frame = prev_frame;
+        u8 *po = Workspace::get<u8>(2 * IMG);
+        launch_balance_frame(po, &prev, nullptr, H, W, elem_sz, lut, st);
+        prev_out = po;
+    }
+    return out;
+}
+
 // the body of stm_d_adcensus_stm, stm_d_adcensus_stm_t and stm_d_adcensus_stm_nv12; hist != nullptr: the temporal step between
 // the bilateral filter and the renderer; nv != nullptr: the frame comes as NV12 planes (d_img_sbs is null, num_cols_sbs >= 2 W).
 // Every argument has been screened by the caller except the `stages` rules the calls share.
@@ -1859,17 +1984,20 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
     const Packing pack = packing(); // a packed frame (stm_set_packing): the caller has screened its geometry
     if (!frame_align_ok(fn, H, num_cols_sbs, W, !nv && !pack.on())) return;
     const Align aln = align();       // the vertical alignment (stm_set_align), screened above
+    if (!frame_balance_ok(fn, H, num_cols_sbs, W, !nv && !pack.on())) return;
+    const Balance bal = balance();   // the colour balance (stm_set_balance), screened above
     Workspace::begin(((stages & 0x100) ? 13 : 4) * V * 4 + (size_t)(N + 2 + (pack.on() && hist && !nv ? 2 : 0)) * IMG + 168 * HW + (1u << 20) +
                      (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0) + // the un-fused NV12 frame's BGR quilt
                      (antialias().mode == 1 ? 2 * IMG + 512 : 0) +                                  // the prefiltered pair
-                     (aln.mode ? align_ws_bytes(H, IMG, hist && !nv) : 0));                          // the aligned frame(s)
+                     (aln.mode ? align_ws_bytes(H, IMG, hist && !nv) : 0) +                          // the aligned frame(s)
+                     (bal.mode ? balance_ws_bytes(IMG, hist && !nv) : 0));                           // the balanced frame(s)
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
     const bool split_hist = nv != nullptr; // ... and an NV12 frame's history comes as split images
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     uint32_t *pre[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const PackInput pin = {pack, nv != nullptr, d_img_sbs, num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr, nv ? nv->pitch_y : 0,
                            nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0};
-    const bool pack_on = pack.on() && !aln.mode;
+    const bool pack_on = pack.on() && !aln.mode && !bal.mode;
     TemporalHist hist_aligned;
     if (aln.mode) { // from here on the call is the plain BGR frame call on the aligned side-by-side frame
         d_img_sbs = align_frame_input(aln, pin, hist && !nv ? hist->sbs : nullptr, H, W, elem_sz, hist_aligned.sbs);
@@ -1878,6 +2006,20 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
             hist_aligned = *hist;
             hist_aligned.sbs = prev;
             hist = &hist_aligned;
+        }
+        num_cols_sbs = 2 * W;
+        nv = nullptr;
+    }
+    TemporalHist hist_balanced;
+    if (bal.mode) { // after the alignment, on whatever the call now points at; then it is the plain BGR frame call on the balanced frame
+        const PackInput plain = {Packing{0, 0, 0, 0}, false, d_img_sbs, num_cols_sbs, nullptr, nullptr, 0, 0, 0};
+        const bool sbs_hist = hist && !split_hist;
+        d_img_sbs = balance_frame_input(bal, aln.mode ? plain : pin, sbs_hist ? hist->sbs : nullptr, H, W, elem_sz, hist_balanced.sbs);
+        if (sbs_hist) {
+            const u8 *prev = hist_balanced.sbs;
+            hist_balanced = *hist;
+            hist_balanced.sbs = prev;
+            hist = &hist_balanced;
         }
         num_cols_sbs = 2 * W;
         nv = nullptr;
@@ -2159,10 +2301,13 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
     const bool guided = (stages & 0x1000) != 0; // the up-scale between the two: stm_disp_upsample instead of tx_disp_scale
     if (!frame_align_ok(fn, H, num_cols_sbs, W, !nv)) return;
     const Align aln = align(); // the vertical alignment (stm_set_align), screened above
+    if (!frame_balance_ok(fn, H, num_cols_sbs, W, !nv)) return;
+    const Balance bal = balance(); // the colour balance (stm_set_balance), screened above
     Workspace::begin((hslo ? 13 : 4) * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 32 * hw + (1u << 20) + // HSLO: as d_adcensus_stm
                      (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0) +
                      (antialias().mode == 1 ? 2 * IMG + 512 : 0) +                // the prefiltered pair
-                     (aln.mode ? align_ws_bytes(H, IMG, hist && !nv) : 0));        // the aligned frame(s)
+                     (aln.mode ? align_ws_bytes(H, IMG, hist && !nv) : 0) +        // the aligned frame(s)
+                     (bal.mode ? balance_ws_bytes(IMG, hist && !nv) : 0));         // the balanced frame(s)
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
     const bool split_hist = nv != nullptr; // ... and an NV12 frame's history comes as split images
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
@@ -2177,6 +2322,21 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
             hist_aligned = *hist;
             hist_aligned.sbs = prev;
             hist = &hist_aligned;
+        }
+        num_cols_sbs = 2 * W;
+        nv = nullptr;
+    }
+    TemporalHist hist_balanced;
+    if (bal.mode) { // after the alignment; then it is the plain BGR reduced-resolution frame call on the balanced side-by-side frame
+        const PackInput pin = {Packing{0, 0, 0, 0}, nv != nullptr, d_img_sbs, num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr,
+                               nv ? nv->pitch_y : 0, nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0};
+        const bool sbs_hist = hist && !split_hist;
+        d_img_sbs = balance_frame_input(bal, pin, sbs_hist ? hist->sbs : nullptr, H, W, elem_sz, hist_balanced.sbs);
+        if (sbs_hist) {
+            const u8 *prev = hist_balanced.sbs;
+            hist_balanced = *hist;
+            hist_balanced.sbs = prev;
+            hist = &hist_balanced;
         }
         num_cols_sbs = 2 * W;
         nv = nullptr;
@@ -2233,6 +2393,7 @@ void reduced_frame_host(const char *fn, unsigned char *img_sbs, float *disp_l, f
         return;
     if (!frame_layout_ok(fn, stages, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return; // before the caller's arrays are written
     if (!frame_align_ok(fn, num_rows, num_cols_sbs, num_cols, true)) return;
+    if (!frame_balance_ok(fn, num_rows, num_cols_sbs, num_cols, true)) return;
     size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
     size_t out_sz = frame_out_bytes(num_rows_out, num_cols_out, elem_sz); // stm_set_output: the NV12 surface
     const size_t need[4] = {sbs_sz, out_sz, HW * 4, HW * 4};
@@ -2542,6 +2703,7 @@ void stm_adcensus_stm(unsigned char *img_sbs, float *disp_l, float *disp_r, unsi
     if (packing_unsupported("adcensus_stm")) return;
     if (!frame_layout_ok("adcensus_stm", 3, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return; // before the caller's arrays are written
     if (!frame_align_ok("adcensus_stm", num_rows, num_cols_sbs, num_cols, true)) return;
+    if (!frame_balance_ok("adcensus_stm", num_rows, num_cols_sbs, num_cols, true)) return;
     size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
     size_t out_sz = frame_out_bytes(num_rows_out, num_cols_out, elem_sz); // stm_set_output: the NV12 surface
     // own buffers are cached outside the workspace: the pipeline call below re-carves the workspace

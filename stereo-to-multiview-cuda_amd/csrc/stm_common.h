@@ -426,6 +426,34 @@ void launch_align_measure(float *state, int *nvalid, uint32_t *prof, uint32_t *s
 // the field applied: a screened frame (in != nullptr) as the aligned side-by-side BGR frame `out` (H x 2 W x elem_sz, the left eye
 // copied), or the one image img (H x W x elem_sz) into out; state != nullptr: a, b, c are read from state[1 .. 3] on the device
 void launch_align_frame(u8 *out, const PackInput *in, const u8 *img, int H, int W, int elem_sz, float a, float b, float c, const float *state);
+// The colour balance between the eyes (stm_set_balance / stm_set_balance_auto, include/stm_hip.h): mode 0 = off (not one launch
+// changes), 1 = given (the right eye through the three tables lut), 2 = measured (the tables fitted on each frame on the device).
+// One per host thread, next to the alignment; a frame stream installs its own copy around its frame calls.
+struct Balance {
+    int mode;
+    u8 lut[768];        // mode 1: B, G, R, 256 bytes each (the identity otherwise)
+    int max_shift;      // mode 2: the largest shift of a level, the state's update rate
+    float rate;
+    int *d_state;       // mode 2: {valid, 768 levels in 1/256} in device memory; null = scratch, every frame on its own
+};
+Balance balance_default();
+Balance balance();
+void set_balance(const Balance &b);
+// the argument rules of the two settings; false with the error recorded
+bool balance_params_ok(const char *fn, int mode, const u8 *lut768);
+bool balance_auto_params_ok(const char *fn, int max_shift, float rate);
+// the measurement's frame rule: num_rows * num_cols < 2^31; false with the error recorded
+bool balance_size_ok(const char *fn, int num_rows, int num_cols);
+// rate in 1/256: clamp((int)floorf(rate * 256 + 0.5f), 1, 256)
+int balance_rate_q(float rate);
+constexpr size_t BALANCE_HIST_WORDS = 1536, BALANCE_STATE_WORDS = 769;
+// the measurement (stm_kernels_balance.hip) of a screened frame (in != nullptr) or of two unpacked images H x W x elem_sz: the six
+// histograms into hist (1536 words), the fit and the update of `state` (769 ints); fresh: the state's history is ignored
+void launch_balance_measure(int *state, uint32_t *hist, const PackInput *in, const u8 *img_l, const u8 *img_r, int H, int W, int elem_sz,
+                            int max_shift, int rate_q, bool fresh);
+// the tables applied: a screened frame (in != nullptr) as the balanced side-by-side BGR frame `out` (H x 2 W x elem_sz, the left eye
+// copied), or the one image img (H x W x elem_sz) into out; the tables are lut768 (host memory), or state's (device) where state != nullptr
+void launch_balance_frame(u8 *out, const PackInput *in, const u8 *img, int H, int W, int elem_sz, const u8 *lut768, const int *state);
 // aggregation on the matrix pipe (stm_kernels_aggm.hip): the frame pipeline's cost -> H -> V, V -> H + WTA
 struct PQViews { // both views of a frame; a / b = the two PQ volumes of a view
     const uint32_t *pk[2], *cen[2];

@@ -528,6 +528,63 @@ bool align_size_ok(const char *fn, int num_rows, int num_cols)
     }
     return true;
 }
+// the calling thread's colour balance (stm_set_balance, stm_set_balance_auto)
+Balance balance_default()
+{
+    Balance b;
+    b.mode = 0;
+    for (int i = 0; i < 768; ++i) b.lut[i] = (u8)i;
+    b.max_shift = 48;
+    b.rate = 1.0f;
+    b.d_state = nullptr;
+    return b;
+}
+static thread_local Balance g_balance = balance_default();
+Balance balance() { return g_balance; }
+void set_balance(const Balance &b) { g_balance = b; }
+bool balance_params_ok(const char *fn, int mode, const u8 *lut768)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (mode < 0 || mode > 2) {
+        snprintf(msg, sizeof msg, "%s: balance mode = %d, must be 0 (off), 1 (given) or 2 (measured)", fn, mode);
+        arg = "mode";
+    } else if (mode == 1 && !lut768) { // off / measured: lut768 is ignored
+        snprintf(msg, sizeof msg, "%s: lut768 must not be null in mode 1", fn);
+        arg = "lut768";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+bool balance_auto_params_ok(const char *fn, int max_shift, float rate)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (max_shift < 0 || max_shift > 255) {
+        snprintf(msg, sizeof msg, "%s: max_shift = %d, must be in 0 .. 255", fn, max_shift);
+        arg = "max_shift";
+    } else if (!(rate > 0.0f && rate <= 1.0f)) { // NaN fails the comparison
+        snprintf(msg, sizeof msg, "%s: rate = %g, must be in (0, 1]", fn, (double)rate);
+        arg = "rate";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+bool balance_size_ok(const char *fn, int num_rows, int num_cols)
+{
+    if ((long long)num_rows * (long long)num_cols < (1ll << 31)) return true;
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: the balance measurement needs num_rows * num_cols < 2147483648 (got %d x %d)", fn, num_rows, num_cols);
+    fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
+    return false;
+}
+int balance_rate_q(float rate)
+{
+    const int q = (int)floorf(rate * 256.0f + 0.5f);
+    return q < 1 ? 1 : q > 256 ? 256 : q;
+}
 bool depth_auto_params_ok(const char *fn, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate)
 {
     char msg[200];
@@ -802,6 +859,32 @@ void stm_get_align(int out_mode[2], float out[4])
     const stm::Align al = stm::align();
     out_mode[0] = al.mode; out_mode[1] = al.radius;
     out[0] = al.a; out[1] = al.b; out[2] = al.c; out[3] = al.rate;
+}
+int stm_set_balance(int mode, const unsigned char *lut768)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (!stm::balance_params_ok("set_balance", mode, lut768)) return -1; // the thread's setting stays as it was
+    stm::Balance b = stm::balance(); // mode 2's parameters (stm_set_balance_auto) are kept
+    b.mode = mode;
+    for (int i = 0; i < 768; ++i) b.lut[i] = mode == 1 ? lut768[i] : (unsigned char)i;
+    stm::set_balance(b);
+    return 0;
+}
+int stm_set_balance_auto(int max_shift, float rate, int *d_state)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (!stm::balance_auto_params_ok("set_balance_auto", max_shift, rate)) return -1;
+    stm::Balance b = stm::balance();
+    b.max_shift = max_shift; b.rate = rate; b.d_state = d_state;
+    stm::set_balance(b);
+    return 0;
+}
+void stm_get_balance(int out_mode[2], float *out_rate, unsigned char out_lut[768])
+{
+    const stm::Balance b = stm::balance();
+    out_mode[0] = b.mode; out_mode[1] = b.max_shift;
+    *out_rate = b.rate;
+    memcpy(out_lut, b.lut, 768);
 }
 void stm_set_agg_variant(int v)
 {

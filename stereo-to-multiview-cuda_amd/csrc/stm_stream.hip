@@ -24,6 +24,7 @@ struct Slot {
     u8 *d_img_l = nullptr, *d_img_r = nullptr; // NV12 input: the slot's converted split images (the other slot's frame reads them as its history)
     float *d_rec = nullptr, *h_rec = nullptr; // depth mode 2: the state as this slot's frame left it (16 bytes), and its download
     float *d_arec = nullptr, *h_arec = nullptr; // align mode 2: likewise the alignment's state
+    int *d_brec = nullptr, *h_brec = nullptr;   // balance mode 2: likewise the balance's state (769 ints)
     u8 *h_ov = nullptr, *d_ov = nullptr;      // stm_stream_set_overlay: the slot's pinned and device copy of the overlay's pixels
     long ov_gen = 0;                          // ... and which stm_stream_overlay call they hold (0 = none yet)
     hipEvent_t ev_in, ev_done, ev_out;
@@ -64,6 +65,8 @@ struct FrameStream {
     float *d_depth_state = nullptr; // mode 2: the state every frame updates, at one address for both slots' graphs
     stm::Align align = {0, 0.0f, 0.0f, 0.0f, 16, 1.0f, nullptr}; // stm_stream_set_align / _auto: the stream's own vertical alignment
     float *d_align_state = nullptr; // align mode 2: the state every frame updates, at one address for both slots' graphs
+    stm::Balance balance = stm::balance_default(); // stm_stream_set_balance / _auto: the stream's own colour balance
+    int *d_balance_state = nullptr; // balance mode 2: the state every frame updates, at one address for both slots' graphs
     int ov_max_rows = 0, ov_max_cols = 0; // stm_stream_set_overlay: the largest overlay the slots' copies hold ((0, 0) = off)
     u8 *ov_pixels = nullptr;              // stm_stream_overlay: the pixels of the overlay in force (host memory of the stream's own)
     stm::Overlay ov = {0, nullptr, 0, 0, 0, 0, 0.0f}; // ... and its arguments; mode 0 = none.  d_overlay is filled in per slot
@@ -101,6 +104,12 @@ struct AlignScope {
     stm::Align saved;
     explicit AlignScope(const stm::Align &a) : saved(stm::align()) { stm::set_align(a); }
     ~AlignScope() { stm::set_align(saved); }
+};
+
+struct BalanceScope {
+    stm::Balance saved;
+    explicit BalanceScope(const stm::Balance &b) : saved(stm::balance()) { stm::set_balance(b); }
+    ~BalanceScope() { stm::set_balance(saved); }
 };
 
 struct AntialiasScope {
@@ -639,6 +648,66 @@ int stm_stream_align(void *h, float out[3])
     else { out[0] = f->align.a; out[1] = f->align.b; out[2] = f->align.c; }
     return 0;
 }
+// The colour balance every frame of the stream is conditioned with (stm_set_balance's rules; the default is mode 0).  Kept and
+// installed like the alignment.  Mode 2 allocates the stream's state and the slots' records.  Only before the first submit.
+int stm_stream_set_balance(void *h, int mode, const unsigned char *lut768)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (!stm::balance_params_ok("stream_set_balance", mode, lut768)) return -1;
+    if (mode != 0 && !f->packing.on() && f->in_format == 0 && f->Wsbs < 2 * f->W) {
+        stm::fail("stream_set_balance: a colour balance needs num_cols_sbs >= 2 * num_cols", "num_cols_sbs", __FILE__, __LINE__);
+        return -1;
+    }
+    if (mode == 2 && !stm::balance_size_ok("stream_set_balance", f->H, f->W)) return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_balance: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    const size_t bytes = stm::BALANCE_STATE_WORDS * 4;
+    if (mode == 2 && !f->d_balance_state) {
+        STM_CHECK(hipMalloc((void **)&f->d_balance_state, bytes));
+        STM_CHECK(hipMemset(f->d_balance_state, 0, bytes)); // valid = 0: the first frame starts the history
+        for (Slot &s : f->slot) {
+            STM_CHECK(hipMalloc((void **)&s.d_brec, bytes));
+            STM_CHECK(hipHostMalloc((void **)&s.h_brec, bytes, hipHostMallocDefault));
+        }
+        if (stm::failed()) return -1;
+    }
+    f->balance.mode = mode;
+    for (int i = 0; i < 768; ++i) f->balance.lut[i] = mode == 1 ? lut768[i] : (unsigned char)i;
+    f->balance.d_state = f->d_balance_state;
+    return 0;
+}
+int stm_stream_set_balance_auto(void *h, int max_shift, float rate)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (!stm::balance_auto_params_ok("stream_set_balance_auto", max_shift, rate)) return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_balance_auto: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    f->balance.max_shift = max_shift;
+    f->balance.rate = rate;
+    return 0;
+}
+// the tables applied to the most recently collected frame (mode 2: step 7 of stm_balance_apply on the slot's record of the state)
+int stm_stream_balance(void *h, unsigned char out_lut[768])
+{
+    FrameStream *f = (FrameStream *)h;
+    if (f->collected == 0) return -1;
+    const Slot &s = f->slot[(f->collected - 1) & 1];
+    for (int i = 0; i < 768; ++i) {
+        if (f->balance.mode == 2) {
+            const int v = (s.h_brec[1 + i] + 128) >> 8;
+            out_lut[i] = (unsigned char)(v < 0 ? 0 : v > 255 ? 255 : v);
+        } else {
+            out_lut[i] = f->balance.lut[i];
+        }
+    }
+    return 0;
+}
 // gain and conv applied to the most recently collected frame
 int stm_stream_depth(void *h, float out[2])
 {
@@ -673,6 +742,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     // depth mode 2: frame k's fit reads the state frame k - 1 wrote, so its compute waits for the other slot's frame as well
     const bool depth_auto = f->depth.mode == 2;
     const bool align_auto = f->align.mode == 2; // likewise the alignment's state
+    const bool balance_auto = f->balance.mode == 2; // ... and the colour balance's
     // In NV12 mode the history is the other slot's converted split images (d_img_l / d_img_r), which no upload touches, and this
     // slot's d_in was last read by this slot's own previous frame, collected before the slot was handed out again: the upload
     // waits for nothing.  This frame's compute still waits for the other slot's frame: it reads that frame's images and maps, and
@@ -690,7 +760,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     }
     STM_CHECK(hipEventRecord(s.ev_in, f->s_in));
     STM_CHECK(hipStreamWaitEvent(s.s_compute, s.ev_in, 0));
-    if (history || ((depth_auto || align_auto) && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
+    if (history || ((depth_auto || align_auto || balance_auto) && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
     void *prev = stm_get_stream();
     LensScope lens_scope(f->lens);
     LayoutScope layout_scope(f->layout);
@@ -698,6 +768,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     DepthScope depth_scope(f->depth);
     AntialiasScope antialias_scope(f->antialias);
     AlignScope align_scope(f->align);
+    BalanceScope balance_scope(f->balance);
     PackingScope packing_scope(f->packing);
     OverlayOffScope overlay_scope;
     stm_set_stream(s.s_compute);
@@ -784,6 +855,8 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     // the state as this frame left it, before ev_done lets the next frame's fit update it
     if (depth_auto) STM_CHECK(hipMemcpyAsync(s.d_rec, f->d_depth_state, 16, hipMemcpyDeviceToDevice, s.s_compute));
     if (align_auto) STM_CHECK(hipMemcpyAsync(s.d_arec, f->d_align_state, 16, hipMemcpyDeviceToDevice, s.s_compute));
+    if (balance_auto)
+        STM_CHECK(hipMemcpyAsync(s.d_brec, f->d_balance_state, stm::BALANCE_STATE_WORDS * 4, hipMemcpyDeviceToDevice, s.s_compute));
     STM_CHECK(hipEventRecord(s.ev_done, s.s_compute));
     STM_CHECK(hipStreamWaitEvent(f->s_out, s.ev_done, 0));
     STM_CHECK(hipMemcpyAsync(s.h_dl, s.d_dl, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
@@ -791,6 +864,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     STM_CHECK(hipMemcpyAsync(s.h_out, s.d_out, f->out_bytes, hipMemcpyDeviceToHost, f->s_out));
     if (depth_auto) STM_CHECK(hipMemcpyAsync(s.h_rec, s.d_rec, 16, hipMemcpyDeviceToHost, f->s_out));
     if (align_auto) STM_CHECK(hipMemcpyAsync(s.h_arec, s.d_arec, 16, hipMemcpyDeviceToHost, f->s_out));
+    if (balance_auto) STM_CHECK(hipMemcpyAsync(s.h_brec, s.d_brec, stm::BALANCE_STATE_WORDS * 4, hipMemcpyDeviceToHost, f->s_out));
     STM_CHECK(hipEventRecord(s.ev_out, f->s_out));
     if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
     if (stm::failed()) return -1; // error mode 1: the frame was not (completely) enqueued
@@ -856,12 +930,15 @@ void stm_stream_destroy(void *h)
         if (s.h_rec) STM_CHECK(hipHostFree(s.h_rec));
         if (s.d_arec) STM_CHECK(hipFree(s.d_arec));
         if (s.h_arec) STM_CHECK(hipHostFree(s.h_arec));
+        if (s.d_brec) STM_CHECK(hipFree(s.d_brec));
+        if (s.h_brec) STM_CHECK(hipHostFree(s.h_brec));
         if (s.h_ov) STM_CHECK(hipHostFree(s.h_ov));
         if (s.d_ov) STM_CHECK(hipFree(s.d_ov));
     }
     free(f->ov_pixels);
     if (f->d_depth_state) STM_CHECK(hipFree(f->d_depth_state));
     if (f->d_align_state) STM_CHECK(hipFree(f->d_align_state));
+    if (f->d_balance_state) STM_CHECK(hipFree(f->d_balance_state));
     stm::ws_private_destroy(f->slot[0].ws);
     STM_CHECK(hipStreamDestroy(f->slot[0].s_compute));
     if (f->overlap) {

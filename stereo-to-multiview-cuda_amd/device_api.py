@@ -390,6 +390,71 @@ def d_align_fit(img_l, img_r, radius, rate, state, valid_blocks=None, profiles=N
                           _p(sad) if sad is not None else None)
 
 
+def _lut768(lut):
+    """a (3, 256) or (768,) table of bytes as a ctypes array the library copies from"""
+    import numpy as np
+    a = np.ascontiguousarray(lut)
+    if a.dtype != np.uint8 or a.size != 768:
+        raise ValueError("a balance table is 768 bytes of uint8 (B, G, R, 256 each), got %s %s" % (a.dtype, a.shape))
+    return (C.c_uint8 * 768).from_buffer_copy(a.tobytes())
+
+
+def set_balance(mode, lut=None):
+    """stm_set_balance: the calling thread's colour balance between the eyes, applied to every frame call's input ahead of the
+    matcher (after the alignment).  mode 0 = off (the default), 1 = given: the right eye through lut, a uint8 array of (3, 256)
+    (B, G, R), 2 = measured: the tables fitted on every frame on the GPU with set_balance_auto's parameters.  Raises ValueError
+    where the library refuses."""
+    buf = _lut768(lut) if lut is not None else None
+    if int(lib().stm_set_balance(int(mode), buf)) != 0:
+        raise ValueError("stm_set_balance(%d) refused: %s" % (mode, lib().stm_last_error().decode()))
+
+
+def set_balance_auto(max_shift=48, rate=1.0, state=None):
+    """stm_set_balance_auto: mode 2's parameters -- the most levels a table moves a level by (0 .. 255), the rate at which the
+    tables follow a frame's fit, and `state`: an int32 tensor of 769 elements on the GPU, {valid, 768 levels in 1/256}, which
+    carries the history from frame to frame (zero `valid` to reset it) -- the caller keeps it alive while the setting is in use;
+    None = every frame on its own.  Raises ValueError where the library refuses."""
+    if state is not None:
+        assert state.is_cuda and state.dtype == torch.int32 and state.is_contiguous() and state.numel() == 769
+    if int(lib().stm_set_balance_auto(int(max_shift), float(rate), _p(state) if state is not None else None)) != 0:
+        raise ValueError("stm_set_balance_auto(%d, %g) refused: %s" % (max_shift, rate, lib().stm_last_error().decode()))
+
+
+def get_balance():
+    """stm_get_balance: the calling thread's (mode, max_shift, rate, lut) as the library holds it; lut a (3, 256) uint8 array"""
+    import numpy as np
+    m = (C.c_int * 2)()
+    r = C.c_float()
+    t = (C.c_uint8 * 768)()
+    lib().stm_get_balance(m, C.byref(r), t)
+    return int(m[0]), int(m[1]), float(r.value), np.frombuffer(bytes(t), np.uint8).reshape(3, 256).copy()
+
+
+def d_balance_fit(img_l, img_r, max_shift, rate, state, hist=None):
+    """stm_d_balance_fit: the measurement of the colour balance as a stage -- the two unpacked images (uint8 [H][W][E] on the GPU)
+    into six histograms, the fit, the update of `state` (int32, 769 elements on the GPU) in place; nothing synchronised.  hist
+    (int32 [2][3][256]) receives the histograms where given."""
+    H, W, E = img_l.shape
+    for t in (img_l, img_r):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    assert state.is_cuda and state.dtype == torch.int32 and state.is_contiguous() and state.numel() == 769
+    assert hist is None or (hist.is_cuda and hist.dtype == torch.int32 and hist.is_contiguous() and hist.numel() == 1536)
+    _use_current_stream()
+    lib().stm_d_balance_fit(_p(img_l), _p(img_r), H, W, E, int(max_shift), float(rate), _p(state), _p(hist) if hist is not None else None)
+
+
+def d_balance_apply(out, img, lut=None, state=None):
+    """stm_d_balance_apply: img (uint8 [H][W][E] on the GPU) through the three tables into out, which must not overlap img; only
+    bytes 0 .. 2 of a pixel are written.  The tables are lut (a uint8 array of (3, 256) in host memory) or those of state (int32, 769
+    elements on the GPU): exactly one of the two."""
+    H, W, E = img.shape
+    for t in (out, img):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    assert state is None or (state.is_cuda and state.dtype == torch.int32 and state.is_contiguous() and state.numel() == 769)
+    _use_current_stream()
+    lib().stm_d_balance_apply(_p(out), _p(img), H, W, E, _lut768(lut) if lut is not None else None, _p(state) if state is not None else None)
+
+
 def d_view_prefilter(out, img, disp, num_views, strength=1.0, max_radius=8, gate=1.0, gain=1.0, conv=0.0):
     """stm_d_view_prefilter: img (uint8 [H][W][E] on the GPU) filtered by its own map disp (float32 [H][W]) into out, which must not
     overlap img; only bytes 0 .. 2 of a pixel are written.  gain, conv: the depth budget the views are rendered with (set_depth)."""

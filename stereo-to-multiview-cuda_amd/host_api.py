@@ -422,6 +422,47 @@ def align_fit(img_l, img_r, radius=16, rate=1.0, state=None):
     return st, n
 
 
+def balance_fit(img_l, img_r, max_shift=48, rate=1.0, state=None):
+    """The measurement of the colour balance between the eyes (stm_balance_fit; an addition, the reference takes graded pairs): the
+    three per-channel tables that bring the right image's histograms onto the left image's, folded into `state` = (valid, 768 levels
+    in 1/256) (None = no history).  Returns the new state as an int32 array of 769; nothing passed in is modified."""
+    img_l, pl = _u8(img_l)
+    img_r, pr = _u8(img_r)
+    H, W, E = img_l.shape
+    assert img_r.shape == (H, W, E)
+    st = np.zeros(769, np.int32) if state is None else np.array(state, dtype=np.int32, order="C")
+    assert st.shape == (769,)
+    if int(lib().stm_balance_fit(pl, pr, H, W, E, int(max_shift), float(rate), st.ctypes.data_as(C.POINTER(C.c_int)))) != 0:
+        raise ValueError("stm_balance_fit refused: %s" % lib().stm_last_error().decode())
+    return st
+
+
+def balance_lut(state):
+    """the (3, 256) uint8 tables of a state: clamp((level + 128) >> 8, 0, 255) (stm_balance_apply's step 7)"""
+    st = np.asarray(state, np.int32)[1:].astype(np.int64)
+    return np.clip((st + 128) >> 8, 0, 255).astype(np.uint8).reshape(3, 256)
+
+
+def balance_apply(img, lut=None, state=None):
+    """The colour balance applied to one image (stm_balance_apply): the first three bytes of every pixel of img [H][W][E] through
+    the tables -- lut, uint8 (3, 256) in B, G, R order, or those of state (int32, 769): exactly one of the two.  Returns the
+    [H][W][E] image (bytes of a pixel past the third are 0); nothing passed in is modified."""
+    img, pi = _u8(img)
+    H, W, E = img.shape
+    out = np.zeros((H, W, E), np.uint8)
+    pl = ps = None
+    if lut is not None:
+        lut = np.ascontiguousarray(lut, dtype=np.uint8)
+        assert lut.size == 768
+        pl = lut.ctypes.data_as(u8p)
+    if state is not None:
+        state = np.ascontiguousarray(state, dtype=np.int32)
+        assert state.shape == (769,)
+        ps = state.ctypes.data_as(C.POINTER(C.c_int))
+    lib().stm_balance_apply(out.ctypes.data_as(u8p), pi, H, W, E, pl, ps)
+    return out
+
+
 def tx_scale(img, out_rows, out_cols):
     """d_tx_scale.h:17-18 (bilinear resize)."""
     img, pi = _u8(img)

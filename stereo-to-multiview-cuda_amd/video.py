@@ -32,11 +32,14 @@ class FrameStream:
     antialias = (strength, max_radius, gate): view antialiasing (set_antialias mode 1) -- both images filtered by their own maps
     before the views are rendered from them; None = off.  align = (a, b, c): the right eye of every frame sampled at row
     y + a + b u + c v ahead of the matcher (set_align mode 1); align_auto = (radius[, rate]): the field measured on every frame on
-    the GPU (mode 2); at most one of the two; .align() reads the field of the last collected frame."""
+    the GPU (mode 2); at most one of the two; .align() reads the field of the last collected frame.  balance = a uint8 array of
+    (3, 256): the right eye of every frame through these tables (B, G, R) ahead of the matcher, after the alignment (set_balance mode
+    1); balance_auto = (max_shift[, rate]): the tables fitted on every frame on the GPU (mode 2); at most one of the two; .balance()
+    reads the tables of the last collected frame."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
                  depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None, overlay=None,
-                 antialias=None, align=None, align_auto=None):
+                 antialias=None, align=None, align_auto=None, balance=None, balance_auto=None):
         self.H, self.W = num_rows, num_cols
         self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
@@ -80,6 +83,39 @@ class FrameStream:
         if align_auto is not None:
             self.set_align_auto(*align_auto)
             self.set_align(2)
+        if balance is not None and balance_auto is not None:
+            raise ValueError("FrameStream: balance and balance_auto are mutually exclusive")
+        if balance is not None:
+            self.set_balance(1, balance)
+        if balance_auto is not None:
+            self.set_balance_auto(*balance_auto)
+            self.set_balance(2)
+
+    def set_balance(self, mode, lut=None):
+        """stm_stream_set_balance: the colour balance of the stream's frames (device_api.set_balance's arguments); the stream's
+        own, independent of the calling thread's; only before the first submit.  Raises ValueError where the library refuses."""
+        buf = None
+        if lut is not None:
+            a = np.ascontiguousarray(lut)
+            if a.dtype != np.uint8 or a.size != 768:
+                raise ValueError("a balance table is 768 bytes of uint8 (B, G, R, 256 each), got %s %s" % (a.dtype, a.shape))
+            buf = (C.c_uint8 * 768).from_buffer_copy(a.tobytes())
+        if int(lib().stm_stream_set_balance(self._h, int(mode), buf)) != 0:
+            raise ValueError("stm_stream_set_balance(%d) refused: %s" % (mode, lib().stm_last_error().decode()))
+
+    def set_balance_auto(self, max_shift=48, rate=1.0):
+        """stm_stream_set_balance_auto: mode 2's parameters (device_api.set_balance_auto's; the state is the stream's own); only
+        before the first submit.  Raises ValueError where the library refuses."""
+        if int(lib().stm_stream_set_balance_auto(self._h, int(max_shift), float(rate))) != 0:
+            raise ValueError("stm_stream_set_balance_auto(%d, %g) refused: %s" % (max_shift, rate, lib().stm_last_error().decode()))
+
+    def balance(self):
+        """stm_stream_balance: the (3, 256) uint8 tables applied to the most recently collected frame, or None before the first
+        collect."""
+        out = (C.c_uint8 * 768)()
+        if int(lib().stm_stream_balance(self._h, out)) != 0:
+            return None
+        return np.frombuffer(bytes(out), np.uint8).reshape(3, 256).copy()
 
     def set_align(self, mode, a=0.0, b=0.0, c=0.0):
         """stm_stream_set_align: the vertical alignment of the stream's frames (device_api.set_align's arguments); the stream's
@@ -293,8 +329,45 @@ def unpacked_eye_shape(frame_rows, frame_cols, packing):
     return ((frame_rows - gap) // 2) * (2 if pk == 3 else 1), frame_cols
 
 
-def _collect(fs, on_depth, on_align=None):
+def take_balance_options(argv):
+    """The two drivers' --balance FILE.npy (768 bytes of uint8: B, G, R, 256 each) and --balance-auto [MAX_SHIFT RATE] (both numbers
+    or neither: 48 and 1), removed from argv.  Returns (tables as a (3, 256) array or None, (max_shift, rate) or None); raises
+    ValueError or IndexError for a malformed option, an unreadable or misshapen file, a value out of range, or both options."""
+    balance, balance_auto = None, None
+    if "--balance" in argv:
+        at = argv.index("--balance")
+        try:
+            a = np.load(argv[at + 1], allow_pickle=False)
+        except OSError as e:
+            raise ValueError(str(e))
+        if a.dtype != np.uint8 or a.size != 768:
+            raise ValueError("--balance: %s holds %s %s, not 768 bytes of uint8" % (argv[at + 1], a.dtype, a.shape))
+        balance = np.ascontiguousarray(a).reshape(3, 256)
+        del argv[at:at + 2]
+    if "--balance-auto" in argv:
+        at = argv.index("--balance-auto")
+        vals = []
+        for tok in argv[at + 1:at + 3]:
+            try:
+                float(tok)
+            except ValueError:
+                break
+            vals.append(tok)
+        if len(vals) == 1:
+            raise ValueError("--balance-auto takes MAX_SHIFT and RATE, or neither")
+        balance_auto = (int(vals[0]), float(vals[1])) if vals else (48, 1.0)
+        if not 0 <= balance_auto[0] <= 255 or not 0.0 < balance_auto[1] <= 1.0:
+            raise ValueError(balance_auto)
+        del argv[at:at + 1 + len(vals)]
+    if balance is not None and balance_auto is not None:
+        raise ValueError("--balance and --balance-auto")
+    return balance, balance_auto
+
+
+def _collect(fs, on_depth, on_align=None, on_balance=None):
     r = fs.collect()
+    if on_balance is not None and r is not None:
+        on_balance(r[0], fs.balance())
     if on_depth is not None and r is not None:
         on_depth(r[0], fs.depth())
     if on_align is not None and r is not None:
@@ -304,7 +377,8 @@ def _collect(fs, on_depth, on_align=None):
 
 def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None,
                      depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None,
-                     overlay=None, antialias=None, align=None, align_auto=None, on_align=None):
+                     overlay=None, antialias=None, align=None, align_auto=None, on_align=None, balance=None, balance_auto=None,
+                     on_balance=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
@@ -316,7 +390,8 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
     output: FrameStream's (1, matrix): the quilt comes out as NV12, [out_rows * 3 / 2][out_cols].
     overlay: (bgra, x0, y0, disparity), one premultiplied overlay composited into every frame of the sequence (FrameStream.overlay).
     antialias: FrameStream's (strength, max_radius, gate): view antialiasing of every frame.  align / align_auto: FrameStream's
-    vertical alignment of every frame's pair; on_align: called with (index, (a, b, c)) after every collected frame."""
+    vertical alignment of every frame's pair; on_align: called with (index, (a, b, c)) after every collected frame.  balance /
+    balance_auto: FrameStream's colour balance of every frame's pair; on_balance: called with (index, tables) likewise."""
     fs = None
     pending = 0
     for sbs in frames:
@@ -327,18 +402,18 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
                 rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
             fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output,
                              overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]), antialias=antialias,
-                             align=align, align_auto=align_auto)
+                             align=align, align_auto=align_auto, balance=balance, balance_auto=balance_auto)
             if overlay is not None:
                 fs.overlay(*overlay)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:
-            yield _collect(fs, on_depth, on_align)
+            yield _collect(fs, on_depth, on_align, on_balance)
             pending -= 1
         fs.submit(sbs)
         pending += 1
     while fs is not None and pending:
-        yield _collect(fs, on_depth, on_align)
+        yield _collect(fs, on_depth, on_align, on_balance)
         pending -= 1
     if fs is not None:
         fs.close()

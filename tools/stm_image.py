@@ -8,6 +8,7 @@ usage: stm_image.py <left.bmp> <right.bmp> <ad coeff> <census coeff> <ndisp> <ze
                     <num views> <angle> <out width> <out height> <thresh_s> <thresh_h> [out dir] [--interp] [--subpixel]
                     [--linear-warp] [--lens MODE PITCH SLOPE CENTRE] [--quilt TX TY ORDER FILTER]
                     [--antialias STRENGTH MAX_RADIUS GATE] [--align A B C | --align-auto RADIUS [RATE]]
+                    [--balance FILE.npy | --balance-auto [MAX_SHIFT RATE]]
 
 --interp (an addition, off by default): the outlier interpolation (host_api.dr_interp) of both maps after region voting, each on
 its own image and outlier map, before --subpixel.
@@ -27,7 +28,11 @@ image is blurred along its rows by its own final map: a box of 1 + STRENGTH * |d
 [0, 8]), at most MAX_RADIUS (1 .. 16) pixels to a side, using only neighbours whose disparity lies within GATE (>= 0) of the pixel's.
 --align A B C (an addition): the right image is first sampled at row y + A + B u + C v (host_api.align_rows; u, v from the image's
 centre), so that a vertical offset between the two cameras does not reach the row-wise matcher.  --align-auto RADIUS [RATE]: the
-field is measured within +-RADIUS rows (host_api.align_fit) and printed.  The aligned right image is what every later stage sees."""
+field is measured within +-RADIUS rows (host_api.align_fit) and printed.  The aligned right image is what every later stage sees.
+--balance FILE.npy (an addition): the right image then goes through the three tables of FILE.npy (768 bytes of uint8: B, G, R, 256
+each; host_api.balance_apply), so that an exposure or white-balance difference between the two cameras reaches neither the matcher
+nor the views.  --balance-auto [MAX_SHIFT RATE]: the tables are fitted from the two images' histograms (host_api.balance_fit),
+moving no level by more than MAX_SHIFT (48); one still pair: RATE has nothing to follow and is accepted for symmetry."""
 import os
 import sys
 
@@ -96,6 +101,13 @@ def main(argv):
     except (ValueError, IndexError):
         print(__doc__)
         return -1
+    try:
+        import stm_amd  # noqa: F401
+        from stm_amd import video
+        balance, balance_auto = video.take_balance_options(argv)
+    except (ValueError, IndexError):
+        print(__doc__)
+        return -1
     if len(argv) not in (17, 18):
         print(__doc__)
         return -1
@@ -112,6 +124,11 @@ def main(argv):
         print("align: a %.6g b %.6g c %.6g (%d of 32 blocks)" % (align + (nvalid,)))
     if align is not None:
         R = api.align_rows(R, *align)
+    if balance_auto is not None:
+        balance = api.balance_lut(api.balance_fit(L, R, balance_auto[0]))
+        print("balance: B %d %d %d G %d %d %d R %d %d %d" % tuple(int(balance[c, v]) for c in range(3) for v in (64, 128, 192)))
+    if balance is not None:
+        R = api.balance_apply(R, balance)
     ad, ce, D, zd = float(a[2]), float(a[3]), int(a[4]), int(a[5])
     ucd, lcd, usd, lsd = float(a[6]), float(a[7]), int(a[8]), int(a[9])
     N, angle, Wo, Ho, ts, th = int(a[10]), float(a[11]), int(a[12]), int(a[13]), int(a[14]), float(a[15])

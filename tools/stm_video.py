@@ -9,7 +9,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--depth GAIN CONV | --depth-auto LO HI [MAX_GAIN CLIP RATE]]
                     [--packing P SWAP FILTER GAP] [--quilt TX TY ORDER FILTER [--nv12-out MATRIX]] [--match H W SCALE [--guided-up]]
                     [--overlay FILE.npy X0 Y0 DISPARITY] [--antialias STRENGTH MAX_RADIUS GATE]
-                    [--align A B C | --align-auto RADIUS [RATE]]
+                    [--align A B C | --align-auto RADIUS [RATE]] [--balance FILE.npy | --balance-auto [MAX_SHIFT RATE]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -53,6 +53,11 @@ right eye is sampled at row y + A + B u + C v, u and v counted from the centre o
 difference between the lenses), B rows per column (roll), C rows per row (focal length).  --align-auto RADIUS [RATE]: the field is
 measured on every frame on the GPU within +-RADIUS rows (1 .. 32) and followed at RATE (1); each frame's applied field is printed.
 The two options are mutually exclusive; both combine with every input format and every other option.
+--balance FILE.npy (an addition): the colour balance between the eyes (stm_stream_set_balance mode 1) -- the right eye of every
+frame goes through the three tables of FILE.npy (768 bytes of uint8: B, G, R, 256 each) ahead of the matcher, after the alignment.
+--balance-auto [MAX_SHIFT RATE]: the tables are fitted on every frame on the GPU from the two eyes' histograms, moving no level by
+more than MAX_SHIFT (0 .. 255; 48) and followed at RATE (1); each frame's tables are printed at the levels 64, 128 and 192.  The
+two options are mutually exclusive; both combine with every input format and every other option.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -232,6 +237,13 @@ def main(argv):
     except (ValueError, IndexError):
         print(__doc__)
         return -1
+    try:
+        import stm_amd  # noqa: F401
+        from stm_amd import video
+        balance, balance_auto = video.take_balance_options(argv)
+    except (ValueError, IndexError):
+        print(__doc__)
+        return -1
     if len(argv) not in (16, 17):
         print(__doc__)
         return -1
@@ -259,7 +271,11 @@ def main(argv):
                                                        output=None if nv12_out is None else (1, nv12_out), overlay=overlay,
                                                        antialias=antialias, align=align, align_auto=align_auto,
                                                        on_align=(lambda k, f: print("frame %d: align a %.6g b %.6g c %.6g" % ((k,) + f)))
-                                                       if align_auto is not None else None):
+                                                       if align_auto is not None else None,
+                                                       balance=balance, balance_auto=balance_auto,
+                                                       on_balance=(lambda k, t: print("frame %d: balance B %d %d %d G %d %d %d R %d %d %d" % (
+                                                           (k,) + tuple(int(t[c, v]) for c in range(3) for v in (64, 128, 192)))))
+                                                       if balance_auto is not None else None):
         if yuv is not None:  # the frame is [out height * 3 / 2][out width]: the Y plane, then the interleaved UV plane
             yuv.write(inter.tobytes())
             video.write_disparities(out_dir, k, dl, dr)
