@@ -184,7 +184,7 @@ int         stm_set_depth(int mode, float gain, float conv);
  * d_state = four floats in device memory, {valid, gain, conv, 0}, or null.  In mode 2 the frame call runs stm_d_depth_fit on the
  * maps it renders from (the up-scaled maps of the reduced frame, the stabilised maps of 0x2000) with these parameters and d_state,
  * and the renderer of the same frame reads gain and conv from that memory: nothing is synchronised or read back.  A null d_state
- * means scratch memory, with every frame fitted on its own.  A caller resets the history, for a scene cut, by zeroing `valid`.
+ * means scratch memory, with every frame fitted on its own.  A caller resets the history, for a scene cut, by zeroing `valid` (stm_set_cut does it on the device).
  * Returns 0, or -1 with stm_last_error set and the old parameters in place. */
 int         stm_set_depth_auto(float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate, float *d_state);
 /* The calling thread's view antialiasing (an addition; stm_view_prefilter has the definition and the reason).  The depth budget above
@@ -228,7 +228,7 @@ int         stm_set_align(int mode, float a, float b, float c);
  * in (0, 1] (1 = every frame on its own); d_state = four floats in device memory, {valid, a, b, c}, or null.  In mode 2 the frame
  * call runs stm_d_align_fit's measurement on its input with these parameters and d_state, and the kernel that applies the field
  * reads a, b, c from that memory: nothing is synchronised or read back.  A null d_state means scratch memory, with every frame
- * fitted on its own.  A caller resets the history, for a scene cut, by zeroing `valid`.  Returns 0, or -1 with stm_last_error set
+ * fitted on its own.  A caller resets the history, for a scene cut, by zeroing `valid` (stm_set_cut does it on the device).  Returns 0, or -1 with stm_last_error set
  * and the old parameters in place. */
 int         stm_set_align_auto(int radius, float rate, float *d_state);
 /* out_mode = {mode, radius}, out = {a, b, c, rate} as the last accepted calls left them.  A frame stream's own setting is not
@@ -255,11 +255,33 @@ int         stm_set_balance(int mode, const unsigned char *lut768);
  * levels in 1/256 units}, or null.  In mode 2 the frame call runs stm_d_balance_fit's measurement on its input with these
  * parameters and d_state, and the kernel that applies the tables reads them from that memory: nothing is synchronised or read
  * back.  A null d_state means scratch memory, with every frame fitted on its own.  A caller resets the history, for a scene cut,
- * by zeroing `valid`.  Returns 0, or -1 with stm_last_error set and the old parameters in place. */
+ * by zeroing `valid` (stm_set_cut does it on the device).  Returns 0, or -1 with stm_last_error set and the old parameters in place. */
 int         stm_set_balance_auto(int max_shift, float rate, int *d_state);
 /* out_mode = {mode, max_shift}, *out_rate and out_lut (mode 1's tables; the identity otherwise) as the last accepted calls left
  * them.  A frame stream's own setting is not visible here except during its submit. */
 void        stm_get_balance(int out_mode[2], float *out_rate, unsigned char out_lut[768]);
+/* The calling thread's shot-change detector (an addition: the reference keeps nothing from frame to frame.  The three recursive
+ * states above -- stm_set_depth_auto's, stm_set_align_auto's, stm_set_balance_auto's -- follow a sequence at a `rate`, and with any
+ * rate < 1 the first frames of a new shot would be conditioned by the previous shot's numbers).  mode 0 = off (the default: the
+ * other arguments are ignored, and not one launch, argument or kernel of any call changes), 1 = on: d_state = 260 ints in device
+ * memory, {valid, cut, since, score, sig[256]} (stm_cut_detect), the caller's, zeroed at the start; null is refused, since without
+ * history there is nothing to detect.
+ * With mode 1 the frame calls stm_d_adcensus_stm, _t, _nv12, _2s, _2t, _2nv12 (and the host flavours through them) first run
+ * stm_d_cut_detect's three launches on the left eye of their full-resolution input, read straight from the frame (BGR or NV12, any
+ * packing), ahead of the alignment's measurement.  The reset pointers are the d_state of depth mode 2 (where the call renders),
+ * alignment mode 2 and balance mode 2, each only where that mode is in force for the call and the pointer is not null (a null one
+ * means scratch memory and has no history to lose).  On a cut their `valid` words are zero before their fits run, so each fit starts
+ * afresh on that frame; nothing is synchronised or read back.  The caller reads the flag from d_state[1] when it likes (an encoder
+ * behind stm_set_output places a key frame there).  0x2000 is untouched: its colour gate already refuses to blend across a cut.
+ * Rules under mode 1: num_rows, num_cols >= 4 and num_rows * num_cols < 2^31 in every frame call.
+ * Known limits: dissolves and fades are not cuts (the recursive filters follow them as they follow anything gradual); a global
+ * exposure step of about 16 levels can score as a cut, and a false cut costs one frame fitted on its own.
+ * Returns 0, or -1 with stm_last_error set and the thread's setting unchanged (mode not 0 or 1; in mode 1 thresh_permille outside
+ * 1 .. 1000, min_gap outside 1 .. 2^20, a null d_state). */
+int         stm_set_cut(int mode, int thresh_permille, int min_gap, int *d_state);
+/* out = {mode, thresh_permille, min_gap} as the last accepted calls left them (before any: 0, 370, 1).  A frame stream's own
+ * setting is not visible here except during its submit. */
+void        stm_get_cut(int out[3]);
 /* The calling thread's output geometry (an addition: the reference shows its views in one form only, sub-pixel interlaced).
  * layout 0 = the interlaced frame (the default; tiles_x, tiles_y, order and filter are ignored, and not one launch, argument or
  * kernel changes), 1 = a quilt: the views side by side as a grid of tiles, whole, for a display that interlaces with its own
@@ -1121,6 +1143,29 @@ void stm_balance_apply(unsigned char *img_out, const unsigned char *img, int num
                        const unsigned char *lut768, const int *state);
 void stm_d_balance_apply(unsigned char *d_img_out, const unsigned char *d_img, int num_rows, int num_cols, int elem_sz,
                          const unsigned char *lut768, const int *d_state);
+/* Shot changes as a stage (an addition, see stm_set_cut).  Everything is integer arithmetic; no result depends on the order of
+ * execution.  The input is the LEFT eye of a frame, unpacked and converted as the other conditioning kernels see it: H x W pixels,
+ * N = H * W.  The left eye is the reference of both the alignment and the balance, so the signature depends on neither.
+ * State: int32 state[260] = {valid, cut, since, score, sig[256]}.
+ *   1. Signature.  Y = (B + 2 G + R) >> 2; bin = Y >> 4; cell = ((4 y) / H) * 4 + (4 x) / W, a 4 x 4 grid, floor division;
+ *      sig[cell * 16 + bin] counts the pixel, as u32.  The 256 counts sum to N.
+ *   2. Score.  History exists when state[0] != 0 and the stored signature sums to N: a state left by a frame of another size counts as
+ *      no history.  Without history score = 1000.  With history D = sum |sig[i] - old_sig[i]| in i64 (D <= 2N) and
+ *      score = (1000 * D) / (2 * N), in 0 .. 1000.
+ *   3. Decision.  since' = min(state[2] + 1, 2^30); cut = no history || (score >= thresh_permille && since' >= min_gap); then
+ *      state = {1, cut, cut ? 0 : since', score, sig}.  The signature is stored on every frame, on a suppressed cut as well.
+ *   4. Resets.  On a cut each non-null pointer of up to three receives one 32-bit zero: zero is the `valid` word of a float state and
+ *      of an int state alike.  Otherwise the pointers are not touched.
+ * stm_cut_detect takes the image in host memory and the state in and out, and returns the cut flag (-1 on an error).
+ * stm_d_cut_detect takes device pointers, synchronises nothing and writes the signature into d_sig (256 words) where it is not null.
+ * Rules: num_rows, num_cols >= 4 (no cell is empty), num_rows * num_cols < 2^31, elem_sz >= 3, thresh_permille in 1 .. 1000,
+ * min_gap in 1 .. 2^20 (1: any frame may be a cut; larger values keep a photographer's flash from being two cuts), no null image
+ * or state.  Violations fail through stm_last_error before anything is launched or written.  Known limits: dissolves and fades
+ * are not cuts; a global exposure step of about 16 levels can score as one.  Parity is against the numpy statement of these lines in
+ * tests/test_cut_ref.py (parity unpinned). */
+int  stm_cut_detect(const unsigned char *img_l, int num_rows, int num_cols, int elem_sz, int thresh_permille, int min_gap, int *state);
+void stm_d_cut_detect(const unsigned char *d_img_l, int num_rows, int num_cols, int elem_sz, int thresh_permille, int min_gap, int *d_state,
+                      void *d_reset0, void *d_reset1, void *d_reset2, unsigned int *d_sig);
 /* View antialiasing: the depth-adaptive prefilter of one image by its own map (an addition, the reference has none: each of its views
  * is a pinhole image at one camera position s, while a lenticular lens shows a band about one view spacing wide.  A scene point of
  * displayed end-to-end disparity e moves e / (N - 1) pixels between adjacent views, so detail finer than that step aliases between
@@ -1277,6 +1322,16 @@ int   stm_stream_set_balance_auto(void *stream, int max_shift, float rate);
  * left it (copied per slot and downloaded with the results), in mode 1 the setting, in mode 0 the identity.  Returns 0, or -1 if
  * no frame has been collected yet. */
 int   stm_stream_balance(void *stream, unsigned char out_lut[768]);
+/* the shot-change detector of the stream's frames (stm_set_cut's rules; the default is mode 0, and the calling thread's own setting
+ * never reaches a stream's frames).  The state is the stream's own: one buffer at a fixed address, zeroed when mode 1 is first set,
+ * so the slots' captured graphs stay valid.  The reset pointers are the stream's own depth, alignment and balance states, for those
+ * whose mode is 2; they are resolved at submit, so the setters may come in any order.  Frame k reads what frame k - 1 wrote, so with
+ * mode 1 the two frames in flight run one after the other on the GPU, as with depth mode 2.  Only before the first submit.  Returns
+ * 0, or -1 with stm_last_error set and the stream unchanged. */
+int   stm_stream_set_cut(void *stream, int mode, int thresh_permille, int min_gap);
+/* out = {cut, score, since} of the most recently collected frame (12 bytes copied per slot after the decision and downloaded with
+ * the results, as stm_stream_depth's); in mode 0 {0, 0, 0}.  Returns 0, or -1 if no frame has been collected yet. */
+int   stm_stream_cut(void *stream, int out[3]);
 /* waits for the oldest uncollected frame and copies its results out (NULL = skip).  Returns its index or -1. */
 long  stm_stream_collect(void *stream, float *disp_l, float *disp_r, unsigned char *interlaced);
 /* zero-copy variants (at 1080p the two host copies of submit / collect take longer than the frame does on the GPU):

@@ -58,6 +58,8 @@ PROTOS = {
     "stm_set_balance": ([i, u8p], i),
     "stm_set_balance_auto": ([i, f, vp], i),
     "stm_get_balance": ([C.POINTER(C.c_int), f32p, u8p], None),
+    "stm_set_cut": ([i, i, i, vp], i),
+    "stm_get_cut": ([C.POINTER(C.c_int)], None),
     "stm_ci_adcensus": ([u8p, u8p, f32pp, f32pp, f, f, i, i, i, i, i], None),
     "stm_d_ci_adcensus": ([vp, vp, vp, vp, f32pp, f32pp, vp, f, f, i, i, i, i, i], None),
     "stm_ca_cross": ([u8p, u8pp, f32pp, f32pp, f, f, i, i, i, i, i, i], None),
@@ -140,6 +142,8 @@ PROTOS = {
     "stm_d_balance_fit": ([vp, vp, i, i, i, i, f, vp, vp], None),
     "stm_balance_apply": ([u8p, u8p, i, i, i, u8p, C.POINTER(C.c_int)], None),
     "stm_d_balance_apply": ([vp, vp, i, i, i, u8p, vp], None),
+    "stm_cut_detect": ([u8p, i, i, i, i, i, C.POINTER(C.c_int)], i),
+    "stm_d_cut_detect": ([vp, i, i, i, i, i, vp, vp, vp, vp, vp], None),
     "stm_view_prefilter": ([u8p, u8p, f32p, i, i, i, i, f, i, f, f, f], None),
     "stm_d_view_prefilter": ([vp, vp, vp, i, i, i, i, f, i, f, f, f], None),
     "stm_d_tx_scale": ([u8p, u8p, i, i, i, i, i], None),
@@ -165,6 +169,8 @@ PROTOS = {
     "stm_stream_set_balance": ([C.c_void_p, i, u8p], i),
     "stm_stream_set_balance_auto": ([C.c_void_p, i, f], i),
     "stm_stream_balance": ([C.c_void_p, u8p], i),
+    "stm_stream_set_cut": ([C.c_void_p, i, i, i], i),
+    "stm_stream_cut": ([C.c_void_p, C.POINTER(C.c_int)], i),
     "stm_stream_collect": ([C.c_void_p, f32p, f32p, u8p], C.c_long),
     "stm_stream_input_buffer": ([C.c_void_p], C.c_void_p),
     "stm_stream_collect_view": ([C.c_void_p, C.POINTER(f32p), C.POINTER(f32p), C.POINTER(u8p)], C.c_long),

@@ -1124,6 +1124,43 @@ void stm_balance_apply(unsigned char *img_out, const unsigned char *img, int num
     sync();
 }
 
+// =============================================================== shot changes: the detector as a stage
+// (an addition, the reference has none: it keeps no state from frame to frame)
+static bool cut_args_ok(const char *fn, const unsigned char *img_l, int num_rows, int num_cols, int elem_sz, int thresh_permille, int min_gap,
+                        const int *state)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 4}, {"num_cols", num_cols, 4}, {"elem_sz", elem_sz, 3}})) return false;
+    if (!cut_size_ok(fn, num_rows, num_cols) || !cut_params_ok(fn, thresh_permille, min_gap)) return false;
+    if (!img_l || !state) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: img_l and state must not be null", fn);
+        fail(msg, "img_l, state", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
+void stm_d_cut_detect(const unsigned char *d_img_l, int num_rows, int num_cols, int elem_sz, int thresh_permille, int min_gap, int *d_state,
+                      void *d_reset0, void *d_reset1, void *d_reset2, unsigned int *d_sig)
+{
+    if (!cut_args_ok("d_cut_detect", d_img_l, num_rows, num_cols, elem_sz, thresh_permille, min_gap, d_state)) return;
+    Workspace::begin(CUT_SIG_WORDS * 4 + 8192);
+    uint32_t *sig = d_sig ? d_sig : Workspace::get<uint32_t>(CUT_SIG_WORDS);
+    launch_cut_detect(d_state, sig, nullptr, d_img_l, num_rows, num_cols, elem_sz, thresh_permille, min_gap, d_reset0, d_reset1, d_reset2);
+}
+int stm_cut_detect(const unsigned char *img_l, int num_rows, int num_cols, int elem_sz, int thresh_permille, int min_gap, int *state)
+{
+    if (!cut_args_ok("cut_detect", img_l, num_rows, num_cols, elem_sz, thresh_permille, min_gap, state)) return -1;
+    const size_t IMG = (size_t)num_rows * num_cols * elem_sz;
+    Workspace::begin(IMG + (CUT_SIG_WORDS + CUT_STATE_WORDS) * 4 + 8192);
+    const u8 *l = up(img_l, IMG);
+    int *st = up(state, CUT_STATE_WORDS);
+    uint32_t *sig = Workspace::get<uint32_t>(CUT_SIG_WORDS);
+    launch_cut_detect(st, sig, nullptr, l, num_rows, num_cols, elem_sz, thresh_permille, min_gap, nullptr, nullptr, nullptr);
+    down(state, st, CUT_STATE_WORDS);
+    sync();
+    return failed() ? -1 : state[1];
+}
+
 // =============================================================== view antialiasing: the prefilter as a stage
 // (an addition, the reference has none: its views are pinhole images whatever the lens shows of them)
 static bool prefilter_args_ok(const char *fn, const unsigned char *img_out, const unsigned char *img, const float *disp, int num_rows,
@@ -1948,6 +1985,22 @@ u8 *balance_frame_input(const Balance &bl, const PackInput &in, const u8 *prev_f
     return out;
 }
 
+// ---- the shot-change detector of a frame call's input (stm_set_cut), ahead of the alignment's measurement
+// the thread's setting against a frame call's geometry; off: nothing to check, the call is as it was
+bool frame_cut_ok(const char *fn, int num_rows, int num_cols) { return !cut().mode || cut_size_ok(fn, num_rows, num_cols); }
+size_t cut_ws_bytes() { return CUT_SIG_WORDS * 4 + 512; }
+// The prelude, inside the frame call's Workspace scope, first of all: the three launches on the screened full-resolution frame `in`.
+// The reset pointers are the caller's states of depth mode 2 (where the call renders), alignment mode 2 and balance mode 2; a null
+// one is scratch memory and has no history to lose.
+void cut_frame_input(const Cut &ct, const PackInput &in, int H, int W, int elem_sz, bool renders, const Align &aln, const Balance &bal)
+{
+    const Depth dp = depth();
+    uint32_t *sig = Workspace::get<uint32_t>(CUT_SIG_WORDS);
+    launch_cut_detect(ct.d_state, sig, &in, nullptr, H, W, elem_sz, ct.thresh_permille, ct.min_gap,
+                      renders && dp.mode == 2 ? (void *)dp.d_state : nullptr, aln.mode == 2 ? (void *)aln.d_state : nullptr,
+                      bal.mode == 2 ? (void *)bal.d_state : nullptr);
+}
+
 // the body of stm_d_adcensus_stm, stm_d_adcensus_stm_t and stm_d_adcensus_stm_nv12; hist != nullptr: the temporal step between
 // the bilateral filter and the renderer; nv != nullptr: the frame comes as NV12 planes (d_img_sbs is null, num_cols_sbs >= 2 W).
 // Every argument has been screened by the caller except the `stages` rules the calls share.
@@ -1986,11 +2039,14 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
     const Align aln = align();       // the vertical alignment (stm_set_align), screened above
     if (!frame_balance_ok(fn, H, num_cols_sbs, W, !nv && !pack.on())) return;
     const Balance bal = balance();   // the colour balance (stm_set_balance), screened above
+    if (!frame_cut_ok(fn, H, W)) return;
+    const Cut ct = cut();            // the shot-change detector (stm_set_cut), screened above
     Workspace::begin(((stages & 0x100) ? 13 : 4) * V * 4 + (size_t)(N + 2 + (pack.on() && hist && !nv ? 2 : 0)) * IMG + 168 * HW + (1u << 20) +
                      (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0) + // the un-fused NV12 frame's BGR quilt
                      (antialias().mode == 1 ? 2 * IMG + 512 : 0) +                                  // the prefiltered pair
                      (aln.mode ? align_ws_bytes(H, IMG, hist && !nv) : 0) +                          // the aligned frame(s)
-                     (bal.mode ? balance_ws_bytes(IMG, hist && !nv) : 0));                           // the balanced frame(s)
+                     (bal.mode ? balance_ws_bytes(IMG, hist && !nv) : 0) +                           // the balanced frame(s)
+                     (ct.mode ? cut_ws_bytes() : 0));                                                // the detector's signature
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
     const bool split_hist = nv != nullptr; // ... and an NV12 frame's history comes as split images
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
@@ -1998,6 +2054,7 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
     const PackInput pin = {pack, nv != nullptr, d_img_sbs, num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr, nv ? nv->pitch_y : 0,
                            nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0};
     const bool pack_on = pack.on() && !aln.mode && !bal.mode;
+    if (ct.mode) cut_frame_input(ct, pin, H, W, elem_sz, (stages & 0xff) >= 3, aln, bal); // before any state's fit runs
     TemporalHist hist_aligned;
     if (aln.mode) { // from here on the call is the plain BGR frame call on the aligned side-by-side frame
         d_img_sbs = align_frame_input(aln, pin, hist && !nv ? hist->sbs : nullptr, H, W, elem_sz, hist_aligned.sbs);
@@ -2303,15 +2360,23 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
     const Align aln = align(); // the vertical alignment (stm_set_align), screened above
     if (!frame_balance_ok(fn, H, num_cols_sbs, W, !nv)) return;
     const Balance bal = balance(); // the colour balance (stm_set_balance), screened above
+    if (!frame_cut_ok(fn, H, W)) return;
+    const Cut ct = cut(); // the shot-change detector (stm_set_cut), screened above
     Workspace::begin((hslo ? 13 : 4) * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 32 * hw + (1u << 20) + // HSLO: as d_adcensus_stm
                      (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0) +
                      (antialias().mode == 1 ? 2 * IMG + 512 : 0) +                // the prefiltered pair
                      (aln.mode ? align_ws_bytes(H, IMG, hist && !nv) : 0) +        // the aligned frame(s)
-                     (bal.mode ? balance_ws_bytes(IMG, hist && !nv) : 0));         // the balanced frame(s)
+                     (bal.mode ? balance_ws_bytes(IMG, hist && !nv) : 0) +         // the balanced frame(s)
+                     (ct.mode ? cut_ws_bytes() : 0));                              // the detector's signature
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
     const bool split_hist = nv != nullptr; // ... and an NV12 frame's history comes as split images
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     u8 *low_l = Workspace::get<u8>(hw * elem_sz), *low_r = Workspace::get<u8>(hw * elem_sz);
+    if (ct.mode) { // before any state's fit runs, on the full-resolution input
+        const PackInput pin = {Packing{0, 0, 0, 0}, nv != nullptr, d_img_sbs, num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr,
+                               nv ? nv->pitch_y : 0, nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0};
+        cut_frame_input(ct, pin, H, W, elem_sz, (stages & 0xff) >= 3, aln, bal);
+    }
     TemporalHist hist_aligned;
     if (aln.mode) { // from here on the call is the plain BGR reduced-resolution frame call on the aligned side-by-side frame
         const PackInput pin = {Packing{0, 0, 0, 0}, nv != nullptr, d_img_sbs, num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr,
@@ -2394,6 +2459,7 @@ void reduced_frame_host(const char *fn, unsigned char *img_sbs, float *disp_l, f
     if (!frame_layout_ok(fn, stages, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return; // before the caller's arrays are written
     if (!frame_align_ok(fn, num_rows, num_cols_sbs, num_cols, true)) return;
     if (!frame_balance_ok(fn, num_rows, num_cols_sbs, num_cols, true)) return;
+    if (!frame_cut_ok(fn, num_rows, num_cols)) return;
     size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
     size_t out_sz = frame_out_bytes(num_rows_out, num_cols_out, elem_sz); // stm_set_output: the NV12 surface
     const size_t need[4] = {sbs_sz, out_sz, HW * 4, HW * 4};
@@ -2704,6 +2770,7 @@ void stm_adcensus_stm(unsigned char *img_sbs, float *disp_l, float *disp_r, unsi
     if (!frame_layout_ok("adcensus_stm", 3, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return; // before the caller's arrays are written
     if (!frame_align_ok("adcensus_stm", num_rows, num_cols_sbs, num_cols, true)) return;
     if (!frame_balance_ok("adcensus_stm", num_rows, num_cols_sbs, num_cols, true)) return;
+    if (!frame_cut_ok("adcensus_stm", num_rows, num_cols)) return;
     size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
     size_t out_sz = frame_out_bytes(num_rows_out, num_cols_out, elem_sz); // stm_set_output: the NV12 surface
     // own buffers are cached outside the workspace: the pipeline call below re-carves the workspace

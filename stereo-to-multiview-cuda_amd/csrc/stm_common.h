@@ -454,6 +454,28 @@ void launch_balance_measure(int *state, uint32_t *hist, const PackInput *in, con
 // the tables applied: a screened frame (in != nullptr) as the balanced side-by-side BGR frame `out` (H x 2 W x elem_sz, the left eye
 // copied), or the one image img (H x W x elem_sz) into out; the tables are lut768 (host memory), or state's (device) where state != nullptr
 void launch_balance_frame(u8 *out, const PackInput *in, const u8 *img, int H, int W, int elem_sz, const u8 *lut768, const int *state);
+// The shot-change detector (stm_set_cut, include/stm_hip.h): mode 0 = off (not one launch changes), 1 = on: every frame call first
+// takes the left eye's signature, decides against the state and, on a cut, zeroes the `valid` word of the recursive states in force.
+// One per host thread, next to the balance; a frame stream installs its own copy around its frame calls.
+struct Cut {
+    int mode;
+    int thresh_permille, min_gap;
+    int *d_state;       // mode 1: {valid, cut, since, score, sig[256]} in device memory, never null
+};
+Cut cut_default();
+Cut cut();
+void set_cut(const Cut &c);
+// the argument rules of the detector's two numbers; false with the error recorded
+bool cut_params_ok(const char *fn, int thresh_permille, int min_gap);
+// the detector's frame rule: num_rows, num_cols >= 4 and num_rows * num_cols < 2^31; false with the error recorded
+bool cut_size_ok(const char *fn, int num_rows, int num_cols);
+constexpr size_t CUT_SIG_WORDS = 256, CUT_STATE_WORDS = 260;
+constexpr int CUT_DEFAULT_THRESH = 370; // the geometric mean of the largest non-cut and the smallest cut score
+// the detector (stm_kernels_cut.hip) on the left eye of a screened frame (in != nullptr) or on one unpacked image H x W x elem_sz:
+// the signature into sig (256 words), the decision and the update of `state` (260 ints); on a cut one 32-bit zero into each
+// non-null reset pointer
+void launch_cut_detect(int *state, uint32_t *sig, const PackInput *in, const u8 *img_l, int H, int W, int elem_sz, int thresh_permille,
+                       int min_gap, void *reset0, void *reset1, void *reset2);
 // aggregation on the matrix pipe (stm_kernels_aggm.hip): the frame pipeline's cost -> H -> V, V -> H + WTA
 struct PQViews { // both views of a frame; a / b = the two PQ volumes of a view
     const uint32_t *pk[2], *cen[2];

@@ -585,6 +585,35 @@ int balance_rate_q(float rate)
     const int q = (int)floorf(rate * 256.0f + 0.5f);
     return q < 1 ? 1 : q > 256 ? 256 : q;
 }
+// the calling thread's shot-change detector (stm_set_cut)
+Cut cut_default() { return Cut{0, CUT_DEFAULT_THRESH, 1, nullptr}; }
+static thread_local Cut g_cut = cut_default();
+Cut cut() { return g_cut; }
+void set_cut(const Cut &c) { g_cut = c; }
+bool cut_params_ok(const char *fn, int thresh_permille, int min_gap)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (thresh_permille < 1 || thresh_permille > 1000) {
+        snprintf(msg, sizeof msg, "%s: thresh_permille = %d, must be in 1 .. 1000", fn, thresh_permille);
+        arg = "thresh_permille";
+    } else if (min_gap < 1 || min_gap > (1 << 20)) {
+        snprintf(msg, sizeof msg, "%s: min_gap = %d, must be in 1 .. 1048576", fn, min_gap);
+        arg = "min_gap";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+bool cut_size_ok(const char *fn, int num_rows, int num_cols)
+{
+    if (num_rows >= 4 && num_cols >= 4 && (long long)num_rows * (long long)num_cols < (1ll << 31)) return true;
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: the shot-change detector needs num_rows, num_cols >= 4 and num_rows * num_cols < 2147483648 (got %d x %d)", fn,
+             num_rows, num_cols);
+    fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
+    return false;
+}
 bool depth_auto_params_ok(const char *fn, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate)
 {
     char msg[200];
@@ -885,6 +914,35 @@ void stm_get_balance(int out_mode[2], float *out_rate, unsigned char out_lut[768
     out_mode[0] = b.mode; out_mode[1] = b.max_shift;
     *out_rate = b.rate;
     memcpy(out_lut, b.lut, 768);
+}
+int stm_set_cut(int mode, int thresh_permille, int min_gap, int *d_state)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (mode != 0 && mode != 1) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "set_cut: mode = %d, must be 0 (off) or 1 (on)", mode);
+        stm::fail(msg, "mode", __FILE__, __LINE__);
+        return -1; // the thread's setting stays as it was
+    }
+    stm::Cut c = stm::cut(); // mode 0: the other arguments are ignored, the numbers stay
+    c.mode = mode;
+    if (mode == 1) {
+        if (!stm::cut_params_ok("set_cut", thresh_permille, min_gap)) return -1;
+        if (!d_state) { // without history there is nothing to detect
+            stm::fail("set_cut: d_state must not be null in mode 1", "d_state", __FILE__, __LINE__);
+            return -1;
+        }
+        c.thresh_permille = thresh_permille; c.min_gap = min_gap; c.d_state = d_state;
+    } else {
+        c.d_state = nullptr;
+    }
+    stm::set_cut(c);
+    return 0;
+}
+void stm_get_cut(int out[3])
+{
+    const stm::Cut c = stm::cut();
+    out[0] = c.mode; out[1] = c.thresh_permille; out[2] = c.min_gap;
 }
 void stm_set_agg_variant(int v)
 {

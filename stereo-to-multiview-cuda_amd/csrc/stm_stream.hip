@@ -25,6 +25,7 @@ struct Slot {
     float *d_rec = nullptr, *h_rec = nullptr; // depth mode 2: the state as this slot's frame left it (16 bytes), and its download
     float *d_arec = nullptr, *h_arec = nullptr; // align mode 2: likewise the alignment's state
     int *d_brec = nullptr, *h_brec = nullptr;   // balance mode 2: likewise the balance's state (769 ints)
+    int *d_crec = nullptr, *h_crec = nullptr;   // cut mode 1: {cut, since, score} as this slot's frame's decision left them (12 bytes)
     u8 *h_ov = nullptr, *d_ov = nullptr;      // stm_stream_set_overlay: the slot's pinned and device copy of the overlay's pixels
     long ov_gen = 0;                          // ... and which stm_stream_overlay call they hold (0 = none yet)
     hipEvent_t ev_in, ev_done, ev_out;
@@ -67,6 +68,8 @@ struct FrameStream {
     float *d_align_state = nullptr; // align mode 2: the state every frame updates, at one address for both slots' graphs
     stm::Balance balance = stm::balance_default(); // stm_stream_set_balance / _auto: the stream's own colour balance
     int *d_balance_state = nullptr; // balance mode 2: the state every frame updates, at one address for both slots' graphs
+    stm::Cut cut = stm::cut_default(); // stm_stream_set_cut: the stream's own shot-change detector
+    int *d_cut_state = nullptr;     // cut mode 1: the 260 ints every frame updates, at one address for both slots' graphs
     int ov_max_rows = 0, ov_max_cols = 0; // stm_stream_set_overlay: the largest overlay the slots' copies hold ((0, 0) = off)
     u8 *ov_pixels = nullptr;              // stm_stream_overlay: the pixels of the overlay in force (host memory of the stream's own)
     stm::Overlay ov = {0, nullptr, 0, 0, 0, 0, 0.0f}; // ... and its arguments; mode 0 = none.  d_overlay is filled in per slot
@@ -110,6 +113,12 @@ struct BalanceScope {
     stm::Balance saved;
     explicit BalanceScope(const stm::Balance &b) : saved(stm::balance()) { stm::set_balance(b); }
     ~BalanceScope() { stm::set_balance(saved); }
+};
+
+struct CutScope {
+    stm::Cut saved;
+    explicit CutScope(const stm::Cut &c) : saved(stm::cut()) { stm::set_cut(c); }
+    ~CutScope() { stm::set_cut(saved); }
 };
 
 struct AntialiasScope {
@@ -708,6 +717,50 @@ int stm_stream_balance(void *h, unsigned char out_lut[768])
     }
     return 0;
 }
+// The shot-change detector of the stream's frames (stm_set_cut's rules; the default is mode 0).  Kept and installed like the balance.
+// Mode 1 allocates the stream's state and the slots' records.  The reset pointers are the stream's own depth, alignment and balance
+// states of mode 2, which the frame call resolves from the settings installed at submit: the setters may come in any order.  Only
+// before the first submit.
+int stm_stream_set_cut(void *h, int mode, int thresh_permille, int min_gap)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (mode != 0 && mode != 1) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "stream_set_cut: mode = %d, must be 0 (off) or 1 (on)", mode);
+        stm::fail(msg, "mode", __FILE__, __LINE__);
+        return -1;
+    }
+    if (mode == 1 && (!stm::cut_params_ok("stream_set_cut", thresh_permille, min_gap) || !stm::cut_size_ok("stream_set_cut", f->H, f->W))) return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_cut: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    const size_t bytes = stm::CUT_STATE_WORDS * 4;
+    if (mode == 1 && !f->d_cut_state) {
+        STM_CHECK(hipMalloc((void **)&f->d_cut_state, bytes));
+        STM_CHECK(hipMemset(f->d_cut_state, 0, bytes)); // valid = 0: the first frame is a cut
+        for (Slot &s : f->slot) {
+            STM_CHECK(hipMalloc((void **)&s.d_crec, 12));
+            STM_CHECK(hipHostMalloc((void **)&s.h_crec, 12, hipHostMallocDefault));
+        }
+        if (stm::failed()) return -1;
+    }
+    f->cut.mode = mode;
+    if (mode == 1) { f->cut.thresh_permille = thresh_permille; f->cut.min_gap = min_gap; }
+    f->cut.d_state = mode == 1 ? f->d_cut_state : nullptr;
+    return 0;
+}
+// {cut, score, since} of the most recently collected frame
+int stm_stream_cut(void *h, int out[3])
+{
+    FrameStream *f = (FrameStream *)h;
+    if (f->collected == 0) return -1;
+    const Slot &s = f->slot[(f->collected - 1) & 1];
+    if (f->cut.mode == 1) { out[0] = s.h_crec[0]; out[1] = s.h_crec[2]; out[2] = s.h_crec[1]; }
+    else { out[0] = out[1] = out[2] = 0; }
+    return 0;
+}
 // gain and conv applied to the most recently collected frame
 int stm_stream_depth(void *h, float out[2])
 {
@@ -743,6 +796,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     const bool depth_auto = f->depth.mode == 2;
     const bool align_auto = f->align.mode == 2; // likewise the alignment's state
     const bool balance_auto = f->balance.mode == 2; // ... and the colour balance's
+    const bool cut_on = f->cut.mode == 1;           // ... and the shot-change detector's
     // In NV12 mode the history is the other slot's converted split images (d_img_l / d_img_r), which no upload touches, and this
     // slot's d_in was last read by this slot's own previous frame, collected before the slot was handed out again: the upload
     // waits for nothing.  This frame's compute still waits for the other slot's frame: it reads that frame's images and maps, and
@@ -760,7 +814,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     }
     STM_CHECK(hipEventRecord(s.ev_in, f->s_in));
     STM_CHECK(hipStreamWaitEvent(s.s_compute, s.ev_in, 0));
-    if (history || ((depth_auto || align_auto || balance_auto) && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
+    if (history || ((depth_auto || align_auto || balance_auto || cut_on) && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
     void *prev = stm_get_stream();
     LensScope lens_scope(f->lens);
     LayoutScope layout_scope(f->layout);
@@ -769,6 +823,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     AntialiasScope antialias_scope(f->antialias);
     AlignScope align_scope(f->align);
     BalanceScope balance_scope(f->balance);
+    CutScope cut_scope(f->cut);
     PackingScope packing_scope(f->packing);
     OverlayOffScope overlay_scope;
     stm_set_stream(s.s_compute);
@@ -857,6 +912,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     if (align_auto) STM_CHECK(hipMemcpyAsync(s.d_arec, f->d_align_state, 16, hipMemcpyDeviceToDevice, s.s_compute));
     if (balance_auto)
         STM_CHECK(hipMemcpyAsync(s.d_brec, f->d_balance_state, stm::BALANCE_STATE_WORDS * 4, hipMemcpyDeviceToDevice, s.s_compute));
+    if (cut_on) STM_CHECK(hipMemcpyAsync(s.d_crec, f->d_cut_state + 1, 12, hipMemcpyDeviceToDevice, s.s_compute));
     STM_CHECK(hipEventRecord(s.ev_done, s.s_compute));
     STM_CHECK(hipStreamWaitEvent(f->s_out, s.ev_done, 0));
     STM_CHECK(hipMemcpyAsync(s.h_dl, s.d_dl, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
@@ -865,6 +921,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     if (depth_auto) STM_CHECK(hipMemcpyAsync(s.h_rec, s.d_rec, 16, hipMemcpyDeviceToHost, f->s_out));
     if (align_auto) STM_CHECK(hipMemcpyAsync(s.h_arec, s.d_arec, 16, hipMemcpyDeviceToHost, f->s_out));
     if (balance_auto) STM_CHECK(hipMemcpyAsync(s.h_brec, s.d_brec, stm::BALANCE_STATE_WORDS * 4, hipMemcpyDeviceToHost, f->s_out));
+    if (cut_on) STM_CHECK(hipMemcpyAsync(s.h_crec, s.d_crec, 12, hipMemcpyDeviceToHost, f->s_out));
     STM_CHECK(hipEventRecord(s.ev_out, f->s_out));
     if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
     if (stm::failed()) return -1; // error mode 1: the frame was not (completely) enqueued
@@ -932,6 +989,8 @@ void stm_stream_destroy(void *h)
         if (s.h_arec) STM_CHECK(hipHostFree(s.h_arec));
         if (s.d_brec) STM_CHECK(hipFree(s.d_brec));
         if (s.h_brec) STM_CHECK(hipHostFree(s.h_brec));
+        if (s.d_crec) STM_CHECK(hipFree(s.d_crec));
+        if (s.h_crec) STM_CHECK(hipHostFree(s.h_crec));
         if (s.h_ov) STM_CHECK(hipHostFree(s.h_ov));
         if (s.d_ov) STM_CHECK(hipFree(s.d_ov));
     }
@@ -939,6 +998,7 @@ void stm_stream_destroy(void *h)
     if (f->d_depth_state) STM_CHECK(hipFree(f->d_depth_state));
     if (f->d_align_state) STM_CHECK(hipFree(f->d_align_state));
     if (f->d_balance_state) STM_CHECK(hipFree(f->d_balance_state));
+    if (f->d_cut_state) STM_CHECK(hipFree(f->d_cut_state));
     stm::ws_private_destroy(f->slot[0].ws);
     STM_CHECK(hipStreamDestroy(f->slot[0].s_compute));
     if (f->overlap) {

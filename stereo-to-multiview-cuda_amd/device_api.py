@@ -455,6 +455,42 @@ def d_balance_apply(out, img, lut=None, state=None):
     lib().stm_d_balance_apply(_p(out), _p(img), H, W, E, _lut768(lut) if lut is not None else None, _p(state) if state is not None else None)
 
 
+def set_cut(mode, thresh_permille=370, min_gap=1, state=None):
+    """stm_set_cut: the calling thread's shot-change detector.  mode 0 = off (the default; the other arguments are ignored), 1 = on:
+    every frame call first takes the left eye's signature and, on a cut, zeroes the `valid` word of the depth, alignment and balance
+    states of mode 2 before their fits run.  `state`: an int32 tensor of 260 elements on the GPU, {valid, cut, since, score, sig[256]},
+    zeroed at the start -- the caller keeps it alive while the setting is in use and reads the flag from state[1].  Raises
+    ValueError where the library refuses (mode 1 without a state among the reasons)."""
+    if state is not None:
+        assert state.is_cuda and state.dtype == torch.int32 and state.is_contiguous() and state.numel() == 260
+    if int(lib().stm_set_cut(int(mode), int(thresh_permille), int(min_gap), _p(state) if state is not None else None)) != 0:
+        raise ValueError("stm_set_cut(%d, %d, %d) refused: %s" % (mode, thresh_permille, min_gap, lib().stm_last_error().decode()))
+
+
+def get_cut():
+    """stm_get_cut: the calling thread's (mode, thresh_permille, min_gap) as the library holds it"""
+    out = (C.c_int * 3)()
+    lib().stm_get_cut(out)
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def d_cut_detect(img_l, thresh_permille, min_gap, state, resets=(), sig=None):
+    """stm_d_cut_detect: the shot-change detector as a stage -- the left image (uint8 [H][W][E] on the GPU) into its signature, the
+    decision against `state` (int32, 260 elements on the GPU), updated in place; nothing synchronised.  resets: up to three tensors
+    on the GPU (or None) whose first 32-bit word is zeroed on a cut; sig (int32, 256 elements) receives the signature where given."""
+    H, W, E = img_l.shape
+    assert img_l.is_cuda and img_l.dtype == torch.uint8 and img_l.is_contiguous()
+    assert state.is_cuda and state.dtype == torch.int32 and state.is_contiguous() and state.numel() == 260
+    assert sig is None or (sig.is_cuda and sig.dtype == torch.int32 and sig.is_contiguous() and sig.numel() == 256)
+    resets = list(resets) + [None] * (3 - len(resets))
+    assert len(resets) == 3
+    for t in resets:
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() >= 4)
+    _use_current_stream()
+    lib().stm_d_cut_detect(_p(img_l), H, W, E, int(thresh_permille), int(min_gap), _p(state), *[_p(t) if t is not None else None for t in resets],
+                           _p(sig) if sig is not None else None)
+
+
 def d_view_prefilter(out, img, disp, num_views, strength=1.0, max_radius=8, gate=1.0, gain=1.0, conv=0.0):
     """stm_d_view_prefilter: img (uint8 [H][W][E] on the GPU) filtered by its own map disp (float32 [H][W]) into out, which must not
     overlap img; only bytes 0 .. 2 of a pixel are written.  gain, conv: the depth budget the views are rendered with (set_depth)."""

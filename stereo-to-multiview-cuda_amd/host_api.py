@@ -463,6 +463,20 @@ def balance_apply(img, lut=None, state=None):
     return out
 
 
+def cut_detect(img_l, thresh_permille=370, min_gap=1, state=None):
+    """The shot-change detector on one left image (stm_cut_detect; an addition, the reference keeps nothing from frame to frame): the
+    image's signature against the one in `state` = (valid, cut, since, score, sig[256]) (None = no history).  Returns (cut, state):
+    the flag and the new state as an int32 array of 260; nothing passed in is modified."""
+    img_l, pl = _u8(img_l)
+    H, W, E = img_l.shape
+    st = np.zeros(260, np.int32) if state is None else np.array(state, dtype=np.int32, order="C")
+    assert st.shape == (260,)
+    cut = int(lib().stm_cut_detect(pl, H, W, E, int(thresh_permille), int(min_gap), st.ctypes.data_as(C.POINTER(C.c_int))))
+    if cut < 0:
+        raise ValueError("stm_cut_detect refused: %s" % lib().stm_last_error().decode())
+    return cut, st
+
+
 def tx_scale(img, out_rows, out_cols):
     """d_tx_scale.h:17-18 (bilinear resize)."""
     img, pi = _u8(img)

@@ -11,6 +11,11 @@ import numpy as np
 from . import bmp_io
 from ._lib import f32p, lib, u8p
 
+# FrameStream(cut=...)'s and --cut's default (thresh_permille, min_gap).  370: DESIGN section 25 (the geometric mean of the largest
+# non-cut and the smallest cut score on the committed images, rounded to 10).  3: a flash lasts one or two frames, so the frame that
+# returns from it comes at most two frames after the flash's own cut and is suppressed; no edited shot is shorter than three frames.
+CUT_DEFAULT = (370, 3)
+
 
 class FrameStream:
     """Pipelined adcensus_stm over a sequence: submit() frames, collect() results in order (two in flight).
@@ -35,11 +40,13 @@ class FrameStream:
     the GPU (mode 2); at most one of the two; .align() reads the field of the last collected frame.  balance = a uint8 array of
     (3, 256): the right eye of every frame through these tables (B, G, R) ahead of the matcher, after the alignment (set_balance mode
     1); balance_auto = (max_shift[, rate]): the tables fitted on every frame on the GPU (mode 2); at most one of the two; .balance()
-    reads the tables of the last collected frame."""
+    reads the tables of the last collected frame.  cut = (thresh_permille, min_gap) or True (CUT_DEFAULT): the shot-change detector
+    (set_cut mode 1) -- at a cut the depth_auto, align_auto and balance_auto states start afresh on the GPU; .cut() reads (cut, score,
+    since) of the last collected frame."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
                  depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None, overlay=None,
-                 antialias=None, align=None, align_auto=None, balance=None, balance_auto=None):
+                 antialias=None, align=None, align_auto=None, balance=None, balance_auto=None, cut=None):
         self.H, self.W = num_rows, num_cols
         self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
@@ -90,6 +97,22 @@ class FrameStream:
         if balance_auto is not None:
             self.set_balance_auto(*balance_auto)
             self.set_balance(2)
+        if cut is not None and cut is not False:
+            self.set_cut(1, *(CUT_DEFAULT if cut is True else cut))
+
+    def set_cut(self, mode, thresh_permille=CUT_DEFAULT[0], min_gap=CUT_DEFAULT[1]):
+        """stm_stream_set_cut: the shot-change detector of the stream's frames (device_api.set_cut's arguments; the state is the
+        stream's own); only before the first submit.  Raises ValueError where the library refuses."""
+        if int(lib().stm_stream_set_cut(self._h, int(mode), int(thresh_permille), int(min_gap))) != 0:
+            raise ValueError("stm_stream_set_cut(%d, %d, %d) refused: %s" % (mode, thresh_permille, min_gap, lib().stm_last_error().decode()))
+
+    def cut(self):
+        """stm_stream_cut: (cut, score, since) of the most recently collected frame ((0, 0, 0) with the detector off), or None
+        before the first collect."""
+        out = (C.c_int * 3)()
+        if int(lib().stm_stream_cut(self._h, out)) != 0:
+            return None
+        return int(out[0]), int(out[1]), int(out[2])
 
     def set_balance(self, mode, lut=None):
         """stm_stream_set_balance: the colour balance of the stream's frames (device_api.set_balance's arguments); the stream's
@@ -364,8 +387,32 @@ def take_balance_options(argv):
     return balance, balance_auto
 
 
-def _collect(fs, on_depth, on_align=None, on_balance=None):
+def take_cut_option(argv):
+    """The driver's --cut [THRESH MIN_GAP] (both numbers or neither: CUT_DEFAULT), removed from argv.  Returns (thresh_permille,
+    min_gap) or None; raises ValueError for a malformed option or a value out of range."""
+    if "--cut" not in argv:
+        return None
+    at = argv.index("--cut")
+    vals = []
+    for tok in argv[at + 1:at + 3]:
+        try:
+            int(tok)
+        except ValueError:
+            break
+        vals.append(tok)
+    if len(vals) == 1:
+        raise ValueError("--cut takes THRESH and MIN_GAP, or neither")
+    cut = (int(vals[0]), int(vals[1])) if vals else CUT_DEFAULT
+    if not 1 <= cut[0] <= 1000 or not 1 <= cut[1] <= (1 << 20):
+        raise ValueError(cut)
+    del argv[at:at + 1 + len(vals)]
+    return cut
+
+
+def _collect(fs, on_depth, on_align=None, on_balance=None, on_cut=None):
     r = fs.collect()
+    if on_cut is not None and r is not None:
+        on_cut(r[0], fs.cut())
     if on_balance is not None and r is not None:
         on_balance(r[0], fs.balance())
     if on_depth is not None and r is not None:
@@ -378,7 +425,7 @@ def _collect(fs, on_depth, on_align=None, on_balance=None):
 def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None,
                      depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None,
                      overlay=None, antialias=None, align=None, align_auto=None, on_align=None, balance=None, balance_auto=None,
-                     on_balance=None):
+                     on_balance=None, cut=None, on_cut=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
@@ -391,7 +438,8 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
     overlay: (bgra, x0, y0, disparity), one premultiplied overlay composited into every frame of the sequence (FrameStream.overlay).
     antialias: FrameStream's (strength, max_radius, gate): view antialiasing of every frame.  align / align_auto: FrameStream's
     vertical alignment of every frame's pair; on_align: called with (index, (a, b, c)) after every collected frame.  balance /
-    balance_auto: FrameStream's colour balance of every frame's pair; on_balance: called with (index, tables) likewise."""
+    balance_auto: FrameStream's colour balance of every frame's pair; on_balance: called with (index, tables) likewise.  cut:
+    FrameStream's shot-change detector; on_cut: called with (index, (cut, score, since)) likewise."""
     fs = None
     pending = 0
     for sbs in frames:
@@ -402,18 +450,18 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
                 rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
             fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output,
                              overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]), antialias=antialias,
-                             align=align, align_auto=align_auto, balance=balance, balance_auto=balance_auto)
+                             align=align, align_auto=align_auto, balance=balance, balance_auto=balance_auto, cut=cut)
             if overlay is not None:
                 fs.overlay(*overlay)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:
-            yield _collect(fs, on_depth, on_align, on_balance)
+            yield _collect(fs, on_depth, on_align, on_balance, on_cut)
             pending -= 1
         fs.submit(sbs)
         pending += 1
     while fs is not None and pending:
-        yield _collect(fs, on_depth, on_align, on_balance)
+        yield _collect(fs, on_depth, on_align, on_balance, on_cut)
         pending -= 1
     if fs is not None:
         fs.close()

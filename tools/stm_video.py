@@ -10,6 +10,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--packing P SWAP FILTER GAP] [--quilt TX TY ORDER FILTER [--nv12-out MATRIX]] [--match H W SCALE [--guided-up]]
                     [--overlay FILE.npy X0 Y0 DISPARITY] [--antialias STRENGTH MAX_RADIUS GATE]
                     [--align A B C | --align-auto RADIUS [RATE]] [--balance FILE.npy | --balance-auto [MAX_SHIFT RATE]]
+                    [--cut [THRESH MIN_GAP]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -58,6 +59,10 @@ frame goes through the three tables of FILE.npy (768 bytes of uint8: B, G, R, 25
 --balance-auto [MAX_SHIFT RATE]: the tables are fitted on every frame on the GPU from the two eyes' histograms, moving no level by
 more than MAX_SHIFT (0 .. 255; 48) and followed at RATE (1); each frame's tables are printed at the levels 64, 128 and 192.  The
 two options are mutually exclusive; both combine with every input format and every other option.
+--cut [THRESH MIN_GAP] (an addition): the shot-change detector (stm_stream_set_cut) -- every frame's left eye is compared on the GPU
+with the previous frame's through a 4 x 4 grid of 16-bin luma histograms; a frame that scores THRESH permille (1 .. 1000; 370) or
+more, at least MIN_GAP frames (3) after the last cut, is a cut, and the --depth-auto, --align-auto and --balance-auto states start
+afresh on it.  Each frame's flag and score are printed, and at the end the indices of the frames found to be cuts.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -241,6 +246,7 @@ def main(argv):
         import stm_amd  # noqa: F401
         from stm_amd import video
         balance, balance_auto = video.take_balance_options(argv)
+        cut = video.take_cut_option(argv)
     except (ValueError, IndexError):
         print(__doc__)
         return -1
@@ -261,6 +267,13 @@ def main(argv):
     if nv12_out is not None:
         os.makedirs(out_dir, exist_ok=True)
         yuv = open(os.path.join(out_dir, "quilt.yuv"), "wb")
+    cuts = []
+
+    def on_cut(k, c):
+        print("frame %d: cut %d score %d since %d" % ((k,) + c))
+        if c[0]:
+            cuts.append(k)
+
     t0 = time.perf_counter()
     n = 0
     for (k, dl, dr, inter) in video.process_sequence(frames, p, out_h, out_w, stages, tuple(temporal) if stages & 0x2000 else None,
@@ -275,7 +288,8 @@ def main(argv):
                                                        balance=balance, balance_auto=balance_auto,
                                                        on_balance=(lambda k, t: print("frame %d: balance B %d %d %d G %d %d %d R %d %d %d" % (
                                                            (k,) + tuple(int(t[c, v]) for c in range(3) for v in (64, 128, 192)))))
-                                                       if balance_auto is not None else None):
+                                                       if balance_auto is not None else None,
+                                                       cut=cut, on_cut=on_cut if cut is not None else None):
         if yuv is not None:  # the frame is [out height * 3 / 2][out width]: the Y plane, then the interleaved UV plane
             yuv.write(inter.tobytes())
             video.write_disparities(out_dir, k, dl, dr)
@@ -284,6 +298,8 @@ def main(argv):
         n += 1
     if yuv is not None:
         yuv.close()
+    if cut is not None:
+        print("cuts at frames: %s" % " ".join(str(k) for k in cuts))
     dt = time.perf_counter() - t0
     print("%d frames in %.3f s (%.1f frames/s including BMP I/O)" % (n, dt, n / dt if dt > 0 else 0.0))
     return 0
