@@ -89,7 +89,9 @@ int         stm_prof_read(const char *kernel, float *total_ms);
  * four columns per wave and the PQ volume layout end to end instead of one column per wave on pixel-major volumes (48 < num_disp <= 64
  * only; elsewhere the default already is the former), 100000000 = the last horizontal pass + WTA on the
  * LDS row walk instead of the register-ring kernel (stm_kernels_aggh.hip), 1000000000 = the window tables of the two register-ring
- * kernels from their own launches instead of from the cross-arm kernel.  Every accepted variant produces identical
+ * kernels from their own launches instead of from the cross-arm kernel, 2000000000 = the pixel-major volumes with a pixel's
+ * hypotheses in ascending order and sixteen 4-byte stores per tile in the first pass and in the vertical kernel instead of the orders
+ * that let both store 16 bytes at a time (stm_px_order; tests/test_gpu_px_store_order.py).  Every accepted variant produces identical
  * results (tests/test_gpu_parity.py::test_device_frame_agg_variants, tests/test_gpu_image_chain.py,
  * tests/test_gpu_cross_arms.py, tests/test_gpu_px_layout.py).  The
  * digit N00000 (timing experiments that skip parts of kernels) is ignored here: it exists only in libstm_hip_timing.so,
@@ -116,6 +118,14 @@ int         stm_agg_path(int num_disp, int zero_disp, int num_rows, int num_cols
  * 0 <= zero_disp < num_disp, and not under variant 2000000.  Host arithmetic only, from the dispatcher's own functions, like
  * stm_agg_path.  An addition. */
 int         stm_first_pass_path(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages);
+/* The order of the 64 hypotheses inside a pixel's 256-byte record of the pixel-major volumes of such a frame call under the current
+ * stm_set_agg_variant, as the last horizontal pass finds it: -1 where stm_agg_path does not report bit 1; 0 = hypothesis d at float d
+ * in both volumes, written as sixteen 4-byte stores per tile of 16 pixels or rows (variant 2000000000); 2 (the default) = the first
+ * pass and the vertical kernel each write float 16 b + n of their registers at float 4 n + b, as four 16-byte stores per tile, which
+ * leaves hypothesis 4 n + b at float 16 b + n of the volume the last pass reads (1, that permutation applied once, is the first
+ * volume's order and never the answer).  The order is internal to the three aggregation kernels: the maps are the same either way.
+ * Host arithmetic only, from the dispatcher's own functions, like stm_agg_path.  An addition. */
+int         stm_px_order(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages);
 /* dr_irv / d_dr_irv / the frame calls: 0 (default) = the reference's accept rule, (winning bin index + zero_disp) / S > thresh_h
  * (d_dr_irv.cu:36 -- the bin INDEX, SURVEY A-Q17 iv); 1 = the paper's rule, (winning bin's COUNT) / S > thresh_h (Mei et al.,
  * region voting).  An addition: the reference has no such switch. */

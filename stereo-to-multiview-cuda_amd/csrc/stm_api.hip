@@ -180,6 +180,12 @@ int frame_first_pass_path(int D, int zd, int H, int W, int usd, int stages)
     if (D < 1 || H < 1 || W < 1 || !agg_on_matrix_pipe(usd, H, W)) return 0;
     return aggm_frame_hc2_parts(D, zd, H, W, usd, stages_hslo(stages), stages_subpix(stages));
 }
+// stm_px_order (stm_hip.h): the same predicates again
+int frame_px_order(int D, int zd, int H, int W, int usd, int stages)
+{
+    if (D < 1 || H < 1 || W < 1 || !agg_on_matrix_pipe(usd, H, W)) return -1;
+    return aggm_frame_px_order(D, zd, H, W, usd, stages_hslo(stages), stages_subpix(stages));
+}
 void core_agg(Vol cost, Vol scratch, const Arms &a, int D, int H, int W, int usd)
 {
     // the frame pipeline's matrix-pipe kernels (round 3) -- unless the caller's volume holds infinities, NaNs or denormals
@@ -2176,6 +2182,11 @@ int stm_agg_path(int num_disp, int zero_disp, int num_rows, int num_cols, int us
 int stm_first_pass_path(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages)
 {
     return frame_first_pass_path(num_disp, zero_disp, num_rows, num_cols, usd, stages);
+}
+// the order of the hypotheses inside a pixel's record of such a call's PX volumes, or -1 off PX (stm_hip.h); no launch, no device
+int stm_px_order(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages)
+{
+    return frame_px_order(num_disp, zero_disp, num_rows, num_cols, usd, stages);
 }
 
 void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,

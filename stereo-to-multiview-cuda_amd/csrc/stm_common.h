@@ -495,6 +495,9 @@ size_t aggm_frame_vtab_dwords(int D, int zd, int H, int W, int usd, bool keep_vo
 // whether the frame's two intermediate volumes take the pixel-major layout PX (float index ((y 4G + x) 64 + d), DESIGN.md
 // section 4): all three register / streaming kernels run, 48 < D <= 64, WTA, and nobody reads a volume afterwards
 bool aggm_frame_px(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later);
+// the order of the hypotheses inside a PX pixel's record as the last pass reads it where aggm_frame_px holds (0: d at float d;
+// 2: 4 n + b at float 16 b + n, after the 16-byte stores of the first pass and of stm_k_pq_v12r), else -1
+int aggm_frame_px_order(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later);
 // what launch_aggm_frame runs for these arguments, as the bits 1 .. 16 of stm_agg_path (include/stm_hip.h); launches nothing
 int aggm_frame_path(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later);
 // the blocks per image row of stm_k_pq_hc2 (first pass, both views from one ring of costs) where launch_aggm_frame runs it, else 0
@@ -508,12 +511,12 @@ size_t aggm_stage_bytes(int D, int H, int W, int usd);
 bool aggh_supports(int usd, int D); // stm_kernels_aggh.hip: last horizontal pass + WTA with the row's window range in registers
 size_t aggh_table_dwords(int nviews, int H, int W);
 void launch_hwin_table(PQViews &v, int nviews, uint32_t *tab, int H, int W); // (the frame path builds the table inside stm_k_cross_arms: launch_cross_arms2's htab)
-void launch_pq_hsr(PQViews &v, int nviews, const uint32_t *tab, int D, int zd, int H, int W, bool px = false); // px: vol_a in the PX layout
+void launch_pq_hsr(PQViews &v, int nviews, const uint32_t *tab, int D, int zd, int H, int W, bool px = false, int ord = 0); // px: vol_a in the PX layout, its records in hypothesis order ord
 bool aggv_supports(int usd);
 int aggv_table_top();
 int aggv_table_rec();
 void launch_pq_v12q(PQViews &v, int nviews, const uint32_t *tab, int rec, int H, int W, int G, int NC); // PQ volumes, a strip of four columns per wave
-void launch_pq_v12r(PQViews &v, int nviews, const uint32_t *tab, int H, int W, int G);                  // PX volumes, one column per wave; tab: vcol_build's records
+void launch_pq_v12r(PQViews &v, int nviews, const uint32_t *tab, int H, int W, int G, bool x4 = false); // PX volumes, one column per wave; tab: vcol_build's records; x4: 16-byte stores
 void launch_vcol_table(PQViews &v, int nviews, uint32_t *tab, int H, int W);                            // that table from the arm planes (aggv_col_table_dwords)
 size_t aggv_col_table_dwords(int nviews, int H, int W);
 void launch_to_pq(Vol in, float *pq, int D, int H, int W, uint32_t *odd = nullptr); // stm_kernels_hslo.hip; odd: see stm_k_to_pq

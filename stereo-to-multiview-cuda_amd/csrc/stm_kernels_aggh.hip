@@ -52,9 +52,13 @@ __global__ __launch_bounds__(256) void stm_k_hwin_table(PQViews v, uint32_t *__r
 // PX: the volume in the pixel-major layout of the frame's fast path (float index ((y 4G + x) 64 + d), NC == 4): a pixel's 64
 // hypotheses are one register (lane = d), a group is four buffer_load_dword of 256 contiguous bytes each.  Four times the loads:
 // the waits below count 16 per step instead of 4.
+// ord: the hypothesis order of a PX record (aggm_frame_px_order; 0 with PQ volumes).  Lane 16 b + n loads float 16 b + n of a record,
+// which holds hypothesis 16 b + n (order 0) or 4 n + b (order 2).  Either way a lane's four chunks hold ascending hypotheses, so
+// "the lower chunk on ties" stays "the lower d on ties", and the 16-lane stage compares the hypotheses themselves: only the
+// per-lane constants below know the order, the sweep and the WTA do not.
 template <int EXP, bool PX> // timing experiments (libstm_hip_timing.so only; results invalid): 1 no sweeps, 2 no volume loads, 4 no WTA, 8 no mask loads
 __global__ __launch_bounds__(64, 3) void stm_k_pq_hsr(PQViews pv, const uint32_t *__restrict__ htab, int D, int zd, int H, int W, int G, int NC, int nTx,
-                                                      int parts, int nviews)
+                                                      int parts, int nviews, int ord)
 {
     // block (one wave) -> (view, row, part of the row)
     const int part = blockIdx.x % parts, rest = blockIdx.x / parts, y = rest % H, view = rest / H;
@@ -68,12 +72,14 @@ __global__ __launch_bounds__(64, 3) void stm_k_pq_hsr(PQViews pv, const uint32_t
     const uint32_t cstride = (uint32_t)H * (uint32_t)G * 256u;                    // bytes between chunks
     const uint32_t nrec = (uint32_t)NC * cstride;                                // bytes of the volume (chunks past the last: out of range -> zeros)
     const int vload = PX ? 4 * l : (l >> 4) * (int)cstride + (l & 15) * 16;      // lane 16 b + n reads chunk b, hypothesis n of a group (PX: of a pixel)
-    const int vn = l & 15;
+    const int hstep = PX && ord ? 1 : 16;                                         // hypothesis of lane n's chunk b: vn + b hstep
+    const int vn = PX && ord ? 4 * (l & 15) : l & 15;
+    const int hs2 = 2 * hstep, hs3 = 3 * hstep;
     const int vst = (l & 15) == 0 ? (l >> 4) * 16 : 0x7ffffff0;                   // lane n == 0 of a pixel quad stores its four pixels
     // hypotheses d >= D (padding of the last chunk, chunks past the last) must never win: their costs become FLT_MAX
     float vbig[4];
 #pragma unroll
-    for (int b = 0; b < 4; ++b) vbig[b] = (16 * b + (l & 15)) >= D ? 3.402823466e+38f : 0.0f;
+    for (int b = 0; b < 4; ++b) vbig[b] = (vn + b * hstep) >= D ? 3.402823466e+38f : 0.0f;
     const int yG = y * G, Gm1 = G - 1, W4 = W * 4;
     const float zdf = (float)zd;
     asm volatile(R"ASM(
@@ -318,7 +324,7 @@ HR_wta_%=_\@:
         v_max_f32 v134, v134, %[vb3]
         v_max_f32 v135, v135, %[vb3]
 HR_nofix_%=_\@:
-        ; per lane: the lowest of its four chunks, the lower chunk on ties; v[138:141] = that hypothesis (d = 16 b + n)
+        ; per lane: the lowest of its four chunks, the lower chunk (= the lower d) on ties; v[138:141] = that hypothesis (v151 .. v153)
         HR_WTA_CHUNK 1, 151
         HR_WTA_CHUNK 2, 152
         HR_WTA_CHUNK 3, 153
@@ -375,9 +381,9 @@ HR_nofix_%=_\@:
         s_mov_b32 s31, 0
         HR_NEXT_MASKS
         v_mov_b32 v150, 0x7fffffff
-        v_add_u32 v151, 16, %[vn]
-        v_add_u32 v152, 32, %[vn]
-        v_add_u32 v153, 48, %[vn]
+        v_add_u32 v151, %[hs1], %[vn]
+        v_add_u32 v152, %[hs2], %[vn]
+        v_add_u32 v153, %[hs3], %[vn]
         v_or_b32 v146, %[vb0], %[vb1]
         v_or3_b32 v146, v146, %[vb2], %[vb3]
         v_cmp_ne_u32 vcc, 0, v146
@@ -448,7 +454,7 @@ HR_done_%=:
         )ASM"
                  :
                  : [exp] "n"(EXP), [px] "n"(PX ? 1 : 0), [in] "s"(in), [disp] "s"(disp_row), [hrec_lo] "s"((uint32_t)(uintptr_t)hrec), [hrec_hi] "s"((uint32_t)((uintptr_t)hrec >> 32)),
-                   [yG] "s"(yG), [Gm1] "s"(Gm1), [nrec] "s"(nrec), [W4] "s"(W4), [t0] "s"(t0), [t1] "s"(t1), [zdf] "s"(zdf),
+                   [yG] "s"(yG), [Gm1] "s"(Gm1), [nrec] "s"(nrec), [W4] "s"(W4), [t0] "s"(t0), [t1] "s"(t1), [zdf] "s"(zdf), [hs1] "s"(hstep), [hs2] "s"(hs2), [hs3] "s"(hs3),
                    [vload] "v"(vload), [vn] "v"(vn), [vst] "v"(vst), [vb0] "v"(vbig[0]),
                    [vb1] "v"(vbig[1]), [vb2] "v"(vbig[2]), [vb3] "v"(vbig[3])
                  : "memory", "scc", "vcc",
@@ -480,7 +486,7 @@ void launch_hwin_table(PQViews &v, int nviews, uint32_t *tab, int H, int W)
 }
 
 // last horizontal pass + WTA, vol_a -> disparities, for `nviews` views
-void launch_pq_hsr(PQViews &v, int nviews, const uint32_t *tab, int D, int zd, int H, int W, bool px)
+void launch_pq_hsr(PQViews &v, int nviews, const uint32_t *tab, int D, int zd, int H, int W, bool px, int ord)
 {
     const int G = (W + 3) / 4, NC = (D + 15) / 16, nTx = cdiv(W, 16);
     // parts per row: about ten tiles per wave measured best at 1080p (0.275 ms against 0.303 with 30 and 0.342 with 5: a wave's
@@ -490,8 +496,8 @@ void launch_pq_hsr(PQViews &v, int nviews, const uint32_t *tab, int D, int zd, i
     const dim3 grid(nviews * H * parts);
 #define STM_HSR_LAUNCH(E, GRID)                                                                                                       \
     {                                                                                                                                 \
-        if (px) STM_LAUNCH((stm_k_pq_hsr<E, true>), GRID, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews);      \
-        else STM_LAUNCH((stm_k_pq_hsr<E, false>), GRID, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews);        \
+        if (px) STM_LAUNCH((stm_k_pq_hsr<E, true>), GRID, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews, ord); \
+        else STM_LAUNCH((stm_k_pq_hsr<E, false>), GRID, dim3(64), 0, stream(), v, tab, D, zd, H, W, G, NC, nTx, parts, nviews, 0);     \
     }
 #ifdef STM_TIMING
     if (const char *e = getenv("STM_HSR_PARTS")) parts = atoi(e);

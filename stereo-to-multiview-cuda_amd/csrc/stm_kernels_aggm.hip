@@ -582,11 +582,16 @@ __global__ __launch_bounds__(64 * NW, (3 * NW) / 4) void stm_k_pq_hs(PQViews v, 
 // between the two barriers that end the segment.  D <= 64 (one chunk set).
 // C(d, x) = rho_ad(|own(x) - other(x')|_1) + rho_c(ham(cen_own(x), cen_other(x'))), x' = clamp(x + sgn (d - zd)) (SURVEY A-Q6);
 // hypotheses d >= D and pixels outside the row are 0.
-// PX: the output volume in the pixel-major layout PX of the frame's fast path (float index ((y 4G + x) 64 + d), 256 contiguous
-// bytes per pixel; NC == 4): sixteen dword stores straight from the accumulators, each four 64-byte pieces.  (Transposing the
-// accumulators first, as stm_k_pq_v12r does, so that every store writes one pixel's 256 bytes, measured 0.010 ms slower:
-// 0.377 against 0.367 ms, profiles/vcol_store_forms.json.)
-template <int NW, bool PX>
+// PX: the output volume in the pixel-major layout PX of the frame's fast path (256 contiguous bytes per pixel; NC == 4), straight
+// from the accumulators.  ORD = the hypothesis order inside a pixel's record as this pass writes it (1 wherever px_order, below,
+// is not 0):
+//   0  float index ((y 4G + x) 64 + d): sixteen dword stores, each four 64-byte pieces.  (Transposing the accumulators first, as
+//      stm_k_pq_v12r does, so that every store writes one pixel's 256 bytes, measured 0.010 ms slower: 0.377 against 0.367 ms,
+//      profiles/vcol_store_forms.json.)
+//   1  hypothesis 16 b + n at float 4 n + b of the record: the four registers b = 0 .. 3 of a lane (fixed pixel i) are 16 contiguous
+//      bytes, so a tile leaves as FOUR 16-byte stores, each four complete pixel records.  No lane moves; the consumers load a
+//      record as before and their lane L carries hypothesis 16 (L mod 4) + L div 4.
+template <int NW, bool PX, int ORD>
 __global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void stm_k_pq_hc(PQViews v, int D, int zd, int H, int W, int G, int NC, int HG, int nseg,
                                                                      int spl, const float *__restrict__ lut_g, int pad, int dbg)
 {
@@ -783,12 +788,18 @@ __global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void stm_k_pq_hc(PQViews v, 
                     const f4 o = {acc[4 * cl], acc[4 * cl + 1], acc[4 * cl + 2], acc[4 * cl + 3]};
                     if (!STM_DBG(dbg, 4)) STM_BSTORE(rout[cl], (X0 >> 2) * 256 + l * 16, o);
                 }
-            } else {
+            } else if (ORD == 0) {
 #pragma unroll
                 for (int k = 0; k < 16; ++k) // register 4 b + i of lane 16 q + n = pixel X0 + 4 q + i, hypothesis 16 b + n
                     if (!STM_DBG(dbg, 4))
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, (float)acc[k]), rpx,
                                                               (X0 + 4 * lb + (k & 3)) * 256 + (16 * (k >> 2) + dd) * 4, 0, 2);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { // pixel X0 + 4 q + i: hypotheses n, 16 + n, 32 + n, 48 + n at bytes 16 n .. 16 n + 15
+                    const f4 o = {acc[i], acc[4 + i], acc[8 + i], acc[12 + i]};
+                    if (!STM_DBG(dbg, 4)) STM_BSTORE(rpx, (X0 + 4 * lb + i) * 256 + 16 * dd, o);
+                }
             }
         }
         if (more) STM_HC_COSTS((sq + 1) & 1, 4 * NW * (sq + 1) + NG - 4 * NW)
@@ -833,6 +844,7 @@ __global__ __launch_bounds__(64 * NW, (2 * NW) / 4) void stm_k_pq_hc(PQViews v, 
 constexpr int HC2_TX = 96, HC2_SR = HC2_TX + 64, HC2_HALO = 40, HC2_RING = 256, HC2_FRONT = HC2_TX + HC2_HALO;
 typedef const float __attribute__((address_space(3))) *hc2_lds_cf;
 constexpr size_t HC2_SMEM =(size_t)(HC2_RING + 3) * 256 + 2 * HC2_TX * 4 + 12 * 8 + (size_t)(2 * HC2_TX + 2 * HC2_SR) * 8 + (768 + 72) * 4;
+template <int ORD> // the hypothesis order of the PX records it writes, as in stm_k_pq_hc
 __global__ __launch_bounds__(768, 6) void stm_k_pq_hc2(PQViews v, int D, int zd, int H, int W, int G, int nseg, int spl,
                                                        const float *__restrict__ lut_g, int dbg)
 {
@@ -1001,11 +1013,19 @@ __global__ __launch_bounds__(768, 6) void stm_k_pq_hc2(PQViews v, int D, int zd,
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[i] = 0.f;
             }
+            if (ORD == 0) {
 #pragma unroll
-            for (int k = 0; k < 16; ++k) // register 4 b + i of lane 16 q + n = pixel X0 + 4 q + i, hypothesis 16 b + n
-                if (!STM_DBG(dbg, 4))
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, (float)acc[k]), rpx,
-                                                          (X0 + 4 * lb + (k & 3)) * 256 + (16 * (k >> 2) + dd) * 4, 0, 2);
+                for (int k = 0; k < 16; ++k) // register 4 b + i of lane 16 q + n = pixel X0 + 4 q + i, hypothesis 16 b + n
+                    if (!STM_DBG(dbg, 4))
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, (float)acc[k]), rpx,
+                                                              (X0 + 4 * lb + (k & 3)) * 256 + (16 * (k >> 2) + dd) * 4, 0, 2);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { // pixel X0 + 4 q + i: hypotheses n, 16 + n, 32 + n, 48 + n at bytes 16 n .. 16 n + 15
+                    const f4 o = {acc[i], acc[4 + i], acc[8 + i], acc[12 + i]};
+                    if (!STM_DBG(dbg, 4)) STM_BSTORE(rpx, (X0 + 4 * lb + i) * 256 + 16 * dd, o);
+                }
+            }
         }
         if (more) STM_HC2_COSTS((sq + 1) & 1)
         __syncthreads(); // every wave is done reading the ring and the staging buffers
@@ -1378,6 +1398,21 @@ bool aggm_frame_px(int D, int zd, int H, int W, int usd, bool keep_volume, bool 
     (void)W;
     return !v2_read_later && chain_px(true, !keep_volume, D, zd, usd);
 }
+// The order of the 64 hypotheses inside a PX pixel's 256-byte record, decided here for the kernels that write the records
+// (stm_k_pq_hc / stm_k_pq_hc2 and the second pass of stm_k_pq_v12r) and the one that needs the true index (stm_k_pq_hsr: WTA and
+// the d >= D guard).  A kernel that holds float 16 b + n of a record in register b of lane n and stores the lane's registers
+// b = 0 .. 3 as 16 contiguous bytes puts that float at 4 n + b: the permutation pi.
+//   0  hypothesis d at float d in both volumes: dword stores everywhere, as before (2000000000; identical results)
+//   1  pi: what the first pass's 16-byte stores leave in vol_b, float L = hypothesis 16 (L mod 4) + L div 4.  stm_k_pq_v12r needs no
+//      word of it: every lane is an independent chain.
+//   2  pi after pi: what stm_k_pq_v12r's 16-byte stores make of that in vol_a, float 16 b + n = hypothesis 4 n + b.  The default.
+// The value is the order of the volume the last pass reads.
+static int px_order() { return (agg_variant() / 1000000000) % 10 == 2 ? 0 : 2; }
+int aggm_frame_px_order(int D, int zd, int H, int W, int usd, bool keep_volume, bool v2_read_later)
+{
+    if (usd > 255) usd = 255;
+    return aggm_frame_px(D, zd, H, W, usd, keep_volume, v2_read_later) ? px_order() : -1;
+}
 
 // Blocks per image row of stm_k_pq_hc2 (one block = a part of a row, both views), or 0 where stm_k_pq_hc runs the first pass: the
 // new kernel takes exactly the frames stm_k_pq_hc<12, true> took (px: aggm_frame_px), whose geometry its ring of 256 positions
@@ -1451,6 +1486,7 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
     const bool fuse_cost = from_costs && (agg_variant() / 1000000) % 10 != 1; // 1: separate stm_k_pq_cost + volume-reading first pass
     const int spl = row_split(nseg); // blocks per image row of the streaming passes
     const ChainPlan plan = chain_plan(from_costs, wta, D, zd, H, W, usd, px && nviews == 2);
+    const int ord = px ? px_order() : 0; // the hypothesis order of the PX records the last pass reads; != 0: 16-byte stores before it
     const bool streaming = NG / 4 >= NW && (agg_variant() / 10) % 10 != 1 && (NC <= 4 || (agg_variant() / 10) % 10 != 2); // the ring is at least one segment long; 20: D > 64 on the block-per-segment kernels as before
     // The window tables of the vertical passes and of the last horizontal pass depend on the arms only; they are built once
     // per call for all views (the horizontal one already by stm_k_cross_arms when the caller passes htab_ready)
@@ -1492,25 +1528,32 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
         const int nsegc = cdiv(W, 16 * NWC);
         const size_t smem_hc8 = (size_t)4 * NG * 256 + 16 * NW * 4 + 8 * NW + (size_t)(2 * 16 * NW + 2 * (16 * NW + 2 * pad)) * 8 + (768 + 72) * 4;
         const int hcw = plan.hcw;
-#define STM_HC_LAUNCH(NWX, PXS, GRID, SMEM, NSEG, SPL)                                                                                      \
-    {                                                                                                                                     \
-        allow_lds_m((const void *)stm_k_pq_hc<NWX, PXS>, SMEM);                                                                            \
-        STM_LAUNCH((stm_k_pq_hc<NWX, PXS>), GRID, dim3(64 * NWX), SMEM, stream(), v, D, zd, H, W, G, NC, HG, NSEG, SPL, lut, pad, dbgh);    \
+#define STM_HC_LAUNCH(NWX, PXS, ORD, GRID, SMEM, NSEG, SPL)                                                                                     \
+    {                                                                                                                                          \
+        allow_lds_m((const void *)stm_k_pq_hc<NWX, PXS, ORD>, SMEM);                                                                            \
+        STM_LAUNCH((stm_k_pq_hc<NWX, PXS, ORD>), GRID, dim3(64 * NWX), SMEM, stream(), v, D, zd, H, W, G, NC, HG, NSEG, SPL, lut, pad, dbgh);    \
+    }
+#define STM_HC2_LAUNCH(ORD)                                                                                                                          \
+    {                                                                                                                                               \
+        allow_lds_m((const void *)stm_k_pq_hc2<ORD>, HC2_SMEM);                                                                                      \
+        STM_LAUNCH(stm_k_pq_hc2<ORD>, dim3(H * plan.hc2_spl), dim3(768), HC2_SMEM, stream(), v, D, zd, H, W, G, cdiv(W, HC2_TX), plan.hc2_spl, lut, dbgh); \
     }
         if (plan.hc2_spl) {
             // both views of a row part per block, every cost evaluated once
-            allow_lds_m((const void *)stm_k_pq_hc2, HC2_SMEM);
-            STM_LAUNCH(stm_k_pq_hc2, dim3(H * plan.hc2_spl), dim3(768), HC2_SMEM, stream(), v, D, zd, H, W, G, cdiv(W, HC2_TX), plan.hc2_spl, lut, dbgh);
+            if (ord) STM_HC2_LAUNCH(1)
+            else STM_HC2_LAUNCH(0)
         } else if (hcw == NWC) {
             // streaming row walk (the staged pixels fit one per thread); 2000: one block per segment as in round 2
             const dim3 grid(nviews * H * plan.hc_spl);
-            if (px) STM_HC_LAUNCH(NWC, true, grid, smem_hc, plan.hc_nseg, plan.hc_spl)
-            else STM_HC_LAUNCH(NWC, false, grid, smem_hc, plan.hc_nseg, plan.hc_spl)
+            if (px && ord) STM_HC_LAUNCH(NWC, true, 1, grid, smem_hc, plan.hc_nseg, plan.hc_spl)
+            else if (px) STM_HC_LAUNCH(NWC, true, 0, grid, smem_hc, plan.hc_nseg, plan.hc_spl)
+            else STM_HC_LAUNCH(NWC, false, 0, grid, smem_hc, plan.hc_nseg, plan.hc_spl)
         } else if (hcw == NW) {
             // large D (more staged pixels): 128-pixel segments keep two blocks per CU
             const dim3 grid(nviews * H * plan.hc_spl);
-            if (px) STM_HC_LAUNCH(NW, true, grid, smem_hc8, plan.hc_nseg, plan.hc_spl)
-            else STM_HC_LAUNCH(NW, false, grid, smem_hc8, plan.hc_nseg, plan.hc_spl)
+            if (px && ord) STM_HC_LAUNCH(NW, true, 1, grid, smem_hc8, plan.hc_nseg, plan.hc_spl)
+            else if (px) STM_HC_LAUNCH(NW, true, 0, grid, smem_hc8, plan.hc_nseg, plan.hc_spl)
+            else STM_HC_LAUNCH(NW, false, 0, grid, smem_hc8, plan.hc_nseg, plan.hc_spl)
         } else if (fuse_cost && smem_c12 <= 80 * 1024 && (agg_variant() / 1000) % 10 != 1) { // 1000: 128-pixel segments as in the other passes
             const int nblkc = ((nsegc * H * nviews + 7) / 8) * 8;
             allow_lds_m((const void *)stm_k_pq_h<NWC, false, true>, smem_c12);
@@ -1526,13 +1569,14 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
             STM_LAUNCH((stm_k_pq_h<NW, false, false>), dim3(nblk), dim3(64 * NW), smem_h, stream(), v, D, zd, H, W, G, NC, HG, nseg, dbgh, lut, 0, nviews);
         }
 #undef STM_HC_LAUNCH
+#undef STM_HC2_LAUNCH
         STM_CHECK_LAUNCH();
     }
     {
         // fused vertical kernel
         ProfScope p("pq_v12");
         if (px) {
-            launch_pq_v12r(v, nviews, vtab, H, W, G);
+            launch_pq_v12r(v, nviews, vtab, H, W, G, ord == 2);
         } else if (regs) {
             launch_pq_v12q(v, nviews, vtab, rec, H, W, G, NC);
         } else {
@@ -1545,7 +1589,7 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
     {
         ProfScope p("pq_hw");
         if (hregs) {
-            launch_pq_hsr(v, nviews, htab, D, zd, H, W, px);
+            launch_pq_hsr(v, nviews, htab, D, zd, H, W, px, ord);
         } else if (streaming && !wta) {
             allow_lds_m((const void *)stm_k_pq_hs<NW, false>, smem_h);
             STM_LAUNCH((stm_k_pq_hs<NW, false>), dim3(nviews * H * spl), dim3(64 * NW), smem_h, stream(), v, D, zd, H, W, G, NC, HG, nseg, spl, dbgh);

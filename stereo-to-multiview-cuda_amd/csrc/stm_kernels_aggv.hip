@@ -543,16 +543,21 @@ VR_done_%=:
 // sweep, s30 ring index of the running block, s31 temporary, s[36:83] the 24 mask pairs of the sweep, s[84:85] record address,
 // then jump target, s[86:87] temporaries, s88 .. s91 this step's headers (q0, n of either pass), s[92:95] the next step's (in
 // flight during a step), s96 / s97 temporaries, s98 store offset, s99 entry block (s32 .. s35 are left alone: the ABI's stack
-// registers).  v[224:227] the store addresses.
-// The first pass's accumulators are transposed into row registers for ring 2; the second pass's leave straight from the
-// accumulator registers (register 4 b + i of lane 16 q + n = row 4 q + i, hypothesis 16 b + n: sixteen dword stores of four 64-byte
-// pieces each, four v_add for their row offsets).  Transposing them too, for stores of 256 contiguous bytes with scalar row
-// offsets, measured 0.013 ms slower (0.525 against 0.512 ms, profiles/vcol_store_forms.json).
+// registers).  v[224:227] the store addresses, v[244:247] / v[248:251] the store tuples (X4).
+// The first pass's accumulators are transposed into row registers for ring 2; the second pass's leave from the accumulator
+// registers (register 4 b + i of lane 16 q + n = row 4 q + i, float 16 b + n of the row's record), four v_add for their row offsets:
+// as sixteen dword stores of four 64-byte pieces each, float for float (X4 false), or as four 16-byte stores of four whole
+// records each, float 16 b + n at float 4 n + b (X4 true, below).  Transposing them, for stores of 256 contiguous bytes with scalar
+// row offsets, measured 0.013 ms slower than the dword stores (0.525 against 0.512 ms, profiles/vcol_store_forms.json).
 // EXP: timing experiments (libstm_hip_timing.so only; results NOT valid): 1 = no sweeps, 2 = no loads / stores, 4 = no mask loads,
 // 8 = no transposition / ring moves.
 // Blocks are dealt to the XCDs as they come: neighbouring columns share no cache line of the volumes and no table record, so
 // the remap of the kernel above (a strip's chunk waves on one XCD) has nothing left to keep together.
-template <int EXP>
+// X4: the second pass's rows leave as four buffer_store_dwordx4 (a lane's floats 16 b + n, b = 0 .. 3, of row 4 q + i to bytes
+// 16 n .. 16 n + 15 of that row's record: float 16 b + n of the input record is float 4 n + b of the output record) instead of sixteen
+// dword stores.  The MFMA leaves block b in registers 4 b .. 4 b + 3, so each store's tuple (i, 4 + i, 8 + i, 12 + i) is copied into
+// v[244:247] / v[248:251] first: sixteen v_mov per step.  A step is then 16 loads + 4 stores.
+template <int EXP, bool X4>
 __global__ __launch_bounds__(64, 2) void stm_k_pq_v12r(PQViews pv, const uint32_t *__restrict__ wtab, int H, int G4, int nviews)
 {
     // block (one wave) -> (view, column); columns in [W, 4G) have empty windows and write zeros
@@ -567,9 +572,10 @@ __global__ __launch_bounds__(64, 2) void stm_k_pq_v12r(PQViews pv, const uint32_
     const uint32_t *trow = wtab + ((size_t)view * nT * G4 + x) * HR_REC; // record of tile 0; tile u at + u * G4 * HR_REC dwords
     const int tstep = G4 * HR_REC * 4;
     const int voff = 4 * l; // lane 16 b + n = hypothesis 16 b + n
-    const int vst = 4 * (l >> 4) * rsb + (l & 15) * 4; // lane 16 q + n stores rows 4 q (+ i) of hypotheses (16 b +) n
+    const int vst = 4 * (l >> 4) * rsb + (l & 15) * (X4 ? 16 : 4); // lane 16 q + n stores rows 4 q (+ i) of floats (16 b +) n
     asm volatile(R"ASM(
         .set VC_EXP, %[exp]
+        .set VC_X4, %[x4]
         ; ---------------------------------------------------------------- macros
         ; one block of a sweep: four MFMAs on one quad of ring rows, the A operand (lanes 16 a + m = row a of the quad, tile row m)
         ; shared through CBSZ / ABID.  p = block index, rb = first register of the ring, acur / anxt = the A registers of this / the
@@ -740,7 +746,11 @@ VC_end_%=_\@:
         s_cmp_lt_i32 s24, -3
         s_cbranch_scc1 VC_nocopy_%=_\@
         .if (VC_EXP & 2) == 0
+        .if VC_X4
+        s_waitcnt vmcnt(24)                   ; the 16 loads of the step before the last (issued since: 4 stores, 16 loads, 4 stores)
+        .else
         s_waitcnt vmcnt(48)                   ; the 16 loads of the step before the last (issued since: 16 stores, 16 loads, 16 stores)
+        .endif
         .endif
         .if (VC_EXP & 8) == 0
         s_mov_b32 s97, s25
@@ -911,7 +921,37 @@ VC_noissue1_%=_\@:
         v_add_u32 v226, s98, %[vst]
         s_add_u32 s98, s98, %[rsb]
         v_add_u32 v227, s98, %[vst]
+        .if VC_X4
+        ; the tuples of rows i = 0 .. 3, two register sets in turn (a set is rewritten five instructions after its store)
+        v_mov_b32 v244, v204
+        v_mov_b32 v245, v208
+        v_mov_b32 v246, v212
+        v_mov_b32 v247, v216
         .if (VC_EXP & 2) == 0
+        buffer_store_dwordx4 v[244:247], v224, s[20:23], 0 offen nt
+        .endif
+        v_mov_b32 v248, v205
+        v_mov_b32 v249, v209
+        v_mov_b32 v250, v213
+        v_mov_b32 v251, v217
+        .if (VC_EXP & 2) == 0
+        buffer_store_dwordx4 v[248:251], v225, s[20:23], 0 offen nt
+        .endif
+        v_mov_b32 v244, v206
+        v_mov_b32 v245, v210
+        v_mov_b32 v246, v214
+        v_mov_b32 v247, v218
+        .if (VC_EXP & 2) == 0
+        buffer_store_dwordx4 v[244:247], v226, s[20:23], 0 offen nt
+        .endif
+        v_mov_b32 v248, v207
+        v_mov_b32 v249, v211
+        v_mov_b32 v250, v215
+        v_mov_b32 v251, v219
+        .if (VC_EXP & 2) == 0
+        buffer_store_dwordx4 v[248:251], v227, s[20:23], 0 offen nt
+        .endif
+        .elseif (VC_EXP & 2) == 0
         buffer_store_dword v204, v224, s[20:23], 0 offen nt
         buffer_store_dword v208, v224, s[20:23], 0 offen offset:64 nt
         buffer_store_dword v212, v224, s[20:23], 0 offen offset:128 nt
@@ -952,7 +992,7 @@ VC_done_%=:
         )ASM"
                  :
                  : [in] "s"(in), [out] "s"(out), [trow] "s"(trow), [trow_lo] "s"((uint32_t)(uintptr_t)trow), [trow_hi] "s"((uint32_t)((uintptr_t)trow >> 32)),
-                   [tstep] "s"(tstep), [rsb] "s"(rsb), [H] "s"(H), [nT] "s"(nT), [range] "s"(range), [voff] "v"(voff), [vst] "v"(vst), [exp] "n"(EXP)
+                   [tstep] "s"(tstep), [rsb] "s"(rsb), [H] "s"(H), [nT] "s"(nT), [range] "s"(range), [voff] "v"(voff), [vst] "v"(vst), [exp] "n"(EXP), [x4] "n"(X4 ? 1 : 0)
                  : "memory", "scc", "vcc",
                    "s16", "s17", "s18", "s19", "s20", "s21", "s22", "s23", "s24", "s25", "s26", "s27", "s28", "s29", "s30", "s31", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98", "s99",
                    "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19",
@@ -968,7 +1008,7 @@ VC_done_%=:
                    "v185", "v186", "v187", "v188", "v189", "v190", "v191", "v192", "v193", "v194", "v195", "v196", "v197", "v198", "v199", "v200", "v201",
                    "v202", "v203", "v204", "v205", "v206", "v207", "v208", "v209", "v210", "v211", "v212", "v213", "v214", "v215", "v216", "v217", "v218",
                    "v219", "v220", "v221", "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235",
-                   "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243");
+                   "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251");
 }
 
 // The per-column window table of `nviews` views from the arm planes (the frame path builds it inside stm_k_cross_arms instead).
@@ -1026,12 +1066,16 @@ void launch_vcol_table(PQViews &v, int nviews, uint32_t *tab, int H, int W)
 }
 
 // both vertical passes on PX volumes, vol_b -> vol_a, for `nviews` views; `tab`: the per-column window table (vcol_build)
-void launch_pq_v12r(PQViews &v, int nviews, const uint32_t *tab, int H, int W, int G)
+void launch_pq_v12r(PQViews &v, int nviews, const uint32_t *tab, int H, int W, int G, bool x4)
 {
     (void)W;
     const int G4 = 4 * G;
     const dim3 grid(G4 * nviews);
-#define STM_V12R_LAUNCH(E) STM_LAUNCH(stm_k_pq_v12r<E>, grid, dim3(64), 0, stream(), v, tab, H, G4, nviews)
+#define STM_V12R_LAUNCH(E)                                                                                  \
+    {                                                                                                       \
+        if (x4) STM_LAUNCH((stm_k_pq_v12r<E, true>), grid, dim3(64), 0, stream(), v, tab, H, G4, nviews);   \
+        else STM_LAUNCH((stm_k_pq_v12r<E, false>), grid, dim3(64), 0, stream(), v, tab, H, G4, nviews);     \
+    }
 #ifdef STM_TIMING
     switch (timing_knobs()) {
     case 1: STM_V12R_LAUNCH(1); break;

@@ -65,6 +65,13 @@ def first_pass_path(num_disp, zero_disp, num_rows, num_cols, usd, stages=3):
     return int(lib().stm_first_pass_path(int(num_disp), int(zero_disp), int(num_rows), int(num_cols), int(usd), int(stages)))
 
 
+def px_order(num_disp, zero_disp, num_rows, num_cols, usd, stages=3):
+    """stm_px_order: -1 where such a frame call is off the pixel-major (PX) volumes under the current stm_set_agg_variant, else the
+    order of the hypotheses inside a pixel's record as the last pass reads it: 2 = after the 16-byte stores of the first pass and
+    of the vertical kernel (the default), 0 = ascending, with their 4-byte stores (variant 2000000000).  Host arithmetic only: it launches nothing and needs no GPU."""
+    return int(lib().stm_px_order(int(num_disp), int(zero_disp), int(num_rows), int(num_cols), int(usd), int(stages)))
+
+
 # stm_irv_path's bit field
 IRV_PRUNE, IRV_RUNS, IRV_CHAIN = 1, 2, 4
 
