@@ -1605,14 +1605,32 @@ void release_host_frame_bufs()
 // instead of once per view (it does not depend on the view).
 namespace {
 
-// cost init .. WTA (.. DCC/IRV/bilateral when `refine`) on one rectified pair already split into L / R
+// A frame call's arguments: the reference's, in its order (num_rows .. thresh_h), the `stages` word (3 where the entry has none;
+// bit 0x2000 is the entry's business -- no body looks at it) and the match size of the reduced-resolution calls.  Each extern "C"
+// frame entry fills one and the screens, the bodies and the host flavour take it by reference.
+struct FrameArgs {
+    int num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views;
+    float angle;
+    int num_disp, zero_disp;
+    float ad_coeff, census_coeff, ucd, lcd;
+    int usd, lsd, thresh_s;
+    float thresh_h;
+    int stages;
+    int num_rows_disp = 0, num_cols_disp = 0; // the reduced-resolution calls only
+    float disp_scale = 0.0f;
+};
+
+// cost init .. WTA (.. DCC/IRV/bilateral when `refine`) on one rectified pair H x W already split into L / R, with a's matching
+// parameters and a's `stages` bits 0x100 (HSLO), 0x200 (sub-pixel) and 0x400 (outlier interpolation)
 // pre: optional {BGRX left, BGRX right, wide left, wide right, census left, census right} planes produced together with the split
 // (full-resolution path); the census pair may be null (then it is computed here)
-void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arms &al, Arms &ar, int H, int W, int elem_sz,
-                     int D, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
-                     int thresh_s, float thresh_h, bool refine, bool hslo = false, uint32_t *const *pre = nullptr,
-                     bool subpix = false, bool interp = false)
+void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, int H, int W, const FrameArgs &a, bool refine,
+                     uint32_t *const *pre)
 {
+    const int elem_sz = a.elem_sz, D = a.num_disp, zero_disp = a.zero_disp, usd = a.usd, lsd = a.lsd, thresh_s = a.thresh_s;
+    const float ad_coeff = a.ad_coeff, census_coeff = a.census_coeff, ucd = a.ucd, lcd = a.lcd, thresh_h = a.thresh_h;
+    const bool hslo = stages_hslo(a.stages), subpix = stages_subpix(a.stages);
+    const bool interp = (a.stages & 0x400) != 0; // + interpolation of the outliers region voting leaves (Mei et al. 3.4)
     const size_t HW = (size_t)H * W;
     const int NQ = (D + 3) / 4;
     const size_t V = HW * NQ * 4; // volumes are kept quad-interleaved (float4 [NQ][H][W]) inside the frame
@@ -1627,8 +1645,7 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
     core_ci(img_l, img_r, cl, cr, pk_l, pk_r, ad_coeff, census_coeff, D, zero_disp, H, W, elem_sz, pre != nullptr,
             cost_volume ? nullptr : cen, pre && pre[4] ? pre + 4 : nullptr);
 
-    al = carve_arms(HW);
-    ar = carve_arms(HW);
+    const Arms al = carve_arms(HW), ar = carve_arms(HW);
     uint32_t *htab = nullptr, *vtab = nullptr;
     int vrec = 0, vtop = -1;
     bool vcol = false;
@@ -1716,8 +1733,6 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, Arm
                       bilateral_one_value_table(D, zero_disp, 10.0f, 5.0f), zero_disp);
 }
 
-// the thread's layout (stm_set_layout) against a rendering frame call's geometry, before anything is launched; layout 0, or a call
-// that renders nothing: nothing to check, the call is as it was.  The thread's output format (stm_set_output) is screened here too.
 // the thread's output format (stm_set_output) against a rendering frame call's geometry under the already screened layout `lo`
 static bool frame_output_ok(const char *fn, const Layout &lo, int Hout, int Wout)
 {
@@ -1755,10 +1770,13 @@ static bool frame_output_ok(const char *fn, const Layout &lo, int Hout, int Wout
     fail(msg, arg, __FILE__, __LINE__);
     return false;
 }
-bool frame_layout_ok(const char *fn, int stages, int num_views, int H, int W, int Hout, int Wout)
+// the thread's layout (stm_set_layout) against a rendering frame call's geometry, before anything is launched; layout 0, or a call
+// that renders nothing: nothing to check, the call is as it was.  The thread's output format (stm_set_output) is screened here too.
+bool frame_layout_ok(const char *fn, const FrameArgs &a)
 {
     const Layout lo = layout();
-    if ((stages & 0xff) < 3) return true;
+    const int num_views = a.num_views, Hout = a.num_rows_out, Wout = a.num_cols_out;
+    if ((a.stages & 0xff) < 3) return true;
     if (overlay().mode == 1) { // an overlay (stm_set_overlay) is composited on BGR frames only
         if (output().format == 1) {
             char msg[240];
@@ -1776,13 +1794,16 @@ bool frame_layout_ok(const char *fn, int stages, int num_views, int H, int W, in
         fail(msg, "layout, lens", __FILE__, __LINE__);
         return false;
     }
-    return quilt_args_ok(fn, lo, num_views, H, W, Hout, Wout, "num_views", "num_rows_out", "num_cols_out") && frame_output_ok(fn, lo, Hout, Wout);
+    return quilt_args_ok(fn, lo, num_views, a.num_rows, a.num_cols, Hout, Wout, "num_views", "num_rows_out", "num_cols_out") &&
+           frame_output_ok(fn, lo, Hout, Wout);
 }
 
 // hit maps -> bleed -> masks -> N-2 views -> interlace (d_io.cu:160-205)
-void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_interlaced, int H, int W, int Hout, int Wout,
-                  int elem_sz, int N, float angle, bool linear = false)
+void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_interlaced, const FrameArgs &a)
 {
+    const int H = a.num_rows, W = a.num_cols, Hout = a.num_rows_out, Wout = a.num_cols_out, elem_sz = a.elem_sz, N = a.num_views;
+    const float angle = a.angle;
+    const bool linear = (a.stages & 0x800) != 0; // the views' warps fetched at the fractional coordinate (stm_dibr_dbm_lin)
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
     float *mask_l = Workspace::get<float>(HW), *mask_r = Workspace::get<float>(HW), *blend = Workspace::get<float>(HW);
     launch_hitmask_rows(mask_l, mask_r, d_disp_l, d_disp_r, H, W); // :165-176: dibr_occl, bleed(1) x2, occl_to_mask
@@ -2007,15 +2028,109 @@ void cut_frame_input(const Cut &ct, const PackInput &in, int H, int W, int elem_
                       bal.mode == 2 ? (void *)bal.d_state : nullptr);
 }
 
+// ---- the input prelude of a frame call: the thread's shot-change detector, alignment and balance ahead of the front
+// the three settings against a frame call's geometry, alignment first; nv: the call's NV12 input or null
+bool frame_settings_ok(const char *fn, const FrameArgs &a, const Nv12Input *nv)
+{
+    const bool bgr_sbs = !nv && !packing().on(); // both eyes are gathered from a side-by-side BGR frame
+    return frame_align_ok(fn, a.num_rows, a.num_cols_sbs, a.num_cols, bgr_sbs) &&
+           frame_balance_ok(fn, a.num_rows, a.num_cols_sbs, a.num_cols, bgr_sbs) && frame_cut_ok(fn, a.num_rows, a.num_cols);
+}
+// what the thread's settings add to a frame body's Workspace::begin; prev: a side-by-side history goes through the prelude too
+size_t frame_settings_ws_bytes(const FrameArgs &a, bool prev)
+{
+    const size_t IMG = (size_t)a.num_rows * a.num_cols * a.elem_sz;
+    return (output().format == 1 ? (size_t)a.num_rows_out * a.num_cols_out * a.elem_sz : 0) + // the un-fused NV12 frame's BGR quilt
+           (antialias().mode == 1 ? 2 * IMG + 512 : 0) +                                       // the prefiltered pair
+           (align().mode ? align_ws_bytes(a.num_rows, IMG, prev) : 0) +                        // the aligned frame(s)
+           (balance().mode ? balance_ws_bytes(IMG, prev) : 0) +                                // the balanced frame(s)
+           (cut().mode ? cut_ws_bytes() : 0);                                                  // the detector's signature
+}
+// what the front and the temporal step of a frame body read, after the prelude
+struct FrameInput {
+    const u8 *d_img_sbs; // the side-by-side BGR frame (the caller's, or the aligned / balanced one in the workspace), null for NV12
+    int num_cols_sbs;
+    const Nv12Input *nv;    // the NV12 planes, null once a setting has converted them
+    const u8 *prev_sbs;     // the history's side-by-side frame, through THIS frame's field and tables; null without one
+    bool pack_on;           // the frame is still packed: the front unpacks it
+    bool split_hist;        // an NV12 call: its history comes as split images, used as they are passed
+    PackInput pin;          // the frame as the call was given it
+};
+// The prelude, inside the frame call's Workspace scope and after the split images (and the reduced pair) have been carved: cut,
+// then align, then balance, each where its setting is on.  After an alignment or a balance the call is the plain BGR frame call on
+// the prepared side-by-side frame, and a side-by-side history has gone through the same field and tables.
+FrameInput frame_input(const FrameArgs &a, const u8 *d_img_sbs, const Nv12Input *nv, const TemporalHist *hist)
+{
+    const int H = a.num_rows, W = a.num_cols, elem_sz = a.elem_sz;
+    const Packing pack = packing(); // a packed frame (stm_set_packing): the caller has screened its geometry, or refused it
+    const Align aln = align();
+    const Balance bal = balance();
+    const Cut ct = cut();
+    FrameInput in = {d_img_sbs, a.num_cols_sbs, nv, hist ? hist->sbs : nullptr, pack.on() && !aln.mode && !bal.mode, nv != nullptr,
+                     {pack, nv != nullptr, d_img_sbs, a.num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr, nv ? nv->pitch_y : 0,
+                      nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0}};
+    if (ct.mode) cut_frame_input(ct, in.pin, H, W, elem_sz, (a.stages & 0xff) >= 3, aln, bal); // before any state's fit runs
+    const bool sbs_hist = hist && !in.split_hist;
+    if (aln.mode) { // from here on the call is the plain BGR frame call on the aligned side-by-side frame
+        const u8 *prev = nullptr;
+        in.d_img_sbs = align_frame_input(aln, in.pin, sbs_hist ? in.prev_sbs : nullptr, H, W, elem_sz, prev);
+        if (sbs_hist) in.prev_sbs = prev;
+    }
+    if (bal.mode) { // after the alignment, on whatever the call now points at; then it is the plain BGR frame call on the balanced frame
+        const PackInput plain = {Packing{0, 0, 0, 0}, false, in.d_img_sbs, 2 * W, nullptr, nullptr, 0, 0, 0};
+        const u8 *prev = nullptr;
+        in.d_img_sbs = balance_frame_input(bal, aln.mode ? plain : in.pin, sbs_hist ? in.prev_sbs : nullptr, H, W, elem_sz, prev);
+        if (sbs_hist) in.prev_sbs = prev;
+    }
+    if (aln.mode || bal.mode) {
+        in.num_cols_sbs = 2 * W;
+        in.nv = nullptr;
+    }
+    return in;
+}
+
+// temporal stabilisation (0x2000): the final maps pulled towards the previous frame's where neither colour nor disparity moved, each
+// view on its own half of the two side-by-side buffers (read in place: the history was never split) -- or, for an NV12 or a packed
+// frame, on the two frames' split images
+void frame_temporal(const FrameArgs &a, const FrameInput &in, const TemporalHist &hist, const u8 *img_l, const u8 *img_r, float *d_disp_l,
+                    float *d_disp_r)
+{
+    const int H = a.num_rows, W = a.num_cols, elem_sz = a.elem_sz;
+    float *c[2] = {d_disp_l, d_disp_r};
+    const float *q[2] = {hist.disp_l, hist.disp_r};
+    const bool split = in.split_hist || in.pack_on; // the views as split images; otherwise in place in the two side-by-side frames
+    const u8 *prev_l = hist.img_l, *prev_r = hist.img_r;
+    if (in.pack_on && !in.nv) { // the previous PACKED frame: its images are its unpacking (one more launch in this combination only)
+        const size_t IMG = (size_t)H * W * elem_sz;
+        u8 *ul = Workspace::get<u8>(IMG), *ur = Workspace::get<u8>(IMG);
+        PackInput prev = in.pin;
+        prev.frame = in.prev_sbs;
+        launch_demux_packed(ul, ur, prev, H, W, elem_sz);
+        prev_l = ul;
+        prev_r = ur;
+    }
+    const u8 *im[2] = {split ? img_l : in.d_img_sbs, split ? img_r : in.d_img_sbs}, *ip[2] = {split ? prev_l : in.prev_sbs, split ? prev_r : in.prev_sbs};
+    const size_t off[2] = {0, split ? 0 : (size_t)W * elem_sz};
+    launch_disp_temporal(2, c, q, im, ip, off, H, W, split ? W : in.num_cols_sbs, elem_sz, hist.alpha, hist.thresh_color, hist.thresh_disp);
+}
+
+// the tail of a rendering frame call: the renderer, then the thread's overlay (stm_set_overlay) composited on the finished frame --
+// the call's last launch
+void frame_tail(const FrameArgs &a, u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_interlaced)
+{
+    frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, a);
+    if (overlay().mode == 1)
+        frame_overlay(d_interlaced, overlay(), lens(), layout(), a.num_views, a.angle, a.num_rows_out, a.num_cols_out, a.elem_sz);
+}
+
 // the body of stm_d_adcensus_stm, stm_d_adcensus_stm_t and stm_d_adcensus_stm_nv12; hist != nullptr: the temporal step between
 // the bilateral filter and the renderer; nv != nullptr: the frame comes as NV12 planes (d_img_sbs is null, num_cols_sbs >= 2 W).
 // Every argument has been screened by the caller except the `stages` rules the calls share.
-void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced, int num_rows,
-                  int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz, int num_views, float angle,
-                  int num_disp, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd, int thresh_s,
-                  float thresh_h, int stages, const TemporalHist *hist, const Nv12Input *nv = nullptr)
+void frame_device(const char *fn, const FrameArgs &a, const u8 *d_img_sbs, float *d_disp_l, float *d_disp_r, u8 *d_interlaced,
+                  const TemporalHist *hist, const Nv12Input *nv = nullptr)
 {
     char msg[200];
+    const int stages = a.stages;
     if ((stages & 0x300) == 0x300) { // sub-pixel enhancement reads the last horizontal pass's input, which HSLO does not keep
         snprintf(msg, sizeof msg, "%s: stages 0x200 (sub-pixel) together with 0x100 (HSLO) is not supported", fn);
         fail(msg, "stages", __FILE__, __LINE__);
@@ -2036,64 +2151,25 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
         fail(msg, "stages", __FILE__, __LINE__);
         return;
     }
-    if (!frame_layout_ok(fn, stages, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return;
-    const int H = num_rows, W = num_cols, N = num_views;
+    if (!frame_layout_ok(fn, a) || !frame_settings_ok(fn, a, nv)) return;
+    const int H = a.num_rows, W = a.num_cols, N = a.num_views, elem_sz = a.elem_sz;
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
-    const size_t V = pq_volume_floats(num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
-    const Packing pack = packing(); // a packed frame (stm_set_packing): the caller has screened its geometry
-    if (!frame_align_ok(fn, H, num_cols_sbs, W, !nv && !pack.on())) return;
-    const Align aln = align();       // the vertical alignment (stm_set_align), screened above
-    if (!frame_balance_ok(fn, H, num_cols_sbs, W, !nv && !pack.on())) return;
-    const Balance bal = balance();   // the colour balance (stm_set_balance), screened above
-    if (!frame_cut_ok(fn, H, W)) return;
-    const Cut ct = cut();            // the shot-change detector (stm_set_cut), screened above
-    Workspace::begin(((stages & 0x100) ? 13 : 4) * V * 4 + (size_t)(N + 2 + (pack.on() && hist && !nv ? 2 : 0)) * IMG + 168 * HW + (1u << 20) +
-                     (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0) + // the un-fused NV12 frame's BGR quilt
-                     (antialias().mode == 1 ? 2 * IMG + 512 : 0) +                                  // the prefiltered pair
-                     (aln.mode ? align_ws_bytes(H, IMG, hist && !nv) : 0) +                          // the aligned frame(s)
-                     (bal.mode ? balance_ws_bytes(IMG, hist && !nv) : 0) +                           // the balanced frame(s)
-                     (ct.mode ? cut_ws_bytes() : 0));                                                // the detector's signature
+    const size_t V = pq_volume_floats(a.num_disp, H, W); // >= the quad-interleaved volume of the HSLO / legacy paths
+    const bool unpacked_hist = packing().on() && hist && !nv; // the previous packed frame's two images (frame_temporal)
+    Workspace::begin(((stages & 0x100) ? 13 : 4) * V * 4 + (size_t)(N + 2 + (unpacked_hist ? 2 : 0)) * IMG + 168 * HW + (1u << 20) +
+                     frame_settings_ws_bytes(a, hist && !nv));
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
-    const bool split_hist = nv != nullptr; // ... and an NV12 frame's history comes as split images
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     uint32_t *pre[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const PackInput pin = {pack, nv != nullptr, d_img_sbs, num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr, nv ? nv->pitch_y : 0,
-                           nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0};
-    const bool pack_on = pack.on() && !aln.mode && !bal.mode;
-    if (ct.mode) cut_frame_input(ct, pin, H, W, elem_sz, (stages & 0xff) >= 3, aln, bal); // before any state's fit runs
-    TemporalHist hist_aligned;
-    if (aln.mode) { // from here on the call is the plain BGR frame call on the aligned side-by-side frame
-        d_img_sbs = align_frame_input(aln, pin, hist && !nv ? hist->sbs : nullptr, H, W, elem_sz, hist_aligned.sbs);
-        if (hist && !nv) {
-            const u8 *prev = hist_aligned.sbs;
-            hist_aligned = *hist;
-            hist_aligned.sbs = prev;
-            hist = &hist_aligned;
-        }
-        num_cols_sbs = 2 * W;
-        nv = nullptr;
-    }
-    TemporalHist hist_balanced;
-    if (bal.mode) { // after the alignment, on whatever the call now points at; then it is the plain BGR frame call on the balanced frame
-        const PackInput plain = {Packing{0, 0, 0, 0}, false, d_img_sbs, num_cols_sbs, nullptr, nullptr, 0, 0, 0};
-        const bool sbs_hist = hist && !split_hist;
-        d_img_sbs = balance_frame_input(bal, aln.mode ? plain : pin, sbs_hist ? hist->sbs : nullptr, H, W, elem_sz, hist_balanced.sbs);
-        if (sbs_hist) {
-            const u8 *prev = hist_balanced.sbs;
-            hist_balanced = *hist;
-            hist_balanced.sbs = prev;
-            hist = &hist_balanced;
-        }
-        num_cols_sbs = 2 * W;
-        nv = nullptr;
-    }
-    bool fused_split = num_cols_sbs >= 2 * W; // both halves complete: emit the derived pixel formats in the same pass
-    if (pack_on && (agg_variant() / 100) % 10 != 6) { // the gather, the filter and the conversion in stm_k_front's pass
+    const FrameInput in = frame_input(a, d_img_sbs, nv, hist);
+    nv = in.nv;
+    bool fused_split = in.num_cols_sbs >= 2 * W; // both halves complete: emit the derived pixel formats in the same pass
+    if (in.pack_on && (agg_variant() / 100) % 10 != 6) { // the gather, the filter and the conversion in stm_k_front's pass
         for (int i = 0; i < 6; ++i) pre[i] = Workspace::get<uint32_t>(HW);
-        launch_front_pack(img_l, img_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], pin, H, W, elem_sz);
+        launch_front_pack(img_l, img_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], in.pin, H, W, elem_sz);
         fused_split = true;
-    } else if (pack_on) { // 600: the plain unpacking, then the pixel formats and the census as kernels of their own
-        launch_demux_packed(img_l, img_r, pin, H, W, elem_sz);
+    } else if (in.pack_on) { // 600: the plain unpacking, then the pixel formats and the census as kernels of their own
+        launch_demux_packed(img_l, img_r, in.pin, H, W, elem_sz);
         fused_split = false;
     } else if (nv && (agg_variant() / 100) % 10 != 6) { // the conversion in stm_k_front's pass
         for (int i = 0; i < 6; ++i) pre[i] = Workspace::get<uint32_t>(HW);
@@ -2104,59 +2180,31 @@ void frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, flo
         fused_split = false;
     } else if (fused_split && (agg_variant() / 100) % 10 != 6) { // ... and the census words; 600: the split and the census as two kernels
         for (int i = 0; i < 6; ++i) pre[i] = Workspace::get<uint32_t>(HW);
-        launch_front(img_l, img_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], d_img_sbs, H, num_cols_sbs, W, elem_sz);
+        launch_front(img_l, img_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], in.d_img_sbs, H, in.num_cols_sbs, W, elem_sz);
     } else if (fused_split) {
         for (int i = 0; i < 4; ++i) pre[i] = Workspace::get<uint32_t>(HW);
-        launch_demux_sbs_packed(img_l, img_r, pre[0], pre[1], pre[2], pre[3], d_img_sbs, H, num_cols_sbs, W, elem_sz);
+        launch_demux_sbs_packed(img_l, img_r, pre[0], pre[1], pre[2], pre[3], in.d_img_sbs, H, in.num_cols_sbs, W, elem_sz);
     } else {
-        launch_demux_sbs(img_l, img_r, d_img_sbs, H, num_cols_sbs, W, elem_sz);
+        launch_demux_sbs(img_l, img_r, in.d_img_sbs, H, in.num_cols_sbs, W, elem_sz);
     }
-    Arms al, ar;
-    const bool hslo = stages_hslo(stages), subpix = stages_subpix(stages);
-    const bool interp = (stages & 0x400) != 0; // + interpolation of the outliers region voting leaves (Mei et al. 3.4)
-    const bool linwarp = (stages & 0x800) != 0; // + the views' warps fetched at the fractional coordinate (stm_dibr_dbm_lin)
-    stages &= 0xff;
-    frame_disparity(img_l, img_r, d_disp_l, d_disp_r, al, ar, H, W, elem_sz, num_disp, zero_disp, ad_coeff, census_coeff, ucd,
-                    lcd, usd, lsd, thresh_s, thresh_h, stages >= 2, hslo, fused_split ? pre : nullptr, subpix, interp);
-    // temporal stabilisation (0x2000): the filtered maps pulled towards the previous frame's where neither colour nor disparity
-    // moved, each view on its own half of the two side-by-side buffers (read in place: the history was never split) -- or, for an
-    // NV12 frame, on the two frames' converted split images
-    if (hist) {
-        float *c[2] = {d_disp_l, d_disp_r};
-        const float *q[2] = {hist->disp_l, hist->disp_r};
-        const bool split = split_hist || pack_on; // the views as split images; otherwise in place in the two side-by-side frames
-        const u8 *prev_l = hist->img_l, *prev_r = hist->img_r;
-        if (pack_on && !nv) { // the previous PACKED frame: its images are its unpacking (one more launch in this combination only)
-            u8 *ul = Workspace::get<u8>(IMG), *ur = Workspace::get<u8>(IMG);
-            PackInput prev = pin;
-            prev.frame = hist->sbs;
-            launch_demux_packed(ul, ur, prev, H, W, elem_sz);
-            prev_l = ul;
-            prev_r = ur;
-        }
-        const u8 *im[2] = {split ? img_l : d_img_sbs, split ? img_r : d_img_sbs}, *ip[2] = {split ? prev_l : hist->sbs, split ? prev_r : hist->sbs};
-        const size_t off[2] = {0, split ? 0 : (size_t)W * elem_sz};
-        launch_disp_temporal(2, c, q, im, ip, off, H, W, split ? W : num_cols_sbs, elem_sz, hist->alpha, hist->thresh_color, hist->thresh_disp);
-    }
-    if (stages < 3) return;
-    frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle, linwarp);
-    // the thread's overlay (stm_set_overlay), composited on the finished frame: the call's last launch
-    if (overlay().mode == 1) frame_overlay(d_interlaced, overlay(), lens(), layout(), N, angle, num_rows_out, num_cols_out, elem_sz);
+    frame_disparity(img_l, img_r, d_disp_l, d_disp_r, H, W, a, (stages & 0xff) >= 2, fused_split ? pre : nullptr);
+    if (hist) frame_temporal(a, in, *hist, img_l, img_r, d_disp_l, d_disp_r);
+    if ((stages & 0xff) >= 3) frame_tail(a, img_l, img_r, d_disp_l, d_disp_r, d_interlaced);
 }
 
-bool frame_dims_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz,
-                   int num_views, int num_disp)
+// ---- the screens of the frame entries
+bool frame_dims_ok(const char *fn, const FrameArgs &a)
 {
-    return args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols", num_cols, 1},
-                        {"num_rows_out", num_rows_out, 1}, {"num_cols_out", num_cols_out, 1}, {"elem_sz", elem_sz, 3},
-                        {"num_views", num_views, 2}, {"num_disp", num_disp, 1}});
+    return args_ok(fn, {{"num_rows", a.num_rows, 1}, {"num_cols_sbs", a.num_cols_sbs, 1}, {"num_cols", a.num_cols, 1},
+                        {"num_rows_out", a.num_rows_out, 1}, {"num_cols_out", a.num_cols_out, 1}, {"elem_sz", a.elem_sz, 3},
+                        {"num_views", a.num_views, 2}, {"num_disp", a.num_disp, 1}});
 }
 
 // the thread's packing (stm_set_packing) against a BGR frame call's geometry; packing off: nothing to check, the call is as it was
-bool frame_packing_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols)
+bool frame_packing_ok(const char *fn, const FrameArgs &a)
 {
     const Packing pk = packing();
-    return !pk.on() || packing_args_ok(fn, pk, num_rows, num_cols_sbs, num_cols, "num_cols", false, 0, 0, 0);
+    return !pk.on() || packing_args_ok(fn, pk, a.num_rows, a.num_cols_sbs, a.num_cols, "num_cols", false, 0, 0, 0);
 }
 // the calls that take the reference's layout only
 bool packing_unsupported(const char *fn)
@@ -2169,159 +2217,79 @@ bool packing_unsupported(const char *fn)
     return true;
 }
 
-} // namespace
-
-extern "C" {
-
-// which aggregation kernels a frame call with these arguments runs (stm_hip.h); no launch, no device
-int stm_agg_path(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages)
+// the two output images of an NV12 call come together or not at all
+bool nv12_images_ok(const char *fn, const Nv12Input &nv)
 {
-    return frame_agg_path(num_disp, zero_disp, num_rows, num_cols, usd, stages);
-}
-// whether stm_k_pq_hc2 runs the first horizontal pass of such a call, as its parts per image row (stm_hip.h); no launch, no device
-int stm_first_pass_path(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages)
-{
-    return frame_first_pass_path(num_disp, zero_disp, num_rows, num_cols, usd, stages);
-}
-// the order of the hypotheses inside a pixel's record of such a call's PX volumes, or -1 off PX (stm_hip.h); no launch, no device
-int stm_px_order(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages)
-{
-    return frame_px_order(num_disp, zero_disp, num_rows, num_cols, usd, stages);
+    if ((nv.img_l != nullptr) == (nv.img_r != nullptr)) return true;
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: d_img_l and d_img_r must be both null (the split images stay in the workspace) or both set", fn);
+    fail(msg, "d_img_l, d_img_r", __FILE__, __LINE__);
+    return false;
 }
 
-void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
-                        int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz,
-                        int num_views, float angle, int num_disp, int zero_disp, float ad_coeff, float census_coeff,
-                        float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages)
+// `stages` bit 0x2000 of the four entries that take a history: the three parameters, then the pointers.  nv == nullptr: the
+// side-by-side form (the previous frame and its two maps), else the split form of the NV12 entries (the previous split images and
+// maps, and this frame's images kept by the caller).  *run: all history pointers are set, so the step runs (all null: the first
+// frame of a sequence).  The rule for stages below 2 can fire for the full-resolution entries only: the reduced ones always render.
+bool frame_history_ok(const char *fn, const FrameArgs &a, const TemporalHist &h, const float *d_disp_l, const float *d_disp_r,
+                      const Nv12Input *nv, bool *run)
 {
-    if (!frame_dims_ok("d_adcensus_stm", num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views, num_disp)) return;
-    if (!frame_packing_ok("d_adcensus_stm", num_rows, num_cols_sbs, num_cols)) return;
-    if (stages & 0x2000) { // temporal stabilisation needs the previous frame: this call has no arguments for it
-        fail("d_adcensus_stm: stages 0x2000 (temporal stabilisation) needs the history arguments of d_adcensus_stm_t", "stages", __FILE__,
-             __LINE__);
-        return;
+    *run = false;
+    if (!(a.stages & 0x2000)) return true;
+    if (!temporal_params_ok(fn, h.alpha, h.thresh_color, h.thresh_disp)) return false;
+    const bool split = nv != nullptr;
+    const size_t HW = (size_t)a.num_rows * a.num_cols, IMG = HW * a.elem_sz;
+    // the history is read while the outputs are written: images first, then maps
+    const void *hp[4] = {h.img_l, h.img_r, h.disp_l, h.disp_r}, *out[4] = {split ? nv->img_l : nullptr, split ? nv->img_r : nullptr, d_disp_l, d_disp_r};
+    const size_t sz[4] = {IMG, IMG, HW * 4, HW * 4};
+    const int first = split ? 0 : 2, all = split ? 4 : 3;
+    const int nset = (split ? (h.img_l != nullptr) + (h.img_r != nullptr) : (h.sbs != nullptr)) + (h.disp_l != nullptr) + (h.disp_r != nullptr);
+    bool alias = false;
+    for (int i = first; i < 4 && nset == all; ++i)
+        for (int j = first; j < 4; ++j) alias = alias || bytes_overlap(hp[i], sz[i], out[j], sz[j]);
+    char msg[240];
+    const char *arg = nullptr;
+    if ((a.stages & 0xff) < 2) { // the step filters the refined maps: stage 1 has none
+        snprintf(msg, sizeof msg, "%s: stages 0x2000 (temporal stabilisation) needs the refinement stages (2 or 3)", fn);
+        arg = "stages";
+    } else if (split && !nv->img_l) { // this frame's converted images are the next frame's history: the caller must keep them
+        snprintf(msg, sizeof msg, "%s: stages 0x2000 (temporal stabilisation) needs the output images d_img_l and d_img_r", fn);
+        arg = "d_img_l, d_img_r";
+    } else if (nset != 0 && nset != all) {
+        snprintf(msg, sizeof msg, "%s: the %s history pointers must be all null (first frame) or all set", fn, split ? "four" : "three");
+        arg = split ? "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r" : "d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r";
+    } else if (nset == all && !split && !packing().on() && a.num_cols_sbs < 2 * a.num_cols) { // the views are read from the two halves in place
+        snprintf(msg, sizeof msg, "%s: stages 0x2000 (temporal stabilisation) needs num_cols_sbs >= 2 * num_cols", fn);
+        arg = "num_cols_sbs";
+    } else if (alias && split) {
+        snprintf(msg, sizeof msg, "%s: a history buffer must not alias an output (d_img_l, d_img_r, d_disp_l, d_disp_r)", fn);
+        arg = "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r";
+    } else if (alias) {
+        snprintf(msg, sizeof msg, "%s: a history map must not alias d_disp_l or d_disp_r", fn);
+        arg = "d_prev_disp_l, d_prev_disp_r";
     }
-    frame_device("d_adcensus_stm", d_img_sbs, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out,
-                 elem_sz, num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages, nullptr);
-}
-
-// stm_d_adcensus_stm with the history of the temporal stabilisation (stm_hip.h)
-void stm_d_adcensus_stm_t(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
-                          int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz,
-                          int num_views, float angle, int num_disp, int zero_disp, float ad_coeff, float census_coeff,
-                          float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages,
-                          unsigned char *d_prev_img_sbs, float *d_prev_disp_l, float *d_prev_disp_r, float alpha, int thresh_color,
-                          float thresh_disp)
-{
-    const char *fn = "d_adcensus_stm_t";
-    if (!frame_dims_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views, num_disp)) return;
-    if (!frame_packing_ok(fn, num_rows, num_cols_sbs, num_cols)) return;
-    TemporalHist hist = {d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp};
-    bool run = false;
-    if (stages & 0x2000) {
-        const int nset = (d_prev_img_sbs != nullptr) + (d_prev_disp_l != nullptr) + (d_prev_disp_r != nullptr);
-        const size_t HW = (size_t)num_rows * num_cols;
-        if (!temporal_params_ok(fn, alpha, thresh_color, thresh_disp)) return;
-        if ((stages & 0xff) < 2) { // the step filters the refined maps: stage 1 has none
-            fail("d_adcensus_stm_t: stages 0x2000 (temporal stabilisation) needs the refinement stages (2 or 3)", "stages", __FILE__, __LINE__);
-            return;
-        }
-        if (nset != 0 && nset != 3) {
-            fail("d_adcensus_stm_t: the three history pointers must be all null (first frame) or all set", "d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r",
-                 __FILE__, __LINE__);
-            return;
-        }
-        if (nset == 3 && !packing().on() && num_cols_sbs < 2 * num_cols) { // the views are read from the two halves in place
-            fail("d_adcensus_stm_t: stages 0x2000 (temporal stabilisation) needs num_cols_sbs >= 2 * num_cols", "num_cols_sbs", __FILE__, __LINE__);
-            return;
-        }
-        if (nset == 3 && (maps_overlap(d_prev_disp_l, d_disp_l, HW) || maps_overlap(d_prev_disp_l, d_disp_r, HW) ||
-                          maps_overlap(d_prev_disp_r, d_disp_l, HW) || maps_overlap(d_prev_disp_r, d_disp_r, HW))) {
-            fail("d_adcensus_stm_t: a history map must not alias d_disp_l or d_disp_r", "d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
-            return;
-        }
-        run = nset == 3;
-    }
-    frame_device(fn, d_img_sbs, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz,
-                 num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages & ~0x2000,
-                 run ? &hist : nullptr);
-}
-
-// stm_d_adcensus_stm_t on an NV12 frame (stm_hip.h): the same body, the conversion fused into its first kernel
-void stm_d_adcensus_stm_nv12(unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv, int matrix, float *d_disp_l, float *d_disp_r,
-                             unsigned char *d_interlaced, int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
-                             int elem_sz, int num_views, float angle, int num_disp, int zero_disp, float ad_coeff, float census_coeff,
-                             float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages,
-                             unsigned char *d_prev_img_l, unsigned char *d_prev_img_r, float *d_prev_disp_l, float *d_prev_disp_r, float alpha,
-                             int thresh_color, float thresh_disp, unsigned char *d_img_l, unsigned char *d_img_r)
-{
-    const char *fn = "d_adcensus_stm_nv12";
-    if (!frame_dims_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views, num_disp)) return;
-    if (packing().on()) { // a packed NV12 frame: the packing's own geometry rules in place of the side-by-side ones
-        if (!packing_args_ok(fn, packing(), num_rows, num_cols_sbs, num_cols, "num_cols", true, pitch_y, pitch_uv, matrix)) return;
-    } else if (!nv12_args_ok(fn, num_rows, num_cols_sbs, num_cols, "num_cols", pitch_y, pitch_uv, matrix)) return;
-    if ((d_img_l != nullptr) != (d_img_r != nullptr)) {
-        fail("d_adcensus_stm_nv12: d_img_l and d_img_r must be both null (the split images stay in the workspace) or both set", "d_img_l, d_img_r",
-             __FILE__, __LINE__);
-        return;
-    }
-    TemporalHist hist = {nullptr, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp, d_prev_img_l, d_prev_img_r};
-    Nv12Input nv = {d_y, d_uv, pitch_y, pitch_uv, matrix, d_img_l, d_img_r};
-    bool run = false;
-    if (stages & 0x2000) {
-        const int nset = (d_prev_img_l != nullptr) + (d_prev_img_r != nullptr) + (d_prev_disp_l != nullptr) + (d_prev_disp_r != nullptr);
-        const size_t HW = (size_t)num_rows * num_cols, IMG = HW * elem_sz;
-        if (!temporal_params_ok(fn, alpha, thresh_color, thresh_disp)) return;
-        if ((stages & 0xff) < 2) { // as d_adcensus_stm_t
-            fail("d_adcensus_stm_nv12: stages 0x2000 (temporal stabilisation) needs the refinement stages (2 or 3)", "stages", __FILE__, __LINE__);
-            return;
-        }
-        if (!d_img_l) { // this frame's converted images are the next frame's history: the caller must keep them
-            fail("d_adcensus_stm_nv12: stages 0x2000 (temporal stabilisation) needs the output images d_img_l and d_img_r", "d_img_l, d_img_r",
-                 __FILE__, __LINE__);
-            return;
-        }
-        if (nset != 0 && nset != 4) {
-            fail("d_adcensus_stm_nv12: the four history pointers must be all null (first frame) or all set",
-                 "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
-            return;
-        }
-        if (nset == 4) { // the history is read while the outputs are written
-            const void *h[4] = {d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r}, *o[4] = {d_img_l, d_img_r, d_disp_l, d_disp_r};
-            const size_t sz[4] = {IMG, IMG, HW * 4, HW * 4};
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 4; ++j)
-                    if (bytes_overlap(h[i], sz[i], o[j], sz[j])) {
-                        fail("d_adcensus_stm_nv12: a history buffer must not alias an output (d_img_l, d_img_r, d_disp_l, d_disp_r)",
-                             "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
-                        return;
-                    }
-        }
-        run = nset == 4;
-    }
-    frame_device(fn, nullptr, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz,
-                 num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages & ~0x2000,
-                 run ? &hist : nullptr, &nv);
+    if (arg) fail(msg, arg, __FILE__, __LINE__);
+    *run = !arg && nset == all;
+    return !arg;
 }
 
 // adcensus_stm_2, d_io.cu:240-508: the disparity is computed on a bilinearly reduced pair
 // (num_rows_disp x num_cols_disp, tx_scale_bilinear_kernel :302-304), scaled back up with
 // tx_disp_scale_kernel(1/disp_scale) (:415-417), then the views are rendered at full resolution.
 // The two _2s calls add the `stages` word (stm_hip.h); the two reference calls are the same bodies with stages = 3.
-} // extern "C"
-namespace {
 
-// temporal_ok: the call has the history arguments of stages bit 0x2000 (d_adcensus_stm_2t, d_adcensus_stm_2nv12)
-bool reduced_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int num_rows_disp,
-                     int num_cols_disp, int elem_sz, int num_views, int num_disp, int stages, bool temporal_ok = false)
+// the screen of every reduced-resolution entry, once per call; temporal_ok: the call has the history arguments of stages bit
+// 0x2000 (d_adcensus_stm_2t, d_adcensus_stm_2nv12)
+bool reduced_args_ok(const char *fn, const FrameArgs &a, bool temporal_ok = false)
 {
-    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols", num_cols, 1},
-                      {"num_rows_out", num_rows_out, 1}, {"num_cols_out", num_cols_out, 1}, {"num_rows_disp", num_rows_disp, 1},
-                      {"num_cols_disp", num_cols_disp, 1}, {"elem_sz", elem_sz, 3}, {"num_views", num_views, 2},
-                      {"num_disp", num_disp, 1}}))
+    if (!args_ok(fn, {{"num_rows", a.num_rows, 1}, {"num_cols_sbs", a.num_cols_sbs, 1}, {"num_cols", a.num_cols, 1},
+                      {"num_rows_out", a.num_rows_out, 1}, {"num_cols_out", a.num_cols_out, 1}, {"num_rows_disp", a.num_rows_disp, 1},
+                      {"num_cols_disp", a.num_cols_disp, 1}, {"elem_sz", a.elem_sz, 3}, {"num_views", a.num_views, 2},
+                      {"num_disp", a.num_disp, 1}}))
         return false;
     if (packing_unsupported(fn)) return false;
     char msg[200];
+    const int stages = a.stages;
     if ((stages & 0xff) != 3 || (stages & ~(temporal_ok ? 0x3fff : 0x1fff))) { // this path always renders
         snprintf(msg, sizeof msg, "%s: stages = 0x%x, must be 3, optionally OR-ed with 0x100, 0x200, 0x400, 0x800%s 0x1000%s", fn, stages,
                  temporal_ok ? "," : " and", temporal_ok ? " and 0x2000" : "");
@@ -2348,94 +2316,40 @@ void reduced_front_chain(u8 *img_l, u8 *img_r, u8 *low_l, u8 *low_r, const u8 *d
 }
 bool reduced_front_fused(int num_cols_sbs, int W) { return num_cols_sbs >= 2 * W && (agg_variant() / 100) % 10 != 6; }
 
-// the body of the reduced-resolution frame calls; hist != nullptr: the temporal step on the up-scaled full-size maps, between the
-// up-scale and the renderer (the placement rule of frame_device: on the final maps); nv != nullptr: the frame comes as NV12 planes
-// (d_img_sbs is null, num_cols_sbs >= 2 W).  temporal_ok: the caller has screened bit 0x2000 and taken it out of `stages`.
-void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
-                          int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int num_rows_disp,
-                          int num_cols_disp, int elem_sz, float disp_scale, int num_views, float angle, int num_disp, int zero_disp,
-                          float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h,
-                          int stages, const TemporalHist *hist = nullptr, const Nv12Input *nv = nullptr)
+// the body of the reduced-resolution frame calls, screened by the caller (reduced_args_ok); hist != nullptr: the temporal step on
+// the up-scaled full-size maps, between the up-scale and the renderer (the placement rule of frame_device: on the final maps);
+// nv != nullptr: the frame comes as NV12 planes (d_img_sbs is null, num_cols_sbs >= 2 W)
+void reduced_frame_device(const char *fn, const FrameArgs &a, const u8 *d_img_sbs, float *d_disp_l, float *d_disp_r, u8 *d_interlaced,
+                          const TemporalHist *hist, const Nv12Input *nv = nullptr)
 {
-    if (!reduced_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp, num_cols_disp, elem_sz,
-                         num_views, num_disp, stages))
-        return;
-    if (!frame_layout_ok(fn, stages, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return;
-    const int H = num_rows, W = num_cols, h = num_rows_disp, w = num_cols_disp, N = num_views;
+    if (!frame_layout_ok(fn, a) || !frame_settings_ok(fn, a, nv)) return;
+    const int H = a.num_rows, W = a.num_cols, h = a.num_rows_disp, w = a.num_cols_disp, N = a.num_views, elem_sz = a.elem_sz;
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz, hw = (size_t)h * w;
-    const size_t V = pq_volume_floats(num_disp, h, w);
-    const bool hslo = stages_hslo(stages), subpix = stages_subpix(stages), interp = (stages & 0x400) != 0; // on the reduced pair
-    const bool linwarp = (stages & 0x800) != 0;                                                             // in the full-size render
-    const bool guided = (stages & 0x1000) != 0; // the up-scale between the two: stm_disp_upsample instead of tx_disp_scale
-    if (!frame_align_ok(fn, H, num_cols_sbs, W, !nv)) return;
-    const Align aln = align(); // the vertical alignment (stm_set_align), screened above
-    if (!frame_balance_ok(fn, H, num_cols_sbs, W, !nv)) return;
-    const Balance bal = balance(); // the colour balance (stm_set_balance), screened above
-    if (!frame_cut_ok(fn, H, W)) return;
-    const Cut ct = cut(); // the shot-change detector (stm_set_cut), screened above
-    Workspace::begin((hslo ? 13 : 4) * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 32 * hw + (1u << 20) + // HSLO: as d_adcensus_stm
-                     (output().format == 1 ? (size_t)num_rows_out * num_cols_out * elem_sz : 0) +
-                     (antialias().mode == 1 ? 2 * IMG + 512 : 0) +                // the prefiltered pair
-                     (aln.mode ? align_ws_bytes(H, IMG, hist && !nv) : 0) +        // the aligned frame(s)
-                     (bal.mode ? balance_ws_bytes(IMG, hist && !nv) : 0) +         // the balanced frame(s)
-                     (ct.mode ? cut_ws_bytes() : 0));                              // the detector's signature
+    const size_t V = pq_volume_floats(a.num_disp, h, w);
+    Workspace::begin((stages_hslo(a.stages) ? 13 : 4) * V * 4 + (size_t)(N + 4) * IMG + 136 * HW + 32 * hw + (1u << 20) + // HSLO: as d_adcensus_stm
+                     frame_settings_ws_bytes(a, hist && !nv));
     const bool own_img = nv && nv->img_l; // the caller keeps the split images (the next frame's history)
-    const bool split_hist = nv != nullptr; // ... and an NV12 frame's history comes as split images
     u8 *img_l = own_img ? nv->img_l : Workspace::get<u8>(IMG), *img_r = own_img ? nv->img_r : Workspace::get<u8>(IMG);
     u8 *low_l = Workspace::get<u8>(hw * elem_sz), *low_r = Workspace::get<u8>(hw * elem_sz);
-    if (ct.mode) { // before any state's fit runs, on the full-resolution input
-        const PackInput pin = {Packing{0, 0, 0, 0}, nv != nullptr, d_img_sbs, num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr,
-                               nv ? nv->pitch_y : 0, nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0};
-        cut_frame_input(ct, pin, H, W, elem_sz, (stages & 0xff) >= 3, aln, bal);
-    }
-    TemporalHist hist_aligned;
-    if (aln.mode) { // from here on the call is the plain BGR reduced-resolution frame call on the aligned side-by-side frame
-        const PackInput pin = {Packing{0, 0, 0, 0}, nv != nullptr, d_img_sbs, num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr,
-                               nv ? nv->pitch_y : 0, nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0};
-        d_img_sbs = align_frame_input(aln, pin, hist && !nv ? hist->sbs : nullptr, H, W, elem_sz, hist_aligned.sbs);
-        if (hist && !nv) {
-            const u8 *prev = hist_aligned.sbs;
-            hist_aligned = *hist;
-            hist_aligned.sbs = prev;
-            hist = &hist_aligned;
-        }
-        num_cols_sbs = 2 * W;
-        nv = nullptr;
-    }
-    TemporalHist hist_balanced;
-    if (bal.mode) { // after the alignment; then it is the plain BGR reduced-resolution frame call on the balanced side-by-side frame
-        const PackInput pin = {Packing{0, 0, 0, 0}, nv != nullptr, d_img_sbs, num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr,
-                               nv ? nv->pitch_y : 0, nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0};
-        const bool sbs_hist = hist && !split_hist;
-        d_img_sbs = balance_frame_input(bal, pin, sbs_hist ? hist->sbs : nullptr, H, W, elem_sz, hist_balanced.sbs);
-        if (sbs_hist) {
-            const u8 *prev = hist_balanced.sbs;
-            hist_balanced = *hist;
-            hist_balanced.sbs = prev;
-            hist = &hist_balanced;
-        }
-        num_cols_sbs = 2 * W;
-        nv = nullptr;
-    }
+    const FrameInput in = frame_input(a, d_img_sbs, nv, hist); // on the full-resolution input
+    nv = in.nv;
     uint32_t *pre[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const bool fused = reduced_front_fused(num_cols_sbs, W); // both halves complete; 600: the chain of kernels
+    const bool fused = reduced_front_fused(in.num_cols_sbs, W); // both halves complete; 600: the chain of kernels
     {
         ProfScope p("reduced_front");
         if (fused) { // the split, both reductions, the reduced pair's pixel formats and census words in one launch
             for (int i = 0; i < 6; ++i) pre[i] = Workspace::get<uint32_t>(hw);
-            launch_front_low(img_l, img_r, low_l, low_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], nv ? nullptr : d_img_sbs, num_cols_sbs,
-                             nv ? nv->y : nullptr, nv ? nv->pitch_y : 0, nv ? nv->uv : nullptr, nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0, H, W,
-                             h, w, elem_sz);
+            launch_front_low(img_l, img_r, low_l, low_r, pre[0], pre[1], pre[2], pre[3], pre[4], pre[5], nv ? nullptr : in.d_img_sbs,
+                             in.num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->pitch_y : 0, nv ? nv->uv : nullptr, nv ? nv->pitch_uv : 0,
+                             nv ? nv->matrix : 0, H, W, h, w, elem_sz);
         } else {
-            reduced_front_chain(img_l, img_r, low_l, low_r, d_img_sbs, num_cols_sbs, nv, H, W, h, w, elem_sz);
+            reduced_front_chain(img_l, img_r, low_l, low_r, in.d_img_sbs, in.num_cols_sbs, nv, H, W, h, w, elem_sz);
         }
     }
     float *low_dl = Workspace::get<float>(hw), *low_dr = Workspace::get<float>(hw);
-    Arms al, ar;
-    frame_disparity(low_l, low_r, low_dl, low_dr, al, ar, h, w, elem_sz, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd,
-                    usd, lsd, thresh_s, thresh_h, true, hslo, fused ? pre : nullptr, subpix, interp);
-    const float up = 1.0f / disp_scale; // :415
-    if (guided) { // each map guided by its own view: the full-size image the views are rendered from against the image the match ran on
+    frame_disparity(low_l, low_r, low_dl, low_dr, h, w, a, true, fused ? pre : nullptr); // HSLO, sub-pixel, interpolation: on the reduced pair
+    const float up = 1.0f / a.disp_scale; // :415
+    if (a.stages & 0x1000) { // guided: each map by its own view, the full-size image the views are rendered from against the image the match ran on
         float *o[2] = {d_disp_l, d_disp_r};
         const float *dl[2] = {low_dl, low_dr};
         const u8 *il[2] = {low_l, low_r}, *im[2] = {img_l, img_r};
@@ -2444,35 +2358,18 @@ void reduced_frame_device(const char *fn, unsigned char *d_img_sbs, float *d_dis
         launch_disp_scale(d_disp_l, low_dl, H, W, h, w, up);
         launch_disp_scale(d_disp_r, low_dr, H, W, h, w, up);
     }
-    // temporal stabilisation (0x2000), as in frame_device: each view on its own half of the two side-by-side frames, read in place,
-    // or -- for an NV12 frame -- on the two frames' converted split images
-    if (hist) {
-        float *c[2] = {d_disp_l, d_disp_r};
-        const float *q[2] = {hist->disp_l, hist->disp_r};
-        const bool split = split_hist;
-        const u8 *im[2] = {split ? img_l : d_img_sbs, split ? img_r : d_img_sbs}, *ip[2] = {split ? hist->img_l : hist->sbs, split ? hist->img_r : hist->sbs};
-        const size_t off[2] = {0, split ? 0 : (size_t)W * elem_sz};
-        launch_disp_temporal(2, c, q, im, ip, off, H, W, split ? W : num_cols_sbs, elem_sz, hist->alpha, hist->thresh_color, hist->thresh_disp);
-    }
-    frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, H, W, num_rows_out, num_cols_out, elem_sz, N, angle, linwarp);
-    // the thread's overlay (stm_set_overlay), composited on the finished frame: the call's last launch
-    if (overlay().mode == 1) frame_overlay(d_interlaced, overlay(), lens(), layout(), N, angle, num_rows_out, num_cols_out, elem_sz);
+    if (hist) frame_temporal(a, in, *hist, img_l, img_r, d_disp_l, d_disp_r);
+    frame_tail(a, img_l, img_r, d_disp_l, d_disp_r, d_interlaced);
 }
 
-void reduced_frame_host(const char *fn, unsigned char *img_sbs, float *disp_l, float *disp_r, unsigned char *interlaced, int num_rows,
-                        int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int num_rows_disp, int num_cols_disp,
-                        int elem_sz, float disp_scale, int num_views, float angle, int num_disp, int zero_disp, float ad_coeff,
-                        float census_coeff, float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages)
+// the host flavour of the reference's three frame calls: the screens, before the caller's arrays are written; the arrays staged in
+// the thread's cached buffers (outside the workspace: the body re-carves it); the device body; the three arrays copied back
+void frame_host(const char *fn, const FrameArgs &a, bool reduced, const u8 *img_sbs, float *disp_l, float *disp_r, u8 *interlaced)
 {
-    if (!reduced_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp, num_cols_disp, elem_sz,
-                         num_views, num_disp, stages))
-        return;
-    if (!frame_layout_ok(fn, stages, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return; // before the caller's arrays are written
-    if (!frame_align_ok(fn, num_rows, num_cols_sbs, num_cols, true)) return;
-    if (!frame_balance_ok(fn, num_rows, num_cols_sbs, num_cols, true)) return;
-    if (!frame_cut_ok(fn, num_rows, num_cols)) return;
-    size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
-    size_t out_sz = frame_out_bytes(num_rows_out, num_cols_out, elem_sz); // stm_set_output: the NV12 surface
+    if (reduced ? !reduced_args_ok(fn, a) : !frame_dims_ok(fn, a) || packing_unsupported(fn)) return;
+    if (!frame_layout_ok(fn, a) || !frame_settings_ok(fn, a, nullptr)) return;
+    const size_t HW = (size_t)a.num_rows * a.num_cols, sbs_sz = (size_t)a.num_rows * a.num_cols_sbs * a.elem_sz;
+    const size_t out_sz = frame_out_bytes(a.num_rows_out, a.num_cols_out, a.elem_sz); // stm_set_output: the NV12 surface
     const size_t need[4] = {sbs_sz, out_sz, HW * 4, HW * 4};
     void *buf[4];
     if (!host_frame_bufs(need, buf)) return;
@@ -2480,16 +2377,91 @@ void reduced_frame_host(const char *fn, unsigned char *img_sbs, float *disp_l, f
     float *d_dl = (float *)buf[2], *d_dr = (float *)buf[3];
     STM_CHECK(hipMemcpyAsync(d_sbs, img_sbs, sbs_sz, hipMemcpyHostToDevice, stream()));
     STM_CHECK(hipMemsetAsync(d_out, 0, out_sz, stream()));
-    ApiNest nest; // the device flavour must not forget a failed upload
-    reduced_frame_device(fn, d_sbs, d_dl, d_dr, d_out, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp,
-                         num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd,
-                         usd, lsd, thresh_s, thresh_h, stages);
+    ApiNest nest; // the device body must not forget a failed upload
+    (reduced ? reduced_frame_device : frame_device)(fn, a, d_sbs, d_dl, d_dr, d_out, nullptr, nullptr);
     down(disp_l, d_dl, HW); down(disp_r, d_dr, HW); down(interlaced, d_out, out_sz);
     sync();
 }
 
+// the reference's frame parameters under the names every extern "C" frame entry gives them, in FrameArgs' order: the one place
+// where that order is written out
+#define STM_FRAME_PARAMS                                                                                                                  \
+    num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff, \
+        ucd, lcd, usd, lsd, thresh_s, thresh_h
+
 } // namespace
+
 extern "C" {
+
+// which aggregation kernels a frame call with these arguments runs (stm_hip.h); no launch, no device
+int stm_agg_path(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages)
+{
+    return frame_agg_path(num_disp, zero_disp, num_rows, num_cols, usd, stages);
+}
+// whether stm_k_pq_hc2 runs the first horizontal pass of such a call, as its parts per image row (stm_hip.h); no launch, no device
+int stm_first_pass_path(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages)
+{
+    return frame_first_pass_path(num_disp, zero_disp, num_rows, num_cols, usd, stages);
+}
+// the order of the hypotheses inside a pixel's record of such a call's PX volumes, or -1 off PX (stm_hip.h); no launch, no device
+int stm_px_order(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages)
+{
+    return frame_px_order(num_disp, zero_disp, num_rows, num_cols, usd, stages);
+}
+
+void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                        int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz,
+                        int num_views, float angle, int num_disp, int zero_disp, float ad_coeff, float census_coeff,
+                        float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages)
+{
+    const char *fn = "d_adcensus_stm";
+    const FrameArgs a = {STM_FRAME_PARAMS, stages};
+    if (!frame_dims_ok(fn, a) || !frame_packing_ok(fn, a)) return;
+    if (stages & 0x2000) { // temporal stabilisation needs the previous frame: this call has no arguments for it
+        fail("d_adcensus_stm: stages 0x2000 (temporal stabilisation) needs the history arguments of d_adcensus_stm_t", "stages", __FILE__,
+             __LINE__);
+        return;
+    }
+    frame_device(fn, a, d_img_sbs, d_disp_l, d_disp_r, d_interlaced, nullptr);
+}
+
+// stm_d_adcensus_stm with the history of the temporal stabilisation (stm_hip.h)
+void stm_d_adcensus_stm_t(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
+                          int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz,
+                          int num_views, float angle, int num_disp, int zero_disp, float ad_coeff, float census_coeff,
+                          float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages,
+                          unsigned char *d_prev_img_sbs, float *d_prev_disp_l, float *d_prev_disp_r, float alpha, int thresh_color,
+                          float thresh_disp)
+{
+    const char *fn = "d_adcensus_stm_t";
+    const FrameArgs a = {STM_FRAME_PARAMS, stages};
+    if (!frame_dims_ok(fn, a) || !frame_packing_ok(fn, a)) return;
+    const TemporalHist hist = {d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp};
+    bool run = false;
+    if (!frame_history_ok(fn, a, hist, d_disp_l, d_disp_r, nullptr, &run)) return;
+    frame_device(fn, a, d_img_sbs, d_disp_l, d_disp_r, d_interlaced, run ? &hist : nullptr);
+}
+
+// stm_d_adcensus_stm_t on an NV12 frame (stm_hip.h): the same body, the conversion fused into its first kernel
+void stm_d_adcensus_stm_nv12(unsigned char *d_y, int pitch_y, unsigned char *d_uv, int pitch_uv, int matrix, float *d_disp_l, float *d_disp_r,
+                             unsigned char *d_interlaced, int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
+                             int elem_sz, int num_views, float angle, int num_disp, int zero_disp, float ad_coeff, float census_coeff,
+                             float ucd, float lcd, int usd, int lsd, int thresh_s, float thresh_h, int stages,
+                             unsigned char *d_prev_img_l, unsigned char *d_prev_img_r, float *d_prev_disp_l, float *d_prev_disp_r, float alpha,
+                             int thresh_color, float thresh_disp, unsigned char *d_img_l, unsigned char *d_img_r)
+{
+    const char *fn = "d_adcensus_stm_nv12";
+    const FrameArgs a = {STM_FRAME_PARAMS, stages};
+    if (!frame_dims_ok(fn, a)) return;
+    if (packing().on()) { // a packed NV12 frame: the packing's own geometry rules in place of the side-by-side ones
+        if (!packing_args_ok(fn, packing(), num_rows, num_cols_sbs, num_cols, "num_cols", true, pitch_y, pitch_uv, matrix)) return;
+    } else if (!nv12_args_ok(fn, num_rows, num_cols_sbs, num_cols, "num_cols", pitch_y, pitch_uv, matrix)) return;
+    const Nv12Input nv = {d_y, d_uv, pitch_y, pitch_uv, matrix, d_img_l, d_img_r};
+    const TemporalHist hist = {nullptr, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp, d_prev_img_l, d_prev_img_r};
+    bool run = false;
+    if (!nv12_images_ok(fn, nv) || !frame_history_ok(fn, a, hist, d_disp_l, d_disp_r, &nv, &run)) return;
+    frame_device(fn, a, nullptr, d_disp_l, d_disp_r, d_interlaced, run ? &hist : nullptr, &nv);
+}
 
 void stm_d_adcensus_stm_2(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
                           int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
@@ -2497,9 +2469,8 @@ void stm_d_adcensus_stm_2(unsigned char *d_img_sbs, float *d_disp_l, float *d_di
                           int num_disp, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd,
                           int lsd, int thresh_s, float thresh_h)
 {
-    reduced_frame_device("d_adcensus_stm_2", d_img_sbs, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out,
-                         num_cols_out, num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp,
-                         ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, 3);
+    const FrameArgs a = {STM_FRAME_PARAMS, 3, num_rows_disp, num_cols_disp, disp_scale};
+    if (reduced_args_ok("d_adcensus_stm_2", a)) reduced_frame_device("d_adcensus_stm_2", a, d_img_sbs, d_disp_l, d_disp_r, d_interlaced, nullptr);
 }
 void stm_d_adcensus_stm_2s(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp_r, unsigned char *d_interlaced,
                            int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out,
@@ -2507,9 +2478,8 @@ void stm_d_adcensus_stm_2s(unsigned char *d_img_sbs, float *d_disp_l, float *d_d
                            int num_disp, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd,
                            int lsd, int thresh_s, float thresh_h, int stages)
 {
-    reduced_frame_device("d_adcensus_stm_2s", d_img_sbs, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out,
-                         num_cols_out, num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp,
-                         ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages);
+    const FrameArgs a = {STM_FRAME_PARAMS, stages, num_rows_disp, num_cols_disp, disp_scale};
+    if (reduced_args_ok("d_adcensus_stm_2s", a)) reduced_frame_device("d_adcensus_stm_2s", a, d_img_sbs, d_disp_l, d_disp_r, d_interlaced, nullptr);
 }
 
 // stm_d_adcensus_stm_2s with the history of the temporal stabilisation (stm_hip.h): stm_d_adcensus_stm_t's rules for bit 0x2000
@@ -2521,34 +2491,12 @@ void stm_d_adcensus_stm_2t(unsigned char *d_img_sbs, float *d_disp_l, float *d_d
                            float *d_prev_disp_r, float alpha, int thresh_color, float thresh_disp)
 {
     const char *fn = "d_adcensus_stm_2t";
-    if (!reduced_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp, num_cols_disp, elem_sz, num_views,
-                         num_disp, stages, true))
-        return;
-    TemporalHist hist = {d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp};
+    const FrameArgs a = {STM_FRAME_PARAMS, stages, num_rows_disp, num_cols_disp, disp_scale};
+    if (!reduced_args_ok(fn, a, true)) return;
+    const TemporalHist hist = {d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp};
     bool run = false;
-    if (stages & 0x2000) {
-        const int nset = (d_prev_img_sbs != nullptr) + (d_prev_disp_l != nullptr) + (d_prev_disp_r != nullptr);
-        const size_t HW = (size_t)num_rows * num_cols;
-        if (!temporal_params_ok(fn, alpha, thresh_color, thresh_disp)) return;
-        if (nset != 0 && nset != 3) {
-            fail("d_adcensus_stm_2t: the three history pointers must be all null (first frame) or all set",
-                 "d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
-            return;
-        }
-        if (nset == 3 && num_cols_sbs < 2 * num_cols) { // the views are read from the two halves in place
-            fail("d_adcensus_stm_2t: stages 0x2000 (temporal stabilisation) needs num_cols_sbs >= 2 * num_cols", "num_cols_sbs", __FILE__, __LINE__);
-            return;
-        }
-        if (nset == 3 && (maps_overlap(d_prev_disp_l, d_disp_l, HW) || maps_overlap(d_prev_disp_l, d_disp_r, HW) ||
-                          maps_overlap(d_prev_disp_r, d_disp_l, HW) || maps_overlap(d_prev_disp_r, d_disp_r, HW))) {
-            fail("d_adcensus_stm_2t: a history map must not alias d_disp_l or d_disp_r", "d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
-            return;
-        }
-        run = nset == 3;
-    }
-    reduced_frame_device(fn, d_img_sbs, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out,
-                         num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff,
-                         ucd, lcd, usd, lsd, thresh_s, thresh_h, stages & ~0x2000, run ? &hist : nullptr);
+    if (!frame_history_ok(fn, a, hist, d_disp_l, d_disp_r, nullptr, &run)) return;
+    reduced_frame_device(fn, a, d_img_sbs, d_disp_l, d_disp_r, d_interlaced, run ? &hist : nullptr);
 }
 
 // stm_d_adcensus_stm_2t on an NV12 frame (stm_hip.h): stm_d_adcensus_stm_nv12's rules, the conversion fused into the front kernel
@@ -2561,48 +2509,14 @@ void stm_d_adcensus_stm_2nv12(unsigned char *d_y, int pitch_y, unsigned char *d_
                               unsigned char *d_img_r)
 {
     const char *fn = "d_adcensus_stm_2nv12";
-    if (!reduced_args_ok(fn, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, num_rows_disp, num_cols_disp, elem_sz, num_views,
-                         num_disp, stages, true))
-        return;
+    const FrameArgs a = {STM_FRAME_PARAMS, stages, num_rows_disp, num_cols_disp, disp_scale};
+    if (!reduced_args_ok(fn, a, true)) return;
     if (!nv12_args_ok(fn, num_rows, num_cols_sbs, num_cols, "num_cols", pitch_y, pitch_uv, matrix)) return;
-    if ((d_img_l != nullptr) != (d_img_r != nullptr)) {
-        fail("d_adcensus_stm_2nv12: d_img_l and d_img_r must be both null (the split images stay in the workspace) or both set", "d_img_l, d_img_r",
-             __FILE__, __LINE__);
-        return;
-    }
-    TemporalHist hist = {nullptr, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp, d_prev_img_l, d_prev_img_r};
-    Nv12Input nv = {d_y, d_uv, pitch_y, pitch_uv, matrix, d_img_l, d_img_r};
+    const Nv12Input nv = {d_y, d_uv, pitch_y, pitch_uv, matrix, d_img_l, d_img_r};
+    const TemporalHist hist = {nullptr, d_prev_disp_l, d_prev_disp_r, alpha, thresh_color, thresh_disp, d_prev_img_l, d_prev_img_r};
     bool run = false;
-    if (stages & 0x2000) {
-        const int nset = (d_prev_img_l != nullptr) + (d_prev_img_r != nullptr) + (d_prev_disp_l != nullptr) + (d_prev_disp_r != nullptr);
-        const size_t HW = (size_t)num_rows * num_cols, IMG = HW * elem_sz;
-        if (!temporal_params_ok(fn, alpha, thresh_color, thresh_disp)) return;
-        if (!d_img_l) { // this frame's converted images are the next frame's history: the caller must keep them
-            fail("d_adcensus_stm_2nv12: stages 0x2000 (temporal stabilisation) needs the output images d_img_l and d_img_r", "d_img_l, d_img_r",
-                 __FILE__, __LINE__);
-            return;
-        }
-        if (nset != 0 && nset != 4) {
-            fail("d_adcensus_stm_2nv12: the four history pointers must be all null (first frame) or all set",
-                 "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
-            return;
-        }
-        if (nset == 4) { // the history is read while the outputs are written
-            const void *hp[4] = {d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r}, *o[4] = {d_img_l, d_img_r, d_disp_l, d_disp_r};
-            const size_t sz[4] = {IMG, IMG, HW * 4, HW * 4};
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 4; ++j)
-                    if (bytes_overlap(hp[i], sz[i], o[j], sz[j])) {
-                        fail("d_adcensus_stm_2nv12: a history buffer must not alias an output (d_img_l, d_img_r, d_disp_l, d_disp_r)",
-                             "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r", __FILE__, __LINE__);
-                        return;
-                    }
-        }
-        run = nset == 4;
-    }
-    reduced_frame_device(fn, nullptr, d_disp_l, d_disp_r, d_interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out,
-                         num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff,
-                         ucd, lcd, usd, lsd, thresh_s, thresh_h, stages & ~0x2000, run ? &hist : nullptr, &nv);
+    if (!nv12_images_ok(fn, nv) || !frame_history_ok(fn, a, hist, d_disp_l, d_disp_r, &nv, &run)) return;
+    reduced_frame_device(fn, a, nullptr, d_disp_l, d_disp_r, d_interlaced, run ? &hist : nullptr, &nv);
 }
 
 // the reduced-resolution frame's front as a stage (stm_hip.h): stm_k_front_low itself, the BGRX and wide planes in the workspace;
@@ -2730,9 +2644,8 @@ void stm_adcensus_stm_2(unsigned char *img_sbs, float *disp_l, float *disp_r, un
                         int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
                         int thresh_s, float thresh_h)
 {
-    reduced_frame_host("adcensus_stm_2", img_sbs, disp_l, disp_r, interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out,
-                       num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp, ad_coeff,
-                       census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, 3);
+    const FrameArgs a = {STM_FRAME_PARAMS, 3, num_rows_disp, num_cols_disp, disp_scale};
+    frame_host("adcensus_stm_2", a, true, img_sbs, disp_l, disp_r, interlaced);
 }
 void stm_adcensus_stm_2s(unsigned char *img_sbs, float *disp_l, float *disp_r, unsigned char *interlaced, int num_rows,
                          int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int num_rows_disp,
@@ -2740,9 +2653,8 @@ void stm_adcensus_stm_2s(unsigned char *img_sbs, float *disp_l, float *disp_r, u
                          int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd, int usd, int lsd,
                          int thresh_s, float thresh_h, int stages)
 {
-    reduced_frame_host("adcensus_stm_2s", img_sbs, disp_l, disp_r, interlaced, num_rows, num_cols_sbs, num_cols, num_rows_out,
-                       num_cols_out, num_rows_disp, num_cols_disp, elem_sz, disp_scale, num_views, angle, num_disp, zero_disp, ad_coeff,
-                       census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, stages);
+    const FrameArgs a = {STM_FRAME_PARAMS, stages, num_rows_disp, num_cols_disp, disp_scale};
+    frame_host("adcensus_stm_2s", a, true, img_sbs, disp_l, disp_r, interlaced);
 }
 
 // d_tx_scale.h:17-18  d_tx_scale (d_tx_scale.cu:83-121): despite the d_ prefix it takes HOST pointers
@@ -2773,30 +2685,8 @@ void stm_adcensus_stm(unsigned char *img_sbs, float *disp_l, float *disp_r, unsi
                       float angle, int num_disp, int zero_disp, float ad_coeff, float census_coeff, float ucd, float lcd,
                       int usd, int lsd, int thresh_s, float thresh_h)
 {
-    if (!args_ok("adcensus_stm", {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols", num_cols, 1},
-                                  {"num_rows_out", num_rows_out, 1}, {"num_cols_out", num_cols_out, 1},
-                                  {"elem_sz", elem_sz, 3}, {"num_views", num_views, 2}, {"num_disp", num_disp, 1}}))
-        return;
-    if (packing_unsupported("adcensus_stm")) return;
-    if (!frame_layout_ok("adcensus_stm", 3, num_views, num_rows, num_cols, num_rows_out, num_cols_out)) return; // before the caller's arrays are written
-    if (!frame_align_ok("adcensus_stm", num_rows, num_cols_sbs, num_cols, true)) return;
-    if (!frame_balance_ok("adcensus_stm", num_rows, num_cols_sbs, num_cols, true)) return;
-    if (!frame_cut_ok("adcensus_stm", num_rows, num_cols)) return;
-    size_t HW = (size_t)num_rows * num_cols, sbs_sz = (size_t)num_rows * num_cols_sbs * elem_sz;
-    size_t out_sz = frame_out_bytes(num_rows_out, num_cols_out, elem_sz); // stm_set_output: the NV12 surface
-    // own buffers are cached outside the workspace: the pipeline call below re-carves the workspace
-    const size_t need[4] = {sbs_sz, out_sz, HW * 4, HW * 4};
-    void *buf[4];
-    if (!host_frame_bufs(need, buf)) return;
-    u8 *d_sbs = (u8 *)buf[0], *d_out = (u8 *)buf[1];
-    float *d_dl = (float *)buf[2], *d_dr = (float *)buf[3];
-    STM_CHECK(hipMemcpyAsync(d_sbs, img_sbs, sbs_sz, hipMemcpyHostToDevice, stream()));
-    STM_CHECK(hipMemsetAsync(d_out, 0, out_sz, stream()));
-    ApiNest nest; // the device flavour must not forget a failed upload
-    stm_d_adcensus_stm(d_sbs, d_dl, d_dr, d_out, num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz,
-                       num_views, angle, num_disp, zero_disp, ad_coeff, census_coeff, ucd, lcd, usd, lsd, thresh_s, thresh_h, 3);
-    down(disp_l, d_dl, HW); down(disp_r, d_dr, HW); down(interlaced, d_out, out_sz);
-    sync();
+    const FrameArgs a = {STM_FRAME_PARAMS, 3};
+    frame_host("adcensus_stm", a, false, img_sbs, disp_l, disp_r, interlaced);
 }
 
 } // extern "C"
