@@ -358,6 +358,21 @@ int         stm_set_overlay(int mode, const unsigned char *d_overlay, int ov_row
 /* out[0 .. 4] = the calling thread's mode, ov_rows, ov_cols, x0 and y0, *disparity its disparity, as the last accepted
  * stm_set_overlay left them ((0, 0, 0, 0, 0) and 0 if none was made, and after mode 0).  A frame stream's overlay is never visible here. */
 void        stm_get_overlay(int out[5], float *disparity);
+/* The calling thread's automatic overlay placement (an addition; stm_overlay_fit has the definition).  A setting of its own, not a
+ * mode of stm_set_overlay: mode 0 (the default) changes nothing anywhere.  While mode 1 is on AND the thread's overlay is on, every
+ * rendering frame call, after its renderer, runs stm_d_overlay_fit on the maps the renderer read -- with the thread's overlay, the
+ * view of the thread's layout (the output frame, or one tile of a quilt), the depth budget in force ((1, 0) in depth mode 0, the
+ * setting in mode 1, the state the same frame's fit left in mode 2, read on the device), restart = 0 and, where stm_set_cut is on,
+ * its state -- and then composites as stm_d_mux_overlay would at fminf(fmaxf(state[1], limit_lo), limit_hi) (a NaN: limit_lo), read
+ * on the device: nothing is read back, the frame is byte for byte stm_d_mux_overlay's at that disparity.  stm_set_overlay's own
+ * disparity is ignored but still screened.  d_state = four floats in device memory {valid, disparity, nearest, 0} the caller owns,
+ * zeroes once and keeps alive while the setting is on, or null: four zeroed floats of the workspace, every frame fitted on its own.
+ * Mode 0 ignores the other arguments and restores the defaults.  Argument rules as stm_overlay_fit's; a refused call leaves the
+ * setting as it was.  Return 0, or -1 with stm_last_error set.  stm_get_overlay_auto: out_mode = {mode, near_permille, pad},
+ * out = {margin, limit_lo, limit_hi, rate_near, rate_far}. */
+int         stm_set_overlay_auto(int mode, int near_permille, float margin, int pad, float limit_lo, float limit_hi, float rate_near,
+                                 float rate_far, float *d_state);
+void        stm_get_overlay_auto(int out_mode[3], float out[5]);
 /* (tests, tools) the bytes of LDS a workgroup of the area filter's staged kernel may take: the block of output pixels it owns is sized
  * so that its footprint's staging fits, and where not even one output pixel's does the per-pixel form runs -- same arithmetic, same
  * bytes.  <= 0: the default, 32768 (five workgroups on a CU); at most 65536.  Process-wide, like stm_set_agg_variant. */
@@ -1067,6 +1082,44 @@ void stm_depth_fit(float *disp_l, float *disp_r, int num_rows, int num_cols, flo
                    int clip_permille, float rate, float *state);
 void stm_d_depth_fit(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
                      int clip_permille, float rate, float *d_state);
+/* The measurement behind the overlay's automatic depth placement (an addition; see stm_mux_overlay for what an overlay's disparity
+ * does and stm_set_overlay_auto for the frame calls' use of it).  Inputs: the two maps of a frame (f32, num_rows x num_cols = H x W,
+ * delta = x_right - x_left, read only); an overlay (ov_rows x ov_cols pixels B, G, R, A premultiplied, read only) at (x0, y0) in view
+ * pixel space view_rows x view_cols = Hv x Wv (layout 0: the output frame; a quilt: one tile); the depth budget (gain, conv) = (g, c)
+ * the frame is rendered with ((1, 0) without one); a state of four floats {valid, disparity, nearest, 0}.
+ * 1. Alpha box.  r0 .. r1 and q0 .. q1 (inclusive) are the least and greatest overlay row and column holding a pixel with A != 0;
+ *    none: n = 0.  (A mostly transparent full-width strip is not placed by what lies under its empty ends.)
+ * 2. Footprint.  View rows [y0 + r0 - pad, y0 + r1 + 1 + pad) and columns [x0 + q0 - pad, x0 + q1 + 1 + pad), clipped to
+ *    [0, Hv) x [0, Wv) = [ya, yb) x [xa, xb); in map pixels, 64-bit integers: rows [ya*H div Hv, (yb*H + Hv - 1) div Hv), columns
+ *    [xa*W div Wv, (xb*W + Wv - 1) div Wv).  Empty: n = 0.  pad (view pixels) is the caller's allowance for the overlay's own
+ *    parallax shift, the scene's warp between a map and a view, and breathing room; nothing else widens the footprint.
+ * 3. Histogram.  Every pixel of BOTH maps inside the map rectangle into 4096 quarter-pixel bins by stm_depth_fit's line
+ *      b = (int)floorf(fminf(fmaxf(4*disp, -2048), 2047) + 0.5f) + 2048
+ *    except that a NaN is not counted (a NaN under a subtitle must not pull it to the near limit).  n = the pixels counted (u32).
+ * 4. Nearest.  k = (u64)n * near_permille / 1000; lo = the first bin whose prefix count exceeds k; dp = (lo - 2048) * 0.25.
+ *    (g >= 0, so the percentile commutes with the budget's map.)
+ * 5. Target, in double, one operation per line, no contraction, correctly rounded division:
+ *      e = g*dp;  e = e - c;  e = e * (double)Wv;  e = e / (double)W;  t = e - margin;  t = min(max(t, limit_lo), limit_hi)
+ * 6. State.  n == 0: none of the four floats is written.  Otherwise the fit has no history when valid == 0, restart != 0, or a cut
+ *    state is given (the 260 ints of stm_cut_detect) and its word 1, this frame's cut flag, is 1: then d = t.  With history:
+ *      r = (t < d_old) ? rate_near : rate_far;  u = t - d_old;  u = r*u;  d = d_old + u;  d = min(max(d, limit_lo), limit_hi)
+ *    and state = {1, (float)d, (float)e, 0}.  Two rates: a scene that comes nearer must be followed at once (rate_near is typically
+ *    1) or the text collides with it; one that recedes is followed slowly, so that the text does not pump.  min and max are C's
+ *    fmin and fmax: a NaN in the old state becomes limit_lo.
+ * Smaller disparities are nearer (delta = x_right - x_left), so the near percentile is the low one and `nearest` is the displayed
+ * disparity of the nearest scene content under the overlay, in view pixels.
+ * The device flavour reads and writes d_state in device memory, reads d_cut_state (may be null) on the device and synchronises
+ * nothing; the host flavour takes and returns the four floats in host memory.  Argument rules, violations fail through
+ * stm_last_error before anything is launched or written: num_rows, num_cols, view_rows, view_cols >= 1 and num_rows * num_cols below
+ * 2^31; the overlay's own as stm_mux_overlay's (the device flavour's pointer 4-byte aligned); gain in [0, 8] and |conv| <= 4096 as
+ * stm_set_depth's; near_permille 0 .. 499; margin finite with |margin| <= 4096; pad 0 .. 4096; limit_lo <= limit_hi, both finite
+ * with magnitude <= 4096; both rates in (0, 1].  Parity is against a numpy statement of these lines (parity unpinned). */
+void stm_overlay_fit(float *disp_l, float *disp_r, int num_rows, int num_cols, const unsigned char *overlay, int ov_rows, int ov_cols, int x0,
+                     int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin, int pad, float limit_lo,
+                     float limit_hi, float rate_near, float rate_far, int restart, float *state);
+void stm_d_overlay_fit(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, const unsigned char *d_overlay, int ov_rows, int ov_cols,
+                       int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin, int pad,
+                       float limit_lo, float limit_hi, float rate_near, float rate_far, int restart, float *d_state, const int *d_cut_state);
 /* Vertical alignment as stages (an addition, see stm_set_align).  H = num_rows, W = num_cols of one unpacked eye.
  * stm_align_rows applies a field to one image (H x W x elem_sz, B G R first): out(y, x) = img sampled at row y + dy(x, y).
  * Per pixel -- f32, one operation per line, no contraction; then exact integers:
@@ -1292,6 +1345,18 @@ int   stm_stream_set_output(void *stream, int format, int matrix);
  * without stm_stream_set_overlay.  Return 0, or -1 with stm_last_error set. */
 int   stm_stream_set_overlay(void *stream, int max_rows, int max_cols);
 int   stm_stream_overlay(void *stream, const unsigned char *overlay, int ov_rows, int ov_cols, int x0, int y0, float disparity);
+/* the automatic placement of the stream's overlay (stm_set_overlay_auto's definition and rules, under the stream's own lens, layout,
+ * depth budget and cut detector).  Accepted only before the first submit and after stm_stream_set_overlay (switching that off
+ * switches this off too).  The state is the stream's own, 16 bytes at a fixed address zeroed when it is allocated; the fit and the
+ * compositor are launched behind the slot's captured graph, where the overlay is composited, so their arguments change from submit
+ * to submit.  Frame k reads the state frame k - 1 left (its compute waits for the other slot's frame, as depth mode 2 arranges
+ * it).  A submit whose overlay comes from another stm_stream_overlay call than the previously fitted frame's passes restart = 1: a
+ * new subtitle has no continuity to keep.  stm_stream_overlay's disparity is then ignored.
+ * stm_stream_overlay_depth reports the four floats as the most recently collected frame left them (with the placement off:
+ * {0, the disparity that frame was submitted under, 0, 0}); -1 before the first collect.  Return 0, or -1 with stm_last_error set. */
+int   stm_stream_set_overlay_auto(void *stream, int mode, int near_permille, float margin, int pad, float limit_lo, float limit_hi,
+                                  float rate_near, float rate_far);
+int   stm_stream_overlay_depth(void *stream, float out[4]);
 /* the depth budget of the stream's frames (stm_set_depth's rules; the default is mode 0).  As with the lens geometry the stream keeps
  * its own copy and installs it only around its frame calls.  stm_stream_set_depth_auto sets mode 2's parameters (stm_set_depth_auto's
  * rules; call it before stm_stream_set_depth(stream, 2, 0, 0)); the state is the stream's own: one buffer at a fixed address, zeroed

@@ -46,6 +46,8 @@ PROTOS = {
     "stm_get_output": ([C.POINTER(C.c_int)], None),
     "stm_set_overlay": ([i, vp, i, i, i, i, f], i),
     "stm_get_overlay": ([C.POINTER(C.c_int), f32p], None),
+    "stm_set_overlay_auto": ([i, i, f, i, f, f, f, f, vp], i),
+    "stm_get_overlay_auto": ([C.POINTER(C.c_int), f32p], None),
     "stm_set_quilt_lds_limit": ([i], None),
     "stm_set_packing": ([i, i, i, i], i),
     "stm_get_packing": ([C.POINTER(C.c_int)], None),
@@ -135,6 +137,8 @@ PROTOS = {
     "stm_d_disp_temporal": ([vp, vp, vp, vp, i, i, i, f, i, f], None),
     "stm_depth_fit": ([f32p, f32p, i, i, f, f, f, i, f, f32p], None),
     "stm_d_depth_fit": ([vp, vp, i, i, f, f, f, i, f, vp], None),
+    "stm_overlay_fit": ([f32p, f32p, i, i, u8p, i, i, i, i, i, i, f, f, i, f, i, f, f, f, f, i, f32p], None),
+    "stm_d_overlay_fit": ([vp, vp, i, i, vp, i, i, i, i, i, i, f, f, i, f, i, f, f, f, f, i, vp, vp], None),
     "stm_align_rows": ([u8p, u8p, i, i, i, f, f, f], None),
     "stm_d_align_rows": ([vp, vp, i, i, i, f, f, f], None),
     "stm_align_fit": ([u8p, u8p, i, i, i, i, f, f32p], i),
@@ -160,6 +164,8 @@ PROTOS = {
     "stm_stream_set_output": ([C.c_void_p, i, i], i),
     "stm_stream_set_overlay": ([C.c_void_p, i, i], i),
     "stm_stream_overlay": ([C.c_void_p, u8p, i, i, i, i, f], i),
+    "stm_stream_set_overlay_auto": ([C.c_void_p, i, i, f, i, f, f, f, f], i),
+    "stm_stream_overlay_depth": ([C.c_void_p, f32p], i),
     "stm_stream_set_depth": ([C.c_void_p, i, f, f], i),
     "stm_stream_set_depth_auto": ([C.c_void_p, f, f, f, i, f], i),
     "stm_stream_set_antialias": ([C.c_void_p, i, f, i, f], i),

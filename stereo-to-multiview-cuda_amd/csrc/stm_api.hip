@@ -363,7 +363,26 @@ void stm::frame_overlay(u8 *d_frame, const Overlay &ov, const Lens &ln, const La
     int ymod = 1;
     if (lo.layout == 0 && ln.mode == 0 && !mux_geom_ok(num_views, angle, elem_sz, &yi, &inv_y, &ymod)) return;
     launch_overlay(d_frame, ov.d_overlay, ov.ov_rows, ov.ov_cols, ov.x0, ov.y0, ov.disparity, num_views, ln, yi, inv_y, ymod, lo, Hout, Wout,
-                   elem_sz);
+                   elem_sz, ov.d_disp, ov.limit_lo, ov.limit_hi);
+}
+
+// the overlay's fit on the maps the renderer read (stm_set_overlay_auto), then the overlay composited at the state's disparity: the
+// setter's own disparity is ignored.  The view is the output frame in layout 0 and one tile of a quilt; the budget is (1, 0) in depth
+// mode 0, the setting in mode 1 and depth_state's in mode 2.  The geometry is screened first: a frame the compositor would refuse is
+// not measured either
+void stm::frame_overlay_auto(u8 *d_frame, const Overlay &ov, const OverlayAuto &oa, float *state, uint32_t *ws, bool fresh, bool zero_state, const float *d_disp_l,
+                             const float *d_disp_r, int H, int W, const Depth &dp, const float *depth_state, const int *cut_state, const Lens &ln,
+                             const Layout &lo, int num_views, float angle, int Hout, int Wout, int elem_sz)
+{
+    if (lo.layout == 0 && ln.mode == 0 && !mux_geom_ok(num_views, angle, elem_sz, nullptr, nullptr, nullptr)) return;
+    const int Hv = lo.layout == 1 ? Hout / lo.tiles_y : Hout, Wv = lo.layout == 1 ? Wout / lo.tiles_x : Wout;
+    launch_overlay_fit(state, ws, d_disp_l, d_disp_r, H, W, ov.d_overlay, ov.ov_rows, ov.ov_cols, ov.x0, ov.y0, Hv, Wv, dp.mode == 1 ? dp.gain : 1.0f,
+                       dp.mode == 1 ? dp.conv : 0.0f, dp.mode == 2 ? depth_state : nullptr, oa, fresh, zero_state, cut_state);
+    Overlay at = ov;
+    at.d_disp = state + 1;
+    at.limit_lo = oa.limit_lo;
+    at.limit_hi = oa.limit_hi;
+    frame_overlay(d_frame, at, ln, lo, num_views, angle, Hout, Wout, elem_sz);
 }
 
 // the rules of an NV12 frame (stm_hip.h, stm_demux_nv12), after the dimension screen; cols_name: what the call names the width of a view
@@ -967,6 +986,55 @@ void stm_depth_fit(float *disp_l, float *disp_r, int num_rows, int num_cols, flo
     float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *st = up(state, 4);
     uint32_t *hist = Workspace::get<uint32_t>(4096);
     launch_depth_fit(st, hist, dl, dr, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, false);
+    down(state, st, 4);
+    sync();
+}
+
+// =============================================================== overlay placement: the measurement as a stage
+// (an addition, the reference has no overlay)
+static bool overlay_fit_args_ok(const char *fn, const unsigned char *overlay, bool words, int num_rows, int num_cols, int ov_rows, int ov_cols,
+                                int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin, int pad,
+                                float limit_lo, float limit_hi, float rate_near, float rate_far)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"view_rows", view_rows, 1}, {"view_cols", view_cols, 1}})) return false;
+    if (!overlay_fit_size_ok(fn, num_rows, num_cols)) return false;
+    if (!overlay_params_ok(fn, overlay, words, ov_rows, ov_cols, x0, y0, 0.0f)) return false;
+    if (!overlay) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "%s: the overlay is null", fn);
+        fail(msg, "overlay", __FILE__, __LINE__);
+        return false;
+    }
+    return depth_params_ok(fn, 1, gain, conv) && overlay_auto_params_ok(fn, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far);
+}
+void stm_d_overlay_fit(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, const unsigned char *d_overlay, int ov_rows, int ov_cols,
+                       int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin, int pad,
+                       float limit_lo, float limit_hi, float rate_near, float rate_far, int restart, float *d_state, const int *d_cut_state)
+{
+    if (!overlay_fit_args_ok("d_overlay_fit", d_overlay, true, num_rows, num_cols, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv,
+                             near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far))
+        return;
+    Workspace::begin(OVERLAY_FIT_WS_WORDS * 4 + 8192);
+    uint32_t *ws = Workspace::get<uint32_t>(OVERLAY_FIT_WS_WORDS);
+    const OverlayAuto oa = {1, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, d_state};
+    launch_overlay_fit(d_state, ws, d_disp_l, d_disp_r, num_rows, num_cols, d_overlay, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv,
+                       nullptr, oa, restart != 0, false, d_cut_state);
+}
+void stm_overlay_fit(float *disp_l, float *disp_r, int num_rows, int num_cols, const unsigned char *overlay, int ov_rows, int ov_cols, int x0,
+                     int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin, int pad, float limit_lo,
+                     float limit_hi, float rate_near, float rate_far, int restart, float *state)
+{
+    if (!overlay_fit_args_ok("overlay_fit", overlay, false, num_rows, num_cols, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv,
+                             near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far))
+        return;
+    const size_t HW = (size_t)num_rows * num_cols, ov_sz = (size_t)ov_rows * ov_cols * 4;
+    Workspace::begin(8 * HW + ov_sz + OVERLAY_FIT_WS_WORDS * 4 + 8192);
+    float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *st = up(state, 4);
+    const u8 *o = up((unsigned char *)overlay, ov_sz);
+    uint32_t *ws = Workspace::get<uint32_t>(OVERLAY_FIT_WS_WORDS);
+    const OverlayAuto oa = {1, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, st};
+    launch_overlay_fit(st, ws, dl, dr, num_rows, num_cols, o, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv, nullptr, oa, restart != 0,
+                       false, nullptr);
     down(state, st, 4);
     sync();
 }
@@ -1786,6 +1854,7 @@ bool frame_layout_ok(const char *fn, const FrameArgs &a)
             return false;
         }
         if (!overlay_tiles_ok(fn, lo, num_views)) return false;
+        if (overlay_auto().mode == 1 && !overlay_fit_size_ok(fn, a.num_rows, a.num_cols)) return false;
     }
     if (lo.layout == 0) return frame_output_ok(fn, lo, Hout, Wout);
     if (lens().mode != 0) {
@@ -1799,8 +1868,10 @@ bool frame_layout_ok(const char *fn, const FrameArgs &a)
 }
 
 // hit maps -> bleed -> masks -> N-2 views -> interlace (d_io.cu:160-205)
-void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_interlaced, const FrameArgs &a)
+// depth_state_out: where depth mode 2's state lies, the workspace's four floats included (null in the other modes)
+void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_interlaced, const FrameArgs &a, float **depth_state_out)
 {
+    *depth_state_out = nullptr;
     const int H = a.num_rows, W = a.num_cols, Hout = a.num_rows_out, Wout = a.num_cols_out, elem_sz = a.elem_sz, N = a.num_views;
     const float angle = a.angle;
     const bool linear = (a.stages & 0x800) != 0; // the views' warps fetched at the fractional coordinate (stm_dibr_dbm_lin)
@@ -1833,6 +1904,7 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
         state = dp.d_state ? dp.d_state : Workspace::get<float>(4);
         launch_depth_fit(state, hist, d_disp_l, d_disp_r, H, W, dp.disp_lo, dp.disp_hi, dp.max_gain, dp.clip_permille, dp.rate,
                          dp.d_state == nullptr);
+        *depth_state_out = state;
     }
     // view antialiasing (stm_set_antialias): both images filtered by their own maps into fresh workspace, and every renderer below
     // takes the filtered pair -- the caller's images (0x2000's history, _nv12's outputs) and the maps stay as they are.  The displayed
@@ -2044,7 +2116,8 @@ size_t frame_settings_ws_bytes(const FrameArgs &a, bool prev)
            (antialias().mode == 1 ? 2 * IMG + 512 : 0) +                                       // the prefiltered pair
            (align().mode ? align_ws_bytes(a.num_rows, IMG, prev) : 0) +                        // the aligned frame(s)
            (balance().mode ? balance_ws_bytes(IMG, prev) : 0) +                                // the balanced frame(s)
-           (cut().mode ? cut_ws_bytes() : 0);                                                  // the detector's signature
+           (cut().mode ? cut_ws_bytes() : 0) +                                                 // the detector's signature
+           (overlay().mode == 1 && overlay_auto().mode == 1 ? OVERLAY_FIT_WS_WORDS * 4 + 16 + 1024 : 0); // the overlay fit's bins, box and scratch state
 }
 // what the front and the temporal step of a frame body read, after the prelude
 struct FrameInput {
@@ -2115,12 +2188,24 @@ void frame_temporal(const FrameArgs &a, const FrameInput &in, const TemporalHist
 }
 
 // the tail of a rendering frame call: the renderer, then the thread's overlay (stm_set_overlay) composited on the finished frame --
-// the call's last launch
+// the call's last launch.  With stm_set_overlay_auto on, the overlay's disparity is first fitted to the maps the renderer read, under
+// the depth budget it rendered with and the thread's cut state, and the compositor reads it from the state on the device
 void frame_tail(const FrameArgs &a, u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_interlaced)
 {
-    frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, a);
-    if (overlay().mode == 1)
+    float *depth_state = nullptr;
+    frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, a, &depth_state);
+    if (overlay().mode != 1) return;
+    const OverlayAuto oa = overlay_auto();
+    if (oa.mode != 1) {
         frame_overlay(d_interlaced, overlay(), lens(), layout(), a.num_views, a.angle, a.num_rows_out, a.num_cols_out, a.elem_sz);
+        return;
+    }
+    uint32_t *ws = Workspace::get<uint32_t>(OVERLAY_FIT_WS_WORDS);
+    float *state = oa.d_state ? oa.d_state : Workspace::get<float>(4); // scratch: zeroed, every frame on its own
+    const Cut ct = cut();
+    frame_overlay_auto(d_interlaced, overlay(), oa, state, ws, oa.d_state == nullptr, oa.d_state == nullptr, d_disp_l, d_disp_r, a.num_rows,
+                       a.num_cols, depth(), depth_state, ct.mode ? ct.d_state : nullptr, lens(), layout(), a.num_views, a.angle, a.num_rows_out,
+                       a.num_cols_out, a.elem_sz);
 }
 
 // the body of stm_d_adcensus_stm, stm_d_adcensus_stm_t and stm_d_adcensus_stm_nv12; hist != nullptr: the temporal step between

@@ -365,6 +365,9 @@ struct Overlay {
     const u8 *d_overlay;
     int ov_rows, ov_cols, x0, y0;
     float disparity;
+    // the disparity read on the device instead (stm_set_overlay_auto): fminf(fmaxf(*d_disp, limit_lo), limit_hi); null = `disparity`
+    const float *d_disp = nullptr;
+    float limit_lo = 0.0f, limit_hi = 0.0f;
 };
 Overlay overlay();
 void set_overlay(const Overlay &o);
@@ -376,8 +379,43 @@ void frame_overlay(u8 *d_frame, const Overlay &ov, const Lens &ln, const Layout 
                    int elem_sz);
 // the compositor (stm_kernels_overlay.hip): `ov` in place on the finished frame `out` (Hout x Wout x elem_sz); lo.layout 0: interlaced
 // under ln (ln.mode 0: the reference's view assignment from y_interval, inv_y_interval and ymod), 1: a quilt.  Screened by the caller
+// d_disp != nullptr: the disparity is *d_disp clamped to [limit_lo, limit_hi] on the device (a NaN goes to limit_lo) and the bounding
+// box is sized from the limits; the columns that adds sample (0, 0, 0, 0) and leave the frame as it is
 void launch_overlay(u8 *out, const u8 *ov, int ov_rows, int ov_cols, int x0, int y0, float disparity, int N, const Lens &ln,
-                    float y_interval, float inv_y_interval, int ymod, const Layout &lo, int Hout, int Wout, int elem_sz);
+                    float y_interval, float inv_y_interval, int ymod, const Layout &lo, int Hout, int Wout, int elem_sz,
+                    const float *d_disp = nullptr, float limit_lo = 0.0f, float limit_hi = 0.0f);
+// The overlay's automatic depth placement (stm_set_overlay_auto, include/stm_hip.h): mode 0 = off (not one launch changes), 1 = every
+// rendering frame call with the thread's overlay on fits the overlay's disparity to the maps under it on the device and composites
+// with the state's disparity.  One per host thread, next to the overlay; a frame stream keeps its own and never installs it here.
+struct OverlayAuto {
+    int mode;
+    int near_permille;
+    float margin;
+    int pad;
+    float limit_lo, limit_hi, rate_near, rate_far;
+    float *d_state; // {valid, disparity, nearest, 0} in device memory; null = scratch, every frame on its own
+};
+OverlayAuto overlay_auto_default();
+OverlayAuto overlay_auto();
+void set_overlay_auto(const OverlayAuto &a);
+// the argument rules of the seven parameters; false with the error recorded
+bool overlay_auto_params_ok(const char *fn, int near_permille, float margin, int pad, float limit_lo, float limit_hi, float rate_near,
+                            float rate_far);
+// the fit's frame rule: num_rows * num_cols < 2^31 (n <= 2 H W is counted in 32 bits); false with the error recorded
+bool overlay_fit_size_ok(const char *fn, int num_rows, int num_cols);
+constexpr size_t OVERLAY_FIT_WS_WORDS = 4096 + 4; // the histogram, then the alpha box
+// the measurement (stm_kernels_ovfit.hip): the alpha box of `ov`, both maps (H x W) under its footprint in the view Hv x Wv into the
+// histogram, the fit and the update of `state` (four floats).  The budget is (gain, conv), or depth_state[1], depth_state[2] read on
+// the device where depth_state != nullptr; fresh: the state's history is ignored; zero_state: `state` is scratch, zeroed first;
+// cut_state: the detector's state or null
+void launch_overlay_fit(float *state, uint32_t *ws, const float *disp_l, const float *disp_r, int H, int W, const u8 *ov, int ov_rows,
+                        int ov_cols, int x0, int y0, int Hv, int Wv, float gain, float conv, const float *depth_state, const OverlayAuto &oa,
+                        bool fresh, bool zero_state, const int *cut_state);
+// stm_api.hip: the fit of the overlay `ov` on a frame's maps under layout lo, then the overlay composited at the state's disparity;
+// state: oa.d_state, or four floats of scratch (zero_state).  The frame calls' tail with the thread's settings, and a frame stream's with its own
+void frame_overlay_auto(u8 *d_frame, const Overlay &ov, const OverlayAuto &oa, float *state, uint32_t *ws, bool fresh, bool zero_state, const float *d_disp_l,
+                        const float *d_disp_r, int H, int W, const Depth &dp, const float *depth_state, const int *cut_state, const Lens &ln,
+                        const Layout &lo, int num_views, float angle, int Hout, int Wout, int elem_sz);
 // View antialiasing (stm_set_antialias, include/stm_hip.h): mode 0 = off, 1 = every rendering frame call filters both images by
 // their own maps (stm_view_prefilter's rule) before it renders from them.  One per host thread, next to the depth budget; a frame
 // stream installs its own copy around its frame calls (stm_stream_set_antialias).

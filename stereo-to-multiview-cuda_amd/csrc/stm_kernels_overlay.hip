@@ -29,6 +29,8 @@ struct OverlayArgs {
     const uint32_t *ov;   // ov_rows x ov_cols pixels B, G, R, A, premultiplied
     int ov_rows, ov_cols, x0, y0;
     float disparity;
+    const float *d_disp;       // the disparity read on the device instead, clamped to [limit_lo, limit_hi] (stm_set_overlay_auto); null = `disparity`
+    float limit_lo, limit_hi;
     int N, Wout, elem_sz;
     int bx0, bx1, by0, by1; // the bounding box in view pixel space (non-empty)
     float y_interval;       // OV_MUX
@@ -42,10 +44,10 @@ struct OverlayArgs {
 struct OvTap {
     uint32_t p0, p1, fr;
 };
-__device__ __forceinline__ OvTap overlay_tap(const OverlayArgs &a, const uint32_t *__restrict__ row, int x, float s)
+__device__ __forceinline__ OvTap overlay_tap(const OverlayArgs &a, float disparity, const uint32_t *__restrict__ row, int x, float s)
 {
     const double t = (double)s - 0.5;
-    const double o = (double)a.disparity * t;
+    const double o = (double)disparity * t;
     double p = (double)((long long)x - (long long)a.x0) - o;
     p = p * 256.0;
     const long long F = (long long)floor(p);
@@ -65,12 +67,12 @@ __device__ __forceinline__ uint32_t overlay_blend(const OvTap &t, int c, uint32_
 }
 // the three bytes of view pixel (x, y) -- output pixel (ox, oy) -- composited: px = B | G << 8 | R << 16 in, the same out
 template <int MODE>
-__device__ __forceinline__ uint32_t overlay_pixel(const OverlayArgs &a, const uint32_t *__restrict__ row, int x, int ox, int oy, float s_tile,
-                                                  uint32_t px)
+__device__ __forceinline__ uint32_t overlay_pixel(const OverlayArgs &a, float disparity, const uint32_t *__restrict__ row, int x, int ox, int oy,
+                                                  float s_tile, uint32_t px)
 {
     uint32_t r = 0;
     if constexpr (MODE == OV_QUILT) { // one view per tile: the three bytes share the tap
-        const OvTap t = overlay_tap(a, row, x, s_tile);
+        const OvTap t = overlay_tap(a, disparity, row, x, s_tile);
 #pragma unroll
         for (int c = 0; c < 3; ++c) r |= overlay_blend(t, c, (px >> (8 * c)) & 255u) << (8 * c);
     } else {
@@ -89,7 +91,7 @@ __device__ __forceinline__ uint32_t overlay_pixel(const OverlayArgs &a, const ui
                 lens_pick<MODE>(lens_phase(ox, oy, c, a.g), a.N, v, w, shift);
                 s = MODE == OV_LENS_VIEW ? view_shift(v, a.N) : shift;
             }
-            const OvTap t = overlay_tap(a, row, x, s);
+            const OvTap t = overlay_tap(a, disparity, row, x, s);
             r |= overlay_blend(t, c, (px >> (8 * c)) & 255u) << (8 * c);
         }
     }
@@ -113,15 +115,17 @@ __global__ __launch_bounds__(OV_BX * OV_BY) void stm_k_overlay(OverlayArgs a)
     const int ox0 = (lo & ~(OV_RUN - 1)) + ((int)blockIdx.x * OV_BX + (int)threadIdx.x) * OV_RUN;
     if (ox0 >= hi) return;
     const uint32_t *__restrict__ row = a.ov + (size_t)(y - a.y0) * a.ov_cols;
+    // one pointer test: the fitted disparity of this frame, written earlier on the same stream (C fmaxf: a NaN becomes limit_lo)
+    const float disparity = a.d_disp ? fminf(fmaxf(*a.d_disp, a.limit_lo), a.limit_hi) : a.disparity;
     u8 *p = a.out + ((size_t)oy * a.Wout + ox0) * a.elem_sz;
     const bool whole = ox0 >= lo && ox0 + OV_RUN <= hi && ((uintptr_t)p & 3) == 0;
     if (whole && a.elem_sz == 3) {
         uint32_t *d = (uint32_t *)p;
         const uint32_t w0 = d[0], w1 = d[1], w2 = d[2];
-        const uint32_t r0 = overlay_pixel<MODE>(a, row, ox0 - left, ox0, oy, s_tile, w0 & 0xffffffu);
-        const uint32_t r1 = overlay_pixel<MODE>(a, row, ox0 + 1 - left, ox0 + 1, oy, s_tile, (w0 >> 24) | ((w1 & 0xffffu) << 8));
-        const uint32_t r2 = overlay_pixel<MODE>(a, row, ox0 + 2 - left, ox0 + 2, oy, s_tile, (w1 >> 16) | ((w2 & 0xffu) << 16));
-        const uint32_t r3 = overlay_pixel<MODE>(a, row, ox0 + 3 - left, ox0 + 3, oy, s_tile, w2 >> 8);
+        const uint32_t r0 = overlay_pixel<MODE>(a, disparity, row, ox0 - left, ox0, oy, s_tile, w0 & 0xffffffu);
+        const uint32_t r1 = overlay_pixel<MODE>(a, disparity, row, ox0 + 1 - left, ox0 + 1, oy, s_tile, (w0 >> 24) | ((w1 & 0xffffu) << 8));
+        const uint32_t r2 = overlay_pixel<MODE>(a, disparity, row, ox0 + 2 - left, ox0 + 2, oy, s_tile, (w1 >> 16) | ((w2 & 0xffu) << 16));
+        const uint32_t r3 = overlay_pixel<MODE>(a, disparity, row, ox0 + 3 - left, ox0 + 3, oy, s_tile, w2 >> 8);
         d[0] = r0 | (r1 << 24);
         d[1] = (r1 >> 8) | (r2 << 16);
         d[2] = (r2 >> 16) | (r3 << 8);
@@ -134,7 +138,7 @@ __global__ __launch_bounds__(OV_BX * OV_BY) void stm_k_overlay(OverlayArgs a)
         for (int i = 0; i < OV_RUN; ++i) w[i] = d[i];
 #pragma unroll
         for (int i = 0; i < OV_RUN; ++i) {
-            const uint32_t r = overlay_pixel<MODE>(a, row, ox0 + i - left, ox0 + i, oy, s_tile, w[i] & 0xffffffu);
+            const uint32_t r = overlay_pixel<MODE>(a, disparity, row, ox0 + i - left, ox0 + i, oy, s_tile, w[i] & 0xffffffu);
             *(uint16_t *)(p + 4 * i) = (uint16_t)r; // the fourth byte is never written
             p[4 * i + 2] = (u8)(r >> 16);
         }
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(OV_BX * OV_BY) void stm_k_overlay(OverlayArgs a)
         if (ox < lo || ox >= hi) continue;
         u8 *o = p + (size_t)i * a.elem_sz;
         const uint32_t px = (uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16);
-        const uint32_t r = overlay_pixel<MODE>(a, row, ox - left, ox, oy, s_tile, px);
+        const uint32_t r = overlay_pixel<MODE>(a, disparity, row, ox - left, ox, oy, s_tile, px);
         o[0] = (u8)r; o[1] = (u8)(r >> 8); o[2] = (u8)(r >> 16);
     }
 }
@@ -154,11 +158,13 @@ __global__ __launch_bounds__(OV_BX * OV_BY) void stm_k_overlay(OverlayArgs a)
 // (ln.mode 0: the reference's view assignment from y_interval, inv_y_interval and ymod); 1: a quilt, screened by quilt_args_ok.
 // The arguments have been screened by the caller (stm_api.hip, overlay_args_ok); an empty bounding box launches nothing.
 void launch_overlay(u8 *out, const u8 *ov, int ov_rows, int ov_cols, int x0, int y0, float disparity, int N, const Lens &ln,
-                    float y_interval, float inv_y_interval, int ymod, const Layout &lo, int Hout, int Wout, int elem_sz)
+                    float y_interval, float inv_y_interval, int ymod, const Layout &lo, int Hout, int Wout, int elem_sz, const float *d_disp,
+                    float limit_lo, float limit_hi)
 {
     OverlayArgs a = {};
     a.out = out; a.ov = (const uint32_t *)ov;
     a.ov_rows = ov_rows; a.ov_cols = ov_cols; a.x0 = x0; a.y0 = y0; a.disparity = disparity;
+    a.d_disp = d_disp; a.limit_lo = limit_lo; a.limit_hi = limit_hi;
     a.N = N; a.Wout = Wout; a.elem_sz = elem_sz;
     a.y_interval = y_interval; a.mg = MuxGeom{inv_y_interval, ymod}; a.g = ln;
     int Hv = Hout, Wv = Wout, tiles = 1;
@@ -167,7 +173,9 @@ void launch_overlay(u8 *out, const u8 *ov, int ov_rows, int ov_cols, int x0, int
         Hv = a.q.th; Wv = a.q.tw; tiles = N;
     }
     // |x0|, |y0| <= 65536, the overlay's sides <= 65535, |disparity| <= 4096: every sum below stays far inside an int
-    const int m = (int)ceilf(fabsf(disparity) * 0.5f) + 1;
+    // a disparity read on the device is only known by its limits here: the box takes the larger one's margin, and the columns that
+    // adds sample (0, 0, 0, 0), which leaves a frame byte exactly as it is
+    const int m = (int)ceilf((d_disp ? fmaxf(fabsf(limit_lo), fabsf(limit_hi)) : fabsf(disparity)) * 0.5f) + 1;
     a.by0 = y0 > 0 ? y0 : 0;
     a.by1 = y0 + ov_rows < Hv ? y0 + ov_rows : Hv;
     a.bx0 = x0 - m > 0 ? x0 - m : 0;

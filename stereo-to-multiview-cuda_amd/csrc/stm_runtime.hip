@@ -354,6 +354,54 @@ bool overlay_params_ok(const char *fn, const void *ov, bool check_ptr, int ov_ro
     fail(msg, arg, __FILE__, __LINE__);
     return false;
 }
+// the calling thread's automatic overlay placement (stm_set_overlay_auto)
+OverlayAuto overlay_auto_default() { return OverlayAuto{0, 20, 1.0f, 8, 0.0f, 0.0f, 1.0f, 0.1f, nullptr}; }
+static thread_local OverlayAuto g_overlay_auto = overlay_auto_default();
+OverlayAuto overlay_auto() { return g_overlay_auto; }
+void set_overlay_auto(const OverlayAuto &a) { g_overlay_auto = a; }
+bool overlay_auto_params_ok(const char *fn, int near_permille, float margin, int pad, float limit_lo, float limit_hi, float rate_near,
+                            float rate_far)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (near_permille < 0 || near_permille > 499) {
+        snprintf(msg, sizeof msg, "%s: near_permille = %d, must be in 0 .. 499", fn, near_permille);
+        arg = "near_permille";
+    } else if (!(fabsf(margin) <= 4096.0f)) { // NaN fails the comparison
+        snprintf(msg, sizeof msg, "%s: margin = %g, must be finite and of magnitude <= 4096", fn, (double)margin);
+        arg = "margin";
+    } else if (pad < 0 || pad > 4096) {
+        snprintf(msg, sizeof msg, "%s: pad = %d, must be in 0 .. 4096", fn, pad);
+        arg = "pad";
+    } else if (!(fabsf(limit_lo) <= 4096.0f)) {
+        snprintf(msg, sizeof msg, "%s: limit_lo = %g, must be finite and of magnitude <= 4096", fn, (double)limit_lo);
+        arg = "limit_lo";
+    } else if (!(fabsf(limit_hi) <= 4096.0f)) {
+        snprintf(msg, sizeof msg, "%s: limit_hi = %g, must be finite and of magnitude <= 4096", fn, (double)limit_hi);
+        arg = "limit_hi";
+    } else if (!(limit_lo <= limit_hi)) {
+        snprintf(msg, sizeof msg, "%s: limit_lo = %g > limit_hi = %g", fn, (double)limit_lo, (double)limit_hi);
+        arg = "limit_lo, limit_hi";
+    } else if (!(rate_near > 0.0f && rate_near <= 1.0f)) {
+        snprintf(msg, sizeof msg, "%s: rate_near = %g, must be in (0, 1]", fn, (double)rate_near);
+        arg = "rate_near";
+    } else if (!(rate_far > 0.0f && rate_far <= 1.0f)) {
+        snprintf(msg, sizeof msg, "%s: rate_far = %g, must be in (0, 1]", fn, (double)rate_far);
+        arg = "rate_far";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+bool overlay_fit_size_ok(const char *fn, int num_rows, int num_cols)
+{
+    if ((size_t)num_rows * num_cols <= 0x7fffffffu) return true;
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: num_rows * num_cols = %zu, must be below 2^31 (the overlay's fit counts in 32 bits)", fn,
+             (size_t)num_rows * num_cols);
+    fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
+    return false;
+}
 // stm_mux_nv12's coefficients (stm_hip.h): each rounded one computed in double and rounded to nearest, the three derived ones by
 // subtraction, so that white lands on the range's end and every grey on 128 / 128
 Nv12OutCoef nv12_out_coef(int matrix)
@@ -804,6 +852,27 @@ void stm_get_overlay(int out[5], float *disparity)
     const stm::Overlay o = stm::overlay();
     out[0] = o.mode; out[1] = o.ov_rows; out[2] = o.ov_cols; out[3] = o.x0; out[4] = o.y0;
     if (disparity) *disparity = o.disparity;
+}
+int stm_set_overlay_auto(int mode, int near_permille, float margin, int pad, float limit_lo, float limit_hi, float rate_near, float rate_far,
+                         float *d_state)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (mode != 0 && mode != 1) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "set_overlay_auto: mode = %d, must be 0 (off) or 1 (on)", mode);
+        stm::fail(msg, "mode", __FILE__, __LINE__);
+        return -1; // the thread's setting stays as it was
+    }
+    if (mode == 1 && !stm::overlay_auto_params_ok("set_overlay_auto", near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far)) return -1;
+    stm::set_overlay_auto(mode == 0 ? stm::overlay_auto_default()
+                                    : stm::OverlayAuto{1, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, d_state});
+    return 0;
+}
+void stm_get_overlay_auto(int out_mode[3], float out[5])
+{
+    const stm::OverlayAuto a = stm::overlay_auto();
+    out_mode[0] = a.mode; out_mode[1] = a.near_permille; out_mode[2] = a.pad;
+    out[0] = a.margin; out[1] = a.limit_lo; out[2] = a.limit_hi; out[3] = a.rate_near; out[4] = a.rate_far;
 }
 void stm_set_quilt_lds_limit(int bytes) { stm::g_quilt_lds_limit = bytes <= 0 ? 32 * 1024 : (bytes > 64 * 1024 ? 64 * 1024 : bytes); }
 int stm_set_packing(int packing, int swap, int filter, int gap)

@@ -28,6 +28,8 @@ struct Slot {
     int *d_crec = nullptr, *h_crec = nullptr;   // cut mode 1: {cut, since, score} as this slot's frame's decision left them (12 bytes)
     u8 *h_ov = nullptr, *d_ov = nullptr;      // stm_stream_set_overlay: the slot's pinned and device copy of the overlay's pixels
     long ov_gen = 0;                          // ... and which stm_stream_overlay call they hold (0 = none yet)
+    float *d_orec = nullptr, *h_orec = nullptr; // stm_stream_set_overlay_auto: the overlay's state as this slot's frame left it (16 bytes), and its download
+    float ov_disparity = 0.0f;                // the setter's disparity this slot's frame was submitted under (0 without an overlay)
     hipEvent_t ev_in, ev_done, ev_out;
     bool busy = false;
     hipStream_t s_compute = nullptr; // this slot's compute stream and private workspace (shared by both slots when overlap is off)
@@ -74,6 +76,10 @@ struct FrameStream {
     u8 *ov_pixels = nullptr;              // stm_stream_overlay: the pixels of the overlay in force (host memory of the stream's own)
     stm::Overlay ov = {0, nullptr, 0, 0, 0, 0, 0.0f}; // ... and its arguments; mode 0 = none.  d_overlay is filled in per slot
     long ov_gen = 0;                      // counts the stm_stream_overlay calls that brought pixels
+    stm::OverlayAuto ov_auto = stm::overlay_auto_default(); // stm_stream_set_overlay_auto: the stream's own automatic placement
+    float *d_ov_state = nullptr;          // ... its state {valid, disparity, nearest, 0}, at one address for every frame
+    uint32_t *d_ov_ws = nullptr;          // ... and the fit's bins and alpha box
+    long ov_fit_gen = 0;                  // the overlay generation the last fitted frame was submitted under
     Slot slot[2];
     long submitted = 0, collected = 0;
 };
@@ -507,6 +513,63 @@ int stm_stream_set_overlay(void *h, int max_rows, int max_cols)
     f->ov_max_cols = max_cols;
     f->ov = stm::Overlay{0, nullptr, 0, 0, 0, 0, 0.0f};
     f->ov_gen = 0;
+    if (off) f->ov_auto.mode = 0; // the placement belongs to the overlay: set it again after the next stm_stream_set_overlay
+    return 0;
+}
+
+// The automatic placement of the stream's overlay (stm_set_overlay_auto's rules; the default is mode 0).  Only before the first
+// submit and after stm_stream_set_overlay.  Mode 1 allocates the stream's state -- 16 bytes at a fixed address, zeroed here, never by
+// a memset node of a graph --, the fit's scratch and the slots' records.  Returns 0, or -1 with the error recorded and the stream unchanged.
+int stm_stream_set_overlay_auto(void *h, int mode, int near_permille, float margin, int pad, float limit_lo, float limit_hi, float rate_near,
+                                float rate_far)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (mode != 0 && mode != 1) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "stream_set_overlay_auto: mode = %d, must be 0 (off) or 1 (on)", mode);
+        stm::fail(msg, "mode", __FILE__, __LINE__);
+        return -1;
+    }
+    if (mode == 1 && (!stm::overlay_auto_params_ok("stream_set_overlay_auto", near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far) ||
+                      !stm::overlay_fit_size_ok("stream_set_overlay_auto", f->H, f->W)))
+        return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_overlay_auto: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    if (mode == 1 && f->ov_max_rows == 0) {
+        stm::fail("stream_set_overlay_auto: the stream has no overlay (stm_stream_set_overlay comes first)", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    if (mode == 1 && !f->d_ov_state) {
+        int caller_dev = f->dev;
+        STM_CHECK(hipGetDevice(&caller_dev));
+        if (caller_dev != f->dev) STM_CHECK(hipSetDevice(f->dev));
+        STM_CHECK(hipMalloc((void **)&f->d_ov_state, 16));
+        STM_CHECK(hipMemset(f->d_ov_state, 0, 16)); // valid = 0: the first fit has no history
+        STM_CHECK(hipMalloc((void **)&f->d_ov_ws, stm::OVERLAY_FIT_WS_WORDS * 4));
+        for (Slot &s : f->slot) {
+            STM_CHECK(hipMalloc((void **)&s.d_orec, 16));
+            STM_CHECK(hipHostMalloc((void **)&s.h_orec, 16, hipHostMallocDefault));
+            if (s.h_orec) memset(s.h_orec, 0, 16);
+        }
+        if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
+        if (stm::failed()) return -1;
+    }
+    f->ov_auto = mode == 0 ? stm::overlay_auto_default()
+                           : stm::OverlayAuto{1, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, f->d_ov_state};
+    return 0;
+}
+// the overlay's state {valid, disparity, nearest, 0} as the most recently collected frame left it; with the placement off:
+// {0, the disparity of stm_stream_overlay that frame was submitted under, 0, 0}
+int stm_stream_overlay_depth(void *h, float out[4])
+{
+    FrameStream *f = (FrameStream *)h;
+    if (f->collected == 0) return -1;
+    const Slot &s = f->slot[(f->collected - 1) & 1];
+    if (f->ov_auto.mode == 1) { for (int i = 0; i < 4; ++i) out[i] = s.h_orec[i]; }
+    else { out[0] = 0.0f; out[1] = s.ov_disparity; out[2] = out[3] = 0.0f; }
     return 0;
 }
 
@@ -797,6 +860,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     const bool align_auto = f->align.mode == 2; // likewise the alignment's state
     const bool balance_auto = f->balance.mode == 2; // ... and the colour balance's
     const bool cut_on = f->cut.mode == 1;           // ... and the shot-change detector's
+    const bool ov_auto = f->ov_auto.mode == 1;      // ... and the overlay placement's, which also reads the depth and the cut state
     // In NV12 mode the history is the other slot's converted split images (d_img_l / d_img_r), which no upload touches, and this
     // slot's d_in was last read by this slot's own previous frame, collected before the slot was handed out again: the upload
     // waits for nothing.  This frame's compute still waits for the other slot's frame: it reads that frame's images and maps, and
@@ -814,7 +878,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     }
     STM_CHECK(hipEventRecord(s.ev_in, f->s_in));
     STM_CHECK(hipStreamWaitEvent(s.s_compute, s.ev_in, 0));
-    if (history || ((depth_auto || align_auto || balance_auto || cut_on) && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
+    if (history || ((depth_auto || align_auto || balance_auto || cut_on || ov_auto) && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
     void *prev = stm_get_stream();
     LensScope lens_scope(f->lens);
     LayoutScope layout_scope(f->layout);
@@ -901,10 +965,19 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
         ++s.eager_runs;
     }
     // the overlay, composited on the slot's finished frame: a launch of its own behind the graph (or the eager pipeline) on the slot's
-    // compute stream, so its arguments change from frame to frame without touching the capture
-    if (ov.mode == 1)
+    // compute stream, so its arguments change from frame to frame without touching the capture.  With the automatic placement the fit's
+    // launches go in front of it in the same way: they read this frame's maps and the depth and cut states its pipeline left, and the
+    // overlay's state the previous frame left (the wait on the other slot's ev_done above).  A new overlay has no continuity to keep
+    s.ov_disparity = ov.mode == 1 ? ov.disparity : 0.0f;
+    if (ov.mode == 1 && ov_auto) {
+        stm::frame_overlay_auto(s.d_out, stm::Overlay{1, s.d_ov, ov.ov_rows, ov.ov_cols, ov.x0, ov.y0, ov.disparity}, f->ov_auto, f->d_ov_state,
+                                f->d_ov_ws, f->ov_gen != f->ov_fit_gen, false, s.d_dl, s.d_dr, f->H, f->W, f->depth, f->depth.d_state,
+                                cut_on ? f->d_cut_state : nullptr, f->lens, f->layout, f->N, f->angle, f->Hout, f->Wout, f->E);
+        f->ov_fit_gen = f->ov_gen;
+    } else if (ov.mode == 1) {
         stm::frame_overlay(s.d_out, stm::Overlay{1, s.d_ov, ov.ov_rows, ov.ov_cols, ov.x0, ov.y0, ov.disparity}, f->lens, f->layout, f->N,
                            f->angle, f->Hout, f->Wout, f->E);
+    }
     stm::ws_private_bind(nullptr);
     stm_set_stream(prev);
     // the state as this frame left it, before ev_done lets the next frame's fit update it
@@ -913,6 +986,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     if (balance_auto)
         STM_CHECK(hipMemcpyAsync(s.d_brec, f->d_balance_state, stm::BALANCE_STATE_WORDS * 4, hipMemcpyDeviceToDevice, s.s_compute));
     if (cut_on) STM_CHECK(hipMemcpyAsync(s.d_crec, f->d_cut_state + 1, 12, hipMemcpyDeviceToDevice, s.s_compute));
+    if (ov_auto) STM_CHECK(hipMemcpyAsync(s.d_orec, f->d_ov_state, 16, hipMemcpyDeviceToDevice, s.s_compute));
     STM_CHECK(hipEventRecord(s.ev_done, s.s_compute));
     STM_CHECK(hipStreamWaitEvent(f->s_out, s.ev_done, 0));
     STM_CHECK(hipMemcpyAsync(s.h_dl, s.d_dl, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
@@ -922,6 +996,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     if (align_auto) STM_CHECK(hipMemcpyAsync(s.h_arec, s.d_arec, 16, hipMemcpyDeviceToHost, f->s_out));
     if (balance_auto) STM_CHECK(hipMemcpyAsync(s.h_brec, s.d_brec, stm::BALANCE_STATE_WORDS * 4, hipMemcpyDeviceToHost, f->s_out));
     if (cut_on) STM_CHECK(hipMemcpyAsync(s.h_crec, s.d_crec, 12, hipMemcpyDeviceToHost, f->s_out));
+    if (ov_auto) STM_CHECK(hipMemcpyAsync(s.h_orec, s.d_orec, 16, hipMemcpyDeviceToHost, f->s_out));
     STM_CHECK(hipEventRecord(s.ev_out, f->s_out));
     if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
     if (stm::failed()) return -1; // error mode 1: the frame was not (completely) enqueued
@@ -993,8 +1068,12 @@ void stm_stream_destroy(void *h)
         if (s.h_crec) STM_CHECK(hipHostFree(s.h_crec));
         if (s.h_ov) STM_CHECK(hipHostFree(s.h_ov));
         if (s.d_ov) STM_CHECK(hipFree(s.d_ov));
+        if (s.d_orec) STM_CHECK(hipFree(s.d_orec));
+        if (s.h_orec) STM_CHECK(hipHostFree(s.h_orec));
     }
     free(f->ov_pixels);
+    if (f->d_ov_state) STM_CHECK(hipFree(f->d_ov_state));
+    if (f->d_ov_ws) STM_CHECK(hipFree(f->d_ov_ws));
     if (f->d_depth_state) STM_CHECK(hipFree(f->d_depth_state));
     if (f->d_align_state) STM_CHECK(hipFree(f->d_align_state));
     if (f->d_balance_state) STM_CHECK(hipFree(f->d_balance_state));

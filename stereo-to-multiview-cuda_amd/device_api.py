@@ -172,6 +172,57 @@ def set_overlay(d_overlay, x0=0, y0=0, disparity=0.0):
     _overlay_keepalive[threading.get_ident()] = d_overlay
 
 
+OVERLAY_AUTO_DEFAULTS = (20, 1.0, 8, 1.0, 0.1)  # near_permille, margin, pad, rate_near, rate_far: choices, not measurements
+
+
+def set_overlay_auto(limit_lo=None, limit_hi=None, near_permille=20, margin=1.0, pad=8, rate_near=1.0, rate_far=0.1, state=None):
+    """stm_set_overlay_auto: the calling thread's automatic overlay placement.  While it is on and the thread's overlay is on
+    (set_overlay, whose disparity is then ignored), every rendering frame call fits the overlay's disparity to the maps under the
+    overlay's alpha box on the GPU (d_overlay_fit has the parameters) and composites at fminf(fmaxf(state[1], limit_lo), limit_hi).
+    `state`: a float32 tensor of four elements on the GPU, {valid, disparity, nearest, 0}, which carries the history from frame to
+    frame (zero `valid` to reset it) -- the caller keeps it alive while the setting is in use; None = every frame on its own.
+    limit_lo None switches the setting off.  Raises ValueError where the library refuses."""
+    if limit_lo is None:
+        lib().stm_set_overlay_auto(0, 0, 0.0, 0, 0.0, 0.0, 0.0, 0.0, None)
+        return
+    if state is not None:
+        assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous() and state.numel() == 4
+    if int(lib().stm_set_overlay_auto(1, int(near_permille), float(margin), int(pad), float(limit_lo), float(limit_hi), float(rate_near),
+                                      float(rate_far), _p(state) if state is not None else None)) != 0:
+        raise ValueError("stm_set_overlay_auto(%d, %g, %d, %g, %g, %g, %g) refused: %s"
+                         % (near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, lib().stm_last_error().decode()))
+
+
+def get_overlay_auto():
+    """stm_get_overlay_auto: the calling thread's (mode, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far)"""
+    m = (C.c_int * 3)()
+    v = (C.c_float * 5)()
+    lib().stm_get_overlay_auto(m, C.cast(v, f32p))
+    return (m[0], m[1], v[0], m[2], v[1], v[2], v[3], v[4])
+
+
+def d_overlay_fit(disp_l, disp_r, overlay, x0, y0, view_rows, view_cols, limit_lo, limit_hi, state, gain=1.0, conv=0.0, near_permille=20,
+                  margin=1.0, pad=8, rate_near=1.0, rate_far=0.1, restart=False, cut_state=None):
+    """stm_d_overlay_fit: the measurement of the overlay's placement as a stage -- the alpha box of `overlay` (uint8 [rows][cols][4]
+    on the GPU) at (x0, y0) of the view view_rows x view_cols, both maps (float32 [H][W] on the GPU) under its footprint widened by
+    `pad` into the quarter-pixel histogram, the near_permille percentile mapped through the budget (gain, conv) and the view's
+    width, `margin` subtracted, clamped to [limit_lo, limit_hi], and the update of `state` (float32, four elements on the GPU:
+    valid, disparity, nearest, 0) in place at rate_near / rate_far; cut_state: stm_cut_detect's 260 ints on the GPU or None.
+    Nothing is synchronised."""
+    H, W = disp_l.shape
+    for t in (disp_l, disp_r):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
+    _check_overlay(overlay)
+    assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous() and state.numel() == 4
+    if cut_state is not None:
+        assert cut_state.is_cuda and cut_state.dtype == torch.int32 and cut_state.is_contiguous() and cut_state.numel() >= 2
+    _use_current_stream()
+    lib().stm_d_overlay_fit(_p(disp_l), _p(disp_r), H, W, _p(overlay), overlay.shape[0], overlay.shape[1], int(x0), int(y0), int(view_rows),
+                            int(view_cols), float(gain), float(conv), int(near_permille), float(margin), int(pad), float(limit_lo),
+                            float(limit_hi), float(rate_near), float(rate_far), int(bool(restart)), _p(state),
+                            _p(cut_state) if cut_state is not None else None)
+
+
 def get_overlay():
     """stm_get_overlay: the calling thread's (mode, ov_rows, ov_cols, x0, y0, disparity) as the library holds it"""
     out = (C.c_int * 5)()

@@ -381,6 +381,25 @@ def depth_fit(disp_l, disp_r, disp_lo, disp_hi, max_gain=1.0, clip_permille=20, 
     return st
 
 
+def overlay_fit(disp_l, disp_r, overlay, x0, y0, view_rows, view_cols, limit_lo, limit_hi, gain=1.0, conv=0.0, near_permille=20, margin=1.0,
+                pad=8, rate_near=1.0, rate_far=0.1, restart=False, state=None):
+    """The measurement of the overlay's automatic depth placement (stm_overlay_fit; an addition, the reference has no overlay): the
+    disparity that keeps the overlay [rows][cols][4] at (x0, y0) of the view view_rows x view_cols in front of what the two maps
+    [H][W] show under its alpha box, folded into `state` = (valid, disparity, nearest, 0) (None = no history).  Returns the new
+    state as a float32 array of four; nothing passed in is modified."""
+    disp_l, pl = _f32(disp_l)
+    disp_r, pr = _f32(disp_r)
+    overlay, po = _u8(overlay)
+    H, W = disp_l.shape
+    assert disp_r.shape == (H, W) and overlay.ndim == 3 and overlay.shape[2] == 4
+    st = np.zeros(4, np.float32) if state is None else np.array(state, dtype=np.float32, order="C")
+    assert st.shape == (4,)
+    lib().stm_overlay_fit(pl, pr, H, W, po, overlay.shape[0], overlay.shape[1], int(x0), int(y0), int(view_rows), int(view_cols), float(gain),
+                          float(conv), int(near_permille), float(margin), int(pad), float(limit_lo), float(limit_hi), float(rate_near),
+                          float(rate_far), int(bool(restart)), st.ctypes.data_as(f32p))
+    return st
+
+
 def view_prefilter(img, disp, num_views, strength=1.0, max_radius=8, gate=1.0, gain=1.0, conv=0.0):
     """View antialiasing (stm_view_prefilter; an addition, the reference's views are pinhole images): img [H][W][E] filtered along
     its rows by its own map disp [H][W] -- a box of 1 + strength * |gain * disp - conv| / (num_views - 1) pixels, at most max_radius

@@ -34,6 +34,9 @@ class FrameStream:
     output = (1, matrix): the quilt comes out as NV12 (set_output), each frame uint8 [out_rows * 3 / 2][out_cols], the Y plane followed
     by the interleaved UV plane; None = BGR.  Needs a layout.  overlay = (max_rows, max_cols): the stream composites an overlay of up
     to that size into its frames (set_overlay; .overlay() sets the one in force); None = none.  Not together with an NV12 output.
+    overlay_auto = (limit_lo, limit_hi[, near_permille, margin, pad, rate_near, rate_far]): the overlay's disparity is fitted on every
+    frame on the GPU to the maps under the overlay (set_overlay_auto) and .overlay()'s own disparity is ignored; needs `overlay`;
+    .overlay_depth() reads the state of the last collected frame.
     antialias = (strength, max_radius, gate): view antialiasing (set_antialias mode 1) -- both images filtered by their own maps
     before the views are rendered from them; None = off.  align = (a, b, c): the right eye of every frame sampled at row
     y + a + b u + c v ahead of the matcher (set_align mode 1); align_auto = (radius[, rate]): the field measured on every frame on
@@ -46,7 +49,7 @@ class FrameStream:
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
                  depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None, overlay=None,
-                 antialias=None, align=None, align_auto=None, balance=None, balance_auto=None, cut=None):
+                 antialias=None, align=None, align_auto=None, balance=None, balance_auto=None, cut=None, overlay_auto=None):
         self.H, self.W = num_rows, num_cols
         self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
@@ -81,6 +84,8 @@ class FrameStream:
             self.set_depth(2)
         if overlay is not None:
             self.set_overlay(*overlay)
+        if overlay_auto is not None:
+            self.set_overlay_auto(1, *overlay_auto)
         if antialias is not None:
             self.set_antialias(1, *antialias)
         if align is not None and align_auto is not None:
@@ -172,6 +177,23 @@ class FrameStream:
         submit; refused together with an NV12 output.  Raises ValueError where the library refuses."""
         if int(lib().stm_stream_set_overlay(self._h, int(max_rows), int(max_cols))) != 0:
             raise ValueError("stm_stream_set_overlay(%d, %d) refused: %s" % (max_rows, max_cols, lib().stm_last_error().decode()))
+
+    def set_overlay_auto(self, mode, limit_lo=0.0, limit_hi=0.0, near_permille=20, margin=1.0, pad=8, rate_near=1.0, rate_far=0.1):
+        """stm_stream_set_overlay_auto: the automatic placement of the stream's overlay (device_api.set_overlay_auto's parameters;
+        the state is the stream's own); only before the first submit and after set_overlay.  Raises ValueError where the library
+        refuses."""
+        if int(lib().stm_stream_set_overlay_auto(self._h, int(mode), int(near_permille), float(margin), int(pad), float(limit_lo),
+                                                 float(limit_hi), float(rate_near), float(rate_far))) != 0:
+            raise ValueError("stm_stream_set_overlay_auto(%d, %d, %g, %d, %g, %g, %g, %g) refused: %s"
+                             % (mode, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, lib().stm_last_error().decode()))
+
+    def overlay_depth(self):
+        """stm_stream_overlay_depth: the overlay's state (valid, disparity, nearest, 0) as the most recently collected frame left it
+        -- a float32 array of four -- or None before the first collect."""
+        out = (C.c_float * 4)()
+        if int(lib().stm_stream_overlay_depth(self._h, C.cast(out, f32p))) != 0:
+            return None
+        return np.array(list(out), np.float32)
 
     def overlay(self, bgra, x0=0, y0=0, disparity=0.0):
         """stm_stream_overlay: the overlay every later submit composites, until the next call -- uint8 [rows][cols][4], B, G, R, A
@@ -409,8 +431,10 @@ def take_cut_option(argv):
     return cut
 
 
-def _collect(fs, on_depth, on_align=None, on_balance=None, on_cut=None):
+def _collect(fs, on_depth, on_align=None, on_balance=None, on_cut=None, on_overlay_depth=None):
     r = fs.collect()
+    if on_overlay_depth is not None and r is not None:
+        on_overlay_depth(r[0], fs.overlay_depth())
     if on_cut is not None and r is not None:
         on_cut(r[0], fs.cut())
     if on_balance is not None and r is not None:
@@ -425,7 +449,7 @@ def _collect(fs, on_depth, on_align=None, on_balance=None, on_cut=None):
 def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None,
                      depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None,
                      overlay=None, antialias=None, align=None, align_auto=None, on_align=None, balance=None, balance_auto=None,
-                     on_balance=None, cut=None, on_cut=None):
+                     on_balance=None, cut=None, on_cut=None, overlay_auto=None, on_overlay_depth=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
@@ -439,7 +463,8 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
     antialias: FrameStream's (strength, max_radius, gate): view antialiasing of every frame.  align / align_auto: FrameStream's
     vertical alignment of every frame's pair; on_align: called with (index, (a, b, c)) after every collected frame.  balance /
     balance_auto: FrameStream's colour balance of every frame's pair; on_balance: called with (index, tables) likewise.  cut:
-    FrameStream's shot-change detector; on_cut: called with (index, (cut, score, since)) likewise."""
+    FrameStream's shot-change detector; on_cut: called with (index, (cut, score, since)) likewise.  overlay_auto: FrameStream's
+    automatic placement of `overlay`, whose disparity is then ignored; on_overlay_depth: called with (index, state) likewise."""
     fs = None
     pending = 0
     for sbs in frames:
@@ -450,18 +475,18 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
                 rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
             fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output,
                              overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]), antialias=antialias,
-                             align=align, align_auto=align_auto, balance=balance, balance_auto=balance_auto, cut=cut)
+                             align=align, align_auto=align_auto, balance=balance, balance_auto=balance_auto, cut=cut, overlay_auto=overlay_auto)
             if overlay is not None:
                 fs.overlay(*overlay)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:
-            yield _collect(fs, on_depth, on_align, on_balance, on_cut)
+            yield _collect(fs, on_depth, on_align, on_balance, on_cut, on_overlay_depth)
             pending -= 1
         fs.submit(sbs)
         pending += 1
     while fs is not None and pending:
-        yield _collect(fs, on_depth, on_align, on_balance, on_cut)
+        yield _collect(fs, on_depth, on_align, on_balance, on_cut, on_overlay_depth)
         pending -= 1
     if fs is not None:
         fs.close()

@@ -8,7 +8,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--nv12 ROWS COLS_SBS [--matrix M]] [--lens MODE PITCH SLOPE CENTRE]
                     [--depth GAIN CONV | --depth-auto LO HI [MAX_GAIN CLIP RATE]]
                     [--packing P SWAP FILTER GAP] [--quilt TX TY ORDER FILTER [--nv12-out MATRIX]] [--match H W SCALE [--guided-up]]
-                    [--overlay FILE.npy X0 Y0 DISPARITY] [--antialias STRENGTH MAX_RADIUS GATE]
+                    [--overlay FILE.npy X0 Y0 DISPARITY] [--overlay-auto LO HI [NEAR MARGIN PAD RATE_NEAR RATE_FAR]] [--antialias STRENGTH MAX_RADIUS GATE]
                     [--align A B C | --align-auto RADIUS [RATE]] [--balance FILE.npy | --balance-auto [MAX_SHIFT RATE]]
                     [--cut [THRESH MIN_GAP]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
@@ -45,6 +45,11 @@ reduced pair.  --guided-up adds frame bit 0x1000, the guided up-sampler in place
 alpha (video.premultiply converts straight alpha) -- composited into every frame of the sequence with its top-left corner at view pixel
 (X0, Y0) -- a pixel of the frame, or of every tile under --quilt -- and at the end-to-end DISPARITY in pixels: > 0 behind the screen,
 < 0 in front, 0 on it (stm_stream_overlay).  Excludes --nv12-out.
+--overlay-auto LO HI [NEAR MARGIN PAD RATE_NEAR RATE_FAR] (an addition, used with --overlay, whose DISPARITY is then ignored): the
+overlay's disparity is fitted on every frame on the GPU (stm_stream_set_overlay_auto) -- the NEAR permille (0 .. 499) nearest of both
+maps' values under the overlay's opaque part, widened by PAD view pixels (0 .. 4096), as the views display it, MARGIN pixels nearer,
+kept within [LO, HI]; a scene that comes nearer is followed at RATE_NEAR, one that recedes at RATE_FAR (both in (0, 1]).  The five
+optional values default to 20, 1, 8, 1 and 0.1: choices, not measurements.  The disparity applied to each frame is printed.
 --antialias STRENGTH MAX_RADIUS GATE (an addition): view antialiasing (stm_stream_set_antialias) -- before the views are rendered both
 images are blurred along their rows by a box of 1 + STRENGTH * |displayed disparity| / (<num views> - 1) pixels (STRENGTH in [0, 8],
 1 = one view spacing), at most MAX_RADIUS (1 .. 16) pixels to a side, using only neighbours whose disparity lies within GATE (>= 0) of
@@ -175,6 +180,28 @@ def main(argv):
             print(__doc__)
             return -1
         del argv[at:at + 5]
+    overlay_auto = None
+    if "--overlay-auto" in argv:
+        at = argv.index("--overlay-auto")
+        try:
+            vals = []
+            for x in argv[at + 1:at + 8]:  # LO HI, then up to five optional numbers
+                try:
+                    vals.append(float(x))
+                except ValueError:
+                    break
+            if len(vals) not in (2, 7) or overlay is None:
+                raise ValueError(vals)
+            lo, hi = vals[0], vals[1]
+            near, margin, pad, rate_near, rate_far = vals[2:] if len(vals) == 7 else (20.0, 1.0, 8.0, 1.0, 0.1)
+            if not (lo <= hi and abs(lo) <= 4096.0 and abs(hi) <= 4096.0 and near == int(near) and 0 <= near <= 499 and abs(margin) <= 4096.0
+                    and pad == int(pad) and 0 <= pad <= 4096 and 0.0 < rate_near <= 1.0 and 0.0 < rate_far <= 1.0):
+                raise ValueError(vals)
+            overlay_auto = (lo, hi, int(near), margin, int(pad), rate_near, rate_far)
+        except (ValueError, IndexError):
+            print(__doc__)
+            return -1
+        del argv[at:at + 1 + len(vals)]
     depth, depth_auto = None, None
     try:
         if "--depth" in argv:
@@ -289,7 +316,10 @@ def main(argv):
                                                        on_balance=(lambda k, t: print("frame %d: balance B %d %d %d G %d %d %d R %d %d %d" % (
                                                            (k,) + tuple(int(t[c, v]) for c in range(3) for v in (64, 128, 192)))))
                                                        if balance_auto is not None else None,
-                                                       cut=cut, on_cut=on_cut if cut is not None else None):
+                                                       cut=cut, on_cut=on_cut if cut is not None else None, overlay_auto=overlay_auto,
+                                                       on_overlay_depth=(lambda k, st: print("frame %d: overlay disparity %.6g nearest %.6g" % (
+                                                           k, min(max(float(st[1]), overlay_auto[0]), overlay_auto[1]), float(st[2]))))
+                                                       if overlay_auto is not None else None):
         if yuv is not None:  # the frame is [out height * 3 / 2][out width]: the Y plane, then the interleaved UV plane
             yuv.write(inter.tobytes())
             video.write_disparities(out_dir, k, dl, dr)
