@@ -292,6 +292,39 @@ int         stm_set_cut(int mode, int thresh_permille, int min_gap, int *d_state
 /* out = {mode, thresh_permille, min_gap} as the last accepted calls left them (before any: 0, 370, 1).  A frame stream's own
  * setting is not visible here except during its submit. */
 void        stm_get_cut(int out[3]);
+/* The calling thread's active picture area (an addition: the reference matches and measures black bars as if they were picture.  A
+ * 2.39:1 film in a 16:9 frame has a quarter of its pixels in two bars, where the matcher has nothing to match: pure black ties at
+ * -zero_disp, codec noise matches anywhere, and both go straight into depth mode 2's range and into the "nearest content" under a
+ * subtitle that lies in the bottom bar).  mode 0 = off (the default: the other arguments are ignored, and not one launch, argument or
+ * kernel of any call changes), 1 = a given rectangle rect = {top, bottom, left, right}: rows [top, bottom), columns [left, right) of
+ * one unpacked eye, 2 = measured: every frame call runs stm_d_active_detect's three launches on the left eye of its full-resolution
+ * input as given (BGR or NV12, any packing), after the shot-change detector and before the alignment's measurement -- the left eye is
+ * the reference of the alignment and the balance, so the result depends on neither -- with stm_set_active_auto's parameters and
+ * state, restart = 0 (1 with a null state) and, where stm_set_cut is on, its state.
+ * With mode != 0 the frame calls stm_d_adcensus_stm, _t, _nv12, _2s, _2t, _2nv12 (and the host flavours through them):
+ *   - fit depth mode 2 as stm_d_depth_fit_rect does, under the rectangle read on the device;
+ *   - fit the automatic overlay placement (stm_set_overlay_auto) as stm_d_overlay_fit_rect does;
+ *   - with fill = 1, run stm_d_active_fill(., fill_disp) on both maps they hand back, after the temporal step and before the
+ *     renderer, whatever the `stages` low byte is, in the reduced-resolution calls on the up-scaled maps: the maps come back clean
+ *     and side bars render as one stable surface.
+ * Nothing is synchronised or read back.  Rules under mode 1: 0 <= top < bottom <= num_rows and 0 <= left < right <= num_cols in every
+ * frame call; under mode 2: num_rows * num_cols < 2^31.  A frame call that breaks one is refused through stm_last_error before
+ * anything is launched or written.
+ * Not treated: the cut signature, the alignment's profiles and the balance's histograms keep reading the whole frame; the bars of
+ * the finished frame are not painted (every warp is along a row, so bar rows sample bar rows); bars that differ between the eyes
+ * (floating windows).
+ * Argument rules: mode 0, 1 or 2; in mode 1 a non-null rect with 0 <= top < bottom and 0 <= left < right; with mode != 0 fill 0 or 1
+ * and fill_disp finite with |fill_disp| <= 4096.  Returns 0, or -1 with stm_last_error set and the thread's setting unchanged. */
+int         stm_set_active(int mode, const int rect[4], int fill, float fill_disp);
+/* Mode 2's parameters, kept when the mode changes: thresh_luma 0 .. 254 (default 24: limited-range black, 16, plus noise),
+ * lit_permille 0 .. 999 (10), max_bar_permille 0 .. 450 (300), hold 1 .. 2^20 (12); stm_active_detect has the definition.  d_state =
+ * 16 ints in device memory the caller owns, zeroes once and keeps alive while the setting is on, or null: scratch memory, every frame
+ * measured on its own.  Returns 0, or -1 with stm_last_error set and the old parameters in place. */
+int         stm_set_active_auto(int thresh_luma, int lit_permille, int max_bar_permille, int hold, int *d_state);
+/* out = {mode, top, bottom, left, right, fill, thresh_luma, lit_permille, max_bar_permille, hold}, *fill_disp the fill value, as the
+ * last accepted calls left them (before any: 0, 0, 0, 0, 0, 0, 24, 10, 300, 12 and 0).  A frame stream's own setting is not visible here
+ * except during its submit. */
+void        stm_get_active(int out[10], float *fill_disp);
 /* The calling thread's output geometry (an addition: the reference shows its views in one form only, sub-pixel interlaced).
  * layout 0 = the interlaced frame (the default; tiles_x, tiles_y, order and filter are ignored, and not one launch, argument or
  * kernel changes), 1 = a quilt: the views side by side as a grid of tiles, whole, for a display that interlaces with its own
@@ -1229,6 +1262,72 @@ void stm_d_balance_apply(unsigned char *d_img_out, const unsigned char *d_img, i
 int  stm_cut_detect(const unsigned char *img_l, int num_rows, int num_cols, int elem_sz, int thresh_permille, int min_gap, int *state);
 void stm_d_cut_detect(const unsigned char *d_img_l, int num_rows, int num_cols, int elem_sz, int thresh_permille, int min_gap, int *d_state,
                       void *d_reset0, void *d_reset1, void *d_reset2, unsigned int *d_sig);
+/* The active picture area as stages (an addition, see stm_set_active).  Everything is integer arithmetic; no result depends on the
+ * order of execution.  The input is the LEFT eye of a frame, unpacked and converted as the shot-change detector sees it: H x W pixels.
+ * State: int32 state[16] = {valid, top, bottom, left, right, changed, H, W, cand[4], run[4]}; the four sides are numbered top, bottom,
+ * left, right.
+ *   1. Lit pixels.  Y = (B + 2 G + R) >> 2 (stm_cut_detect's luma); a pixel is lit when Y > thresh_luma.
+ *   2. Counts.  r[y] = the lit pixels of row y, c[x] = the lit pixels of column x, u32; counts = r then c, H + W words.
+ *   3. Picture lines, in u64.  Row y is a picture row when r[y] * 1000 > lit_permille * W; column x is a picture column when
+ *      c[x] * 1000 > lit_permille * H (the column's count runs over all rows, the bars' included).  A burnt-in logo or a few hot
+ *      pixels in a bar stay below the permille and move nothing.
+ *   4. Bars of this frame.  m[0] = the rows above the first picture row, m[1] = the rows below the last, m[2], m[3] likewise for the
+ *      columns left of the first and right of the last picture column.  No picture row or no picture column: the frame is BLANK.
+ *      Otherwise m[0], m[1] = min(m, H * max_bar_permille / 1000) and m[2], m[3] = min(m, W * max_bar_permille / 1000), floor
+ *      division: at most 450 permille a side, so the rectangle is never empty and a night scene with a lit centre cannot turn most
+ *      of the frame into bars.
+ *   5. History exists when state[0] != 0, state[6] == H and state[7] == W: a state left by a frame of another size counts as none.
+ *      The fit RESTARTS when there is no history, when restart != 0, or when a cut state is given (the 260 ints of stm_cut_detect)
+ *      and its word 1, this frame's cut flag, is 1.
+ *   6. Blank frame.  With history and no restart only `changed` is written, as 0: a fade through black says nothing.  Otherwise the
+ *      state becomes {0, 0, H, 0, W, 0, H, W, 0 x 8}: no bars, nothing known, the next frame that is not blank starts afresh.
+ *   7. Otherwise, each side i on its own, b = m[i], B = the bar the state holds (top, H - bottom, left, W - right; 0 without history):
+ *        on a restart      B = b, cand = b, run = 0
+ *        b <  B            B = b, run = 0                      (picture was seen inside the bar: it is given back at once)
+ *        b == B            run = 0
+ *        b >  B            cand = (run == 0) ? b : min(cand, b);  run += 1;  if run >= hold: B = cand, run = 0
+ *      so a bar grows only after `hold` consecutive frames that agree on at least that much, and to the least of them; hold = 1
+ *      takes every frame on its own.  state = {1, B0, H - B1, B2, W - B3, changed, H, W, cand, run}; changed = 1 when the rectangle
+ *      differs from the one the state held (the whole frame, without history), else 0.
+ * The rectangle is rows [top, bottom) and columns [left, right): the state's words 1 .. 4, which is what every consumer below takes
+ * as four ints in device memory.
+ * stm_active_detect takes the image in host memory and the state in and out, and returns `changed` (-1 on an error).
+ * stm_d_active_detect takes device pointers, synchronises nothing, reads d_cut_state (may be null) on the device and writes the
+ * counts into d_counts (H + W words, rows first) where it is not null.
+ * Rules: num_rows, num_cols >= 1, num_rows * num_cols < 2^31, elem_sz >= 3, thresh_luma in 0 .. 254, lit_permille in 0 .. 999,
+ * max_bar_permille in 0 .. 450, hold in 1 .. 2^20, no null image or state.  Violations fail through stm_last_error before anything is
+ * launched or written.  Parity is against the numpy statement of these lines in tests/test_active_ref.py (parity unpinned).
+ *
+ * stm_active_fill: every pixel of disp (f32, num_rows x num_cols) outside the rectangle becomes `value`, bit for bit; the pixels
+ * inside are not touched, NaNs included.  One launch that visits the four strips only; a full rectangle writes nothing, and so does
+ * a null one.  The device flavour reads the four ints on the device, clamped to the map (no store can leave it), the host flavour
+ * takes four host ints under the rule 0 <= top < bottom <= num_rows, 0 <= left < right <= num_cols.
+ *
+ * stm_depth_fit_rect is stm_depth_fit with only the pixels of both maps inside the rectangle counted, so n = twice its area; a null
+ * rectangle is stm_depth_fit itself, launch for launch.  stm_overlay_fit_rect is stm_overlay_fit with one line after step 2: the map
+ * rectangle is moved into the active one, per axis, with [a, b) the footprint's interval and [A, B) the active one:
+ *      if max(a, A) < min(b, B): [max(a, A), min(b, B));  else len = min(b - a, B - A) and [A, A + len) where b <= A, [B - len, B)
+ *      where a >= B
+ * so a subtitle that lies wholly in the bottom bar is placed by the picture rows nearest to it, not left unplaced.  Steps 3 to 6 are
+ * unchanged; a null rectangle is stm_overlay_fit itself.  In both, the device flavour takes the rectangle in device memory (clamped
+ * to the map as above), the host flavour four host ints under stm_active_fill's rule. */
+int  stm_active_detect(const unsigned char *img_l, int num_rows, int num_cols, int elem_sz, int thresh_luma, int lit_permille,
+                       int max_bar_permille, int hold, int restart, int *state);
+void stm_d_active_detect(const unsigned char *d_img_l, int num_rows, int num_cols, int elem_sz, int thresh_luma, int lit_permille,
+                         int max_bar_permille, int hold, int restart, int *d_state, const int *d_cut_state, unsigned int *d_counts);
+void stm_active_fill(float *disp, int num_rows, int num_cols, const int *rect, float value);
+void stm_d_active_fill(float *d_disp, int num_rows, int num_cols, const int *d_rect, float value);
+void stm_depth_fit_rect(float *disp_l, float *disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
+                        int clip_permille, float rate, float *state, const int *rect);
+void stm_d_depth_fit_rect(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
+                          int clip_permille, float rate, float *d_state, const int *d_rect);
+void stm_overlay_fit_rect(float *disp_l, float *disp_r, int num_rows, int num_cols, const unsigned char *overlay, int ov_rows, int ov_cols,
+                          int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin, int pad,
+                          float limit_lo, float limit_hi, float rate_near, float rate_far, int restart, float *state, const int *rect);
+void stm_d_overlay_fit_rect(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, const unsigned char *d_overlay, int ov_rows,
+                            int ov_cols, int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin,
+                            int pad, float limit_lo, float limit_hi, float rate_near, float rate_far, int restart, float *d_state,
+                            const int *d_cut_state, const int *d_rect);
 /* View antialiasing: the depth-adaptive prefilter of one image by its own map (an addition, the reference has none: each of its views
  * is a pinhole image at one camera position s, while a lenticular lens shows a band about one view spacing wide.  A scene point of
  * displayed end-to-end disparity e moves e / (N - 1) pixels between adjacent views, so detail finer than that step aliases between
@@ -1407,6 +1506,20 @@ int   stm_stream_set_cut(void *stream, int mode, int thresh_permille, int min_ga
 /* out = {cut, score, since} of the most recently collected frame (12 bytes copied per slot after the decision and downloaded with
  * the results, as stm_stream_depth's); in mode 0 {0, 0, 0}.  Returns 0, or -1 if no frame has been collected yet. */
 int   stm_stream_cut(void *stream, int out[3]);
+/* the active picture area of the stream's frames (stm_set_active's and stm_set_active_auto's rules in one call; the default is mode
+ * 0, and the calling thread's own setting never reaches a stream's frames).  Mode 1's rectangle is screened against the stream's
+ * num_rows x num_cols here.  The state is the stream's own: 16 ints at a fixed address, zeroed when mode 2 is set, so the slots'
+ * captured graphs stay valid and replay the measurement, the fill and both fits.  The cut state mode 2 reads is the stream's own
+ * (stm_stream_set_cut); it is resolved at submit, so the setters may come in any order.  Frame k reads what frame k - 1 wrote, so
+ * with mode 2 the two frames in flight run one after the other on the GPU, as with the cut detector.  The stream's automatic overlay
+ * placement (stm_stream_set_overlay_auto) is fitted under the rectangle in modes 1 and 2.  Only before the first submit.  Returns 0,
+ * or -1 with stm_last_error set and the stream unchanged. */
+int   stm_stream_set_active(void *stream, int mode, const int rect[4], int fill, float fill_disp, int thresh_luma, int lit_permille,
+                            int max_bar_permille, int hold);
+/* out = {top, bottom, left, right, changed} of the most recently collected frame (20 bytes copied per slot after the decision and
+ * downloaded with the results, as stm_stream_cut's); in mode 1 the given rectangle and 0, in mode 0 the whole frame and 0.  Returns
+ * 0, or -1 if no frame has been collected yet. */
+int   stm_stream_active(void *stream, int out[5]);
 /* waits for the oldest uncollected frame and copies its results out (NULL = skip).  Returns its index or -1. */
 long  stm_stream_collect(void *stream, float *disp_l, float *disp_r, unsigned char *interlaced);
 /* zero-copy variants (at 1080p the two host copies of submit / collect take longer than the frame does on the GPU):

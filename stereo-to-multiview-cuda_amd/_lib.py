@@ -63,6 +63,9 @@ PROTOS = {
     "stm_get_balance": ([C.POINTER(C.c_int), f32p, u8p], None),
     "stm_set_cut": ([i, i, i, vp], i),
     "stm_get_cut": ([C.POINTER(C.c_int)], None),
+    "stm_set_active": ([i, C.POINTER(C.c_int), i, f], i),
+    "stm_set_active_auto": ([i, i, i, i, vp], i),
+    "stm_get_active": ([C.POINTER(C.c_int), f32p], None),
     "stm_ci_adcensus": ([u8p, u8p, f32pp, f32pp, f, f, i, i, i, i, i], None),
     "stm_d_ci_adcensus": ([vp, vp, vp, vp, f32pp, f32pp, vp, f, f, i, i, i, i, i], None),
     "stm_ca_cross": ([u8p, u8pp, f32pp, f32pp, f, f, i, i, i, i, i, i], None),
@@ -149,6 +152,14 @@ PROTOS = {
     "stm_d_balance_apply": ([vp, vp, i, i, i, u8p, vp], None),
     "stm_cut_detect": ([u8p, i, i, i, i, i, C.POINTER(C.c_int)], i),
     "stm_d_cut_detect": ([vp, i, i, i, i, i, vp, vp, vp, vp, vp], None),
+    "stm_active_detect": ([u8p, i, i, i, i, i, i, i, i, C.POINTER(C.c_int)], i),
+    "stm_d_active_detect": ([vp, i, i, i, i, i, i, i, i, vp, vp, vp], None),
+    "stm_active_fill": ([f32p, i, i, C.POINTER(C.c_int), f], None),
+    "stm_d_active_fill": ([vp, i, i, vp, f], None),
+    "stm_depth_fit_rect": ([f32p, f32p, i, i, f, f, f, i, f, f32p, C.POINTER(C.c_int)], None),
+    "stm_d_depth_fit_rect": ([vp, vp, i, i, f, f, f, i, f, vp, vp], None),
+    "stm_overlay_fit_rect": ([f32p, f32p, i, i, u8p, i, i, i, i, i, i, f, f, i, f, i, f, f, f, f, i, f32p, C.POINTER(C.c_int)], None),
+    "stm_d_overlay_fit_rect": ([vp, vp, i, i, vp, i, i, i, i, i, i, f, f, i, f, i, f, f, f, f, i, vp, vp, vp], None),
     "stm_view_prefilter": ([u8p, u8p, f32p, i, i, i, i, f, i, f, f, f], None),
     "stm_d_view_prefilter": ([vp, vp, vp, i, i, i, i, f, i, f, f, f], None),
     "stm_d_tx_scale": ([u8p, u8p, i, i, i, i, i], None),
@@ -178,6 +189,8 @@ PROTOS = {
     "stm_stream_balance": ([C.c_void_p, u8p], i),
     "stm_stream_set_cut": ([C.c_void_p, i, i, i], i),
     "stm_stream_cut": ([C.c_void_p, C.POINTER(C.c_int)], i),
+    "stm_stream_set_active": ([C.c_void_p, i, C.POINTER(C.c_int), i, f, i, i, i, i], i),
+    "stm_stream_active": ([C.c_void_p, C.POINTER(C.c_int)], i),
     "stm_stream_collect": ([C.c_void_p, f32p, f32p, u8p], C.c_long),
     "stm_stream_input_buffer": ([C.c_void_p], C.c_void_p),
     "stm_stream_collect_view": ([C.c_void_p, C.POINTER(f32p), C.POINTER(f32p), C.POINTER(u8p)], C.c_long),

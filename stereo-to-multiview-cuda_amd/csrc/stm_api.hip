@@ -372,12 +372,12 @@ void stm::frame_overlay(u8 *d_frame, const Overlay &ov, const Lens &ln, const La
 // not measured either
 void stm::frame_overlay_auto(u8 *d_frame, const Overlay &ov, const OverlayAuto &oa, float *state, uint32_t *ws, bool fresh, bool zero_state, const float *d_disp_l,
                              const float *d_disp_r, int H, int W, const Depth &dp, const float *depth_state, const int *cut_state, const Lens &ln,
-                             const Layout &lo, int num_views, float angle, int Hout, int Wout, int elem_sz)
+                             const Layout &lo, int num_views, float angle, int Hout, int Wout, int elem_sz, const int *d_rect)
 {
     if (lo.layout == 0 && ln.mode == 0 && !mux_geom_ok(num_views, angle, elem_sz, nullptr, nullptr, nullptr)) return;
     const int Hv = lo.layout == 1 ? Hout / lo.tiles_y : Hout, Wv = lo.layout == 1 ? Wout / lo.tiles_x : Wout;
     launch_overlay_fit(state, ws, d_disp_l, d_disp_r, H, W, ov.d_overlay, ov.ov_rows, ov.ov_cols, ov.x0, ov.y0, Hv, Wv, dp.mode == 1 ? dp.gain : 1.0f,
-                       dp.mode == 1 ? dp.conv : 0.0f, dp.mode == 2 ? depth_state : nullptr, oa, fresh, zero_state, cut_state);
+                       dp.mode == 1 ? dp.conv : 0.0f, dp.mode == 2 ? depth_state : nullptr, oa, fresh, zero_state, cut_state, d_rect);
     Overlay at = ov;
     at.d_disp = state + 1;
     at.limit_lo = oa.limit_lo;
@@ -1235,6 +1235,134 @@ int stm_cut_detect(const unsigned char *img_l, int num_rows, int num_cols, int e
     return failed() ? -1 : state[1];
 }
 
+// =============================================================== active picture area: measured and applied as stages
+// (an addition, the reference has none: it matches and measures black bars as if they were picture)
+static bool active_args_ok(const char *fn, const unsigned char *img_l, int num_rows, int num_cols, int elem_sz, int thresh_luma, int lit_permille,
+                           int max_bar_permille, int hold, const int *state)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
+    if (!active_size_ok(fn, num_rows, num_cols) || !active_auto_params_ok(fn, thresh_luma, lit_permille, max_bar_permille, hold)) return false;
+    if (!img_l || !state) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "%s: img_l and state must not be null", fn);
+        fail(msg, "img_l, state", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
+void stm_d_active_detect(const unsigned char *d_img_l, int num_rows, int num_cols, int elem_sz, int thresh_luma, int lit_permille,
+                         int max_bar_permille, int hold, int restart, int *d_state, const int *d_cut_state, unsigned int *d_counts)
+{
+    if (!active_args_ok("d_active_detect", d_img_l, num_rows, num_cols, elem_sz, thresh_luma, lit_permille, max_bar_permille, hold, d_state)) return;
+    const size_t words = (size_t)num_rows + num_cols;
+    Workspace::begin(words * 4 + 8192);
+    uint32_t *counts = d_counts ? d_counts : Workspace::get<uint32_t>(words);
+    launch_active_detect(d_state, counts, nullptr, d_img_l, num_rows, num_cols, elem_sz, thresh_luma, lit_permille, max_bar_permille, hold,
+                         restart != 0, d_cut_state);
+}
+int stm_active_detect(const unsigned char *img_l, int num_rows, int num_cols, int elem_sz, int thresh_luma, int lit_permille, int max_bar_permille,
+                      int hold, int restart, int *state)
+{
+    if (!active_args_ok("active_detect", img_l, num_rows, num_cols, elem_sz, thresh_luma, lit_permille, max_bar_permille, hold, state)) return -1;
+    const size_t IMG = (size_t)num_rows * num_cols * elem_sz, words = (size_t)num_rows + num_cols;
+    Workspace::begin(IMG + (words + ACTIVE_STATE_WORDS) * 4 + 8192);
+    const u8 *l = up(img_l, IMG);
+    int *st = up(state, ACTIVE_STATE_WORDS);
+    uint32_t *counts = Workspace::get<uint32_t>(words);
+    launch_active_detect(st, counts, nullptr, l, num_rows, num_cols, elem_sz, thresh_luma, lit_permille, max_bar_permille, hold, restart != 0, nullptr);
+    down(state, st, ACTIVE_STATE_WORDS);
+    sync();
+    return failed() ? -1 : state[5];
+}
+static bool active_fill_args_ok(const char *fn, const float *disp, int num_rows, int num_cols)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}})) return false;
+    if (!disp) {
+        char msg[120];
+        snprintf(msg, sizeof msg, "%s: disp must not be null", fn);
+        fail(msg, "disp", __FILE__, __LINE__);
+        return false;
+    }
+    return true;
+}
+void stm_d_active_fill(float *d_disp, int num_rows, int num_cols, const int *d_rect, float value)
+{
+    if (!active_fill_args_ok("d_active_fill", d_disp, num_rows, num_cols)) return;
+    if (!d_rect) return; // the whole map is picture: nothing to write
+    float *m[1] = {d_disp};
+    launch_active_fill(1, m, num_rows, num_cols, d_rect, value);
+}
+void stm_active_fill(float *disp, int num_rows, int num_cols, const int *rect, float value)
+{
+    if (!active_fill_args_ok("active_fill", disp, num_rows, num_cols)) return;
+    if (!rect) return;
+    if (!active_rect_ok("active_fill", rect, num_rows, num_cols)) return;
+    const size_t HW = (size_t)num_rows * num_cols;
+    Workspace::begin(4 * HW + 8192);
+    float *d = up(disp, HW);
+    const int *rc = up(rect, 4);
+    float *m[1] = {d};
+    launch_active_fill(1, m, num_rows, num_cols, rc, value);
+    down(disp, d, HW);
+    sync();
+}
+void stm_d_depth_fit_rect(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
+                          int clip_permille, float rate, float *d_state, const int *d_rect)
+{
+    if (!depth_fit_args_ok("d_depth_fit_rect", num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate)) return;
+    Workspace::begin(4096 * 4 + 8192);
+    uint32_t *hist = Workspace::get<uint32_t>(4096);
+    launch_depth_fit(d_state, hist, d_disp_l, d_disp_r, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, false, d_rect);
+}
+void stm_depth_fit_rect(float *disp_l, float *disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
+                        int clip_permille, float rate, float *state, const int *rect)
+{
+    if (!depth_fit_args_ok("depth_fit_rect", num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate)) return;
+    if (rect && !active_rect_ok("depth_fit_rect", rect, num_rows, num_cols)) return;
+    const size_t HW = (size_t)num_rows * num_cols;
+    Workspace::begin(8 * HW + 4096 * 4 + 8192);
+    float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *st = up(state, 4);
+    const int *rc = rect ? up(rect, 4) : nullptr;
+    uint32_t *hist = Workspace::get<uint32_t>(4096);
+    launch_depth_fit(st, hist, dl, dr, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, false, rc);
+    down(state, st, 4);
+    sync();
+}
+void stm_d_overlay_fit_rect(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, const unsigned char *d_overlay, int ov_rows,
+                            int ov_cols, int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin,
+                            int pad, float limit_lo, float limit_hi, float rate_near, float rate_far, int restart, float *d_state,
+                            const int *d_cut_state, const int *d_rect)
+{
+    if (!overlay_fit_args_ok("d_overlay_fit_rect", d_overlay, true, num_rows, num_cols, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv,
+                             near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far))
+        return;
+    Workspace::begin(OVERLAY_FIT_WS_WORDS * 4 + 8192);
+    uint32_t *ws = Workspace::get<uint32_t>(OVERLAY_FIT_WS_WORDS);
+    const OverlayAuto oa = {1, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, d_state};
+    launch_overlay_fit(d_state, ws, d_disp_l, d_disp_r, num_rows, num_cols, d_overlay, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv,
+                       nullptr, oa, restart != 0, false, d_cut_state, d_rect);
+}
+void stm_overlay_fit_rect(float *disp_l, float *disp_r, int num_rows, int num_cols, const unsigned char *overlay, int ov_rows, int ov_cols,
+                          int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin, int pad,
+                          float limit_lo, float limit_hi, float rate_near, float rate_far, int restart, float *state, const int *rect)
+{
+    if (!overlay_fit_args_ok("overlay_fit_rect", overlay, false, num_rows, num_cols, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv,
+                             near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far))
+        return;
+    if (rect && !active_rect_ok("overlay_fit_rect", rect, num_rows, num_cols)) return;
+    const size_t HW = (size_t)num_rows * num_cols, ov_sz = (size_t)ov_rows * ov_cols * 4;
+    Workspace::begin(8 * HW + ov_sz + OVERLAY_FIT_WS_WORDS * 4 + 8192);
+    float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *st = up(state, 4);
+    const u8 *o = up((unsigned char *)overlay, ov_sz);
+    const int *rc = rect ? up(rect, 4) : nullptr;
+    uint32_t *ws = Workspace::get<uint32_t>(OVERLAY_FIT_WS_WORDS);
+    const OverlayAuto oa = {1, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, st};
+    launch_overlay_fit(st, ws, dl, dr, num_rows, num_cols, o, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv, nullptr, oa, restart != 0,
+                       false, nullptr, rc);
+    down(state, st, 4);
+    sync();
+}
+
 // =============================================================== view antialiasing: the prefilter as a stage
 // (an addition, the reference has none: its views are pinhole images whatever the lens shows of them)
 static bool prefilter_args_ok(const char *fn, const unsigned char *img_out, const unsigned char *img, const float *disp, int num_rows,
@@ -1869,7 +1997,9 @@ bool frame_layout_ok(const char *fn, const FrameArgs &a)
 
 // hit maps -> bleed -> masks -> N-2 views -> interlace (d_io.cu:160-205)
 // depth_state_out: where depth mode 2's state lies, the workspace's four floats included (null in the other modes)
-void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_interlaced, const FrameArgs &a, float **depth_state_out)
+// d_rect: the active rectangle mode 2's fit is restricted to (stm_set_active), or null
+void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_interlaced, const FrameArgs &a, float **depth_state_out,
+                  const int *d_rect)
 {
     *depth_state_out = nullptr;
     const int H = a.num_rows, W = a.num_cols, Hout = a.num_rows_out, Wout = a.num_cols_out, elem_sz = a.elem_sz, N = a.num_views;
@@ -1903,7 +2033,7 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
         uint32_t *hist = Workspace::get<uint32_t>(4096);
         state = dp.d_state ? dp.d_state : Workspace::get<float>(4);
         launch_depth_fit(state, hist, d_disp_l, d_disp_r, H, W, dp.disp_lo, dp.disp_hi, dp.max_gain, dp.clip_permille, dp.rate,
-                         dp.d_state == nullptr);
+                         dp.d_state == nullptr, d_rect);
         *depth_state_out = state;
     }
     // view antialiasing (stm_set_antialias): both images filtered by their own maps into fresh workspace, and every renderer below
@@ -2100,13 +2230,49 @@ void cut_frame_input(const Cut &ct, const PackInput &in, int H, int W, int elem_
                       bal.mode == 2 ? (void *)bal.d_state : nullptr);
 }
 
+// ---- the active picture area of a frame call's input (stm_set_active), after the cut detector and before the alignment
+// the thread's setting against a frame call's geometry; off: nothing to check, the call is as it was
+bool frame_active_ok(const char *fn, int num_rows, int num_cols)
+{
+    const Active ac = active();
+    if (!ac.mode) return true;
+    return ac.mode == 1 ? active_rect_ok(fn, ac.rect, num_rows, num_cols) : active_size_ok(fn, num_rows, num_cols);
+}
+// the counts, a scratch state and the rectangle's four words
+size_t active_ws_bytes(int num_rows, int num_cols) { return ((size_t)num_rows + num_cols + ACTIVE_STATE_WORDS + 4) * 4 + 1024; }
+// The prelude, inside the frame call's Workspace scope: mode 2 runs the three launches on the screened full-resolution frame `in`
+// (the left eye is the reference of the alignment and the balance, so the result depends on neither) and the rectangle is the
+// state's words 1 .. 4; mode 1 writes the given rectangle into four workspace words.  Either way the consumers read it on the device.
+const int *active_frame_input(const Active &ac, const Cut &ct, const PackInput &in, int H, int W, int elem_sz)
+{
+    if (ac.mode == 1) {
+        int *rect = Workspace::get<int>(4);
+        launch_active_rect(rect, ac.rect);
+        return rect;
+    }
+    int *state = ac.d_state ? ac.d_state : Workspace::get<int>(ACTIVE_STATE_WORDS); // scratch: every frame on its own
+    uint32_t *counts = Workspace::get<uint32_t>((size_t)H + W);
+    launch_active_detect(state, counts, &in, nullptr, H, W, elem_sz, ac.thresh_luma, ac.lit_permille, ac.max_bar_permille, ac.hold,
+                         ac.d_state == nullptr, ct.mode ? ct.d_state : nullptr);
+    return state + 1;
+}
+// with `fill` on, both maps a frame call hands back take fill_disp outside the rectangle: after the temporal step, before the tail
+void frame_active_fill(const int *d_rect, float *d_disp_l, float *d_disp_r, int H, int W)
+{
+    const Active ac = active();
+    if (!ac.mode || !ac.fill || !d_rect) return;
+    float *m[2] = {d_disp_l, d_disp_r};
+    launch_active_fill(2, m, H, W, d_rect, ac.fill_disp);
+}
+
 // ---- the input prelude of a frame call: the thread's shot-change detector, alignment and balance ahead of the front
 // the three settings against a frame call's geometry, alignment first; nv: the call's NV12 input or null
 bool frame_settings_ok(const char *fn, const FrameArgs &a, const Nv12Input *nv)
 {
     const bool bgr_sbs = !nv && !packing().on(); // both eyes are gathered from a side-by-side BGR frame
     return frame_align_ok(fn, a.num_rows, a.num_cols_sbs, a.num_cols, bgr_sbs) &&
-           frame_balance_ok(fn, a.num_rows, a.num_cols_sbs, a.num_cols, bgr_sbs) && frame_cut_ok(fn, a.num_rows, a.num_cols);
+           frame_balance_ok(fn, a.num_rows, a.num_cols_sbs, a.num_cols, bgr_sbs) && frame_cut_ok(fn, a.num_rows, a.num_cols) &&
+           frame_active_ok(fn, a.num_rows, a.num_cols);
 }
 // what the thread's settings add to a frame body's Workspace::begin; prev: a side-by-side history goes through the prelude too
 size_t frame_settings_ws_bytes(const FrameArgs &a, bool prev)
@@ -2117,6 +2283,7 @@ size_t frame_settings_ws_bytes(const FrameArgs &a, bool prev)
            (align().mode ? align_ws_bytes(a.num_rows, IMG, prev) : 0) +                        // the aligned frame(s)
            (balance().mode ? balance_ws_bytes(IMG, prev) : 0) +                                // the balanced frame(s)
            (cut().mode ? cut_ws_bytes() : 0) +                                                 // the detector's signature
+           (active().mode ? active_ws_bytes(a.num_rows, a.num_cols) : 0) +                     // the active area's counts, state and rectangle
            (overlay().mode == 1 && overlay_auto().mode == 1 ? OVERLAY_FIT_WS_WORDS * 4 + 16 + 1024 : 0); // the overlay fit's bins, box and scratch state
 }
 // what the front and the temporal step of a frame body read, after the prelude
@@ -2128,6 +2295,7 @@ struct FrameInput {
     bool pack_on;           // the frame is still packed: the front unpacks it
     bool split_hist;        // an NV12 call: its history comes as split images, used as they are passed
     PackInput pin;          // the frame as the call was given it
+    const int *rect;        // the active rectangle's four words in device memory (stm_set_active), null with the setting off
 };
 // The prelude, inside the frame call's Workspace scope and after the split images (and the reduced pair) have been carved: cut,
 // then align, then balance, each where its setting is on.  After an alignment or a balance the call is the plain BGR frame call on
@@ -2141,8 +2309,10 @@ FrameInput frame_input(const FrameArgs &a, const u8 *d_img_sbs, const Nv12Input 
     const Cut ct = cut();
     FrameInput in = {d_img_sbs, a.num_cols_sbs, nv, hist ? hist->sbs : nullptr, pack.on() && !aln.mode && !bal.mode, nv != nullptr,
                      {pack, nv != nullptr, d_img_sbs, a.num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr, nv ? nv->pitch_y : 0,
-                      nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0}};
+                      nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0}, nullptr};
     if (ct.mode) cut_frame_input(ct, in.pin, H, W, elem_sz, (a.stages & 0xff) >= 3, aln, bal); // before any state's fit runs
+    const Active ac = active();
+    in.rect = ac.mode ? active_frame_input(ac, ct, in.pin, H, W, elem_sz) : nullptr; // after the cut flag, on the input as given
     const bool sbs_hist = hist && !in.split_hist;
     if (aln.mode) { // from here on the call is the plain BGR frame call on the aligned side-by-side frame
         const u8 *prev = nullptr;
@@ -2190,10 +2360,11 @@ void frame_temporal(const FrameArgs &a, const FrameInput &in, const TemporalHist
 // the tail of a rendering frame call: the renderer, then the thread's overlay (stm_set_overlay) composited on the finished frame --
 // the call's last launch.  With stm_set_overlay_auto on, the overlay's disparity is first fitted to the maps the renderer read, under
 // the depth budget it rendered with and the thread's cut state, and the compositor reads it from the state on the device
-void frame_tail(const FrameArgs &a, u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_interlaced)
+// d_rect: the active rectangle the two fits read on the device (stm_set_active), or null
+void frame_tail(const FrameArgs &a, u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_interlaced, const int *d_rect)
 {
     float *depth_state = nullptr;
-    frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, a, &depth_state);
+    frame_render(img_l, img_r, d_disp_l, d_disp_r, d_interlaced, a, &depth_state, d_rect);
     if (overlay().mode != 1) return;
     const OverlayAuto oa = overlay_auto();
     if (oa.mode != 1) {
@@ -2205,7 +2376,7 @@ void frame_tail(const FrameArgs &a, u8 *img_l, u8 *img_r, float *d_disp_l, float
     const Cut ct = cut();
     frame_overlay_auto(d_interlaced, overlay(), oa, state, ws, oa.d_state == nullptr, oa.d_state == nullptr, d_disp_l, d_disp_r, a.num_rows,
                        a.num_cols, depth(), depth_state, ct.mode ? ct.d_state : nullptr, lens(), layout(), a.num_views, a.angle, a.num_rows_out,
-                       a.num_cols_out, a.elem_sz);
+                       a.num_cols_out, a.elem_sz, d_rect);
 }
 
 // the body of stm_d_adcensus_stm, stm_d_adcensus_stm_t and stm_d_adcensus_stm_nv12; hist != nullptr: the temporal step between
@@ -2274,7 +2445,8 @@ void frame_device(const char *fn, const FrameArgs &a, const u8 *d_img_sbs, float
     }
     frame_disparity(img_l, img_r, d_disp_l, d_disp_r, H, W, a, (stages & 0xff) >= 2, fused_split ? pre : nullptr);
     if (hist) frame_temporal(a, in, *hist, img_l, img_r, d_disp_l, d_disp_r);
-    if ((stages & 0xff) >= 3) frame_tail(a, img_l, img_r, d_disp_l, d_disp_r, d_interlaced);
+    frame_active_fill(in.rect, d_disp_l, d_disp_r, H, W);
+    if ((stages & 0xff) >= 3) frame_tail(a, img_l, img_r, d_disp_l, d_disp_r, d_interlaced, in.rect);
 }
 
 // ---- the screens of the frame entries
@@ -2444,7 +2616,8 @@ void reduced_frame_device(const char *fn, const FrameArgs &a, const u8 *d_img_sb
         launch_disp_scale(d_disp_r, low_dr, H, W, h, w, up);
     }
     if (hist) frame_temporal(a, in, *hist, img_l, img_r, d_disp_l, d_disp_r);
-    frame_tail(a, img_l, img_r, d_disp_l, d_disp_r, d_interlaced);
+    frame_active_fill(in.rect, d_disp_l, d_disp_r, H, W);
+    frame_tail(a, img_l, img_r, d_disp_l, d_disp_r, d_interlaced, in.rect);
 }
 
 // the host flavour of the reference's three frame calls: the screens, before the caller's arrays are written; the arrays staged in

@@ -407,15 +407,15 @@ constexpr size_t OVERLAY_FIT_WS_WORDS = 4096 + 4; // the histogram, then the alp
 // the measurement (stm_kernels_ovfit.hip): the alpha box of `ov`, both maps (H x W) under its footprint in the view Hv x Wv into the
 // histogram, the fit and the update of `state` (four floats).  The budget is (gain, conv), or depth_state[1], depth_state[2] read on
 // the device where depth_state != nullptr; fresh: the state's history is ignored; zero_state: `state` is scratch, zeroed first;
-// cut_state: the detector's state or null
+// cut_state: the detector's state or null; d_rect: the active rectangle (four ints in device memory) the footprint is moved into, or null
 void launch_overlay_fit(float *state, uint32_t *ws, const float *disp_l, const float *disp_r, int H, int W, const u8 *ov, int ov_rows,
                         int ov_cols, int x0, int y0, int Hv, int Wv, float gain, float conv, const float *depth_state, const OverlayAuto &oa,
-                        bool fresh, bool zero_state, const int *cut_state);
+                        bool fresh, bool zero_state, const int *cut_state, const int *d_rect = nullptr);
 // stm_api.hip: the fit of the overlay `ov` on a frame's maps under layout lo, then the overlay composited at the state's disparity;
 // state: oa.d_state, or four floats of scratch (zero_state).  The frame calls' tail with the thread's settings, and a frame stream's with its own
 void frame_overlay_auto(u8 *d_frame, const Overlay &ov, const OverlayAuto &oa, float *state, uint32_t *ws, bool fresh, bool zero_state, const float *d_disp_l,
                         const float *d_disp_r, int H, int W, const Depth &dp, const float *depth_state, const int *cut_state, const Lens &ln,
-                        const Layout &lo, int num_views, float angle, int Hout, int Wout, int elem_sz);
+                        const Layout &lo, int num_views, float angle, int Hout, int Wout, int elem_sz, const int *d_rect = nullptr);
 // View antialiasing (stm_set_antialias, include/stm_hip.h): mode 0 = off, 1 = every rendering frame call filters both images by
 // their own maps (stm_view_prefilter's rule) before it renders from them.  One per host thread, next to the depth budget; a frame
 // stream installs its own copy around its frame calls (stm_stream_set_antialias).
@@ -434,9 +434,10 @@ bool antialias_params_ok(const char *fn, float strength, int max_radius, float g
 void launch_view_prefilter(int nimg, u8 *const *out, const u8 *const *in, const float *const *disp, int H, int W, int elem_sz, int num_views,
                            float strength, int max_radius, float gate, float gain, float conv, const float *state);
 // the measurement (stm_kernels_depth.hip): both maps into the 4096-bin histogram `hist` (scratch), the fit, the update of `state`
-// (four floats); fresh: the state's history is ignored
+// (four floats); fresh: the state's history is ignored; d_rect: the active rectangle (four ints in device memory) the count is
+// restricted to, or null
 void launch_depth_fit(float *state, uint32_t *hist, const float *disp_l, const float *disp_r, int H, int W, float disp_lo, float disp_hi,
-                      float max_gain, int clip_permille, float rate, bool fresh);
+                      float max_gain, int clip_permille, float rate, bool fresh, const int *d_rect = nullptr);
 // The vertical alignment of the pair (stm_set_align / stm_set_align_auto, include/stm_hip.h): mode 0 = off (not one launch changes),
 // 1 = manual (the field a, b, c), 2 = automatic (the field measured on each frame on the device).  One per host thread, next to the
 // depth budget; a frame stream installs its own copy around its frame calls.
@@ -514,6 +515,38 @@ constexpr int CUT_DEFAULT_THRESH = 370; // the geometric mean
 // non-null reset pointer
 void launch_cut_detect(int *state, uint32_t *sig, const PackInput *in, const u8 *img_l, int H, int W, int elem_sz, int thresh_permille,
                        int min_gap, void *reset0, void *reset1, void *reset2);
+// The active picture area (stm_set_active / stm_set_active_auto, include/stm_hip.h): mode 0 = off (not one launch changes), 1 = a
+// given rectangle, 2 = measured on each frame's left eye on the device.  The depth fit and the overlay fit of a frame call read the
+// rectangle on the device; with `fill` the maps handed back take fill_disp outside it.  One per host thread, next to the cut
+// detector; a frame stream installs its own copy around its frame calls.
+struct Active {
+    int mode;
+    int rect[4];        // mode 1: {top, bottom, left, right}, rows [top, bottom) and columns [left, right)
+    int fill;
+    float fill_disp;
+    int thresh_luma, lit_permille, max_bar_permille, hold; // mode 2
+    int *d_state;       // mode 2: the 16 ints of stm_active_detect in device memory; null = scratch, every frame on its own
+};
+Active active_default();
+Active active();
+void set_active(const Active &a);
+// the argument rules of the two settings; false with the error recorded
+bool active_params_ok(const char *fn, int mode, const int *rect, int fill, float fill_disp);
+bool active_auto_params_ok(const char *fn, int thresh_luma, int lit_permille, int max_bar_permille, int hold);
+// the measurement's frame rule: num_rows * num_cols < 2^31; false with the error recorded
+bool active_size_ok(const char *fn, int num_rows, int num_cols);
+// a rectangle against a map: 0 <= top < bottom <= num_rows and 0 <= left < right <= num_cols; false with the error recorded
+bool active_rect_ok(const char *fn, const int *rect, int num_rows, int num_cols);
+constexpr size_t ACTIVE_STATE_WORDS = 16;
+// the measurement (stm_kernels_active.hip) on the left eye of a screened frame (in != nullptr) or on one unpacked image
+// H x W x elem_sz: the lit pixels per row and column into counts (H + W words), the decision and the update of `state` (16 ints);
+// restart: the state's history is ignored; cut_state: the shot-change detector's state or null
+void launch_active_detect(int *state, uint32_t *counts, const PackInput *in, const u8 *img_l, int H, int W, int elem_sz, int thresh_luma,
+                          int lit_permille, int max_bar_permille, int hold, bool restart, const int *cut_state);
+// a given rectangle's four words written to d_rect by a kernel (no copy node, nothing the host must keep alive)
+void launch_active_rect(int *d_rect, const int rect[4]);
+// disp[i] (H x W), i < nmaps (1 or 2), takes `value` outside the rectangle d_rect holds; one launch over the four strips
+void launch_active_fill(int nmaps, float *const *disp, int H, int W, const int *d_rect, float value);
 // aggregation on the matrix pipe (stm_kernels_aggm.hip): the frame pipeline's cost -> H -> V, V -> H + WTA
 struct PQViews { // both views of a frame; a / b = the two PQ volumes of a view
     const uint32_t *pk[2], *cen[2];

@@ -69,6 +69,37 @@ __global__ __launch_bounds__(256) void stm_k_disp_hist(uint32_t *__restrict__ hi
     }
 }
 
+// The same count over the pixels of both maps inside the active rectangle only (stm_depth_fit_rect): `rect` holds {top, bottom, left,
+// right} in device memory, clamped to the map here, and the rectangle is walked as one run of rh * rw pixels (its rows keep the
+// map's pitch, so the lanes run along x).  The grid was sized on the host from the whole map, an upper bound: a block whose first
+// tile lies past the run's end does nothing.  H W < 2^31 (screened).
+__global__ __launch_bounds__(256) void stm_k_disp_hist_rect(uint32_t *__restrict__ hist, const float *__restrict__ disp_l,
+                                                            const float *__restrict__ disp_r, int H, int W, const int *__restrict__ rect)
+{
+    __shared__ uint32_t h[DH_BINS];
+    const int t = min(max(rect[0], 0), H), b = min(max(rect[1], t), H), l = min(max(rect[2], 0), W), r = min(max(rect[3], l), W);
+    const uint32_t rw = (uint32_t)(r - l), n = (uint32_t)(b - t) * rw;
+    if (blockIdx.x * 256u >= n) return; // uniform for the block; an empty rectangle counts nothing
+    for (int i = threadIdx.x; i < DH_BINS; i += 256) h[i] = 0;
+    __syncthreads();
+    const uint32_t step = gridDim.x * 256u; // <= 2^18 and base < 2^31: no wrap
+    for (uint32_t base = blockIdx.x * 256u; base < n; base += step) {
+        const uint32_t i = base + threadIdx.x;
+        const bool valid = i < n;
+        const uint32_t y = valid ? i / rw : 0u, x = valid ? i - y * rw : 0u;
+        const size_t at = (size_t)(t + (int)y) * W + (size_t)(l + (int)x);
+        const int bl = valid ? depth_bin(disp_l[at]) : 0;
+        const int br = valid ? depth_bin(disp_r[at]) : 0;
+        hist_add(h, bl, valid);
+        hist_add(h, br, valid);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < DH_BINS; i += 256) {
+        const uint32_t c = h[i];
+        if (c) atomicAdd(&hist[i], c);
+    }
+}
+
 struct DepthFitArgs {
     float disp_lo, disp_hi, max_gain, rate;
     int clip_permille;
@@ -148,16 +179,18 @@ __global__ __launch_bounds__(64) void stm_k_depth_fit(float *__restrict__ state,
     state[2] = (float)(oc + t);
 }
 
-// hist: DH_BINS words of scratch; state: four floats {valid, gain, conv, 0}
+// hist: DH_BINS words of scratch; state: four floats {valid, gain, conv, 0}; d_rect: the active rectangle's four words in device
+// memory, or null: the whole maps, with the launches as they always were
 void launch_depth_fit(float *state, uint32_t *hist, const float *disp_l, const float *disp_r, int H, int W, float disp_lo, float disp_hi,
-                      float max_gain, int clip_permille, float rate, bool fresh)
+                      float max_gain, int clip_permille, float rate, bool fresh, const int *d_rect)
 {
     const size_t n = (size_t)H * W;
     const int blocks = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
     {
         ProfScope p("disp_hist");
         STM_LAUNCH(stm_k_disp_hist_clear, dim3(DH_BINS / 256), dim3(256), 0, stream(), hist); // a kernel, not a memset node
-        STM_LAUNCH(stm_k_disp_hist, dim3(blocks), dim3(256), 0, stream(), hist, disp_l, disp_r, n);
+        if (d_rect) STM_LAUNCH(stm_k_disp_hist_rect, dim3(blocks), dim3(256), 0, stream(), hist, disp_l, disp_r, H, W, d_rect);
+        else STM_LAUNCH(stm_k_disp_hist, dim3(blocks), dim3(256), 0, stream(), hist, disp_l, disp_r, n);
         STM_CHECK_LAUNCH();
     }
     ProfScope p("depth_fit");

@@ -70,6 +70,17 @@ __device__ __forceinline__ OvFitRect ovfit_rect(const OvFitGeom &g, const int *_
     r.x0 = (int)(xa * g.W / g.Wv); r.x1 = (int)((xb * g.W + g.Wv - 1) / g.Wv);
     return r;
 }
+// the footprint's interval [a, b) of one axis moved into the active interval [A, B): their intersection where there is one, else as
+// much of the footprint's length as fits, taken from the active end nearest to it (a subtitle that lies wholly in a bar is placed
+// by the picture lines next to it)
+__device__ __forceinline__ void ovfit_slide(int &a, int &b, int A, int B)
+{
+    const int lo = max(a, A), hi = min(b, B);
+    if (lo < hi) { a = lo; b = hi; return; }
+    const int len = min(b - a, B - A);
+    if (b <= A) { a = A; b = A + len; }
+    else { b = B; a = B - len; }
+}
 } // namespace
 
 // ws: OF_BINS words of histogram, then the box {r0, r1, q0, q1}
@@ -132,11 +143,16 @@ __global__ __launch_bounds__(256) void stm_k_ovfit_box(int *__restrict__ box, co
 // of rh * rw pixels in 256-pixel tiles (its rows keep the map's pitch, so the lanes run along x), the grid was sized on the host
 // from the overlay's full rectangle -- an upper bound -- and a block whose first tile lies past the end does nothing.  Counts go
 // into the block's 16 KB LDS histogram; the bins it touched are merged with integer atomics.
-__global__ __launch_bounds__(256) void stm_k_ovfit_hist(uint32_t *__restrict__ ws, const float *__restrict__ disp_l,
-                                                        const float *__restrict__ disp_r, OvFitGeom g)
+// active != nullptr (stm_overlay_fit_rect): the map rectangle is first moved into the active one, per axis.
+__device__ __forceinline__ void ovfit_hist_body(uint32_t *__restrict__ h, uint32_t *__restrict__ ws, const float *__restrict__ disp_l,
+                                                const float *__restrict__ disp_r, const OvFitGeom &g, const int *__restrict__ active)
 {
-    __shared__ uint32_t h[OF_BINS];
-    const OvFitRect rc = ovfit_rect(g, (const int *)ws + OF_BINS);
+    OvFitRect rc = ovfit_rect(g, (const int *)ws + OF_BINS);
+    if (active && rc.y0 < rc.y1 && rc.x0 < rc.x1) { // the four words clamped to the map first: whatever they hold, no load leaves it
+        const int t = min(max(active[0], 0), g.H), b = min(max(active[1], t), g.H), l = min(max(active[2], 0), g.W), r = min(max(active[3], l), g.W);
+        ovfit_slide(rc.y0, rc.y1, t, b);
+        ovfit_slide(rc.x0, rc.x1, l, r);
+    }
     if (rc.y0 >= rc.y1 || rc.x0 >= rc.x1) return; // uniform for the grid
     const uint32_t rw = (uint32_t)(rc.x1 - rc.x0);
     const uint32_t n = (uint32_t)(rc.y1 - rc.y0) * rw; // <= H W < 2^31 (screened)
@@ -159,6 +175,18 @@ __global__ __launch_bounds__(256) void stm_k_ovfit_hist(uint32_t *__restrict__ w
         const uint32_t c = h[i];
         if (c) atomicAdd(&ws[i], c);
     }
+}
+__global__ __launch_bounds__(256) void stm_k_ovfit_hist(uint32_t *__restrict__ ws, const float *__restrict__ disp_l,
+                                                        const float *__restrict__ disp_r, OvFitGeom g)
+{
+    __shared__ uint32_t h[OF_BINS];
+    ovfit_hist_body(h, ws, disp_l, disp_r, g, nullptr);
+}
+__global__ __launch_bounds__(256) void stm_k_ovfit_hist_rect(uint32_t *__restrict__ ws, const float *__restrict__ disp_l,
+                                                             const float *__restrict__ disp_r, OvFitGeom g, const int *__restrict__ active)
+{
+    __shared__ uint32_t h[OF_BINS];
+    ovfit_hist_body(h, ws, disp_l, disp_r, g, active);
 }
 
 struct OvFitArgs {
@@ -231,10 +259,11 @@ __global__ __launch_bounds__(64) void stm_k_ovfit_fit(float *__restrict__ state,
 }
 
 // ws: OVERLAY_FIT_WS_WORDS words of scratch; state: four floats {valid, disparity, nearest, 0}; zero_state: they are scratch and
-// zeroed first (a null d_state: a fit that counts nothing leaves disparity 0).  Screened by the caller
+// zeroed first (a null d_state: a fit that counts nothing leaves disparity 0); d_rect: the active rectangle's four words in device
+// memory, or null: the footprint as it is, with the launches as they always were.  Screened by the caller
 void launch_overlay_fit(float *state, uint32_t *ws, const float *disp_l, const float *disp_r, int H, int W, const u8 *ov, int ov_rows,
                         int ov_cols, int x0, int y0, int Hv, int Wv, float gain, float conv, const float *depth_state, const OverlayAuto &oa,
-                        bool fresh, bool zero_state, const int *cut_state)
+                        bool fresh, bool zero_state, const int *cut_state, const int *d_rect)
 {
     {
         ProfScope p("ovfit_box");
@@ -253,7 +282,9 @@ void launch_overlay_fit(float *state, uint32_t *ws, const float *disp_l, const f
         const long long rows = (yb * H + Hv - 1) / Hv - ya * H / Hv, cols = (xb * W + Wv - 1) / Wv - xa * W / Wv;
         const long long tiles = (rows * cols + 255) / 256;
         ProfScope p("ovfit_hist");
-        STM_LAUNCH(stm_k_ovfit_hist, dim3((unsigned)(tiles < 1024 ? tiles : 1024)), dim3(256), 0, stream(), ws, disp_l, disp_r, g);
+        const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024)); // the slid rectangle is never larger than the footprint's
+        if (d_rect) STM_LAUNCH(stm_k_ovfit_hist_rect, grid, dim3(256), 0, stream(), ws, disp_l, disp_r, g, d_rect);
+        else STM_LAUNCH(stm_k_ovfit_hist, grid, dim3(256), 0, stream(), ws, disp_l, disp_r, g);
         STM_CHECK_LAUNCH();
     }
     ProfScope p("ovfit_fit");

@@ -662,6 +662,76 @@ bool cut_size_ok(const char *fn, int num_rows, int num_cols)
     fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
     return false;
 }
+// the calling thread's active picture area (stm_set_active, stm_set_active_auto)
+Active active_default() { return Active{0, {0, 0, 0, 0}, 0, 0.0f, 24, 10, 300, 12, nullptr}; }
+static thread_local Active g_active = active_default();
+Active active() { return g_active; }
+void set_active(const Active &a) { g_active = a; }
+bool active_params_ok(const char *fn, int mode, const int *rect, int fill, float fill_disp)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (mode < 0 || mode > 2) {
+        snprintf(msg, sizeof msg, "%s: active mode = %d, must be 0 (off), 1 (given) or 2 (measured)", fn, mode);
+        arg = "mode";
+    } else if (mode == 0) { // off: the other arguments are ignored
+        return true;
+    } else if (mode == 1 && !rect) {
+        snprintf(msg, sizeof msg, "%s: rect must not be null in mode 1", fn);
+        arg = "rect";
+    } else if (mode == 1 && !(rect[0] >= 0 && rect[0] < rect[1] && rect[2] >= 0 && rect[2] < rect[3])) {
+        snprintf(msg, sizeof msg, "%s: rect = {%d, %d, %d, %d}, must hold 0 <= top < bottom and 0 <= left < right", fn, rect[0], rect[1], rect[2],
+                 rect[3]);
+        arg = "rect";
+    } else if (fill != 0 && fill != 1) {
+        snprintf(msg, sizeof msg, "%s: fill = %d, must be 0 or 1", fn, fill);
+        arg = "fill";
+    } else if (!(fabsf(fill_disp) <= 4096.0f)) { // NaN fails the comparison
+        snprintf(msg, sizeof msg, "%s: fill_disp = %g, must be finite and of magnitude <= 4096", fn, (double)fill_disp);
+        arg = "fill_disp";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+bool active_auto_params_ok(const char *fn, int thresh_luma, int lit_permille, int max_bar_permille, int hold)
+{
+    char msg[200];
+    const char *arg = nullptr;
+    if (thresh_luma < 0 || thresh_luma > 254) {
+        snprintf(msg, sizeof msg, "%s: thresh_luma = %d, must be in 0 .. 254", fn, thresh_luma);
+        arg = "thresh_luma";
+    } else if (lit_permille < 0 || lit_permille > 999) {
+        snprintf(msg, sizeof msg, "%s: lit_permille = %d, must be in 0 .. 999", fn, lit_permille);
+        arg = "lit_permille";
+    } else if (max_bar_permille < 0 || max_bar_permille > 450) {
+        snprintf(msg, sizeof msg, "%s: max_bar_permille = %d, must be in 0 .. 450", fn, max_bar_permille);
+        arg = "max_bar_permille";
+    } else if (hold < 1 || hold > (1 << 20)) {
+        snprintf(msg, sizeof msg, "%s: hold = %d, must be in 1 .. 1048576", fn, hold);
+        arg = "hold";
+    }
+    if (!arg) return true;
+    fail(msg, arg, __FILE__, __LINE__);
+    return false;
+}
+bool active_size_ok(const char *fn, int num_rows, int num_cols)
+{
+    if ((long long)num_rows * (long long)num_cols < (1ll << 31)) return true;
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: the active area needs num_rows * num_cols < 2147483648 (got %d x %d)", fn, num_rows, num_cols);
+    fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
+    return false;
+}
+bool active_rect_ok(const char *fn, const int *rect, int num_rows, int num_cols)
+{
+    if (rect[0] >= 0 && rect[0] < rect[1] && rect[1] <= num_rows && rect[2] >= 0 && rect[2] < rect[3] && rect[3] <= num_cols) return true;
+    char msg[240];
+    snprintf(msg, sizeof msg, "%s: the active rectangle {%d, %d, %d, %d} must hold 0 <= top < bottom <= num_rows = %d and 0 <= left < right <= "
+             "num_cols = %d", fn, rect[0], rect[1], rect[2], rect[3], num_rows, num_cols);
+    fail(msg, "rect", __FILE__, __LINE__);
+    return false;
+}
 bool depth_auto_params_ok(const char *fn, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate)
 {
     char msg[200];
@@ -1012,6 +1082,35 @@ void stm_get_cut(int out[3])
 {
     const stm::Cut c = stm::cut();
     out[0] = c.mode; out[1] = c.thresh_permille; out[2] = c.min_gap;
+}
+int stm_set_active(int mode, const int rect[4], int fill, float fill_disp)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (!stm::active_params_ok("set_active", mode, rect, fill, fill_disp)) return -1; // the thread's setting stays as it was
+    stm::Active a = stm::active(); // mode 2's parameters (stm_set_active_auto) are kept
+    a.mode = mode;
+    for (int i = 0; i < 4; ++i) a.rect[i] = mode == 1 ? rect[i] : 0;
+    a.fill = mode ? fill : 0;
+    a.fill_disp = mode ? fill_disp : 0.0f;
+    stm::set_active(a);
+    return 0;
+}
+int stm_set_active_auto(int thresh_luma, int lit_permille, int max_bar_permille, int hold, int *d_state)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    if (!stm::active_auto_params_ok("set_active_auto", thresh_luma, lit_permille, max_bar_permille, hold)) return -1;
+    stm::Active a = stm::active();
+    a.thresh_luma = thresh_luma; a.lit_permille = lit_permille; a.max_bar_permille = max_bar_permille; a.hold = hold; a.d_state = d_state;
+    stm::set_active(a);
+    return 0;
+}
+void stm_get_active(int out[10], float *fill_disp)
+{
+    const stm::Active a = stm::active();
+    out[0] = a.mode;
+    for (int i = 0; i < 4; ++i) out[1 + i] = a.rect[i];
+    out[5] = a.fill; out[6] = a.thresh_luma; out[7] = a.lit_permille; out[8] = a.max_bar_permille; out[9] = a.hold;
+    *fill_disp = a.fill_disp;
 }
 void stm_set_agg_variant(int v)
 {

@@ -26,6 +26,7 @@ struct Slot {
     float *d_arec = nullptr, *h_arec = nullptr; // align mode 2: likewise the alignment's state
     int *d_brec = nullptr, *h_brec = nullptr;   // balance mode 2: likewise the balance's state (769 ints)
     int *d_crec = nullptr, *h_crec = nullptr;   // cut mode 1: {cut, since, score} as this slot's frame's decision left them (12 bytes)
+    int *d_acrec = nullptr, *h_acrec = nullptr; // active mode 2: {top, bottom, left, right, changed} as this slot's frame left them (20 bytes)
     u8 *h_ov = nullptr, *d_ov = nullptr;      // stm_stream_set_overlay: the slot's pinned and device copy of the overlay's pixels
     long ov_gen = 0;                          // ... and which stm_stream_overlay call they hold (0 = none yet)
     float *d_orec = nullptr, *h_orec = nullptr; // stm_stream_set_overlay_auto: the overlay's state as this slot's frame left it (16 bytes), and its download
@@ -72,6 +73,9 @@ struct FrameStream {
     int *d_balance_state = nullptr; // balance mode 2: the state every frame updates, at one address for both slots' graphs
     stm::Cut cut = stm::cut_default(); // stm_stream_set_cut: the stream's own shot-change detector
     int *d_cut_state = nullptr;     // cut mode 1: the 260 ints every frame updates, at one address for both slots' graphs
+    stm::Active active = stm::active_default(); // stm_stream_set_active: the stream's own active picture area
+    int *d_active_state = nullptr;  // active mode 1 and 2: 16 ints at one address for both slots' graphs; mode 2 updates them on every
+                                    // frame, mode 1 wrote the given rectangle into words 1 .. 4 once (the overlay fit behind the graph reads it)
     int ov_max_rows = 0, ov_max_cols = 0; // stm_stream_set_overlay: the largest overlay the slots' copies hold ((0, 0) = off)
     u8 *ov_pixels = nullptr;              // stm_stream_overlay: the pixels of the overlay in force (host memory of the stream's own)
     stm::Overlay ov = {0, nullptr, 0, 0, 0, 0, 0.0f}; // ... and its arguments; mode 0 = none.  d_overlay is filled in per slot
@@ -121,6 +125,11 @@ struct BalanceScope {
     ~BalanceScope() { stm::set_balance(saved); }
 };
 
+struct ActiveScope {
+    stm::Active saved;
+    explicit ActiveScope(const stm::Active &a) : saved(stm::active()) { stm::set_active(a); }
+    ~ActiveScope() { stm::set_active(saved); }
+};
 struct CutScope {
     stm::Cut saved;
     explicit CutScope(const stm::Cut &c) : saved(stm::cut()) { stm::set_cut(c); }
@@ -814,6 +823,63 @@ int stm_stream_set_cut(void *h, int mode, int thresh_permille, int min_gap)
     f->cut.d_state = mode == 1 ? f->d_cut_state : nullptr;
     return 0;
 }
+// The active picture area of the stream's frames (stm_set_active's and stm_set_active_auto's rules in one call; the default is mode
+// 0).  Kept and installed like the cut detector.  The stream owns the state; the cut state mode 2 reads is the stream's own, which the
+// frame call resolves from the settings installed at submit: the setters may come in any order.  Only before the first submit.
+int stm_stream_set_active(void *h, int mode, const int rect[4], int fill, float fill_disp, int thresh_luma, int lit_permille, int max_bar_permille,
+                          int hold)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (!stm::active_params_ok("stream_set_active", mode, rect, fill, fill_disp)) return -1;
+    if (mode == 1 && !stm::active_rect_ok("stream_set_active", rect, f->H, f->W)) return -1;
+    if (mode == 2 && (!stm::active_auto_params_ok("stream_set_active", thresh_luma, lit_permille, max_bar_permille, hold) ||
+                      !stm::active_size_ok("stream_set_active", f->H, f->W)))
+        return -1;
+    if (f->submitted > 0) {
+        stm::fail("stream_set_active: only before the first submit", "stream", __FILE__, __LINE__);
+        return -1;
+    }
+    const size_t bytes = stm::ACTIVE_STATE_WORDS * 4;
+    if (mode != 0 && !f->d_active_state) {
+        STM_CHECK(hipMalloc((void **)&f->d_active_state, bytes));
+        for (Slot &s : f->slot) {
+            STM_CHECK(hipMalloc((void **)&s.d_acrec, 20));
+            STM_CHECK(hipHostMalloc((void **)&s.h_acrec, 20, hipHostMallocDefault));
+        }
+        if (stm::failed()) return -1;
+    }
+    if (mode != 0) { // mode 2: valid = 0, the first frame starts afresh; mode 1: the rectangle where the fits read it
+        int st[stm::ACTIVE_STATE_WORDS] = {0};
+        if (mode == 1) {
+            st[0] = 1;
+            for (int i = 0; i < 4; ++i) st[1 + i] = rect[i];
+            st[6] = f->H; st[7] = f->W;
+        }
+        STM_CHECK(hipMemcpy(f->d_active_state, st, bytes, hipMemcpyHostToDevice));
+        if (stm::failed()) return -1;
+    }
+    stm::Active a = f->active;
+    a.mode = mode;
+    for (int i = 0; i < 4; ++i) a.rect[i] = mode == 1 ? rect[i] : 0;
+    a.fill = mode ? fill : 0;
+    a.fill_disp = mode ? fill_disp : 0.0f;
+    if (mode == 2) { a.thresh_luma = thresh_luma; a.lit_permille = lit_permille; a.max_bar_permille = max_bar_permille; a.hold = hold; }
+    a.d_state = mode == 2 ? f->d_active_state : nullptr;
+    f->active = a;
+    return 0;
+}
+// {top, bottom, left, right, changed} of the most recently collected frame
+int stm_stream_active(void *h, int out[5])
+{
+    FrameStream *f = (FrameStream *)h;
+    if (f->collected == 0) return -1;
+    const Slot &s = f->slot[(f->collected - 1) & 1];
+    if (f->active.mode == 2) { for (int i = 0; i < 5; ++i) out[i] = s.h_acrec[i]; }
+    else if (f->active.mode == 1) { for (int i = 0; i < 4; ++i) out[i] = f->active.rect[i]; out[4] = 0; }
+    else { out[0] = 0; out[1] = f->H; out[2] = 0; out[3] = f->W; out[4] = 0; }
+    return 0;
+}
 // {cut, score, since} of the most recently collected frame
 int stm_stream_cut(void *h, int out[3])
 {
@@ -861,6 +927,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     const bool balance_auto = f->balance.mode == 2; // ... and the colour balance's
     const bool cut_on = f->cut.mode == 1;           // ... and the shot-change detector's
     const bool ov_auto = f->ov_auto.mode == 1;      // ... and the overlay placement's, which also reads the depth and the cut state
+    const bool active_auto = f->active.mode == 2;   // ... and the active area's, which also reads the cut state
     // In NV12 mode the history is the other slot's converted split images (d_img_l / d_img_r), which no upload touches, and this
     // slot's d_in was last read by this slot's own previous frame, collected before the slot was handed out again: the upload
     // waits for nothing.  This frame's compute still waits for the other slot's frame: it reads that frame's images and maps, and
@@ -878,7 +945,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     }
     STM_CHECK(hipEventRecord(s.ev_in, f->s_in));
     STM_CHECK(hipStreamWaitEvent(s.s_compute, s.ev_in, 0));
-    if (history || ((depth_auto || align_auto || balance_auto || cut_on || ov_auto) && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
+    if (history || ((depth_auto || align_auto || balance_auto || cut_on || ov_auto || active_auto) && f->submitted > 0)) STM_CHECK(hipStreamWaitEvent(s.s_compute, other.ev_done, 0));
     void *prev = stm_get_stream();
     LensScope lens_scope(f->lens);
     LayoutScope layout_scope(f->layout);
@@ -888,6 +955,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     AlignScope align_scope(f->align);
     BalanceScope balance_scope(f->balance);
     CutScope cut_scope(f->cut);
+    ActiveScope active_scope(f->active);
     PackingScope packing_scope(f->packing);
     OverlayOffScope overlay_scope;
     stm_set_stream(s.s_compute);
@@ -972,7 +1040,8 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     if (ov.mode == 1 && ov_auto) {
         stm::frame_overlay_auto(s.d_out, stm::Overlay{1, s.d_ov, ov.ov_rows, ov.ov_cols, ov.x0, ov.y0, ov.disparity}, f->ov_auto, f->d_ov_state,
                                 f->d_ov_ws, f->ov_gen != f->ov_fit_gen, false, s.d_dl, s.d_dr, f->H, f->W, f->depth, f->depth.d_state,
-                                cut_on ? f->d_cut_state : nullptr, f->lens, f->layout, f->N, f->angle, f->Hout, f->Wout, f->E);
+                                cut_on ? f->d_cut_state : nullptr, f->lens, f->layout, f->N, f->angle, f->Hout, f->Wout, f->E,
+                                f->active.mode ? f->d_active_state + 1 : nullptr);
         f->ov_fit_gen = f->ov_gen;
     } else if (ov.mode == 1) {
         stm::frame_overlay(s.d_out, stm::Overlay{1, s.d_ov, ov.ov_rows, ov.ov_cols, ov.x0, ov.y0, ov.disparity}, f->lens, f->layout, f->N,
@@ -987,6 +1056,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
         STM_CHECK(hipMemcpyAsync(s.d_brec, f->d_balance_state, stm::BALANCE_STATE_WORDS * 4, hipMemcpyDeviceToDevice, s.s_compute));
     if (cut_on) STM_CHECK(hipMemcpyAsync(s.d_crec, f->d_cut_state + 1, 12, hipMemcpyDeviceToDevice, s.s_compute));
     if (ov_auto) STM_CHECK(hipMemcpyAsync(s.d_orec, f->d_ov_state, 16, hipMemcpyDeviceToDevice, s.s_compute));
+    if (active_auto) STM_CHECK(hipMemcpyAsync(s.d_acrec, f->d_active_state + 1, 20, hipMemcpyDeviceToDevice, s.s_compute));
     STM_CHECK(hipEventRecord(s.ev_done, s.s_compute));
     STM_CHECK(hipStreamWaitEvent(f->s_out, s.ev_done, 0));
     STM_CHECK(hipMemcpyAsync(s.h_dl, s.d_dl, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
@@ -997,6 +1067,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     if (balance_auto) STM_CHECK(hipMemcpyAsync(s.h_brec, s.d_brec, stm::BALANCE_STATE_WORDS * 4, hipMemcpyDeviceToHost, f->s_out));
     if (cut_on) STM_CHECK(hipMemcpyAsync(s.h_crec, s.d_crec, 12, hipMemcpyDeviceToHost, f->s_out));
     if (ov_auto) STM_CHECK(hipMemcpyAsync(s.h_orec, s.d_orec, 16, hipMemcpyDeviceToHost, f->s_out));
+    if (active_auto) STM_CHECK(hipMemcpyAsync(s.h_acrec, s.d_acrec, 20, hipMemcpyDeviceToHost, f->s_out));
     STM_CHECK(hipEventRecord(s.ev_out, f->s_out));
     if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
     if (stm::failed()) return -1; // error mode 1: the frame was not (completely) enqueued
@@ -1065,6 +1136,8 @@ void stm_stream_destroy(void *h)
         if (s.d_brec) STM_CHECK(hipFree(s.d_brec));
         if (s.h_brec) STM_CHECK(hipHostFree(s.h_brec));
         if (s.d_crec) STM_CHECK(hipFree(s.d_crec));
+        if (s.d_acrec) STM_CHECK(hipFree(s.d_acrec));
+        if (s.h_acrec) STM_CHECK(hipHostFree(s.h_acrec));
         if (s.h_crec) STM_CHECK(hipHostFree(s.h_crec));
         if (s.h_ov) STM_CHECK(hipHostFree(s.h_ov));
         if (s.d_ov) STM_CHECK(hipFree(s.d_ov));
@@ -1078,6 +1151,7 @@ void stm_stream_destroy(void *h)
     if (f->d_align_state) STM_CHECK(hipFree(f->d_align_state));
     if (f->d_balance_state) STM_CHECK(hipFree(f->d_balance_state));
     if (f->d_cut_state) STM_CHECK(hipFree(f->d_cut_state));
+    if (f->d_active_state) STM_CHECK(hipFree(f->d_active_state));
     stm::ws_private_destroy(f->slot[0].ws);
     STM_CHECK(hipStreamDestroy(f->slot[0].s_compute));
     if (f->overlap) {

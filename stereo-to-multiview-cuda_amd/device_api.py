@@ -549,6 +549,107 @@ def d_cut_detect(img_l, thresh_permille, min_gap, state, resets=(), sig=None):
                            _p(sig) if sig is not None else None)
 
 
+ACTIVE_AUTO_DEFAULTS = (24, 10, 300, 12)  # thresh_luma, lit_permille, max_bar_permille, hold
+
+
+def _rect4(rect):
+    r = (C.c_int * 4)(*[int(v) for v in rect])
+    return r
+
+
+def _is_rect(t):
+    return t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= 4
+
+
+def set_active(mode, rect=None, fill=False, fill_disp=0.0):
+    """stm_set_active: the calling thread's active picture area.  mode 0 = off (the default; the other arguments are ignored), 1 = the
+    given rect = (top, bottom, left, right) -- rows [top, bottom), columns [left, right) of one eye --, 2 = measured on each frame's
+    left eye on the GPU with set_active_auto's parameters.  With a mode on, depth mode 2 and the automatic overlay placement of every
+    frame call are fitted under the rectangle, and with `fill` the maps the call hands back hold fill_disp outside it.  Raises
+    ValueError where the library refuses."""
+    if int(lib().stm_set_active(int(mode), _rect4(rect) if rect is not None else None, int(fill), float(fill_disp))) != 0:
+        raise ValueError("stm_set_active(%d, %r, %r, %g) refused: %s" % (mode, rect, fill, fill_disp, lib().stm_last_error().decode()))
+
+
+def set_active_auto(thresh_luma=24, lit_permille=10, max_bar_permille=300, hold=12, state=None):
+    """stm_set_active_auto: mode 2's parameters (d_active_detect has their meaning), kept when the mode changes.  `state`: an int32
+    tensor of 16 elements on the GPU, {valid, top, bottom, left, right, changed, H, W, cand[4], run[4]}, zeroed at the start -- the
+    caller keeps it alive while the setting is in use; None = every frame measured on its own.  Raises ValueError where the library
+    refuses."""
+    if state is not None:
+        assert state.is_cuda and state.dtype == torch.int32 and state.is_contiguous() and state.numel() == 16
+    if int(lib().stm_set_active_auto(int(thresh_luma), int(lit_permille), int(max_bar_permille), int(hold),
+                                     _p(state) if state is not None else None)) != 0:
+        raise ValueError("stm_set_active_auto(%d, %d, %d, %d) refused: %s"
+                         % (thresh_luma, lit_permille, max_bar_permille, hold, lib().stm_last_error().decode()))
+
+
+def get_active():
+    """stm_get_active: the calling thread's (mode, (top, bottom, left, right), fill, fill_disp, thresh_luma, lit_permille,
+    max_bar_permille, hold) as the library holds it"""
+    out = (C.c_int * 10)()
+    fd = C.c_float(0.0)
+    lib().stm_get_active(out, C.cast(C.byref(fd), f32p))
+    return (int(out[0]), tuple(int(v) for v in out[1:5]), int(out[5]), float(fd.value), int(out[6]), int(out[7]), int(out[8]), int(out[9]))
+
+
+def d_active_detect(img_l, state, thresh_luma=24, lit_permille=10, max_bar_permille=300, hold=12, restart=False, cut_state=None, counts=None):
+    """stm_d_active_detect: the active picture area as a stage -- the lit pixels (luma above thresh_luma) of the left image (uint8
+    [H][W][E] on the GPU) per row and column, the bars of this frame, and the update of `state` (int32, 16 elements on the GPU) under
+    the hold rule, in place; nothing synchronised.  cut_state: stm_cut_detect's 260 ints on the GPU or None; counts (int32, H + W
+    elements, rows first) receives the counts where given.  The rectangle is state[1:5]."""
+    H, W, E = img_l.shape
+    assert img_l.is_cuda and img_l.dtype == torch.uint8 and img_l.is_contiguous()
+    assert state.is_cuda and state.dtype == torch.int32 and state.is_contiguous() and state.numel() == 16
+    assert counts is None or (counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == H + W)
+    if cut_state is not None:
+        assert cut_state.is_cuda and cut_state.dtype == torch.int32 and cut_state.is_contiguous() and cut_state.numel() >= 2
+    _use_current_stream()
+    lib().stm_d_active_detect(_p(img_l), H, W, E, int(thresh_luma), int(lit_permille), int(max_bar_permille), int(hold), int(bool(restart)),
+                              _p(state), _p(cut_state) if cut_state is not None else None, _p(counts) if counts is not None else None)
+
+
+def d_active_fill(disp, rect, value):
+    """stm_d_active_fill: every pixel of disp (float32 [H][W] on the GPU) outside rect (int32, four elements on the GPU: top, bottom,
+    left, right; None = the whole map) becomes `value`, in place; the inside is not touched.  Nothing synchronised."""
+    H, W = disp.shape
+    assert disp.is_cuda and disp.dtype == torch.float32 and disp.is_contiguous()
+    assert rect is None or _is_rect(rect)
+    _use_current_stream()
+    lib().stm_d_active_fill(_p(disp), H, W, _p(rect) if rect is not None else None, float(value))
+
+
+def d_depth_fit_rect(disp_l, disp_r, disp_lo, disp_hi, max_gain, clip_permille, rate, state, rect):
+    """stm_d_depth_fit_rect: d_depth_fit over the pixels inside rect only (int32, four elements on the GPU; None = d_depth_fit)."""
+    H, W = disp_l.shape
+    for t in (disp_l, disp_r):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
+    assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous() and state.numel() == 4
+    assert rect is None or _is_rect(rect)
+    _use_current_stream()
+    lib().stm_d_depth_fit_rect(_p(disp_l), _p(disp_r), H, W, float(disp_lo), float(disp_hi), float(max_gain), int(clip_permille), float(rate),
+                               _p(state), _p(rect) if rect is not None else None)
+
+
+def d_overlay_fit_rect(disp_l, disp_r, overlay, x0, y0, view_rows, view_cols, limit_lo, limit_hi, state, rect, gain=1.0, conv=0.0,
+                       near_permille=20, margin=1.0, pad=8, rate_near=1.0, rate_far=0.1, restart=False, cut_state=None):
+    """stm_d_overlay_fit_rect: d_overlay_fit with the footprint's map rectangle moved into rect (int32, four elements on the GPU;
+    None = d_overlay_fit): their intersection, or the picture lines nearest to a footprint that lies wholly in a bar."""
+    H, W = disp_l.shape
+    for t in (disp_l, disp_r):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H, W)
+    _check_overlay(overlay)
+    assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous() and state.numel() == 4
+    assert rect is None or _is_rect(rect)
+    if cut_state is not None:
+        assert cut_state.is_cuda and cut_state.dtype == torch.int32 and cut_state.is_contiguous() and cut_state.numel() >= 2
+    _use_current_stream()
+    lib().stm_d_overlay_fit_rect(_p(disp_l), _p(disp_r), H, W, _p(overlay), overlay.shape[0], overlay.shape[1], int(x0), int(y0), int(view_rows),
+                                 int(view_cols), float(gain), float(conv), int(near_permille), float(margin), int(pad), float(limit_lo),
+                                 float(limit_hi), float(rate_near), float(rate_far), int(bool(restart)), _p(state),
+                                 _p(cut_state) if cut_state is not None else None, _p(rect) if rect is not None else None)
+
+
 def d_view_prefilter(out, img, disp, num_views, strength=1.0, max_radius=8, gate=1.0, gain=1.0, conv=0.0):
     """stm_d_view_prefilter: img (uint8 [H][W][E] on the GPU) filtered by its own map disp (float32 [H][W]) into out, which must not
     overlap img; only bytes 0 .. 2 of a pixel are written.  gain, conv: the depth budget the views are rendered with (set_depth)."""

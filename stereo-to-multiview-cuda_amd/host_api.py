@@ -496,6 +496,65 @@ def cut_detect(img_l, thresh_permille=370, min_gap=1, state=None):
     return cut, st
 
 
+def _rect4(rect):
+    return None if rect is None else (C.c_int * 4)(*[int(v) for v in rect])
+
+
+def active_detect(img_l, thresh_luma=24, lit_permille=10, max_bar_permille=300, hold=12, restart=False, state=None):
+    """The active picture area of one left image (stm_active_detect; an addition, the reference measures black bars as picture): the
+    rows and columns that hold lit pixels against the bars in `state` = (valid, top, bottom, left, right, changed, H, W, cand[4],
+    run[4]) (None = no history).  Returns (changed, state): the flag and the new state as an int32 array of 16, whose words 1 .. 4
+    are the rectangle; nothing passed in is modified."""
+    img_l, pl = _u8(img_l)
+    H, W, E = img_l.shape
+    st = np.zeros(16, np.int32) if state is None else np.array(state, dtype=np.int32, order="C")
+    assert st.shape == (16,)
+    changed = int(lib().stm_active_detect(pl, H, W, E, int(thresh_luma), int(lit_permille), int(max_bar_permille), int(hold), int(bool(restart)),
+                                          st.ctypes.data_as(C.POINTER(C.c_int))))
+    if changed < 0:
+        raise ValueError("stm_active_detect refused: %s" % lib().stm_last_error().decode())
+    return changed, st
+
+
+def active_fill(disp, rect, value):
+    """stm_active_fill: the map disp [H][W] with every pixel outside rect = (top, bottom, left, right) set to `value` (None: the map
+    as it is).  Returns the new map; nothing passed in is modified."""
+    out = np.array(disp, dtype=np.float32, order="C")
+    H, W = out.shape
+    lib().stm_active_fill(out.ctypes.data_as(f32p), H, W, _rect4(rect), float(value))
+    return out
+
+
+def depth_fit_rect(disp_l, disp_r, disp_lo, disp_hi, max_gain=1.0, clip_permille=20, rate=1.0, state=None, rect=None):
+    """depth_fit over the pixels of both maps inside rect = (top, bottom, left, right) only (stm_depth_fit_rect; None = depth_fit)."""
+    disp_l, pl = _f32(disp_l)
+    disp_r, pr = _f32(disp_r)
+    H, W = disp_l.shape
+    assert disp_r.shape == (H, W)
+    st = np.zeros(4, np.float32) if state is None else np.array(state, dtype=np.float32, order="C")
+    assert st.shape == (4,)
+    lib().stm_depth_fit_rect(pl, pr, H, W, float(disp_lo), float(disp_hi), float(max_gain), int(clip_permille), float(rate),
+                             st.ctypes.data_as(f32p), _rect4(rect))
+    return st
+
+
+def overlay_fit_rect(disp_l, disp_r, overlay, x0, y0, view_rows, view_cols, limit_lo, limit_hi, gain=1.0, conv=0.0, near_permille=20,
+                     margin=1.0, pad=8, rate_near=1.0, rate_far=0.1, restart=False, state=None, rect=None):
+    """overlay_fit with the footprint's map rectangle moved into rect = (top, bottom, left, right) (stm_overlay_fit_rect; None =
+    overlay_fit)."""
+    disp_l, pl = _f32(disp_l)
+    disp_r, pr = _f32(disp_r)
+    overlay, po = _u8(overlay)
+    H, W = disp_l.shape
+    assert disp_r.shape == (H, W) and overlay.ndim == 3 and overlay.shape[2] == 4
+    st = np.zeros(4, np.float32) if state is None else np.array(state, dtype=np.float32, order="C")
+    assert st.shape == (4,)
+    lib().stm_overlay_fit_rect(pl, pr, H, W, po, overlay.shape[0], overlay.shape[1], int(x0), int(y0), int(view_rows), int(view_cols),
+                               float(gain), float(conv), int(near_permille), float(margin), int(pad), float(limit_lo), float(limit_hi),
+                               float(rate_near), float(rate_far), int(bool(restart)), st.ctypes.data_as(f32p), _rect4(rect))
+    return st
+
+
 def tx_scale(img, out_rows, out_cols):
     """d_tx_scale.h:17-18 (bilinear resize)."""
     img, pi = _u8(img)

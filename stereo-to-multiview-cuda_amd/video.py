@@ -15,6 +15,9 @@ from ._lib import f32p, lib, u8p
 # non-cut and the smallest cut score on the committed images, rounded to 10).  3: a flash lasts one or two frames, so the frame that
 # returns from it comes at most two frames after the flash's own cut and is suppressed; no edited shot is shorter than three frames.
 CUT_DEFAULT = (370, 3)
+# FrameStream(active_auto=True)'s and --active-auto's default (thresh_luma, lit_permille, max_bar_permille, hold): the C calls' own
+# (DESIGN section 28).  24 clears limited-range black (16) plus codec noise; 12 frames is half a second of film.
+ACTIVE_AUTO_DEFAULT = (24, 10, 300, 12)
 
 
 class FrameStream:
@@ -45,11 +48,16 @@ class FrameStream:
     1); balance_auto = (max_shift[, rate]): the tables fitted on every frame on the GPU (mode 2); at most one of the two; .balance()
     reads the tables of the last collected frame.  cut = (thresh_permille, min_gap) or True (CUT_DEFAULT): the shot-change detector
     (set_cut mode 1) -- at a cut the depth_auto, align_auto and balance_auto states start afresh on the GPU; .cut() reads (cut, score,
-    since) of the last collected frame."""
+    since) of the last collected frame.  active = (top, bottom, left, right): the picture's rectangle inside a letterboxed or
+    pillarboxed frame (set_active mode 1); active_auto = (thresh_luma, lit_permille, max_bar_permille, hold) or True
+    (ACTIVE_AUTO_DEFAULT): the rectangle measured on every frame on the GPU (mode 2), restarted at a cut; at most one of the two.
+    depth_auto and overlay_auto are then fitted under the rectangle.  active_fill = a disparity: the maps that come back hold it in
+    the bars; None = the maps as matched.  .active() reads (top, bottom, left, right, changed) of the last collected frame."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
                  depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None, overlay=None,
-                 antialias=None, align=None, align_auto=None, balance=None, balance_auto=None, cut=None, overlay_auto=None):
+                 antialias=None, align=None, align_auto=None, balance=None, balance_auto=None, cut=None, overlay_auto=None,
+                 active=None, active_auto=None, active_fill=None):
         self.H, self.W = num_rows, num_cols
         self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
@@ -104,6 +112,33 @@ class FrameStream:
             self.set_balance(2)
         if cut is not None and cut is not False:
             self.set_cut(1, *(CUT_DEFAULT if cut is True else cut))
+        if active is not None and active_auto is not None and active_auto is not False:
+            raise ValueError("FrameStream: active and active_auto are mutually exclusive")
+        fill = (0, 0.0) if active_fill is None else (1, float(active_fill))
+        if active is not None:
+            self.set_active(1, active, *fill)
+        elif active_auto is not None and active_auto is not False:
+            self.set_active(2, None, *fill, *(ACTIVE_AUTO_DEFAULT if active_auto is True else active_auto))
+        elif active_fill is not None:
+            raise ValueError("FrameStream: active_fill needs active or active_auto")
+
+    def set_active(self, mode, rect=None, fill=0, fill_disp=0.0, thresh_luma=ACTIVE_AUTO_DEFAULT[0], lit_permille=ACTIVE_AUTO_DEFAULT[1],
+                   max_bar_permille=ACTIVE_AUTO_DEFAULT[2], hold=ACTIVE_AUTO_DEFAULT[3]):
+        """stm_stream_set_active: the active picture area of the stream's frames (device_api.set_active's and set_active_auto's
+        arguments; the state is the stream's own); only before the first submit.  Raises ValueError where the library refuses."""
+        r = None if rect is None else (C.c_int * 4)(*[int(v) for v in rect])
+        if int(lib().stm_stream_set_active(self._h, int(mode), r, int(fill), float(fill_disp), int(thresh_luma), int(lit_permille),
+                                           int(max_bar_permille), int(hold))) != 0:
+            raise ValueError("stm_stream_set_active(%d, %r, %d, %g, %d, %d, %d, %d) refused: %s"
+                             % (mode, rect, fill, fill_disp, thresh_luma, lit_permille, max_bar_permille, hold, lib().stm_last_error().decode()))
+
+    def active(self):
+        """stm_stream_active: (top, bottom, left, right, changed) of the most recently collected frame (the whole frame and 0 with
+        the setting off), or None before the first collect."""
+        out = (C.c_int * 5)()
+        if int(lib().stm_stream_active(self._h, out)) != 0:
+            return None
+        return tuple(int(v) for v in out)
 
     def set_cut(self, mode, thresh_permille=CUT_DEFAULT[0], min_gap=CUT_DEFAULT[1]):
         """stm_stream_set_cut: the shot-change detector of the stream's frames (device_api.set_cut's arguments; the state is the
@@ -431,8 +466,55 @@ def take_cut_option(argv):
     return cut
 
 
-def _collect(fs, on_depth, on_align=None, on_balance=None, on_cut=None, on_overlay_depth=None):
+def take_active_options(argv):
+    """The drivers' --active T B L R, --active-auto [THRESH LIT MAX_BAR HOLD] (all four numbers or none: ACTIVE_AUTO_DEFAULT) and
+    --active-fill DISP, removed from argv.  Returns (rect or None, (thresh_luma, lit_permille, max_bar_permille, hold) or None,
+    fill disparity or None); raises ValueError for a malformed option, a value out of range, both --active and --active-auto, or
+    --active-fill without either."""
+    rect, auto, fill = None, None, None
+    if "--active" in argv:
+        at = argv.index("--active")
+        toks = argv[at + 1:at + 5]
+        if len(toks) != 4:
+            raise ValueError("--active takes T B L R")
+        rect = tuple(int(t) for t in toks)
+        if not (0 <= rect[0] < rect[1] and 0 <= rect[2] < rect[3]):
+            raise ValueError(rect)
+        del argv[at:at + 5]
+    if "--active-auto" in argv:
+        at = argv.index("--active-auto")
+        vals = []
+        for tok in argv[at + 1:at + 5]:
+            try:
+                int(tok)
+            except ValueError:
+                break
+            vals.append(tok)
+        if len(vals) not in (0, 4):
+            raise ValueError("--active-auto takes THRESH LIT MAX_BAR HOLD, or none of them")
+        auto = tuple(int(v) for v in vals) if vals else ACTIVE_AUTO_DEFAULT
+        if not (0 <= auto[0] <= 254 and 0 <= auto[1] <= 999 and 0 <= auto[2] <= 450 and 1 <= auto[3] <= (1 << 20)):
+            raise ValueError(auto)
+        del argv[at:at + 1 + len(vals)]
+    if "--active-fill" in argv:
+        at = argv.index("--active-fill")
+        if at + 1 >= len(argv):
+            raise ValueError("--active-fill takes DISP")
+        fill = float(argv[at + 1])
+        if not abs(fill) <= 4096.0:  # a NaN fails the comparison
+            raise ValueError(fill)
+        del argv[at:at + 2]
+    if rect is not None and auto is not None:
+        raise ValueError("--active and --active-auto")
+    if fill is not None and rect is None and auto is None:
+        raise ValueError("--active-fill needs --active or --active-auto")
+    return rect, auto, fill
+
+
+def _collect(fs, on_depth, on_align=None, on_balance=None, on_cut=None, on_overlay_depth=None, on_active=None):
     r = fs.collect()
+    if on_active is not None and r is not None:
+        on_active(r[0], fs.active())
     if on_overlay_depth is not None and r is not None:
         on_overlay_depth(r[0], fs.overlay_depth())
     if on_cut is not None and r is not None:
@@ -449,7 +531,8 @@ def _collect(fs, on_depth, on_align=None, on_balance=None, on_cut=None, on_overl
 def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, temporal=None, input_format="bgr", matrix=0, lens=None,
                      depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None,
                      overlay=None, antialias=None, align=None, align_auto=None, on_align=None, balance=None, balance_auto=None,
-                     on_balance=None, cut=None, on_cut=None, overlay_auto=None, on_overlay_depth=None):
+                     on_balance=None, cut=None, on_cut=None, overlay_auto=None, on_overlay_depth=None, active=None,
+                     active_auto=None, active_fill=None, on_active=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
@@ -464,7 +547,9 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
     vertical alignment of every frame's pair; on_align: called with (index, (a, b, c)) after every collected frame.  balance /
     balance_auto: FrameStream's colour balance of every frame's pair; on_balance: called with (index, tables) likewise.  cut:
     FrameStream's shot-change detector; on_cut: called with (index, (cut, score, since)) likewise.  overlay_auto: FrameStream's
-    automatic placement of `overlay`, whose disparity is then ignored; on_overlay_depth: called with (index, state) likewise."""
+    automatic placement of `overlay`, whose disparity is then ignored; on_overlay_depth: called with (index, state) likewise.
+    active / active_auto / active_fill: FrameStream's active picture area; on_active: called with (index, (top, bottom, left, right,
+    changed)) likewise."""
     fs = None
     pending = 0
     for sbs in frames:
@@ -475,18 +560,19 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
                 rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
             fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output,
                              overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]), antialias=antialias,
-                             align=align, align_auto=align_auto, balance=balance, balance_auto=balance_auto, cut=cut, overlay_auto=overlay_auto)
+                             align=align, align_auto=align_auto, balance=balance, balance_auto=balance_auto, cut=cut, overlay_auto=overlay_auto,
+                             active=active, active_auto=active_auto, active_fill=active_fill)
             if overlay is not None:
                 fs.overlay(*overlay)
             if temporal is not None:
                 fs.set_temporal(*temporal)
         if pending == 2:
-            yield _collect(fs, on_depth, on_align, on_balance, on_cut, on_overlay_depth)
+            yield _collect(fs, on_depth, on_align, on_balance, on_cut, on_overlay_depth, on_active)
             pending -= 1
         fs.submit(sbs)
         pending += 1
     while fs is not None and pending:
-        yield _collect(fs, on_depth, on_align, on_balance, on_cut, on_overlay_depth)
+        yield _collect(fs, on_depth, on_align, on_balance, on_cut, on_overlay_depth, on_active)
         pending -= 1
     if fs is not None:
         fs.close()

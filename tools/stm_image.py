@@ -9,6 +9,7 @@ usage: stm_image.py <left.bmp> <right.bmp> <ad coeff> <census coeff> <ndisp> <ze
                     [--linear-warp] [--lens MODE PITCH SLOPE CENTRE] [--quilt TX TY ORDER FILTER]
                     [--antialias STRENGTH MAX_RADIUS GATE] [--align A B C | --align-auto RADIUS [RATE]]
                     [--balance FILE.npy | --balance-auto [MAX_SHIFT RATE]]
+                    [--active T B L R | --active-auto [THRESH LIT MAX_BAR HOLD]] [--active-fill DISP]
 
 --interp (an addition, off by default): the outlier interpolation (host_api.dr_interp) of both maps after region voting, each on
 its own image and outlier map, before --subpixel.
@@ -32,7 +33,12 @@ field is measured within +-RADIUS rows (host_api.align_fit) and printed.  The al
 --balance FILE.npy (an addition): the right image then goes through the three tables of FILE.npy (768 bytes of uint8: B, G, R, 256
 each; host_api.balance_apply), so that an exposure or white-balance difference between the two cameras reaches neither the matcher
 nor the views.  --balance-auto [MAX_SHIFT RATE]: the tables are fitted from the two images' histograms (host_api.balance_fit),
-moving no level by more than MAX_SHIFT (48); one still pair: RATE has nothing to follow and is accepted for symmetry."""
+moving no level by more than MAX_SHIFT (48); one still pair: RATE has nothing to follow and is accepted for symmetry.
+--active T B L R (an addition): the picture's rectangle inside a letterboxed or pillarboxed pair, rows [T, B) and columns [L, R).
+--active-auto [THRESH LIT MAX_BAR HOLD]: the rectangle is measured on the left image (host_api.active_detect: a line is picture
+when more than LIT permille (10) of its pixels have a luma above THRESH (24), a bar is at most MAX_BAR permille (300) of the frame to
+a side; one still pair: HOLD has nothing to wait for and is accepted for symmetry) and printed.  --active-fill DISP (with either):
+both final maps take DISP in the bars (host_api.active_fill) before the views are rendered from them."""
 import os
 import sys
 
@@ -105,6 +111,7 @@ def main(argv):
         import stm_amd  # noqa: F401
         from stm_amd import video
         balance, balance_auto = video.take_balance_options(argv)
+        active, active_auto, active_fill = video.take_active_options(argv)
     except (ValueError, IndexError):
         print(__doc__)
         return -1
@@ -129,6 +136,12 @@ def main(argv):
         print("balance: B %d %d %d G %d %d %d R %d %d %d" % tuple(int(balance[c, v]) for c in range(3) for v in (64, 128, 192)))
     if balance is not None:
         R = api.balance_apply(R, balance)
+    if active_auto is not None:  # on the left image as given: the reference of the alignment and the balance
+        active = tuple(int(v) for v in api.active_detect(L, *active_auto[:3], hold=1, restart=True)[1][1:5])
+        print("active: rows %d..%d cols %d..%d" % active)
+    if active is not None and not (active[1] <= L.shape[0] and active[3] <= L.shape[1]):
+        print("Error! --active %d %d %d %d does not fit a %d x %d image" % (active + L.shape[:2]))
+        return -1
     ad, ce, D, zd = float(a[2]), float(a[3]), int(a[4]), int(a[5])
     ucd, lcd, usd, lsd = float(a[6]), float(a[7]), int(a[8]), int(a[9])
     N, angle, Wo, Ho, ts, th = int(a[10]), float(a[11]), int(a[12]), int(a[13]), int(a[14]), float(a[15])
@@ -152,6 +165,8 @@ def main(argv):
         dl, dr = api.dc_subpixel(al, dl, zd), api.dc_subpixel(ar, dr, zd)
     dl = api.filter_bilateral_1(dl, 7, 7.0, 7.0, D)                       # :242
     dr = api.filter_bilateral_1(dr, 7, 7.0, 7.0, D)                       # :243
+    if active is not None and active_fill is not None:
+        dl, dr = api.active_fill(dl, active, active_fill), api.active_fill(dr, active, active_fill)
     wr("disp_l", video.normalize_minmax_u8(dl)); wr("disp_r", video.normalize_minmax_u8(dr))
     wr("outliers_l", (ol.astype(np.uint16) * 127).astype(np.uint8)); wr("outliers_r", (orr.astype(np.uint16) * 127).astype(np.uint8))
     occl_l, occl_r = api.dibr_occl(dl, dr)                                # :255

@@ -11,6 +11,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--overlay FILE.npy X0 Y0 DISPARITY] [--overlay-auto LO HI [NEAR MARGIN PAD RATE_NEAR RATE_FAR]] [--antialias STRENGTH MAX_RADIUS GATE]
                     [--align A B C | --align-auto RADIUS [RATE]] [--balance FILE.npy | --balance-auto [MAX_SHIFT RATE]]
                     [--cut [THRESH MIN_GAP]]
+                    [--active T B L R | --active-auto [THRESH LIT MAX_BAR HOLD]] [--active-fill DISP]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -68,6 +69,13 @@ two options are mutually exclusive; both combine with every input format and eve
 with the previous frame's through a 4 x 4 grid of 16-bin luma histograms; a frame that scores THRESH permille (1 .. 1000; 370) or
 more, at least MIN_GAP frames (3) after the last cut, is a cut, and the --depth-auto, --align-auto and --balance-auto states start
 afresh on it.  Each frame's flag and score are printed, and at the end the indices of the frames found to be cuts.
+--active T B L R (an addition): the picture's rectangle inside a letterboxed or pillarboxed frame (stm_stream_set_active mode 1) --
+rows [T, B) and columns [L, R) of one eye; --depth-auto and --overlay-auto are then fitted under it, not under the bars.
+--active-auto [THRESH LIT MAX_BAR HOLD]: the rectangle is measured on every frame's left eye on the GPU (mode 2) -- a line is picture
+when more than LIT permille (0 .. 999; 10) of its pixels have a luma above THRESH (0 .. 254; 24); a bar is at most MAX_BAR permille
+(0 .. 450; 300) of the frame to a side, grows only after HOLD (1 .. 2^20; 12) agreeing frames, shrinks at once, and starts afresh at a
+--cut; each frame's rectangle is printed.  The two options are mutually exclusive.  --active-fill DISP (with either): the maps come
+back with DISP (|DISP| <= 4096) in the bars.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -274,6 +282,7 @@ def main(argv):
         from stm_amd import video
         balance, balance_auto = video.take_balance_options(argv)
         cut = video.take_cut_option(argv)
+        active, active_auto, active_fill = video.take_active_options(argv)
     except (ValueError, IndexError):
         print(__doc__)
         return -1
@@ -319,7 +328,10 @@ def main(argv):
                                                        cut=cut, on_cut=on_cut if cut is not None else None, overlay_auto=overlay_auto,
                                                        on_overlay_depth=(lambda k, st: print("frame %d: overlay disparity %.6g nearest %.6g" % (
                                                            k, min(max(float(st[1]), overlay_auto[0]), overlay_auto[1]), float(st[2]))))
-                                                       if overlay_auto is not None else None):
+                                                       if overlay_auto is not None else None,
+                                                       active=active, active_auto=active_auto, active_fill=active_fill,
+                                                       on_active=(lambda k, r: print("frame %d: active rows %d..%d cols %d..%d changed %d" % ((k,) + r)))
+                                                       if active_auto is not None else None):
         if yuv is not None:  # the frame is [out height * 3 / 2][out width]: the Y plane, then the interleaved UV plane
             yuv.write(inter.tobytes())
             video.write_disparities(out_dir, k, dl, dr)
