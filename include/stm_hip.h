@@ -126,6 +126,25 @@ int         stm_first_pass_path(int num_disp, int zero_disp, int num_rows, int n
  * volume's order and never the answer).  The order is internal to the three aggregation kernels: the maps are the same either way.
  * Host arithmetic only, from the dispatcher's own functions, like stm_agg_path.  An addition. */
 int         stm_px_order(int num_disp, int zero_disp, int num_rows, int num_cols, int usd, int stages);
+/* Test access to the aggregation chain of the calling thread's frame calls.  All four null = off (the default).  An addition.
+ * Every buffer is the caller's device memory, float [2][num_disp][H][W]: view 0 is the left and 1 the right, the true hypothesis d
+ * ascends, only d < num_disp is stored, and H x W is the size the pair is matched at (the match size of the _2* calls).  While a
+ * pointer is set, every frame entry of the thread (stm_adcensus_stm, stm_d_adcensus_stm, _t, _nv12, _2 ..) does this on the frame's
+ * stream, each copy as a launch directly behind the pass that produced the volume:
+ *   d_h1         receives the volume after the first horizontal pass;
+ *   d_v2         receives the volume after both vertical passes;
+ *   d_inject_v2  is then written over the chain's V2 volumes, before the last horizontal pass reads them (with stage bit 0x200 the
+ *                sub-pixel step reads the injected volume as well).  The padding hypotheses d >= num_disp of the volumes' last chunk
+ *                take -1.0f: every last pass guards d >= num_disp itself, so a broken guard shows as a winner outside the range;
+ *   d_h4         receives the last pass's output, but only where the chain keeps it (stage bit 0x100 on the matrix pipe; the
+ *                vector-ALU chains never write it, and a vector-ALU frame with 0x100 aggregates through the per-stage kernels
+ *                and is not tapped at all).
+ * The copy kernels know the chain's layouts (PQ, pixel-major in each hypothesis order, quads); no aggregation kernel knows of the tap,
+ * no workspace is taken, and stm_agg_path, stm_first_pass_path and stm_px_order answer the same with the tap on and off.  With the tap
+ * off there is no extra launch.  Per host thread, read when a call enqueues its kernels; the frames of a stream
+ * (stm_stream_submit) never see it.  The per-stage stm_ca_cross / stm_d_ca_cross is not tapped.  Returns 0, or -1 with stm_last_error
+ * set and the tap unchanged for a pointer that is not 4-byte aligned (an error like any other: the default error mode exits). */
+int         stm_set_agg_tap(float *d_h1, float *d_v2, float *d_h4, const float *d_inject_v2);
 /* dr_irv / d_dr_irv / the frame calls: 0 (default) = the reference's accept rule, (winning bin index + zero_disp) / S > thresh_h
  * (d_dr_irv.cu:36 -- the bin INDEX, SURVEY A-Q17 iv); 1 = the paper's rule, (winning bin's COUNT) / S > thresh_h (Mei et al.,
  * region voting).  An addition: the reference has no such switch. */

@@ -35,6 +35,7 @@ PROTOS = {
     "stm_agg_path": ([i, i, i, i, i, i], i),
     "stm_first_pass_path": ([i, i, i, i, i, i], i),
     "stm_px_order": ([i, i, i, i, i, i], i),
+    "stm_set_agg_tap": ([vp, vp, vp, vp], i),
     "stm_set_irv_paper_ratio": ([i], None),
     "stm_set_irv_chunk": ([i], i),
     "stm_irv_path": ([i, i, i, i, i, i], i),

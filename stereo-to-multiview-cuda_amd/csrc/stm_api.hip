@@ -1890,10 +1890,14 @@ void frame_disparity(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, int
         Vol s2 = vol_quads(scratch2, HW);
         launch_agg_h2_cost(pk_l, cen[0], pk_r, cen[1], rho_table(ad_coeff, census_coeff), sc, al.left, al.right, s2, ar.left, ar.right,
                            D, zero_disp, H, W);
+        const AggTap tap = agg_tap(); // the test tap (stm_set_agg_tap): copies behind the passes, no h4 (this chain keeps no last volume)
+        if (tap.h1) launch_tap_read(sc.base, s2.base, TAP_QUADS, 0, tap.h1, D, H, W);
         launch_agg_v(sc, cl, al.up, al.down, D, H, W, usd);
         launch_agg_v(s2, cr, ar.up, ar.down, D, H, W, usd);
         launch_agg_v(cl, sc, al.up, al.down, D, H, W, usd);
         launch_agg_v(cr, s2, ar.up, ar.down, D, H, W, usd);
+        if (tap.v2) launch_tap_read(sc.base, s2.base, TAP_QUADS, 0, tap.v2, D, H, W);
+        if (tap.inject_v2) launch_tap_write(sc.base, s2.base, TAP_QUADS, 0, tap.inject_v2, D, H, W);
         launch_agg_h_wta2(sc, al.left, al.right, wl, s2, ar.left, ar.right, wr, D, zero_disp, H, W);
         v2_quads[0] = sc.base;
         v2_quads[1] = s2.base;

@@ -547,6 +547,23 @@ void launch_active_detect(int *state, uint32_t *counts, const PackInput *in, con
 void launch_active_rect(int *d_rect, const int rect[4]);
 // disp[i] (H x W), i < nmaps (1 or 2), takes `value` outside the rectangle d_rect holds; one launch over the four strips
 void launch_active_fill(int nmaps, float *const *disp, int H, int W, const int *d_rect, float value);
+// The test tap on the frame's aggregation chain (stm_set_agg_tap, include/stm_hip.h): the caller's float [2][D][H][W] buffers that
+// receive the volume after the first horizontal pass (h1), after both vertical passes (v2) and after a last pass that keeps its
+// volume (h4), and the volume written over V2 before the last pass (inject_v2).  All null = off: not one launch changes.  One per
+// host thread; a frame stream switches it off around its frame calls (a captured graph must not hold the copies).
+struct AggTap {
+    float *h1, *v2, *h4;
+    const float *inject_v2;
+    bool on() const { return h1 || v2 || h4 || inject_v2; }
+};
+AggTap agg_tap();
+void set_agg_tap(const AggTap &t);
+// the copies (stm_kernels_aggtap.hip) between one volume per view in a layout of the chain and a tap buffer, on the launch stream.
+// ord: the hypothesis order of a PX record (px_order, stm_kernels_aggm.hip).  launch_tap_write also sets the padding hypotheses
+// d >= D of the layout's last chunk to -1.0f
+enum { TAP_PQ = 0, TAP_PX = 1, TAP_QUADS = 2 };
+void launch_tap_read(const float *vol_l, const float *vol_r, int layout, int ord, float *dst, int D, int H, int W);
+void launch_tap_write(float *vol_l, float *vol_r, int layout, int ord, const float *src, int D, int H, int W);
 // aggregation on the matrix pipe (stm_kernels_aggm.hip): the frame pipeline's cost -> H -> V, V -> H + WTA
 struct PQViews { // both views of a frame; a / b = the two PQ volumes of a view
     const uint32_t *pk[2], *cen[2];

@@ -1470,8 +1470,10 @@ int aggm_frame_hc2_parts(int D, int zd, int H, int W, int usd, bool keep_volume,
 //   from_costs: the first horizontal pass computes the initial costs itself (images -> vol_b), else it reads vol_a;
 //   then both vertical passes (vol_b -> vol_a); then the last horizontal pass, vol_a -> disparities (wta) or -> vol_b.
 //   px: the two intermediate volumes in the PX layout (chain_px holds; the caller's vtab_ready, if any, is in the per-column layout)
+//   tap: the thread's test tap (stm_set_agg_tap) where it is set, both views (launch_aggm_frame only), else null: each copy is a
+//   launch directly behind the pass that produced the volume.  vol_b after a first pass with 16-byte stores is in order 1
 static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const float *lut, int D, int zd, int H, int W, int usd,
-                       uint32_t *htab_ready = nullptr, uint32_t *vtab_ready = nullptr, bool px = false)
+                       uint32_t *htab_ready = nullptr, uint32_t *vtab_ready = nullptr, bool px = false, const AggTap *tap = nullptr)
 {
     const int G = (W + 3) / 4, NC = (D + 15) / 16;
     if (usd > 255) usd = 255;
@@ -1572,6 +1574,7 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
 #undef STM_HC2_LAUNCH
         STM_CHECK_LAUNCH();
     }
+    if (tap && tap->h1) launch_tap_read(v.b[0], v.b[1], px ? TAP_PX : TAP_PQ, px && ord ? 1 : 0, tap->h1, D, H, W);
     {
         // fused vertical kernel
         ProfScope p("pq_v12");
@@ -1586,6 +1589,8 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
             STM_CHECK_LAUNCH();
         }
     }
+    if (tap && tap->v2) launch_tap_read(v.a[0], v.a[1], px ? TAP_PX : TAP_PQ, ord, tap->v2, D, H, W);
+    if (tap && tap->inject_v2) launch_tap_write(v.a[0], v.a[1], px ? TAP_PX : TAP_PQ, ord, tap->inject_v2, D, H, W);
     {
         ProfScope p("pq_hw");
         if (hregs) {
@@ -1609,6 +1614,7 @@ static void aggm_chain(PQViews &v, int nviews, bool from_costs, bool wta, const 
         }
         STM_CHECK_LAUNCH();
     }
+    if (tap && tap->h4 && !wta) launch_tap_read(v.b[0], v.b[1], TAP_PQ, 0, tap->h4, D, H, W);
 }
 
 // cost -> H -> V, V -> H + WTA for both views of a frame.  vol_a / vol_b: two PQ volumes per view (pq_volume_floats each).
@@ -1640,7 +1646,9 @@ void launch_aggm_frame(const uint32_t *const *pk, const uint32_t *const *cen, co
         v.pk[i] = pk[i]; v.cen[i] = cen[i]; v.a[i] = vol_a[i]; v.b[i] = vol_b[i];
         v.armU[i] = armU[i]; v.armD[i] = armD[i]; v.armL[i] = armL[i]; v.armR[i] = armR[i]; v.disp[i] = disp[i];
     }
-    aggm_chain(v, 2, true, !keep_volume, lut, D, zd, H, W, usd, htab_ready, vtab_ready, aggm_frame_px(D, zd, H, W, usd, keep_volume, v2_read_later));
+    const AggTap tap = agg_tap();
+    aggm_chain(v, 2, true, !keep_volume, lut, D, zd, H, W, usd, htab_ready, vtab_ready, aggm_frame_px(D, zd, H, W, usd, keep_volume, v2_read_later),
+               tap.on() ? &tap : nullptr);
 }
 
 // The per-stage aggregation (ca_cross / d_ca_cross, d_ca_cross.cu:255-270) of ONE volume in the caller's layout on the

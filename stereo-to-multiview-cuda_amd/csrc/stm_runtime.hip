@@ -354,6 +354,10 @@ bool overlay_params_ok(const char *fn, const void *ov, bool check_ptr, int ov_ro
     fail(msg, arg, __FILE__, __LINE__);
     return false;
 }
+// the calling thread's test tap on the aggregation chain (stm_set_agg_tap)
+static thread_local AggTap g_agg_tap = {nullptr, nullptr, nullptr, nullptr};
+AggTap agg_tap() { return g_agg_tap; }
+void set_agg_tap(const AggTap &t) { g_agg_tap = t; }
 // the calling thread's automatic overlay placement (stm_set_overlay_auto)
 OverlayAuto overlay_auto_default() { return OverlayAuto{0, 20, 1.0f, 8, 0.0f, 0.0f, 1.0f, 0.1f, nullptr}; }
 static thread_local OverlayAuto g_overlay_auto = overlay_auto_default();
@@ -1111,6 +1115,21 @@ void stm_get_active(int out[10], float *fill_disp)
     for (int i = 0; i < 4; ++i) out[1 + i] = a.rect[i];
     out[5] = a.fill; out[6] = a.thresh_luma; out[7] = a.lit_permille; out[8] = a.max_bar_permille; out[9] = a.hold;
     *fill_disp = a.fill_disp;
+}
+int stm_set_agg_tap(float *d_h1, float *d_v2, float *d_h4, const float *d_inject_v2)
+{
+    if (stm::api_outermost()) stm::clear_failed();
+    const void *p[4] = {d_h1, d_v2, d_h4, d_inject_v2};
+    const char *name[4] = {"d_h1", "d_v2", "d_h4", "d_inject_v2"};
+    for (int i = 0; i < 4; ++i)
+        if (((uintptr_t)p[i] & 3) != 0) {
+            char msg[120];
+            snprintf(msg, sizeof msg, "set_agg_tap: %s must be 4-byte aligned (a volume of floats)", name[i]);
+            stm::fail(msg, name[i], __FILE__, __LINE__);
+            return -1; // the thread's tap stays as it was
+        }
+    stm::set_agg_tap(stm::AggTap{d_h1, d_v2, d_h4, d_inject_v2});
+    return 0;
 }
 void stm_set_agg_variant(int v)
 {

@@ -148,6 +148,12 @@ struct OverlayOffScope {
     OverlayOffScope() : saved(stm::overlay()) { stm::set_overlay(stm::Overlay{0, nullptr, 0, 0, 0, 0, 0.0f}); }
     ~OverlayOffScope() { stm::set_overlay(saved); }
 };
+// nor does the thread's test tap on the aggregation chain (stm_set_agg_tap): a captured graph must not hold its copies
+struct AggTapOffScope {
+    stm::AggTap saved;
+    AggTapOffScope() : saved(stm::agg_tap()) { stm::set_agg_tap(stm::AggTap{nullptr, nullptr, nullptr, nullptr}); }
+    ~AggTapOffScope() { stm::set_agg_tap(saved); }
+};
 
 struct PackingScope {
     stm::Packing saved;
@@ -958,6 +964,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     ActiveScope active_scope(f->active);
     PackingScope packing_scope(f->packing);
     OverlayOffScope overlay_scope;
+    AggTapOffScope agg_tap_scope;
     stm_set_stream(s.s_compute);
     stm::ws_private_bind(s.ws);
     auto pipeline = [&]() {

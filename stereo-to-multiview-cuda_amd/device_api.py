@@ -101,6 +101,34 @@ def set_irv_chunk(entries=0):
         raise ValueError("stm_set_irv_chunk(%d) refused: %s" % (entries, lib().stm_last_error().decode()))
 
 
+def set_agg_tap(h1=None, v2=None, h4=None, inject_v2=None):
+    """stm_set_agg_tap: test access to the aggregation chain of this thread's frame calls.  Each argument is None or a contiguous
+    float32 tensor [2][D][H][W] on the GPU (view, true hypothesis, the size the pair is matched at): h1 / v2 receive the volume after
+    the first horizontal pass / after both vertical passes, inject_v2 is written over V2 before the last pass, h4 receives the last
+    pass's output where the chain keeps it (stage bit 0x100).  All None = off.  The caller keeps the tensors alive while the tap is
+    set (agg_tap does both).  Raises ValueError where the library refuses."""
+    for t in (h1, v2, h4, inject_v2):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4 and t.shape[0] == 2)
+    if int(lib().stm_set_agg_tap(*[_p(t) if t is not None else None for t in (h1, v2, h4, inject_v2)])) != 0:
+        raise ValueError("stm_set_agg_tap refused: %s" % lib().stm_last_error().decode())
+
+
+class agg_tap:
+    """`with agg_tap(h1=..., v2=..., h4=..., inject_v2=...):` -- set_agg_tap around a block of frame calls; the tap is always cleared
+    on the way out, and the tensors stay referenced until then."""
+
+    def __init__(self, h1=None, v2=None, h4=None, inject_v2=None):
+        self.bufs = (h1, v2, h4, inject_v2)
+
+    def __enter__(self):
+        set_agg_tap(*self.bufs)
+        return self
+
+    def __exit__(self, *exc):
+        set_agg_tap()
+        return False
+
+
 def set_lens(mode, pitch=0.0, slope=0.0, centre=0.0):
     """stm_set_lens: the calling thread's display geometry, which every rendering frame call interlaces through.  mode 0 = off (the
     reference's interlacer, the default), 1 = nearest view, 2 = two views blended, 3 = every sub-pixel rendered at its own
