@@ -84,7 +84,10 @@ int         stm_prof_read(const char *kernel, float *total_ms);
  * chain of the frame as separate kernels (split + pixel formats, then census; L/R check, then row counts, then the full-height
  * column prefix, with the vote codes packed by the compaction kernel) instead of the fused front kernel, the fused row kernel and
  * the column sums inside the compaction kernel, 700 = the cross-arm walk with its bookkeeping in vector registers (round 3) instead
- * of in lane masks and scalar row offsets, 10000000 = the vertical passes on the LDS-ring
+ * of in lane masks and scalar row offsets, 800 = the vertical passes of the pixel-major fast path as masked MFMA sweeps with the
+ * windows as mask records (stm_k_pq_v12m) instead of as exact runs of vector adds with the arms as a table of jump offsets
+ * (stm_k_pq_v12r; the frame stays on the pixel-major volumes and every query below answers as under 0;
+ * tests/test_gpu_vertical_vadd.py), 10000000 = the vertical passes on the LDS-ring
  * kernel of round 3 instead of the register-ring kernel (stm_kernels_aggv.hip), 20000000 = the register-ring kernel with a strip of
  * four columns per wave and the PQ volume layout end to end instead of one column per wave on pixel-major volumes (48 < num_disp <= 64
  * only; elsewhere the default already is the former), 100000000 = the last horizontal pass + WTA on the

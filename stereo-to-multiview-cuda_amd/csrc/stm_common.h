@@ -604,9 +604,10 @@ bool aggv_supports(int usd);
 int aggv_table_top();
 int aggv_table_rec();
 void launch_pq_v12q(PQViews &v, int nviews, const uint32_t *tab, int rec, int H, int W, int G, int NC); // PQ volumes, a strip of four columns per wave
-void launch_pq_v12r(PQViews &v, int nviews, const uint32_t *tab, int H, int W, int G, bool x4 = false); // PX volumes, one column per wave; tab: vcol_build's records; x4: 16-byte stores
+void launch_pq_v12r(PQViews &v, int nviews, const uint32_t *tab, int H, int W, int G, bool x4 = false); // PX volumes, one column per wave; tab: the per-column table; x4: records leave in order 2
 void launch_vcol_table(PQViews &v, int nviews, uint32_t *tab, int H, int W);                            // that table from the arm planes (aggv_col_table_dwords)
 size_t aggv_col_table_dwords(int nviews, int H, int W);
+bool aggv_col_vadd(); // that table holds the arms as jump offsets (stm_k_pq_v12r, the default), not mask records (stm_k_pq_v12m, stm_set_agg_variant(800))
 void launch_to_pq(Vol in, float *pq, int D, int H, int W, uint32_t *odd = nullptr); // stm_kernels_hslo.hip; odd: see stm_k_to_pq
 void launch_from_pq(const float *pq, Vol out, int D, int H, int W); // stm_kernels_aggm.hip
 // HSLO (stm_kernels_hslo.hip)

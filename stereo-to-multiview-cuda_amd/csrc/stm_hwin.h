@@ -75,7 +75,7 @@ static __device__ __forceinline__ void hwin_build(uint32_t *__restrict__ tab, ui
     win16_build(t < nTx ? tab + ((size_t)y * nTx + t) * HR_REC : nullptr, ev4 + r * 96, 16 * t - HR_TOP, s0, nn);
 }
 
-// The vertical twin (stm_k_pq_v12r, stm_kernels_aggv.hip: one column per wave): the same record per (tile of 16 rows, column),
+// The vertical twin (stm_k_pq_v12m, stm_kernels_aggv.hip: one column per wave): the same record per (tile of 16 rows, column),
 // the walk's axis being y.  Lane 16 c + m = row 16 u + m of column x0 + c, s0 / nn its window [y - armU, y + armD) (nn = 0: none;
 // d_ca_cross_sum.cu:172-173,189-194): mask bit 16 a + m of a group = row m has the group's row a in its window.
 // `tile`: the records of (view, tile u), column x at + x * HR_REC; every column in [x0, x0 + 4) must exist there.
@@ -83,6 +83,28 @@ static __device__ __forceinline__ void vcol_build(uint32_t *__restrict__ tile, u
 {
     const int r = (threadIdx.x & 63) >> 4;
     win16_build(tile + (size_t)(x0 + r) * HR_REC, ev4 + r * 96, 16 * u - HR_TOP, s0, nn);
+}
+
+// ---- the arms of a column as jump offsets (stm_k_pq_v12r, stm_kernels_aggv.hip: exact window sums as runs of vector adds).
+// One dword per (view, column, row): [view][column][VA_PAD + y], va_rows(H) rows per column (the kernel reads a step ahead and a
+// pass behind without clamping; only rows of the image are ever used).  The kernel keeps the last VA_RING rows of either pass in
+// registers, row r of its input in slot (r - VA_LAG) mod VA_RING, row r of the first pass in slot r mod VA_RING, and holds, per
+// ring, one sequence of VA_RING adds for every slot a window can end in: sequence e adds the slots e + 1 .. e + VA_RING (mod
+// VA_RING) in that order, VA_SEQ bytes each (the adds and the return).  The window [y - armU, y + armD) of L rows ends in row
+// y + armD - 1, that is in sequence e = (y + armD - 1 - VA_LAG) mod VA_RING of the input ring, and is summed by entering that
+// sequence L adds before its end: the entry is that byte offset.  The second pass uses the same offset in the other ring's
+// sequences, which are laid out VA_LAG slots further on.  L = 0 enters at the return.
+constexpr int VA_RING = 72;             // rows per ring: 2 usd at the largest usd the kernel takes
+constexpr int VA_LAG = 36;              // the second pass runs this many rows behind the first
+constexpr int VA_SEQ = 4 * VA_RING + 4; // bytes of a sequence
+constexpr int VA_PAD = 72;              // table rows in front of row 0
+static inline __host__ __device__ int va_rows(int H) { return H + 128; }
+static inline __host__ __device__ uint32_t va_entry(int y, int aU, int aD)
+{
+    int L = aU + aD;
+    L = L > VA_RING ? VA_RING : L;
+    const int e = (y + aD - 1 - VA_LAG + 2 * VA_RING) % VA_RING; // (y + aD - 1 >= 0 - 1)
+    return (uint32_t)(VA_SEQ * e + 4 * (VA_RING - L));
 }
 
 // ---- the vertical window table (stm_k_vwin_table, stm_kernels_aggm.hip; layout: DESIGN.md section 3) -- one record, one wave.

@@ -62,7 +62,8 @@ struct ArmsArgs {
     uint32_t *htab; // MODE >= 1: the horizontal window table of stm_k_pq_hsr, records of view 0 then view 1 (stm_hwin.h)
     uint32_t *vtab; // MODE 2: the vertical window table of a register-ring kernel (static layout), `vrec` dwords per record, `vtop` = its range's reach
     int vrec, vtop;
-    int vcol;       // MODE 2: one record per column (stm_k_pq_v12r, vcol_build) instead of one per group of four (stm_k_pq_v12q, vwin_build)
+    int vcol;       // MODE 2: 1 = one record per column (stm_k_pq_v12m, vcol_build) instead of one per group of four (stm_k_pq_v12q, vwin_build), 2 = the arms
+                    // of every column as jump offsets (stm_k_pq_v12r, va_entry)
 };
 
 // The walk with vector min / select bookkeeping (round 3, above): behind stm_set_agg_variant(700), for comparison with the one below.
@@ -278,7 +279,9 @@ static __device__ __forceinline__ void cross_arms_body(const ArmsArgs &a, uint32
         if (gg < G) { // (wave-uniform)
             const int b = l >> 4, i = l & 15;
             const int aU = s_u[i][4 * wv_ + b], aD = s_d[i][4 * wv_ + b];
-            if (a.vcol) // (uniform) the wave's four columns, one record each; the wave's own event slots are free again
+            if (a.vcol == 2) // (uniform) one dword per row of the wave's four columns
+                a.vtab[((size_t)v * (4 * G) + 4 * gg + b) * va_rows(H) + VA_PAD + blockIdx.y * 16 + i] = va_entry(blockIdx.y * 16 + i, aU, aD);
+            else if (a.vcol) // (uniform) the wave's four columns, one record each; the wave's own event slots are free again
                 vcol_build(a.vtab + (size_t)(v * nT + u) * (4 * G) * HR_REC, ev_all[wv_], u, 4 * gg, blockIdx.y * 16 + i - aU, aU + aD);
             else
                 vwin_build(a.vtab + ((size_t)(v * nT + u) * G + gg) * a.vrec, ev_v[wv_], u, a.vtop, blockIdx.y * 16 + i - aU, aU + aD);
@@ -337,7 +340,7 @@ void launch_cross_arms2(int nviews, const uint32_t *const *packed, u8 *const *up
     a.vtab = vtab;
     a.vrec = vrec;
     a.vtop = vtop;
-    a.vcol = vcol ? 1 : 0;
+    a.vcol = !vcol ? 0 : aggv_col_vadd() ? 2 : 1;
     // 700 (and planes of 2 GiB and more, whose row offsets do not fit the scalar walk's 32 bits): the walk with vector min / select bookkeeping
     const bool vmin = (agg_variant() / 100) % 10 == 7 || (size_t)H * W * 4 >= ((size_t)1 << 31);
     const uint32_t tg_far = wide_threshold(ucd), tg_near = wide_threshold(lcd);

@@ -5,9 +5,10 @@
 //
 // Round 3's fused vertical kernel (stm_k_pq_v12t, stm_kernels_aggm.hip) streams a strip through two LDS rings shared by the
 // six waves of a block, two barriers per step; its matrix pipe was busy 48 % of the time (profiles/r03_pmc_sq_aggm.txt).
-// Two kernels.  stm_k_pq_v12q (first below, round 4; PQ volumes, every path but the frame's fast one): a strip of 4 columns x 16
-// hypotheses belongs to ONE wave.  stm_k_pq_v12r (second below; PX volumes, the frame's fast path): ONE column x 64 hypotheses per
-// wave, the same walk with the sweep block of stm_k_pq_hsr; its comment says what differs.  In stm_k_pq_v12q nothing is shared:
+// Three kernels.  stm_k_pq_v12q (first below, round 4; PQ volumes, every path but the frame's fast one): a strip of 4 columns x 16
+// hypotheses belongs to ONE wave.  stm_k_pq_v12m (second below; PX volumes, stm_set_agg_variant(800)): ONE column x 64 hypotheses per
+// wave, the same walk with the sweep block of stm_k_pq_hsr; its comment says what differs.  stm_k_pq_v12r (third; PX volumes, the
+// frame's fast path): one column per wave again, the windows summed exactly by vector adds, no MFMA.  In stm_k_pq_v12q nothing is shared:
 //  * a row of the strip is 64 floats = ONE vector register, laid out exactly as the B operand of v_mfma_f32_16x16x1_4B_f32
 //    wants it (lane 16 b + n = column b, hypothesis n).  The CU's register file (512 KB) is three times its LDS: the 88 input
 //    rows a tile's sweep can touch and the 100 first-pass rows the second pass needs are two rings of registers per wave;
@@ -525,7 +526,7 @@ VR_done_%=:
                    "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247");
 }
 
-// ------------------------------------------------------------------ one column per wave (the frame's fast path, PX volumes)
+// ------------------------------------------------------------------ one column per wave, masked MFMA sweeps (PX volumes; variant 800)
 // The kernel above spends one v_cndmask per MFMA: with a tile of 16 rows x 4 columns every MFMA carries 64 distinct mask bits.
 // Here a wave owns ONE column and all 64 hypotheses of it (the volumes are pixel-major, PX: float index ((y 4G + x) 64 + d), a
 // row of the column = 256 contiguous bytes = one register, lane 16 b + n = chunk b, hypothesis n).  The MFMA's four blocks are the
@@ -558,7 +559,7 @@ VR_done_%=:
 // dword stores.  The MFMA leaves block b in registers 4 b .. 4 b + 3, so each store's tuple (i, 4 + i, 8 + i, 12 + i) is copied into
 // v[244:247] / v[248:251] first: sixteen v_mov per step.  A step is then 16 loads + 4 stores.
 template <int EXP, bool X4>
-__global__ __launch_bounds__(64, 2) void stm_k_pq_v12r(PQViews pv, const uint32_t *__restrict__ wtab, int H, int G4, int nviews)
+__global__ __launch_bounds__(64, 2) void stm_k_pq_v12m(PQViews pv, const uint32_t *__restrict__ wtab, int H, int G4, int nviews)
 {
     // block (one wave) -> (view, column); columns in [W, 4G) have empty windows and write zeros
     const int x = blockIdx.x % G4, view = blockIdx.x / G4;
@@ -1011,8 +1012,279 @@ VC_done_%=:
                    "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251");
 }
 
+// ------------------------------------------------------------------ one column per wave, exact windows as runs of vector adds
+// The default of the frame's fast path.  stm_k_pq_v12m above sweeps, per tile of 16 rows, the union of the tile's windows with
+// masked MFMAs: half of its add slots multiply by zero.  With one column per wave and lane = hypothesis the
+// window [y - armU, y + armD) is the same for all 64 lanes, so its sum is a straight run of `v_add_f32 acc, row, acc` over exactly
+// its rows, in the reference's order (d_ca_cross_sum.cu:148-198): no mask, no select, no accumulator tile, no transposition.
+// Every register of a run is NAMED: through the VGPR index mode an add issues in 4 cycles instead of 2
+// (tools/vadd_chain_probe.hip), so each ring has one sequence of 72 adds per slot a window can end in (72 sequences of 292 bytes,
+// 42 KB for both rings), a window is one computed jump into the sequence of its last row, 72 - L adds from the start, and a window
+// that crosses the ring's end is summed like any other.  The jump offset of every row comes ready from the table (stm_hwin.h,
+// va_entry: one dword per row, 9 MB at 1080p where the masks took 67 MB).
+// A step handles one row: the second pass of row y - 36 (ring 2 -> acc -> HBM), the first pass of row y (ring 1 -> acc), then acc
+// enters ring 2 and input row y + 36 ring 1, both at slot y mod 72 (relative destination: the index mode is on for these two moves
+// only).  Input rows arrive in sixteen landing registers, sixteen steps ahead of their move (4 KB in flight per wave).  Every step
+// issues exactly one load and one store, so that one vmcnt value fits all steps: rows below the image are read as the last row
+// (no window reaches them), stores of rows outside the image go to an empty buffer.
+// Register map: v0 accumulator, v[1:72] ring 1, v[73:144] ring 2, v[145:160] landing registers.  s[16:19] / s[20:23] buffer
+// descriptors (input column, output column), s24 y, s25 y mod 72, s26 byte offset of the next row to load, s27 that of the last
+// row, s28 byte offset of row y - 36, s29 table offset of row y, s30 y - 36, s[36:37] / s[38:39] the sequences of ring 1 / ring 2,
+// s[40:41] / s[42:43] table of the column at row -36 / -72, s[44:45] / s[46:47] entries (first, second pass) of an even / odd
+// step, s[48:49] jump target, s[50:51] return address, s52 last step + 1, s31 y - first row of the first pass (s32 .. s35 are left alone: the ABI's stack registers).
+// Blocks: the kernel's 163 registers let three waves share a SIMD, V12R_SLOTS on the chip.  `full` columns (a multiple of the slots)
+// are one block each; every column beyond them is cut into `parts` row ranges, one block each, which start when the whole columns
+// end -- 3840 columns as 3840 blocks left 768 of them running alone on their SIMDs at the end, a third of the kernel's time.  A
+// range [y0, y1) begins 72 rows early with the ring's fill and ends 36 rows late (the first pass of the rows its last windows need).
+// s53 / s54: 36 + y0 and y1 - y0 (the second pass's rows), s55 / s56: first row and number of the first pass's rows, s57 / s58: the
+// steps [y0 + 36, min(y1 + 36, H)) at which both passes have a row of the block: sixteen such steps in a row run without asking.
+// Results are bit-identical to stm_k_pq_v12m (the same chains in the same order; adding 0.0 * row changed nothing).
+// X4: lane 16 b + n stores at float 4 n + b of the record (order 2 of stm_px_order), else at float 16 b + n.
+// EXP: timing experiments (libstm_hip_timing.so only; results NOT valid): 1 = no sums, 2 = no loads / stores.
+constexpr int V12R_SLOTS = 3 * 4 * 256; // resident waves of the chip: three on each SIMD of MI355X's 256 CUs
+template <int EXP, bool X4>
+__global__ __launch_bounds__(64) void stm_k_pq_v12r(PQViews pv, const uint32_t *__restrict__ atab, int H, int G4, int nviews, int full, int parts)
+{
+    // block (one wave) -> (view, column, rows [y0, y1)); columns in [W, 4G) have empty windows and write zeros
+    const int b = blockIdx.x, cidx = b < full ? b : full + (b - full) / parts, part = b < full ? 0 : (b - full) % parts, np = b < full ? 1 : parts;
+    const int x = cidx % G4, view = cidx / G4;
+    if (view >= nviews) return;
+    const int y0 = (int)((long long)H * part / np), y1 = (int)((long long)H * (part + 1) / np);
+    const int ys = max(y0 - 108, -36);                              // first step: row ys + 36 is the first to enter ring 1
+    const int p1lo = max(y0 - 36, 0), p1n = min(y1 + 36, H) - p1lo; // rows of the first pass
+    const int l = threadIdx.x;
+    const int rsb = G4 * 256; // bytes between consecutive rows of the column
+    const float *in = (const float *)(view ? pv.b[1] : pv.b[0]) + (size_t)x * 64;
+    float *out = (float *)(view ? pv.a[1] : pv.a[0]) + (size_t)x * 64;
+    const uint32_t last = (uint32_t)(H - 1) * (uint32_t)rsb, range = last + 256u; // bytes of a column up to the end of its last row
+    const uint32_t *tcol = atab + ((size_t)view * G4 + x) * va_rows(H);           // the column's entries, row -VA_PAD first
+    const int voff = 4 * l;                                                       // lane 16 b + n = float 16 b + n of a record
+    const int vst = X4 ? 4 * (4 * (l & 15) + (l >> 4)) : 4 * l;
+    static_assert(VA_RING == 72 && VA_LAG == 36 && VA_SEQ == 292 && VA_PAD == 72, "the asm block below is written for these");
+    asm volatile(R"ASM(
+        .set VA_EXP, %[exp]
+        .macro VA_FILL k
+        .if (VA_EXP & 2) == 0
+        buffer_store_dword v0, %[vst], s[20:23], 0 offen nt   ; (empty buffer: counted, not written)
+        buffer_load_dword v[145+\k], %[voff], s[16:19], s26 offen nt
+        .endif
+        s_add_u32 s26, s26, %[rsb]
+        s_min_u32 s26, s26, s27
+        .endm
+        ; one row.  k = step mod 16 (the landing register), cur / nxt = first SGPR of this / the next step's entries, g = 1: either
+        ; pass asks whether its row is one of the block's (the steps at both ends of a range), g = 0: both are (seven scalar
+        ; instructions less)
+        .macro VA_STEP k, cur, nxt, g
+        s_waitcnt lgkmcnt(0)                  ; this step's entries, requested a step ago
+        s_add_u32 s29, s29, 4
+        s_load_dword s[\nxt], s[40:41], s29
+        s_load_dword s[\nxt+1], s[42:43], s29
+        ; ------------------------------------------------------------ second pass of row y - 36
+        .if \g
+        s_sub_u32 s30, s24, s53
+        s_cmp_lt_u32 s30, s54                 ; (unsigned: also false above the range)
+        s_cselect_b32 s22, %[range], 0
+        s_cbranch_scc0 VA_skip2_%=_\@
+        .endif
+        v_mov_b32 v0, 0
+        .if (VA_EXP & 1) == 0
+        s_add_u32 s48, s38, s[\cur+1]
+        s_addc_u32 s49, s39, 0
+        s_swappc_b64 s[50:51], s[48:49]
+        .endif
+VA_skip2_%=_\@:
+        .if (VA_EXP & 2) == 0
+        buffer_store_dword v0, %[vst], s[20:23], s28 offen nt
+        .endif
+        s_add_u32 s28, s28, %[rsb]
+        ; ------------------------------------------------------------ first pass of row y
+        .if \g
+        s_sub_u32 s31, s24, s55
+        s_cmp_lt_u32 s31, s56
+        s_cbranch_scc0 VA_skip1_%=_\@
+        .endif
+        v_mov_b32 v0, 0
+        .if (VA_EXP & 1) == 0
+        s_add_u32 s48, s36, s[\cur]
+        s_addc_u32 s49, s37, 0
+        s_swappc_b64 s[50:51], s[48:49]
+        .endif
+VA_skip1_%=_\@:
+        .if (VA_EXP & 2) == 0
+        s_waitcnt vmcnt(31)                   ; the load of sixteen steps ago (issued since: 15 loads, 16 stores)
+        .endif
+        s_set_gpr_idx_on s25, 0x8
+        v_mov_b32 v73, v0                     ; first-pass row y -> ring 2
+        v_mov_b32 v1, v[145+\k]               ; input row y + 36 -> ring 1
+        s_set_gpr_idx_off
+        .if (VA_EXP & 2) == 0
+        buffer_load_dword v[145+\k], %[voff], s[16:19], s26 offen nt   ; row y + 52 (below the image: the last row again)
+        .endif
+        s_add_u32 s26, s26, %[rsb]
+        s_min_u32 s26, s26, s27
+        s_add_u32 s25, s25, 1
+        s_cmp_eq_u32 s25, 72
+        s_cselect_b32 s25, 0, s25
+        s_add_i32 s24, s24, 1
+        .endm
+
+        ; ---------------------------------------------------------------- setup
+        s_mov_b64 s[16:17], %[in]
+        s_and_b32 s17, s17, 0xffff
+        s_mov_b32 s18, %[range]
+        s_mov_b32 s19, 0x20000
+        s_mov_b64 s[20:21], %[out]
+        s_and_b32 s21, s21, 0xffff
+        s_mov_b32 s22, 0
+        s_mov_b32 s23, 0x20000
+        s_mov_b32 s24, %[ys]                  ; the first steps only bring rows into ring 1 (a column from its top: 36 steps, rows [0, 36))
+        s_mov_b32 s25, %[ys72]
+        s_mov_b32 s27, %[last]
+        s_add_u32 s26, s24, 36
+        s_mul_i32 s26, s26, %[rsb]
+        s_min_u32 s26, s26, s27
+        s_sub_u32 s28, s24, 36
+        s_mul_i32 s28, s28, %[rsb]
+        s_add_u32 s29, s24, 36
+        s_lshl_b32 s29, s29, 2
+        s_mov_b32 s53, %[p2lo]
+        s_mov_b32 s54, %[p2n]
+        s_mov_b32 s55, %[p1lo]
+        s_mov_b32 s56, %[p1n]
+        s_mov_b32 s57, %[mlo]
+        s_mov_b32 s58, %[mhi]
+        s_add_u32 s40, %[tcol_lo], 144
+        s_addc_u32 s41, %[tcol_hi], 0
+        s_mov_b32 s42, %[tcol_lo]
+        s_mov_b32 s43, %[tcol_hi]
+        s_add_u32 s52, %[y1], 36
+        s_load_dword s44, s[40:41], s29
+        s_load_dword s45, s[42:43], s29
+        s_getpc_b64 s[36:37]
+VA_pc_%=:
+        s_add_u32 s36, s36, VA_seq_%=-VA_pc_%=
+        s_addc_u32 s37, s37, 0
+        s_add_u32 s38, s36, 72*292
+        s_addc_u32 s39, s37, 0
+        v_mov_b32 v0, 0
+        VA_FILL 0
+        VA_FILL 1
+        VA_FILL 2
+        VA_FILL 3
+        VA_FILL 4
+        VA_FILL 5
+        VA_FILL 6
+        VA_FILL 7
+        VA_FILL 8
+        VA_FILL 9
+        VA_FILL 10
+        VA_FILL 11
+        VA_FILL 12
+        VA_FILL 13
+        VA_FILL 14
+        VA_FILL 15
+        s_branch VA_loop_%=
+        ; ---------------------------------------------------------------- the sequences: ring 1 (slots e + 1 .. e + 72), then
+        ; ring 2 (its slot of a row lies 36 further on)
+VA_seq_%=:
+        .set VA_e, 0
+        .rept 72
+        .set VA_j, 0
+        .rept 72
+        v_add_f32 v0, v[1+(VA_e+1+VA_j)%%72], v0
+        .set VA_j, VA_j+1
+        .endr
+        s_setpc_b64 s[50:51]
+        .set VA_e, VA_e+1
+        .endr
+        .set VA_e, 0
+        .rept 72
+        .set VA_j, 0
+        .rept 72
+        v_add_f32 v0, v[73+(VA_e+37+VA_j)%%72], v0
+        .set VA_j, VA_j+1
+        .endr
+        s_setpc_b64 s[50:51]
+        .set VA_e, VA_e+1
+        .endr
+VA_seqend_%=:
+        .if (VA_seqend_%=-VA_seq_%=) != 144*292
+        .error "a sequence is not 292 bytes"
+        .endif
+VA_loop_%=:
+        ; sixteen steps that ask (the ends of the range) ...
+        s_cmp_ge_i32 s24, s52
+        s_cbranch_scc1 VA_done_%=
+        VA_STEP 0, 44, 46, 1
+        VA_STEP 1, 46, 44, 1
+        VA_STEP 2, 44, 46, 1
+        VA_STEP 3, 46, 44, 1
+        VA_STEP 4, 44, 46, 1
+        VA_STEP 5, 46, 44, 1
+        VA_STEP 6, 44, 46, 1
+        VA_STEP 7, 46, 44, 1
+        VA_STEP 8, 44, 46, 1
+        VA_STEP 9, 46, 44, 1
+        VA_STEP 10, 44, 46, 1
+        VA_STEP 11, 46, 44, 1
+        VA_STEP 12, 44, 46, 1
+        VA_STEP 13, 46, 44, 1
+        VA_STEP 14, 44, 46, 1
+        VA_STEP 15, 46, 44, 1
+        s_cmp_lt_i32 s24, s57
+        s_cbranch_scc1 VA_loop_%=
+        s_add_u32 s30, s24, 16
+        s_cmp_gt_i32 s30, s58
+        s_cbranch_scc1 VA_loop_%=
+        s_mov_b32 s22, %[range]
+VA_main_%=:
+        ; ... and sixteen that do not, while all sixteen rows belong to both passes
+        VA_STEP 0, 44, 46, 0
+        VA_STEP 1, 46, 44, 0
+        VA_STEP 2, 44, 46, 0
+        VA_STEP 3, 46, 44, 0
+        VA_STEP 4, 44, 46, 0
+        VA_STEP 5, 46, 44, 0
+        VA_STEP 6, 44, 46, 0
+        VA_STEP 7, 46, 44, 0
+        VA_STEP 8, 44, 46, 0
+        VA_STEP 9, 46, 44, 0
+        VA_STEP 10, 44, 46, 0
+        VA_STEP 11, 46, 44, 0
+        VA_STEP 12, 44, 46, 0
+        VA_STEP 13, 46, 44, 0
+        VA_STEP 14, 44, 46, 0
+        VA_STEP 15, 46, 44, 0
+        s_add_u32 s30, s24, 16
+        s_cmp_le_i32 s30, s58
+        s_cbranch_scc1 VA_main_%=
+        s_branch VA_loop_%=
+VA_done_%=:
+        s_waitcnt vmcnt(0) lgkmcnt(0)         ; the last rows and entries: nothing may be in flight when the wave ends
+        .purgem VA_FILL
+        .purgem VA_STEP
+        )ASM"
+                 :
+                 : [in] "s"(in), [out] "s"(out), [tcol_lo] "s"((uint32_t)(uintptr_t)tcol), [tcol_hi] "s"((uint32_t)((uintptr_t)tcol >> 32)), [rsb] "s"(rsb), [y1] "s"(y1),
+                   [ys] "s"(ys), [ys72] "s"((ys + 72) % 72), [p2lo] "s"(36 + y0), [p2n] "s"(y1 - y0), [p1lo] "s"(p1lo), [p1n] "s"(p1n), [mlo] "s"(y0 + 36), [mhi] "s"(min(y1 + 36, H)), [range] "s"(range), [last] "s"(last), [voff] "v"(voff), [vst] "v"(vst), [exp] "n"(EXP)
+                 : "memory", "scc", "vcc",
+                   "s16", "s17", "s18", "s19", "s20", "s21", "s22", "s23", "s24", "s25", "s26", "s27", "s28", "s29", "s30", "s31", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58",
+                   "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19",
+                   "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37",
+                   "v38", "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55",
+                   "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71", "v72", "v73",
+                   "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91",
+                   "v92", "v93", "v94", "v95", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108",
+                   "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "v124",
+                   "v125", "v126", "v127", "v128", "v129", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137", "v138", "v139", "v140",
+                   "v141", "v142", "v143", "v144", "v145", "v146", "v147", "v148", "v149", "v150", "v151", "v152", "v153", "v154", "v155", "v156",
+                   "v157", "v158", "v159", "v160");
+}
+
 // The per-column window table of `nviews` views from the arm planes (the frame path builds it inside stm_k_cross_arms instead).
-// A wave = the tile's 16 rows x four columns, lane 16 c + m.
+// A wave = the tile's 16 rows x four columns, lane 16 c + m.  ENTRIES: the arms as jump offsets (va_entry) for stm_k_pq_v12r, else
+// the mask records (vcol_build) of stm_k_pq_v12m.
+template <bool ENTRIES>
 __global__ __launch_bounds__(256) void stm_k_vcol_table(PQViews v, uint32_t *__restrict__ tab, int H, int W, int G, int nT)
 {
     __shared__ uint32_t ev_all[4][4 * 96];
@@ -1020,13 +1292,13 @@ __global__ __launch_bounds__(256) void stm_k_vcol_table(PQViews v, uint32_t *__r
     if (g >= G) return; // uniform per wave; no block-wide barrier below
     const u8 *__restrict__ armU = view ? v.armU[1] : v.armU[0], *__restrict__ armD = view ? v.armD[1] : v.armD[0];
     const int c = l >> 4, m = l & 15, y = u * 16 + m, x = 4 * g + c;
-    int s0 = 0, nn = 0;
+    int aU = 0, aD = 0; // no window outside the image
     if (y < H && x < W) {
-        const int aU = armU[(size_t)y * W + x], aD = armD[(size_t)y * W + x];
-        s0 = y - aU;
-        nn = aU + aD;
+        aU = armU[(size_t)y * W + x];
+        aD = armD[(size_t)y * W + x];
     }
-    vcol_build(tab + (size_t)(view * nT + u) * (4 * G) * HR_REC, ev_all[wv], u, 4 * g, s0, nn);
+    if (ENTRIES) tab[((size_t)view * (4 * G) + x) * va_rows(H) + VA_PAD + y] = va_entry(y, aU, aD);
+    else vcol_build(tab + (size_t)(view * nT + u) * (4 * G) * HR_REC, ev_all[wv], u, 4 * g, y - aU, aU + aD);
 }
 
 bool aggv_supports(int usd) { return usd >= 1 && usd <= VR_TOP; }
@@ -1056,25 +1328,40 @@ void launch_pq_v12q(PQViews &v, int nviews, const uint32_t *tab, int rec, int H,
 }
 
 
-size_t aggv_col_table_dwords(int nviews, int H, int W) { return (size_t)nviews * cdiv(H, 16) * (4 * cdiv(W, 4)) * HR_REC + 64; }
+// 800: the masked-MFMA column kernel stm_k_pq_v12m and its mask records instead of stm_k_pq_v12r and its table of arms
+bool aggv_col_vadd() { return (agg_variant() / 100) % 10 != 8; }
+size_t aggv_col_table_dwords(int nviews, int H, int W)
+{
+    if (aggv_col_vadd()) return (size_t)nviews * (4 * cdiv(W, 4)) * va_rows(H) + 64;
+    return (size_t)nviews * cdiv(H, 16) * (4 * cdiv(W, 4)) * HR_REC + 64;
+}
 
 void launch_vcol_table(PQViews &v, int nviews, uint32_t *tab, int H, int W)
 {
     const int G = cdiv(W, 4), nT = cdiv(H, 16);
-    STM_LAUNCH(stm_k_vcol_table, dim3(cdiv(G, 4), nT, nviews), dim3(256), 0, stream(), v, tab, H, W, G, nT);
+    if (aggv_col_vadd()) STM_LAUNCH(stm_k_vcol_table<true>, dim3(cdiv(G, 4), nT, nviews), dim3(256), 0, stream(), v, tab, H, W, G, nT);
+    else STM_LAUNCH(stm_k_vcol_table<false>, dim3(cdiv(G, 4), nT, nviews), dim3(256), 0, stream(), v, tab, H, W, G, nT);
     STM_CHECK_LAUNCH();
 }
 
-// both vertical passes on PX volumes, vol_b -> vol_a, for `nviews` views; `tab`: the per-column window table (vcol_build)
+// both vertical passes on PX volumes, vol_b -> vol_a, for `nviews` views; `tab`: the per-column table in the form of
+// aggv_col_vadd() (the arms as jump offsets, or vcol_build's mask records under 800)
 void launch_pq_v12r(PQViews &v, int nviews, const uint32_t *tab, int H, int W, int G, bool x4)
 {
     (void)W;
     const int G4 = 4 * G;
     const dim3 grid(G4 * nviews);
-#define STM_V12R_LAUNCH(E)                                                                                  \
-    {                                                                                                       \
-        if (x4) STM_LAUNCH((stm_k_pq_v12r<E, true>), grid, dim3(64), 0, stream(), v, tab, H, G4, nviews);   \
-        else STM_LAUNCH((stm_k_pq_v12r<E, false>), grid, dim3(64), 0, stream(), v, tab, H, G4, nviews);     \
+    const bool vadd = aggv_col_vadd();
+    // stm_k_pq_v12r: whole columns in rounds that fill the chip's wave slots, the rest in row ranges of 128 rows and more
+    const int ncol = G4 * nviews, full = ncol / V12R_SLOTS * V12R_SLOTS, rest = ncol - full;
+    const int parts = rest ? std::max(1, std::min(V12R_SLOTS / rest, H / 128)) : 1;
+    const dim3 grid_a(full + rest * parts);
+#define STM_V12R_LAUNCH(E)                                                                                      \
+    {                                                                                                           \
+        if (vadd && x4) STM_LAUNCH((stm_k_pq_v12r<E, true>), grid_a, dim3(64), 0, stream(), v, tab, H, G4, nviews, full, parts);   \
+        else if (vadd) STM_LAUNCH((stm_k_pq_v12r<E, false>), grid_a, dim3(64), 0, stream(), v, tab, H, G4, nviews, full, parts);   \
+        else if (x4) STM_LAUNCH((stm_k_pq_v12m<E, true>), grid, dim3(64), 0, stream(), v, tab, H, G4, nviews);      \
+        else STM_LAUNCH((stm_k_pq_v12m<E, false>), grid, dim3(64), 0, stream(), v, tab, H, G4, nviews);             \
     }
 #ifdef STM_TIMING
     switch (timing_knobs()) {
