@@ -114,6 +114,16 @@ void down_planes(float **planes, const float *slab, int D, size_t HW)
     for (int d = 0; d < D; ++d)
         STM_CHECK(hipMemcpyAsync(planes[d], slab + (size_t)d * HW, HW * sizeof(float), hipMemcpyDeviceToHost, stream()));
 }
+// the views of a host-flavour interlacer or quilt uploaded, and their device table
+u8 **up_views(unsigned char **views, int num_views, size_t in_sz)
+{
+    std::vector<u8 *> h(num_views);
+    for (int v = 0; v < num_views; ++v) h[v] = up(views[v], in_sz);
+    u8 **dv = Workspace::get<u8 *>(num_views);
+    STM_CHECK(hipMemcpyAsync(dv, h.data(), sizeof(u8 *) * num_views, hipMemcpyHostToDevice, stream()));
+    sync(); // h goes out of scope here
+    return dv;
+}
 
 struct Arms {
     u8 *up, *down, *left, *right;
@@ -126,12 +136,7 @@ bool args_ok(const char *fn, std::initializer_list<Dim> dims)
 {
     if (api_outermost()) clear_failed(); // every entry point starts here: a failure is sticky for one (outermost) API call (stm_common.h)
     for (const Dim &d : dims)
-        if (d.v < d.lo) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "%s: %s = %d, must be >= %d", fn, d.name, d.v, d.lo);
-            fail(msg, d.name, __FILE__, __LINE__);
-            return false;
-        }
+        if (d.v < d.lo) return STM_REJECT(d.name, "%s: %s = %d, must be >= %d", fn, d.name, d.v, d.lo);
     return true;
 }
 
@@ -259,15 +264,9 @@ bool mux_geom_ok(int N, float angle, int elem_sz, float *y_interval, float *inv_
     float yi = mux_y_interval(N, angle, elem_sz);
     // tan(angle) = 0 divides by zero in the reference (d_mux_multiview.cu:146, SURVEY A-Q24); a period beyond the int
     // range would make the (int) conversion undefined
-    if (!(fabsf(yi) < 1.0e9f)) {
-        fail("mux_multiview: y_interval is not finite (tan(angle) == 0 or angle is not a number)", "angle", __FILE__, __LINE__);
-        return false;
-    }
+    if (!(fabsf(yi) < 1.0e9f)) return STM_REJECT("angle", "mux_multiview: y_interval is not finite (tan(angle) == 0 or angle is not a number)");
     int ymod = (int)roundf(yi);
-    if (ymod == 0) {
-        fail("mux_multiview: round(y_interval) == 0 (angle too steep)", "ymod", __FILE__, __LINE__);
-        return false;
-    }
+    if (ymod == 0) return STM_REJECT("ymod", "mux_multiview: round(y_interval) == 0 (angle too steep)");
     if (y_interval) *y_interval = yi;
     if (inv_y_interval) *inv_y_interval = 1.0f / yi;
     if (ymod_out) *ymod_out = ymod;
@@ -285,10 +284,7 @@ void core_mux(const u8 *const *d_views, u8 *d_out, int N, float angle, int Hin, 
 bool overlay_tiles_ok(const char *fn, const Layout &lo, int num_views)
 {
     if (lo.layout == 0 || num_views <= 65535) return true;
-    char msg[160];
-    snprintf(msg, sizeof msg, "%s: an overlay on a quilt of %d tiles: at most 65535 tiles", fn, num_views);
-    fail(msg, "num_views", __FILE__, __LINE__);
-    return false;
+    return STM_REJECT("num_views", "%s: an overlay on a quilt of %d tiles: at most 65535 tiles", fn, num_views);
 }
 
 // guided up-sampling: the dimension screen, then sigma_color (stm_hip.h)
@@ -297,34 +293,17 @@ bool upsample_args_ok(const char *fn, int out_rows, int out_cols, int in_rows, i
     if (!args_ok(fn, {{"out_rows", out_rows, 1}, {"out_cols", out_cols, 1}, {"in_rows", in_rows, 1}, {"in_cols", in_cols, 1},
                       {"elem_sz", elem_sz, 3}}))
         return false;
-    if (!(sigma_color > 0.0f)) { // 0, negative, NaN: the table would hold 0 / 0
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: sigma_color = %g, must be > 0", fn, (double)sigma_color);
-        fail(msg, "sigma_color", __FILE__, __LINE__);
-        return false;
-    }
+    if (!(sigma_color > 0.0f)) // 0, negative, NaN: the table would hold 0 / 0
+        return STM_REJECT("sigma_color", "%s: sigma_color = %g, must be > 0", fn, (double)sigma_color);
     return true;
 }
 // the three parameters of the temporal stabilisation (stm_hip.h): 0 <= alpha <= 1, 0 <= thresh_color <= 765, thresh_disp >= 0
 // (+inf allowed); a NaN fails every one of these comparisons
 bool temporal_params_ok(const char *fn, float alpha, int thresh_color, float thresh_disp)
 {
-    char msg[160];
-    if (!(alpha >= 0.0f && alpha <= 1.0f)) {
-        snprintf(msg, sizeof msg, "%s: alpha = %g, must be in [0, 1]", fn, (double)alpha);
-        fail(msg, "alpha", __FILE__, __LINE__);
-        return false;
-    }
-    if (thresh_color < 0 || thresh_color > 765) {
-        snprintf(msg, sizeof msg, "%s: thresh_color = %d, must be in [0, 765]", fn, thresh_color);
-        fail(msg, "thresh_color", __FILE__, __LINE__);
-        return false;
-    }
-    if (!(thresh_disp >= 0.0f)) {
-        snprintf(msg, sizeof msg, "%s: thresh_disp = %g, must be >= 0", fn, (double)thresh_disp);
-        fail(msg, "thresh_disp", __FILE__, __LINE__);
-        return false;
-    }
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) return STM_REJECT("alpha", "%s: alpha = %g, must be in [0, 1]", fn, (double)alpha);
+    if (thresh_color < 0 || thresh_color > 765) return STM_REJECT("thresh_color", "%s: thresh_color = %d, must be in [0, 765]", fn, thresh_color);
+    if (!(thresh_disp >= 0.0f)) return STM_REJECT("thresh_disp", "%s: thresh_disp = %g, must be >= 0", fn, (double)thresh_disp);
     return true;
 }
 // two maps of n floats each share at least one element
@@ -338,12 +317,8 @@ bool temporal_args_ok(const char *fn, const float *disp, const float *disp_prev,
 {
     if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
     if (!temporal_params_ok(fn, alpha, thresh_color, thresh_disp)) return false;
-    if (disp && disp_prev && maps_overlap(disp, disp_prev, (size_t)num_rows * num_cols)) { // the map is rewritten in place
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: disp_prev must not alias disp", fn);
-        fail(msg, "disp_prev", __FILE__, __LINE__);
-        return false;
-    }
+    if (disp && disp_prev && maps_overlap(disp, disp_prev, (size_t)num_rows * num_cols)) // the map is rewritten in place
+        return STM_REJECT("disp_prev", "%s: disp_prev must not alias disp", fn);
     return true;
 }
 // [a, a + n) and [b, b + m) share a byte
@@ -385,106 +360,65 @@ void stm::frame_overlay_auto(u8 *d_frame, const Overlay &ov, const OverlayAuto &
     frame_overlay(d_frame, at, ln, lo, num_views, angle, Hout, Wout, elem_sz);
 }
 
+// the two pitches and the matrix of NV12 planes num_cols_sbs samples wide: the tail of the plain and of the packed frame's rules
+static bool nv12_planes_ok(const char *fn, int num_cols_sbs, int pitch_y, int pitch_uv, int matrix)
+{
+    if (pitch_y < num_cols_sbs) return STM_REJECT("pitch_y", "%s: pitch_y = %d, must be >= num_cols_sbs = %d", fn, pitch_y, num_cols_sbs);
+    if (pitch_uv < 2 * ((num_cols_sbs + 1) / 2))
+        return STM_REJECT("pitch_uv", "%s: pitch_uv = %d, must be >= 2 * ((num_cols_sbs + 1) / 2) = %d", fn, pitch_uv, 2 * ((num_cols_sbs + 1) / 2));
+    if (matrix < 0 || matrix > 3)
+        return STM_REJECT("matrix", "%s: matrix = %d, must be 0 (BT.601 limited), 1 (BT.709 limited), 2 (BT.601 full) or 3 (BT.709 full)", fn, matrix);
+    return true;
+}
 // the rules of an NV12 frame (stm_hip.h, stm_demux_nv12), after the dimension screen; cols_name: what the call names the width of a view
 bool stm::nv12_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, const char *cols_name, int pitch_y, int pitch_uv,
                        int matrix)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (num_rows & 1) {
-        snprintf(msg, sizeof msg, "%s: num_rows = %d, must be even (a chroma row serves two rows)", fn, num_rows);
-        arg = "num_rows";
-    } else if (num_cols & 1) {
-        snprintf(msg, sizeof msg, "%s: %s = %d, must be even (each half starts on a chroma sample)", fn, cols_name, num_cols);
-        arg = cols_name;
-    } else if (num_cols_sbs < 2 * num_cols) {
-        snprintf(msg, sizeof msg, "%s: num_cols_sbs = %d, must be >= 2 * %s = %d", fn, num_cols_sbs, cols_name, 2 * num_cols);
-        arg = "num_cols_sbs";
-    } else if (pitch_y < num_cols_sbs) {
-        snprintf(msg, sizeof msg, "%s: pitch_y = %d, must be >= num_cols_sbs = %d", fn, pitch_y, num_cols_sbs);
-        arg = "pitch_y";
-    } else if (pitch_uv < 2 * ((num_cols_sbs + 1) / 2)) {
-        snprintf(msg, sizeof msg, "%s: pitch_uv = %d, must be >= 2 * ((num_cols_sbs + 1) / 2) = %d", fn, pitch_uv, 2 * ((num_cols_sbs + 1) / 2));
-        arg = "pitch_uv";
-    } else if (matrix < 0 || matrix > 3) {
-        snprintf(msg, sizeof msg, "%s: matrix = %d, must be 0 (BT.601 limited), 1 (BT.709 limited), 2 (BT.601 full) or 3 (BT.709 full)", fn, matrix);
-        arg = "matrix";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (num_rows & 1) return STM_REJECT("num_rows", "%s: num_rows = %d, must be even (a chroma row serves two rows)", fn, num_rows);
+    if (num_cols & 1) return STM_REJECT(cols_name, "%s: %s = %d, must be even (each half starts on a chroma sample)", fn, cols_name, num_cols);
+    if (num_cols_sbs < 2 * num_cols)
+        return STM_REJECT("num_cols_sbs", "%s: num_cols_sbs = %d, must be >= 2 * %s = %d", fn, num_cols_sbs, cols_name, 2 * num_cols);
+    return nv12_planes_ok(fn, num_cols_sbs, pitch_y, pitch_uv, matrix);
 }
 
 // the rules of a packed frame (stm_hip.h, stm_demux_packed), after the dimension screen
 bool stm::quilt_args_ok(const char *fn, const Layout &lo, int num_views, int in_rows, int in_cols, int out_rows, int out_cols,
                         const char *views_name, const char *rows_name, const char *cols_name)
 {
-    char msg[240];
-    const char *arg = nullptr;
     const int tw = out_cols / lo.tiles_x, th = out_rows / lo.tiles_y;
-    if ((long long)lo.tiles_x * lo.tiles_y != num_views) {
-        snprintf(msg, sizeof msg, "%s: a quilt of tiles_x * tiles_y = %d * %d tiles needs as many views, %s = %d", fn, lo.tiles_x, lo.tiles_y,
-                 views_name, num_views);
-        arg = views_name;
-    } else if (tw == 0) {
-        snprintf(msg, sizeof msg, "%s: %s = %d leaves tiles_x = %d tiles no column", fn, cols_name, out_cols, lo.tiles_x);
-        arg = cols_name;
-    } else if (th == 0) {
-        snprintf(msg, sizeof msg, "%s: %s = %d leaves tiles_y = %d tiles no row", fn, rows_name, out_rows, lo.tiles_y);
-        arg = rows_name;
-    } else if ((long long)tw * in_cols > 0x7fffffffll) { // the area filter's weights are ints
-        snprintf(msg, sizeof msg, "%s: tile width * view width = %d * %d does not fit 31 bits (%s)", fn, tw, in_cols, cols_name);
-        arg = cols_name;
-    } else if ((long long)th * in_rows > 0x7fffffffll) {
-        snprintf(msg, sizeof msg, "%s: tile height * view height = %d * %d does not fit 31 bits (%s)", fn, th, in_rows, rows_name);
-        arg = rows_name;
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if ((long long)lo.tiles_x * lo.tiles_y != num_views)
+        return STM_REJECT(views_name, "%s: a quilt of tiles_x * tiles_y = %d * %d tiles needs as many views, %s = %d", fn, lo.tiles_x, lo.tiles_y,
+                          views_name, num_views);
+    if (tw == 0) return STM_REJECT(cols_name, "%s: %s = %d leaves tiles_x = %d tiles no column", fn, cols_name, out_cols, lo.tiles_x);
+    if (th == 0) return STM_REJECT(rows_name, "%s: %s = %d leaves tiles_y = %d tiles no row", fn, rows_name, out_rows, lo.tiles_y);
+    if ((long long)tw * in_cols > 0x7fffffffll) // the area filter's weights are ints
+        return STM_REJECT(cols_name, "%s: tile width * view width = %d * %d does not fit 31 bits (%s)", fn, tw, in_cols, cols_name);
+    if ((long long)th * in_rows > 0x7fffffffll)
+        return STM_REJECT(rows_name, "%s: tile height * view height = %d * %d does not fit 31 bits (%s)", fn, th, in_rows, rows_name);
+    return true;
 }
 bool stm::packing_args_ok(const char *fn, const Packing &pk, int num_rows, int num_cols_sbs, int num_cols, const char *cols_name, bool nv12,
                           int pitch_y, int pitch_uv, int matrix)
 {
     if (!packing_params_ok(fn, pk)) return false;
-    char msg[240];
-    const char *arg = nullptr;
     const int H = num_rows, W = num_cols, half = pk.packing & 1, axis = pk.packing >> 1;
     const long long need = axis == 0 ? 2LL * (half ? W / 2 : W) + pk.gap : W; // the row the rule asks for
-    if (pk.packing == 1 && (W & 1)) {
-        snprintf(msg, sizeof msg, "%s: %s = %d, must be even with packing 1 (each eye is squeezed to half the columns)", fn, cols_name, W);
-        arg = cols_name;
-    } else if (pk.packing == 3 && (H & 1)) {
-        snprintf(msg, sizeof msg, "%s: num_rows = %d, must be even with packing 3 (each eye is squeezed to half the rows)", fn, H);
-        arg = "num_rows";
-    } else if (num_cols_sbs < need) {
-        snprintf(msg, sizeof msg, "%s: num_cols_sbs = %d, must be >= %lld with packing %d, gap %d and %s = %d", fn, num_cols_sbs, need, pk.packing,
-                 pk.gap, cols_name, W);
-        arg = "num_cols_sbs";
-    } else if (nv12 && ((H & 1) || (pk.packing == 3 && (H & 3)))) {
-        snprintf(msg, sizeof msg, "%s: num_rows = %d, must be a multiple of %d for NV12 with packing %d (each packed eye has an even number of rows)",
-                 fn, H, pk.packing == 3 ? 4 : 2, pk.packing);
-        arg = "num_rows";
-    } else if (nv12 && ((W & 1) || (pk.packing == 1 && (W & 3)))) {
-        snprintf(msg, sizeof msg, "%s: %s = %d, must be a multiple of %d for NV12 with packing %d (each packed eye starts on a chroma sample)",
-                 fn, cols_name, W, pk.packing == 1 ? 4 : 2, pk.packing);
-        arg = cols_name;
-    } else if (nv12 && (pk.gap & 1)) {
-        snprintf(msg, sizeof msg, "%s: gap = %d, must be even for NV12 (the second eye starts on a chroma sample)", fn, pk.gap);
-        arg = "gap";
-    } else if (nv12 && pitch_y < num_cols_sbs) {
-        snprintf(msg, sizeof msg, "%s: pitch_y = %d, must be >= num_cols_sbs = %d", fn, pitch_y, num_cols_sbs);
-        arg = "pitch_y";
-    } else if (nv12 && pitch_uv < 2 * ((num_cols_sbs + 1) / 2)) {
-        snprintf(msg, sizeof msg, "%s: pitch_uv = %d, must be >= 2 * ((num_cols_sbs + 1) / 2) = %d", fn, pitch_uv, 2 * ((num_cols_sbs + 1) / 2));
-        arg = "pitch_uv";
-    } else if (nv12 && (matrix < 0 || matrix > 3)) {
-        snprintf(msg, sizeof msg, "%s: matrix = %d, must be 0 (BT.601 limited), 1 (BT.709 limited), 2 (BT.601 full) or 3 (BT.709 full)", fn, matrix);
-        arg = "matrix";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (pk.packing == 1 && (W & 1))
+        return STM_REJECT(cols_name, "%s: %s = %d, must be even with packing 1 (each eye is squeezed to half the columns)", fn, cols_name, W);
+    if (pk.packing == 3 && (H & 1))
+        return STM_REJECT("num_rows", "%s: num_rows = %d, must be even with packing 3 (each eye is squeezed to half the rows)", fn, H);
+    if (num_cols_sbs < need)
+        return STM_REJECT("num_cols_sbs", "%s: num_cols_sbs = %d, must be >= %lld with packing %d, gap %d and %s = %d", fn, num_cols_sbs, need,
+                          pk.packing, pk.gap, cols_name, W);
+    if (!nv12) return true;
+    if ((H & 1) || (pk.packing == 3 && (H & 3)))
+        return STM_REJECT("num_rows", "%s: num_rows = %d, must be a multiple of %d for NV12 with packing %d (each packed eye has an even number of rows)",
+                          fn, H, pk.packing == 3 ? 4 : 2, pk.packing);
+    if ((W & 1) || (pk.packing == 1 && (W & 3)))
+        return STM_REJECT(cols_name, "%s: %s = %d, must be a multiple of %d for NV12 with packing %d (each packed eye starts on a chroma sample)",
+                          fn, cols_name, W, pk.packing == 1 ? 4 : 2, pk.packing);
+    if (pk.gap & 1) return STM_REJECT("gap", "%s: gap = %d, must be even for NV12 (the second eye starts on a chroma sample)", fn, pk.gap);
+    return nv12_planes_ok(fn, num_cols_sbs, pitch_y, pitch_uv, matrix);
 }
 
 extern "C" {
@@ -961,82 +895,134 @@ static bool depth_fit_args_ok(const char *fn, int num_rows, int num_cols, float 
                               float rate)
 {
     if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}})) return false;
-    if ((size_t)num_rows * num_cols > 0x7fffffffu) { // n = 2 H W is counted in 32 bits
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: num_rows * num_cols = %zu, must be below 2^31", fn, (size_t)num_rows * num_cols);
-        fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
-        return false;
-    }
+    if ((size_t)num_rows * num_cols > 0x7fffffffu) // n = 2 H W is counted in 32 bits
+        return STM_REJECT("num_rows, num_cols", "%s: num_rows * num_cols = %zu, must be below 2^31", fn, (size_t)num_rows * num_cols);
     return depth_auto_params_ok(fn, disp_lo, disp_hi, max_gain, clip_permille, rate);
+}
+// stm_d_depth_fit and stm_d_depth_fit_rect (d_rect null: the whole map), stm_depth_fit and stm_depth_fit_rect likewise
+static void depth_fit_device(const char *fn, float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi,
+                             float max_gain, int clip_permille, float rate, float *d_state, const int *d_rect)
+{
+    if (!depth_fit_args_ok(fn, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate)) return;
+    Workspace::begin(4096 * 4 + 8192);
+    uint32_t *hist = Workspace::get<uint32_t>(4096);
+    launch_depth_fit(d_state, hist, d_disp_l, d_disp_r, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, false, d_rect);
+}
+static void depth_fit_host(const char *fn, float *disp_l, float *disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
+                           int clip_permille, float rate, float *state, const int *rect)
+{
+    if (!depth_fit_args_ok(fn, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate)) return;
+    if (rect && !active_rect_ok(fn, rect, num_rows, num_cols)) return;
+    const size_t HW = (size_t)num_rows * num_cols;
+    Workspace::begin(8 * HW + 4096 * 4 + 8192);
+    float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *st = up(state, 4);
+    const int *rc = rect ? up(rect, 4) : nullptr;
+    uint32_t *hist = Workspace::get<uint32_t>(4096);
+    launch_depth_fit(st, hist, dl, dr, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, false, rc);
+    down(state, st, 4);
+    sync();
 }
 void stm_d_depth_fit(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
                      int clip_permille, float rate, float *d_state)
 {
-    if (!depth_fit_args_ok("d_depth_fit", num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate)) return;
-    Workspace::begin(4096 * 4 + 8192);
-    uint32_t *hist = Workspace::get<uint32_t>(4096);
-    launch_depth_fit(d_state, hist, d_disp_l, d_disp_r, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, false);
+    depth_fit_device("d_depth_fit", d_disp_l, d_disp_r, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, d_state, nullptr);
+}
+void stm_d_depth_fit_rect(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
+                          int clip_permille, float rate, float *d_state, const int *d_rect)
+{
+    depth_fit_device("d_depth_fit_rect", d_disp_l, d_disp_r, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, d_state, d_rect);
 }
 void stm_depth_fit(float *disp_l, float *disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
                    int clip_permille, float rate, float *state)
 {
-    if (!depth_fit_args_ok("depth_fit", num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate)) return;
-    const size_t HW = (size_t)num_rows * num_cols;
-    Workspace::begin(8 * HW + 4096 * 4 + 8192);
-    float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *st = up(state, 4);
-    uint32_t *hist = Workspace::get<uint32_t>(4096);
-    launch_depth_fit(st, hist, dl, dr, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, false);
-    down(state, st, 4);
-    sync();
+    depth_fit_host("depth_fit", disp_l, disp_r, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, state, nullptr);
+}
+void stm_depth_fit_rect(float *disp_l, float *disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
+                        int clip_permille, float rate, float *state, const int *rect)
+{
+    depth_fit_host("depth_fit_rect", disp_l, disp_r, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, state, rect);
 }
 
 // =============================================================== overlay placement: the measurement as a stage
 // (an addition, the reference has no overlay)
-static bool overlay_fit_args_ok(const char *fn, const unsigned char *overlay, bool words, int num_rows, int num_cols, int ov_rows, int ov_cols,
-                                int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin, int pad,
-                                float limit_lo, float limit_hi, float rate_near, float rate_far)
+// the numbers of an overlay fit under the names the four entries give them, and those names in the record's order (as STM_FRAME_PARAMS)
+struct OverlayFitArgs {
+    int num_rows, num_cols, ov_rows, ov_cols, x0, y0, view_rows, view_cols;
+    float gain, conv;
+    int near_permille;
+    float margin;
+    int pad;
+    float limit_lo, limit_hi, rate_near, rate_far;
+    int restart;
+};
+#define STM_OVERLAY_FIT_PARAMS \
+    num_rows, num_cols, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, restart
+static bool overlay_fit_args_ok(const char *fn, const unsigned char *overlay, bool words, const OverlayFitArgs &a)
 {
-    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"view_rows", view_rows, 1}, {"view_cols", view_cols, 1}})) return false;
-    if (!overlay_fit_size_ok(fn, num_rows, num_cols)) return false;
-    if (!overlay_params_ok(fn, overlay, words, ov_rows, ov_cols, x0, y0, 0.0f)) return false;
-    if (!overlay) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "%s: the overlay is null", fn);
-        fail(msg, "overlay", __FILE__, __LINE__);
+    if (!args_ok(fn, {{"num_rows", a.num_rows, 1}, {"num_cols", a.num_cols, 1}, {"view_rows", a.view_rows, 1}, {"view_cols", a.view_cols, 1}}))
         return false;
-    }
-    return depth_params_ok(fn, 1, gain, conv) && overlay_auto_params_ok(fn, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far);
+    if (!overlay_fit_size_ok(fn, a.num_rows, a.num_cols)) return false;
+    if (!overlay_params_ok(fn, overlay, words, a.ov_rows, a.ov_cols, a.x0, a.y0, 0.0f)) return false;
+    if (!overlay) return STM_REJECT("overlay", "%s: the overlay is null", fn);
+    return depth_params_ok(fn, 1, a.gain, a.conv) &&
+           overlay_auto_params_ok(fn, a.near_permille, a.margin, a.pad, a.limit_lo, a.limit_hi, a.rate_near, a.rate_far);
+}
+// the fit's launch on device buffers, shared by both flavours
+static void overlay_fit_launch(float *st, uint32_t *ws, const float *dl, const float *dr, const u8 *ov, const OverlayFitArgs &a, const int *cut_state,
+                               const int *d_rect)
+{
+    const OverlayAuto oa = {1, a.near_permille, a.margin, a.pad, a.limit_lo, a.limit_hi, a.rate_near, a.rate_far, st};
+    launch_overlay_fit(st, ws, dl, dr, a.num_rows, a.num_cols, ov, a.ov_rows, a.ov_cols, a.x0, a.y0, a.view_rows, a.view_cols, a.gain, a.conv, nullptr,
+                       oa, a.restart != 0, false, cut_state, d_rect);
+}
+// stm_d_overlay_fit and stm_d_overlay_fit_rect (d_rect null: the whole map), stm_overlay_fit and stm_overlay_fit_rect likewise
+static void overlay_fit_device(const char *fn, float *d_disp_l, float *d_disp_r, const unsigned char *d_overlay, const OverlayFitArgs &a,
+                               float *d_state, const int *d_cut_state, const int *d_rect)
+{
+    if (!overlay_fit_args_ok(fn, d_overlay, true, a)) return;
+    Workspace::begin(OVERLAY_FIT_WS_WORDS * 4 + 8192);
+    uint32_t *ws = Workspace::get<uint32_t>(OVERLAY_FIT_WS_WORDS);
+    overlay_fit_launch(d_state, ws, d_disp_l, d_disp_r, d_overlay, a, d_cut_state, d_rect);
+}
+static void overlay_fit_host(const char *fn, float *disp_l, float *disp_r, const unsigned char *overlay, const OverlayFitArgs &a, float *state,
+                             const int *rect)
+{
+    if (!overlay_fit_args_ok(fn, overlay, false, a)) return;
+    if (rect && !active_rect_ok(fn, rect, a.num_rows, a.num_cols)) return;
+    const size_t HW = (size_t)a.num_rows * a.num_cols, ov_sz = (size_t)a.ov_rows * a.ov_cols * 4;
+    Workspace::begin(8 * HW + ov_sz + OVERLAY_FIT_WS_WORDS * 4 + 8192);
+    float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *st = up(state, 4);
+    const u8 *o = up((unsigned char *)overlay, ov_sz);
+    const int *rc = rect ? up(rect, 4) : nullptr;
+    uint32_t *ws = Workspace::get<uint32_t>(OVERLAY_FIT_WS_WORDS);
+    overlay_fit_launch(st, ws, dl, dr, o, a, nullptr, rc);
+    down(state, st, 4);
+    sync();
 }
 void stm_d_overlay_fit(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, const unsigned char *d_overlay, int ov_rows, int ov_cols,
                        int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin, int pad,
                        float limit_lo, float limit_hi, float rate_near, float rate_far, int restart, float *d_state, const int *d_cut_state)
 {
-    if (!overlay_fit_args_ok("d_overlay_fit", d_overlay, true, num_rows, num_cols, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv,
-                             near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far))
-        return;
-    Workspace::begin(OVERLAY_FIT_WS_WORDS * 4 + 8192);
-    uint32_t *ws = Workspace::get<uint32_t>(OVERLAY_FIT_WS_WORDS);
-    const OverlayAuto oa = {1, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, d_state};
-    launch_overlay_fit(d_state, ws, d_disp_l, d_disp_r, num_rows, num_cols, d_overlay, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv,
-                       nullptr, oa, restart != 0, false, d_cut_state);
+    overlay_fit_device("d_overlay_fit", d_disp_l, d_disp_r, d_overlay, {STM_OVERLAY_FIT_PARAMS}, d_state, d_cut_state, nullptr);
+}
+void stm_d_overlay_fit_rect(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, const unsigned char *d_overlay, int ov_rows,
+                            int ov_cols, int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin,
+                            int pad, float limit_lo, float limit_hi, float rate_near, float rate_far, int restart, float *d_state,
+                            const int *d_cut_state, const int *d_rect)
+{
+    overlay_fit_device("d_overlay_fit_rect", d_disp_l, d_disp_r, d_overlay, {STM_OVERLAY_FIT_PARAMS}, d_state, d_cut_state, d_rect);
 }
 void stm_overlay_fit(float *disp_l, float *disp_r, int num_rows, int num_cols, const unsigned char *overlay, int ov_rows, int ov_cols, int x0,
                      int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin, int pad, float limit_lo,
                      float limit_hi, float rate_near, float rate_far, int restart, float *state)
 {
-    if (!overlay_fit_args_ok("overlay_fit", overlay, false, num_rows, num_cols, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv,
-                             near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far))
-        return;
-    const size_t HW = (size_t)num_rows * num_cols, ov_sz = (size_t)ov_rows * ov_cols * 4;
-    Workspace::begin(8 * HW + ov_sz + OVERLAY_FIT_WS_WORDS * 4 + 8192);
-    float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *st = up(state, 4);
-    const u8 *o = up((unsigned char *)overlay, ov_sz);
-    uint32_t *ws = Workspace::get<uint32_t>(OVERLAY_FIT_WS_WORDS);
-    const OverlayAuto oa = {1, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, st};
-    launch_overlay_fit(st, ws, dl, dr, num_rows, num_cols, o, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv, nullptr, oa, restart != 0,
-                       false, nullptr);
-    down(state, st, 4);
-    sync();
+    overlay_fit_host("overlay_fit", disp_l, disp_r, overlay, {STM_OVERLAY_FIT_PARAMS}, state, nullptr);
+}
+void stm_overlay_fit_rect(float *disp_l, float *disp_r, int num_rows, int num_cols, const unsigned char *overlay, int ov_rows, int ov_cols,
+                          int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin, int pad,
+                          float limit_lo, float limit_hi, float rate_near, float rate_far, int restart, float *state, const int *rect)
+{
+    overlay_fit_host("overlay_fit_rect", disp_l, disp_r, overlay, {STM_OVERLAY_FIT_PARAMS}, state, rect);
 }
 
 // =============================================================== vertical alignment: the field applied and measured as stages
@@ -1046,18 +1032,9 @@ static bool align_rows_args_ok(const char *fn, const unsigned char *img_out, con
 {
     if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
     if (!align_params_ok(fn, 1, a, b, c)) return false;
-    char msg[160];
-    if (!img_out || !img) {
-        snprintf(msg, sizeof msg, "%s: img_out and img must not be null", fn);
-        fail(msg, "img_out, img", __FILE__, __LINE__);
-        return false;
-    }
+    if (!ptrs_ok(fn, {{"img_out", img_out}, {"img", img}})) return false;
     const size_t bytes = (size_t)num_rows * num_cols * elem_sz;
-    if (bytes_overlap(img_out, bytes, img, bytes)) { // a pixel's taps are other rows' outputs
-        snprintf(msg, sizeof msg, "%s: img_out must not overlap img", fn);
-        fail(msg, "img_out", __FILE__, __LINE__);
-        return false;
-    }
+    if (bytes_overlap(img_out, bytes, img, bytes)) return STM_REJECT("img_out", "%s: img_out must not overlap img", fn); // a pixel's taps are other rows' outputs
     return true;
 }
 void stm_d_align_rows(unsigned char *d_img_out, const unsigned char *d_img, int num_rows, int num_cols, int elem_sz, float a, float b, float c)
@@ -1082,13 +1059,7 @@ static bool align_fit_args_ok(const char *fn, const unsigned char *img_l, const 
 {
     if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
     if (!align_size_ok(fn, num_rows, num_cols) || !align_auto_params_ok(fn, radius, rate)) return false;
-    if (!img_l || !img_r || !state) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: img_l, img_r and state must not be null", fn);
-        fail(msg, "img_l, img_r, state", __FILE__, __LINE__);
-        return false;
-    }
-    return true;
+    return ptrs_ok(fn, {{"img_l", img_l}, {"img_r", img_r}, {"state", state}});
 }
 void stm_d_align_fit(const unsigned char *d_img_l, const unsigned char *d_img_r, int num_rows, int num_cols, int elem_sz, int radius,
                      float rate, float *d_state, int *d_valid_blocks, unsigned int *d_profiles, unsigned int *d_sad)
@@ -1124,13 +1095,7 @@ static bool balance_fit_args_ok(const char *fn, const unsigned char *img_l, cons
 {
     if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
     if (!balance_size_ok(fn, num_rows, num_cols) || !balance_auto_params_ok(fn, max_shift, rate)) return false;
-    if (!img_l || !img_r || !state) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: img_l, img_r and state must not be null", fn);
-        fail(msg, "img_l, img_r, state", __FILE__, __LINE__);
-        return false;
-    }
-    return true;
+    return ptrs_ok(fn, {{"img_l", img_l}, {"img_r", img_r}, {"state", state}});
 }
 void stm_d_balance_fit(const unsigned char *d_img_l, const unsigned char *d_img_r, int num_rows, int num_cols, int elem_sz, int max_shift,
                        float rate, int *d_state, unsigned int *d_hist)
@@ -1158,23 +1123,11 @@ static bool balance_apply_args_ok(const char *fn, const unsigned char *img_out, 
                                   const unsigned char *lut768, const int *state)
 {
     if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
-    char msg[160];
-    if (!img_out || !img) {
-        snprintf(msg, sizeof msg, "%s: img_out and img must not be null", fn);
-        fail(msg, "img_out, img", __FILE__, __LINE__);
-        return false;
-    }
-    if ((lut768 != nullptr) == (state != nullptr)) {
-        snprintf(msg, sizeof msg, "%s: exactly one of lut768 and state must be given", fn);
-        fail(msg, "lut768, state", __FILE__, __LINE__);
-        return false;
-    }
+    if (!ptrs_ok(fn, {{"img_out", img_out}, {"img", img}})) return false;
+    if ((lut768 != nullptr) == (state != nullptr))
+        return STM_REJECT("lut768, state", "%s: exactly one of lut768 and state must be given", fn);
     const size_t bytes = (size_t)num_rows * num_cols * elem_sz;
-    if (bytes_overlap(img_out, bytes, img, bytes)) {
-        snprintf(msg, sizeof msg, "%s: img_out must not overlap img", fn);
-        fail(msg, "img_out", __FILE__, __LINE__);
-        return false;
-    }
+    if (bytes_overlap(img_out, bytes, img, bytes)) return STM_REJECT("img_out", "%s: img_out must not overlap img", fn);
     return true;
 }
 void stm_d_balance_apply(unsigned char *d_img_out, const unsigned char *d_img, int num_rows, int num_cols, int elem_sz,
@@ -1205,13 +1158,7 @@ static bool cut_args_ok(const char *fn, const unsigned char *img_l, int num_rows
 {
     if (!args_ok(fn, {{"num_rows", num_rows, 4}, {"num_cols", num_cols, 4}, {"elem_sz", elem_sz, 3}})) return false;
     if (!cut_size_ok(fn, num_rows, num_cols) || !cut_params_ok(fn, thresh_permille, min_gap)) return false;
-    if (!img_l || !state) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: img_l and state must not be null", fn);
-        fail(msg, "img_l, state", __FILE__, __LINE__);
-        return false;
-    }
-    return true;
+    return ptrs_ok(fn, {{"img_l", img_l}, {"state", state}});
 }
 void stm_d_cut_detect(const unsigned char *d_img_l, int num_rows, int num_cols, int elem_sz, int thresh_permille, int min_gap, int *d_state,
                       void *d_reset0, void *d_reset1, void *d_reset2, unsigned int *d_sig)
@@ -1242,13 +1189,7 @@ static bool active_args_ok(const char *fn, const unsigned char *img_l, int num_r
 {
     if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
     if (!active_size_ok(fn, num_rows, num_cols) || !active_auto_params_ok(fn, thresh_luma, lit_permille, max_bar_permille, hold)) return false;
-    if (!img_l || !state) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: img_l and state must not be null", fn);
-        fail(msg, "img_l, state", __FILE__, __LINE__);
-        return false;
-    }
-    return true;
+    return ptrs_ok(fn, {{"img_l", img_l}, {"state", state}});
 }
 void stm_d_active_detect(const unsigned char *d_img_l, int num_rows, int num_cols, int elem_sz, int thresh_luma, int lit_permille,
                          int max_bar_permille, int hold, int restart, int *d_state, const int *d_cut_state, unsigned int *d_counts)
@@ -1277,13 +1218,7 @@ int stm_active_detect(const unsigned char *img_l, int num_rows, int num_cols, in
 static bool active_fill_args_ok(const char *fn, const float *disp, int num_rows, int num_cols)
 {
     if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}})) return false;
-    if (!disp) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "%s: disp must not be null", fn);
-        fail(msg, "disp", __FILE__, __LINE__);
-        return false;
-    }
-    return true;
+    return ptrs_ok(fn, {{"disp", disp}});
 }
 void stm_d_active_fill(float *d_disp, int num_rows, int num_cols, const int *d_rect, float value)
 {
@@ -1306,62 +1241,6 @@ void stm_active_fill(float *disp, int num_rows, int num_cols, const int *rect, f
     down(disp, d, HW);
     sync();
 }
-void stm_d_depth_fit_rect(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
-                          int clip_permille, float rate, float *d_state, const int *d_rect)
-{
-    if (!depth_fit_args_ok("d_depth_fit_rect", num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate)) return;
-    Workspace::begin(4096 * 4 + 8192);
-    uint32_t *hist = Workspace::get<uint32_t>(4096);
-    launch_depth_fit(d_state, hist, d_disp_l, d_disp_r, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, false, d_rect);
-}
-void stm_depth_fit_rect(float *disp_l, float *disp_r, int num_rows, int num_cols, float disp_lo, float disp_hi, float max_gain,
-                        int clip_permille, float rate, float *state, const int *rect)
-{
-    if (!depth_fit_args_ok("depth_fit_rect", num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate)) return;
-    if (rect && !active_rect_ok("depth_fit_rect", rect, num_rows, num_cols)) return;
-    const size_t HW = (size_t)num_rows * num_cols;
-    Workspace::begin(8 * HW + 4096 * 4 + 8192);
-    float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *st = up(state, 4);
-    const int *rc = rect ? up(rect, 4) : nullptr;
-    uint32_t *hist = Workspace::get<uint32_t>(4096);
-    launch_depth_fit(st, hist, dl, dr, num_rows, num_cols, disp_lo, disp_hi, max_gain, clip_permille, rate, false, rc);
-    down(state, st, 4);
-    sync();
-}
-void stm_d_overlay_fit_rect(float *d_disp_l, float *d_disp_r, int num_rows, int num_cols, const unsigned char *d_overlay, int ov_rows,
-                            int ov_cols, int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin,
-                            int pad, float limit_lo, float limit_hi, float rate_near, float rate_far, int restart, float *d_state,
-                            const int *d_cut_state, const int *d_rect)
-{
-    if (!overlay_fit_args_ok("d_overlay_fit_rect", d_overlay, true, num_rows, num_cols, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv,
-                             near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far))
-        return;
-    Workspace::begin(OVERLAY_FIT_WS_WORDS * 4 + 8192);
-    uint32_t *ws = Workspace::get<uint32_t>(OVERLAY_FIT_WS_WORDS);
-    const OverlayAuto oa = {1, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, d_state};
-    launch_overlay_fit(d_state, ws, d_disp_l, d_disp_r, num_rows, num_cols, d_overlay, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv,
-                       nullptr, oa, restart != 0, false, d_cut_state, d_rect);
-}
-void stm_overlay_fit_rect(float *disp_l, float *disp_r, int num_rows, int num_cols, const unsigned char *overlay, int ov_rows, int ov_cols,
-                          int x0, int y0, int view_rows, int view_cols, float gain, float conv, int near_permille, float margin, int pad,
-                          float limit_lo, float limit_hi, float rate_near, float rate_far, int restart, float *state, const int *rect)
-{
-    if (!overlay_fit_args_ok("overlay_fit_rect", overlay, false, num_rows, num_cols, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv,
-                             near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far))
-        return;
-    if (rect && !active_rect_ok("overlay_fit_rect", rect, num_rows, num_cols)) return;
-    const size_t HW = (size_t)num_rows * num_cols, ov_sz = (size_t)ov_rows * ov_cols * 4;
-    Workspace::begin(8 * HW + ov_sz + OVERLAY_FIT_WS_WORDS * 4 + 8192);
-    float *dl = up(disp_l, HW), *dr = up(disp_r, HW), *st = up(state, 4);
-    const u8 *o = up((unsigned char *)overlay, ov_sz);
-    const int *rc = rect ? up(rect, 4) : nullptr;
-    uint32_t *ws = Workspace::get<uint32_t>(OVERLAY_FIT_WS_WORDS);
-    const OverlayAuto oa = {1, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, st};
-    launch_overlay_fit(st, ws, dl, dr, num_rows, num_cols, o, ov_rows, ov_cols, x0, y0, view_rows, view_cols, gain, conv, nullptr, oa, restart != 0,
-                       false, nullptr, rc);
-    down(state, st, 4);
-    sync();
-}
 
 // =============================================================== view antialiasing: the prefilter as a stage
 // (an addition, the reference has none: its views are pinhole images whatever the lens shows of them)
@@ -1371,18 +1250,9 @@ static bool prefilter_args_ok(const char *fn, const unsigned char *img_out, cons
     if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}, {"elem_sz", elem_sz, 3}, {"num_views", num_views, 2}})) return false;
     if (!antialias_params_ok(fn, strength, max_radius, gate)) return false;
     if (!depth_params_ok(fn, 1, gain, conv)) return false;
-    char msg[160];
-    if (!img_out || !img || !disp) {
-        snprintf(msg, sizeof msg, "%s: img_out, img and disp must not be null", fn);
-        fail(msg, "img_out, img, disp", __FILE__, __LINE__);
-        return false;
-    }
+    if (!ptrs_ok(fn, {{"img_out", img_out}, {"img", img}, {"disp", disp}})) return false;
     const size_t bytes = (size_t)num_rows * num_cols * elem_sz;
-    if (bytes_overlap(img_out, bytes, img, bytes)) { // a pixel's taps are its neighbours' inputs
-        snprintf(msg, sizeof msg, "%s: img_out must not overlap img", fn);
-        fail(msg, "img_out", __FILE__, __LINE__);
-        return false;
-    }
+    if (bytes_overlap(img_out, bytes, img, bytes)) return STM_REJECT("img_out", "%s: img_out must not overlap img", fn); // a pixel's taps are its neighbours' inputs
     return true;
 }
 void stm_d_view_prefilter(unsigned char *d_img_out, const unsigned char *d_img, const float *d_disp, int num_rows, int num_cols, int elem_sz,
@@ -1426,11 +1296,7 @@ void stm_mux_multiview(unsigned char **views, unsigned char *out_data, int num_v
         return;
     size_t in_sz = (size_t)in_rows * in_cols * elem_sz, out_sz = (size_t)out_rows * out_cols * elem_sz;
     Workspace::begin(num_views * (in_sz + 256) + out_sz + 8192);
-    std::vector<u8 *> h(num_views);
-    for (int v = 0; v < num_views; ++v) h[v] = up(views[v], in_sz);
-    u8 **dv = Workspace::get<u8 *>(num_views);
-    STM_CHECK(hipMemcpyAsync(dv, h.data(), sizeof(u8 *) * num_views, hipMemcpyHostToDevice, stream()));
-    sync(); // h goes out of scope below
+    u8 **dv = up_views(views, num_views, in_sz);
     u8 *o = Workspace::get<u8>(out_sz);
     STM_CHECK(hipMemsetAsync(o, 0, out_sz, stream()));
     int variant = (out_rows % num_views == 0) ? 2 : 1; // d_mux_multiview.cu:184-192
@@ -1461,11 +1327,7 @@ void stm_mux_multiview_lens(unsigned char **views, unsigned char *out_data, int 
     if (!lens_params_ok(fn, mode, 1, 2, pitch, slope, centre)) return;
     size_t in_sz = (size_t)in_rows * in_cols * elem_sz, out_sz = (size_t)out_rows * out_cols * elem_sz;
     Workspace::begin(num_views * (in_sz + 256) + out_sz + 8192);
-    std::vector<u8 *> h(num_views);
-    for (int v = 0; v < num_views; ++v) h[v] = up(views[v], in_sz);
-    u8 **dv = Workspace::get<u8 *>(num_views);
-    STM_CHECK(hipMemcpyAsync(dv, h.data(), sizeof(u8 *) * num_views, hipMemcpyHostToDevice, stream()));
-    sync(); // h goes out of scope below
+    u8 **dv = up_views(views, num_views, in_sz);
     u8 *o = Workspace::get<u8>(out_sz);
     STM_CHECK(hipMemsetAsync(o, 0, out_sz, stream())); // bytes past a pixel's third come back 0
     launch_mux_lens((const u8 *const *)dv, o, num_views, Lens{mode, pitch, slope, centre}, in_rows, in_cols, out_rows, out_cols, elem_sz);
@@ -1498,11 +1360,7 @@ void stm_quilt_multiview(unsigned char **views, unsigned char *out_data, int num
     if (!quilt_args_ok(fn, lo, num_views, in_rows, in_cols, out_rows, out_cols, "num_views", "out_rows", "out_cols")) return;
     size_t in_sz = (size_t)in_rows * in_cols * elem_sz, out_sz = (size_t)out_rows * out_cols * elem_sz;
     Workspace::begin(num_views * (in_sz + 256) + out_sz + 8192);
-    std::vector<u8 *> h(num_views);
-    for (int v = 0; v < num_views; ++v) h[v] = up(views[v], in_sz);
-    u8 **dv = Workspace::get<u8 *>(num_views);
-    STM_CHECK(hipMemcpyAsync(dv, h.data(), sizeof(u8 *) * num_views, hipMemcpyHostToDevice, stream()));
-    sync(); // h goes out of scope below
+    u8 **dv = up_views(views, num_views, in_sz);
     u8 *o = Workspace::get<u8>(out_sz);
     STM_CHECK(hipMemsetAsync(o, 0, out_sz, stream())); // bytes past a pixel's third come back 0
     launch_quilt((const u8 *const *)dv, o, num_views, lo, in_rows, in_cols, out_rows, out_cols, elem_sz);
@@ -1519,22 +1377,14 @@ static bool overlay_stage_ok(const char *fn, const unsigned char *overlay, bool 
 {
     if (!args_ok(fn, {{"num_views", num_views, 2}, {"out_rows", out_rows, 1}, {"out_cols", out_cols, 1}, {"elem_sz", elem_sz, 3}})) return false;
     if (!overlay_params_ok(fn, overlay, words, ov_rows, ov_cols, x0, y0, disparity)) return false;
-    if (!overlay) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "%s: the overlay is null", fn);
-        fail(msg, "overlay", __FILE__, __LINE__);
-        return false;
-    }
+    if (!overlay) return STM_REJECT("overlay", "%s: the overlay is null", fn);
     if (!lens_params_ok(fn, lens_mode, 0, 3, pitch, slope, centre)) return false;
     if (!layout_params_ok(fn, layout, tiles_x, tiles_y, order, 0)) return false;
     if (layout == 0) return true;
     if (!overlay_tiles_ok(fn, Layout{1, tiles_x, tiles_y, order, 0}, num_views)) return false;
-    if (lens_mode != 0) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "%s: layout 1 (quilt) together with lens mode %d: a quilt is not interlaced, set one of them to 0", fn, lens_mode);
-        fail(msg, "layout, lens_mode", __FILE__, __LINE__);
-        return false;
-    }
+    if (lens_mode != 0)
+        return STM_REJECT("layout, lens_mode", "%s: layout 1 (quilt) together with lens mode %d: a quilt is not interlaced, set one of them to 0", fn,
+                          lens_mode);
     return quilt_args_ok(fn, Layout{1, tiles_x, tiles_y, order, 0}, num_views, 1, 1, out_rows, out_cols, "num_views", "out_rows", "out_cols");
 }
 void stm_d_mux_overlay(unsigned char *d_frame, const unsigned char *d_overlay, int ov_rows, int ov_cols, int x0, int y0, float disparity,
@@ -1613,27 +1463,13 @@ namespace {
 bool mux_nv12_args_ok(const char *fn, int pitch_y, int pitch_uv, int num_rows, int num_cols, int elem_sz, int matrix)
 {
     if (!args_ok(fn, {{"num_rows", num_rows, 2}, {"num_cols", num_cols, 2}, {"elem_sz", elem_sz, 3}})) return false;
-    char msg[200];
-    const char *arg = nullptr;
-    if (num_rows & 1) {
-        snprintf(msg, sizeof msg, "%s: num_rows = %d, must be even (a chroma row serves two rows)", fn, num_rows);
-        arg = "num_rows";
-    } else if (num_cols & 1) {
-        snprintf(msg, sizeof msg, "%s: num_cols = %d, must be even (a chroma sample serves two columns)", fn, num_cols);
-        arg = "num_cols";
-    } else if (pitch_y < num_cols) {
-        snprintf(msg, sizeof msg, "%s: pitch_y = %d, must be >= num_cols = %d", fn, pitch_y, num_cols);
-        arg = "pitch_y";
-    } else if (pitch_uv < num_cols) {
-        snprintf(msg, sizeof msg, "%s: pitch_uv = %d, must be >= num_cols = %d", fn, pitch_uv, num_cols);
-        arg = "pitch_uv";
-    } else if (matrix < 0 || matrix > 3) {
-        snprintf(msg, sizeof msg, "%s: matrix = %d, must be 0 (BT.601 limited), 1 (BT.709 limited), 2 (BT.601 full) or 3 (BT.709 full)", fn, matrix);
-        arg = "matrix";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (num_rows & 1) return STM_REJECT("num_rows", "%s: num_rows = %d, must be even (a chroma row serves two rows)", fn, num_rows);
+    if (num_cols & 1) return STM_REJECT("num_cols", "%s: num_cols = %d, must be even (a chroma sample serves two columns)", fn, num_cols);
+    if (pitch_y < num_cols) return STM_REJECT("pitch_y", "%s: pitch_y = %d, must be >= num_cols = %d", fn, pitch_y, num_cols);
+    if (pitch_uv < num_cols) return STM_REJECT("pitch_uv", "%s: pitch_uv = %d, must be >= num_cols = %d", fn, pitch_uv, num_cols);
+    if (matrix < 0 || matrix > 3)
+        return STM_REJECT("matrix", "%s: matrix = %d, must be 0 (BT.601 limited), 1 (BT.709 limited), 2 (BT.601 full) or 3 (BT.709 full)", fn, matrix);
+    return true;
 }
 } // namespace
 extern "C" {
@@ -1938,37 +1774,22 @@ static bool frame_output_ok(const char *fn, const Layout &lo, int Hout, int Wout
 {
     const Output o = output();
     if (o.format == 0) return true;
-    char msg[240];
-    const char *arg = nullptr;
     const long long P = o.pitch ? o.pitch : Wout, R = o.uv_row ? o.uv_row : Hout;
-    if (lo.layout == 0) {
-        snprintf(msg, sizeof msg, "%s: output format 1 (NV12) exists for quilts only (chroma subsampling destroys a sub-pixel interlaced frame): "
-                 "set a layout (stm_set_layout) or format 0", fn);
-        arg = "format, layout";
-    } else if (Hout & 1) {
-        snprintf(msg, sizeof msg, "%s: num_rows_out = %d, must be even for NV12 output (a chroma row serves two rows)", fn, Hout);
-        arg = "num_rows_out";
-    } else if (Wout & 1) {
-        snprintf(msg, sizeof msg, "%s: num_cols_out = %d, must be even for NV12 output (a chroma sample serves two columns)", fn, Wout);
-        arg = "num_cols_out";
-    } else if ((Wout / lo.tiles_x) & 1) {
-        snprintf(msg, sizeof msg, "%s: tile width num_cols_out / tiles_x = %d, must be even for NV12 output (every tile starts on a chroma sample)",
-                 fn, Wout / lo.tiles_x);
-        arg = "num_cols_out";
-    } else if ((Hout / lo.tiles_y) & 1) {
-        snprintf(msg, sizeof msg, "%s: tile height num_rows_out / tiles_y = %d, must be even for NV12 output (every tile starts on a chroma sample)",
-                 fn, Hout / lo.tiles_y);
-        arg = "num_rows_out";
-    } else if (P < Wout) {
-        snprintf(msg, sizeof msg, "%s: the NV12 surface's pitch = %lld, must be >= num_cols_out = %d", fn, P, Wout);
-        arg = "pitch";
-    } else if (R < Hout) {
-        snprintf(msg, sizeof msg, "%s: the NV12 surface's uv_row = %lld, must be >= num_rows_out = %d", fn, R, Hout);
-        arg = "uv_row";
-    } // pitch * (uv_row + num_rows_out / 2) < 2^31 * 1.5 * 2^31 < 2^63 for every int
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (lo.layout == 0)
+        return STM_REJECT("format, layout", "%s: output format 1 (NV12) exists for quilts only (chroma subsampling destroys a sub-pixel interlaced "
+                          "frame): set a layout (stm_set_layout) or format 0", fn);
+    if (Hout & 1) return STM_REJECT("num_rows_out", "%s: num_rows_out = %d, must be even for NV12 output (a chroma row serves two rows)", fn, Hout);
+    if (Wout & 1)
+        return STM_REJECT("num_cols_out", "%s: num_cols_out = %d, must be even for NV12 output (a chroma sample serves two columns)", fn, Wout);
+    if ((Wout / lo.tiles_x) & 1)
+        return STM_REJECT("num_cols_out", "%s: tile width num_cols_out / tiles_x = %d, must be even for NV12 output (every tile starts on a chroma "
+                          "sample)", fn, Wout / lo.tiles_x);
+    if ((Hout / lo.tiles_y) & 1)
+        return STM_REJECT("num_rows_out", "%s: tile height num_rows_out / tiles_y = %d, must be even for NV12 output (every tile starts on a chroma "
+                          "sample)", fn, Hout / lo.tiles_y);
+    if (P < Wout) return STM_REJECT("pitch", "%s: the NV12 surface's pitch = %lld, must be >= num_cols_out = %d", fn, P, Wout);
+    if (R < Hout) return STM_REJECT("uv_row", "%s: the NV12 surface's uv_row = %lld, must be >= num_rows_out = %d", fn, R, Hout);
+    return true; // pitch * (uv_row + num_rows_out / 2) < 2^31 * 1.5 * 2^31 < 2^63 for every int
 }
 // the thread's layout (stm_set_layout) against a rendering frame call's geometry, before anything is launched; layout 0, or a call
 // that renders nothing: nothing to check, the call is as it was.  The thread's output format (stm_set_output) is screened here too.
@@ -1978,23 +1799,16 @@ bool frame_layout_ok(const char *fn, const FrameArgs &a)
     const int num_views = a.num_views, Hout = a.num_rows_out, Wout = a.num_cols_out;
     if ((a.stages & 0xff) < 3) return true;
     if (overlay().mode == 1) { // an overlay (stm_set_overlay) is composited on BGR frames only
-        if (output().format == 1) {
-            char msg[240];
-            snprintf(msg, sizeof msg, "%s: an overlay (stm_set_overlay) together with output format 1 (NV12): compositing on a chroma-subsampled "
-                     "surface is not defined, set one of them to 0", fn);
-            fail(msg, "overlay, format", __FILE__, __LINE__);
-            return false;
-        }
+        if (output().format == 1)
+            return STM_REJECT("overlay, format", "%s: an overlay (stm_set_overlay) together with output format 1 (NV12): compositing on a "
+                              "chroma-subsampled surface is not defined, set one of them to 0", fn);
         if (!overlay_tiles_ok(fn, lo, num_views)) return false;
         if (overlay_auto().mode == 1 && !overlay_fit_size_ok(fn, a.num_rows, a.num_cols)) return false;
     }
     if (lo.layout == 0) return frame_output_ok(fn, lo, Hout, Wout);
-    if (lens().mode != 0) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "%s: layout 1 (quilt) together with lens mode %d: a quilt is not interlaced, set one of them to 0", fn, lens().mode);
-        fail(msg, "layout, lens", __FILE__, __LINE__);
-        return false;
-    }
+    if (lens().mode != 0)
+        return STM_REJECT("layout, lens", "%s: layout 1 (quilt) together with lens mode %d: a quilt is not interlaced, set one of them to 0", fn,
+                          lens().mode);
     return quilt_args_ok(fn, lo, num_views, a.num_rows, a.num_cols, Hout, Wout, "num_views", "num_rows_out", "num_cols_out") &&
            frame_output_ok(fn, lo, Hout, Wout);
 }
@@ -2090,18 +1904,11 @@ void frame_render(u8 *img_l, u8 *img_r, float *d_disp_l, float *d_disp_r, u8 *d_
     }
     if ((agg_variant() / 100) % 10 != 2) {
         // views + interlacing in one pass: an output pixel synthesises exactly the samples it interlaces (stm_k_synth_mux)
-        const float yi = mux_y_interval(N, angle, elem_sz);
-        if (!(fabsf(yi) < 1.0e9f)) {
-            fail("mux_multiview: y_interval is not finite (tan(angle) == 0 or angle is not a number)", "angle", __FILE__, __LINE__);
-            return;
-        }
-        const int ymod = (int)roundf(yi);
-        if (ymod == 0) {
-            fail("mux_multiview: round(y_interval) == 0 (angle too steep)", "ymod", __FILE__, __LINE__);
-            return;
-        }
-        launch_synth_mux(img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, d_interlaced, N, yi, 1.0f / yi, ymod, H, W, Hout, Wout,
-                         elem_sz, 2, linear);
+        float yi, inv_y;
+        int ymod;
+        if (!mux_geom_ok(N, angle, elem_sz, &yi, &inv_y, &ymod)) return;
+        launch_synth_mux(img_l, img_r, d_disp_l, d_disp_r, mask_l, mask_r, blend, d_interlaced, N, yi, inv_y, ymod, H, W, Hout, Wout, elem_sz, 2,
+                         linear);
         return;
     }
     // 200: the un-fused form (every view written, then interlaced), as the reference structures it (d_io.cu:182-203)
@@ -2138,12 +1945,8 @@ bool frame_align_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols
 {
     const Align al = align();
     if (!al.mode) return true;
-    if (bgr_sbs && num_cols_sbs < 2 * num_cols) { // both eyes are gathered from the frame
-        char msg[200];
-        snprintf(msg, sizeof msg, "%s: an alignment is set on this thread (stm_set_align), which needs num_cols_sbs >= 2 * num_cols", fn);
-        fail(msg, "num_cols_sbs", __FILE__, __LINE__);
-        return false;
-    }
+    if (bgr_sbs && num_cols_sbs < 2 * num_cols) // both eyes are gathered from the frame
+        return STM_REJECT("num_cols_sbs", "%s: an alignment is set on this thread (stm_set_align), which needs num_cols_sbs >= 2 * num_cols", fn);
     return al.mode != 2 || align_size_ok(fn, num_rows, num_cols);
 }
 // the workspace the prelude below takes: the aligned frame (and the previous frame's), the profiles, the SADs, a scratch state
@@ -2180,12 +1983,8 @@ bool frame_balance_ok(const char *fn, int num_rows, int num_cols_sbs, int num_co
 {
     const Balance bl = balance();
     if (!bl.mode) return true;
-    if (bgr_sbs && num_cols_sbs < 2 * num_cols) { // both eyes are gathered from the frame
-        char msg[200];
-        snprintf(msg, sizeof msg, "%s: a colour balance is set on this thread (stm_set_balance), which needs num_cols_sbs >= 2 * num_cols", fn);
-        fail(msg, "num_cols_sbs", __FILE__, __LINE__);
-        return false;
-    }
+    if (bgr_sbs && num_cols_sbs < 2 * num_cols) // both eyes are gathered from the frame
+        return STM_REJECT("num_cols_sbs", "%s: a colour balance is set on this thread (stm_set_balance), which needs num_cols_sbs >= 2 * num_cols", fn);
     return bl.mode != 2 || balance_size_ok(fn, num_rows, num_cols);
 }
 // the workspace the prelude below takes: the balanced frame (and the previous frame's), the histograms, a scratch state
@@ -2389,28 +2188,15 @@ void frame_tail(const FrameArgs &a, u8 *img_l, u8 *img_r, float *d_disp_l, float
 void frame_device(const char *fn, const FrameArgs &a, const u8 *d_img_sbs, float *d_disp_l, float *d_disp_r, u8 *d_interlaced,
                   const TemporalHist *hist, const Nv12Input *nv = nullptr)
 {
-    char msg[200];
     const int stages = a.stages;
-    if ((stages & 0x300) == 0x300) { // sub-pixel enhancement reads the last horizontal pass's input, which HSLO does not keep
-        snprintf(msg, sizeof msg, "%s: stages 0x200 (sub-pixel) together with 0x100 (HSLO) is not supported", fn);
-        fail(msg, "stages", __FILE__, __LINE__);
-        return;
-    }
-    if ((stages & 0x400) && (stages & 0xff) < 2) { // interpolation fills what the L/R check marked: stage 1 has no outlier maps
-        snprintf(msg, sizeof msg, "%s: stages 0x400 (outlier interpolation) needs the refinement stages (2 or 3)", fn);
-        fail(msg, "stages", __FILE__, __LINE__);
-        return;
-    }
-    if ((stages & 0x800) && (stages & 0xff) < 3) { // linear sampling changes the renderer only: stages 1 and 2 render nothing
-        snprintf(msg, sizeof msg, "%s: stages 0x800 (linear sampling of the warps) needs the rendering stage (3)", fn);
-        fail(msg, "stages", __FILE__, __LINE__);
-        return;
-    }
-    if (stages & 0x1000) { // guided up-sampling belongs to the reduced-resolution frame: here nothing is up-scaled
-        snprintf(msg, sizeof msg, "%s: stages 0x1000 (guided disparity up-sampling) needs the reduced-resolution frame (d_adcensus_stm_2s)", fn);
-        fail(msg, "stages", __FILE__, __LINE__);
-        return;
-    }
+    if ((stages & 0x300) == 0x300) // sub-pixel enhancement reads the last horizontal pass's input, which HSLO does not keep
+        return (void)STM_REJECT("stages", "%s: stages 0x200 (sub-pixel) together with 0x100 (HSLO) is not supported", fn);
+    if ((stages & 0x400) && (stages & 0xff) < 2) // interpolation fills what the L/R check marked: stage 1 has no outlier maps
+        return (void)STM_REJECT("stages", "%s: stages 0x400 (outlier interpolation) needs the refinement stages (2 or 3)", fn);
+    if ((stages & 0x800) && (stages & 0xff) < 3) // linear sampling changes the renderer only: stages 1 and 2 render nothing
+        return (void)STM_REJECT("stages", "%s: stages 0x800 (linear sampling of the warps) needs the rendering stage (3)", fn);
+    if (stages & 0x1000) // guided up-sampling belongs to the reduced-resolution frame: here nothing is up-scaled
+        return (void)STM_REJECT("stages", "%s: stages 0x1000 (guided disparity up-sampling) needs the reduced-resolution frame (d_adcensus_stm_2s)", fn);
     if (!frame_layout_ok(fn, a) || !frame_settings_ok(fn, a, nv)) return;
     const int H = a.num_rows, W = a.num_cols, N = a.num_views, elem_sz = a.elem_sz;
     const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
@@ -2471,21 +2257,15 @@ bool frame_packing_ok(const char *fn, const FrameArgs &a)
 bool packing_unsupported(const char *fn)
 {
     if (!packing().on()) return false;
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: a packing is set on this thread (stm_set_packing), which this call does not support: use d_adcensus_stm, "
-             "d_adcensus_stm_t or d_adcensus_stm_nv12", fn);
-    fail(msg, "packing", __FILE__, __LINE__);
-    return true;
+    return !STM_REJECT("packing", "%s: a packing is set on this thread (stm_set_packing), which this call does not support: use d_adcensus_stm, "
+                       "d_adcensus_stm_t or d_adcensus_stm_nv12", fn);
 }
 
 // the two output images of an NV12 call come together or not at all
 bool nv12_images_ok(const char *fn, const Nv12Input &nv)
 {
     if ((nv.img_l != nullptr) == (nv.img_r != nullptr)) return true;
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: d_img_l and d_img_r must be both null (the split images stay in the workspace) or both set", fn);
-    fail(msg, "d_img_l, d_img_r", __FILE__, __LINE__);
-    return false;
+    return STM_REJECT("d_img_l, d_img_r", "%s: d_img_l and d_img_r must be both null (the split images stay in the workspace) or both set", fn);
 }
 
 // `stages` bit 0x2000 of the four entries that take a history: the three parameters, then the pointers.  nv == nullptr: the
@@ -2508,30 +2288,21 @@ bool frame_history_ok(const char *fn, const FrameArgs &a, const TemporalHist &h,
     bool alias = false;
     for (int i = first; i < 4 && nset == all; ++i)
         for (int j = first; j < 4; ++j) alias = alias || bytes_overlap(hp[i], sz[i], out[j], sz[j]);
-    char msg[240];
-    const char *arg = nullptr;
-    if ((a.stages & 0xff) < 2) { // the step filters the refined maps: stage 1 has none
-        snprintf(msg, sizeof msg, "%s: stages 0x2000 (temporal stabilisation) needs the refinement stages (2 or 3)", fn);
-        arg = "stages";
-    } else if (split && !nv->img_l) { // this frame's converted images are the next frame's history: the caller must keep them
-        snprintf(msg, sizeof msg, "%s: stages 0x2000 (temporal stabilisation) needs the output images d_img_l and d_img_r", fn);
-        arg = "d_img_l, d_img_r";
-    } else if (nset != 0 && nset != all) {
-        snprintf(msg, sizeof msg, "%s: the %s history pointers must be all null (first frame) or all set", fn, split ? "four" : "three");
-        arg = split ? "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r" : "d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r";
-    } else if (nset == all && !split && !packing().on() && a.num_cols_sbs < 2 * a.num_cols) { // the views are read from the two halves in place
-        snprintf(msg, sizeof msg, "%s: stages 0x2000 (temporal stabilisation) needs num_cols_sbs >= 2 * num_cols", fn);
-        arg = "num_cols_sbs";
-    } else if (alias && split) {
-        snprintf(msg, sizeof msg, "%s: a history buffer must not alias an output (d_img_l, d_img_r, d_disp_l, d_disp_r)", fn);
-        arg = "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r";
-    } else if (alias) {
-        snprintf(msg, sizeof msg, "%s: a history map must not alias d_disp_l or d_disp_r", fn);
-        arg = "d_prev_disp_l, d_prev_disp_r";
-    }
-    if (arg) fail(msg, arg, __FILE__, __LINE__);
-    *run = !arg && nset == all;
-    return !arg;
+    if ((a.stages & 0xff) < 2) // the step filters the refined maps: stage 1 has none
+        return STM_REJECT("stages", "%s: stages 0x2000 (temporal stabilisation) needs the refinement stages (2 or 3)", fn);
+    if (split && !nv->img_l) // this frame's converted images are the next frame's history: the caller must keep them
+        return STM_REJECT("d_img_l, d_img_r", "%s: stages 0x2000 (temporal stabilisation) needs the output images d_img_l and d_img_r", fn);
+    if (nset != 0 && nset != all)
+        return STM_REJECT(split ? "d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r" : "d_prev_img_sbs, d_prev_disp_l, d_prev_disp_r",
+                          "%s: the %s history pointers must be all null (first frame) or all set", fn, split ? "four" : "three");
+    if (nset == all && !split && !packing().on() && a.num_cols_sbs < 2 * a.num_cols) // the views are read from the two halves in place
+        return STM_REJECT("num_cols_sbs", "%s: stages 0x2000 (temporal stabilisation) needs num_cols_sbs >= 2 * num_cols", fn);
+    if (alias && split)
+        return STM_REJECT("d_prev_img_l, d_prev_img_r, d_prev_disp_l, d_prev_disp_r",
+                          "%s: a history buffer must not alias an output (d_img_l, d_img_r, d_disp_l, d_disp_r)", fn);
+    if (alias) return STM_REJECT("d_prev_disp_l, d_prev_disp_r", "%s: a history map must not alias d_disp_l or d_disp_r", fn);
+    *run = nset == all;
+    return true;
 }
 
 // adcensus_stm_2, d_io.cu:240-508: the disparity is computed on a bilinearly reduced pair
@@ -2549,19 +2320,12 @@ bool reduced_args_ok(const char *fn, const FrameArgs &a, bool temporal_ok = fals
                       {"num_disp", a.num_disp, 1}}))
         return false;
     if (packing_unsupported(fn)) return false;
-    char msg[200];
     const int stages = a.stages;
-    if ((stages & 0xff) != 3 || (stages & ~(temporal_ok ? 0x3fff : 0x1fff))) { // this path always renders
-        snprintf(msg, sizeof msg, "%s: stages = 0x%x, must be 3, optionally OR-ed with 0x100, 0x200, 0x400, 0x800%s 0x1000%s", fn, stages,
-                 temporal_ok ? "," : " and", temporal_ok ? " and 0x2000" : "");
-        fail(msg, "stages", __FILE__, __LINE__);
-        return false;
-    }
-    if ((stages & 0x300) == 0x300) { // as d_adcensus_stm
-        snprintf(msg, sizeof msg, "%s: stages 0x200 (sub-pixel) together with 0x100 (HSLO) is not supported", fn);
-        fail(msg, "stages", __FILE__, __LINE__);
-        return false;
-    }
+    if ((stages & 0xff) != 3 || (stages & ~(temporal_ok ? 0x3fff : 0x1fff))) // this path always renders
+        return STM_REJECT("stages", "%s: stages = 0x%x, must be 3, optionally OR-ed with 0x100, 0x200, 0x400, 0x800%s 0x1000%s", fn, stages,
+                          temporal_ok ? "," : " and", temporal_ok ? " and 0x2000" : "");
+    if ((stages & 0x300) == 0x300) // as d_adcensus_stm
+        return STM_REJECT("stages", "%s: stages 0x200 (sub-pixel) together with 0x100 (HSLO) is not supported", fn);
     return true;
 }
 
@@ -2679,11 +2443,8 @@ void stm_d_adcensus_stm(unsigned char *d_img_sbs, float *d_disp_l, float *d_disp
     const char *fn = "d_adcensus_stm";
     const FrameArgs a = {STM_FRAME_PARAMS, stages};
     if (!frame_dims_ok(fn, a) || !frame_packing_ok(fn, a)) return;
-    if (stages & 0x2000) { // temporal stabilisation needs the previous frame: this call has no arguments for it
-        fail("d_adcensus_stm: stages 0x2000 (temporal stabilisation) needs the history arguments of d_adcensus_stm_t", "stages", __FILE__,
-             __LINE__);
-        return;
-    }
+    if (stages & 0x2000) // temporal stabilisation needs the previous frame: this call has no arguments for it
+        return (void)STM_REJECT("stages", "d_adcensus_stm: stages 0x2000 (temporal stabilisation) needs the history arguments of d_adcensus_stm_t");
     frame_device(fn, a, d_img_sbs, d_disp_l, d_disp_r, d_interlaced, nullptr);
 }
 
@@ -2791,12 +2552,8 @@ bool front_low_args_ok(const char *fn, int num_rows, int num_cols_sbs, int num_c
     if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols_sbs", num_cols_sbs, 1}, {"num_cols", num_cols, 1},
                       {"num_rows_disp", num_rows_disp, 1}, {"num_cols_disp", num_cols_disp, 1}, {"elem_sz", elem_sz, 3}}))
         return false;
-    if ((census_l != nullptr) != (census_r != nullptr)) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: the two census planes must be both null or both set", fn);
-        fail(msg, "census_l, census_r", __FILE__, __LINE__);
-        return false;
-    }
+    if ((census_l != nullptr) != (census_r != nullptr))
+        return STM_REJECT("census_l, census_r", "%s: the two census planes must be both null or both set", fn);
     return true;
 }
 // inside a Workspace scope; cen_l / cen_r both null: the census words stay in the workspace

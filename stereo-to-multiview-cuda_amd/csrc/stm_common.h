@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <initializer_list>
 
 typedef unsigned char u8;
 
@@ -11,6 +12,15 @@ namespace stm {
 
 // ---- error handling: reference semantics (cuda_utils.h:12-21) = message + exit(1) ----
 void fail(const char *what, const char *expr, const char *file, int line);
+// A refused argument: fail() with the printf-formatted message and `arg` as its expression.  Returns false, so a screen reads
+// `if (bad) return STM_REJECT("arg", "%s: arg = %d, must be ...", fn, arg);` and an entry that answers -1
+// `if (bad) return STM_REJECT(...) ? 0 : -1;`.  The macro hands on the rule's own file and line.
+bool reject(const char *file, int line, const char *arg, const char *fmt, ...) __attribute__((format(printf, 4, 5)));
+#define STM_REJECT(arg, ...) ::stm::reject(__FILE__, __LINE__, arg, __VA_ARGS__)
+// the null-pointer rule of a screen: "a must not be null", "a and b must not be null", "a, b and c must not be null" (the names of all
+// the pointers, whichever is null; the expression is "a, b, c"); false with the error recorded
+struct NamedPtr { const char *name; const void *p; };
+bool ptrs_ok(const char *fn, std::initializer_list<NamedPtr> ptrs);
 // Error mode 1 (record and return, stm_set_error_mode): a failure is STICKY for the rest of the API call on this thread --
 // every later kernel launch of the call is skipped (STM_LAUNCH) and the workspace hands out no memory, so a failed
 // allocation can never turn into a kernel running on a null or stale pointer.  Each API entry point clears the flag.

@@ -6,6 +6,7 @@
 #include <float.h>
 #include <math.h>
 #include <cmath>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -38,6 +39,28 @@ void fail(const char *what, const char *expr, const char *file, int line)
     fprintf(stderr, "%s\n", buf);
     if (g_error_mode == 0)
         exit(1); // cuda_utils.h:15-20
+}
+bool reject(const char *file, int line, const char *arg, const char *fmt, ...)
+{
+    char msg[512]; // the longest message of any screen stays below 300 bytes; vsnprintf cuts a longer one short
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(msg, sizeof msg, fmt, ap);
+    va_end(ap);
+    fail(msg, arg, file, line);
+    return false;
+}
+bool ptrs_ok(const char *fn, std::initializer_list<NamedPtr> ptrs)
+{
+    bool ok = true;
+    std::string all, list;
+    size_t k = 0;
+    for (const NamedPtr &p : ptrs) {
+        ok = ok && p.p != nullptr;
+        all += (k == 0 ? "" : k + 1 == ptrs.size() ? " and " : ", ") + std::string(p.name);
+        list += (k++ == 0 ? "" : ", ") + std::string(p.name);
+    }
+    return ok || STM_REJECT(list.c_str(), "%s: %s must not be null", fn, all.c_str());
 }
 
 // ------------------------------------------------------------------ stream
@@ -241,26 +264,13 @@ Lens lens() { return g_lens; }
 void set_lens(const Lens &l) { g_lens = l; }
 bool lens_params_ok(const char *fn, int mode, int mode_lo, int mode_hi, double pitch, double slope, double centre)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (mode < mode_lo || mode > mode_hi) {
-        snprintf(msg, sizeof msg, "%s: lens mode = %d, must be in %d .. %d", fn, mode, mode_lo, mode_hi);
-        arg = "mode";
-    } else if (mode == 0) {
-        return true; // off: the other arguments are ignored
-    } else if (!(pitch >= 1.0) || std::isinf(pitch)) { // NaN fails the comparison
-        snprintf(msg, sizeof msg, "%s: lens pitch = %g, must be finite and >= 1 (sub-pixels per lens)", fn, pitch);
-        arg = "pitch";
-    } else if (!std::isfinite(slope)) {
-        snprintf(msg, sizeof msg, "%s: lens slope = %g, must be finite", fn, slope);
-        arg = "slope";
-    } else if (!std::isfinite(centre)) {
-        snprintf(msg, sizeof msg, "%s: lens centre = %g, must be finite", fn, centre);
-        arg = "centre";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (mode < mode_lo || mode > mode_hi) return STM_REJECT("mode", "%s: lens mode = %d, must be in %d .. %d", fn, mode, mode_lo, mode_hi);
+    if (mode == 0) return true; // off: the other arguments are ignored
+    if (!(pitch >= 1.0) || std::isinf(pitch)) // NaN fails the comparison
+        return STM_REJECT("pitch", "%s: lens pitch = %g, must be finite and >= 1 (sub-pixels per lens)", fn, pitch);
+    if (!std::isfinite(slope)) return STM_REJECT("slope", "%s: lens slope = %g, must be finite", fn, slope);
+    if (!std::isfinite(centre)) return STM_REJECT("centre", "%s: lens centre = %g, must be finite", fn, centre);
+    return true;
 }
 
 // the calling thread's output geometry (stm_set_layout)
@@ -269,29 +279,15 @@ Layout layout() { return g_layout; }
 void set_layout(const Layout &l) { g_layout = l; }
 bool layout_params_ok(const char *fn, int layout, int tiles_x, int tiles_y, int order, int filter)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (layout != 0 && layout != 1) {
-        snprintf(msg, sizeof msg, "%s: layout = %d, must be 0 (interlaced) or 1 (quilt)", fn, layout);
-        arg = "layout";
-    } else if (layout == 0) {
-        return true; // interlaced: the other arguments are ignored
-    } else if (tiles_x < 1 || tiles_x > 65535) {
-        snprintf(msg, sizeof msg, "%s: tiles_x = %d, must be in 1 .. 65535", fn, tiles_x);
-        arg = "tiles_x";
-    } else if (tiles_y < 1 || tiles_y > 65535) {
-        snprintf(msg, sizeof msg, "%s: tiles_y = %d, must be in 1 .. 65535", fn, tiles_y);
-        arg = "tiles_y";
-    } else if (order < 0 || order > 3) {
-        snprintf(msg, sizeof msg, "%s: order = %d, must be 0 .. 3 (bit 0: tile rows bottom-up, bit 1: view order reversed)", fn, order);
-        arg = "order";
-    } else if (filter != 0 && filter != 1) {
-        snprintf(msg, sizeof msg, "%s: filter = %d, must be 0 (four-neighbour sampler) or 1 (area average)", fn, filter);
-        arg = "filter";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (layout != 0 && layout != 1) return STM_REJECT("layout", "%s: layout = %d, must be 0 (interlaced) or 1 (quilt)", fn, layout);
+    if (layout == 0) return true; // interlaced: the other arguments are ignored
+    if (tiles_x < 1 || tiles_x > 65535) return STM_REJECT("tiles_x", "%s: tiles_x = %d, must be in 1 .. 65535", fn, tiles_x);
+    if (tiles_y < 1 || tiles_y > 65535) return STM_REJECT("tiles_y", "%s: tiles_y = %d, must be in 1 .. 65535", fn, tiles_y);
+    if (order < 0 || order > 3)
+        return STM_REJECT("order", "%s: order = %d, must be 0 .. 3 (bit 0: tile rows bottom-up, bit 1: view order reversed)", fn, order);
+    if (filter != 0 && filter != 1)
+        return STM_REJECT("filter", "%s: filter = %d, must be 0 (four-neighbour sampler) or 1 (area average)", fn, filter);
+    return true;
 }
 // the calling thread's output format (stm_set_output)
 static thread_local Output g_output = {0, 0, 0, 0};
@@ -299,26 +295,13 @@ Output output() { return g_output; }
 void set_output(const Output &o) { g_output = o; }
 bool output_params_ok(const char *fn, int format, int matrix, int pitch, int uv_row)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (format != 0 && format != 1) {
-        snprintf(msg, sizeof msg, "%s: format = %d, must be 0 (BGR) or 1 (NV12)", fn, format);
-        arg = "format";
-    } else if (format == 0) {
-        return true; // BGR: the other arguments are ignored
-    } else if (matrix < 0 || matrix > 3) {
-        snprintf(msg, sizeof msg, "%s: matrix = %d, must be 0 (BT.601 limited), 1 (BT.709 limited), 2 (BT.601 full) or 3 (BT.709 full)", fn, matrix);
-        arg = "matrix";
-    } else if (pitch < 0) {
-        snprintf(msg, sizeof msg, "%s: pitch = %d, must be >= 0 (0: num_cols_out)", fn, pitch);
-        arg = "pitch";
-    } else if (uv_row < 0) {
-        snprintf(msg, sizeof msg, "%s: uv_row = %d, must be >= 0 (0: num_rows_out)", fn, uv_row);
-        arg = "uv_row";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (format != 0 && format != 1) return STM_REJECT("format", "%s: format = %d, must be 0 (BGR) or 1 (NV12)", fn, format);
+    if (format == 0) return true; // BGR: the other arguments are ignored
+    if (matrix < 0 || matrix > 3)
+        return STM_REJECT("matrix", "%s: matrix = %d, must be 0 (BT.601 limited), 1 (BT.709 limited), 2 (BT.601 full) or 3 (BT.709 full)", fn, matrix);
+    if (pitch < 0) return STM_REJECT("pitch", "%s: pitch = %d, must be >= 0 (0: num_cols_out)", fn, pitch);
+    if (uv_row < 0) return STM_REJECT("uv_row", "%s: uv_row = %d, must be >= 0 (0: num_rows_out)", fn, uv_row);
+    return true;
 }
 // the calling thread's overlay (stm_set_overlay)
 static thread_local Overlay g_overlay = {0, nullptr, 0, 0, 0, 0, 0.0f};
@@ -326,33 +309,16 @@ Overlay overlay() { return g_overlay; }
 void set_overlay(const Overlay &o) { g_overlay = o; }
 bool overlay_params_ok(const char *fn, const void *ov, bool check_ptr, int ov_rows, int ov_cols, int x0, int y0, float disparity)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (check_ptr && !ov) {
-        snprintf(msg, sizeof msg, "%s: the overlay is null", fn);
-        arg = "overlay";
-    } else if (check_ptr && ((uintptr_t)ov & 3) != 0) {
-        snprintf(msg, sizeof msg, "%s: the overlay must be 4-byte aligned (a pixel is read as one word)", fn);
-        arg = "overlay";
-    } else if (ov_rows < 1 || ov_rows > 65535) {
-        snprintf(msg, sizeof msg, "%s: ov_rows = %d, must be in 1 .. 65535", fn, ov_rows);
-        arg = "ov_rows";
-    } else if (ov_cols < 1 || ov_cols > 65535) {
-        snprintf(msg, sizeof msg, "%s: ov_cols = %d, must be in 1 .. 65535", fn, ov_cols);
-        arg = "ov_cols";
-    } else if (x0 < -65536 || x0 > 65536) {
-        snprintf(msg, sizeof msg, "%s: x0 = %d, must be in -65536 .. 65536", fn, x0);
-        arg = "x0";
-    } else if (y0 < -65536 || y0 > 65536) {
-        snprintf(msg, sizeof msg, "%s: y0 = %d, must be in -65536 .. 65536", fn, y0);
-        arg = "y0";
-    } else if (!(fabsf(disparity) <= 4096.0f)) { // NaN fails the comparison
-        snprintf(msg, sizeof msg, "%s: disparity = %g, must be finite and of magnitude <= 4096", fn, (double)disparity);
-        arg = "disparity";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (check_ptr && !ov) return STM_REJECT("overlay", "%s: the overlay is null", fn);
+    if (check_ptr && ((uintptr_t)ov & 3) != 0)
+        return STM_REJECT("overlay", "%s: the overlay must be 4-byte aligned (a pixel is read as one word)", fn);
+    if (ov_rows < 1 || ov_rows > 65535) return STM_REJECT("ov_rows", "%s: ov_rows = %d, must be in 1 .. 65535", fn, ov_rows);
+    if (ov_cols < 1 || ov_cols > 65535) return STM_REJECT("ov_cols", "%s: ov_cols = %d, must be in 1 .. 65535", fn, ov_cols);
+    if (x0 < -65536 || x0 > 65536) return STM_REJECT("x0", "%s: x0 = %d, must be in -65536 .. 65536", fn, x0);
+    if (y0 < -65536 || y0 > 65536) return STM_REJECT("y0", "%s: y0 = %d, must be in -65536 .. 65536", fn, y0);
+    if (!(fabsf(disparity) <= 4096.0f)) // NaN fails the comparison
+        return STM_REJECT("disparity", "%s: disparity = %g, must be finite and of magnitude <= 4096", fn, (double)disparity);
+    return true;
 }
 // the calling thread's test tap on the aggregation chain (stm_set_agg_tap)
 static thread_local AggTap g_agg_tap = {nullptr, nullptr, nullptr, nullptr};
@@ -366,45 +332,26 @@ void set_overlay_auto(const OverlayAuto &a) { g_overlay_auto = a; }
 bool overlay_auto_params_ok(const char *fn, int near_permille, float margin, int pad, float limit_lo, float limit_hi, float rate_near,
                             float rate_far)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (near_permille < 0 || near_permille > 499) {
-        snprintf(msg, sizeof msg, "%s: near_permille = %d, must be in 0 .. 499", fn, near_permille);
-        arg = "near_permille";
-    } else if (!(fabsf(margin) <= 4096.0f)) { // NaN fails the comparison
-        snprintf(msg, sizeof msg, "%s: margin = %g, must be finite and of magnitude <= 4096", fn, (double)margin);
-        arg = "margin";
-    } else if (pad < 0 || pad > 4096) {
-        snprintf(msg, sizeof msg, "%s: pad = %d, must be in 0 .. 4096", fn, pad);
-        arg = "pad";
-    } else if (!(fabsf(limit_lo) <= 4096.0f)) {
-        snprintf(msg, sizeof msg, "%s: limit_lo = %g, must be finite and of magnitude <= 4096", fn, (double)limit_lo);
-        arg = "limit_lo";
-    } else if (!(fabsf(limit_hi) <= 4096.0f)) {
-        snprintf(msg, sizeof msg, "%s: limit_hi = %g, must be finite and of magnitude <= 4096", fn, (double)limit_hi);
-        arg = "limit_hi";
-    } else if (!(limit_lo <= limit_hi)) {
-        snprintf(msg, sizeof msg, "%s: limit_lo = %g > limit_hi = %g", fn, (double)limit_lo, (double)limit_hi);
-        arg = "limit_lo, limit_hi";
-    } else if (!(rate_near > 0.0f && rate_near <= 1.0f)) {
-        snprintf(msg, sizeof msg, "%s: rate_near = %g, must be in (0, 1]", fn, (double)rate_near);
-        arg = "rate_near";
-    } else if (!(rate_far > 0.0f && rate_far <= 1.0f)) {
-        snprintf(msg, sizeof msg, "%s: rate_far = %g, must be in (0, 1]", fn, (double)rate_far);
-        arg = "rate_far";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (near_permille < 0 || near_permille > 499)
+        return STM_REJECT("near_permille", "%s: near_permille = %d, must be in 0 .. 499", fn, near_permille);
+    if (!(fabsf(margin) <= 4096.0f)) // NaN fails the comparison
+        return STM_REJECT("margin", "%s: margin = %g, must be finite and of magnitude <= 4096", fn, (double)margin);
+    if (pad < 0 || pad > 4096) return STM_REJECT("pad", "%s: pad = %d, must be in 0 .. 4096", fn, pad);
+    if (!(fabsf(limit_lo) <= 4096.0f))
+        return STM_REJECT("limit_lo", "%s: limit_lo = %g, must be finite and of magnitude <= 4096", fn, (double)limit_lo);
+    if (!(fabsf(limit_hi) <= 4096.0f))
+        return STM_REJECT("limit_hi", "%s: limit_hi = %g, must be finite and of magnitude <= 4096", fn, (double)limit_hi);
+    if (!(limit_lo <= limit_hi))
+        return STM_REJECT("limit_lo, limit_hi", "%s: limit_lo = %g > limit_hi = %g", fn, (double)limit_lo, (double)limit_hi);
+    if (!(rate_near > 0.0f && rate_near <= 1.0f)) return STM_REJECT("rate_near", "%s: rate_near = %g, must be in (0, 1]", fn, (double)rate_near);
+    if (!(rate_far > 0.0f && rate_far <= 1.0f)) return STM_REJECT("rate_far", "%s: rate_far = %g, must be in (0, 1]", fn, (double)rate_far);
+    return true;
 }
 bool overlay_fit_size_ok(const char *fn, int num_rows, int num_cols)
 {
     if ((size_t)num_rows * num_cols <= 0x7fffffffu) return true;
-    char msg[160];
-    snprintf(msg, sizeof msg, "%s: num_rows * num_cols = %zu, must be below 2^31 (the overlay's fit counts in 32 bits)", fn,
-             (size_t)num_rows * num_cols);
-    fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
-    return false;
+    return STM_REJECT("num_rows, num_cols", "%s: num_rows * num_cols = %zu, must be below 2^31 (the overlay's fit counts in 32 bits)", fn,
+                      (size_t)num_rows * num_cols);
 }
 // stm_mux_nv12's coefficients (stm_hip.h): each rounded one computed in double and rounded to nearest, the three derived ones by
 // subtraction, so that white lands on the range's end and every grey on 128 / 128
@@ -452,27 +399,14 @@ Packing packing() { return g_packing; }
 void set_packing(const Packing &p) { g_packing = p; }
 bool packing_params_ok(const char *fn, const Packing &pk)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (pk.packing < 0 || pk.packing > 3) {
-        snprintf(msg, sizeof msg, "%s: packing = %d, must be 0 (side by side), 1 (half-width side by side), 2 (top and bottom) or 3 (half-height top and bottom)", fn, pk.packing);
-        arg = "packing";
-    } else if (pk.swap != 0 && pk.swap != 1) {
-        snprintf(msg, sizeof msg, "%s: swap = %d, must be 0 (left eye first) or 1 (right eye first)", fn, pk.swap);
-        arg = "swap";
-    } else if (pk.filter != 0 && pk.filter != 1) {
-        snprintf(msg, sizeof msg, "%s: filter = %d, must be 0 (linear) or 1 (Catmull-Rom)", fn, pk.filter);
-        arg = "filter";
-    } else if (pk.gap < 0 || pk.gap > (1 << 24)) {
-        snprintf(msg, sizeof msg, "%s: gap = %d, must be >= 0 (and at most 2^24)", fn, pk.gap);
-        arg = "gap";
-    } else if (pk.filter != 0 && (pk.packing & 1) == 0) {
-        snprintf(msg, sizeof msg, "%s: filter = %d with packing = %d: a full packing copies, the filter must be 0", fn, pk.filter, pk.packing);
-        arg = "filter";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (pk.packing < 0 || pk.packing > 3)
+        return STM_REJECT("packing", "%s: packing = %d, must be 0 (side by side), 1 (half-width side by side), 2 (top and bottom) or 3 (half-height top and bottom)", fn, pk.packing);
+    if (pk.swap != 0 && pk.swap != 1) return STM_REJECT("swap", "%s: swap = %d, must be 0 (left eye first) or 1 (right eye first)", fn, pk.swap);
+    if (pk.filter != 0 && pk.filter != 1) return STM_REJECT("filter", "%s: filter = %d, must be 0 (linear) or 1 (Catmull-Rom)", fn, pk.filter);
+    if (pk.gap < 0 || pk.gap > (1 << 24)) return STM_REJECT("gap", "%s: gap = %d, must be >= 0 (and at most 2^24)", fn, pk.gap);
+    if (pk.filter != 0 && (pk.packing & 1) == 0)
+        return STM_REJECT("filter", "%s: filter = %d with packing = %d: a full packing copies, the filter must be 0", fn, pk.filter, pk.packing);
+    return true;
 }
 
 // the calling thread's depth budget (stm_set_depth, stm_set_depth_auto)
@@ -481,23 +415,12 @@ Depth depth() { return g_depth; }
 void set_depth(const Depth &d) { g_depth = d; }
 bool depth_params_ok(const char *fn, int mode, float gain, float conv)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (mode < 0 || mode > 2) {
-        snprintf(msg, sizeof msg, "%s: depth mode = %d, must be 0 (off), 1 (manual) or 2 (automatic)", fn, mode);
-        arg = "mode";
-    } else if (mode != 1) {
-        return true; // off / automatic: gain and conv are ignored
-    } else if (!(gain >= 0.0f && gain <= 8.0f)) { // NaN fails the comparison
-        snprintf(msg, sizeof msg, "%s: depth gain = %g, must be in [0, 8]", fn, (double)gain);
-        arg = "gain";
-    } else if (!(fabsf(conv) <= 4096.0f)) {
-        snprintf(msg, sizeof msg, "%s: depth conv = %g, must be finite with |conv| <= 4096", fn, (double)conv);
-        arg = "conv";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (mode < 0 || mode > 2) return STM_REJECT("mode", "%s: depth mode = %d, must be 0 (off), 1 (manual) or 2 (automatic)", fn, mode);
+    if (mode != 1) return true; // off / automatic: gain and conv are ignored
+    if (!(gain >= 0.0f && gain <= 8.0f)) // NaN fails the comparison
+        return STM_REJECT("gain", "%s: depth gain = %g, must be in [0, 8]", fn, (double)gain);
+    if (!(fabsf(conv) <= 4096.0f)) return STM_REJECT("conv", "%s: depth conv = %g, must be finite with |conv| <= 4096", fn, (double)conv);
+    return true;
 }
 // the calling thread's view antialiasing (stm_set_antialias)
 static thread_local Antialias g_antialias = {0, 0.0f, 0, 0.0f};
@@ -505,21 +428,11 @@ Antialias antialias() { return g_antialias; }
 void set_antialias(const Antialias &a) { g_antialias = a; }
 bool antialias_params_ok(const char *fn, float strength, int max_radius, float gate)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (!(strength >= 0.0f && strength <= 8.0f)) { // NaN fails the comparison
-        snprintf(msg, sizeof msg, "%s: antialias strength = %g, must be in [0, 8]", fn, (double)strength);
-        arg = "strength";
-    } else if (max_radius < 1 || max_radius > 16) {
-        snprintf(msg, sizeof msg, "%s: antialias max_radius = %d, must be in 1 .. 16", fn, max_radius);
-        arg = "max_radius";
-    } else if (!(gate >= 0.0f && gate <= FLT_MAX)) {
-        snprintf(msg, sizeof msg, "%s: antialias gate = %g, must be finite and >= 0", fn, (double)gate);
-        arg = "gate";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (!(strength >= 0.0f && strength <= 8.0f)) // NaN fails the comparison
+        return STM_REJECT("strength", "%s: antialias strength = %g, must be in [0, 8]", fn, (double)strength);
+    if (max_radius < 1 || max_radius > 16) return STM_REJECT("max_radius", "%s: antialias max_radius = %d, must be in 1 .. 16", fn, max_radius);
+    if (!(gate >= 0.0f && gate <= FLT_MAX)) return STM_REJECT("gate", "%s: antialias gate = %g, must be finite and >= 0", fn, (double)gate);
+    return true;
 }
 // the calling thread's vertical alignment (stm_set_align, stm_set_align_auto)
 static thread_local Align g_align = {0, 0.0f, 0.0f, 0.0f, 16, 1.0f, nullptr};
@@ -527,57 +440,28 @@ Align align() { return g_align; }
 void set_align(const Align &a) { g_align = a; }
 bool align_params_ok(const char *fn, int mode, float a, float b, float c)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (mode < 0 || mode > 2) {
-        snprintf(msg, sizeof msg, "%s: align mode = %d, must be 0 (off), 1 (manual) or 2 (automatic)", fn, mode);
-        arg = "mode";
-    } else if (mode != 1) {
-        return true; // off / automatic: a, b and c are ignored
-    } else if (!(fabsf(a) <= FLT_MAX)) { // NaN fails the comparison
-        snprintf(msg, sizeof msg, "%s: align a = %g, must be finite", fn, (double)a);
-        arg = "a";
-    } else if (!(fabsf(b) <= FLT_MAX)) {
-        snprintf(msg, sizeof msg, "%s: align b = %g, must be finite", fn, (double)b);
-        arg = "b";
-    } else if (!(fabsf(c) <= FLT_MAX)) {
-        snprintf(msg, sizeof msg, "%s: align c = %g, must be finite", fn, (double)c);
-        arg = "c";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (mode < 0 || mode > 2) return STM_REJECT("mode", "%s: align mode = %d, must be 0 (off), 1 (manual) or 2 (automatic)", fn, mode);
+    if (mode != 1) return true; // off / automatic: a, b and c are ignored
+    if (!(fabsf(a) <= FLT_MAX)) return STM_REJECT("a", "%s: align a = %g, must be finite", fn, (double)a); // NaN fails the comparison
+    if (!(fabsf(b) <= FLT_MAX)) return STM_REJECT("b", "%s: align b = %g, must be finite", fn, (double)b);
+    if (!(fabsf(c) <= FLT_MAX)) return STM_REJECT("c", "%s: align c = %g, must be finite", fn, (double)c);
+    return true;
 }
 bool align_auto_params_ok(const char *fn, int radius, float rate)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (radius < 1 || radius > 32) {
-        snprintf(msg, sizeof msg, "%s: radius = %d, must be in 1 .. 32", fn, radius);
-        arg = "radius";
-    } else if (!(rate > 0.0f && rate <= 1.0f)) {
-        snprintf(msg, sizeof msg, "%s: rate = %g, must be in (0, 1]", fn, (double)rate);
-        arg = "rate";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (radius < 1 || radius > 32) return STM_REJECT("radius", "%s: radius = %d, must be in 1 .. 32", fn, radius);
+    if (!(rate > 0.0f && rate <= 1.0f)) return STM_REJECT("rate", "%s: rate = %g, must be in (0, 1]", fn, (double)rate);
+    return true;
 }
 bool align_size_ok(const char *fn, int num_rows, int num_cols)
 {
-    char msg[200];
-    if (num_rows < 4 || num_cols < 8) {
-        snprintf(msg, sizeof msg, "%s: the alignment measurement needs num_rows >= 4 and num_cols >= 8 (got %d x %d)", fn, num_rows, num_cols);
-        fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
-        return false;
-    }
+    if (num_rows < 4 || num_cols < 8)
+        return STM_REJECT("num_rows, num_cols", "%s: the alignment measurement needs num_rows >= 4 and num_cols >= 8 (got %d x %d)", fn, num_rows,
+                          num_cols);
     // a block's sum of |G_L - G_R| is at most 510 (W/8 + 1) (H/4 + 1), kept in 32 bits
-    if ((unsigned long long)(num_rows / 4 + 1) * (unsigned long long)(num_cols / 8 + 1) > 0xffffffffull / 510) {
-        snprintf(msg, sizeof msg, "%s: the alignment measurement needs (num_rows/4 + 1) * (num_cols/8 + 1) <= %llu (got %d x %d)", fn,
-                 0xffffffffull / 510, num_rows, num_cols);
-        fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
-        return false;
-    }
+    if ((unsigned long long)(num_rows / 4 + 1) * (unsigned long long)(num_cols / 8 + 1) > 0xffffffffull / 510)
+        return STM_REJECT("num_rows, num_cols", "%s: the alignment measurement needs (num_rows/4 + 1) * (num_cols/8 + 1) <= %llu (got %d x %d)", fn,
+                          0xffffffffull / 510, num_rows, num_cols);
     return true;
 }
 // the calling thread's colour balance (stm_set_balance, stm_set_balance_auto)
@@ -596,41 +480,20 @@ Balance balance() { return g_balance; }
 void set_balance(const Balance &b) { g_balance = b; }
 bool balance_params_ok(const char *fn, int mode, const u8 *lut768)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (mode < 0 || mode > 2) {
-        snprintf(msg, sizeof msg, "%s: balance mode = %d, must be 0 (off), 1 (given) or 2 (measured)", fn, mode);
-        arg = "mode";
-    } else if (mode == 1 && !lut768) { // off / measured: lut768 is ignored
-        snprintf(msg, sizeof msg, "%s: lut768 must not be null in mode 1", fn);
-        arg = "lut768";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (mode < 0 || mode > 2) return STM_REJECT("mode", "%s: balance mode = %d, must be 0 (off), 1 (given) or 2 (measured)", fn, mode);
+    if (mode == 1 && !lut768) return STM_REJECT("lut768", "%s: lut768 must not be null in mode 1", fn); // off / measured: lut768 is ignored
+    return true;
 }
 bool balance_auto_params_ok(const char *fn, int max_shift, float rate)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (max_shift < 0 || max_shift > 255) {
-        snprintf(msg, sizeof msg, "%s: max_shift = %d, must be in 0 .. 255", fn, max_shift);
-        arg = "max_shift";
-    } else if (!(rate > 0.0f && rate <= 1.0f)) { // NaN fails the comparison
-        snprintf(msg, sizeof msg, "%s: rate = %g, must be in (0, 1]", fn, (double)rate);
-        arg = "rate";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (max_shift < 0 || max_shift > 255) return STM_REJECT("max_shift", "%s: max_shift = %d, must be in 0 .. 255", fn, max_shift);
+    if (!(rate > 0.0f && rate <= 1.0f)) return STM_REJECT("rate", "%s: rate = %g, must be in (0, 1]", fn, (double)rate); // NaN fails the comparison
+    return true;
 }
 bool balance_size_ok(const char *fn, int num_rows, int num_cols)
 {
     if ((long long)num_rows * (long long)num_cols < (1ll << 31)) return true;
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: the balance measurement needs num_rows * num_cols < 2147483648 (got %d x %d)", fn, num_rows, num_cols);
-    fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
-    return false;
+    return STM_REJECT("num_rows, num_cols", "%s: the balance measurement needs num_rows * num_cols < 2147483648 (got %d x %d)", fn, num_rows, num_cols);
 }
 int balance_rate_q(float rate)
 {
@@ -644,27 +507,17 @@ Cut cut() { return g_cut; }
 void set_cut(const Cut &c) { g_cut = c; }
 bool cut_params_ok(const char *fn, int thresh_permille, int min_gap)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (thresh_permille < 1 || thresh_permille > 1000) {
-        snprintf(msg, sizeof msg, "%s: thresh_permille = %d, must be in 1 .. 1000", fn, thresh_permille);
-        arg = "thresh_permille";
-    } else if (min_gap < 1 || min_gap > (1 << 20)) {
-        snprintf(msg, sizeof msg, "%s: min_gap = %d, must be in 1 .. 1048576", fn, min_gap);
-        arg = "min_gap";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (thresh_permille < 1 || thresh_permille > 1000)
+        return STM_REJECT("thresh_permille", "%s: thresh_permille = %d, must be in 1 .. 1000", fn, thresh_permille);
+    if (min_gap < 1 || min_gap > (1 << 20)) return STM_REJECT("min_gap", "%s: min_gap = %d, must be in 1 .. 1048576", fn, min_gap);
+    return true;
 }
 bool cut_size_ok(const char *fn, int num_rows, int num_cols)
 {
     if (num_rows >= 4 && num_cols >= 4 && (long long)num_rows * (long long)num_cols < (1ll << 31)) return true;
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: the shot-change detector needs num_rows, num_cols >= 4 and num_rows * num_cols < 2147483648 (got %d x %d)", fn,
-             num_rows, num_cols);
-    fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
-    return false;
+    return STM_REJECT("num_rows, num_cols",
+                      "%s: the shot-change detector needs num_rows, num_cols >= 4 and num_rows * num_cols < 2147483648 (got %d x %d)", fn, num_rows,
+                      num_cols);
 }
 // the calling thread's active picture area (stm_set_active, stm_set_active_auto)
 Active active_default() { return Active{0, {0, 0, 0, 0}, 0, 0.0f, 24, 10, 300, 12, nullptr}; }
@@ -673,90 +526,46 @@ Active active() { return g_active; }
 void set_active(const Active &a) { g_active = a; }
 bool active_params_ok(const char *fn, int mode, const int *rect, int fill, float fill_disp)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (mode < 0 || mode > 2) {
-        snprintf(msg, sizeof msg, "%s: active mode = %d, must be 0 (off), 1 (given) or 2 (measured)", fn, mode);
-        arg = "mode";
-    } else if (mode == 0) { // off: the other arguments are ignored
-        return true;
-    } else if (mode == 1 && !rect) {
-        snprintf(msg, sizeof msg, "%s: rect must not be null in mode 1", fn);
-        arg = "rect";
-    } else if (mode == 1 && !(rect[0] >= 0 && rect[0] < rect[1] && rect[2] >= 0 && rect[2] < rect[3])) {
-        snprintf(msg, sizeof msg, "%s: rect = {%d, %d, %d, %d}, must hold 0 <= top < bottom and 0 <= left < right", fn, rect[0], rect[1], rect[2],
-                 rect[3]);
-        arg = "rect";
-    } else if (fill != 0 && fill != 1) {
-        snprintf(msg, sizeof msg, "%s: fill = %d, must be 0 or 1", fn, fill);
-        arg = "fill";
-    } else if (!(fabsf(fill_disp) <= 4096.0f)) { // NaN fails the comparison
-        snprintf(msg, sizeof msg, "%s: fill_disp = %g, must be finite and of magnitude <= 4096", fn, (double)fill_disp);
-        arg = "fill_disp";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (mode < 0 || mode > 2) return STM_REJECT("mode", "%s: active mode = %d, must be 0 (off), 1 (given) or 2 (measured)", fn, mode);
+    if (mode == 0) return true; // off: the other arguments are ignored
+    if (mode == 1 && !rect) return STM_REJECT("rect", "%s: rect must not be null in mode 1", fn);
+    if (mode == 1 && !(rect[0] >= 0 && rect[0] < rect[1] && rect[2] >= 0 && rect[2] < rect[3]))
+        return STM_REJECT("rect", "%s: rect = {%d, %d, %d, %d}, must hold 0 <= top < bottom and 0 <= left < right", fn, rect[0], rect[1], rect[2],
+                          rect[3]);
+    if (fill != 0 && fill != 1) return STM_REJECT("fill", "%s: fill = %d, must be 0 or 1", fn, fill);
+    if (!(fabsf(fill_disp) <= 4096.0f)) // NaN fails the comparison
+        return STM_REJECT("fill_disp", "%s: fill_disp = %g, must be finite and of magnitude <= 4096", fn, (double)fill_disp);
+    return true;
 }
 bool active_auto_params_ok(const char *fn, int thresh_luma, int lit_permille, int max_bar_permille, int hold)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (thresh_luma < 0 || thresh_luma > 254) {
-        snprintf(msg, sizeof msg, "%s: thresh_luma = %d, must be in 0 .. 254", fn, thresh_luma);
-        arg = "thresh_luma";
-    } else if (lit_permille < 0 || lit_permille > 999) {
-        snprintf(msg, sizeof msg, "%s: lit_permille = %d, must be in 0 .. 999", fn, lit_permille);
-        arg = "lit_permille";
-    } else if (max_bar_permille < 0 || max_bar_permille > 450) {
-        snprintf(msg, sizeof msg, "%s: max_bar_permille = %d, must be in 0 .. 450", fn, max_bar_permille);
-        arg = "max_bar_permille";
-    } else if (hold < 1 || hold > (1 << 20)) {
-        snprintf(msg, sizeof msg, "%s: hold = %d, must be in 1 .. 1048576", fn, hold);
-        arg = "hold";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (thresh_luma < 0 || thresh_luma > 254) return STM_REJECT("thresh_luma", "%s: thresh_luma = %d, must be in 0 .. 254", fn, thresh_luma);
+    if (lit_permille < 0 || lit_permille > 999) return STM_REJECT("lit_permille", "%s: lit_permille = %d, must be in 0 .. 999", fn, lit_permille);
+    if (max_bar_permille < 0 || max_bar_permille > 450)
+        return STM_REJECT("max_bar_permille", "%s: max_bar_permille = %d, must be in 0 .. 450", fn, max_bar_permille);
+    if (hold < 1 || hold > (1 << 20)) return STM_REJECT("hold", "%s: hold = %d, must be in 1 .. 1048576", fn, hold);
+    return true;
 }
 bool active_size_ok(const char *fn, int num_rows, int num_cols)
 {
     if ((long long)num_rows * (long long)num_cols < (1ll << 31)) return true;
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: the active area needs num_rows * num_cols < 2147483648 (got %d x %d)", fn, num_rows, num_cols);
-    fail(msg, "num_rows, num_cols", __FILE__, __LINE__);
-    return false;
+    return STM_REJECT("num_rows, num_cols", "%s: the active area needs num_rows * num_cols < 2147483648 (got %d x %d)", fn, num_rows, num_cols);
 }
 bool active_rect_ok(const char *fn, const int *rect, int num_rows, int num_cols)
 {
     if (rect[0] >= 0 && rect[0] < rect[1] && rect[1] <= num_rows && rect[2] >= 0 && rect[2] < rect[3] && rect[3] <= num_cols) return true;
-    char msg[240];
-    snprintf(msg, sizeof msg, "%s: the active rectangle {%d, %d, %d, %d} must hold 0 <= top < bottom <= num_rows = %d and 0 <= left < right <= "
-             "num_cols = %d", fn, rect[0], rect[1], rect[2], rect[3], num_rows, num_cols);
-    fail(msg, "rect", __FILE__, __LINE__);
-    return false;
+    return STM_REJECT("rect", "%s: the active rectangle {%d, %d, %d, %d} must hold 0 <= top < bottom <= num_rows = %d and 0 <= left < right <= "
+                      "num_cols = %d", fn, rect[0], rect[1], rect[2], rect[3], num_rows, num_cols);
 }
 bool depth_auto_params_ok(const char *fn, float disp_lo, float disp_hi, float max_gain, int clip_permille, float rate)
 {
-    char msg[200];
-    const char *arg = nullptr;
-    if (!(fabsf(disp_lo) <= 4096.0f) || !(fabsf(disp_hi) <= 4096.0f) || !(disp_lo < disp_hi)) {
-        snprintf(msg, sizeof msg, "%s: depth budget [%g, %g]: disp_lo < disp_hi, both finite and of magnitude <= 4096", fn, (double)disp_lo,
-                 (double)disp_hi);
-        arg = "disp_lo, disp_hi";
-    } else if (!(max_gain > 0.0f && max_gain <= 8.0f)) {
-        snprintf(msg, sizeof msg, "%s: max_gain = %g, must be in (0, 8]", fn, (double)max_gain);
-        arg = "max_gain";
-    } else if (clip_permille < 0 || clip_permille > 499) {
-        snprintf(msg, sizeof msg, "%s: clip_permille = %d, must be in 0 .. 499", fn, clip_permille);
-        arg = "clip_permille";
-    } else if (!(rate > 0.0f && rate <= 1.0f)) {
-        snprintf(msg, sizeof msg, "%s: rate = %g, must be in (0, 1]", fn, (double)rate);
-        arg = "rate";
-    }
-    if (!arg) return true;
-    fail(msg, arg, __FILE__, __LINE__);
-    return false;
+    if (!(fabsf(disp_lo) <= 4096.0f) || !(fabsf(disp_hi) <= 4096.0f) || !(disp_lo < disp_hi))
+        return STM_REJECT("disp_lo, disp_hi", "%s: depth budget [%g, %g]: disp_lo < disp_hi, both finite and of magnitude <= 4096", fn,
+                          (double)disp_lo, (double)disp_hi);
+    if (!(max_gain > 0.0f && max_gain <= 8.0f)) return STM_REJECT("max_gain", "%s: max_gain = %g, must be in (0, 8]", fn, (double)max_gain);
+    if (clip_permille < 0 || clip_permille > 499) return STM_REJECT("clip_permille", "%s: clip_permille = %d, must be in 0 .. 499", fn, clip_permille);
+    if (!(rate > 0.0f && rate <= 1.0f)) return STM_REJECT("rate", "%s: rate = %g, must be in (0, 1]", fn, (double)rate);
+    return true;
 }
 
 // ------------------------------------------------------------------ tables
@@ -864,12 +673,8 @@ void stm_set_irv_paper_ratio(int on) { stm::g_irv_paper_ratio = on ? 1 : 0; }
 int stm_set_irv_chunk(int entries)
 {
     if (stm::api_outermost()) stm::clear_failed();
-    if (entries < 0 || entries > 16) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "set_irv_chunk: entries = %d, must be 0 (the library's own rule) or 1 .. 16", entries);
-        stm::fail(msg, "entries", __FILE__, __LINE__);
-        return -1; // the setting stays as it was
-    }
+    if (entries < 0 || entries > 16) // the setting stays as it was
+        return STM_REJECT("entries", "set_irv_chunk: entries = %d, must be 0 (the library's own rule) or 1 .. 16", entries) ? 0 : -1;
     stm::g_irv_chunk = entries;
     return 0;
 }
@@ -911,12 +716,8 @@ void stm_get_output(int out[4])
 int stm_set_overlay(int mode, const unsigned char *d_overlay, int ov_rows, int ov_cols, int x0, int y0, float disparity)
 {
     if (stm::api_outermost()) stm::clear_failed();
-    if (mode != 0 && mode != 1) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "set_overlay: mode = %d, must be 0 (off) or 1 (on)", mode);
-        stm::fail(msg, "mode", __FILE__, __LINE__);
-        return -1; // the thread's setting stays as it was
-    }
+    if (mode != 0 && mode != 1) // the thread's setting stays as it was
+        return STM_REJECT("mode", "set_overlay: mode = %d, must be 0 (off) or 1 (on)", mode) ? 0 : -1;
     if (mode == 1 && !stm::overlay_params_ok("set_overlay", d_overlay, true, ov_rows, ov_cols, x0, y0, disparity)) return -1;
     stm::set_overlay(mode == 0 ? stm::Overlay{0, nullptr, 0, 0, 0, 0, 0.0f} : stm::Overlay{1, d_overlay, ov_rows, ov_cols, x0, y0, disparity});
     return 0;
@@ -931,12 +732,8 @@ int stm_set_overlay_auto(int mode, int near_permille, float margin, int pad, flo
                          float *d_state)
 {
     if (stm::api_outermost()) stm::clear_failed();
-    if (mode != 0 && mode != 1) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "set_overlay_auto: mode = %d, must be 0 (off) or 1 (on)", mode);
-        stm::fail(msg, "mode", __FILE__, __LINE__);
-        return -1; // the thread's setting stays as it was
-    }
+    if (mode != 0 && mode != 1) // the thread's setting stays as it was
+        return STM_REJECT("mode", "set_overlay_auto: mode = %d, must be 0 (off) or 1 (on)", mode) ? 0 : -1;
     if (mode == 1 && !stm::overlay_auto_params_ok("set_overlay_auto", near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far)) return -1;
     stm::set_overlay_auto(mode == 0 ? stm::overlay_auto_default()
                                     : stm::OverlayAuto{1, near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far, d_state});
@@ -967,10 +764,8 @@ int stm_set_depth(int mode, float gain, float conv)
     if (stm::api_outermost()) stm::clear_failed();
     if (!stm::depth_params_ok("set_depth", mode, gain, conv)) return -1; // the thread's setting stays as it was
     stm::Depth d = stm::depth(); // mode 2's parameters (stm_set_depth_auto) are kept
-    if (mode == 2 && !(d.disp_lo < d.disp_hi)) {
-        stm::fail("set_depth: mode 2 (automatic) needs the budget of stm_set_depth_auto first", "mode", __FILE__, __LINE__);
-        return -1;
-    }
+    if (mode == 2 && !(d.disp_lo < d.disp_hi))
+        return STM_REJECT("mode", "set_depth: mode 2 (automatic) needs the budget of stm_set_depth_auto first") ? 0 : -1;
     d.mode = mode;
     d.gain = mode == 1 ? gain : 1.0f;
     d.conv = mode == 1 ? conv : 0.0f;
@@ -989,12 +784,8 @@ int stm_set_depth_auto(float disp_lo, float disp_hi, float max_gain, int clip_pe
 int stm_set_antialias(int mode, float strength, int max_radius, float gate)
 {
     if (stm::api_outermost()) stm::clear_failed();
-    if (mode != 0 && mode != 1) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "set_antialias: mode = %d, must be 0 (off) or 1 (on)", mode);
-        stm::fail(msg, "mode", __FILE__, __LINE__);
-        return -1; // the thread's setting stays as it was
-    }
+    if (mode != 0 && mode != 1) // the thread's setting stays as it was
+        return STM_REJECT("mode", "set_antialias: mode = %d, must be 0 (off) or 1 (on)", mode) ? 0 : -1;
     if (mode == 1 && !stm::antialias_params_ok("set_antialias", strength, max_radius, gate)) return -1;
     stm::set_antialias(mode == 0 ? stm::Antialias{0, 0.0f, 0, 0.0f} : stm::Antialias{1, strength, max_radius, gate});
     return 0;
@@ -1061,20 +852,14 @@ void stm_get_balance(int out_mode[2], float *out_rate, unsigned char out_lut[768
 int stm_set_cut(int mode, int thresh_permille, int min_gap, int *d_state)
 {
     if (stm::api_outermost()) stm::clear_failed();
-    if (mode != 0 && mode != 1) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "set_cut: mode = %d, must be 0 (off) or 1 (on)", mode);
-        stm::fail(msg, "mode", __FILE__, __LINE__);
-        return -1; // the thread's setting stays as it was
-    }
+    if (mode != 0 && mode != 1) // the thread's setting stays as it was
+        return STM_REJECT("mode", "set_cut: mode = %d, must be 0 (off) or 1 (on)", mode) ? 0 : -1;
     stm::Cut c = stm::cut(); // mode 0: the other arguments are ignored, the numbers stay
     c.mode = mode;
     if (mode == 1) {
         if (!stm::cut_params_ok("set_cut", thresh_permille, min_gap)) return -1;
-        if (!d_state) { // without history there is nothing to detect
-            stm::fail("set_cut: d_state must not be null in mode 1", "d_state", __FILE__, __LINE__);
-            return -1;
-        }
+        if (!d_state) // without history there is nothing to detect
+            return STM_REJECT("d_state", "set_cut: d_state must not be null in mode 1") ? 0 : -1;
         c.thresh_permille = thresh_permille; c.min_gap = min_gap; c.d_state = d_state;
     } else {
         c.d_state = nullptr;
@@ -1122,12 +907,8 @@ int stm_set_agg_tap(float *d_h1, float *d_v2, float *d_h4, const float *d_inject
     const void *p[4] = {d_h1, d_v2, d_h4, d_inject_v2};
     const char *name[4] = {"d_h1", "d_v2", "d_h4", "d_inject_v2"};
     for (int i = 0; i < 4; ++i)
-        if (((uintptr_t)p[i] & 3) != 0) {
-            char msg[120];
-            snprintf(msg, sizeof msg, "set_agg_tap: %s must be 4-byte aligned (a volume of floats)", name[i]);
-            stm::fail(msg, name[i], __FILE__, __LINE__);
-            return -1; // the thread's tap stays as it was
-        }
+        if (((uintptr_t)p[i] & 3) != 0) // the thread's tap stays as it was
+            return STM_REJECT(name[i], "set_agg_tap: %s must be 4-byte aligned (a volume of floats)", name[i]) ? 0 : -1;
     stm::set_agg_tap(stm::AggTap{d_h1, d_v2, d_h4, d_inject_v2});
     return 0;
 }

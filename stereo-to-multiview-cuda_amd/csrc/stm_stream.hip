@@ -164,14 +164,15 @@ struct PackingScope {
 // the rules an input format and a packing set together on the stream's geometry (either may come first); false with the error recorded
 bool stream_input_ok(const char *fn, const FrameStream *f, int format, int matrix, const stm::Packing &pk)
 {
-    if (format == 1 && (f->Wsbs & 1)) { // the UV plane follows the Y plane with the same pitch
-        char msg[120];
-        snprintf(msg, sizeof msg, "%s: NV12 needs an even num_cols_sbs", fn);
-        stm::fail(msg, "num_cols_sbs", __FILE__, __LINE__);
-        return false;
-    }
+    if (format == 1 && (f->Wsbs & 1)) // the UV plane follows the Y plane with the same pitch
+        return STM_REJECT("num_cols_sbs", "%s: NV12 needs an even num_cols_sbs", fn);
     if (pk.on()) return stm::packing_args_ok(fn, pk, f->H, f->Wsbs, f->W, "num_cols", format == 1, f->Wsbs, f->Wsbs, matrix);
     return format != 1 || stm::nv12_args_ok(fn, f->H, f->Wsbs, f->W, "num_cols", f->Wsbs, f->Wsbs, matrix);
+}
+// what the slots' graphs capture is set before the first submit only; false with the error recorded
+bool not_submitted(const FrameStream *f, const char *fn, const char *arg = "stream")
+{
+    return f->submitted == 0 || STM_REJECT(arg, "%s: only before the first submit", fn);
 }
 
 } // namespace
@@ -234,19 +235,12 @@ int stm_stream_set_stages(void *h, int stages)
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     const bool reduced = f->match_h > 0;
-    if ((stages & 0x1000) && !reduced) { // the stream runs the full-resolution frame: nothing is up-scaled
-        stm::fail("stream_set_stages: stages 0x1000 (guided disparity up-sampling) needs the reduced-resolution frame", "stages", __FILE__, __LINE__);
-        return -1;
-    }
-    if ((stages & ~(reduced ? 0x3e00 : 0x2e00)) != 3) {
-        stm::fail(reduced ? "stream_set_stages: stages must be 3, optionally OR-ed with 0x200, 0x400, 0x800, 0x1000 and 0x2000"
-                          : "stream_set_stages: stages must be 3, optionally OR-ed with 0x200, 0x400, 0x800 and 0x2000", "stages", __FILE__, __LINE__);
-        return -1;
-    }
-    if (f->submitted > 0) {
-        stm::fail("stream_set_stages: only before the first submit", "stages", __FILE__, __LINE__);
-        return -1;
-    }
+    if ((stages & 0x1000) && !reduced) // the stream runs the full-resolution frame: nothing is up-scaled
+        return STM_REJECT("stages", "stream_set_stages: stages 0x1000 (guided disparity up-sampling) needs the reduced-resolution frame") ? 0 : -1;
+    if ((stages & ~(reduced ? 0x3e00 : 0x2e00)) != 3)
+        return STM_REJECT("stages", "stream_set_stages: stages must be 3, optionally OR-ed with 0x200, 0x400, 0x800%s and 0x2000",
+                          reduced ? ", 0x1000" : "") ? 0 : -1;
+    if (!not_submitted(f, "stream_set_stages", "stages")) return -1;
     f->stages = stages;
     return 0;
 }
@@ -260,29 +254,17 @@ int stm_stream_set_match_size(void *h, int num_rows_disp, int num_cols_disp, flo
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     const bool off = num_rows_disp == 0 && num_cols_disp == 0;
-    if (!off && (num_rows_disp < 1 || num_cols_disp < 1)) {
-        stm::fail("stream_set_match_size: num_rows_disp and num_cols_disp must be >= 1, or both 0 (off)", "num_rows_disp, num_cols_disp", __FILE__,
-                  __LINE__);
-        return -1;
-    }
-    if (!off && !(disp_scale > 0.0f && disp_scale <= 3.402823466e38f)) { // (NaN fails the first comparison)
-        stm::fail("stream_set_match_size: disp_scale must be finite and > 0", "disp_scale", __FILE__, __LINE__);
-        return -1;
-    }
-    if (f->submitted > 0) {
-        stm::fail("stream_set_match_size: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
-    if (!off && f->packing.on()) {
-        stm::fail("stream_set_match_size: the stream has a packing (stm_stream_set_packing), which the reduced-resolution frame does not support",
-                  "packing", __FILE__, __LINE__);
-        return -1;
-    }
-    if (off && (f->stages & 0x1000)) {
-        stm::fail("stream_set_match_size: the stream's stages hold 0x1000 (guided disparity up-sampling), which needs a match size", "stages",
-                  __FILE__, __LINE__);
-        return -1;
-    }
+    if (!off && (num_rows_disp < 1 || num_cols_disp < 1))
+        return STM_REJECT("num_rows_disp, num_cols_disp", "stream_set_match_size: num_rows_disp and num_cols_disp must be >= 1, or both 0 (off)") ? 0 : -1;
+    if (!off && !(disp_scale > 0.0f && disp_scale <= 3.402823466e38f)) // (NaN fails the first comparison)
+        return STM_REJECT("disp_scale", "stream_set_match_size: disp_scale must be finite and > 0") ? 0 : -1;
+    if (!not_submitted(f, "stream_set_match_size")) return -1;
+    if (!off && f->packing.on())
+        return STM_REJECT("packing", "stream_set_match_size: the stream has a packing (stm_stream_set_packing), which the reduced-resolution frame "
+                          "does not support") ? 0 : -1;
+    if (off && (f->stages & 0x1000))
+        return STM_REJECT("stages", "stream_set_match_size: the stream's stages hold 0x1000 (guided disparity up-sampling), which needs a match size")
+                   ? 0 : -1;
     f->match_h = off ? 0 : num_rows_disp;
     f->match_w = off ? 0 : num_cols_disp;
     f->match_scale = off ? 1.0f : disp_scale;
@@ -295,22 +277,10 @@ int stm_stream_set_temporal(void *h, float alpha, int thresh_color, float thresh
 {
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
-    if (!(alpha >= 0.0f && alpha <= 1.0f)) {
-        stm::fail("stream_set_temporal: alpha must be in [0, 1]", "alpha", __FILE__, __LINE__);
-        return -1;
-    }
-    if (thresh_color < 0 || thresh_color > 765) {
-        stm::fail("stream_set_temporal: thresh_color must be in [0, 765]", "thresh_color", __FILE__, __LINE__);
-        return -1;
-    }
-    if (!(thresh_disp >= 0.0f)) {
-        stm::fail("stream_set_temporal: thresh_disp must be >= 0", "thresh_disp", __FILE__, __LINE__);
-        return -1;
-    }
-    if (f->submitted > 0) {
-        stm::fail("stream_set_temporal: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) return STM_REJECT("alpha", "stream_set_temporal: alpha must be in [0, 1]") ? 0 : -1;
+    if (thresh_color < 0 || thresh_color > 765) return STM_REJECT("thresh_color", "stream_set_temporal: thresh_color must be in [0, 765]") ? 0 : -1;
+    if (!(thresh_disp >= 0.0f)) return STM_REJECT("thresh_disp", "stream_set_temporal: thresh_disp must be >= 0") ? 0 : -1;
+    if (!not_submitted(f, "stream_set_temporal")) return -1;
     f->t_alpha = alpha; f->t_color = thresh_color; f->t_disp = thresh_disp;
     return 0;
 }
@@ -322,14 +292,8 @@ int stm_stream_set_input(void *h, int format, int matrix)
 {
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
-    if (format != 0 && format != 1) {
-        stm::fail("stream_set_input: format must be 0 (side-by-side BGR) or 1 (NV12)", "format", __FILE__, __LINE__);
-        return -1;
-    }
-    if (f->submitted > 0) {
-        stm::fail("stream_set_input: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (format != 0 && format != 1) return STM_REJECT("format", "stream_set_input: format must be 0 (side-by-side BGR) or 1 (NV12)") ? 0 : -1;
+    if (!not_submitted(f, "stream_set_input")) return -1;
     if (format == 1) {
         if (!stream_input_ok("stream_set_input", f, format, matrix, f->packing)) return -1;
         for (Slot &s : f->slot)
@@ -356,15 +320,10 @@ int stm_stream_set_packing(void *h, int packing, int swap, int filter, int gap)
     stm::clear_failed();
     const stm::Packing pk = {packing, swap, filter, gap};
     if (!stm::packing_params_ok("stream_set_packing", pk)) return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_packing: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
-    if (pk.on() && f->match_h > 0) {
-        stm::fail("stream_set_packing: the stream has a match size (stm_stream_set_match_size): the reduced-resolution frame takes no packing",
-                  "packing", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_packing")) return -1;
+    if (pk.on() && f->match_h > 0)
+        return STM_REJECT("packing", "stream_set_packing: the stream has a match size (stm_stream_set_match_size): the reduced-resolution frame "
+                          "takes no packing") ? 0 : -1;
     if (!stream_input_ok("stream_set_packing", f, f->in_format, f->in_matrix, pk)) return -1;
     const int rows_f = pk.rows_f(f->H);
     const size_t in_sz = (size_t)rows_f * f->Wsbs * f->E;
@@ -411,10 +370,7 @@ int stm_stream_set_lens(void *h, int mode, double pitch, double slope, double ce
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     if (!stm::lens_params_ok("stream_set_lens", mode, 0, 3, pitch, slope, centre)) return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_lens: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_lens")) return -1;
     f->lens = mode == 0 ? stm::Lens{0, 0.0, 0.0, 0.0} : stm::Lens{mode, pitch, slope, centre};
     return 0;
 }
@@ -427,15 +383,10 @@ int stm_stream_set_layout(void *h, int layout, int tiles_x, int tiles_y, int ord
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     if (!stm::layout_params_ok("stream_set_layout", layout, tiles_x, tiles_y, order, filter)) return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_layout: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
-    if (layout == 0 && f->output.format == 1) {
-        stm::fail("stream_set_layout: the stream's output format is 1 (NV12), which exists for quilts only: set format 0 first "
-                  "(stm_stream_set_output)", "layout", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_layout")) return -1;
+    if (layout == 0 && f->output.format == 1)
+        return STM_REJECT("layout", "stream_set_layout: the stream's output format is 1 (NV12), which exists for quilts only: set format 0 first "
+                          "(stm_stream_set_output)") ? 0 : -1;
     f->layout = layout == 0 ? stm::Layout{0, 1, 1, 0, 0} : stm::Layout{layout, tiles_x, tiles_y, order, filter};
     return 0;
 }
@@ -450,20 +401,13 @@ int stm_stream_set_output(void *h, int format, int matrix)
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     if (!stm::output_params_ok("stream_set_output", format, matrix, 0, 0)) return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_output: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
-    if (format == 1 && f->layout.layout == 0) {
-        stm::fail("stream_set_output: format 1 (NV12) exists for quilts only: set the stream's layout first (stm_stream_set_layout)", "format",
-                  __FILE__, __LINE__);
-        return -1;
-    }
-    if (format == 1 && f->ov_max_rows > 0) {
-        stm::fail("stream_set_output: format 1 (NV12) together with the stream's overlay (stm_stream_set_overlay): compositing on a "
-                  "chroma-subsampled surface is not defined, switch the overlay off first", "format", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_output")) return -1;
+    if (format == 1 && f->layout.layout == 0)
+        return STM_REJECT("format", "stream_set_output: format 1 (NV12) exists for quilts only: set the stream's layout first "
+                          "(stm_stream_set_layout)") ? 0 : -1;
+    if (format == 1 && f->ov_max_rows > 0)
+        return STM_REJECT("format", "stream_set_output: format 1 (NV12) together with the stream's overlay (stm_stream_set_overlay): compositing "
+                          "on a chroma-subsampled surface is not defined, switch the overlay off first") ? 0 : -1;
     f->output = format == 0 ? stm::Output{0, 0, 0, 0} : stm::Output{1, matrix, 0, 0};
     f->out_bytes = format == 1 ? (size_t)f->Hout * f->Wout * 3 / 2 : f->out_sz;
     return 0;
@@ -477,19 +421,12 @@ int stm_stream_set_overlay(void *h, int max_rows, int max_cols)
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     const bool off = max_rows == 0 && max_cols == 0;
-    if (!off && (max_rows < 1 || max_rows > 65535 || max_cols < 1 || max_cols > 65535)) {
-        stm::fail("stream_set_overlay: max_rows and max_cols must be in 1 .. 65535, or both 0 (off)", "max_rows, max_cols", __FILE__, __LINE__);
-        return -1;
-    }
-    if (f->submitted > 0) {
-        stm::fail("stream_set_overlay: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
-    if (!off && f->output.format == 1) {
-        stm::fail("stream_set_overlay: the stream's output format is 1 (NV12): compositing on a chroma-subsampled surface is not defined, "
-                  "set format 0 first (stm_stream_set_output)", "format", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!off && (max_rows < 1 || max_rows > 65535 || max_cols < 1 || max_cols > 65535))
+        return STM_REJECT("max_rows, max_cols", "stream_set_overlay: max_rows and max_cols must be in 1 .. 65535, or both 0 (off)") ? 0 : -1;
+    if (!not_submitted(f, "stream_set_overlay")) return -1;
+    if (!off && f->output.format == 1)
+        return STM_REJECT("format", "stream_set_overlay: the stream's output format is 1 (NV12): compositing on a chroma-subsampled surface is not "
+                          "defined, set format 0 first (stm_stream_set_output)") ? 0 : -1;
     int caller_dev = f->dev;
     STM_CHECK(hipGetDevice(&caller_dev));
     if (caller_dev != f->dev) STM_CHECK(hipSetDevice(f->dev));
@@ -540,23 +477,13 @@ int stm_stream_set_overlay_auto(void *h, int mode, int near_permille, float marg
 {
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
-    if (mode != 0 && mode != 1) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "stream_set_overlay_auto: mode = %d, must be 0 (off) or 1 (on)", mode);
-        stm::fail(msg, "mode", __FILE__, __LINE__);
-        return -1;
-    }
+    if (mode != 0 && mode != 1) return STM_REJECT("mode", "stream_set_overlay_auto: mode = %d, must be 0 (off) or 1 (on)", mode) ? 0 : -1;
     if (mode == 1 && (!stm::overlay_auto_params_ok("stream_set_overlay_auto", near_permille, margin, pad, limit_lo, limit_hi, rate_near, rate_far) ||
                       !stm::overlay_fit_size_ok("stream_set_overlay_auto", f->H, f->W)))
         return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_overlay_auto: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
-    if (mode == 1 && f->ov_max_rows == 0) {
-        stm::fail("stream_set_overlay_auto: the stream has no overlay (stm_stream_set_overlay comes first)", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_overlay_auto")) return -1;
+    if (mode == 1 && f->ov_max_rows == 0)
+        return STM_REJECT("stream", "stream_set_overlay_auto: the stream has no overlay (stm_stream_set_overlay comes first)") ? 0 : -1;
     if (mode == 1 && !f->d_ov_state) {
         int caller_dev = f->dev;
         STM_CHECK(hipGetDevice(&caller_dev));
@@ -595,22 +522,16 @@ int stm_stream_overlay(void *h, const unsigned char *overlay, int ov_rows, int o
 {
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
-    if (f->ov_max_rows == 0) {
-        stm::fail("stream_overlay: the stream has no overlay (stm_stream_set_overlay, before the first submit)", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (f->ov_max_rows == 0)
+        return STM_REJECT("stream", "stream_overlay: the stream has no overlay (stm_stream_set_overlay, before the first submit)") ? 0 : -1;
     if (!overlay || ov_rows == 0 || ov_cols == 0) {
         f->ov.mode = 0;
         return 0;
     }
     if (!stm::overlay_params_ok("stream_overlay", overlay, false, ov_rows, ov_cols, x0, y0, disparity)) return -1;
-    if (ov_rows > f->ov_max_rows || ov_cols > f->ov_max_cols) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "stream_overlay: an overlay of %d x %d pixels, the stream holds at most %d x %d (stm_stream_set_overlay)", ov_rows,
-                 ov_cols, f->ov_max_rows, f->ov_max_cols);
-        stm::fail(msg, "ov_rows, ov_cols", __FILE__, __LINE__);
-        return -1;
-    }
+    if (ov_rows > f->ov_max_rows || ov_cols > f->ov_max_cols)
+        return STM_REJECT("ov_rows, ov_cols", "stream_overlay: an overlay of %d x %d pixels, the stream holds at most %d x %d (stm_stream_set_overlay)",
+                          ov_rows, ov_cols, f->ov_max_rows, f->ov_max_cols) ? 0 : -1;
     memcpy(f->ov_pixels, overlay, (size_t)ov_rows * ov_cols * 4);
     f->ov = stm::Overlay{1, nullptr, ov_rows, ov_cols, x0, y0, disparity};
     ++f->ov_gen;
@@ -624,14 +545,9 @@ int stm_stream_set_depth(void *h, int mode, float gain, float conv)
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     if (!stm::depth_params_ok("stream_set_depth", mode, gain, conv)) return -1;
-    if (mode == 2 && !(f->depth.disp_lo < f->depth.disp_hi)) {
-        stm::fail("stream_set_depth: mode 2 (automatic) needs the budget of stm_stream_set_depth_auto first", "mode", __FILE__, __LINE__);
-        return -1;
-    }
-    if (f->submitted > 0) {
-        stm::fail("stream_set_depth: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (mode == 2 && !(f->depth.disp_lo < f->depth.disp_hi))
+        return STM_REJECT("mode", "stream_set_depth: mode 2 (automatic) needs the budget of stm_stream_set_depth_auto first") ? 0 : -1;
+    if (!not_submitted(f, "stream_set_depth")) return -1;
     if (mode == 2 && !f->d_depth_state) {
         STM_CHECK(hipMalloc((void **)&f->d_depth_state, 16));
         STM_CHECK(hipMemset(f->d_depth_state, 0, 16)); // valid = 0: the first frame starts the history
@@ -653,17 +569,9 @@ int stm_stream_set_antialias(void *h, int mode, float strength, int max_radius, 
 {
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
-    if (mode != 0 && mode != 1) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "stream_set_antialias: mode = %d, must be 0 (off) or 1 (on)", mode);
-        stm::fail(msg, "mode", __FILE__, __LINE__);
-        return -1;
-    }
+    if (mode != 0 && mode != 1) return STM_REJECT("mode", "stream_set_antialias: mode = %d, must be 0 (off) or 1 (on)", mode) ? 0 : -1;
     if (mode == 1 && !stm::antialias_params_ok("stream_set_antialias", strength, max_radius, gate)) return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_antialias: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_antialias")) return -1;
     f->antialias = mode == 0 ? stm::Antialias{0, 0.0f, 0, 0.0f} : stm::Antialias{1, strength, max_radius, gate};
     return 0;
 }
@@ -672,10 +580,7 @@ int stm_stream_set_depth_auto(void *h, float disp_lo, float disp_hi, float max_g
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     if (!stm::depth_auto_params_ok("stream_set_depth_auto", disp_lo, disp_hi, max_gain, clip_permille, rate)) return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_depth_auto: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_depth_auto")) return -1;
     f->depth.disp_lo = disp_lo; f->depth.disp_hi = disp_hi; f->depth.max_gain = max_gain; f->depth.clip_permille = clip_permille;
     f->depth.rate = rate;
     return 0;
@@ -687,15 +592,10 @@ int stm_stream_set_align(void *h, int mode, float a, float b, float c)
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     if (!stm::align_params_ok("stream_set_align", mode, a, b, c)) return -1;
-    if (mode != 0 && !f->packing.on() && f->in_format == 0 && f->Wsbs < 2 * f->W) {
-        stm::fail("stream_set_align: an alignment needs num_cols_sbs >= 2 * num_cols", "num_cols_sbs", __FILE__, __LINE__);
-        return -1;
-    }
+    if (mode != 0 && !f->packing.on() && f->in_format == 0 && f->Wsbs < 2 * f->W)
+        return STM_REJECT("num_cols_sbs", "stream_set_align: an alignment needs num_cols_sbs >= 2 * num_cols") ? 0 : -1;
     if (mode == 2 && !stm::align_size_ok("stream_set_align", f->H, f->W)) return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_align: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_align")) return -1;
     if (mode == 2 && !f->d_align_state) {
         STM_CHECK(hipMalloc((void **)&f->d_align_state, 16));
         STM_CHECK(hipMemset(f->d_align_state, 0, 16)); // valid = 0: the first frame starts the history
@@ -717,10 +617,7 @@ int stm_stream_set_align_auto(void *h, int radius, float rate)
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     if (!stm::align_auto_params_ok("stream_set_align_auto", radius, rate)) return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_align_auto: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_align_auto")) return -1;
     f->align.radius = radius;
     f->align.rate = rate;
     return 0;
@@ -742,15 +639,10 @@ int stm_stream_set_balance(void *h, int mode, const unsigned char *lut768)
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     if (!stm::balance_params_ok("stream_set_balance", mode, lut768)) return -1;
-    if (mode != 0 && !f->packing.on() && f->in_format == 0 && f->Wsbs < 2 * f->W) {
-        stm::fail("stream_set_balance: a colour balance needs num_cols_sbs >= 2 * num_cols", "num_cols_sbs", __FILE__, __LINE__);
-        return -1;
-    }
+    if (mode != 0 && !f->packing.on() && f->in_format == 0 && f->Wsbs < 2 * f->W)
+        return STM_REJECT("num_cols_sbs", "stream_set_balance: a colour balance needs num_cols_sbs >= 2 * num_cols") ? 0 : -1;
     if (mode == 2 && !stm::balance_size_ok("stream_set_balance", f->H, f->W)) return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_balance: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_balance")) return -1;
     const size_t bytes = stm::BALANCE_STATE_WORDS * 4;
     if (mode == 2 && !f->d_balance_state) {
         STM_CHECK(hipMalloc((void **)&f->d_balance_state, bytes));
@@ -771,10 +663,7 @@ int stm_stream_set_balance_auto(void *h, int max_shift, float rate)
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     if (!stm::balance_auto_params_ok("stream_set_balance_auto", max_shift, rate)) return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_balance_auto: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_balance_auto")) return -1;
     f->balance.max_shift = max_shift;
     f->balance.rate = rate;
     return 0;
@@ -803,17 +692,9 @@ int stm_stream_set_cut(void *h, int mode, int thresh_permille, int min_gap)
 {
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
-    if (mode != 0 && mode != 1) {
-        char msg[120];
-        snprintf(msg, sizeof msg, "stream_set_cut: mode = %d, must be 0 (off) or 1 (on)", mode);
-        stm::fail(msg, "mode", __FILE__, __LINE__);
-        return -1;
-    }
+    if (mode != 0 && mode != 1) return STM_REJECT("mode", "stream_set_cut: mode = %d, must be 0 (off) or 1 (on)", mode) ? 0 : -1;
     if (mode == 1 && (!stm::cut_params_ok("stream_set_cut", thresh_permille, min_gap) || !stm::cut_size_ok("stream_set_cut", f->H, f->W))) return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_cut: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_cut")) return -1;
     const size_t bytes = stm::CUT_STATE_WORDS * 4;
     if (mode == 1 && !f->d_cut_state) {
         STM_CHECK(hipMalloc((void **)&f->d_cut_state, bytes));
@@ -842,10 +723,7 @@ int stm_stream_set_active(void *h, int mode, const int rect[4], int fill, float 
     if (mode == 2 && (!stm::active_auto_params_ok("stream_set_active", thresh_luma, lit_permille, max_bar_permille, hold) ||
                       !stm::active_size_ok("stream_set_active", f->H, f->W)))
         return -1;
-    if (f->submitted > 0) {
-        stm::fail("stream_set_active: only before the first submit", "stream", __FILE__, __LINE__);
-        return -1;
-    }
+    if (!not_submitted(f, "stream_set_active")) return -1;
     const size_t bytes = stm::ACTIVE_STATE_WORDS * 4;
     if (mode != 0 && !f->d_active_state) {
         STM_CHECK(hipMalloc((void **)&f->d_active_state, bytes));
