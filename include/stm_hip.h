@@ -1550,6 +1550,38 @@ long  stm_stream_collect(void *stream, float *disp_l, float *disp_r, unsigned ch
  * result buffers, valid until the frame after the next one is submitted. */
 unsigned char *stm_stream_input_buffer(void *stream);
 long  stm_stream_collect_view(void *stream, const float **disp_l, const float **disp_r, const unsigned char **interlaced);
+/* what a frame's two disparity maps leave the stream as.  An addition: the reference's loop hands out float maps only, and at 1080p
+ * they are 16.6 of the 22.8 MB a frame downloads.
+ *   format 0 = float32 maps, the default: exactly the stream without this call;  1 = no maps;  2 = u8 planes;  3 = u16 planes.
+ *   which (formats 2 and 3; ignored otherwise): 0 = the left map only, 1 = the right map only, 2 = both.
+ *   lo, hi (formats 2 and 3; ignored otherwise): the map values that code 0 and code maxcode stand for.
+ * Definition of a plane, f32, one operation per line, for a map value d and maxcode = 255 (u8) or 65535 (u16):
+ *   k    = (float)((double)maxcode / ((double)hi - (double)lo))    on the host, once; negative when hi < lo, so either of
+ *                                                                   near = bright and near = dark is a choice of lo and hi
+ *   t    = d - lo
+ *   t    = t * k                                                   (two roundings: no fused multiply-add)
+ *   t    = fmaxf(t, 0.0f)                                          (a NaN becomes 0: fmaxf returns its other operand)
+ *   t    = fminf(t, (float)maxcode)
+ *   code = (unsigned)(t + 0.5f)                                    (exact: t + 0.5 <= 65535.5 is an f32)
+ * A stream's maps are always finite; the NaN rule only makes the definition total.  A plane is tight: num_rows rows of num_cols
+ * codes with no pitch, the rows x cols of the float maps the stream hands out in format 0 -- for a stream with a match size too,
+ * whose maps are full-resolution.  u16 codes are little-endian.
+ * With a format other than 0 the float maps are still computed, and stay on the device: 0x2000's history, the renderer and the
+ * overlay fit read them as before, and the interlaced frames are byte for byte those of format 0.  The two float downloads are
+ * not issued and their pinned buffers not held.  Formats 2 and 3 hold a device and a pinned buffer per slot for the planes (the
+ * selected ones, tight behind each other); one kernel launch per frame quantises them on the slot's compute stream right behind
+ * the frame -- inside the slot's captured graph, its arguments being fixed -- and they are downloaded with the frame.
+ * stm_stream_collect and stm_stream_collect_view then refuse a non-null map pointer (-1, stm_last_error set, nothing consumed:
+ * the frame can still be collected) and work as before with both null.  stm_stream_collect_maps and stm_stream_collect_maps_view
+ * are their counterparts for formats 1 to 3: plane_l / plane_r receive (or point at) num_rows * num_cols codes of 1 or 2 bytes.
+ * A plane the stream does not produce -- not selected by `which`, or any plane in format 1 -- has a NULL view, and a non-null
+ * destination for it is refused like a map pointer above; on a stream of format 0 both calls are refused.  The views stay valid
+ * until the frame after the next one is submitted.  Every other setting of the stream combines with every format.
+ * stm_stream_maps errors (stm_last_error names stream_maps; -1, the stream unchanged): a format outside 0 .. 3; for formats 2 and 3
+ * a `which` outside 0 .. 2, lo or hi not finite or beyond +-4096, |hi - lo| < 1/64; a call after the first submit.  Returns 0. */
+int   stm_stream_maps(void *stream, int format, int which, float lo, float hi);
+long  stm_stream_collect_maps(void *stream, void *plane_l, void *plane_r, unsigned char *interlaced);
+long  stm_stream_collect_maps_view(void *stream, const void **plane_l, const void **plane_r, const unsigned char **interlaced);
 void  stm_stream_destroy(void *stream);
 
 /* ----------------------------------------------------------------- BMP I/O */

@@ -342,6 +342,10 @@ void launch_disp_upsample(int nviews, float *const *out, const float *const *dlo
 // (1 or 2) in one launch.  Pixel (x, y) of view v's images lies at base + byte_off[v] + ((size_t)y * stride + x) * elem_sz
 void launch_disp_temporal(int nviews, float *const *cur, const float *const *prev, const u8 *const *img, const u8 *const *img_prev,
                           const size_t *byte_off, int H, int W, int stride, int elem_sz, float alpha, int thresh_color, float thresh_disp);
+// the maps of a frame stream as depth planes (stm_kernels_dplane.hip; stm_stream_maps' definition): plane dst[v] of HW codes, u8
+// (bytes_per_code 1) or little-endian u16 (2), from the float map src[v]; v < nviews (1 or 2) in one launch.  dst[v] may lie at any
+// address that is a multiple of bytes_per_code; k = (float)(maxcode / ((double)hi - lo)) is the host's
+void launch_disp_plane(int nviews, const float *const *src, void *const *dst, size_t HW, int bytes_per_code, float lo, float k);
 // frame pipeline: the N - 2 views are synthesised inside the interlacer, sample by sample (no view buffers)
 void launch_synth_mux(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l, const float *mask_r,
                       const float *blend, u8 *out, int N, float y_interval, float inv_y_interval, int ymod, int Hin, int Win, int Hout,

@@ -20,7 +20,8 @@ namespace {
 
 struct Slot {
     u8 *h_in = nullptr, *d_in = nullptr, *d_out = nullptr, *h_out = nullptr;
-    float *d_dl = nullptr, *d_dr = nullptr, *h_dl = nullptr, *h_dr = nullptr;
+    float *d_dl = nullptr, *d_dr = nullptr, *h_dl = nullptr, *h_dr = nullptr; // (h_dl, h_dr: null while stm_stream_maps' format is not 0)
+    u8 *d_pl = nullptr, *h_pl = nullptr; // stm_stream_maps, formats 2 and 3: the slot's planes, tight behind each other, and their download
     u8 *d_img_l = nullptr, *d_img_r = nullptr; // NV12 input: the slot's converted split images (the other slot's frame reads them as its history)
     float *d_rec = nullptr, *h_rec = nullptr; // depth mode 2: the state as this slot's frame left it (16 bytes), and its download
     float *d_arec = nullptr, *h_arec = nullptr; // align mode 2: likewise the alignment's state
@@ -84,6 +85,10 @@ struct FrameStream {
     float *d_ov_state = nullptr;          // ... its state {valid, disparity, nearest, 0}, at one address for every frame
     uint32_t *d_ov_ws = nullptr;          // ... and the fit's bins and alpha box
     long ov_fit_gen = 0;                  // the overlay generation the last fitted frame was submitted under
+    int maps_format = 0, maps_which = 2; // stm_stream_maps: what a frame's maps leave as (0 = float32, 1 = not at all, 2 = u8, 3 = u16 planes)
+    float maps_lo = 0.0f, maps_k = 0.0f; // ... formats 2 and 3: the definition's lo and k
+    size_t plane_bytes = 0;              // ... the bytes of one plane
+    int planes = 0;                      // ... and how many a frame has (which 2: left, then right)
     Slot slot[2];
     long submitted = 0, collected = 0;
 };
@@ -173,6 +178,31 @@ bool stream_input_ok(const char *fn, const FrameStream *f, int format, int matri
 bool not_submitted(const FrameStream *f, const char *fn, const char *arg = "stream")
 {
     return f->submitted == 0 || STM_REJECT(arg, "%s: only before the first submit", fn);
+}
+// stm_stream_collect / _view on a stream that downloads no float maps (stm_stream_maps, format != 0): a map pointer has nothing to
+// receive.  false with the error recorded; the caller consumes nothing
+bool float_maps_ok(const FrameStream *f, const char *fn, const void *disp_l, const void *disp_r)
+{
+    if (f->maps_format == 0 || (!disp_l && !disp_r)) return true;
+    stm::clear_failed();
+    return STM_REJECT("disp_l, disp_r", "%s: the stream's maps format is %d (stm_stream_maps): it downloads no float maps, disp_l and disp_r must "
+                      "be null (the planes: stm_stream_collect_maps)", fn, f->maps_format);
+}
+// stm_stream_collect_maps / _view: not on a stream of float maps, and no destination for a plane the stream does not produce
+bool planes_ok(const FrameStream *f, const char *fn, const void *plane_l, const void *plane_r)
+{
+    if (f->maps_format == 0) {
+        stm::clear_failed();
+        return STM_REJECT("stream", "%s: the stream's maps format is 0 (float32 maps): stm_stream_collect hands them out; planes need "
+                          "stm_stream_maps before the first submit", fn);
+    }
+    const bool left = f->planes > 0 && f->maps_which != 1, right = f->planes > 0 && f->maps_which != 0;
+    if ((plane_l && !left) || (plane_r && !right)) {
+        stm::clear_failed();
+        return STM_REJECT(plane_l && !left ? "plane_l" : "plane_r", "%s: the stream produces no %s plane (stm_stream_maps: format %d, which %d): "
+                          "its pointer must be null", fn, plane_l && !left ? "left" : "right", f->maps_format, f->maps_which);
+    }
+    return true;
 }
 
 } // namespace
@@ -785,6 +815,73 @@ int stm_stream_depth(void *h, float out[2])
     return 0;
 }
 
+// What a frame's two disparity maps leave the stream as (stm_hip.h): format 0 = float32 (the default), 1 = not at all, 2 / 3 = u8 / u16
+// planes of the maps selected by `which`, quantised between lo and hi.  The float maps are computed in every format.  Format 0 owns
+// the slots' pinned float buffers, formats 2 and 3 a device and a pinned buffer per slot for the planes; whatever the new format does
+// not download is freed, after everything it needs exists: a failed allocation leaves the stream as it was.  Only before the first
+// submit.  Returns 0, or -1 with the error recorded and the stream unchanged.
+int stm_stream_maps(void *h, int format, int which, float lo, float hi)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    if (format < 0 || format > 3)
+        return STM_REJECT("format", "stream_maps: format = %d, must be 0 (float32 maps), 1 (no maps), 2 (u8 planes) or 3 (u16 planes)", format) ? 0 : -1;
+    const bool planes = format >= 2;
+    if (planes && (which < 0 || which > 2))
+        return STM_REJECT("which", "stream_maps: which = %d, must be 0 (left), 1 (right) or 2 (both)", which) ? 0 : -1;
+    if (planes && !(fabsf(lo) <= 4096.0f && fabsf(hi) <= 4096.0f)) // (NaN fails the comparison, inf the bound)
+        return STM_REJECT("lo, hi", "stream_maps: lo and hi must be finite and in [-4096, 4096]") ? 0 : -1;
+    if (planes && !(fabs((double)hi - (double)lo) >= 1.0 / 64.0))
+        return STM_REJECT("lo, hi", "stream_maps: lo and hi must differ by at least 1/64") ? 0 : -1;
+    if (!not_submitted(f, "stream_maps")) return -1;
+    const int maxcode = format == 2 ? 255 : 65535, n = !planes ? 0 : which == 2 ? 2 : 1;
+    const size_t plane_bytes = planes ? f->hw * (format == 2 ? 1 : 2) : 0;
+    int caller_dev = f->dev;
+    STM_CHECK(hipGetDevice(&caller_dev));
+    if (caller_dev != f->dev) STM_CHECK(hipSetDevice(f->dev));
+    float *h_dl[2] = {nullptr, nullptr}, *h_dr[2] = {nullptr, nullptr};
+    u8 *d_pl[2] = {nullptr, nullptr}, *h_pl[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i) {
+        if (format == 0 && !f->slot[i].h_dl) {
+            STM_CHECK(hipHostMalloc((void **)&h_dl[i], f->hw * 4, hipHostMallocDefault));
+            STM_CHECK(hipHostMalloc((void **)&h_dr[i], f->hw * 4, hipHostMallocDefault));
+        }
+        if (planes) {
+            STM_CHECK(hipMalloc((void **)&d_pl[i], plane_bytes * n));
+            STM_CHECK(hipHostMalloc((void **)&h_pl[i], plane_bytes * n, hipHostMallocDefault));
+        }
+    }
+    if (stm::failed()) { // (error mode 1)
+        for (int i = 0; i < 2; ++i) {
+            if (h_dl[i]) (void)hipHostFree(h_dl[i]);
+            if (h_dr[i]) (void)hipHostFree(h_dr[i]);
+            if (d_pl[i]) (void)hipFree(d_pl[i]);
+            if (h_pl[i]) (void)hipHostFree(h_pl[i]);
+        }
+        if (caller_dev != f->dev) (void)hipSetDevice(caller_dev);
+        return -1;
+    }
+    for (int i = 0; i < 2; ++i) {
+        Slot &s = f->slot[i];
+        if (format == 0 && !s.h_dl) { s.h_dl = h_dl[i]; s.h_dr = h_dr[i]; }
+        if (format != 0 && s.h_dl) {
+            STM_CHECK(hipHostFree(s.h_dl)); STM_CHECK(hipHostFree(s.h_dr));
+            s.h_dl = s.h_dr = nullptr;
+        }
+        if (s.d_pl) { STM_CHECK(hipFree(s.d_pl)); STM_CHECK(hipHostFree(s.h_pl)); }
+        s.d_pl = d_pl[i];
+        s.h_pl = h_pl[i];
+    }
+    if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
+    f->maps_format = format;
+    f->maps_which = planes ? which : 2;
+    f->maps_lo = planes ? lo : 0.0f;
+    f->maps_k = planes ? (float)((double)maxcode / ((double)hi - (double)lo)) : 0.0f;
+    f->plane_bytes = plane_bytes;
+    f->planes = n;
+    return 0;
+}
+
 // Stage frame `submitted`; at most two frames may be in flight (collect the older one first).
 // Returns the frame's index, or -1 when both slots are still uncollected.
 long stm_stream_submit(void *h, const unsigned char *img_sbs)
@@ -845,7 +942,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     AggTapOffScope agg_tap_scope;
     stm_set_stream(s.s_compute);
     stm::ws_private_bind(s.ws);
-    auto pipeline = [&]() {
+    auto frame = [&]() {
         stm::ApiNest nest; // a failed upload above must survive the nested call's argument screen
         if (f->match_h > 0) { // the reduced-resolution frame, picked as below
             if (f->in_format == 1) {
@@ -883,6 +980,17 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
         }
         stm_d_adcensus_stm(s.d_in, s.d_dl, s.d_dr, s.d_out, f->H, f->Wsbs, f->W, f->Hout, f->Wout, f->E, f->N, f->angle, f->D,
                            f->zd, f->ad, f->ce, f->ucd, f->lcd, f->usd, f->lsd, f->thresh_s, f->thresh_h, f->stages);
+    };
+    // stm_stream_maps, formats 2 and 3: the planes are quantised right behind the frame, from the float maps it left in d_dl / d_dr
+    // (which stay what 0x2000's history and the overlay fit read).  The launch's arguments are the slot's own buffers and the
+    // stream's settings, fixed from the first submit on, so it is part of what the slot captures and replays with the graph
+    auto pipeline = [&]() {
+        frame();
+        if (f->planes > 0) {
+            const float *src[2] = {f->maps_which == 1 ? s.d_dr : s.d_dl, s.d_dr};
+            void *dst[2] = {s.d_pl, s.d_pl + f->plane_bytes};
+            stm::launch_disp_plane(f->planes, src, dst, f->hw, f->maps_format == 2 ? 1 : 2, f->maps_lo, f->maps_k);
+        }
     };
     void *wb = nullptr;
     size_t wc = 0;
@@ -944,8 +1052,12 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     if (active_auto) STM_CHECK(hipMemcpyAsync(s.d_acrec, f->d_active_state + 1, 20, hipMemcpyDeviceToDevice, s.s_compute));
     STM_CHECK(hipEventRecord(s.ev_done, s.s_compute));
     STM_CHECK(hipStreamWaitEvent(f->s_out, s.ev_done, 0));
-    STM_CHECK(hipMemcpyAsync(s.h_dl, s.d_dl, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
-    STM_CHECK(hipMemcpyAsync(s.h_dr, s.d_dr, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
+    if (f->maps_format == 0) {
+        STM_CHECK(hipMemcpyAsync(s.h_dl, s.d_dl, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
+        STM_CHECK(hipMemcpyAsync(s.h_dr, s.d_dr, f->hw * 4, hipMemcpyDeviceToHost, f->s_out));
+    } else if (f->planes > 0) { // the planes in place of the float maps; format 1 downloads the frame alone
+        STM_CHECK(hipMemcpyAsync(s.h_pl, s.d_pl, f->plane_bytes * f->planes, hipMemcpyDeviceToHost, f->s_out));
+    }
     STM_CHECK(hipMemcpyAsync(s.h_out, s.d_out, f->out_bytes, hipMemcpyDeviceToHost, f->s_out));
     if (depth_auto) STM_CHECK(hipMemcpyAsync(s.h_rec, s.d_rec, 16, hipMemcpyDeviceToHost, f->s_out));
     if (align_auto) STM_CHECK(hipMemcpyAsync(s.h_arec, s.d_arec, 16, hipMemcpyDeviceToHost, f->s_out));
@@ -966,6 +1078,7 @@ long stm_stream_collect(void *h, float *disp_l, float *disp_r, unsigned char *in
 {
     FrameStream *f = (FrameStream *)h;
     if (f->collected >= f->submitted) return -1;
+    if (!float_maps_ok(f, "stream_collect", disp_l, disp_r)) return -1;
     Slot &s = f->slot[f->collected & 1];
     STM_CHECK(hipEventSynchronize(s.ev_out));
     if (disp_l) memcpy(disp_l, s.h_dl, f->hw * 4);
@@ -991,10 +1104,43 @@ long stm_stream_collect_view(void *h, const float **disp_l, const float **disp_r
 {
     FrameStream *f = (FrameStream *)h;
     if (f->collected >= f->submitted) return -1;
+    if (!float_maps_ok(f, "stream_collect_view", disp_l, disp_r)) return -1;
     Slot &s = f->slot[f->collected & 1];
     STM_CHECK(hipEventSynchronize(s.ev_out));
     if (disp_l) *disp_l = s.h_dl;
     if (disp_r) *disp_r = s.h_dr;
+    if (interlaced) *interlaced = s.h_out;
+    s.busy = false;
+    return f->collected++;
+}
+
+// The collects of a stream whose maps leave as planes, or not at all (stm_stream_maps, formats 1 to 3; stm_hip.h): as
+// stm_stream_collect and stm_stream_collect_view, with the planes in place of the float maps.  A plane the stream does not produce
+// has nothing to copy -- a destination for it is refused, and nothing is consumed -- and its view is NULL.
+long stm_stream_collect_maps(void *h, void *plane_l, void *plane_r, unsigned char *interlaced)
+{
+    FrameStream *f = (FrameStream *)h;
+    if (f->collected >= f->submitted) return -1;
+    if (!planes_ok(f, "stream_collect_maps", plane_l, plane_r)) return -1;
+    Slot &s = f->slot[f->collected & 1];
+    STM_CHECK(hipEventSynchronize(s.ev_out));
+    if (plane_l) memcpy(plane_l, s.h_pl, f->plane_bytes);
+    if (plane_r) memcpy(plane_r, s.h_pl + (f->planes == 2 ? f->plane_bytes : 0), f->plane_bytes);
+    if (interlaced) memcpy(interlaced, s.h_out, f->out_bytes);
+    s.busy = false;
+    return f->collected++;
+}
+
+long stm_stream_collect_maps_view(void *h, const void **plane_l, const void **plane_r, const unsigned char **interlaced)
+{
+    FrameStream *f = (FrameStream *)h;
+    if (f->collected >= f->submitted) return -1;
+    if (!planes_ok(f, "stream_collect_maps_view", nullptr, nullptr)) return -1;
+    Slot &s = f->slot[f->collected & 1];
+    STM_CHECK(hipEventSynchronize(s.ev_out));
+    const bool left = f->planes > 0 && f->maps_which != 1, right = f->planes > 0 && f->maps_which != 0;
+    if (plane_l) *plane_l = left ? s.h_pl : nullptr;
+    if (plane_r) *plane_r = right ? s.h_pl + (f->planes == 2 ? f->plane_bytes : 0) : nullptr;
     if (interlaced) *interlaced = s.h_out;
     s.busy = false;
     return f->collected++;
@@ -1008,7 +1154,9 @@ void stm_stream_destroy(void *h)
     for (Slot &s : f->slot) STM_CHECK(hipStreamSynchronize(s.s_compute));
     STM_CHECK(hipStreamSynchronize(f->s_out));
     for (Slot &s : f->slot) {
-        STM_CHECK(hipHostFree(s.h_in)); STM_CHECK(hipHostFree(s.h_out)); STM_CHECK(hipHostFree(s.h_dl)); STM_CHECK(hipHostFree(s.h_dr));
+        STM_CHECK(hipHostFree(s.h_in)); STM_CHECK(hipHostFree(s.h_out));
+        if (s.h_dl) { STM_CHECK(hipHostFree(s.h_dl)); STM_CHECK(hipHostFree(s.h_dr)); }
+        if (s.d_pl) { STM_CHECK(hipFree(s.d_pl)); STM_CHECK(hipHostFree(s.h_pl)); }
         STM_CHECK(hipFree(s.d_in)); STM_CHECK(hipFree(s.d_out)); STM_CHECK(hipFree(s.d_dl)); STM_CHECK(hipFree(s.d_dr));
         STM_CHECK(hipEventDestroy(s.ev_in)); STM_CHECK(hipEventDestroy(s.ev_done)); STM_CHECK(hipEventDestroy(s.ev_out));
         if (s.gexec) STM_CHECK(hipGraphExecDestroy(s.gexec));

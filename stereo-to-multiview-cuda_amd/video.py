@@ -52,13 +52,18 @@ class FrameStream:
     pillarboxed frame (set_active mode 1); active_auto = (thresh_luma, lit_permille, max_bar_permille, hold) or True
     (ACTIVE_AUTO_DEFAULT): the rectangle measured on every frame on the GPU (mode 2), restarted at a cut; at most one of the two.
     depth_auto and overlay_auto are then fitted under the rectangle.  active_fill = a disparity: the maps that come back hold it in
-    the bars; None = the maps as matched.  .active() reads (top, bottom, left, right, changed) of the last collected frame."""
+    the bars; None = the maps as matched.  .active() reads (top, bottom, left, right, changed) of the last collected frame.
+    maps = (format, which, lo, hi) or a format alone: what the two disparity maps of a frame come back as (set_maps) -- "f32" (the
+    default: float32 arrays), "none" (collect() and collect_view() return None for both), "u8" or "u16": depth planes of one code per
+    pixel, code 0 at map value lo and the largest code at hi (lo > hi: near = dark), of the maps `which` selects ("left", "right" or
+    "both"; or 0, 1, 2) -- the other one comes back as None.  The float maps are computed either way; only the download changes."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
                  depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None, overlay=None,
                  antialias=None, align=None, align_auto=None, balance=None, balance_auto=None, cut=None, overlay_auto=None,
-                 active=None, active_auto=None, active_fill=None):
+                 active=None, active_auto=None, active_fill=None, maps=None):
         self.H, self.W = num_rows, num_cols
+        self._maps = (0, 2)
         self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
         self._nv12 = False
@@ -121,6 +126,20 @@ class FrameStream:
             self.set_active(2, None, *fill, *(ACTIVE_AUTO_DEFAULT if active_auto is True else active_auto))
         elif active_fill is not None:
             raise ValueError("FrameStream: active_fill needs active or active_auto")
+        if maps is not None:
+            self.set_maps(*((maps,) if isinstance(maps, str) else maps))
+
+    def set_maps(self, format="f32", which="both", lo=0.0, hi=0.0):
+        """stm_stream_maps: what a frame's disparity maps come back as -- "f32", "none", "u8" or "u16" (or 0 .. 3); for the planes
+        `which` = "left", "right" or "both" (or 0, 1, 2) and the map values lo and hi of code 0 and of the largest code.  Only before
+        the first submit.  Raises ValueError where the library refuses."""
+        fmt = {"f32": 0, "none": 1, "u8": 2, "u16": 3}.get(format, format)
+        sel = {"left": 0, "right": 1, "both": 2}.get(which, which)
+        if not isinstance(fmt, int) or not isinstance(sel, int):
+            raise ValueError("FrameStream.set_maps: format %r, which %r" % (format, which))
+        if int(lib().stm_stream_maps(self._h, fmt, sel, float(lo), float(hi))) != 0:
+            raise ValueError("stm_stream_maps(%r, %r, %g, %g) refused: %s" % (format, which, lo, hi, lib().stm_last_error().decode()))
+        self._maps = (fmt, sel if fmt >= 2 else 2)
 
     def set_active(self, mode, rect=None, fill=0, fill_disp=0.0, thresh_luma=ACTIVE_AUTO_DEFAULT[0], lit_permille=ACTIVE_AUTO_DEFAULT[1],
                    max_bar_permille=ACTIVE_AUTO_DEFAULT[2], hold=ACTIVE_AUTO_DEFAULT[3]):
@@ -351,6 +370,14 @@ class FrameStream:
     def collect_view(self):
         """Like collect(), but returns views of the stream's pinned result buffers (valid until the frame after the next
         one is submitted) instead of copies."""
+        if self._maps[0] != 0:  # planes, or no maps: uint8 / uint16 views, None for a plane the stream does not produce
+            vl, vr, po = C.c_void_p(), C.c_void_p(), u8p()
+            k = int(lib().stm_stream_collect_maps_view(self._h, C.byref(vl), C.byref(vr), C.byref(po)))
+            if k < 0:
+                return None
+            ct = C.c_uint8 if self._maps[0] == 2 else C.c_uint16
+            planes = [np.ctypeslib.as_array(C.cast(v, C.POINTER(ct)), shape=(self.H, self.W)) if v.value else None for v in (vl, vr)]
+            return k, planes[0], planes[1], np.ctypeslib.as_array(po, shape=self.out_shape)
         pl, pr, po = f32p(), f32p(), u8p()
         k = int(lib().stm_stream_collect_view(self._h, C.byref(pl), C.byref(pr), C.byref(po)))
         if k < 0:
@@ -359,6 +386,15 @@ class FrameStream:
                 np.ctypeslib.as_array(po, shape=self.out_shape))
 
     def collect(self):
+        if self._maps[0] != 0:
+            fmt, sel = self._maps
+            dt = np.uint8 if fmt == 2 else np.dtype("<u2")
+            dl = np.empty((self.H, self.W), dt) if fmt >= 2 and sel != 1 else None
+            dr = np.empty((self.H, self.W), dt) if fmt >= 2 and sel != 0 else None
+            out = np.empty(self.out_shape, np.uint8)
+            k = int(lib().stm_stream_collect_maps(self._h, None if dl is None else dl.ctypes.data, None if dr is None else dr.ctypes.data,
+                                                  out.ctypes.data_as(u8p)))
+            return (k, dl, dr, out) if k >= 0 else None
         dl = np.empty((self.H, self.W), np.float32)
         dr = np.empty((self.H, self.W), np.float32)
         out = np.empty(self.out_shape, np.uint8)
@@ -511,6 +547,28 @@ def take_active_options(argv):
     return rect, auto, fill
 
 
+def take_maps_option(argv):
+    """The driver's --maps FORMAT [WHICH LO HI [FILE]], removed from argv: FORMAT f32, none, u8 or u16; for u8 and u16 WHICH (left,
+    right or both) and the map values LO and HI of code 0 and of the largest code, then optionally the FILE the raw planes are
+    appended to (the next token, unless it starts with "--").  Returns (format, which, lo, hi, file or None) or None; raises ValueError
+    or IndexError for a malformed option or a value stm_stream_maps would refuse."""
+    if "--maps" not in argv:
+        return None
+    at = argv.index("--maps")
+    fmt = argv[at + 1]
+    if fmt in ("f32", "none"):
+        del argv[at:at + 2]
+        return fmt, "both", 0.0, 0.0, None
+    if fmt not in ("u8", "u16"):
+        raise ValueError("--maps FORMAT is f32, none, u8 or u16")
+    which, lo, hi = argv[at + 2], float(argv[at + 3]), float(argv[at + 4])
+    if which not in ("left", "right", "both") or not (abs(lo) <= 4096.0 and abs(hi) <= 4096.0 and abs(hi - lo) >= 1.0 / 64.0):  # a NaN fails
+        raise ValueError((which, lo, hi))
+    path = argv[at + 5] if at + 5 < len(argv) and not argv[at + 5].startswith("--") else None
+    del argv[at:at + (6 if path is not None else 5)]
+    return fmt, which, lo, hi, path
+
+
 def _collect(fs, on_depth, on_align=None, on_balance=None, on_cut=None, on_overlay_depth=None, on_active=None):
     r = fs.collect()
     if on_active is not None and r is not None:
@@ -532,8 +590,9 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
                      depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None,
                      overlay=None, antialias=None, align=None, align_auto=None, on_align=None, balance=None, balance_auto=None,
                      on_balance=None, cut=None, on_cut=None, overlay_auto=None, on_overlay_depth=None, active=None,
-                     active_auto=None, active_fill=None, on_active=None):
+                     active_auto=None, active_fill=None, on_active=None, maps=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
+    maps: FrameStream's (format, which, lo, hi): disp_l and disp_r are then uint8 / uint16 depth planes, or None.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
     stabilisation); temporal: (alpha, thresh_color, thresh_disp) for FrameStream.set_temporal, None = the defaults; lens: (mode,
@@ -561,7 +620,7 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
             fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output,
                              overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]), antialias=antialias,
                              align=align, align_auto=align_auto, balance=balance, balance_auto=balance_auto, cut=cut, overlay_auto=overlay_auto,
-                             active=active, active_auto=active_auto, active_fill=active_fill)
+                             active=active, active_auto=active_auto, active_fill=active_fill, maps=maps)
             if overlay is not None:
                 fs.overlay(*overlay)
             if temporal is not None:

@@ -12,6 +12,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--align A B C | --align-auto RADIUS [RATE]] [--balance FILE.npy | --balance-auto [MAX_SHIFT RATE]]
                     [--cut [THRESH MIN_GAP]]
                     [--active T B L R | --active-auto [THRESH LIT MAX_BAR HOLD]] [--active-fill DISP]
+                    [--maps FORMAT [WHICH LO HI [FILE]]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -76,6 +77,11 @@ when more than LIT permille (0 .. 999; 10) of its pixels have a luma above THRES
 (0 .. 450; 300) of the frame to a side, grows only after HOLD (1 .. 2^20; 12) agreeing frames, shrinks at once, and starts afresh at a
 --cut; each frame's rectangle is printed.  The two options are mutually exclusive.  --active-fill DISP (with either): the maps come
 back with DISP (|DISP| <= 4096) in the bars.
+--maps FORMAT [WHICH LO HI [FILE]] (an addition; put it behind the positional arguments): what the disparity maps leave the GPU as
+(stm_stream_maps) -- FORMAT f32 (the default: float maps, written as normalised BMPs), none (no maps are downloaded or written), u8 or
+u16: depth planes of one code per pixel of the maps WHICH selects (left, right or both), code 0 at map value LO and the largest code
+at HI (LO > HI: near = dark; both within +-4096, at least 1/64 apart).  Every frame's planes -- raw, tight, u16 little-endian, the
+left one first -- are appended to FILE (default <out dir>/maps_u8.raw or maps_u16.raw).
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -283,6 +289,7 @@ def main(argv):
         balance, balance_auto = video.take_balance_options(argv)
         cut = video.take_cut_option(argv)
         active, active_auto, active_fill = video.take_active_options(argv)
+        maps = video.take_maps_option(argv)
     except (ValueError, IndexError):
         print(__doc__)
         return -1
@@ -290,7 +297,7 @@ def main(argv):
         print(__doc__)
         return -1
     import stm_amd  # noqa: F401
-    from stm_amd import device_api as dev, video
+    from stm_amd import bmp_io, device_api as dev, video
     a = argv[1:]
     angle = float(a[2]) if os.environ.get("STM_EXACT_ANGLE") == "1" else float(int(float(a[2])))  # SURVEY A-Q24
     p = dev.FrameParams(num_views=int(a[1]), angle=angle, num_disp=int(a[5]), zero_disp=int(a[6]), ad_coeff=float(a[7]),
@@ -303,6 +310,10 @@ def main(argv):
     if nv12_out is not None:
         os.makedirs(out_dir, exist_ok=True)
         yuv = open(os.path.join(out_dir, "quilt.yuv"), "wb")
+    planes = None
+    if maps is not None and maps[0] in ("u8", "u16"):
+        os.makedirs(out_dir, exist_ok=True)
+        planes = open(maps[4] if maps[4] is not None else os.path.join(out_dir, "maps_%s.raw" % maps[0]), "ab")
     cuts = []
 
     def on_cut(k, c):
@@ -331,15 +342,24 @@ def main(argv):
                                                        if overlay_auto is not None else None,
                                                        active=active, active_auto=active_auto, active_fill=active_fill,
                                                        on_active=(lambda k, r: print("frame %d: active rows %d..%d cols %d..%d changed %d" % ((k,) + r)))
-                                                       if active_auto is not None else None):
+                                                       if active_auto is not None else None,
+                                                       maps=None if maps is None else maps[:4]):
         if yuv is not None:  # the frame is [out height * 3 / 2][out width]: the Y plane, then the interleaved UV plane
             yuv.write(inter.tobytes())
-            video.write_disparities(out_dir, k, dl, dr)
         else:
-            video.write_outputs(out_dir, k, dl, dr, inter)
+            os.makedirs(out_dir, exist_ok=True)
+            bmp_io.write_bmp(os.path.join(out_dir, "interlaced_%05d.bmp" % k), inter)
+        if planes is not None:  # the frame's planes, raw and tight: the left one, then the right one, whichever the stream produces
+            for plane in (dl, dr):
+                if plane is not None:
+                    planes.write(plane.tobytes())
+        elif dl is not None:
+            video.write_disparities(out_dir, k, dl, dr)
         n += 1
     if yuv is not None:
         yuv.close()
+    if planes is not None:
+        planes.close()
     if cut is not None:
         print("cuts at frames: %s" % " ".join(str(k) for k in cuts))
     dt = time.perf_counter() - t0
