@@ -1582,6 +1582,9 @@ long  stm_stream_collect_view(void *stream, const float **disp_l, const float **
 int   stm_stream_maps(void *stream, int format, int which, float lo, float hi);
 long  stm_stream_collect_maps(void *stream, void *plane_l, void *plane_r, unsigned char *interlaced);
 long  stm_stream_collect_maps_view(void *stream, const void **plane_l, const void **plane_r, const unsigned char **interlaced);
+/* image-plus-depth input of a frame stream (an image with its depth plane in, the second eye built on the GPU): its one entry
+ * point is declared, with the definition line by line, in stm_depth_input.h.  This header's set of names is recorded in the
+ * screening tables of the test suite and stays what it is. */
 void  stm_stream_destroy(void *stream);
 
 /* ----------------------------------------------------------------- BMP I/O */

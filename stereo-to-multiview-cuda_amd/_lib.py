@@ -203,6 +203,11 @@ PROTOS = {
     "stm_bmp_write": ([C.c_char_p, u8p, i, i], i),
     "stm_bmp_free": ([C.c_void_p], None),
 }
+# include/stm_depth_input.h: the entry of a frame stream's image-plus-depth input.  PROTOS is include/stm_hip.h, name for name, and that
+# header's names are recorded in the test suite's screening tables, so a later stream entry has its own header and its own table
+PROTOS_DEPTH = {
+    "stm_stream_input_depth": ([C.c_void_p, i, f, f, i, f], i),
+}
 
 _lib = None
 
@@ -220,7 +225,7 @@ def lib():
         # other order starts two runtimes and the second one finds "no ROCm-capable device".
         import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
-        for name, (args, res) in PROTOS.items():
+        for name, (args, res) in list(PROTOS.items()) + list(PROTOS_DEPTH.items()):
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = res

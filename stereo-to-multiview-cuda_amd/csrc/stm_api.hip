@@ -2417,6 +2417,38 @@ void frame_host(const char *fn, const FrameArgs &a, bool reduced, const u8 *img_
 
 } // namespace
 
+// The body of a frame stream's image-plus-depth frame (stm_stream_input_depth, step F of its definition): frame_device without the
+// front and the matcher.  The cut and the active-area detector run on the given image as the left eye, ahead of the kernel, as
+// frame_input runs them; stm_k_eye decodes the plane into d_disp_l and synthesises the right image and d_disp_r; then the active fill
+// and frame_tail exactly as the stereo body calls them.  The stream has screened the plane's arguments and keeps the settings that
+// condition a stereo pair (packing, alignment, balance, NV12 input, a match size) off.  Not an extern "C" entry: see stm_common.h
+void stm::depth_frame_device(const u8 *d_img, const void *d_plane, const DepthInput &di, float *d_disp_l, float *d_disp_r, u8 *d_interlaced,
+                             int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz, int num_views,
+                             float angle, int stages)
+{
+    const char *fn = "stream_input_depth";
+    const FrameArgs a = {num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views, angle, 1, 0, 0.0f, 0.0f, 0.0f, 0.0f,
+                         0, 0, 0, 0.0f, stages};
+    if (!frame_dims_ok(fn, a)) return;
+    if ((stages & ~0x800) != 3) return (void)STM_REJECT("stages", "%s: stages = 0x%x, must be 3 or 3 | 0x800 (nothing is matched)", fn, stages);
+    if (num_cols > 8192) return (void)STM_REJECT("num_cols", "%s: num_cols = %d, must be <= 8192 (a row's keys live in LDS)", fn, num_cols);
+    if (num_cols_sbs < num_cols) return (void)STM_REJECT("num_cols_sbs", "%s: num_cols_sbs = %d, must be >= num_cols = %d", fn, num_cols_sbs, num_cols);
+    if (!frame_layout_ok(fn, a) || !frame_cut_ok(fn, num_rows, num_cols) || !frame_active_ok(fn, num_rows, num_cols)) return;
+    const int H = num_rows, W = num_cols;
+    const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
+    // the two images, the tail's masks, views and tables; no volumes
+    Workspace::begin((size_t)(num_views + 2) * IMG + 40 * HW + (1u << 20) + frame_settings_ws_bytes(a, false));
+    u8 *img_r = Workspace::get<u8>(IMG), *img_l = num_cols_sbs > W ? Workspace::get<u8>(IMG) : nullptr;
+    const PackInput pin = {Packing{0, 0, 0, 0}, false, d_img, num_cols_sbs, nullptr, nullptr, 0, 0, 0};
+    const Cut ct = cut();
+    if (ct.mode) cut_frame_input(ct, pin, H, W, elem_sz, true, align(), balance()); // before any state's fit runs
+    const Active ac = active();
+    const int *rect = ac.mode ? active_frame_input(ac, ct, pin, H, W, elem_sz) : nullptr;
+    launch_depth_eye(d_img, num_cols_sbs, d_plane, di.format, di.lo, di.hi, di.fill, di.gate, img_l, img_r, d_disp_l, d_disp_r, H, W, elem_sz);
+    frame_active_fill(rect, d_disp_l, d_disp_r, H, W);
+    frame_tail(a, img_l ? img_l : const_cast<u8 *>(d_img), img_r, d_disp_l, d_disp_r, d_interlaced, rect);
+}
+
 extern "C" {
 
 // which aggregation kernels a frame call with these arguments runs (stm_hip.h); no launch, no device

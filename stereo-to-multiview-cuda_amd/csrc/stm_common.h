@@ -346,6 +346,25 @@ void launch_disp_temporal(int nviews, float *const *cur, const float *const *pre
 // (bytes_per_code 1) or little-endian u16 (2), from the float map src[v]; v < nviews (1 or 2) in one launch.  dst[v] may lie at any
 // address that is a multiple of bytes_per_code; k = (float)(maxcode / ((double)hi - lo)) is the host's
 void launch_disp_plane(int nviews, const float *const *src, void *const *dst, size_t HW, int bytes_per_code, float lo, float k);
+// The image-plus-depth input of a frame stream (stm_stream_input_depth, include/stm_depth_input.h): format -1 = off, 0 = f32, 2 = u8,
+// 3 = u16 planes between lo and hi; fill and gate of step E
+struct DepthInput {
+    int format;
+    float lo, hi;
+    int fill;
+    float gate;
+};
+// the second eye (stm_kernels_eye.hip; steps A to E of the definition): from the image `img` (H rows of pitch_px pixels, the first W
+// read) and the tight plane, the decoded map disp_l, the synthesised img_r and disp_r, and the tight copy img_l of the image (null
+// where pitch_px == W).  plane, img_r, disp_l and disp_r 16-byte aligned, W <= 8192
+void launch_depth_eye(const u8 *img, int pitch_px, const void *plane, int format, float lo, float hi, int fill, float gate, u8 *img_l,
+                      u8 *img_r, float *disp_l, float *disp_r, int H, int W, int elem_sz);
+// stm_api.hip: the body of a stream's image-plus-depth frame -- the cut and active-area detectors on the given image, the second eye,
+// the active fill and the stereo body's own tail; no matcher.  stages 3 or 3 | 0x800.  No extern "C" entry calls it: a frame entry
+// would have to join the recorded screening tables.  Errors are recorded like a frame entry's
+void depth_frame_device(const u8 *d_img, const void *d_plane, const DepthInput &di, float *d_disp_l, float *d_disp_r, u8 *d_interlaced,
+                        int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz, int num_views,
+                        float angle, int stages);
 // frame pipeline: the N - 2 views are synthesised inside the interlacer, sample by sample (no view buffers)
 void launch_synth_mux(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l, const float *mask_r,
                       const float *blend, u8 *out, int N, float y_interval, float inv_y_interval, int ymod, int Hin, int Win, int Hout,

@@ -11,6 +11,7 @@
 // compute stream and workspace for both slots, as in round 2.
 #include "stm_common.h"
 #include "../../include/stm_hip.h"
+#include "../../include/stm_depth_input.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -89,6 +90,8 @@ struct FrameStream {
     float maps_lo = 0.0f, maps_k = 0.0f; // ... formats 2 and 3: the definition's lo and k
     size_t plane_bytes = 0;              // ... the bytes of one plane
     int planes = 0;                      // ... and how many a frame has (which 2: left, then right)
+    stm::DepthInput din = {-1, 0.0f, 0.0f, 0, 0.0f}; // stm_stream_input_depth: a frame is an image and its depth plane (format -1 = off)
+    size_t plane_off = 0;                // ... the plane's byte offset in a frame: the image's bytes rounded up to a multiple of 16
     Slot slot[2];
     long submitted = 0, collected = 0;
 };
@@ -178,6 +181,13 @@ bool stream_input_ok(const char *fn, const FrameStream *f, int format, int matri
 bool not_submitted(const FrameStream *f, const char *fn, const char *arg = "stream")
 {
     return f->submitted == 0 || STM_REJECT(arg, "%s: only before the first submit", fn);
+}
+// the settings that condition a stereo pair or its matcher do not go with image-plus-depth frames (stm_stream_input_depth); false with
+// the error recorded
+bool no_depth_input(const FrameStream *f, const char *fn, const char *arg)
+{
+    return f->din.format < 0 || STM_REJECT(arg, "%s: the stream has depth input (stm_stream_input_depth): a frame is an image and its depth plane, "
+                                           "nothing is matched and there is no second image to condition; switch the depth input off first", fn);
 }
 // stm_stream_collect / _view on a stream that downloads no float maps (stm_stream_maps, format != 0): a map pointer has nothing to
 // receive.  false with the error recorded; the caller consumes nothing
@@ -270,6 +280,7 @@ int stm_stream_set_stages(void *h, int stages)
     if ((stages & ~(reduced ? 0x3e00 : 0x2e00)) != 3)
         return STM_REJECT("stages", "stream_set_stages: stages must be 3, optionally OR-ed with 0x200, 0x400, 0x800%s and 0x2000",
                           reduced ? ", 0x1000" : "") ? 0 : -1;
+    if ((stages & ~0x800) != 3 && !no_depth_input(f, "stream_set_stages", "stages")) return -1; // 3 and 3 | 0x800 render only
     if (!not_submitted(f, "stream_set_stages", "stages")) return -1;
     f->stages = stages;
     return 0;
@@ -288,6 +299,7 @@ int stm_stream_set_match_size(void *h, int num_rows_disp, int num_cols_disp, flo
         return STM_REJECT("num_rows_disp, num_cols_disp", "stream_set_match_size: num_rows_disp and num_cols_disp must be >= 1, or both 0 (off)") ? 0 : -1;
     if (!off && !(disp_scale > 0.0f && disp_scale <= 3.402823466e38f)) // (NaN fails the first comparison)
         return STM_REJECT("disp_scale", "stream_set_match_size: disp_scale must be finite and > 0") ? 0 : -1;
+    if (!no_depth_input(f, "stream_set_match_size", "stream")) return -1;
     if (!not_submitted(f, "stream_set_match_size")) return -1;
     if (!off && f->packing.on())
         return STM_REJECT("packing", "stream_set_match_size: the stream has a packing (stm_stream_set_packing), which the reduced-resolution frame "
@@ -323,6 +335,7 @@ int stm_stream_set_input(void *h, int format, int matrix)
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     if (format != 0 && format != 1) return STM_REJECT("format", "stream_set_input: format must be 0 (side-by-side BGR) or 1 (NV12)") ? 0 : -1;
+    if (!no_depth_input(f, "stream_set_input", "stream")) return -1;
     if (!not_submitted(f, "stream_set_input")) return -1;
     if (format == 1) {
         if (!stream_input_ok("stream_set_input", f, format, matrix, f->packing)) return -1;
@@ -350,6 +363,7 @@ int stm_stream_set_packing(void *h, int packing, int swap, int filter, int gap)
     stm::clear_failed();
     const stm::Packing pk = {packing, swap, filter, gap};
     if (!stm::packing_params_ok("stream_set_packing", pk)) return -1;
+    if (!no_depth_input(f, "stream_set_packing", "stream")) return -1;
     if (!not_submitted(f, "stream_set_packing")) return -1;
     if (pk.on() && f->match_h > 0)
         return STM_REJECT("packing", "stream_set_packing: the stream has a match size (stm_stream_set_match_size): the reduced-resolution frame "
@@ -622,6 +636,7 @@ int stm_stream_set_align(void *h, int mode, float a, float b, float c)
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     if (!stm::align_params_ok("stream_set_align", mode, a, b, c)) return -1;
+    if (!no_depth_input(f, "stream_set_align", "stream")) return -1; // ahead of the geometry rule: a depth frame has no second half
     if (mode != 0 && !f->packing.on() && f->in_format == 0 && f->Wsbs < 2 * f->W)
         return STM_REJECT("num_cols_sbs", "stream_set_align: an alignment needs num_cols_sbs >= 2 * num_cols") ? 0 : -1;
     if (mode == 2 && !stm::align_size_ok("stream_set_align", f->H, f->W)) return -1;
@@ -669,6 +684,7 @@ int stm_stream_set_balance(void *h, int mode, const unsigned char *lut768)
     FrameStream *f = (FrameStream *)h;
     stm::clear_failed();
     if (!stm::balance_params_ok("stream_set_balance", mode, lut768)) return -1;
+    if (!no_depth_input(f, "stream_set_balance", "stream")) return -1; // ahead of the geometry rule, as in stm_stream_set_align
     if (mode != 0 && !f->packing.on() && f->in_format == 0 && f->Wsbs < 2 * f->W)
         return STM_REJECT("num_cols_sbs", "stream_set_balance: a colour balance needs num_cols_sbs >= 2 * num_cols") ? 0 : -1;
     if (mode == 2 && !stm::balance_size_ok("stream_set_balance", f->H, f->W)) return -1;
@@ -882,6 +898,80 @@ int stm_stream_maps(void *h, int format, int which, float lo, float hi)
     return 0;
 }
 
+// The stream's frames are an image and its depth plane (stm_depth_input.h has the definition): format -1 = off (the default), 0 = float32, 2 =
+// u8, 3 = u16 codes between lo and hi; fill and gate of the hole filling.  A frame is then the image (num_rows * num_cols_sbs *
+// elem_sz bytes) followed by the tight plane at the next multiple of 16 bytes, so each slot's pinned and device input buffers are
+// allocated anew, after everything the new setting needs exists: pointers handed out by stm_stream_input_buffer before this call are
+// void, and a failed allocation leaves the stream as it was.  Every frame is then computed by stm::depth_frame_device (no matcher).
+// Not together with NV12 input, a packing, a match size, an alignment, a balance or stages beyond 3 | 0x800, in either order.  Only
+// before the first submit.  Returns 0, or -1 with the error recorded and the stream unchanged.
+int stm_stream_input_depth(void *h, int format, float lo, float hi, int fill, float gate)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    const char *fn = "stream_input_depth";
+    if (format != -1 && format != 0 && format != 2 && format != 3)
+        return STM_REJECT("format", "%s: format = %d, must be -1 (off), 0 (float32 plane), 2 (u8 plane) or 3 (u16 plane)", fn, format) ? 0 : -1;
+    const bool on = format != -1;
+    if (on && !(fabsf(lo) <= 4096.0f && fabsf(hi) <= 4096.0f)) // (NaN fails the comparison, inf the bound)
+        return STM_REJECT("lo, hi", "%s: lo and hi must be finite and in [-4096, 4096]", fn) ? 0 : -1;
+    if (on && !(fabs((double)hi - (double)lo) >= 1.0 / 64.0))
+        return STM_REJECT("lo, hi", "%s: lo and hi must differ by at least 1/64", fn) ? 0 : -1;
+    if (on && fill != 0 && fill != 1)
+        return STM_REJECT("fill", "%s: fill = %d, must be 0 (constant extension) or 1 (continue the background)", fn, fill) ? 0 : -1;
+    if (on && fill == 1 && !(gate >= 0.0f && gate <= 4096.0f)) // (NaN fails the comparison)
+        return STM_REJECT("gate", "%s: gate must be finite and in [0, 4096]", fn) ? 0 : -1;
+    if (on && f->W > 8192)
+        return STM_REJECT("num_cols", "%s: the stream's num_cols = %d, must be <= 8192 (a row's keys live in LDS)", fn, f->W) ? 0 : -1;
+    if (on && f->Wsbs < f->W)
+        return STM_REJECT("num_cols_sbs", "%s: the stream's num_cols_sbs = %d, must be >= num_cols = %d", fn, f->Wsbs, f->W) ? 0 : -1;
+    if (!not_submitted(f, fn)) return -1;
+    if (on && f->in_format != 0)
+        return STM_REJECT("input", "%s: the stream's input format is 1 (NV12, stm_stream_set_input): the image of a depth frame is BGR", fn) ? 0 : -1;
+    if (on && f->packing.on())
+        return STM_REJECT("packing", "%s: the stream has a packing (stm_stream_set_packing): a depth frame holds one image", fn) ? 0 : -1;
+    if (on && f->match_h > 0)
+        return STM_REJECT("match_size", "%s: the stream has a match size (stm_stream_set_match_size): nothing is matched", fn) ? 0 : -1;
+    if (on && f->align.mode != 0)
+        return STM_REJECT("align", "%s: the stream has an alignment (stm_stream_set_align): there is no second image to align", fn) ? 0 : -1;
+    if (on && f->balance.mode != 0)
+        return STM_REJECT("balance", "%s: the stream has a colour balance (stm_stream_set_balance): there is no second image to balance", fn) ? 0 : -1;
+    if (on && (f->stages & ~0x800) != 3)
+        return STM_REJECT("stages", "%s: the stream's stages are 0x%x (stm_stream_set_stages): a depth frame takes 3 or 3 | 0x800, nothing is "
+                          "matched", fn, f->stages) ? 0 : -1;
+    if (!on && f->din.format < 0) return 0; // off stays off: not one byte of the stream changes
+    const size_t plane_off = (f->in_sz + 15) & ~(size_t)15;
+    const size_t need = on ? plane_off + f->hw * (format == 0 ? 4 : format == 2 ? 1 : 2) : f->in_sz;
+    int caller_dev = f->dev;
+    STM_CHECK(hipGetDevice(&caller_dev));
+    if (caller_dev != f->dev) STM_CHECK(hipSetDevice(f->dev));
+    u8 *h_new[2] = {nullptr, nullptr}, *d_new[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i) {
+        STM_CHECK(hipHostMalloc((void **)&h_new[i], need, hipHostMallocDefault));
+        STM_CHECK(hipMalloc((void **)&d_new[i], need));
+    }
+    if (stm::failed()) { // (error mode 1; the hip calls take null pointers)
+        for (int i = 0; i < 2; ++i) {
+            if (h_new[i]) (void)hipHostFree(h_new[i]);
+            if (d_new[i]) (void)hipFree(d_new[i]);
+        }
+        if (caller_dev != f->dev) (void)hipSetDevice(caller_dev);
+        return -1;
+    }
+    for (int i = 0; i < 2; ++i) {
+        Slot &s = f->slot[i];
+        STM_CHECK(hipHostFree(s.h_in));
+        STM_CHECK(hipFree(s.d_in));
+        s.h_in = h_new[i];
+        s.d_in = d_new[i];
+    }
+    if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
+    f->din = on ? stm::DepthInput{format, lo, hi, fill, fill == 1 ? gate : 0.0f} : stm::DepthInput{-1, 0.0f, 0.0f, 0, 0.0f};
+    f->plane_off = on ? plane_off : 0;
+    f->in_bytes = need;
+    return 0;
+}
+
 // Stage frame `submitted`; at most two frames may be in flight (collect the older one first).
 // Returns the frame's index, or -1 when both slots are still uncollected.
 long stm_stream_submit(void *h, const unsigned char *img_sbs)
@@ -944,6 +1034,11 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     stm::ws_private_bind(s.ws);
     auto frame = [&]() {
         stm::ApiNest nest; // a failed upload above must survive the nested call's argument screen
+        if (f->din.format >= 0) { // an image and its depth plane: the second eye, then the stereo frame's own tail (no matcher)
+            stm::depth_frame_device(s.d_in, s.d_in + f->plane_off, f->din, s.d_dl, s.d_dr, s.d_out, f->H, f->Wsbs, f->W, f->Hout, f->Wout, f->E,
+                                    f->N, f->angle, f->stages);
+            return;
+        }
         if (f->match_h > 0) { // the reduced-resolution frame, picked as below
             if (f->in_format == 1) {
                 stm_d_adcensus_stm_2nv12(s.d_in, f->Wsbs, s.d_in + (size_t)f->rows_f * f->Wsbs, f->Wsbs, f->in_matrix, s.d_dl, s.d_dr, s.d_out,

@@ -56,16 +56,27 @@ class FrameStream:
     maps = (format, which, lo, hi) or a format alone: what the two disparity maps of a frame come back as (set_maps) -- "f32" (the
     default: float32 arrays), "none" (collect() and collect_view() return None for both), "u8" or "u16": depth planes of one code per
     pixel, code 0 at map value lo and the largest code at hi (lo > hi: near = dark), of the maps `which` selects ("left", "right" or
-    "both"; or 0, 1, 2) -- the other one comes back as None.  The float maps are computed either way; only the download changes."""
+    "both"; or 0, 1, 2) -- the other one comes back as None.  The float maps are computed either way; only the download changes.
+    depth_input = (format, lo, hi[, fill, gate]): the frames are one image and its depth plane (set_depth_input) -- format "f32", "u8"
+    or "u16", lo and hi the map values of code 0 and of the largest code (f32: the limits the values are clamped to), fill 0 =
+    constant extension of the background into the holes, 1 = continue the background where the mirror pixel lies within `gate` of it.
+    The image is the left eye, uint8 [H][depth_pitch][3] (depth_pitch = num_cols unless given), the plane [H][W] of disparities
+    x_right - x_left (smaller is nearer); submit_depth(img, plane) takes the two, pack_depth_frame lays them out as submit() and
+    input_buffer() see them.  The second eye is synthesised on the GPU and nothing is matched: collect() returns the decoded plane as
+    disp_l and the synthesised right map as disp_r.  Not together with NV12 input, a packing, a match size, an alignment, a balance
+    or stages beyond 3 | 0x800."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
                  depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None, overlay=None,
                  antialias=None, align=None, align_auto=None, balance=None, balance_auto=None, cut=None, overlay_auto=None,
-                 active=None, active_auto=None, active_fill=None, maps=None):
+                 active=None, active_auto=None, active_fill=None, maps=None, depth_input=None, depth_pitch=None):
         self.H, self.W = num_rows, num_cols
         self._maps = (0, 2)
+        self._depth_input = None
         self.packing = tuple(int(v) for v in packing) if packing is not None else (0, 0, 0, 0)
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
+        if depth_input is not None and packing is None:  # one image a frame: its rows are num_cols pixels unless the caller says otherwise
+            self.Wsbs = int(depth_pitch) if depth_pitch is not None else num_cols
         self._nv12 = False
         self.in_shape = (self.rows_f, self.Wsbs, 3)
         self.Ho, self.Wo = out_rows or num_rows, out_cols or num_cols
@@ -82,6 +93,8 @@ class FrameStream:
             self.set_packing(*self.packing)
         if input_format != "bgr":
             self.set_input(input_format, matrix)
+        if depth_input is not None:
+            self.set_depth_input(*depth_input)
         if lens is not None:
             self.set_lens(*lens)
         if layout is not None:
@@ -128,6 +141,43 @@ class FrameStream:
             raise ValueError("FrameStream: active_fill needs active or active_auto")
         if maps is not None:
             self.set_maps(*((maps,) if isinstance(maps, str) else maps))
+
+    def set_depth_input(self, format, lo=0.0, hi=0.0, fill=0, gate=0.0):
+        """stm_stream_input_depth: the frames are an image and its depth plane -- format "f32", "u8" or "u16" (or 0, 2, 3), None or
+        "off" (or -1) = side-by-side frames again; lo, hi, fill and gate as FrameStream's depth_input.  Buffers handed out by
+        input_buffer() before this call are void.  Only before the first submit.  Raises ValueError where the library refuses."""
+        fmt = {"f32": 0, "u8": 2, "u16": 3, "off": -1, None: -1}.get(format, format)
+        if not isinstance(fmt, int):
+            raise ValueError("FrameStream.set_depth_input: format %r" % (format,))
+        if int(lib().stm_stream_input_depth(self._h, fmt, float(lo), float(hi), int(fill), float(gate))) != 0:
+            raise ValueError("stm_stream_input_depth(%r, %g, %g, %d, %g) refused: %s" % (format, lo, hi, fill, gate, lib().stm_last_error().decode()))
+        self._depth_input = None if fmt < 0 else {0: np.dtype("<f4"), 2: np.dtype(np.uint8), 3: np.dtype("<u2")}[fmt]
+
+    def depth_frame_bytes(self):
+        """(the plane's byte offset in a depth frame, the frame's bytes): the image's bytes rounded up to a multiple of 16, and that
+        plus the tight plane"""
+        assert self._depth_input is not None
+        off = (self.H * self.Wsbs * 3 + 15) // 16 * 16
+        return off, off + self.H * self.W * self._depth_input.itemsize
+
+    def pack_depth_frame(self, img, plane):
+        """The flat frame of a stream with depth input: the image uint8 [H][Wsbs][3], then the plane [H][W] of the stream's format at
+        the next multiple of 16 bytes.  Returns a uint8 array of depth_frame_bytes()[1] bytes."""
+        off, n = self.depth_frame_bytes()
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        plane = np.asarray(plane)
+        if img.shape != self.in_shape or plane.shape != (self.H, self.W) or plane.dtype != self._depth_input:
+            raise ValueError("a depth frame is an image uint8 %s and a plane %s %s, got %s %s and %s %s"
+                             % (self.in_shape, self._depth_input, (self.H, self.W), img.dtype, img.shape, plane.dtype, plane.shape))
+        flat = np.zeros(n, np.uint8)
+        flat[:img.size] = img.reshape(-1)
+        flat[off:] = np.ascontiguousarray(plane).view(np.uint8).reshape(-1)
+        return flat
+
+    def submit_depth(self, img, plane):
+        """submit() for a stream with depth input: one image and its plane"""
+        flat = self.pack_depth_frame(img, plane)
+        return int(lib().stm_stream_submit(self._h, flat.ctypes.data_as(u8p)))
 
     def set_maps(self, format="f32", which="both", lo=0.0, hi=0.0):
         """stm_stream_maps: what a frame's disparity maps come back as -- "f32", "none", "u8" or "u16" (or 0 .. 3); for the planes
@@ -353,6 +403,9 @@ class FrameStream:
 
     def submit(self, sbs):
         sbs = np.ascontiguousarray(sbs, dtype=np.uint8)
+        if self._depth_input is not None:  # the flat frame pack_depth_frame returns
+            assert sbs.shape == (self.depth_frame_bytes()[1],)
+            return int(lib().stm_stream_submit(self._h, sbs.ctypes.data_as(u8p)))
         assert sbs.shape == self.in_shape
         return int(lib().stm_stream_submit(self._h, sbs.ctypes.data_as(u8p)))
 
@@ -362,6 +415,8 @@ class FrameStream:
         p = lib().stm_stream_input_buffer(self._h)
         if not p:
             return None
+        if self._depth_input is not None:  # flat: the image, then the plane at depth_frame_bytes()[0]
+            return np.ctypeslib.as_array(C.cast(p, u8p), shape=(self.depth_frame_bytes()[1],))
         return np.ctypeslib.as_array(C.cast(p, u8p), shape=self.in_shape)
 
     def submit_inplace(self):
@@ -547,6 +602,41 @@ def take_active_options(argv):
     return rect, auto, fill
 
 
+DEPTH_INPUT_FORMATS = {np.dtype(np.float32): "f32", np.dtype(np.uint8): "u8", np.dtype(np.uint16): "u16"}
+
+
+def take_depth_input_option(argv, stack=False):
+    """The drivers' --depth-input PLANE.npy LO HI [FILL GATE] (both of FILL and GATE or neither: 0 and 0), removed from argv.  The file
+    holds one plane [H][W] -- with `stack` a stack [n][H][W], one plane a frame -- of float32, uint8 or uint16, and the format follows
+    the dtype.  Returns (planes, (format, lo, hi, fill, gate)) or None; raises ValueError or IndexError for a malformed option, an
+    unreadable or misshapen file or a value stm_stream_input_depth would refuse."""
+    if "--depth-input" not in argv:
+        return None
+    at = argv.index("--depth-input")
+    path, lo, hi = argv[at + 1], float(argv[at + 2]), float(argv[at + 3])
+    vals = []
+    for tok in argv[at + 4:at + 6]:
+        try:
+            float(tok)
+        except ValueError:
+            break
+        vals.append(tok)
+    if len(vals) == 1:
+        raise ValueError("--depth-input takes FILL and GATE, or neither")
+    fill, gate = (int(vals[0]), float(vals[1])) if vals else (0, 0.0)
+    if not (abs(lo) <= 4096.0 and abs(hi) <= 4096.0 and abs(hi - lo) >= 1.0 / 64.0) or fill not in (0, 1) or not 0.0 <= gate <= 4096.0:  # a NaN fails
+        raise ValueError((lo, hi, fill, gate))
+    try:
+        planes = np.load(path, allow_pickle=False)
+    except OSError as e:
+        raise ValueError(str(e))
+    if planes.dtype not in DEPTH_INPUT_FORMATS or planes.ndim != (3 if stack else 2):
+        raise ValueError("--depth-input: %s holds %s %s, not %s of float32, uint8 or uint16"
+                         % (path, planes.dtype, planes.shape, "a stack [n][H][W]" if stack else "a plane [H][W]"))
+    del argv[at:at + 4 + len(vals)]
+    return planes, (DEPTH_INPUT_FORMATS[planes.dtype], lo, hi, fill, gate)
+
+
 def take_maps_option(argv):
     """The driver's --maps FORMAT [WHICH LO HI [FILE]], removed from argv: FORMAT f32, none, u8 or u16; for u8 and u16 WHICH (left,
     right or both) and the map values LO and HI of code 0 and of the largest code, then optionally the FILE the raw planes are
@@ -590,8 +680,9 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
                      depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None,
                      overlay=None, antialias=None, align=None, align_auto=None, on_align=None, balance=None, balance_auto=None,
                      on_balance=None, cut=None, on_cut=None, overlay_auto=None, on_overlay_depth=None, active=None,
-                     active_auto=None, active_fill=None, on_active=None, maps=None):
+                     active_auto=None, active_fill=None, on_active=None, maps=None, depth_input=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
+    depth_input: FrameStream's (format, lo, hi[, fill, gate]): `frames` then yields (image, plane) pairs, the image [H][W][3].
     maps: FrameStream's (format, which, lo, hi): disp_l and disp_r are then uint8 / uint16 depth planes, or None.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
@@ -613,14 +704,15 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
     pending = 0
     for sbs in frames:
         if fs is None:
-            rows = sbs.shape[0] * 2 // 3 if input_format == "nv12" else sbs.shape[0]
-            cols = sbs.shape[1] // 2
+            first = sbs[0] if depth_input is not None else sbs
+            rows = first.shape[0] * 2 // 3 if input_format == "nv12" else first.shape[0]
+            cols = first.shape[1] if depth_input is not None else first.shape[1] // 2
             if packing is not None:
                 rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
             fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output,
                              overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]), antialias=antialias,
                              align=align, align_auto=align_auto, balance=balance, balance_auto=balance_auto, cut=cut, overlay_auto=overlay_auto,
-                             active=active, active_auto=active_auto, active_fill=active_fill, maps=maps)
+                             active=active, active_auto=active_auto, active_fill=active_fill, maps=maps, depth_input=depth_input)
             if overlay is not None:
                 fs.overlay(*overlay)
             if temporal is not None:
@@ -628,7 +720,10 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
         if pending == 2:
             yield _collect(fs, on_depth, on_align, on_balance, on_cut, on_overlay_depth, on_active)
             pending -= 1
-        fs.submit(sbs)
+        if depth_input is not None:
+            fs.submit_depth(*sbs)
+        else:
+            fs.submit(sbs)
         pending += 1
     while fs is not None and pending:
         yield _collect(fs, on_depth, on_align, on_balance, on_cut, on_overlay_depth, on_active)

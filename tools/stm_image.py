@@ -10,6 +10,7 @@ usage: stm_image.py <left.bmp> <right.bmp> <ad coeff> <census coeff> <ndisp> <ze
                     [--antialias STRENGTH MAX_RADIUS GATE] [--align A B C | --align-auto RADIUS [RATE]]
                     [--balance FILE.npy | --balance-auto [MAX_SHIFT RATE]]
                     [--active T B L R | --active-auto [THRESH LIT MAX_BAR HOLD]] [--active-fill DISP]
+                    [--depth-input PLANE.npy LO HI [FILL GATE]]
 
 --interp (an addition, off by default): the outlier interpolation (host_api.dr_interp) of both maps after region voting, each on
 its own image and outlier map, before --subpixel.
@@ -38,7 +39,13 @@ moving no level by more than MAX_SHIFT (48); one still pair: RATE has nothing to
 --active-auto [THRESH LIT MAX_BAR HOLD]: the rectangle is measured on the left image (host_api.active_detect: a line is picture
 when more than LIT permille (10) of its pixels have a luma above THRESH (24), a bar is at most MAX_BAR permille (300) of the frame to
 a side; one still pair: HOLD has nothing to wait for and is accepted for symmetry) and printed.  --active-fill DISP (with either):
-both final maps take DISP in the bars (host_api.active_fill) before the views are rendered from them."""
+both final maps take DISP in the bars (host_api.active_fill) before the views are rendered from them.
+--depth-input PLANE.npy LO HI [FILL GATE] (an addition): <left.bmp> comes with its depth plane instead of a right image -- PLANE.npy
+holds [H][W] float32, uint8 or uint16 disparities x_right - x_left (the format follows the dtype; code 0 at LO, the largest code at
+HI; float32: clamped to the two), <right.bmp> is not read ("-" will do) and the matching parameters are read and ignored.  The second
+eye is synthesised on the GPU (stm_stream_input_depth; FILL 0 = the background extended into the holes, 1 = continued from the mirror
+pixel within GATE) and the frame rendered by a one-frame stream, which has no per-stage products: disp_l (the decoded plane), disp_r
+(the synthesised map) and the output frame are written.  Excludes --interp, --subpixel, --align, --balance and their -auto forms."""
 import os
 import sys
 
@@ -46,6 +53,36 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def depth_input_frame(a, depth_input, linear_warp, lens, quilt, antialias, active, active_auto, active_fill):
+    """--depth-input: the left image and its plane through a one-frame stream"""
+    import stm_amd
+    from stm_amd import device_api as dev, video
+    L = stm_amd.bmp_io.read_bmp(a[0])
+    plane, setting = depth_input
+    if plane.shape != L.shape[:2]:
+        print("Error! the image is %d x %d, the depth plane %s" % (L.shape[0], L.shape[1], plane.shape))
+        return -1
+    N, angle, Wo, Ho = int(a[10]), float(a[11]), int(a[12]), int(a[13])
+    out = a[16] if len(a) > 16 else "stm_out"
+    os.makedirs(out, exist_ok=True)
+    try:
+        fs = video.FrameStream(L.shape[0], L.shape[1], dev.FrameParams(num_views=N, angle=angle), Ho, Wo, 3 | (0x800 if linear_warp else 0),
+                               lens=lens, layout=None if quilt is None else (1,) + quilt, antialias=antialias, active=active,
+                               active_auto=active_auto, active_fill=active_fill, depth_input=setting)
+    except ValueError as e:
+        print("Error! %s" % e)
+        return -1
+    try:
+        fs.submit_depth(L, plane)
+        _, dl, dr, frame = fs.collect()
+    finally:
+        fs.close()
+    for name, img in (("disp_l", video.normalize_minmax_u8(dl)), ("disp_r", video.normalize_minmax_u8(dr)), ("interlaced", frame)):
+        stm_amd.bmp_io.write_bmp(os.path.join(out, name + ".bmp"), img)
+    print("wrote 3 files to %s (%dx%d, %d views, depth input %s)" % (out, L.shape[1], L.shape[0], N, setting[0]))
+    return 0
 
 
 def main(argv):
@@ -112,6 +149,10 @@ def main(argv):
         from stm_amd import video
         balance, balance_auto = video.take_balance_options(argv)
         active, active_auto, active_fill = video.take_active_options(argv)
+        depth_input = video.take_depth_input_option(argv)
+        if depth_input is not None and (subpixel or interp or align is not None or align_auto is not None or balance is not None
+                                        or balance_auto is not None):
+            raise ValueError("--depth-input")
     except (ValueError, IndexError):
         print(__doc__)
         return -1
@@ -121,6 +162,8 @@ def main(argv):
     import stm_amd
     from stm_amd import host_api as api, video
     a = argv[1:]
+    if depth_input is not None:
+        return depth_input_frame(a, depth_input, linear_warp, lens, quilt, antialias, active, active_auto, active_fill)
     L, R = stm_amd.bmp_io.read_bmp(a[0]), stm_amd.bmp_io.read_bmp(a[1])
     if L.shape != R.shape:
         print("Error! left and right image sizes differ: %s vs %s" % (L.shape, R.shape))

@@ -12,7 +12,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--align A B C | --align-auto RADIUS [RATE]] [--balance FILE.npy | --balance-auto [MAX_SHIFT RATE]]
                     [--cut [THRESH MIN_GAP]]
                     [--active T B L R | --active-auto [THRESH LIT MAX_BAR HOLD]] [--active-fill DISP]
-                    [--maps FORMAT [WHICH LO HI [FILE]]]
+                    [--maps FORMAT [WHICH LO HI [FILE]]] [--depth-input PLANES.npy LO HI [FILL GATE]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -82,6 +82,12 @@ back with DISP (|DISP| <= 4096) in the bars.
 u16: depth planes of one code per pixel of the maps WHICH selects (left, right or both), code 0 at map value LO and the largest code
 at HI (LO > HI: near = dark; both within +-4096, at least 1/64 apart).  Every frame's planes -- raw, tight, u16 little-endian, the
 left one first -- are appended to FILE (default <out dir>/maps_u8.raw or maps_u16.raw).
+--depth-input PLANES.npy LO HI [FILL GATE] (an addition; put it behind the positional arguments): the frames of <frames dir> are single
+images, the left eye, and PLANES.npy holds their depth planes, a stack [n][H][W] of float32, uint8 or uint16 (the format follows the
+dtype; stm_stream_input_depth): disparities x_right - x_left, code 0 at LO and the largest code at HI (float32: clamped to the two).
+The second eye is synthesised on the GPU and nothing is matched; FILL 0 (the default) extends the background into the disoccluded
+holes, FILL 1 continues it from the mirror pixel where that lies within GATE of the background.  The matching parameters are read and
+ignored; excludes --nv12, --packing, --match, --align, --balance and the frame bits other than --linear-warp.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -290,6 +296,10 @@ def main(argv):
         cut = video.take_cut_option(argv)
         active, active_auto, active_fill = video.take_active_options(argv)
         maps = video.take_maps_option(argv)
+        depth_input = video.take_depth_input_option(argv, stack=True)
+        if depth_input is not None and (nv12 is not None or packing is not None or match is not None or align is not None or align_auto is not None
+                                        or balance is not None or balance_auto is not None or (stages & ~0x800) != 3):
+            raise ValueError("--depth-input")
     except (ValueError, IndexError):
         print(__doc__)
         return -1
@@ -306,6 +316,8 @@ def main(argv):
     out_w, out_h = int(a[3]), int(a[4])
     out_dir = a[15] if len(a) > 15 else os.path.join(a[0] if nv12 is None else os.path.dirname(os.path.abspath(a[0])), "out")
     frames = video.read_bmp_sequence(a[0]) if nv12 is None else video.read_nv12_sequence(a[0], *nv12)
+    if depth_input is not None:  # one image a frame and its plane of the stack
+        frames = zip(frames, depth_input[0])
     yuv = None
     if nv12_out is not None:
         os.makedirs(out_dir, exist_ok=True)
@@ -343,7 +355,8 @@ def main(argv):
                                                        active=active, active_auto=active_auto, active_fill=active_fill,
                                                        on_active=(lambda k, r: print("frame %d: active rows %d..%d cols %d..%d changed %d" % ((k,) + r)))
                                                        if active_auto is not None else None,
-                                                       maps=None if maps is None else maps[:4]):
+                                                       maps=None if maps is None else maps[:4],
+                                                       depth_input=None if depth_input is None else depth_input[1]):
         if yuv is not None:  # the frame is [out height * 3 / 2][out width]: the Y plane, then the interleaved UV plane
             yuv.write(inter.tobytes())
         else:
