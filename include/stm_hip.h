@@ -1584,7 +1584,10 @@ long  stm_stream_collect_maps(void *stream, void *plane_l, void *plane_r, unsign
 long  stm_stream_collect_maps_view(void *stream, const void **plane_l, const void **plane_r, const unsigned char **interlaced);
 /* image-plus-depth input of a frame stream (an image with its depth plane in, the second eye built on the GPU): its one entry
  * point is declared, with the definition line by line, in stm_depth_input.h.  This header's set of names is recorded in the
- * screening tables of the test suite and stays what it is. */
+ * screening tables of the test suite and stays what it is.
+ * Rectification from camera calibration (both eyes remapped through a camera matrix, distortion coefficients and a rectifying
+ * rotation, as a stage and as the first step of a stream's frames): its entry points are declared, with the definition line by
+ * line, in stm_rectify.h, for the same reason. */
 void  stm_stream_destroy(void *stream);
 
 /* ----------------------------------------------------------------- BMP I/O */

@@ -208,6 +208,14 @@ PROTOS = {
 PROTOS_DEPTH = {
     "stm_stream_input_depth": ([C.c_void_p, i, f, f, i, f], i),
 }
+# include/stm_rectify.h: rectification from camera calibration, likewise in a header and a table of its own
+PROTOS_RECTIFY = {
+    "stm_rectify": ([u8p, u8p, f32p, i, i, i, i], None),
+    "stm_d_rectify": ([vp, vp, f32p, i, i, i, i], None),
+    "stm_rectify_coords": ([C.POINTER(C.c_int), f32p, i, i], None),
+    "stm_stream_rectify": ([C.c_void_p, i, f32p, i], i),
+    "stm_stream_get_rectify": ([C.c_void_p, C.POINTER(C.c_int), f32p, C.POINTER(C.c_int)], i),
+}
 
 _lib = None
 
@@ -225,7 +233,7 @@ def lib():
         # other order starts two runtimes and the second one finds "no ROCm-capable device".
         import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
-        for name, (args, res) in list(PROTOS.items()) + list(PROTOS_DEPTH.items()):
+        for name, (args, res) in list(PROTOS.items()) + list(PROTOS_DEPTH.items()) + list(PROTOS_RECTIFY.items()):
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = res

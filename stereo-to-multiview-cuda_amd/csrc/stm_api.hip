@@ -5,6 +5,7 @@
 #include <initializer_list>
 #include <mutex>
 #include "../../include/stm_hip.h"
+#include "../../include/stm_rectify.h"
 
 #include <map>
 #include <stdio.h>
@@ -1054,6 +1055,54 @@ void stm_align_rows(unsigned char *img_out, const unsigned char *img, int num_ro
     down(img_out, o, IMG);
     sync();
 }
+// =============================================================== rectification: one image through one record, and the test tap
+// (include/stm_rectify.h; an addition, the reference has none: it takes rectified pairs)
+static bool rectify_dims_ok(const char *fn, int num_rows, int num_cols)
+{
+    if (!args_ok(fn, {{"num_rows", num_rows, 1}, {"num_cols", num_cols, 1}})) return false;
+    if (num_rows > 16384) return STM_REJECT("num_rows", "%s: num_rows = %d, must be <= 16384", fn, num_rows);
+    if (num_cols > 16384) return STM_REJECT("num_cols", "%s: num_cols = %d, must be <= 16384", fn, num_cols);
+    return true;
+}
+static bool rectify_args_ok(const char *fn, const unsigned char *img_out, const unsigned char *img, const float *rec18, int num_rows,
+                            int num_cols, int elem_sz, int border)
+{
+    if (!rectify_dims_ok(fn, num_rows, num_cols) || !args_ok(fn, {{"elem_sz", elem_sz, 3}})) return false;
+    if (!ptrs_ok(fn, {{"img_out", img_out}, {"img", img}, {"rec18", rec18}})) return false;
+    if (!rectify_params_ok(fn, rec18, border)) return false;
+    const size_t bytes = (size_t)num_rows * num_cols * elem_sz;
+    if (bytes_overlap(img_out, bytes, img, bytes)) return STM_REJECT("img_out", "%s: img_out must not overlap img", fn); // a pixel's taps are other pixels' outputs
+    return true;
+}
+void stm_d_rectify(unsigned char *d_img_out, const unsigned char *d_img, const float *rec18, int num_rows, int num_cols, int elem_sz, int border)
+{
+    if (!rectify_args_ok("d_rectify", d_img_out, d_img, rec18, num_rows, num_cols, elem_sz, border)) return;
+    launch_rectify_frame(d_img_out, nullptr, d_img, num_rows, num_cols, elem_sz, (const float (*)[18])rec18, border);
+}
+void stm_rectify(unsigned char *img_out, const unsigned char *img, const float *rec18, int num_rows, int num_cols, int elem_sz, int border)
+{
+    if (!rectify_args_ok("rectify", img_out, img, rec18, num_rows, num_cols, elem_sz, border)) return;
+    const size_t IMG = (size_t)num_rows * num_cols * elem_sz;
+    Workspace::begin(2 * IMG + 8192);
+    const u8 *i = up(img, IMG);
+    u8 *o = Workspace::get<u8>(IMG);
+    if (elem_sz > 3) STM_CHECK(hipMemsetAsync(o, 0, IMG, stream())); // bytes past the third come back 0
+    launch_rectify_frame(o, nullptr, i, num_rows, num_cols, elem_sz, (const float (*)[18])rec18, border);
+    down(img_out, o, IMG);
+    sync();
+}
+void stm_rectify_coords(int *quv, const float *rec18, int num_rows, int num_cols)
+{
+    const char *fn = "rectify_coords";
+    if (!rectify_dims_ok(fn, num_rows, num_cols)) return;
+    if (!ptrs_ok(fn, {{"quv", quv}, {"rec18", rec18}}) || !rectify_params_ok(fn, rec18, 0)) return;
+    const size_t n = (size_t)num_rows * num_cols * 2;
+    Workspace::begin(n * 4 + 8192);
+    int *d = Workspace::get<int>(n);
+    launch_rectify_coords(d, num_rows, num_cols, rec18);
+    down(quv, d, n);
+    sync();
+}
 static bool align_fit_args_ok(const char *fn, const unsigned char *img_l, const unsigned char *img_r, int num_rows, int num_cols, int elem_sz,
                               int radius, float rate, const float *state)
 {
@@ -1977,6 +2026,36 @@ u8 *align_frame_input(const Align &al, const PackInput &in, const u8 *prev_frame
     return out;
 }
 
+// ---- the rectification of a frame call's input (a frame stream's stm_stream_rectify), ahead of every other prelude
+// the thread's setting against a frame call's geometry; off: nothing to check, the call is as it was
+bool frame_rectify_ok(const char *fn, int num_cols_sbs, int num_cols, bool bgr_sbs)
+{
+    if (!rectify().mode) return true;
+    if (bgr_sbs && num_cols_sbs < 2 * num_cols) // both eyes are gathered from the frame
+        return STM_REJECT("num_cols_sbs", "%s: a rectification is on (stm_stream_rectify), which needs num_cols_sbs >= 2 * num_cols", fn);
+    return true;
+}
+// the workspace the prelude below takes: the rectified frame (and the previous frame's)
+size_t rectify_ws_bytes(size_t IMG, bool prev) { return (prev ? 4 : 2) * IMG + 1024; }
+// The prelude, inside the frame call's Workspace scope: the unpacked, converted pair, each eye through its record, returned as one
+// side-by-side BGR frame (H x 2 W x elem_sz) in the workspace.  prev_frame != nullptr: the previous BGR frame, of the same
+// geometry, through the same kernel with the same records into prev_out.
+u8 *rectify_frame_input(const Rectify &rc, const PackInput &in, const u8 *prev_frame, int H, int W, int elem_sz, const u8 *&prev_out)
+{
+    const size_t IMG = (size_t)H * W * elem_sz;
+    u8 *out = Workspace::get<u8>(2 * IMG);
+    launch_rectify_frame(out, &in, nullptr, H, W, elem_sz, rc.rec, rc.border);
+    prev_out = nullptr;
+    if (prev_frame) {
+        PackInput prev = in;
+        prev.frame = prev_frame;
+        u8 *po = Workspace::get<u8>(2 * IMG);
+        launch_rectify_frame(po, &prev, nullptr, H, W, elem_sz, rc.rec, rc.border);
+        prev_out = po;
+    }
+    return out;
+}
+
 // ---- the colour balance of a frame call's input (stm_set_balance), after the alignment
 // the thread's setting against a frame call's geometry; off: nothing to check, the call is as it was
 bool frame_balance_ok(const char *fn, int num_rows, int num_cols_sbs, int num_cols, bool bgr_sbs)
@@ -2073,7 +2152,7 @@ void frame_active_fill(const int *d_rect, float *d_disp_l, float *d_disp_r, int 
 bool frame_settings_ok(const char *fn, const FrameArgs &a, const Nv12Input *nv)
 {
     const bool bgr_sbs = !nv && !packing().on(); // both eyes are gathered from a side-by-side BGR frame
-    return frame_align_ok(fn, a.num_rows, a.num_cols_sbs, a.num_cols, bgr_sbs) &&
+    return frame_rectify_ok(fn, a.num_cols_sbs, a.num_cols, bgr_sbs) && frame_align_ok(fn, a.num_rows, a.num_cols_sbs, a.num_cols, bgr_sbs) &&
            frame_balance_ok(fn, a.num_rows, a.num_cols_sbs, a.num_cols, bgr_sbs) && frame_cut_ok(fn, a.num_rows, a.num_cols) &&
            frame_active_ok(fn, a.num_rows, a.num_cols);
 }
@@ -2083,6 +2162,7 @@ size_t frame_settings_ws_bytes(const FrameArgs &a, bool prev)
     const size_t IMG = (size_t)a.num_rows * a.num_cols * a.elem_sz;
     return (output().format == 1 ? (size_t)a.num_rows_out * a.num_cols_out * a.elem_sz : 0) + // the un-fused NV12 frame's BGR quilt
            (antialias().mode == 1 ? 2 * IMG + 512 : 0) +                                       // the prefiltered pair
+           (rectify().mode ? rectify_ws_bytes(IMG, prev) : 0) +                                // the rectified frame(s)
            (align().mode ? align_ws_bytes(a.num_rows, IMG, prev) : 0) +                        // the aligned frame(s)
            (balance().mode ? balance_ws_bytes(IMG, prev) : 0) +                                // the balanced frame(s)
            (cut().mode ? cut_ws_bytes() : 0) +                                                 // the detector's signature
@@ -2100,8 +2180,9 @@ struct FrameInput {
     PackInput pin;          // the frame as the call was given it
     const int *rect;        // the active rectangle's four words in device memory (stm_set_active), null with the setting off
 };
-// The prelude, inside the frame call's Workspace scope and after the split images (and the reduced pair) have been carved: cut,
-// then align, then balance, each where its setting is on.  After an alignment or a balance the call is the plain BGR frame call on
+// The prelude, inside the frame call's Workspace scope and after the split images (and the reduced pair) have been carved: the
+// rectification, then cut, active area, align and balance, each where its setting is on.  After a rectification every later step
+// sees the plain BGR frame call on the rectified pair.  After an alignment or a balance the call is the plain BGR frame call on
 // the prepared side-by-side frame, and a side-by-side history has gone through the same field and tables.
 FrameInput frame_input(const FrameArgs &a, const u8 *d_img_sbs, const Nv12Input *nv, const TemporalHist *hist)
 {
@@ -2113,10 +2194,20 @@ FrameInput frame_input(const FrameArgs &a, const u8 *d_img_sbs, const Nv12Input 
     FrameInput in = {d_img_sbs, a.num_cols_sbs, nv, hist ? hist->sbs : nullptr, pack.on() && !aln.mode && !bal.mode, nv != nullptr,
                      {pack, nv != nullptr, d_img_sbs, a.num_cols_sbs, nv ? nv->y : nullptr, nv ? nv->uv : nullptr, nv ? nv->pitch_y : 0,
                       nv ? nv->pitch_uv : 0, nv ? nv->matrix : 0}, nullptr};
+    const bool sbs_hist = hist && !in.split_hist;
+    const Rectify rc = rectify();
+    if (rc.mode) { // first of all: from here on the call is the plain BGR frame call on the rectified side-by-side frame
+        const u8 *prev = nullptr;
+        in.d_img_sbs = rectify_frame_input(rc, in.pin, sbs_hist ? in.prev_sbs : nullptr, H, W, elem_sz, prev);
+        if (sbs_hist) in.prev_sbs = prev;
+        in.pin = PackInput{Packing{0, 0, 0, 0}, false, in.d_img_sbs, 2 * W, nullptr, nullptr, 0, 0, 0};
+        in.num_cols_sbs = 2 * W;
+        in.nv = nullptr;
+        in.pack_on = false;
+    }
     if (ct.mode) cut_frame_input(ct, in.pin, H, W, elem_sz, (a.stages & 0xff) >= 3, aln, bal); // before any state's fit runs
     const Active ac = active();
     in.rect = ac.mode ? active_frame_input(ac, ct, in.pin, H, W, elem_sz) : nullptr; // after the cut flag, on the input as given
-    const bool sbs_hist = hist && !in.split_hist;
     if (aln.mode) { // from here on the call is the plain BGR frame call on the aligned side-by-side frame
         const u8 *prev = nullptr;
         in.d_img_sbs = align_frame_input(aln, in.pin, sbs_hist ? in.prev_sbs : nullptr, H, W, elem_sz, prev);

@@ -498,6 +498,25 @@ void launch_align_measure(float *state, int *nvalid, uint32_t *prof, uint32_t *s
 // the field applied: a screened frame (in != nullptr) as the aligned side-by-side BGR frame `out` (H x 2 W x elem_sz, the left eye
 // copied), or the one image img (H x W x elem_sz) into out; state != nullptr: a, b, c are read from state[1 .. 3] on the device
 void launch_align_frame(u8 *out, const PackInput *in, const u8 *img, int H, int W, int elem_sz, float a, float b, float c, const float *state);
+// Rectification from camera calibration (stm_stream_rectify, include/stm_rectify.h): mode 0 = off (not one launch changes), 1 = both
+// eyes remapped through their records of 18 floats (rec[0] the left eye's, rec[1] the right's) ahead of everything else a frame
+// call does.  One per host thread, but no exported setter: a frame stream installs its own copy around its frame calls.
+struct Rectify {
+    int mode;
+    float rec[2][18];
+    int border; // 0 = taps outside the eye are 0, 1 = their coordinates are clamped
+};
+Rectify rectify();
+void set_rectify(const Rectify &r);
+// the rules of a record and a border; false with the error recorded
+bool rectify_params_ok(const char *fn, const float *rec18, int border);
+// the remap (stm_kernels_rectify.hip).  A screened frame (in != nullptr): both eyes, unpacked and converted, through rec[0] and rec[1]
+// into the side-by-side BGR frame `out` (H x 2 W x elem_sz; 16-byte aligned with 3- or 4-byte pixels: dword or wider stores, a
+// 4-byte pixel's last byte written 0).  in == nullptr: the one image img (H x W x elem_sz) through rec[0] into out, at any address; of a pixel of more than
+// three bytes the first three are written
+void launch_rectify_frame(u8 *out, const PackInput *in, const u8 *img, int H, int W, int elem_sz, const float (*rec)[18], int border);
+// the test tap: (qu, qv) per pixel of one eye, INT32_MIN twice where the pixel is not ok
+void launch_rectify_coords(int *quv, int H, int W, const float *rec18);
 // The colour balance between the eyes (stm_set_balance / stm_set_balance_auto, include/stm_hip.h): mode 0 = off (not one launch
 // changes), 1 = given (the right eye through the three tables lut), 2 = measured (the tables fitted on each frame on the device).
 // One per host thread, next to the alignment; a frame stream installs its own copy around its frame calls.

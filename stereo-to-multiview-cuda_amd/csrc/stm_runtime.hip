@@ -447,6 +447,18 @@ bool align_params_ok(const char *fn, int mode, float a, float b, float c)
     if (!(fabsf(c) <= FLT_MAX)) return STM_REJECT("c", "%s: align c = %g, must be finite", fn, (double)c);
     return true;
 }
+// the calling thread's rectification: installed by a frame stream only (stm_stream_rectify), there is no exported setter
+static thread_local Rectify g_rectify = {0, {{0.0f}, {0.0f}}, 0};
+Rectify rectify() { return g_rectify; }
+void set_rectify(const Rectify &r) { g_rectify = r; }
+bool rectify_params_ok(const char *fn, const float *rec18, int border)
+{
+    if (border != 0 && border != 1) return STM_REJECT("border", "%s: border = %d, must be 0 (taps outside are 0) or 1 (clamped)", fn, border);
+    for (int i = 0; i < 18; ++i)
+        if (!(fabsf(rec18[i]) <= FLT_MAX)) // NaN fails the comparison
+            return STM_REJECT("rec18", "%s: rec18[%d] = %g, must be finite", fn, i, (double)rec18[i]);
+    return true;
+}
 bool align_auto_params_ok(const char *fn, int radius, float rate)
 {
     if (radius < 1 || radius > 32) return STM_REJECT("radius", "%s: radius = %d, must be in 1 .. 32", fn, radius);

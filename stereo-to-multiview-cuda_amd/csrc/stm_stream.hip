@@ -12,6 +12,7 @@
 #include "stm_common.h"
 #include "../../include/stm_hip.h"
 #include "../../include/stm_depth_input.h"
+#include "../../include/stm_rectify.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -92,6 +93,7 @@ struct FrameStream {
     int planes = 0;                      // ... and how many a frame has (which 2: left, then right)
     stm::DepthInput din = {-1, 0.0f, 0.0f, 0, 0.0f}; // stm_stream_input_depth: a frame is an image and its depth plane (format -1 = off)
     size_t plane_off = 0;                // ... the plane's byte offset in a frame: the image's bytes rounded up to a multiple of 16
+    stm::Rectify rectify = {0, {{0.0f}, {0.0f}}, 0}; // stm_stream_rectify: the stream's own rectification, installed around its frame calls
     Slot slot[2];
     long submitted = 0, collected = 0;
 };
@@ -125,6 +127,12 @@ struct AlignScope {
     stm::Align saved;
     explicit AlignScope(const stm::Align &a) : saved(stm::align()) { stm::set_align(a); }
     ~AlignScope() { stm::set_align(saved); }
+};
+
+struct RectifyScope {
+    stm::Rectify saved;
+    explicit RectifyScope(const stm::Rectify &r) : saved(stm::rectify()) { stm::set_rectify(r); }
+    ~RectifyScope() { stm::set_rectify(saved); }
 };
 
 struct BalanceScope {
@@ -936,6 +944,8 @@ int stm_stream_input_depth(void *h, int format, float lo, float hi, int fill, fl
         return STM_REJECT("align", "%s: the stream has an alignment (stm_stream_set_align): there is no second image to align", fn) ? 0 : -1;
     if (on && f->balance.mode != 0)
         return STM_REJECT("balance", "%s: the stream has a colour balance (stm_stream_set_balance): there is no second image to balance", fn) ? 0 : -1;
+    if (on && f->rectify.mode != 0)
+        return STM_REJECT("rectify", "%s: the stream has a rectification (stm_stream_rectify): an image-plus-depth frame is not rectified", fn) ? 0 : -1;
     if (on && (f->stages & ~0x800) != 3)
         return STM_REJECT("stages", "%s: the stream's stages are 0x%x (stm_stream_set_stages): a depth frame takes 3 or 3 | 0x800, nothing is "
                           "matched", fn, f->stages) ? 0 : -1;
@@ -969,6 +979,43 @@ int stm_stream_input_depth(void *h, int format, float lo, float hi, int fill, fl
     f->din = on ? stm::DepthInput{format, lo, hi, fill, fill == 1 ? gate : 0.0f} : stm::DepthInput{-1, 0.0f, 0.0f, 0, 0.0f};
     f->plane_off = on ? plane_off : 0;
     f->in_bytes = need;
+    return 0;
+}
+
+// The rectification every frame of the stream starts with (stm_rectify.h has the definition): mode 0 = off (the default), 1 = the
+// left eye's record, then the right eye's, copied into the stream and installed around its frame calls like the alignment; the
+// kernel takes them by value, so nothing is allocated.  Not together with depth input, in either order.  Only before the first
+// submit.  Returns 0, or -1 with the error recorded and the stream unchanged.
+int stm_stream_rectify(void *h, int mode, const float *rec36, int border)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    const char *fn = "stream_rectify";
+    if (mode != 0 && mode != 1) return STM_REJECT("mode", "%s: mode = %d, must be 0 (off) or 1 (both eyes through their records)", fn, mode) ? 0 : -1;
+    if (mode == 1) {
+        if (!stm::ptrs_ok(fn, {{"rec36", rec36}})) return -1;
+        if (!stm::rectify_params_ok(fn, rec36, border) || !stm::rectify_params_ok(fn, rec36 + 18, border)) return -1;
+    }
+    if (mode != 0 && !no_depth_input(f, fn, "stream")) return -1; // ahead of the geometry rule, as in stm_stream_set_align
+    if (mode != 0 && !f->packing.on() && f->in_format == 0 && f->Wsbs < 2 * f->W)
+        return STM_REJECT("num_cols_sbs", "%s: a rectification needs num_cols_sbs >= 2 * num_cols", fn) ? 0 : -1;
+    if (!not_submitted(f, fn)) return -1;
+    stm::Rectify r = {0, {{0.0f}, {0.0f}}, 0};
+    if (mode == 1) {
+        r.mode = 1;
+        r.border = border;
+        memcpy(r.rec, rec36, sizeof r.rec);
+    }
+    f->rectify = r;
+    return 0;
+}
+int stm_stream_get_rectify(void *h, int *mode, float *rec36, int *border)
+{
+    const FrameStream *f = (const FrameStream *)h;
+    if (!f) return -1;
+    if (mode) *mode = f->rectify.mode;
+    if (rec36 && f->rectify.mode) memcpy(rec36, f->rectify.rec, sizeof f->rectify.rec);
+    if (border && f->rectify.mode) *border = f->rectify.border;
     return 0;
 }
 
@@ -1024,6 +1071,7 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     DepthScope depth_scope(f->depth);
     AntialiasScope antialias_scope(f->antialias);
     AlignScope align_scope(f->align);
+    RectifyScope rectify_scope(f->rectify);
     BalanceScope balance_scope(f->balance);
     CutScope cut_scope(f->cut);
     ActiveScope active_scope(f->active);

@@ -459,6 +459,19 @@ def d_align_rows(out, img, a, b, c):
     lib().stm_d_align_rows(_p(out), _p(img), H, W, E, float(a), float(b), float(c))
 
 
+def d_rectify(out, img, rec, border=0):
+    """stm_d_rectify: img (uint8 [H][W][E] on the GPU) through the rectification record rec (18 floats, host memory) into out, which
+    must not overlap img; border 0 = taps outside are 0, 1 = clamped.  Only bytes 0 .. 2 of a pixel are written."""
+    import numpy as np
+    H, W, E = img.shape
+    for t in (out, img):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == (H, W, E)
+    r = np.ascontiguousarray(rec, dtype=np.float32)
+    assert r.shape == (18,)
+    _use_current_stream()
+    lib().stm_d_rectify(_p(out), _p(img), r.ctypes.data_as(f32p), H, W, E, int(border))
+
+
 def d_align_fit(img_l, img_r, radius, rate, state, valid_blocks=None, profiles=None, sad=None):
     """stm_d_align_fit: the measurement of the automatic alignment as a stage -- the two unpacked images (uint8 [H][W][E] on the
     GPU) into the band profiles, their gradients' SADs, the fit, the update of `state` (float32, four elements on the GPU) in

@@ -426,6 +426,30 @@ def align_rows(img, a, b, c):
     return out
 
 
+def rectify(img, rec, border=0):
+    """One image through one rectification record (stm_rectify, include/stm_rectify.h; an addition, the reference takes rectified
+    pairs): img [H][W][E] sampled bilinearly, in 1/32 pixel, where the record's camera model puts each output pixel; border 0 =
+    taps outside the image are 0, 1 = their coordinates are clamped.  rec: 18 floats (stm_amd.rectify.record).  Returns the
+    [H][W][E] image (bytes of a pixel past the third are 0); nothing passed in is modified."""
+    img, pi = _u8(img)
+    H, W, E = img.shape
+    rec, pr = _f32(rec)
+    assert rec.shape == (18,)
+    out = np.zeros((H, W, E), np.uint8)
+    lib().stm_rectify(out.ctypes.data_as(u8p), pi, pr, H, W, E, int(border))
+    return out
+
+
+def rectify_coords(rec, num_rows, num_cols):
+    """The test tap on the record's coordinate chain (stm_rectify_coords): int32 [H][W][2] of (qu, qv), the source position in 1/32
+    pixel, both INT32_MIN where the pixel is not ok."""
+    rec, pr = _f32(rec)
+    assert rec.shape == (18,)
+    quv = np.zeros((int(num_rows), int(num_cols), 2), np.int32)
+    lib().stm_rectify_coords(quv.ctypes.data_as(C.POINTER(C.c_int)), pr, int(num_rows), int(num_cols))
+    return quv
+
+
 def align_fit(img_l, img_r, radius=16, rate=1.0, state=None):
     """The measurement of the automatic alignment (stm_align_fit): the vertical offset field a + b u + c v at which the right
     image's content matches the left image's rows, from the SADs of band profiles over +-radius rows, folded into `state` =

@@ -64,12 +64,16 @@ class FrameStream:
     x_right - x_left (smaller is nearer); submit_depth(img, plane) takes the two, pack_depth_frame lays them out as submit() and
     input_buffer() see them.  The second eye is synthesised on the GPU and nothing is matched: collect() returns the decoded plane as
     disp_l and the synthesised right map as disp_r.  Not together with NV12 input, a packing, a match size, an alignment, a balance
-    or stages beyond 3 | 0x800."""
+    or stages beyond 3 | 0x800.
+    rectify = (rec_l, rec_r[, border]): every frame's eyes are first remapped through their rectification records (set_rectify;
+    stm_amd.rectify.record makes one from a camera calibration), ahead of every other setting: the stream is then, by definition,
+    the stream without it on the rectified pairs.  border 0 (the default) = taps outside an eye are 0, 1 = clamped.  Not together
+    with depth_input."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
                  depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None, overlay=None,
                  antialias=None, align=None, align_auto=None, balance=None, balance_auto=None, cut=None, overlay_auto=None,
-                 active=None, active_auto=None, active_fill=None, maps=None, depth_input=None, depth_pitch=None):
+                 active=None, active_auto=None, active_fill=None, maps=None, depth_input=None, depth_pitch=None, rectify=None):
         self.H, self.W = num_rows, num_cols
         self._maps = (0, 2)
         self._depth_input = None
@@ -95,6 +99,8 @@ class FrameStream:
             self.set_input(input_format, matrix)
         if depth_input is not None:
             self.set_depth_input(*depth_input)
+        if rectify is not None:
+            self.set_rectify(*rectify)
         if lens is not None:
             self.set_lens(*lens)
         if layout is not None:
@@ -152,6 +158,25 @@ class FrameStream:
         if int(lib().stm_stream_input_depth(self._h, fmt, float(lo), float(hi), int(fill), float(gate))) != 0:
             raise ValueError("stm_stream_input_depth(%r, %g, %g, %d, %g) refused: %s" % (format, lo, hi, fill, gate, lib().stm_last_error().decode()))
         self._depth_input = None if fmt < 0 else {0: np.dtype("<f4"), 2: np.dtype(np.uint8), 3: np.dtype("<u2")}[fmt]
+
+    def set_rectify(self, rec_l, rec_r=None, border=0):
+        """stm_stream_rectify: both eyes of every frame through their records (18 floats each, stm_amd.rectify.record) before anything
+        else is done with the frame; rec_l None = off.  Only before the first submit.  Raises ValueError where the library refuses."""
+        if rec_l is None:
+            if int(lib().stm_stream_rectify(self._h, 0, None, 0)) != 0:
+                raise ValueError("stm_stream_rectify(off) refused: %s" % lib().stm_last_error().decode())
+            return
+        from . import rectify as _rectify
+        rec = np.ascontiguousarray(np.stack([_rectify.check(rec_l, "left record"), _rectify.check(rec_r, "right record")]), dtype=np.float32)
+        if int(lib().stm_stream_rectify(self._h, 1, rec.ctypes.data_as(C.POINTER(C.c_float)), int(border))) != 0:
+            raise ValueError("stm_stream_rectify(border %d) refused: %s" % (border, lib().stm_last_error().decode()))
+
+    def get_rectify(self):
+        """stm_stream_get_rectify: None with the rectification off, else (rec_l, rec_r, border)."""
+        mode, border = C.c_int(0), C.c_int(0)
+        rec = np.zeros((2, 18), np.float32)
+        lib().stm_stream_get_rectify(self._h, C.byref(mode), rec.ctypes.data_as(C.POINTER(C.c_float)), C.byref(border))
+        return None if mode.value == 0 else (rec[0], rec[1], border.value)
 
     def depth_frame_bytes(self):
         """(the plane's byte offset in a depth frame, the frame's bytes): the image's bytes rounded up to a multiple of 16, and that
@@ -637,6 +662,23 @@ def take_depth_input_option(argv, stack=False):
     return planes, (DEPTH_INPUT_FORMATS[planes.dtype], lo, hi, fill, gate)
 
 
+def take_rectify_option(argv):
+    """The drivers' --rectify FILE.npy [BORDER] (BORDER 0 or 1, default 0), removed from argv.  The file is a (2, 18) float32 array:
+    the left eye's rectification record, then the right eye's (stm_amd.rectify.record).  Returns (rec_l, rec_r, border) or None;
+    raises ValueError or IndexError for a malformed option or file, before any frame is read."""
+    if "--rectify" not in argv:
+        return None
+    from . import rectify as _rectify
+    at = argv.index("--rectify")
+    path = argv[at + 1]
+    n, border = 2, 0
+    if at + 2 < len(argv) and argv[at + 2] in ("0", "1"):
+        n, border = 3, int(argv[at + 2])
+    rec_l, rec_r = _rectify.load_records(path)
+    del argv[at:at + n]
+    return rec_l, rec_r, border
+
+
 def take_maps_option(argv):
     """The driver's --maps FORMAT [WHICH LO HI [FILE]], removed from argv: FORMAT f32, none, u8 or u16; for u8 and u16 WHICH (left,
     right or both) and the map values LO and HI of code 0 and of the largest code, then optionally the FILE the raw planes are
@@ -680,7 +722,7 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
                      depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None,
                      overlay=None, antialias=None, align=None, align_auto=None, on_align=None, balance=None, balance_auto=None,
                      on_balance=None, cut=None, on_cut=None, overlay_auto=None, on_overlay_depth=None, active=None,
-                     active_auto=None, active_fill=None, on_active=None, maps=None, depth_input=None):
+                     active_auto=None, active_fill=None, on_active=None, maps=None, depth_input=None, rectify=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     depth_input: FrameStream's (format, lo, hi[, fill, gate]): `frames` then yields (image, plane) pairs, the image [H][W][3].
     maps: FrameStream's (format, which, lo, hi): disp_l and disp_r are then uint8 / uint16 depth planes, or None.
@@ -699,7 +741,7 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
     FrameStream's shot-change detector; on_cut: called with (index, (cut, score, since)) likewise.  overlay_auto: FrameStream's
     automatic placement of `overlay`, whose disparity is then ignored; on_overlay_depth: called with (index, state) likewise.
     active / active_auto / active_fill: FrameStream's active picture area; on_active: called with (index, (top, bottom, left, right,
-    changed)) likewise."""
+    changed)) likewise.  rectify: FrameStream's (rec_l, rec_r[, border]): every frame's eyes remapped through their records first."""
     fs = None
     pending = 0
     for sbs in frames:
@@ -712,7 +754,7 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
             fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output,
                              overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]), antialias=antialias,
                              align=align, align_auto=align_auto, balance=balance, balance_auto=balance_auto, cut=cut, overlay_auto=overlay_auto,
-                             active=active, active_auto=active_auto, active_fill=active_fill, maps=maps, depth_input=depth_input)
+                             active=active, active_auto=active_auto, active_fill=active_fill, maps=maps, depth_input=depth_input, rectify=rectify)
             if overlay is not None:
                 fs.overlay(*overlay)
             if temporal is not None:

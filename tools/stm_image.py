@@ -11,6 +11,7 @@ usage: stm_image.py <left.bmp> <right.bmp> <ad coeff> <census coeff> <ndisp> <ze
                     [--balance FILE.npy | --balance-auto [MAX_SHIFT RATE]]
                     [--active T B L R | --active-auto [THRESH LIT MAX_BAR HOLD]] [--active-fill DISP]
                     [--depth-input PLANE.npy LO HI [FILL GATE]]
+                    [--rectify FILE.npy [BORDER]]
 
 --interp (an addition, off by default): the outlier interpolation (host_api.dr_interp) of both maps after region voting, each on
 its own image and outlier map, before --subpixel.
@@ -45,7 +46,11 @@ holds [H][W] float32, uint8 or uint16 disparities x_right - x_left (the format f
 HI; float32: clamped to the two), <right.bmp> is not read ("-" will do) and the matching parameters are read and ignored.  The second
 eye is synthesised on the GPU (stm_stream_input_depth; FILL 0 = the background extended into the holes, 1 = continued from the mirror
 pixel within GATE) and the frame rendered by a one-frame stream, which has no per-stage products: disp_l (the decoded plane), disp_r
-(the synthesised map) and the output frame are written.  Excludes --interp, --subpixel, --align, --balance and their -auto forms."""
+(the synthesised map) and the output frame are written.  Excludes --interp, --subpixel, --align, --balance and their -auto forms.
+--rectify FILE.npy [BORDER] (an addition; put it behind the positional arguments): both images are first remapped on the GPU through
+their rectification records (host_api.rectify): FILE.npy is a (2, 18) float32 array, the left eye's record and then the right eye's
+(stm_amd.rectify.record).  BORDER 0 (the default): source positions outside an image read 0; 1: they are clamped.  Every stage then
+runs on the rectified pair.  A malformed file is refused before any image is read; excludes --depth-input."""
 import os
 import sys
 
@@ -153,6 +158,9 @@ def main(argv):
         if depth_input is not None and (subpixel or interp or align is not None or align_auto is not None or balance is not None
                                         or balance_auto is not None):
             raise ValueError("--depth-input")
+        rectify = video.take_rectify_option(argv)
+        if rectify is not None and depth_input is not None:
+            raise ValueError("--rectify")
     except (ValueError, IndexError):
         print(__doc__)
         return -1
@@ -168,6 +176,8 @@ def main(argv):
     if L.shape != R.shape:
         print("Error! left and right image sizes differ: %s vs %s" % (L.shape, R.shape))
         return -1
+    if rectify is not None:  # first of all: everything below runs on the rectified pair
+        L, R = api.rectify(L, rectify[0], rectify[2]), api.rectify(R, rectify[1], rectify[2])
     if align_auto is not None:
         st, nvalid = api.align_fit(L, R, align_auto[0])
         align = tuple(float(v) for v in st[1:])

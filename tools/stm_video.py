@@ -13,6 +13,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--cut [THRESH MIN_GAP]]
                     [--active T B L R | --active-auto [THRESH LIT MAX_BAR HOLD]] [--active-fill DISP]
                     [--maps FORMAT [WHICH LO HI [FILE]]] [--depth-input PLANES.npy LO HI [FILL GATE]]
+                    [--rectify FILE.npy [BORDER]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
 (sub-pixel enhancement) of every frame, set on the frame stream before its first frame.
@@ -88,6 +89,11 @@ dtype; stm_stream_input_depth): disparities x_right - x_left, code 0 at LO and t
 The second eye is synthesised on the GPU and nothing is matched; FILL 0 (the default) extends the background into the disoccluded
 holes, FILL 1 continues it from the mirror pixel where that lies within GATE of the background.  The matching parameters are read and
 ignored; excludes --nv12, --packing, --match, --align, --balance and the frame bits other than --linear-warp.
+--rectify FILE.npy [BORDER] (an addition; put it behind the positional arguments): both eyes of every frame are first remapped on the
+GPU through their rectification records (stm_stream_rectify): FILE.npy is a (2, 18) float32 array, the left eye's record and then the
+right eye's (stm_amd.rectify.record makes one from a camera matrix, distortion coefficients, the rectifying rotation and the new
+camera matrix).  BORDER 0 (the default): source positions outside an eye read 0; 1: they are clamped.  Everything else then runs on the
+rectified pair.  A malformed file is refused before any frame is read; excludes --depth-input.
 The angle is truncated to an integer as the reference does (adcensus_stm declares `int angle`, d_io.h:36, and video_io.cpp:158
 passes it a float); set STM_EXACT_ANGLE=1 to keep the fractional slant."""
 import os
@@ -300,6 +306,9 @@ def main(argv):
         if depth_input is not None and (nv12 is not None or packing is not None or match is not None or align is not None or align_auto is not None
                                         or balance is not None or balance_auto is not None or (stages & ~0x800) != 3):
             raise ValueError("--depth-input")
+        rectify = video.take_rectify_option(argv)
+        if rectify is not None and depth_input is not None:
+            raise ValueError("--rectify")
     except (ValueError, IndexError):
         print(__doc__)
         return -1
@@ -356,7 +365,7 @@ def main(argv):
                                                        on_active=(lambda k, r: print("frame %d: active rows %d..%d cols %d..%d changed %d" % ((k,) + r)))
                                                        if active_auto is not None else None,
                                                        maps=None if maps is None else maps[:4],
-                                                       depth_input=None if depth_input is None else depth_input[1]):
+                                                       depth_input=None if depth_input is None else depth_input[1], rectify=rectify):
         if yuv is not None:  # the frame is [out height * 3 / 2][out width]: the Y plane, then the interleaved UV plane
             yuv.write(inter.tobytes())
         else:
