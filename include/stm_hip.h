@@ -1587,7 +1587,9 @@ long  stm_stream_collect_maps_view(void *stream, const void **plane_l, const voi
  * screening tables of the test suite and stays what it is.
  * Rectification from camera calibration (both eyes remapped through a camera matrix, distortion coefficients and a rectifying
  * rotation, as a stage and as the first step of a stream's frames): its entry points are declared, with the definition line by
- * line, in stm_rectify.h, for the same reason. */
+ * line, in stm_rectify.h, for the same reason.
+ * Scanline optimisation of the right view as a stage, and the test tap on the scanline passes' path-cost sums: declared in
+ * stm_hslo_tap.h, for the same reason. */
 void  stm_stream_destroy(void *stream);
 
 /* ----------------------------------------------------------------- BMP I/O */

@@ -213,6 +213,23 @@ def dc_hslo(cost, img_l, img_r, T, H1, H2, zd, return_cost=False):
     return (disp, co) if return_cost else disp
 
 
+def dc_hslo_sums(cost, img_own, img_other, T, H1, H2, zd, osign=1):
+    """orc_dc_hslo_sums: scanline optimisation of one view -- osign +1 = the left view, -1 = the right view (img_own is then the
+    right image) -- with the running sums of its four directions.  Returns (disp [H][W], s2, s3, fin), the three float32 [D][H][W]:
+    C_lr + C_rl, that + C_tb, and the final volume (s3 + C_bt) * 0.25 the map is taken from."""
+    assert osign in (1, -1)
+    D, H, W = cost.shape
+    E = img_own.shape[2]
+    cost, pc = _f32(cost)
+    img_own, pa = _u8(img_own)
+    img_other, pb = _u8(img_other)
+    disp = np.empty((H, W), np.float32)
+    s2, s3, fin = (np.empty_like(cost) for _ in range(3))
+    lib().orc_dc_hslo_sums(pc, disp.ctypes.data_as(f32p), None, pa, pb, C.c_float(T), C.c_float(H1), C.c_float(H2), D, zd, H, W, E,
+                           osign, s2.ctypes.data_as(f32p), s3.ctypes.data_as(f32p), fin.ctypes.data_as(f32p))
+    return disp, s2, s3, fin
+
+
 def dr_dcc(disp_l, disp_r):
     H, W = disp_l.shape
     disp_l, pl = _f32(disp_l)

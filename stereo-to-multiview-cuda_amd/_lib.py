@@ -216,6 +216,11 @@ PROTOS_RECTIFY = {
     "stm_stream_rectify": ([C.c_void_p, i, f32p, i], i),
     "stm_stream_get_rectify": ([C.c_void_p, C.POINTER(C.c_int), f32p, C.POINTER(C.c_int)], i),
 }
+# include/stm_hslo_tap.h: the test tap on the scanline passes' sums and the right view as a stage, likewise
+PROTOS_HSLO = {
+    "stm_set_hslo_tap": ([vp, vp, vp], i),
+    "stm_d_dc_hslo_view": ([vp, vp, vp, vp, f, f, f, i, i, i, i, i, i], None),
+}
 
 _lib = None
 
@@ -233,7 +238,7 @@ def lib():
         # other order starts two runtimes and the second one finds "no ROCm-capable device".
         import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
-        for name, (args, res) in list(PROTOS.items()) + list(PROTOS_DEPTH.items()) + list(PROTOS_RECTIFY.items()):
+        for name, (args, res) in list(PROTOS.items()) + list(PROTOS_DEPTH.items()) + list(PROTOS_RECTIFY.items()) + list(PROTOS_HSLO.items()):
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = res

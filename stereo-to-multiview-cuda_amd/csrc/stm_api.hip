@@ -6,6 +6,7 @@
 #include <mutex>
 #include "../../include/stm_hip.h"
 #include "../../include/stm_rectify.h"
+#include "../../include/stm_hslo_tap.h"
 
 #include <map>
 #include <stdio.h>
@@ -542,19 +543,51 @@ void stm_dc_subpixel(float **cost, float *disp, int num_disp, int zero_disp, int
     sync();
 }
 
+// d_dc_hslo and d_dc_hslo_view (include/stm_hslo_tap.h) behind their screens: one view's volume, the view's own image and the other one,
+// osign = +1 (left view) / -1 (right view)
+static void d_dc_hslo_rect(float **d_cost, float *d_disp, unsigned char *d_img_own, unsigned char *d_img_other, float T, float H1,
+                           float H2, int num_disp, int zero_disp, int num_rows, int num_cols, int elem_sz, int osign)
+{
+    size_t HW = (size_t)num_rows * num_cols;
+    Workspace::begin((size_t)((num_disp + 3) / 4) * HW * 16 * 6 + 16 * HW + 16384);
+    Vol c = vol_table(d_cost);
+    const u8 *ia[1] = {d_img_own}, *ib[1] = {d_img_other};
+    const int os[1] = {osign};
+    float *dv[1] = {d_disp};
+    launch_hslo_wta(1, &c, ia, ib, os, dv, T, H1, H2, num_disp, zero_disp, num_rows, num_cols, elem_sz);
+}
 void stm_d_dc_hslo(float **d_cost, float *d_disp, unsigned char *d_img_l, unsigned char *d_img_r, float T, float H1,
                    float H2, int num_disp, int zero_disp, int num_rows, int num_cols, int elem_sz)
 {
     if (!args_ok("d_dc_hslo", {{"num_disp", num_disp, 1}, {"num_rows", num_rows, 1}, {"num_cols", num_cols, 1},
                                {"elem_sz", elem_sz, 3}}))
         return;
-    size_t HW = (size_t)num_rows * num_cols;
-    Workspace::begin((size_t)((num_disp + 3) / 4) * HW * 16 * 6 + 16 * HW + 16384);
-    Vol c = vol_table(d_cost);
-    const u8 *ia[1] = {d_img_l}, *ib[1] = {d_img_r};
-    const int os[1] = {1};
-    float *dv[1] = {d_disp};
-    launch_hslo_wta(1, &c, ia, ib, os, dv, T, H1, H2, num_disp, zero_disp, num_rows, num_cols, elem_sz);
+    d_dc_hslo_rect(d_cost, d_disp, d_img_l, d_img_r, T, H1, H2, num_disp, zero_disp, num_rows, num_cols, elem_sz, 1);
+}
+static bool hslo_view_ok(const char *fn, int view)
+{
+    if (view < 0 || view > 1) return STM_REJECT("view", "%s: view = %d, must be 0 (the left view) or 1 (the right view)", fn, view);
+    return true;
+}
+void stm_d_dc_hslo_view(float **d_cost, float *d_disp, unsigned char *d_img_own, unsigned char *d_img_other, float T, float H1,
+                        float H2, int num_disp, int zero_disp, int num_rows, int num_cols, int elem_sz, int view)
+{
+    if (!args_ok("d_dc_hslo_view", {{"num_disp", num_disp, 1}, {"num_rows", num_rows, 1}, {"num_cols", num_cols, 1},
+                                    {"elem_sz", elem_sz, 3}}) ||
+        !hslo_view_ok("d_dc_hslo_view", view))
+        return;
+    d_dc_hslo_rect(d_cost, d_disp, d_img_own, d_img_other, T, H1, H2, num_disp, zero_disp, num_rows, num_cols, elem_sz, view ? -1 : 1);
+}
+int stm_set_hslo_tap(float *d_s2, float *d_s3, float *d_fin)
+{
+    if (api_outermost()) clear_failed();
+    const void *p[3] = {d_s2, d_s3, d_fin};
+    const char *name[3] = {"d_s2", "d_s3", "d_fin"};
+    for (int i = 0; i < 3; ++i)
+        if (((uintptr_t)p[i] & 3) != 0) // the thread's tap stays as it was
+            return STM_REJECT(name[i], "set_hslo_tap: %s must be 4-byte aligned (a volume of floats)", name[i]) ? 0 : -1;
+    set_hslo_tap(HsloTap{d_s2, d_s3, d_fin});
+    return 0;
 }
 void stm_dc_hslo(float **cost, float *disp, unsigned char *img_l, unsigned char *img_r, float T, float H1, float H2,
                  int num_disp, int zero_disp, int num_rows, int num_cols, int elem_sz)

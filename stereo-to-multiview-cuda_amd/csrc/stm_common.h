@@ -665,6 +665,15 @@ void launch_from_pq(const float *pq, Vol out, int D, int H, int W); // stm_kerne
 // HSLO (stm_kernels_hslo.hip)
 void launch_hslo_wta(int nviews, const Vol *cost, const u8 *const *img_a, const u8 *const *img_b, const int *osign,
                      float *const *disp, float T, float H1, float H2, int D, int zd, int H, int W, int elem_sz);
+// The test tap on the scanline passes (stm_set_hslo_tap, include/stm_hslo_tap.h): the caller's float [views][D][H][W] buffers that
+// receive the accumulator after the horizontal passes (s2 = C_lr + C_rl), after the top-to-bottom pass (s3 = s2 + C_tb) and the final
+// volume (fin = (s3 + C_bt) * 0.25f), image columns only; views = the nviews of the run.  All null = off: not one launch is added.
+// One per host thread; a frame stream refuses stage bit 0x100, so its frames never run the tap.
+struct HsloTap {
+    float *s2, *s3, *fin;
+};
+HsloTap hslo_tap();
+void set_hslo_tap(const HsloTap &t);
 // the same on PQ volumes (the frame pipeline): cost_pq read only, acc_pq scratch of the same size
 void launch_hslo_wta_pq(int nviews, float *const *cost_pq, float *const *acc_pq, const u8 *const *img_a, const u8 *const *img_b,
                         const int *osign, float *const *disp, float T, float H1, float H2, int D, int zd, int H, int W, int elem_sz);

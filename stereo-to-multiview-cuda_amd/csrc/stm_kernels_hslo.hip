@@ -56,6 +56,7 @@ struct HsloArgs {
     int osign[2];      // +1 left view (matched pixel x + d - zd), -1 right view
     f4 *inf;           // 256 B of +inf: what the lanes of absent hypotheses (d >= D) read, and where their (+inf) results go
     float p1[9], p2[9]; // penalties by 3 class(D1) + class(D2)
+    float *fin;        // the test tap's final volume (stm_set_hslo_tap), float [views][D][H][W], or null: the tap is clear
 };
 
 // grid (cdiv(WP, 256), H, views)
@@ -124,6 +125,19 @@ template <bool QUAD> __global__ __launch_bounds__(256) void stm_k_to_pq(Vol in, 
     o[1] = f4{px[0].y, px[1].y, px[2].y, px[3].y};
     o[2] = f4{px[0].z, px[1].z, px[2].z, px[3].z};
     o[3] = f4{px[0].w, px[1].w, px[2].w, px[3].w};
+}
+
+// The test tap (stm_set_hslo_tap, include/stm_hslo_tap.h) on the accumulator: dst[view][d][y][x] = acc[view] at (d, y, x), d < D, x < W.
+// Test access only: one thread per element of dst, nothing tuned; launched only where the tap is set.
+__global__ __launch_bounds__(256) void stm_k_hslo_tap_copy(HsloArgs a, float *__restrict__ dst, int nviews, int D, int H, int W, int G)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, n = (size_t)D * H * W;
+    if (i >= (size_t)nviews * n) return;
+    const int view = i >= n;
+    const size_t e = i - (view ? n : 0);
+    const int x = (int)(e % W), y = (int)(e / W % H), d = (int)(e / W / H);
+    const float *acc = (const float *)(view ? a.acc[1] : a.acc[0]);
+    dst[i] = acc[((((size_t)(d >> 4) * H + y) * G + (x >> 2)) * 16 + (d & 15)) * 4 + (x & 3)];
 }
 
 // ------------------------------------------------------------------ the recurrence
@@ -553,7 +567,8 @@ __global__ __launch_bounds__(256) void stm_k_hslo_v(HsloArgs a, int D, int zd, i
     for (int k = 0; k < 4; ++k)
 #pragma unroll
         for (int j = 0; j < DPL; ++j) prev[k][j] = 0.f;
-    auto process = [&](const Row &r, int v) {
+    auto process = [&](const Row &r, int v, auto tap_) {
+        constexpr bool TAP = decltype(tap_)::value;
         const int y = BWD ? H - 1 - v : v;
         float cur[4][DPL];
         if (v == 0 || STM_DBG(dbg, 1)) { // first pixel of the four lines
@@ -623,23 +638,58 @@ __global__ __launch_bounds__(256) void stm_k_hslo_v(HsloArgs a, int D, int zd, i
                 const float best = lane == 0 ? cd[0] : (lane == 1 ? cd[1] : (lane == 2 ? cd[2] : cd[3]));
                 disp[(size_t)y * W + 4 * g + lane] = best - (float)zd;
             }
+            // the test tap (stm_set_hslo_tap): the volume this kernel otherwise never materialises.  TAP is the walk's compile-time
+            // choice (below): the production walk holds nothing of this
+            if constexpr (TAP) {
+                asm volatile("" ::: "memory"); // (keeps the scheduler from spreading the stores over the row: registers)
+#pragma unroll
+                for (int j = 0; j < DPL; ++j) {
+                    const int d = lane + 64 * j;
+                    if (d >= D) continue;
+                    float *f = a.fin + (((size_t)view * D + d) * H + y) * W + 4 * g;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (4 * g + k < W) f[k] = (r.s[j][k] + cur[k][j]) * 0.25f;
+                }
+                asm volatile("" ::: "memory");
+            }
         }
     };
 
-    Row buf[PF];
+    auto walk = [&](auto tap_) {
+        Row buf[PF];
 #pragma unroll
-    for (int i = 0; i < PF; ++i) load_row(buf[i], i);
-    for (int v0 = 0; v0 < H; v0 += PF) {
+        for (int i = 0; i < PF; ++i) load_row(buf[i], i);
+        for (int v0 = 0; v0 < H; v0 += PF) {
 #pragma unroll
-        for (int i = 0; i < PF; ++i) {
-            if (v0 + i < H) process(buf[i], v0 + i);
-            load_row(buf[i], v0 + PF + i);
+            for (int i = 0; i < PF; ++i) {
+                if (v0 + i < H) process(buf[i], v0 + i, tap_);
+                load_row(buf[i], v0 + PF + i);
+            }
         }
+    };
+    // The tap's pointer is tested once per wave, outside the row loop: a wave walks its rows alone on its SIMD, so any test inside
+    // a row is in the kernel's time.  Both walks are this one kernel and this one `process`; with the
+    // pointer null the wave runs the walk without the store, which is the kernel without a tap.
+    if constexpr (BWD) {
+        if (a.fin) walk(std::true_type());
+        else walk(std::false_type());
+    } else {
+        walk(std::false_type());
     }
 }
 
+// the tap's copy of the accumulator behind a pass; launches nothing where dst is null
+void hslo_tap_copy(const HsloArgs &a, float *dst, int nviews, int D, int H, int W, int G)
+{
+    if (!dst) return;
+    const size_t n = (size_t)nviews * D * H * W;
+    STM_LAUNCH(stm_k_hslo_tap_copy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream(), a, dst, nviews, D, H, W, G);
+    STM_CHECK_LAUNCH();
+}
+
 template <int DPL, int PF>
-void hslo_passes(const HsloArgs &a, int nviews, int D, int zd, int H, int W, int G, int WU, int WP, int PAD)
+void hslo_passes(const HsloArgs &a, const HsloTap &tap, int nviews, int D, int zd, int H, int W, int G, int WU, int WP, int PAD)
 {
     const int dbg = timing_knobs(); // timing build only (stm_common.h): 1 = no recurrence, 2 = no stores
     bool both = false;
@@ -663,11 +713,13 @@ void hslo_passes(const HsloArgs &a, int nviews, int D, int zd, int H, int W, int
             STM_CHECK_LAUNCH();
         }
     }
+    hslo_tap_copy(a, tap.s2, nviews, D, H, W, G);
     {
         ProfScope p("hslo_tb");
         STM_LAUNCH((stm_k_hslo_v<DPL, false, PF>), dim3(cdiv(G, 4), nviews), dim3(256), 0, stream(), a, D, zd, H, W, G, WU, WP, PAD, dbg);
         STM_CHECK_LAUNCH();
     }
+    hslo_tap_copy(a, tap.s3, nviews, D, H, W, G);
     {
         ProfScope p("hslo_bt");
         STM_LAUNCH((stm_k_hslo_v<DPL, true, PF>), dim3(cdiv(G, 4), nviews), dim3(256), 0, stream(), a, D, zd, H, W, G, WU, WP, PAD, dbg);
@@ -703,7 +755,9 @@ void launch_hslo_wta_pq(int nviews, float *const *cost_pq, float *const *acc_pq,
     const int G = (W + 3) / 4, WU = 4 * G;
     const int PAD = max(max(zd, D - 1 - zd), 0);
     const int WP = (4 * G + 2 * PAD + 8 + 3) & ~3;
+    const HsloTap tap = hslo_tap(); // the test tap (stm_set_hslo_tap): two copies behind the passes and the last kernel's own store
     HsloArgs a;
+    a.fin = tap.fin;
     a.inf = (f4 *)Workspace::get<float>(64);
     for (int v = 0; v < 2; ++v) {
         const int s = v < nviews ? v : 0;
@@ -729,9 +783,9 @@ void launch_hslo_wta_pq(int nviews, float *const *cost_pq, float *const *acc_pq,
         STM_LAUNCH(stm_k_hslo_classes, dim3(cdiv(WP, 256), H, nviews), dim3(256), 0, stream(), a, T, H, W, WU, WP, PAD, elem_sz);
         STM_CHECK_LAUNCH();
     }
-    if (D <= 64) hslo_passes<1, 8>(a, nviews, D, zd, H, W, G, WU, WP, PAD);
-    else if (D <= 128) hslo_passes<2, 4>(a, nviews, D, zd, H, W, G, WU, WP, PAD);
-    else hslo_passes<4, 2>(a, nviews, D, zd, H, W, G, WU, WP, PAD);
+    if (D <= 64) hslo_passes<1, 8>(a, tap, nviews, D, zd, H, W, G, WU, WP, PAD);
+    else if (D <= 128) hslo_passes<2, 4>(a, tap, nviews, D, zd, H, W, G, WU, WP, PAD);
+    else hslo_passes<4, 2>(a, tap, nviews, D, zd, H, W, G, WU, WP, PAD);
 }
 
 // The same for cost volumes in any other layout (the per-stage API, the vector-ALU aggregation path): converted to PQ

@@ -324,6 +324,10 @@ bool overlay_params_ok(const char *fn, const void *ov, bool check_ptr, int ov_ro
 static thread_local AggTap g_agg_tap = {nullptr, nullptr, nullptr, nullptr};
 AggTap agg_tap() { return g_agg_tap; }
 void set_agg_tap(const AggTap &t) { g_agg_tap = t; }
+// the calling thread's test tap on the scanline passes (stm_set_hslo_tap)
+static thread_local HsloTap g_hslo_tap = {nullptr, nullptr, nullptr};
+HsloTap hslo_tap() { return g_hslo_tap; }
+void set_hslo_tap(const HsloTap &t) { g_hslo_tap = t; }
 // the calling thread's automatic overlay placement (stm_set_overlay_auto)
 OverlayAuto overlay_auto_default() { return OverlayAuto{0, 20, 1.0f, 8, 0.0f, 0.0f, 1.0f, 0.1f, nullptr}; }
 static thread_local OverlayAuto g_overlay_auto = overlay_auto_default();

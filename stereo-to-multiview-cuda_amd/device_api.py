@@ -129,6 +129,33 @@ class agg_tap:
         return False
 
 
+def set_hslo_tap(s2=None, s3=None, fin=None):
+    """stm_set_hslo_tap (include/stm_hslo_tap.h): test access to the scanline passes of this thread's calls.  Each argument is None or
+    a contiguous float32 tensor [views][D][H][W] on the GPU -- views = 1 for the stage calls, 2 (left, right) for a frame call with
+    stage bit 0x100: s2 receives C_lr + C_rl, s3 that + C_tb, fin the final volume ((s3 + C_bt) * 0.25).  All None = off.  The caller
+    keeps the tensors alive while the tap is set (hslo_tap does both).  Raises ValueError where the library refuses."""
+    for t in (s2, s3, fin):
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4 and t.shape[0] in (1, 2))
+    if int(lib().stm_set_hslo_tap(*[_p(t) if t is not None else None for t in (s2, s3, fin)])) != 0:
+        raise ValueError("stm_set_hslo_tap refused: %s" % lib().stm_last_error().decode())
+
+
+class hslo_tap:
+    """`with hslo_tap(s2=..., s3=..., fin=...):` -- set_hslo_tap around a block of calls; the tap is always cleared on the way out,
+    and the tensors stay referenced until then."""
+
+    def __init__(self, s2=None, s3=None, fin=None):
+        self.bufs = (s2, s3, fin)
+
+    def __enter__(self):
+        set_hslo_tap(*self.bufs)
+        return self
+
+    def __exit__(self, *exc):
+        set_hslo_tap()
+        return False
+
+
 def set_lens(mode, pitch=0.0, slope=0.0, centre=0.0):
     """stm_set_lens: the calling thread's display geometry, which every rendering frame call interlaces through.  mode 0 = off (the
     reference's interlacer, the default), 1 = nearest view, 2 = two views blended, 3 = every sub-pixel rendered at its own
@@ -967,6 +994,20 @@ def d_dc_wta(cost_tab, disp, num_disp, zero_disp):
     H, W = disp.shape
     _use_current_stream()
     lib().stm_d_dc_wta(_p(cost_tab), _p(disp), num_disp, zero_disp, H, W)
+
+
+def d_dc_hslo_view(cost_tab, disp, img_own, img_other, T, H1, H2, num_disp, zero_disp, view=0):
+    """stm_d_dc_hslo_view: scanline optimisation + WTA of one view on the aggregated volume behind cost_tab; disp float32 [H][W]
+    receives the map.  view 0 = the left view (stm_d_dc_hslo), 1 = the right view; img_own is the view's own image, img_other the
+    other one, both uint8 [H][W][E] on the GPU."""
+    H, W, E = img_own.shape
+    assert img_other.shape == img_own.shape and tuple(disp.shape) == (H, W)
+    for t in (img_own, img_other):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+    assert disp.is_cuda and disp.dtype == torch.float32 and disp.is_contiguous()
+    _use_current_stream()
+    lib().stm_d_dc_hslo_view(_p(cost_tab), _p(disp), _p(img_own), _p(img_other), float(T), float(H1), float(H2), int(num_disp),
+                             int(zero_disp), H, W, E, int(view))
 
 
 def d_dc_subpixel(cost_tab, disp, num_disp, zero_disp):

@@ -9,6 +9,7 @@ CPU only: these run in the `-m "not gpu"` suite.
 import numpy as np
 import pytest
 
+import hslo_cases as hc
 from conftest import rand_pair
 
 
@@ -236,12 +237,14 @@ def test_wta_and_dcc_second_opinion(orc):
 
 
 # ------------------------------------------------------------------------------------------------ HSLO (a14)
-def _hslo_py(cost, img_l, img_r, T, H1, H2, zd):
+def _hslo_py(cost, img_l, img_r, T, H1, H2, zd, osign=1, sums=False):
     """Mei et al. section 3.3 as DESIGN.md section 2 fixes it: four scan directions; along direction r
     Cr(p,d) = C(p,d) + min(Cr(p-r,d), Cr(p-r,d+-1) + P1, min_k Cr(p-r,k) + P2) - min_k Cr(p-r,k); the first pixel of a line
     takes C(p,d); (P1, P2) from the colour steps D1 (own image, integer mean of B,G,R) and D2 (other image at the matched
     pixel x + (d - zd), clamped; float mean): both < T -> (H1, H2); exactly one strictly on each side -> / 4; else / 10.
-    Final cost = mean of the four directions; WTA with the first strictly-lowest rule.  float64 throughout."""
+    Final cost = mean of the four directions; WTA with the first strictly-lowest rule.  float64 throughout.
+    osign = -1: the right view -- img_l is then the view's own (right) image, img_r the other one, and the matched pixel is
+    x - (d - zd).  sums: return (C_lr + C_rl, that + C_tb, the final cost) instead of the final cost alone."""
     D, H, W = cost.shape
     c = cost.astype(np.float64)
     mean_l = (img_l.astype(np.int64).sum(axis=2) // 3).astype(np.float64)            # u8 integer average
@@ -249,6 +252,7 @@ def _hslo_py(cost, img_l, img_r, T, H1, H2, zd):
     # class depends on that rounding, so it is part of the stage's definition
     mean_r = (img_r.astype(np.int64).sum(axis=2).astype(np.float64) / 3.0).astype(np.float32)
     total = np.zeros_like(c)
+    partial = []
     for (dx, dy) in [(1, 0), (-1, 0), (0, 1), (0, -1)]:
         acc = np.zeros_like(c)
         lines = range(H) if dx else range(W)
@@ -268,7 +272,7 @@ def _hslo_py(cost, img_l, img_r, T, H1, H2, zd):
                     D1 = abs(mean_l[y, x] - mean_l[py, px])
                     cur = np.empty(D)
                     for d in range(D):
-                        o = d - zd
+                        o = osign * (d - zd)
                         qx, qpx = min(max(x + o, 0), W - 1), min(max(px + o, 0), W - 1)
                         D2 = float(np.abs(np.float32(mean_r[y, qx] - mean_r[py, qpx])))
                         if D1 < T and D2 < T:
@@ -287,8 +291,9 @@ def _hslo_py(cost, img_l, img_r, T, H1, H2, zd):
                 acc[:, y, x] = cur
                 prev = cur
         total += acc
+        partial.append(total.copy())
     total *= 0.25
-    return total
+    return (partial[1], partial[2], total) if sums else total
 
 
 def test_hslo_second_opinion(orc):
@@ -313,6 +318,56 @@ def test_hslo_second_opinion(orc):
     assert np.allclose(v_flat, _hslo_py(cl, flat, flat, 15.0, 1.0, 3.0, zd), rtol=1e-5, atol=1e-5)
     assert np.allclose(v_edge, _hslo_py(cl, edge, edge, 15.0, 1.0, 3.0, zd), rtol=1e-5, atol=1e-5)
     assert float(v_edge.mean()) < float(v_flat.mean())  # smaller penalties across the edge: cheaper paths on average
+
+
+def _rel(got, want):
+    return float(np.max(np.abs(got.astype(np.float64) - want) / np.maximum(np.abs(want), 1e-3)))
+
+
+@pytest.mark.parametrize("osign", [1, -1])
+@pytest.mark.parametrize("params", sorted(hc.PARAM_SETS))
+def test_hslo_running_sums_second_opinion(orc, params, osign):
+    """orc_dc_hslo_sums against the float64 restatement: the accumulator after the second direction (C_lr + C_rl), after the third
+    (+ C_tb) and the final volume, for the left view (osign +1) and the right view (-1), with every parameter set the GPU tests
+    run, on palette images (hslo_cases: the two means differ, steps fall below, on and above T) -- and, for T = float32(1/3), on
+    images of unit steps, where the class of D2 is decided by the float32 rounding of the other image's mean.  The bound is the
+    one test_hslo_second_opinion holds the final volume to."""
+    T, H1, H2 = hc.PARAM_SETS[params]
+    H, W, D, zd = 9, 33, 5, 2
+    image = hc.unit_step_image if params == "t_one_third" else hc.palette_image
+    own, other = image(H, W, 11), image(H, W, 12)
+    if T == 15.0:
+        hc.assert_all_class_pairs(own, other, D, zd, osign, T)
+    if params == "t_one_third":  # the input's point: D2 falls on both sides of T by rounding alone, D1 (0 or 1) on both sides too
+        n = hc.class_counts(own, other, D, zd, osign, T)
+        assert n[:, 0, 0].min() > 0 and n[:, 0, 1].min() > 0 and n[:, 1, 0].min() > 0 and n[:, 1, 1].min() > 0
+    cost = hc.cost_volume("uniform", D, H, W, 5)
+    disp, s2, s3, fin = orc.dc_hslo_sums(cost, own, other, T, H1, H2, zd, osign)
+    w2, w3, wfin = _hslo_py(cost, own, other, T, H1, H2, zd, osign=osign, sums=True)
+    assert _rel(s2, w2) < 1e-5 and _rel(s3, w3) < 1e-5 and _rel(fin, wfin) < 1e-5
+    # the entries that existed before give what they gave: the same final volume and map
+    if osign == 1:
+        d0, v0 = orc.dc_hslo(cost, own, other, T, H1, H2, zd, return_cost=True)
+        assert np.array_equal(d0, disp) and np.array_equal(v0, fin)
+    srt = np.sort(wfin, axis=0)
+    clear = (srt[1] - srt[0]) > 1e-4
+    assert np.array_equal(disp[clear], (np.argmin(wfin, axis=0) - zd).astype(np.float32)[clear])
+
+
+@pytest.mark.parametrize("zd", [0, 2, 6])
+def test_hslo_right_view_is_the_mirrored_left_view(orc, zd):
+    """The oracle's right view on (cost, own, other) equals, flipped back, its left view on the horizontally flipped inputs --
+    exactly: mirroring turns x - (d - zd) into x' + (d - zd) and swaps the two horizontal directions, whose sum is one float add
+    that commutes; the vertical directions and the order of the later adds are untouched."""
+    H, W, D = 6, 19, 7
+    own, other = hc.palette_image(H, W, 21), hc.palette_image(H, W, 22)
+    cost = hc.cost_volume("quarters", D, H, W, 9)
+    right = orc.dc_hslo_sums(cost, own, other, 15.0, 1.0, 3.0, zd, -1)
+    left = orc.dc_hslo_sums(cost[:, :, ::-1], own[:, ::-1], other[:, ::-1], 15.0, 1.0, 3.0, zd, 1)
+    for r, l in zip(right, left):
+        assert np.array_equal(r, l[..., ::-1])
+    # and the two views differ on the same inputs, so the identity is not vacuous
+    assert not np.array_equal(right[1], orc.dc_hslo_sums(cost, own, other, 15.0, 1.0, 3.0, zd, 1)[1])
 
 
 # ------------------------------------------------------------------------------------------------ forward warp (a23)
