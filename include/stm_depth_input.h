@@ -65,7 +65,9 @@ extern "C" {
  * than 0, or stages other than 3 / 3 | 0x800.  In the other direction stm_stream_set_input, _set_packing, _set_match_size,
  * _set_align, _set_balance, and _set_stages for anything but 3 / 3 | 0x800, refuse while depth input is on.  Returns 0.
  * There is no stage call and no frame entry for this input: the stream is its only door.  The entry is
- * declared here and not in stm_hip.h because that header's set of names is recorded in the test suite's screening tables. */
+ * declared here and not in stm_hip.h because that header's set of names is recorded in the test suite's screening tables.
+ * Where the image and its depth arrive as ONE video frame -- a 2D-plus-depth stream out of a decoder, BGR or NV12, side by side or top
+ * and bottom, full or squeezed -- stm_depth_video.h has the entry that reads that frame directly (stm_stream_input_packed_depth). */
 int   stm_stream_input_depth(void *stream, int format, float lo, float hi, int fill, float gate);
 
 #if defined(STM_BUILD) && defined(__GNUC__)

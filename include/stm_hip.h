@@ -1589,7 +1589,10 @@ long  stm_stream_collect_maps_view(void *stream, const void **plane_l, const voi
  * rotation, as a stage and as the first step of a stream's frames): its entry points are declared, with the definition line by
  * line, in stm_rectify.h, for the same reason.
  * Scanline optimisation of the right view as a stage, and the test tap on the scanline passes' path-cost sums: declared in
- * stm_hslo_tap.h, for the same reason. */
+ * stm_hslo_tap.h, for the same reason.
+ * Packed 2D-plus-depth video frames as a stream's input (the image and its depth picture in one BGR or NV12 frame, under
+ * stm_set_packing's settings): its one entry point is declared, with the definition line by line, in stm_depth_video.h, for the
+ * same reason. */
 void  stm_stream_destroy(void *stream);
 
 /* ----------------------------------------------------------------- BMP I/O */

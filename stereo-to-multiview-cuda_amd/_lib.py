@@ -221,6 +221,10 @@ PROTOS_HSLO = {
     "stm_set_hslo_tap": ([vp, vp, vp], i),
     "stm_d_dc_hslo_view": ([vp, vp, vp, vp, f, f, f, i, i, i, i, i, i], None),
 }
+# include/stm_depth_video.h: packed 2D-plus-depth video frames as a frame stream's input, likewise
+PROTOS_DEPTH_VIDEO = {
+    "stm_stream_input_packed_depth": ([C.c_void_p, i, i, i, i, i, i, i, i, i, f, f, i, f], i),
+}
 
 _lib = None
 
@@ -238,7 +242,7 @@ def lib():
         # other order starts two runtimes and the second one finds "no ROCm-capable device".
         import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
-        for name, (args, res) in list(PROTOS.items()) + list(PROTOS_DEPTH.items()) + list(PROTOS_RECTIFY.items()) + list(PROTOS_HSLO.items()):
+        for name, (args, res) in list(PROTOS.items()) + list(PROTOS_DEPTH.items()) + list(PROTOS_RECTIFY.items()) + list(PROTOS_HSLO.items()) + list(PROTOS_DEPTH_VIDEO.items()):
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = res

@@ -2573,6 +2573,41 @@ void stm::depth_frame_device(const u8 *d_img, const void *d_plane, const DepthIn
     frame_tail(a, img_l ? img_l : const_cast<u8 *>(d_img), img_r, d_disp_l, d_disp_r, d_interlaced, rect);
 }
 
+// The body of a frame stream's packed 2D-plus-depth video frame (stm_stream_input_packed_depth, include/stm_depth_video.h):
+// depth_frame_device with one packed BGR or NV12 frame in place of the image and the plane.  The cut and the active-area detector
+// read the image half as the left eye through the PackInput they take from any packed stereo frame (eye 0 under dv.pk), so the depth
+// half never reaches them; stm_k_eye_video unpacks and converts the image into the tight img_l, decodes the depth picture into
+// d_disp_l and synthesises img_r and d_disp_r; then the active fill and frame_tail as above.  The stream has screened dv and the
+// geometry (stm_stream_set_packing's rules) and keeps every setting that conditions a stereo pair off.  Not an extern "C" entry
+void stm::depth_video_frame_device(const u8 *d_frame, const DepthVideo &dv, float *d_disp_l, float *d_disp_r, u8 *d_interlaced, int num_rows,
+                                   int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz, int num_views,
+                                   float angle, int stages)
+{
+    const char *fn = "stream_input_packed_depth";
+    const FrameArgs a = {num_rows, num_cols_sbs, num_cols, num_rows_out, num_cols_out, elem_sz, num_views, angle, 1, 0, 0.0f, 0.0f, 0.0f, 0.0f,
+                         0, 0, 0, 0.0f, stages};
+    if (!frame_dims_ok(fn, a)) return;
+    if ((stages & ~0x800) != 3) return (void)STM_REJECT("stages", "%s: stages = 0x%x, must be 3 or 3 | 0x800 (nothing is matched)", fn, stages);
+    if (num_cols > 8192) return (void)STM_REJECT("num_cols", "%s: num_cols = %d, must be <= 8192 (a row's keys live in LDS)", fn, num_cols);
+    const bool nv12 = dv.format == 1;
+    if (!packing_args_ok(fn, dv.pk, num_rows, num_cols_sbs, num_cols, "num_cols", nv12, num_cols_sbs, num_cols_sbs, dv.matrix)) return;
+    if (!frame_layout_ok(fn, a) || !frame_cut_ok(fn, num_rows, num_cols) || !frame_active_ok(fn, num_rows, num_cols)) return;
+    const int H = num_rows, W = num_cols;
+    const size_t HW = (size_t)H * W, IMG = HW * elem_sz;
+    Workspace::begin((size_t)(num_views + 2) * IMG + 40 * HW + (1u << 20) + frame_settings_ws_bytes(a, false));
+    u8 *img_r = Workspace::get<u8>(IMG), *img_l = Workspace::get<u8>(IMG);
+    const u8 *uv = d_frame + (size_t)dv.pk.rows_f(H) * num_cols_sbs;
+    const PackInput pin = {dv.pk, nv12, nv12 ? nullptr : d_frame, num_cols_sbs, nv12 ? d_frame : nullptr, nv12 ? uv : nullptr,
+                           nv12 ? num_cols_sbs : 0, nv12 ? num_cols_sbs : 0, nv12 ? dv.matrix : 0};
+    const Cut ct = cut();
+    if (ct.mode) cut_frame_input(ct, pin, H, W, elem_sz, true, align(), balance()); // before any state's fit runs
+    const Active ac = active();
+    const int *rect = ac.mode ? active_frame_input(ac, ct, pin, H, W, elem_sz) : nullptr;
+    launch_depth_eye_video(pin, dv, img_l, img_r, d_disp_l, d_disp_r, H, W, elem_sz);
+    frame_active_fill(rect, d_disp_l, d_disp_r, H, W);
+    frame_tail(a, img_l, img_r, d_disp_l, d_disp_r, d_interlaced, rect);
+}
+
 extern "C" {
 
 // which aggregation kernels a frame call with these arguments runs (stm_hip.h); no launch, no device

@@ -365,6 +365,26 @@ void launch_depth_eye(const u8 *img, int pitch_px, const void *plane, int format
 void depth_frame_device(const u8 *d_img, const void *d_plane, const DepthInput &di, float *d_disp_l, float *d_disp_r, u8 *d_interlaced,
                         int num_rows, int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz, int num_views,
                         float angle, int stages);
+// The packed 2D-plus-depth video input of a frame stream (stm_stream_input_packed_depth, include/stm_depth_video.h): format -1 = off, 0 =
+// BGR, 1 = NV12 frame converted by `matrix`; pk: where the image (eye 0) and the depth picture (eye 1) lie; range, dfilter, dgate, lo,
+// hi: steps A' to A'''; fill and gate of step E
+struct DepthVideo {
+    int format, matrix;
+    Packing pk;
+    int range, dfilter, dgate;
+    float lo, hi;
+    int fill;
+    float gate;
+};
+// the second eye of such a frame (stm_kernels_eye.hip, stm_k_eye_video): `in` is the screened frame under dv.pk; the tight BGR image
+// img_l, the decoded map disp_l, the synthesised img_r and disp_r, all 16-byte aligned; W <= 8192
+void launch_depth_eye_video(const PackInput &in, const DepthVideo &dv, u8 *img_l, u8 *img_r, float *disp_l, float *disp_r, int H, int W,
+                            int elem_sz);
+// stm_api.hip: the body of a stream's packed 2D-plus-depth frame: depth_frame_device with the packed frame in place of the image and
+// the plane (NV12: the UV plane at byte rows_f * num_cols_sbs, both pitches num_cols_sbs).  No extern "C" entry calls it either
+void depth_video_frame_device(const u8 *d_frame, const DepthVideo &dv, float *d_disp_l, float *d_disp_r, u8 *d_interlaced, int num_rows,
+                              int num_cols_sbs, int num_cols, int num_rows_out, int num_cols_out, int elem_sz, int num_views, float angle,
+                              int stages);
 // frame pipeline: the N - 2 views are synthesised inside the interlacer, sample by sample (no view buffers)
 void launch_synth_mux(const u8 *img_l, const u8 *img_r, const float *disp_l, const float *disp_r, const float *mask_l, const float *mask_r,
                       const float *blend, u8 *out, int N, float y_interval, float inv_y_interval, int ymod, int Hin, int Win, int Hout,

@@ -1,6 +1,6 @@
 // stm_fetch.h -- a pixel of an unpacked eye read straight from a frame call's input: BGR or NV12, any packing, or two images of their
 // own.  Private to the kernels that run ahead of the front (stm_kernels_align.hip, stm_kernels_balance.hip, stm_kernels_cut.hip,
-// stm_kernels_active.hip).
+// stm_kernels_active.hip) and to the second eye of a packed 2D-plus-depth frame (stm_kernels_eye.hip, stm_k_eye_video).
 // Everything has internal linkage, so each file compiles its own copy.
 #pragma once
 #include "stm_common.h"

@@ -12,6 +12,7 @@
 #include "stm_common.h"
 #include "../../include/stm_hip.h"
 #include "../../include/stm_depth_input.h"
+#include "../../include/stm_depth_video.h"
 #include "../../include/stm_rectify.h"
 
 #include <stdio.h>
@@ -93,6 +94,8 @@ struct FrameStream {
     int planes = 0;                      // ... and how many a frame has (which 2: left, then right)
     stm::DepthInput din = {-1, 0.0f, 0.0f, 0, 0.0f}; // stm_stream_input_depth: a frame is an image and its depth plane (format -1 = off)
     size_t plane_off = 0;                // ... the plane's byte offset in a frame: the image's bytes rounded up to a multiple of 16
+    stm::DepthVideo dvid = {-1, 0, {0, 0, 0, 0}, 0, 0, 0, 0.0f, 0.0f, 0, 0.0f}; // stm_stream_input_packed_depth: a frame is one packed BGR or
+                                         // NV12 picture, the image in one half and its depth in the other (format -1 = off)
     stm::Rectify rectify = {0, {{0.0f}, {0.0f}}, 0}; // stm_stream_rectify: the stream's own rectification, installed around its frame calls
     Slot slot[2];
     long submitted = 0, collected = 0;
@@ -197,6 +200,13 @@ bool no_depth_input(const FrameStream *f, const char *fn, const char *arg)
     return f->din.format < 0 || STM_REJECT(arg, "%s: the stream has depth input (stm_stream_input_depth): a frame is an image and its depth plane, "
                                            "nothing is matched and there is no second image to condition; switch the depth input off first", fn);
 }
+// likewise with packed 2D-plus-depth video frames (stm_stream_input_packed_depth): the frame's format and packing are that call's own
+bool no_depth_video(const FrameStream *f, const char *fn, const char *arg)
+{
+    return f->dvid.format < 0 || STM_REJECT(arg, "%s: the stream has packed depth video input (stm_stream_input_packed_depth): a frame is an image and "
+                                            "its depth picture in one packed frame whose format and packing that call sets, and nothing is matched; "
+                                            "switch it off first", fn);
+}
 // stm_stream_collect / _view on a stream that downloads no float maps (stm_stream_maps, format != 0): a map pointer has nothing to
 // receive.  false with the error recorded; the caller consumes nothing
 bool float_maps_ok(const FrameStream *f, const char *fn, const void *disp_l, const void *disp_r)
@@ -289,6 +299,7 @@ int stm_stream_set_stages(void *h, int stages)
         return STM_REJECT("stages", "stream_set_stages: stages must be 3, optionally OR-ed with 0x200, 0x400, 0x800%s and 0x2000",
                           reduced ? ", 0x1000" : "") ? 0 : -1;
     if ((stages & ~0x800) != 3 && !no_depth_input(f, "stream_set_stages", "stages")) return -1; // 3 and 3 | 0x800 render only
+    if ((stages & ~0x800) != 3 && !no_depth_video(f, "stream_set_stages", "stages")) return -1;
     if (!not_submitted(f, "stream_set_stages", "stages")) return -1;
     f->stages = stages;
     return 0;
@@ -308,6 +319,7 @@ int stm_stream_set_match_size(void *h, int num_rows_disp, int num_cols_disp, flo
     if (!off && !(disp_scale > 0.0f && disp_scale <= 3.402823466e38f)) // (NaN fails the first comparison)
         return STM_REJECT("disp_scale", "stream_set_match_size: disp_scale must be finite and > 0") ? 0 : -1;
     if (!no_depth_input(f, "stream_set_match_size", "stream")) return -1;
+    if (!no_depth_video(f, "stream_set_match_size", "stream")) return -1;
     if (!not_submitted(f, "stream_set_match_size")) return -1;
     if (!off && f->packing.on())
         return STM_REJECT("packing", "stream_set_match_size: the stream has a packing (stm_stream_set_packing), which the reduced-resolution frame "
@@ -344,6 +356,7 @@ int stm_stream_set_input(void *h, int format, int matrix)
     stm::clear_failed();
     if (format != 0 && format != 1) return STM_REJECT("format", "stream_set_input: format must be 0 (side-by-side BGR) or 1 (NV12)") ? 0 : -1;
     if (!no_depth_input(f, "stream_set_input", "stream")) return -1;
+    if (!no_depth_video(f, "stream_set_input", "stream")) return -1;
     if (!not_submitted(f, "stream_set_input")) return -1;
     if (format == 1) {
         if (!stream_input_ok("stream_set_input", f, format, matrix, f->packing)) return -1;
@@ -372,6 +385,7 @@ int stm_stream_set_packing(void *h, int packing, int swap, int filter, int gap)
     const stm::Packing pk = {packing, swap, filter, gap};
     if (!stm::packing_params_ok("stream_set_packing", pk)) return -1;
     if (!no_depth_input(f, "stream_set_packing", "stream")) return -1;
+    if (!no_depth_video(f, "stream_set_packing", "stream")) return -1;
     if (!not_submitted(f, "stream_set_packing")) return -1;
     if (pk.on() && f->match_h > 0)
         return STM_REJECT("packing", "stream_set_packing: the stream has a match size (stm_stream_set_match_size): the reduced-resolution frame "
@@ -645,6 +659,7 @@ int stm_stream_set_align(void *h, int mode, float a, float b, float c)
     stm::clear_failed();
     if (!stm::align_params_ok("stream_set_align", mode, a, b, c)) return -1;
     if (!no_depth_input(f, "stream_set_align", "stream")) return -1; // ahead of the geometry rule: a depth frame has no second half
+    if (!no_depth_video(f, "stream_set_align", "stream")) return -1;
     if (mode != 0 && !f->packing.on() && f->in_format == 0 && f->Wsbs < 2 * f->W)
         return STM_REJECT("num_cols_sbs", "stream_set_align: an alignment needs num_cols_sbs >= 2 * num_cols") ? 0 : -1;
     if (mode == 2 && !stm::align_size_ok("stream_set_align", f->H, f->W)) return -1;
@@ -693,6 +708,7 @@ int stm_stream_set_balance(void *h, int mode, const unsigned char *lut768)
     stm::clear_failed();
     if (!stm::balance_params_ok("stream_set_balance", mode, lut768)) return -1;
     if (!no_depth_input(f, "stream_set_balance", "stream")) return -1; // ahead of the geometry rule, as in stm_stream_set_align
+    if (!no_depth_video(f, "stream_set_balance", "stream")) return -1;
     if (mode != 0 && !f->packing.on() && f->in_format == 0 && f->Wsbs < 2 * f->W)
         return STM_REJECT("num_cols_sbs", "stream_set_balance: a colour balance needs num_cols_sbs >= 2 * num_cols") ? 0 : -1;
     if (mode == 2 && !stm::balance_size_ok("stream_set_balance", f->H, f->W)) return -1;
@@ -934,6 +950,7 @@ int stm_stream_input_depth(void *h, int format, float lo, float hi, int fill, fl
     if (on && f->Wsbs < f->W)
         return STM_REJECT("num_cols_sbs", "%s: the stream's num_cols_sbs = %d, must be >= num_cols = %d", fn, f->Wsbs, f->W) ? 0 : -1;
     if (!not_submitted(f, fn)) return -1;
+    if (on && !no_depth_video(f, fn, "stream")) return -1;
     if (on && f->in_format != 0)
         return STM_REJECT("input", "%s: the stream's input format is 1 (NV12, stm_stream_set_input): the image of a depth frame is BGR", fn) ? 0 : -1;
     if (on && f->packing.on())
@@ -982,6 +999,104 @@ int stm_stream_input_depth(void *h, int format, float lo, float hi, int fill, fl
     return 0;
 }
 
+// The stream's frames are packed 2D-plus-depth video frames (stm_depth_video.h has the definition): one BGR (format 0) or NV12 (1,
+// converted by `matrix`) picture that holds the image as eye 0 and its depth picture as eye 1 of the packing (packing, swap, filter,
+// gap: stm_stream_set_packing's settings and geometry rules on the stream's num_rows, num_cols_sbs and num_cols); range, dfilter,
+// dgate, lo, hi decode the depth picture, fill and gate are stm_stream_input_depth's.  format -1 = off, the default.  A frame is then
+// rows_f * num_cols_sbs * elem_sz bytes (NV12: * 3 / 2), so each slot's pinned and device input buffers are allocated anew, the old
+// ones freed once all four new ones exist: pointers handed out by stm_stream_input_buffer before this call are void, and a failed
+// allocation leaves the stream as it was.  Every frame is then computed by stm::depth_video_frame_device (no matcher).  Not together
+// with stm_stream_input_depth, NV12 input or a packing of the stereo setters, a match size, an alignment, a balance, a rectification
+// or stages beyond 3 | 0x800, in either order.  Only before the first submit.  Returns 0, or -1 with the error recorded and the
+// stream unchanged.
+int stm_stream_input_packed_depth(void *h, int format, int matrix, int packing, int swap, int filter, int gap, int range, int dfilter,
+                                  int dgate, float lo, float hi, int fill, float gate)
+{
+    FrameStream *f = (FrameStream *)h;
+    stm::clear_failed();
+    const char *fn = "stream_input_packed_depth";
+    if (format != -1 && format != 0 && format != 1)
+        return STM_REJECT("format", "%s: format = %d, must be -1 (off), 0 (BGR frame) or 1 (NV12 frame)", fn, format) ? 0 : -1;
+    const bool on = format != -1;
+    const stm::Packing pk = {packing, swap, filter, gap};
+    if (on) {
+        if (!stm::packing_params_ok(fn, pk)) return -1;
+        if (range != 0 && range != 1)
+            return STM_REJECT("range", "%s: range = %d, must be 0 (codes 0 .. 255) or 1 (limited-range video grey, 16 .. 235)", fn, range) ? 0 : -1;
+        if (dfilter != 0 && dfilter != 1)
+            return STM_REJECT("dfilter", "%s: dfilter = %d, must be 0 (replicate the depth sample) or 1 (linear inside a surface)", fn, dfilter) ? 0 : -1;
+        if (dfilter != 0 && !(packing & 1))
+            return STM_REJECT("dfilter", "%s: dfilter = %d with packing %d: a full-size depth picture is not expanded, dfilter must be 0", fn,
+                              dfilter, packing) ? 0 : -1;
+        if (dgate < 0 || dgate > 255) return STM_REJECT("dgate", "%s: dgate = %d, must be in 0 .. 255", fn, dgate) ? 0 : -1;
+        if (!(fabsf(lo) <= 4096.0f && fabsf(hi) <= 4096.0f)) // (NaN fails the comparison, inf the bound)
+            return STM_REJECT("lo, hi", "%s: lo and hi must be finite and in [-4096, 4096]", fn) ? 0 : -1;
+        if (!(fabs((double)hi - (double)lo) >= 1.0 / 64.0)) return STM_REJECT("lo, hi", "%s: lo and hi must differ by at least 1/64", fn) ? 0 : -1;
+        if (fill != 0 && fill != 1)
+            return STM_REJECT("fill", "%s: fill = %d, must be 0 (constant extension) or 1 (continue the background)", fn, fill) ? 0 : -1;
+        if (fill == 1 && !(gate >= 0.0f && gate <= 4096.0f)) // (NaN fails the comparison)
+            return STM_REJECT("gate", "%s: gate must be finite and in [0, 4096]", fn) ? 0 : -1;
+        if (f->W > 8192)
+            return STM_REJECT("num_cols", "%s: the stream's num_cols = %d, must be <= 8192 (a row's keys live in LDS)", fn, f->W) ? 0 : -1;
+        if (format == 1 && (f->Wsbs & 1)) // the UV plane follows the Y plane with the same pitch
+            return STM_REJECT("num_cols_sbs", "%s: NV12 needs an even num_cols_sbs", fn) ? 0 : -1;
+        if (!stm::packing_args_ok(fn, pk, f->H, f->Wsbs, f->W, "num_cols", format == 1, f->Wsbs, f->Wsbs, matrix)) return -1;
+    }
+    if (!not_submitted(f, fn)) return -1;
+    if (on && f->din.format >= 0)
+        return STM_REJECT("stream", "%s: the stream has depth input (stm_stream_input_depth): its frames are an image and a separate plane; "
+                          "switch it off first", fn) ? 0 : -1;
+    if (on && f->in_format != 0)
+        return STM_REJECT("input", "%s: the stream's input format is 1 (NV12, stm_stream_set_input): the frame's format is this call's own "
+                          "argument, set the stream's back to 0", fn) ? 0 : -1;
+    if (on && f->packing.on())
+        return STM_REJECT("packing", "%s: the stream has a packing (stm_stream_set_packing): the frame's packing is this call's own argument, "
+                          "switch the stream's off", fn) ? 0 : -1;
+    if (on && f->match_h > 0)
+        return STM_REJECT("match_size", "%s: the stream has a match size (stm_stream_set_match_size): nothing is matched", fn) ? 0 : -1;
+    if (on && f->align.mode != 0)
+        return STM_REJECT("align", "%s: the stream has an alignment (stm_stream_set_align): there is no second image to align", fn) ? 0 : -1;
+    if (on && f->balance.mode != 0)
+        return STM_REJECT("balance", "%s: the stream has a colour balance (stm_stream_set_balance): there is no second image to balance", fn) ? 0 : -1;
+    if (on && f->rectify.mode != 0)
+        return STM_REJECT("rectify", "%s: the stream has a rectification (stm_stream_rectify): a 2D-plus-depth frame is not rectified", fn) ? 0 : -1;
+    if (on && (f->stages & ~0x800) != 3)
+        return STM_REJECT("stages", "%s: the stream's stages are 0x%x (stm_stream_set_stages): a 2D-plus-depth frame takes 3 or 3 | 0x800, nothing "
+                          "is matched", fn, f->stages) ? 0 : -1;
+    if (!on && f->dvid.format < 0) return 0; // off stays off: not one byte of the stream changes
+    // (neither stereo setter is in force, so in_sz is the plain side-by-side frame the stream goes back to)
+    const size_t frame_px = (size_t)pk.rows_f(f->H) * f->Wsbs;
+    const size_t need = !on ? f->in_sz : format == 1 ? frame_px * 3 / 2 : frame_px * f->E;
+    int caller_dev = f->dev;
+    STM_CHECK(hipGetDevice(&caller_dev));
+    if (caller_dev != f->dev) STM_CHECK(hipSetDevice(f->dev));
+    u8 *h_new[2] = {nullptr, nullptr}, *d_new[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i) {
+        STM_CHECK(hipHostMalloc((void **)&h_new[i], need, hipHostMallocDefault));
+        STM_CHECK(hipMalloc((void **)&d_new[i], need));
+    }
+    if (stm::failed()) { // (error mode 1; the hip calls take null pointers)
+        for (int i = 0; i < 2; ++i) {
+            if (h_new[i]) (void)hipHostFree(h_new[i]);
+            if (d_new[i]) (void)hipFree(d_new[i]);
+        }
+        if (caller_dev != f->dev) (void)hipSetDevice(caller_dev);
+        return -1;
+    }
+    for (int i = 0; i < 2; ++i) {
+        Slot &s = f->slot[i];
+        STM_CHECK(hipHostFree(s.h_in));
+        STM_CHECK(hipFree(s.d_in));
+        s.h_in = h_new[i];
+        s.d_in = d_new[i];
+    }
+    if (caller_dev != f->dev) STM_CHECK(hipSetDevice(caller_dev));
+    f->dvid = on ? stm::DepthVideo{format, format == 1 ? matrix : 0, pk, range, dfilter, dgate, lo, hi, fill, fill == 1 ? gate : 0.0f}
+                 : stm::DepthVideo{-1, 0, {0, 0, 0, 0}, 0, 0, 0, 0.0f, 0.0f, 0, 0.0f};
+    f->in_bytes = need;
+    return 0;
+}
+
 // The rectification every frame of the stream starts with (stm_rectify.h has the definition): mode 0 = off (the default), 1 = the
 // left eye's record, then the right eye's, copied into the stream and installed around its frame calls like the alignment; the
 // kernel takes them by value, so nothing is allocated.  Not together with depth input, in either order.  Only before the first
@@ -997,6 +1112,7 @@ int stm_stream_rectify(void *h, int mode, const float *rec36, int border)
         if (!stm::rectify_params_ok(fn, rec36, border) || !stm::rectify_params_ok(fn, rec36 + 18, border)) return -1;
     }
     if (mode != 0 && !no_depth_input(f, fn, "stream")) return -1; // ahead of the geometry rule, as in stm_stream_set_align
+    if (mode != 0 && !no_depth_video(f, fn, "stream")) return -1;
     if (mode != 0 && !f->packing.on() && f->in_format == 0 && f->Wsbs < 2 * f->W)
         return STM_REJECT("num_cols_sbs", "%s: a rectification needs num_cols_sbs >= 2 * num_cols", fn) ? 0 : -1;
     if (!not_submitted(f, fn)) return -1;
@@ -1082,6 +1198,11 @@ long stm_stream_submit(void *h, const unsigned char *img_sbs)
     stm::ws_private_bind(s.ws);
     auto frame = [&]() {
         stm::ApiNest nest; // a failed upload above must survive the nested call's argument screen
+        if (f->dvid.format >= 0) { // one packed frame, the image in one half and its depth picture in the other: likewise, from that frame
+            stm::depth_video_frame_device(s.d_in, f->dvid, s.d_dl, s.d_dr, s.d_out, f->H, f->Wsbs, f->W, f->Hout, f->Wout, f->E, f->N, f->angle,
+                                          f->stages);
+            return;
+        }
         if (f->din.format >= 0) { // an image and its depth plane: the second eye, then the stereo frame's own tail (no matcher)
             stm::depth_frame_device(s.d_in, s.d_in + f->plane_off, f->din, s.d_dl, s.d_dr, s.d_out, f->H, f->Wsbs, f->W, f->Hout, f->Wout, f->E,
                                     f->N, f->angle, f->stages);

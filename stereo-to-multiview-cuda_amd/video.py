@@ -68,12 +68,21 @@ class FrameStream:
     rectify = (rec_l, rec_r[, border]): every frame's eyes are first remapped through their rectification records (set_rectify;
     stm_amd.rectify.record makes one from a camera calibration), ahead of every other setting: the stream is then, by definition,
     the stream without it on the rectified pairs.  border 0 (the default) = taps outside an eye are 0, 1 = clamped.  Not together
-    with depth_input."""
+    with depth_input.
+    depth_video = (format, matrix, packing, swap, filter, gap, range, dfilter, dgate, lo, hi[, fill, gate]): the frames are packed
+    2D-plus-depth video frames (set_depth_video; include/stm_depth_video.h) -- format "bgr" or "nv12" with its conversion matrix; the
+    image is eye 0 and its depth, a grey picture, eye 1 of the packing (the settings of `packing`; filter expands the image); range 0
+    = codes 0 .. 255, 1 = limited-range video grey; dfilter 1 expands a squeezed depth picture linearly where neighbours lie within
+    dgate codes, 0 replicates; lo and hi are the map values of the lowest and the highest code; fill and gate as depth_input's.
+    submit() takes the packed frame as it is, `in_shape` as under packing= ([rows_f][Wsbs][3], NV12 [rows_f * 3 / 2][Wsbs]; depth_pitch
+    = a row length larger than the packing needs).  Not together with depth_input, input_format "nv12", packing, match, an alignment, a
+    balance, rectify or stages beyond 3 | 0x800."""
 
     def __init__(self, num_rows, num_cols, params, out_rows=None, out_cols=None, stages=3, input_format="bgr", matrix=0, lens=None,
                  depth=None, depth_auto=None, packing=None, layout=None, match=None, output=None, overlay=None,
                  antialias=None, align=None, align_auto=None, balance=None, balance_auto=None, cut=None, overlay_auto=None,
-                 active=None, active_auto=None, active_fill=None, maps=None, depth_input=None, depth_pitch=None, rectify=None):
+                 active=None, active_auto=None, active_fill=None, maps=None, depth_input=None, depth_pitch=None, rectify=None,
+                 depth_video=None):
         self.H, self.W = num_rows, num_cols
         self._maps = (0, 2)
         self._depth_input = None
@@ -81,6 +90,10 @@ class FrameStream:
         self.Wsbs, self.rows_f = packed_frame_geometry(num_rows, num_cols, self.packing)
         if depth_input is not None and packing is None:  # one image a frame: its rows are num_cols pixels unless the caller says otherwise
             self.Wsbs = int(depth_pitch) if depth_pitch is not None else num_cols
+        if depth_video is not None and packing is None and depth_input is None:  # one packed frame: the geometry of its own packing
+            self.Wsbs = packed_frame_geometry(num_rows, num_cols, tuple(depth_video[2:6]))[0]
+            if depth_pitch is not None:
+                self.Wsbs = int(depth_pitch)
         self._nv12 = False
         self.in_shape = (self.rows_f, self.Wsbs, 3)
         self.Ho, self.Wo = out_rows or num_rows, out_cols or num_cols
@@ -99,6 +112,8 @@ class FrameStream:
             self.set_input(input_format, matrix)
         if depth_input is not None:
             self.set_depth_input(*depth_input)
+        if depth_video is not None:
+            self.set_depth_video(*depth_video)
         if rectify is not None:
             self.set_rectify(*rectify)
         if lens is not None:
@@ -158,6 +173,23 @@ class FrameStream:
         if int(lib().stm_stream_input_depth(self._h, fmt, float(lo), float(hi), int(fill), float(gate))) != 0:
             raise ValueError("stm_stream_input_depth(%r, %g, %g, %d, %g) refused: %s" % (format, lo, hi, fill, gate, lib().stm_last_error().decode()))
         self._depth_input = None if fmt < 0 else {0: np.dtype("<f4"), 2: np.dtype(np.uint8), 3: np.dtype("<u2")}[fmt]
+
+    def set_depth_video(self, format, matrix=0, packing=0, swap=0, filter=0, gap=0, range=0, dfilter=0, dgate=0, lo=0.0, hi=0.0, fill=0,
+                        gate=0.0):
+        """stm_stream_input_packed_depth: the frames are packed 2D-plus-depth video frames -- format "bgr" or "nv12" (or 0, 1), None or
+        "off" (or -1) = side-by-side frames again; the other arguments as FrameStream's depth_video.  `in_shape` follows the packing;
+        buffers handed out by input_buffer() before this call are void.  Only before the first submit.  Raises ValueError where the
+        library refuses."""
+        fmt = {"bgr": 0, "nv12": 1, "off": -1, None: -1}.get(format, format)
+        if not isinstance(fmt, int):
+            raise ValueError("FrameStream.set_depth_video: format %r" % (format,))
+        args = (fmt, int(matrix), int(packing), int(swap), int(filter), int(gap), int(range), int(dfilter), int(dgate), float(lo), float(hi),
+                int(fill), float(gate))
+        if int(lib().stm_stream_input_packed_depth(self._h, *args)) != 0:
+            raise ValueError("stm_stream_input_packed_depth%r refused: %s" % (args, lib().stm_last_error().decode()))
+        self.rows_f = self.H if fmt < 0 else packed_frame_geometry(self.H, self.W, args[2:6])[1]
+        self._nv12 = fmt == 1
+        self.in_shape = (self.rows_f * 3 // 2, self.Wsbs) if fmt == 1 else (self.rows_f, self.Wsbs, 3)
 
     def set_rectify(self, rec_l, rec_r=None, border=0):
         """stm_stream_rectify: both eyes of every frame through their records (18 floats each, stm_amd.rectify.record) before anything
@@ -662,6 +694,34 @@ def take_depth_input_option(argv, stack=False):
     return planes, (DEPTH_INPUT_FORMATS[planes.dtype], lo, hi, fill, gate)
 
 
+def take_depth_video_option(argv):
+    """The drivers' --depth-video RANGE DFILTER DGATE LO HI [FILL GATE] (both of FILL and GATE or neither: 0 and 0), removed from argv:
+    the frames are packed 2D-plus-depth video frames whose layout the drivers' --nv12, --matrix and --packing options give.  Returns
+    (range, dfilter, dgate, lo, hi, fill, gate) or None; raises ValueError or IndexError for a malformed option or a value
+    stm_stream_input_packed_depth would refuse of these seven."""
+    if "--depth-video" not in argv:
+        return None
+    at = argv.index("--depth-video")
+    rng, dfilter, dgate = (int(v) for v in argv[at + 1:at + 4])
+    lo, hi = float(argv[at + 4]), float(argv[at + 5])
+    vals = []
+    for tok in argv[at + 6:at + 8]:
+        try:
+            float(tok)
+        except ValueError:
+            break
+        vals.append(tok)
+    if len(vals) == 1:
+        raise ValueError("--depth-video takes FILL and GATE, or neither")
+    fill, gate = (int(vals[0]), float(vals[1])) if vals else (0, 0.0)
+    if rng not in (0, 1) or dfilter not in (0, 1) or not 0 <= dgate <= 255 or fill not in (0, 1) or not 0.0 <= gate <= 4096.0:
+        raise ValueError((rng, dfilter, dgate, fill, gate))
+    if not (abs(lo) <= 4096.0 and abs(hi) <= 4096.0 and abs(hi - lo) >= 1.0 / 64.0):  # a NaN fails
+        raise ValueError((lo, hi))
+    del argv[at:at + 6 + len(vals)]
+    return rng, dfilter, dgate, lo, hi, fill, gate
+
+
 def take_rectify_option(argv):
     """The drivers' --rectify FILE.npy [BORDER] (BORDER 0 or 1, default 0), removed from argv.  The file is a (2, 18) float32 array:
     the left eye's rectification record, then the right eye's (stm_amd.rectify.record).  Returns (rec_l, rec_r, border) or None;
@@ -722,9 +782,11 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
                      depth=None, depth_auto=None, on_depth=None, packing=None, eye_shape=None, layout=None, match=None, output=None,
                      overlay=None, antialias=None, align=None, align_auto=None, on_align=None, balance=None, balance_auto=None,
                      on_balance=None, cut=None, on_cut=None, overlay_auto=None, on_overlay_depth=None, active=None,
-                     active_auto=None, active_fill=None, on_active=None, maps=None, depth_input=None, rectify=None):
+                     active_auto=None, active_fill=None, on_active=None, maps=None, depth_input=None, rectify=None, depth_video=None):
     """Generator: yields (index, disp_l, disp_r, interlaced) for every side-by-side frame of `frames`.
     depth_input: FrameStream's (format, lo, hi[, fill, gate]): `frames` then yields (image, plane) pairs, the image [H][W][3].
+    depth_video: FrameStream's (format, matrix, packing, swap, filter, gap, range, dfilter, dgate, lo, hi[, fill, gate]): `frames` then
+    yields packed 2D-plus-depth frames, BGR or NV12 by its format; eye_shape as under `packing`.
     maps: FrameStream's (format, which, lo, hi): disp_l and disp_r are then uint8 / uint16 depth planes, or None.
     input_format / matrix: FrameStream's ("nv12": the frames are [H * 3 / 2][2W] arrays, read_nv12_sequence's).
     stages: FrameStream.set_stages (3 | 0x200 sub-pixel | 0x400 outlier interpolation | 0x800 linear sampling | 0x2000 temporal
@@ -747,14 +809,20 @@ def process_sequence(frames, params, out_rows=None, out_cols=None, stages=3, tem
     for sbs in frames:
         if fs is None:
             first = sbs[0] if depth_input is not None else sbs
-            rows = first.shape[0] * 2 // 3 if input_format == "nv12" else first.shape[0]
+            nv12 = input_format == "nv12" or (depth_video is not None and depth_video[0] in ("nv12", 1))
+            rows = first.shape[0] * 2 // 3 if nv12 else first.shape[0]
             cols = first.shape[1] if depth_input is not None else first.shape[1] // 2
+            pitch = None
             if packing is not None:
                 rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], packing)
+            elif depth_video is not None:
+                rows, cols = eye_shape if eye_shape is not None else unpacked_eye_shape(rows, sbs.shape[1], tuple(depth_video[2:6]))
+                pitch = sbs.shape[1]
             fs = FrameStream(rows, cols, params, out_rows, out_cols, stages, input_format, matrix, lens, depth, depth_auto, packing, layout, match, output,
                              overlay=None if overlay is None else tuple(np.asarray(overlay[0]).shape[:2]), antialias=antialias,
                              align=align, align_auto=align_auto, balance=balance, balance_auto=balance_auto, cut=cut, overlay_auto=overlay_auto,
-                             active=active, active_auto=active_auto, active_fill=active_fill, maps=maps, depth_input=depth_input, rectify=rectify)
+                             active=active, active_auto=active_auto, active_fill=active_fill, maps=maps, depth_input=depth_input, rectify=rectify,
+                             depth_video=depth_video, depth_pitch=pitch)
             if overlay is not None:
                 fs.overlay(*overlay)
             if temporal is not None:

@@ -12,6 +12,7 @@ usage: stm_image.py <left.bmp> <right.bmp> <ad coeff> <census coeff> <ndisp> <ze
                     [--active T B L R | --active-auto [THRESH LIT MAX_BAR HOLD]] [--active-fill DISP]
                     [--depth-input PLANE.npy LO HI [FILL GATE]]
                     [--rectify FILE.npy [BORDER]]
+                    [--depth-video RANGE DFILTER DGATE LO HI [FILL GATE] [--packing P SWAP FILTER GAP]]
 
 --interp (an addition, off by default): the outlier interpolation (host_api.dr_interp) of both maps after region voting, each on
 its own image and outlier map, before --subpixel.
@@ -50,7 +51,13 @@ pixel within GATE) and the frame rendered by a one-frame stream, which has no pe
 --rectify FILE.npy [BORDER] (an addition; put it behind the positional arguments): both images are first remapped on the GPU through
 their rectification records (host_api.rectify): FILE.npy is a (2, 18) float32 array, the left eye's record and then the right eye's
 (stm_amd.rectify.record).  BORDER 0 (the default): source positions outside an image read 0; 1: they are clamped.  Every stage then
-runs on the rectified pair.  A malformed file is refused before any image is read; excludes --depth-input."""
+runs on the rectified pair.  A malformed file is refused before any image is read; excludes --depth-input.
+--depth-video RANGE DFILTER DGATE LO HI [FILL GATE] (an addition): <left.bmp> is one packed 2D-plus-depth frame, the image in one half
+and its depth as a grey picture in the other (stm_stream_input_packed_depth); --packing P SWAP FILTER GAP (stm_set_packing's
+settings; only with this option; without it: side by side, full size) says where the halves lie.  RANGE 0 = grey 0 .. 255, 1 = 16 ..
+235; LO and HI are the disparities of the darkest and the brightest grey; DFILTER 1 expands a squeezed depth picture linearly between
+neighbours at most DGATE codes apart.  <right.bmp> is not read and one frame goes through a stream, as with --depth-input, which it
+excludes together with what that option excludes and --rectify."""
 import os
 import sys
 
@@ -60,33 +67,42 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def depth_input_frame(a, depth_input, linear_warp, lens, quilt, antialias, active, active_auto, active_fill):
-    """--depth-input: the left image and its plane through a one-frame stream"""
+def depth_input_frame(a, depth_input, linear_warp, lens, quilt, antialias, active, active_auto, active_fill, depth_video=None):
+    """--depth-input: the left image and its plane through a one-frame stream; --depth-video: the packed frame likewise"""
     import stm_amd
     from stm_amd import device_api as dev, video
     L = stm_amd.bmp_io.read_bmp(a[0])
-    plane, setting = depth_input
-    if plane.shape != L.shape[:2]:
+    if depth_video is not None:
+        plane, setting = None, None
+        H, W = video.unpacked_eye_shape(L.shape[0], L.shape[1], depth_video[2:6])
+    else:
+        plane, setting = depth_input
+        H, W = L.shape[:2]
+    if plane is not None and plane.shape != L.shape[:2]:
         print("Error! the image is %d x %d, the depth plane %s" % (L.shape[0], L.shape[1], plane.shape))
         return -1
     N, angle, Wo, Ho = int(a[10]), float(a[11]), int(a[12]), int(a[13])
     out = a[16] if len(a) > 16 else "stm_out"
     os.makedirs(out, exist_ok=True)
     try:
-        fs = video.FrameStream(L.shape[0], L.shape[1], dev.FrameParams(num_views=N, angle=angle), Ho, Wo, 3 | (0x800 if linear_warp else 0),
+        fs = video.FrameStream(H, W, dev.FrameParams(num_views=N, angle=angle), Ho, Wo, 3 | (0x800 if linear_warp else 0),
                                lens=lens, layout=None if quilt is None else (1,) + quilt, antialias=antialias, active=active,
-                               active_auto=active_auto, active_fill=active_fill, depth_input=setting)
+                               active_auto=active_auto, active_fill=active_fill, depth_input=setting, depth_video=depth_video,
+                               depth_pitch=None if depth_video is None else L.shape[1])
     except ValueError as e:
         print("Error! %s" % e)
         return -1
     try:
-        fs.submit_depth(L, plane)
+        if depth_video is not None:
+            fs.submit(L)
+        else:
+            fs.submit_depth(L, plane)
         _, dl, dr, frame = fs.collect()
     finally:
         fs.close()
     for name, img in (("disp_l", video.normalize_minmax_u8(dl)), ("disp_r", video.normalize_minmax_u8(dr)), ("interlaced", frame)):
         stm_amd.bmp_io.write_bmp(os.path.join(out, name + ".bmp"), img)
-    print("wrote 3 files to %s (%dx%d, %d views, depth input %s)" % (out, L.shape[1], L.shape[0], N, setting[0]))
+    print("wrote 3 files to %s (%dx%d, %d views, depth input %s)" % (out, W, H, N, "packed video" if setting is None else setting[0]))
     return 0
 
 
@@ -161,6 +177,22 @@ def main(argv):
         rectify = video.take_rectify_option(argv)
         if rectify is not None and depth_input is not None:
             raise ValueError("--rectify")
+        depth_video = video.take_depth_video_option(argv)
+        packing = None
+        if "--packing" in argv:
+            at = argv.index("--packing")
+            packing = tuple(int(x) for x in argv[at + 1:at + 5])
+            if len(packing) != 4 or depth_video is None:
+                raise ValueError("--packing")
+            del argv[at:at + 5]
+        if depth_video is not None:
+            if (depth_input is not None or rectify is not None or subpixel or interp or align is not None or align_auto is not None
+                    or balance is not None or balance_auto is not None):
+                raise ValueError("--depth-video")
+            pk = packing if packing is not None else (0, 0, 0, 0)
+            if depth_video[1] and not pk[0] & 1:  # a full-size depth picture is not expanded
+                raise ValueError("--depth-video DFILTER")
+            depth_video = ("bgr", 0) + pk + depth_video
     except (ValueError, IndexError):
         print(__doc__)
         return -1
@@ -170,8 +202,8 @@ def main(argv):
     import stm_amd
     from stm_amd import host_api as api, video
     a = argv[1:]
-    if depth_input is not None:
-        return depth_input_frame(a, depth_input, linear_warp, lens, quilt, antialias, active, active_auto, active_fill)
+    if depth_input is not None or depth_video is not None:
+        return depth_input_frame(a, depth_input, linear_warp, lens, quilt, antialias, active, active_auto, active_fill, depth_video)
     L, R = stm_amd.bmp_io.read_bmp(a[0]), stm_amd.bmp_io.read_bmp(a[1])
     if L.shape != R.shape:
         print("Error! left and right image sizes differ: %s vs %s" % (L.shape, R.shape))

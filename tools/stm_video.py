@@ -13,6 +13,7 @@ usage: stm_video.py <frames dir> <num views> <angle> <out width> <out height> <n
                     [--cut [THRESH MIN_GAP]]
                     [--active T B L R | --active-auto [THRESH LIT MAX_BAR HOLD]] [--active-fill DISP]
                     [--maps FORMAT [WHICH LO HI [FILE]]] [--depth-input PLANES.npy LO HI [FILL GATE]]
+                    [--depth-video RANGE DFILTER DGATE LO HI [FILL GATE]]
                     [--rectify FILE.npy [BORDER]]
 (the 15 arguments of video_io.cpp:49-109; frames are *.bmp, sorted by name)
 --interp / --subpixel (additions, off by default): frame bits 0x400 (outlier interpolation after region voting) and 0x200
@@ -89,6 +90,15 @@ dtype; stm_stream_input_depth): disparities x_right - x_left, code 0 at LO and t
 The second eye is synthesised on the GPU and nothing is matched; FILL 0 (the default) extends the background into the disoccluded
 holes, FILL 1 continues it from the mirror pixel where that lies within GATE of the background.  The matching parameters are read and
 ignored; excludes --nv12, --packing, --match, --align, --balance and the frame bits other than --linear-warp.
+--depth-video RANGE DFILTER DGATE LO HI [FILL GATE] (an addition; put it behind the positional arguments): the frames are packed
+2D-plus-depth video frames (stm_stream_input_packed_depth): the image in one half and its depth, a grey picture, in the other.  The
+frame's layout comes from the existing options: BGR files, or with --nv12 ROWS COLS_SBS [--matrix M] a raw NV12 file; --packing P SWAP
+FILTER GAP says where the halves lie (the image is the first one unless SWAP is 1; FILTER expands a squeezed image; without it: side
+by side, full size).  RANGE 0 = grey 0 .. 255, 1 = limited-range video grey 16 .. 235; LO and HI are the disparities x_right - x_left
+of the darkest and the brightest grey; DFILTER 1 expands a squeezed depth picture linearly between neighbours at most DGATE (0 .. 255)
+codes apart and replicates across larger steps, DFILTER 0 always replicates.  FILL and GATE as --depth-input's.  Nothing is converted
+or resampled on the CPU and nothing is matched; excludes --depth-input, --match, --align, --balance, --rectify and the frame bits other
+than --linear-warp.
 --rectify FILE.npy [BORDER] (an addition; put it behind the positional arguments): both eyes of every frame are first remapped on the
 GPU through their rectification records (stm_stream_rectify): FILE.npy is a (2, 18) float32 array, the left eye's record and then the
 right eye's (stm_amd.rectify.record makes one from a camera matrix, distortion coefficients, the rectifying rotation and the new
@@ -309,6 +319,15 @@ def main(argv):
         rectify = video.take_rectify_option(argv)
         if rectify is not None and depth_input is not None:
             raise ValueError("--rectify")
+        depth_video = video.take_depth_video_option(argv)
+        if depth_video is not None:
+            if (depth_input is not None or rectify is not None or match is not None or align is not None or align_auto is not None
+                    or balance is not None or balance_auto is not None or (stages & ~0x800) != 3):
+                raise ValueError("--depth-video")
+            pk = packing if packing is not None else (0, 0, 0, 0)
+            if depth_video[1] and not pk[0] & 1:  # a full-size depth picture is not expanded
+                raise ValueError("--depth-video DFILTER")
+            depth_video = ("bgr" if nv12 is None else "nv12", matrix) + pk + depth_video
     except (ValueError, IndexError):
         print(__doc__)
         return -1
@@ -345,9 +364,9 @@ def main(argv):
     t0 = time.perf_counter()
     n = 0
     for (k, dl, dr, inter) in video.process_sequence(frames, p, out_h, out_w, stages, tuple(temporal) if stages & 0x2000 else None,
-                                                       "bgr" if nv12 is None else "nv12", matrix, lens, depth, depth_auto,
+                                                       "bgr" if nv12 is None or depth_video is not None else "nv12", matrix, lens, depth, depth_auto,
                                                        (lambda k, gc: print("frame %d: gain %.6g conv %.6g" % (k, gc[0], gc[1])))
-                                                       if depth_auto is not None else None, packing,
+                                                       if depth_auto is not None else None, packing if depth_video is None else None,
                                                        layout=None if quilt is None else (1,) + quilt, match=match,
                                                        output=None if nv12_out is None else (1, nv12_out), overlay=overlay,
                                                        antialias=antialias, align=align, align_auto=align_auto,
@@ -365,7 +384,8 @@ def main(argv):
                                                        on_active=(lambda k, r: print("frame %d: active rows %d..%d cols %d..%d changed %d" % ((k,) + r)))
                                                        if active_auto is not None else None,
                                                        maps=None if maps is None else maps[:4],
-                                                       depth_input=None if depth_input is None else depth_input[1], rectify=rectify):
+                                                       depth_input=None if depth_input is None else depth_input[1], rectify=rectify,
+                                                       depth_video=depth_video):
         if yuv is not None:  # the frame is [out height * 3 / 2][out width]: the Y plane, then the interleaved UV plane
             yuv.write(inter.tobytes())
         else:
