@@ -507,14 +507,30 @@ void stm_d_dc_hslo(float **d_cost, float *d_disp, unsigned char *d_img_l, unsign
                    int num_rows, int num_cols, int elem_sz);
 
 /* -------------------------------------------------------- refinement (a15-a17) */
+/* MAP VALUES A STAGE CANNOT PLACE.  dr_dcc, dr_irv, filter_bilateral_1, filter_median, dibr_occl and dibr_dfm take whatever map
+ * the caller has: NaN, +-inf, values far outside the row.  The reference converts with a plain (int), which is undefined there;
+ * these rules define it (host and d_ flavour alike, tests/test_gpu_map_edges.py):
+ *   f2i_sat(v)   every float -> int conversion of a map value: truncate toward zero, saturate at INT_MIN / INT_MAX, NaN -> 0
+ *                (what v_cvt_i32_f32 does, and the reference's hardware conversion);
+ *   no integer sum with a converted value as an operand overflows: a target column is clamp((int64)x +- f2i_sat(v), 0, W - 1).
+ * For maps with every value in (-2^31 + 65536, 2^31 - 65536) no conversion saturates and no sum leaves 32 bits. */
 /* d_dr_dcc.h:17-19 / :13-15  (d_dr_dcc.cu:84-203).  Host flavour zero-fills the outlier maps itself
  * (:166-171); the device flavour expects them zero-filled by the caller (d_io.cu:138-141). */
+/*   c_l = clamp(x + f2i_sat(disp_l[x]), 0, W - 1):  outliers_l[x] = |disp_l[x] - disp_r[c_l]| > 1 (false for a NaN difference),
+ *                                                  hit_r[c_l] = 0;
+ *   c_r = clamp(x - f2i_sat(disp_r[x]), 0, W - 1):  outliers_r[x] = |disp_r[x] - disp_l[c_r]| > 1,  hit_l[c_r] = 0;
+ *   both sums without overflow (x - INT_MIN is column W - 1).  An outlier whose pixel was never hit is class 2. */
 void stm_dr_dcc(unsigned char *outliers_l, unsigned char *outliers_r, float *disp_l, float *disp_r,
                 int num_rows, int num_cols);
 void stm_d_dr_dcc(unsigned char *d_outliers_l, unsigned char *d_outliers_r, float *d_disp_l, float *d_disp_r,
                   int num_rows, int num_cols);
 /* d_dr_irv.h:15-19 / :8-13  (d_dr_irv.cu:222-364).  Host flavour votes once and applies `iterations`
  * times (:344-353); device flavour repeats vote+apply (:259-265). */
+/*   a reliable pixel votes in bin b = f2i_sat(d) + zero_disp when 0 <= b < max(num_disp, 65), taken without overflow; any other
+ *     b counts towards the region's size S only;
+ *   where no pixel of the region has a bin the winner is f2i_sat(own), the outlier's own value;
+ *   the accept ratio's numerator is (float)(winner + zero_disp), the sum in 64 bits (f2i_sat(own) may be INT_MAX), unless
+ *     stm_set_irv_paper_ratio(1) makes it the winning bin's count;  an accepted pixel takes (float)winner. */
 void stm_dr_irv(float *disp, unsigned char *outliers, unsigned char **cross, int thresh_s, float thresh_h,
                 int num_rows, int num_cols, int num_disp, int zero_disp, int usd, int iterations);
 void stm_d_dr_irv(float *d_disp, unsigned char *d_outliers, unsigned char **d_cross, int thresh_s, float thresh_h,
@@ -534,6 +550,8 @@ void stm_d_dr_irv(float *d_disp, unsigned char *d_outliers, unsigned char **d_cr
 void stm_dr_interp(float *disp, unsigned char *outliers, unsigned char *img, int num_rows, int num_cols, int elem_sz);
 void stm_d_dr_interp(float *d_disp, unsigned char *d_outliers, unsigned char *d_img, int num_rows, int num_cols, int elem_sz);
 /* d_filter_bilateral.h:17-20 / :13-15  (d_filter_bilateral.cu:517-630) */
+/*   colour-table index ci = min(f2i_sat(fabsf(va - vs)), num_disp - 1): a NaN difference takes entry 0, an infinite one or one of
+ *   2^31 and more entry num_disp - 1.  w = gs * ck[ci]; norm += w; t = vs * w; res += t: one f32 operation each, taps row-major. */
 void stm_filter_bilateral_1(float *img, int radius, float sigma_color, float sigma_spatial,
                             int num_rows, int num_cols, int num_disp);
 void stm_d_filter_bilateral_1(float *d_img, int radius, float sigma_color, float sigma_spatial,
@@ -546,11 +564,14 @@ void stm_filter_bleed_1(unsigned char *img, int radius, int num_rows, int num_co
 void stm_d_filter_bleed_1(unsigned char *d_img, int radius, int num_rows, int num_cols);
 /* d_filter.h:11-16  (d_filter.cu:7-103): 3x3 "median" on int-truncated values; unused by the reference's
  * drivers (image_io.cpp:239-240 are commented out) but part of its stage API */
+/*   the selection sort compares f2i_sat of the nine samples and stores the converted values back with every swap */
 void stm_filter_median(float *img, int num_rows, int num_cols);
 void stm_d_filter_median(float *d_img, int num_rows, int num_cols);
 
 /* --------------------------------------------------------------- DIBR (a18-a23) */
 /* d_dibr_occl.h:27-33  (d_dibr_occl.cu:130-218) */
+/*   occl_r[clamp(x + f2i_sat(disp_l[x] * 1.0f), 0, W - 1)] = 1;  occl_l[clamp(x + f2i_sat(disp_r[x] * -1.0f), 0, W - 1)] = 1;
+ *   both sums without overflow */
 void stm_dibr_occl(unsigned char *occl_l, unsigned char *occl_r, float *disp_l, float *disp_r,
                    int num_rows, int num_cols);
 void stm_d_dibr_occl(unsigned char *d_occl_l, unsigned char *d_occl_r, float *d_disp_l, float *d_disp_r,
@@ -595,6 +616,8 @@ void stm_d_dibr_dbm_lin(unsigned char *d_img_out, unsigned char *d_img_in_l, uns
                         float *d_mask_l, float *d_mask_r, float shift, int num_rows, int num_cols, int elem_sz);
 /* d_dibr_fwarp.h:12-20  (d_dibr_fwarp.cu:27-193): racy in the reference; deterministic here
  * (largest source x wins), parity unpinned */
+/*   source x lands on column clamp(x + f2i_sat(disp_l[x] * shift), 0, W - 1), the sum without overflow; the f32 product may be
+ *   +-inf (saturates) or NaN (inf * 0: column x) */
 void stm_dibr_dfm(unsigned char *img_out, unsigned char *img_in_l, unsigned char *img_in_r,
                   float *disp_l, float *disp_r, float shift, int num_rows, int num_cols, int elem_sz);
 void stm_d_dibr_dfm(unsigned char *d_img_out, unsigned char *d_img_in_l, unsigned char *d_img_in_r,

@@ -201,6 +201,13 @@ static inline Vol vol_slab(float *base, size_t stride) { Vol v; v.tab = nullptr;
 static inline Vol vol_quads(float *base, size_t stride) { Vol v; v.tab = nullptr; v.base = base; v.plane_stride = stride; v.quad = 1; return v; }
 
 #ifdef __HIPCC__
+// Target column of a caller's map value: clamp(x + sd, 0, W - 1) (map_col) or clamp(x - sd, 0, W - 1) (map_col_sub), the sum
+// taken without overflow.  sd is a float -> int conversion (v_cvt_i32_f32: truncates, saturates at INT_MIN / INT_MAX, NaN -> 0),
+// so x + INT_MAX and x - INT_MIN would wrap in a 32-bit register; a shift bounded to [-W, W] first lands on the same column
+// (x is in [0, W): anything at or beyond +-W leaves the row on that side).  Same column as before for every |sd| < 2^31 - W.
+__device__ __forceinline__ int map_col(int x, int sd, int W) { return min(max(x + min(max(sd, -W), W), 0), W - 1); }
+__device__ __forceinline__ int map_col_sub(int x, int sd, int W) { return min(max(x - min(max(sd, -W), W), 0), W - 1); }
+
 // A "quad" = the four hypotheses d0..d0+3 of one pixel.  PLANES layout: four dword accesses, one per
 // plane (each wave instruction is a contiguous 256-B row segment).  QUADS layout (internal to the frame
 // pipeline, Vol::quad): one 16-byte access.

@@ -67,10 +67,10 @@ __global__ __launch_bounds__(256) void stm_k_occl(u8 *__restrict__ occl_l, u8 *_
     int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= W) return;
     size_t row = (size_t)y * W;
-    int sd = (int)(disp_l[row + x] * 1.0f);
-    occl_r[row + min(max(x + sd, 0), W - 1)] = 1;
+    int sd = (int)(disp_l[row + x] * 1.0f); // a caller's map: the conversion saturates, the sum must not wrap (map_col)
+    occl_r[row + map_col(x, sd, W)] = 1;
     sd = (int)(disp_r[row + x] * -1.0f);
-    occl_l[row + min(max(x + sd, 0), W - 1)] = 1;
+    occl_l[row + map_col(x, sd, W)] = 1;
 }
 void launch_occl(u8 *occl_l, u8 *occl_r, const float *disp_l, const float *disp_r, int H, int W)
 {
@@ -359,8 +359,8 @@ __global__ __launch_bounds__(256) void stm_k_fwarp_vote(const float *__restrict_
     int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
     if (x >= W) return;
     size_t row = (size_t)y * W;
-    int sd = (int)(disp[row + x] * shift);
-    int sx = min(max(x + sd, 0), W - 1);
+    int sd = (int)(disp[row + x] * shift); // the f32 product may be +-inf or NaN: saturates / 0, and the sum must not wrap
+    int sx = map_col(x, sd, W);
     atomicMax(&keys[row + sx], (unsigned long long)(x + 1));
 }
 __global__ __launch_bounds__(256) void stm_k_fwarp_copy(u8 *__restrict__ out, const u8 *__restrict__ img,

@@ -29,11 +29,11 @@ __global__ __launch_bounds__(256) void stm_k_dcc_mark(u8 *__restrict__ out_l, u8
     size_t row = (size_t)y * W;
     const float thresh = 1.0f; // d_dr_dcc.cu:117
     float dl = disp_l[row + x];
-    int c = min(max(x + (int)dl, 0), W - 1);
+    int c = map_col(x, (int)dl, W); // a caller's map: the conversion saturates, the sum must not wrap
     if (fabsf(dl - disp_r[row + c]) > thresh) out_l[row + x] = 1;
     hit_r[row + c] = 0; // dr_ddc_kernel: same coordinate (d_dr_dcc.cu:45-48)
     float dr = disp_r[row + x];
-    c = min(max(x - (int)dr, 0), W - 1);
+    c = map_col_sub(x, (int)dr, W);
     if (fabsf(dr - disp_l[row + c]) > thresh) out_r[row + x] = 1;
     hit_l[row + c] = 0;
 }
@@ -140,9 +140,16 @@ constexpr uint32_t IV_NOVOTE = 0xFFFFu;
 __device__ __forceinline__ uint16_t irv_code(u8 outl, float disp, int zd, int nb)
 {
     if (outl != 0) return (uint16_t)IV_NOVOTE;
-    const int b = (int)disp + zd;
+    // the conversion saturates (a caller's map may hold anything), so the sum saturates too: where (int)disp + zd leaves 32 bits
+    // it stays at INT_MAX / INT_MIN, outside [0, nb) like the exact sum; everywhere else it is the exact sum
+    const int b = __builtin_elementwise_add_sat((int)disp, zd);
     return (b >= 0 && b < nb) ? (uint16_t)(b + 1) : (uint16_t)0;
 }
+// f2i_sat(own) + zd as the float the accept ratio divides: the numerator where nothing in the region has a bin, and with nb - 1
+// the bound of every numerator (see stm_k_irv_rowcount).  64 bits: own = INT_MAX (a map value of 2^31 or more) plus zd leaves 32.
+__device__ __forceinline__ float irv_own_num(int own_i, int zd) { return (float)((long long)own_i + zd); }
+// (float)max(nb - 1, f2i_sat(own) + zd): int -> float is monotone, so the maximum may be taken on the floats
+__device__ __forceinline__ float irv_nmax(int nb, int own_i, int zd) { return fmaxf((float)(nb - 1), irv_own_num(own_i, zd)); }
 
 // counters + dirty bytes of a frame, cleared by a kernel rather than hipMemsetAsync.  Round 2 saw stm_k_irv_vote fault
 // (gpurun_out/r02i/gdb.txt: SIGSEGV in stm_k_irv_vote) only in test_frame_stream_graph_replay_survives_other_calls, i.e. only
@@ -401,8 +408,8 @@ __global__ __launch_bounds__(IC_T) void stm_k_irv_compact(IrvArgs a, uint32_t HW
                 cu = min(cu, gy);
                 cd = min(cd, H - 1 - gy);
                 const int s0 = (int)(vp[(size_t)(gy + cd + 1) * W + gx] - vp[(size_t)(gy - cu) * W + gx]);
-                const int nmax = max(nb - 1, (int)disp[q] + zd);
-                if (s0 > 0 && !((float)nmax / (float)s0 > thresh_h)) w &= ~(0xffu << (8 * j));
+                const float nmax = irv_nmax(nb, (int)disp[q], zd);
+                if (s0 > 0 && !(nmax / (float)s0 > thresh_h)) w &= ~(0xffu << (8 * j));
                 else if (s0 <= thresh_s) later |= 1u << j;
             }
     }
@@ -637,7 +644,7 @@ __global__ __launch_bounds__(64 * IV_WAVES) void stm_k_irv_vote(IrvArgs a, int i
         int max_d = (int)own; // default: own disparity (d_dr_irv.cu:182)
         if (key != 0) max_d = (0xFFFF - (int)(key & 0xFFFF)) - zd;
         // apply (d_dr_irv.cu:32-41): the ratio uses the winning BIN INDEX, not its count (:36, SURVEY A-Q17 iv)
-        const float num = paper_ratio ? (float)(key >> 16) : (float)(max_d + zd);
+        const float num = paper_ratio ? (float)(key >> 16) : irv_own_num(max_d, zd); // max_d + zd: the bin, or f2i_sat(own) + zd beyond 32 bits
         if (total > thresh_s && num / (float)total > thresh_h) {
             const uint16_t nc = irv_code(0, (float)max_d, zd, nb);
             if (lane == 0) {
@@ -647,7 +654,7 @@ __global__ __launch_bounds__(64 * IV_WAVES) void stm_k_irv_vote(IrvArgs a, int i
                 dirty_out[(gy >> tile_sh) * tiles_x + (gx >> tile_sh)] = 1; // same value from every writer
                 list[i] = (uint32_t)p | IV_ACCEPTED;
             }
-        } else if (!paper_ratio && total > 0 && !((float)max(nb - 1, (int)own + zd) / (float)total > thresh_h)) {
+        } else if (!paper_ratio && total > 0 && !(irv_nmax(nb, (int)own, zd) / (float)total > thresh_h)) {
             // S only grows and the numerator never exceeds this bound (see stm_k_irv_rowcount): rejected now = rejected for good
             if (lane == 0) list[i] = IV_DEAD;
         }
@@ -751,8 +758,8 @@ __global__ __launch_bounds__(IC_T) void stm_k_irv_compact_cm(IrvArgs a, uint32_t
                 if (TILE) cd = min(cd, usd); // arms of the frame's own stm_k_cross_arms never exceed usd: this only keeps the read inside pf
                 const int s0 = TILE ? (int)(ic_pf[(gy + cd + 1 - yb) * 64 + c4 + j] - ic_pf[(gy - cu - yb) * 64 + c4 + j])
                                     : (int)(vp[(size_t)(gy + cd + 1) * W + gx] - vp[(size_t)(gy - cu) * W + gx]);
-                const int nmax = max(nb - 1, (int)disp[q] + zd);
-                if (s0 > 0 && !((float)nmax / (float)s0 > thresh_h)) w &= ~(0xffu << (8 * j));
+                const float nmax = irv_nmax(nb, (int)disp[q], zd);
+                if (s0 > 0 && !(nmax / (float)s0 > thresh_h)) w &= ~(0xffu << (8 * j));
                 else if (s0 <= thresh_s) later |= 1u << j;
             }
     }
@@ -985,7 +992,7 @@ __global__ __launch_bounds__(64 * IV_WAVES) __attribute__((amdgpu_waves_per_eu(7
             int max_d = (int)own; // default: own disparity (d_dr_irv.cu:182)
             if (key != 0) max_d = (0xFFFF - (int)(key & 0xFFFF)) - zd;
             // apply (d_dr_irv.cu:32-41): the ratio uses the winning BIN INDEX, not its count (:36, SURVEY A-Q17 iv)
-            const float num = paper_ratio ? (float)(key >> 16) : (float)(max_d + zd);
+            const float num = paper_ratio ? (float)(key >> 16) : irv_own_num(max_d, zd); // max_d + zd: the bin, or f2i_sat(own) + zd beyond 32 bits
             if (total > thresh_s && num / (float)total > thresh_h) {
                 const uint16_t nc = irv_code(0, (float)max_d, zd, nb);
                 if (lane == 0) {
@@ -995,7 +1002,7 @@ __global__ __launch_bounds__(64 * IV_WAVES) __attribute__((amdgpu_waves_per_eu(7
                     dirty_out[(gy >> tile_sh) * tiles_x + (gx >> tile_sh)] = 1; // same value from every writer
                     list[i] = (entry & ~IV_LATER) | IV_ACCEPTED;
                 }
-            } else if (!paper_ratio && total > 0 && !((float)max(nb - 1, (int)own + zd) / (float)total > thresh_h)) {
+            } else if (!paper_ratio && total > 0 && !(irv_nmax(nb, (int)own, zd) / (float)total > thresh_h)) {
                 // S only grows and the numerator never exceeds this bound (see stm_k_irv_rowcount): rejected now = rejected for good
                 if (lane == 0) list[i] = IV_DEAD;
             }

@@ -10,8 +10,11 @@ these vectors on any machine.
 It also measures max |reference - oracle| and the number of differing elements per case and output and writes them next to the
 fixtures as ref_parity_measured.json (the source of profiles/ref_parity.json and of ref_cases.MEASURED_MAX).
 
-Run on a machine with an MI355X, from the repo root:  python tests/golden/make_golden_ref.py [--dir OUT_DIR]
+Run on a machine with an MI355X, from the repo root:  python tests/golden/make_golden_ref.py [--dir OUT_DIR] [--new]
 It stops at the first child that ends abnormally and starts nothing after it.
+
+--new records only the cases of ref_cases.CASES that tests/golden/ has no vector for yet, into files of their own with the next
+part numbers; ref_parity_measured.json then holds their measurements only.  The recorded files stay as they are, byte for byte.
 """
 import glob
 import json
@@ -37,8 +40,17 @@ def main(argv):
     os.makedirs(out_dir, exist_ok=True)
     assert pyref.available(), "oracle/_ref/libstm_ref_hip.so is missing"
     recorded, measured = {}, {}
+    only_new = "--new" in argv
+    golden = os.path.join(ROOT, "tests", "golden")
+    cases = rc.CASES + rc.GPU_ONLY_CASES
+    if only_new:
+        have = set()
+        for f in glob.glob(os.path.join(golden, "ref_gfx950_*.npz")):
+            have |= {k.split("/", 1)[0] for k in np.load(f).files}
+        cases = [c for c in rc.CASES if c[0] not in have]
+        print("--new: %s" % [c[0] for c in cases], flush=True)
     with tempfile.TemporaryDirectory() as tmp:
-        for name, stage, params, build in rc.CASES + rc.GPU_ONLY_CASES:
+        for name, stage, params, build in cases:
             arrays = build(orc, params)
             status, ref, tail = rc.reference_child(tmp, stage, params, arrays, tag=name)
             if status != 0:
@@ -57,9 +69,13 @@ def main(argv):
             if name in rc.CASE_IDS:  # the large GPU-only cases are measured, not recorded
                 for k, v in rc.views_of(name, ref).items():
                     recorded[name + "/" + k] = v
-    for f in glob.glob(os.path.join(out_dir, "ref_gfx950_*.npz")):
-        os.remove(f)
-    part, group, size = 0, {}, 0
+    if only_new:
+        part = len(glob.glob(os.path.join(golden, "ref_gfx950_*.npz")))  # the parts are numbered from 0 without gaps
+    else:
+        for f in glob.glob(os.path.join(out_dir, "ref_gfx950_*.npz")):
+            os.remove(f)
+        part = 0
+    first, group, size = part, {}, 0
 
     def flush():
         nonlocal part, group, size
@@ -76,7 +92,7 @@ def main(argv):
     flush()
     with open(os.path.join(out_dir, "ref_parity_measured.json"), "w") as fh:
         json.dump(measured, fh, indent=1, sort_keys=True)
-    print("recorded %d arrays in %d files" % (len(recorded), part))
+    print("recorded %d arrays in %d files" % (len(recorded), part - first))
     return 0
 
 

@@ -129,6 +129,21 @@ def _b_disp(kind, H, W, D=16, zd=8):
             dr = (rs.randint(-7, 7, size=(H, W)) + rs.random_sample((H, W)) * 0.9).astype(np.float32)
             dl[::5, ::3] = np.round(dl[::5, ::3])
             return {"disp_l": dl, "disp_r": dr}
+        if kind == "edges":
+            # the fractional maps with NaN and values far beyond the row planted in both: every one with |v| < 2^31 - W, so that
+            # x + (int)v and x - (int)v overflow in nobody's 32 bits, the reference's included (it clamps the column after the
+            # sum, d_dr_dcc.cu:45-51, :69-76, d_dibr_occl.cu:124-125).  Pins "NaN -> 0, truncate toward zero" to its binary.
+            a = _b_disp("frac", H, W)(orc, p)
+            vals = np.array([np.nan, 2147483520.0, -2147483520.0, 1e9, -1e9, W, -W, W - 1, -(W - 1), W + 0.5, -(W + 0.5), 0.999,
+                             -0.999, -0.0, 1e-40, -1e-40], np.float32)
+            assert all(abs(float(v)) < 2 ** 31 - W for v in vals[1:])
+            rs = np.random.RandomState(3 * H + W)
+            for m in (a["disp_l"], a["disp_r"]):
+                cols = [0, 1, W // 2, W - 2, W - 1] + rs.randint(2, W - 2, size=3 * len(vals)).tolist()
+                for j, c in enumerate(cols):
+                    m[(5 * j + 1) % H, c] = vals[j % len(vals)]
+                m[H - 1, :len(vals)] = vals          # and side by side, so that neighbours' targets collide
+            return a
         _, _, dl, dr = _disp_pair(orc, kind, H, W, D, zd)
         return {"disp_l": dl, "disp_r": dr}
     return build
@@ -232,6 +247,7 @@ CASES = [
     # left-right check classes
     ("dcc_bud_160x64", "dr_dcc", {}, _b_disp("bud", 64, 160)),
     ("dcc_frac_96x32", "dr_dcc", {}, _b_disp("frac", 32, 96)),
+    ("dcc_edges_96x32", "dr_dcc", {}, _b_disp("edges", 32, 96)),   # NaN and |v| up to 2147483520 in both maps
     # bilateral: H % 30 == 0, W % 32 == 0 (A-L6); value range below D (A-Q18)
     ("bil_bud_160x60_D16", "filter_bilateral_1", {"radius": 7, "sigma_color": 5.0, "sigma_spatial": 10.0, "D": 16}, _b_bilateral("bud", 60, 160)),
     ("bil_steps_64x90_D32", "filter_bilateral_1", {"radius": 7, "sigma_color": 5.0, "sigma_spatial": 10.0, "D": 32}, _b_bilateral("steps", 90, 64)),
@@ -244,6 +260,7 @@ CASES = [
     # hit maps and mask
     ("occl_bud_160x64", "dibr_occl", {}, _b_disp("bud", 64, 160)),
     ("occl_frac_96x32", "dibr_occl", {}, _b_disp("frac", 32, 96)),
+    ("occl_edges_96x32", "dibr_occl", {}, _b_disp("edges", 32, 96)),
     ("mask_160x32", "dibr_occl_to_mask", {}, _b_occl_mask(32, 160)),
     ("mask_96x64", "dibr_occl_to_mask", {}, _b_occl_mask(64, 96)),
     # backward warp + invert + gaussian-max + merge (host flavour: gaussian(7, 10)), two shifts, integer and fractional maps

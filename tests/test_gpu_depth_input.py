@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_depth_input_ref import COUNTS, PLANE_DTYPE, decode_ref, eye_ref, scene_image, scene_plane
+from test_depth_input_ref import COUNTS, PLANE_DTYPE, decode_ref, eye_ref, scene_disp, scene_image, scene_plane
 from test_depth_ref import depth_fit_ref
 from test_lens_ref import LINEAR_WARP, chain_views, render_chain, render_lens_ref
 from test_overlay_ref import ANGLE, PANEL, overlay_ref, random_overlay, subpixel_shift_ref
@@ -311,6 +311,66 @@ def test_round_trip_through_the_planes_of_stream_maps(gpu_ready):
         assert np.array_equal(g[0], dl), k
         assert np.array_equal(plane_ref(g[0], "u16", lo, hi), pl), k
         assert np.array_equal(g[1], eye_ref(img, dl, 1, GATE)[1]), k
+
+
+# ----------------------------------------------------------------------------- 4b. disparities far beyond the row
+FAR = (-4096.0, 4096.0)
+
+
+@functools.lru_cache(maxsize=None)
+def far_frames(shape):
+    """the scene with +-4096 and +-W planted at columns 0, 1, W / 2, W - 2 and W - 1, the signs and rows moving with the frame"""
+    H, W = SHAPES[shape]
+    img = scene_image(H, W)
+    img.setflags(write=False)
+    vals = [4096.0, -4096.0, float(W), float(-W)]
+    frames = []
+    for k in range(N):
+        d = scene_disp(H, W, k)
+        for j, c in enumerate((0, 1, W // 2, W - 2, W - 1)):
+            d[(2 * j + k) % H, c] = vals[(j + k) % 4]
+            d[(2 * j + k + 1) % H, c] = vals[(j + k + 2) % 4]
+        d.setflags(write=False)
+        frames.append((img, d))
+    return tuple(frames)
+
+
+@functools.lru_cache(maxsize=None)
+def far_reference(shape, fill):
+    out = []
+    for img, plane in far_frames(shape):
+        dl = decode_ref(plane, "f32", *FAR)
+        out.append((dl,) + eye_ref(img, dl, fill, GATE))
+    return tuple(out)
+
+
+@pytest.mark.parametrize("shape,fill", [("9x37", 1), ("5x300", 0)])
+def test_disparities_far_beyond_the_row(gpu_ready, orc, shape, fill):
+    """An f32 depth stream with limits (-4096, 4096), the widest a plane's values survive step A: the only public route by which maps
+    with |d| far beyond W reach stm_k_eye, stm_k_hitmask_rows and the fused renderer.  The maps and img_r against eye_ref, the
+    frame against the chain.  Those kernels add before they clamp the column (x + (int)d, x + (int)(d * +-1)), in 32 bits: after
+    step A |d| <= 4096, and x < W, so |x + (int)d| <= W + 4096, which is below 2^31 for every width a frame can have; nothing
+    saturates and no sum wraps.  (The per-stage calls take any map: tests/test_gpu_map_edges.py.)"""
+    H, W = SHAPES[shape]
+    frames, ref = far_frames(shape), far_reference(shape, fill)
+    x = np.arange(W)[None, :]
+    for r in ref:  # conditions on the inputs: pixels land beyond both ends of the row, from both maps
+        assert r[4]["clamped_left"] > 0 and r[4]["clamped_right"] > 0, r[4]
+        assert (r[0] == 4096).any() and (r[0] == -4096).any() and (r[0] == W).any() and (r[0] == -W).any()
+        for sd in (r[0].astype(np.int64), -r[2].astype(np.int64)):  # the hit maps' shifts: disp_l and -disp_r
+            assert ((x + sd) < 0).any() and ((x + sd) > W - 1).any()
+    order = 0 if fill == 0 else 2
+    got = run_depth(shape, "f32", fill, frames=frames, limits=FAR, params=_params(2), out_rows=H, out_cols=2 * W,
+                    layout=(1, 2, 1, order, 0))
+    check_maps(got, ref)
+    for k, (g, r, (img, _)) in enumerate(zip(got, ref, frames)):
+        want = quilt_ref([r[1], img], 2, 1, order, 0, H, 2 * W)
+        assert np.array_equal(g[2], want), (k, "img_r", int((g[2] != want).sum()))
+    got = run_depth(shape, "f32", fill, frames=frames, limits=FAR, stages=3)
+    check_maps(got, ref)
+    for k in (0, 2, N - 1):  # eager, capture, replay
+        want = orc.mux_multiview(chain_views(orc, chain_of(orc, frames[k][0], ref[k]), 8, False), ANGLE, H, W)
+        assert np.array_equal(got[k][2], want), (k, int((got[k][2] != want).sum()))
 
 
 # ----------------------------------------------------------------------------- 5. the refusals, in both directions
